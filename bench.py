@@ -22,6 +22,12 @@ and its one-time Gram reduction are resident in HBM before the timed region; the
 separately.  --scaling weak (default): every rank evaluates its own batch_size samples per step (global batch =
 N x batch_size).  --scaling strong: BASELINE config 4's semantics, the global batch of batch_size samples is dealt
 over the ranks (batch_size / N samples each).  The only data-path collective is the all-reduce of the moments.
+
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, and the configuration).  --full adds everything
+else the benchmark measures: the event pass behind `kernels` / `roofline`, the sustained region, the strong-scaling
+region and probe, the time-to-tolerance legs, full_run, the correlated leg and the CPU baseline.  --dump-outputs DIR
+writes the statistics the timed steps produced as DIR/*.npy; the inputs are seeded, so two builds compare file by file.
 """
 from __future__ import annotations
 
@@ -87,6 +93,15 @@ def parse():
                          "shape -- the harder, secondary workload of SURVEY.md 8(d)")
     ap.add_argument("--no-correlated-leg", action="store_true",
                     help="skip the time-to-tolerance run on the reference's correlated data (one GPU, default data only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the Gram kernels' roofline, the sustained region, the event pass "
+                         "(kernels / roofline), the full-batch pass, the strong-scaling region and probe, the "
+                         "time-to-tolerance legs, full_run, the correlated leg and the CPU baseline (the --no-* switches "
+                         "above drop single parts of it).  Off: set up, warm up, time the K steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64): the running "
+                         "statistics a caller of the step receives -- attribution (mean lift vector), covariance (a fixed, "
+                         "seeded sample of its rows beyond 2048 features) and samples")
     return ap.parse_args()
 
 
@@ -261,6 +276,32 @@ def host_threads():
         return os.cpu_count() or 1
 
 
+def blas_threads_cap():
+    """The thread count the host BLAS pools started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else the core
+    count): OpenBLAS builds crash when threadpool_limits raises a pool above that, so the CPU baseline stays at or
+    below it."""
+    from threadpoolctl import threadpool_info
+    counts = [int(i["num_threads"]) for i in threadpool_info() if i.get("user_api") == "blas"]
+    return max(1, min(counts)) if counts else host_threads()
+
+
+def dump_outputs(directory, n_seen, mean, cov):
+    """What the timed path computed, as float64 .npy files (<= 64 MB together): the mean lift vector, the covariance of
+    the lift vectors (every row up to p = 2048, else a fixed sample of its rows, default_rng(0), whose indices go to
+    covariance_rows.npy) and the number of samples behind them."""
+    os.makedirs(directory, exist_ok=True)
+    p = len(mean)
+    np.save(os.path.join(directory, "attribution.npy"), np.asarray(mean, dtype=np.float64))
+    np.save(os.path.join(directory, "samples.npy"), np.array([n_seen], dtype=np.float64))
+    if p <= 2048:
+        np.save(os.path.join(directory, "covariance.npy"), np.asarray(cov, dtype=np.float64))
+    else:
+        k = (32 << 20) // (8 * p)
+        rows = np.sort(np.random.default_rng(0).choice(p, size=k, replace=False))
+        np.save(os.path.join(directory, "covariance.npy"), np.asarray(cov[rows], dtype=np.float64))
+        np.save(os.path.join(directory, "covariance_rows.npy"), rows.astype(np.float64))
+
+
 def cpu_baseline(host, G, g, H, h, yy, p, reg, n_stop, n_checks, cov_at_stop, seconds=20.0):
     """The oracle (NumPy/SciPy restatement of the reference's algorithm, kind "port") on this host's cores:
     per-ordering rate on a bounded sample (QR + triangular solve + GEMM per ordering, ls_spa/ls_spa.py:256-287), the
@@ -271,12 +312,13 @@ def cpu_baseline(host, G, g, H, h, yy, p, reg, n_stop, n_checks, cov_at_stop, se
     import lsspa_oracle as O
     from threadpoolctl import threadpool_limits
     ncpu = host_threads()
+    usable = min(ncpu, blas_threads_cap())
     R = np.linalg.cholesky(G).T
     F = np.linalg.cholesky(H).T
     q = np.linalg.solve(R.T, g)
     qt = np.linalg.solve(F.T, h)
     rng = np.random.default_rng(0)
-    cand = sorted({t for t in (1, 2, 4, 8, 16, 32) if t <= ncpu})
+    cand = sorted({t for t in (1, 2, 4, 8, 16, 32) if t <= usable})
     best_t, best_rate = 1, 0.0
     O.ordering_lift(R, F, q, qt, yy, rng.permutation(p))     # warm-up
     reps = 2 if p >= 1000 else 50
@@ -302,7 +344,7 @@ def cpu_baseline(host, G, g, H, h, yy, p, reg, n_stop, n_checks, cov_at_stop, se
     # reduction: two Householder QRs with explicit Q, ~4 (N + M) p^2 flop
     Xa, Xe, ya, ye = host
     rows = Xa.shape[0]
-    red_threads = min(ncpu, 32)
+    red_threads = min(usable, 32)
     full_cost = 4.0 * 2 * rows * p * p
     sub = rows if full_cost <= 2e12 else max(4 * p, int(rows * 2e12 / full_cost))
     with threadpool_limits(limits=red_threads):
@@ -316,7 +358,7 @@ def cpu_baseline(host, G, g, H, h, yy, p, reg, n_stop, n_checks, cov_at_stop, se
     # error estimate on the covariance of the stopping check
     est_s = None
     if cov_at_stop is not None and n_stop > 1:
-        with threadpool_limits(limits=min(ncpu, 16)):
+        with threadpool_limits(limits=min(usable, 16)):
             t0 = time.perf_counter()
             O.error_quantiles(np.random.default_rng(1), cov_at_stop * n_stop / (n_stop - 1) / n_stop)
             est_s = time.perf_counter() - t0
@@ -466,7 +508,7 @@ def main():
         eng.set_flags(args.flags)
     peak_tf = FP32_PEAK_TFLOPS if args.dtype == "f32" else FP64_PEAK_TFLOPS
     esz = 4 if args.dtype == "f32" else 8
-    eng.profile(True)
+    eng.profile(args.full)
     t0 = time.perf_counter()
     eng.load_device_data(dXa.data_ptr(), p, dya.data_ptr(), rows, dXe.data_ptr(), p, dye.data_ptr(), rows, p, reg,
                          f32=args.dtype == "f32")
@@ -476,14 +518,15 @@ def main():
     # code object load), which a roofline figure for the kernel should not carry, and two 2 ms launches after seconds
     # of host work do not bring the chip to the clock it holds under load either -- three more calls, the last one is
     # the one reported
-    for _ in range(3):
-        eng.profile_reset()
-        t0 = time.perf_counter()
-        eng.load_device_data(dXa.data_ptr(), p, dya.data_ptr(), rows, dXe.data_ptr(), p, dye.data_ptr(), rows, p, reg,
-                             f32=args.dtype == "f32")
-        eng.synchronize()
-        reduce_warm_ms = 1e3 * (time.perf_counter() - t0)
-    gram_ms, gram_n = eng.profile_read()["gram"]
+    if args.full:
+        for _ in range(3):
+            eng.profile_reset()
+            t0 = time.perf_counter()
+            eng.load_device_data(dXa.data_ptr(), p, dya.data_ptr(), rows, dXe.data_ptr(), p, dye.data_ptr(), rows, p,
+                                 reg, f32=args.dtype == "f32")
+            eng.synchronize()
+            reduce_warm_ms = 1e3 * (time.perf_counter() - t0)
+        gram_ms, gram_n = eng.profile_read()["gram"]
     # theta and R^2 of the full model, as the public call computes them before its loop: from here on every batch of the
     # engine is checked on the device against "the lifts of a sample sum to R^2" (LSSPA_INFO_SUM, include/lsspa.h)
     _, r2_full, _ = eng.full_fit()
@@ -602,14 +645,17 @@ def main():
     # ~10 us bubble per kernel boundary)
     eng.profile(False)
     _, elapsed, elapsed_min = timed_region(step, args.warmup, total_steps)
-    n_seen, mean, _ = eng.stats(want_cov=False)
+    n_seen, mean, cov = eng.stats(want_cov=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, n_seen, mean, cov)
+    del cov
     # sustained rate (orderings/s "sustained over the sampling loop"): the headline region is K steps --
     # 0.13 s at C3 -- and the chip needs ~0.4 s of back-to-back launches to settle on the clock it holds under load.  The
     # same step function over >= SUSTAIN_S seconds (the step count follows from the headline time, identical on every
     # rank), after the headline region so that `value` keeps its definition; the orderings are the region's, cyclically.
     # Rank 0 reads clock and power from the driver's sysfs files about a second into the region (helper thread; None if absent).
     sustained = None
-    if not args.no_sustained:
+    if args.full and not args.no_sustained:
         SUSTAIN_S = 3.0
         n_sus = max(args.steps, int(np.ceil(SUSTAIN_S / max(elapsed / args.steps, 1e-6))))
         n_sus = -(-n_sus // D) * D          # whole look-ahead groups
@@ -650,36 +696,37 @@ def main():
                      "sclk_mhz": smi.get("sclk_mhz"), "power_w": smi.get("power_w"), "sysfs_error": smi.get("error"),
                      "note": "the same step function as the headline region over >= 3 s (max over ranks); clock and power "
                              "as the amdgpu driver's sysfs files (hwmon) report them about one second into the region"}
-    # pass 2: the same K steps again with a HIP-event pair around every launch on the engine's
-    # stream -> per-kernel durations for the roofline figures (one lane: each kernel alone on the GPU)
-    eng.set_lanes(1)
-    eng.profile(True)
-    eng.profile_reset()
-    step.region(args.warmup, total_steps)
-    for k in range(args.warmup, total_steps):
-        step(k)
-    barrier()
-    prof = eng.profile_read()
-    # pass 3 (only when a step goes to the engine in several launch sequences): the same K steps once more as ONE launch
-    # sequence per step on one lane -- the dominant kernel at its full batch size, alone on the GPU.  This is the shape
-    # `rocprofv3 --stats -- python3 bench.py --lanes 1` shows (profiles/r0N_c3_one_lane_kernel_stats.csv): under the
-    # default command the profiler's averages mix the timed region's launches, which overlap across the two streams and
-    # are stretched by it, with this pass's.
-    prof_full = None
-    if SPLIT > 1 and not args.no_full_pass:
+    prof = prof_full = None
+    if args.full:
+        # pass 2: the same K steps again with a HIP-event pair around every launch on the engine's
+        # stream -> per-kernel durations for the roofline figures (one lane: each kernel alone on the GPU)
+        eng.set_lanes(1)
+        eng.profile(True)
         eng.profile_reset()
-        full = Steps(my_perms, B_rank, D, 1)
-        full.region(args.warmup, total_steps)
+        step.region(args.warmup, total_steps)
         for k in range(args.warmup, total_steps):
-            full(k)
+            step(k)
         barrier()
-        prof_full = eng.profile_read()
-    eng.profile(False)
+        prof = eng.profile_read()
+        # pass 3 (only when a step goes to the engine in several launch sequences): the same K steps once more as ONE
+        # launch sequence per step on one lane -- the dominant kernel at its full batch size, alone on the GPU.  This is
+        # the shape `rocprofv3 --stats -- python3 bench.py --full --lanes 1` shows
+        # (profiles/r0N_c3_one_lane_kernel_stats.csv): under the default command the profiler's averages mix the timed
+        # region's launches, which overlap across the two streams and are stretched by it, with this pass's.
+        if SPLIT > 1 and not args.no_full_pass:
+            eng.profile_reset()
+            full = Steps(my_perms, B_rank, D, 1)
+            full.region(args.warmup, total_steps)
+            for k in range(args.warmup, total_steps):
+                full(k)
+            barrier()
+            prof_full = eng.profile_read()
+        eng.profile(False)
 
     # several ranks, weak line: the same K steps once more in BASELINE config 4's semantics -- the global batch of
     # batch_size samples dealt over the ranks (batch_size / N each), kernels of `lookahead` steps launched together
     strong = None
-    if world > 1 and args.scaling == "weak" and B % world == 0:
+    if args.full and world > 1 and args.scaling == "weak" and B % world == 0:
         b_s = B // world
         d_s = args.lookahead if args.lookahead > 0 else (8 if p <= SMALL_P_MAX else max(1, min(8, 64 // b_s)))
         src_s = S.ArgsortSource(p, 42, 2 ** 62)
@@ -697,7 +744,7 @@ def main():
 
     # what one of 8 ranks runs per step under strong scaling (C4): batch_size / 8 samples on this GPU
     probe = None
-    if world == 1 and B >= 16 and args.scaling == "weak" and not args.no_probe:
+    if args.full and world == 1 and B >= 16 and args.scaling == "weak" and not args.no_probe:
         eng.set_lanes(args.lanes)
         b8, dd, reps = B // 8, 4, 24
         pool = np.ascontiguousarray(my_perms[:2].reshape(-1, p)[: dd * b8])
@@ -730,53 +777,6 @@ def main():
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
         value = world * n_ord * args.steps / elapsed
-        per_class = {k: {"ms_per_step": v[0] / args.steps, "launches_per_step": v[1] / args.steps,
-                         "avg_launch_ms": (v[0] / v[1]) if v[1] else None}
-                     for k, v in prof.items() if v[1]}
-        mfma_classes = [k for k in ("strip", "chol_panel", "chol_diag", "small_p") if k in per_class]
-        dom = max(mfma_classes, key=lambda k: per_class[k]["ms_per_step"])
-        lpb = per_class[dom]["launches_per_step"]
-        vt = bool(eng.tri) and "strip" not in per_class      # V^T by the panel launches' X tiles (no strip launch)
-        flops = algorithmic_flops(dom, p, n_ord, eng.tri, lpb, vt)
-        ach = flops / (per_class[dom]["avg_launch_ms"] * 1e-3) / 1e12
-        traffic, traffic_src = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc):
-            try:
-                for rec in json.load(open(pmc)).get("runs", []):
-                    if (rec.get("p"), rec.get("batch_size"), rec.get("dtype")) == (p, B_rank, args.dtype):
-                        traffic = rec.get("hbm_bytes_per_launch", {}).get(dom)
-                        # the counters were collected with the launch sizes of the default pipeline: per launch of THIS
-                        # run = per step there / launches per step here
-                        rec_lps = rec.get("launches_per_step", {}).get(dom)
-                        if traffic and rec_lps:
-                            traffic = traffic * rec_lps / lpb
-                        traffic_src = ("profiles/pmc_traffic.json (static): FETCH_SIZE x 2 + WRITE_SIZE from separate "
-                                       "rocprofv3 --pmc passes of bench.py, collected when the profiles were last refreshed "
-                                       "-- NOT measured in this run")
-            except Exception:
-                traffic = None
-        roofline = {"kernel": dom, "bound": "mfma", "achieved": ach, "peak": peak_tf,
-                    "unit": "TFLOP/s", "frac": ach / peak_tf, "traffic": traffic, "traffic_source": traffic_src,
-                    "algorithmic_flops_per_launch": flops, "avg_launch_ms": per_class[dom]["avg_launch_ms"],
-                    "launches_per_step": lpb,
-                    "traffic_gbps": (traffic / (per_class[dom]["avg_launch_ms"] * 1e-3) / 1e9) if traffic else None,
-                    "note": "peak = vendor fp64 (fp32) matrix figure, which the chip does sustain: a register-resident loop of "
-                            "v_mfma_f64_16x16x4 runs at 77.6 TFLOP/s on all 256 CUs for as long as asked "
-                            "(profiles/r04_mfma_cap_probe.log); the isolated k-loop of these kernels sustains ~60 TFLOP/s fp64 "
-                            "fed from HBM and ~67 fed from the caches, the vendor library's GEMM 69-71 at 8192^3 and 59-67 "
-                            "batched at 1024^3 (profiles/r02_kloop_ceiling.log)"}
-        if prof_full is not None and prof_full.get(dom, (0, 0))[1]:
-            ms_f, n_f = prof_full[dom]
-            lpb_f = n_f / args.steps
-            fl_f = algorithmic_flops(dom, p, n_ord, eng.tri, lpb_f, vt)
-            roofline["full_batch_one_lane"] = {
-                "avg_launch_ms": ms_f / n_f, "launches_per_step": lpb_f, "algorithmic_flops_per_launch": fl_f,
-                "achieved": fl_f / (ms_f / n_f * 1e-3) / 1e12, "frac": fl_f / (ms_f / n_f * 1e-3) / 1e12 / peak_tf,
-                "ms_per_step": ms_f / args.steps,
-                "note": "the same kernel with a step's batch as ONE launch sequence (what --lanes 1 runs and what rocprofv3 "
-                        "--stats of `bench.py --lanes 1` averages); the figures above are for the half-batch launches of "
-                        "the default pipeline, each alone on the GPU in the event pass"}
         out = {
             "metric": "orderings_per_sec", "value": value, "unit": "orderings/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
@@ -794,9 +794,7 @@ def main():
                                           if args.data == "gaussian" else
                                           "the reference's gen_data (experiments/ground_truth_medium.py:74-106), seed 42, "
                                           "generated on the host, moved to HBM before timing")},
-            "roofline": roofline,
-            "kernels": per_class,
-            "reduction_ms": reduce_ms, "reduction_ms_warm_call": reduce_warm_ms,
+            "reduction_ms": reduce_ms,
             "host_data_generation_s": gen_s,
             # engine_info: LSSPA_INFO_* bits raised by any launch of this process so far (1: a pivot was not positive,
             # 4: a hand-over inside a panel launch timed out, 8: a sample's lifts did not sum to R^2) -- 0 on the benchmark data
@@ -805,51 +803,100 @@ def main():
             "check": {"samples": int(n_seen), "sum_attribution": float(mean.sum()), "r_squared": float(r2_full),
                       "engine_info": int(eng.info()), "sum_deviation_max": float(eng.sum_deviation())},
             "ms_per_step_min_rank": 1e3 * elapsed_min / args.steps,
-            "sustained": sustained,
             "timing_note": "value/ms_per_step: K steps without events (two lanes: launch sequences overlap across two "
-                           "streams); kernels/roofline: the same K steps repeated on ONE lane with a HIP-event pair around "
-                           "every launch on the engine's stream, i.e. each kernel alone on the GPU",
+                           "streams)",
         }
-        if "gather" in per_class:
-            # 2 p^2 s bytes per ordering; a step's orderings may go in several launch sequences
-            g_bytes = 2.0 * p * p * esz * n_ord / max(per_class["gather"]["launches_per_step"], 1.0)
-            g_ach = g_bytes / (per_class["gather"]["avg_launch_ms"] * 1e-3) / 1e9
-            out["roofline_gather"] = {"bound": "hbm", "achieved": g_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                      "frac": g_ach / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": g_bytes}
-        gram_flops = 2.0 * rows * (p + 1) * (p + 2) / 2   # (N + M)(p + 1)(p + 2) over both sides -> per launch
-        gram_avg = gram_ms / max(gram_n, 1)
-        gram_ach = gram_flops / (gram_avg * 1e-3) / 1e12
-        out["roofline_gram"] = {"bound": "mfma", "achieved": gram_ach, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                "frac": gram_ach / FP64_PEAK_TFLOPS, "algorithmic_flops_per_launch": gram_flops,
-                                "avg_launch_ms": gram_avg, "launches": int(gram_n),
-                                "note": "one launch per side = the Gram contraction kernel plus its fixed-order slab "
-                                        "reduction, fourth call on the resident data; fp64 accumulation in both data types"}
-        if probe is not None:
-            probe["per_ordering_throughput_vs_full_step"] = probe["orderings_per_s"] / value
-            out["strong_scaling_probe"] = probe
-        if "roofline_gather" in out and os.path.exists(pmc):
-            try:
-                for rec in json.load(open(pmc)).get("runs", []):
-                    if (rec.get("p"), rec.get("batch_size"), rec.get("dtype")) == (p, B_rank, args.dtype):
-                        g_tr = rec.get("hbm_bytes_per_launch", {}).get("gather")
-                        g_lps = rec.get("launches_per_step", {}).get("gather")
-                        if g_tr and g_lps:
-                            g_tr = g_tr * g_lps / max(per_class["gather"]["launches_per_step"], 1.0)
-                        if g_tr:
-                            g_ms = per_class["gather"]["avg_launch_ms"]
-                            out["roofline_gather"].update(
-                                traffic=g_tr, physical_gbps=g_tr / (g_ms * 1e-3) / 1e9,
-                                physical_frac=g_tr / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                traffic_source="profiles/pmc_traffic.json (static; FETCH_SIZE x 2 + WRITE_SIZE of the last "
-                                               "profile refresh, not measured in this run)")
-            except Exception:
-                pass
-        if "roofline_gather" in out:
-            out["roofline_gather"]["note"] = (
-                "algorithmic bytes = SURVEY 8d's 2 p^2 s per ordering; by the PMC counters (profiles/*pmc_summary*) the kernel "
-                "moves fewer: the sources stay on chip and a pair shares a row -- at C3 3.58 GB per step against 4.10 "
-                "algorithmic, i.e. the physical rate (physical_frac, where the counters of this shape are on file) is 0.87 of "
-                "the algorithmic one")
+        if args.full:
+            per_class = {k: {"ms_per_step": v[0] / args.steps, "launches_per_step": v[1] / args.steps,
+                             "avg_launch_ms": (v[0] / v[1]) if v[1] else None}
+                         for k, v in prof.items() if v[1]}
+            mfma_classes = [k for k in ("strip", "chol_panel", "chol_diag", "small_p") if k in per_class]
+            dom = max(mfma_classes, key=lambda k: per_class[k]["ms_per_step"])
+            lpb = per_class[dom]["launches_per_step"]
+            vt = bool(eng.tri) and "strip" not in per_class      # V^T by the panel launches' X tiles (no strip launch)
+            flops = algorithmic_flops(dom, p, n_ord, eng.tri, lpb, vt)
+            ach = flops / (per_class[dom]["avg_launch_ms"] * 1e-3) / 1e12
+            traffic, traffic_src = None, None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc):
+                try:
+                    for rec in json.load(open(pmc)).get("runs", []):
+                        if (rec.get("p"), rec.get("batch_size"), rec.get("dtype")) == (p, B_rank, args.dtype):
+                            traffic = rec.get("hbm_bytes_per_launch", {}).get(dom)
+                            # the counters were collected with the launch sizes of the default pipeline: per launch of THIS
+                            # run = per step there / launches per step here
+                            rec_lps = rec.get("launches_per_step", {}).get(dom)
+                            if traffic and rec_lps:
+                                traffic = traffic * rec_lps / lpb
+                            traffic_src = ("profiles/pmc_traffic.json (static): FETCH_SIZE x 2 + WRITE_SIZE from separate "
+                                           "rocprofv3 --pmc passes of bench.py, collected when the profiles were last refreshed "
+                                           "-- NOT measured in this run")
+                except Exception:
+                    traffic = None
+            roofline = {"kernel": dom, "bound": "mfma", "achieved": ach, "peak": peak_tf,
+                        "unit": "TFLOP/s", "frac": ach / peak_tf, "traffic": traffic, "traffic_source": traffic_src,
+                        "algorithmic_flops_per_launch": flops, "avg_launch_ms": per_class[dom]["avg_launch_ms"],
+                        "launches_per_step": lpb,
+                        "traffic_gbps": (traffic / (per_class[dom]["avg_launch_ms"] * 1e-3) / 1e9) if traffic else None,
+                        "note": "peak = vendor fp64 (fp32) matrix figure, which the chip does sustain: a register-resident loop of "
+                                "v_mfma_f64_16x16x4 runs at 77.6 TFLOP/s on all 256 CUs for as long as asked "
+                                "(profiles/r04_mfma_cap_probe.log); the isolated k-loop of these kernels sustains ~60 TFLOP/s fp64 "
+                                "fed from HBM and ~67 fed from the caches, the vendor library's GEMM 69-71 at 8192^3 and 59-67 "
+                                "batched at 1024^3 (profiles/r02_kloop_ceiling.log)"}
+            if prof_full is not None and prof_full.get(dom, (0, 0))[1]:
+                ms_f, n_f = prof_full[dom]
+                lpb_f = n_f / args.steps
+                fl_f = algorithmic_flops(dom, p, n_ord, eng.tri, lpb_f, vt)
+                roofline["full_batch_one_lane"] = {
+                    "avg_launch_ms": ms_f / n_f, "launches_per_step": lpb_f, "algorithmic_flops_per_launch": fl_f,
+                    "achieved": fl_f / (ms_f / n_f * 1e-3) / 1e12, "frac": fl_f / (ms_f / n_f * 1e-3) / 1e12 / peak_tf,
+                    "ms_per_step": ms_f / args.steps,
+                    "note": "the same kernel with a step's batch as ONE launch sequence (what --lanes 1 runs and what rocprofv3 "
+                            "--stats of `bench.py --lanes 1` averages); the figures above are for the half-batch launches of "
+                            "the default pipeline, each alone on the GPU in the event pass"}
+            out.update(roofline=roofline, kernels=per_class, reduction_ms_warm_call=reduce_warm_ms, sustained=sustained)
+            out["timing_note"] += ("; kernels/roofline: the same K steps repeated on ONE lane with a HIP-event pair around "
+                                   "every launch on the engine's stream, i.e. each kernel alone on the GPU")
+            if "gather" in per_class:
+                # 2 p^2 s bytes per ordering; a step's orderings may go in several launch sequences
+                g_bytes = 2.0 * p * p * esz * n_ord / max(per_class["gather"]["launches_per_step"], 1.0)
+                g_ach = g_bytes / (per_class["gather"]["avg_launch_ms"] * 1e-3) / 1e9
+                out["roofline_gather"] = {"bound": "hbm", "achieved": g_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                          "frac": g_ach / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": g_bytes}
+            gram_flops = 2.0 * rows * (p + 1) * (p + 2) / 2   # (N + M)(p + 1)(p + 2) over both sides -> per launch
+            gram_avg = gram_ms / max(gram_n, 1)
+            gram_ach = gram_flops / (gram_avg * 1e-3) / 1e12
+            out["roofline_gram"] = {"bound": "mfma", "achieved": gram_ach, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                    "frac": gram_ach / FP64_PEAK_TFLOPS, "algorithmic_flops_per_launch": gram_flops,
+                                    "avg_launch_ms": gram_avg, "launches": int(gram_n),
+                                    "note": "one launch per side = the Gram contraction kernel plus its fixed-order slab "
+                                            "reduction, fourth call on the resident data; fp64 accumulation in both data types"}
+            if probe is not None:
+                probe["per_ordering_throughput_vs_full_step"] = probe["orderings_per_s"] / value
+                out["strong_scaling_probe"] = probe
+            if "roofline_gather" in out and os.path.exists(pmc):
+                try:
+                    for rec in json.load(open(pmc)).get("runs", []):
+                        if (rec.get("p"), rec.get("batch_size"), rec.get("dtype")) == (p, B_rank, args.dtype):
+                            g_tr = rec.get("hbm_bytes_per_launch", {}).get("gather")
+                            g_lps = rec.get("launches_per_step", {}).get("gather")
+                            if g_tr and g_lps:
+                                g_tr = g_tr * g_lps / max(per_class["gather"]["launches_per_step"], 1.0)
+                            if g_tr:
+                                g_ms = per_class["gather"]["avg_launch_ms"]
+                                out["roofline_gather"].update(
+                                    traffic=g_tr, physical_gbps=g_tr / (g_ms * 1e-3) / 1e9,
+                                    physical_frac=g_tr / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                    traffic_source="profiles/pmc_traffic.json (static; FETCH_SIZE x 2 + WRITE_SIZE of the last "
+                                                   "profile refresh, not measured in this run)")
+                except Exception:
+                    pass
+            if "roofline_gather" in out:
+                out["roofline_gather"]["note"] = (
+                    "algorithmic bytes = SURVEY 8d's 2 p^2 s per ordering; by the PMC counters (profiles/*pmc_summary*) the kernel "
+                    "moves fewer: the sources stay on chip and a pair shares a row -- at C3 3.58 GB per step against 4.10 "
+                    "algorithmic, i.e. the physical rate (physical_frac, where the counters of this shape are on file) is 0.87 of "
+                    "the algorithmic one")
         if multi:
             # did RCCL see N ranks: answered by RCCL (ncclCommCount through lsspa_comm_info), not by our bookkeeping
             rccl_world = None
@@ -862,7 +909,7 @@ def main():
                 rccl_world = None
             out["rccl_world"] = rccl_world
             out["torch_world"] = int(dist.get_world_size())
-            if "comm" in per_class:
+            if args.full and "comm" in per_class:
                 out["allreduce_ms_per_step"] = per_class["comm"]["ms_per_step"]
                 out["allreduce_bytes"] = 8 * (1 + p + p * p) if p < 2048 else 8 * (1 + p + p * (p + 1) // 2)
             if strong is not None:
@@ -892,8 +939,8 @@ def main():
     # stalls in a collective must not hang the job: a watchdog ends THIS rank with a non-zero status once the legs
     # have taken longer than LSSPA_BENCH_TTT_LIMIT_S seconds (default 180) -- the launcher (or torch.distributed.run)
     # then ends the others; nothing is re-executed.  LSSPA_BENCH_TTT_MULTI=0 switches the legs off with several ranks.
-    ttt_on = not args.no_ttt and (world == 1 or os.environ.get("LSSPA_BENCH_TTT_MULTI", "1") != "0")
-    if not args.no_ttt and not ttt_on:
+    ttt_on = args.full and not args.no_ttt and (world == 1 or os.environ.get("LSSPA_BENCH_TTT_MULTI", "1") != "0")
+    if args.full and not args.no_ttt and not ttt_on:
         legs["time_to_tolerance"] = {"skipped": "several ranks and LSSPA_BENCH_TTT_MULTI=0"}
     watchdog = None
     if ttt_on and world > 1:
@@ -1099,7 +1146,7 @@ def main():
         if isinstance(out.get("full_run"), dict) and "orderings_per_s" in out["full_run"]:
             out["full_run"]["fraction_of_value"] = out["full_run"]["orderings_per_s"] / out["value"]
 
-    if out is not None and world == 1 and not args.no_cpu_baseline:
+    if args.full and out is not None and world == 1 and not args.no_cpu_baseline:
         G, g, H, h = eng.gram()
         out["cpu_baseline"] = cpu_baseline(host, G, g, H, h, eng.y_norm_sq, p, reg, n_stop, n_checks, cov_at_stop)
         cb = out["cpu_baseline"]

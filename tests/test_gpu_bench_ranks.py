@@ -13,15 +13,16 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--p", "200", "--rows", "3000", "--batch-size", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
-        "--no-sustained", "--no-correlated-leg"]
+ARGS = ["--p", "200", "--rows", "3000", "--batch-size", "16", "--steps", "4", "--warmup", "1", "--full",
+        "--no-cpu-baseline", "--no-sustained", "--no-correlated-leg"]
+PLAIN = ["--p", "200", "--rows", "3000", "--batch-size", "16", "--steps", "3", "--warmup", "1"]
 
 
-def _bench(gpus, extra_env, timeout=900):
+def _bench(gpus, extra_env, timeout=900, args=ARGS):
     env = dict(os.environ, **extra_env)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LSSPA_BENCH_LAUNCHED"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), *ARGS], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), *args], env=env,
                        capture_output=True, text=True, timeout=timeout)
     return r
 
@@ -68,3 +69,34 @@ def test_a_failing_rank_fails_the_job():
     r = _bench(2, {"LSSPA_BENCH_REHEARSE_WORLD": "2", "LSSPA_BENCH_FAIL_RANK": "1"}, timeout=600)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]     # no result line from a broken job
+
+
+def test_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """Without --full the run is the headline alone: K timed steps, the result line, and with --dump-outputs the
+    statistics of those steps -- the same files, bit for bit, from two runs with the same arguments."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r = _bench(1, {}, timeout=600, args=[*PLAIN, "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        got = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(got) == 1
+        lines.append(json.loads(got[0]))
+    d1 = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d1, k
+    assert d1["metric"] == "orderings_per_sec" and d1["higher_is_better"] is True and d1["dtype"] == "f64"
+    assert d1["steps"] == 3 and d1["value"] == pytest.approx(2 * 16 * 3 / (3 * d1["ms_per_step"] * 1e-3))
+    for k in ("kernels", "roofline", "sustained", "time_to_tolerance", "full_run", "cpu_baseline"):
+        assert k not in d1, k
+    assert d1["check"]["samples"] == 16 * (1 + 3)                 # the statistics hold the warm-up steps too
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["attribution.npy", "covariance.npy", "samples.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float64 and x.shape == y.shape
+        np.testing.assert_array_equal(x, y)
+    att = np.load(tmp_path / "a" / "attribution.npy")
+    assert att.shape == (200,) and abs(att.sum() - d1["check"]["sum_attribution"]) < 1e-12
+    assert np.load(tmp_path / "a" / "covariance.npy").shape == (200, 200)
+    assert float(np.load(tmp_path / "a" / "samples.npy")[0]) == 16 * (1 + 3)

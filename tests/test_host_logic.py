@@ -808,6 +808,35 @@ def test_bench_helpers_follow_the_baseline_recipe():
     assert bench.algorithmic_flops("small_p", 100, n_ord, True, 1) == pytest.approx(100 ** 3 * n_ord)
 
 
+def test_bench_dump_outputs_and_blas_cap(tmp_path):
+    """--dump-outputs writes float64 files of at most 64 MB: the whole covariance up to p = 2048, beyond that a fixed
+    (seeded) sample of its rows with their indices; the CPU baseline never asks BLAS for more threads than it has."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    mean, cov = rng.standard_normal(30), rng.standard_normal((30, 30))
+    bench.dump_outputs(str(tmp_path / "small"), 64, mean, cov)
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "attribution.npy"), mean)
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "covariance.npy"), cov)
+    assert np.load(tmp_path / "small" / "samples.npy").tolist() == [64.0]
+    p = 3000
+    big = np.arange(p * p, dtype=np.float64).reshape(p, p)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 8, np.zeros(p), big)
+    files = list((tmp_path / "a").iterdir())
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    assert all(np.load(f).dtype == np.float64 for f in files)
+    rows = np.load(tmp_path / "a" / "covariance_rows.npy")
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "b" / "covariance_rows.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "covariance.npy"), big[rows.astype(np.int64)])
+    from threadpoolctl import threadpool_info
+    cap = bench.blas_threads_cap()
+    assert cap >= 1 and all(cap <= i["num_threads"] for i in threadpool_info() if i.get("user_api") == "blas")
+
+
 def _bench_path():
     import os
     return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")

@@ -4,7 +4,7 @@ MI355X_MICROARCH.md section HBM prescribes) into per-kernel memory-side traffic 
     python tools/pmc_summary.py <fetch counter_collection.csv> <write counter_collection.csv> \
         --label c3 --p 1000 --batch-size 128 --dtype f64
 
-The profiled command must be `bench.py ... --no-probe --no-ttt --no-cpu-baseline` (every launch of a kernel then
+The profiled command must be `bench.py --full ... --no-probe --no-ttt --no-cpu-baseline` (every launch of a kernel then
 belongs to a full-size step).  Units and corrections: both counters are in KiB; on gfx950 FETCH_SIZE reads exactly 1/2
 of the bytes of a wide (16 B/lane) coalesced stream, so it is doubled; WRITE_SIZE is exact for 16-B/lane stores.
 Infinity-Cache hits are counted (the counters sit on the L2's memory side), so this is fabric traffic, an upper bound

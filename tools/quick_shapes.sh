@@ -1,5 +1,5 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-P="--no-probe --no-ttt --no-cpu-baseline --no-sustained --no-full-pass"
+P="--full --no-probe --no-ttt --no-cpu-baseline --no-sustained --no-full-pass"
 python3 bench.py --steps 5 --warmup 2 --p 5000 --rows 200000 --dtype f32 $P > gpurun_out/q_c5.json 2> gpurun_out/q_c5.err
 python3 bench.py --steps 20 --warmup 5 --dtype f32 --reg 0 $P > gpurun_out/q_f32.json 2> gpurun_out/q_f32.err
 python3 bench.py --steps 64 --warmup 8 --p 100 --rows 10000 $P > gpurun_out/q_c2.json 2> gpurun_out/q_c2.err
