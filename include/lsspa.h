@@ -91,6 +91,25 @@ int lsspa_set_reduced(lsspa_ctx* ctx, int32_t p, const double* G, const double* 
                       int32_t tri, const double* H, const double* h, int32_t m, const double* Ft,
                       const double* ytil, double y_norm_sq);
 
+/* Exact Shapley attribution of the loaded problem by enumeration of all 2^p feature subsets (p <= 32) -- the
+ * definition the reference's brute-force table uses (notebooks/shapley_toy.py:100-140):
+ *   phi_j = sum over S not containing j of |S|! (p - 1 - |S|)! / p! (v(S + j) - v(S)),
+ *   v(S) = (2 theta_S^T h_S - theta_S^T H_SS theta_S) / ||y_test||^2,  theta_S = G_SS^-1 g_S,  v({}) = 0,
+ * the R^2 of square_shapley's prefix sets (ls_spa/ls_spa.py:275-285); in rect mode H = Ft Ft^T and h = Ft ytil.
+ * The phi sum to the R^2 of lsspa_full_fit; for p <= 8 they equal the mean over all p! orderings.  fp64 whatever
+ * lsspa_set_precision says.  Works after lsspa_reduce, lsspa_reduce_finish or lsspa_set_reduced; p > 32 or no problem
+ * loaded is LSSPA_ERR_ARG.  info: LSSPA_INFO_NOT_PD if a subset's pivot failed the engine's relative test (16 p eps).
+ * Nothing of the sampling path changes: running statistics, history, flags, lanes, per-batch workspace and the info
+ * word of lsspa_get_info stay as they were.  The work is split into launches of bounded length; the result is
+ * bitwise reproducible (partial sums are added in a fixed order).
+ *   lsspa_subsets_timing      : device milliseconds of the last call's enumeration launches, its longest launch and
+ *                               the number of launches (any pointer may be NULL)
+ *   lsspa_debug_subset_values : test hook -- v[i] = v(masks[i]) (bit j = feature j; masks < 2^p) by the enumeration's
+ *                               own device code; a failed pivot is LSSPA_ERR_STATE */
+int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info);
+int lsspa_subsets_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches);
+int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

@@ -1,0 +1,363 @@
+// Exact Shapley attribution by subset enumeration (p <= 32): v(K) of all 2^p feature subsets, never stored, folded
+// into the Shapley sum as it is computed.  fp64 throughout, whatever the per-ordering precision says.
+//
+// With G, g (training side) and H, h (test side) of the reduced problem, for a subset K
+//   theta_K = G_KK^-1 g_K,   v(K) = (2 theta_K^T h_K - theta_K^T H_KK theta_K) / ||y_test||^2,   v({}) = 0,
+// the out-of-sample R^2 of the prefix set K in square_shapley (the reference's ls_spa/ls_spa.py:275-285), and
+//   phi_j = sum_{S not containing j} w(|S|) (v(S + j) - v(S)),   w(k) = k! (p - 1 - k)! / p!.
+//
+// Decomposition ("Exact attribution by subset enumeration"): the features split into q = min(p, 6) LOW ones
+// (features 0 .. q-1) and p - q HIGH ones.  One wave owns one high subset Hs at a time:
+//   1. it sweeps (Gauss-Jordan in Goodnight's form) the pivots of Hs out of the compacted augmented matrix
+//      [G g; g^T 0] over Hs + low features, which leaves A^-1 [B g] in the Hs rows (A = G_HsHs, B = G_Hs,low) and the
+//      Schur complement S = G_LL - B^T A^-1 B, g~ = g_L - B^T A^-1 g_Hs in the low block;
+//   2. theta over Hs + T is e0 + E theta_T with e0 = [A^-1 g_Hs; 0], E = [-A^-1 B; I]: the test side reduces to the
+//      (q+1) x (q+1) matrix Z = X^T H X and z = X^T h of X = [e0 E], whence f0, r and W of
+//        v(Hs + T) = (f0 + 2 theta_T^T r_T - theta_T^T W_TT theta_T) / ||y||^2,   theta_T = S_TT^-1 g~_T;
+//   3. lane T (one lane per low subset, 2^6 = 64) masks rows and columns of S outside T to the identity and runs the
+//      same fixed 6 x 6 Cholesky, solve and quadratic form as every other lane: no divergence on |T|.
+// The Shapley sum: with a(K) = w(|K| - 1) v(K) (|K| >= 1) and b(K) = w(|K|) v(K) (|K| <= p - 1),
+//   phi_j = sum_{K containing j} (a + b)(K) - sum_K b(K),
+// so a lane keeps sum (a + b) per high feature of the subsets it saw, one sum for its own T and one of b; a unit's
+// partials are reduced once per launch by fixed butterflies and added to its own row of the partial table, which a
+// last kernel sums in fixed order.  No floating-point atomics: the result is bitwise the same from call to call.
+#include "kernels.h"
+
+namespace lsspa {
+namespace {
+
+constexpr int SQ = 6;                          // low features: one lane per low subset, 2^6 lanes = one wave
+constexpr int SP = SUBSETS_MAX_P;              // 32
+constexpr int SNH = SP - SQ;                   // largest number of high features
+constexpr int LDM = SP + 1;                    // row stride of the compacted sweep matrix (n <= p + 1 <= 33)
+constexpr int SENT = (LDM * LDM + 63) / 64;    // sweep entries a lane owns at most (18)
+constexpr int ZC = SQ + 2;                     // row stride of Z: columns 0 .. q of X^T H X, then X^T h
+
+struct SubShared {
+  double H[SP * LDM];      // test Gram, stride LDM
+  double h[SP];
+  double gdiag[SP];        // diagonal of G: the pivot scale
+  double wa[SP + 1], wb[SP + 1];
+  double M[LDM * LDM];     // compacted augmented matrix being swept
+  double X[SP * (SQ + 1)]; // [e0 E] over Hs + low, stride SQ + 1
+  double Y[SP * (SQ + 1)]; // H X
+  double Z[(SQ + 1) * ZC]; // X^T H X | X^T h
+  int idx[SP];             // compacted position -> feature
+};
+
+__device__ inline double wave_sum(double x) {
+  // fixed butterfly, then lane 0's value for everyone: the same order on every call
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return __shfl(x, 0, 64);
+}
+
+// v(Hs + T) of this lane's low subset T = lane (0 for lanes >= 2^q).  Enters and leaves with the workgroup (one wave)
+// in step: every shared array it writes is free when it is called and is read by nobody after it returns.
+__device__ double subset_values(SubShared& sh, const SubsetArgs& a, uint64_t hi, int lane, bool& bad) {
+  const int p = a.p, q = a.q;
+  const int nhs = __popcll(hi);
+  if (lane < p) {
+    if (lane < q)
+      sh.idx[nhs + lane] = lane;
+    else if ((hi >> (lane - q)) & 1ull)
+      sh.idx[__popcll(hi & ((1ull << (lane - q)) - 1ull))] = lane;
+  }
+  const int nk = nhs + q;     // features of Hs + low
+  const int n = nk + 1;       // ... and the right-hand side
+  const int nn = n * n;
+  __syncthreads();
+  int ea[SENT], eb[SENT];
+#pragma unroll
+  for (int r = 0; r < SENT; ++r) {
+    const int e = lane + 64 * r;
+    ea[r] = e / n;
+    eb[r] = e - ea[r] * n;
+    if (e < nn) {
+      const int i = ea[r], j = eb[r];
+      double val = 0.0;
+      if (i < nk && j < nk)
+        val = a.G[(int64_t)sh.idx[i] * a.ldg + sh.idx[j]];
+      else if (i < nk)
+        val = a.g[sh.idx[i]];
+      else if (j < nk)
+        val = a.g[sh.idx[j]];
+      sh.M[i * LDM + j] = val;
+    }
+  }
+  __syncthreads();
+  // sweep the high pivots: new M_kj = M_kj / d, M_ik = -M_ik / d, M_kk = 1 / d, M_ij -= M_ik M_kj / d
+  for (int k = 0; k < nhs; ++k) {
+    const double d = sh.M[k * LDM + k];
+    if (!(d > a.piv_tol * sh.gdiag[sh.idx[k]])) bad = true;
+    const double inv = 1.0 / d;
+    double nv[SENT];
+#pragma unroll
+    for (int r = 0; r < SENT; ++r) {
+      nv[r] = 0.0;
+      if (lane + 64 * r < nn) {
+        const int i = ea[r], j = eb[r];
+        const double mik = sh.M[i * LDM + k], mkj = sh.M[k * LDM + j];
+        if (i == k)
+          nv[r] = (j == k) ? inv : mkj * inv;
+        else if (j == k)
+          nv[r] = -mik * inv;
+        else
+          nv[r] = sh.M[i * LDM + j] - mik * (mkj * inv);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SENT; ++r)
+      if (lane + 64 * r < nn) sh.M[ea[r] * LDM + eb[r]] = nv[r];
+    __syncthreads();
+  }
+  // X = [e0 E] over the nk compacted features (columns 0 .. q)
+  const int nc = q + 1;
+  for (int e = lane; e < nk * nc; e += 64) {
+    const int i = e / nc, c = e - i * nc;
+    double x;
+    if (i < nhs)
+      x = (c == 0) ? sh.M[i * LDM + nk] : -sh.M[i * LDM + nhs + c - 1];
+    else
+      x = (c - 1 == i - nhs) ? 1.0 : 0.0;
+    sh.X[i * (SQ + 1) + c] = x;
+  }
+  __syncthreads();
+  for (int e = lane; e < nk * nc; e += 64) {
+    const int i = e / nc, c = e - i * nc;
+    const double* Hr = sh.H + sh.idx[i] * LDM;
+    double s = 0.0;
+    for (int b = 0; b < nk; ++b) s += Hr[sh.idx[b]] * sh.X[b * (SQ + 1) + c];
+    sh.Y[i * (SQ + 1) + c] = s;
+  }
+  __syncthreads();
+  if (lane < nc * (nc + 1)) {
+    const int c = lane / (nc + 1), c2 = lane - c * (nc + 1);
+    double s = 0.0;
+    if (c2 < nc)
+      for (int i = 0; i < nk; ++i) s += sh.X[i * (SQ + 1) + c] * sh.Y[i * (SQ + 1) + c2];
+    else
+      for (int i = 0; i < nk; ++i) s += sh.X[i * (SQ + 1) + c] * sh.h[sh.idx[i]];
+    sh.Z[c * ZC + (c2 < nc ? c2 : SQ + 1)] = s;
+  }
+  __syncthreads();
+  // lane T: theta_T = S_TT^-1 g~_T with everything outside T masked to the identity
+  double v = 0.0;
+  if (lane < (1 << q)) {
+    bool in[SQ];
+#pragma unroll
+    for (int t = 0; t < SQ; ++t) in[t] = (t < q) && ((lane >> t) & 1);
+    double L[SQ][SQ], y[SQ];
+#pragma unroll
+    for (int t = 0; t < SQ; ++t) {
+      const double mt = sh.M[(nhs + t) * LDM + nk];
+      y[t] = in[t] ? mt : 0.0;
+#pragma unroll
+      for (int s = 0; s <= t; ++s) {
+        const double ms = sh.M[(nhs + t) * LDM + nhs + s];
+        L[t][s] = (in[t] && in[s]) ? ms : (s == t ? 1.0 : 0.0);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SQ; ++j) {
+      double d = L[j][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+      if (in[j] && !(d > a.piv_tol * sh.gdiag[j])) bad = true;
+      const double r = 1.0 / sqrt(d);
+      L[j][j] = d * r;
+#pragma unroll
+      for (int i = j + 1; i < SQ; ++i) {
+        double s = L[i][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+        L[i][j] = s * r;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < SQ; ++i) {
+      double s = y[i];
+#pragma unroll
+      for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+      y[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = SQ - 1; i >= 0; --i) {
+      double s = y[i];
+#pragma unroll
+      for (int k = i + 1; k < SQ; ++k) s -= L[k][i] * y[k];
+      y[i] = s / L[i][i];                 // theta_T (exactly 0 outside T)
+    }
+    double f = 2.0 * sh.Z[SQ + 1] - sh.Z[0];
+#pragma unroll
+    for (int t = 0; t < SQ; ++t) {
+      if (t < q) {
+        double u = 2.0 * (sh.Z[(1 + t) * ZC + SQ + 1] - sh.Z[(1 + t) * ZC]);
+#pragma unroll
+        for (int s = 0; s < SQ; ++s)
+          if (s < q) u -= sh.Z[(1 + t) * ZC + 1 + s] * y[s];
+        f += y[t] * u;
+      }
+    }
+    v = f * a.inv_yy;
+  }
+  return v;
+}
+
+__device__ void load_shared(SubShared& sh, const SubsetArgs& a, int lane) {
+  const int p = a.p;
+  for (int e = lane; e < p * p; e += 64) {
+    const int i = e / p, j = e - i * p;
+    sh.H[i * LDM + j] = a.H[(int64_t)i * a.ldh + j];
+  }
+  if (lane < p) {
+    sh.h[lane] = a.h[lane];
+    sh.gdiag[lane] = a.G[(int64_t)lane * a.ldg + lane];
+  }
+  if (lane <= p) {
+    sh.wa[lane] = a.w[lane];
+    sh.wb[lane] = a.w[SP + 1 + lane];
+  }
+  for (int e = lane; e < (SQ + 1) * ZC; e += 64) sh.Z[e] = 0.0;   // rows / columns beyond q stay 0
+}
+
+__global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t s0, uint64_t s1) {
+  __shared__ SubShared sh;
+  const int lane = threadIdx.x;
+  const int p = a.p, q = a.q, nh = p - q;
+  load_shared(sh, a, lane);
+  double acc[SNH];
+#pragma unroll
+  for (int j = 0; j < SNH; ++j) acc[j] = 0.0;
+  double c_own = 0.0, b_own = 0.0;
+  bool bad = false;
+  const bool live = lane < (1 << q);
+  const int kt = __popc(lane);
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    const double v = subset_values(sh, a, hi, lane, bad);
+    if (live) {
+      const int k = __popcll(hi) + kt;
+      const double c = (sh.wa[k] + sh.wb[k]) * v;
+      c_own += c;
+      b_own += sh.wb[k] * v;
+#pragma unroll
+      for (int j = 0; j < SNH; ++j)
+        if (j < nh && ((hi >> j) & 1ull)) acc[j] += c;
+    }
+    __syncthreads();
+  }
+  double* part = a.part + (int64_t)blockIdx.x * (p + 1);
+#pragma unroll
+  for (int t = 0; t < SQ; ++t) {
+    if (t < q) {
+      const double tot = wave_sum((live && ((lane >> t) & 1)) ? c_own : 0.0);
+      if (lane == 0) part[t] += tot;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < SNH; ++j) {
+    if (j < nh) {
+      const double tot = wave_sum(acc[j]);
+      if (lane == 0) part[q + j] += tot;
+    }
+  }
+  const double tb = wave_sum(b_own);
+  if (lane == 0) part[p] += tb;
+  if (__any(bad) && lane == 0) atomicOr(a.info, 1);
+}
+
+__global__ __launch_bounds__(64) void subsets_reduce_kernel(const double* __restrict__ part, int64_t units, int p1,
+                                                            double* __restrict__ out) {
+  const int j = blockIdx.x, lane = threadIdx.x;
+  double s = 0.0;
+  for (int64_t u = lane; u < units; u += 64) s += part[u * p1 + j];
+  s = wave_sum(s);
+  if (lane == 0) out[j] = s;
+}
+
+__global__ __launch_bounds__(64) void subsets_debug_kernel(SubsetArgs a, const uint64_t* __restrict__ masks,
+                                                           int64_t n, double* __restrict__ vals) {
+  __shared__ SubShared sh;
+  const int lane = threadIdx.x;
+  load_shared(sh, a, lane);
+  bool bad = false;
+  const uint64_t low = (1ull << a.q) - 1ull;
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint64_t m = masks[i];
+    const double v = subset_values(sh, a, m >> a.q, lane, bad);
+    if ((uint64_t)lane == (m & low)) vals[i] = v;
+    __syncthreads();
+  }
+  if (__any(bad) && lane == 0) atomicOr(a.info, 1);
+}
+
+// H = Ft Ft^T [p][p] (stride p) and h = Ft ytil (appended) of the rect-mode test factor: one workgroup per entry, its
+// 256 threads strided over the m columns, then a fixed tree (the same sums on every call; m may be up to 2^20 through
+// lsspa_set_reduced).  Entries (i, j) and (j, i) both form the product of rows min(i, j) and max(i, j) in the same
+// order, so H is exactly symmetric.
+__global__ __launch_bounds__(256) void subsets_test_gram_kernel(const double* __restrict__ Ft, int64_t ldf,
+                                                                const double* __restrict__ ytil, int p, int m,
+                                                                double* __restrict__ Hh) {
+  __shared__ double red[256];
+  const int e = blockIdx.x;                  // grid = p (p + 1): entry (i, j), j == p is h
+  const int i = e / (p + 1), j = e - i * (p + 1);
+  const int a = (j < p && j < i) ? j : i, b = (j < p && j < i) ? i : j;   // (a, b) with a <= b or b == p
+  const double* ra = Ft + (int64_t)a * ldf;
+  const double* rb = (b < p) ? Ft + (int64_t)b * ldf : ytil;
+  double s = 0.0;
+  for (int r = threadIdx.x; r < m; r += 256) s += ra[r] * rb[r];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (j < p)
+      Hh[i * p + j] = red[0];
+    else
+      Hh[p * p + i] = red[0];
+  }
+}
+
+bool args_ok(const SubsetArgs& a) {
+  return a.p >= 1 && a.p <= SP && a.q == (a.p < SQ ? a.p : SQ) && a.G && a.g && a.H && a.h && a.w && a.info &&
+         a.ldg >= a.p && a.ldh >= a.p;
+}
+
+}  // namespace
+
+int subsets_low_features(int p) { return p < SQ ? p : SQ; }
+
+hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st) {
+  if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^(p - q)
+  const int nh = a.p - a.q;
+  if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_enum_kernel, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_reduce(const double* part, int64_t units, int p, double* out, hipStream_t st) {
+  if (!part || !out || units < 1 || p < 1 || p > SP) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_reduce_kernel, dim3(p + 1), dim3(64), 0, st, part, units, p + 1, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st) {
+  if (!args_ok(a) || !masks || !vals || n < 1) return hipErrorInvalidValue;
+  const int64_t grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(subsets_debug_kernel, dim3((unsigned)grid), dim3(64), 0, st, a, masks, n, vals);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_test_gram(const double* Ft, int64_t ldf, const double* ytil, int p, int m, double* Hh,
+                                    hipStream_t st) {
+  if (!Ft || !ytil || !Hh || p < 1 || p > SP || m < 1 || ldf < m) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_test_gram_kernel, dim3(p * (p + 1)), dim3(256), 0, st, Ft, ldf, ytil, p, m, Hh);
+  return hipGetLastError();
+}
+
+}  // namespace lsspa

@@ -261,4 +261,34 @@ hipError_t launch_error_running_draws(const double* D, const double* s, const do
 // unit test hook: D = A(16x4) * B(4x16) on one wave through Tr<T>::mfma / acc_row (fp64 or fp32)
 hipError_t launch_mfma_probe(const double* A, const double* B, double* D, int f32, hipStream_t st);
 
+// Exact attribution by subset enumeration (k_subsets.hip), p <= SUBSETS_MAX_P, fp64.  Features 0 .. q-1 are the low
+// ones (q = subsets_low_features(p)); high subset number hi is the set {q + j : bit j of hi}.  The enumeration runs
+// `units` workgroups; unit u owns high subsets u per .. (u + 1) per - 1 (units * per = 2^(p - q)) and one launch takes
+// steps s0 .. s1 - 1 of every unit, adding to the unit's row of part [units][p + 1]:
+//   part[u][j] += sum over its subsets K containing j of (w(|K| - 1) + w(|K|)) v(K),  part[u][p] += sum w(|K|) v(K)
+// with w = wa, wb below; phi_j = sum_u part[u][j] - sum_u part[u][p] (launch_subsets_reduce, fixed order).
+constexpr int SUBSETS_MAX_P = 32;
+struct SubsetArgs {
+  const double* G;         // [p][ldg] training Gram
+  const double* g;         // [p]
+  const double* H;         // [p][ldh] test Gram
+  const double* h;         // [p]
+  int64_t ldg, ldh;
+  const double* w;         // [2][SUBSETS_MAX_P + 1]: wa[k] = w(k - 1) (0 for k = 0), wb[k] = w(k) (0 for k = p)
+  int p, q;
+  double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
+  double inv_yy;           // 1 / ||y_test||^2
+  uint64_t per;            // high subsets per unit
+  double* part;            // [units][p + 1]
+  int32_t* info;           // bit 1: a pivot failed
+};
+int subsets_low_features(int p);
+hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
+hipError_t launch_subsets_reduce(const double* part, int64_t units, int p, double* out, hipStream_t st);
+// vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
+hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
+// Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used
+hipError_t launch_subsets_test_gram(const double* Ft, int64_t ldf, const double* ytil, int p, int m, double* Hh,
+                                    hipStream_t st);
+
 }  // namespace lsspa

@@ -140,6 +140,12 @@ struct lsspa_ctx {
   Comm* comm = nullptr;
   DevBuf<double> pack, xfer;     // packed moments; staging of host-side all-gathers
   DevBuf<double> theta_d;        // lsspa_full_fit's back-substitution
+  // exact attribution by subset enumeration (lsspa_subsets_shapley): its own buffers, nothing of the sampling path's
+  DevBuf<double> sub_Hh, sub_w, sub_part, sub_out, sub_vals;
+  DevBuf<uint64_t> sub_masks;
+  DevBuf<int32_t> sub_info;
+  double sub_kernel_ms = 0.0, sub_max_launch_ms = 0.0;
+  int64_t sub_launches = 0;
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -1088,6 +1094,8 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   dev_free(ctx->mean_alt); dev_free(ctx->state_alt);
   dev_free(ctx->Cred);
   dev_free(ctx->Gf); dev_free(ctx->Hf);
+  dev_free(ctx->sub_Hh); dev_free(ctx->sub_w); dev_free(ctx->sub_part); dev_free(ctx->sub_out);
+  dev_free(ctx->sub_vals); dev_free(ctx->sub_masks); dev_free(ctx->sub_info);
   free_workspace(ctx);
   for (Lane& L : ctx->lanes) {
     if (L.copy_stream) {
@@ -2619,6 +2627,147 @@ int lsspa_debug_factor(lsspa_ctx* ctx, const int32_t* perm, double* L, double* L
       for (size_t c = 0; c < mp; ++c)
         V[r * mp + c] = (ctx->tri && r < (c / 128) * 128) ? 0.0 : tmp[r * ldv + c];
   }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+// ---- exact attribution by subset enumeration (k_subsets.hip) ------------------------------------------------------
+// high subsets one enumeration launch takes at most (over all units): ~35 ms of GPU time at p = 32
+static constexpr uint64_t SUBSETS_PER_LAUNCH = 1ull << 20;
+static constexpr uint64_t SUBSETS_UNITS = 8192;
+
+// the kernels' view of the loaded problem: G, g, the test Gram (formed from the test factor in rect mode) and the
+// Shapley weights by subset size
+static int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, "no problem loaded (exact attribution by subsets)");
+  const int p = ctx->p;
+  if (p > SUBSETS_MAX_P) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "exact attribution by subsets takes at most p = %d features (this problem has %d)",
+             SUBSETS_MAX_P, p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  a = SubsetArgs{};
+  a.p = p;
+  a.q = subsets_low_features(p);
+  a.G = ctx->G.ptr;
+  a.g = ctx->g.ptr;
+  a.ldg = ctx->p_pad;
+  if (ctx->tri) {
+    a.H = ctx->H.ptr;
+    a.h = ctx->h.ptr;
+    a.ldh = ctx->p_pad;
+  } else {
+    TRY(dev_alloc(ctx, ctx->sub_Hh, (size_t)p * p + p));
+    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, ctx->sub_Hh.ptr, ctx->stream));
+    a.H = ctx->sub_Hh.ptr;
+    a.h = ctx->sub_Hh.ptr + (size_t)p * p;
+    a.ldh = p;
+  }
+  // w(k) = k! (p - 1 - k)! / p! = 1 / (p C(p - 1, k)); C(31, k) < 2^53 is exact in fp64
+  double w[2 * (SUBSETS_MAX_P + 1)] = {0.0};
+  double binom = 1.0;
+  for (int k = 0; k < p; ++k) {
+    const double wk = 1.0 / ((double)p * binom);
+    w[SUBSETS_MAX_P + 1 + k] = wk;   // wb[k]
+    w[k + 1] = wk;                   // wa[k + 1]
+    binom = binom * (double)(p - 1 - k) / (double)(k + 1);
+  }
+  TRY(dev_alloc(ctx, ctx->sub_w, 2 * (SUBSETS_MAX_P + 1)));
+  TRY(dev_alloc(ctx, ctx->sub_info, 8));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // the weights are copied from this frame (a previous call may read them)
+  HIPCHK(hipMemcpy(ctx->sub_w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(ctx->sub_info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
+  a.w = ctx->sub_w.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.inv_yy = 1.0 / ctx->y_norm_sq;
+  a.info = ctx->sub_info.ptr;
+  return LSSPA_OK;
+}
+
+int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!phi) return ctx->fail(LSSPA_ERR_ARG, "phi is NULL");
+  SubsetArgs a;
+  TRY(subsets_args(ctx, a));
+  const int p = ctx->p;
+  const uint64_t n_high = 1ull << (p - a.q);
+  const uint64_t units = std::min(n_high, SUBSETS_UNITS);
+  a.per = n_high / units;                              // both powers of two
+  const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
+  TRY(dev_alloc(ctx, ctx->sub_part, (size_t)units * (p + 1)));
+  TRY(dev_alloc(ctx, ctx->sub_out, (size_t)p + 1));
+  a.part = ctx->sub_part.ptr;
+  HIPCHK(hipMemsetAsync(ctx->sub_part.ptr, 0, sizeof(double) * units * (p + 1), ctx->stream));
+  // every launch is bracketed by events: the call's kernel time and its longest launch (lsspa_subsets_timing)
+  const size_t n_launch = (size_t)((a.per + steps - 1) / steps);
+  std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
+  struct Events {
+    std::vector<hipEvent_t>& v;
+    ~Events() {
+      for (hipEvent_t e : v)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev[0], ctx->stream));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < a.per; s0 += steps, ++l) {
+    HIPCHK(launch_subsets_enum(a, units, s0, std::min(a.per, s0 + steps), ctx->stream));
+    HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
+  }
+  HIPCHK(launch_subsets_reduce(ctx->sub_part.ptr, (int64_t)units, p, ctx->sub_out.ptr, ctx->stream));
+  std::vector<double> out(p + 1);
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(out.data(), ctx->sub_out.ptr, sizeof(double) * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&bits, ctx->sub_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int j = 0; j < p; ++j) phi[j] = out[j] - out[p];
+  if (info) *info = bits;
+  ctx->sub_kernel_ms = 0.0;
+  ctx->sub_max_launch_ms = 0.0;
+  ctx->sub_launches = (int64_t)n_launch;
+  for (size_t k = 0; k < n_launch; ++k) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+    ctx->sub_kernel_ms += ms;
+    ctx->sub_max_launch_ms = std::max(ctx->sub_max_launch_ms, (double)ms);
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_subsets_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (kernel_ms) *kernel_ms = ctx->sub_kernel_ms;
+  if (max_launch_ms) *max_launch_ms = ctx->sub_max_launch_ms;
+  if (launches) *launches = ctx->sub_launches;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (n < 0 || (n > 0 && (!masks || !v))) return ctx->fail(LSSPA_ERR_ARG, "masks / v NULL or n < 0");
+  SubsetArgs a;
+  TRY(subsets_args(ctx, a));
+  const uint64_t full = (1ull << ctx->p) - 1ull;     // p <= 32 here
+  for (int64_t i = 0; i < n; ++i)
+    if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a feature beyond p");
+  if (n == 0) return LSSPA_OK;
+  TRY(dev_alloc(ctx, ctx->sub_masks, (size_t)n));
+  TRY(dev_alloc(ctx, ctx->sub_vals, (size_t)n));
+  HIPCHK(hipMemcpy(ctx->sub_masks.ptr, masks, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(launch_subsets_debug(a, ctx->sub_masks.ptr, n, ctx->sub_vals.ptr, ctx->stream));
+  HIPCHK(hipMemcpyAsync(v, ctx->sub_vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(&bits, ctx->sub_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (bits & LSSPA_INFO_NOT_PD) return ctx->fail(LSSPA_ERR_STATE, "a subset's Gram matrix is not positive definite");
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

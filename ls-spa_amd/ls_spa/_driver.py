@@ -151,6 +151,20 @@ def gather_ints_by_sum(comm, values):
     return [total[r * k:(r + 1) * k] for r in range(comm.world)]
 
 
+def _singular_fit(engine, X_test, y_test):
+    """theta and r^2 when the full model's Gram matrix is numerically singular (full_fit's info bit 1)."""
+    G, g, _, _ = engine.gram()
+    theta = _min_norm_theta(G, g)
+    yy = engine.y_norm_sq
+    if engine.tri:      # from the Gram side: also right when the test rows are sharded
+        _, _, H, h = engine.gram()
+        r_squared = float((2.0 * (h @ theta) - theta @ H @ theta) / yy)
+    else:
+        pred = X_test.astype(np.float64) @ theta
+        r_squared = float((2.0 * (pred @ y_test) - pred @ pred) / yy)
+    return theta, r_squared
+
+
 def _min_norm_theta(G, g):
     """theta of minimal norm for a numerically singular Gram matrix (the reference gets it
     from lstsq on the triangular factor, ls_spa/ls_spa.py:240)."""
@@ -280,7 +294,7 @@ def prepare_sampling(p, *, max_samples, batch_size, seed, perms, antithetical, m
     elif method == "permutohedron":
         source = S.PermutohedronSource(p, seed, max_samples)
     else:
-        raise ValueError(f"method must be one of {S.METHODS} or None")
+        raise ValueError(f"method must be one of {S.METHODS + ('subsets',)} or None")
     if source.independent:
         # the QMC samplers draw ahead of the loop on a helper thread (their stream is nobody else's), from now on --
         # in ls_spa() that is under the data reduction
@@ -683,7 +697,14 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
     next call of the same shape starts at once; ``ls_spa.release()`` (or ``release(device)``) frees it, and
     ``LSSPA_ENGINE_CACHE=0`` in the environment makes every call create and free its own.  Keyword-only additions:
 
-    method:  None (reference behaviour), 'exact', 'random', 'argsort' or 'permutohedron'.
+    method:  None (reference behaviour), 'exact', 'random', 'argsort', 'permutohedron' or 'subsets'.
+        'subsets' (p <= 32): the exact attribution from the R^2 of all 2^p feature subsets, enumerated on the GPU in
+        fp64 (include/lsspa.h, lsspa_subsets_shapley) -- no orderings, no sampling loop; overall_error 0,
+        attribution_errors zeros, error_history empty, as the reference's exact path gives them.  The sampling
+        parameters (max_samples, batch_size, num_batches, tolerance, seed, antithetical, lookahead, lanes,
+        error_estimator, precision) are ignored -- phi, theta and r_squared are fp64 whatever an earlier call of the
+        process set; return_attribution_history and checkpoint raise ValueError (there is
+        no history and nothing to resume).  With comm= every rank enumerates by itself after the shared reduction.
     num_batches:  if given, ``max_samples = batch_size * num_batches`` (README dialect).
     return_history:  alias of ``return_attribution_history``.
     device:  GPU index.
@@ -737,6 +758,11 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
         return_attribution_history = bool(return_history)
     if num_batches is not None:
         max_samples = int(batch_size) * int(num_batches)
+    if method == "subsets":
+        return _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, perms=perms,
+                               return_attribution_history=return_attribution_history, device=device,
+                               row_sharded=row_sharded, checkpoint=checkpoint, comm=comm if comm is not None else _comm,
+                               engine=_engine)
     if error_estimator is None:
         error_estimator = "device" if (perms is None and method in ("argsort", "permutohedron")) else "reference"
     if error_estimator not in ("reference", "lowrank", "device"):
@@ -839,15 +865,7 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
                           "of collinear features is not meaningful (the reference's is not either)",
                           RuntimeWarning, stacklevel=2)
         if info & 1:
-            G, g, _, _ = engine.gram()
-            theta = _min_norm_theta(G, g)
-            yy = engine.y_norm_sq
-            if engine.tri:      # from the Gram side: also right when the test rows are sharded
-                _, _, H, h = engine.gram()
-                r_squared = float((2.0 * (h @ theta) - theta @ H @ theta) / yy)
-            else:
-                pred = X_test.astype(np.float64) @ theta
-                r_squared = float((2.0 * (pred @ y_test) - pred @ pred) / yy)
+            theta, r_squared = _singular_fit(engine, X_test, y_test)
         t0 = lap("final_fit", t0)
         ok = True
     finally:
@@ -870,6 +888,65 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
     return ShapleyResults(attribution=attribution, theta=theta, overall_error=total_err,
                           attribution_errors=feat_err, r_squared=r_squared, error_history=err_hist,
                           attribution_history=history)
+
+
+SUBSETS_MAX_P = 32     # include/lsspa.h, lsspa_subsets_shapley
+
+
+def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attribution_history, device, row_sharded,
+                    checkpoint, comm, engine):
+    """ls_spa(method='subsets'): the data reduction as for every method, then the exact attribution over all 2^p
+    subsets on the engine.  No ordering source, generator or sampling loop exists in this call."""
+    p = X_train.shape[1]
+    if perms is not None:
+        raise ValueError("pass either perms= or method=, not both")
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"method='subsets' enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} "
+                         f"features (this problem has p = {p}); use a sampling method")
+    if return_attribution_history:
+        raise ValueError("method='subsets' computes no attribution history (there are no samples)")
+    if checkpoint is not None:
+        raise ValueError("method='subsets' has no state to checkpoint or resume")
+    owns = engine is None
+    kept = None
+    ok = False
+    try:
+        if owns:
+            engine, kept = _acquire_engine(device)
+        if comm is not None and hasattr(comm, "bind"):
+            comm.bind(engine)
+        # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like phi
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        if row_sharded:
+            engine.load_data_sharded(X_train, X_test, y_train, y_test, reg, comm or _Comm(),
+                                     shard_test=row_sharded != "train")
+        else:
+            engine.load_data(X_train, X_test, y_train, y_test, reg)
+        theta, r_squared, info = engine.full_fit()
+        phi, bits = engine.subsets_shapley()
+        if (bits | info) & 1:
+            warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
+                          "of collinear features is not meaningful (the reference's is not either)",
+                          RuntimeWarning, stacklevel=3)
+        if info & 1:
+            theta, r_squared = _singular_fit(engine, X_test, y_test)
+        ok = True
+    finally:
+        if owns and engine is not None:
+            try:
+                if comm is not None and hasattr(comm, "close"):
+                    comm.close()
+                if kept is None or not ok:
+                    engine.close()
+                else:
+                    engine.set_flags(0)
+                    engine.history_enable(0)
+            finally:
+                if kept is not None:
+                    kept.release()
+    return ShapleyResults(attribution=phi, theta=theta, overall_error=0.0, attribution_errors=np.zeros(p),
+                          r_squared=r_squared, error_history=np.zeros(0), attribution_history=None)
 
 
 # ------------------------------------------------------------------------------------------

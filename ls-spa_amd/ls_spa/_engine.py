@@ -188,6 +188,31 @@ class HipEngine:
         self._check(self._lib.lsspa_full_fit(self._h, N.dptr(theta), C.byref(r2), C.byref(info)))
         return theta, r2.value, info.value
 
+    # ---- exact attribution by subset enumeration (p <= 32) --------------------------------
+    SUBSETS_MAX_P = 32
+
+    def subsets_shapley(self):
+        """(phi, info): the exact Shapley attribution of the loaded problem over all 2^p subsets (include/lsspa.h,
+        lsspa_subsets_shapley); info & 1: a subset's Gram matrix was not numerically positive definite."""
+        phi = np.empty(self.p)
+        info = C.c_int32()
+        self._check(self._lib.lsspa_subsets_shapley(self._h, N.dptr(phi), C.byref(info)))
+        return phi, info.value
+
+    def subsets_timing(self):
+        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley call."""
+        ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
+        self._check(self._lib.lsspa_subsets_timing(self._h, C.byref(ms), C.byref(mx), C.byref(n)))
+        return ms.value / 1e3, mx.value / 1e3, n.value
+
+    def debug_subset_values(self, masks):
+        """Test hook: v(S) of every mask (bit j = feature j) by the enumeration's own device code."""
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
+        out = np.empty(len(masks))
+        self._check(self._lib.lsspa_debug_subset_values(self._h, masks.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                        len(masks), N.dptr(out)))
+        return out
+
     def factors(self):
         p, m = self.p, self.m
         R, q = np.empty((p, p)), np.empty(p)
