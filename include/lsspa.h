@@ -110,6 +110,24 @@ int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info);
 int lsspa_subsets_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches);
 int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v);
 
+/* Exact Shapley attribution over GROUPS of columns: the players are the g <= 32 groups, the problem has p <= 64 columns.
+ * labels[j] in {-1, 0 .. g-1} for every column j: group k is {j : labels[j] == k} (none may be empty), the columns
+ * labelled -1 are the baseline B, part of every model and given no attribution.  With F(S) = B + the columns of the
+ * groups in S and u(S) = v(F(S)), v as above,
+ *   phi_k = sum over S not containing k of |S|! (g - 1 - |S|)! / g! (u(S + k) - u(S)),   k = 0 .. g-1.
+ * The phi sum to R^2(all columns) - R^2(B alone).  All-singleton labels 0 .. p-1 give lsspa_subsets_shapley's phi.
+ * The cost is set by g (2^g group subsets), not by p.  Everything else as lsspa_subsets_shapley: fp64, any reduction,
+ * bounded launches, bitwise reproducible, LSSPA_INFO_NOT_PD in info, nothing of the sampling path and nothing of
+ * lsspa_subsets_shapley's state touched.  g > 32, p > 64, a label outside -1 .. g-1, an empty group, g < 1 or no
+ * problem loaded is LSSPA_ERR_ARG (lsspa_last_error names it).
+ *   lsspa_groups_timing      : as lsspa_subsets_timing, for the last lsspa_groups_shapley call
+ *   lsspa_debug_group_values : test hook -- u[i] = u(masks[i]) (bit k = group k; masks < 2^g) by the enumeration's own
+ *                              device code; a failed pivot is LSSPA_ERR_STATE */
+int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */, int32_t* info);
+int lsspa_groups_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches);
+int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const uint64_t* masks, int64_t n,
+                             double* u);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

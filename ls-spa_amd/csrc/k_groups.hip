@@ -1,0 +1,376 @@
+// Exact Shapley attribution over GROUPS of columns (g <= 32 groups, p <= 64 columns, an always-included baseline):
+// u(S) = v(B + columns of the groups in S) of all 2^g group subsets, never stored, folded into the Shapley sum of the
+// group game as it is computed.  fp64 throughout.  k_subsets.hip with "feature" read as "set of columns":
+//
+//   v(K) = (2 theta_K^T h_K - theta_K^T H_KK theta_K) / ||y_test||^2,  theta_K = G_KK^-1 g_K,  v({}) = 0,
+//   phi_k = sum_{S not containing k} w(|S|) (u(S + k) - u(S)),   w(s) = s! (g - 1 - s)! / g!.
+//
+// Decomposition ("Exact attribution over groups of columns"): the host picks gl LOW groups (the smallest
+// ones, while their columns total ql <= 6); the other gh = g - gl groups are HIGH.  One workgroup of four waves owns one
+// high subset Hs at a time:
+//   1. it compacts [G g] over B + cols(Hs) + low columns into LDS (nk <= 64 rows, nk + 1 columns) and eliminates the
+//      pivots of B + cols(Hs) by Gauss-Jordan, in place.  A lane owns a row, a wave every fourth column to the right of
+//      the pivot: the columns to its left are never read again, so they are not kept up (half the work of a full
+//      sweep), and a column is read and written by one wave only, so a pivot costs one barrier.  That leaves
+//      A^-1 [C g] in the pivot rows (A = G over B + cols(Hs), C its coupling to the low columns) and the Schur
+//      complement S, g~ in the low block;
+//   2. theta over everything is e0 + E theta_T with e0 = [A^-1 g; 0], E = [-A^-1 C; I]: the test side reduces to the
+//      (ql+1) x (ql+1) matrix Z = X^T H X and z = X^T h of X = [e0 E] (H read from global memory, a row at a time:
+//      H is symmetric, so the lanes of a wave read neighbouring words);
+//   3. lane T of the first wave (one lane per subset of the low groups, 2^gl <= 64) masks the rows and columns of S
+//      whose group is not in T to the identity and runs the fixed 6 x 6 Cholesky, solves and quadratic form of
+//      k_subsets.hip in registers.
+// The Shapley sum is that file's too, over groups: with a(K) = w(|K| - 1) u(K), b(K) = w(|K|) u(K),
+//   phi_k = sum_{K containing k} (a + b)(K) - sum_K b(K),
+// kept per lane, reduced once per launch by fixed butterflies into the unit's row of a partial table [units][g + 1]
+// (low groups first, then the high ones, then b) which launch_subsets_reduce sums in fixed order.  No floating-point
+// atomics: the result is bitwise the same from call to call.
+#include "kernels.h"
+
+#include <algorithm>
+#include <numeric>
+
+namespace lsspa {
+namespace {
+
+constexpr int GQ = GROUPS_LOW_COLS;            // low columns at most: the register-resident Cholesky
+constexpr int GP = GROUPS_MAX_P;               // 64
+constexpr int GG = GROUPS_MAX_G;               // 32
+constexpr int LDM = GP + 1;                    // row stride of the compacted matrix: nk columns and the right-hand side
+constexpr int XC = GQ + 1;                     // row stride of X and Y
+constexpr int ZC = GQ + 2;                     // row stride of Z: columns 0 .. ql of X^T H X, then X^T h
+constexpr int NT = 256;                        // four waves
+
+struct GrpShared {
+  double M[GP * LDM];      // compacted [G g] being eliminated: rows = columns of the subset, odd stride
+  double X[GP * XC];       // [e0 E]
+  double Y[GP * XC];       // H X
+  double Z[XC * ZC];       // X^T H X | X^T h
+  double h[GP];
+  double gdiag[GP];        // diagonal of G: the pivot scale
+  double wa[GG + 1], wb[GG + 1];
+  int idx[GP];             // compacted position -> column
+  int cols[GP];            // the layout (GroupLayout::tab)
+  int colgrp[GP];
+  int colin[GP];
+  int hsize[GG];
+  int lgrp[GQ];
+};
+
+__device__ inline double wave_sum(double x) {
+  // fixed butterfly, then lane 0's value for everyone: the same order on every call
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return __shfl(x, 0, 64);
+}
+
+// u(Hs + T) of this thread's low subset T = tid (0 for threads >= 2^gl).  Enters and leaves with the workgroup in
+// step: every shared array it writes is free when it is called and is read by nobody after it returns.
+__device__ double group_values(GrpShared& sh, const GroupArgs& a, uint64_t hi, int tid, bool& bad) {
+  const int p = a.p, ql = a.ql, nb = a.nb, gh = a.gh;
+  const int wv = tid >> 6, lane = tid & 63;
+  // pivots of this subset: the baseline, then the columns of the high groups of hi in layout order
+  const int myg = (tid < p) ? sh.colgrp[tid] : -1;
+  int nhs = nb, off = 0;
+  for (int j = 0; j < gh; ++j) {
+    if (j == myg) off = nhs;
+    if ((hi >> j) & 1ull) nhs += sh.hsize[j];
+  }
+  if (tid < p) {
+    if (tid < nb)
+      sh.idx[tid] = sh.cols[tid];
+    else if (tid >= p - ql)
+      sh.idx[nhs + tid - (p - ql)] = sh.cols[tid];
+    else if ((hi >> myg) & 1ull)
+      sh.idx[off + sh.colin[tid]] = sh.cols[tid];
+  }
+  const int nk = nhs + ql;    // columns of B + Hs + low: rows of M; column nk of M is the right-hand side
+  __syncthreads();
+  for (int i = wv; i < nk; i += 4) {
+    const int ci = sh.idx[i];
+    for (int j = lane; j <= nk; j += 64)
+      sh.M[i * LDM + j] = (j < nk) ? a.G[(int64_t)ci * a.ldg + sh.idx[j]] : a.g[ci];
+  }
+  __syncthreads();
+  // Gauss-Jordan on the pivots 0 .. nhs-1, columns right of the pivot only.  Column j belongs to wave (j - k - 1) % 4
+  // of step k: its lanes read the pivot row's entry before lane k overwrites it (one instruction stream), column k
+  // itself is not written in step k, and the barrier separates the steps.
+  for (int k = 0; k < nhs; ++k) {
+    const double d = sh.M[k * LDM + k];
+    if (!(d > a.piv_tol * sh.gdiag[sh.idx[k]])) bad = true;
+    const double inv = 1.0 / d;
+    if (lane < nk) {
+      const double mik = sh.M[lane * LDM + k];
+      for (int j = k + 1 + wv; j <= nk; j += 4) {
+        const double mkj = sh.M[k * LDM + j] * inv;
+        const double mij = sh.M[lane * LDM + j];
+        sh.M[lane * LDM + j] = (lane == k) ? mkj : mij - mik * mkj;
+      }
+    }
+    __syncthreads();
+  }
+  // X = [e0 E] over the nk compacted columns (columns 0 .. ql of X)
+  const int nc = ql + 1;
+  for (int e = tid; e < nk * nc; e += NT) {
+    const int i = e / nc, c = e - i * nc;
+    double x;
+    if (i < nhs)
+      x = (c == 0) ? sh.M[i * LDM + nk] : -sh.M[i * LDM + nhs + c - 1];
+    else
+      x = (c - 1 == i - nhs) ? 1.0 : 0.0;
+    sh.X[i * XC + c] = x;
+  }
+  __syncthreads();
+  // Y = H X: lane = row i, wave wv takes columns wv and wv + 4; H_ib is read as H_bi, a contiguous run of row b
+  if (lane < nk && wv < nc) {
+    const bool two = wv + 4 < nc;
+    const double* Hc = a.H + sh.idx[lane];
+    double s0 = 0.0, s1 = 0.0;
+    for (int b = 0; b < nk; ++b) {
+      const double hv = Hc[(int64_t)sh.idx[b] * a.ldh];
+      s0 += hv * sh.X[b * XC + wv];
+      if (two) s1 += hv * sh.X[b * XC + wv + 4];
+    }
+    sh.Y[lane * XC + wv] = s0;
+    if (two) sh.Y[lane * XC + wv + 4] = s1;
+  }
+  __syncthreads();
+  if (tid < nc * (nc + 1)) {
+    const int c = tid / (nc + 1), c2 = tid - c * (nc + 1);
+    double s = 0.0;
+    if (c2 < nc)
+      for (int i = 0; i < nk; ++i) s += sh.X[i * XC + c] * sh.Y[i * XC + c2];
+    else
+      for (int i = 0; i < nk; ++i) s += sh.X[i * XC + c] * sh.h[sh.idx[i]];
+    sh.Z[c * ZC + (c2 < nc ? c2 : GQ + 1)] = s;
+  }
+  __syncthreads();
+  // lane T of the first wave: theta_T = S_TT^-1 g~_T with every column whose group is outside T masked to the identity
+  double v = 0.0;
+  if (tid < (1 << a.gl)) {
+    bool in[GQ];
+#pragma unroll
+    for (int t = 0; t < GQ; ++t) in[t] = (t < ql) && ((tid >> sh.lgrp[t]) & 1);
+    double L[GQ][GQ], y[GQ];
+#pragma unroll
+    for (int t = 0; t < GQ; ++t) {
+      const double mt = (t < ql) ? sh.M[(nhs + t) * LDM + nk] : 0.0;
+      y[t] = in[t] ? mt : 0.0;
+#pragma unroll
+      for (int s = 0; s <= t; ++s) {
+        const double ms = (t < ql) ? sh.M[(nhs + t) * LDM + nhs + s] : 0.0;
+        L[t][s] = (in[t] && in[s]) ? ms : (s == t ? 1.0 : 0.0);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < GQ; ++j) {
+      double d = L[j][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+      if (in[j] && !(d > a.piv_tol * sh.gdiag[sh.idx[nhs + j]])) bad = true;
+      const double r = 1.0 / sqrt(d);
+      L[j][j] = d * r;
+#pragma unroll
+      for (int i = j + 1; i < GQ; ++i) {
+        double s = L[i][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+        L[i][j] = s * r;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < GQ; ++i) {
+      double s = y[i];
+#pragma unroll
+      for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+      y[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = GQ - 1; i >= 0; --i) {
+      double s = y[i];
+#pragma unroll
+      for (int k = i + 1; k < GQ; ++k) s -= L[k][i] * y[k];
+      y[i] = s / L[i][i];                 // theta_T (exactly 0 outside T)
+    }
+    double f = 2.0 * sh.Z[GQ + 1] - sh.Z[0];
+#pragma unroll
+    for (int t = 0; t < GQ; ++t) {
+      if (t < ql) {
+        double u = 2.0 * (sh.Z[(1 + t) * ZC + GQ + 1] - sh.Z[(1 + t) * ZC]);
+#pragma unroll
+        for (int s = 0; s < GQ; ++s)
+          if (s < ql) u -= sh.Z[(1 + t) * ZC + 1 + s] * y[s];
+        f += y[t] * u;
+      }
+    }
+    v = f * a.inv_yy;
+  }
+  return v;
+}
+
+__device__ void load_shared(GrpShared& sh, const GroupArgs& a, int tid) {
+  const int p = a.p;
+  if (tid < p) {
+    sh.h[tid] = a.h[tid];
+    sh.gdiag[tid] = a.G[(int64_t)tid * a.ldg + tid];
+    sh.cols[tid] = a.tab[GROUPS_TAB_COLS + tid];
+    sh.colgrp[tid] = a.tab[GROUPS_TAB_COLGRP + tid];
+    sh.colin[tid] = a.tab[GROUPS_TAB_COLIN + tid];
+  }
+  if (tid < GG) sh.hsize[tid] = a.tab[GROUPS_TAB_HSIZE + tid];
+  if (tid < GQ) sh.lgrp[tid] = a.tab[GROUPS_TAB_LGRP + tid];
+  if (tid <= a.ng) {
+    sh.wa[tid] = a.w[tid];
+    sh.wb[tid] = a.w[GG + 1 + tid];
+  }
+  for (int e = tid; e < XC * ZC; e += NT) sh.Z[e] = 0.0;   // rows / columns beyond ql stay 0
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s0, uint64_t s1) {
+  __shared__ GrpShared sh;
+  const int tid = threadIdx.x;
+  const int ng = a.ng, gl = a.gl, gh = a.gh;
+  load_shared(sh, a, tid);
+  double acc[GG];
+#pragma unroll
+  for (int j = 0; j < GG; ++j) acc[j] = 0.0;
+  double c_own = 0.0, b_own = 0.0;
+  bool bad = false;
+  const bool live = tid < (1 << gl);
+  const int kt = __popc(tid);
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    const double v = group_values(sh, a, hi, tid, bad);
+    if (live) {
+      const int k = __popcll(hi) + kt;
+      const double c = (sh.wa[k] + sh.wb[k]) * v;
+      c_own += c;
+      b_own += sh.wb[k] * v;
+#pragma unroll
+      for (int j = 0; j < GG; ++j)
+        if (j < gh && ((hi >> j) & 1ull)) acc[j] += c;
+    }
+    __syncthreads();
+  }
+  if (tid < 64) {     // the live lanes all sit in the first wave
+    double* part = a.part + (int64_t)blockIdx.x * (ng + 1);
+#pragma unroll
+    for (int t = 0; t < GQ; ++t) {
+      if (t < gl) {
+        const double tot = wave_sum((live && ((tid >> t) & 1)) ? c_own : 0.0);
+        if (tid == 0) part[t] += tot;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < GG; ++j) {
+      if (j < gh) {
+        const double tot = wave_sum(acc[j]);
+        if (tid == 0) part[gl + j] += tot;
+      }
+    }
+    const double tb = wave_sum(b_own);
+    if (tid == 0) part[ng] += tb;
+  }
+  if (__any(bad) && (tid & 63) == 0) atomicOr(a.info, 1);
+}
+
+// masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
+__global__ __launch_bounds__(NT) void groups_debug_kernel(GroupArgs a, const uint64_t* __restrict__ masks, int64_t n,
+                                                          double* __restrict__ vals) {
+  __shared__ GrpShared sh;
+  const int tid = threadIdx.x;
+  load_shared(sh, a, tid);
+  bool bad = false;
+  const uint64_t low = (1ull << a.gl) - 1ull;
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint64_t m = masks[i];
+    const double v = group_values(sh, a, m >> a.gl, tid, bad);
+    if ((uint64_t)tid == (m & low)) vals[i] = v;
+    __syncthreads();
+  }
+  if (__any(bad) && (tid & 63) == 0) atomicOr(a.info, 1);
+}
+
+bool args_ok(const GroupArgs& a) {
+  return a.p >= 1 && a.p <= GP && a.ng >= 1 && a.ng <= GG && a.gl >= 0 && a.gl <= GQ && a.gl + a.gh == a.ng &&
+         a.ql >= a.gl && a.ql <= GQ && a.nb >= 0 && a.nb + a.ql <= a.p && a.G && a.g && a.H && a.h && a.w && a.tab &&
+         a.info && a.ldg >= a.p && a.ldh >= a.p;
+}
+
+}  // namespace
+
+const char* groups_layout(const int32_t* labels, int p, int g, GroupLayout& L) {
+  if (!labels) return "labels is NULL";
+  if (g < 1) return "grouped attribution needs at least one group";
+  if (g > GG) return "grouped attribution takes at most 32 groups";
+  if (p < 1 || p > GP) return "grouped attribution takes at most 64 columns";
+  int size[GG] = {0};
+  L = GroupLayout{};
+  for (int j = 0; j < p; ++j) {
+    if (labels[j] < -1 || labels[j] >= g) return "a label lies outside -1 .. g-1";
+    if (labels[j] >= 0) ++size[labels[j]];
+  }
+  for (int k = 0; k < g; ++k)
+    if (size[k] == 0) return "a group of 0 .. g-1 has no column";
+  // low groups: the smallest first (ties by number) while their columns fit the register-resident Cholesky
+  int order[GG];
+  std::iota(order, order + g, 0);
+  std::stable_sort(order, order + g, [&](int x, int y) { return size[x] < size[y]; });
+  bool low[GG] = {false};
+  L.p = p;
+  L.ng = g;
+  for (int r = 0; r < g && L.ql + size[order[r]] <= GQ; ++r) {
+    low[order[r]] = true;
+    L.gid[L.gl++] = order[r];
+    L.ql += size[order[r]];
+  }
+  L.gh = g - L.gl;
+  for (int k = 0, j = 0; k < g; ++k)
+    if (!low[k]) L.gid[L.gl + j++] = k;
+  int32_t* cols = L.tab + GROUPS_TAB_COLS;
+  int32_t* colgrp = L.tab + GROUPS_TAB_COLGRP;
+  int32_t* colin = L.tab + GROUPS_TAB_COLIN;
+  int c = 0;
+  for (int j = 0; j < p; ++j)
+    if (labels[j] < 0) {
+      colgrp[c] = -1;
+      cols[c++] = j;
+    }
+  L.nb = c;
+  for (int r = L.gl; r < g; ++r) {
+    int n = 0;
+    for (int j = 0; j < p; ++j)
+      if (labels[j] == L.gid[r]) {
+        colgrp[c] = r - L.gl;
+        colin[c] = n++;
+        cols[c++] = j;
+      }
+    L.tab[GROUPS_TAB_HSIZE + r - L.gl] = n;
+  }
+  for (int r = 0, t = 0; r < L.gl; ++r)
+    for (int j = 0; j < p; ++j)
+      if (labels[j] == L.gid[r]) {
+        colgrp[c] = -1;
+        L.tab[GROUPS_TAB_LGRP + t++] = r;
+        cols[c++] = j;
+      }
+  return nullptr;
+}
+
+hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st) {
+  if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^gh
+  if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(groups_enum_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+  return hipGetLastError();
+}
+
+hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st) {
+  if (!args_ok(a) || !masks || !vals || n < 1) return hipErrorInvalidValue;
+  const int64_t grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(groups_debug_kernel, dim3((unsigned)grid), dim3(NT), 0, st, a, masks, n, vals);
+  return hipGetLastError();
+}
+
+}  // namespace lsspa

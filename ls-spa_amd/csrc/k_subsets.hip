@@ -355,7 +355,7 @@ hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int6
 
 hipError_t launch_subsets_test_gram(const double* Ft, int64_t ldf, const double* ytil, int p, int m, double* Hh,
                                     hipStream_t st) {
-  if (!Ft || !ytil || !Hh || p < 1 || p > SP || m < 1 || ldf < m) return hipErrorInvalidValue;
+  if (!Ft || !ytil || !Hh || p < 1 || p > GROUPS_MAX_P || m < 1 || ldf < m) return hipErrorInvalidValue;
   hipLaunchKernelGGL(subsets_test_gram_kernel, dim3(p * (p + 1)), dim3(256), 0, st, Ft, ldf, ytil, p, m, Hh);
   return hipGetLastError();
 }

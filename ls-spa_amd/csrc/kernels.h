@@ -288,7 +288,45 @@ hipError_t launch_subsets_reduce(const double* part, int64_t units, int p, doubl
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used
+// (p <= 64: the grouped enumeration of k_groups.hip uses it too)
 hipError_t launch_subsets_test_gram(const double* Ft, int64_t ldf, const double* ytil, int p, int m, double* Hh,
                                     hipStream_t st);
+
+// Exact attribution over groups of columns (k_groups.hip), g <= GROUPS_MAX_G groups, p <= GROUPS_MAX_P columns, fp64.
+// groups_layout turns labels (-1: baseline, 0 .. g-1: group) into the kernels' layout: gl low groups (the smallest,
+// ql <= GROUPS_LOW_COLS columns together) and gh high ones; gid[r] is the label of the layout's group r (low groups
+// first).  tab: the columns in layout order (baseline, high groups, low groups), per column its high group (-1: none)
+// and its place inside it, the high groups' sizes and per low column its low group.  High subset number hi is the set
+// of high groups {j : bit j of hi}.  Units, steps and the partial table [units][g + 1] (layout numbering, then b) are
+// those of launch_subsets_enum; launch_subsets_reduce sums the table.
+constexpr int GROUPS_MAX_G = 32, GROUPS_MAX_P = 64, GROUPS_LOW_COLS = 6;
+constexpr int GROUPS_TAB_COLS = 0, GROUPS_TAB_COLGRP = GROUPS_MAX_P, GROUPS_TAB_COLIN = 2 * GROUPS_MAX_P,
+              GROUPS_TAB_HSIZE = 3 * GROUPS_MAX_P, GROUPS_TAB_LGRP = GROUPS_TAB_HSIZE + GROUPS_MAX_G,
+              GROUPS_TAB_LEN = GROUPS_TAB_LGRP + 8;
+struct GroupLayout {
+  int p, ng, nb, gl, gh, ql;
+  int gid[GROUPS_MAX_G];
+  int32_t tab[GROUPS_TAB_LEN];
+};
+// nullptr, or what is wrong with the labels
+const char* groups_layout(const int32_t* labels, int p, int g, GroupLayout& L);
+struct GroupArgs {
+  const double* G;         // [p][ldg] training Gram
+  const double* g;         // [p]
+  const double* H;         // [p][ldh] test Gram (symmetric)
+  const double* h;         // [p]
+  int64_t ldg, ldh;
+  const double* w;         // [2][GROUPS_MAX_G + 1]: wa[k] = w(k - 1) (0 for k = 0), wb[k] = w(k) (0 for k = g)
+  const int32_t* tab;      // GroupLayout::tab on the device
+  int p, ng, nb, gl, gh, ql;
+  double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
+  double inv_yy;           // 1 / ||y_test||^2
+  uint64_t per;            // high subsets per unit
+  double* part;            // [units][g + 1]
+  int32_t* info;           // bit 1: a pivot failed
+};
+hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
+// vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
+hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 
 }  // namespace lsspa

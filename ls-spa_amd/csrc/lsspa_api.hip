@@ -146,6 +146,12 @@ struct lsspa_ctx {
   DevBuf<int32_t> sub_info;
   double sub_kernel_ms = 0.0, sub_max_launch_ms = 0.0;
   int64_t sub_launches = 0;
+  // ... and over groups of columns (lsspa_groups_shapley): again its own buffers, info word and timing
+  DevBuf<double> gsh_Hh, gsh_w, gsh_part, gsh_out, gsh_vals;
+  DevBuf<uint64_t> gsh_masks;
+  DevBuf<int32_t> gsh_info, gsh_tab;
+  double gsh_kernel_ms = 0.0, gsh_max_launch_ms = 0.0;
+  int64_t gsh_launches = 0;
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -2768,6 +2774,176 @@ int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, 
   HIPCHK(hipMemcpyAsync(&bits, ctx->sub_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (bits & LSSPA_INFO_NOT_PD) return ctx->fail(LSSPA_ERR_STATE, "a subset's Gram matrix is not positive definite");
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+// ---- exact attribution over groups of columns (k_groups.hip) -------------------------------------------------------
+// One enumeration launch takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high subset
+// counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
+// subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X: far below the bound of
+// 0.2 s, and long enough that the launches' own cost does not show.
+static constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
+static constexpr uint64_t GROUPS_UNITS = 8192;
+
+static int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, GroupLayout& L) {
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, "no problem loaded (exact attribution over groups)");
+  const int p = ctx->p;
+  char msg[200];
+  if (p > GROUPS_MAX_P) {
+    snprintf(msg, sizeof msg, "exact attribution over groups takes at most p = %d columns (this problem has %d)",
+             GROUPS_MAX_P, p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+             (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (const char* why = groups_layout(labels, p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  a = GroupArgs{};
+  a.p = p;
+  a.ng = L.ng;
+  a.nb = L.nb;
+  a.gl = L.gl;
+  a.gh = L.gh;
+  a.ql = L.ql;
+  a.G = ctx->G.ptr;
+  a.g = ctx->g.ptr;
+  a.ldg = ctx->p_pad;
+  if (ctx->tri) {
+    a.H = ctx->H.ptr;
+    a.h = ctx->h.ptr;
+    a.ldh = ctx->p_pad;
+  } else {
+    TRY(dev_alloc(ctx, ctx->gsh_Hh, (size_t)p * p + p));
+    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, ctx->gsh_Hh.ptr, ctx->stream));
+    a.H = ctx->gsh_Hh.ptr;
+    a.h = ctx->gsh_Hh.ptr + (size_t)p * p;
+    a.ldh = p;
+  }
+  // w(k) = k! (g - 1 - k)! / g! = 1 / (g C(g - 1, k)); C(31, k) < 2^53 is exact in fp64
+  double w[2 * (GROUPS_MAX_G + 1)] = {0.0};
+  double binom = 1.0;
+  for (int k = 0; k < L.ng; ++k) {
+    const double wk = 1.0 / ((double)L.ng * binom);
+    w[GROUPS_MAX_G + 1 + k] = wk;   // wb[k]
+    w[k + 1] = wk;                  // wa[k + 1]
+    binom = binom * (double)(L.ng - 1 - k) / (double)(k + 1);
+  }
+  TRY(dev_alloc(ctx, ctx->gsh_w, 2 * (GROUPS_MAX_G + 1)));
+  TRY(dev_alloc(ctx, ctx->gsh_tab, GROUPS_TAB_LEN));
+  TRY(dev_alloc(ctx, ctx->gsh_info, 8));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // weights and layout are copied from this frame
+  HIPCHK(hipMemcpy(ctx->gsh_w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->gsh_tab.ptr, L.tab, sizeof L.tab, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(ctx->gsh_info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
+  a.w = ctx->gsh_w.ptr;
+  a.tab = ctx->gsh_tab.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.inv_yy = 1.0 / ctx->y_norm_sq;
+  a.info = ctx->gsh_info.ptr;
+  return LSSPA_OK;
+}
+
+int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!phi || !labels) return ctx->fail(LSSPA_ERR_ARG, "labels / phi is NULL");
+  GroupArgs a;
+  GroupLayout L;
+  TRY(groups_args(ctx, labels, g, a, L));
+  const int ng = L.ng;
+  const uint64_t n_high = 1ull << L.gh;
+  const uint64_t units = std::min(n_high, GROUPS_UNITS);
+  a.per = n_high / units;                              // both powers of two
+  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
+  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
+  const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
+  const uint64_t steps = std::max<uint64_t>(1, per_launch / units);
+  TRY(dev_alloc(ctx, ctx->gsh_part, (size_t)units * (ng + 1)));
+  TRY(dev_alloc(ctx, ctx->gsh_out, (size_t)ng + 1));
+  a.part = ctx->gsh_part.ptr;
+  HIPCHK(hipMemsetAsync(ctx->gsh_part.ptr, 0, sizeof(double) * units * (ng + 1), ctx->stream));
+  // every launch is bracketed by events: the call's kernel time and its longest launch (lsspa_groups_timing)
+  const size_t n_launch = (size_t)((a.per + steps - 1) / steps);
+  std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
+  struct Events {
+    std::vector<hipEvent_t>& v;
+    ~Events() {
+      for (hipEvent_t e : v)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev[0], ctx->stream));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < a.per; s0 += steps, ++l) {
+    HIPCHK(launch_groups_enum(a, units, s0, std::min(a.per, s0 + steps), ctx->stream));
+    HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
+  }
+  HIPCHK(launch_subsets_reduce(ctx->gsh_part.ptr, (int64_t)units, ng, ctx->gsh_out.ptr, ctx->stream));
+  std::vector<double> out(ng + 1);
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(out.data(), ctx->gsh_out.ptr, sizeof(double) * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&bits, ctx->gsh_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int r = 0; r < ng; ++r) phi[L.gid[r]] = out[r] - out[ng];
+  if (info) *info = bits;
+  ctx->gsh_kernel_ms = 0.0;
+  ctx->gsh_max_launch_ms = 0.0;
+  ctx->gsh_launches = (int64_t)n_launch;
+  for (size_t k = 0; k < n_launch; ++k) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+    ctx->gsh_kernel_ms += ms;
+    ctx->gsh_max_launch_ms = std::max(ctx->gsh_max_launch_ms, (double)ms);
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_groups_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (kernel_ms) *kernel_ms = ctx->gsh_kernel_ms;
+  if (max_launch_ms) *max_launch_ms = ctx->gsh_max_launch_ms;
+  if (launches) *launches = ctx->gsh_launches;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const uint64_t* masks, int64_t n,
+                             double* u) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!labels || n < 0 || (n > 0 && (!masks || !u))) return ctx->fail(LSSPA_ERR_ARG, "labels / masks / u NULL or n < 0");
+  GroupArgs a;
+  GroupLayout L;
+  TRY(groups_args(ctx, labels, g, a, L));
+  const uint64_t full = L.ng < 64 ? (1ull << L.ng) - 1ull : ~0ull;
+  for (int64_t i = 0; i < n; ++i)
+    if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a group beyond g");
+  if (n == 0) return LSSPA_OK;
+  // bit k = group k  ->  the layout's numbering (low groups first)
+  std::vector<uint64_t> lay((size_t)n, 0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int r = 0; r < L.ng; ++r)
+      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  TRY(dev_alloc(ctx, ctx->gsh_masks, (size_t)n));
+  TRY(dev_alloc(ctx, ctx->gsh_vals, (size_t)n));
+  HIPCHK(hipMemcpy(ctx->gsh_masks.ptr, lay.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(launch_groups_debug(a, ctx->gsh_masks.ptr, n, ctx->gsh_vals.ptr, ctx->stream));
+  HIPCHK(hipMemcpyAsync(u, ctx->gsh_vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(&bits, ctx->gsh_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (bits & LSSPA_INFO_NOT_PD)
+    return ctx->fail(LSSPA_ERR_STATE, "a group subset's Gram matrix is not positive definite");
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

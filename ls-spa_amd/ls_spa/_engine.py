@@ -213,6 +213,42 @@ class HipEngine:
                                                         len(masks), N.dptr(out)))
         return out
 
+    # ---- exact attribution over groups of columns (g <= 32, p <= 64) ---------------------
+    @staticmethod
+    def _labels(labels):
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        return labels, (int(labels.max()) + 1 if len(labels) else 0)
+
+    def groups_shapley(self, labels):
+        """(phi, info): the exact Shapley attribution over the groups of columns that labels names (one label per
+        column: -1 the baseline, 0 .. g-1 the groups; include/lsspa.h, lsspa_groups_shapley), phi of length g.  The
+        library checks the labels (their length is the caller's to get right: p of the loaded problem)."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        phi = np.empty(max(g, 1))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_groups_shapley(self._h, N.iptr(labels), g, N.dptr(phi), C.byref(info)))
+        return phi, info.value
+
+    def groups_timing(self):
+        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley call."""
+        ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
+        self._check(self._lib.lsspa_groups_timing(self._h, C.byref(ms), C.byref(mx), C.byref(n)))
+        return ms.value / 1e3, mx.value / 1e3, n.value
+
+    def debug_group_values(self, labels, masks):
+        """Test hook: u(S) of every mask (bit k = group k) by the grouped enumeration's own device code."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
+        out = np.empty(len(masks))
+        self._check(self._lib.lsspa_debug_group_values(self._h, N.iptr(labels), g,
+                                                       masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks),
+                                                       N.dptr(out)))
+        return out
+
     def factors(self):
         p, m = self.p, self.m
         R, q = np.empty((p, p)), np.empty(p)
