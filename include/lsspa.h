@@ -175,6 +175,27 @@ int lsspa_lift_collect(lsspa_ctx* ctx, int32_t ticket, int32_t first, int32_t co
 int lsspa_lift_collect_chunks(lsspa_ctx* ctx, int32_t ticket, int32_t first, int32_t chunk, int32_t n_chunks,
                               int32_t accumulate);
 int lsspa_lift_discard(lsspa_ctx* ctx, int32_t ticket);
+/* Sampled attribution over GROUPS of columns: a player map.  labels [p] as in lsspa_groups_shapley (-1: baseline, 0 ..
+ * g-1: group, none empty), any 1 <= g <= p.  From now until the next reduction, lsspa_set_reduced or
+ * lsspa_set_players(ctx, NULL, 0): perms of lsspa_lift_batch / lsspa_lift_launch are [B][g] orderings of the GROUPS (each
+ * row a permutation of 0 .. g-1); lifts_out, the pending buffer, running statistics, history, estimator state, result
+ * slots and every other [p]-sized output of the sampling path have dimension g.  The library expands a group ordering to
+ * the column ordering "baseline columns, then each group's columns (ascending) in the ordering's order", runs it through
+ * the same kernels, checks the un-folded lifts against the full R^2 as ever (LSSPA_INFO_SUM) and then folds them on the
+ * device: sample s, group k = mean over the sample's one or two orderings of the sum of its columns' lifts, in a fixed
+ * order (two runs agree bitwise).  The mean over all g! group orderings is lsspa_groups_shapley's phi.  Antithetical: the
+ * second ordering is the baseline followed by the groups in REVERSED order; with a baseline the pair runs as two unpaired
+ * orderings, without one as the kernels' pair (the forward column ordering read backwards, an expansion of the reversed
+ * group ordering).  Setting or clearing a map resets the running statistics and switches history and estimator off
+ * (enable them again: their row stride is the sample dimension); lsspa_full_fit, lsspa_get_factors, lsspa_debug_factor,
+ * the enumerations and the reduction side are untouched by it.  Refused (LSSPA_ERR_STATE) while a launched batch is
+ * uncollected; bad labels are LSSPA_ERR_ARG.  With no map set every entry point behaves bit for bit as before.
+ *   lsspa_debug_expand_groups : test hook, host only (no context, no GPU) -- out [B * (antithetical ? 2 : 1)][p] = the
+ *                               column orderings the kernels are given for group_perms [B][g]; bad labels or a row that
+ *                               is not a permutation of 0 .. g-1 is LSSPA_ERR_ARG */
+int lsspa_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g);
+int lsspa_debug_expand_groups(const int32_t* labels, int32_t p, int32_t g, const int32_t* group_perms, int32_t B,
+                              int32_t antithetical, int32_t* out);
 /* 1 (default): every batch runs on the context's stream, one after the other.  2: successive batches alternate
  * between two workspaces on two streams, staggered by half a batch, so that the memory-bound stages (gather, lifts)
  * and the launch tails of one batch run beside the matrix-pipe-bound stages of the other; statistics, collectives
@@ -198,7 +219,9 @@ int lsspa_get_sum_deviation(lsspa_ctx* ctx, double* max_deviation);
 int lsspa_stats_reset(lsspa_ctx* ctx);
 int lsspa_stats_pending(lsspa_ctx* ctx, void** device_ptr, int64_t* count);
 int lsspa_stats_merge(lsspa_ctx* ctx);
-/* n samples, mean [p], biased covariance [p][p] (may be NULL) */
+/* n samples, mean [p], biased covariance [p][p] (may be NULL); with a player map (lsspa_set_players) p reads g here and
+ * in lsspa_stats_set, lsspa_stats_pending, lsspa_history_get / _append, lsspa_error_quantiles, lsspa_error_result and
+ * lsspa_error_state_get / _set */
 int lsspa_stats_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* cov_biased);
 /* checkpoint / resume: overwrite the running statistics with (n, mean [p], biased covariance [p][p]) as
  * lsspa_stats_get returned them; the pending buffer is cleared.  (The reference keeps these in three Python

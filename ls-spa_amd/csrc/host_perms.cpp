@@ -76,6 +76,49 @@ bool all_permutations_plain(const int32_t* perms, int B, int p, std::vector<int3
   return rows_stamped(perms, B, p, mark);
 }
 
+
+// ---- groups of columns as the players (lsspa_set_players) ---------------------------------------------------------
+// The sampled orderings are orderings of the g groups; the kernels take orderings of the p columns.  The expansion is
+// host work on the launch path, next to the validation above: baseline columns first (they are part of every model),
+// then every group's columns contiguously, ascending inside a group (the group's summed lift does not depend on the
+// order inside it).
+struct PlayerMap {      // as kernels.h declares it (this file is host-only C++ and does not include the HIP headers)
+  int p = 0, g = 0;
+  std::vector<int32_t> off, cols, base;
+};
+
+const char* player_map_build(const int32_t* labels, int p, int g, PlayerMap& m) {
+  if (p < 1) return "no problem loaded";
+  if (g < 1 || g > p) return "the number of groups g must be between 1 and p";
+  m.p = p;
+  m.g = g;
+  m.off.assign((size_t)g + 1, 0);
+  m.base.clear();
+  for (int j = 0; j < p; ++j) {
+    if (labels[j] < -1 || labels[j] >= g) return "labels: every label must be -1 (baseline) or a group number 0 .. g-1";
+    if (labels[j] < 0) m.base.push_back(j);
+    else ++m.off[(size_t)labels[j] + 1];
+  }
+  for (int k = 0; k < g; ++k) {
+    if (m.off[(size_t)k + 1] == 0) return "labels: a group has no column (the groups 0 .. g-1 must all be used)";
+    m.off[(size_t)k + 1] += m.off[k];
+  }
+  m.cols.assign((size_t)p - m.base.size(), 0);
+  std::vector<int32_t> at(m.off.begin(), m.off.end() - 1);
+  for (int j = 0; j < p; ++j)
+    if (labels[j] >= 0) m.cols[(size_t)at[labels[j]]++] = j;
+  return nullptr;
+}
+
+void expand_group_row(const PlayerMap& m, const int32_t* gperm, int reversed, int32_t* out) {
+  int32_t* w = out;
+  for (int32_t j : m.base) *w++ = j;
+  for (int i = 0; i < m.g; ++i) {
+    const int k = gperm[reversed ? m.g - 1 - i : i];
+    for (int c = m.off[k]; c < m.off[(size_t)k + 1]; ++c) *w++ = m.cols[c];
+  }
+}
+
 }  // namespace lsspa
 
 

@@ -51,6 +51,7 @@ struct Lane {
   int cap_samples = 0;               // samples the lifts buffer can hold
   DevBuf<char> A, V, Dinv;           // raw bytes: esz() per element
   DevBuf<double> Ppart, lifts, diag0;
+  DevBuf<double> folded;             // player map set: [samples][g] group lifts, what collect reads instead of lifts
   DevBuf<double> run;                // [cap_ord][p_pad] running sums of the fused lift scan (tri mode)
   DevBuf<int32_t> row_flags;         // [2 cap_ord] "row p of panel J is final" per work matrix (fused lift scan)
   DevBuf<int32_t> perms_d;
@@ -121,7 +122,14 @@ struct lsspa_ctx {
   DevBuf<double> Cred;
   bool reduce_open = false;
   int64_t hist_cap = 0, hist_n = 0;
-  int ldh() const { return ((p + 127) / 128) * 128; }
+  // player map (lsspa_set_players): groups of columns are the players; g_players = 0: none, the columns are
+  PlayerMap players;
+  int g_players = 0;
+  DevBuf<int32_t> pl_off, pl_cols;   // the map's CSR on the device
+  // dimension of a SAMPLE -- lift vector handed to collect, running statistics, history, estimator, results.  The
+  // factorisation side (orderings the kernels see, work matrices, the un-folded lift buffer) keeps p.
+  int sd() const { return g_players ? g_players : p; }
+  int ldh() const { return ((sd() + 127) / 128) * 128; }
   // running form of the estimator (lsspa_error_running_*): D = Xi L, s = Xi 1 of the samples folded in so far; the
   // history buffer then only stages the lift vectors between a collect and the next lsspa_error_advance
   bool run_on = false;
@@ -316,6 +324,7 @@ void free_lane_workspace(Lane& L) {
   dev_free(L.row_flags);
   dev_free(L.perms_d);
   dev_free(L.lifts);
+  dev_free(L.folded);
 }
 
 void free_workspace(lsspa_ctx* ctx) {
@@ -349,6 +358,7 @@ int set_dims(lsspa_ctx* ctx, int p, int m, int tri) {
   ctx->have_problem = false;
   ctx->r2_valid = false;
   ctx->src_f32_valid = false;
+  ctx->g_players = 0;   // a player map belongs to the problem it was set on
   // a workspace sized for another shape is released now: kept, it would count as unavailable memory when the
   // new one is sized from hipMemGetInfo (and its layout depends on p_pad / m_pad / tri anyway)
   for (Lane& L : ctx->lanes) L.in_flight = false;   // a batch launched on the previous problem is void
@@ -405,7 +415,7 @@ int stats_reset(lsspa_ctx* ctx) {
   return LSSPA_OK;
 }
 
-// append rows [rows][p] (device or host, row stride p) to the history
+// append rows [rows][sd] (device or host, row stride sd = the sample dimension) to the history
 int hist_append(lsspa_ctx* ctx, const double* src, int64_t rows, hipMemcpyKind kind) {
   const size_t ldh = ctx->ldh();
   if (ctx->hist_n + rows > ctx->hist_cap) {
@@ -423,8 +433,8 @@ int hist_append(lsspa_ctx* ctx, const double* src, int64_t rows, hipMemcpyKind k
     ctx->hist = bigger;
     ctx->hist_cap = cap;
   }
-  HIPCHK(hipMemcpy2DAsync(ctx->hist.ptr + (size_t)ctx->hist_n * ldh, ldh * 8, src, (size_t)ctx->p * 8,
-                          (size_t)ctx->p * 8, (size_t)rows, kind, ctx->stream));
+  HIPCHK(hipMemcpy2DAsync(ctx->hist.ptr + (size_t)ctx->hist_n * ldh, ldh * 8, src, (size_t)ctx->sd() * 8,
+                          (size_t)ctx->sd() * 8, (size_t)rows, kind, ctx->stream));
   ctx->hist_n += rows;
   return LSSPA_OK;
 }
@@ -501,6 +511,25 @@ int ensure_workspace(lsspa_ctx* ctx, Lane& L, int want_ord, int want_samples) {
     L.cap_samples = want_samples;
   }
   return LSSPA_OK;
+}
+
+// player map set: the lane's [samples][g] buffer of group lifts (the fold's output)
+int ensure_folded(lsspa_ctx* ctx, Lane& L, int want_samples) {
+  const size_t need = (size_t)want_samples * ctx->g_players;
+  if (L.folded.ptr && L.folded.count >= need) return LSSPA_OK;
+  TRY(sync_all(ctx));  // work in flight still uses the old buffer
+  return dev_alloc(ctx, L.folded, need);
+}
+
+// what a launched batch hands to collect: its lift vectors [B][p], or -- player map set -- its group lifts [B][g]
+static inline const double* lane_out(const lsspa_ctx* ctx, const Lane& L) {
+  return ctx->g_players ? L.folded.ptr : L.lifts.ptr;
+}
+// player map with a baseline: an antithetical sample's two orderings run as two unpaired orderings (rows 2 s and
+// 2 s + 1 of the lift buffer, averaged by the fold).  The kernels' paired form takes ordering 2 s + 1 to be ordering 2 s
+// read backwards, which expands the reversed group ordering only when no baseline has to stay in front.
+static inline bool split_pairs(const lsspa_ctx* ctx, int per_sample) {
+  return ctx->g_players && per_sample == 2 && !ctx->players.base.empty();
 }
 
 int ensure_pinned(lsspa_ctx* ctx, Lane& L, size_t count) {
@@ -747,10 +776,16 @@ int run_orderings(lsspa_ctx* ctx, Lane& L, int n_ord, int per_sample, int s_off)
   return LSSPA_OK;
 }
 
-// Stage `count` orderings (with their reverses when per_sample == 2) on lane L and run them.
+// Stage `count` orderings (with their reverses when per_sample == 2) on lane L and run them.  Player map set: perms
+// are [n_samples][g] orderings of the groups, expanded to column orderings as they are staged, and the batch's last
+// launch folds its lift vectors into group lifts (lane_out).
 int stage_and_run(lsspa_ctx* ctx, Lane& L, const int32_t* perms, int n_samples, int per_sample, int s_off) {
   const int p = ctx->p;
   const int n_ord = n_samples * per_sample;
+  const int grp = ctx->g_players;
+  const bool split = split_pairs(ctx, per_sample);
+  const int kper = split ? 1 : per_sample;          // orderings per sample as the kernels see them
+  const int row_off = split ? 2 * s_off : s_off;    // the batch's first row of the lane's lift buffer
   const hipStream_t st = ctx->lane_stream(L);
   const int turn = L.perms_turn;
   L.perms_turn ^= 1;
@@ -766,8 +801,20 @@ int stage_and_run(lsspa_ctx* ctx, Lane& L, const int32_t* perms, int n_samples, 
   int32_t* hp = L.perms_h[turn];
   // the small-problem kernels read a sample's reverse ordering out of the forward one themselves: half the staging, half
   // the upload (the host's share of a 2048-ordering group at p = 100 was longer than the GPU's)
-  L.perms_fwd_only = per_sample == 2 && small_path(ctx);
-  if (L.perms_fwd_only || per_sample == 1) {
+  L.perms_fwd_only = kper == 2 && small_path(ctx);
+  if (grp) {
+    const int stride = L.perms_fwd_only ? 1 : per_sample;
+    for (int s = 0; s < n_samples; ++s) {
+      const int32_t* src = perms + (size_t)s * grp;
+      int32_t* d0 = hp + (size_t)s * stride * p;
+      expand_group_row(ctx->players, src, 0, d0);
+      if (stride == 2) {
+        int32_t* d1 = d0 + p;
+        if (split) expand_group_row(ctx->players, src, 1, d1);
+        else for (int j = 0; j < p; ++j) d1[j] = d0[p - 1 - j];
+      }
+    }
+  } else if (L.perms_fwd_only || per_sample == 1) {
     std::memcpy(hp, perms, sizeof(int32_t) * (size_t)n_samples * p);   // validated by the caller
   } else {
     for (int s = 0; s < n_samples; ++s) {
@@ -778,6 +825,15 @@ int stage_and_run(lsspa_ctx* ctx, Lane& L, const int32_t* perms, int n_samples, 
       for (int j = 0; j < p; ++j) d1[j] = src[p - 1 - j];
     }
   }
+  // the kernels of the batch, then (player map) the fold of rows [row_off ..) into group lifts [s_off ..)
+  auto run = [&]() -> int {
+    TRY(run_orderings(ctx, L, n_ord, kper, row_off));
+    if (!grp) return LSSPA_OK;
+    ProfScope ps(ctx, LSSPA_K_LIFT, st);
+    HIPCHK(launch_fold_players(L.lifts.ptr + (size_t)row_off * p, p, split ? 2 : 1, ctx->pl_off.ptr, ctx->pl_cols.ptr, grp,
+                               n_samples, L.folded.ptr + (size_t)s_off * grp, st));
+    return LSSPA_OK;
+  };
   int32_t* dp = L.perms_d.ptr + (size_t)turn * L.cap_ord * p;
   const size_t bytes = sizeof(int32_t) * (size_t)(L.perms_fwd_only ? n_samples : n_ord) * p;
   if (bytes <= ((size_t)256 << 10) || (ctx->n_lanes == 2 && bytes <= ((size_t)1 << 20))) {
@@ -792,7 +848,7 @@ int stage_and_run(lsspa_ctx* ctx, Lane& L, const int32_t* perms, int n_samples, 
     L.perms_busy[turn] = true;
     L.perms_cur = dp;
     L.perms_used_valid[turn] = false;    // stream order protects the device slot
-    return run_orderings(ctx, L, n_ord, per_sample, s_off);
+    return run();
   }
   if (!L.copy_stream) {
     HIPCHK(hipStreamCreateWithFlags(&L.copy_stream, hipStreamNonBlocking));
@@ -804,7 +860,7 @@ int stage_and_run(lsspa_ctx* ctx, Lane& L, const int32_t* perms, int n_samples, 
   L.perms_busy[turn] = true;
   HIPCHK(hipStreamWaitEvent(st, L.perms_ev[turn], 0));
   L.perms_cur = dp;
-  const int rc = run_orderings(ctx, L, n_ord, per_sample, s_off);
+  const int rc = run();
   if (rc != LSSPA_OK) return rc;
   HIPCHK(hipEventRecord(L.perms_used[turn], st));
   L.perms_used_valid[turn] = true;
@@ -822,7 +878,8 @@ int lift_launch(lsspa_ctx* ctx, const int32_t* perms, int B, int per, Lane** out
   // orderings per launch sequence: everything at once up to ~8 GB of workspace or 4096 orderings
   const size_t per_ord = bytes_per_ordering(ctx);
   const int want = (int)std::max<size_t>(2, std::min<size_t>(4096, ((size_t)8 << 30) / per_ord));
-  TRY(ensure_workspace(ctx, L, std::min(B * per, std::max(want, 512)), B));
+  TRY(ensure_workspace(ctx, L, std::min(B * per, std::max(want, 512)), split_pairs(ctx, per) ? 2 * B : B));
+  if (ctx->g_players) TRY(ensure_folded(ctx, L, B));
   const int sub = std::max(1, L.cap_ord / per);
   TRY(ensure_pinned(ctx, L, (size_t)std::min(sub, (int)B) * per * p));
   const hipStream_t st = ctx->lane_stream(L);
@@ -843,7 +900,7 @@ int lift_launch(lsspa_ctx* ctx, const int32_t* perms, int B, int per, Lane** out
   }
   for (int s0 = 0; s0 < B; s0 += sub) {
     const int ns = std::min(sub, B - s0);
-    TRY(stage_and_run(ctx, L, perms + (size_t)s0 * p, ns, per, s0));
+    TRY(stage_and_run(ctx, L, perms + (size_t)s0 * ctx->sd(), ns, per, s0));
   }
   if (ctx->n_lanes == 2) {
     if (L.mid_armed) {   // one-level path or a single panel: no mid point was met
@@ -888,8 +945,8 @@ int keep_lifts(lsspa_ctx* ctx, const double* src, int count, const int64_t* ids 
     const int n_pad = ((count + KCH - 1) / KCH) * KCH;
     TRY(dev_alloc(ctx, ctx->xi_d, (size_t)ERR_DRAWS * n_pad));
     ProfScope ps(ctx, LSSPA_K_ERROR);
-    HIPCHK(launch_error_accumulate(ctx->run_seed, ids[0], ids[1], count, n_pad, ctx->xi_d.ptr, src, ctx->p, 1,
-                                   ctx->ldh(), ctx->p, ctx->Dacc.ptr, ctx->sacc.ptr, ctx->stream));
+    HIPCHK(launch_error_accumulate(ctx->run_seed, ids[0], ids[1], count, n_pad, ctx->xi_d.ptr, src, ctx->sd(), 1,
+                                   ctx->ldh(), ctx->sd(), ctx->Dacc.ptr, ctx->sacc.ptr, ctx->stream));
     return LSSPA_OK;
   }
   if (ctx->hist_cap > 0) TRY(hist_append(ctx, src, count, hipMemcpyDeviceToDevice));
@@ -901,12 +958,12 @@ int lane_taken(lsspa_ctx* ctx, Lane& L, int upto);
 int lift_collect(lsspa_ctx* ctx, Lane& L, int first, int count, double* lifts_out, int accumulate,
                  const int64_t* est_ids = nullptr) {
   if (!L.in_flight) return ctx->fail(LSSPA_ERR_STATE, "no launched batch on this lane");
-  const int p = ctx->p;
+  const int p = ctx->sd();   // a sample's dimension: g with a player map
   if (count <= 0) count = L.B - first;
   if (first != L.taken || count < 1 || first + count > L.B)
     return ctx->fail(LSSPA_ERR_ARG, "parts of a launched batch are collected front to back, without gaps");
   TRY(check_accumulate(ctx, accumulate));   // before the stream is touched: a refused call leaves the lane as it was
-  const double* src = L.lifts.ptr + (size_t)first * p;
+  const double* src = lane_out(ctx, L) + (size_t)first * p;
   if (ctx->n_lanes == 2 && first == 0) HIPCHK(hipStreamWaitEvent(ctx->stream, L.ev_done, 0));
   if (accumulate == 2 && stats_small_fusable(count, p)) {
     // single GPU, small p: moments and merge in ONE launch; the advanced mean and n land in the other halves of the
@@ -945,7 +1002,7 @@ bool chunks_fusable(const lsspa_ctx* ctx, const Lane& L, int n_chunks, const int
   if (first[0] != L.taken) return false;
   int next = first[0];
   for (int c = 0; c < n_chunks; ++c) {
-    if (first[c] != next || !stats_small_fusable(count[c], ctx->p)) return false;
+    if (first[c] != next || !stats_small_fusable(count[c], ctx->sd())) return false;
     next += count[c];
   }
   return next <= L.B;
@@ -953,7 +1010,7 @@ bool chunks_fusable(const lsspa_ctx* ctx, const Lane& L, int n_chunks, const int
 
 int collect_chunks_small(lsspa_ctx* ctx, Lane& L, int n_chunks, const int32_t* first, const int32_t* count,
                                 bool snap) {
-  const int p = ctx->p;
+  const int p = ctx->sd();
   if (ctx->n_lanes == 2 && first[0] == 0) HIPCHK(hipStreamWaitEvent(ctx->stream, L.ev_done, 0));
   StatsChunks ch;
   ch.n = n_chunks;
@@ -967,7 +1024,7 @@ int collect_chunks_small(lsspa_ctx* ctx, Lane& L, int n_chunks, const int32_t* f
   }
   {
     ProfScope ps(ctx, LSSPA_K_STATS);
-    HIPCHK(launch_stats_small_multi(L.lifts.ptr, ctx->mean.ptr, ctx->state_n.ptr, ctx->mean_alt.ptr, ctx->state_alt.ptr,
+    HIPCHK(launch_stats_small_multi(lane_out(ctx, L), ctx->mean.ptr, ctx->state_n.ptr, ctx->mean_alt.ptr, ctx->state_alt.ptr,
                                     ctx->M2.ptr, ch, p, snap ? ctx->mean_snap.ptr : nullptr,
                                     snap ? ctx->n_snap.ptr : nullptr, ctx->stream));
   }
@@ -1102,6 +1159,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   dev_free(ctx->Gf); dev_free(ctx->Hf);
   dev_free(ctx->sub_Hh); dev_free(ctx->sub_w); dev_free(ctx->sub_part); dev_free(ctx->sub_out);
   dev_free(ctx->sub_vals); dev_free(ctx->sub_masks); dev_free(ctx->sub_info);
+  dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   free_workspace(ctx);
   for (Lane& L : ctx->lanes) {
     if (L.copy_stream) {
@@ -1568,7 +1626,10 @@ static int factor_identity(lsspa_ctx* ctx, const int32_t* perm_or_null) {
   for (int j = 0; j < p; ++j) id[j] = perm_or_null ? perm_or_null[j] : j;
   TRY(sync_all(ctx));                       // the conversion above ran on the context's stream
   ctx->general_path_once = true;            // the callers read L back from the work matrices
+  const int players_kept = ctx->g_players;  // ... and the lifts of a COLUMN ordering: a player map sits this out
+  ctx->g_players = 0;
   const int rc = stage_and_run(ctx, L, id.data(), 1, 1, 0);
+  ctx->g_players = players_kept;
   ctx->general_path_once = false;
   if (rc != LSSPA_OK) return rc;
   TRY(sync_all(ctx));                       // callers read results with blocking copies
@@ -1658,11 +1719,11 @@ int lsspa_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int32_t B, int32_t an
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   if (!perms || B < 1) return ctx->fail(LSSPA_ERR_ARG, "perms / B");
   HIPCHK(hipSetDevice(ctx->device));
-  const int p = ctx->p;
   const int per = antithetical ? 2 : 1;
   // validate before anything is launched: a repeated index would make a permuted Gram singular
-  if (!all_permutations(perms, B, p, ctx->perm_mark))
-    return ctx->fail(LSSPA_ERR_ARG, "perms: a row is not a permutation of 0..p-1");
+  if (!all_permutations(perms, B, ctx->sd(), ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, ctx->g_players ? "perms: a row is not a permutation of the groups 0..g-1"
+                                                   : "perms: a row is not a permutation of 0..p-1");
   TRY(check_accumulate(ctx, accumulate));   // nothing is launched for a call that cannot be collected
   Lane* L = nullptr;
   TRY(lift_launch(ctx, perms, B, per, &L));
@@ -1686,8 +1747,9 @@ int lsspa_lift_launch(lsspa_ctx* ctx, const int32_t* perms, int32_t B, int32_t a
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   if (!perms || B < 1 || !ticket) return ctx->fail(LSSPA_ERR_ARG, "perms / B / ticket");
   HIPCHK(hipSetDevice(ctx->device));
-  if (!all_permutations(perms, B, ctx->p, ctx->perm_mark))
-    return ctx->fail(LSSPA_ERR_ARG, "perms: a row is not a permutation of 0..p-1");
+  if (!all_permutations(perms, B, ctx->sd(), ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, ctx->g_players ? "perms: a row is not a permutation of the groups 0..g-1"
+                                                   : "perms: a row is not a permutation of 0..p-1");
   Lane* L = nullptr;
   TRY(lift_launch(ctx, perms, B, antithetical ? 2 : 1, &L));
   *ticket = (int32_t)(L - ctx->lanes);
@@ -1726,7 +1788,7 @@ int lsspa_lift_collect_chunks(lsspa_ctx* ctx, int32_t ticket, int32_t first, int
     if (chunks_fusable(ctx, L, n_chunks, f, k)) {
       TRY(check_accumulate(ctx, 2));
       TRY(collect_chunks_small(ctx, L, n_chunks, f, k, false));
-      TRY(keep_lifts(ctx, L.lifts.ptr + (size_t)first * ctx->p, n_chunks * chunk, nullptr));
+      TRY(keep_lifts(ctx, lane_out(ctx, L) + (size_t)first * ctx->sd(), n_chunks * chunk, nullptr));
       return lane_taken(ctx, L, first + n_chunks * chunk);
     }
   }
@@ -1751,6 +1813,63 @@ int lsspa_lift_discard(lsspa_ctx* ctx, int32_t ticket) try {
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
+}
+
+// Groups of columns as the players of the sampling path.  The map changes the dimension of everything a sample is
+// (sd()): the statistics start over, and the history and the estimator -- whose row stride follows the dimension --
+// have to be enabled again, as after a new problem.
+int lsspa_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
+  HIPCHK(hipSetDevice(ctx->device));
+  for (const Lane& L : ctx->lanes)
+    if (L.in_flight) return ctx->fail(LSSPA_ERR_STATE, "a launched batch is still to be collected");
+  if (!labels && g != 0) return ctx->fail(LSSPA_ERR_ARG, "labels is NULL (clear the map with labels = NULL, g = 0)");
+  PlayerMap map;
+  if (labels) {
+    const char* why = player_map_build(labels, ctx->p, g, map);
+    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
+  }
+  TRY(sync_all(ctx));
+  if (labels) {
+    TRY(dev_alloc(ctx, ctx->pl_off, (size_t)ctx->p + 1));
+    TRY(dev_alloc(ctx, ctx->pl_cols, (size_t)ctx->p));
+    HIPCHK(hipMemcpy(ctx->pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
+    ctx->players = std::move(map);
+    ctx->g_players = g;
+  } else {
+    ctx->g_players = 0;
+  }
+  ctx->hist_cap = 0;
+  ctx->hist_n = 0;
+  ctx->run_on = false;
+  return stats_reset(ctx);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_expand_groups(const int32_t* labels, int32_t p, int32_t g, const int32_t* group_perms, int32_t B,
+                              int32_t antithetical, int32_t* out) try {
+  if (!labels || !group_perms || !out || p < 1 || B < 1) return LSSPA_ERR_ARG;
+  PlayerMap map;
+  if (player_map_build(labels, p, g, map)) return LSSPA_ERR_ARG;
+  std::vector<int32_t> mark;
+  if (!all_permutations(group_perms, B, g, mark)) return LSSPA_ERR_ARG;
+  const int per = antithetical ? 2 : 1;
+  for (int s = 0; s < B; ++s) {
+    int32_t* d0 = out + (size_t)s * per * p;
+    expand_group_row(map, group_perms + (size_t)s * g, 0, d0);
+    if (per == 2) {
+      // as stage_and_run lays a pair out: with a baseline the expansion of the reversed group ordering (run unpaired),
+      // without one the forward row read backwards (the kernels' paired form)
+      if (!map.base.empty()) expand_group_row(map, group_perms + (size_t)s * g, 1, d0 + p);
+      else for (int j = 0; j < p; ++j) d0[p + j] = d0[p - 1 - j];
+    }
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(nullptr);
 }
 
 int lsspa_get_info(lsspa_ctx* ctx, int32_t* info) try {
@@ -1803,7 +1922,7 @@ int lsspa_stats_pending(lsspa_ctx* ctx, void** device_ptr, int64_t* count) try {
   if (!ctx || !device_ptr || !count) return LSSPA_ERR_ARG;
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   *device_ptr = ctx->pend.ptr;
-  *count = (int64_t)1 + ctx->p + (int64_t)ctx->p * ctx->p;
+  *count = (int64_t)1 + ctx->sd() + (int64_t)ctx->sd() * ctx->sd();
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -1816,7 +1935,7 @@ int lsspa_stats_merge(lsspa_ctx* ctx) try {
   bool cleared = false;
   {
     ProfScope ps(ctx, LSSPA_K_STATS);
-    HIPCHK(launch_stats_merge(ctx->pend.ptr, ctx->state_n.ptr, ctx->mean.ptr, ctx->M2.ptr, ctx->p, ctx->stream,
+    HIPCHK(launch_stats_merge(ctx->pend.ptr, ctx->state_n.ptr, ctx->mean.ptr, ctx->M2.ptr, ctx->sd(), ctx->stream,
                               &cleared));
   }
   // an empty pending buffer (n_b = 0) is what a rank with no samples contributes
@@ -1833,7 +1952,7 @@ int lsspa_stats_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* cov_biased
   if (!ctx) return LSSPA_ERR_ARG;
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t p = ctx->p;
+  const size_t p = ctx->sd();
   double nd = 0.0;
   HIPCHK(hipMemcpyAsync(&nd, ctx->state_n.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
   if (mean) HIPCHK(hipMemcpyAsync(mean, ctx->mean.ptr, p * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1853,7 +1972,7 @@ int lsspa_stats_set(lsspa_ctx* ctx, int64_t n, const double* mean, const double*
   if (!ctx || !mean || !cov_biased || n < 0) return LSSPA_ERR_ARG;
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t p = ctx->p;
+  const size_t p = ctx->sd();
   std::vector<double> m2(p * p);
   for (size_t i = 0; i < p * p; ++i) m2[i] = cov_biased[i] * (double)n;
   double st[8] = {(double)n, 0, 0, 0, 0, 0, 0, 0};
@@ -1902,7 +2021,7 @@ int lsspa_history_get(lsspa_ctx* ctx, int64_t* count, double* lifts) try {
   *count = ctx->hist_n;
   if (lifts && ctx->hist_n > 0) {
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpy2DAsync(lifts, (size_t)ctx->p * 8, ctx->hist.ptr, (size_t)ctx->ldh() * 8, (size_t)ctx->p * 8,
+    HIPCHK(hipMemcpy2DAsync(lifts, (size_t)ctx->sd() * 8, ctx->hist.ptr, (size_t)ctx->ldh() * 8, (size_t)ctx->sd() * 8,
                             (size_t)ctx->hist_n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
@@ -1949,7 +2068,7 @@ int lsspa_error_draws(lsspa_ctx* ctx, const double* xi, int64_t ld_xi, int64_t n
   const double scale = 1.0 / sqrt(nt * (nt - 1.0));   // inf for n_total = 1, as numpy's division gives
   ProfScope ps(ctx, LSSPA_K_ERROR);
   HIPCHK(launch_error_draws(ctx->xi_d.ptr, (int)n_pad, ctx->hist.ptr, ldh, (int)n_pad, ctx->mean.ptr, scale,
-                            ctx->p, ctx->draws.ptr, ldh, ctx->stream));
+                            ctx->sd(), ctx->draws.ptr, ldh, ctx->stream));
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -1970,7 +2089,7 @@ int lsspa_error_quantiles(lsspa_ctx* ctx, double* feature_errors, double* overal
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   if (ctx->hist_cap == 0) return ctx->fail(LSSPA_ERR_STATE, "history is not enabled");
   HIPCHK(hipSetDevice(ctx->device));
-  const int p = ctx->p;
+  const int p = ctx->sd();
   {
     ProfScope ps(ctx, LSSPA_K_ERROR);
     HIPCHK(launch_error_quantiles(ctx->draws.ptr, ctx->ldh(), p, ctx->err_out.ptr + 2 * p + 2, ctx->err_out.ptr,
@@ -2037,7 +2156,7 @@ int lsspa_error_advance(lsspa_ctx* ctx, int64_t first_id, int64_t stride) try {
   ProfScope ps(ctx, LSSPA_K_ERROR);
   // rows cnt .. n_pad of the staging hold older chunks' (finite) lift vectors: they meet the zero columns of Xi
   HIPCHK(launch_error_accumulate(ctx->run_seed, first_id, stride, (int)cnt, (int)n_pad, ctx->xi_d.ptr, ctx->hist.ptr,
-                                 ctx->ldh(), 0, ctx->ldh(), ctx->p, ctx->Dacc.ptr, ctx->sacc.ptr, ctx->stream));
+                                 ctx->ldh(), 0, ctx->ldh(), ctx->sd(), ctx->Dacc.ptr, ctx->sacc.ptr, ctx->stream));
   ctx->hist_n = 0;
   return LSSPA_OK;
 } catch (...) {
@@ -2054,7 +2173,7 @@ int lsspa_error_running_draws(lsspa_ctx* ctx, int64_t n_total) try {
   const double nt = (double)n_total;
   const double scale = 1.0 / sqrt(nt * (nt - 1.0));   // inf for n_total = 1, as numpy's division gives
   ProfScope ps(ctx, LSSPA_K_ERROR);
-  HIPCHK(launch_error_running_draws(ctx->Dacc.ptr, ctx->sacc.ptr, ctx->mean.ptr, scale, ctx->p, ctx->ldh(),
+  HIPCHK(launch_error_running_draws(ctx->Dacc.ptr, ctx->sacc.ptr, ctx->mean.ptr, scale, ctx->sd(), ctx->ldh(),
                                     ctx->draws.ptr, ctx->stream));
   return LSSPA_OK;
 } catch (...) {
@@ -2084,7 +2203,7 @@ static int quantiles_enqueue(lsspa_ctx* ctx, int32_t slot, bool record) {
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   if (!ctx->run_on) return ctx->fail(LSSPA_ERR_STATE, "the running estimator is not enabled");
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t p = ctx->p;
+  const size_t p = ctx->sd();
   {
     ProfScope ps(ctx, LSSPA_K_ERROR);
     HIPCHK(launch_error_quantiles(ctx->draws.ptr, ctx->ldh(), (int)p, ctx->err_out.ptr + 2 * p + 2,
@@ -2108,7 +2227,7 @@ static int check_enqueue(lsspa_ctx* ctx, int64_t n_total, int32_t slot, bool rec
   if (ctx->hist_n != 0) return ctx->fail(LSSPA_ERR_STATE, "collected samples not yet folded in: call lsspa_error_advance");
   if (ctx->pend_dirty) return ctx->fail(LSSPA_ERR_STATE, "merge the pending batch first: the mean is stale");
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t p = ctx->p;
+  const size_t p = ctx->sd();
   const double nt = (double)n_total;
   const double scale = 1.0 / sqrt(nt * (nt - 1.0));
   {
@@ -2137,7 +2256,7 @@ int lsspa_error_result(lsspa_ctx* ctx, int32_t slot, int32_t wait, int32_t* read
     }
     HIPCHK(e);
   }
-  const size_t p = ctx->p;
+  const size_t p = ctx->sd();
   const double* src = ctx->res_h + (size_t)slot * (2 * p + 2);
   if (feature_errors) std::copy(src, src + p, feature_errors);
   if (overall_error) *overall_error = src[p];
@@ -2153,7 +2272,7 @@ int lsspa_error_state_get(lsspa_ctx* ctx, double* D, double* s) try {
   if (!ctx || !D || !s) return LSSPA_ERR_ARG;
   if (!ctx->run_on) return ctx->fail(LSSPA_ERR_STATE, "the running estimator is not enabled");
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipMemcpy2DAsync(D, (size_t)ctx->p * 8, ctx->Dacc.ptr, (size_t)ctx->ldh() * 8, (size_t)ctx->p * 8, ERR_DRAWS,
+  HIPCHK(hipMemcpy2DAsync(D, (size_t)ctx->sd() * 8, ctx->Dacc.ptr, (size_t)ctx->ldh() * 8, (size_t)ctx->sd() * 8, ERR_DRAWS,
                           hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemcpyAsync(s, ctx->sacc.ptr, (size_t)ERR_DRAWS * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2166,7 +2285,7 @@ int lsspa_error_state_set(lsspa_ctx* ctx, const double* D, const double* s) try 
   if (!ctx || !D || !s) return LSSPA_ERR_ARG;
   if (!ctx->run_on) return ctx->fail(LSSPA_ERR_STATE, "the running estimator is not enabled");
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipMemcpy2DAsync(ctx->Dacc.ptr, (size_t)ctx->ldh() * 8, D, (size_t)ctx->p * 8, (size_t)ctx->p * 8, ERR_DRAWS,
+  HIPCHK(hipMemcpy2DAsync(ctx->Dacc.ptr, (size_t)ctx->ldh() * 8, D, (size_t)ctx->sd() * 8, (size_t)ctx->sd() * 8, ERR_DRAWS,
                           hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->sacc.ptr, s, (size_t)ERR_DRAWS * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2260,7 +2379,7 @@ int lsspa_group_collect(lsspa_ctx* ctx, int32_t ticket, int32_t n_chunks, const 
     TRY(collect_chunks_small(ctx, Lg, n_chunks, first, count, true));
     {
       ProfScope ps(ctx, LSSPA_K_ERROR);
-      HIPCHK(launch_error_group(ctx->run_seed, stride, ch, ck, ctx->xi_d.ptr, Lg.lifts.ptr, ctx->p, (int)ld,
+      HIPCHK(launch_error_group(ctx->run_seed, stride, ch, ck, ctx->xi_d.ptr, lane_out(ctx, Lg), ctx->sd(), (int)ld,
                                 ctx->grp_P.ptr, ctx->grp_S.ptr, ctx->Dacc.ptr, ctx->sacc.ptr, ctx->grp_D.ptr,
                                 ctx->grp_s.ptr, ctx->mean_snap.ptr, ctx->n_snap.ptr, ctx->grp_norms.ptr, ctx->res_hd,
                                 ctx->stream));
@@ -2357,7 +2476,7 @@ int lsspa_stats_allreduce(lsspa_ctx* ctx) try {
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
   if (!ctx->comm) return ctx->fail(LSSPA_ERR_STATE, "no communicator: call lsspa_comm_init first");
   HIPCHK(hipSetDevice(ctx->device));
-  const int p = ctx->p;
+  const int p = ctx->sd();
   ProfScope ps(ctx, LSSPA_K_COMM);
   if (p < ctx->pack_from_p) return allreduce_buffer(ctx, ctx->pend.ptr, (size_t)1 + p + (size_t)p * p);
   const size_t cnt = (size_t)stats_packed_count(p);

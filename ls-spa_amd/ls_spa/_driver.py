@@ -305,9 +305,13 @@ def prepare_sampling(p, *, max_samples, batch_size, seed, perms, antithetical, m
 
 def run_estimator(engine, p, *, max_samples, batch_size, tolerance, seed, perms, antithetical,
                   return_attribution_history, method, error_estimator, comm=None, chunk_cap=None,
-                  checkpoint=None, prepared=None, lookahead=1, timings=None, defer=None):
+                  checkpoint=None, prepared=None, lookahead=1, timings=None, defer=None, cost_p=None):
     """The sampling loop on an engine whose problem is already loaded.  Returns
     (attribution, attribution_errors, overall_error, error_history, attribution_history, n).
+
+    p is the dimension of a sample.  With groups of columns as the players (ls_spa_groups: the engine carries a player
+    map) that is the number of groups g, and cost_p is the number of columns: what an ordering costs, hence the sizes of
+    the automatic look-ahead groups and the decision to defer checks, follows the columns.
 
     checkpoint: path of a state file.  Written after every error check (sample count, running mean and
     covariance, generator state, error history, the lift history the thin-form estimators need); if it
@@ -330,7 +334,7 @@ def run_estimator(engine, p, *, max_samples, batch_size, tolerance, seed, perms,
                               tolerance=tolerance, seed=seed, return_attribution_history=return_attribution_history,
                               method=method, error_estimator=error_estimator, chunk_cap=chunk_cap,
                               checkpoint=checkpoint, lookahead=lookahead, timings=timings, defer=defer,
-                              t_loop0=t_loop0)
+                              t_loop0=t_loop0, cost_p=p if cost_p is None else int(cost_p))
     finally:
         if hasattr(source, "close"):
             source.close()
@@ -338,7 +342,7 @@ def run_estimator(engine, p, *, max_samples, batch_size, tolerance, seed, perms,
 
 def _run_estimator(engine, p, comm, rng, source, batch_size, antithetical, max_samples, never_stop, *, tolerance, seed,
                    return_attribution_history, method, error_estimator, chunk_cap, checkpoint, lookahead, timings,
-                   defer, t_loop0):
+                   defer, t_loop0, cost_p):
     import time as _time
     t_sampler = t_estimator = 0.0
 
@@ -409,7 +413,7 @@ def _run_estimator(engine, p, comm, rng, source, batch_size, antithetical, max_s
     # current one has been taken up, whatever its checks will say.
     ramp = None
     if lookahead == "auto":
-        lookahead = auto_lookahead(p, -(-int(batch_size) // comm.world))
+        lookahead = auto_lookahead(cost_p, -(-int(batch_size) // comm.world))
         # the automatic groups grow: 1, 2, 4, ... chunks up to the size above.  A run that stops at one of its first checks
         # -- the usual run to a tolerance -- then has its answer after about as many chunks as it needed, not after a
         # whole group (its kernels are one launch: none of its checks is known before all of its chunks have run); a long
@@ -432,7 +436,7 @@ def _run_estimator(engine, p, comm, rng, source, batch_size, antithetical, max_s
         per_rank = -(-min(int(batch_size), max_samples) // comm.world) * (2 if antithetical else 1)
         # a chunk's kernels, at 40 TFLOP/s, under 50 ms; the chunks of a look-ahead group are checked without waiting
         # in between (their kernels were one launch)
-        defer = min(max(1, group), engine.RESULT_SLOTS - 2) if (can_defer and per_rank * float(p) ** 3 / 4e13 < 0.05) else 0
+        defer = min(max(1, group), engine.RESULT_SLOTS - 2) if (can_defer and per_rank * float(cost_p) ** 3 / 4e13 < 0.05) else 0
     defer = int(defer) if can_defer else 0
     if not 0 <= defer < engine.RESULT_SLOTS - 1 if on_device else False:
         raise ValueError("defer must be between 0 and the number of result slots - 2")
@@ -688,7 +692,7 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
            tolerance=1e-2, seed=42, perms=None, antithetical=True, return_attribution_history=False, *,
            method=None, num_batches=None, return_history=None, device=0, error_estimator=None,
            precision="float64", row_sharded=False, checkpoint=None, comm=None, lookahead=None, lanes="auto",
-           groups=None, _engine=None, _comm=None, _timings=None, _defer=None):
+           groups=None, _engine=None, _comm=None, _timings=None, _defer=None, _players=None):
     """Estimates the Shapley attribution of the out-of-sample R^2 of a least-squares fit.
 
     Positional parameters, defaults and behaviour follow cvxgrp/ls-spa
@@ -717,7 +721,7 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
         takes 1.5 ms at g = 12 / p = 64, 26 ms at g = 20 / p = 60, 0.21 s at g = 24 / p = 64 and 2.7 s at g = 28 /
         p = 56; it grows 16-fold per four groups, so expect about a minute at g = 32 (projected, not measured).
         With any other method (None and perms= too) groups raises ValueError: grouped attribution exists for the
-        exact path only.
+        exact path only.  ``ls_spa_groups`` is the sampled counterpart, for any number of groups and columns.
     num_batches:  if given, ``max_samples = batch_size * num_batches`` (README dialect).
     return_history:  alias of ``return_attribution_history``.
     device:  GPU index.
@@ -767,6 +771,9 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
     if y_train.ndim != 1 or y_test.ndim != 1:
         raise ValueError("y_train and y_test must be one-dimensional")  # reference: concatenate error, :312
     p = X_train.shape[1]
+    # _players = (labels, g), ls_spa_groups only: the players of the game are g groups of columns.  Orderings, statistics,
+    # estimator and results then have dimension g (`dim`); what follows the cost of an ordering keeps p.
+    dim = p if _players is None else int(_players[1])
     if return_history is not None:
         return_attribution_history = bool(return_history)
     if num_batches is not None:
@@ -800,7 +807,7 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
     # under the engine's creation and the data reduction instead of in front of the sampling loop.
     t0 = _time.perf_counter()
     share = dict(rank=comm.rank, world=comm.world) if comm is not None else {}
-    prepared = prepare_sampling(p, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
+    prepared = prepare_sampling(dim, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
                                 antithetical=antithetical, method=method, **share)
     t0 = lap("sampler_start", t0)
     ok = False
@@ -845,9 +852,11 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
         t0 = _time.perf_counter()
         theta, r_squared, info = engine.full_fit()
         t0 = lap("final_fit", t0)
+        if _players is not None:
+            engine.set_players(_players[0])      # after the full fit: that one is about the columns
         def sampling_run(prep):
             out = run_estimator(
-                engine, p, max_samples=max_samples, batch_size=batch_size, tolerance=tolerance, seed=seed,
+                engine, dim, cost_p=p, max_samples=max_samples, batch_size=batch_size, tolerance=tolerance, seed=seed,
                 perms=perms, antithetical=antithetical, return_attribution_history=return_attribution_history,
                 method=method, error_estimator=error_estimator, comm=comm, checkpoint=checkpoint, prepared=prep,
                 lookahead=lookahead, timings=tm, defer=_defer)
@@ -867,7 +876,7 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
                           "kernel of its own", RuntimeWarning, stacklevel=2)
             engine.set_flags(512)
             prepared[1].close() if hasattr(prepared[1], "close") else None
-            prepared = prepare_sampling(p, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
+            prepared = prepare_sampling(dim, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
                                         antithetical=antithetical, method=method, **share)
             (attribution, feat_err, total_err, err_hist, history, _), bits = sampling_run(prepared)
             fault = bool(bits & 12) and not bits & 1
@@ -888,6 +897,8 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
         t0 = _time.perf_counter()
         if prepared is not None and hasattr(prepared[1], "close"):
             prepared[1].close()      # the sampler's helper thread (already ended by a run that got as far as its loop)
+        if _players is not None and ok and engine is not None and hasattr(engine, "clear_players"):
+            engine.clear_players()     # the caller's engine too: a player map never outlives the call that set it
         if owns and engine is not None:
             try:
                 if comm is not None and hasattr(comm, "close"):
@@ -911,9 +922,10 @@ GROUPS_MAX_G = 32      # include/lsspa.h, lsspa_groups_shapley
 GROUPS_MAX_P = 64
 
 
-def group_labels(groups, p):
-    """(labels as int32, g) of ls_spa(groups=): a label per column, -1 the baseline, 0 .. g-1 the groups, none of them
-    empty.  ValueError names what is wrong."""
+def group_labels(groups, p, max_groups=GROUPS_MAX_G):
+    """(labels as int32, g) of ls_spa(groups=) and ls_spa_groups: a label per column, -1 the baseline, 0 .. g-1 the
+    groups, none of them empty.  max_groups: the enumeration's limit (None for the sampled methods, whose only limit is
+    g <= p, which labels of length p cannot break).  ValueError names what is wrong."""
     labels = np.asarray(groups)
     if labels.ndim != 1 or len(labels) != p:
         raise ValueError(f"groups must have one label per column: length p = {p}, got shape {labels.shape}")
@@ -925,8 +937,8 @@ def group_labels(groups, p):
     g = int(labels.max()) + 1
     if g < 1:
         raise ValueError("groups names no group at all (every label is -1): there is nothing to attribute to")
-    if g > GROUPS_MAX_G:
-        raise ValueError(f"grouped attribution enumerates all 2^g group subsets and takes at most g = {GROUPS_MAX_G} "
+    if max_groups is not None and g > max_groups:
+        raise ValueError(f"grouped attribution enumerates all 2^g group subsets and takes at most g = {max_groups} "
                          f"groups (groups= names {g})")
     missing = np.setdiff1d(np.arange(g), labels)
     if len(missing):
@@ -997,6 +1009,72 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
     return ShapleyResults(attribution=phi, theta=theta, overall_error=0.0,
                           attribution_errors=np.zeros(p if labels is None else n_players),
                           r_squared=r_squared, error_history=np.zeros(0), attribution_history=None)
+
+
+GROUPS_AUTO_MAX_G = 20     # ls_spa_groups(method='auto'): the enumeration up to here (26 ms at g = 20, README.md)
+
+
+def ls_spa_groups(X_train, X_test, y_train, y_test, groups, reg=0., max_samples=2 ** 13, batch_size=2 ** 8,
+                  tolerance=1e-2, seed=42, perms=None, antithetical=True, return_attribution_history=False, *,
+                  method="auto", num_batches=None, return_history=None, device=0, error_estimator=None,
+                  precision="float64", lookahead=None, lanes="auto", row_sharded=False, comm=None, checkpoint=None,
+                  _engine=None, _timings=None, _defer=None):
+    """Shapley attribution of the out-of-sample R^2 over GROUPS of columns, for any number of groups and columns.
+
+    The players of the game are the groups that ``groups`` names: one integer label per column, k in 0 .. g-1 puts the
+    column into group k (every group needs a column), -1 into the baseline -- the columns of every model (an intercept,
+    controls), which get no attribution.  u(S) is the R^2 of the baseline plus the columns of the groups in S, and the
+    result's ``attribution`` (length g) are its Shapley values: they sum to ``r_squared`` minus the R^2 of the baseline
+    alone and are not per-column attributions summed over a group.  ``theta`` (length p) and ``r_squared`` are those of
+    the full fit.  Limits: 1 <= g <= p and the engine's p <= 32767.
+
+    The Shapley value of a group is the mean over orderings of the GROUPS of the summed lifts of its columns, when every
+    group ordering is expanded to a column ordering with the baseline first and each group's columns contiguous.  So a
+    sample is an ordinary ordering through the engine's kernels, folded on the device from p lifts to g, and the sampling
+    loop of ``ls_spa`` -- statistics, error estimate, stop rule, history -- runs in dimension g.
+
+    Everything not named here is as in ``ls_spa``, with g in place of p wherever the dimension of a sample decides
+    (the error estimate needs g >= 9, ``attribution_errors`` has length g, ``attribution_history`` is n x g); the sizes
+    of the automatic look-ahead groups stay keyed on p, the cost of an ordering.
+
+    method:  'auto' (default): 'subsets' when g <= 20 and p <= 64 (exact, and cheaper than any sampling run), else
+        'argsort'.  'subsets': the exact enumeration, ``ls_spa(method='subsets', groups=groups)`` unchanged (g <= 32,
+        p <= 64, the same errors).  'random', 'argsort', 'permutohedron': orderings of the g groups from the sources
+        ``ls_spa`` uses for columns.  'exact': all g! group orderings through the sampling path (g up to 8 or 9).
+        None: the reference's rule with g for p (all orderings below g = 9, else 'random').
+    perms:  an iterable of group orderings, each a permutation of 0 .. g-1 (method must be left at 'auto' or None).
+    antithetical:  a sample is a group ordering and its reverse -- the baseline first, then the groups in reversed
+        order -- and its lift vector the mean of the two.
+    error_estimator, precision, lookahead, lanes:  as in ``ls_spa``, same defaults per method.
+    comm, checkpoint, row_sharded:  not supported here (several ranks and resuming are out of this function's scope):
+        anything but None / False raises a ValueError that names the option."""
+    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
+    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
+    validate_data(X_train, X_test, y_train, y_test)
+    p = X_train.shape[1]
+    if comm is not None:
+        raise ValueError("ls_spa_groups does not take comm= (several ranks): grouped sampling runs on one GPU")
+    if checkpoint is not None:
+        raise ValueError("ls_spa_groups does not take checkpoint=: grouped sampling cannot be resumed")
+    if row_sharded:
+        raise ValueError("ls_spa_groups does not take row_sharded=: it needs comm=, which is not supported here")
+    if method == "auto":
+        if perms is not None:
+            method = None
+        else:
+            _, g_seen = group_labels(groups, p, max_groups=None)
+            method = "subsets" if (g_seen <= GROUPS_AUTO_MAX_G and p <= GROUPS_MAX_P) else "argsort"
+    if method == "subsets":
+        return ls_spa(X_train, X_test, y_train, y_test, reg, perms=perms, method="subsets", groups=groups,
+                      return_attribution_history=return_attribution_history, return_history=return_history,
+                      device=device, _engine=_engine)
+    if method is not None and method not in S.METHODS:
+        raise ValueError(f"method must be one of {('auto',) + tuple(S.METHODS) + ('subsets',)} or None")
+    labels, g = group_labels(groups, p, max_groups=None)
+    return ls_spa(X_train, X_test, y_train, y_test, reg, max_samples, batch_size, tolerance, seed, perms, antithetical,
+                  return_attribution_history, method=method, num_batches=num_batches, return_history=return_history,
+                  device=device, error_estimator=error_estimator, precision=precision, lookahead=lookahead, lanes=lanes,
+                  _engine=_engine, _timings=_timings, _defer=_defer, _players=(labels, g))
 
 
 # ------------------------------------------------------------------------------------------

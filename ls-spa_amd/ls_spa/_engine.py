@@ -34,6 +34,24 @@ class DeviceArrayView:
         }
 
 
+def debug_expand_groups(labels, group_perms, antithetical: bool):
+    """Test hook, host only (no engine, no GPU): the column orderings the kernels are given for (B, g) orderings of the
+    groups under a player map of these labels (include/lsspa.h, lsspa_debug_expand_groups)."""
+    lib = N.load()
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    group_perms = np.ascontiguousarray(group_perms, dtype=np.int32)
+    if group_perms.ndim != 2 or group_perms.shape[1] != g:
+        raise ValueError(f"group_perms must have shape (B, {g})")
+    B = group_perms.shape[0]
+    out = np.empty((B * (2 if antithetical else 1), len(labels)), dtype=np.int32)
+    rc = lib.lsspa_debug_expand_groups(N.iptr(labels), len(labels), g, N.iptr(group_perms), B, int(bool(antithetical)),
+                                       N.iptr(out))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_expand_groups: status {rc} (labels or a row of group_perms refused)")
+    return out
+
+
 class HipEngine:
     """One MI355X.  Raises LSSPANativeError when the HIP library or the GPU is missing."""
 
@@ -47,6 +65,7 @@ class HipEngine:
         self._h = h
         self.device = int(device)
         self.p = 0
+        self.players = 0      # groups of a player map (set_players); 0: the columns are the players
         self.m = 0
         self.tri = False
         self.y_norm_sq = float("nan")
@@ -84,6 +103,28 @@ class HipEngine:
         p, m, tri, yy = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
         self._check(self._lib.lsspa_get_problem(self._h, C.byref(p), C.byref(m), C.byref(tri), C.byref(yy)))
         self.p, self.m, self.tri, self.y_norm_sq = p.value, m.value, bool(tri.value), yy.value
+        self.players = 0      # a reduction drops the player map (include/lsspa.h)
+
+    @property
+    def dim(self) -> int:
+        """Dimension of a sample: lift vectors, statistics, history, estimator results.  p, or g under a player map."""
+        return self.players or self.p
+
+    # ---- groups of columns as the players of the sampling path ---------------------------------
+    def set_players(self, labels):
+        """One label per column (-1 the baseline, 0 .. g-1 the groups): from now on run_batch / launch_batch take
+        (B, g) orderings of the groups and everything a sample is has length g (include/lsspa.h, lsspa_set_players).
+        Resets the statistics; history and estimator have to be enabled again."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        self._check(self._lib.lsspa_set_players(self._h, N.iptr(labels), g))
+        self.players = g
+
+    def clear_players(self):
+        if self.players:
+            self._check(self._lib.lsspa_set_players(self._h, None, 0))
+            self.players = 0
 
     # ---- a1: reduction ---------------------------------------------------------------
     def load_data(self, X_train, X_test, y_train, y_test, reg: float):
@@ -259,10 +300,10 @@ class HipEngine:
     # ---- a2 / a3 / a4 ------------------------------------------------------------------
     def run_batch(self, perms, antithetical: bool, want_lifts: bool = False, accumulate: bool = True):
         perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if perms.ndim != 2 or perms.shape[1] != self.p:
-            raise ValueError(f"perms must have shape (B, {self.p})")
+        if perms.ndim != 2 or perms.shape[1] != self.dim:
+            raise ValueError(f"perms must have shape (B, {self.dim})")
         B = perms.shape[0]
-        out = np.empty((B, self.p)) if want_lifts else None
+        out = np.empty((B, self.dim)) if want_lifts else None
         self._check(self._lib.lsspa_lift_batch(self._h, N.iptr(perms), B, int(bool(antithetical)),
                                                N.dptr(out), self._acc_mode(accumulate)))
         return out
@@ -284,8 +325,8 @@ class HipEngine:
     def launch_batch(self, perms, antithetical: bool):
         """Enqueue a batch up to its lift vectors; returns a ticket for collect_batch / discard_batch."""
         perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if perms.ndim != 2 or perms.shape[1] != self.p:
-            raise ValueError(f"perms must have shape (B, {self.p})")
+        if perms.ndim != 2 or perms.shape[1] != self.dim:
+            raise ValueError(f"perms must have shape (B, {self.dim})")
         t = C.c_int32()
         self._check(self._lib.lsspa_lift_launch(self._h, N.iptr(perms), perms.shape[0], int(bool(antithetical)),
                                                 C.byref(t)))
@@ -297,7 +338,7 @@ class HipEngine:
         all of it).  Parts are taken front to back."""
         t, B = ticket
         count = B - first if count is None else int(count)
-        out = np.empty((count, self.p)) if want_lifts else None
+        out = np.empty((count, self.dim)) if want_lifts else None
         self._check(self._lib.lsspa_lift_collect(self._h, t, int(first), count, N.dptr(out),
                                                  self._acc_mode(accumulate)))
         return out
@@ -341,8 +382,8 @@ class HipEngine:
 
     def stats(self, want_cov: bool = True):
         n = C.c_int64()
-        mean = np.empty(self.p)
-        cov = np.empty((self.p, self.p)) if want_cov else None
+        mean = np.empty(self.dim)
+        cov = np.empty((self.dim, self.dim)) if want_cov else None
         self._check(self._lib.lsspa_stats_get(self._h, C.byref(n), N.dptr(mean), N.dptr(cov)))
         return n.value, mean, cov
 
@@ -350,7 +391,7 @@ class HipEngine:
         """Restore running statistics saved from ``stats()`` (checkpoint / resume)."""
         mean = np.ascontiguousarray(mean, dtype=np.float64)
         cov = np.ascontiguousarray(cov_biased, dtype=np.float64)
-        if mean.shape != (self.p,) or cov.shape != (self.p, self.p):
+        if mean.shape != (self.dim,) or cov.shape != (self.dim, self.dim):
             raise ValueError("mean / covariance shapes do not match the loaded problem")
         self._check(self._lib.lsspa_stats_set(self._h, int(n), N.dptr(mean), N.dptr(cov)))
 
@@ -365,14 +406,14 @@ class HipEngine:
 
     def history(self):
         """All accumulated samples' lift vectors, (count, p)."""
-        out = np.empty((self.history_count(), self.p))
+        out = np.empty((self.history_count(), self.dim))
         n = C.c_int64()
         self._check(self._lib.lsspa_history_get(self._h, C.byref(n), N.dptr(out)))
         return out
 
     def history_append(self, lifts):
         lifts = np.ascontiguousarray(lifts, dtype=np.float64)
-        if lifts.ndim != 2 or lifts.shape[1] != self.p:
+        if lifts.ndim != 2 or lifts.shape[1] != self.dim:
             raise ValueError("lifts must be (rows, p)")
         self._check(self._lib.lsspa_history_append(self._h, N.dptr(lifts), lifts.shape[0]))
 
@@ -391,7 +432,7 @@ class HipEngine:
         return DeviceArrayView(ptr.value, cnt.value, self)
 
     def error_quantiles(self):
-        feat, tot = np.empty(self.p), C.c_double()
+        feat, tot = np.empty(self.dim), C.c_double()
         self._check(self._lib.lsspa_error_quantiles(self._h, N.dptr(feat), C.byref(tot)))
         return feat, tot.value
 
@@ -419,7 +460,7 @@ class HipEngine:
 
     def error_result(self, slot: int, wait: bool = True):
         """(feature_errors, overall_error, mean, n) of a slot, or None if wait is False and it is not there yet."""
-        feat, mean = np.empty(self.p), np.empty(self.p)
+        feat, mean = np.empty(self.dim), np.empty(self.dim)
         tot, n, ready = C.c_double(), C.c_int64(), C.c_int32()
         self._check(self._lib.lsspa_error_result(self._h, int(slot), int(bool(wait)), C.byref(ready), N.dptr(feat),
                                                  C.byref(tot), N.dptr(mean), C.byref(n)))
@@ -442,14 +483,14 @@ class HipEngine:
             n_after.ctypes.data_as(N._pi64), N.iptr(slot)))
 
     def error_state(self):
-        D, s = np.empty((1024, self.p)), np.empty(1024)
+        D, s = np.empty((1024, self.dim)), np.empty(1024)
         self._check(self._lib.lsspa_error_state_get(self._h, N.dptr(D), N.dptr(s)))
         return D, s
 
     def set_error_state(self, D, s):
         D = np.ascontiguousarray(D, dtype=np.float64)
         s = np.ascontiguousarray(s, dtype=np.float64)
-        if D.shape != (1024, self.p) or s.shape != (1024,):
+        if D.shape != (1024, self.dim) or s.shape != (1024,):
             raise ValueError("D must be (1024, p) and s (1024,)")
         self._check(self._lib.lsspa_error_state_set(self._h, N.dptr(D), N.dptr(s)))
 
