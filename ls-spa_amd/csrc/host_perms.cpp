@@ -10,6 +10,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "players.h"
+
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -82,11 +84,6 @@ bool all_permutations_plain(const int32_t* perms, int B, int p, std::vector<int3
 // host work on the launch path, next to the validation above: baseline columns first (they are part of every model),
 // then every group's columns contiguously, ascending inside a group (the group's summed lift does not depend on the
 // order inside it).
-struct PlayerMap {      // as kernels.h declares it (this file is host-only C++ and does not include the HIP headers)
-  int p = 0, g = 0;
-  std::vector<int32_t> off, cols, base;
-};
-
 const char* player_map_build(const int32_t* labels, int p, int g, PlayerMap& m) {
   if (p < 1) return "no problem loaded";
   if (g < 1 || g > p) return "the number of groups g must be between 1 and p";

@@ -12,6 +12,8 @@
 #include <mutex>
 #include <vector>
 
+#include "players.h"
+
 namespace lsspa {
 
 // Dynamic LDS beyond the 64 KB default needs hipFuncAttributeMaxDynamicSharedMemorySize, which is set on the CURRENT
@@ -157,19 +159,10 @@ hipError_t launch_lift(const LiftArgs& a, hipStream_t st);
 hipError_t launch_sum_check(const double* lifts, int n_samples, int p, double r2, double tol, int32_t* info,
                             hipStream_t st);
 
-// Sampled attribution over groups of columns (lsspa_set_players).  PlayerMap is the host side of the map: labels [p] in
-// {-1, 0 .. g-1} as a CSR -- group k owns cols[off[k] .. off[k+1]), ascending column index -- and the baseline's columns.
-// host_perms.cpp: player_map_build returns nullptr, or what is wrong with the labels; expand_group_row writes the column
-// ordering of one ordering of the groups (gperm [g], validated by the caller): the baseline, then the groups' columns
-// in the order of gperm (read backwards when reversed != 0), each group's columns ascending.
-struct PlayerMap {
-  int p = 0, g = 0;
-  std::vector<int32_t> off, cols, base;
-};
-const char* player_map_build(const int32_t* labels, int p, int g, PlayerMap& m);
-void expand_group_row(const PlayerMap& m, const int32_t* gperm, int reversed, int32_t* out);
+// Sampled attribution over groups of columns (lsspa_set_players): PlayerMap, the host side of the map, and its two host
+// functions are declared in players.h.
 // k_players.hip: out[s][k] = mean over the sample's `per` (1 or 2) rows of the sum of lifts[row][j] over group k's columns
-// (off [g + 1], cols: the CSR above on the device); lifts [n_samples * per][p], out [n_samples][g].  Fixed summation order.
+// (off [g + 1], cols: PlayerMap's CSR on the device); lifts [n_samples * per][p], out [n_samples][g].  Fixed summation order.
 hipError_t launch_fold_players(const double* lifts, int p, int per, const int32_t* off, const int32_t* cols, int g,
                                int n_samples, double* out, hipStream_t st);
 

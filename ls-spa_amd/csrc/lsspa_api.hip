@@ -36,6 +36,27 @@ struct DevBuf {
   size_t count = 0;
 };
 
+template <typename T>
+void dev_free(DevBuf<T>& b) {
+  if (b.ptr) (void)hipFree(b.ptr);
+  b.ptr = nullptr;
+  b.count = 0;
+}
+
+// What an exact enumeration keeps between calls (lsspa_subsets_shapley, lsspa_groups_shapley): its own buffers and info
+// word, nothing of the sampling path's, and the timing of its last call.  The context holds one per entry point.
+struct ExactWork {
+  DevBuf<double> Hh, w, part, out, vals;   // rect-mode test Gram, Shapley weights, partial table, its sums, debug values
+  DevBuf<uint64_t> masks;                  // the debug values' subsets
+  DevBuf<int32_t> info, tab;               // info word; GroupLayout::tab (groups only)
+  double kernel_ms = 0.0, max_launch_ms = 0.0;
+  int64_t launches = 0;
+  void release() {
+    dev_free(Hh); dev_free(w); dev_free(part); dev_free(out); dev_free(vals);
+    dev_free(masks); dev_free(info); dev_free(tab);
+  }
+};
+
 }  // namespace
 
 // One lane = everything a batch of orderings needs while its kernels run: work matrices, solve results, staged
@@ -148,18 +169,8 @@ struct lsspa_ctx {
   Comm* comm = nullptr;
   DevBuf<double> pack, xfer;     // packed moments; staging of host-side all-gathers
   DevBuf<double> theta_d;        // lsspa_full_fit's back-substitution
-  // exact attribution by subset enumeration (lsspa_subsets_shapley): its own buffers, nothing of the sampling path's
-  DevBuf<double> sub_Hh, sub_w, sub_part, sub_out, sub_vals;
-  DevBuf<uint64_t> sub_masks;
-  DevBuf<int32_t> sub_info;
-  double sub_kernel_ms = 0.0, sub_max_launch_ms = 0.0;
-  int64_t sub_launches = 0;
-  // ... and over groups of columns (lsspa_groups_shapley): again its own buffers, info word and timing
-  DevBuf<double> gsh_Hh, gsh_w, gsh_part, gsh_out, gsh_vals;
-  DevBuf<uint64_t> gsh_masks;
-  DevBuf<int32_t> gsh_info, gsh_tab;
-  double gsh_kernel_ms = 0.0, gsh_max_launch_ms = 0.0;
-  int64_t gsh_launches = 0;
+  // exact attribution by subset enumeration (lsspa_subsets_shapley) and over groups of columns (lsspa_groups_shapley)
+  ExactWork sub, grp;
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -217,13 +228,6 @@ int dev_alloc(lsspa_ctx* ctx, DevBuf<T>& b, size_t count) {
   }
   b.count = count;
   return LSSPA_OK;
-}
-
-template <typename T>
-void dev_free(DevBuf<T>& b) {
-  if (b.ptr) (void)hipFree(b.ptr);
-  b.ptr = nullptr;
-  b.count = 0;
 }
 
 #define TRY(expr)                     \
@@ -1157,8 +1161,8 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   dev_free(ctx->mean_alt); dev_free(ctx->state_alt);
   dev_free(ctx->Cred);
   dev_free(ctx->Gf); dev_free(ctx->Hf);
-  dev_free(ctx->sub_Hh); dev_free(ctx->sub_w); dev_free(ctx->sub_part); dev_free(ctx->sub_out);
-  dev_free(ctx->sub_vals); dev_free(ctx->sub_masks); dev_free(ctx->sub_info);
+  ctx->sub.release();
+  ctx->grp.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   free_workspace(ctx);
   for (Lane& L : ctx->lanes) {
@@ -2757,26 +2761,30 @@ int lsspa_debug_factor(lsspa_ctx* ctx, const int32_t* perm, double* L, double* L
   return abi_caught(ctx);
 }
 
-// ---- exact attribution by subset enumeration (k_subsets.hip) ------------------------------------------------------
-// high subsets one enumeration launch takes at most (over all units): ~35 ms of GPU time at p = 32 (DESIGN.md)
-static constexpr uint64_t SUBSETS_PER_LAUNCH = 1ull << 20;
-static constexpr uint64_t SUBSETS_UNITS = 8192;
+}  // extern "C"
 
-// the kernels' view of the loaded problem: G, g, the test Gram (formed from the test factor in rect mode) and the
-// Shapley weights by subset size
-static int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
-  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, "no problem loaded (exact attribution by subsets)");
+// ---- exact attribution by enumeration: the host path that k_subsets.hip and k_groups.hip share ---------------------
+// n players (features, or groups of columns) and 2^n subsets, of which the kernels enumerate the n_high high ones in
+// `units` workgroups of `per` each.  What differs between the two entry points stays with them: their limits, how many
+// steps one launch takes, which kernel runs and where a player's value goes in phi.
+namespace {
+
+// row length of the weight table [2][EXACT_MAX_PLAYERS + 1], which each kernel indexes with its own constant
+constexpr int EXACT_MAX_PLAYERS = SUBSETS_MAX_P;
+static_assert(SUBSETS_MAX_P == GROUPS_MAX_G, "the two enumerations share the layout of the Shapley weight table");
+constexpr uint64_t EXACT_UNITS = 8192;
+uint64_t exact_units(uint64_t n_high) { return std::min(n_high, EXACT_UNITS); }
+
+// The kernels' view of the loaded problem, the part that SubsetArgs and GroupArgs (Args) have in common: G, g, the test
+// Gram (formed from the test factor in rect mode), the Shapley weights of n players by subset size, the tolerances and
+// a cleared info word.  no_problem: the entry point's error for that; tab: GROUPS_TAB_LEN words to upload into W.tab
+// beside the weights (nullptr: none).
+template <typename Args>
+int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, const int32_t* tab, Args& a) {
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, no_problem);
   const int p = ctx->p;
-  if (p > SUBSETS_MAX_P) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "exact attribution by subsets takes at most p = %d features (this problem has %d)",
-             SUBSETS_MAX_P, p);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
   HIPCHK(hipSetDevice(ctx->device));
-  a = SubsetArgs{};
-  a.p = p;
-  a.q = subsets_low_features(p);
+  a = Args{};
   a.G = ctx->G.ptr;
   a.g = ctx->g.ptr;
   a.ldg = ctx->p_pad;
@@ -2785,32 +2793,162 @@ static int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
     a.h = ctx->h.ptr;
     a.ldh = ctx->p_pad;
   } else {
-    TRY(dev_alloc(ctx, ctx->sub_Hh, (size_t)p * p + p));
-    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, ctx->sub_Hh.ptr, ctx->stream));
-    a.H = ctx->sub_Hh.ptr;
-    a.h = ctx->sub_Hh.ptr + (size_t)p * p;
+    TRY(dev_alloc(ctx, W.Hh, (size_t)p * p + p));
+    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, W.Hh.ptr, ctx->stream));
+    a.H = W.Hh.ptr;
+    a.h = W.Hh.ptr + (size_t)p * p;
     a.ldh = p;
   }
-  // w(k) = k! (p - 1 - k)! / p! = 1 / (p C(p - 1, k)); C(31, k) < 2^53 is exact in fp64
-  double w[2 * (SUBSETS_MAX_P + 1)] = {0.0};
+  // w(k) = k! (n - 1 - k)! / n! = 1 / (n C(n - 1, k)); C(31, k) < 2^53 is exact in fp64
+  double w[2 * (EXACT_MAX_PLAYERS + 1)] = {0.0};
   double binom = 1.0;
-  for (int k = 0; k < p; ++k) {
-    const double wk = 1.0 / ((double)p * binom);
-    w[SUBSETS_MAX_P + 1 + k] = wk;   // wb[k]
-    w[k + 1] = wk;                   // wa[k + 1]
-    binom = binom * (double)(p - 1 - k) / (double)(k + 1);
+  for (int k = 0; k < n; ++k) {
+    const double wk = 1.0 / ((double)n * binom);
+    w[EXACT_MAX_PLAYERS + 1 + k] = wk;   // wb[k]
+    w[k + 1] = wk;                       // wa[k + 1]
+    binom = binom * (double)(n - 1 - k) / (double)(k + 1);
   }
-  TRY(dev_alloc(ctx, ctx->sub_w, 2 * (SUBSETS_MAX_P + 1)));
-  TRY(dev_alloc(ctx, ctx->sub_info, 8));
-  HIPCHK(hipStreamSynchronize(ctx->stream));   // the weights are copied from this frame (a previous call may read them)
-  HIPCHK(hipMemcpy(ctx->sub_w.ptr, w, sizeof w, hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(ctx->sub_info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
-  a.w = ctx->sub_w.ptr;
+  TRY(dev_alloc(ctx, W.w, 2 * (EXACT_MAX_PLAYERS + 1)));
+  if (tab) TRY(dev_alloc(ctx, W.tab, GROUPS_TAB_LEN));
+  TRY(dev_alloc(ctx, W.info, 8));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // a previous call may still read W.w / W.tab; the copies are from host frames
+  HIPCHK(hipMemcpy(W.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  if (tab) HIPCHK(hipMemcpy(W.tab.ptr, tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
+  a.w = W.w.ptr;
   a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
   a.inv_yy = 1.0 / ctx->y_norm_sq;
-  a.info = ctx->sub_info.ptr;
+  a.info = W.info.ptr;
   return LSSPA_OK;
 }
+
+struct Events {
+  std::vector<hipEvent_t>& v;
+  ~Events() {
+    for (hipEvent_t e : v)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// The enumeration itself: launch(part, s0, s1) runs steps s0 .. s1 - 1 of every unit into the partial table part
+// [units][n + 1], `steps` of the n_high / units a launch.  out[0 .. n]: the table's column sums (launch_subsets_reduce),
+// a player's phi is its column minus column n; info (may be NULL): the info word.  Leaves the call's timing in W.
+template <typename Launch>
+int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int n, uint64_t n_high, uint64_t steps, Launch&& launch,
+                    double* out, int32_t* info) {
+  const uint64_t units = exact_units(n_high);
+  const uint64_t per = n_high / units;                 // both powers of two
+  TRY(dev_alloc(ctx, W.part, (size_t)units * (n + 1)));
+  TRY(dev_alloc(ctx, W.out, (size_t)n + 1));
+  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * units * (n + 1), ctx->stream));
+  // every launch is bracketed by events: the call's kernel time and its longest launch (exact_timing)
+  const size_t n_launch = (size_t)((per + steps - 1) / steps);
+  std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev[0], ctx->stream));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < per; s0 += steps, ++l) {
+    HIPCHK(launch(W.part.ptr, s0, std::min(per, s0 + steps)));
+    HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
+  }
+  HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, n, W.out.ptr, ctx->stream));
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (info) *info = bits;
+  W.kernel_ms = 0.0;
+  W.max_launch_ms = 0.0;
+  W.launches = (int64_t)n_launch;
+  for (size_t k = 0; k < n_launch; ++k) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+    W.kernel_ms += ms;
+    W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
+  }
+  return LSSPA_OK;
+}
+
+int exact_timing(const ExactWork& W, double* kernel_ms, double* max_launch_ms, int64_t* launches) {
+  if (kernel_ms) *kernel_ms = W.kernel_ms;
+  if (max_launch_ms) *max_launch_ms = W.max_launch_ms;
+  if (launches) *launches = W.launches;
+  return LSSPA_OK;
+}
+
+// test hook: vals[i] = the value of masks[i] (n > 0 of them, in the kernel's numbering) by launch(masks_d, vals_d);
+// not_pd: the error when a subset's pivot failed
+template <typename Launch>
+int exact_debug_values(lsspa_ctx* ctx, ExactWork& W, const uint64_t* masks, int64_t n, double* vals, Launch&& launch,
+                       const char* not_pd) {
+  TRY(dev_alloc(ctx, W.masks, (size_t)n));
+  TRY(dev_alloc(ctx, W.vals, (size_t)n));
+  HIPCHK(hipMemcpy(W.masks.ptr, masks, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(launch(W.masks.ptr, W.vals.ptr));
+  HIPCHK(hipMemcpyAsync(vals, W.vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (bits & LSSPA_INFO_NOT_PD) return ctx->fail(LSSPA_ERR_STATE, not_pd);
+  return LSSPA_OK;
+}
+
+// ---- ... by subset enumeration (k_subsets.hip) ----
+// high subsets one enumeration launch takes at most (over all units): ~35 ms of GPU time at p = 32 (DESIGN.md)
+constexpr uint64_t SUBSETS_PER_LAUNCH = 1ull << 20;
+
+int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
+  const int p = ctx->p;
+  if (ctx->have_problem && p > SUBSETS_MAX_P) {   // (no problem loaded: exact_view says so)
+    char msg[160];
+    snprintf(msg, sizeof msg, "exact attribution by subsets takes at most p = %d features (this problem has %d)",
+             SUBSETS_MAX_P, p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  TRY(exact_view(ctx, ctx->sub, "no problem loaded (exact attribution by subsets)", p, nullptr, a));
+  a.p = p;
+  a.q = subsets_low_features(p);
+  return LSSPA_OK;
+}
+
+// ---- ... over groups of columns (k_groups.hip) ----
+// One enumeration launch takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high subset
+// counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
+// subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X (DESIGN.md): far below the bound of
+// 0.2 s, and long enough that the launches' own cost does not show.
+constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
+
+int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, GroupLayout& L) {
+  const int p = ctx->p;
+  char msg[200];
+  L = GroupLayout{};
+  if (ctx->have_problem) {   // (no problem loaded: exact_view says so)
+    if (p > GROUPS_MAX_P) {
+      snprintf(msg, sizeof msg, "exact attribution over groups takes at most p = %d columns (this problem has %d)",
+               GROUPS_MAX_P, p);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+    if (g > GROUPS_MAX_G) {
+      snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+               (int)g);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+    if (const char* why = groups_layout(labels, p, g, L)) {
+      snprintf(msg, sizeof msg, "group labels: %s", why);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  }
+  TRY(exact_view(ctx, ctx->grp, "no problem loaded (exact attribution over groups)", L.ng, L.tab, a));
+  a.tab = ctx->grp.tab.ptr;
+  a.p = p; a.ng = L.ng; a.nb = L.nb;
+  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
@@ -2819,47 +2957,16 @@ int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info) try {
   TRY(subsets_args(ctx, a));
   const int p = ctx->p;
   const uint64_t n_high = 1ull << (p - a.q);
-  const uint64_t units = std::min(n_high, SUBSETS_UNITS);
-  a.per = n_high / units;                              // both powers of two
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
   const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
-  TRY(dev_alloc(ctx, ctx->sub_part, (size_t)units * (p + 1)));
-  TRY(dev_alloc(ctx, ctx->sub_out, (size_t)p + 1));
-  a.part = ctx->sub_part.ptr;
-  HIPCHK(hipMemsetAsync(ctx->sub_part.ptr, 0, sizeof(double) * units * (p + 1), ctx->stream));
-  // every launch is bracketed by events: the call's kernel time and its longest launch (lsspa_subsets_timing)
-  const size_t n_launch = (size_t)((a.per + steps - 1) / steps);
-  std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
-  struct Events {
-    std::vector<hipEvent_t>& v;
-    ~Events() {
-      for (hipEvent_t e : v)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ev[0], ctx->stream));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < a.per; s0 += steps, ++l) {
-    HIPCHK(launch_subsets_enum(a, units, s0, std::min(a.per, s0 + steps), ctx->stream));
-    HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
-  }
-  HIPCHK(launch_subsets_reduce(ctx->sub_part.ptr, (int64_t)units, p, ctx->sub_out.ptr, ctx->stream));
-  std::vector<double> out(p + 1);
-  int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(out.data(), ctx->sub_out.ptr, sizeof(double) * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(&bits, ctx->sub_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  double out[EXACT_MAX_PLAYERS + 1];
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_subsets_enum(a, units, s0, s1, ctx->stream);
+  };
+  TRY(exact_enumerate(ctx, ctx->sub, p, n_high, steps, launch, out, info));
   for (int j = 0; j < p; ++j) phi[j] = out[j] - out[p];
-  if (info) *info = bits;
-  ctx->sub_kernel_ms = 0.0;
-  ctx->sub_max_launch_ms = 0.0;
-  ctx->sub_launches = (int64_t)n_launch;
-  for (size_t k = 0; k < n_launch; ++k) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-    ctx->sub_kernel_ms += ms;
-    ctx->sub_max_launch_ms = std::max(ctx->sub_max_launch_ms, (double)ms);
-  }
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -2867,10 +2974,7 @@ int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info) try {
 
 int lsspa_subsets_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches) try {
   if (!ctx) return LSSPA_ERR_ARG;
-  if (kernel_ms) *kernel_ms = ctx->sub_kernel_ms;
-  if (max_launch_ms) *max_launch_ms = ctx->sub_max_launch_ms;
-  if (launches) *launches = ctx->sub_launches;
-  return LSSPA_OK;
+  return exact_timing(ctx->sub, kernel_ms, max_launch_ms, launches);
 } catch (...) {
   return abi_caught(const_cast<lsspa_ctx*>(ctx));
 }
@@ -2884,90 +2988,12 @@ int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, 
   for (int64_t i = 0; i < n; ++i)
     if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a feature beyond p");
   if (n == 0) return LSSPA_OK;
-  TRY(dev_alloc(ctx, ctx->sub_masks, (size_t)n));
-  TRY(dev_alloc(ctx, ctx->sub_vals, (size_t)n));
-  HIPCHK(hipMemcpy(ctx->sub_masks.ptr, masks, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
-  HIPCHK(launch_subsets_debug(a, ctx->sub_masks.ptr, n, ctx->sub_vals.ptr, ctx->stream));
-  HIPCHK(hipMemcpyAsync(v, ctx->sub_vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(&bits, ctx->sub_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (bits & LSSPA_INFO_NOT_PD) return ctx->fail(LSSPA_ERR_STATE, "a subset's Gram matrix is not positive definite");
-  return LSSPA_OK;
+  auto launch = [&](const uint64_t* masks_d, double* vals_d) {
+    return launch_subsets_debug(a, masks_d, n, vals_d, ctx->stream);
+  };
+  return exact_debug_values(ctx, ctx->sub, masks, n, v, launch, "a subset's Gram matrix is not positive definite");
 } catch (...) {
   return abi_caught(ctx);
-}
-
-// ---- exact attribution over groups of columns (k_groups.hip) -------------------------------------------------------
-// One enumeration launch takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high subset
-// counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
-// subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X (DESIGN.md): far below the bound of
-// 0.2 s, and long enough that the launches' own cost does not show.
-static constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
-static constexpr uint64_t GROUPS_UNITS = 8192;
-
-static int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, GroupLayout& L) {
-  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, "no problem loaded (exact attribution over groups)");
-  const int p = ctx->p;
-  char msg[200];
-  if (p > GROUPS_MAX_P) {
-    snprintf(msg, sizeof msg, "exact attribution over groups takes at most p = %d columns (this problem has %d)",
-             GROUPS_MAX_P, p);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (g > GROUPS_MAX_G) {
-    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
-             (int)g);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (const char* why = groups_layout(labels, p, g, L)) {
-    snprintf(msg, sizeof msg, "group labels: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  a = GroupArgs{};
-  a.p = p;
-  a.ng = L.ng;
-  a.nb = L.nb;
-  a.gl = L.gl;
-  a.gh = L.gh;
-  a.ql = L.ql;
-  a.G = ctx->G.ptr;
-  a.g = ctx->g.ptr;
-  a.ldg = ctx->p_pad;
-  if (ctx->tri) {
-    a.H = ctx->H.ptr;
-    a.h = ctx->h.ptr;
-    a.ldh = ctx->p_pad;
-  } else {
-    TRY(dev_alloc(ctx, ctx->gsh_Hh, (size_t)p * p + p));
-    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, ctx->gsh_Hh.ptr, ctx->stream));
-    a.H = ctx->gsh_Hh.ptr;
-    a.h = ctx->gsh_Hh.ptr + (size_t)p * p;
-    a.ldh = p;
-  }
-  // w(k) = k! (g - 1 - k)! / g! = 1 / (g C(g - 1, k)); C(31, k) < 2^53 is exact in fp64
-  double w[2 * (GROUPS_MAX_G + 1)] = {0.0};
-  double binom = 1.0;
-  for (int k = 0; k < L.ng; ++k) {
-    const double wk = 1.0 / ((double)L.ng * binom);
-    w[GROUPS_MAX_G + 1 + k] = wk;   // wb[k]
-    w[k + 1] = wk;                  // wa[k + 1]
-    binom = binom * (double)(L.ng - 1 - k) / (double)(k + 1);
-  }
-  TRY(dev_alloc(ctx, ctx->gsh_w, 2 * (GROUPS_MAX_G + 1)));
-  TRY(dev_alloc(ctx, ctx->gsh_tab, GROUPS_TAB_LEN));
-  TRY(dev_alloc(ctx, ctx->gsh_info, 8));
-  HIPCHK(hipStreamSynchronize(ctx->stream));   // weights and layout are copied from this frame
-  HIPCHK(hipMemcpy(ctx->gsh_w.ptr, w, sizeof w, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->gsh_tab.ptr, L.tab, sizeof L.tab, hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(ctx->gsh_info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
-  a.w = ctx->gsh_w.ptr;
-  a.tab = ctx->gsh_tab.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  a.inv_yy = 1.0 / ctx->y_norm_sq;
-  a.info = ctx->gsh_info.ptr;
-  return LSSPA_OK;
 }
 
 int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, int32_t* info) try {
@@ -2978,50 +3004,19 @@ int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, doubl
   TRY(groups_args(ctx, labels, g, a, L));
   const int ng = L.ng;
   const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = std::min(n_high, GROUPS_UNITS);
-  a.per = n_high / units;                              // both powers of two
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
   // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
   const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
   const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
   const uint64_t steps = std::max<uint64_t>(1, per_launch / units);
-  TRY(dev_alloc(ctx, ctx->gsh_part, (size_t)units * (ng + 1)));
-  TRY(dev_alloc(ctx, ctx->gsh_out, (size_t)ng + 1));
-  a.part = ctx->gsh_part.ptr;
-  HIPCHK(hipMemsetAsync(ctx->gsh_part.ptr, 0, sizeof(double) * units * (ng + 1), ctx->stream));
-  // every launch is bracketed by events: the call's kernel time and its longest launch (lsspa_groups_timing)
-  const size_t n_launch = (size_t)((a.per + steps - 1) / steps);
-  std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
-  struct Events {
-    std::vector<hipEvent_t>& v;
-    ~Events() {
-      for (hipEvent_t e : v)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ev[0], ctx->stream));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < a.per; s0 += steps, ++l) {
-    HIPCHK(launch_groups_enum(a, units, s0, std::min(a.per, s0 + steps), ctx->stream));
-    HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
-  }
-  HIPCHK(launch_subsets_reduce(ctx->gsh_part.ptr, (int64_t)units, ng, ctx->gsh_out.ptr, ctx->stream));
-  std::vector<double> out(ng + 1);
-  int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(out.data(), ctx->gsh_out.ptr, sizeof(double) * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(&bits, ctx->gsh_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  double out[EXACT_MAX_PLAYERS + 1];
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_groups_enum(a, units, s0, s1, ctx->stream);
+  };
+  TRY(exact_enumerate(ctx, ctx->grp, ng, n_high, steps, launch, out, info));
   for (int r = 0; r < ng; ++r) phi[L.gid[r]] = out[r] - out[ng];
-  if (info) *info = bits;
-  ctx->gsh_kernel_ms = 0.0;
-  ctx->gsh_max_launch_ms = 0.0;
-  ctx->gsh_launches = (int64_t)n_launch;
-  for (size_t k = 0; k < n_launch; ++k) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-    ctx->gsh_kernel_ms += ms;
-    ctx->gsh_max_launch_ms = std::max(ctx->gsh_max_launch_ms, (double)ms);
-  }
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -3029,10 +3024,7 @@ int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, doubl
 
 int lsspa_groups_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches) try {
   if (!ctx) return LSSPA_ERR_ARG;
-  if (kernel_ms) *kernel_ms = ctx->gsh_kernel_ms;
-  if (max_launch_ms) *max_launch_ms = ctx->gsh_max_launch_ms;
-  if (launches) *launches = ctx->gsh_launches;
-  return LSSPA_OK;
+  return exact_timing(ctx->grp, kernel_ms, max_launch_ms, launches);
 } catch (...) {
   return abi_caught(const_cast<lsspa_ctx*>(ctx));
 }
@@ -3053,17 +3045,11 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
   for (int64_t i = 0; i < n; ++i)
     for (int r = 0; r < L.ng; ++r)
       if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
-  TRY(dev_alloc(ctx, ctx->gsh_masks, (size_t)n));
-  TRY(dev_alloc(ctx, ctx->gsh_vals, (size_t)n));
-  HIPCHK(hipMemcpy(ctx->gsh_masks.ptr, lay.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
-  HIPCHK(launch_groups_debug(a, ctx->gsh_masks.ptr, n, ctx->gsh_vals.ptr, ctx->stream));
-  HIPCHK(hipMemcpyAsync(u, ctx->gsh_vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(&bits, ctx->gsh_info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (bits & LSSPA_INFO_NOT_PD)
-    return ctx->fail(LSSPA_ERR_STATE, "a group subset's Gram matrix is not positive definite");
-  return LSSPA_OK;
+  auto launch = [&](const uint64_t* masks_d, double* vals_d) {
+    return launch_groups_debug(a, masks_d, n, vals_d, ctx->stream);
+  };
+  return exact_debug_values(ctx, ctx->grp, lay.data(), n, u, launch,
+                            "a group subset's Gram matrix is not positive definite");
 } catch (...) {
   return abi_caught(ctx);
 }

@@ -240,19 +240,24 @@ class HipEngine:
         self._check(self._lib.lsspa_subsets_shapley(self._h, N.dptr(phi), C.byref(info)))
         return phi, info.value
 
+    def _exact_timing(self, getter):
+        ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
+        self._check(getter(self._h, C.byref(ms), C.byref(mx), C.byref(n)))
+        return ms.value / 1e3, mx.value / 1e3, n.value
+
+    def _exact_values(self, fn, masks, *labels_g):
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
+        out = np.empty(len(masks))
+        self._check(fn(self._h, *labels_g, masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks), N.dptr(out)))
+        return out
+
     def subsets_timing(self):
         """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley call."""
-        ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
-        self._check(self._lib.lsspa_subsets_timing(self._h, C.byref(ms), C.byref(mx), C.byref(n)))
-        return ms.value / 1e3, mx.value / 1e3, n.value
+        return self._exact_timing(self._lib.lsspa_subsets_timing)
 
     def debug_subset_values(self, masks):
         """Test hook: v(S) of every mask (bit j = feature j) by the enumeration's own device code."""
-        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
-        out = np.empty(len(masks))
-        self._check(self._lib.lsspa_debug_subset_values(self._h, masks.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                        len(masks), N.dptr(out)))
-        return out
+        return self._exact_values(self._lib.lsspa_debug_subset_values, masks)
 
     # ---- exact attribution over groups of columns (g <= 32, p <= 64) ---------------------
     @staticmethod
@@ -274,21 +279,14 @@ class HipEngine:
 
     def groups_timing(self):
         """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley call."""
-        ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
-        self._check(self._lib.lsspa_groups_timing(self._h, C.byref(ms), C.byref(mx), C.byref(n)))
-        return ms.value / 1e3, mx.value / 1e3, n.value
+        return self._exact_timing(self._lib.lsspa_groups_timing)
 
     def debug_group_values(self, labels, masks):
         """Test hook: u(S) of every mask (bit k = group k) by the grouped enumeration's own device code."""
         labels, g = self._labels(labels)
         if len(labels) != self.p:
             raise ValueError(f"labels must have length p = {self.p}")
-        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
-        out = np.empty(len(masks))
-        self._check(self._lib.lsspa_debug_group_values(self._h, N.iptr(labels), g,
-                                                       masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks),
-                                                       N.dptr(out)))
-        return out
+        return self._exact_values(self._lib.lsspa_debug_group_values, masks, N.iptr(labels), g)
 
     def factors(self):
         p, m = self.p, self.m

@@ -499,6 +499,40 @@ def test_library_exports_every_declared_symbol():
     assert _native.load().lsspa_abi_version() == 1
 
 
+def test_every_device_buffer_is_freed():
+    """DevBuf has no destructor (gram_side aliases a caller's pointer into one), so every DevBuf member of the
+    context, of a lane and of an exact enumeration's state must be named in a dev_free( call of lsspa_api.hip: as
+    ctx->name, as L.name, or -- ExactWork -- bare inside its release().  A member added without one leaks device
+    memory whenever a context is closed."""
+    src = open(os.path.join(ROOT, "ls-spa_amd", "csrc", "lsspa_api.hip")).read()
+
+    def body(struct):
+        m = re.search(r"^struct %s \{\n(.*?)^\};" % struct, src, re.S | re.M)
+        return m.group(1) if m else ""
+
+    def members(struct):
+        names = []
+        for decl in re.findall(r"^\s*DevBuf<[^>]+>\s+([^;]+);", body(struct), re.M):
+            names += [re.sub(r"\[\w+\]", "", n).strip() for n in decl.split(",")]
+        return names
+
+    release = re.search(r"void release\(\) \{(.*?)\n  \}", body("ExactWork"), re.S)
+    freed = {"lsspa_ctx": set(re.findall(r"dev_free\(ctx->(\w+)", src)),
+             "Lane": set(re.findall(r"dev_free\(L\.(\w+)", src)),
+             "ExactWork": set(re.findall(r"dev_free\((\w+)\)", release.group(1))) if release else set()}
+    leaked = [f"{s}::{n}" for s in freed for n in members(s) if n not in freed[s]]
+    assert not leaked, leaked
+    for s in freed:
+        assert members(s), f"no DevBuf member found in struct {s}: has the source moved on from this test's patterns?"
+    # ... and the context releases both of its ExactWork instances
+    works = [n.strip() for d in re.findall(r"^\s*ExactWork\s+([^;]+);", body("lsspa_ctx"), re.M) for n in d.split(",")]
+    assert len(works) == 2, works
+    destroy = src[src.index("int lsspa_destroy("):]
+    destroy = destroy[:destroy.index("\n}")]
+    for n in works:
+        assert f"ctx->{n}.release();" in destroy, n
+
+
 def test_batch_validation_fast_form_agrees_with_the_stamp_loop():
     """Every batch launch checks on the host that its rows are permutations (csrc/host_perms.cpp; the reference's
     orderings come from its own samplers, ls_spa/ls_spa.py:375-456, and are never checked).  The AVX2 form (a row as
