@@ -791,4 +791,27 @@ hipError_t launch_backsolve(const void* A, double* theta, int p, int p_pad, int 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------
+// out[j] = L[j][j]^2 / G[j][j]: the relative pivots of the identity ordering's factor (lsspa_full_fit takes their
+// minimum as the problem's conditioning, which scales the tolerance of the batches' sum check).
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void rel_pivots_kernel(const T* __restrict__ L, const double* __restrict__ G,
+                                                         double* __restrict__ out, int p, int p_pad) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= p) return;
+  const double l = (double)L[cm_off(p_pad, j, j)];
+  out[j] = l * l / G[(int64_t)j * p_pad + j];
+}
+
+hipError_t launch_rel_pivots(const void* A, const double* G, double* out, int p, int p_pad, int f32, hipStream_t st) {
+  if (p < 1 || p_pad <= p) return hipErrorInvalidValue;
+  if (f32)
+    hipLaunchKernelGGL(rel_pivots_kernel<float>, dim3((p + 255) / 256), dim3(256), 0, st, (const float*)A, G, out, p, p_pad);
+  else
+    hipLaunchKernelGGL(rel_pivots_kernel<double>, dim3((p + 255) / 256), dim3(256), 0, st, (const double*)A, G, out, p,
+                       p_pad);
+  return hipGetLastError();
+}
+
 }  // namespace lsspa

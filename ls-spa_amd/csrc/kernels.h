@@ -202,6 +202,9 @@ hipError_t launch_stats_unpack(const double* packed, double* buf, int p, hipStre
 hipError_t launch_backsolve(const void* A, double* theta, int p, int p_pad, int f32, hipStream_t st,
                             double* wg = nullptr);
 
+// out[j] = L_jj^2 / G_jj of the factor stored in A (identity ordering; G [p][p_pad] row-major), j < p
+hipError_t launch_rel_pivots(const void* A, const double* G, double* out, int p, int p_pad, int f32, hipStream_t st);
+
 // Gram contraction  C = Z^T Z, Z = [X | y]  (rows n, P1 = p + 1 columns), fp64 MFMA, split over rows
 struct GramArgs {
   const void* X;           // [n][ld] row-major (device)
