@@ -371,6 +371,16 @@ int lsspa_set_flags(lsspa_ctx* ctx, int32_t flags);
 int lsspa_debug_fail_alloc(lsspa_ctx* ctx, int32_t nth);
 /* use the packed (upper-triangle) form of lsspa_stats_allreduce from this p on (default 2048) */
 int lsspa_debug_pack_from(lsspa_ctx* ctx, int32_t p_min);
+/* chosen lift vectors in front of the collect paths: lifts [B][p] (host) are copied into the lane's lift buffer and the
+ * lane is marked as lsspa_lift_launch leaves it (B samples, none taken), *ticket names it.  lsspa_lift_collect (every
+ * accumulate mode), lsspa_lift_collect_chunks, lsspa_group_collect, the history and the running estimator then see
+ * those vectors as a batch's; no ordering is factored and no sum is checked.  LSSPA_ERR_STATE with two lanes, with a
+ * player map set, with no problem loaded or while a launched batch is uncollected. */
+int lsspa_debug_lift_inject(lsspa_ctx* ctx, const double* lifts, int32_t B, int32_t* ticket);
+/* how lsspa_lift_collect cuts a chunk of n_samples at dimension p for its moments: *small = 1 if the one-launch forms of
+ * small problems take it (p <= 128, up to 512 samples), *n_slices and *per_slice = the slices of the general kernel and
+ * the samples each is given (the last ones may get fewer, or none).  No context, no GPU: host code only. */
+int lsspa_debug_stats_slices(int32_t n_samples, int32_t p, int32_t* n_slices, int32_t* per_slice, int32_t* small);
 /* Host helper of the QMC ordering sources (the reference: np.argsort of Sobol' points / projected normals,
  * experiments/ground_truth_medium.py:56-71): out [B][p] = the argsort of every row of keys [B][p], on up to `threads`
  * threads of this library (no interpreter lock between them and the caller's other threads).  A row with all keys

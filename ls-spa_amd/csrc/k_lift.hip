@@ -571,6 +571,8 @@ int stats_batch_slices(int n_samples, int p) {
   return z < 1 ? 1 : z;
 }
 
+int stats_batch_per_slice(int n_samples, int nz) { return (((n_samples + nz - 1) / nz + 15) / 16) * 16; }
+
 hipError_t launch_stats_batch(const double* lifts, const double* mean, double* buf, int n_samples, int p,
                               int accumulate, double* parts, hipStream_t st) {
   if (n_samples < 1 || p < 1) return hipErrorInvalidValue;
@@ -582,7 +584,7 @@ hipError_t launch_stats_batch(const double* lifts, const double* mean, double* b
   }
   const int nt = (p + 63) / 64;
   const int nz = parts ? stats_batch_slices(n_samples, p) : 1;
-  const int per = (((n_samples + nz - 1) / nz + 15) / 16) * 16;
+  const int per = stats_batch_per_slice(n_samples, nz);
   hipLaunchKernelGGL(stats_batch_kernel, dim3(nt, nt, nz), dim3(256), 0, st, lifts, mean, nz > 1 ? parts : buf,
                      n_samples, p, accumulate, per);
   hipError_t e = hipGetLastError();

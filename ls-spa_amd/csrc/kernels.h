@@ -169,6 +169,8 @@ hipError_t launch_fold_players(const double* lifts, int p, int per, const int32_
 // pending-batch moments about the current running mean: buf = [n_b, S (p), Q (p x p)]
 // parts: workspace of stats_batch_slices(n_samples, p) * (1 + p + p*p) doubles (or NULL: one slice)
 int stats_batch_slices(int n_samples, int p);
+// samples per slice when n_samples are cut into nz slices: whole 16-sample steps
+int stats_batch_per_slice(int n_samples, int nz);
 hipError_t launch_stats_batch(const double* lifts, const double* mean, double* buf, int n_samples, int p,
                               int accumulate, double* parts, hipStream_t st);
 // single GPU, small p: batch moments AND merge in one launch (no pending buffer): reads (mean, state[0] = n), writes

@@ -2705,6 +2705,41 @@ int lsspa_debug_fail_alloc(lsspa_ctx* ctx, int32_t nth) try {
   return abi_caught(ctx);
 }
 
+// Chosen lift vectors in front of the collect paths: a host [B][p] matrix goes into the lane's lift buffer and the lane
+// is marked as lift_launch leaves it.  Nothing downstream knows the difference.
+int lsspa_debug_lift_inject(lsspa_ctx* ctx, const double* lifts, int32_t B, int32_t* ticket) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!lifts || B < 1 || !ticket) return ctx->fail(LSSPA_ERR_ARG, "lifts / B / ticket");
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
+  if (ctx->n_lanes != 1) return ctx->fail(LSSPA_ERR_STATE, "lift vectors are injected on a one-lane context only");
+  if (ctx->g_players) return ctx->fail(LSSPA_ERR_STATE, "lift vectors are not injected under a player map");
+  Lane& L = ctx->lanes[0];
+  if (L.in_flight) return ctx->fail(LSSPA_ERR_STATE, "a launched batch is still to be collected");
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(ensure_workspace(ctx, L, 0, B));     // the lift buffer alone: no ordering is factored
+  HIPCHK(hipMemcpyAsync(L.lifts.ptr, lifts, sizeof(double) * (size_t)B * ctx->p, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // lifts is the caller's (pageable, possibly temporary) buffer
+  L.B = B;
+  L.per = 1;
+  L.taken = 0;
+  L.in_flight = true;
+  ctx->lane_last = 0;
+  *ticket = 0;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_stats_slices(int32_t n_samples, int32_t p, int32_t* n_slices, int32_t* per_slice, int32_t* small) try {
+  if (n_samples < 1 || p < 1 || !n_slices || !per_slice || !small) return LSSPA_ERR_ARG;
+  *small = stats_small_fusable(n_samples, p) ? 1 : 0;
+  *n_slices = stats_batch_slices(n_samples, p);
+  *per_slice = *n_slices > 1 ? stats_batch_per_slice(n_samples, *n_slices) : n_samples;
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
+}
+
 int lsspa_set_precision(lsspa_ctx* ctx, int32_t dtype) try {
   if (!ctx) return LSSPA_ERR_ARG;
   if (dtype != LSSPA_F64 && dtype != LSSPA_F32) return ctx->fail(LSSPA_ERR_ARG, "dtype");

@@ -52,6 +52,16 @@ def debug_expand_groups(labels, group_perms, antithetical: bool):
     return out
 
 
+def debug_stats_slices(n_samples: int, p: int):
+    """Test hook, host only: (samples given to every slice of a chunk's moments, small) as the library cuts a chunk of
+    n_samples at dimension p (include/lsspa.h, lsspa_debug_stats_slices)."""
+    nz, per, small = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = N.load().lsspa_debug_stats_slices(int(n_samples), int(p), C.byref(nz), C.byref(per), C.byref(small))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_stats_slices: status {rc}")
+    return [max(0, min(n_samples, (k + 1) * per.value) - k * per.value) for k in range(nz.value)], bool(small.value)
+
+
 class HipEngine:
     """One MI355X.  Raises LSSPANativeError when the HIP library or the GPU is missing."""
 
@@ -528,6 +538,16 @@ class HipEngine:
     def debug_fail_alloc(self, nth: int):
         """Test hook: the nth device allocation from now fails with MemoryError (0 disarms)."""
         self._check(self._lib.lsspa_debug_fail_alloc(self._h, int(nth)))
+
+    def debug_inject_lifts(self, lifts):
+        """Test hook: a (B, p) matrix of chosen lift vectors as a launched batch (include/lsspa.h,
+        lsspa_debug_lift_inject); returns the ticket collect_batch / collect_chunks / group_collect take."""
+        lifts = np.ascontiguousarray(lifts, dtype=np.float64)
+        if lifts.ndim != 2 or lifts.shape[1] != self.p:
+            raise ValueError(f"lifts must have shape (B, {self.p})")
+        t = C.c_int32()
+        self._check(self._lib.lsspa_debug_lift_inject(self._h, N.dptr(lifts), lifts.shape[0], C.byref(t)))
+        return (t.value, lifts.shape[0])
 
     def mfma_probe(self, A, B, f32=False):
         A = np.ascontiguousarray(A, dtype=np.float64)
