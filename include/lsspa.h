@@ -75,7 +75,9 @@ int lsspa_reduce_timing(const lsspa_ctx* ctx, double* seconds4);
  *   lsspa_reduce_partial : unscaled Gram sums of n_local training rows and m_local test rows.  M_total is the
  *                          test-row count over all ranks; if M_total < p the test rows ARE the test factor and
  *                          every rank has to pass all of them (m_local == M_total).  n_local / m_local may be 0.
- *   lsspa_reduce_buffer  : device pointer / element count (fp64) of the sums -- the all-reduce(SUM) target
+ *   lsspa_reduce_buffer  : device pointer / element count (fp64) of the sums -- the all-reduce(SUM) target:
+ *                          [2][P1pad][P1pad] (train, test), P1pad = p + 1 rounded up to 128; rows and columns beyond
+ *                          p are zero whatever the data hold (a NaN or Inf stays in its own row and column)
  *   lsspa_reduce_finish  : G, g, H, h from the summed buffers with the global N; the context is then in the
  *                          same state as after lsspa_reduce on the stacked rows (up to summation order). */
 int lsspa_reduce_partial(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train,
@@ -381,6 +383,18 @@ int lsspa_debug_lift_inject(lsspa_ctx* ctx, const double* lifts, int32_t B, int3
  * small problems take it (p <= 128, up to 512 samples), *n_slices and *per_slice = the slices of the general kernel and
  * the samples each is given (the last ones may get fewer, or none).  No context, no GPU: host code only. */
 int lsspa_debug_stats_slices(int32_t n_samples, int32_t p, int32_t* n_slices, int32_t* per_slice, int32_t* small);
+/* how a Gram launch of n rows at p features is cut (csrc/k_gram.hip): *n_split = the class-A slice count the library
+ * picks for it, cnt3 / slices3 / rps3 = units per slice, row slices and rows per slice of the three unit classes (A:
+ * pairs of full tiles, B: pairs with the ragged last tile, C: diagonal duos / a single), *nt = 128-column tiles of
+ * [X | y], *xlive = live 16-column blocks of the last tile.  No context, no GPU: host code only. */
+int lsspa_debug_gram_plan(int64_t n, int32_t p, int32_t* n_split, int32_t* cnt3, int32_t* slices3, int32_t* rps3,
+                          int32_t* nt, int32_t* xlive);
+/* rows per chunk of the streamed reduction of host-resident data, instead of its ~96 MB sizing with a 1024-row floor:
+ * 0 (the default sizing again) or a multiple of 16 that is at least 16, anything else is LSSPA_ERR_ARG.  The slice count
+ * of every chunk's launch is the one for `rows` rows, as with the default sizing.  Stays set until changed: a
+ * reduction does not reset it.  A test reaches three and more chunks, a short last one and the accumulating forms of
+ * both reduce kernels with a small matrix through it. */
+int lsspa_debug_reduce_chunk_rows(lsspa_ctx* ctx, int64_t rows);
 /* Host helper of the QMC ordering sources (the reference: np.argsort of Sobol' points / projected normals,
  * experiments/ground_truth_medium.py:56-71): out [B][p] = the argsort of every row of keys [B][p], on up to `threads`
  * threads of this library (no interpreter lock between them and the caller's other threads).  A row with all keys

@@ -161,20 +161,6 @@ __device__ __forceinline__ void zstore(const ZRegs<T>& r, double* lds, int tid) 
 #define LSSPA_TRI_BI(t) ((t) < 1 ? 0 : (t) < 3 ? 1 : (t) < 6 ? 2 : 3)
 #define LSSPA_TRI_BJ(t) ((t) - LSSPA_TRI_BI(t) * (LSSPA_TRI_BI(t) + 1) / 2)
 
-// What a launch is cut into (host and device agree on it through this struct).  Units come in three classes -- A:
-// off-diagonal pairs of full tiles (16 blocks a wave and k-step), B: pairs whose tile i is the ragged last tile
-// (2 xlive blocks), C: duos (18) -- each with its own slice count (gram_plan: 16 : 18 : 20 from six tiles on).
-struct GramPlan {
-  int nt;                 // 128-column tiles of Z = [X | y]
-  int xlive;              // live 16-column blocks of the last tile
-  int cnt[3];             // units per slice, classes A, B, C
-  int slices[3];          // row slices per class
-  int rps[3];             // rows per slice (multiple of 16)
-  int per_xcd;            // workgroups per XCD (grid = 8 x per_xcd)
-  int natural;            // developer A/B: unit = workgroup id (units of a slice spread over the XCDs)
-  __host__ __device__ int total() const { return cnt[0] * slices[0] + cnt[1] * slices[1] + cnt[2] * slices[2]; }
-};
-
 template <typename T>
 __global__ __launch_bounds__(256, 2) void gram_kernel(const T* __restrict__ X, const T* __restrict__ y,
                                                       int64_t n, int64_t ld, int p, GramPlan plan,
@@ -396,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void gram_kernel(const T* __restrict__ X, c
 // writes their lower 16 x 16 blocks only; the blocks above the diagonal are stored as zeros (nobody reads them:
 // gram_finalize symmetrises from the lower part) and never loaded.
 __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restrict__ slabs, GramPlan plan,
-                                                          int n_pairs, int P1pad, double* __restrict__ C,
+                                                          int n_pairs, int P1pad, int p, double* __restrict__ C,
                                                           int accumulate) {
   __shared__ double s_t[32][33];
   int pair = blockIdx.x, ti = 0;
@@ -435,6 +421,8 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restri
   for (int q = 0; q < 4; ++q) {
     const int64_t o = (int64_t)(i0 + r0 + 8 * q) * P1pad + j0 + c;
     if (accumulate && live[q]) v[q] += C[o];   // fixed chunk order: still reproducible
+    // padding (a row or column beyond y) is zero whatever the data: its sums are 0 x z, NaN for a NaN or Inf z
+    if (i0 + r0 + 8 * q > p || j0 + c > p) v[q] = 0.0;
     C[o] = v[q];
   }
   if (diag) return;                // workgroup-uniform
@@ -450,7 +438,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restri
 // and the slices are many and short: one workgroup per 16 x 16 block of the pair, one element per thread, the slices
 // fetched eight at a time (independent loads) and added in their fixed order.
 __global__ __launch_bounds__(256) void gram_reduce_small_kernel(const double* __restrict__ slabs, GramPlan plan,
-                                                                int n_pairs, int P1pad, double* __restrict__ C,
+                                                                int n_pairs, int P1pad, int p, double* __restrict__ C,
                                                                 int accumulate) {
   int pair = blockIdx.x, ti = 0;
   while (pair >= ti + 1) {
@@ -478,6 +466,7 @@ __global__ __launch_bounds__(256) void gram_reduce_small_kernel(const double* __
   for (; k < n_split; ++k) v += src[(int64_t)k * slice_stride];
   const int64_t o = (int64_t)(ti * 128 + row) * P1pad + tj * 128 + col;
   if (accumulate) v += C[o];       // fixed chunk order: still reproducible
+  if (ti * 128 + row > p || tj * 128 + col > p) v = 0.0;   // padding stays zero whatever the data (0 x NaN is NaN)
   C[o] = v;
   if (!diag) C[(int64_t)(tj * 128 + col) * P1pad + ti * 128 + row] = v;
 }
@@ -507,7 +496,7 @@ static inline int n_pairs_of(int p) {
 }
 
 // n_split = row slices of class A (the caller's knob, gram_default_split); the other classes in proportion to their cost
-static GramPlan gram_plan(int64_t n, int p, int n_split, int variant = 0) {
+GramPlan gram_plan(int64_t n, int p, int n_split, int variant) {
   GramPlan g;
   g.nt = n_tiles_of(p);
   g.xlive = std::min(8, (p + 1 - (g.nt - 1) * 128 + 15) / 16);
@@ -591,10 +580,11 @@ hipError_t launch_gram(const GramArgs& a, hipStream_t st) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (np <= 3)
-    hipLaunchKernelGGL(gram_reduce_small_kernel, dim3(np, 64), dim3(256), 0, st, a.slabs, g, np, P1pad, a.C,
+    hipLaunchKernelGGL(gram_reduce_small_kernel, dim3(np, 64), dim3(256), 0, st, a.slabs, g, np, P1pad, a.p, a.C,
                        a.accumulate);
   else
-    hipLaunchKernelGGL(gram_reduce_kernel, dim3(np, 16), dim3(256), 0, st, a.slabs, g, np, P1pad, a.C, a.accumulate);
+    hipLaunchKernelGGL(gram_reduce_kernel, dim3(np, 16), dim3(256), 0, st, a.slabs, g, np, P1pad, a.p, a.C,
+                       a.accumulate);
   return hipGetLastError();
 }
 

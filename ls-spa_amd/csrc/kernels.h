@@ -220,6 +220,21 @@ struct GramArgs {
   int accumulate;          // C += (row chunks of a streamed matrix) instead of C =
   int variant = 0;         // developer A/B switches (bit 0: workgroup id = unit, no XCD-contiguous map)
 };
+// What a launch is cut into (host and device agree on it through this struct).  Units come in three classes -- A:
+// off-diagonal pairs of full tiles (16 blocks a wave and k-step), B: pairs whose tile i is the ragged last tile
+// (2 xlive blocks), C: duos (18) -- each with its own slice count (gram_plan: 16 : 18 : 20 from six tiles on).
+struct GramPlan {
+  int nt;                 // 128-column tiles of Z = [X | y]
+  int xlive;              // live 16-column blocks of the last tile
+  int cnt[3];             // units per slice, classes A, B, C
+  int slices[3];          // row slices per class
+  int rps[3];             // rows per slice (multiple of 16)
+  int per_xcd;            // workgroups per XCD (grid = 8 x per_xcd)
+  int natural;            // developer A/B: unit = workgroup id (units of a slice spread over the XCDs)
+  __host__ __device__ int total() const { return cnt[0] * slices[0] + cnt[1] * slices[1] + cnt[2] * slices[2]; }
+};
+// n_split = row slices of class A (gram_default_split for the launch's rows); launch_gram cuts its launch by it
+GramPlan gram_plan(int64_t n, int p, int n_split, int variant = 0);
 size_t gram_workspace_bytes(int p, int n_split);
 int gram_default_split(int64_t n, int p);
 hipError_t launch_gram(const GramArgs& a, hipStream_t st);

@@ -183,6 +183,7 @@ struct lsspa_ctx {
   std::vector<int32_t> perm_mark;   // scratch of the ordering validation
   bool general_path_once = false;   // set while the factors themselves are wanted (full_fit, get_factors, debug_factor)
   int fail_alloc_in = 0;   // test hook (lsspa_debug_fail_alloc): the n-th device allocation from now fails
+  int64_t red_chunk_rows = 0;   // test hook (lsspa_debug_reduce_chunk_rows): rows per streamed chunk, 0 = default sizing
 
   // host seconds of the last reduction's parts (lsspa_reduce_timing): streamed copies + Gram kernels, finalize
   // (scaling, Cholesky-side set-up of the statistics, sync)
@@ -1305,6 +1306,7 @@ static int gram_side_streamed(lsspa_ctx* ctx, const void* X, const void* y, int6
   const size_t es = is_f32 ? 4 : 8;
   int64_t rows = (((int64_t)96 << 20) / ((int64_t)p * (int64_t)es) / 16) * 16;   // ~96 MB chunks
   rows = std::max<int64_t>(1024, std::min<int64_t>(rows, ((n + 15) / 16) * 16));
+  if (ctx->red_chunk_rows > 0) rows = ctx->red_chunk_rows;   // test hook: many short chunks from a small matrix
   const int n_split = gram_default_split(rows, p);
   DevBuf<double> slabs, C;
   void* dX[2] = {nullptr, nullptr};
@@ -2738,6 +2740,33 @@ int lsspa_debug_stats_slices(int32_t n_samples, int32_t p, int32_t* n_slices, in
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_ARG;
+}
+
+int lsspa_debug_gram_plan(int64_t n, int32_t p, int32_t* n_split, int32_t* cnt3, int32_t* slices3, int32_t* rps3,
+                          int32_t* nt, int32_t* xlive) try {
+  if (n < 1 || p < 1 || !n_split || !cnt3 || !slices3 || !rps3 || !nt || !xlive) return LSSPA_ERR_ARG;
+  *n_split = gram_default_split(n, p);
+  const GramPlan g = gram_plan(n, p, *n_split);
+  for (int c = 0; c < 3; ++c) {
+    cnt3[c] = g.cnt[c];
+    slices3[c] = g.slices[c];
+    rps3[c] = g.rps[c];
+  }
+  *nt = g.nt;
+  *xlive = g.xlive;
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
+}
+
+int lsspa_debug_reduce_chunk_rows(lsspa_ctx* ctx, int64_t rows) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (rows != 0 && (rows < 16 || rows % 16 != 0))
+    return ctx->fail(LSSPA_ERR_ARG, "rows per streamed chunk: 0 (default) or a multiple of 16");
+  ctx->red_chunk_rows = rows;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
 }
 
 int lsspa_set_precision(lsspa_ctx* ctx, int32_t dtype) try {

@@ -62,6 +62,19 @@ def debug_stats_slices(n_samples: int, p: int):
     return [max(0, min(n_samples, (k + 1) * per.value) - k * per.value) for k in range(nz.value)], bool(small.value)
 
 
+def debug_gram_plan(n: int, p: int):
+    """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
+    a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
+    ns, nt, xl = C.c_int32(), C.c_int32(), C.c_int32()
+    cnt, sl, rps = (np.zeros(3, dtype=np.int32) for _ in range(3))
+    rc = N.load().lsspa_debug_gram_plan(int(n), int(p), C.byref(ns), N.iptr(cnt), N.iptr(sl), N.iptr(rps), C.byref(nt),
+                                        C.byref(xl))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_gram_plan: status {rc}")
+    return {"n_split": ns.value, "nt": nt.value, "xlive": xl.value, "cnt": [int(v) for v in cnt],
+            "slices": [int(v) for v in sl], "rps": [int(v) for v in rps]}
+
+
 class HipEngine:
     """One MI355X.  Raises LSSPANativeError when the HIP library or the GPU is missing."""
 
@@ -538,6 +551,10 @@ class HipEngine:
     def debug_fail_alloc(self, nth: int):
         """Test hook: the nth device allocation from now fails with MemoryError (0 disarms)."""
         self._check(self._lib.lsspa_debug_fail_alloc(self._h, int(nth)))
+
+    def debug_reduce_chunk_rows(self, rows: int):
+        """Test hook: rows per chunk of the streamed reduction of host arrays (a multiple of 16; 0: default sizing)."""
+        self._check(self._lib.lsspa_debug_reduce_chunk_rows(self._h, int(rows)))
 
     def debug_inject_lifts(self, lifts):
         """Test hook: a (B, p) matrix of chosen lift vectors as a launched batch (include/lsspa.h,
