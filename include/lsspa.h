@@ -112,6 +112,17 @@ int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info);
 int lsspa_subsets_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches);
 int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v);
 
+/* Exact pairwise Shapley interaction index of the loaded problem, from the same enumeration of all 2^p subsets
+ * (p <= 32) and the same v:
+ *   I_ij = sum over S without i and j of |S|! (p - 2 - |S|)! / (p - 1)! (v(S + i + j) - v(S + i) - v(S + j) + v(S)).
+ * inter [p][p] is symmetric, holds the raw index I_ij off the diagonal and 0 on it (SHAP's matrix has I_ij / 2 off the
+ * diagonal and phi_i minus the rest of row i on it; the Python driver forms it).  phi [p] is bitwise the phi of
+ * lsspa_subsets_shapley.  Errors, the p <= 32 limit, info, fp64, bounded launches, bitwise reproducibility and "nothing
+ * of the sampling path changes" are those of lsspa_subsets_shapley; the two calls share their buffers, and this call
+ * leaves its timing where lsspa_subsets_timing reads it.  The partial table is p (p + 3) / 2 + 2 columns wide: about
+ * 37 MB of device memory at p = 32. */
+int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi /* [p] */, double* inter /* [p*p] */, int32_t* info);
+
 /* Exact Shapley attribution over GROUPS of columns: the players are the g <= 32 groups, the problem has p <= 64 columns.
  * labels[j] in {-1, 0 .. g-1} for every column j: group k is {j : labels[j] == k} (none may be empty), the columns
  * labelled -1 are the baseline B, part of every model and given no attribution.  With F(S) = B + the columns of the

@@ -21,6 +21,20 @@
 // so a lane keeps sum (a + b) per high feature of the subsets it saw, one sum for its own T and one of b; a unit's
 // partials are reduced once per launch by fixed butterflies and added to its own row of the partial table, which a
 // last kernel sums in fixed order.  No floating-point atomics: the result is bitwise the same from call to call.
+//
+// Pairwise Shapley interaction index (lsspa_subsets_interactions, the INTER instantiation of the enumeration kernel):
+//   I_ij = sum_{S without i, j} w2(|S|) (v(S + i + j) - v(S + i) - v(S + j) + v(S)),   w2(s) = s! (p - 2 - s)! / (p - 1)!,
+// is another linear functional of the same v(K).  With alpha(k) = w2(k - 2), beta(k) = w2(k - 1), gamma(k) = w2(k) (0
+// outside 0 .. p - 2) and k = |K|,
+//   I_ij = T0 - T1_i - T1_j + T2_ij,   T0 = sum_K gamma v,   T1_i = sum_{K with i} (beta + gamma) v,
+//   T2_ij = sum_{K with i and j} (alpha + 2 beta + gamma) v.
+// T0 and T1 are kept like b and phi's sums above.  T2: a lane keeps the (alpha + 2 beta + gamma) sum of its own T and
+// one per high feature -- reduced over the lanes with bit t, or bits s and t, at the end of a launch they are the
+// high-low and low-low pairs; a pair of HIGH features depends on hi alone, which the whole wave shares, so the wave's
+// sum of the weighted values of one high subset goes to the pairs inside hi, which are dealt over the lanes (at most
+// SHH = 6 a lane) with their masks built once.  A unit's row of the partial table is then
+//   [0 .. p] as above | T0 | T1 [p] | T2 [p (p - 1) / 2] (pairs i < j, row-major),
+// its first p + 1 columns computed by the very operations of the phi-only kernel.
 #include "kernels.h"
 
 namespace lsspa {
@@ -32,6 +46,7 @@ constexpr int SNH = SP - SQ;                   // largest number of high feature
 constexpr int LDM = SP + 1;                    // row stride of the compacted sweep matrix (n <= p + 1 <= 33)
 constexpr int SENT = (LDM * LDM + 63) / 64;    // sweep entries a lane owns at most (18)
 constexpr int ZC = SQ + 2;                     // row stride of Z: columns 0 .. q of X^T H X, then X^T h
+constexpr int SHH = (SNH * (SNH - 1) / 2 + 63) / 64;   // pairs of high features a lane owns at most (6)
 
 struct SubShared {
   double H[SP * LDM];      // test Gram, stride LDM
@@ -222,8 +237,15 @@ __device__ void load_shared(SubShared& sh, const SubsetArgs& a, int lane) {
   for (int e = lane; e < (SQ + 1) * ZC; e += 64) sh.Z[e] = 0.0;   // rows / columns beyond q stay 0
 }
 
+// column of pair (i, j), i < j, among the p (p - 1) / 2 pairs of a row of the interactions table
+__device__ inline int pair_col(int p, int i, int j) { return i * (2 * p - i - 1) / 2 + (j - i - 1); }
+
+// INTER: the interaction sums T0, T1, T2 beside phi's (lsspa_subsets_interactions); a row of part is then
+// subsets_inter_cols(p) wide.  Everything of the phi-only instantiation is in both, unchanged.
+template <bool INTER>
 __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t s0, uint64_t s1) {
   __shared__ SubShared sh;
+  __shared__ double w2[INTER ? 3 * (SP + 1) : 1];   // gamma, beta + gamma, alpha + 2 beta + gamma by |K|
   const int lane = threadIdx.x;
   const int p = a.p, q = a.q, nh = p - q;
   load_shared(sh, a, lane);
@@ -231,6 +253,27 @@ __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t
 #pragma unroll
   for (int j = 0; j < SNH; ++j) acc[j] = 0.0;
   double c_own = 0.0, b_own = 0.0;
+  // INTER only (dead code otherwise)
+  double acc1[INTER ? SNH : 1], acc2[INTER ? SNH : 1], hh[SHH];
+  uint32_t hm[SHH];
+  double g_own = 0.0, e_own = 0.0, d_own = 0.0;
+  if constexpr (INTER) {
+    for (int e = lane; e < 3 * (SP + 1); e += 64) w2[e] = a.w[2 * (SP + 1) + e];
+#pragma unroll
+    for (int j = 0; j < SNH; ++j) acc1[j] = acc2[j] = 0.0;
+    // pair number e = lane + 64 r of the nh (nh - 1) / 2 pairs j1 < j2 of high features, as a mask over hi; a slot
+    // without a pair gets a mask that no hi contains (nh <= 26)
+#pragma unroll
+    for (int r = 0; r < SHH; ++r) {
+      hh[r] = 0.0;
+      int rem = lane + 64 * r, j1 = 0;
+      while (j1 < nh - 1 && rem >= nh - 1 - j1) {
+        rem -= nh - 1 - j1;
+        ++j1;
+      }
+      hm[r] = (j1 < nh - 1) ? ((1u << j1) | (1u << (j1 + 1 + rem))) : 0x80000000u;
+    }
+  }
   bool bad = false;
   const bool live = lane < (1 << q);
   const int kt = __popc(lane);
@@ -246,9 +289,33 @@ __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t
       for (int j = 0; j < SNH; ++j)
         if (j < nh && ((hi >> j) & 1ull)) acc[j] += c;
     }
+    if constexpr (INTER) {
+      double d = 0.0;
+      if (live) {
+        const int k = __popcll(hi) + kt;
+        const double e = w2[SP + 1 + k] * v;
+        d = w2[2 * (SP + 1) + k] * v;
+        g_own += w2[k] * v;
+        e_own += e;
+        d_own += d;
+#pragma unroll
+        for (int j = 0; j < SNH; ++j)
+          if (j < nh && ((hi >> j) & 1ull)) {
+            acc1[j] += e;
+            acc2[j] += d;
+          }
+      }
+      if (nh >= 2) {                          // the same for the whole wave
+        const double dw = wave_sum(d);
+        const uint32_t h32 = (uint32_t)hi;
+#pragma unroll
+        for (int r = 0; r < SHH; ++r)
+          if ((h32 & hm[r]) == hm[r]) hh[r] += dw;
+      }
+    }
     __syncthreads();
   }
-  double* part = a.part + (int64_t)blockIdx.x * (p + 1);
+  double* part = a.part + (int64_t)blockIdx.x * (INTER ? (p + 2 + p + p * (p - 1) / 2) : (p + 1));
 #pragma unroll
   for (int t = 0; t < SQ; ++t) {
     if (t < q) {
@@ -265,6 +332,45 @@ __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t
   }
   const double tb = wave_sum(b_own);
   if (lane == 0) part[p] += tb;
+  if constexpr (INTER) {
+    double* t1 = part + p + 2;
+    double* t2 = t1 + p;
+    const double t0 = wave_sum(g_own);
+    if (lane == 0) part[p + 1] += t0;
+#pragma unroll
+    for (int t = 0; t < SQ; ++t) {
+      if (t < q) {
+        const bool has_t = live && ((lane >> t) & 1);
+        const double tot = wave_sum(has_t ? e_own : 0.0);
+        if (lane == 0) t1[t] += tot;
+#pragma unroll
+        for (int u = 0; u < SQ; ++u) {          // low-low pairs (u, t), u < t
+          if (u < t) {
+            const double both = wave_sum((has_t && ((lane >> u) & 1)) ? d_own : 0.0);
+            if (lane == 0) t2[pair_col(p, u, t)] += both;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SNH; ++j) {
+      if (j < nh) {
+        const double tot = wave_sum(acc1[j]);
+        if (lane == 0) t1[q + j] += tot;
+        for (int t = 0; t < q; ++t) {           // high-low pairs (t, q + j)
+          const double hl = wave_sum((live && ((lane >> t) & 1)) ? acc2[j] : 0.0);
+          if (lane == 0) t2[pair_col(p, t, q + j)] += hl;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < SHH; ++r) {             // high-high pairs: every lane holds the sums of its own
+      if (hm[r] != 0x80000000u) {
+        const int j1 = __ffs((int)hm[r]) - 1, j2 = 31 - __clz((int)hm[r]);
+        t2[pair_col(p, q + j1, q + j2)] += hh[r];
+      }
+    }
+  }
   if (__any(bad) && lane == 0) atomicOr(a.info, 1);
 }
 
@@ -331,18 +437,24 @@ bool args_ok(const SubsetArgs& a) {
 
 int subsets_low_features(int p) { return p < SQ ? p : SQ; }
 
-hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st) {
+int subsets_inter_cols(int p) { return p + 2 + p + p * (p - 1) / 2; }
+
+hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
+                               hipStream_t st) {
   if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
   // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^(p - q)
   const int nh = a.p - a.q;
   if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(subsets_enum_kernel, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
+  if (inter)
+    hipLaunchKernelGGL(subsets_enum_kernel<true>, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
+  else
+    hipLaunchKernelGGL(subsets_enum_kernel<false>, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
   return hipGetLastError();
 }
 
-hipError_t launch_subsets_reduce(const double* part, int64_t units, int p, double* out, hipStream_t st) {
-  if (!part || !out || units < 1 || p < 1 || p > SP) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(subsets_reduce_kernel, dim3(p + 1), dim3(64), 0, st, part, units, p + 1, out);
+hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st) {
+  if (!part || !out || units < 1 || cols < 2 || cols > subsets_inter_cols(SP)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_reduce_kernel, dim3(cols), dim3(64), 0, st, part, units, cols, out);
   return hipGetLastError();
 }
 

@@ -296,6 +296,9 @@ hipError_t launch_mfma_probe(const double* A, const double* B, double* D, int f3
 // steps s0 .. s1 - 1 of every unit, adding to the unit's row of part [units][p + 1]:
 //   part[u][j] += sum over its subsets K containing j of (w(|K| - 1) + w(|K|)) v(K),  part[u][p] += sum w(|K|) v(K)
 // with w = wa, wb below; phi_j = sum_u part[u][j] - sum_u part[u][p] (launch_subsets_reduce, fixed order).
+// With inter (the pairwise interaction index, k_subsets.hip's header) a row is subsets_inter_cols(p) wide:
+//   [0 .. p] as above | T0 | T1_i [p] | T2_ij [p (p - 1) / 2], pairs i < j row-major;  I_ij = T0 - T1_i - T1_j + T2_ij
+// of the column sums, and w holds three more rows: gamma, beta + gamma, alpha + 2 beta + gamma by |K|.
 constexpr int SUBSETS_MAX_P = 32;
 struct SubsetArgs {
   const double* G;         // [p][ldg] training Gram
@@ -303,17 +306,21 @@ struct SubsetArgs {
   const double* H;         // [p][ldh] test Gram
   const double* h;         // [p]
   int64_t ldg, ldh;
-  const double* w;         // [2][SUBSETS_MAX_P + 1]: wa[k] = w(k - 1) (0 for k = 0), wb[k] = w(k) (0 for k = p)
+  const double* w;         // [2][SUBSETS_MAX_P + 1]: wa[k] = w(k - 1) (0 for k = 0), wb[k] = w(k) (0 for k = p);
+                           // inter: [5][SUBSETS_MAX_P + 1], the interaction weights after them
   int p, q;
   double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
   double inv_yy;           // 1 / ||y_test||^2
   uint64_t per;            // high subsets per unit
-  double* part;            // [units][p + 1]
+  double* part;            // [units][p + 1], inter: [units][subsets_inter_cols(p)]
   int32_t* info;           // bit 1: a pivot failed
 };
 int subsets_low_features(int p);
-hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
-hipError_t launch_subsets_reduce(const double* part, int64_t units, int p, double* out, hipStream_t st);
+int subsets_inter_cols(int p);
+hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
+                               hipStream_t st);
+// out[j] = sum over the units of part[u][j], j < cols (the table's width), in a fixed order
+hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st);
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used

@@ -2866,7 +2866,9 @@ uint64_t exact_units(uint64_t n_high) { return std::min(n_high, EXACT_UNITS); }
 // The kernels' view of the loaded problem, the part that SubsetArgs and GroupArgs (Args) have in common: G, g, the test
 // Gram (formed from the test factor in rect mode), the Shapley weights of n players by subset size, the tolerances and
 // a cleared info word.  no_problem: the entry point's error for that; tab: GROUPS_TAB_LEN words to upload into W.tab
-// beside the weights (nullptr: none).
+// beside the weights (nullptr: none).  The weight table carries three more rows, the interaction weights of n players
+// (kernels.h, SubsetArgs::w), which only the interactions kernel reads.
+constexpr int EXACT_W_ROWS = 5;
 template <typename Args>
 int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, const int32_t* tab, Args& a) {
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, no_problem);
@@ -2888,15 +2890,30 @@ int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, cons
     a.ldh = p;
   }
   // w(k) = k! (n - 1 - k)! / n! = 1 / (n C(n - 1, k)); C(31, k) < 2^53 is exact in fp64
-  double w[2 * (EXACT_MAX_PLAYERS + 1)] = {0.0};
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  double w[EXACT_W_ROWS * WR] = {0.0};
   double binom = 1.0;
   for (int k = 0; k < n; ++k) {
     const double wk = 1.0 / ((double)n * binom);
-    w[EXACT_MAX_PLAYERS + 1 + k] = wk;   // wb[k]
+    w[WR + k] = wk;                      // wb[k]
     w[k + 1] = wk;                       // wa[k + 1]
     binom = binom * (double)(n - 1 - k) / (double)(k + 1);
   }
-  TRY(dev_alloc(ctx, W.w, 2 * (EXACT_MAX_PLAYERS + 1)));
+  // w2(s) = s! (n - 2 - s)! / (n - 1)! = 1 / ((n - 1) C(n - 2, s)), s = 0 .. n - 2; C(30, s) < 2^53 is exact in fp64.
+  // By subset size k: gamma = w2(k), beta = w2(k - 1), alpha = w2(k - 2), each 0 outside 0 .. n - 2.
+  double w2[EXACT_MAX_PLAYERS + 3] = {0.0};          // w2[s + 2]: alpha, beta read below 0 without a test
+  binom = 1.0;
+  for (int s = 0; s + 2 <= n; ++s) {
+    w2[s + 2] = 1.0 / ((double)(n - 1) * binom);
+    binom = binom * (double)(n - 2 - s) / (double)(s + 1);
+  }
+  for (int k = 0; k <= n; ++k) {
+    const double al = w2[k], be = w2[k + 1], ga = w2[k + 2];
+    w[2 * WR + k] = ga;
+    w[3 * WR + k] = be + ga;
+    w[4 * WR + k] = al + 2.0 * be + ga;
+  }
+  TRY(dev_alloc(ctx, W.w, EXACT_W_ROWS * WR));
   if (tab) TRY(dev_alloc(ctx, W.tab, GROUPS_TAB_LEN));
   TRY(dev_alloc(ctx, W.info, 8));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // a previous call may still read W.w / W.tab; the copies are from host frames
@@ -2919,16 +2936,17 @@ struct Events {
 };
 
 // The enumeration itself: launch(part, s0, s1) runs steps s0 .. s1 - 1 of every unit into the partial table part
-// [units][n + 1], `steps` of the n_high / units a launch.  out[0 .. n]: the table's column sums (launch_subsets_reduce),
-// a player's phi is its column minus column n; info (may be NULL): the info word.  Leaves the call's timing in W.
+// [units][cols], `steps` of the n_high / units a launch.  out[0 .. cols - 1]: the table's column sums
+// (launch_subsets_reduce).  With n players the first n + 1 columns are phi's: a player's phi is its column minus column
+// n; what follows them is the entry point's own.  info (may be NULL): the info word.  Leaves the call's timing in W.
 template <typename Launch>
-int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int n, uint64_t n_high, uint64_t steps, Launch&& launch,
+int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uint64_t steps, Launch&& launch,
                     double* out, int32_t* info) {
   const uint64_t units = exact_units(n_high);
   const uint64_t per = n_high / units;                 // both powers of two
-  TRY(dev_alloc(ctx, W.part, (size_t)units * (n + 1)));
-  TRY(dev_alloc(ctx, W.out, (size_t)n + 1));
-  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * units * (n + 1), ctx->stream));
+  TRY(dev_alloc(ctx, W.part, (size_t)units * cols));
+  TRY(dev_alloc(ctx, W.out, (size_t)cols));
+  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * units * cols, ctx->stream));
   // every launch is bracketed by events: the call's kernel time and its longest launch (exact_timing)
   const size_t n_launch = (size_t)((per + steps - 1) / steps);
   std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
@@ -2940,9 +2958,9 @@ int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int n, uint64_t n_high, uint64
     HIPCHK(launch(W.part.ptr, s0, std::min(per, s0 + steps)));
     HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
   }
-  HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, n, W.out.ptr, ctx->stream));
+  HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, cols, W.out.ptr, ctx->stream));
   int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (info) *info = bits;
@@ -3000,6 +3018,23 @@ int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
   return LSSPA_OK;
 }
 
+// lsspa_subsets_shapley and, with inter, lsspa_subsets_interactions: out receives the column sums of the partial
+// table, p + 1 or subsets_inter_cols(p) of them (kernels.h).  Same units, launch splitting and timing for both.
+int subsets_enumerate(lsspa_ctx* ctx, bool inter, double* out, int32_t* info) {
+  SubsetArgs a;
+  TRY(subsets_args(ctx, a));
+  const int p = ctx->p;
+  const uint64_t n_high = 1ull << (p - a.q);
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
+  const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_subsets_enum(a, units, s0, s1, inter, ctx->stream);
+  };
+  return exact_enumerate(ctx, ctx->sub, inter ? subsets_inter_cols(p) : p + 1, n_high, steps, launch, out, info);
+}
+
 // ---- ... over groups of columns (k_groups.hip) ----
 // One enumeration launch takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high subset
 // counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
@@ -3041,20 +3076,34 @@ extern "C" {
 int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   if (!phi) return ctx->fail(LSSPA_ERR_ARG, "phi is NULL");
-  SubsetArgs a;
-  TRY(subsets_args(ctx, a));
-  const int p = ctx->p;
-  const uint64_t n_high = 1ull << (p - a.q);
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
   double out[EXACT_MAX_PLAYERS + 1];
-  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
-    a.part = part;
-    return launch_subsets_enum(a, units, s0, s1, ctx->stream);
-  };
-  TRY(exact_enumerate(ctx, ctx->sub, p, n_high, steps, launch, out, info));
+  TRY(subsets_enumerate(ctx, false, out, info));
+  const int p = ctx->p;
   for (int j = 0; j < p; ++j) phi[j] = out[j] - out[p];
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi, double* inter, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!phi || !inter) return ctx->fail(LSSPA_ERR_ARG, "phi / inter is NULL");
+  std::vector<double> out((size_t)subsets_inter_cols(SUBSETS_MAX_P));
+  TRY(subsets_enumerate(ctx, true, out.data(), info));
+  const int p = ctx->p;
+  for (int j = 0; j < p; ++j) phi[j] = out[j] - out[p];
+  // I_ij = T0 - T1_i - T1_j + T2_ij (k_subsets.hip)
+  const double t0 = out[p + 1];
+  const double* t1 = out.data() + p + 2;
+  const double* t2 = t1 + p;
+  for (int i = 0; i < p; ++i) {
+    inter[(size_t)i * p + i] = 0.0;
+    for (int j = i + 1; j < p; ++j, ++t2) {
+      const double v = ((t0 - t1[i]) - t1[j]) + *t2;
+      inter[(size_t)i * p + j] = v;
+      inter[(size_t)j * p + i] = v;
+    }
+  }
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -3103,7 +3152,7 @@ int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, doubl
     a.part = part;
     return launch_groups_enum(a, units, s0, s1, ctx->stream);
   };
-  TRY(exact_enumerate(ctx, ctx->grp, ng, n_high, steps, launch, out, info));
+  TRY(exact_enumerate(ctx, ctx->grp, ng + 1, n_high, steps, launch, out, info));
   for (int r = 0; r < ng; ++r) phi[L.gid[r]] = out[r] - out[ng];
   return LSSPA_OK;
 } catch (...) {

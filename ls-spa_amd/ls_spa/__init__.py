@@ -3,17 +3,18 @@
 Same public names as the reference's ``from .ls_spa import *`` (ls_spa/__init__.py:1):
 ``ls_spa``, ``ShapleyResults``, ``SizeIncompatible``, ``validate_data``,
 ``merge_sample_mean``, ``merge_sample_cov``, ``square_shapley``, ``reduce_data``,
-``error_estimates``; ``ls_spa_groups`` (sampled attribution over groups of columns) is this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
+``error_estimates``; ``ls_spa_groups`` (sampled attribution over groups of columns) and ``ls_spa_interactions`` (exact
+pairwise Shapley interaction values, p <= 32) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
-from ._results import ShapleyResults, SizeIncompatible, validate_data
+from ._results import InteractionResults, ShapleyResults, SizeIncompatible, validate_data
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
-from ._driver import ls_spa, ls_spa_groups, reduce_data, square_shapley, run_estimator, release
+from ._driver import ls_spa, ls_spa_groups, ls_spa_interactions, reduce_data, square_shapley, run_estimator, release
 from ._native import LSSPANativeError
 from ._rccl import NativeComm
 
 __all__ = [
-    "ls_spa", "ls_spa_groups", "ShapleyResults", "SizeIncompatible", "validate_data", "merge_sample_mean",
+    "ls_spa", "ls_spa_groups", "ls_spa_interactions", "ShapleyResults", "InteractionResults", "SizeIncompatible", "validate_data", "merge_sample_mean",
     "merge_sample_cov", "square_shapley", "reduce_data", "error_estimates",
     "error_estimates_lowrank", "run_estimator", "release", "LSSPANativeError", "NativeComm",
 ]

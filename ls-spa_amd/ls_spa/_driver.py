@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import ShapleyResults, validate_data
+from ._results import InteractionResults, ShapleyResults, validate_data
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -703,7 +703,8 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
 
     method:  None (reference behaviour), 'exact', 'random', 'argsort', 'permutohedron' or 'subsets'.
         'subsets' (p <= 32): the exact attribution from the R^2 of all 2^p feature subsets, enumerated on the GPU in
-        fp64 (include/lsspa.h, lsspa_subsets_shapley) -- no orderings, no sampling loop; overall_error 0,
+        fp64 (include/lsspa.h, lsspa_subsets_shapley; ``ls_spa_interactions`` adds the pairwise interaction values
+        from the same enumeration) -- no orderings, no sampling loop; overall_error 0,
         attribution_errors zeros, error_history empty, as the reference's exact path gives them.  The sampling
         parameters (max_samples, batch_size, num_batches, tolerance, seed, antithetical, lookahead, lanes,
         error_estimator, precision) are ignored -- phi, theta and r_squared are fp64 whatever an earlier call of the
@@ -948,10 +949,11 @@ def group_labels(groups, p, max_groups=GROUPS_MAX_G):
 
 
 def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attribution_history, device, row_sharded,
-                    checkpoint, comm, engine, groups=None):
+                    checkpoint, comm, engine, groups=None, interactions=False):
     """ls_spa(method='subsets'): the data reduction as for every method, then the exact attribution over all 2^p
     subsets -- with groups=, over all 2^g subsets of the groups of columns -- on the engine.  No ordering source,
-    generator or sampling loop exists in this call."""
+    generator or sampling loop exists in this call.  interactions (ls_spa_interactions, no groups): the same call
+    with the pairwise interaction index from the same enumeration, returned as InteractionResults."""
     p = X_train.shape[1]
     if perms is not None:
         raise ValueError("pass either perms= or method=, not both")
@@ -985,7 +987,10 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
         else:
             engine.load_data(X_train, X_test, y_train, y_test, reg)
         theta, r_squared, info = engine.full_fit()
-        phi, bits = engine.subsets_shapley() if labels is None else engine.groups_shapley(labels)
+        if interactions:
+            phi, raw, bits = engine.subsets_interactions()
+        else:
+            phi, bits = engine.subsets_shapley() if labels is None else engine.groups_shapley(labels)
         if (bits | info) & 1:
             warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
                           "of collinear features is not meaningful (the reference's is not either)",
@@ -1006,9 +1011,42 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
             finally:
                 if kept is not None:
                     kept.release()
+    if interactions:
+        # SHAP's matrix: half the index off the diagonal, the main effect phi_i - sum_{j != i} Phi_ij on it
+        Phi = 0.5 * np.asarray(raw, dtype=np.float64)
+        np.fill_diagonal(Phi, 0.0)
+        np.fill_diagonal(Phi, phi - Phi.sum(axis=1))
+        return InteractionResults(interactions=Phi, attribution=phi, theta=theta, r_squared=r_squared)
     return ShapleyResults(attribution=phi, theta=theta, overall_error=0.0,
                           attribution_errors=np.zeros(p if labels is None else n_players),
                           r_squared=r_squared, error_history=np.zeros(0), attribution_history=None)
+
+
+def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, device=0, row_sharded=False, comm=None,
+                        _engine=None):
+    """Exact pairwise Shapley interaction values of the out-of-sample R^2 (p <= 32).
+
+    The game is that of ``ls_spa``: v(S) is the out-of-sample R^2 of the model fitted on the features in S.  From the
+    same enumeration of all 2^p subsets on the GPU that ``ls_spa(method='subsets')`` runs (fp64, bitwise reproducible;
+    include/lsspa.h, lsspa_subsets_interactions) comes, beside the attribution, the Shapley interaction index
+
+        I_ij = sum over S without i and j of |S|! (p - 2 - |S|)! / (p - 1)! (v(S+i+j) - v(S+i) - v(S+j) + v(S)),
+
+    positive where two features create R^2 together (complements), negative where they share it (correlated
+    regressors).  Returns ``InteractionResults``: ``interactions`` is the p x p matrix Phi in SHAP's convention --
+    Phi_ij = I_ij / 2 for i != j, Phi_ii = phi_i - sum_{j != i} Phi_ij -- so Phi is symmetric, row i sums to
+    ``attribution[i]`` and the whole matrix to ``r_squared``; at p = 1 it is [[phi_0]].  ``attribution``, ``theta`` and
+    ``r_squared`` are exactly those of ``ls_spa(method='subsets')``, as are ``reg``, ``device``, ``row_sharded``,
+    ``comm`` and the RuntimeWarning for a Gram matrix that is not numerically positive definite.  p > 32 raises
+    ValueError.  Interactions between groups of columns (``groups=``) are not computed."""
+    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
+    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
+    validate_data(X_train, X_test, y_train, y_test)
+    if y_train.ndim != 1 or y_test.ndim != 1:
+        raise ValueError("y_train and y_test must be one-dimensional")
+    return _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, perms=None, return_attribution_history=False,
+                           device=device, row_sharded=row_sharded, checkpoint=None, comm=comm, engine=_engine,
+                           interactions=True)
 
 
 GROUPS_AUTO_MAX_G = 20     # ls_spa_groups(method='auto'): the enumeration up to here (26 ms at g = 20, README.md)

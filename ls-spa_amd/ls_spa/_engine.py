@@ -263,6 +263,15 @@ class HipEngine:
         self._check(self._lib.lsspa_subsets_shapley(self._h, N.dptr(phi), C.byref(info)))
         return phi, info.value
 
+    def subsets_interactions(self):
+        """(phi, I, info): phi as subsets_shapley gives it (bitwise) and the raw pairwise Shapley interaction index
+        I [p][p] from the same enumeration (include/lsspa.h, lsspa_subsets_interactions): symmetric, 0 on the diagonal.
+        subsets_timing() then speaks of this call."""
+        phi, inter = np.empty(self.p), np.empty((self.p, self.p))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_subsets_interactions(self._h, N.dptr(phi), N.dptr(inter), C.byref(info)))
+        return phi, inter, info.value
+
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
         self._check(getter(self._h, C.byref(ms), C.byref(mx), C.byref(n)))
@@ -275,7 +284,8 @@ class HipEngine:
         return out
 
     def subsets_timing(self):
-        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley call."""
+        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley or subsets_interactions
+        call."""
         return self._exact_timing(self._lib.lsspa_subsets_timing)
 
     def debug_subset_values(self, masks):

@@ -43,6 +43,33 @@ class ShapleyResults:
         return "\n".join(lines)
 
 
+@dataclass
+class InteractionResults:
+    """What ``ls_spa_interactions`` returns.  ``interactions`` [p][p] is the Shapley interaction matrix in SHAP's
+    convention: symmetric, half the pairwise interaction index off the diagonal, row i summing to ``attribution[i]``
+    and the whole matrix to ``r_squared``.  The other three fields are those of ``ls_spa(method='subsets')``."""
+    interactions: np.ndarray
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+
+    def __repr__(self):
+        pad = " " * 8
+        inter = np.asarray(self.interactions)
+        off = inter - np.diag(np.diag(inter))
+        lines = [
+            "",
+            f"{pad}p = {np.asarray(self.attribution).size}",
+            f"{pad}Out-of-sample R^2 with all features: {self.r_squared:.2f}",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}Main effects (diagonal): {_head(np.diag(inter))}",
+            f"{pad}Largest pairwise interaction: {float(np.abs(off).max()) if off.size else 0.0:.2E}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
 class SizeIncompatible(Exception):
     """Raised when the shapes of the four data arrays do not fit together."""
 
