@@ -133,13 +133,28 @@ int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi /* [p] */, double* in
  * bounded launches, bitwise reproducible, LSSPA_INFO_NOT_PD in info, nothing of the sampling path and nothing of
  * lsspa_subsets_shapley's state touched.  g > 32, p > 64, a label outside -1 .. g-1, an empty group, g < 1 or no
  * problem loaded is LSSPA_ERR_ARG (lsspa_last_error names it).
- *   lsspa_groups_timing      : as lsspa_subsets_timing, for the last lsspa_groups_shapley call
+ *   lsspa_groups_timing      : as lsspa_subsets_timing, for the last lsspa_groups_shapley or
+ *                              lsspa_groups_interactions call
  *   lsspa_debug_group_values : test hook -- u[i] = u(masks[i]) (bit k = group k; masks < 2^g) by the enumeration's own
  *                              device code; a failed pivot is LSSPA_ERR_STATE */
 int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */, int32_t* info);
 int lsspa_groups_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches);
 int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const uint64_t* masks, int64_t n,
                              double* u);
+
+/* Exact pairwise Shapley interaction index between GROUPS of columns, from the same enumeration of all 2^g group
+ * subsets (g <= 32, p <= 64) and the same u as lsspa_groups_shapley:
+ *   I_kl = sum over S without k and l of |S|! (g - 2 - |S|)! / (g - 1)! (u(S + k + l) - u(S + k) - u(S + l) + u(S)).
+ * inter [g][g], indexed by the caller's labels like phi, is symmetric, holds the raw index I_kl off the diagonal and 0
+ * on it (SHAP's matrix as for lsspa_subsets_interactions; its rows sum to phi and the whole to R^2(all columns) -
+ * R^2(B alone)).  phi [g] is bitwise the phi of lsspa_groups_shapley.  All-singleton labels 0 .. p-1 give
+ * lsspa_subsets_interactions' index.  Errors, limits, labels, info, fp64, bounded launches, bitwise reproducibility and
+ * "nothing of the sampling path and nothing of lsspa_subsets_shapley's state touched" are those of lsspa_groups_shapley
+ * (NULL inter is LSSPA_ERR_ARG); the two calls share their buffers, and this call leaves its timing where
+ * lsspa_groups_timing reads it.  The partial table is g (g + 3) / 2 + 2 columns wide: 8192 x 562 doubles, about 37 MB
+ * of device memory, at g = 32. */
+int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */,
+                              double* inter /* [g*g] */, int32_t* info);
 
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift

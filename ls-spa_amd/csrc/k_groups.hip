@@ -25,6 +25,21 @@
 // kept per lane, reduced once per launch by fixed butterflies into the unit's row of a partial table [units][g + 1]
 // (low groups first, then the high ones, then b) which launch_subsets_reduce sums in fixed order.  No floating-point
 // atomics: the result is bitwise the same from call to call.
+//
+// Pairwise Shapley interaction index between groups (lsspa_groups_interactions, the INTER instantiation of the
+// enumeration kernel): k_subsets.hip's sums with players = groups of the layout,
+//   I_kl = T0 - T1_k - T1_l + T2_kl,   T0 = sum_K gamma u,   T1_k = sum_{K with k} (beta + gamma) u,
+//   T2_kl = sum_{K with k and l} (alpha + 2 beta + gamma) u,
+// and a unit's row of the partial table [0 .. g] as above | T0 | T1 [g] | T2 [g (g - 1) / 2] (layout numbering, pairs
+// i < j row-major: subsets_inter_cols(g) columns).  Only wave 0 holds values here, and its registers are the scarce ones
+// (the 6 x 6 Cholesky), so per step it keeps three sums a lane (for T0, the low groups' T1 and the low-low pairs) and
+// hands the rest to all four waves through LDS, under the barrier that ends a step anyway:
+//   - dv[T] = (alpha + 2 beta + gamma) u(Hs + T) per lane.  High-low pair (t, j) is the sum over the lanes T with t of the
+//     steps with j in hi: wave w, lane T keeps that sum for the eight high groups j = 8 w .. 8 w + 7;
+//   - wave 0's sums of the step over T of (beta + gamma) u and of dv.  Both belong to hi alone: the first goes to T1 of
+//     the high groups in hi (thread j keeps group j's), the second to the pairs of high groups inside hi, which are
+//     dealt over the 256 threads (at most HH = 2 a thread) with their masks built once.
+// Every cell of the table is written by one thread, the sums are fixed butterflies and fixed loops: bitwise reproducible.
 #include "kernels.h"
 
 #include <algorithm>
@@ -40,6 +55,9 @@ constexpr int LDM = GP + 1;                    // row stride of the compacted ma
 constexpr int XC = GQ + 1;                     // row stride of X and Y
 constexpr int ZC = GQ + 2;                     // row stride of Z: columns 0 .. ql of X^T H X, then X^T h
 constexpr int NT = 256;                        // four waves
+constexpr int GW = GG / 4;                     // INTER: high groups whose high-low sums one wave keeps (8)
+constexpr int GHI = GG - 1;                    // INTER: high groups at most (launch_groups_enum)
+constexpr int HH = (GHI * (GHI - 1) / 2 + NT - 1) / NT;   // INTER: pairs of high groups a thread owns at most (2)
 
 struct GrpShared {
   double M[GP * LDM];      // compacted [G g] being eliminated: rows = columns of the subset, odd stride
@@ -57,11 +75,28 @@ struct GrpShared {
   int lgrp[GQ];
 };
 
+// what the INTER instantiation adds (the other one declares none of it)
+struct GrpInterShared {
+  double w2[3 * (GG + 1)];   // gamma, beta + gamma, alpha + 2 beta + gamma by |K|
+  double dv[64];             // the step's (alpha + 2 beta + gamma) u per lane of wave 0
+  double se, sd;             // the step's sums over wave 0 of (beta + gamma) u and of dv
+};
+
 __device__ inline double wave_sum(double x) {
   // fixed butterfly, then lane 0's value for everyone: the same order on every call
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
   return __shfl(x, 0, 64);
+}
+
+// wave_sum of one value per low group at once: each by the butterfly above, the chains interleaved -- a shuffle's latency
+// is most of a lone wave_sum, and the interactions kernel ends a launch with up to 48 of them a wave
+__device__ inline void wave_sum_low(double (&x)[GQ]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int t = 0; t < GQ; ++t) x[t] += __shfl_xor(x[t], o, 64);
+  }
 }
 
 // u(Hs + T) of this thread's low subset T = tid (0 for threads >= 2^gl).  Enters and leaves with the workgroup in
@@ -227,8 +262,15 @@ __device__ void load_shared(GrpShared& sh, const GroupArgs& a, int tid) {
   __syncthreads();
 }
 
+// column of pair (i, j), i < j, among the g (g - 1) / 2 pairs of a row of the interactions table
+__device__ inline int pair_col(int g, int i, int j) { return i * (2 * g - i - 1) / 2 + (j - i - 1); }
+
+// INTER: the interaction sums T0, T1, T2 beside phi's (lsspa_groups_interactions); a row of part is then
+// subsets_inter_cols(g) wide.  Everything of the phi-only instantiation is in both, unchanged.
+template <bool INTER>
 __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s0, uint64_t s1) {
   __shared__ GrpShared sh;
+  __shared__ GrpInterShared si;                // INTER only: never referenced, hence not allocated, otherwise
   const int tid = threadIdx.x;
   const int ng = a.ng, gl = a.gl, gh = a.gh;
   load_shared(sh, a, tid);
@@ -236,6 +278,30 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
 #pragma unroll
   for (int j = 0; j < GG; ++j) acc[j] = 0.0;
   double c_own = 0.0, b_own = 0.0;
+  // INTER only (dead code otherwise)
+  double hl[GW], hh[HH];
+  uint32_t hm[HH];
+  double g_own = 0.0, e_own = 0.0, d_own = 0.0, t1h = 0.0;
+  if constexpr (INTER) {
+    for (int e = tid; e < 3 * (GG + 1); e += NT) si.w2[e] = a.w[2 * (GG + 1) + e];
+#pragma unroll
+    for (int j = 0; j < GW; ++j) hl[j] = 0.0;
+    // pair number e = tid + NT r of the gh (gh - 1) / 2 pairs j1 < j2 of high groups, as a mask over hi.  A slot without
+    // a pair gets bit 31, which no hi contains: hi < 2^gh and gh <= 31 (launch_groups_enum refuses more; groups_layout
+    // never makes more, for gh = 32 means g = 32 without a low group, every group of 7 columns or more, and
+    // 32 x 7 > 64 = GROUPS_MAX_P).
+#pragma unroll
+    for (int r = 0; r < HH; ++r) {
+      hh[r] = 0.0;
+      int rem = tid + NT * r, j1 = 0;
+      while (j1 < gh - 1 && rem >= gh - 1 - j1) {
+        rem -= gh - 1 - j1;
+        ++j1;
+      }
+      hm[r] = (j1 < gh - 1) ? ((1u << j1) | (1u << (j1 + 1 + rem))) : 0x80000000u;
+    }
+    __syncthreads();                           // w2
+  }
   bool bad = false;
   const bool live = tid < (1 << gl);
   const int kt = __popc(tid);
@@ -251,10 +317,45 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
       for (int j = 0; j < GG; ++j)
         if (j < gh && ((hi >> j) & 1ull)) acc[j] += c;
     }
+    if constexpr (INTER) {
+      // si.dv, se, sd: written here, after the last barrier of group_values; read below, before the first barrier of the
+      // next step's group_values
+      if (tid < 64) {
+        double e = 0.0, d = 0.0;
+        if (live) {
+          const int k = __popcll(hi) + kt;
+          e = si.w2[GG + 1 + k] * v;
+          d = si.w2[2 * (GG + 1) + k] * v;
+          g_own += si.w2[k] * v;
+          e_own += e;
+          d_own += d;
+        }
+        si.dv[tid] = d;
+        const double se = wave_sum(e), sd = wave_sum(d);
+        if (tid == 0) {
+          si.se = se;
+          si.sd = sd;
+        }
+      }
+    }
     __syncthreads();
+    if constexpr (INTER) {
+      const uint32_t h32 = (uint32_t)hi;       // gh <= 31
+      const double d = si.dv[tid & 63];
+      const int jw = (tid >> 6) * GW;
+#pragma unroll
+      for (int j = 0; j < GW; ++j)
+        if ((h32 >> (jw + j)) & 1u) hl[j] += d;          // (bits of hi from gh on are 0)
+      if ((h32 >> (tid & 31)) & 1u) t1h += si.se;        // thread j < gh: T1 of high group j (the others' is not read)
+      const double sd = si.sd;
+#pragma unroll
+      for (int r = 0; r < HH; ++r)
+        if ((h32 & hm[r]) == hm[r]) hh[r] += sd;
+    }
   }
+  const int cols = INTER ? ng + 2 + ng + ng * (ng - 1) / 2 : ng + 1;
   if (tid < 64) {     // the live lanes all sit in the first wave
-    double* part = a.part + (int64_t)blockIdx.x * (ng + 1);
+    double* part = a.part + (int64_t)blockIdx.x * cols;
 #pragma unroll
     for (int t = 0; t < GQ; ++t) {
       if (t < gl) {
@@ -271,6 +372,56 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
     }
     const double tb = wave_sum(b_own);
     if (tid == 0) part[ng] += tb;
+  }
+  if constexpr (INTER) {
+    double* part = a.part + (int64_t)blockIdx.x * cols;
+    double* t1 = part + ng + 2;
+    double* t2 = t1 + ng;
+    const int lane = tid & 63;
+    const bool lane_live = lane < (1 << gl);
+    double x[GQ];
+    if (tid < 64) {
+      const double t0 = wave_sum(g_own);
+      if (tid == 0) part[ng + 1] += t0;
+#pragma unroll
+      for (int t = 0; t < GQ; ++t) x[t] = (lane_live && ((lane >> t) & 1)) ? e_own : 0.0;
+      wave_sum_low(x);
+#pragma unroll
+      for (int t = 0; t < GQ; ++t)
+        if (tid == 0 && t < gl) t1[t] += x[t];
+#pragma unroll
+      for (int u = 0; u < GQ - 1; ++u) {          // low-low pairs (u, t), u < t
+        if (u < gl - 1) {
+#pragma unroll
+          for (int t = 0; t < GQ; ++t)
+            x[t] = (t > u && lane_live && ((lane >> u) & 1) && ((lane >> t) & 1)) ? d_own : 0.0;
+          wave_sum_low(x);
+#pragma unroll
+          for (int t = u + 1; t < GQ; ++t)
+            if (tid == 0 && t < gl) t2[pair_col(ng, u, t)] += x[t];
+        }
+      }
+    }
+    if (tid < gh) t1[gl + tid] += t1h;            // (gh <= 31: tid & 31 above was tid)
+    const int jw = (tid >> 6) * GW;
+#pragma unroll
+    for (int j = 0; j < GW; ++j) {
+      if (jw + j < gh) {                          // the same for the whole wave: high-low pairs (t, gl + jw + j)
+#pragma unroll
+        for (int t = 0; t < GQ; ++t) x[t] = (lane_live && ((lane >> t) & 1)) ? hl[j] : 0.0;
+        wave_sum_low(x);
+#pragma unroll
+        for (int t = 0; t < GQ; ++t)
+          if (lane == 0 && t < gl) t2[pair_col(ng, t, gl + jw + j)] += x[t];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < HH; ++r) {                // high-high pairs: every thread holds the sums of its own
+      if (hm[r] != 0x80000000u) {
+        const int j1 = __ffs((int)hm[r]) - 1, j2 = 31 - __clz((int)hm[r]);
+        t2[pair_col(ng, gl + j1, gl + j2)] += hh[r];
+      }
+    }
   }
   if (__any(bad) && (tid & 63) == 0) atomicOr(a.info, 1);
 }
@@ -358,11 +509,17 @@ const char* groups_layout(const int32_t* labels, int p, int g, GroupLayout& L) {
   return nullptr;
 }
 
-hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st) {
+hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
+                              hipStream_t st) {
   if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
   // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^gh
   if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(groups_enum_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+  if (inter) {
+    if (a.gh > GHI) return hipErrorInvalidValue;   // the kernel's pair masks (no layout of <= 64 columns has more)
+    hipLaunchKernelGGL(groups_enum_kernel<true>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+  } else {
+    hipLaunchKernelGGL(groups_enum_kernel<false>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+  }
   return hipGetLastError();
 }
 

@@ -334,7 +334,9 @@ hipError_t launch_subsets_test_gram(const double* Ft, int64_t ldf, const double*
 // first).  tab: the columns in layout order (baseline, high groups, low groups), per column its high group (-1: none)
 // and its place inside it, the high groups' sizes and per low column its low group.  High subset number hi is the set
 // of high groups {j : bit j of hi}.  Units, steps and the partial table [units][g + 1] (layout numbering, then b) are
-// those of launch_subsets_enum; launch_subsets_reduce sums the table.
+// those of launch_subsets_enum; launch_subsets_reduce sums the table.  With inter (the pairwise interaction index
+// between groups, k_groups.hip's header) a row is subsets_inter_cols(g) wide, as launch_subsets_enum's with p = g and
+// the layout's numbering, and w holds the three rows of interaction weights of g players.
 constexpr int GROUPS_MAX_G = 32, GROUPS_MAX_P = 64, GROUPS_LOW_COLS = 6;
 constexpr int GROUPS_TAB_COLS = 0, GROUPS_TAB_COLGRP = GROUPS_MAX_P, GROUPS_TAB_COLIN = 2 * GROUPS_MAX_P,
               GROUPS_TAB_HSIZE = 3 * GROUPS_MAX_P, GROUPS_TAB_LGRP = GROUPS_TAB_HSIZE + GROUPS_MAX_G,
@@ -352,16 +354,18 @@ struct GroupArgs {
   const double* H;         // [p][ldh] test Gram (symmetric)
   const double* h;         // [p]
   int64_t ldg, ldh;
-  const double* w;         // [2][GROUPS_MAX_G + 1]: wa[k] = w(k - 1) (0 for k = 0), wb[k] = w(k) (0 for k = g)
+  const double* w;         // [2][GROUPS_MAX_G + 1]: wa[k] = w(k - 1) (0 for k = 0), wb[k] = w(k) (0 for k = g);
+                           // inter: [5][GROUPS_MAX_G + 1], the interaction weights after them
   const int32_t* tab;      // GroupLayout::tab on the device
   int p, ng, nb, gl, gh, ql;
   double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
   double inv_yy;           // 1 / ||y_test||^2
   uint64_t per;            // high subsets per unit
-  double* part;            // [units][g + 1]
+  double* part;            // [units][g + 1], inter: [units][subsets_inter_cols(g)]
   int32_t* info;           // bit 1: a pivot failed
 };
-hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
+hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
+                              hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

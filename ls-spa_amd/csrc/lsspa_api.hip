@@ -3069,6 +3069,28 @@ int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, 
   return LSSPA_OK;
 }
 
+// lsspa_groups_shapley and, with inter, lsspa_groups_interactions: the layout L of the labels, and in out the column
+// sums of the partial table, g + 1 or subsets_inter_cols(g) of them in the layout's numbering (kernels.h).  Same units,
+// launch splitting and timing for both.
+int groups_enumerate(lsspa_ctx* ctx, bool inter, const int32_t* labels, int32_t g, GroupLayout& L, double* out,
+                     int32_t* info) {
+  GroupArgs a;
+  TRY(groups_args(ctx, labels, g, a, L));
+  const int ng = L.ng;
+  const uint64_t n_high = 1ull << L.gh;
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
+  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
+  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
+  const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
+  const uint64_t steps = std::max<uint64_t>(1, per_launch / units);
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_groups_enum(a, units, s0, s1, inter, ctx->stream);
+  };
+  return exact_enumerate(ctx, ctx->grp, inter ? subsets_inter_cols(ng) : ng + 1, n_high, steps, launch, out, info);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3136,24 +3158,39 @@ int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, 
 int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   if (!phi || !labels) return ctx->fail(LSSPA_ERR_ARG, "labels / phi is NULL");
-  GroupArgs a;
   GroupLayout L;
-  TRY(groups_args(ctx, labels, g, a, L));
-  const int ng = L.ng;
-  const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
-  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
-  const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
-  const uint64_t steps = std::max<uint64_t>(1, per_launch / units);
   double out[EXACT_MAX_PLAYERS + 1];
-  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
-    a.part = part;
-    return launch_groups_enum(a, units, s0, s1, ctx->stream);
-  };
-  TRY(exact_enumerate(ctx, ctx->grp, ng + 1, n_high, steps, launch, out, info));
+  TRY(groups_enumerate(ctx, false, labels, g, L, out, info));
+  const int ng = L.ng;
   for (int r = 0; r < ng; ++r) phi[L.gid[r]] = out[r] - out[ng];
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, double* inter,
+                              int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!phi || !inter || !labels) return ctx->fail(LSSPA_ERR_ARG, "labels / phi / inter is NULL");
+  GroupLayout L;
+  std::vector<double> out((size_t)subsets_inter_cols(GROUPS_MAX_G));
+  TRY(groups_enumerate(ctx, true, labels, g, L, out.data(), info));
+  const int ng = L.ng;
+  for (int r = 0; r < ng; ++r) phi[L.gid[r]] = out[r] - out[ng];
+  // I_kl = T0 - T1_k - T1_l + T2_kl in the layout's numbering (k_groups.hip), then to the caller's labels
+  const double t0 = out[ng + 1];
+  const double* t1 = out.data() + ng + 2;
+  const double* t2 = t1 + ng;
+  for (int i = 0; i < ng; ++i) {
+    const size_t gi = (size_t)L.gid[i];
+    inter[gi * ng + gi] = 0.0;
+    for (int j = i + 1; j < ng; ++j, ++t2) {
+      const size_t gj = (size_t)L.gid[j];
+      const double v = ((t0 - t1[i]) - t1[j]) + *t2;
+      inter[gi * ng + gj] = v;
+      inter[gj * ng + gi] = v;
+    }
+  }
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

@@ -4,7 +4,7 @@ Same public names as the reference's ``from .ls_spa import *`` (ls_spa/__init__.
 ``ls_spa``, ``ShapleyResults``, ``SizeIncompatible``, ``validate_data``,
 ``merge_sample_mean``, ``merge_sample_cov``, ``square_shapley``, ``reduce_data``,
 ``error_estimates``; ``ls_spa_groups`` (sampled attribution over groups of columns) and ``ls_spa_interactions`` (exact
-pairwise Shapley interaction values, p <= 32) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
+pairwise Shapley interaction values between features, p <= 32, or between groups of columns, g <= 32) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import InteractionResults, ShapleyResults, SizeIncompatible, validate_data

@@ -952,8 +952,9 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
                     checkpoint, comm, engine, groups=None, interactions=False):
     """ls_spa(method='subsets'): the data reduction as for every method, then the exact attribution over all 2^p
     subsets -- with groups=, over all 2^g subsets of the groups of columns -- on the engine.  No ordering source,
-    generator or sampling loop exists in this call.  interactions (ls_spa_interactions, no groups): the same call
-    with the pairwise interaction index from the same enumeration, returned as InteractionResults."""
+    generator or sampling loop exists in this call.  interactions (ls_spa_interactions): the same call with the
+    pairwise interaction index between the players, features or groups, from the same enumeration, returned as
+    InteractionResults."""
     p = X_train.shape[1]
     if perms is not None:
         raise ValueError("pass either perms= or method=, not both")
@@ -988,7 +989,7 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
             engine.load_data(X_train, X_test, y_train, y_test, reg)
         theta, r_squared, info = engine.full_fit()
         if interactions:
-            phi, raw, bits = engine.subsets_interactions()
+            phi, raw, bits = engine.subsets_interactions() if labels is None else engine.groups_interactions(labels)
         else:
             phi, bits = engine.subsets_shapley() if labels is None else engine.groups_shapley(labels)
         if (bits | info) & 1:
@@ -1022,9 +1023,10 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
                           r_squared=r_squared, error_history=np.zeros(0), attribution_history=None)
 
 
-def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, device=0, row_sharded=False, comm=None,
-                        _engine=None):
-    """Exact pairwise Shapley interaction values of the out-of-sample R^2 (p <= 32).
+def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, groups=None, device=0, row_sharded=False,
+                        comm=None, _engine=None):
+    """Exact pairwise Shapley interaction values of the out-of-sample R^2, between features (p <= 32) or, with
+    ``groups=``, between groups of columns (g <= 32 groups over p <= 64 columns).
 
     The game is that of ``ls_spa``: v(S) is the out-of-sample R^2 of the model fitted on the features in S.  From the
     same enumeration of all 2^p subsets on the GPU that ``ls_spa(method='subsets')`` runs (fp64, bitwise reproducible;
@@ -1038,7 +1040,16 @@ def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, device=0, r
     ``attribution[i]`` and the whole matrix to ``r_squared``; at p = 1 it is [[phi_0]].  ``attribution``, ``theta`` and
     ``r_squared`` are exactly those of ``ls_spa(method='subsets')``, as are ``reg``, ``device``, ``row_sharded``,
     ``comm`` and the RuntimeWarning for a Gram matrix that is not numerically positive definite.  p > 32 raises
-    ValueError.  Interactions between groups of columns (``groups=``) are not computed."""
+    ValueError.
+
+    groups:  a length-p sequence of integer labels, one per column, as for ``ls_spa(method='subsets', groups=)``: k in
+        0 .. g-1 puts the column into group k, -1 into the always-included baseline.  The players are then the g groups
+        -- the variables, where a one-hot factor or a spline basis is several columns -- and the game is that call's
+        u(S) = R^2 of the baseline plus the columns of the groups in S (include/lsspa.h, lsspa_groups_interactions).
+        ``interactions`` is g x g in the same convention: row k sums to ``attribution[k]``, the group's Shapley value as
+        ``ls_spa(method='subsets', groups=)`` returns it, and the whole matrix to ``r_squared`` minus the R^2 of the
+        baseline alone.  ``theta`` keeps length p.  The limits and errors are that call's: g <= 32, p <= 64 (the
+        p <= 32 limit does not apply), labels refused with ValueError before any GPU work."""
     X_train, X_test = np.asarray(X_train), np.asarray(X_test)
     y_train, y_test = np.asarray(y_train), np.asarray(y_test)
     validate_data(X_train, X_test, y_train, y_test)
@@ -1046,7 +1057,7 @@ def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, device=0, r
         raise ValueError("y_train and y_test must be one-dimensional")
     return _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, perms=None, return_attribution_history=False,
                            device=device, row_sharded=row_sharded, checkpoint=None, comm=comm, engine=_engine,
-                           interactions=True)
+                           groups=groups, interactions=True)
 
 
 GROUPS_AUTO_MAX_G = 20     # ls_spa_groups(method='auto'): the enumeration up to here (26 ms at g = 20, README.md)

@@ -310,8 +310,23 @@ class HipEngine:
         self._check(self._lib.lsspa_groups_shapley(self._h, N.iptr(labels), g, N.dptr(phi), C.byref(info)))
         return phi, info.value
 
+    def groups_interactions(self, labels):
+        """(phi, I, info): phi as groups_shapley gives it (bitwise) and the raw pairwise Shapley interaction index
+        I [g][g] between the groups from the same enumeration (include/lsspa.h, lsspa_groups_interactions): symmetric,
+        0 on the diagonal, indexed by the labels like phi.  groups_timing() then speaks of this call."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        n = max(g, 1)
+        phi, inter = np.empty(n), np.empty((n, n))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_groups_interactions(self._h, N.iptr(labels), g, N.dptr(phi), N.dptr(inter),
+                                                        C.byref(info)))
+        return phi, inter, info.value
+
     def groups_timing(self):
-        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley call."""
+        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley or groups_interactions
+        call."""
         return self._exact_timing(self._lib.lsspa_groups_timing)
 
     def debug_group_values(self, labels, masks):

@@ -113,6 +113,7 @@ SIGNATURES = {
     "lsspa_subsets_timing": (C.c_int, [_vp, _pd, _pd, _pi64]),
     "lsspa_debug_subset_values": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64, _pd]),
     "lsspa_groups_shapley": (C.c_int, [_vp, _pi32, _i32, _pd, _pi32]),
+    "lsspa_groups_interactions": (C.c_int, [_vp, _pi32, _i32, _pd, _pd, _pi32]),
     "lsspa_groups_timing": (C.c_int, [_vp, _pd, _pd, _pi64]),
     "lsspa_debug_group_values": (C.c_int, [_vp, _pi32, _i32, C.POINTER(C.c_uint64), _i64, _pd]),
     "lsspa_set_players": (C.c_int, [_vp, _pi32, _i32]),

@@ -47,7 +47,9 @@ class ShapleyResults:
 class InteractionResults:
     """What ``ls_spa_interactions`` returns.  ``interactions`` [p][p] is the Shapley interaction matrix in SHAP's
     convention: symmetric, half the pairwise interaction index off the diagonal, row i summing to ``attribution[i]``
-    and the whole matrix to ``r_squared``.  The other three fields are those of ``ls_spa(method='subsets')``."""
+    and the whole matrix to ``r_squared``.  The other three fields are those of ``ls_spa(method='subsets')``.  With
+    ``groups=`` the players are the g groups of columns: ``interactions`` is [g][g], ``attribution`` [g], the whole matrix
+    sums to ``r_squared`` minus the R^2 of the baseline columns alone, and ``theta`` keeps length p."""
     interactions: np.ndarray
     attribution: np.ndarray
     theta: np.ndarray
