@@ -224,6 +224,41 @@ int lsspa_lift_discard(lsspa_ctx* ctx, int32_t ticket);
 int lsspa_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g);
 int lsspa_debug_expand_groups(const int32_t* labels, int32_t p, int32_t g, const int32_t* group_perms, int32_t B,
                               int32_t antithetical, int32_t* out);
+/* Sampled pairwise Shapley interaction index, for any number of players d = p, or g under lsspa_set_players (the exact
+ * enumerations above stop at 32).  For a uniformly random ordering pi in which a and b sit at adjacent positions k, k + 1,
+ * S = {pi_0 .. pi_{k-1}} carries exactly the index's weight, so I_ab = E[v(S+a+b) - v(S+a) - v(S+b) + v(S) | a, b adjacent].
+ * One SAMPLE is three orderings through the ordinary kernels -- pi, pi with positions (0,1), (2,3), .. swapped, pi with
+ * positions (1,2), (3,4), .. swapped -- and yields that difference for all d - 1 adjacent pairs of pi: with b = pi_{k+1},
+ * Delta_k = lift_pi[b] - lift_pi'[b], pi' the row that swaps k and k + 1.  Every row is itself a uniformly random ordering.
+ *   lsspa_pairs_enable : on != 0 allocates and zeroes the pair state (the sample count, a sum of lift vectors [d] and
+ *                        three d x d tables: count as int64, mean, M2); 2 <= d <= LSSPA_PAIRS_MAX_D (three tables of
+ *                        134 MB there), else LSSPA_ERR_ARG.  on == 0 frees it.  A reduction, lsspa_set_reduced and
+ *                        setting or clearing a player map switch the state off (the dimension changed).
+ *   lsspa_pairs_batch  : perms [B][d], every row a permutation of 0 .. d-1 (else LSSPA_ERR_ARG).  Runs the 3 B rows as one
+ *                        unpaired batch (group expansion, fold and the LSSPA_INFO_SUM check included), then on the device
+ *                        folds every Delta into its pair's (count, mean, M2) -- Welford over the batch in sample order,
+ *                        one Chan merge into the table, no atomics: two runs agree bitwise -- and adds the 3 B lift
+ *                        vectors to the sum.  Takes and releases a lane itself; LSSPA_ERR_STATE while a launched batch is
+ *                        uncollected or the state is off.  Running statistics, pending buffer, history, estimator state
+ *                        and result slots are not touched.
+ *   lsspa_pairs_get    : n_samples; phi [d] = mean of all 3 n lift vectors (an unbiased attribution: every one of them
+ *                        sums to the full R^2); count, mean, m2 [d*d]: symmetric, zero diagonal; mean is the raw index
+ *                        estimate of the pair, m2 the sum of squared deviations of its count values.  Any pointer may be
+ *                        NULL.  Waits for work in flight.
+ *   lsspa_pairs_reset  : zero the state, keep it on.
+ *   lsspa_debug_expand_pairs : test hook, host only (no context) -- out [3 B][d], the rows a batch runs; a row of perms
+ *                        that is not a permutation, d < 1 or B < 1 is LSSPA_ERR_ARG
+ *   lsspa_debug_pairs_inject : test hook -- the pair kernels alone on given lifts [3 B][d] (host) and perms [B][d]; no
+ *                        ordering is factored (the counterpart of lsspa_debug_lift_inject) */
+#define LSSPA_PAIRS_MAX_D 4096
+int lsspa_pairs_enable(lsspa_ctx* ctx, int32_t on);
+int lsspa_pairs_batch(lsspa_ctx* ctx, const int32_t* perms /* [B][d] */, int32_t B);
+int lsspa_pairs_get(lsspa_ctx* ctx, int64_t* n_samples, double* phi /* [d] */, int64_t* count /* [d*d] */,
+                    double* mean /* [d*d] */, double* m2 /* [d*d] */);
+int lsspa_pairs_reset(lsspa_ctx* ctx);
+int lsspa_debug_expand_pairs(int32_t d, const int32_t* perms, int32_t B, int32_t* out /* [3B][d] */);
+int lsspa_debug_pairs_inject(lsspa_ctx* ctx, const double* lifts /* [3B][d] */, const int32_t* perms /* [B][d] */,
+                             int32_t B);
 /* 1 (default): every batch runs on the context's stream, one after the other.  2: successive batches alternate
  * between two workspaces on two streams, staggered by half a batch, so that the memory-bound stages (gather, lifts)
  * and the launch tails of one batch run beside the matrix-pipe-bound stages of the other; statistics, collectives
@@ -372,7 +407,8 @@ int lsspa_comm_allgather(lsspa_ctx* ctx, const double* send, int64_t count, doub
 #define LSSPA_K_ERROR 7
 #define LSSPA_K_COMM 8
 #define LSSPA_K_SMALL 9     /* fused small-p kernel: gather .. lifts of one ordering in one workgroup */
-#define LSSPA_K_COUNT 10
+#define LSSPA_K_PAIRS 10    /* pair kernels of lsspa_pairs_batch: Delta, per-pair statistics, lift sum */
+#define LSSPA_K_COUNT 11
 int lsspa_profile_enable(lsspa_ctx* ctx, int32_t on);
 int lsspa_profile_get(lsspa_ctx* ctx, int32_t kernel_class, double* total_ms, int64_t* launches);
 int lsspa_profile_reset(lsspa_ctx* ctx);

@@ -116,6 +116,27 @@ void expand_group_row(const PlayerMap& m, const int32_t* gperm, int reversed, in
   }
 }
 
+// ---- sampled pairwise interactions (lsspa_pairs_batch) --------------------------------------------------------------
+// A sample is an ordering and its two "neighbour-swapped" forms: between them every adjacent pair of the ordering
+// appears once in swapped order, which is what the fourth value of the pair's second difference needs (k_pairs.hip).
+void expand_pair_rows(const int32_t* perms, int B, int d, int32_t* out) {
+  for (int s = 0; s < B; ++s) {
+    const int32_t* pi = perms + (size_t)s * d;
+    int32_t* r0 = out + (size_t)3 * s * d;
+    int32_t* r1 = r0 + d;
+    int32_t* r2 = r1 + d;
+    for (int j = 0; j < d; ++j) r0[j] = r1[j] = r2[j] = pi[j];
+    for (int j = 0; j + 1 < d; j += 2) {
+      r1[j] = pi[j + 1];
+      r1[j + 1] = pi[j];
+    }
+    for (int j = 1; j + 1 < d; j += 2) {
+      r2[j] = pi[j + 1];
+      r2[j + 1] = pi[j];
+    }
+  }
+}
+
 }  // namespace lsspa
 
 

@@ -166,6 +166,15 @@ hipError_t launch_sum_check(const double* lifts, int n_samples, int p, double r2
 hipError_t launch_fold_players(const double* lifts, int p, int per, const int32_t* off, const int32_t* cols, int g,
                                int n_samples, double* out, hipStream_t st);
 
+// Sampled pairwise interaction index (lsspa_pairs_batch, k_pairs.hip).  lifts [3 n_samples][ld]: rows 3 s .. 3 s + 2 are
+// the lift vectors of sample s's three orderings (expand_pair_rows, players.h), perms [n_samples][d] its orderings pi_s.
+// Three launches: delta [n_samples][d] and pos [n_samples][d] (the inverse orderings) are written; every pair adjacent
+// in an ordering folds its Delta into the tables t_count / t_mean / t_m2 [d][d] (kept at [a][b], a < b: Welford over the
+// batch in sample order, one Chan merge into the table); phi [d] += the 3 n_samples rows, in order.
+constexpr int PAIRS_MAX_D = 4096;   // LSSPA_PAIRS_MAX_D: positions are 16-bit, three d x d tables
+hipError_t launch_pairs(const double* lifts, int ld, const int32_t* perms, int d, int n_samples, double* delta,
+                        int16_t* pos, int64_t* t_count, double* t_mean, double* t_m2, double* phi, hipStream_t st);
+
 // pending-batch moments about the current running mean: buf = [n_b, S (p), Q (p x p)]
 // parts: workspace of stats_batch_slices(n_samples, p) * (1 + p + p*p) doubles (or NULL: one slice)
 int stats_batch_slices(int n_samples, int p);

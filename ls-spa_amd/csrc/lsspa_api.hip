@@ -148,6 +148,20 @@ struct lsspa_ctx {
   PlayerMap players;
   int g_players = 0;
   DevBuf<int32_t> pl_off, pl_cols;   // the map's CSR on the device
+  // sampled pairwise interactions (lsspa_pairs_*): per-pair tables [d][d] kept at [a][b], a < b; the sum of all lift
+  // vectors; per-batch Delta / inverse orderings / orderings; injected lifts (test hook).  pairs_d = sd() when enabled.
+  bool pairs_on = false;
+  int pairs_d = 0;
+  int64_t pairs_n = 0;
+  DevBuf<int64_t> pr_count;
+  DevBuf<double> pr_mean, pr_m2, pr_phi, pr_delta, pr_lifts;
+  DevBuf<int16_t> pr_pos;
+  DevBuf<int32_t> pr_perms;
+  int32_t* pr_perms_h = nullptr;     // pinned staging of a batch's orderings, guarded by the event of its upload
+  size_t pr_perms_h_count = 0;
+  hipEvent_t pr_ev = nullptr;
+  bool pr_ev_busy = false;
+  std::vector<int32_t> pr_rows;      // the 3 B expanded rows of a batch
   // dimension of a SAMPLE -- lift vector handed to collect, running statistics, history, estimator, results.  The
   // factorisation side (orderings the kernels see, work matrices, the un-folded lift buffer) keeps p.
   int sd() const { return g_players ? g_players : p; }
@@ -366,6 +380,7 @@ int set_dims(lsspa_ctx* ctx, int p, int m, int tri) {
   ctx->min_rel_pivot = 1.0;
   ctx->src_f32_valid = false;
   ctx->g_players = 0;   // a player map belongs to the problem it was set on
+  ctx->pairs_on = false;   // ... and so does the pair state: its dimension is the sample's
   // a workspace sized for another shape is released now: kept, it would count as unavailable memory when the
   // new one is sized from hipMemGetInfo (and its layout depends on p_pad / m_pad / tri anyway)
   for (Lane& L : ctx->lanes) L.in_flight = false;   // a batch launched on the previous problem is void
@@ -1175,6 +1190,10 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->sub.release();
   ctx->grp.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
+  dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
+  dev_free(ctx->pr_delta); dev_free(ctx->pr_lifts); dev_free(ctx->pr_pos); dev_free(ctx->pr_perms);
+  if (ctx->pr_perms_h) (void)hipHostFree(ctx->pr_perms_h);
+  if (ctx->pr_ev) (void)hipEventDestroy(ctx->pr_ev);
   free_workspace(ctx);
   for (Lane& L : ctx->lanes) {
     if (L.copy_stream) {
@@ -1871,6 +1890,7 @@ int lsspa_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) try {
   } else {
     ctx->g_players = 0;
   }
+  ctx->pairs_on = false;   // the pair state has the dimension it was enabled at
   ctx->hist_cap = 0;
   ctx->hist_n = 0;
   ctx->run_on = false;
@@ -1900,6 +1920,204 @@ int lsspa_debug_expand_groups(const int32_t* labels, int32_t p, int32_t g, const
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sampled pairwise interaction index (include/lsspa.h, lsspa_pairs_*; csrc/k_pairs.hip)
+namespace {
+
+int pairs_zero(lsspa_ctx* ctx) {
+  const size_t d = (size_t)ctx->pairs_d;
+  HIPCHK(hipMemsetAsync(ctx->pr_count.ptr, 0, d * d * sizeof(int64_t), ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->pr_mean.ptr, 0, d * d * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->pr_m2.ptr, 0, d * d * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->pr_phi.ptr, 0, d * 8, ctx->stream));
+  ctx->pairs_n = 0;
+  return LSSPA_OK;
+}
+
+int pairs_usable(lsspa_ctx* ctx) {
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
+  if (!ctx->pairs_on || ctx->pairs_d != ctx->sd())
+    return ctx->fail(LSSPA_ERR_STATE, "the pair state is off: call lsspa_pairs_enable (a reduction, lsspa_set_reduced "
+                                      "and lsspa_set_players switch it off)");
+  return LSSPA_OK;
+}
+
+// the orderings of a batch on the device (pinned staging, no wait for the stream) and the per-batch buffers
+int pairs_stage(lsspa_ctx* ctx, const int32_t* perms, int B) {
+  const size_t d = (size_t)ctx->pairs_d, cnt = (size_t)B * d;
+  if (ctx->pr_delta.count < cnt || ctx->pr_pos.count < cnt || ctx->pr_perms.count < cnt)
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the previous batch's pair kernels still use the old buffers
+  TRY(dev_alloc(ctx, ctx->pr_delta, cnt));
+  TRY(dev_alloc(ctx, ctx->pr_pos, cnt));
+  TRY(dev_alloc(ctx, ctx->pr_perms, cnt));
+  if (!ctx->pr_ev) HIPCHK(hipEventCreateWithFlags(&ctx->pr_ev, hipEventDisableTiming));
+  if (ctx->pr_ev_busy) {
+    HIPCHK(hipEventSynchronize(ctx->pr_ev));
+    ctx->pr_ev_busy = false;
+  }
+  if (ctx->pr_perms_h_count < cnt) {
+    if (ctx->pr_perms_h) (void)hipHostFree(ctx->pr_perms_h);
+    ctx->pr_perms_h = nullptr;
+    ctx->pr_perms_h_count = 0;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ctx->pr_perms_h), cnt * sizeof(int32_t), 0);
+    if (e != hipSuccess) return ctx->fail(LSSPA_ERR_NOMEM, "hipHostMalloc", e);
+    ctx->pr_perms_h_count = cnt;
+  }
+  std::memcpy(ctx->pr_perms_h, perms, cnt * sizeof(int32_t));
+  // on the context's stream, behind the previous batch's pair kernels (which read pr_perms)
+  HIPCHK(hipMemcpyAsync(ctx->pr_perms.ptr, ctx->pr_perms_h, cnt * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->pr_ev, ctx->stream));
+  ctx->pr_ev_busy = true;
+  return LSSPA_OK;
+}
+
+int pairs_kernels(lsspa_ctx* ctx, const double* lifts, int B) {
+  ProfScope ps(ctx, LSSPA_K_PAIRS);
+  const int d = ctx->pairs_d;
+  HIPCHK(launch_pairs(lifts, d, ctx->pr_perms.ptr, d, B, ctx->pr_delta.ptr, ctx->pr_pos.ptr, ctx->pr_count.ptr,
+                      ctx->pr_mean.ptr, ctx->pr_m2.ptr, ctx->pr_phi.ptr, ctx->stream));
+  ctx->pairs_n += B;
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+int lsspa_pairs_enable(lsspa_ctx* ctx, int32_t on) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!on) {
+    TRY(sync_all(ctx));
+    ctx->pairs_on = false;
+    dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
+    dev_free(ctx->pr_delta); dev_free(ctx->pr_lifts); dev_free(ctx->pr_pos); dev_free(ctx->pr_perms);
+    return LSSPA_OK;
+  }
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_STATE, "no problem loaded");
+  const int d = ctx->sd();
+  if (d < 2 || d > LSSPA_PAIRS_MAX_D) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "sampled pairwise interactions take 2 <= d <= LSSPA_PAIRS_MAX_D = %d players (16-bit "
+             "positions, three d x d tables); this problem has d = %d", LSSPA_PAIRS_MAX_D, d);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  TRY(sync_all(ctx));
+  ctx->pairs_on = false;
+  const size_t dd = (size_t)d * d;
+  TRY(dev_alloc(ctx, ctx->pr_count, dd));
+  TRY(dev_alloc(ctx, ctx->pr_mean, dd));
+  TRY(dev_alloc(ctx, ctx->pr_m2, dd));
+  TRY(dev_alloc(ctx, ctx->pr_phi, (size_t)d));
+  ctx->pairs_d = d;
+  TRY(pairs_zero(ctx));
+  ctx->pairs_on = true;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_pairs_reset(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(pairs_usable(ctx));
+  HIPCHK(hipSetDevice(ctx->device));
+  return pairs_zero(ctx);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_pairs_batch(lsspa_ctx* ctx, const int32_t* perms, int32_t B) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(pairs_usable(ctx));
+  if (!perms || B < 1 || B > (1 << 20)) return ctx->fail(LSSPA_ERR_ARG, "perms / B");
+  for (const Lane& L : ctx->lanes)
+    if (L.in_flight) return ctx->fail(LSSPA_ERR_STATE, "a launched batch is still to be collected");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int d = ctx->pairs_d;
+  if (!all_permutations(perms, B, d, ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, ctx->g_players ? "perms: a row is not a permutation of the groups 0..g-1"
+                                                   : "perms: a row is not a permutation of 0..p-1");
+  ctx->pr_rows.resize((size_t)3 * B * d);
+  expand_pair_rows(perms, B, d, ctx->pr_rows.data());
+  TRY(pairs_stage(ctx, perms, B));
+  Lane* L = nullptr;
+  TRY(lift_launch(ctx, ctx->pr_rows.data(), 3 * B, 1, &L));   // unpaired: three rows a sample
+  // from here on the lane is this call's to give back, whatever happens
+  int rc = LSSPA_OK;
+  if (ctx->n_lanes == 2 && hipStreamWaitEvent(ctx->stream, L->ev_done, 0) != hipSuccess)
+    rc = ctx->fail(LSSPA_ERR_HIP, "hipStreamWaitEvent");
+  if (rc == LSSPA_OK) rc = pairs_kernels(ctx, lane_out(ctx, *L), B);
+  const int rc2 = lane_taken(ctx, *L, L->B);
+  L->in_flight = false;
+  return rc != LSSPA_OK ? rc : rc2;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_pairs_get(lsspa_ctx* ctx, int64_t* n_samples, double* phi, int64_t* count, double* mean, double* m2) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(pairs_usable(ctx));
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(sync_all(ctx));
+  const size_t d = (size_t)ctx->pairs_d, dd = d * d;
+  if (n_samples) *n_samples = ctx->pairs_n;
+  if (phi) {
+    HIPCHK(hipMemcpy(phi, ctx->pr_phi.ptr, d * 8, hipMemcpyDeviceToHost));
+    const double scale = ctx->pairs_n > 0 ? 1.0 / (3.0 * (double)ctx->pairs_n) : 0.0;
+    for (size_t j = 0; j < d; ++j) phi[j] *= scale;
+  }
+  // the device keeps a pair at [a][b], a < b (the rest of its tables stays zero): mirrored here
+  auto mirror = [d](auto* t) {
+    for (size_t a = 0; a < d; ++a) {
+      t[a * d + a] = 0;
+      for (size_t b = a + 1; b < d; ++b) t[b * d + a] = t[a * d + b];
+    }
+  };
+  if (count) {
+    HIPCHK(hipMemcpy(count, ctx->pr_count.ptr, dd * sizeof(int64_t), hipMemcpyDeviceToHost));
+    mirror(count);
+  }
+  if (mean) {
+    HIPCHK(hipMemcpy(mean, ctx->pr_mean.ptr, dd * 8, hipMemcpyDeviceToHost));
+    mirror(mean);
+  }
+  if (m2) {
+    HIPCHK(hipMemcpy(m2, ctx->pr_m2.ptr, dd * 8, hipMemcpyDeviceToHost));
+    mirror(m2);
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_expand_pairs(int32_t d, const int32_t* perms, int32_t B, int32_t* out) try {
+  if (!perms || !out || d < 1 || B < 1) return LSSPA_ERR_ARG;
+  std::vector<int32_t> mark;
+  if (!all_permutations(perms, B, d, mark)) return LSSPA_ERR_ARG;
+  expand_pair_rows(perms, B, d, out);
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(nullptr);
+}
+
+int lsspa_debug_pairs_inject(lsspa_ctx* ctx, const double* lifts, const int32_t* perms, int32_t B) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(pairs_usable(ctx));
+  if (!lifts || !perms || B < 1 || B > (1 << 20)) return ctx->fail(LSSPA_ERR_ARG, "lifts / perms / B");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int d = ctx->pairs_d;
+  if (!all_permutations(perms, B, d, ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, "perms: a row is not a permutation of 0..d-1");
+  const size_t cnt = (size_t)3 * B * d;
+  if (ctx->pr_lifts.count < cnt) HIPCHK(hipStreamSynchronize(ctx->stream));
+  TRY(dev_alloc(ctx, ctx->pr_lifts, cnt));
+  TRY(pairs_stage(ctx, perms, B));
+  HIPCHK(hipMemcpyAsync(ctx->pr_lifts.ptr, lifts, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // lifts is the caller's (pageable, possibly temporary) buffer
+  TRY(pairs_kernels(ctx, ctx->pr_lifts.ptr, B));
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
 }
 
 int lsspa_get_info(lsspa_ctx* ctx, int32_t* info) try {

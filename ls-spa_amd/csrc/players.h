@@ -19,4 +19,9 @@ struct PlayerMap {
 const char* player_map_build(const int32_t* labels, int p, int g, PlayerMap& m);
 void expand_group_row(const PlayerMap& m, const int32_t* gperm, int reversed, int32_t* out);
 
+// Sampled pairwise interactions (lsspa_pairs_batch): the three orderings of every sample.  perms [B][d] (validated by
+// the caller) -> out [3 B][d]: row 3 s is perms[s], row 3 s + 1 perms[s] with positions (0,1), (2,3), .. swapped, row
+// 3 s + 2 with positions (1,2), (3,4), .. swapped (a last position without a partner stays).
+void expand_pair_rows(const int32_t* perms, int B, int d, int32_t* out);
+
 }  // namespace lsspa

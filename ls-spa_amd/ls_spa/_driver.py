@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import InteractionResults, ShapleyResults, validate_data
+from ._results import InteractionResults, SampledInteractionResults, ShapleyResults, validate_data
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -1124,6 +1124,144 @@ def ls_spa_groups(X_train, X_test, y_train, y_test, groups, reg=0., max_samples=
                   return_attribution_history, method=method, num_batches=num_batches, return_history=return_history,
                   device=device, error_estimator=error_estimator, precision=precision, lookahead=lookahead, lanes=lanes,
                   _engine=_engine, _timings=_timings, _defer=_defer, _players=(labels, g))
+
+
+PAIRS_MAX_D = 4096     # include/lsspa.h, LSSPA_PAIRS_MAX_D
+
+
+def pair_standard_errors(counts, m2):
+    """Standard errors of the SHAP-convention interaction entries Phi_ab = I_ab / 2 from a pair's count n and sum of
+    squared deviations M2: sqrt(M2 / (n (n - 1))) / 2; ``inf`` where n < 2, 0 on the diagonal."""
+    counts = np.asarray(counts, dtype=np.float64)
+    err = np.full(counts.shape, np.inf)
+    seen = counts >= 2
+    err[seen] = 0.5 * np.sqrt(np.maximum(np.asarray(m2)[seen], 0.0) / (counts[seen] * (counts[seen] - 1.0)))
+    np.fill_diagonal(err, 0.0)
+    return err
+
+
+def ls_spa_interactions_sampled(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_size=2 ** 8,
+                                tolerance=None, seed=42, perms=None, *, groups=None, method="random", device=0,
+                                precision="float64", _engine=None):
+    """Sampled pairwise Shapley interaction values of the out-of-sample R^2, for any number of players: the p features,
+    or with ``groups=`` the g groups of columns (2 <= d <= 4096 players; ``ls_spa_interactions`` is exact and stops at 32).
+
+    For a uniformly random ordering of the d players in which a and b are neighbours, the players in front of them are
+    a set S drawn with exactly the weight of the interaction index, so I_ab = E[v(S+a+b) - v(S+a) - v(S+b) + v(S)] over
+    such orderings.  A sample is one ordering pi and its two neighbour-swapped forms -- three ordinary orderings through
+    the engine's kernels -- and gives that second difference for all d - 1 neighbouring pairs of pi at once
+    (include/lsspa.h, lsspa_pairs_batch); per pair the engine keeps count, mean and sum of squared deviations on the GPU,
+    in a fixed order (two runs agree bitwise).  A pair is hit by a fraction 2 / d of the samples.
+
+    Returns ``SampledInteractionResults``: ``interactions`` is d x d in SHAP's convention -- half the estimated index off
+    the diagonal, attribution[a] minus the rest of row a on it -- so row a sums to ``attribution[a]`` and the whole matrix
+    to ``r_squared`` (minus the R^2 of the baseline with one).  ``attribution`` is the mean of all 3 n lift vectors (each
+    of a sample's three orderings is itself uniformly random), ``theta`` and ``r_squared`` are those of the full fit.
+    ``interaction_errors`` holds the standard errors of the off-diagonal entries, sqrt(M2 / (n (n - 1))) / 2 with n the
+    pair's count; ``counts`` those counts; a pair no sample hit has interaction 0, error ``inf`` and count 0.  The
+    standard errors assume independent samples: they are only indicative for the QMC sources ('argsort',
+    'permutohedron'), whose orderings are not independent, and for a caller's ``perms``.
+
+    max_samples, batch_size:  samples are drawn in batches of ``batch_size`` until ``max_samples`` (every sample costs
+        three orderings).
+    tolerance:  None (default): run to ``max_samples``.  Otherwise sampling stops after the first batch at which every
+        pair has count >= 2 and the largest standard error is <= tolerance.
+    method:  'random' (default), 'argsort', 'permutohedron', or 'exact' (all d! orderings, d up to 8 or 9): the ordering
+        sources of ``ls_spa``, in dimension d.
+    perms:  an iterable of orderings of the d players instead (leave ``method`` at its default).
+    groups:  one integer label per column as for ``ls_spa_groups`` (-1: baseline, 0 .. g-1: group); the players are the
+        groups, ``theta`` keeps length p.
+    precision:  as in ``ls_spa`` ('float32': the per-ordering factorisation work in fp32).
+    d < 2 or d > 4096 raises ValueError before any GPU work.  Several ranks and resuming are not part of this function."""
+    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
+    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
+    validate_data(X_train, X_test, y_train, y_test)
+    if y_train.ndim != 1 or y_test.ndim != 1:
+        raise ValueError("y_train and y_test must be one-dimensional")
+    p = X_train.shape[1]
+    labels, d = (None, p) if groups is None else group_labels(groups, p, max_groups=None)
+    if d < 2 or d > PAIRS_MAX_D:
+        raise ValueError(f"sampled pairwise interactions take between 2 and {PAIRS_MAX_D} players (this problem has "
+                         f"{d} {'features' if groups is None else 'groups'})")
+    if perms is not None:
+        if method != "random":
+            raise ValueError("pass either perms= or method=, not both")
+        method = None
+    elif method not in S.METHODS:
+        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
+    if int(batch_size) < 1 or int(max_samples) < 1:
+        raise ValueError("batch_size and max_samples must be positive")
+    _, source, batch_size, _, max_samples, never_stop = prepare_sampling(
+        d, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms, antithetical=False,
+        method=method)
+    if never_stop:
+        tolerance = None
+    engine, owns, kept, ok = _engine, _engine is None, None, False
+    off = ~np.eye(d, dtype=bool)
+    try:
+        if owns:
+            engine, kept = _acquire_engine(device)
+        if precision != "float64" or getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision(precision)
+        if hasattr(engine, "set_lanes") and getattr(engine, "lanes", 1) != 1:
+            engine.set_lanes(1)
+        engine.load_data(X_train, X_test, y_train, y_test, reg)
+        theta, r_squared, info = engine.full_fit()
+        if labels is not None:
+            engine.set_players(labels)      # after the full fit: that one is about the columns
+        engine.pairs_enable(True)
+        n, state = 0, None
+        while n < max_samples:
+            rows = source.take(min(batch_size, max_samples - n))
+            if len(rows) == 0:
+                break
+            engine.pairs_batch(rows)
+            n += len(rows)
+            state = None
+            if tolerance is not None:
+                state = engine.pairs_get()      # the state is read once per batch
+                _, _, counts, _, m2 = state
+                if counts[off].min() >= 2 and pair_standard_errors(counts, m2).max() <= tolerance:
+                    break
+        if n == 0:
+            raise ValueError("no ordering to sample: perms is empty")
+        n, phi, counts, mean, m2 = state if state is not None else engine.pairs_get()
+        bits = info | (engine.info_collected() if hasattr(engine, "info_collected") else engine.info())
+        if bits & 12 and not bits & 1:
+            raise LSSPANativeError(
+                ("the fused lift scan gave up waiting for a row of its panel" if bits & 4 else
+                 "a sample's lifts did not sum to the R^2 of the full model")
+                + f" (info bits {bits}): the lift vectors of this run are not valid (engine fault)")
+        if bits & 1:
+            warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
+                          "of collinear features is not meaningful (the reference's is not either)",
+                          RuntimeWarning, stacklevel=2)
+        if info & 1:
+            theta, r_squared = _singular_fit(engine, X_test, y_test)
+        ok = True
+    finally:
+        if hasattr(source, "close"):
+            source.close()
+        if engine is not None and ok:
+            engine.pairs_enable(False)      # the tables go back (three of 134 MB at d = 4096) ...
+            if labels is not None:
+                engine.clear_players()      # ... and a player map never outlives the call that set it
+        if owns and engine is not None:
+            try:
+                if kept is None or not ok:
+                    engine.close()
+                else:
+                    engine.set_flags(0)
+                    engine.history_enable(0)
+            finally:
+                if kept is not None:
+                    kept.release()
+    Phi = 0.5 * np.asarray(mean, dtype=np.float64)
+    np.fill_diagonal(Phi, 0.0)
+    np.fill_diagonal(Phi, phi - Phi.sum(axis=1))
+    return SampledInteractionResults(interactions=Phi, attribution=phi, theta=theta, r_squared=r_squared,
+                                     interaction_errors=pair_standard_errors(counts, m2), counts=counts,
+                                     n_samples=int(n))
 
 
 # ------------------------------------------------------------------------------------------

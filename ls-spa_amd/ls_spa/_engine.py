@@ -52,6 +52,20 @@ def debug_expand_groups(labels, group_perms, antithetical: bool):
     return out
 
 
+def debug_expand_pairs(perms):
+    """Test hook, host only (no engine, no GPU): the (3 B, d) orderings a batch of sampled pairwise interactions runs for
+    the (B, d) orderings ``perms`` (include/lsspa.h, lsspa_debug_expand_pairs): row 3 s is perms[s], row 3 s + 1 has its
+    positions (0,1), (2,3), .. swapped, row 3 s + 2 its positions (1,2), (3,4), ..."""
+    perms = np.ascontiguousarray(perms, dtype=np.int32)
+    if perms.ndim != 2 or perms.shape[0] < 1 or perms.shape[1] < 1:
+        raise ValueError("perms must have shape (B, d)")
+    out = np.empty((3 * perms.shape[0], perms.shape[1]), dtype=np.int32)
+    rc = N.load().lsspa_debug_expand_pairs(perms.shape[1], N.iptr(perms), perms.shape[0], N.iptr(out))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_expand_pairs: status {rc} (a row of perms is not a permutation)")
+    return out
+
+
 def debug_stats_slices(n_samples: int, p: int):
     """Test hook, host only: (samples given to every slice of a chunk's moments, small) as the library cuts a chunk of
     n_samples at dimension p (include/lsspa.h, lsspa_debug_stats_slices)."""
@@ -361,6 +375,46 @@ class HipEngine:
         if isinstance(accumulate, (bool, np.bool_)):
             return int(accumulate)
         return int(accumulate)      # integers go through as they are: the library refuses anything but 0, 1, 2
+
+    # ---- sampled pairwise interactions (any number of players) -----------------------------
+    PAIRS_MAX_D = 4096     # include/lsspa.h, LSSPA_PAIRS_MAX_D
+
+    def pairs_enable(self, on: bool = True):
+        """Allocate and zero (or free) the state of the sampled pairwise interaction index in the sample dimension
+        (include/lsspa.h, lsspa_pairs_enable); a reduction and set_players / clear_players switch it off."""
+        self._check(self._lib.lsspa_pairs_enable(self._h, int(bool(on))))
+
+    def pairs_reset(self):
+        self._check(self._lib.lsspa_pairs_reset(self._h))
+
+    def pairs_batch(self, perms):
+        """One batch of (B, dim) orderings: three orderings a sample through the kernels, every adjacent pair's second
+        difference folded into its (count, mean, M2) on the device (include/lsspa.h, lsspa_pairs_batch)."""
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        if perms.ndim != 2 or perms.shape[1] != self.dim:
+            raise ValueError(f"perms must have shape (B, {self.dim})")
+        self._check(self._lib.lsspa_pairs_batch(self._h, N.iptr(perms), perms.shape[0]))
+
+    def pairs_get(self, tables: bool = True):
+        """(n_samples, phi, count, mean, M2): phi the mean of all 3 n lift vectors; the three (dim, dim) tables symmetric
+        with a zero diagonal, mean the raw index estimate of a pair (None, None, None with tables=False)."""
+        d = self.dim
+        n = C.c_int64()
+        phi = np.empty(d)
+        count = np.empty((d, d), dtype=np.int64) if tables else None
+        mean, m2 = (np.empty((d, d)), np.empty((d, d))) if tables else (None, None)
+        self._check(self._lib.lsspa_pairs_get(self._h, C.byref(n), N.dptr(phi),
+                                              count.ctypes.data_as(N._pi64) if tables else None, N.dptr(mean), N.dptr(m2)))
+        return n.value, phi, count, mean, m2
+
+    def debug_pairs_inject(self, lifts, perms):
+        """Test hook: the pair kernels alone on chosen lift vectors (3 B, dim) and orderings (B, dim) (include/lsspa.h,
+        lsspa_debug_pairs_inject); no ordering is factored."""
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        lifts = np.ascontiguousarray(lifts, dtype=np.float64)
+        if perms.ndim != 2 or perms.shape[1] != self.dim or lifts.shape != (3 * perms.shape[0], self.dim):
+            raise ValueError(f"perms must have shape (B, {self.dim}) and lifts (3 B, {self.dim})")
+        self._check(self._lib.lsspa_debug_pairs_inject(self._h, N.dptr(lifts), N.iptr(perms), perms.shape[0]))
 
     def set_lanes(self, n: int):
         """1: batches run one after the other (default).  2: successive batches alternate between two workspaces on

@@ -14,7 +14,8 @@ OK = 0
 F64, F32 = 0, 1
 HOST, DEVICE = 0, 1
 INFO_NOT_PD = 1
-KERNEL_CLASSES = ("gather", "chol_diag", "chol_panel", "strip", "lift", "stats", "gram", "error", "comm", "small_p")
+KERNEL_CLASSES = ("gather", "chol_diag", "chol_panel", "strip", "lift", "stats", "gram", "error", "comm", "small_p",
+                  "pairs")
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", "liblsspa_hip.so"))
@@ -118,6 +119,12 @@ SIGNATURES = {
     "lsspa_debug_group_values": (C.c_int, [_vp, _pi32, _i32, C.POINTER(C.c_uint64), _i64, _pd]),
     "lsspa_set_players": (C.c_int, [_vp, _pi32, _i32]),
     "lsspa_debug_expand_groups": (C.c_int, [_pi32, _i32, _i32, _pi32, _i32, _i32, _pi32]),
+    "lsspa_pairs_enable": (C.c_int, [_vp, _i32]),
+    "lsspa_pairs_batch": (C.c_int, [_vp, _pi32, _i32]),
+    "lsspa_pairs_get": (C.c_int, [_vp, _pi64, _pd, _pi64, _pd, _pd]),
+    "lsspa_pairs_reset": (C.c_int, [_vp]),
+    "lsspa_debug_expand_pairs": (C.c_int, [_i32, _pi32, _i32, _pi32]),
+    "lsspa_debug_pairs_inject": (C.c_int, [_vp, _pd, _pi32, _i32]),
 }
 
 

@@ -72,6 +72,42 @@ class InteractionResults:
         return "\n".join(lines)
 
 
+@dataclass
+class SampledInteractionResults:
+    """What ``ls_spa_interactions_sampled`` returns.  ``interactions`` [d][d] is the estimated Shapley interaction matrix
+    in SHAP's convention (half the estimated pairwise index off the diagonal, row a summing to ``attribution[a]``, the
+    whole matrix to ``r_squared`` -- minus the R^2 of the baseline with ``groups=``); ``interaction_errors`` [d][d] the
+    standard errors of its off-diagonal entries (0 on the diagonal, ``inf`` for a pair no sample hit) and ``counts``
+    [d][d] the number of samples in which the pair was adjacent; ``n_samples`` the samples drawn (three orderings each).
+    ``attribution`` is the mean of all 3 n lift vectors; ``theta`` and ``r_squared`` are those of the full fit."""
+    interactions: np.ndarray
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+    interaction_errors: np.ndarray
+    counts: np.ndarray
+    n_samples: int
+
+    def __repr__(self):
+        pad = " " * 8
+        inter = np.asarray(self.interactions)
+        off = inter - np.diag(np.diag(inter))
+        err = np.asarray(self.interaction_errors)
+        finite = err[np.isfinite(err)]
+        lines = [
+            "",
+            f"{pad}d = {np.asarray(self.attribution).size}, {self.n_samples} samples",
+            f"{pad}Out-of-sample R^2 with all features: {self.r_squared:.2f}",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}Largest pairwise interaction: {float(np.abs(off).max()) if off.size else 0.0:.2E}",
+            f"{pad}Largest standard error: {float(finite.max()) if finite.size else float('nan'):.2E}"
+            f" ({int((np.asarray(self.counts) == 0).sum() - len(inter)) // 2} pairs never hit)",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
 class SizeIncompatible(Exception):
     """Raised when the shapes of the four data arrays do not fit together."""
 
