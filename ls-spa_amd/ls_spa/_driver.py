@@ -21,6 +21,7 @@ README-dialect keywords (README.md:96-106) are accepted on top: ``method``,
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import warnings
@@ -688,6 +689,141 @@ def _run_estimator(engine, p, comm, rng, source, batch_size, antithetical, max_s
     return mean, feat_err, total_err, np.array(err_hist), history, n
 
 
+# ---- what every entry point does round its GPU work ------------------------------------------------------------------
+def _coerce_data(X_train, X_test, y_train, y_test):
+    """The four arrays as ndarrays, their shapes checked.  The reference coerces with np.array (a copy,
+    ls_spa/ls_spa.py:158-161); the inputs are never written here, so asarray gives the same result without copying
+    1.6 GB at the C3 shape."""
+    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
+    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
+    validate_data(X_train, X_test, y_train, y_test)
+    if y_train.ndim != 1 or y_test.ndim != 1:
+        raise ValueError("y_train and y_test must be one-dimensional")  # reference: concatenate error, :312
+    return X_train, X_test, y_train, y_test
+
+
+def _sampling_options(method, perms, p, error_estimator=None, lookahead=None, lanes="auto"):
+    """(error_estimator, lookahead, lanes) of a sampling call of ls_spa with what the caller left open filled in: the
+    defaults ls_spa's docstring gives, keyed on whether the orderings come from a QMC method; p is the number of
+    columns.  ValueError for a value that is none of the documented ones."""
+    qmc = perms is None and method in ("argsort", "permutohedron")
+    if error_estimator is None:
+        error_estimator = "device" if qmc else "reference"
+    if error_estimator not in ("reference", "lowrank", "device"):
+        raise ValueError("error_estimator must be None, 'reference', 'lowrank' or 'device'")
+    if lookahead is None:
+        # the device estimator's checks never make the loop wait: launching the chunks of a thin batch together costs
+        # nothing but the samples already in flight at a stop
+        lookahead = "auto" if (error_estimator == "device" and qmc) else 1
+    if lookahead != "auto" and int(lookahead) < 1:
+        raise ValueError("lookahead must be >= 1 or 'auto'")
+    if lanes == "auto":
+        lanes = 2 if (qmc and p > SMALL_P_MAX) else 1
+    if int(lanes) not in (1, 2):
+        raise ValueError("lanes must be 1, 2 or 'auto'")
+    return error_estimator, lookahead, int(lanes)
+
+
+def _stopwatch(tm):
+    """lap(key): the host seconds since the last lap are added to tm[key]; lap() only starts the next one."""
+    from time import perf_counter
+    mark = [perf_counter()]
+
+    def lap(key=None):
+        if key is not None:
+            tm[key] = tm.get(key, 0.0) + (perf_counter() - mark[0])
+        mark[0] = perf_counter()
+    return lap
+
+
+def _close_source(source):
+    if hasattr(source, "close"):
+        source.close()
+
+
+@contextlib.contextmanager
+def _engine_call(engine, device, comm=None, undo=(), lap=lambda key=None: None):
+    """The engine of one call of an entry point: the caller's (`engine`), else the device's kept engine or one made for
+    the call (_acquire_engine), with `comm` bound to it.  undo: (function, always) pairs, a list the body may extend,
+    called in order on the way out: all of them after success, after an exception those marked `always`.  An engine that
+    is not the caller's then loses its communicator and is reset for the next call -- a kept one, if neither the body nor
+    an undo step raised -- or closed; its lock is released whatever the teardown does.  lap: ls_spa's stopwatch."""
+    owns, lock, ok = engine is None, None, False
+    try:
+        if owns:
+            engine, lock = _acquire_engine(device)
+        lap("engine_create")
+        if comm is not None and hasattr(comm, "bind"):
+            comm.bind(engine)      # RCCL communicator on this engine's GPU and stream (collective)
+        yield engine
+        ok = True
+    finally:
+        lap()
+        try:
+            try:
+                for step, always in undo:
+                    if ok or always:
+                        step()
+            except BaseException:
+                ok = False      # what may still carry a player map or pair tables is not handed to the next call
+                raise
+            finally:
+                if owns and engine is not None:
+                    if comm is not None and hasattr(comm, "close"):
+                        comm.close()       # the communicator lives on the engine's context
+                    if lock is None or not ok:
+                        engine.close()     # a kept engine an exception went through is not trusted with another call
+                    else:
+                        engine.set_flags(0)
+                        engine.history_enable(0)      # (the lanes stay as they are: the next call sets what it needs)
+        finally:
+            if lock is not None:
+                lock.release()
+        lap("teardown")
+
+
+def _load_and_fit(engine, data, reg, row_sharded, comm, lap=lambda key=None: None):
+    """The data reduction (of this rank's rows, with row_sharded), then the full fit: (theta, r_squared, info)."""
+    if row_sharded:
+        engine.load_data_sharded(*data, reg, comm or _Comm(), shard_test=row_sharded != "train")
+    else:
+        engine.load_data(*data, reg)
+    lap("reduction_h2d_gram")
+    fit = engine.full_fit()
+    lap("final_fit")
+    return fit
+
+
+def _engine_fault(bits):
+    """LSSPA_INFO_SCAN_WAIT (4): a hand-over inside a panel launch timed out; LSSPA_INFO_SUM (8): a sample's lifts did
+    not sum to the R^2 of the full model (every ordering's must, ls_spa/ls_spa.py:284-285).  Either way the lift vectors
+    of the run are not valid (with a pivot that broke down, bit 1, they are meaningless anyway)."""
+    return bool(bits & 12) and not bits & 1
+
+
+def _info_verdict(bits, stacklevel):
+    """What the info bits of a finished run mean to the caller: LSSPANativeError for an engine fault, a RuntimeWarning
+    (attributed `stacklevel` frames above the function that asks) for a Gram matrix that was not positive definite."""
+    if _engine_fault(bits):
+        raise LSSPANativeError(
+            ("the fused lift scan gave up waiting for a row of its panel" if bits & 4 else
+             "a sample's lifts did not sum to the R^2 of the full model")
+            + f" (info bits {bits}): the lift vectors of this run are not valid (engine fault)")
+    if bits & 1:
+        warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
+                      "of collinear features is not meaningful (the reference's is not either)",
+                      RuntimeWarning, stacklevel=stacklevel + 1)
+
+
+def _shap_matrix(phi, index):
+    """SHAP's matrix of an interaction index: half the index off the diagonal, the main effect
+    phi_i - sum_{j != i} Phi_ij on it, so that row i sums to phi_i."""
+    Phi = 0.5 * np.asarray(index, dtype=np.float64)
+    np.fill_diagonal(Phi, 0.0)
+    np.fill_diagonal(Phi, phi - Phi.sum(axis=1))
+    return Phi
+
+
 def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_size=2 ** 8,
            tolerance=1e-2, seed=42, perms=None, antithetical=True, return_attribution_history=False, *,
            method=None, num_batches=None, return_history=None, device=0, error_estimator=None,
@@ -764,14 +900,8 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
         their rows and sum the Gram matrices with one all-reduce.  'train': only the training rows are
         sharded, every rank passes all test rows (needed when there are fewer than p test rows).
     """
-    # the reference coerces with np.array (a copy, ls_spa/ls_spa.py:158-161); the inputs are never written here, so
-    # asarray gives the same result without copying 1.6 GB at the C3 shape
-    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
-    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
-    validate_data(X_train, X_test, y_train, y_test)
-    if y_train.ndim != 1 or y_test.ndim != 1:
-        raise ValueError("y_train and y_test must be one-dimensional")  # reference: concatenate error, :312
-    p = X_train.shape[1]
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    p = data[0].shape[1]
     # _players = (labels, g), ls_spa_groups only: the players of the game are g groups of columns.  Orderings, statistics,
     # estimator and results then have dimension g (`dim`); what follows the cost of an ordering keeps p.
     dim = p if _players is None else int(_players[1])
@@ -782,79 +912,49 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
     if groups is not None and (method != "subsets" or perms is not None):
         raise ValueError("groups= is grouped attribution, which exists for the exact path only: pass method='subsets' "
                          "(no sampling method and no perms=)")
-    if method == "subsets":
-        return _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, perms=perms, groups=groups,
-                               return_attribution_history=return_attribution_history, device=device,
-                               row_sharded=row_sharded, checkpoint=checkpoint, comm=comm if comm is not None else _comm,
-                               engine=_engine)
-    if error_estimator is None:
-        error_estimator = "device" if (perms is None and method in ("argsort", "permutohedron")) else "reference"
-    if error_estimator not in ("reference", "lowrank", "device"):
-        raise ValueError("error_estimator must be None, 'reference', 'lowrank' or 'device'")
-
-    import time as _time
-    tm = _timings if _timings is not None else {}   # bench.py's e2e_breakdown: host seconds per phase of this call
-
-    def lap(key, t0):
-        tm[key] = tm.get(key, 0.0) + (_time.perf_counter() - t0)
-        return _time.perf_counter()
-
     comm = comm if comm is not None else _comm
-    engine = _engine
-    owns = engine is None          # this call made (or borrowed) the engine: it also ends the communicator bound to it
-    kept = None                    # the lock of a borrowed, kept engine
+    if method == "subsets":
+        return _ls_spa_subsets(*data, reg, perms=perms, groups=groups,
+                               return_attribution_history=return_attribution_history, device=device,
+                               row_sharded=row_sharded, checkpoint=checkpoint, comm=comm, engine=_engine)
+    error_estimator, lookahead, lanes = _sampling_options(method, perms, p, error_estimator, lookahead, lanes)
+    tm = _timings if _timings is not None else {}   # bench.py's e2e_breakdown: host seconds per phase of this call
+    lap = _stopwatch(tm)
+
+    def prepare():
+        share = dict(rank=comm.rank, world=comm.world) if comm is not None else {}
+        return prepare_sampling(dim, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
+                                antithetical=antithetical, method=method, **share)
+
     # The ordering source first: a QMC source starts its helper thread here -- the first `import scipy.stats` of a process
     # (0.26 s; 1.3 s on a cold box), the Sobol' constructor (18 ms at p = 1000) and the first block of orderings then run
     # under the engine's creation and the data reduction instead of in front of the sampling loop.
-    t0 = _time.perf_counter()
-    share = dict(rank=comm.rank, world=comm.world) if comm is not None else {}
-    prepared = prepare_sampling(dim, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
-                                antithetical=antithetical, method=method, **share)
-    t0 = lap("sampler_start", t0)
-    ok = False
-    try:
-        if owns:
-            engine, kept = _acquire_engine(device)
-        t0 = lap("engine_create", t0)
-        if comm is not None and hasattr(comm, "bind"):
-            comm.bind(engine)      # RCCL communicator on this engine's GPU and stream (collective)
+    prepared = prepare()
+    lap("sampler_start")
+    # on the way out: the sampler's helper thread (already ended by a run that got as far as its loop)
+    undo = [(lambda: _close_source(prepared[1]), True)]
+    with _engine_call(_engine, device, comm, undo, lap) as engine:
         if precision != "float64" or getattr(engine, "precision", "float64") != "float64":
             engine.set_precision(precision)
-        if lookahead is None:
-            # the device estimator's checks never make the loop wait: launching the chunks of a thin batch together costs
-            # nothing but the samples already in flight at a stop
-            lookahead = "auto" if (error_estimator == "device" and perms is None
-                                   and method in ("argsort", "permutohedron")) else 1
-        if lookahead != "auto" and int(lookahead) < 1:
-            raise ValueError("lookahead must be >= 1 or 'auto'")
-        if lanes == "auto":
-            lanes = 2 if (perms is None and method in ("argsort", "permutohedron") and p > SMALL_P_MAX) else 1
-        if int(lanes) not in (1, 2):
-            raise ValueError("lanes must be 1, 2 or 'auto'")
-        if hasattr(engine, "set_lanes") and getattr(engine, "lanes", 1) != int(lanes):
-            engine.set_lanes(int(lanes))
-        t0 = lap("setup", t0)
-        if row_sharded:
-            engine.load_data_sharded(X_train, X_test, y_train, y_test, reg, comm or _Comm(),
-                                     shard_test=row_sharded != "train")
-        else:
-            engine.load_data(X_train, X_test, y_train, y_test, reg)
-        t0 = lap("reduction_h2d_gram", t0)
+        if hasattr(engine, "set_lanes") and getattr(engine, "lanes", 1) != lanes:
+            engine.set_lanes(lanes)
+        lap("setup")
+        # theta and r^2 (ls_spa/ls_spa.py:240-243) depend on the reduced problem only: computed BEFORE the sampling loop,
+        # so that the call does not end behind whatever the loop launched ahead of a stop and never collected
+        theta, r_squared, info = _load_and_fit(engine, data, reg, row_sharded, comm, lap)
         if _timings is not None and hasattr(engine, "reduce_timing"):
-            # the library's own split of that phase: chunked copies + Gram kernels, finalize (the page-locking parts
+            # the library's own split of the reduction: chunked copies + Gram kernels, finalize (the page-locking parts
             # are zero since round 4); what is left of the phase is host-side coercion and the call itself
             parts = engine.reduce_timing()
             whole = tm.pop("reduction_h2d_gram")
             tm["reduction_pin"], tm["reduction_copy_gram"] = parts["pin"], parts["h2d_gram"]
             tm["reduction_unpin"], tm["reduction_finalize"] = parts["unpin"], parts["finalize"]
             tm["reduction_host"] = whole - sum(parts.values())
-        # theta and r^2 (ls_spa/ls_spa.py:240-243) depend on the reduced problem only: computed BEFORE the sampling loop,
-        # so that the call does not end behind whatever the loop launched ahead of a stop and never collected
-        t0 = _time.perf_counter()
-        theta, r_squared, info = engine.full_fit()
-        t0 = lap("final_fit", t0)
         if _players is not None:
             engine.set_players(_players[0])      # after the full fit: that one is about the columns
+            if hasattr(engine, "clear_players"):      # the caller's engine too: the map never outlives this call
+                undo.append((engine.clear_players, False))
+
         def sampling_run(prep):
             out = run_estimator(
                 engine, dim, cost_p=p, max_samples=max_samples, batch_size=batch_size, tolerance=tolerance, seed=seed,
@@ -864,55 +964,21 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
             return out, info | (engine.info_collected() if hasattr(engine, "info_collected") else engine.info())
 
         (attribution, feat_err, total_err, err_hist, history, _), bits = sampling_run(prepared)
-        t0 = _time.perf_counter()
-        # LSSPA_INFO_SCAN_WAIT (4): a hand-over inside a panel launch timed out; LSSPA_INFO_SUM (8): a sample's lifts did
-        # not sum to the R^2 of the full model (every ordering's must, ls_spa/ls_spa.py:284-285).  Either way the lift
-        # vectors of the run are not valid (with a pivot that broke down, bit 1, they are meaningless anyway).
-        fault = bool(bits & 12) and not bits & 1
-        if fault and perms is None and checkpoint is None and hasattr(engine, "set_flags"):
+        lap()
+        if _engine_fault(bits) and perms is None and checkpoint is None and hasattr(engine, "set_flags"):
             # An ordering source that can be drawn again (seed or QMC method; not the caller's iterable): the run is
             # repeated ONCE on the conservative path -- the lift kernel of its own reads V^T back, nothing is handed over
             # inside a launch (developer flag 512) -- instead of being lost.
             warnings.warn(f"engine fault in the fused lift scan (info bits {bits}): the run is repeated with the lift "
                           "kernel of its own", RuntimeWarning, stacklevel=2)
             engine.set_flags(512)
-            prepared[1].close() if hasattr(prepared[1], "close") else None
-            prepared = prepare_sampling(dim, max_samples=max_samples, batch_size=batch_size, seed=seed, perms=perms,
-                                        antithetical=antithetical, method=method, **share)
+            _close_source(prepared[1])
+            prepared = prepare()
             (attribution, feat_err, total_err, err_hist, history, _), bits = sampling_run(prepared)
-            fault = bool(bits & 12) and not bits & 1
-        if fault:
-            raise LSSPANativeError(
-                ("the fused lift scan gave up waiting for a row of its panel" if bits & 4 else
-                 "a sample's lifts did not sum to the R^2 of the full model")
-                + f" (info bits {bits}): the lift vectors of this run are not valid (engine fault)")
-        if bits & 1:
-            warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
-                          "of collinear features is not meaningful (the reference's is not either)",
-                          RuntimeWarning, stacklevel=2)
+        _info_verdict(bits, stacklevel=2)
         if info & 1:
-            theta, r_squared = _singular_fit(engine, X_test, y_test)
-        t0 = lap("final_fit", t0)
-        ok = True
-    finally:
-        t0 = _time.perf_counter()
-        if prepared is not None and hasattr(prepared[1], "close"):
-            prepared[1].close()      # the sampler's helper thread (already ended by a run that got as far as its loop)
-        if _players is not None and ok and engine is not None and hasattr(engine, "clear_players"):
-            engine.clear_players()     # the caller's engine too: a player map never outlives the call that set it
-        if owns and engine is not None:
-            try:
-                if comm is not None and hasattr(comm, "close"):
-                    comm.close()       # the communicator lives on the engine's context
-                if kept is None or not ok:
-                    engine.close()     # a kept engine an exception went through is not trusted with another call
-                else:
-                    engine.set_flags(0)
-                    engine.history_enable(0)      # (the lanes stay as they are: the next call sets what it needs)
-            finally:
-                if kept is not None:
-                    kept.release()
-        lap("teardown", t0)
+            theta, r_squared = _singular_fit(engine, data[1], data[3])
+        lap("final_fit")
     return ShapleyResults(attribution=attribution, theta=theta, overall_error=total_err,
                           attribution_errors=feat_err, r_squared=r_squared, error_history=err_hist,
                           attribution_history=history)
@@ -971,53 +1037,21 @@ def _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, *, perms, return_attr
         raise ValueError("method='subsets' computes no attribution history (there are no samples)")
     if checkpoint is not None:
         raise ValueError("method='subsets' has no state to checkpoint or resume")
-    owns = engine is None
-    kept = None
-    ok = False
-    try:
-        if owns:
-            engine, kept = _acquire_engine(device)
-        if comm is not None and hasattr(comm, "bind"):
-            comm.bind(engine)
+    with _engine_call(engine, device, comm) as engine:
         # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like phi
         if getattr(engine, "precision", "float64") != "float64":
             engine.set_precision("float64")
-        if row_sharded:
-            engine.load_data_sharded(X_train, X_test, y_train, y_test, reg, comm or _Comm(),
-                                     shard_test=row_sharded != "train")
-        else:
-            engine.load_data(X_train, X_test, y_train, y_test, reg)
-        theta, r_squared, info = engine.full_fit()
+        theta, r_squared, info = _load_and_fit(engine, (X_train, X_test, y_train, y_test), reg, row_sharded, comm)
         if interactions:
             phi, raw, bits = engine.subsets_interactions() if labels is None else engine.groups_interactions(labels)
         else:
             phi, bits = engine.subsets_shapley() if labels is None else engine.groups_shapley(labels)
-        if (bits | info) & 1:
-            warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
-                          "of collinear features is not meaningful (the reference's is not either)",
-                          RuntimeWarning, stacklevel=3)
+        _info_verdict((bits | info) & 1, stacklevel=3)      # (an enumeration reports a broken pivot, nothing else)
         if info & 1:
             theta, r_squared = _singular_fit(engine, X_test, y_test)
-        ok = True
-    finally:
-        if owns and engine is not None:
-            try:
-                if comm is not None and hasattr(comm, "close"):
-                    comm.close()
-                if kept is None or not ok:
-                    engine.close()
-                else:
-                    engine.set_flags(0)
-                    engine.history_enable(0)
-            finally:
-                if kept is not None:
-                    kept.release()
     if interactions:
-        # SHAP's matrix: half the index off the diagonal, the main effect phi_i - sum_{j != i} Phi_ij on it
-        Phi = 0.5 * np.asarray(raw, dtype=np.float64)
-        np.fill_diagonal(Phi, 0.0)
-        np.fill_diagonal(Phi, phi - Phi.sum(axis=1))
-        return InteractionResults(interactions=Phi, attribution=phi, theta=theta, r_squared=r_squared)
+        return InteractionResults(interactions=_shap_matrix(phi, raw), attribution=phi, theta=theta,
+                                  r_squared=r_squared)
     return ShapleyResults(attribution=phi, theta=theta, overall_error=0.0,
                           attribution_errors=np.zeros(p if labels is None else n_players),
                           r_squared=r_squared, error_history=np.zeros(0), attribution_history=None)
@@ -1050,12 +1084,8 @@ def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, groups=None
         ``ls_spa(method='subsets', groups=)`` returns it, and the whole matrix to ``r_squared`` minus the R^2 of the
         baseline alone.  ``theta`` keeps length p.  The limits and errors are that call's: g <= 32, p <= 64 (the
         p <= 32 limit does not apply), labels refused with ValueError before any GPU work."""
-    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
-    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
-    validate_data(X_train, X_test, y_train, y_test)
-    if y_train.ndim != 1 or y_test.ndim != 1:
-        raise ValueError("y_train and y_test must be one-dimensional")
-    return _ls_spa_subsets(X_train, X_test, y_train, y_test, reg, perms=None, return_attribution_history=False,
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    return _ls_spa_subsets(*data, reg, perms=None, return_attribution_history=False,
                            device=device, row_sharded=row_sharded, checkpoint=None, comm=comm, engine=_engine,
                            groups=groups, interactions=True)
 
@@ -1097,16 +1127,14 @@ def ls_spa_groups(X_train, X_test, y_train, y_test, groups, reg=0., max_samples=
     error_estimator, precision, lookahead, lanes:  as in ``ls_spa``, same defaults per method.
     comm, checkpoint, row_sharded:  not supported here (several ranks and resuming are out of this function's scope):
         anything but None / False raises a ValueError that names the option."""
-    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
-    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
-    validate_data(X_train, X_test, y_train, y_test)
-    p = X_train.shape[1]
     if comm is not None:
         raise ValueError("ls_spa_groups does not take comm= (several ranks): grouped sampling runs on one GPU")
     if checkpoint is not None:
         raise ValueError("ls_spa_groups does not take checkpoint=: grouped sampling cannot be resumed")
     if row_sharded:
         raise ValueError("ls_spa_groups does not take row_sharded=: it needs comm=, which is not supported here")
+    X_train, X_test, y_train, y_test = _coerce_data(X_train, X_test, y_train, y_test)
+    p = X_train.shape[1]
     if method == "auto":
         if perms is not None:
             method = None
@@ -1173,12 +1201,8 @@ def ls_spa_interactions_sampled(X_train, X_test, y_train, y_test, reg=0., max_sa
         groups, ``theta`` keeps length p.
     precision:  as in ``ls_spa`` ('float32': the per-ordering factorisation work in fp32).
     d < 2 or d > 4096 raises ValueError before any GPU work.  Several ranks and resuming are not part of this function."""
-    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
-    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
-    validate_data(X_train, X_test, y_train, y_test)
-    if y_train.ndim != 1 or y_test.ndim != 1:
-        raise ValueError("y_train and y_test must be one-dimensional")
-    p = X_train.shape[1]
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    p = data[0].shape[1]
     labels, d = (None, p) if groups is None else group_labels(groups, p, max_groups=None)
     if d < 2 or d > PAIRS_MAX_D:
         raise ValueError(f"sampled pairwise interactions take between 2 and {PAIRS_MAX_D} players (this problem has "
@@ -1196,20 +1220,20 @@ def ls_spa_interactions_sampled(X_train, X_test, y_train, y_test, reg=0., max_sa
         method=method)
     if never_stop:
         tolerance = None
-    engine, owns, kept, ok = _engine, _engine is None, None, False
+    undo = [(lambda: _close_source(source), True)]
     off = ~np.eye(d, dtype=bool)
-    try:
-        if owns:
-            engine, kept = _acquire_engine(device)
+    with _engine_call(_engine, device, undo=undo) as engine:
         if precision != "float64" or getattr(engine, "precision", "float64") != "float64":
             engine.set_precision(precision)
         if hasattr(engine, "set_lanes") and getattr(engine, "lanes", 1) != 1:
             engine.set_lanes(1)
-        engine.load_data(X_train, X_test, y_train, y_test, reg)
-        theta, r_squared, info = engine.full_fit()
+        theta, r_squared, info = _load_and_fit(engine, data, reg, False, None)
         if labels is not None:
             engine.set_players(labels)      # after the full fit: that one is about the columns
         engine.pairs_enable(True)
+        undo.append((lambda: engine.pairs_enable(False), False))      # the tables go back (134 MB each at d = 4096) ...
+        if labels is not None:
+            undo.append((engine.clear_players, False))      # ... and a player map never outlives the call that set it
         n, state = 0, None
         while n < max_samples:
             rows = source.take(min(batch_size, max_samples - n))
@@ -1226,42 +1250,13 @@ def ls_spa_interactions_sampled(X_train, X_test, y_train, y_test, reg=0., max_sa
         if n == 0:
             raise ValueError("no ordering to sample: perms is empty")
         n, phi, counts, mean, m2 = state if state is not None else engine.pairs_get()
-        bits = info | (engine.info_collected() if hasattr(engine, "info_collected") else engine.info())
-        if bits & 12 and not bits & 1:
-            raise LSSPANativeError(
-                ("the fused lift scan gave up waiting for a row of its panel" if bits & 4 else
-                 "a sample's lifts did not sum to the R^2 of the full model")
-                + f" (info bits {bits}): the lift vectors of this run are not valid (engine fault)")
-        if bits & 1:
-            warnings.warn("a permuted Gram matrix was not numerically positive definite; the attribution "
-                          "of collinear features is not meaningful (the reference's is not either)",
-                          RuntimeWarning, stacklevel=2)
+        _info_verdict(info | (engine.info_collected() if hasattr(engine, "info_collected") else engine.info()),
+                      stacklevel=2)
         if info & 1:
-            theta, r_squared = _singular_fit(engine, X_test, y_test)
-        ok = True
-    finally:
-        if hasattr(source, "close"):
-            source.close()
-        if engine is not None and ok:
-            engine.pairs_enable(False)      # the tables go back (three of 134 MB at d = 4096) ...
-            if labels is not None:
-                engine.clear_players()      # ... and a player map never outlives the call that set it
-        if owns and engine is not None:
-            try:
-                if kept is None or not ok:
-                    engine.close()
-                else:
-                    engine.set_flags(0)
-                    engine.history_enable(0)
-            finally:
-                if kept is not None:
-                    kept.release()
-    Phi = 0.5 * np.asarray(mean, dtype=np.float64)
-    np.fill_diagonal(Phi, 0.0)
-    np.fill_diagonal(Phi, phi - Phi.sum(axis=1))
-    return SampledInteractionResults(interactions=Phi, attribution=phi, theta=theta, r_squared=r_squared,
-                                     interaction_errors=pair_standard_errors(counts, m2), counts=counts,
-                                     n_samples=int(n))
+            theta, r_squared = _singular_fit(engine, data[1], data[3])
+    return SampledInteractionResults(interactions=_shap_matrix(phi, mean), attribution=phi, theta=theta,
+                                     r_squared=r_squared, interaction_errors=pair_standard_errors(counts, m2),
+                                     counts=counts, n_samples=int(n))
 
 
 # ------------------------------------------------------------------------------------------
