@@ -156,6 +156,55 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
 int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */,
                               double* inter /* [g*g] */, int32_t* info);
 
+/* Bootstrap of the exact attribution (p <= 32): how far would phi move had the rows been another draw from the same
+ * population?  Replicate r resamples the rows of a side with replacement -- or takes the caller's weights -- and its
+ * reduced problem is a WEIGHTED Gram of rows that stay on the device: with z = [x, y], S = sum_i w_i z_i z_i^T per side and
+ * W = sum_i w_i of the training side,
+ *   G = S_tr[:p,:p] / W + reg I,  g = S_tr[:p,p] / W,  H = S_te[:p,:p],  h = S_te[:p,p],  ||y||^2 = S_te[p][p],
+ * then lsspa_subsets_shapley's enumeration, all replicates of a block in one grid.  fp64 throughout.
+ *   lsspa_boot_load : keeps [X | y] of both sides on the device in fp64 (arguments as lsspa_reduce's).  p > 32 is
+ *                     LSSPA_ERR_ARG naming the limit; N, M < 2^31.  The loaded problem, the running statistics and the
+ *                     exact enumerations' state are not touched, now or by any call below; a reduction or
+ *                     lsspa_set_reduced does not free the bootstrap data, and lsspa_boot_free does not touch the problem.
+ *   lsspa_boot_run  : replicates first .. first + R - 1 of the bootstrap keyed by `seed`; phi [R][p], r2 [R] (R^2 of the
+ *                     replicate's full model, by a Cholesky solve of its G on the host; NaN where that fails), info [R].
+ *                     w_train host fp64 [R][N] / w_test [R][M]: weights instead of counts on that side, finite, >= 0 and
+ *                     with a positive sum in every replicate, else LSSPA_ERR_ARG (Bayesian bootstrap, survey weights,
+ *                     a jackknife by zero weights, weight 1 everywhere for a side that is not resampled).  NULL: the
+ *                     counts below.  A replicate whose pivot fails the engine's relative test (16 p eps) has
+ *                     LSSPA_INFO_NOT_PD in ITS word, and its phi is whatever came out; the others are unaffected.
+ *                     block: replicates reduced and enumerated together, 0 = as many as 256 MB hold (counts or weights of
+ *                     both sides, Gram partials, the enumeration's partial table; at most 1024), a larger request is cut
+ *                     to that; R itself is unlimited.  Results do not depend on block or on how a run is cut into calls
+ *                     (`first`), and two runs agree bitwise: integer atomics for the counts, no floating-point atomics,
+ *                     row slices that depend on the rows alone, sums in a fixed order.  LSSPA_ERR_STATE before a load.
+ *   Counts: draw t = 0 .. n-1 of replicate r on side s (0 train, 1 test; n = N or M) picks row
+ *                     (uint64(word) * n) >> 32, word = output word t % 4 of Philox4x32-10 with key = (seed & 0xffffffff,
+ *                     seed >> 32) and counter = (t / 4, s, r & 0xffffffff, r >> 32); cnt[i] = draws that picked row i.
+ *                     Row i has probability within n / 2^32 (relative) of 1 / n.  tests/boot_ref.py restates it on
+ *                     tests/philox_ref.py bit for bit.
+ *   lsspa_boot_timing       : kernel ms of the last run: counts (or the upload of the caller's weights), Gram (both
+ *                     passes, their sums, finalise) and enumeration (any pointer may be NULL)
+ *   lsspa_boot_debug_counts : test hook -- the counts [n] of replicate r on `side`
+ *   lsspa_boot_debug_grams  : test hook -- S_train, S_test [R][p+1][p+1] and wsum [R] (training side) before finalise;
+ *                     NULL weights on a side: weight 1 on every row (any output pointer may be NULL)
+ *   lsspa_debug_boot_plan   : host only (no context, no GPU) -- how a run of R replicates on N / M rows at p features is
+ *                     cut: plan15 = cb (16-column blocks of [X | y]), ldz, block pairs, replicates per wave, rows per
+ *                     slice train / test, slices train / test, bytes per replicate, replicates per block, blocks,
+ *                     replicates per enumeration launch, units, high subsets per unit, steps per launch */
+int lsspa_boot_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                    const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                    int32_t dtype, int32_t location);
+int lsspa_boot_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train /* [R][N] or NULL */,
+                   const double* w_test /* [R][M] or NULL */, int64_t block, double* phi /* [R][p] */,
+                   double* r2 /* [R] */, int32_t* info /* [R] */);
+int lsspa_boot_free(lsspa_ctx* ctx);
+int lsspa_boot_timing(const lsspa_ctx* ctx, double* counts_ms, double* gram_ms, double* enum_ms);
+int lsspa_boot_debug_counts(lsspa_ctx* ctx, uint64_t seed, uint64_t r, int32_t side, uint32_t* out /* [n] */);
+int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, const double* w_test,
+                           double* S_train /* [R][c][c] */, double* S_test, double* wsum /* [R] */);
+int lsspa_debug_boot_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

@@ -26,6 +26,7 @@
 // With several GPUs each rank holds D and s of its own samples; x is linear in them, so ONE all-reduce of the
 // per-rank x (the same buffer and call as before) gives every rank the same draws.
 #include "kernels.h"
+#include "philox.h"
 #include "tiles.h"
 
 namespace lsspa {
@@ -33,22 +34,7 @@ namespace lsspa {
 constexpr int ND = 1024;  // draws, as in the reference
 
 // ---- running form: counter-based normals ------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32 x 32 -> 64 multiplies and xors, the key bumped by the
-// Weyl constants between rounds.  Pinned by the generator's published known-answer vectors (tests/philox_ref.py).
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t m0 = (uint64_t)0xD2511F53u * c0, m1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(m1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)m1;
-    const uint32_t n2 = (uint32_t)(m0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)m0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// Philox4x32-10 itself is in philox.h (the bootstrap's counts kernel, k_boot.hip, draws from it too).
 // The two normals Philox call j of sample `id` yields: u1, u2 = the 53 high bits of (w0, w1), (w2, w3) plus a half, over
 // 2^53 -- both in (0, 1) --, then Box-Muller.  They are draws 64 b + r and 64 b + r + 32 of the sample, j = 32 b + r
 // (r < 32).

@@ -35,6 +35,10 @@
 // SHH = 6 a lane) with their masks built once.  A unit's row of the partial table is then
 //   [0 .. p] as above | T0 | T1 [p] | T2 [p (p - 1) / 2] (pairs i < j, row-major),
 // its first p + 1 columns computed by the very operations of the phi-only kernel.
+//
+// Replicates (the bootstrap, k_boot.hip): launch_subsets_enum(.., reps) runs `reps` problems laid out one behind the other
+// as the second grid dimension of the phi-only kernel (the REPS instantiation, rep_offset below); a replicate's arithmetic
+// is that of the one-problem kernel, operation for operation.
 #include "kernels.h"
 
 namespace lsspa {
@@ -60,6 +64,13 @@ struct SubShared {
   int idx[SP];             // compacted position -> feature
 };
 
+// Replicates (the bootstrap, k_boot.hip): replicate r = blockIdx.y of a launch has its problem r strides behind the
+// launch's -- G, H: p ld, g, h: p, one 1 / ||y||^2 and one info word each, part: the table of the replicates before it.
+// That is the REPS instantiation of the phi-only kernel; without REPS the replicate is 0 at compile time and the code is
+// what it was before replicates existed (the kernel sits at the edge of its register budget: see DESIGN.md).
+template <bool REPS>
+__device__ inline int64_t rep_offset(int64_t stride) { return REPS ? (int64_t)blockIdx.y * stride : 0; }
+
 __device__ inline double wave_sum(double x) {
   // fixed butterfly, then lane 0's value for everyone: the same order on every call
 #pragma unroll
@@ -69,6 +80,7 @@ __device__ inline double wave_sum(double x) {
 
 // v(Hs + T) of this lane's low subset T = lane (0 for lanes >= 2^q).  Enters and leaves with the workgroup (one wave)
 // in step: every shared array it writes is free when it is called and is read by nobody after it returns.
+template <bool REPS>
 __device__ double subset_values(SubShared& sh, const SubsetArgs& a, uint64_t hi, int lane, bool& bad) {
   const int p = a.p, q = a.q;
   const int nhs = __popcll(hi);
@@ -81,6 +93,8 @@ __device__ double subset_values(SubShared& sh, const SubsetArgs& a, uint64_t hi,
   const int nk = nhs + q;     // features of Hs + low
   const int n = nk + 1;       // ... and the right-hand side
   const int nn = n * n;
+  const double* Gr = a.G + rep_offset<REPS>(p * a.ldg);
+  const double* gr = a.g + rep_offset<REPS>(p);
   __syncthreads();
   int ea[SENT], eb[SENT];
 #pragma unroll
@@ -92,11 +106,11 @@ __device__ double subset_values(SubShared& sh, const SubsetArgs& a, uint64_t hi,
       const int i = ea[r], j = eb[r];
       double val = 0.0;
       if (i < nk && j < nk)
-        val = a.G[(int64_t)sh.idx[i] * a.ldg + sh.idx[j]];
+        val = Gr[(int64_t)sh.idx[i] * a.ldg + sh.idx[j]];
       else if (i < nk)
-        val = a.g[sh.idx[i]];
+        val = gr[sh.idx[i]];
       else if (j < nk)
-        val = a.g[sh.idx[j]];
+        val = gr[sh.idx[j]];
       sh.M[i * LDM + j] = val;
     }
   }
@@ -215,20 +229,22 @@ __device__ double subset_values(SubShared& sh, const SubsetArgs& a, uint64_t hi,
         f += y[t] * u;
       }
     }
-    v = f * a.inv_yy;
+    v = f * a.inv_yy[rep_offset<REPS>(1)];
   }
   return v;
 }
 
+template <bool REPS>
 __device__ void load_shared(SubShared& sh, const SubsetArgs& a, int lane) {
   const int p = a.p;
+  const double* Hr = a.H + rep_offset<REPS>(p * a.ldh);
   for (int e = lane; e < p * p; e += 64) {
     const int i = e / p, j = e - i * p;
-    sh.H[i * LDM + j] = a.H[(int64_t)i * a.ldh + j];
+    sh.H[i * LDM + j] = Hr[(int64_t)i * a.ldh + j];
   }
   if (lane < p) {
-    sh.h[lane] = a.h[lane];
-    sh.gdiag[lane] = a.G[(int64_t)lane * a.ldg + lane];
+    sh.h[lane] = a.h[rep_offset<REPS>(p) + lane];
+    sh.gdiag[lane] = a.G[rep_offset<REPS>(p * a.ldg) + (int64_t)lane * a.ldg + lane];
   }
   if (lane <= p) {
     sh.wa[lane] = a.w[lane];
@@ -242,13 +258,13 @@ __device__ inline int pair_col(int p, int i, int j) { return i * (2 * p - i - 1)
 
 // INTER: the interaction sums T0, T1, T2 beside phi's (lsspa_subsets_interactions); a row of part is then
 // subsets_inter_cols(p) wide.  Everything of the phi-only instantiation is in both, unchanged.
-template <bool INTER>
+template <bool INTER, bool REPS = false>
 __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t s0, uint64_t s1) {
   __shared__ SubShared sh;
   __shared__ double w2[INTER ? 3 * (SP + 1) : 1];   // gamma, beta + gamma, alpha + 2 beta + gamma by |K|
   const int lane = threadIdx.x;
   const int p = a.p, q = a.q, nh = p - q;
-  load_shared(sh, a, lane);
+  load_shared<REPS>(sh, a, lane);
   double acc[SNH];
 #pragma unroll
   for (int j = 0; j < SNH; ++j) acc[j] = 0.0;
@@ -279,7 +295,7 @@ __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t
   const int kt = __popc(lane);
   for (uint64_t s = s0; s < s1; ++s) {
     const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
-    const double v = subset_values(sh, a, hi, lane, bad);
+    const double v = subset_values<REPS>(sh, a, hi, lane, bad);
     if (live) {
       const int k = __popcll(hi) + kt;
       const double c = (sh.wa[k] + sh.wb[k]) * v;
@@ -315,7 +331,7 @@ __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t
     }
     __syncthreads();
   }
-  double* part = a.part + (int64_t)blockIdx.x * (INTER ? (p + 2 + p + p * (p - 1) / 2) : (p + 1));
+  double* part = a.part + (rep_offset<REPS>(gridDim.x) + blockIdx.x) * (INTER ? (p + 2 + p + p * (p - 1) / 2) : (p + 1));
 #pragma unroll
   for (int t = 0; t < SQ; ++t) {
     if (t < q) {
@@ -371,12 +387,14 @@ __global__ __launch_bounds__(64) void subsets_enum_kernel(SubsetArgs a, uint64_t
       }
     }
   }
-  if (__any(bad) && lane == 0) atomicOr(a.info, 1);
+  if (__any(bad) && lane == 0) atomicOr(a.info + rep_offset<REPS>(1), 1);
 }
 
 __global__ __launch_bounds__(64) void subsets_reduce_kernel(const double* __restrict__ part, int64_t units, int p1,
                                                             double* __restrict__ out) {
   const int j = blockIdx.x, lane = threadIdx.x;
+  part += rep_offset<true>(units * p1);      // replicate blockIdx.y: its table, its sums
+  out += rep_offset<true>(p1);
   double s = 0.0;
   for (int64_t u = lane; u < units; u += 64) s += part[u * p1 + j];
   s = wave_sum(s);
@@ -387,12 +405,12 @@ __global__ __launch_bounds__(64) void subsets_debug_kernel(SubsetArgs a, const u
                                                            int64_t n, double* __restrict__ vals) {
   __shared__ SubShared sh;
   const int lane = threadIdx.x;
-  load_shared(sh, a, lane);
+  load_shared<false>(sh, a, lane);
   bool bad = false;
   const uint64_t low = (1ull << a.q) - 1ull;
   for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
     const uint64_t m = masks[i];
-    const double v = subset_values(sh, a, m >> a.q, lane, bad);
+    const double v = subset_values<false>(sh, a, m >> a.q, lane, bad);
     if ((uint64_t)lane == (m & low)) vals[i] = v;
     __syncthreads();
   }
@@ -430,7 +448,7 @@ __global__ __launch_bounds__(256) void subsets_test_gram_kernel(const double* __
 
 bool args_ok(const SubsetArgs& a) {
   return a.p >= 1 && a.p <= SP && a.q == (a.p < SQ ? a.p : SQ) && a.G && a.g && a.H && a.h && a.w && a.info &&
-         a.ldg >= a.p && a.ldh >= a.p;
+         a.inv_yy && a.ldg >= a.p && a.ldh >= a.p;
 }
 
 }  // namespace
@@ -440,21 +458,27 @@ int subsets_low_features(int p) { return p < SQ ? p : SQ; }
 int subsets_inter_cols(int p) { return p + 2 + p + p * (p - 1) / 2; }
 
 hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
-                               hipStream_t st) {
+                               hipStream_t st, int reps) {
   if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // replicates: phi only (the caller vouches for `reps` problems, tables, info words behind the first)
+  if (reps < 1 || reps > 65535 || (reps > 1 && inter)) return hipErrorInvalidValue;
   // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^(p - q)
   const int nh = a.p - a.q;
   if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
   if (inter)
     hipLaunchKernelGGL(subsets_enum_kernel<true>, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
+  else if (reps > 1)
+    hipLaunchKernelGGL((subsets_enum_kernel<false, true>), dim3((unsigned)units, (unsigned)reps), dim3(64), 0, st, a, s0,
+                       s1);
   else
     hipLaunchKernelGGL(subsets_enum_kernel<false>, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
   return hipGetLastError();
 }
 
-hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st) {
-  if (!part || !out || units < 1 || cols < 2 || cols > subsets_inter_cols(SP)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(subsets_reduce_kernel, dim3(cols), dim3(64), 0, st, part, units, cols, out);
+hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st, int reps) {
+  if (!part || !out || units < 1 || cols < 2 || cols > subsets_inter_cols(SP) || reps < 1 || reps > 65535)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_reduce_kernel, dim3(cols, (unsigned)reps), dim3(64), 0, st, part, units, cols, out);
   return hipGetLastError();
 }
 

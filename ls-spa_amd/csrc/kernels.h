@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 
+#include "boot_plan.h"
 #include "players.h"
 
 namespace lsspa {
@@ -319,17 +320,23 @@ struct SubsetArgs {
                            // inter: [5][SUBSETS_MAX_P + 1], the interaction weights after them
   int p, q;
   double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
-  double inv_yy;           // 1 / ||y_test||^2
+  const double* inv_yy;    // [replicates] 1 / ||y_test||^2 (device)
   uint64_t per;            // high subsets per unit
   double* part;            // [units][p + 1], inter: [units][subsets_inter_cols(p)]
-  int32_t* info;           // bit 1: a pivot failed
+  int32_t* info;           // [replicates] bit 1: a pivot failed
+  // Replicates (the bootstrap, k_boot.hip): a launch with `reps` replicates runs them as its second grid dimension;
+  // replicate r has its problem at the dense replicate stride behind the launch's: G + r p ldg, g + r p, H + r p ldh,
+  // h + r p, inv_yy[r], info[r], part + r units cols.  One replicate (every other launch): r = 0, nothing moves.
 };
 int subsets_low_features(int p);
 int subsets_inter_cols(int p);
+// reps > 1 (phi only): the replicates behind the launch's problem (SubsetArgs) as its second grid dimension
 hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
-                               hipStream_t st);
-// out[j] = sum over the units of part[u][j], j < cols (the table's width), in a fixed order
-hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st);
+                               hipStream_t st, int reps = 1);
+// out[j] = sum over the units of part[u][j], j < cols (the table's width), in a fixed order; replicate r of `reps` reads
+// part + r units cols and writes out + r cols
+hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st,
+                                 int reps = 1);
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used
@@ -377,5 +384,30 @@ hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, u
                               hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
+
+// Bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp), p <= SUBSETS_MAX_P, fp64.  Z = [X | y] of one side
+// lives on the device as [n][ldz], ldz = 16 cb, cb = ceil((p + 1) / 16), columns beyond p zero.  A BLOCK of replicates
+// is reduced at a time: counts or weights [block][n], one weighted Gram pass per side into per-slice partial sums, a
+// fixed-order sum over the slices, finalise, and one enumeration grid for all its replicates.
+// BootPlan, boot_plan and the bounds they work with: boot_plan.h (host code that compiles without the HIP headers).
+
+// cnt[r][i] (uint32, zeroed by the launch) = how often row i is drawn among the n draws of replicate r0 + r, side s
+hipError_t launch_boot_counts(uint64_t seed, uint64_t r0, int side, int64_t n, int reps, uint32_t* cnt, hipStream_t st);
+// part[slice][r][pair][256] = sum over the slice's rows of w[r][i] z_i z_i^T, 16 x 16 blocks (bi <= bj) in the matrix
+// instruction's accumulator layout; w = cnt (uint32) or wt (fp64), exactly one of them non-null, [reps][n]
+hipError_t launch_boot_gram(const BootPlan& P, int side, const double* Z, int64_t n, const uint32_t* cnt,
+                            const double* wt, int reps, double* part, hipStream_t st);
+// wsum[r] = sum_i w[r][i] in a fixed order
+hipError_t launch_boot_wsum(const uint32_t* cnt, const double* wt, int64_t n, int reps, double* wsum, hipStream_t st);
+// S[r][c][c] (c = p + 1, exactly symmetric) = sum over the slices, in order, of the partials
+hipError_t launch_boot_reduce(const BootPlan& P, int side, const double* part, int p, int reps, double* S,
+                              hipStream_t st);
+// G[r] = S_tr[:p,:p] / W + reg I (stride p), g[r] = S_tr[:p,p] / W, H[r] = S_te[:p,:p], h[r] = S_te[:p,p],
+// inv_yy[r] = 1 / S_te[p][p], W = wsum_tr[r]
+hipError_t launch_boot_finalize(const double* S_tr, const double* S_te, const double* wsum_tr, int p, double reg,
+                                int reps, double* G, double* g, double* H, double* h, double* inv_yy, hipStream_t st);
+// Z[i][0 .. p-1] = X[i][:], Z[i][p] = y[i], zero up to ldz, for rows row0 .. row0 + rows - 1 of Z; X [rows][ld], y [rows]
+hipError_t launch_boot_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Z,
+                            int ldz, int64_t row0, hipStream_t st);
 
 }  // namespace lsspa

@@ -57,6 +57,37 @@ struct ExactWork {
   }
 };
 
+// What the bootstrap keeps (lsspa_boot_load .. lsspa_boot_free): the rows of both sides and the buffers of one block of
+// replicates.  Nothing of the loaded problem, the sampling path or the exact enumerations' state is in here, and a
+// reduction does not touch it.
+struct BootWork {
+  bool loaded = false;
+  int p = 0;
+  int64_t n[2] = {0, 0};                   // rows: train, test
+  double reg = 0.0;
+  DevBuf<double> Z0, Z1;                   // [n][ldz] rows [X | y] of the two sides, zero-padded columns
+  DevBuf<char> stage_x, stage_y;           // host rows on their way into Z
+  DevBuf<uint32_t> cnt0, cnt1;             // [block][n] bootstrap counts
+  DevBuf<double> wt0, wt1;                 // [block][n] caller's weights
+  DevBuf<double> part0, part1, S0, S1, wsum;   // Gram partials, their sums [block][c][c], sum of the training weights
+  DevBuf<double> G, g, H, h, inv_yy;       // the block's reduced problems
+  DevBuf<double> w, epart, eout;           // Shapley weights, the enumeration's partial table and its column sums
+  DevBuf<int32_t> info;                    // [block]
+  double ms[3] = {0.0, 0.0, 0.0};          // kernel ms of the last run: counts, Gram (to the reduced problems), enumeration
+  DevBuf<double>& Z(int s) { return s ? Z1 : Z0; }
+  DevBuf<uint32_t>& cnt(int s) { return s ? cnt1 : cnt0; }
+  DevBuf<double>& wt(int s) { return s ? wt1 : wt0; }
+  DevBuf<double>& part(int s) { return s ? part1 : part0; }
+  DevBuf<double>& S(int s) { return s ? S1 : S0; }
+  void release() {
+    dev_free(Z0); dev_free(Z1); dev_free(stage_x); dev_free(stage_y); dev_free(cnt0); dev_free(cnt1);
+    dev_free(wt0); dev_free(wt1); dev_free(part0); dev_free(part1); dev_free(S0); dev_free(S1); dev_free(wsum);
+    dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(epart);
+    dev_free(eout); dev_free(info);
+    loaded = false;
+  }
+};
+
 }  // namespace
 
 // One lane = everything a batch of orderings needs while its kernels run: work matrices, solve results, staged
@@ -186,6 +217,7 @@ struct lsspa_ctx {
   DevBuf<double> theta_d;        // lsspa_full_fit's back-substitution
   // exact attribution by subset enumeration (lsspa_subsets_shapley) and over groups of columns (lsspa_groups_shapley)
   ExactWork sub, grp;
+  BootWork boot;                 // bootstrap of the exact attribution (lsspa_boot_*)
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -1189,6 +1221,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   dev_free(ctx->Gf); dev_free(ctx->Hf);
   ctx->sub.release();
   ctx->grp.release();
+  ctx->boot.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
   dev_free(ctx->pr_delta); dev_free(ctx->pr_lifts); dev_free(ctx->pr_pos); dev_free(ctx->pr_perms);
@@ -3087,29 +3120,11 @@ uint64_t exact_units(uint64_t n_high) { return std::min(n_high, EXACT_UNITS); }
 // beside the weights (nullptr: none).  The weight table carries three more rows, the interaction weights of n players
 // (kernels.h, SubsetArgs::w), which only the interactions kernel reads.
 constexpr int EXACT_W_ROWS = 5;
-template <typename Args>
-int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, const int32_t* tab, Args& a) {
-  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, no_problem);
-  const int p = ctx->p;
-  HIPCHK(hipSetDevice(ctx->device));
-  a = Args{};
-  a.G = ctx->G.ptr;
-  a.g = ctx->g.ptr;
-  a.ldg = ctx->p_pad;
-  if (ctx->tri) {
-    a.H = ctx->H.ptr;
-    a.h = ctx->h.ptr;
-    a.ldh = ctx->p_pad;
-  } else {
-    TRY(dev_alloc(ctx, W.Hh, (size_t)p * p + p));
-    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, W.Hh.ptr, ctx->stream));
-    a.H = W.Hh.ptr;
-    a.h = W.Hh.ptr + (size_t)p * p;
-    a.ldh = p;
-  }
+// w [EXACT_W_ROWS][EXACT_MAX_PLAYERS + 1]: the Shapley weights of n players by subset size (kernels.h, SubsetArgs::w)
+void exact_weight_table(int n, double* w) {
   // w(k) = k! (n - 1 - k)! / n! = 1 / (n C(n - 1, k)); C(31, k) < 2^53 is exact in fp64
   constexpr int WR = EXACT_MAX_PLAYERS + 1;
-  double w[EXACT_W_ROWS * WR] = {0.0};
+  std::fill(w, w + EXACT_W_ROWS * WR, 0.0);
   double binom = 1.0;
   for (int k = 0; k < n; ++k) {
     const double wk = 1.0 / ((double)n * binom);
@@ -3131,7 +3146,35 @@ int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, cons
     w[3 * WR + k] = be + ga;
     w[4 * WR + k] = al + 2.0 * be + ga;
   }
-  TRY(dev_alloc(ctx, W.w, EXACT_W_ROWS * WR));
+}
+// the subsets kernel reads 1 / ||y||^2 per replicate from the device, the groups kernel takes the value
+inline void set_inv_yy(SubsetArgs& a, const double* on_device, double) { a.inv_yy = on_device; }
+inline void set_inv_yy(GroupArgs& a, const double*, double value) { a.inv_yy = value; }
+template <typename Args>
+int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, const int32_t* tab, Args& a) {
+  if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, no_problem);
+  const int p = ctx->p;
+  HIPCHK(hipSetDevice(ctx->device));
+  a = Args{};
+  a.G = ctx->G.ptr;
+  a.g = ctx->g.ptr;
+  a.ldg = ctx->p_pad;
+  if (ctx->tri) {
+    a.H = ctx->H.ptr;
+    a.h = ctx->h.ptr;
+    a.ldh = ctx->p_pad;
+  } else {
+    TRY(dev_alloc(ctx, W.Hh, (size_t)p * p + p));
+    HIPCHK(launch_subsets_test_gram(ctx->Ft.ptr, ctx->m_pad, ctx->ytil.ptr, p, ctx->m, W.Hh.ptr, ctx->stream));
+    a.H = W.Hh.ptr;
+    a.h = W.Hh.ptr + (size_t)p * p;
+    a.ldh = p;
+  }
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  double w[EXACT_W_ROWS * WR + 1];
+  exact_weight_table(n, w);
+  w[EXACT_W_ROWS * WR] = 1.0 / ctx->y_norm_sq;     // behind the table: what SubsetArgs::inv_yy points at
+  TRY(dev_alloc(ctx, W.w, EXACT_W_ROWS * WR + 1));
   if (tab) TRY(dev_alloc(ctx, W.tab, GROUPS_TAB_LEN));
   TRY(dev_alloc(ctx, W.info, 8));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // a previous call may still read W.w / W.tab; the copies are from host frames
@@ -3140,7 +3183,7 @@ int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, cons
   HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
   a.w = W.w.ptr;
   a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  a.inv_yy = 1.0 / ctx->y_norm_sq;
+  set_inv_yy(a, W.w.ptr + EXACT_W_ROWS * WR, w[EXACT_W_ROWS * WR]);
   a.info = W.info.ptr;
   return LSSPA_OK;
 }
@@ -3442,6 +3485,370 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
   };
   return exact_debug_values(ctx, ctx->grp, lay.data(), n, u, launch,
                             "a group subset's Gram matrix is not positive definite");
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+}  // extern "C"
+
+// ---- bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp) ------------------------------------------------
+// lsspa_boot_run cuts its R replicates into blocks (boot_plan: by memory).  A block: the weights of both sides on the
+// device (counts drawn there, or the caller's rows copied), one weighted Gram pass per side, the fixed-order sum of its
+// slices, finalise, and the enumeration of k_subsets.hip with the block's replicates as its second grid dimension.
+namespace {
+
+static_assert(EXACT_UNITS == BOOT_UNITS && SUBSETS_PER_LAUNCH == BOOT_SUBSETS_PER_LAUNCH && SUBSETS_MAX_P == BOOT_MAX_P,
+              "boot_plan cuts the enumeration as exact_enumerate does");
+
+int boot_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->boot.loaded) return ctx->fail(LSSPA_ERR_STATE, "no bootstrap data loaded (lsspa_boot_load comes first)");
+  return LSSPA_OK;
+}
+
+// finite, >= 0, a positive sum in every replicate
+int boot_check_weights(lsspa_ctx* ctx, const double* w, int64_t R, int64_t n, const char* name) {
+  char msg[200];
+  for (int64_t r = 0; r < R; ++r) {
+    double sum = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = w[r * n + i];
+      if (!(v >= 0.0) || !std::isfinite(v)) {
+        snprintf(msg, sizeof msg, "%s[%lld][%lld] = %g: weights must be finite and >= 0", name, (long long)r,
+                 (long long)i, v);
+        return ctx->fail(LSSPA_ERR_ARG, msg);
+      }
+      sum += v;
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) {
+      snprintf(msg, sizeof msg, "%s: the weights of replicate %lld sum to %g (a positive finite sum is needed)", name,
+               (long long)r, sum);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  }
+  return LSSPA_OK;
+}
+
+int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, bool counts[2], bool enumerate) {
+  BootWork& B = ctx->boot;
+  const size_t blk = (size_t)P.block, c = (size_t)B.p + 1, p = (size_t)B.p;
+  for (int s = 0; s < 2; ++s) {
+    if (counts[s])
+      TRY(dev_alloc(ctx, B.cnt(s), blk * (size_t)B.n[s]));
+    else
+      TRY(dev_alloc(ctx, B.wt(s), blk * (size_t)B.n[s]));
+    TRY(dev_alloc(ctx, B.part(s), (size_t)P.slices[s] * blk * P.pairs * 256));
+    TRY(dev_alloc(ctx, B.S(s), blk * c * c));
+  }
+  TRY(dev_alloc(ctx, B.wsum, blk));
+  if (!enumerate) return LSSPA_OK;
+  TRY(dev_alloc(ctx, B.G, blk * p * p));
+  TRY(dev_alloc(ctx, B.H, blk * p * p));
+  TRY(dev_alloc(ctx, B.g, blk * p));
+  TRY(dev_alloc(ctx, B.h, blk * p));
+  TRY(dev_alloc(ctx, B.inv_yy, blk));
+  TRY(dev_alloc(ctx, B.info, blk));
+  TRY(dev_alloc(ctx, B.epart, (size_t)P.enum_reps * P.units * c));
+  TRY(dev_alloc(ctx, B.eout, blk * c));
+  TRY(dev_alloc(ctx, B.w, EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)));
+  return LSSPA_OK;
+}
+
+// The weights of replicates b0 .. b0 + nb - 1 of a run onto the device (w_host: the caller's [R][n] rows; NULL: counts
+// of replicates r0 + b0 ..., or with `ones` weight 1 everywhere), then S [nb][c][c] of both sides and the sum of the
+// training weights.  Nothing waits.  ev (may be NULL): events recorded after the counts and after the sums.
+int boot_block_sums(lsspa_ctx* ctx, const BootPlan& P, const double* const w_host[2], bool ones, uint64_t seed,
+                    uint64_t r0, int64_t b0, int nb, hipEvent_t after_counts) {
+  BootWork& B = ctx->boot;
+  hipStream_t st = ctx->stream;
+  std::vector<double> one;
+  for (int s = 0; s < 2; ++s) {
+    if (w_host[s]) {
+      HIPCHK(hipMemcpyAsync(B.wt(s).ptr, w_host[s] + b0 * B.n[s], sizeof(double) * (size_t)nb * B.n[s],
+                            hipMemcpyHostToDevice, st));
+    } else if (ones) {
+      one.assign((size_t)nb * B.n[s], 1.0);
+      HIPCHK(hipMemcpyAsync(B.wt(s).ptr, one.data(), sizeof(double) * one.size(), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));        // `one` is reused for the other side
+    } else {
+      HIPCHK(launch_boot_counts(seed, r0 + (uint64_t)b0, s, B.n[s], nb, B.cnt(s).ptr, st));
+    }
+  }
+  if (after_counts) HIPCHK(hipEventRecord(after_counts, st));
+  for (int s = 0; s < 2; ++s) {
+    const bool counts = !w_host[s] && !ones;
+    const uint32_t* cnt = counts ? B.cnt(s).ptr : nullptr;
+    const double* wt = counts ? nullptr : B.wt(s).ptr;
+    HIPCHK(launch_boot_gram(P, s, B.Z(s).ptr, B.n[s], cnt, wt, nb, B.part(s).ptr, st));
+    if (s == 0) HIPCHK(launch_boot_wsum(cnt, wt, B.n[s], nb, B.wsum.ptr, st));
+    HIPCHK(launch_boot_reduce(P, s, B.part(s).ptr, B.p, nb, B.S(s).ptr, st));
+  }
+  return LSSPA_OK;
+}
+
+// R^2 of the full model of one replicate on the host: theta = G^-1 g by Cholesky, (2 theta.h - theta.H theta) / ||y||^2;
+// NaN where G is not positive definite
+double boot_r2(int p, const double* G, const double* g, const double* H, const double* h, double inv_yy) {
+  double L[SUBSETS_MAX_P * SUBSETS_MAX_P], t[SUBSETS_MAX_P];
+  for (int j = 0; j < p; ++j) {
+    double d = G[j * p + j];
+    for (int k = 0; k < j; ++k) d -= L[j * p + k] * L[j * p + k];
+    if (!(d > 0.0)) return std::nan("");
+    const double l = std::sqrt(d);
+    L[j * p + j] = l;
+    for (int i = j + 1; i < p; ++i) {
+      double v = G[i * p + j];
+      for (int k = 0; k < j; ++k) v -= L[i * p + k] * L[j * p + k];
+      L[i * p + j] = v / l;
+    }
+  }
+  for (int i = 0; i < p; ++i) {
+    double v = g[i];
+    for (int k = 0; k < i; ++k) v -= L[i * p + k] * t[k];
+    t[i] = v / L[i * p + i];
+  }
+  for (int i = p - 1; i >= 0; --i) {
+    double v = t[i];
+    for (int k = i + 1; k < p; ++k) v -= L[k * p + i] * t[k];
+    t[i] = v / L[i * p + i];
+  }
+  double lin = 0.0, quad = 0.0;
+  for (int i = 0; i < p; ++i) {
+    lin += t[i] * h[i];
+    double v = 0.0;
+    for (int j = 0; j < p; ++j) v += H[i * p + j] * t[j];
+    quad += t[i] * v;
+  }
+  return (2.0 * lin - quad) * inv_yy;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_debug_boot_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15) try {
+  if (!plan15) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
+  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
+                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
+  std::copy(v, v + 15, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_boot_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                    const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                    int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  char msg[200];
+  if (p > SUBSETS_MAX_P) {
+    snprintf(msg, sizeof msg, "the bootstrap of the exact attribution takes at most p = %d features (%d given)",
+             SUBSETS_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  if (const char* why = boot_plan(1, N, M, p, 0, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_load: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (!X_train || !y_train || !X_test || !y_test || ld_train < p || ld_test < p || !std::isfinite(reg) ||
+      (dtype != LSSPA_F64 && dtype != LSSPA_F32) || (location != LSSPA_HOST && location != LSSPA_DEVICE))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_load: NULL array, ld < p, reg not finite, or bad dtype / location");
+  HIPCHK(hipSetDevice(ctx->device));
+  BootWork& B = ctx->boot;
+  B.loaded = false;
+  const void* X[2] = {X_train, X_test};
+  const void* y[2] = {y_train, y_test};
+  const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test};
+  const size_t esz = dtype == LSSPA_F32 ? 4 : 8;
+  for (int s = 0; s < 2; ++s) {
+    TRY(dev_alloc(ctx, B.Z(s), (size_t)n[s] * P.ldz));
+    if (location == LSSPA_DEVICE) {
+      HIPCHK(launch_boot_pack(X[s], ld[s], y[s], n[s], p, dtype == LSSPA_F32, B.Z(s).ptr, P.ldz, 0, ctx->stream));
+      continue;
+    }
+    // host rows: through a staging buffer of at most ~64 MB, chunk by chunk (plain copies, as lsspa_reduce's)
+    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n[s], (64ll << 20) / (int64_t)(ld[s] * esz)));
+    TRY(dev_alloc(ctx, B.stage_x, (size_t)rows * ld[s] * esz));
+    TRY(dev_alloc(ctx, B.stage_y, (size_t)rows * esz));
+    for (int64_t r0 = 0; r0 < n[s]; r0 += rows) {
+      const int64_t nr = std::min(rows, n[s] - r0);
+      // the last row of the caller's array ends with its column p - 1
+      const size_t xbytes = ((size_t)(nr - 1) * ld[s] + p) * esz;
+      HIPCHK(hipMemcpyAsync(B.stage_x.ptr, (const char*)X[s] + (size_t)r0 * ld[s] * esz, xbytes, hipMemcpyHostToDevice,
+                            ctx->stream));
+      HIPCHK(hipMemcpyAsync(B.stage_y.ptr, (const char*)y[s] + (size_t)r0 * esz, (size_t)nr * esz,
+                            hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(launch_boot_pack(B.stage_x.ptr, ld[s], B.stage_y.ptr, nr, p, dtype == LSSPA_F32, B.Z(s).ptr, P.ldz, r0,
+                              ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));     // the staging buffer is reused
+    }
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  dev_free(B.stage_x);
+  dev_free(B.stage_y);
+  B.p = p;
+  B.n[0] = N;
+  B.n[1] = M;
+  B.reg = reg;
+  B.loaded = true;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->boot.release();
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train,
+                   const double* w_test, int64_t block, double* phi, double* r2, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  BootWork& B = ctx->boot;
+  if (!phi || !r2 || !info || first < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_run: phi / r2 / info NULL or first < 0");
+  BootPlan P;
+  if (const char* why = boot_plan(R, B.n[0], B.n[1], B.p, block, P)) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "lsspa_boot_run: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {!w_train, !w_test};
+  TRY(boot_alloc_block(ctx, P, counts, true));
+  hipStream_t st = ctx->stream;
+  const int p = B.p, c = p + 1;
+  {
+    double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
+    exact_weight_table(p, w);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(B.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  }
+  std::vector<hipEvent_t> ev(4, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  std::vector<double> out((size_t)P.block * c), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
+      gh((size_t)P.block * p), hh((size_t)P.block * p), yh((size_t)P.block);
+  B.ms[0] = B.ms[1] = B.ms[2] = 0.0;
+  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
+    const int nb = (int)std::min<int64_t>(P.block, R - b0);
+    HIPCHK(hipEventRecord(ev[0], st));
+    TRY(boot_block_sums(ctx, P, w_host, false, seed, (uint64_t)first, b0, nb, ev[1]));
+    HIPCHK(launch_boot_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
+                                B.inv_yy.ptr, st));
+    HIPCHK(hipEventRecord(ev[2], st));
+    HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
+    for (int e0 = 0; e0 < nb; e0 += (int)P.enum_reps) {
+      const int ne = std::min<int>((int)P.enum_reps, nb - e0);
+      SubsetArgs a{};
+      a.p = p;
+      a.q = subsets_low_features(p);
+      a.G = B.G.ptr + (size_t)e0 * p * p;
+      a.H = B.H.ptr + (size_t)e0 * p * p;
+      a.g = B.g.ptr + (size_t)e0 * p;
+      a.h = B.h.ptr + (size_t)e0 * p;
+      a.ldg = a.ldh = p;
+      a.w = B.w.ptr;
+      a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+      a.inv_yy = B.inv_yy.ptr + e0;
+      a.info = B.info.ptr + e0;
+      a.per = P.per;
+      a.part = B.epart.ptr;
+      HIPCHK(hipMemsetAsync(B.epart.ptr, 0, sizeof(double) * (size_t)ne * P.units * c, st));
+      for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps)
+        HIPCHK(launch_subsets_enum(a, P.units, s0, std::min(P.per, s0 + P.steps), false, st, ne));
+      HIPCHK(launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, c, B.eout.ptr + (size_t)e0 * c, st, ne));
+    }
+    HIPCHK(hipEventRecord(ev[3], st));
+    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Gh.data(), B.G.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Hh.data(), B.H.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(gh.data(), B.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hh.data(), B.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(yh.data(), B.inv_yy.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int r = 0; r < nb; ++r) {
+      for (int j = 0; j < p; ++j) phi[(b0 + r) * p + j] = out[(size_t)r * c + j] - out[(size_t)r * c + p];
+      r2[b0 + r] = boot_r2(p, &Gh[(size_t)r * p * p], &gh[(size_t)r * p], &Hh[(size_t)r * p * p], &hh[(size_t)r * p],
+                           yh[r]);
+    }
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      B.ms[k] += ms;
+    }
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_timing(const lsspa_ctx* ctx, double* counts_ms, double* gram_ms, double* enum_ms) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (counts_ms) *counts_ms = ctx->boot.ms[0];
+  if (gram_ms) *gram_ms = ctx->boot.ms[1];
+  if (enum_ms) *enum_ms = ctx->boot.ms[2];
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_boot_debug_counts(lsspa_ctx* ctx, uint64_t seed, uint64_t r, int32_t side, uint32_t* out) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  if (!out || side < 0 || side > 1) return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_debug_counts: out NULL or side not 0 / 1");
+  HIPCHK(hipSetDevice(ctx->device));
+  BootWork& B = ctx->boot;
+  const int64_t n = B.n[side];
+  TRY(dev_alloc(ctx, B.cnt(side), (size_t)n));
+  HIPCHK(launch_boot_counts(seed, r, side, n, 1, B.cnt(side).ptr, ctx->stream));
+  HIPCHK(hipMemcpyAsync(out, B.cnt(side).ptr, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, const double* w_test, double* S_train,
+                           double* S_test, double* wsum) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  BootWork& B = ctx->boot;
+  BootPlan P;
+  if (const char* why = boot_plan(R, B.n[0], B.n[1], B.p, 0, P)) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "lsspa_boot_debug_grams: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {false, false};
+  TRY(boot_alloc_block(ctx, P, counts, false));
+  const size_t cc = (size_t)(B.p + 1) * (B.p + 1);
+  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
+    const int nb = (int)std::min<int64_t>(P.block, R - b0);
+    TRY(boot_block_sums(ctx, P, w_host, true, 0, 0, b0, nb, nullptr));
+    if (S_train)
+      HIPCHK(hipMemcpyAsync(S_train + b0 * cc, B.S0.ptr, sizeof(double) * nb * cc, hipMemcpyDeviceToHost, ctx->stream));
+    if (S_test)
+      HIPCHK(hipMemcpyAsync(S_test + b0 * cc, B.S1.ptr, sizeof(double) * nb * cc, hipMemcpyDeviceToHost, ctx->stream));
+    if (wsum) HIPCHK(hipMemcpyAsync(wsum + b0, B.wsum.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
 }

@@ -30,7 +30,8 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import InteractionResults, SampledInteractionResults, ShapleyResults, validate_data
+from ._results import (BootstrapResults, InteractionResults, SampledInteractionResults, ShapleyResults,
+                       validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -1088,6 +1089,105 @@ def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, groups=None
     return _ls_spa_subsets(*data, reg, perms=None, return_attribution_history=False,
                            device=device, row_sharded=row_sharded, checkpoint=None, comm=comm, engine=_engine,
                            groups=groups, interactions=True)
+
+
+BOOT_ONES_BYTES = 64 << 20     # ls_spa_bootstrap: host bytes of the unit weights of a side that is not resampled
+
+
+def _bootstrap_options(n_boot, confidence, weights, resample, n, m):
+    """(w_train, w_test, sides): the caller's weights as (n_boot, rows) float64 arrays or None, and which sides are
+    resampled; ValueError names what is wrong.  Needs no engine."""
+    if int(n_boot) != n_boot or n_boot < 2:
+        raise ValueError(f"n_boot must be an integer >= 2 (got {n_boot!r})")
+    if not 0.0 < float(confidence) < 1.0:
+        raise ValueError(f"confidence must lie strictly between 0 and 1 (got {confidence!r})")
+    if isinstance(resample, str):
+        resample = (resample,)
+    sides = tuple(resample)
+    if not sides or any(s not in ("train", "test") for s in sides) or len(set(sides)) != len(sides):
+        raise ValueError(f"resample must name 'train', 'test' or both (got {resample!r})")
+    out = [None, None]
+    if weights is not None:
+        if len(weights) != 2:
+            raise ValueError("weights must be a pair (w_train, w_test); either may be None")
+        for k, (w, rows, name) in enumerate(zip(weights, (n, m), ("w_train", "w_test"))):
+            if w is None:
+                continue
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (n_boot, rows):
+                raise ValueError(f"{name} must have shape (n_boot, rows) = ({n_boot}, {rows}), got {w.shape}")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError(f"{name} must be finite and >= 0")
+            if np.any(w.sum(axis=1) <= 0):
+                raise ValueError(f"{name}: the weights of replicate {int(np.argmax(w.sum(axis=1) <= 0))} sum to zero")
+            out[k] = w
+    return out[0], out[1], sides
+
+
+def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, confidence=0.95, weights=None,
+                     resample=("train", "test"), device=0, _engine=None):
+    """Bootstrap confidence intervals for the exact attribution (p <= 32).
+
+    ``ls_spa(method='subsets')`` is exact for the rows it was handed; this call says how far it would move had the rows
+    been another draw from the same population.  The point estimate is that call's (``attribution``, ``theta``,
+    ``r_squared``, by the same path).  Each of the ``n_boot`` replicates resamples the rows with replacement, refits and
+    re-attributes -- on the GPU, from rows that stay there: a replicate's reduced problem is a weighted Gram with the
+    bootstrap counts as weights, a block of replicates is one pass over the rows, and their enumerations share one grid
+    (include/lsspa.h, lsspa_boot_run).  The counts are a pure function of (seed, replicate, side): two calls agree bitwise.
+
+    Returns ``BootstrapResults``: ``replicates`` [n_boot][p], ``r_squared_replicates``, ``std_error``, the percentile
+    interval ``lower`` / ``upper`` at ``confidence`` (numpy's default interpolation), ``r_squared_interval``,
+    ``prob_greater`` [p][p] (the share of replicates with phi_i > phi_j: "is feature 3 really worth more than feature
+    7?") and ``n_failed``: replicates whose Gram matrix was not numerically positive definite are NaN and left out, with
+    a RuntimeWarning; more than half of them is a RuntimeError.
+
+    weights:  (w_train, w_test), each None or an (n_boot, rows) array of finite weights >= 0 with a positive sum per
+        replicate, used instead of the counts on that side: a Bayesian bootstrap (Dirichlet weights), survey weights,
+        a jackknife (zero weights).
+    resample: ('train', 'test') (default) or one of them; the side not named keeps weight 1 on every row.
+    p > 32 raises ValueError: group the columns (``ls_spa_groups``) or use a sampling method."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    n, p = data[0].shape
+    m = data[1].shape[0]
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_bootstrap re-runs the enumeration of all 2^p feature subsets and takes at most p = "
+                         f"{SUBSETS_MAX_P} features (this problem has p = {p}); group the columns (ls_spa_groups) to "
+                         "attribute to at most 32 players, or use a sampling method")
+    w_train, w_test, sides = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
+    n_boot = int(n_boot)
+    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
+    undo = []
+    with _engine_call(_engine, device, undo=undo) as engine:
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        theta, r_squared, info = _load_and_fit(engine, data, reg, False, None)
+        phi, bits = engine.subsets_shapley()
+        _info_verdict((bits | info) & 1, stacklevel=3)
+        if info & 1:
+            theta, r_squared = _singular_fit(engine, data[1], data[3])
+        engine.boot_load(*data, reg)
+        undo.append((engine.boot_free, True))
+        if not fixed:
+            rep, r2, binfo = engine.boot_run(n_boot, seed, w_train, w_test)
+        else:
+            # a side that is not resampled has weight 1 on every row: the run is cut so that those rows of ones stay small
+            rows = max((n, m)[k] for k in fixed)
+            step = max(1, min(n_boot, BOOT_ONES_BYTES // (8 * rows)))
+            parts = []
+            for r0 in range(0, n_boot, step):
+                nb = min(step, n_boot - r0)
+                w = [None if x is None else x[r0:r0 + nb] for x in (w_train, w_test)]
+                for k in fixed:
+                    w[k] = np.ones((nb, (n, m)[k]))
+                parts.append(engine.boot_run(nb, seed, w[0], w[1], first=r0))
+            rep, r2, binfo = (np.concatenate([q[k] for q in parts]) for k in range(3))
+    failed = (binfo & 1).astype(bool) | ~np.isfinite(rep).all(axis=1) | ~np.isfinite(r2)
+    res = BootstrapResults.from_replicates(phi, theta, r_squared, rep, r2, failed, confidence)
+    if res.n_failed:
+        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
+                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
+                      "`replicates` and left out of the intervals", RuntimeWarning, stacklevel=2)
+    return res
 
 
 GROUPS_AUTO_MAX_G = 20     # ls_spa_groups(method='auto'): the enumeration up to here (26 ms at g = 20, README.md)

@@ -76,6 +76,20 @@ def debug_stats_slices(n_samples: int, p: int):
     return [max(0, min(n_samples, (k + 1) * per.value) - k * per.value) for k in range(nz.value)], bool(small.value)
 
 
+BOOT_PLAN_FIELDS = ("cb", "ldz", "pairs", "rpw", "rps_train", "rps_test", "slices_train", "slices_test", "rep_bytes",
+                    "block", "n_blocks", "enum_reps", "units", "per", "steps")
+
+
+def debug_boot_plan(R: int, n: int, m: int, p: int, block: int = 0):
+    """Test hook, host only: how a bootstrap run of R replicates on n / m rows at p features is cut (include/lsspa.h,
+    lsspa_debug_boot_plan), as a dict of BOOT_PLAN_FIELDS."""
+    out = np.zeros(15, dtype=np.int64)
+    rc = N.load().lsspa_debug_boot_plan(int(R), int(n), int(m), int(p), int(block), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_boot_plan: status {rc}")
+    return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -285,6 +299,65 @@ class HipEngine:
         info = C.c_int32()
         self._check(self._lib.lsspa_subsets_interactions(self._h, N.dptr(phi), N.dptr(inter), C.byref(info)))
         return phi, inter, info.value
+
+    # ---- bootstrap of the exact attribution (p <= 32) -------------------------------------
+    def boot_load(self, X_train, X_test, y_train, y_test, reg: float):
+        """Keep [X | y] of both sides on the device for boot_run (include/lsspa.h, lsspa_boot_load); the loaded problem is
+        not touched."""
+        dt = np.float32 if (X_train.dtype == np.float32 and X_test.dtype == np.float32) else np.float64
+        Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
+        ya, ye = np.ascontiguousarray(y_train, dtype=dt), np.ascontiguousarray(y_test, dtype=dt)
+        n, p = Xa.shape
+        self._check(self._lib.lsspa_boot_load(
+            self._h, Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p,
+            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._boot_dims = (p, n, Xe.shape[0])
+
+    def boot_free(self):
+        self.boot_timing_last = self.boot_timing()      # the data go, the last run's timing stays readable
+        self._check(self._lib.lsspa_boot_free(self._h))
+        self._boot_dims = None
+
+    def _boot_weights(self, w, R, side):
+        if w is None:
+            return None
+        dims = getattr(self, "_boot_dims", None)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if dims is not None and w.shape != (R, dims[1 + side]):
+            raise ValueError(f"weights of the {('training', 'test')[side]} side must have shape ({R}, {dims[1 + side]}), "
+                             f"got {w.shape}")
+        return w
+
+    def boot_run(self, R: int, seed: int, w_train=None, w_test=None, block: int = 0, first: int = 0):
+        """(phi [R][p], r2 [R], info [R]) of replicates first .. first + R - 1 (include/lsspa.h, lsspa_boot_run)."""
+        dims = getattr(self, "_boot_dims", None)
+        p = dims[0] if dims else 1
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        phi, r2, info = np.empty((R, p)), np.empty(R), np.zeros(R, dtype=np.int32)
+        self._check(self._lib.lsspa_boot_run(self._h, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa),
+                                             N.dptr(we), int(block), N.dptr(phi), N.dptr(r2), N.iptr(info)))
+        return phi, r2, info
+
+    def boot_timing(self):
+        """Kernel seconds of the last boot_run: counts (or the upload of weights), Gram, enumeration."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.lsspa_boot_timing(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"counts": a.value / 1e3, "gram": b.value / 1e3, "enumeration": c.value / 1e3}
+
+    def boot_debug_counts(self, seed: int, r: int, side: int):
+        out = np.empty(self._boot_dims[1 + side], dtype=np.uint32)
+        self._check(self._lib.lsspa_boot_debug_counts(self._h, int(seed) & (2 ** 64 - 1), int(r), int(side),
+                                                      out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def boot_debug_grams(self, R: int, w_train=None, w_test=None):
+        """(S_train, S_test [R][p+1][p+1], wsum [R]): the weighted sums before finalise (None: weight 1 on that side)."""
+        c = self._boot_dims[0] + 1
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        Sa, Se, ws = np.empty((R, c, c)), np.empty((R, c, c)), np.empty(R)
+        self._check(self._lib.lsspa_boot_debug_grams(self._h, int(R), N.dptr(wa), N.dptr(we), N.dptr(Sa), N.dptr(Se),
+                                                     N.dptr(ws)))
+        return Sa, Se, ws
 
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()

@@ -125,6 +125,13 @@ SIGNATURES = {
     "lsspa_pairs_reset": (C.c_int, [_vp]),
     "lsspa_debug_expand_pairs": (C.c_int, [_i32, _pi32, _i32, _pi32]),
     "lsspa_debug_pairs_inject": (C.c_int, [_vp, _pd, _pi32, _i32]),
+    "lsspa_boot_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _dbl, _i32, _i32]),
+    "lsspa_boot_run": (C.c_int, [_vp, _i64, C.c_uint64, _i64, _pd, _pd, _i64, _pd, _pd, _pi32]),
+    "lsspa_boot_free": (C.c_int, [_vp]),
+    "lsspa_boot_timing": (C.c_int, [_vp, _pd, _pd, _pd]),
+    "lsspa_boot_debug_counts": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _i32, C.POINTER(C.c_uint32)]),
+    "lsspa_boot_debug_grams": (C.c_int, [_vp, _i64, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_debug_boot_plan": (C.c_int, [_i64, _i64, _i64, _i32, _i64, _pi64]),
 }
 
 

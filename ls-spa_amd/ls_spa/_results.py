@@ -132,3 +132,66 @@ def validate_data(X_train, X_test, y_train, y_test):
     for broken, message in _CHECKS:
         if broken(X_train, X_test, y_train, y_test):
             raise SizeIncompatible(message)
+
+
+@dataclass
+class BootstrapResults:
+    """What ``ls_spa_bootstrap`` returns.  ``attribution``, ``theta`` and ``r_squared`` are the point estimate on the
+    original rows, exactly those of ``ls_spa(method='subsets')``.  ``replicates`` [n_boot][p] and
+    ``r_squared_replicates`` [n_boot] are the bootstrap replicates; a replicate whose Gram matrix was not numerically
+    positive definite is NaN in both and counted in ``n_failed``.  Over the valid replicates: ``std_error`` [p] (sample
+    standard deviation), ``lower`` / ``upper`` [p] and ``r_squared_interval`` (percentile interval: ``np.quantile`` at alpha =
+    (1 - ``confidence``) / 2 and 1 - alpha, numpy's default interpolation) and ``prob_greater`` [p][p], the share of replicates with phi_i > phi_j."""
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+    replicates: np.ndarray
+    r_squared_replicates: np.ndarray
+    std_error: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    r_squared_interval: tuple
+    n_failed: int
+    prob_greater: np.ndarray
+    confidence: float = 0.95
+
+    @classmethod
+    def from_replicates(cls, attribution, theta, r_squared, replicates, r_squared_replicates, failed, confidence=0.95):
+        """The summary fields from the replicates; failed [n_boot]: which replicates to mask.  RuntimeError when more
+        than half of them failed."""
+        rep = np.array(replicates, dtype=np.float64)
+        r2 = np.array(r_squared_replicates, dtype=np.float64)
+        failed = np.asarray(failed, dtype=bool)
+        rep[failed] = np.nan
+        r2[failed] = np.nan
+        n_failed = int(failed.sum())
+        if 2 * n_failed > len(rep):
+            raise RuntimeError(f"{n_failed} of {len(rep)} bootstrap replicates had a Gram matrix that was not numerically "
+                               "positive definite: no interval can be read from the rest")
+        ok = rep[~failed]
+        alpha = (1.0 - float(confidence)) / 2.0      # the interval is [quantile(alpha), quantile(1 - alpha)]
+        lower, upper = np.quantile(ok, alpha, axis=0), np.quantile(ok, 1.0 - alpha, axis=0)
+        r2_ok = r2[~failed]
+        return cls(attribution=np.asarray(attribution), theta=np.asarray(theta), r_squared=float(r_squared),
+                   replicates=rep, r_squared_replicates=r2,
+                   std_error=ok.std(axis=0, ddof=1) if len(ok) > 1 else np.full(rep.shape[1], np.nan),
+                   lower=lower, upper=upper,
+                   r_squared_interval=(float(np.quantile(r2_ok, alpha)), float(np.quantile(r2_ok, 1.0 - alpha))),
+                   n_failed=n_failed, prob_greater=(ok[:, :, None] > ok[:, None, :]).mean(axis=0),
+                   confidence=float(confidence))
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}p = {np.asarray(self.attribution).size}, {len(self.replicates)} bootstrap replicates"
+            + (f" ({self.n_failed} failed)" if self.n_failed else ""),
+            f"{pad}Out-of-sample R^2 with all features: {self.r_squared:.2f}"
+            f" [{self.r_squared_interval[0]:.2f}, {self.r_squared_interval[1]:.2f}]",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}{100 * self.confidence:g} % interval, lower: {_head(self.lower)}",
+            f"{pad}{100 * self.confidence:g} % interval, upper: {_head(self.upper)}",
+            pad,
+        ]
+        return "\n".join(lines)
