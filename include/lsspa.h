@@ -205,6 +205,37 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
                            double* S_train /* [R][c][c] */, double* S_test, double* wsum /* [R] */);
 int lsspa_debug_boot_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15);
 
+/* The bootstrap over groups of columns (g <= 32 groups, p <= 64 columns, label -1 = an always-included baseline): the
+ * replicates of lsspa_boot_run -- the same rows, counts, weights and weighted Grams -- attributed by
+ * lsspa_groups_shapley's enumeration of the 2^g group subsets, all replicates of a block in one grid.
+ *   lsspa_boot_groups_load : lsspa_boot_load for p <= 64 (p > 64 is LSSPA_ERR_ARG naming the limit).  The same device
+ *                     store: one set of bootstrap rows per context, freed by lsspa_boot_free.  After a load with p > 32
+ *                     lsspa_boot_run is LSSPA_ERR_ARG; lsspa_boot_debug_grams, lsspa_boot_debug_counts and
+ *                     lsspa_boot_timing work as before.
+ *   lsspa_boot_groups_run  : after either load.  labels [p] as lsspa_groups_shapley's (bad labels: LSSPA_ERR_ARG).  R,
+ *                     seed, first, w_train, w_test, block: lsspa_boot_run's -- draw (seed, r, side, t) is the same
+ *                     function, so a seed resamples the same rows with and without groups.  phi [R][g] in label order;
+ *                     r2 [R] the R^2 of the replicate's full model and r2_base [R] that of its baseline columns alone (0
+ *                     without a baseline), both by Cholesky solves on the host (NaN where one fails): the phi of a
+ *                     replicate sum to r2 - r2_base.  info [R] as lsspa_boot_run's.  Results do not depend on block or on
+ *                     `first`, and two runs agree bitwise: a unit's high subsets are cut into launches by the layout
+ *                     alone, as lsspa_groups_shapley cuts them, never by R, block or the replicates a launch takes.  A
+ *                     replicate's phi has the bits lsspa_groups_shapley returns for its reduced problem.
+ *   lsspa_debug_boot_groups_plan : host only (no context, no GPU) -- lsspa_debug_boot_plan's fifteen numbers for a run
+ *                     over the groups of labels [p]: cb up to 5 (p + 1 = 65 columns), one replicate a wave from cb = 4,
+ *                     units / per / steps over the 2^gh high group subsets as the one-problem enumeration cuts them
+ *                     (a function of the labels alone), replicates per launch within that call's work bound and
+ *                     units * replicates <= 2^20.  Bad labels or sizes: LSSPA_ERR_ARG. */
+int lsspa_boot_groups_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                           const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                           int32_t dtype, int32_t location);
+int lsspa_boot_groups_run(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, int64_t R, uint64_t seed,
+                          int64_t first, const double* w_train /* [R][N] or NULL */,
+                          const double* w_test /* [R][M] or NULL */, int64_t block, double* phi /* [R][g] */,
+                          double* r2 /* [R] */, double* r2_base /* [R] */, int32_t* info /* [R] */);
+int lsspa_debug_boot_groups_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p, int32_t g,
+                                 int64_t block, int64_t* plan15);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

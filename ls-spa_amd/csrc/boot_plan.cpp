@@ -7,17 +7,15 @@
 
 namespace lsspa {
 
-const char* boot_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P) {
-  P = BootPlan{};
-  if (p < 1 || p > BOOT_MAX_P) return "p must be 1 .. 32";
-  if (R < 1) return "R must be at least 1";
-  if (N < 1 || M < 1 || N >= (1ll << 31) || M >= (1ll << 31)) return "N and M must be 1 .. 2^31 - 1";
-  if (block < 0) return "block must be >= 0";
-  const int c = p + 1;
+namespace {
+
+// what the rows and the columns decide: the column blocks of Z, replicates per wave and the row slices of both sides
+void plan_gram(int64_t N, int64_t M, int c, BootPlan& P) {
   P.cb = (c + 15) / 16;
   P.ldz = 16 * P.cb;
   P.pairs = P.cb * (P.cb + 1) / 2;
-  P.rpw = P.cb <= 2 ? 4 : 2;          // accumulators a wave holds: rpw * pairs * 4 doubles a lane (<= 96 registers)
+  // accumulators a wave holds: rpw * pairs * 4 doubles a lane (<= 96 registers up to cb = 3; 80 and 120 at cb = 4, 5)
+  P.rpw = P.cb <= 2 ? 4 : P.cb == 3 ? 2 : 1;
   const int64_t rows[2] = {N, M};
   for (int s = 0; s < 2; ++s) {
     // a slice: at least BOOT_MIN_SLICE_ROWS rows, at most BOOT_MAX_SLICES of them -- a function of the rows alone, so
@@ -27,20 +25,69 @@ const char* boot_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, Boo
     P.rps[s] = rps;
     P.slices[s] = (int)((rows[s] + rps - 1) / rps);
   }
+}
+
+// per replicate: weights of both sides (8 bytes a row: fp64 weights; counts take half), the Gram partials of both
+// sides, the enumeration's partial table [units][players + 1], and the small per-replicate matrices (S, G, H, ...
+// < 8 c^2 doubles); then the replicates of a block and the blocks
+void plan_blocks(int64_t R, int64_t N, int64_t M, int c, int players, int64_t block, BootPlan& P) {
+  P.rep_bytes = 8 * (N + M) + (int64_t)(P.slices[0] + P.slices[1]) * P.pairs * 256 * 8 +
+                (int64_t)P.units * (players + 1) * 8 + 8ll * c * c * 8;
+  int64_t most = std::max<int64_t>(1, std::min<int64_t>(BOOT_MAX_BLOCK, BOOT_BLOCK_BYTES / P.rep_bytes));
+  P.block = std::min<int64_t>(R, block > 0 ? std::min(block, most) : most);
+  P.n_blocks = (R + P.block - 1) / P.block;
+}
+
+const char* plan_sizes(int64_t R, int64_t N, int64_t M, int64_t block) {
+  if (R < 1) return "R must be at least 1";
+  if (N < 1 || M < 1 || N >= (1ll << 31) || M >= (1ll << 31)) return "N and M must be 1 .. 2^31 - 1";
+  if (block < 0) return "block must be >= 0";
+  return nullptr;
+}
+
+}  // namespace
+
+const char* boot_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P) {
+  P = BootPlan{};
+  if (p < 1 || p > BOOT_MAX_P) return "p must be 1 .. 32";
+  if (const char* why = plan_sizes(R, N, M, block)) return why;
+  const int c = p + 1;
+  plan_gram(N, M, c, P);
   const int q = p < BOOT_LOW ? p : BOOT_LOW;
   const uint64_t n_high = 1ull << (p - q);
   P.units = std::min<uint64_t>(n_high, BOOT_UNITS);
   P.per = n_high / P.units;
-  // per replicate: weights of both sides (8 bytes a row: fp64 weights; counts take half), the Gram partials of both
-  // sides, the enumeration's partial table, and the small per-replicate matrices (S, G, H, ... < 8 c^2 doubles)
-  P.rep_bytes = 8 * (N + M) + (int64_t)(P.slices[0] + P.slices[1]) * P.pairs * 256 * 8 +
-                (int64_t)P.units * c * 8 + 8ll * c * c * 8;
-  int64_t most = std::max<int64_t>(1, std::min<int64_t>(BOOT_MAX_BLOCK, BOOT_BLOCK_BYTES / P.rep_bytes));
-  P.block = std::min<int64_t>(R, block > 0 ? std::min(block, most) : most);
-  P.n_blocks = (R + P.block - 1) / P.block;
+  plan_blocks(R, N, M, c, p, block, P);
   P.enum_reps = std::max<int64_t>(1, std::min<int64_t>(P.block, (int64_t)(BOOT_SUBSETS_PER_LAUNCH / P.units)));
   P.steps = std::max<uint64_t>(1, BOOT_SUBSETS_PER_LAUNCH / (P.units * (uint64_t)P.enum_reps));
   P.steps = std::min<uint64_t>(P.steps, P.per);
+  return nullptr;
+}
+
+const char* boot_groups_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
+                             BootPlan& P) {
+  P = BootPlan{};
+  if (p < 1 || p > BOOT_GROUPS_MAX_P) return "p must be 1 .. 64";
+  if (g < 1 || g > BOOT_GROUPS_MAX_G) return "g must be 1 .. 32";
+  if (gh < 0 || gh > g || g - gh > BOOT_LOW || nb < 0 || ql < g - gh || ql > BOOT_LOW || nb + ql + gh > p || g > p)
+    return "gh, nb, ql are not those of a layout of g groups over p columns";
+  if (const char* why = plan_sizes(R, N, M, block)) return why;
+  const int c = p + 1;
+  plan_gram(N, M, c, P);
+  const uint64_t n_high = 1ull << gh;
+  P.units = std::min<uint64_t>(n_high, BOOT_UNITS);
+  P.per = n_high / P.units;
+  plan_blocks(R, N, M, c, g, block, P);
+  // a launch: the work bound of the one-problem grouped enumeration (a high subset counts as the square of its matrix's
+  // rows: baseline and low columns always, the high columns half of the time), and at most 2^20 workgroups.  A unit's
+  // row of the partial table is the sum of its launches' sums, so how `per` is cut into launches shows in the bits:
+  // `steps` is a function of the layout alone -- the one-problem call's own cut -- and never of R, the block or the
+  // replicates a launch takes; those fill what a launch of `steps` steps leaves of the bound.
+  const uint64_t rows = (uint64_t)(nb + ql + 1) + (uint64_t)(p - nb - ql + 1) / 2;
+  const uint64_t per_launch = std::max<uint64_t>(1, BOOT_GROUPS_WORK_PER_LAUNCH / (rows * rows));
+  P.steps = std::min<uint64_t>(P.per, std::max<uint64_t>(1, per_launch / P.units));
+  const uint64_t groups = std::min<uint64_t>(BOOT_SUBSETS_PER_LAUNCH, per_launch) / (P.units * P.steps);
+  P.enum_reps = std::max<int64_t>(1, std::min<int64_t>(P.block, (int64_t)groups));
   return nullptr;
 }
 

@@ -23,5 +23,15 @@ constexpr uint64_t BOOT_UNITS = 8192, BOOT_SUBSETS_PER_LAUNCH = 1ull << 20;   //
 // BOOT_BLOCK_BYTES holds (at most BOOT_MAX_BLOCK); a larger request is cut to that.
 const char* boot_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P);
 constexpr int BOOT_MAX_P = 32, BOOT_LOW = 6;   // SUBSETS_MAX_P and the enumeration's low features (k_subsets.hip)
+// The bootstrap over groups of columns (lsspa_boot_groups_run): g groups over p <= 64 columns, of which gh are high, nb
+// columns the baseline and ql the low groups' (GroupLayout, kernels.h).  c = p + 1 <= 65 columns of Z: cb up to 5; the
+// slices are boot_plan's for the same rows; units, per, steps cut the 2^gh high subsets as the one-problem grouped
+// enumeration cuts them (BOOT_GROUPS_WORK_PER_LAUNCH / rows^2 subsets a launch): a function of the layout alone, since
+// the cut of `per` into launches shows in the bits.  enum_reps replicates share a launch, within that work bound and
+// 2^20 workgroups; the enumeration's partial table is g + 1 wide.
+const char* boot_groups_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
+                             BootPlan& P);
+constexpr int BOOT_GROUPS_MAX_P = 64, BOOT_GROUPS_MAX_G = 32;   // GROUPS_MAX_P, GROUPS_MAX_G (k_groups.hip)
+constexpr uint64_t BOOT_GROUPS_WORK_PER_LAUNCH = 1ull << 26;    // that of lsspa_groups_shapley's host path
 
 }  // namespace lsspa

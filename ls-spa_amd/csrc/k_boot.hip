@@ -15,7 +15,8 @@
 // B likewise B[k = l >> 4][j = l & 15]; D four a lane, register v of lane l is D[(l >> 4) + 4 v][l & 15] (tiles.h).  A wave
 // takes four rows a step: lane l loads z[row + (l >> 4)][16 b + (l & 15)] for the cb 16-column blocks b of Z -- as it
 // stands the B operand of block b -- and the row's weight of each of its RPW replicates; the A operand w z is formed in
-// registers.  Block pairs bi <= bj only (S is symmetric): RPW * cb (cb + 1) / 2 accumulators of four doubles.  A workgroup
+// registers.  Block pairs bi <= bj only (S is symmetric): RPW * cb (cb + 1) / 2 accumulators of four doubles (RPW = 4, 4,
+// 2, 1, 1 at cb = 1 .. 5; cb = 4, 5 are the bootstrap over groups of columns, p <= 64).  A workgroup
 // is four waves with four different sets of replicates on the SAME rows, so a row of Z comes from memory once per
 // workgroup and from the first-level cache for the other three waves; the workgroups of one row slice that belong to the
 // other replicates of the block find it in L2 (a slice is at most a few hundred KB).  Rows beyond the slice get weight 0
@@ -209,6 +210,10 @@ hipError_t launch_boot_gram(const BootPlan& P, int side, const double* Z, int64_
     gram_launch<2, 4>(P, side, Z, n, cnt, wt, reps, part, st);
   else if (P.cb == 3 && P.rpw == 2)
     gram_launch<3, 2>(P, side, Z, n, cnt, wt, reps, part, st);
+  else if (P.cb == 4 && P.rpw == 1)            // the bootstrap over groups: p + 1 = 49 .. 64 columns
+    gram_launch<4, 1>(P, side, Z, n, cnt, wt, reps, part, st);
+  else if (P.cb == 5 && P.rpw == 1)            // p = 64
+    gram_launch<5, 1>(P, side, Z, n, cnt, wt, reps, part, st);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -222,7 +227,7 @@ hipError_t launch_boot_wsum(const uint32_t* cnt, const double* wt, int64_t n, in
 
 hipError_t launch_boot_reduce(const BootPlan& P, int side, const double* part, int p, int reps, double* S,
                               hipStream_t st) {
-  if (!part || !S || p < 1 || p > SUBSETS_MAX_P || reps < 1 || side < 0 || side > 1 || P.cb != (p + 16) / 16 ||
+  if (!part || !S || p < 1 || p > GROUPS_MAX_P || reps < 1 || side < 0 || side > 1 || P.cb != (p + 16) / 16 ||
       P.slices[side] < 1)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(boot_reduce_kernel, dim3((unsigned)reps), dim3(256), 0, st, part, P.slices[side], reps, P.cb,
@@ -233,7 +238,7 @@ hipError_t launch_boot_reduce(const BootPlan& P, int side, const double* part, i
 hipError_t launch_boot_finalize(const double* S_tr, const double* S_te, const double* wsum_tr, int p, double reg,
                                 int reps, double* G, double* g, double* H, double* h, double* inv_yy,
                                 hipStream_t st) {
-  if (!S_tr || !S_te || !wsum_tr || !G || !g || !H || !h || !inv_yy || p < 1 || p > SUBSETS_MAX_P || reps < 1)
+  if (!S_tr || !S_te || !wsum_tr || !G || !g || !H || !h || !inv_yy || p < 1 || p > GROUPS_MAX_P || reps < 1)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(boot_finalize_kernel, dim3((unsigned)reps), dim3(256), 0, st, S_tr, S_te, wsum_tr, p, reg, G, g,
                      H, h, inv_yy);
@@ -242,7 +247,7 @@ hipError_t launch_boot_finalize(const double* S_tr, const double* S_te, const do
 
 hipError_t launch_boot_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Z,
                             int ldz, int64_t row0, hipStream_t st) {
-  if (!X || !y || !Z || rows < 1 || p < 1 || p > SUBSETS_MAX_P || ld < p || ldz < p + 1 || row0 < 0)
+  if (!X || !y || !Z || rows < 1 || p < 1 || p > GROUPS_MAX_P || ld < p || ldz < p + 1 || row0 < 0)
     return hipErrorInvalidValue;
   const int64_t blocks = (rows * ldz + 255) / 256;
   if (blocks > (1ll << 31) - 1) return hipErrorInvalidValue;

@@ -99,11 +99,22 @@ __device__ inline void wave_sum_low(double (&x)[GQ]) {
   }
 }
 
+// Replicates (the bootstrap, k_boot.hip): replicate r = blockIdx.y of a launch has its problem r strides behind the
+// launch's, at the dense strides of k_subsets.hip -- G, H: p ld, g, h: p, one 1 / ||y||^2 (GroupArgs::inv_yy_rep) and one
+// info word each, part: the table of the replicates before it.  The layout table, the weights and the labels are the
+// launch's.  That is the REPS instantiation of the phi-only kernel; without REPS the replicate is 0 at compile time and
+// the code is what it was before replicates existed (explicit stride arguments cost k_subsets.hip its occupancy).
+template <bool REPS>
+__device__ inline int64_t rep_offset(int64_t stride) { return REPS ? (int64_t)blockIdx.y * stride : 0; }
+
 // u(Hs + T) of this thread's low subset T = tid (0 for threads >= 2^gl).  Enters and leaves with the workgroup in
 // step: every shared array it writes is free when it is called and is read by nobody after it returns.
+template <bool REPS>
 __device__ double group_values(GrpShared& sh, const GroupArgs& a, uint64_t hi, int tid, bool& bad) {
   const int p = a.p, ql = a.ql, nb = a.nb, gh = a.gh;
   const int wv = tid >> 6, lane = tid & 63;
+  const double* Gr = a.G + rep_offset<REPS>((int64_t)p * a.ldg);
+  const double* gr = a.g + rep_offset<REPS>(p);
   // pivots of this subset: the baseline, then the columns of the high groups of hi in layout order
   const int myg = (tid < p) ? sh.colgrp[tid] : -1;
   int nhs = nb, off = 0;
@@ -124,7 +135,7 @@ __device__ double group_values(GrpShared& sh, const GroupArgs& a, uint64_t hi, i
   for (int i = wv; i < nk; i += 4) {
     const int ci = sh.idx[i];
     for (int j = lane; j <= nk; j += 64)
-      sh.M[i * LDM + j] = (j < nk) ? a.G[(int64_t)ci * a.ldg + sh.idx[j]] : a.g[ci];
+      sh.M[i * LDM + j] = (j < nk) ? Gr[(int64_t)ci * a.ldg + sh.idx[j]] : gr[ci];
   }
   __syncthreads();
   // Gauss-Jordan on the pivots 0 .. nhs-1, columns right of the pivot only.  Column j belongs to wave (j - k - 1) % 4
@@ -159,7 +170,7 @@ __device__ double group_values(GrpShared& sh, const GroupArgs& a, uint64_t hi, i
   // Y = H X: lane = row i, wave wv takes columns wv and wv + 4; H_ib is read as H_bi, a contiguous run of row b
   if (lane < nk && wv < nc) {
     const bool two = wv + 4 < nc;
-    const double* Hc = a.H + sh.idx[lane];
+    const double* Hc = a.H + rep_offset<REPS>((int64_t)p * a.ldh) + sh.idx[lane];
     double s0 = 0.0, s1 = 0.0;
     for (int b = 0; b < nk; ++b) {
       const double hv = Hc[(int64_t)sh.idx[b] * a.ldh];
@@ -238,16 +249,20 @@ __device__ double group_values(GrpShared& sh, const GroupArgs& a, uint64_t hi, i
         f += y[t] * u;
       }
     }
-    v = f * a.inv_yy;
+    if constexpr (REPS)
+      v = f * a.inv_yy_rep[blockIdx.y];
+    else
+      v = f * a.inv_yy;
   }
   return v;
 }
 
+template <bool REPS>
 __device__ void load_shared(GrpShared& sh, const GroupArgs& a, int tid) {
   const int p = a.p;
   if (tid < p) {
-    sh.h[tid] = a.h[tid];
-    sh.gdiag[tid] = a.G[(int64_t)tid * a.ldg + tid];
+    sh.h[tid] = a.h[rep_offset<REPS>(p) + tid];
+    sh.gdiag[tid] = a.G[rep_offset<REPS>((int64_t)p * a.ldg) + (int64_t)tid * a.ldg + tid];
     sh.cols[tid] = a.tab[GROUPS_TAB_COLS + tid];
     sh.colgrp[tid] = a.tab[GROUPS_TAB_COLGRP + tid];
     sh.colin[tid] = a.tab[GROUPS_TAB_COLIN + tid];
@@ -266,14 +281,15 @@ __device__ void load_shared(GrpShared& sh, const GroupArgs& a, int tid) {
 __device__ inline int pair_col(int g, int i, int j) { return i * (2 * g - i - 1) / 2 + (j - i - 1); }
 
 // INTER: the interaction sums T0, T1, T2 beside phi's (lsspa_groups_interactions); a row of part is then
-// subsets_inter_cols(g) wide.  Everything of the phi-only instantiation is in both, unchanged.
-template <bool INTER>
+// subsets_inter_cols(g) wide.  Everything of the phi-only instantiation is in both, unchanged.  REPS (phi only): the
+// launch's second grid dimension is the replicate (rep_offset above).
+template <bool INTER, bool REPS = false>
 __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s0, uint64_t s1) {
   __shared__ GrpShared sh;
   __shared__ GrpInterShared si;                // INTER only: never referenced, hence not allocated, otherwise
   const int tid = threadIdx.x;
   const int ng = a.ng, gl = a.gl, gh = a.gh;
-  load_shared(sh, a, tid);
+  load_shared<REPS>(sh, a, tid);
   double acc[GG];
 #pragma unroll
   for (int j = 0; j < GG; ++j) acc[j] = 0.0;
@@ -307,7 +323,7 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
   const int kt = __popc(tid);
   for (uint64_t s = s0; s < s1; ++s) {
     const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
-    const double v = group_values(sh, a, hi, tid, bad);
+    const double v = group_values<REPS>(sh, a, hi, tid, bad);
     if (live) {
       const int k = __popcll(hi) + kt;
       const double c = (sh.wa[k] + sh.wb[k]) * v;
@@ -355,7 +371,7 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
   }
   const int cols = INTER ? ng + 2 + ng + ng * (ng - 1) / 2 : ng + 1;
   if (tid < 64) {     // the live lanes all sit in the first wave
-    double* part = a.part + (int64_t)blockIdx.x * cols;
+    double* part = a.part + (rep_offset<REPS>(gridDim.x) + (int64_t)blockIdx.x) * cols;
 #pragma unroll
     for (int t = 0; t < GQ; ++t) {
       if (t < gl) {
@@ -423,7 +439,7 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
       }
     }
   }
-  if (__any(bad) && (tid & 63) == 0) atomicOr(a.info, 1);
+  if (__any(bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<REPS>(1), 1);
 }
 
 // masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
@@ -431,12 +447,12 @@ __global__ __launch_bounds__(NT) void groups_debug_kernel(GroupArgs a, const uin
                                                           double* __restrict__ vals) {
   __shared__ GrpShared sh;
   const int tid = threadIdx.x;
-  load_shared(sh, a, tid);
+  load_shared<false>(sh, a, tid);
   bool bad = false;
   const uint64_t low = (1ull << a.gl) - 1ull;
   for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
     const uint64_t m = masks[i];
-    const double v = group_values(sh, a, m >> a.gl, tid, bad);
+    const double v = group_values<false>(sh, a, m >> a.gl, tid, bad);
     if ((uint64_t)tid == (m & low)) vals[i] = v;
     __syncthreads();
   }
@@ -510,13 +526,20 @@ const char* groups_layout(const int32_t* labels, int p, int g, GroupLayout& L) {
 }
 
 hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
-                              hipStream_t st) {
+                              hipStream_t st, int reps) {
   if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // replicates: phi only, with inv_yy_rep, at most 2^20 workgroups a launch (the caller vouches for `reps` problems,
+  // tables, info words behind the first); one problem: no inv_yy_rep
+  if (reps < 1 || reps > 65535 || (a.inv_yy_rep ? inter || units * (uint64_t)reps > (1ull << 20) : reps != 1))
+    return hipErrorInvalidValue;
   // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^gh
   if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
   if (inter) {
     if (a.gh > GHI) return hipErrorInvalidValue;   // the kernel's pair masks (no layout of <= 64 columns has more)
     hipLaunchKernelGGL(groups_enum_kernel<true>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+  } else if (a.inv_yy_rep) {
+    hipLaunchKernelGGL((groups_enum_kernel<false, true>), dim3((unsigned)units, (unsigned)reps), dim3(NT), 0, st, a, s0,
+                       s1);
   } else {
     hipLaunchKernelGGL(groups_enum_kernel<false>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
   }

@@ -379,13 +379,20 @@ struct GroupArgs {
   uint64_t per;            // high subsets per unit
   double* part;            // [units][g + 1], inter: [units][subsets_inter_cols(g)]
   int32_t* info;           // bit 1: a pivot failed
+  // Replicates (the bootstrap, k_boot.hip): with inv_yy_rep set a launch runs `reps` replicates as its second grid
+  // dimension; replicate r has its problem at the dense replicate stride behind the launch's: G + r p ldg, g + r p,
+  // H + r p ldh, h + r p, inv_yy_rep[r] (device; inv_yy is not read), info[r], part + r units (g + 1).  w and tab are
+  // shared.  NULL (every other launch): one problem, nothing moves.
+  const double* inv_yy_rep;
 };
+// reps: with GroupArgs::inv_yy_rep only (phi only, units * reps <= 2^20)
 hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
-                              hipStream_t st);
+                              hipStream_t st, int reps = 1);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 
-// Bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp), p <= SUBSETS_MAX_P, fp64.  Z = [X | y] of one side
+// Bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp), p <= SUBSETS_MAX_P -- over groups of columns
+// p <= GROUPS_MAX_P (cb = 4, 5) --, fp64.  Z = [X | y] of one side
 // lives on the device as [n][ldz], ldz = 16 cb, cb = ceil((p + 1) / 16), columns beyond p zero.  A BLOCK of replicates
 // is reduced at a time: counts or weights [block][n], one weighted Gram pass per side into per-slice partial sums, a
 // fixed-order sum over the slices, finalise, and one enumeration grid for all its replicates.

@@ -73,6 +73,7 @@ struct BootWork {
   DevBuf<double> G, g, H, h, inv_yy;       // the block's reduced problems
   DevBuf<double> w, epart, eout;           // Shapley weights, the enumeration's partial table and its column sums
   DevBuf<int32_t> info;                    // [block]
+  DevBuf<int32_t> tab;                     // GroupLayout::tab (lsspa_boot_groups_run)
   double ms[3] = {0.0, 0.0, 0.0};          // kernel ms of the last run: counts, Gram (to the reduced problems), enumeration
   DevBuf<double>& Z(int s) { return s ? Z1 : Z0; }
   DevBuf<uint32_t>& cnt(int s) { return s ? cnt1 : cnt0; }
@@ -83,7 +84,7 @@ struct BootWork {
     dev_free(Z0); dev_free(Z1); dev_free(stage_x); dev_free(stage_y); dev_free(cnt0); dev_free(cnt1);
     dev_free(wt0); dev_free(wt1); dev_free(part0); dev_free(part1); dev_free(S0); dev_free(S1); dev_free(wsum);
     dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(epart);
-    dev_free(eout); dev_free(info);
+    dev_free(eout); dev_free(info); dev_free(tab);
     loaded = false;
   }
 };
@@ -3499,6 +3500,9 @@ namespace {
 
 static_assert(EXACT_UNITS == BOOT_UNITS && SUBSETS_PER_LAUNCH == BOOT_SUBSETS_PER_LAUNCH && SUBSETS_MAX_P == BOOT_MAX_P,
               "boot_plan cuts the enumeration as exact_enumerate does");
+static_assert(GROUPS_MAX_P == BOOT_GROUPS_MAX_P && GROUPS_MAX_G == BOOT_GROUPS_MAX_G && GROUPS_LOW_COLS == BOOT_LOW &&
+                  GROUPS_WORK_PER_LAUNCH == BOOT_GROUPS_WORK_PER_LAUNCH,
+              "boot_groups_plan cuts the enumeration as groups_enumerate does");
 
 int boot_need_loaded(lsspa_ctx* ctx) {
   if (!ctx->boot.loaded) return ctx->fail(LSSPA_ERR_STATE, "no bootstrap data loaded (lsspa_boot_load comes first)");
@@ -3528,9 +3532,18 @@ int boot_check_weights(lsspa_ctx* ctx, const double* w, int64_t R, int64_t n, co
   return LSSPA_OK;
 }
 
-int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, bool counts[2], bool enumerate) {
+// The plan of a run on the loaded rows without a layout of groups (the Gram side: lsspa_boot_debug_grams).  Up to p = 32
+// that is boot_plan; beyond, the grouped planner with the columns as one group, whose Gram side is that of every layout.
+const char* boot_rows_plan(const BootWork& B, int64_t R, int64_t block, BootPlan& P) {
+  if (B.p <= BOOT_MAX_P) return boot_plan(R, B.n[0], B.n[1], B.p, block, P);
+  return boot_groups_plan(R, B.n[0], B.n[1], B.p, 1, 1, 0, 0, block, P);
+}
+
+// ecols: the width of the enumeration's partial table (players + 1)
+int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, bool counts[2], bool enumerate, int ecols = 0) {
   BootWork& B = ctx->boot;
   const size_t blk = (size_t)P.block, c = (size_t)B.p + 1, p = (size_t)B.p;
+  const size_t ec = ecols ? (size_t)ecols : c;
   for (int s = 0; s < 2; ++s) {
     if (counts[s])
       TRY(dev_alloc(ctx, B.cnt(s), blk * (size_t)B.n[s]));
@@ -3547,8 +3560,8 @@ int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, bool counts[2], bool enu
   TRY(dev_alloc(ctx, B.h, blk * p));
   TRY(dev_alloc(ctx, B.inv_yy, blk));
   TRY(dev_alloc(ctx, B.info, blk));
-  TRY(dev_alloc(ctx, B.epart, (size_t)P.enum_reps * P.units * c));
-  TRY(dev_alloc(ctx, B.eout, blk * c));
+  TRY(dev_alloc(ctx, B.epart, (size_t)P.enum_reps * P.units * ec));
+  TRY(dev_alloc(ctx, B.eout, blk * ec));
   TRY(dev_alloc(ctx, B.w, EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)));
   return LSSPA_OK;
 }
@@ -3621,40 +3634,57 @@ double boot_r2(int p, const double* G, const double* g, const double* H, const d
   return (2.0 * lin - quad) * inv_yy;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lsspa_debug_boot_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15) try {
-  if (!plan15) return LSSPA_ERR_ARG;
-  BootPlan P;
-  if (boot_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
-  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
-                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
-  std::copy(v, v + 15, plan15);
-  return LSSPA_OK;
-} catch (...) {
-  return LSSPA_ERR_NOMEM;
+// The same over the columns cols[0 .. k-1] of a problem of p columns (p <= GROUPS_MAX_P): R^2 of the model on those
+// columns alone; 0 for k = 0.  ws: the caller's workspace, grown here.  boot_r2 is kept beside it as it was: its
+// arrays stop at SUBSETS_MAX_P, and lsspa_boot_run's r2 keeps the bits it had (the compiler contracts the two
+// index forms into fused operations as it sees fit).
+double boot_r2_cols(int p, const int* cols, int k, const double* G, const double* g, const double* H, const double* h,
+                    double inv_yy, std::vector<double>& ws) {
+  if (k == 0) return 0.0;
+  if (ws.size() < (size_t)k * k + k) ws.resize((size_t)k * k + k);
+  double *L = ws.data(), *t = ws.data() + (size_t)k * k;
+  for (int j = 0; j < k; ++j) {
+    double d = G[cols[j] * p + cols[j]];
+    for (int q = 0; q < j; ++q) d -= L[j * k + q] * L[j * k + q];
+    if (!(d > 0.0)) return std::nan("");
+    const double l = std::sqrt(d);
+    L[j * k + j] = l;
+    for (int i = j + 1; i < k; ++i) {
+      double v = G[cols[i] * p + cols[j]];
+      for (int q = 0; q < j; ++q) v -= L[i * k + q] * L[j * k + q];
+      L[i * k + j] = v / l;
+    }
+  }
+  for (int i = 0; i < k; ++i) {
+    double v = g[cols[i]];
+    for (int q = 0; q < i; ++q) v -= L[i * k + q] * t[q];
+    t[i] = v / L[i * k + i];
+  }
+  for (int i = k - 1; i >= 0; --i) {
+    double v = t[i];
+    for (int q = i + 1; q < k; ++q) v -= L[q * k + i] * t[q];
+    t[i] = v / L[i * k + i];
+  }
+  double lin = 0.0, quad = 0.0;
+  for (int i = 0; i < k; ++i) {
+    lin += t[i] * h[cols[i]];
+    double v = 0.0;
+    for (int j = 0; j < k; ++j) v += H[cols[i] * p + cols[j]] * t[j];
+    quad += t[i] * v;
+  }
+  return (2.0 * lin - quad) * inv_yy;
 }
 
-int lsspa_boot_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
-                    const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
-                    int32_t dtype, int32_t location) try {
-  if (!ctx) return LSSPA_ERR_ARG;
-  char msg[200];
-  if (p > SUBSETS_MAX_P) {
-    snprintf(msg, sizeof msg, "the bootstrap of the exact attribution takes at most p = %d features (%d given)",
-             SUBSETS_MAX_P, (int)p);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  BootPlan P;
-  if (const char* why = boot_plan(1, N, M, p, 0, P)) {
-    snprintf(msg, sizeof msg, "lsspa_boot_load: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
+// lsspa_boot_load and lsspa_boot_groups_load: the rows of both sides into Z [n][ldz]; P: a plan for these rows
+int boot_load_rows(lsspa_ctx* ctx, const BootPlan& P, const char* name, const void* X_train, int64_t ld_train,
+                   const void* y_train, int64_t N, const void* X_test, int64_t ld_test, const void* y_test, int64_t M,
+                   int32_t p, double reg, int32_t dtype, int32_t location) {
   if (!X_train || !y_train || !X_test || !y_test || ld_train < p || ld_test < p || !std::isfinite(reg) ||
-      (dtype != LSSPA_F64 && dtype != LSSPA_F32) || (location != LSSPA_HOST && location != LSSPA_DEVICE))
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_load: NULL array, ld < p, reg not finite, or bad dtype / location");
+      (dtype != LSSPA_F64 && dtype != LSSPA_F32) || (location != LSSPA_HOST && location != LSSPA_DEVICE)) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: NULL array, ld < p, reg not finite, or bad dtype / location", name);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
   HIPCHK(hipSetDevice(ctx->device));
   BootWork& B = ctx->boot;
   B.loaded = false;
@@ -3694,6 +3724,62 @@ int lsspa_boot_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const
   B.reg = reg;
   B.loaded = true;
   return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_debug_boot_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15) try {
+  if (!plan15) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
+  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
+                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
+  std::copy(v, v + 15, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_boot_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                    const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                    int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  char msg[200];
+  if (p > SUBSETS_MAX_P) {
+    snprintf(msg, sizeof msg, "the bootstrap of the exact attribution takes at most p = %d features (%d given)",
+             SUBSETS_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  if (const char* why = boot_plan(1, N, M, p, 0, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_load: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return boot_load_rows(ctx, P, "lsspa_boot_load", X_train, ld_train, y_train, N, X_test, ld_test, y_test, M, p, reg,
+                        dtype, location);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_groups_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                           const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                           int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  char msg[200];
+  if (p > GROUPS_MAX_P) {
+    snprintf(msg, sizeof msg, "the bootstrap over groups of columns takes at most p = %d columns (%d given)",
+             GROUPS_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;      // the rows' layout does not depend on the groups: the columns as one group
+  if (const char* why = boot_groups_plan(1, N, M, p, 1, 1, 0, 0, 0, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_groups_load: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return boot_load_rows(ctx, P, "lsspa_boot_groups_load", X_train, ld_train, y_train, N, X_test, ld_test, y_test, M, p,
+                        reg, dtype, location);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -3714,6 +3800,12 @@ int lsspa_boot_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, cons
   TRY(boot_need_loaded(ctx));
   BootWork& B = ctx->boot;
   if (!phi || !r2 || !info || first < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_run: phi / r2 / info NULL or first < 0");
+  if (B.p > SUBSETS_MAX_P) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "lsspa_boot_run enumerates feature subsets and takes at most p = %d features (%d loaded by "
+             "lsspa_boot_groups_load: lsspa_boot_groups_run attributes to groups of them)", SUBSETS_MAX_P, B.p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
   BootPlan P;
   if (const char* why = boot_plan(R, B.n[0], B.n[1], B.p, block, P)) {
     char msg[200];
@@ -3794,6 +3886,129 @@ int lsspa_boot_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, cons
   return abi_caught(ctx);
 }
 
+int lsspa_debug_boot_groups_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels, int32_t p, int32_t g,
+                                 int64_t block, int64_t* plan15) try {
+  if (!plan15 || !labels || p < 1 || p > GROUPS_MAX_P) return LSSPA_ERR_ARG;
+  GroupLayout L;
+  if (groups_layout(labels, p, g, L)) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_groups_plan(R, N, M, p, L.ng, L.gh, L.nb, L.ql, block, P)) return LSSPA_ERR_ARG;
+  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
+                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
+  std::copy(v, v + 15, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_boot_groups_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, uint64_t seed, int64_t first,
+                          const double* w_train, const double* w_test, int64_t block, double* phi, double* r2,
+                          double* r2_base, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  BootWork& B = ctx->boot;
+  if (!labels || !phi || !r2 || !r2_base || !info || first < 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_groups_run: labels / phi / r2 / r2_base / info NULL or first < 0");
+  char msg[200];
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, "the bootstrap over groups of columns takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+             (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  GroupLayout L;
+  if (const char* why = groups_layout(labels, B.p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  if (const char* why = boot_groups_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_groups_run: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {!w_train, !w_test};
+  const int p = B.p, ng = L.ng, c = ng + 1;
+  TRY(boot_alloc_block(ctx, P, counts, true, c));
+  TRY(dev_alloc(ctx, B.tab, GROUPS_TAB_LEN));
+  hipStream_t st = ctx->stream;
+  {
+    double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
+    exact_weight_table(ng, w);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(B.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.tab.ptr, L.tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  std::vector<hipEvent_t> ev(4, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  std::vector<double> out((size_t)P.block * c), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
+      gh((size_t)P.block * p), hh((size_t)P.block * p), yh((size_t)P.block);
+  std::vector<double> r2_ws;
+  int all[GROUPS_MAX_P];       // the full model's columns; the baseline's are the layout's first nb
+  for (int j = 0; j < p; ++j) all[j] = j;
+  int base[GROUPS_MAX_P];
+  for (int j = 0; j < L.nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
+  B.ms[0] = B.ms[1] = B.ms[2] = 0.0;
+  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
+    const int nb = (int)std::min<int64_t>(P.block, R - b0);
+    HIPCHK(hipEventRecord(ev[0], st));
+    TRY(boot_block_sums(ctx, P, w_host, false, seed, (uint64_t)first, b0, nb, ev[1]));
+    HIPCHK(launch_boot_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
+                                B.inv_yy.ptr, st));
+    HIPCHK(hipEventRecord(ev[2], st));
+    HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
+    for (int e0 = 0; e0 < nb; e0 += (int)P.enum_reps) {
+      const int ne = std::min<int>((int)P.enum_reps, nb - e0);
+      GroupArgs a{};
+      a.p = p; a.ng = ng; a.nb = L.nb;
+      a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+      a.G = B.G.ptr + (size_t)e0 * p * p;
+      a.H = B.H.ptr + (size_t)e0 * p * p;
+      a.g = B.g.ptr + (size_t)e0 * p;
+      a.h = B.h.ptr + (size_t)e0 * p;
+      a.ldg = a.ldh = p;
+      a.w = B.w.ptr;
+      a.tab = B.tab.ptr;
+      a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+      a.inv_yy_rep = B.inv_yy.ptr + e0;
+      a.info = B.info.ptr + e0;
+      a.per = P.per;
+      a.part = B.epart.ptr;
+      HIPCHK(hipMemsetAsync(B.epart.ptr, 0, sizeof(double) * (size_t)ne * P.units * c, st));
+      for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps)
+        HIPCHK(launch_groups_enum(a, P.units, s0, std::min(P.per, s0 + P.steps), false, st, ne));
+      HIPCHK(launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, c, B.eout.ptr + (size_t)e0 * c, st, ne));
+    }
+    HIPCHK(hipEventRecord(ev[3], st));
+    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Gh.data(), B.G.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Hh.data(), B.H.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(gh.data(), B.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hh.data(), B.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(yh.data(), B.inv_yy.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int r = 0; r < nb; ++r) {
+      for (int k = 0; k < ng; ++k) phi[(b0 + r) * ng + L.gid[k]] = out[(size_t)r * c + k] - out[(size_t)r * c + ng];
+      const double *Gr = &Gh[(size_t)r * p * p], *gr = &gh[(size_t)r * p], *Hr = &Hh[(size_t)r * p * p],
+                   *hr = &hh[(size_t)r * p];
+      r2[b0 + r] = boot_r2_cols(p, all, p, Gr, gr, Hr, hr, yh[r], r2_ws);
+      r2_base[b0 + r] = boot_r2_cols(p, base, L.nb, Gr, gr, Hr, hr, yh[r], r2_ws);
+    }
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      B.ms[k] += ms;
+    }
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
 int lsspa_boot_timing(const lsspa_ctx* ctx, double* counts_ms, double* gram_ms, double* enum_ms) try {
   if (!ctx) return LSSPA_ERR_ARG;
   if (counts_ms) *counts_ms = ctx->boot.ms[0];
@@ -3826,7 +4041,7 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
   TRY(boot_need_loaded(ctx));
   BootWork& B = ctx->boot;
   BootPlan P;
-  if (const char* why = boot_plan(R, B.n[0], B.n[1], B.p, 0, P)) {
+  if (const char* why = boot_rows_plan(B, R, 0, P)) {
     char msg[200];
     snprintf(msg, sizeof msg, "lsspa_boot_debug_grams: %s", why);
     return ctx->fail(LSSPA_ERR_ARG, msg);

@@ -6,7 +6,7 @@ Same public names as the reference's ``from .ls_spa import *`` (ls_spa/__init__.
 ``error_estimates``; ``ls_spa_groups`` (sampled attribution over groups of columns) and ``ls_spa_interactions`` (exact
 pairwise Shapley interaction values between features, p <= 32, or between groups of columns, g <= 32) and
 ``ls_spa_interactions_sampled`` (their sampled counterpart, for any number of features or groups) and
-``ls_spa_bootstrap`` (bootstrap confidence intervals of the exact attribution, p <= 32) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
+``ls_spa_bootstrap`` (bootstrap confidence intervals of the exact attribution, p <= 32, or over g <= 32 groups of p <= 64 columns) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import (BootstrapResults, InteractionResults, SampledInteractionResults, ShapleyResults, SizeIncompatible,

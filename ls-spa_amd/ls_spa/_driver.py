@@ -22,6 +22,7 @@ README-dialect keywords (README.md:96-106) are accepted on top: ``method``,
 from __future__ import annotations
 
 import contextlib
+import functools
 import json
 import os
 import warnings
@@ -1125,8 +1126,9 @@ def _bootstrap_options(n_boot, confidence, weights, resample, n, m):
 
 
 def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, confidence=0.95, weights=None,
-                     resample=("train", "test"), device=0, _engine=None):
-    """Bootstrap confidence intervals for the exact attribution (p <= 32).
+                     resample=("train", "test"), groups=None, device=0, _engine=None):
+    """Bootstrap confidence intervals for the exact attribution (p <= 32; with ``groups=``, g <= 32 groups over p <= 64
+    columns).
 
     ``ls_spa(method='subsets')`` is exact for the rows it was handed; this call says how far it would move had the rows
     been another draw from the same population.  The point estimate is that call's (``attribution``, ``theta``,
@@ -1145,11 +1147,24 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
         replicate, used instead of the counts on that side: a Bayesian bootstrap (Dirichlet weights), survey weights,
         a jackknife (zero weights).
     resample: ('train', 'test') (default) or one of them; the side not named keeps weight 1 on every row.
-    p > 32 raises ValueError: group the columns (``ls_spa_groups``) or use a sampling method."""
+    groups:   one label per column as ``ls_spa(groups=)`` takes them (-1: a baseline that every model includes, 0 .. g-1:
+        the groups).  The players are then the groups: the point estimate is that of ``ls_spa(method='subsets',
+        groups=)``, every replicate is re-attributed over the 2^g group subsets (include/lsspa.h,
+        lsspa_boot_groups_run), and ``attribution``, ``replicates`` [n_boot][g], ``std_error``, ``lower``, ``upper`` and
+        ``prob_greater`` [g][g] speak of groups; ``theta`` keeps length p, and ``baseline_r_squared_replicates`` holds
+        the R^2 of each replicate's baseline alone (a replicate sums to its R^2 minus that).  A given seed resamples
+        the same rows with and without groups.  Limits: g <= 32 and p <= 64, ValueError otherwise.
+    Without groups, p > 32 raises ValueError: group the columns (``ls_spa_groups``) or use a sampling method."""
     data = _coerce_data(X_train, X_test, y_train, y_test)
     n, p = data[0].shape
     m = data[1].shape[0]
-    if p > SUBSETS_MAX_P:
+    labels = None
+    if groups is not None:
+        if p > GROUPS_MAX_P:
+            raise ValueError(f"ls_spa_bootstrap(groups=) takes at most p = {GROUPS_MAX_P} columns, the baseline's "
+                             f"included (this problem has p = {p})")
+        labels, _ = group_labels(groups, p)
+    elif p > SUBSETS_MAX_P:
         raise ValueError(f"ls_spa_bootstrap re-runs the enumeration of all 2^p feature subsets and takes at most p = "
                          f"{SUBSETS_MAX_P} features (this problem has p = {p}); group the columns (ls_spa_groups) to "
                          "attribute to at most 32 players, or use a sampling method")
@@ -1161,14 +1176,19 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
         if getattr(engine, "precision", "float64") != "float64":
             engine.set_precision("float64")
         theta, r_squared, info = _load_and_fit(engine, data, reg, False, None)
-        phi, bits = engine.subsets_shapley()
+        phi, bits = engine.subsets_shapley() if labels is None else engine.groups_shapley(labels)
         _info_verdict((bits | info) & 1, stacklevel=3)
         if info & 1:
             theta, r_squared = _singular_fit(engine, data[1], data[3])
-        engine.boot_load(*data, reg)
+        if labels is None:
+            engine.boot_load(*data, reg)
+            run = engine.boot_run
+        else:
+            engine.boot_load(*data, reg, grouped=True)
+            run = functools.partial(engine.boot_groups_run, labels)
         undo.append((engine.boot_free, True))
         if not fixed:
-            rep, r2, binfo = engine.boot_run(n_boot, seed, w_train, w_test)
+            parts = [run(n_boot, seed, w_train, w_test)]
         else:
             # a side that is not resampled has weight 1 on every row: the run is cut so that those rows of ones stay small
             rows = max((n, m)[k] for k in fixed)
@@ -1179,10 +1199,12 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
                 w = [None if x is None else x[r0:r0 + nb] for x in (w_train, w_test)]
                 for k in fixed:
                     w[k] = np.ones((nb, (n, m)[k]))
-                parts.append(engine.boot_run(nb, seed, w[0], w[1], first=r0))
-            rep, r2, binfo = (np.concatenate([q[k] for q in parts]) for k in range(3))
+                parts.append(run(nb, seed, w[0], w[1], first=r0))
+        rep, r2, *base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(len(parts[0])))
     failed = (binfo & 1).astype(bool) | ~np.isfinite(rep).all(axis=1) | ~np.isfinite(r2)
-    res = BootstrapResults.from_replicates(phi, theta, r_squared, rep, r2, failed, confidence)
+    for b in base:
+        failed |= ~np.isfinite(b)
+    res = BootstrapResults.from_replicates(phi, theta, r_squared, rep, r2, failed, confidence, *base)
     if res.n_failed:
         warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
                       "positive definite (a column constant or collinear on the resampled rows); they are NaN in "

@@ -90,6 +90,19 @@ def debug_boot_plan(R: int, n: int, m: int, p: int, block: int = 0):
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def debug_boot_groups_plan(R: int, n: int, m: int, labels, block: int = 0):
+    """Test hook, host only: debug_boot_plan for a bootstrap over the groups of columns that labels names (one label per
+    column; include/lsspa.h, lsspa_debug_boot_groups_plan).  ValueError for labels or sizes the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(15, dtype=np.int64)
+    rc = N.load().lsspa_debug_boot_groups_plan(int(R), int(n), int(m), N.iptr(labels), len(labels), g, int(block),
+                                               out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_boot_groups_plan: status {rc}")
+    return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -300,15 +313,16 @@ class HipEngine:
         self._check(self._lib.lsspa_subsets_interactions(self._h, N.dptr(phi), N.dptr(inter), C.byref(info)))
         return phi, inter, info.value
 
-    # ---- bootstrap of the exact attribution (p <= 32) -------------------------------------
-    def boot_load(self, X_train, X_test, y_train, y_test, reg: float):
+    # ---- bootstrap of the exact attribution (p <= 32; over groups of columns p <= 64) ------
+    def boot_load(self, X_train, X_test, y_train, y_test, reg: float, grouped: bool = False):
         """Keep [X | y] of both sides on the device for boot_run (include/lsspa.h, lsspa_boot_load); the loaded problem is
-        not touched."""
+        not touched.  grouped: lsspa_boot_groups_load, which takes p <= 64 for boot_groups_run."""
         dt = np.float32 if (X_train.dtype == np.float32 and X_test.dtype == np.float32) else np.float64
         Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
         ya, ye = np.ascontiguousarray(y_train, dtype=dt), np.ascontiguousarray(y_test, dtype=dt)
         n, p = Xa.shape
-        self._check(self._lib.lsspa_boot_load(
+        load = self._lib.lsspa_boot_groups_load if grouped else self._lib.lsspa_boot_load
+        self._check(load(
             self._h, Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p,
             float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
         self._boot_dims = (p, n, Xe.shape[0])
@@ -337,6 +351,21 @@ class HipEngine:
         self._check(self._lib.lsspa_boot_run(self._h, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa),
                                              N.dptr(we), int(block), N.dptr(phi), N.dptr(r2), N.iptr(info)))
         return phi, r2, info
+
+    def boot_groups_run(self, labels, R: int, seed: int, w_train=None, w_test=None, block: int = 0, first: int = 0):
+        """(phi [R][g], r2 [R], r2_base [R], info [R]) of replicates first .. first + R - 1 over the groups of columns that
+        labels names (include/lsspa.h, lsspa_boot_groups_run); the phi of a replicate sum to r2 - r2_base."""
+        labels, g = self._labels(labels)
+        dims = getattr(self, "_boot_dims", None)
+        if dims is not None and len(labels) != dims[0]:
+            raise ValueError(f"labels must have length p = {dims[0]}")
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        phi, r2, base = np.empty((R, max(g, 1))), np.empty(R), np.empty(R)
+        info = np.zeros(R, dtype=np.int32)
+        self._check(self._lib.lsspa_boot_groups_run(self._h, N.iptr(labels), g, int(R), int(seed) & (2 ** 64 - 1),
+                                                    int(first), N.dptr(wa), N.dptr(we), int(block), N.dptr(phi),
+                                                    N.dptr(r2), N.dptr(base), N.iptr(info)))
+        return phi, r2, base, info
 
     def boot_timing(self):
         """Kernel seconds of the last boot_run: counts (or the upload of weights), Gram, enumeration."""

@@ -141,7 +141,12 @@ class BootstrapResults:
     ``r_squared_replicates`` [n_boot] are the bootstrap replicates; a replicate whose Gram matrix was not numerically
     positive definite is NaN in both and counted in ``n_failed``.  Over the valid replicates: ``std_error`` [p] (sample
     standard deviation), ``lower`` / ``upper`` [p] and ``r_squared_interval`` (percentile interval: ``np.quantile`` at alpha =
-    (1 - ``confidence``) / 2 and 1 - alpha, numpy's default interpolation) and ``prob_greater`` [p][p], the share of replicates with phi_i > phi_j."""
+    (1 - ``confidence``) / 2 and 1 - alpha, numpy's default interpolation) and ``prob_greater`` [p][p], the share of replicates with phi_i > phi_j.
+
+    With ``groups=`` the players are the g groups: ``attribution``, ``replicates`` [n_boot][g], ``std_error``, ``lower``,
+    ``upper`` have length g and ``prob_greater`` is [g][g] ("is variable A really worth more than variable B?");
+    ``theta`` keeps length p.  A replicate's attribution then sums to its R^2 minus the R^2 of its baseline columns
+    alone, ``baseline_r_squared_replicates`` [n_boot] (zeros without a baseline; None without ``groups=``)."""
     attribution: np.ndarray
     theta: np.ndarray
     r_squared: float
@@ -154,9 +159,11 @@ class BootstrapResults:
     n_failed: int
     prob_greater: np.ndarray
     confidence: float = 0.95
+    baseline_r_squared_replicates: np.ndarray | None = None
 
     @classmethod
-    def from_replicates(cls, attribution, theta, r_squared, replicates, r_squared_replicates, failed, confidence=0.95):
+    def from_replicates(cls, attribution, theta, r_squared, replicates, r_squared_replicates, failed, confidence=0.95,
+                        baseline_r_squared_replicates=None):
         """The summary fields from the replicates; failed [n_boot]: which replicates to mask.  RuntimeError when more
         than half of them failed."""
         rep = np.array(replicates, dtype=np.float64)
@@ -164,6 +171,10 @@ class BootstrapResults:
         failed = np.asarray(failed, dtype=bool)
         rep[failed] = np.nan
         r2[failed] = np.nan
+        base = None
+        if baseline_r_squared_replicates is not None:
+            base = np.array(baseline_r_squared_replicates, dtype=np.float64)
+            base[failed] = np.nan
         n_failed = int(failed.sum())
         if 2 * n_failed > len(rep):
             raise RuntimeError(f"{n_failed} of {len(rep)} bootstrap replicates had a Gram matrix that was not numerically "
@@ -178,7 +189,7 @@ class BootstrapResults:
                    lower=lower, upper=upper,
                    r_squared_interval=(float(np.quantile(r2_ok, alpha)), float(np.quantile(r2_ok, 1.0 - alpha))),
                    n_failed=n_failed, prob_greater=(ok[:, :, None] > ok[:, None, :]).mean(axis=0),
-                   confidence=float(confidence))
+                   confidence=float(confidence), baseline_r_squared_replicates=base)
 
     def __repr__(self):
         pad = " " * 8

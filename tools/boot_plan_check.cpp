@@ -4,6 +4,7 @@
 // Sweeps R, N, M, p and block over their edges (1, the 16-column block edges, the row limit 2^31 - 1, block requests
 // beyond the memory bound) and checks what the callers rely on: at least one replicate a block, blocks that cover R,
 // the memory bound wherever one replicate fits it, slices that cover the rows, enumeration launches within their bound.
+// Then the same for the grouped planner (boot_groups_plan) up to p = 64, and both planners' refusals.
 #include <cstdio>
 #include <cstdlib>
 
@@ -46,6 +47,52 @@ int main() {
             CHECK(P.units * P.per == (1ull << (p < BOOT_LOW ? 0 : p - BOOT_LOW)) && P.steps >= 1 && P.steps <= P.per);
             ++n_ok;
           }
+  // The grouped planner (boot_groups_plan): every p up to 64 with layouts of gh high groups, nb baseline and ql low
+  // columns at their edges -- no high group, no low group, gh = 26 (the most that 64 columns hold beside six low
+  // singletons), a baseline that leaves one column a group
+  struct Lay { int g, gh, nb, ql; };
+  const int64_t rows_test[] = {1, 513, (1ll << 31) - 1};
+  for (int64_t R : reps)
+    for (int64_t N : rows)
+      for (int64_t M : rows_test)
+        for (int p = 1; p <= 64; ++p)
+          for (int64_t block : blocks) {
+            const int six = p < 6 ? p : 6;
+            const Lay lays[] = {{1, p > 6 ? 1 : 0, 0, p > 6 ? 0 : p},            // the columns as one group
+                                {six, 0, p - six, six},                          // low singletons, the rest baseline
+                                {p < 32 ? p : 32, (p < 32 ? p : 32) - six, 0, six},   // as many groups as fit
+                                {p > 6 ? 2 : 1, p > 6 ? 1 : 0, p > 6 ? 1 : 0, p > 6 ? 3 : p}};
+            for (const Lay& L : lays) {
+              BootPlan P;
+              CHECK(boot_groups_plan(R, N, M, p, L.g, L.gh, L.nb, L.ql, block, P) == nullptr);
+              CHECK(P.cb == (p + 16) / 16 && P.cb <= 5 && P.ldz == 16 * P.cb && P.pairs == P.cb * (P.cb + 1) / 2);
+              CHECK(P.rpw == (P.cb <= 2 ? 4 : P.cb == 3 ? 2 : 1) && P.rpw * P.pairs * 4 <= 60);
+              CHECK(P.block >= 1 && P.block <= R && P.block <= BOOT_MAX_BLOCK && (block == 0 || P.block <= block));
+              CHECK(P.n_blocks >= 1 && (P.n_blocks - 1) * P.block < R && P.n_blocks * P.block >= R);
+              CHECK(P.block == 1 || P.block * P.rep_bytes <= BOOT_BLOCK_BYTES);
+              BootPlan Q;      // the slices are the ungrouped planner's for the same rows
+              CHECK(boot_plan(R, N, M, 1, block, Q) == nullptr);
+              for (int s = 0; s < 2; ++s) CHECK(P.rps[s] == Q.rps[s] && P.slices[s] == Q.slices[s]);
+              CHECK(P.enum_reps >= 1 && P.enum_reps <= P.block &&
+                    P.units * (uint64_t)P.enum_reps <= BOOT_SUBSETS_PER_LAUNCH);
+              CHECK(P.units * P.per == (1ull << L.gh) && P.units <= BOOT_UNITS && P.steps >= 1 && P.steps <= P.per);
+              // the cut of `per` into launches is the layout's alone: not R's, the block's or the rows'
+              CHECK(boot_groups_plan(1, 1, 1, p, L.g, L.gh, L.nb, L.ql, 0, Q) == nullptr && Q.steps == P.steps &&
+                    Q.units == P.units && Q.per == P.per);
+              ++n_ok;
+            }
+          }
+  {
+    int64_t R = 1, N = 1, M = 1, block = 0;
+    int p = 8;
+    BootPlan P;
+    CHECK(boot_groups_plan(1, 1, 1, 65, 1, 1, 0, 0, 0, P) && boot_groups_plan(1, 1, 1, 0, 1, 1, 0, 0, 0, P));
+    CHECK(boot_groups_plan(1, 1, 1, 40, 33, 27, 0, 6, 0, P) && boot_groups_plan(1, 1, 1, 8, 0, 0, 0, 0, 0, P));
+    CHECK(boot_groups_plan(1, 1, 1, 8, 2, 3, 0, 0, 0, P) && boot_groups_plan(1, 1, 1, 8, 2, 1, 0, 7, 0, P));
+    CHECK(boot_groups_plan(1, 1, 1, 8, 8, 1, 0, 6, 0, P) && boot_groups_plan(1, 1, 1, 8, 2, 1, 8, 1, 0, P));
+    CHECK(boot_groups_plan(0, 1, 1, 8, 2, 1, 0, 1, 0, P) && boot_groups_plan(1, 1, 1ll << 31, 8, 2, 1, 0, 1, 0, P));
+    CHECK(boot_groups_plan(1, 1, 1, 8, 2, 1, 0, 1, -1, P) && !boot_groups_plan(1, 1, 1, 8, 2, 1, 0, 1, 0, P));
+  }
   BootPlan P;
   const bool refused = boot_plan(0, 1, 1, 1, 0, P) && boot_plan(1, 0, 1, 1, 0, P) && boot_plan(1, 1, 1ll << 31, 1, 0, P) &&
                        boot_plan(1, 1, 1, 33, 0, P) && boot_plan(1, 1, 1, 0, 0, P) && boot_plan(1, 1, 1, 1, -1, P);
