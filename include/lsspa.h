@@ -236,6 +236,39 @@ int lsspa_boot_groups_run(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32
 int lsspa_debug_boot_groups_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p, int32_t g,
                                  int64_t block, int64_t* plan15);
 
+/* Bootstrap of the exact pairwise interaction values: the replicates of lsspa_boot_run / lsspa_boot_groups_run -- the
+ * same loaded rows, draws, weights, weighted Grams, finalise, r2, r2_base, info, `first`, `block` and refusals --
+ * enumerated by the interaction instantiation of the same kernels, all replicates of a launch in one grid.
+ *   lsspa_boot_interactions_run : after lsspa_boot_load (a load with p > 32 is LSSPA_ERR_ARG naming the limit).  phi
+ *                     [R][p] is bitwise lsspa_boot_run's for the same seed; inter [R][p][p] is replicate r's raw index
+ *                     I_ij = T0 - T1_i - T1_j + T2_ij as lsspa_subsets_interactions returns it (symmetric, 0 on the
+ *                     diagonal), formed on the host by that call's code.  A replicate's phi and inter have the bits
+ *                     lsspa_subsets_interactions returns for its reduced problem, whatever R, block and first are: a
+ *                     unit's high subsets are cut into launches by p alone, as the one-problem call cuts them.
+ *   lsspa_boot_groups_interactions_run : after either load; labels, g as lsspa_boot_groups_run's.  phi [R][g] and
+ *                     inter [R][g][g] in label order, with the bits of lsspa_groups_interactions on the replicate's
+ *                     reduced problem; phi is bitwise lsspa_boot_groups_run's.
+ *   The partial table is d (d + 3) / 2 + 2 columns wide (d = p or g; 37 MB a replicate at d = 32): it is kept for the
+ *   replicates of one enumeration launch only, beside the block's 256 MB, so a block is not cut to a few replicates.
+ *   lsspa_boot_timing reports these runs like the others.
+ *   lsspa_debug_boot_inter_plan, lsspa_debug_boot_groups_inter_plan : host only -- the fifteen numbers of
+ *                     lsspa_debug_boot_plan / lsspa_debug_boot_groups_plan for these runs.  Bytes per replicate leave
+ *                     the partial table out: block * bytes + replicates per launch * units * columns * 8 <= 256 MB
+ *                     (or block = 1).  steps is a function of the players alone; units * replicates per launch *
+ *                     steps <= 2^20. */
+int lsspa_boot_interactions_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first,
+                                const double* w_train /* [R][N] or NULL */, const double* w_test /* [R][M] or NULL */,
+                                int64_t block, double* phi /* [R][p] */, double* inter /* [R][p][p] */,
+                                double* r2 /* [R] */, int32_t* info /* [R] */);
+int lsspa_boot_groups_interactions_run(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, int64_t R,
+                                       uint64_t seed, int64_t first, const double* w_train /* [R][N] or NULL */,
+                                       const double* w_test /* [R][M] or NULL */, int64_t block,
+                                       double* phi /* [R][g] */, double* inter /* [R][g][g] */, double* r2 /* [R] */,
+                                       double* r2_base /* [R] */, int32_t* info /* [R] */);
+int lsspa_debug_boot_inter_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15);
+int lsspa_debug_boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p,
+                                       int32_t g, int64_t block, int64_t* plan15);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

@@ -38,6 +38,24 @@ void plan_blocks(int64_t R, int64_t N, int64_t M, int c, int players, int64_t bl
   P.n_blocks = (R + P.block - 1) / P.block;
 }
 
+// The interaction planners' blocks: the partial table [enum_reps][units][cols] is one launch's and stands beside the
+// block; launch_reps: the replicates a launch of P.steps steps may take by its launch bounds.  Needs units, steps.
+void plan_inter_blocks(int64_t R, int64_t N, int64_t M, int c, int cols, uint64_t launch_reps, int64_t block,
+                       BootPlan& P) {
+  const int64_t rep_table = (int64_t)P.units * cols * 8;
+  const int64_t most_reps = std::max<int64_t>(
+      1, std::min<int64_t>({BOOT_MAX_BLOCK, (int64_t)std::min<uint64_t>(launch_reps, 1ull << 30),
+                            BOOT_INTER_TABLE_BYTES / rep_table}));
+  P.rep_bytes = 8 * (N + M) + (int64_t)(P.slices[0] + P.slices[1]) * P.pairs * 256 * 8 + (int64_t)cols * 8 +
+                8ll * c * c * 8;
+  const int64_t left = BOOT_BLOCK_BYTES - most_reps * rep_table;
+  int64_t most = std::max<int64_t>(1, std::min<int64_t>(BOOT_MAX_BLOCK, left / P.rep_bytes));
+  P.block = std::min<int64_t>(R, block > 0 ? std::min(block, most) : most);
+  P.n_blocks = (R + P.block - 1) / P.block;
+  P.enum_reps = std::min<int64_t>(P.block, most_reps);
+  P.table_bytes = P.enum_reps * rep_table;
+}
+
 const char* plan_sizes(int64_t R, int64_t N, int64_t M, int64_t block) {
   if (R < 1) return "R must be at least 1";
   if (N < 1 || M < 1 || N >= (1ll << 31) || M >= (1ll << 31)) return "N and M must be 1 .. 2^31 - 1";
@@ -88,6 +106,37 @@ const char* boot_groups_plan(int64_t R, int64_t N, int64_t M, int p, int g, int 
   P.steps = std::min<uint64_t>(P.per, std::max<uint64_t>(1, per_launch / P.units));
   const uint64_t groups = std::min<uint64_t>(BOOT_SUBSETS_PER_LAUNCH, per_launch) / (P.units * P.steps);
   P.enum_reps = std::max<int64_t>(1, std::min<int64_t>(P.block, (int64_t)groups));
+  return nullptr;
+}
+
+const char* boot_inter_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P) {
+  P = BootPlan{};
+  if (p < 1 || p > BOOT_MAX_P) return "p must be 1 .. 32";
+  if (const char* why = plan_sizes(R, N, M, block)) return why;
+  const int c = p + 1;
+  plan_gram(N, M, c, P);
+  const int q = p < BOOT_LOW ? p : BOOT_LOW;
+  const uint64_t n_high = 1ull << (p - q);
+  P.units = std::min<uint64_t>(n_high, BOOT_UNITS);
+  P.per = n_high / P.units;
+  // the one-problem call's own cut: the players alone decide it
+  P.steps = std::min<uint64_t>(P.per, std::max<uint64_t>(1, BOOT_SUBSETS_PER_LAUNCH / P.units));
+  plan_inter_blocks(R, N, M, c, boot_inter_cols(p), BOOT_SUBSETS_PER_LAUNCH / (P.units * P.steps), block, P);
+  return nullptr;
+}
+
+const char* boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
+                                   BootPlan& P) {
+  BootPlan Q;      // arguments, Gram side, units, per and steps: the phi planner's
+  if (const char* why = boot_groups_plan(R, N, M, p, g, gh, nb, ql, block, Q)) {
+    P = BootPlan{};
+    return why;
+  }
+  P = Q;
+  const uint64_t rows = (uint64_t)(nb + ql + 1) + (uint64_t)(p - nb - ql + 1) / 2;
+  const uint64_t per_launch = std::max<uint64_t>(1, BOOT_GROUPS_WORK_PER_LAUNCH / (rows * rows));
+  const uint64_t launch_reps = std::min<uint64_t>(BOOT_SUBSETS_PER_LAUNCH, per_launch) / (P.units * P.steps);
+  plan_inter_blocks(R, N, M, p + 1, boot_inter_cols(g), launch_reps, block, P);
   return nullptr;
 }
 

@@ -12,8 +12,11 @@ struct BootPlan {
   int slices[2];           // row slices, train / test (the last one may be ragged)
   int64_t rep_bytes;       // device bytes one replicate of a block takes: weights, Gram partials, enumeration partials
   int64_t block, n_blocks; // replicates per block (the last block may hold fewer), blocks
-  int64_t enum_reps;       // replicates one enumeration launch takes (units * enum_reps <= BOOT_SUBSETS_PER_LAUNCH)
+  int64_t enum_reps;       // replicates one enumeration launch takes: units * enum_reps <= BOOT_SUBSETS_PER_LAUNCH; the
+                           // interaction planners: units * enum_reps * steps <= that, enum_reps <= BOOT_MAX_BLOCK and a
+                           // table of at most BOOT_INTER_TABLE_BYTES (below)
   uint64_t units, per, steps;   // enumeration: units per replicate, high subsets per unit, steps per launch
+  int64_t table_bytes;     // the interaction planners: the enumeration's partial table, kept once beside the block (else 0)
 };
 constexpr int64_t BOOT_BLOCK_BYTES = 256ll << 20;   // what the replicates of one block may take together
 constexpr int64_t BOOT_MAX_BLOCK = 1024;
@@ -33,5 +36,23 @@ const char* boot_groups_plan(int64_t R, int64_t N, int64_t M, int p, int g, int 
                              BootPlan& P);
 constexpr int BOOT_GROUPS_MAX_P = 64, BOOT_GROUPS_MAX_G = 32;   // GROUPS_MAX_P, GROUPS_MAX_G (k_groups.hip)
 constexpr uint64_t BOOT_GROUPS_WORK_PER_LAUNCH = 1ull << 26;    // that of lsspa_groups_shapley's host path
+
+// The bootstrap of the interaction values (lsspa_boot_interactions_run, lsspa_boot_groups_interactions_run): the plans
+// above with the enumeration's partial table inter_cols(d) = d (d + 3) / 2 + 2 wide, d = p or g players -- 37 MB a
+// replicate at d = 32.  The accounting differs for that reason:
+//   - the table is kept for the enum_reps replicates of ONE enumeration launch, not for the block: table_bytes =
+//     enum_reps units inter_cols(d) 8, and rep_bytes holds everything else a replicate takes (its row of column sums
+//     included).  block rep_bytes + table_bytes <= BOOT_BLOCK_BYTES, or block = 1;
+//   - units, per, steps are the one-problem interaction call's own cut, a function of the players alone (ungrouped:
+//     steps = min(per, max(1, BOOT_SUBSETS_PER_LAUNCH / units)); grouped: boot_groups_plan's) and never of R, block or
+//     enum_reps, since the cut of `per` into launches shows in the bits;
+//   - enum_reps fills what a launch of `steps` steps leaves: units enum_reps steps <= 2^20 (grouped: and the work bound
+//     BOOT_GROUPS_WORK_PER_LAUNCH), a table of at most BOOT_INTER_TABLE_BYTES, at most the block, at least 1.
+// Everything of the Gram side (cb .. slices) is that of boot_plan / boot_groups_plan for the same rows.
+constexpr int64_t BOOT_INTER_TABLE_BYTES = 64ll << 20;
+inline int boot_inter_cols(int d) { return d + 2 + d + d * (d - 1) / 2; }   // subsets_inter_cols (k_subsets.hip)
+const char* boot_inter_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P);
+const char* boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
+                                   BootPlan& P);
 
 }  // namespace lsspa

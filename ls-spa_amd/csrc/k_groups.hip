@@ -102,8 +102,9 @@ __device__ inline void wave_sum_low(double (&x)[GQ]) {
 // Replicates (the bootstrap, k_boot.hip): replicate r = blockIdx.y of a launch has its problem r strides behind the
 // launch's, at the dense strides of k_subsets.hip -- G, H: p ld, g, h: p, one 1 / ||y||^2 (GroupArgs::inv_yy_rep) and one
 // info word each, part: the table of the replicates before it.  The layout table, the weights and the labels are the
-// launch's.  That is the REPS instantiation of the phi-only kernel; without REPS the replicate is 0 at compile time and
-// the code is what it was before replicates existed (explicit stride arguments cost k_subsets.hip its occupancy).
+// launch's.  Those are the REPS instantiations (phi-only and INTER, whose row of the table is subsets_inter_cols(g)
+// wide); without REPS the replicate is 0 at compile time and the code is what it was before replicates existed (explicit
+// stride arguments cost k_subsets.hip its occupancy).
 template <bool REPS>
 __device__ inline int64_t rep_offset(int64_t stride) { return REPS ? (int64_t)blockIdx.y * stride : 0; }
 
@@ -281,15 +282,29 @@ __device__ void load_shared(GrpShared& sh, const GroupArgs& a, int tid) {
 __device__ inline int pair_col(int g, int i, int j) { return i * (2 * g - i - 1) / 2 + (j - i - 1); }
 
 // INTER: the interaction sums T0, T1, T2 beside phi's (lsspa_groups_interactions); a row of part is then
-// subsets_inter_cols(g) wide.  Everything of the phi-only instantiation is in both, unchanged.  REPS (phi only): the
-// launch's second grid dimension is the replicate (rep_offset above).
+// subsets_inter_cols(g) wide.  Everything of the phi-only instantiation is in both, unchanged.  REPS: the launch's second
+// grid dimension is the replicate (rep_offset above).
 template <bool INTER, bool REPS = false>
 __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s0, uint64_t s1) {
   __shared__ GrpShared sh;
   __shared__ GrpInterShared si;                // INTER only: never referenced, hence not allocated, otherwise
   const int tid = threadIdx.x;
   const int ng = a.ng, gl = a.gl, gh = a.gh;
-  load_shared<REPS>(sh, a, tid);
+  // INTER with REPS: the replicate's strides go into the arguments once, here, and the code below is the one-problem
+  // kernel's (RO = false) -- offsets formed at every use, as the phi-only REPS instantiation forms them, cost this one
+  // scalar registers it does not have and sent it to scratch
+  constexpr bool RO = REPS && !INTER;
+  if constexpr (REPS && INTER) {
+    const int64_t r = blockIdx.y;
+    a.G += r * a.p * a.ldg;
+    a.H += r * a.p * a.ldh;
+    a.g += r * a.p;
+    a.h += r * a.p;
+    a.info += r;
+    a.part += r * gridDim.x * (ng + 2 + ng + ng * (ng - 1) / 2);
+    a.inv_yy = a.inv_yy_rep[r];
+  }
+  load_shared<RO>(sh, a, tid);
   double acc[GG];
 #pragma unroll
   for (int j = 0; j < GG; ++j) acc[j] = 0.0;
@@ -323,7 +338,7 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
   const int kt = __popc(tid);
   for (uint64_t s = s0; s < s1; ++s) {
     const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
-    const double v = group_values<REPS>(sh, a, hi, tid, bad);
+    const double v = group_values<RO>(sh, a, hi, tid, bad);
     if (live) {
       const int k = __popcll(hi) + kt;
       const double c = (sh.wa[k] + sh.wb[k]) * v;
@@ -371,7 +386,7 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
   }
   const int cols = INTER ? ng + 2 + ng + ng * (ng - 1) / 2 : ng + 1;
   if (tid < 64) {     // the live lanes all sit in the first wave
-    double* part = a.part + (rep_offset<REPS>(gridDim.x) + (int64_t)blockIdx.x) * cols;
+    double* part = a.part + (rep_offset<RO>(gridDim.x) + (int64_t)blockIdx.x) * cols;
 #pragma unroll
     for (int t = 0; t < GQ; ++t) {
       if (t < gl) {
@@ -439,7 +454,7 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
       }
     }
   }
-  if (__any(bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<REPS>(1), 1);
+  if (__any(bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<RO>(1), 1);
 }
 
 // masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
@@ -528,15 +543,19 @@ const char* groups_layout(const int32_t* labels, int p, int g, GroupLayout& L) {
 hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
                               hipStream_t st, int reps) {
   if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
-  // replicates: phi only, with inv_yy_rep, at most 2^20 workgroups a launch (the caller vouches for `reps` problems,
-  // tables, info words behind the first); one problem: no inv_yy_rep
-  if (reps < 1 || reps > 65535 || (a.inv_yy_rep ? inter || units * (uint64_t)reps > (1ull << 20) : reps != 1))
+  // replicates: with inv_yy_rep, at most 2^20 workgroups a launch (the caller vouches for `reps` problems, tables, info
+  // words behind the first); one problem: no inv_yy_rep
+  if (reps < 1 || reps > 65535 || (a.inv_yy_rep ? units * (uint64_t)reps > (1ull << 20) : reps != 1))
     return hipErrorInvalidValue;
   // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^gh
   if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
   if (inter) {
     if (a.gh > GHI) return hipErrorInvalidValue;   // the kernel's pair masks (no layout of <= 64 columns has more)
-    hipLaunchKernelGGL(groups_enum_kernel<true>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+    if (a.inv_yy_rep)
+      hipLaunchKernelGGL((groups_enum_kernel<true, true>), dim3((unsigned)units, (unsigned)reps), dim3(NT), 0, st, a, s0,
+                         s1);
+    else
+      hipLaunchKernelGGL(groups_enum_kernel<true>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
   } else if (a.inv_yy_rep) {
     hipLaunchKernelGGL((groups_enum_kernel<false, true>), dim3((unsigned)units, (unsigned)reps), dim3(NT), 0, st, a, s0,
                        s1);

@@ -37,8 +37,8 @@
 // its first p + 1 columns computed by the very operations of the phi-only kernel.
 //
 // Replicates (the bootstrap, k_boot.hip): launch_subsets_enum(.., reps) runs `reps` problems laid out one behind the other
-// as the second grid dimension of the phi-only kernel (the REPS instantiation, rep_offset below); a replicate's arithmetic
-// is that of the one-problem kernel, operation for operation.
+// as the second grid dimension of the kernel (the REPS instantiations, rep_offset below), phi-only or with the interaction
+// sums; a replicate's arithmetic is that of the one-problem kernel, operation for operation.
 #include "kernels.h"
 
 namespace lsspa {
@@ -66,8 +66,9 @@ struct SubShared {
 
 // Replicates (the bootstrap, k_boot.hip): replicate r = blockIdx.y of a launch has its problem r strides behind the
 // launch's -- G, H: p ld, g, h: p, one 1 / ||y||^2 and one info word each, part: the table of the replicates before it.
-// That is the REPS instantiation of the phi-only kernel; without REPS the replicate is 0 at compile time and the code is
-// what it was before replicates existed (the kernel sits at the edge of its register budget: see DESIGN.md).
+// Those are the REPS instantiations (phi-only and INTER, whose row of the table is subsets_inter_cols(p) wide); without
+// REPS the replicate is 0 at compile time and the code is what it was before replicates existed (the kernel sits at the
+// edge of its register budget: see DESIGN.md).
 template <bool REPS>
 __device__ inline int64_t rep_offset(int64_t stride) { return REPS ? (int64_t)blockIdx.y * stride : 0; }
 
@@ -460,12 +461,15 @@ int subsets_inter_cols(int p) { return p + 2 + p + p * (p - 1) / 2; }
 hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
                                hipStream_t st, int reps) {
   if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
-  // replicates: phi only (the caller vouches for `reps` problems, tables, info words behind the first)
-  if (reps < 1 || reps > 65535 || (reps > 1 && inter)) return hipErrorInvalidValue;
+  // replicates: the caller vouches for `reps` problems, tables, info words behind the first
+  if (reps < 1 || reps > 65535) return hipErrorInvalidValue;
   // every high subset index of the launch must exist: unit u covers [u per, (u + 1) per) of 2^(p - q)
   const int nh = a.p - a.q;
   if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
-  if (inter)
+  if (inter && reps > 1)
+    hipLaunchKernelGGL((subsets_enum_kernel<true, true>), dim3((unsigned)units, (unsigned)reps), dim3(64), 0, st, a, s0,
+                       s1);
+  else if (inter)
     hipLaunchKernelGGL(subsets_enum_kernel<true>, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1);
   else if (reps > 1)
     hipLaunchKernelGGL((subsets_enum_kernel<false, true>), dim3((unsigned)units, (unsigned)reps), dim3(64), 0, st, a, s0,

@@ -326,11 +326,12 @@ struct SubsetArgs {
   int32_t* info;           // [replicates] bit 1: a pivot failed
   // Replicates (the bootstrap, k_boot.hip): a launch with `reps` replicates runs them as its second grid dimension;
   // replicate r has its problem at the dense replicate stride behind the launch's: G + r p ldg, g + r p, H + r p ldh,
-  // h + r p, inv_yy[r], info[r], part + r units cols.  One replicate (every other launch): r = 0, nothing moves.
+  // h + r p, inv_yy[r], info[r], part + r units cols (cols: the table's width, p + 1 or inter's).  One replicate (every
+  // other launch): r = 0, nothing moves.
 };
 int subsets_low_features(int p);
 int subsets_inter_cols(int p);
-// reps > 1 (phi only): the replicates behind the launch's problem (SubsetArgs) as its second grid dimension
+// reps > 1: the replicates behind the launch's problem (SubsetArgs) as its second grid dimension, phi-only or inter
 hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
                                hipStream_t st, int reps = 1);
 // out[j] = sum over the units of part[u][j], j < cols (the table's width), in a fixed order; replicate r of `reps` reads
@@ -381,11 +382,11 @@ struct GroupArgs {
   int32_t* info;           // bit 1: a pivot failed
   // Replicates (the bootstrap, k_boot.hip): with inv_yy_rep set a launch runs `reps` replicates as its second grid
   // dimension; replicate r has its problem at the dense replicate stride behind the launch's: G + r p ldg, g + r p,
-  // H + r p ldh, h + r p, inv_yy_rep[r] (device; inv_yy is not read), info[r], part + r units (g + 1).  w and tab are
+  // H + r p ldh, h + r p, inv_yy_rep[r] (device; inv_yy is not read), info[r], part + r units cols.  w and tab are
   // shared.  NULL (every other launch): one problem, nothing moves.
   const double* inv_yy_rep;
 };
-// reps: with GroupArgs::inv_yy_rep only (phi only, units * reps <= 2^20)
+// reps: with GroupArgs::inv_yy_rep only (phi-only or inter, units * reps <= 2^20)
 hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
                               hipStream_t st, int reps = 1);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering

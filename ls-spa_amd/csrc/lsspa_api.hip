@@ -3238,6 +3238,25 @@ int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uin
   return LSSPA_OK;
 }
 
+// inter [n][n] of the column sums `out` of an interactions table of n players (kernels.h): I_ij = T0 - T1_i - T1_j +
+// T2_ij off the diagonal, 0 on it, symmetric.  gid (may be NULL: the identity): the caller's number of player r, as
+// GroupLayout::gid.  The one place where the index is formed: the one-problem calls and the bootstrap's share it.
+void exact_inter_matrix(const double* out, int n, const int* gid, double* inter) {
+  const double t0 = out[n + 1];
+  const double* t1 = out + n + 2;
+  const double* t2 = t1 + n;
+  for (int i = 0; i < n; ++i) {
+    const size_t gi = (size_t)(gid ? gid[i] : i);
+    inter[gi * n + gi] = 0.0;
+    for (int j = i + 1; j < n; ++j, ++t2) {
+      const size_t gj = (size_t)(gid ? gid[j] : j);
+      const double v = ((t0 - t1[i]) - t1[j]) + *t2;
+      inter[gi * n + gj] = v;
+      inter[gj * n + gi] = v;
+    }
+  }
+}
+
 int exact_timing(const ExactWork& W, double* kernel_ms, double* max_launch_ms, int64_t* launches) {
   if (kernel_ms) *kernel_ms = W.kernel_ms;
   if (max_launch_ms) *max_launch_ms = W.max_launch_ms;
@@ -3376,18 +3395,7 @@ int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi, double* inter, int32
   TRY(subsets_enumerate(ctx, true, out.data(), info));
   const int p = ctx->p;
   for (int j = 0; j < p; ++j) phi[j] = out[j] - out[p];
-  // I_ij = T0 - T1_i - T1_j + T2_ij (k_subsets.hip)
-  const double t0 = out[p + 1];
-  const double* t1 = out.data() + p + 2;
-  const double* t2 = t1 + p;
-  for (int i = 0; i < p; ++i) {
-    inter[(size_t)i * p + i] = 0.0;
-    for (int j = i + 1; j < p; ++j, ++t2) {
-      const double v = ((t0 - t1[i]) - t1[j]) + *t2;
-      inter[(size_t)i * p + j] = v;
-      inter[(size_t)j * p + i] = v;
-    }
-  }
+  exact_inter_matrix(out.data(), p, nullptr, inter);
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -3439,20 +3447,7 @@ int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, 
   TRY(groups_enumerate(ctx, true, labels, g, L, out.data(), info));
   const int ng = L.ng;
   for (int r = 0; r < ng; ++r) phi[L.gid[r]] = out[r] - out[ng];
-  // I_kl = T0 - T1_k - T1_l + T2_kl in the layout's numbering (k_groups.hip), then to the caller's labels
-  const double t0 = out[ng + 1];
-  const double* t1 = out.data() + ng + 2;
-  const double* t2 = t1 + ng;
-  for (int i = 0; i < ng; ++i) {
-    const size_t gi = (size_t)L.gid[i];
-    inter[gi * ng + gi] = 0.0;
-    for (int j = i + 1; j < ng; ++j, ++t2) {
-      const size_t gj = (size_t)L.gid[j];
-      const double v = ((t0 - t1[i]) - t1[j]) + *t2;
-      inter[gi * ng + gj] = v;
-      inter[gj * ng + gi] = v;
-    }
-  }
+  exact_inter_matrix(out.data(), ng, L.gid, inter);
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -3496,6 +3491,8 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
 // lsspa_boot_run cuts its R replicates into blocks (boot_plan: by memory).  A block: the weights of both sides on the
 // device (counts drawn there, or the caller's rows copied), one weighted Gram pass per side, the fixed-order sum of its
 // slices, finalise, and the enumeration of k_subsets.hip with the block's replicates as its second grid dimension.
+// lsspa_boot_groups_run enumerates by k_groups.hip instead; the two interaction runs take the INTER instantiations of the
+// same kernels and the interaction planners.  One block loop serves all four (boot_run_blocks).
 namespace {
 
 static_assert(EXACT_UNITS == BOOT_UNITS && SUBSETS_PER_LAUNCH == BOOT_SUBSETS_PER_LAUNCH && SUBSETS_MAX_P == BOOT_MAX_P,
@@ -3539,7 +3536,7 @@ const char* boot_rows_plan(const BootWork& B, int64_t R, int64_t block, BootPlan
   return boot_groups_plan(R, B.n[0], B.n[1], B.p, 1, 1, 0, 0, block, P);
 }
 
-// ecols: the width of the enumeration's partial table (players + 1)
+// ecols: the width of the enumeration's partial table (players + 1; the interaction runs: subsets_inter_cols(players))
 int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, bool counts[2], bool enumerate, int ecols = 0) {
   BootWork& B = ctx->boot;
   const size_t blk = (size_t)P.block, c = (size_t)B.p + 1, p = (size_t)B.p;
@@ -3726,6 +3723,196 @@ int boot_load_rows(lsspa_ctx* ctx, const BootPlan& P, const char* name, const vo
   return LSSPA_OK;
 }
 
+// the fifteen numbers of the debug entry points (include/lsspa.h, lsspa_debug_boot_plan)
+void boot_plan15(const BootPlan& P, int64_t* plan15) {
+  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
+                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
+  std::copy(v, v + 15, plan15);
+}
+
+// The Shapley weights of `players` players -- and with tab the layout of the groups -- onto the device, for a run
+int boot_upload_tables(lsspa_ctx* ctx, int players, const int32_t* tab) {
+  BootWork& B = ctx->boot;
+  if (tab) TRY(dev_alloc(ctx, B.tab, GROUPS_TAB_LEN));
+  double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
+  exact_weight_table(players, w);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(B.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  if (tab) HIPCHK(hipMemcpy(B.tab.ptr, tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
+  return LSSPA_OK;
+}
+
+// The block loop of the four run functions (phi or interactions, features or groups).  Per block of P.block replicates:
+// weights, the weighted Grams and their sums, finalise, then the enumeration in launches of P.enum_reps replicates and
+// P.steps steps into a partial table `cols` wide, its column sums, and the block's results on the host.  What differs
+// stays with the entry point:
+//   launch(e0, ne, s0, s1): steps s0 .. s1 - 1 of replicates e0 .. e0 + ne - 1 of the block into B.epart;
+//   emit(r, out, G, g, H, h, inv_yy): replicate r of the run from its `cols` column sums and its reduced problem (host).
+// The buffers are the caller's (boot_alloc_block with this P and cols, boot_upload_tables).  Leaves the run's timing in
+// B.ms.
+template <typename Launch, typename Emit>
+int boot_run_blocks(lsspa_ctx* ctx, const BootPlan& P, int64_t R, uint64_t seed, int64_t first,
+                    const double* const w_host[2], int cols, Launch&& launch, Emit&& emit, int32_t* info) {
+  BootWork& B = ctx->boot;
+  hipStream_t st = ctx->stream;
+  const int p = B.p;
+  const size_t c = (size_t)cols;
+  std::vector<hipEvent_t> ev(4, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  std::vector<double> out((size_t)P.block * c), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
+      gh((size_t)P.block * p), hh((size_t)P.block * p), yh((size_t)P.block);
+  B.ms[0] = B.ms[1] = B.ms[2] = 0.0;
+  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
+    const int nb = (int)std::min<int64_t>(P.block, R - b0);
+    HIPCHK(hipEventRecord(ev[0], st));
+    TRY(boot_block_sums(ctx, P, w_host, false, seed, (uint64_t)first, b0, nb, ev[1]));
+    HIPCHK(launch_boot_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
+                                B.inv_yy.ptr, st));
+    HIPCHK(hipEventRecord(ev[2], st));
+    HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
+    for (int e0 = 0; e0 < nb; e0 += (int)P.enum_reps) {
+      const int ne = std::min<int>((int)P.enum_reps, nb - e0);
+      HIPCHK(hipMemsetAsync(B.epart.ptr, 0, sizeof(double) * (size_t)ne * P.units * c, st));
+      for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps) HIPCHK(launch(e0, ne, s0, std::min(P.per, s0 + P.steps)));
+      HIPCHK(launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, cols, B.eout.ptr + (size_t)e0 * c, st, ne));
+    }
+    HIPCHK(hipEventRecord(ev[3], st));
+    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Gh.data(), B.G.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Hh.data(), B.H.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(gh.data(), B.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hh.data(), B.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(yh.data(), B.inv_yy.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int r = 0; r < nb; ++r)
+      emit(b0 + r, &out[(size_t)r * c], &Gh[(size_t)r * p * p], &gh[(size_t)r * p], &Hh[(size_t)r * p * p],
+           &hh[(size_t)r * p], yh[r]);
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      B.ms[k] += ms;
+    }
+  }
+  return LSSPA_OK;
+}
+
+// lsspa_boot_run and, with inter, lsspa_boot_interactions_run: the enumeration of k_subsets.hip over the block's
+// replicates; `name` is the entry point's
+int boot_subsets_run(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, int64_t first, const double* w_train,
+                     const double* w_test, int64_t block, double* phi, double* inter, double* r2, int32_t* info) {
+  BootWork& B = ctx->boot;
+  char msg[240];
+  if (B.p > SUBSETS_MAX_P) {
+    snprintf(msg, sizeof msg, "%s enumerates feature subsets and takes at most p = %d features (%d loaded by "
+             "lsspa_boot_groups_load: %s attributes to groups of them)", name, SUBSETS_MAX_P, B.p,
+             inter ? "lsspa_boot_groups_interactions_run" : "lsspa_boot_groups_run");
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  if (const char* why = inter ? boot_inter_plan(R, B.n[0], B.n[1], B.p, block, P)
+                              : boot_plan(R, B.n[0], B.n[1], B.p, block, P)) {
+    snprintf(msg, sizeof msg, "%s: %s", name, why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {!w_train, !w_test};
+  const int p = B.p, cols = inter ? subsets_inter_cols(p) : p + 1;
+  TRY(boot_alloc_block(ctx, P, counts, true, cols));
+  TRY(boot_upload_tables(ctx, p, nullptr));
+  auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
+    SubsetArgs a{};
+    a.p = p;
+    a.q = subsets_low_features(p);
+    a.G = B.G.ptr + (size_t)e0 * p * p;
+    a.H = B.H.ptr + (size_t)e0 * p * p;
+    a.g = B.g.ptr + (size_t)e0 * p;
+    a.h = B.h.ptr + (size_t)e0 * p;
+    a.ldg = a.ldh = p;
+    a.w = B.w.ptr;
+    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+    a.inv_yy = B.inv_yy.ptr + e0;
+    a.info = B.info.ptr + e0;
+    a.per = P.per;
+    a.part = B.epart.ptr;
+    return launch_subsets_enum(a, P.units, s0, s1, inter != nullptr, ctx->stream, ne);
+  };
+  auto emit = [&](int64_t r, const double* out, const double* G, const double* g, const double* H, const double* h,
+                  double inv_yy) {
+    for (int j = 0; j < p; ++j) phi[r * p + j] = out[j] - out[p];
+    if (inter) exact_inter_matrix(out, p, nullptr, inter + (size_t)r * p * p);
+    r2[r] = boot_r2(p, G, g, H, h, inv_yy);
+  };
+  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, launch, emit, info);
+}
+
+// lsspa_boot_groups_run and, with inter, lsspa_boot_groups_interactions_run: the enumeration of k_groups.hip
+int boot_groups_run(lsspa_ctx* ctx, const char* name, const int32_t* labels, int32_t g, int64_t R, uint64_t seed,
+                    int64_t first, const double* w_train, const double* w_test, int64_t block, double* phi,
+                    double* inter, double* r2, double* r2_base, int32_t* info) {
+  BootWork& B = ctx->boot;
+  char msg[200];
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, "the bootstrap over groups of columns takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+             (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  GroupLayout L;
+  if (const char* why = groups_layout(labels, B.p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  if (const char* why = inter ? boot_groups_inter_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)
+                              : boot_groups_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)) {
+    snprintf(msg, sizeof msg, "%s: %s", name, why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {!w_train, !w_test};
+  const int p = B.p, ng = L.ng, cols = inter ? subsets_inter_cols(ng) : ng + 1;
+  TRY(boot_alloc_block(ctx, P, counts, true, cols));
+  TRY(boot_upload_tables(ctx, ng, L.tab));
+  std::vector<double> r2_ws;
+  int all[GROUPS_MAX_P];       // the full model's columns; the baseline's are the layout's first nb
+  for (int j = 0; j < p; ++j) all[j] = j;
+  int base[GROUPS_MAX_P];
+  for (int j = 0; j < L.nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
+  auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
+    GroupArgs a{};
+    a.p = p; a.ng = ng; a.nb = L.nb;
+    a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+    a.G = B.G.ptr + (size_t)e0 * p * p;
+    a.H = B.H.ptr + (size_t)e0 * p * p;
+    a.g = B.g.ptr + (size_t)e0 * p;
+    a.h = B.h.ptr + (size_t)e0 * p;
+    a.ldg = a.ldh = p;
+    a.w = B.w.ptr;
+    a.tab = B.tab.ptr;
+    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+    a.inv_yy_rep = B.inv_yy.ptr + e0;
+    a.info = B.info.ptr + e0;
+    a.per = P.per;
+    a.part = B.epart.ptr;
+    return launch_groups_enum(a, P.units, s0, s1, inter != nullptr, ctx->stream, ne);
+  };
+  auto emit = [&](int64_t r, const double* out, const double* G, const double* gv, const double* H, const double* h,
+                  double inv_yy) {
+    for (int k = 0; k < ng; ++k) phi[r * ng + L.gid[k]] = out[k] - out[ng];
+    if (inter) exact_inter_matrix(out, ng, L.gid, inter + (size_t)r * ng * ng);
+    r2[r] = boot_r2_cols(p, all, p, G, gv, H, h, inv_yy, r2_ws);
+    r2_base[r] = boot_r2_cols(p, base, L.nb, G, gv, H, h, inv_yy, r2_ws);
+  };
+  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, launch, emit, info);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3734,9 +3921,7 @@ int lsspa_debug_boot_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t bl
   if (!plan15) return LSSPA_ERR_ARG;
   BootPlan P;
   if (boot_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
-  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
-                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
-  std::copy(v, v + 15, plan15);
+  boot_plan15(P, plan15);
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_NOMEM;
@@ -3798,92 +3983,33 @@ int lsspa_boot_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, cons
                    const double* w_test, int64_t block, double* phi, double* r2, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(boot_need_loaded(ctx));
-  BootWork& B = ctx->boot;
   if (!phi || !r2 || !info || first < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_run: phi / r2 / info NULL or first < 0");
-  if (B.p > SUBSETS_MAX_P) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "lsspa_boot_run enumerates feature subsets and takes at most p = %d features (%d loaded by "
-             "lsspa_boot_groups_load: lsspa_boot_groups_run attributes to groups of them)", SUBSETS_MAX_P, B.p);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  BootPlan P;
-  if (const char* why = boot_plan(R, B.n[0], B.n[1], B.p, block, P)) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "lsspa_boot_run: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
-  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {!w_train, !w_test};
-  TRY(boot_alloc_block(ctx, P, counts, true));
-  hipStream_t st = ctx->stream;
-  const int p = B.p, c = p + 1;
-  {
-    double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
-    exact_weight_table(p, w);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(B.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
-  }
-  std::vector<hipEvent_t> ev(4, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  std::vector<double> out((size_t)P.block * c), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
-      gh((size_t)P.block * p), hh((size_t)P.block * p), yh((size_t)P.block);
-  B.ms[0] = B.ms[1] = B.ms[2] = 0.0;
-  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
-    const int nb = (int)std::min<int64_t>(P.block, R - b0);
-    HIPCHK(hipEventRecord(ev[0], st));
-    TRY(boot_block_sums(ctx, P, w_host, false, seed, (uint64_t)first, b0, nb, ev[1]));
-    HIPCHK(launch_boot_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
-                                B.inv_yy.ptr, st));
-    HIPCHK(hipEventRecord(ev[2], st));
-    HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
-    for (int e0 = 0; e0 < nb; e0 += (int)P.enum_reps) {
-      const int ne = std::min<int>((int)P.enum_reps, nb - e0);
-      SubsetArgs a{};
-      a.p = p;
-      a.q = subsets_low_features(p);
-      a.G = B.G.ptr + (size_t)e0 * p * p;
-      a.H = B.H.ptr + (size_t)e0 * p * p;
-      a.g = B.g.ptr + (size_t)e0 * p;
-      a.h = B.h.ptr + (size_t)e0 * p;
-      a.ldg = a.ldh = p;
-      a.w = B.w.ptr;
-      a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-      a.inv_yy = B.inv_yy.ptr + e0;
-      a.info = B.info.ptr + e0;
-      a.per = P.per;
-      a.part = B.epart.ptr;
-      HIPCHK(hipMemsetAsync(B.epart.ptr, 0, sizeof(double) * (size_t)ne * P.units * c, st));
-      for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps)
-        HIPCHK(launch_subsets_enum(a, P.units, s0, std::min(P.per, s0 + P.steps), false, st, ne));
-      HIPCHK(launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, c, B.eout.ptr + (size_t)e0 * c, st, ne));
-    }
-    HIPCHK(hipEventRecord(ev[3], st));
-    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Gh.data(), B.G.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Hh.data(), B.H.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(gh.data(), B.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hh.data(), B.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(yh.data(), B.inv_yy.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int r = 0; r < nb; ++r) {
-      for (int j = 0; j < p; ++j) phi[(b0 + r) * p + j] = out[(size_t)r * c + j] - out[(size_t)r * c + p];
-      r2[b0 + r] = boot_r2(p, &Gh[(size_t)r * p * p], &gh[(size_t)r * p], &Hh[(size_t)r * p * p], &hh[(size_t)r * p],
-                           yh[r]);
-    }
-    for (int k = 0; k < 3; ++k) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-      B.ms[k] += ms;
-    }
-  }
-  return LSSPA_OK;
+  return boot_subsets_run(ctx, "lsspa_boot_run", R, seed, first, w_train, w_test, block, phi, nullptr, r2, info);
 } catch (...) {
   return abi_caught(ctx);
+}
+
+int lsspa_boot_interactions_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train,
+                                const double* w_test, int64_t block, double* phi, double* inter, double* r2,
+                                int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  if (!phi || !inter || !r2 || !info || first < 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_interactions_run: phi / inter / r2 / info NULL or first < 0");
+  return boot_subsets_run(ctx, "lsspa_boot_interactions_run", R, seed, first, w_train, w_test, block, phi, inter, r2,
+                          info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_boot_inter_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15) try {
+  if (!plan15) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_inter_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
+  boot_plan15(P, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
 }
 
 int lsspa_debug_boot_groups_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels, int32_t p, int32_t g,
@@ -3893,9 +4019,20 @@ int lsspa_debug_boot_groups_plan(int64_t R, int64_t N, int64_t M, const int32_t*
   if (groups_layout(labels, p, g, L)) return LSSPA_ERR_ARG;
   BootPlan P;
   if (boot_groups_plan(R, N, M, p, L.ng, L.gh, L.nb, L.ql, block, P)) return LSSPA_ERR_ARG;
-  const int64_t v[15] = {P.cb, P.ldz, P.pairs, P.rpw, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.rep_bytes,
-                         P.block, P.n_blocks, P.enum_reps, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps};
-  std::copy(v, v + 15, plan15);
+  boot_plan15(P, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_debug_boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels, int32_t p, int32_t g,
+                                       int64_t block, int64_t* plan15) try {
+  if (!plan15 || !labels || p < 1 || p > GROUPS_MAX_P) return LSSPA_ERR_ARG;
+  GroupLayout L;
+  if (groups_layout(labels, p, g, L)) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_groups_inter_plan(R, N, M, p, L.ng, L.gh, L.nb, L.ql, block, P)) return LSSPA_ERR_ARG;
+  boot_plan15(P, plan15);
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_NOMEM;
@@ -3906,105 +4043,24 @@ int lsspa_boot_groups_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int6
                           double* r2_base, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(boot_need_loaded(ctx));
-  BootWork& B = ctx->boot;
   if (!labels || !phi || !r2 || !r2_base || !info || first < 0)
     return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_groups_run: labels / phi / r2 / r2_base / info NULL or first < 0");
-  char msg[200];
-  if (g > GROUPS_MAX_G) {
-    snprintf(msg, sizeof msg, "the bootstrap over groups of columns takes at most g = %d groups (%d given)", GROUPS_MAX_G,
-             (int)g);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  GroupLayout L;
-  if (const char* why = groups_layout(labels, B.p, g, L)) {
-    snprintf(msg, sizeof msg, "group labels: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  BootPlan P;
-  if (const char* why = boot_groups_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)) {
-    snprintf(msg, sizeof msg, "lsspa_boot_groups_run: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
-  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {!w_train, !w_test};
-  const int p = B.p, ng = L.ng, c = ng + 1;
-  TRY(boot_alloc_block(ctx, P, counts, true, c));
-  TRY(dev_alloc(ctx, B.tab, GROUPS_TAB_LEN));
-  hipStream_t st = ctx->stream;
-  {
-    double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
-    exact_weight_table(ng, w);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(B.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(B.tab.ptr, L.tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  std::vector<hipEvent_t> ev(4, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  std::vector<double> out((size_t)P.block * c), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
-      gh((size_t)P.block * p), hh((size_t)P.block * p), yh((size_t)P.block);
-  std::vector<double> r2_ws;
-  int all[GROUPS_MAX_P];       // the full model's columns; the baseline's are the layout's first nb
-  for (int j = 0; j < p; ++j) all[j] = j;
-  int base[GROUPS_MAX_P];
-  for (int j = 0; j < L.nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
-  B.ms[0] = B.ms[1] = B.ms[2] = 0.0;
-  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
-    const int nb = (int)std::min<int64_t>(P.block, R - b0);
-    HIPCHK(hipEventRecord(ev[0], st));
-    TRY(boot_block_sums(ctx, P, w_host, false, seed, (uint64_t)first, b0, nb, ev[1]));
-    HIPCHK(launch_boot_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
-                                B.inv_yy.ptr, st));
-    HIPCHK(hipEventRecord(ev[2], st));
-    HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
-    for (int e0 = 0; e0 < nb; e0 += (int)P.enum_reps) {
-      const int ne = std::min<int>((int)P.enum_reps, nb - e0);
-      GroupArgs a{};
-      a.p = p; a.ng = ng; a.nb = L.nb;
-      a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
-      a.G = B.G.ptr + (size_t)e0 * p * p;
-      a.H = B.H.ptr + (size_t)e0 * p * p;
-      a.g = B.g.ptr + (size_t)e0 * p;
-      a.h = B.h.ptr + (size_t)e0 * p;
-      a.ldg = a.ldh = p;
-      a.w = B.w.ptr;
-      a.tab = B.tab.ptr;
-      a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-      a.inv_yy_rep = B.inv_yy.ptr + e0;
-      a.info = B.info.ptr + e0;
-      a.per = P.per;
-      a.part = B.epart.ptr;
-      HIPCHK(hipMemsetAsync(B.epart.ptr, 0, sizeof(double) * (size_t)ne * P.units * c, st));
-      for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps)
-        HIPCHK(launch_groups_enum(a, P.units, s0, std::min(P.per, s0 + P.steps), false, st, ne));
-      HIPCHK(launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, c, B.eout.ptr + (size_t)e0 * c, st, ne));
-    }
-    HIPCHK(hipEventRecord(ev[3], st));
-    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Gh.data(), B.G.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Hh.data(), B.H.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(gh.data(), B.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hh.data(), B.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(yh.data(), B.inv_yy.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int r = 0; r < nb; ++r) {
-      for (int k = 0; k < ng; ++k) phi[(b0 + r) * ng + L.gid[k]] = out[(size_t)r * c + k] - out[(size_t)r * c + ng];
-      const double *Gr = &Gh[(size_t)r * p * p], *gr = &gh[(size_t)r * p], *Hr = &Hh[(size_t)r * p * p],
-                   *hr = &hh[(size_t)r * p];
-      r2[b0 + r] = boot_r2_cols(p, all, p, Gr, gr, Hr, hr, yh[r], r2_ws);
-      r2_base[b0 + r] = boot_r2_cols(p, base, L.nb, Gr, gr, Hr, hr, yh[r], r2_ws);
-    }
-    for (int k = 0; k < 3; ++k) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-      B.ms[k] += ms;
-    }
-  }
-  return LSSPA_OK;
+  return boot_groups_run(ctx, "lsspa_boot_groups_run", labels, g, R, seed, first, w_train, w_test, block, phi, nullptr,
+                         r2, r2_base, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_groups_interactions_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, uint64_t seed,
+                                       int64_t first, const double* w_train, const double* w_test, int64_t block,
+                                       double* phi, double* inter, double* r2, double* r2_base, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  if (!labels || !phi || !inter || !r2 || !r2_base || !info || first < 0)
+    return ctx->fail(LSSPA_ERR_ARG,
+                     "lsspa_boot_groups_interactions_run: labels / phi / inter / r2 / r2_base / info NULL or first < 0");
+  return boot_groups_run(ctx, "lsspa_boot_groups_interactions_run", labels, g, R, seed, first, w_train, w_test, block,
+                         phi, inter, r2, r2_base, info);
 } catch (...) {
   return abi_caught(ctx);
 }

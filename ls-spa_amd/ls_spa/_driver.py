@@ -31,8 +31,8 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BootstrapResults, InteractionResults, SampledInteractionResults, ShapleyResults,
-                       validate_data)
+from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, SampledInteractionResults,
+                       ShapleyResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -1125,6 +1125,24 @@ def _bootstrap_options(n_boot, confidence, weights, resample, n, m):
     return out[0], out[1], sides
 
 
+def _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m):
+    """The engine's results of a bootstrap run of n_boot replicates, as a list of one tuple per engine call.  fixed: the
+    sides (0 train, 1 test) that are not resampled and have no weights of the caller's -- weight 1 on every row: the run
+    is then cut so that those rows of ones stay within BOOT_ONES_BYTES on the host."""
+    if not fixed:
+        return [run(n_boot, seed, w_train, w_test)]
+    rows = max((n, m)[k] for k in fixed)
+    step = max(1, min(n_boot, BOOT_ONES_BYTES // (8 * rows)))
+    parts = []
+    for r0 in range(0, n_boot, step):
+        nb = min(step, n_boot - r0)
+        w = [None if x is None else x[r0:r0 + nb] for x in (w_train, w_test)]
+        for k in fixed:
+            w[k] = np.ones((nb, (n, m)[k]))
+        parts.append(run(nb, seed, w[0], w[1], first=r0))
+    return parts
+
+
 def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, confidence=0.95, weights=None,
                      resample=("train", "test"), groups=None, device=0, _engine=None):
     """Bootstrap confidence intervals for the exact attribution (p <= 32; with ``groups=``, g <= 32 groups over p <= 64
@@ -1187,24 +1205,85 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
             engine.boot_load(*data, reg, grouped=True)
             run = functools.partial(engine.boot_groups_run, labels)
         undo.append((engine.boot_free, True))
-        if not fixed:
-            parts = [run(n_boot, seed, w_train, w_test)]
-        else:
-            # a side that is not resampled has weight 1 on every row: the run is cut so that those rows of ones stay small
-            rows = max((n, m)[k] for k in fixed)
-            step = max(1, min(n_boot, BOOT_ONES_BYTES // (8 * rows)))
-            parts = []
-            for r0 in range(0, n_boot, step):
-                nb = min(step, n_boot - r0)
-                w = [None if x is None else x[r0:r0 + nb] for x in (w_train, w_test)]
-                for k in fixed:
-                    w[k] = np.ones((nb, (n, m)[k]))
-                parts.append(run(nb, seed, w[0], w[1], first=r0))
+        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
         rep, r2, *base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(len(parts[0])))
     failed = (binfo & 1).astype(bool) | ~np.isfinite(rep).all(axis=1) | ~np.isfinite(r2)
     for b in base:
         failed |= ~np.isfinite(b)
     res = BootstrapResults.from_replicates(phi, theta, r_squared, rep, r2, failed, confidence, *base)
+    if res.n_failed:
+        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
+                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
+                      "`replicates` and left out of the intervals", RuntimeWarning, stacklevel=2)
+    return res
+
+
+def ls_spa_interactions_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, confidence=0.95,
+                                  weights=None, resample=("train", "test"), groups=None, device=0, _engine=None):
+    """Bootstrap confidence intervals for the exact pairwise interaction values (p <= 32; with ``groups=``, g <= 32 groups
+    over p <= 64 columns).
+
+    ``ls_spa_interactions`` is exact for the rows it was handed, and its entries are second differences of v(K): far
+    noisier under resampling than the attribution.  This call says whether "features 3 and 7 share -0.04 of the R^2"
+    keeps its sign on another draw of the rows.  The point estimate is that call's (``interactions``, ``attribution``,
+    ``theta``, ``r_squared``, by the same path).  Each of the ``n_boot`` replicates is one of ``ls_spa_bootstrap``'s -- a
+    given seed resamples the same rows, and a replicate's attribution is bitwise that call's -- re-attributed by the
+    interaction enumeration on the GPU, the replicates of a launch sharing one grid (include/lsspa.h,
+    lsspa_boot_interactions_run).  Two calls agree bitwise.
+
+    Returns ``InteractionBootstrapResults``: ``replicates`` [n_boot][d][d] in SHAP's convention like ``interactions``,
+    ``attribution_replicates``, ``r_squared_replicates``, and per entry of the matrix ``std_error``, the percentile
+    interval ``lower`` / ``upper`` at ``confidence`` and ``prob_positive``, the share of replicates with Phi_ij > 0;
+    ``n_failed``: replicates whose Gram matrix was not numerically positive definite are NaN and left out, with a
+    RuntimeWarning; more than half of them is a RuntimeError.
+
+    weights, resample: as ``ls_spa_bootstrap`` takes them.
+    groups:   one label per column as ``ls_spa_interactions(groups=)`` takes them; the players are then the g groups
+        (include/lsspa.h, lsspa_boot_groups_interactions_run), every matrix is g x g and sums to the replicate's R^2
+        minus ``baseline_r_squared_replicates``; ``theta`` keeps length p.  Limits: g <= 32 and p <= 64.
+    Fewer than two players, p > 32 without groups, p > 64 or g > 32 with groups raise ValueError."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    n, p = data[0].shape
+    m = data[1].shape[0]
+    labels, d = None, p
+    if groups is not None:
+        if p > GROUPS_MAX_P:
+            raise ValueError(f"ls_spa_interactions_bootstrap(groups=) takes at most p = {GROUPS_MAX_P} columns, the "
+                             f"baseline's included (this problem has p = {p})")
+        labels, d = group_labels(groups, p)
+    elif p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_interactions_bootstrap re-runs the enumeration of all 2^p feature subsets and takes at "
+                         f"most p = {SUBSETS_MAX_P} features (this problem has p = {p}); group the columns (groups=) to "
+                         "at most 32 players")
+    if d < 2:
+        raise ValueError(f"an interaction needs two players (this problem has {d})")
+    w_train, w_test, sides = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
+    n_boot = int(n_boot)
+    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
+    undo = []
+    with _engine_call(_engine, device, undo=undo) as engine:
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        theta, r_squared, info = _load_and_fit(engine, data, reg, False, None)
+        phi, raw, bits = engine.subsets_interactions() if labels is None else engine.groups_interactions(labels)
+        _info_verdict((bits | info) & 1, stacklevel=3)
+        if info & 1:
+            theta, r_squared = _singular_fit(engine, data[1], data[3])
+        if labels is None:
+            engine.boot_load(*data, reg)
+            run = engine.boot_interactions_run
+        else:
+            engine.boot_load(*data, reg, grouped=True)
+            run = functools.partial(engine.boot_groups_interactions_run, labels)
+        undo.append((engine.boot_free, True))
+        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
+        att, index, r2, *base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(len(parts[0])))
+    failed = (binfo & 1).astype(bool) | ~np.isfinite(att).all(axis=1) | ~np.isfinite(index).all(axis=(1, 2)) | ~np.isfinite(r2)
+    for b in base:
+        failed |= ~np.isfinite(b)
+    rep = np.stack([_shap_matrix(a, i) for a, i in zip(att, index)])
+    res = InteractionBootstrapResults.from_replicates(_shap_matrix(phi, raw), phi, theta, r_squared, rep, att, r2, failed,
+                                                      confidence, *base)
     if res.n_failed:
         warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
                       "positive definite (a column constant or collinear on the resampled rows); they are NaN in "

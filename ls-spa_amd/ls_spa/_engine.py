@@ -80,26 +80,30 @@ BOOT_PLAN_FIELDS = ("cb", "ldz", "pairs", "rpw", "rps_train", "rps_test", "slice
                     "block", "n_blocks", "enum_reps", "units", "per", "steps")
 
 
-def debug_boot_plan(R: int, n: int, m: int, p: int, block: int = 0):
+def debug_boot_plan(R: int, n: int, m: int, p: int, block: int = 0, inter: bool = False):
     """Test hook, host only: how a bootstrap run of R replicates on n / m rows at p features is cut (include/lsspa.h,
-    lsspa_debug_boot_plan), as a dict of BOOT_PLAN_FIELDS."""
+    lsspa_debug_boot_plan), as a dict of BOOT_PLAN_FIELDS.  inter: the run of the interaction values
+    (lsspa_debug_boot_inter_plan), whose rep_bytes leave the enumeration's partial table out."""
     out = np.zeros(15, dtype=np.int64)
-    rc = N.load().lsspa_debug_boot_plan(int(R), int(n), int(m), int(p), int(block), out.ctypes.data_as(N._pi64))
+    name = "lsspa_debug_boot_inter_plan" if inter else "lsspa_debug_boot_plan"
+    rc = getattr(N.load(), name)(int(R), int(n), int(m), int(p), int(block), out.ctypes.data_as(N._pi64))
     if rc != N.OK:
-        raise ValueError(f"lsspa_debug_boot_plan: status {rc}")
+        raise ValueError(f"{name}: status {rc}")
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
-def debug_boot_groups_plan(R: int, n: int, m: int, labels, block: int = 0):
+def debug_boot_groups_plan(R: int, n: int, m: int, labels, block: int = 0, inter: bool = False):
     """Test hook, host only: debug_boot_plan for a bootstrap over the groups of columns that labels names (one label per
-    column; include/lsspa.h, lsspa_debug_boot_groups_plan).  ValueError for labels or sizes the library refuses."""
+    column; include/lsspa.h, lsspa_debug_boot_groups_plan).  ValueError for labels or sizes the library refuses.
+    inter: the run of the interaction values (lsspa_debug_boot_groups_inter_plan)."""
     labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
     g = int(labels.max()) + 1 if len(labels) else 0
     out = np.zeros(15, dtype=np.int64)
-    rc = N.load().lsspa_debug_boot_groups_plan(int(R), int(n), int(m), N.iptr(labels), len(labels), g, int(block),
-                                               out.ctypes.data_as(N._pi64))
+    name = "lsspa_debug_boot_groups_inter_plan" if inter else "lsspa_debug_boot_groups_plan"
+    rc = getattr(N.load(), name)(int(R), int(n), int(m), N.iptr(labels), len(labels), g, int(block),
+                                 out.ctypes.data_as(N._pi64))
     if rc != N.OK:
-        raise ValueError(f"lsspa_debug_boot_groups_plan: status {rc}")
+        raise ValueError(f"{name}: status {rc}")
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
@@ -366,6 +370,36 @@ class HipEngine:
                                                     int(first), N.dptr(wa), N.dptr(we), int(block), N.dptr(phi),
                                                     N.dptr(r2), N.dptr(base), N.iptr(info)))
         return phi, r2, base, info
+
+    def boot_interactions_run(self, R: int, seed: int, w_train=None, w_test=None, block: int = 0, first: int = 0):
+        """(phi [R][p], I [R][p][p], r2 [R], info [R]) of replicates first .. first + R - 1: boot_run's replicates with the
+        raw pairwise interaction index of each (include/lsspa.h, lsspa_boot_interactions_run); phi is boot_run's."""
+        dims = getattr(self, "_boot_dims", None)
+        p = dims[0] if dims else 1
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        phi, inter, r2 = np.empty((R, p)), np.empty((R, p, p)), np.empty(R)
+        info = np.zeros(R, dtype=np.int32)
+        self._check(self._lib.lsspa_boot_interactions_run(self._h, int(R), int(seed) & (2 ** 64 - 1), int(first),
+                                                          N.dptr(wa), N.dptr(we), int(block), N.dptr(phi), N.dptr(inter),
+                                                          N.dptr(r2), N.iptr(info)))
+        return phi, inter, r2, info
+
+    def boot_groups_interactions_run(self, labels, R: int, seed: int, w_train=None, w_test=None, block: int = 0,
+                                     first: int = 0):
+        """(phi [R][g], I [R][g][g], r2 [R], r2_base [R], info [R]): boot_groups_run's replicates with the raw interaction
+        index between the groups of each (include/lsspa.h, lsspa_boot_groups_interactions_run)."""
+        labels, g = self._labels(labels)
+        dims = getattr(self, "_boot_dims", None)
+        if dims is not None and len(labels) != dims[0]:
+            raise ValueError(f"labels must have length p = {dims[0]}")
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        n = max(g, 1)
+        phi, inter, r2, base = np.empty((R, n)), np.empty((R, n, n)), np.empty(R), np.empty(R)
+        info = np.zeros(R, dtype=np.int32)
+        self._check(self._lib.lsspa_boot_groups_interactions_run(
+            self._h, N.iptr(labels), g, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa), N.dptr(we), int(block),
+            N.dptr(phi), N.dptr(inter), N.dptr(r2), N.dptr(base), N.iptr(info)))
+        return phi, inter, r2, base, info
 
     def boot_timing(self):
         """Kernel seconds of the last boot_run: counts (or the upload of weights), Gram, enumeration."""

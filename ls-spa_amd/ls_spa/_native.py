@@ -135,6 +135,11 @@ SIGNATURES = {
     "lsspa_boot_groups_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _dbl, _i32, _i32]),
     "lsspa_boot_groups_run": (C.c_int, [_vp, _pi32, _i32, _i64, C.c_uint64, _i64, _pd, _pd, _i64, _pd, _pd, _pd, _pi32]),
     "lsspa_debug_boot_groups_plan": (C.c_int, [_i64, _i64, _i64, _pi32, _i32, _i32, _i64, _pi64]),
+    "lsspa_boot_interactions_run": (C.c_int, [_vp, _i64, C.c_uint64, _i64, _pd, _pd, _i64, _pd, _pd, _pd, _pi32]),
+    "lsspa_boot_groups_interactions_run": (C.c_int, [_vp, _pi32, _i32, _i64, C.c_uint64, _i64, _pd, _pd, _i64, _pd, _pd,
+                                                     _pd, _pd, _pi32]),
+    "lsspa_debug_boot_inter_plan": (C.c_int, [_i64, _i64, _i64, _i32, _i64, _pi64]),
+    "lsspa_debug_boot_groups_inter_plan": (C.c_int, [_i64, _i64, _i64, _pi32, _i32, _i32, _i64, _pi64]),
 }
 
 

@@ -206,3 +206,79 @@ class BootstrapResults:
             pad,
         ]
         return "\n".join(lines)
+
+
+@dataclass
+class InteractionBootstrapResults:
+    """What ``ls_spa_interactions_bootstrap`` returns.  ``interactions`` [d][d], ``attribution``, ``theta`` and
+    ``r_squared`` are the point estimate on the original rows, exactly those of ``ls_spa_interactions``; d is p, or g with
+    ``groups=``.  ``replicates`` [n_boot][d][d] are the bootstrap replicates of the matrix in the same convention (SHAP's:
+    symmetric, half the pairwise index off the diagonal, main effects on it, row i summing to
+    ``attribution_replicates[r][i]``), ``attribution_replicates`` [n_boot][d] and ``r_squared_replicates`` [n_boot] those
+    of the attribution and of R^2; a replicate whose Gram matrix was not numerically positive definite is NaN in all of
+    them and counted in ``n_failed``.  Over the valid replicates, each [d][d]: ``std_error`` (sample standard
+    deviation), ``lower`` / ``upper`` (percentile interval: ``np.quantile`` at alpha = (1 - ``confidence``) / 2 and
+    1 - alpha, numpy's default interpolation) and ``prob_positive``, the share of replicates with Phi_ij > 0 ("is this
+    interaction really negative?" -- a share near 0 says yes).  With ``groups=`` a replicate's matrix sums to its R^2 minus
+    the R^2 of its baseline columns alone, ``baseline_r_squared_replicates`` [n_boot] (zeros without a baseline; None
+    without ``groups=``), and ``theta`` keeps length p."""
+    interactions: np.ndarray
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+    replicates: np.ndarray
+    attribution_replicates: np.ndarray
+    r_squared_replicates: np.ndarray
+    std_error: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    prob_positive: np.ndarray
+    n_failed: int
+    confidence: float = 0.95
+    baseline_r_squared_replicates: np.ndarray | None = None
+
+    @classmethod
+    def from_replicates(cls, interactions, attribution, theta, r_squared, replicates, attribution_replicates,
+                        r_squared_replicates, failed, confidence=0.95, baseline_r_squared_replicates=None):
+        """The summary fields from the replicates (matrices already in SHAP's convention); failed [n_boot]: which
+        replicates to mask.  RuntimeError when more than half of them failed."""
+        rep = np.array(replicates, dtype=np.float64)
+        att = np.array(attribution_replicates, dtype=np.float64)
+        r2 = np.array(r_squared_replicates, dtype=np.float64)
+        failed = np.asarray(failed, dtype=bool)
+        rep[failed] = np.nan
+        att[failed] = np.nan
+        r2[failed] = np.nan
+        base = None
+        if baseline_r_squared_replicates is not None:
+            base = np.array(baseline_r_squared_replicates, dtype=np.float64)
+            base[failed] = np.nan
+        n_failed = int(failed.sum())
+        if 2 * n_failed > len(rep):
+            raise RuntimeError(f"{n_failed} of {len(rep)} bootstrap replicates had a Gram matrix that was not numerically "
+                               "positive definite: no interval can be read from the rest")
+        ok = rep[~failed]
+        alpha = (1.0 - float(confidence)) / 2.0      # the interval is [quantile(alpha), quantile(1 - alpha)]
+        return cls(interactions=np.asarray(interactions), attribution=np.asarray(attribution), theta=np.asarray(theta),
+                   r_squared=float(r_squared), replicates=rep, attribution_replicates=att, r_squared_replicates=r2,
+                   std_error=ok.std(axis=0, ddof=1) if len(ok) > 1 else np.full(rep.shape[1:], np.nan),
+                   lower=np.quantile(ok, alpha, axis=0), upper=np.quantile(ok, 1.0 - alpha, axis=0),
+                   prob_positive=(ok > 0.0).mean(axis=0), n_failed=n_failed, confidence=float(confidence),
+                   baseline_r_squared_replicates=base)
+
+    def __repr__(self):
+        pad = " " * 8
+        inter = np.asarray(self.interactions)
+        off = inter - np.diag(np.diag(inter))
+        lines = [
+            "",
+            f"{pad}d = {np.asarray(self.attribution).size}, {len(self.replicates)} bootstrap replicates"
+            + (f" ({self.n_failed} failed)" if self.n_failed else ""),
+            f"{pad}Out-of-sample R^2 with all features: {self.r_squared:.2f}",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}Largest pairwise interaction: {float(np.abs(off).max()) if off.size else 0.0:.2E}",
+            f"{pad}Largest standard error: {float(np.nanmax(self.std_error)) if np.size(self.std_error) else 0.0:.2E}",
+            pad,
+        ]
+        return "\n".join(lines)

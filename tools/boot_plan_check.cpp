@@ -4,9 +4,13 @@
 // Sweeps R, N, M, p and block over their edges (1, the 16-column block edges, the row limit 2^31 - 1, block requests
 // beyond the memory bound) and checks what the callers rely on: at least one replicate a block, blocks that cover R,
 // the memory bound wherever one replicate fits it, slices that cover the rows, enumeration launches within their bound.
-// Then the same for the grouped planner (boot_groups_plan) up to p = 64, and both planners' refusals.
+// Then the same for the grouped planner (boot_groups_plan) up to p = 64, and both planners' refusals.  The interaction
+// planners (boot_inter_plan, boot_groups_inter_plan) ride the same sweeps: the Gram side is the phi planner's, steps is
+// the one-problem call's cut whatever R and block are, units * enum_reps * steps <= 2^20 (grouped: and the work bound),
+// and block * rep_bytes + table_bytes <= BOOT_BLOCK_BYTES or block == 1.
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "boot_plan.h"
 
@@ -45,6 +49,21 @@ int main() {
             }
             CHECK(P.enum_reps >= 1 && P.enum_reps <= P.block && P.units * (uint64_t)P.enum_reps <= BOOT_SUBSETS_PER_LAUNCH);
             CHECK(P.units * P.per == (1ull << (p < BOOT_LOW ? 0 : p - BOOT_LOW)) && P.steps >= 1 && P.steps <= P.per);
+            CHECK(P.table_bytes == 0);
+            BootPlan I;
+            CHECK(boot_inter_plan(R, N, M, p, block, I) == nullptr);
+            CHECK(I.cb == P.cb && I.ldz == P.ldz && I.pairs == P.pairs && I.rpw == P.rpw);
+            for (int s = 0; s < 2; ++s) CHECK(I.rps[s] == P.rps[s] && I.slices[s] == P.slices[s]);
+            CHECK(I.units == P.units && I.per == P.per);
+            CHECK(I.steps == (I.per < BOOT_SUBSETS_PER_LAUNCH / I.units ? I.per : BOOT_SUBSETS_PER_LAUNCH / I.units));
+            CHECK(I.steps >= 1 && I.steps <= I.per);
+            CHECK(I.block >= 1 && I.block <= R && I.block <= BOOT_MAX_BLOCK && (block == 0 || I.block <= block));
+            CHECK(I.n_blocks >= 1 && (I.n_blocks - 1) * I.block < R && I.n_blocks * I.block >= R);
+            CHECK(I.enum_reps >= 1 && I.enum_reps <= I.block && I.enum_reps <= 65535);
+            CHECK(I.units * (uint64_t)I.enum_reps * I.steps <= BOOT_SUBSETS_PER_LAUNCH);
+            CHECK(I.table_bytes == I.enum_reps * (int64_t)I.units * boot_inter_cols(p) * 8);
+            CHECK(I.block == 1 || I.block * I.rep_bytes + I.table_bytes <= BOOT_BLOCK_BYTES);
+            CHECK(I.rep_bytes >= 8 * (N + M) + 8 * boot_inter_cols(p));
             ++n_ok;
           }
   // The grouped planner (boot_groups_plan): every p up to 64 with layouts of gh high groups, nb baseline and ql low
@@ -79,6 +98,21 @@ int main() {
               // the cut of `per` into launches is the layout's alone: not R's, the block's or the rows'
               CHECK(boot_groups_plan(1, 1, 1, p, L.g, L.gh, L.nb, L.ql, 0, Q) == nullptr && Q.steps == P.steps &&
                     Q.units == P.units && Q.per == P.per);
+              CHECK(P.table_bytes == 0);
+              BootPlan I;
+              CHECK(boot_groups_inter_plan(R, N, M, p, L.g, L.gh, L.nb, L.ql, block, I) == nullptr);
+              CHECK(I.cb == P.cb && I.ldz == P.ldz && I.pairs == P.pairs && I.rpw == P.rpw);
+              for (int s = 0; s < 2; ++s) CHECK(I.rps[s] == P.rps[s] && I.slices[s] == P.slices[s]);
+              CHECK(I.units == P.units && I.per == P.per && I.steps == P.steps);
+              CHECK(I.block >= 1 && I.block <= R && I.block <= BOOT_MAX_BLOCK && (block == 0 || I.block <= block));
+              CHECK(I.n_blocks >= 1 && (I.n_blocks - 1) * I.block < R && I.n_blocks * I.block >= R);
+              CHECK(I.enum_reps >= 1 && I.enum_reps <= I.block && I.enum_reps <= 65535);
+              CHECK(I.units * (uint64_t)I.enum_reps * I.steps <= BOOT_SUBSETS_PER_LAUNCH);
+              const uint64_t mrows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(p - L.nb - L.ql + 1) / 2;
+              CHECK(I.enum_reps == 1 ||
+                    I.units * (uint64_t)I.enum_reps * I.steps * mrows * mrows <= BOOT_GROUPS_WORK_PER_LAUNCH);
+              CHECK(I.table_bytes == I.enum_reps * (int64_t)I.units * boot_inter_cols(L.g) * 8);
+              CHECK(I.block == 1 || I.block * I.rep_bytes + I.table_bytes <= BOOT_BLOCK_BYTES);
               ++n_ok;
             }
           }
@@ -92,6 +126,29 @@ int main() {
     CHECK(boot_groups_plan(1, 1, 1, 8, 8, 1, 0, 6, 0, P) && boot_groups_plan(1, 1, 1, 8, 2, 1, 8, 1, 0, P));
     CHECK(boot_groups_plan(0, 1, 1, 8, 2, 1, 0, 1, 0, P) && boot_groups_plan(1, 1, 1ll << 31, 8, 2, 1, 0, 1, 0, P));
     CHECK(boot_groups_plan(1, 1, 1, 8, 2, 1, 0, 1, -1, P) && !boot_groups_plan(1, 1, 1, 8, 2, 1, 0, 1, 0, P));
+    CHECK(boot_groups_inter_plan(1, 1, 1, 65, 1, 1, 0, 0, 0, P) && boot_groups_inter_plan(1, 1, 1, 40, 33, 27, 0, 6, 0, P));
+    CHECK(boot_groups_inter_plan(0, 1, 1, 8, 2, 1, 0, 1, 0, P) && boot_groups_inter_plan(1, 1, 1, 8, 2, 1, 0, 1, -1, P));
+    CHECK(!boot_groups_inter_plan(1, 1, 1, 8, 2, 1, 0, 1, 0, P));
+    CHECK(boot_inter_plan(0, 1, 1, 1, 0, P) && boot_inter_plan(1, 0, 1, 1, 0, P) && boot_inter_plan(1, 1, 1ll << 31, 1, 0, P));
+    CHECK(boot_inter_plan(1, 1, 1, 33, 0, P) && boot_inter_plan(1, 1, 1, 0, 0, P) && boot_inter_plan(1, 1, 1, 1, -1, P));
+    // group layouts up to (g, p) = (32, 64): 26 high groups of one or two columns beside six low singletons
+    for (int g = 7; g <= 32; ++g) {
+      p = 64;
+      R = 1000;
+      N = M = 100000;
+      for (int64_t blk : {0ll, 1ll, 3ll}) {
+        block = blk;
+        BootPlan I, Q;
+        CHECK(boot_groups_inter_plan(R, N, M, p, g, g - 6, 0, 6, block, I) == nullptr);
+        CHECK(boot_groups_plan(1, 1, 1, p, g, g - 6, 0, 6, 0, Q) == nullptr && Q.steps == I.steps && Q.units == I.units);
+        CHECK(I.units * (uint64_t)I.enum_reps * I.steps <= BOOT_SUBSETS_PER_LAUNCH && I.enum_reps >= 1);
+        CHECK(I.block == 1 || I.block * I.rep_bytes + I.table_bytes <= BOOT_BLOCK_BYTES);
+        ++n_ok;
+      }
+    }
+    // the table does not cut a block to a handful of replicates at large p
+    R = 1000; N = M = 10000; block = 0; p = 32;
+    CHECK(boot_inter_plan(R, N, M, p, block, P) == nullptr && P.enum_reps == 1 && P.block >= 100);
   }
   BootPlan P;
   const bool refused = boot_plan(0, 1, 1, 1, 0, P) && boot_plan(1, 0, 1, 1, 0, P) && boot_plan(1, 1, 1ll << 31, 1, 0, P) &&
