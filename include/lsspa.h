@@ -269,6 +269,50 @@ int lsspa_debug_boot_inter_plan(int64_t R, int64_t N, int64_t M, int32_t p, int6
 int lsspa_debug_boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p,
                                        int32_t g, int64_t block, int64_t* plan15);
 
+/* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
+ * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the
+ * 2^p subsets are enumerated once for every 8 responses: a wave sweeps a high subset's pivots out of [G | g_r ...] with
+ * eight right-hand sides, and only the two 6-long solves and the quadratic form are per response (csrc/k_multi.hip).
+ * One Gram pass per side over Z = [X | Y], p + m columns, gives
+ *   G = S_tr[:p,:p] / N + reg I,  g_r = S_tr[:p,p+r] / N,  H = S_te[:p,:p],  h_r = S_te[:p,p+r],  ||y_r||^2 = S_te[p+r][p+r];
+ * H is always a Gram (M < p works).  fp64 throughout.
+ *   lsspa_multi_load        : X [N][ld], Y [N][ldy] (m columns used) of both sides, dtype and location as lsspa_reduce's.
+ *                     p > 32, m < 1 or p + m > 32767 is LSSPA_ERR_ARG naming the limit; so is a column of Y_test that
+ *                     is identically zero (or NaN), which lsspa_reduce refuses for one y.  Both sides are on the device
+ *                     whole for the length of the call.  The loaded problem, the running statistics and the state of
+ *                     lsspa_subsets_*, lsspa_groups_* and lsspa_boot_* are not touched, now or by any call below.
+ *   lsspa_multi_set_reduced : the same from the Gram form (host): G, H [p][p], g, h [m][p], yy [m].
+ *   lsspa_multi_shapley     : responses first .. first + count - 1 into phi [count][p] (out of range: LSSPA_ERR_ARG).
+ *                     block: responses enumerated together, 0 = as many as 256 MB of partial table hold (whole chunks
+ *                     of 8), a larger request is cut to that.  info: one word -- G is shared, so a failed pivot
+ *                     (LSSPA_INFO_NOT_PD) concerns every response.  A response's bits depend on G, H and its own g, h,
+ *                     yy alone: not on its place among the responses, on the others, on block or on first / count, and
+ *                     two calls agree bitwise (no floating-point atomics, sums in a fixed order, a unit's high subsets
+ *                     cut into launches by p alone).  Launches are bounded as lsspa_subsets_shapley's.
+ *   lsspa_multi_get_gram    : the reduced form back (any pointer may be NULL).
+ *   lsspa_multi_timing      : device ms of the last load's two Gram passes and of the last lsspa_multi_shapley's
+ *                     enumeration launches, its longest launch and their number (any pointer may be NULL).
+ *   lsspa_multi_free        : frees the responses and the buffers.
+ *   lsspa_debug_multi_values : test hook -- v [n][m], v[i][r] = v_r(masks[i]) (bit j = feature j; masks < 2^p) by the
+ *                     enumeration's own device code; a failed pivot is LSSPA_ERR_STATE.
+ * LSSPA_ERR_STATE before a load; LSSPA_ERR_NOMEM when device memory runs out.
+ * Measured on one MI355X (tools/multi_time.py, on top of commit 5f361f6): the enumeration costs 1.36 ms a response at
+ * p = 24 and 25.4 ms at p = 28 against lsspa_subsets_shapley's 4.6 - 4.7 ms and 87.1 ms (3.4 x), 0.0081 ms against
+ * 0.038 ms at p = 16 with m = 64 (4.7 x); the longest launch 14.7 ms at p = 28 (DESIGN.md has the tables). */
+int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
+                     int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M,
+                     int32_t p, int32_t m, double reg, int32_t dtype, int32_t location);
+int lsspa_multi_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* G /* [p][p] */,
+                            const double* g /* [m][p] */, const double* H /* [p][p] */, const double* h /* [m][p] */,
+                            const double* yy /* [m] */);
+int lsspa_multi_shapley(lsspa_ctx* ctx, int64_t first, int64_t count, int64_t block, double* phi /* [count][p] */,
+                        int32_t* info);
+int lsspa_multi_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy);
+int lsspa_multi_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms,
+                       int64_t* launches);
+int lsspa_multi_free(lsspa_ctx* ctx);
+int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v /* [n][m] */);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

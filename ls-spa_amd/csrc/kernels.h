@@ -392,6 +392,30 @@ hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, u
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 
+// Exact attribution of many responses at once (k_multi.hip), p <= MULTI_MAX_P, fp64: launch_subsets_enum's units, steps
+// and weights with MULTI_RB responses carried by a wave per pass.  The `count` responses behind g, h, inv_yy are cut
+// into chunks of MULTI_RB, the launch's second grid dimension; the partial table is part [chunks][MULTI_RB][units][p + 1]
+// (rows of slots beyond count are never written), which launch_subsets_reduce sums with reps = chunks * MULTI_RB.
+constexpr int MULTI_MAX_P = SUBSETS_MAX_P, MULTI_RB = 8;
+struct MultiArgs {
+  const double* G;         // [p][ldg] training Gram, shared by the responses
+  const double* H;         // [p][ldh] test Gram
+  int64_t ldg, ldh;
+  const double* g;         // [count][p] per response
+  const double* h;         // [count][p]
+  const double* inv_yy;    // [count] 1 / ||y_r||^2
+  const double* w;         // SubsetArgs::w (its first two rows are read)
+  int p, q, count;
+  double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
+  uint64_t per;            // high subsets per unit
+  double* part;
+  int32_t* info;           // one word: G is shared
+};
+hipError_t launch_multi_enum(const MultiArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
+// vals [n][m], column r0 + r = v_r(masks[i]) of the launch's response r by the enumeration's own device code (test hook)
+hipError_t launch_multi_debug(const MultiArgs& a, const uint64_t* masks, int64_t n, double* vals, int m, int r0,
+                              hipStream_t st);
+
 // Bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp), p <= SUBSETS_MAX_P -- over groups of columns
 // p <= GROUPS_MAX_P (cb = 4, 5) --, fp64.  Z = [X | y] of one side
 // lives on the device as [n][ldz], ldz = 16 cb, cb = ceil((p + 1) / 16), columns beyond p zero.  A BLOCK of replicates

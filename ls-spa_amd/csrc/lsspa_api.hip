@@ -89,6 +89,26 @@ struct BootWork {
   }
 };
 
+// What the multi-response enumeration keeps (lsspa_multi_load / lsspa_multi_set_reduced .. lsspa_multi_free): the shared
+// G and H, one g, h and 1 / ||y||^2 per response, the buffers of one block of responses and the last call's timing.
+// Nothing of the loaded problem, the sampling path, the exact enumerations' or the bootstrap's state is in here.
+struct MultiWork {
+  bool loaded = false;
+  int p = 0, m = 0;
+  DevBuf<double> G, H, g, h, inv_yy;       // [p][p], [p][p], [m][p], [m][p], [m]
+  DevBuf<double> w, part, out, vals;       // Shapley weights, partial table of a block, its column sums, debug values
+  DevBuf<uint64_t> masks;
+  DevBuf<int32_t> info;
+  std::vector<double> Gh, Hh, gh, hh, yyh; // the same on the host (lsspa_multi_get_gram)
+  double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
+  int64_t launches = 0;
+  void release() {
+    dev_free(G); dev_free(H); dev_free(g); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(part); dev_free(out);
+    dev_free(vals); dev_free(masks); dev_free(info);
+    loaded = false;
+  }
+};
+
 }  // namespace
 
 // One lane = everything a batch of orderings needs while its kernels run: work matrices, solve results, staged
@@ -219,6 +239,7 @@ struct lsspa_ctx {
   // exact attribution by subset enumeration (lsspa_subsets_shapley) and over groups of columns (lsspa_groups_shapley)
   ExactWork sub, grp;
   BootWork boot;                 // bootstrap of the exact attribution (lsspa_boot_*)
+  MultiWork multi;               // exact attribution of many responses at once (lsspa_multi_*)
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -1223,6 +1244,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->sub.release();
   ctx->grp.release();
   ctx->boot.release();
+  ctx->multi.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
   dev_free(ctx->pr_delta); dev_free(ctx->pr_lifts); dev_free(ctx->pr_pos); dev_free(ctx->pr_perms);
@@ -4119,6 +4141,365 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
     if (wsum) HIPCHK(hipMemcpyAsync(wsum + b0, B.wsum.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+}  // extern "C"
+
+// ---- exact attribution of many responses at once (k_multi.hip) ------------------------------------------------------
+// One reduction of Z = [X | Y] per side gives the shared G, H and every response's g_r, h_r, ||y_r||^2; the enumeration
+// then runs blocks of responses, a block's chunks of MULTI_RB as the second grid dimension, into a partial table
+// [chunks][MULTI_RB][units][p + 1] that launch_subsets_reduce sums in fixed order.  How often a unit's row is added to
+// (the steps per launch) depends on p alone, so a response's bits do not depend on the block it runs in.
+namespace {
+
+// (high subset, chunk) passes one enumeration launch takes at most, over all units and chunks.  A pass carries MULTI_RB
+// responses and costs 2.7 passes of k_subsets.hip (p = 28: 14.7 ms per 2^18 against 21.8 ms per 2^20; DESIGN.md, "Many
+// responses at once"), whose launches take SUBSETS_PER_LAUNCH = 2^20 of them in ~35 ms at p = 32: a quarter of that
+// keeps a launch inside the same bound (about 24 ms at p = 32).
+constexpr uint64_t MULTI_PASSES_PER_LAUNCH = SUBSETS_PER_LAUNCH / 4;
+constexpr size_t MULTI_TABLE_BYTES = 256ull << 20;     // the partial table of a block of responses stays inside this
+constexpr int64_t MULTI_MAX_COLS = 32767;              // p + m
+constexpr int64_t MULTI_MAX_CHUNKS = 8191;             // chunks * MULTI_RB is launch_subsets_reduce's replicate count
+
+int multi_limits(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
+  char msg[200];
+  if (p < 1 || p > MULTI_MAX_P) {
+    snprintf(msg, sizeof msg, "%s enumerates all 2^p feature subsets and takes 1 <= p <= %d features (%lld given)", name,
+             MULTI_MAX_P, (long long)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (m < 1 || p + m > MULTI_MAX_COLS) {
+    snprintf(msg, sizeof msg, "%s takes m >= 1 responses with p + m <= %lld (p = %lld, m = %lld given)", name,
+             (long long)MULTI_MAX_COLS, (long long)p, (long long)m);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+int multi_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->multi.loaded)
+    return ctx->fail(LSSPA_ERR_STATE, "no responses loaded (lsspa_multi_load or lsspa_multi_set_reduced comes first)");
+  return LSSPA_OK;
+}
+
+// responses enumerated together: as many as MULTI_TABLE_BYTES hold, whole chunks, at least one chunk
+int64_t multi_block_max(int p) {
+  const uint64_t units = exact_units(1ull << (p - subsets_low_features(p)));
+  const int64_t fit = (int64_t)(MULTI_TABLE_BYTES / (units * (uint64_t)(p + 1) * sizeof(double)));
+  const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(fit / MULTI_RB, MULTI_MAX_CHUNKS));
+  return chunks * MULTI_RB;
+}
+
+// the reduced form (host arrays: G, H [p][p], g, h [m][p], yy [m]) into the context
+int multi_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, const double* H, const double* h,
+                const double* yy) {
+  MultiWork& W = ctx->multi;
+  W.loaded = false;
+  char msg[160];
+  for (int r = 0; r < m; ++r)
+    if (!(yy[r] > 0.0) || !std::isfinite(yy[r])) {
+      snprintf(msg, sizeof msg, "column %d of Y_test is identically zero (or NaN)", r);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  const size_t pp = (size_t)p * p, mp = (size_t)m * p;
+  W.Gh.assign(G, G + pp);
+  W.Hh.assign(H, H + pp);
+  W.gh.assign(g, g + mp);
+  W.hh.assign(h, h + mp);
+  W.yyh.assign(yy, yy + m);
+  std::vector<double> inv((size_t)m);
+  for (int r = 0; r < m; ++r) inv[r] = 1.0 / yy[r];
+  TRY(dev_alloc(ctx, W.G, pp));
+  TRY(dev_alloc(ctx, W.H, pp));
+  TRY(dev_alloc(ctx, W.g, mp));
+  TRY(dev_alloc(ctx, W.h, mp));
+  TRY(dev_alloc(ctx, W.inv_yy, (size_t)m));
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the buffers
+  HIPCHK(hipMemcpy(W.G.ptr, G, sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.H.ptr, H, sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.g.ptr, g, sizeof(double) * mp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.h.ptr, h, sizeof(double) * mp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.inv_yy.ptr, inv.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+  W.p = p;
+  W.m = m;
+  W.loaded = true;
+  return LSSPA_OK;
+}
+
+// The kernels' view of the loaded responses first .. first + count - 1: weights on the device, a cleared info word
+int multi_args(lsspa_ctx* ctx, int64_t first, int64_t count, MultiArgs& a) {
+  MultiWork& W = ctx->multi;
+  const int p = W.p;
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  double w[EXACT_W_ROWS * WR];
+  exact_weight_table(p, w);
+  TRY(dev_alloc(ctx, W.w, EXACT_W_ROWS * WR));
+  TRY(dev_alloc(ctx, W.info, 8));
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read W.w; the copy is from a host frame
+  HIPCHK(hipMemcpy(W.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
+  a = MultiArgs{};
+  a.G = W.G.ptr;
+  a.H = W.H.ptr;
+  a.ldg = a.ldh = p;
+  a.g = W.g.ptr + (size_t)first * p;
+  a.h = W.h.ptr + (size_t)first * p;
+  a.inv_yy = W.inv_yy.ptr + first;
+  a.w = W.w.ptr;
+  a.p = p;
+  a.q = subsets_low_features(p);
+  a.count = (int)count;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.info = W.info.ptr;
+  return LSSPA_OK;
+}
+
+// frees what a load borrows from the device on every way out
+struct MultiScratch {
+  DevBuf<char> zx, yl;
+  DevBuf<double> C;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~MultiScratch() {
+    dev_free(zx);
+    dev_free(yl);
+    dev_free(C);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
+                     int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M,
+                     int32_t p, int32_t m, double reg, int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_limits(ctx, "lsspa_multi_load", p, m));
+  if (!X_train || !Y_train || !X_test || !Y_test || N < 1 || M < 1 || ld_train < p || ld_test < p || ldy_train < m ||
+      ldy_test < m || !(reg >= 0.0) || !std::isfinite(reg) || (dtype != LSSPA_F64 && dtype != LSSPA_F32) ||
+      (location != LSSPA_HOST && location != LSSPA_DEVICE))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_load: NULL array, N or M < 1, ld < p, ldy < m, reg not finite and >= 0, "
+                                    "or bad dtype / location");
+  HIPCHK(hipSetDevice(ctx->device));
+  MultiWork& W = ctx->multi;
+  W.loaded = false;
+  const size_t es = dtype == LSSPA_F32 ? 4 : 8;
+  const int cols = p + m - 1;                      // launch_gram's "features": Z = [X | Y] has cols + 1 columns
+  const size_t P1pad = (size_t)round_up(p + m, 128);
+  const hipMemcpyKind kind = location == LSSPA_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  MultiScratch S;
+  TRY(dev_alloc(ctx, S.C, P1pad * P1pad));
+  for (hipEvent_t& e : S.ev) HIPCHK(hipEventCreate(&e));
+  const void* X[2] = {X_train, X_test};
+  const void* Y[2] = {Y_train, Y_test};
+  const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test}, ldy[2] = {ldy_train, ldy_test};
+  std::vector<double> rows[2], cross[2], yy((size_t)m);
+  W.gram_ms = 0.0;
+  for (int s = 0; s < 2; ++s) {
+    // [X | Y[:, :m-1]] as launch_gram's X and Y's last column as its y
+    TRY(dev_alloc(ctx, S.zx, (size_t)n[s] * cols * es));
+    TRY(dev_alloc(ctx, S.yl, (size_t)n[s] * es));
+    HIPCHK(hipMemcpy2DAsync(S.zx.ptr, (size_t)cols * es, X[s], (size_t)ld[s] * es, (size_t)p * es, (size_t)n[s], kind,
+                            ctx->stream));
+    if (m > 1)
+      HIPCHK(hipMemcpy2DAsync(S.zx.ptr + (size_t)p * es, (size_t)cols * es, Y[s], (size_t)ldy[s] * es,
+                              (size_t)(m - 1) * es, (size_t)n[s], kind, ctx->stream));
+    HIPCHK(hipMemcpy2DAsync(S.yl.ptr, es, (const char*)Y[s] + (size_t)(m - 1) * es, (size_t)ldy[s] * es, es,
+                            (size_t)n[s], kind, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.C.ptr, 0, sizeof(double) * P1pad * P1pad, ctx->stream));
+    HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+    TRY(gram_side(ctx, S.zx.ptr, S.yl.ptr, n[s], cols, cols, dtype == LSSPA_F32, S.C.ptr));
+    HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+    // launch_gram leaves the lower part (row >= column) of a diagonal tile: G, H from rows < p, the responses' sums from
+    // the first p columns of rows p .. p + m - 1
+    rows[s].resize((size_t)p * P1pad);
+    cross[s].resize((size_t)m * p);
+    HIPCHK(hipMemcpyAsync(rows[s].data(), S.C.ptr, sizeof(double) * p * P1pad, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpy2DAsync(cross[s].data(), sizeof(double) * p, S.C.ptr + (size_t)p * P1pad, sizeof(double) * P1pad,
+                            sizeof(double) * p, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    if (s == 1)
+      HIPCHK(hipMemcpy2DAsync(yy.data(), sizeof(double), S.C.ptr + (size_t)p * P1pad + p, sizeof(double) * (P1pad + 1),
+                              sizeof(double), (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+    W.gram_ms += ms;
+  }
+  const double scale = 1.0 / (double)N;
+  std::vector<double> G((size_t)p * p), H((size_t)p * p), g((size_t)m * p), h((size_t)m * p);
+  for (int a = 0; a < p; ++a) {
+    for (int b = 0; b < p; ++b) {
+      const size_t lo = a >= b ? a * P1pad + b : b * P1pad + a;
+      G[(size_t)a * p + b] = rows[0][lo] * scale + (a == b ? reg : 0.0);
+      H[(size_t)a * p + b] = rows[1][lo];
+    }
+    for (int r = 0; r < m; ++r) {
+      g[(size_t)r * p + a] = cross[0][(size_t)r * p + a] * scale;
+      h[(size_t)r * p + a] = cross[1][(size_t)r * p + a];
+    }
+  }
+  return multi_store(ctx, p, m, G.data(), g.data(), H.data(), h.data(), yy.data());
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* G, const double* g, const double* H,
+                            const double* h, const double* yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_limits(ctx, "lsspa_multi_set_reduced", p, m));
+  if (!G || !g || !H || !h || !yy) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_set_reduced: NULL array");
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->multi.gram_ms = 0.0;
+  return multi_store(ctx, p, m, G, g, H, h, yy);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_shapley(lsspa_ctx* ctx, int64_t first, int64_t count, int64_t block, double* phi, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_need_loaded(ctx));
+  MultiWork& W = ctx->multi;
+  const int p = W.p;
+  if (!phi) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_shapley: phi is NULL");
+  if (first < 0 || count < 1 || first > W.m || count > W.m - first || block < 0) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "lsspa_multi_shapley: responses first = %lld, count = %lld must lie inside the %d loaded, "
+             "count >= 1, block >= 0", (long long)first, (long long)count, W.m);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t bmax = multi_block_max(p);
+  const int64_t blk = std::min<int64_t>(block == 0 ? bmax : std::min(block, bmax), count);
+  const int q = subsets_low_features(p);
+  const uint64_t n_high = 1ull << (p - q);
+  const uint64_t units = exact_units(n_high), per = n_high / units;
+  // steps per launch by p alone; the chunks of a launch make up the rest of its bound
+  const uint64_t steps = std::min(per, std::max<uint64_t>(1, MULTI_PASSES_PER_LAUNCH / units));
+  const int64_t chunks_per_launch = (int64_t)std::max<uint64_t>(1, MULTI_PASSES_PER_LAUNCH / (units * steps));
+  const size_t c = (size_t)p + 1;
+  const int64_t max_chunks = (blk + MULTI_RB - 1) / MULTI_RB;
+  TRY(dev_alloc(ctx, W.part, (size_t)max_chunks * MULTI_RB * units * c));
+  TRY(dev_alloc(ctx, W.out, (size_t)max_chunks * MULTI_RB * c));
+  MultiArgs a;
+  TRY(multi_args(ctx, first, count, a));
+  a.per = per;
+  std::vector<double> out((size_t)max_chunks * MULTI_RB * c);
+  std::vector<hipEvent_t> ev;
+  Events guard{ev};
+  W.enum_ms = W.max_launch_ms = 0.0;
+  W.launches = 0;
+  for (int64_t b0 = 0; b0 < count; b0 += blk) {
+    const int64_t nb = std::min(blk, count - b0);
+    const int64_t chunks = (nb + MULTI_RB - 1) / MULTI_RB;
+    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)chunks * MULTI_RB * units * c, ctx->stream));
+    const size_t e0 = ev.size();
+    ev.push_back(nullptr);
+    HIPCHK(hipEventCreate(&ev.back()));
+    HIPCHK(hipEventRecord(ev.back(), ctx->stream));
+    for (int64_t c0 = 0; c0 < chunks; c0 += chunks_per_launch) {
+      MultiArgs l = a;
+      const int64_t r0 = b0 + c0 * MULTI_RB;                 // the launch's first response, among those of the call
+      l.g = a.g + (size_t)r0 * p;
+      l.h = a.h + (size_t)r0 * p;
+      l.inv_yy = a.inv_yy + r0;
+      l.count = (int)std::min<int64_t>(chunks_per_launch * MULTI_RB, b0 + nb - r0);
+      l.part = W.part.ptr + (size_t)c0 * MULTI_RB * units * c;
+      for (uint64_t s0 = 0; s0 < per; s0 += steps) {
+        HIPCHK(launch_multi_enum(l, units, s0, std::min(per, s0 + steps), ctx->stream));
+        ev.push_back(nullptr);
+        HIPCHK(hipEventCreate(&ev.back()));
+        HIPCHK(hipEventRecord(ev.back(), ctx->stream));
+      }
+    }
+    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, (int)c, W.out.ptr, ctx->stream, (int)(chunks * MULTI_RB)));
+    HIPCHK(hipMemcpyAsync(out.data(), W.out.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int64_t r = 0; r < nb; ++r)
+      for (int j = 0; j < p; ++j) phi[(size_t)(b0 + r) * p + j] = out[(size_t)r * c + j] - out[(size_t)r * c + p];
+    for (size_t k = e0; k + 1 < ev.size(); ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      W.enum_ms += ms;
+      W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
+      ++W.launches;
+    }
+    for (hipEvent_t& e : ev) {
+      (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    ev.clear();
+  }
+  int32_t bits = 0;
+  HIPCHK(hipMemcpy(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost));
+  if (info) *info = bits;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_need_loaded(ctx));
+  const MultiWork& W = ctx->multi;
+  if (G) std::copy(W.Gh.begin(), W.Gh.end(), G);
+  if (g) std::copy(W.gh.begin(), W.gh.end(), g);
+  if (H) std::copy(W.Hh.begin(), W.Hh.end(), H);
+  if (h) std::copy(W.hh.begin(), W.hh.end(), h);
+  if (yy) std::copy(W.yyh.begin(), W.yyh.end(), yy);
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms,
+                       int64_t* launches) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (gram_ms) *gram_ms = ctx->multi.gram_ms;
+  if (enum_ms) *enum_ms = ctx->multi.enum_ms;
+  if (max_launch_ms) *max_launch_ms = ctx->multi.max_launch_ms;
+  if (launches) *launches = ctx->multi.launches;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_multi_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->multi.release();
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_need_loaded(ctx));
+  MultiWork& W = ctx->multi;
+  if (n < 0 || (n > 0 && (!masks || !v))) return ctx->fail(LSSPA_ERR_ARG, "masks / v NULL or n < 0");
+  const uint64_t full = (1ull << W.p) - 1ull;     // p <= 32 here
+  for (int64_t i = 0; i < n; ++i)
+    if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a feature beyond p");
+  if (n == 0) return LSSPA_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const int m = W.m;
+  MultiArgs a;
+  TRY(multi_args(ctx, 0, m, a));
+  TRY(dev_alloc(ctx, W.masks, (size_t)n));
+  TRY(dev_alloc(ctx, W.vals, (size_t)n * m));
+  HIPCHK(hipMemcpy(W.masks.ptr, masks, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(launch_multi_debug(a, W.masks.ptr, n, W.vals.ptr, m, 0, ctx->stream));
+  HIPCHK(hipMemcpyAsync(v, W.vals.ptr, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToHost, ctx->stream));
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (bits & LSSPA_INFO_NOT_PD) return ctx->fail(LSSPA_ERR_STATE, "a subset's Gram matrix is not positive definite");
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

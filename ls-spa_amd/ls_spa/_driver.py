@@ -31,8 +31,8 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, SampledInteractionResults,
-                       ShapleyResults, validate_data)
+from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiResponseResults,
+                       SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -777,7 +777,8 @@ def _engine_call(engine, device, comm=None, undo=(), lap=lambda key=None: None):
                         engine.close()     # a kept engine an exception went through is not trusted with another call
                     else:
                         engine.set_flags(0)
-                        engine.history_enable(0)      # (the lanes stay as they are: the next call sets what it needs)
+                        if engine.p:                  # (no problem loaded -- ls_spa_multi on a fresh engine --: no history)
+                            engine.history_enable(0)  # (the lanes stay as they are: the next call sets what it needs)
         finally:
             if lock is not None:
                 lock.release()
@@ -1090,6 +1091,79 @@ def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, groups=None
     return _ls_spa_subsets(*data, reg, perms=None, return_attribution_history=False,
                            device=device, row_sharded=row_sharded, checkpoint=None, comm=comm, engine=_engine,
                            groups=groups, interactions=True)
+
+
+MULTI_MAX_COLS = 32767     # include/lsspa.h, lsspa_multi_load: p + m
+
+
+def _multi_fit(G, g, H, h, yy):
+    """(theta [m][p], r_squared [m], singular) of the full model of every response from the reduced form: one host
+    Cholesky factor of the p x p G, a solve per response (what lsspa_boot_run does for a replicate's R^2).  singular: G
+    has no Cholesky factor, or a pivot of it fails the engine's relative test (16 p eps); theta is then the solution of
+    minimal norm, as ls_spa's for a single y."""
+    p = G.shape[0]
+    try:
+        L = np.linalg.cholesky(G)
+        singular = bool(np.any(np.diag(L) ** 2 <= 16.0 * p * np.finfo(float).eps * np.diag(G)))
+    except np.linalg.LinAlgError:
+        singular = True
+    if singular:
+        theta = np.stack([_min_norm_theta(G, gr) for gr in g])
+    else:
+        theta = np.linalg.solve(L.T, np.linalg.solve(L, g.T)).T
+    r2 = (2.0 * np.einsum("rj,rj->r", theta, h) - np.einsum("ri,ij,rj->r", theta, H, theta)) / yy
+    return np.ascontiguousarray(theta), r2, singular
+
+
+def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, device=0, _engine=None):
+    """Exact Shapley attribution of many responses on one design matrix (p <= 32).
+
+    ``Y_train`` is [N][m] and ``Y_test`` [M][m] (a one-dimensional y counts as m = 1): the same features explain m
+    targets -- a multi-output ridge model, one model per asset, gene or sensor, the permuted-y columns of a
+    significance test.  Row r of the result is what ``ls_spa(X_train, X_test, Y_train[:, r], Y_test[:, r], reg,
+    method='subsets')`` returns, but the rows of X are reduced once (one Gram pass per side over [X | Y]) and the 2^p
+    subsets are enumerated once for every eight responses instead of once each: the elimination of a subset's
+    features and the test-side products do not depend on y (include/lsspa.h, lsspa_multi_shapley).  fp64 throughout; a
+    response's row is bitwise the same whatever the other columns are and wherever it stands among them.
+
+    Returns ``MultiResponseResults``: ``attribution`` [m][p], ``theta`` [m][p] (the full-model coefficients of each
+    response) and ``r_squared`` [m]; row r of ``attribution`` sums to ``r_squared[r]``.
+
+    Shapes that do not fit raise ``SizeIncompatible``; p > 32 or p + m > 32767 ValueError naming the limit, before any
+    GPU work.  As for a single y, a column of ``Y_test`` that is identically zero is a ValueError, and a Gram matrix
+    that is not numerically positive definite a RuntimeWarning (it is shared, so it concerns every response); theta is
+    then the solution of minimal norm.  M < p works."""
+    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
+    Y_train, Y_test = np.asarray(Y_train), np.asarray(Y_test)
+    if X_train.ndim != 2 or X_test.ndim != 2:
+        raise ValueError("X_train and X_test must be two-dimensional")
+    if Y_train.ndim == 1:
+        Y_train = Y_train[:, None]
+    if Y_test.ndim == 1:
+        Y_test = Y_test[:, None]
+    if Y_train.ndim != 2 or Y_test.ndim != 2:
+        raise ValueError("Y_train and Y_test must be [rows][m] (or one-dimensional for one response)")
+    if Y_train.shape[1] != Y_test.shape[1]:
+        raise SizeIncompatible("Y_train and Y_test should have the same number of columns (responses).")
+    validate_data(X_train, X_test, Y_train, Y_test)
+    p, m = X_train.shape[1], Y_train.shape[1]
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_multi enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} "
+                         f"features (this problem has p = {p}); use a sampling method per response")
+    if p < 1 or m < 1 or X_test.shape[0] < 1:
+        raise ValueError(f"ls_spa_multi needs p >= 1 features, m >= 1 responses and M >= 1 test rows "
+                         f"(p = {p}, m = {m}, M = {X_test.shape[0]})")
+    if p + m > MULTI_MAX_COLS:
+        raise ValueError(f"ls_spa_multi takes p + m <= {MULTI_MAX_COLS} columns of [X | Y] (p = {p}, m = {m}); "
+                         "cut the responses into several calls")
+    undo = []
+    with _engine_call(_engine, device, undo=undo) as engine:
+        undo.append((engine.multi_free, True))
+        engine.multi_load(X_train, X_test, Y_train, Y_test, reg)
+        phi, bits = engine.multi_shapley()
+        theta, r_squared, singular = _multi_fit(*engine.multi_gram())
+    _info_verdict((bits | int(singular)) & 1, stacklevel=2)
+    return MultiResponseResults(attribution=phi, theta=theta, r_squared=r_squared)
 
 
 BOOT_ONES_BYTES = 64 << 20     # ls_spa_bootstrap: host bytes of the unit weights of a side that is not resampled

@@ -422,6 +422,70 @@ class HipEngine:
                                                      N.dptr(ws)))
         return Sa, Se, ws
 
+    # ---- exact attribution of many responses at once (p <= 32) -----------------------------
+    MULTI_RB = 8      # responses a wave carries per pass (csrc/kernels.h)
+
+    def multi_load(self, X_train, X_test, Y_train, Y_test, reg: float):
+        """One Gram pass per side over [X | Y] (Y_train [N][m], Y_test [M][m]) for multi_shapley (include/lsspa.h,
+        lsspa_multi_load); the loaded problem is not touched."""
+        dt = np.float32 if (X_train.dtype == np.float32 and X_test.dtype == np.float32) else np.float64
+        Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
+        Ya, Ye = np.ascontiguousarray(Y_train, dtype=dt), np.ascontiguousarray(Y_test, dtype=dt)
+        n, p = Xa.shape
+        m = Ya.shape[1]
+        self._check(self._lib.lsspa_multi_load(
+            self._h, Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m, Xe.shape[0], p, m,
+            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._multi_dims = (p, m)
+
+    def multi_load_reduced(self, G, g, H, h, yy):
+        """The same from the Gram form: G, H [p][p], g, h [m][p], yy [m] (lsspa_multi_set_reduced)."""
+        G, H = (np.ascontiguousarray(a, dtype=np.float64) for a in (G, H))
+        g, h = (np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64) for a in (g, h))
+        yy = np.ascontiguousarray(np.atleast_1d(yy), dtype=np.float64)
+        p, m = G.shape[0], g.shape[0]
+        if G.shape != (p, p) or H.shape != (p, p) or g.shape != (m, p) or h.shape != (m, p) or yy.shape != (m,):
+            raise ValueError("multi_load_reduced takes G, H [p][p], g, h [m][p] and yy [m]")
+        self._check(self._lib.lsspa_multi_set_reduced(self._h, p, m, N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
+                                                      N.dptr(yy)))
+        self._multi_dims = (p, m)
+
+    def multi_shapley(self, first: int = 0, count=None, block: int = 0):
+        """(phi [count][p], info) of responses first .. first + count - 1 (all from `first` on by default); block:
+        responses enumerated together, 0 = as many as the budget holds (include/lsspa.h, lsspa_multi_shapley)."""
+        p, m = getattr(self, "_multi_dims", None) or (1, 0)
+        count = m - int(first) if count is None else int(count)
+        phi = np.empty((max(count, 0), p))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_multi_shapley(self._h, int(first), count, int(block), N.dptr(phi), C.byref(info)))
+        return phi, info.value
+
+    def multi_gram(self):
+        """(G, g [m][p], H, h [m][p], yy [m]) of the loaded responses."""
+        p, m = self._multi_dims
+        G, g, H, h, yy = np.empty((p, p)), np.empty((m, p)), np.empty((p, p)), np.empty((m, p)), np.empty(m)
+        self._check(self._lib.lsspa_multi_get_gram(self._h, N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h), N.dptr(yy)))
+        return G, g, H, h, yy
+
+    def multi_values(self, masks):
+        """Test hook: v [n][m], v_r(S) of every mask (bit j = feature j) by the enumeration's own device code."""
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
+        out = np.empty((len(masks), self._multi_dims[1]))
+        self._check(self._lib.lsspa_debug_multi_values(self._h, masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks),
+                                                       N.dptr(out)))
+        return out
+
+    def multi_timing(self):
+        """Device seconds of the last multi_load's Gram passes and of the last multi_shapley's enumeration, its longest
+        launch, and the number of launches."""
+        a, b, c, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._check(self._lib.lsspa_multi_timing(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return {"gram": a.value / 1e3, "enumeration": b.value / 1e3, "max_launch": c.value / 1e3, "launches": n.value}
+
+    def multi_free(self):
+        self._check(self._lib.lsspa_multi_free(self._h))
+        self._multi_dims = None
+
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
         self._check(getter(self._h, C.byref(ms), C.byref(mx), C.byref(n)))

@@ -140,6 +140,14 @@ SIGNATURES = {
                                                      _pd, _pd, _pi32]),
     "lsspa_debug_boot_inter_plan": (C.c_int, [_i64, _i64, _i64, _i32, _i64, _pi64]),
     "lsspa_debug_boot_groups_inter_plan": (C.c_int, [_i64, _i64, _i64, _pi32, _i32, _i32, _i64, _pi64]),
+    "lsspa_multi_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _dbl, _i32,
+                                   _i32]),
+    "lsspa_multi_set_reduced": (C.c_int, [_vp, _i32, _i32, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_multi_shapley": (C.c_int, [_vp, _i64, _i64, _i64, _pd, _pi32]),
+    "lsspa_multi_get_gram": (C.c_int, [_vp, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_multi_timing": (C.c_int, [_vp, _pd, _pd, _pd, _pi64]),
+    "lsspa_multi_free": (C.c_int, [_vp]),
+    "lsspa_debug_multi_values": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64, _pd]),
 }
 
 

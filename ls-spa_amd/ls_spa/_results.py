@@ -108,6 +108,30 @@ class SampledInteractionResults:
         return "\n".join(lines)
 
 
+@dataclass
+class MultiResponseResults:
+    """What ``ls_spa_multi`` returns for m responses on one design matrix.  ``attribution`` [m][p]: row r is the exact
+    Shapley attribution of response r, what ``ls_spa(method='subsets')`` returns for that column alone; ``theta`` [m][p]
+    the full-model coefficients of each response; ``r_squared`` [m] their out-of-sample R^2 -- row r of ``attribution``
+    sums to ``r_squared[r]``."""
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        att = np.asarray(self.attribution)
+        lines = [
+            "",
+            f"{pad}p = {att.shape[1]}, m = {att.shape[0]} responses",
+            f"{pad}Out-of-sample R^2 with all features: {_head(self.r_squared)}",
+            "",
+            f"{pad}Shapley attribution of response 0: {_head(att[0])}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
 class SizeIncompatible(Exception):
     """Raised when the shapes of the four data arrays do not fit together."""
 
