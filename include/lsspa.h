@@ -277,8 +277,10 @@ int lsspa_debug_boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, const in
  *   G = S_tr[:p,:p] / N + reg I,  g_r = S_tr[:p,p+r] / N,  H = S_te[:p,:p],  h_r = S_te[:p,p+r],  ||y_r||^2 = S_te[p+r][p+r];
  * H is always a Gram (M < p works).  fp64 throughout.
  *   lsspa_multi_load        : X [N][ld], Y [N][ldy] (m columns used) of both sides, dtype and location as lsspa_reduce's.
- *                     p > 32, m < 1 or p + m > 32767 is LSSPA_ERR_ARG naming the limit; so is a column of Y_test that
- *                     is identically zero (or NaN), which lsspa_reduce refuses for one y.  Both sides are on the device
+ *                     p > 64, m < 1 or p + m > 32767 is LSSPA_ERR_ARG naming the limit; so is a column of Y_test that
+ *                     is identically zero (or NaN), which lsspa_reduce refuses for one y.  33 <= p <= 64 loads for
+ *                     lsspa_multi_groups_shapley alone: lsspa_multi_shapley and lsspa_debug_multi_values then refuse
+ *                     with LSSPA_ERR_ARG naming p <= 32.  Both sides are on the device
  *                     whole for the length of the call.  The loaded problem, the running statistics and the state of
  *                     lsspa_subsets_*, lsspa_groups_* and lsspa_boot_* are not touched, now or by any call below.
  *   lsspa_multi_set_reduced : the same from the Gram form (host): G, H [p][p], g, h [m][p], yy [m].
@@ -295,10 +297,27 @@ int lsspa_debug_boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, const in
  *   lsspa_multi_free        : frees the responses and the buffers.
  *   lsspa_debug_multi_values : test hook -- v [n][m], v[i][r] = v_r(masks[i]) (bit j = feature j; masks < 2^p) by the
  *                     enumeration's own device code; a failed pivot is LSSPA_ERR_STATE.
+ *   lsspa_multi_groups_shapley : the same over GROUPS of columns (g <= 32 groups over p <= 64 columns, labels as
+ *                     lsspa_groups_shapley takes them: -1 the always-included baseline, 0 .. g-1 the groups; what is
+ *                     wrong with them comes back in the LSSPA_ERR_ARG message).  phi [count][g] in label numbering: row r
+ *                     is what lsspa_groups_shapley gives for response r alone (to rounding), and sums to the response's
+ *                     R^2 minus that of its baseline.  The enumeration of csrc/k_groups.hip with eight right-hand sides
+ *                     carried through one Gauss-Jordan elimination of a high subset's pivots (csrc/k_multi_groups.hip):
+ *                     the elimination, H E and E^T H E are formed once for a chunk of 8 responses.  first, count,
+ *                     block, the 256 MB budget, info and the bitwise independence are lsspa_multi_shapley's (a unit's
+ *                     high subsets are cut into launches by the layout alone); launches are bounded as
+ *                     lsspa_groups_shapley's.  lsspa_multi_timing afterwards reports this call's enumeration.
+ *   lsspa_debug_multi_group_values : test hook -- u [n][m], u[i][r] = u_r(masks[i]) (bit k = label k; a mask at or beyond
+ *                     2^g is LSSPA_ERR_ARG) by that enumeration's own device code; a failed pivot is LSSPA_ERR_STATE.
  * LSSPA_ERR_STATE before a load; LSSPA_ERR_NOMEM when device memory runs out.
  * Measured on one MI355X (tools/multi_time.py, on top of commit 5f361f6): the enumeration costs 1.36 ms a response at
  * p = 24 and 25.4 ms at p = 28 against lsspa_subsets_shapley's 4.6 - 4.7 ms and 87.1 ms (3.4 x), 0.0081 ms against
- * 0.038 ms at p = 16 with m = 64 (4.7 x); the longest launch 14.7 ms at p = 28 (DESIGN.md has the tables). */
+ * 0.038 ms at p = 16 with m = 64 (4.7 x); the longest launch 14.7 ms at p = 28 (DESIGN.md has the tables).
+ * lsspa_multi_groups_shapley (tools/multi_groups_time.py, on top of commit 2f04542, m = 64): the enumeration costs
+ * 0.0377 ms a response at g = 12, p = 64 against lsspa_groups_shapley's 0.322 ms (ratio 0.117), 0.190 against 1.353 ms
+ * at g = 16, p = 48 (0.141), 1.001 against 6.39 ms at g = 20, p = 60 (0.157; the same at m = 8); the whole call of the
+ * Python driver against the loop of m one-response calls 19.9 x, 11.1 x and 7.3 x (5.8 x at m = 8); the longest launch
+ * 1.5 ms. */
 int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
                      int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M,
                      int32_t p, int32_t m, double reg, int32_t dtype, int32_t location);
@@ -307,11 +326,15 @@ int lsspa_multi_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* 
                             const double* yy /* [m] */);
 int lsspa_multi_shapley(lsspa_ctx* ctx, int64_t first, int64_t count, int64_t block, double* phi /* [count][p] */,
                         int32_t* info);
+int lsspa_multi_groups_shapley(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, int64_t first, int64_t count,
+                               int64_t block, double* phi /* [count][g] */, int32_t* info);
 int lsspa_multi_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy);
 int lsspa_multi_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms,
                        int64_t* launches);
 int lsspa_multi_free(lsspa_ctx* ctx);
 int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v /* [n][m] */);
+int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, const uint64_t* masks,
+                                   int64_t n, double* u /* [n][m] */);
 
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift

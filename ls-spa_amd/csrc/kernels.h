@@ -416,6 +416,31 @@ hipError_t launch_multi_enum(const MultiArgs& a, uint64_t units, uint64_t s0, ui
 hipError_t launch_multi_debug(const MultiArgs& a, const uint64_t* masks, int64_t n, double* vals, int m, int r0,
                               hipStream_t st);
 
+// ... over groups of columns (k_multi_groups.hip), g <= GROUPS_MAX_G, p <= GROUPS_MAX_P, fp64: launch_groups_enum's
+// layout, units, steps and weights with MULTI_RB responses carried by a workgroup per pass.  Chunks and the partial table
+// part [chunks][MULTI_RB][units][g + 1] (layout numbering, then b) as launch_multi_enum's; launch_subsets_reduce sums it
+// with reps = chunks * MULTI_RB.
+struct MultiGroupArgs {
+  const double* G;         // [p][ldg] training Gram, shared by the responses
+  const double* H;         // [p][ldh] test Gram (symmetric)
+  int64_t ldg, ldh;
+  const double* g;         // [count][p] per response
+  const double* h;         // [count][p]
+  const double* inv_yy;    // [count] 1 / ||y_r||^2
+  const double* w;         // GroupArgs::w (its first two rows are read)
+  const int32_t* tab;      // GroupLayout::tab on the device
+  int p, ng, nb, gl, gh, ql, count;
+  double piv_tol;          // relative pivot test: a pivot d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
+  uint64_t per;            // high subsets per unit
+  double* part;
+  int32_t* info;           // one word: G is shared
+};
+hipError_t launch_multi_groups_enum(const MultiGroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
+// vals [n][m], column r0 + r = u_r(masks[i]) of the launch's response r by the enumeration's own device code (test hook);
+// masks in the layout's numbering
+hipError_t launch_multi_groups_debug(const MultiGroupArgs& a, const uint64_t* masks, int64_t n, double* vals, int m,
+                                     int r0, hipStream_t st);
+
 // Bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp), p <= SUBSETS_MAX_P -- over groups of columns
 // p <= GROUPS_MAX_P (cb = 4, 5) --, fp64.  Z = [X | y] of one side
 // lives on the device as [n][ldz], ldz = 16 cb, cb = ceil((p + 1) / 16), columns beyond p zero.  A BLOCK of replicates

@@ -98,13 +98,13 @@ struct MultiWork {
   DevBuf<double> G, H, g, h, inv_yy;       // [p][p], [p][p], [m][p], [m][p], [m]
   DevBuf<double> w, part, out, vals;       // Shapley weights, partial table of a block, its column sums, debug values
   DevBuf<uint64_t> masks;
-  DevBuf<int32_t> info;
+  DevBuf<int32_t> info, tab;               // tab: the layout of the last grouped call (GroupLayout::tab)
   std::vector<double> Gh, Hh, gh, hh, yyh; // the same on the host (lsspa_multi_get_gram)
   double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
     dev_free(G); dev_free(H); dev_free(g); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(part); dev_free(out);
-    dev_free(vals); dev_free(masks); dev_free(info);
+    dev_free(vals); dev_free(masks); dev_free(info); dev_free(tab);
     loaded = false;
   }
 };
@@ -4153,6 +4153,8 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
 // then runs blocks of responses, a block's chunks of MULTI_RB as the second grid dimension, into a partial table
 // [chunks][MULTI_RB][units][p + 1] that launch_subsets_reduce sums in fixed order.  How often a unit's row is added to
 // (the steps per launch) depends on p alone, so a response's bits do not depend on the block it runs in.
+// lsspa_multi_groups_shapley (k_multi_groups.hip) is the same over groups of columns: the players are the g groups of a
+// layout (groups_layout), the table [chunks][MULTI_RB][units][g + 1], the block loop multi_enumerate for both.
 namespace {
 
 // (high subset, chunk) passes one enumeration launch takes at most, over all units and chunks.  A pass carries MULTI_RB
@@ -4166,9 +4168,9 @@ constexpr int64_t MULTI_MAX_CHUNKS = 8191;             // chunks * MULTI_RB is l
 
 int multi_limits(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
   char msg[200];
-  if (p < 1 || p > MULTI_MAX_P) {
-    snprintf(msg, sizeof msg, "%s enumerates all 2^p feature subsets and takes 1 <= p <= %d features (%lld given)", name,
-             MULTI_MAX_P, (long long)p);
+  if (p < 1 || p > GROUPS_MAX_P) {       // (p > MULTI_MAX_P: for lsspa_multi_groups_shapley only, multi_need_ungrouped)
+    snprintf(msg, sizeof msg, "%s takes 1 <= p <= %d columns, of which the ungrouped enumeration takes p <= %d "
+             "(%lld given)", name, GROUPS_MAX_P, MULTI_MAX_P, (long long)p);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
   if (m < 1 || p + m > MULTI_MAX_COLS) {
@@ -4185,10 +4187,23 @@ int multi_need_loaded(lsspa_ctx* ctx) {
   return LSSPA_OK;
 }
 
-// responses enumerated together: as many as MULTI_TABLE_BYTES hold, whole chunks, at least one chunk
-int64_t multi_block_max(int p) {
-  const uint64_t units = exact_units(1ull << (p - subsets_low_features(p)));
-  const int64_t fit = (int64_t)(MULTI_TABLE_BYTES / (units * (uint64_t)(p + 1) * sizeof(double)));
+// the enumeration over features takes p <= MULTI_MAX_P of the p <= GROUPS_MAX_P columns a load accepts
+int multi_need_ungrouped(lsspa_ctx* ctx, const char* name) {
+  if (ctx->multi.p > MULTI_MAX_P) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s enumerates all 2^p feature subsets and takes at most p = %d features (%d loaded); "
+             "lsspa_multi_groups_shapley attributes to groups of up to %d columns", name, MULTI_MAX_P, ctx->multi.p,
+             GROUPS_MAX_P);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+// responses enumerated together: as many as MULTI_TABLE_BYTES hold, whole chunks, at least one chunk.  n players
+// (features, or groups of columns), n_high high subsets
+int64_t multi_block_max(int n, uint64_t n_high) {
+  const uint64_t units = exact_units(n_high);
+  const int64_t fit = (int64_t)(MULTI_TABLE_BYTES / (units * (uint64_t)(n + 1) * sizeof(double)));
   const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(fit / MULTI_RB, MULTI_MAX_CHUNKS));
   return chunks * MULTI_RB;
 }
@@ -4251,6 +4266,128 @@ int multi_args(lsspa_ctx* ctx, int64_t first, int64_t count, MultiArgs& a) {
   a.w = W.w.ptr;
   a.p = p;
   a.q = subsets_low_features(p);
+  a.count = (int)count;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.info = W.info.ptr;
+  return LSSPA_OK;
+}
+
+// first, count, block of an enumeration call against the responses loaded
+int multi_range(lsspa_ctx* ctx, const char* name, int64_t first, int64_t count, int64_t block) {
+  const int m = ctx->multi.m;
+  if (first < 0 || count < 1 || first > m || count > m - first || block < 0) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: responses first = %lld, count = %lld must lie inside the %d loaded, "
+             "count >= 1, block >= 0", name, (long long)first, (long long)count, m);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+// The enumeration of `count` responses, shared by the calls over features and over groups: n players, n_high high subsets
+// in exact_units(n_high) units, blocks of responses as MULTI_TABLE_BYTES hold (or `block`), at most `passes` (high subset,
+// chunk) passes a launch.  launch(r0, cnt, part, units, s0, s1): steps s0 .. s1 - 1 of every unit for the cnt responses
+// from r0 (among those of the call) into part; store(r, out): the n + 1 column sums of response r's table.  The steps a
+// launch takes depend on n_high and passes alone, so a response's bits do not depend on the block it runs in.  Leaves the
+// call's timing in ctx->multi and the info word in info (may be NULL).
+template <typename Launch, typename Store>
+int multi_enumerate(lsspa_ctx* ctx, int n, uint64_t n_high, uint64_t passes, int64_t count, int64_t block,
+                    Launch&& launch, Store&& store, int32_t* info) {
+  MultiWork& W = ctx->multi;
+  const int64_t bmax = multi_block_max(n, n_high);
+  const int64_t blk = std::min<int64_t>(block == 0 ? bmax : std::min(block, bmax), count);
+  const uint64_t units = exact_units(n_high), per = n_high / units;
+  // steps per launch by the players alone; the chunks of a launch make up the rest of its bound
+  const uint64_t steps = std::min(per, std::max<uint64_t>(1, passes / units));
+  const int64_t chunks_per_launch = (int64_t)std::max<uint64_t>(1, passes / (units * steps));
+  const size_t c = (size_t)n + 1;
+  const int64_t max_chunks = (blk + MULTI_RB - 1) / MULTI_RB;
+  TRY(dev_alloc(ctx, W.part, (size_t)max_chunks * MULTI_RB * units * c));
+  TRY(dev_alloc(ctx, W.out, (size_t)max_chunks * MULTI_RB * c));
+  std::vector<double> out((size_t)max_chunks * MULTI_RB * c);
+  std::vector<hipEvent_t> ev;
+  Events guard{ev};
+  W.enum_ms = W.max_launch_ms = 0.0;
+  W.launches = 0;
+  for (int64_t b0 = 0; b0 < count; b0 += blk) {
+    const int64_t nb = std::min(blk, count - b0);
+    const int64_t chunks = (nb + MULTI_RB - 1) / MULTI_RB;
+    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)chunks * MULTI_RB * units * c, ctx->stream));
+    const size_t e0 = ev.size();
+    ev.push_back(nullptr);
+    HIPCHK(hipEventCreate(&ev.back()));
+    HIPCHK(hipEventRecord(ev.back(), ctx->stream));
+    for (int64_t c0 = 0; c0 < chunks; c0 += chunks_per_launch) {
+      const int64_t r0 = b0 + c0 * MULTI_RB;                 // the launch's first response, among those of the call
+      const int64_t cnt = std::min<int64_t>(chunks_per_launch * MULTI_RB, b0 + nb - r0);
+      double* part = W.part.ptr + (size_t)c0 * MULTI_RB * units * c;
+      for (uint64_t s0 = 0; s0 < per; s0 += steps) {
+        HIPCHK(launch(r0, cnt, part, units, s0, std::min(per, s0 + steps)));
+        ev.push_back(nullptr);
+        HIPCHK(hipEventCreate(&ev.back()));
+        HIPCHK(hipEventRecord(ev.back(), ctx->stream));
+      }
+    }
+    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, (int)c, W.out.ptr, ctx->stream, (int)(chunks * MULTI_RB)));
+    HIPCHK(hipMemcpyAsync(out.data(), W.out.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int64_t r = 0; r < nb; ++r) store(b0 + r, out.data() + (size_t)r * c);
+    for (size_t k = e0; k + 1 < ev.size(); ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      W.enum_ms += ms;
+      W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
+      ++W.launches;
+    }
+    for (hipEvent_t& e : ev) {
+      (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    ev.clear();
+  }
+  int32_t bits = 0;
+  HIPCHK(hipMemcpy(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost));
+  if (info) *info = bits;
+  return LSSPA_OK;
+}
+
+// The grouped kernels' view of the loaded responses first .. first + count - 1: the layout L of the labels and its table
+// on the device, the weights of g players, a cleared info word
+int multi_group_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t first, int64_t count,
+                     MultiGroupArgs& a, GroupLayout& L) {
+  MultiWork& W = ctx->multi;
+  const int p = W.p;
+  char msg[200];
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+             (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (const char* why = groups_layout(labels, p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  double w[EXACT_W_ROWS * WR];
+  exact_weight_table(L.ng, w);
+  TRY(dev_alloc(ctx, W.w, EXACT_W_ROWS * WR));
+  TRY(dev_alloc(ctx, W.tab, GROUPS_TAB_LEN));
+  TRY(dev_alloc(ctx, W.info, 8));
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read W.w / W.tab; the copies are from host frames
+  HIPCHK(hipMemcpy(W.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.tab.ptr, L.tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
+  a = MultiGroupArgs{};
+  a.G = W.G.ptr;
+  a.H = W.H.ptr;
+  a.ldg = a.ldh = p;
+  a.g = W.g.ptr + (size_t)first * p;
+  a.h = W.h.ptr + (size_t)first * p;
+  a.inv_yy = W.inv_yy.ptr + first;
+  a.w = W.w.ptr;
+  a.tab = W.tab.ptr;
+  a.p = p; a.ng = L.ng; a.nb = L.nb;
+  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
   a.count = (int)count;
   a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
   a.info = W.info.ptr;
@@ -4363,81 +4500,66 @@ int lsspa_multi_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* 
 int lsspa_multi_shapley(lsspa_ctx* ctx, int64_t first, int64_t count, int64_t block, double* phi, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(multi_need_loaded(ctx));
+  TRY(multi_need_ungrouped(ctx, "lsspa_multi_shapley"));
   MultiWork& W = ctx->multi;
   const int p = W.p;
   if (!phi) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_shapley: phi is NULL");
-  if (first < 0 || count < 1 || first > W.m || count > W.m - first || block < 0) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "lsspa_multi_shapley: responses first = %lld, count = %lld must lie inside the %d loaded, "
-             "count >= 1, block >= 0", (long long)first, (long long)count, W.m);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
+  TRY(multi_range(ctx, "lsspa_multi_shapley", first, count, block));
   HIPCHK(hipSetDevice(ctx->device));
-  const int64_t bmax = multi_block_max(p);
-  const int64_t blk = std::min<int64_t>(block == 0 ? bmax : std::min(block, bmax), count);
   const int q = subsets_low_features(p);
   const uint64_t n_high = 1ull << (p - q);
-  const uint64_t units = exact_units(n_high), per = n_high / units;
-  // steps per launch by p alone; the chunks of a launch make up the rest of its bound
-  const uint64_t steps = std::min(per, std::max<uint64_t>(1, MULTI_PASSES_PER_LAUNCH / units));
-  const int64_t chunks_per_launch = (int64_t)std::max<uint64_t>(1, MULTI_PASSES_PER_LAUNCH / (units * steps));
-  const size_t c = (size_t)p + 1;
-  const int64_t max_chunks = (blk + MULTI_RB - 1) / MULTI_RB;
-  TRY(dev_alloc(ctx, W.part, (size_t)max_chunks * MULTI_RB * units * c));
-  TRY(dev_alloc(ctx, W.out, (size_t)max_chunks * MULTI_RB * c));
   MultiArgs a;
   TRY(multi_args(ctx, first, count, a));
-  a.per = per;
-  std::vector<double> out((size_t)max_chunks * MULTI_RB * c);
-  std::vector<hipEvent_t> ev;
-  Events guard{ev};
-  W.enum_ms = W.max_launch_ms = 0.0;
-  W.launches = 0;
-  for (int64_t b0 = 0; b0 < count; b0 += blk) {
-    const int64_t nb = std::min(blk, count - b0);
-    const int64_t chunks = (nb + MULTI_RB - 1) / MULTI_RB;
-    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)chunks * MULTI_RB * units * c, ctx->stream));
-    const size_t e0 = ev.size();
-    ev.push_back(nullptr);
-    HIPCHK(hipEventCreate(&ev.back()));
-    HIPCHK(hipEventRecord(ev.back(), ctx->stream));
-    for (int64_t c0 = 0; c0 < chunks; c0 += chunks_per_launch) {
-      MultiArgs l = a;
-      const int64_t r0 = b0 + c0 * MULTI_RB;                 // the launch's first response, among those of the call
-      l.g = a.g + (size_t)r0 * p;
-      l.h = a.h + (size_t)r0 * p;
-      l.inv_yy = a.inv_yy + r0;
-      l.count = (int)std::min<int64_t>(chunks_per_launch * MULTI_RB, b0 + nb - r0);
-      l.part = W.part.ptr + (size_t)c0 * MULTI_RB * units * c;
-      for (uint64_t s0 = 0; s0 < per; s0 += steps) {
-        HIPCHK(launch_multi_enum(l, units, s0, std::min(per, s0 + steps), ctx->stream));
-        ev.push_back(nullptr);
-        HIPCHK(hipEventCreate(&ev.back()));
-        HIPCHK(hipEventRecord(ev.back(), ctx->stream));
-      }
-    }
-    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, (int)c, W.out.ptr, ctx->stream, (int)(chunks * MULTI_RB)));
-    HIPCHK(hipMemcpyAsync(out.data(), W.out.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int64_t r = 0; r < nb; ++r)
-      for (int j = 0; j < p; ++j) phi[(size_t)(b0 + r) * p + j] = out[(size_t)r * c + j] - out[(size_t)r * c + p];
-    for (size_t k = e0; k + 1 < ev.size(); ++k) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-      W.enum_ms += ms;
-      W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
-      ++W.launches;
-    }
-    for (hipEvent_t& e : ev) {
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    ev.clear();
-  }
-  int32_t bits = 0;
-  HIPCHK(hipMemcpy(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost));
-  if (info) *info = bits;
-  return LSSPA_OK;
+  a.per = n_high / exact_units(n_high);
+  auto launch = [&](int64_t r0, int64_t cnt, double* part, uint64_t units, uint64_t s0, uint64_t s1) {
+    MultiArgs l = a;
+    l.g = a.g + (size_t)r0 * p;
+    l.h = a.h + (size_t)r0 * p;
+    l.inv_yy = a.inv_yy + r0;
+    l.count = (int)cnt;
+    l.part = part;
+    return launch_multi_enum(l, units, s0, s1, ctx->stream);
+  };
+  auto store = [&](int64_t r, const double* out) {
+    for (int j = 0; j < p; ++j) phi[(size_t)r * p + j] = out[j] - out[p];
+  };
+  return multi_enumerate(ctx, p, n_high, MULTI_PASSES_PER_LAUNCH, count, block, launch, store, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t first, int64_t count,
+                               int64_t block, double* phi, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_need_loaded(ctx));
+  MultiWork& W = ctx->multi;
+  const int p = W.p;
+  if (!phi || !labels) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_groups_shapley: labels / phi is NULL");
+  TRY(multi_range(ctx, "lsspa_multi_groups_shapley", first, count, block));
+  HIPCHK(hipSetDevice(ctx->device));
+  MultiGroupArgs a;
+  GroupLayout L;
+  TRY(multi_group_args(ctx, labels, g, first, count, a, L));
+  const int ng = L.ng;
+  const uint64_t n_high = 1ull << L.gh;
+  a.per = n_high / exact_units(n_high);
+  // passes per launch: groups_enumerate's bound by the rows of a subset's matrix, a quarter of it as a pass carries
+  // MULTI_RB responses (MULTI_PASSES_PER_LAUNCH); by the layout alone, so a response's bits do not depend on the block
+  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
+  const uint64_t passes = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows) / 4);
+  auto launch = [&](int64_t r0, int64_t cnt, double* part, uint64_t units, uint64_t s0, uint64_t s1) {
+    MultiGroupArgs l = a;
+    l.g = a.g + (size_t)r0 * p;
+    l.h = a.h + (size_t)r0 * p;
+    l.inv_yy = a.inv_yy + r0;
+    l.count = (int)cnt;
+    l.part = part;
+    return launch_multi_groups_enum(l, units, s0, s1, ctx->stream);
+  };
+  auto store = [&](int64_t r, const double* out) {
+    for (int k = 0; k < ng; ++k) phi[(size_t)r * ng + L.gid[k]] = out[k] - out[ng];
+  };
+  return multi_enumerate(ctx, ng, n_high, passes, count, block, launch, store, info);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -4481,6 +4603,7 @@ int lsspa_multi_free(lsspa_ctx* ctx) try {
 int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(multi_need_loaded(ctx));
+  TRY(multi_need_ungrouped(ctx, "lsspa_debug_multi_values"));
   MultiWork& W = ctx->multi;
   if (n < 0 || (n > 0 && (!masks || !v))) return ctx->fail(LSSPA_ERR_ARG, "masks / v NULL or n < 0");
   const uint64_t full = (1ull << W.p) - 1ull;     // p <= 32 here
@@ -4500,6 +4623,41 @@ int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, d
   HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (bits & LSSPA_INFO_NOT_PD) return ctx->fail(LSSPA_ERR_STATE, "a subset's Gram matrix is not positive definite");
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const uint64_t* masks, int64_t n,
+                                   double* u) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_need_loaded(ctx));
+  MultiWork& W = ctx->multi;
+  if (!labels || n < 0 || (n > 0 && (!masks || !u))) return ctx->fail(LSSPA_ERR_ARG, "labels / masks / u NULL or n < 0");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int m = W.m;
+  MultiGroupArgs a;
+  GroupLayout L;
+  TRY(multi_group_args(ctx, labels, g, 0, m, a, L));
+  const uint64_t full = (1ull << L.ng) - 1ull;     // g <= 32
+  for (int64_t i = 0; i < n; ++i)
+    if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a group beyond g");
+  if (n == 0) return LSSPA_OK;
+  // bit k = group k  ->  the layout's numbering (low groups first)
+  std::vector<uint64_t> lay((size_t)n, 0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int r = 0; r < L.ng; ++r)
+      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  TRY(dev_alloc(ctx, W.masks, (size_t)n));
+  TRY(dev_alloc(ctx, W.vals, (size_t)n * m));
+  HIPCHK(hipMemcpy(W.masks.ptr, lay.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(launch_multi_groups_debug(a, W.masks.ptr, n, W.vals.ptr, m, 0, ctx->stream));
+  HIPCHK(hipMemcpyAsync(u, W.vals.ptr, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToHost, ctx->stream));
+  int32_t bits = 0;
+  HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (bits & LSSPA_INFO_NOT_PD)
+    return ctx->fail(LSSPA_ERR_STATE, "a group subset's Gram matrix is not positive definite");
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

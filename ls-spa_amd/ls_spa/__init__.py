@@ -8,10 +8,12 @@ pairwise Shapley interaction values between features, p <= 32, or between groups
 ``ls_spa_interactions_sampled`` (their sampled counterpart, for any number of features or groups) and
 ``ls_spa_bootstrap`` (bootstrap confidence intervals of the exact attribution, p <= 32, or over g <= 32 groups of p <= 64 columns)
 and ``ls_spa_interactions_bootstrap`` (the same for the exact interaction values) and ``ls_spa_multi`` (the exact
-attribution of many responses on one design matrix, p <= 32) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
+attribution of many responses on one design matrix, p <= 32, or with ``groups=`` over g <= 32 groups of p <= 64 columns,
+returning ``MultiGroupResults``) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
-from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiResponseResults,
+from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+                       MultiResponseResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
 from ._driver import (ls_spa, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
@@ -25,4 +27,5 @@ __all__ = [
     "merge_sample_cov", "square_shapley", "reduce_data", "error_estimates",
     "error_estimates_lowrank", "run_estimator", "release", "LSSPANativeError", "NativeComm",
     "ls_spa_interactions_bootstrap", "InteractionBootstrapResults", "ls_spa_multi", "MultiResponseResults",
+    "MultiGroupResults",
 ]

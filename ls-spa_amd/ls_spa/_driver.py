@@ -31,7 +31,8 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiResponseResults,
+from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+                       MultiResponseResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
@@ -1115,8 +1116,19 @@ def _multi_fit(G, g, H, h, yy):
     return np.ascontiguousarray(theta), r2, singular
 
 
-def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, device=0, _engine=None):
-    """Exact Shapley attribution of many responses on one design matrix (p <= 32).
+def _multi_baseline_r_squared(G, g, H, h, yy, labels):
+    """[m]: every response's R^2 of the baseline columns (label -1) alone, from the reduced form as _multi_fit forms the
+    full models'; 0 without a baseline."""
+    base = np.nonzero(np.asarray(labels) == -1)[0]
+    if len(base) == 0:
+        return np.zeros(len(yy))
+    sub = np.ix_(base, base)
+    return _multi_fit(G[sub], g[:, base], H[sub], h[:, base], yy)[1]
+
+
+def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, groups=None, device=0, _engine=None):
+    """Exact Shapley attribution of many responses on one design matrix (p <= 32; with ``groups=``, g <= 32 groups over
+    p <= 64 columns).
 
     ``Y_train`` is [N][m] and ``Y_test`` [M][m] (a one-dimensional y counts as m = 1): the same features explain m
     targets -- a multi-output ridge model, one model per asset, gene or sensor, the permuted-y columns of a
@@ -1132,7 +1144,17 @@ def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, device=0, _engine=
     Shapes that do not fit raise ``SizeIncompatible``; p > 32 or p + m > 32767 ValueError naming the limit, before any
     GPU work.  As for a single y, a column of ``Y_test`` that is identically zero is a ValueError, and a Gram matrix
     that is not numerically positive definite a RuntimeWarning (it is shared, so it concerns every response); theta is
-    then the solution of minimal norm.  M < p works."""
+    then the solution of minimal norm.  M < p works.
+
+    groups:  one integer label per column as ``ls_spa(method='subsets', groups=)`` takes them: k in 0 .. g-1 puts the
+        column into group k, -1 into a baseline that every model includes.  The players are then the g groups, and the
+        result is a ``MultiGroupResults``: row r of ``attribution`` [m][g] is what ``ls_spa(X_train, X_test,
+        Y_train[:, r], Y_test[:, r], reg, method='subsets', groups=groups).attribution`` returns and sums to
+        ``r_squared[r] - baseline_r_squared[r]``; ``theta`` [m][p] and ``r_squared`` [m] are the full models',
+        ``baseline_r_squared`` [m] each response's R^2 of the baseline columns alone (0 without a baseline).  The
+        elimination of a group subset's columns is shared by every eight responses (include/lsspa.h,
+        lsspa_multi_groups_shapley).  The limits and messages are that call's -- g <= 32, p <= 64 (the p <= 32 limit
+        does not apply), labels refused with ValueError -- before any GPU work."""
     X_train, X_test = np.asarray(X_train), np.asarray(X_test)
     Y_train, Y_test = np.asarray(Y_train), np.asarray(Y_test)
     if X_train.ndim != 2 or X_test.ndim != 2:
@@ -1147,7 +1169,13 @@ def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, device=0, _engine=
         raise SizeIncompatible("Y_train and Y_test should have the same number of columns (responses).")
     validate_data(X_train, X_test, Y_train, Y_test)
     p, m = X_train.shape[1], Y_train.shape[1]
-    if p > SUBSETS_MAX_P:
+    labels = None
+    if groups is not None:
+        if p > GROUPS_MAX_P:
+            raise ValueError(f"grouped attribution takes at most p = {GROUPS_MAX_P} columns, the baseline's included "
+                             f"(this problem has p = {p})")
+        labels, _ = group_labels(groups, p)
+    elif p > SUBSETS_MAX_P:
         raise ValueError(f"ls_spa_multi enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} "
                          f"features (this problem has p = {p}); use a sampling method per response")
     if p < 1 or m < 1 or X_test.shape[0] < 1:
@@ -1160,10 +1188,14 @@ def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, device=0, _engine=
     with _engine_call(_engine, device, undo=undo) as engine:
         undo.append((engine.multi_free, True))
         engine.multi_load(X_train, X_test, Y_train, Y_test, reg)
-        phi, bits = engine.multi_shapley()
-        theta, r_squared, singular = _multi_fit(*engine.multi_gram())
+        phi, bits = engine.multi_shapley() if labels is None else engine.multi_groups_shapley(labels)
+        gram = engine.multi_gram()
+        theta, r_squared, singular = _multi_fit(*gram)
     _info_verdict((bits | int(singular)) & 1, stacklevel=2)
-    return MultiResponseResults(attribution=phi, theta=theta, r_squared=r_squared)
+    if labels is None:
+        return MultiResponseResults(attribution=phi, theta=theta, r_squared=r_squared)
+    return MultiGroupResults(attribution=phi, theta=theta, r_squared=r_squared,
+                             baseline_r_squared=_multi_baseline_r_squared(*gram, labels))
 
 
 BOOT_ONES_BYTES = 64 << 20     # ls_spa_bootstrap: host bytes of the unit weights of a side that is not resampled

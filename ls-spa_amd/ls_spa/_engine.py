@@ -422,7 +422,7 @@ class HipEngine:
                                                      N.dptr(ws)))
         return Sa, Se, ws
 
-    # ---- exact attribution of many responses at once (p <= 32) -----------------------------
+    # ---- exact attribution of many responses at once (p <= 32; over groups g <= 32, p <= 64) ----
     MULTI_RB = 8      # responses a wave carries per pass (csrc/kernels.h)
 
     def multi_load(self, X_train, X_test, Y_train, Y_test, reg: float):
@@ -475,9 +475,39 @@ class HipEngine:
                                                        N.dptr(out)))
         return out
 
+    def _multi_labels(self, labels):
+        labels, g = self._labels(labels)
+        dims = getattr(self, "_multi_dims", None)
+        if dims is not None and len(labels) != dims[0]:
+            raise ValueError(f"labels must have length p = {dims[0]}")
+        return labels, g
+
+    def multi_groups_shapley(self, labels, first: int = 0, count=None, block: int = 0):
+        """(phi [count][g], info): multi_shapley over the groups of columns that labels names (one label per column: -1
+        the baseline, 0 .. g-1 the groups; include/lsspa.h, lsspa_multi_groups_shapley).  The library checks the
+        labels."""
+        labels, g = self._multi_labels(labels)
+        m = (getattr(self, "_multi_dims", None) or (1, 0))[1]
+        count = m - int(first) if count is None else int(count)
+        phi = np.empty((max(count, 0), max(g, 1)))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_multi_groups_shapley(self._h, N.iptr(labels), g, int(first), count, int(block),
+                                                         N.dptr(phi), C.byref(info)))
+        return phi, info.value
+
+    def multi_group_values(self, labels, masks):
+        """Test hook: u [n][m], u_r(S) of every mask (bit k = group k) by the grouped enumeration's own device code."""
+        labels, g = self._multi_labels(labels)
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
+        out = np.empty((len(masks), (getattr(self, "_multi_dims", None) or (1, 0))[1]))
+        self._check(self._lib.lsspa_debug_multi_group_values(self._h, N.iptr(labels), g,
+                                                             masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks),
+                                                             N.dptr(out)))
+        return out
+
     def multi_timing(self):
-        """Device seconds of the last multi_load's Gram passes and of the last multi_shapley's enumeration, its longest
-        launch, and the number of launches."""
+        """Device seconds of the last multi_load's Gram passes and of the last multi_shapley's (or
+        multi_groups_shapley's) enumeration, its longest launch, and the number of launches."""
         a, b, c, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
         self._check(self._lib.lsspa_multi_timing(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return {"gram": a.value / 1e3, "enumeration": b.value / 1e3, "max_launch": c.value / 1e3, "launches": n.value}

@@ -148,6 +148,8 @@ SIGNATURES = {
     "lsspa_multi_timing": (C.c_int, [_vp, _pd, _pd, _pd, _pi64]),
     "lsspa_multi_free": (C.c_int, [_vp]),
     "lsspa_debug_multi_values": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64, _pd]),
+    "lsspa_multi_groups_shapley": (C.c_int, [_vp, _pi32, _i32, _i64, _i64, _i64, _pd, _pi32]),
+    "lsspa_debug_multi_group_values": (C.c_int, [_vp, _pi32, _i32, C.POINTER(C.c_uint64), _i64, _pd]),
 }
 
 

@@ -132,6 +132,33 @@ class MultiResponseResults:
         return "\n".join(lines)
 
 
+@dataclass
+class MultiGroupResults:
+    """What ``ls_spa_multi(groups=)`` returns for m responses on one design matrix whose columns form g groups.
+    ``attribution`` [m][g]: row r is the exact Shapley attribution of response r over the groups, what
+    ``ls_spa(method='subsets', groups=)`` returns for that column alone; ``theta`` [m][p] the full-model coefficients of
+    each response; ``r_squared`` [m] their out-of-sample R^2 and ``baseline_r_squared`` [m] that of the baseline columns
+    alone (0 without a baseline) -- row r of ``attribution`` sums to ``r_squared[r] - baseline_r_squared[r]``."""
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: np.ndarray
+    baseline_r_squared: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        att = np.asarray(self.attribution)
+        lines = [
+            "",
+            f"{pad}g = {att.shape[1]} groups, p = {np.asarray(self.theta).shape[1]}, m = {att.shape[0]} responses",
+            f"{pad}Out-of-sample R^2 with all columns: {_head(self.r_squared)}",
+            f"{pad}Out-of-sample R^2 of the baseline: {_head(self.baseline_r_squared)}",
+            "",
+            f"{pad}Shapley attribution of response 0: {_head(att[0])}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
 class SizeIncompatible(Exception):
     """Raised when the shapes of the four data arrays do not fit together."""
 
