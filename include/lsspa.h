@@ -631,6 +631,20 @@ int lsspa_debug_stats_slices(int32_t n_samples, int32_t p, int32_t* n_slices, in
  * [X | y], *xlive = live 16-column blocks of the last tile.  No context, no GPU: host code only. */
 int lsspa_debug_gram_plan(int64_t n, int32_t p, int32_t* n_split, int32_t* cnt3, int32_t* slices3, int32_t* rps3,
                           int32_t* nt, int32_t* xlive);
+/* what the per-ordering general path launches for n_ord orderings at p features (csrc/k_factor.hip, panel_plan, under
+ * the engine's own shape rules: p_pad = p + 1 rounded up to 128, p_live = p + 1 rounded up to 16, two matrices an
+ * ordering in tri mode, and in tri mode one more panel launch, X tiles only, unless developer flag 128 is in `flags`):
+ * *p_pad, *n_mats, *n_launch panel launches and, for the first `cap` of them, plans [launch][8] = Jo, L tiles per
+ * matrix, X tiles per ordering, grouped (the eight-matrices-at-a-time workgroup map), xlast (the instantiation without
+ * the last panel's dead columns), workgroups, p_live, orderings as the kernel counts them.  p = 127 in rect mode has
+ * no panel launch.  Whether a problem takes the general path at all (p + 1 <= 128 in fp64 tri mode does not, without
+ * developer flag 1024) is not this function's business.  No context, no GPU: host code only. */
+int lsspa_debug_panel_plan(int32_t p, int32_t n_ord, int32_t tri, int32_t flags, int32_t* p_pad, int32_t* n_mats,
+                           int32_t* n_launch, int32_t* plans, int32_t cap);
+/* one launch from launch_chol2_panel's own arguments (has_X: X tiles are computed; p_live <= 0 or > p_pad: none
+ * known), plan [8] as above; LSSPA_ERR_ARG for what launch_chol2_panel refuses. */
+int lsspa_debug_panel_plan_launch(int32_t p_pad, int32_t Jo, int32_t n_mats, int32_t n_ord, int32_t has_X,
+                                  int32_t p_live, int32_t* plan);
 /* rows per chunk of the streamed reduction of host-resident data, instead of its ~96 MB sizing with a 1024-row floor:
  * 0 (the default sizing again) or a multiple of 16 that is at least 16, anything else is LSSPA_ERR_ARG.  The slice count
  * of every chunk's launch is the one for `rows` rows, as with the default sizing.  Stays set until changed: a

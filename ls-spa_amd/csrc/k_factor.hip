@@ -1284,14 +1284,31 @@ hipError_t launch_chol2_diag(void* A, void* Dinv, const double* diag0, double pi
   return hipGetLastError();
 }
 
+// the decisions of one panel launch, on the host alone (kernels.h)
+bool panel_plan(int p_pad, int Jo, int n_mats, int n_ord, bool has_X, int p_live, PanelPlan* out) {
+  if (p_live <= 0 || p_live > p_pad) p_live = p_pad;
+  const int n_panel = p_pad / 128 - 1;
+  // with X tiles the matrices are [n_ord training][n_ord test] and there is one more launch, Jo = n_panel
+  if (p_pad % 128 != 0 || Jo < 0 || n_mats < 1 || Jo > n_panel || (Jo == n_panel && !has_X)) return false;
+  if (has_X && (n_ord < 1 || n_mats != 2 * n_ord)) return false;
+  PanelPlan pp;
+  pp.n_ord = has_X ? n_ord : n_mats;
+  pp.n_lt = n_panel - Jo;
+  pp.n_x = has_X ? Jo + 1 : 0;
+  pp.p_live = p_live;
+  pp.grid = (int64_t)n_mats * pp.n_lt + (int64_t)pp.n_ord * pp.n_x;
+  if (pp.grid < 1 || pp.grid > 0x7fffffff) return false;
+  pp.grouped = (n_mats % 8 == 0 && pp.n_lt > 1) ? 1 : 0;
+  pp.xlast = (pp.n_lt == 0 && p_live < p_pad - 15) ? 1 : 0;     // X tiles only, and dead columns in the last panel
+  *out = pp;
+  return true;
+}
+
 hipError_t launch_chol2_panel(void* A, void* Dinv, const double* diag0, double piv_tol, int32_t* info, int p_pad,
                               int Jo, int n_mats, int f32, hipStream_t st, int flags, int p_live, void* X,
                               int n_ord, const PanelLift* pl) {
-  if (p_live <= 0 || p_live > p_pad) p_live = p_pad;
-  const int n_panel = p_pad / 128 - 1;
-  // with X tiles (X != null) the matrices are [n_ord training][n_ord test] and there is one more launch, Jo = n_panel
-  if (p_pad % 128 != 0 || Jo < 0 || n_mats < 1 || Jo > n_panel || (Jo == n_panel && !X)) return hipErrorInvalidValue;
-  if (X && (n_ord < 1 || n_mats != 2 * n_ord)) return hipErrorInvalidValue;
+  PanelPlan pp;
+  if (!panel_plan(p_pad, Jo, n_mats, n_ord, X != nullptr, p_live, &pp)) return hipErrorInvalidValue;
   Panel2Args a;
   a.A = A;
   a.Dinv = Dinv;
@@ -1303,10 +1320,10 @@ hipError_t launch_chol2_panel(void* A, void* Dinv, const double* diag0, double p
   a.Jo = Jo;
   a.nblk = p_pad / NB;
   a.n_mats = n_mats;
-  a.n_ord = X ? n_ord : n_mats;
-  a.n_lt = n_panel - Jo;
-  a.n_x = X ? Jo + 1 : 0;
-  a.p_live = p_live;
+  a.n_ord = pp.n_ord;
+  a.n_lt = pp.n_lt;
+  a.n_x = pp.n_x;
+  a.p_live = pp.p_live;
   a.flags = nullptr;
   a.run = a.Ppart = nullptr;
   a.pstride = 0;
@@ -1324,18 +1341,15 @@ hipError_t launch_chol2_panel(void* A, void* Dinv, const double* diag0, double p
     a.lift = pl->mode;
   }
   a.mute = (flags & 4096) ? 1 : 0;
-  const int64_t total = (int64_t)n_mats * a.n_lt + (int64_t)a.n_ord * a.n_x;
-  if (total < 1 || total > 0x7fffffff) return hipErrorInvalidValue;
-  a.grouped = (n_mats % 8 == 0 && a.n_lt > 1) ? 1 : 0;
-  const dim3 grid((unsigned)total);
+  a.grouped = pp.grouped;
+  const dim3 grid((unsigned)pp.grid);
   // 256 threads: 512-thread workgroups (16 rows per wave, twice the waves per SIMD) were measured
   // slower in both precisions -- the epilogue is bound by its memory traffic, not by latency
-  const bool xlast = a.n_lt == 0 && p_live < p_pad - 15;     // X tiles only, and dead columns in the last panel
   if (f32) {
-    if (xlast) hipLaunchKernelGGL((chol_panel2_kernel<float, 256, true>), grid, dim3(256), 0, st, a);
+    if (pp.xlast) hipLaunchKernelGGL((chol_panel2_kernel<float, 256, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((chol_panel2_kernel<float, 256, false>), grid, dim3(256), 0, st, a);
   } else {
-    if (xlast) hipLaunchKernelGGL((chol_panel2_kernel<double, 256, true>), grid, dim3(256), 0, st, a);
+    if (pp.xlast) hipLaunchKernelGGL((chol_panel2_kernel<double, 256, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((chol_panel2_kernel<double, 256, false>), grid, dim3(256), 0, st, a);
   }
   return hipGetLastError();

@@ -120,6 +120,16 @@ struct PanelLift {
   int p;                   // features
   int mode;                // 0 off, 1 scan, 2 scan + last panel of V^T not stored
 };
+// What launch_chol2_panel decides per launch, as a host function of its own (the tests read it through
+// lsspa_debug_panel_plan): n_lt L tiles per matrix and n_x X tiles per ordering (has_X: X tiles are computed), n_ord as
+// the kernel counts orderings (n_mats without X tiles), p_live clamped to p_pad, the 1-D grid, grouped (the workgroup
+// -> (matrix, tile) map that walks eight matrices at a time) and xlast (the instantiation that leaves the last
+// panel's dead columns out).  false: launch_chol2_panel refuses these arguments.
+struct PanelPlan {
+  int n_lt, n_x, n_ord, p_live, grouped, xlast;
+  int64_t grid;
+};
+bool panel_plan(int p_pad, int Jo, int n_mats, int n_ord, bool has_X, int p_live, PanelPlan* out);
 hipError_t launch_chol2_panel(void* A, void* Dinv, const double* diag0, double piv_tol, int32_t* info, int p_pad,
                               int Jo, int n_mats, int f32, hipStream_t st, int flags = 0, int p_live = 0,
                               void* X = nullptr, int n_ord = 0, const PanelLift* pl = nullptr);

@@ -308,6 +308,16 @@ int dev_alloc(lsspa_ctx* ctx, DevBuf<T>& b, size_t count) {
 
 inline int round_up(int x, int q) { return ((x + q - 1) / q) * q; }
 
+// The shape rules of the general path, in one place for set_dims, run_slice and lsspa_debug_panel_plan:
+// the two-level factorisation walks 128-wide panels of the p features and the carried row;
+inline int work_p_pad(int p) { return round_up(p + 1, 128); }
+// rows and columns of a work matrix at or beyond this are identity / zero padding, written by the gather;
+inline int work_p_live(int p) { return round_up(p + 1, 16); }
+// tri mode computes V^T inside the panel launches; rect mode (and developer flag 128) uses the strip kernel;
+inline bool vt_rule(int tri, int flags) { return tri && !(flags & 128); }
+// panel steps Jo = 0 .. p_pad / 128 - 2; with V^T one more (X tiles only): step Jo also computes block column Jo of V^T
+inline int panel_launches(int p_pad, bool vt) { return p_pad / 128 - 1 + (vt ? 1 : 0); }
+
 struct ProfScope {
   lsspa_ctx* ctx;
   ProfRec rec;
@@ -446,7 +456,7 @@ int set_dims(lsspa_ctx* ctx, int p, int m, int tri) {
   ctx->p = p;
   ctx->m = m;
   ctx->tri = tri;
-  ctx->p_pad = round_up(p + 1, 128);   // the two-level factorisation walks 128-wide panels
+  ctx->p_pad = work_p_pad(p);
   ctx->m_pad = round_up(m, 128);
   const size_t pp = (size_t)ctx->p_pad;
   TRY(dev_alloc(ctx, ctx->G, (size_t)p * pp));
@@ -524,7 +534,7 @@ size_t v_elems_per_ordering(const lsspa_ctx* ctx) {
 }
 
 // tri mode computes V^T inside the panel launches; rect mode (and developer flag 128) uses the strip kernel
-static inline bool vt_path(const lsspa_ctx* ctx) { return ctx->tri && !(ctx->flags & 128); }
+static inline bool vt_path(const lsspa_ctx* ctx) { return vt_rule(ctx->tri, ctx->flags); }
 // the X tiles scan their own blocks of V^T for the lifts (developer flag 512: the lift kernel reads V^T back instead)
 static inline bool fused_scan(const lsspa_ctx* ctx) { return vt_path(ctx) && !(ctx->flags & 512); }
 
@@ -743,8 +753,7 @@ int run_slice(lsspa_ctx* ctx, Lane& L, int ord_off, int n_ord, int per_sample, i
     HIPCHK(launch_chol2_diag(A_s, Dinv_s, diag0_s, piv_tol, ctx->info_d.ptr, p_pad, n_mats, ctx->f32, st,
                              fused_scan(ctx) ? L.row_flags.ptr + (size_t)ord_off * n_src : nullptr));
   }
-  // panel steps; with vt one more (X tiles only): step Jo also computes block column Jo of V^T
-  const int n_panel = p_pad / 128 - 1;
+  const int n_launch = panel_launches(p_pad, vt);
   PanelLift pl;
   pl.mode = 0;
   if (fused_scan(ctx)) {
@@ -756,11 +765,11 @@ int run_slice(lsspa_ctx* ctx, Lane& L, int ord_off, int n_ord, int per_sample, i
     // the factors themselves are wanted (debug_factor reads V^T back): keep the last panel's stores
     pl.mode = ctx->general_path_once ? 1 : 2;
   }
-  for (int Jo = 0; Jo < n_panel + (vt ? 1 : 0); ++Jo) {
+  for (int Jo = 0; Jo < n_launch; ++Jo) {
     {
       ProfScope ps(timed ? ctx : nullptr, LSSPA_K_CHOL_PANEL, st);
       HIPCHK(launch_chol2_panel(A_s, Dinv_s, diag0_s, piv_tol, ctx->info_d.ptr, p_pad, Jo, n_mats, ctx->f32, st,
-                                ctx->flags, round_up(p + 1, 16), vt ? V_s : nullptr, n_ord, pl.mode ? &pl : nullptr));
+                                ctx->flags, work_p_live(p), vt ? V_s : nullptr, n_ord, pl.mode ? &pl : nullptr));
     }
     // two lanes: the other lane's next batch may start once this one is about half done
     // (the hand-over point scanned at the C3 shape, round 4, eight launches: after launch 0 / 1 / 2 / 3 / 4 / 5 / 6 / 7 ->
@@ -768,8 +777,7 @@ int run_slice(lsspa_ctx* ctx, Lane& L, int ord_off, int n_ord, int per_sample, i
     // (with two half-batches per step on the two lanes, 20 steps: after launch 1 / 2 / 3 / 4 / 5 -> 6.24 / 6.22 / 6.19 /
     // 6.28 / 6.38 ms)
     static const int handover_env = [] { const char* e = getenv("LSSPA_HANDOVER"); return e ? atoi(e) : -1; }();
-    const int handover = handover_env >= 0 ? std::min(handover_env, n_panel + (vt ? 1 : 0) - 1)
-                                           : std::max(0, (n_panel + (vt ? 1 : 0)) / 2 - 1);
+    const int handover = handover_env >= 0 ? std::min(handover_env, n_launch - 1) : std::max(0, n_launch / 2 - 1);
     if (L.mid_armed && timed && Jo == handover) {
       HIPCHK(hipEventRecord(L.ev_mid, st));
       L.mid_valid = true;
@@ -792,8 +800,8 @@ int run_slice(lsspa_ctx* ctx, Lane& L, int ord_off, int n_ord, int per_sample, i
     sa.n_ord = n_ord;
     sa.tri = ctx->tri;
     sa.flags = ctx->flags;
-    sa.row_live = round_up(p + 1, 16);
-    sa.col_live = ctx->tri ? round_up(p + 1, 16) : round_up(ctx->m, 16);
+    sa.row_live = work_p_live(p);
+    sa.col_live = ctx->tri ? work_p_live(p) : round_up(ctx->m, 16);
     HIPCHK(launch_strip(sa, st));
   }
   {
@@ -3028,6 +3036,46 @@ int lsspa_debug_gram_plan(int64_t n, int32_t p, int32_t* n_split, int32_t* cnt3,
   }
   *nt = g.nt;
   *xlive = g.xlive;
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
+}
+
+static void panel_plan_out(int Jo, const PanelPlan& pp, int32_t* o) {
+  o[0] = Jo;
+  o[1] = pp.n_lt;
+  o[2] = pp.n_x;
+  o[3] = pp.grouped;
+  o[4] = pp.xlast;
+  o[5] = (int32_t)pp.grid;      // panel_plan refuses a grid beyond 2^31 - 1
+  o[6] = pp.p_live;
+  o[7] = pp.n_ord;
+}
+
+int lsspa_debug_panel_plan(int32_t p, int32_t n_ord, int32_t tri, int32_t flags, int32_t* p_pad, int32_t* n_mats,
+                           int32_t* n_launch, int32_t* plans, int32_t cap) try {
+  if (p < 1 || p > max_features() || n_ord < 1 || n_ord > 0x3fffffff || !p_pad || !n_mats || !n_launch || cap < 0 ||
+      (cap > 0 && !plans))
+    return LSSPA_ERR_ARG;
+  const bool vt = vt_rule(tri, flags);
+  *p_pad = work_p_pad(p);
+  *n_mats = (tri ? 2 : 1) * n_ord;
+  *n_launch = panel_launches(*p_pad, vt);
+  for (int Jo = 0; Jo < *n_launch && Jo < cap; ++Jo) {
+    PanelPlan pp;
+    if (!panel_plan(*p_pad, Jo, *n_mats, n_ord, vt, work_p_live(p), &pp)) return LSSPA_ERR_ARG;
+    panel_plan_out(Jo, pp, plans + 8 * Jo);
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
+}
+
+int lsspa_debug_panel_plan_launch(int32_t p_pad, int32_t Jo, int32_t n_mats, int32_t n_ord, int32_t has_X,
+                                  int32_t p_live, int32_t* plan) try {
+  PanelPlan pp;
+  if (!plan || !panel_plan(p_pad, Jo, n_mats, n_ord, has_X != 0, p_live, &pp)) return LSSPA_ERR_ARG;
+  panel_plan_out(Jo, pp, plan);
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_ARG;

@@ -120,6 +120,43 @@ def debug_gram_plan(n: int, p: int):
             "slices": [int(v) for v in sl], "rps": [int(v) for v in rps]}
 
 
+PANEL_PLAN_FIELDS = ("Jo", "n_lt", "n_x", "grouped", "xlast", "grid", "p_live", "n_ord")
+
+
+def debug_panel_plan(p: int, n_ord: int, tri: bool, flags: int = 0):
+    """Test hook, host only: the panel launches of the general path for n_ord orderings at p features (include/lsspa.h,
+    lsspa_debug_panel_plan) -- a dict of p_pad, n_mats and launches, a list with one dict of PANEL_PLAN_FIELDS per
+    launch (grouped and xlast as bool)."""
+    pp, nm, nl = C.c_int32(), C.c_int32(), C.c_int32()
+    fn = N.load().lsspa_debug_panel_plan
+    rc = fn(int(p), int(n_ord), int(bool(tri)), int(flags), C.byref(pp), C.byref(nm), C.byref(nl), None, 0)
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_panel_plan: status {rc}")
+    out = np.zeros((nl.value, 8), dtype=np.int32)
+    rc = fn(int(p), int(n_ord), int(bool(tri)), int(flags), C.byref(pp), C.byref(nm), C.byref(nl), N.iptr(out),
+            nl.value)
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_panel_plan: status {rc}")
+    return {"p_pad": pp.value, "n_mats": nm.value, "launches": [_panel_plan_dict(row) for row in out]}
+
+
+def debug_panel_plan_launch(p_pad: int, Jo: int, n_mats: int, n_ord: int, has_X: bool, p_live: int):
+    """Test hook, host only: one panel launch from launch_chol2_panel's own arguments, a dict of PANEL_PLAN_FIELDS;
+    ValueError for what the launch refuses (include/lsspa.h, lsspa_debug_panel_plan_launch)."""
+    out = np.zeros(8, dtype=np.int32)
+    rc = N.load().lsspa_debug_panel_plan_launch(int(p_pad), int(Jo), int(n_mats), int(n_ord), int(bool(has_X)),
+                                                int(p_live), N.iptr(out))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_panel_plan_launch: status {rc}")
+    return _panel_plan_dict(out)
+
+
+def _panel_plan_dict(row):
+    d = dict(zip(PANEL_PLAN_FIELDS, (int(v) for v in row)))
+    d["grouped"], d["xlast"] = bool(d["grouped"]), bool(d["xlast"])
+    return d
+
+
 class HipEngine:
     """One MI355X.  Raises LSSPANativeError when the HIP library or the GPU is missing."""
 

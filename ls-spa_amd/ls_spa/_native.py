@@ -90,6 +90,8 @@ SIGNATURES = {
     "lsspa_debug_lift_inject": (C.c_int, [_vp, _pd, _i32, _pi32]),
     "lsspa_debug_stats_slices": (C.c_int, [_i32, _i32, _pi32, _pi32, _pi32]),
     "lsspa_debug_gram_plan": (C.c_int, [_i64, _i32, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32]),
+    "lsspa_debug_panel_plan": (C.c_int, [_i32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _i32]),
+    "lsspa_debug_panel_plan_launch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _pi32]),
     "lsspa_debug_reduce_chunk_rows": (C.c_int, [_vp, _i64]),
     "lsspa_host_argsort_rows": (C.c_int, [_pd, _i64, _i32, _pi32, C.POINTER(C.c_uint8), _i32, _pi64]),
     "lsspa_sampler_create": (C.c_int, [_i32, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dbl, _i64, _i32, _i64,
