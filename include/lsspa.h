@@ -336,6 +336,64 @@ int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, d
 int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, const uint64_t* masks,
                                    int64_t n, double* u /* [n][m] */);
 
+/* SAMPLED attribution of MANY RESPONSES on one design matrix (p <= 104): the lift vectors of m targets for the same
+ * orderings.  Of an ordering's work the two factorisations G_pi = L L^T, H_pi = L_t L_t^T and V = L^-1 L_t are O(p^3)
+ * and the same for every response; only z_r = L^-1 g_r[pi], y~_r = L_t^-1 h_r[pi] and the lift scan over V are O(p^2)
+ * per response.  A workgroup of csrc/k_small_multi.hip carries 8 responses as 8 augmented rows of the two work
+ * matrices (both resident in LDS) through one gather, one pair of factorisations and one V solve; the grid is
+ * orderings x chunks of 8 responses.  The reduced form is lsspa_multi_load's.  fp64 throughout.
+ *   lsspa_multi_lift_load   : arguments and the one Gram pass per side over [X | Y] as lsspa_multi_load's.  Limits:
+ *                     1 <= p <= LSSPA_MULTI_LIFT_MAX_P, m >= 1, p + m <= 32767, and M >= p (H must have a Cholesky
+ *                     factor); a column of Y_test that is identically zero (or NaN) is refused.  Each refusal is
+ *                     LSSPA_ERR_ARG naming the limit.  Clears the running statistics and the info word.  The loaded
+ *                     problem, the sampling path's statistics and the state of lsspa_subsets_*, lsspa_groups_*,
+ *                     lsspa_boot_* and lsspa_multi_* are not touched, now or by any call below.
+ *   lsspa_multi_lift_set_reduced : the same from the Gram form (host): G, H [p][p], g, h [m][p], yy [m].
+ *   lsspa_multi_lift_batch  : perms [B][p], every row a permutation of 0 .. p-1 (else LSSPA_ERR_ARG).  Sample s is
+ *                     ordering s, with antithetical != 0 the mean of ordering s and its reverse.  lifts_out [B][m][p]
+ *                     (may be NULL): lifts_out[s][r][j] = the lift of feature j for response r in sample s.
+ *                     accumulate != 0 folds the batch into the running (n, mean, M2) per (response, feature): Welford
+ *                     over the batch in sample order, one Chan merge into the state, no atomics.  The batch is cut into
+ *                     launches of whole samples (at most 2^16 workgroups and 256 MB of lift vectors a launch, a cut that
+ *                     depends on B, m and p alone).  Returns when the batch is done.
+ *   lsspa_multi_lift_get    : n, mean [m][p], m2 [m][p] (any pointer may be NULL); waits for work in flight.
+ *   lsspa_multi_lift_reset  : n = 0, the info word cleared.
+ *   lsspa_multi_lift_get_gram : the reduced form back, as lsspa_multi_get_gram.
+ *   lsspa_multi_lift_info   : one word -- G and H are shared, so a failed pivot (LSSPA_INFO_NOT_PD) concerns every
+ *                     response.  Only the pivots j < p of either matrix count, with the relative test 16 p eps; the
+ *                     augmented rows' own pivots never raise it (a response in the span of X is as good as any other).
+ *   lsspa_multi_lift_timing : device ms of the last load's two Gram passes, of the last batch's lift launches and of its
+ *                     statistics launches (any pointer may be NULL).
+ *   lsspa_multi_lift_free   : frees the responses, the statistics and the buffers.
+ * LSSPA_ERR_STATE before a load (lsspa_multi_lift_free and lsspa_multi_lift_timing excepted: freeing nothing is not an
+ * error, as for lsspa_multi_free); LSSPA_ERR_NOMEM when device memory runs out.
+ * Contract: two calls agree bitwise (the antithetical pair's two terms are added into a zeroed destination, a sum that
+ * commutes).  The bits of response r's lifts depend on G, H, the ordering, its own g_r, h_r, yy_r, p and its slot
+ * r mod 8 -- not on the other responses' values, on m beyond the slot, on B, on the other orderings of the batch or on
+ * how a batch is cut.  Independence of the slot itself is NOT promised: the augmented rows may straddle a 16-row block
+ * edge and then take another, equally accurate, route; across slots the results agree to the accuracy of the
+ * one-response path (tests/test_gpu_multi_sampled.py).
+ * Measured on one MI355X (tools/multi_sampled_time.py, on top of commit cd86a46; N = M = 10^4, 256 antithetical samples a
+ * batch): a batch costs 0.0092 ms a response at p = 40, m = 8 and 0.0085 ms at m = 64 against lsspa_lift_batch's 0.029 ms
+ * on one response (ratios 0.31 and 0.30), 0.0221 and 0.0208 ms at p = 100 against 0.064 ms (0.34 and 0.33); the whole call
+ * of the Python driver against the loop of m one-response calls 8.7 x and 49 x at p = 40, 13.5 x and 60 x at p = 100
+ * (DESIGN.md has the tables). */
+#define LSSPA_MULTI_LIFT_MAX_P 104
+int lsspa_multi_lift_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
+                          int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test,
+                          int64_t M, int32_t p, int32_t m, double reg, int32_t dtype, int32_t location);
+int lsspa_multi_lift_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* G /* [p][p] */,
+                                 const double* g /* [m][p] */, const double* H /* [p][p] */,
+                                 const double* h /* [m][p] */, const double* yy /* [m] */);
+int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms /* [B][p] */, int64_t B, int32_t antithetical,
+                           double* lifts_out /* [B][m][p] or NULL */, int32_t accumulate);
+int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean /* [m][p] */, double* m2 /* [m][p] */);
+int lsspa_multi_lift_reset(lsspa_ctx* ctx);
+int lsspa_multi_lift_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy);
+int lsspa_multi_lift_info(lsspa_ctx* ctx, int32_t* info);
+int lsspa_multi_lift_timing(const lsspa_ctx* ctx, double* gram_ms, double* batch_ms, double* stats_ms);
+int lsspa_multi_lift_free(lsspa_ctx* ctx);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

@@ -451,6 +451,34 @@ hipError_t launch_multi_groups_enum(const MultiGroupArgs& a, uint64_t units, uin
 hipError_t launch_multi_groups_debug(const MultiGroupArgs& a, const uint64_t* masks, int64_t n, double* vals, int m,
                                      int r0, hipStream_t st);
 
+// Sampled attribution of many responses on one design matrix (k_small_multi.hip), p <= MLIFT_MAX_P, fp64: k_small.hip's
+// LDS-resident kernel with MLIFT_RB augmented rows.  One workgroup per (ordering, chunk of MLIFT_RB responses): the grid
+// is (n_samples * per_sample) x ceil(count / MLIFT_RB).  With per_sample == 2 ordering 2 s + 1 is sample s's read
+// backwards and each adds half its lift vectors to sample s (lifts must be zero beforehand); with 1 they are stored.
+constexpr int MLIFT_MAX_P = 104, MLIFT_RB = 8;
+struct MultiLiftArgs {
+  const double* G;         // [p][ld] training Gram, shared by the responses
+  const double* H;         // [p][ld] test Gram
+  int64_t ld;
+  const double* g;         // [count][p] per response
+  const double* h;         // [count][p]
+  const double* yy;        // [count] ||y_r||^2
+  double aug[2];           // diagonal of the augmented rows (train, test): above the sum of any MLIFT_RB responses'
+                           // ||L^-1 g_r||^2 (||L_t^-1 h_r||^2), so that their unused trailing corner stays positive definite
+  const int32_t* perms;    // [n_samples][p]
+  int p, nb, n_samples, per_sample, count;   // nb = ceil((p + MLIFT_RB) / 16)
+  int m;                   // responses of a sample's block of lifts (>= count)
+  double* lifts;           // [n_samples][m][p]
+  double piv_tol;          // relative pivot test of the pivots j < p: d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
+  int32_t* info;           // one word: G and H are shared
+};
+size_t multi_lift_lds_bytes(int nb);
+hipError_t launch_multi_lift(const MultiLiftArgs& a, hipStream_t st);
+// (n, mean, M2) [entries] += the n_b lift vectors lifts [n_b][entries]: Welford over the batch in sample order, then one
+// Chan merge into the state of n_old samples.  No atomics: two runs agree bitwise.
+hipError_t launch_multi_lift_stats(const double* lifts, int64_t entries, int n_b, int64_t n_old, double* mean, double* M2,
+                                   hipStream_t st);
+
 // Bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp), p <= SUBSETS_MAX_P -- over groups of columns
 // p <= GROUPS_MAX_P (cb = 4, 5) --, fp64.  Z = [X | y] of one side
 // lives on the device as [n][ldz], ldz = 16 cb, cb = ceil((p + 1) / 16), columns beyond p zero.  A BLOCK of replicates

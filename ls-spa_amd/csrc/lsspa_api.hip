@@ -109,6 +109,28 @@ struct MultiWork {
   }
 };
 
+// What the sampled attribution of many responses keeps (lsspa_multi_lift_load / lsspa_multi_lift_set_reduced ..
+// lsspa_multi_lift_free): the shared G and H, one g, h and ||y||^2 per response, the orderings and lift vectors of one
+// launch, the running (n, mean, M2) per (response, feature) and the last calls' timing.  Nothing of the loaded problem,
+// the sampling path's statistics, the enumerations, the bootstrap or lsspa_multi_* is in here.
+struct MultiLiftWork {
+  bool loaded = false;
+  int p = 0, m = 0;
+  double aug[2] = {1.0, 1.0};              // diagonal of the augmented rows (MultiLiftArgs::aug)
+  DevBuf<double> G, H, g, h, yy;           // [p][p], [p][p], [m][p], [m][p], [m]
+  DevBuf<double> lifts, mean, M2;          // [samples of a launch][m][p]; the running state [m][p]
+  DevBuf<int32_t> perms, info;             // [samples of a launch][p]; the info word
+  int64_t n = 0;                           // samples folded into (mean, M2)
+  std::vector<double> Gh, Hh, gh, hh, yyh; // the reduced form on the host (lsspa_multi_lift_get_gram)
+  double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
+  void release() {
+    dev_free(G); dev_free(H); dev_free(g); dev_free(h); dev_free(yy); dev_free(lifts); dev_free(mean); dev_free(M2);
+    dev_free(perms); dev_free(info);
+    loaded = false;
+    n = 0;
+  }
+};
+
 }  // namespace
 
 // One lane = everything a batch of orderings needs while its kernels run: work matrices, solve results, staged
@@ -240,6 +262,7 @@ struct lsspa_ctx {
   ExactWork sub, grp;
   BootWork boot;                 // bootstrap of the exact attribution (lsspa_boot_*)
   MultiWork multi;               // exact attribution of many responses at once (lsspa_multi_*)
+  MultiLiftWork mlift;           // sampled attribution of many responses (lsspa_multi_lift_*)
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -1253,6 +1276,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->grp.release();
   ctx->boot.release();
   ctx->multi.release();
+  ctx->mlift.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
   dev_free(ctx->pr_delta); dev_free(ctx->pr_lifts); dev_free(ctx->pr_pos); dev_free(ctx->pr_perms);
@@ -4456,23 +4480,23 @@ struct MultiScratch {
   }
 };
 
-}  // namespace
+// the array arguments of a load from the rows (lsspa_multi_load, lsspa_multi_lift_load)
+bool multi_sides_ok(const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train, int64_t N,
+                    const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M, int32_t p,
+                    int32_t m, double reg, int32_t dtype, int32_t location) {
+  return !(!X_train || !Y_train || !X_test || !Y_test || N < 1 || M < 1 || ld_train < p || ld_test < p || ldy_train < m ||
+           ldy_test < m || !(reg >= 0.0) || !std::isfinite(reg) || (dtype != LSSPA_F64 && dtype != LSSPA_F32) ||
+           (location != LSSPA_HOST && location != LSSPA_DEVICE));
+}
 
-extern "C" {
-
-int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
-                     int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M,
-                     int32_t p, int32_t m, double reg, int32_t dtype, int32_t location) try {
-  if (!ctx) return LSSPA_ERR_ARG;
-  TRY(multi_limits(ctx, "lsspa_multi_load", p, m));
-  if (!X_train || !Y_train || !X_test || !Y_test || N < 1 || M < 1 || ld_train < p || ld_test < p || ldy_train < m ||
-      ldy_test < m || !(reg >= 0.0) || !std::isfinite(reg) || (dtype != LSSPA_F64 && dtype != LSSPA_F32) ||
-      (location != LSSPA_HOST && location != LSSPA_DEVICE))
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_load: NULL array, N or M < 1, ld < p, ldy < m, reg not finite and >= 0, "
-                                    "or bad dtype / location");
-  HIPCHK(hipSetDevice(ctx->device));
-  MultiWork& W = ctx->multi;
-  W.loaded = false;
+// One Gram pass per side over Z = [X | Y] -> the reduced form on the host: G = X^T X / N + reg I and H = X_te^T X_te
+// [p][p], g = X^T Y / N and h = X_te^T Y_te [m][p], yy [m] = the test responses' squared norms; gram_ms: the two passes'
+// kernel time.  The arguments have been checked (multi_sides_ok and the caller's limits).
+int multi_reduce_sides(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
+                       int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M,
+                       int32_t p, int32_t m, double reg, int32_t dtype, int32_t location, std::vector<double>& G,
+                       std::vector<double>& g, std::vector<double>& H, std::vector<double>& h, std::vector<double>& yy,
+                       double& gram_ms) {
   const size_t es = dtype == LSSPA_F32 ? 4 : 8;
   const int cols = p + m - 1;                      // launch_gram's "features": Z = [X | Y] has cols + 1 columns
   const size_t P1pad = (size_t)round_up(p + m, 128);
@@ -4483,8 +4507,9 @@ int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, cons
   const void* X[2] = {X_train, X_test};
   const void* Y[2] = {Y_train, Y_test};
   const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test}, ldy[2] = {ldy_train, ldy_test};
-  std::vector<double> rows[2], cross[2], yy((size_t)m);
-  W.gram_ms = 0.0;
+  std::vector<double> rows[2], cross[2];
+  yy.assign((size_t)m, 0.0);
+  gram_ms = 0.0;
   for (int s = 0; s < 2; ++s) {
     // [X | Y[:, :m-1]] as launch_gram's X and Y's last column as its y
     TRY(dev_alloc(ctx, S.zx, (size_t)n[s] * cols * es));
@@ -4513,10 +4538,13 @@ int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, cons
     HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
-    W.gram_ms += ms;
+    gram_ms += ms;
   }
   const double scale = 1.0 / (double)N;
-  std::vector<double> G((size_t)p * p), H((size_t)p * p), g((size_t)m * p), h((size_t)m * p);
+  G.assign((size_t)p * p, 0.0);
+  H.assign((size_t)p * p, 0.0);
+  g.assign((size_t)m * p, 0.0);
+  h.assign((size_t)m * p, 0.0);
   for (int a = 0; a < p; ++a) {
     for (int b = 0; b < p; ++b) {
       const size_t lo = a >= b ? a * P1pad + b : b * P1pad + a;
@@ -4528,6 +4556,28 @@ int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, cons
       h[(size_t)r * p + a] = cross[1][(size_t)r * p + a];
     }
   }
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_multi_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
+                     int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test, int64_t M,
+                     int32_t p, int32_t m, double reg, int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(multi_limits(ctx, "lsspa_multi_load", p, m));
+  if (!multi_sides_ok(X_train, ld_train, Y_train, ldy_train, N, X_test, ld_test, Y_test, ldy_test, M, p, m, reg, dtype,
+                      location))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_load: NULL array, N or M < 1, ld < p, ldy < m, reg not finite and >= 0, "
+                                    "or bad dtype / location");
+  HIPCHK(hipSetDevice(ctx->device));
+  MultiWork& W = ctx->multi;
+  W.loaded = false;
+  std::vector<double> G, g, H, h, yy;
+  TRY(multi_reduce_sides(ctx, X_train, ld_train, Y_train, ldy_train, N, X_test, ld_test, Y_test, ldy_test, M, p, m, reg,
+                         dtype, location, G, g, H, h, yy, W.gram_ms));
   return multi_store(ctx, p, m, G.data(), g.data(), H.data(), h.data(), yy.data());
 } catch (...) {
   return abi_caught(ctx);
@@ -4706,6 +4756,303 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (bits & LSSPA_INFO_NOT_PD)
     return ctx->fail(LSSPA_ERR_STATE, "a group subset's Gram matrix is not positive definite");
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+}  // extern "C"
+
+// ---- sampled attribution of many responses on one design matrix (k_small_multi.hip) ----------------------------------
+// The reduced form is lsspa_multi_load's (one Gram pass per side over Z = [X | Y]).  A batch of orderings runs as
+// launches of whole samples, a launch's grid (orderings of its samples) x (chunks of MLIFT_RB responses); its lift vectors
+// [samples][m][p] are folded into the running (n, mean, M2) [m][p] by a launch of their own and copied out if asked for.
+namespace {
+
+constexpr int64_t MLIFT_GRID_PER_LAUNCH = 1 << 16;            // workgroups a launch takes at most (one sample at least)
+constexpr int64_t MLIFT_LIFT_DOUBLES = (256ll << 20) / 8;     // lift vectors of a launch: 256 MB at most (one sample at least)
+
+int mlift_limits(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
+  char msg[200];
+  if (p < 1 || p > MLIFT_MAX_P) {
+    snprintf(msg, sizeof msg, "%s takes 1 <= p <= %d features (%lld given): both work matrices and %d augmented rows "
+             "stay in a compute unit's LDS", name, MLIFT_MAX_P, (long long)p, MLIFT_RB);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (m < 1 || p + m > MULTI_MAX_COLS) {
+    snprintf(msg, sizeof msg, "%s takes m >= 1 responses with p + m <= %lld (p = %lld, m = %lld given)", name,
+             (long long)MULTI_MAX_COLS, (long long)p, (long long)m);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+int mlift_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->mlift.loaded)
+    return ctx->fail(LSSPA_ERR_STATE, "no responses loaded (lsspa_multi_lift_load or lsspa_multi_lift_set_reduced comes "
+                                      "first)");
+  return LSSPA_OK;
+}
+
+// max over the responses of ||L^-1 b_r||^2, A = L L^T [p][p], b [m][p]: what the diagonal of the augmented rows has to
+// exceed (MultiLiftArgs::aug).  A pivot that is not positive is replaced by 1, as the kernels do (they flag it).
+double mlift_rhs_bound(int p, int m, const double* A, const double* b) {
+  std::vector<double> L(A, A + (size_t)p * p), z((size_t)p);
+  for (int j = 0; j < p; ++j) {
+    double d = L[(size_t)j * p + j];
+    for (int k = 0; k < j; ++k) d -= L[(size_t)j * p + k] * L[(size_t)j * p + k];
+    if (!(d > 0.0) || !std::isfinite(d)) d = 1.0;
+    const double ljj = std::sqrt(d);
+    L[(size_t)j * p + j] = ljj;
+    for (int i = j + 1; i < p; ++i) {
+      double v = L[(size_t)i * p + j];
+      for (int k = 0; k < j; ++k) v -= L[(size_t)i * p + k] * L[(size_t)j * p + k];
+      L[(size_t)i * p + j] = v / ljj;
+    }
+  }
+  double worst = 0.0;
+  for (int r = 0; r < m; ++r) {
+    double nn = 0.0;
+    for (int i = 0; i < p; ++i) {
+      double v = b[(size_t)r * p + i];
+      for (int k = 0; k < i; ++k) v -= L[(size_t)i * p + k] * z[k];
+      z[i] = v / L[(size_t)i * p + i];
+      nn += z[i] * z[i];
+    }
+    if (nn > worst) worst = nn;
+  }
+  return std::isfinite(worst) ? worst : 0.0;
+}
+
+// the reduced form (host arrays: G, H [p][p], g, h [m][p], yy [m]) into the context; statistics and info word cleared
+int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, const double* H, const double* h,
+                const double* yy) {
+  MultiLiftWork& W = ctx->mlift;
+  W.loaded = false;
+  char msg[160];
+  for (int r = 0; r < m; ++r)
+    if (!(yy[r] > 0.0) || !std::isfinite(yy[r])) {
+      snprintf(msg, sizeof msg, "column %d of Y_test is identically zero (or NaN)", r);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  const size_t pp = (size_t)p * p, mp = (size_t)m * p;
+  W.Gh.assign(G, G + pp);
+  W.Hh.assign(H, H + pp);
+  W.gh.assign(g, g + mp);
+  W.hh.assign(h, h + mp);
+  W.yyh.assign(yy, yy + m);
+  // the augmented rows' trailing corner  aug I - Z Z^T  (Z: the z rows of a chunk) stays positive definite when aug
+  // exceeds the sum of the chunk's ||z_r||^2: twice MLIFT_RB times the largest, plus one
+  W.aug[0] = 1.0 + 2.0 * MLIFT_RB * mlift_rhs_bound(p, m, G, g);
+  W.aug[1] = 1.0 + 2.0 * MLIFT_RB * mlift_rhs_bound(p, m, H, h);
+  TRY(dev_alloc(ctx, W.G, pp));
+  TRY(dev_alloc(ctx, W.H, pp));
+  TRY(dev_alloc(ctx, W.g, mp));
+  TRY(dev_alloc(ctx, W.h, mp));
+  TRY(dev_alloc(ctx, W.yy, (size_t)m));
+  TRY(dev_alloc(ctx, W.mean, mp));
+  TRY(dev_alloc(ctx, W.M2, mp));
+  TRY(dev_alloc(ctx, W.info, 8));
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the buffers
+  HIPCHK(hipMemcpy(W.G.ptr, G, sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.H.ptr, H, sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.g.ptr, g, sizeof(double) * mp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.h.ptr, h, sizeof(double) * mp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.yy.ptr, yy, sizeof(double) * m, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
+  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
+  HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
+  W.p = p;
+  W.m = m;
+  W.n = 0;
+  W.batch_ms = W.stats_ms = 0.0;
+  W.loaded = true;
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_multi_lift_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* Y_train, int64_t ldy_train,
+                          int64_t N, const void* X_test, int64_t ld_test, const void* Y_test, int64_t ldy_test,
+                          int64_t M, int32_t p, int32_t m, double reg, int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_limits(ctx, "lsspa_multi_lift_load", p, m));
+  if (!multi_sides_ok(X_train, ld_train, Y_train, ldy_train, N, X_test, ld_test, Y_test, ldy_test, M, p, m, reg, dtype,
+                      location))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_load: NULL array, N or M < 1, ld < p, ldy < m, reg not finite and "
+                                    ">= 0, or bad dtype / location");
+  if (M < p) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "lsspa_multi_lift_load takes M >= p test rows (M = %lld, p = %d given): the test Gram "
+             "matrix must have a Cholesky factor", (long long)M, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  MultiLiftWork& W = ctx->mlift;
+  W.loaded = false;
+  std::vector<double> G, g, H, h, yy;
+  TRY(multi_reduce_sides(ctx, X_train, ld_train, Y_train, ldy_train, N, X_test, ld_test, Y_test, ldy_test, M, p, m, reg,
+                         dtype, location, G, g, H, h, yy, W.gram_ms));
+  return mlift_store(ctx, p, m, G.data(), g.data(), H.data(), h.data(), yy.data());
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* G, const double* g, const double* H,
+                                 const double* h, const double* yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_limits(ctx, "lsspa_multi_lift_set_reduced", p, m));
+  if (!G || !g || !H || !h || !yy) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_set_reduced: NULL array");
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->mlift.gram_ms = 0.0;
+  return mlift_store(ctx, p, m, G, g, H, h, yy);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int32_t antithetical, double* lifts_out,
+                           int32_t accumulate) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_need_loaded(ctx));
+  MultiLiftWork& W = ctx->mlift;
+  const int p = W.p, m = W.m;
+  if (!perms || B < 1 || B > (int64_t)INT32_MAX / p)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_batch: perms is NULL, B < 1 or B p >= 2^31");
+  if (!all_permutations(perms, (int)B, p, ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_batch: a row of perms is not a permutation of 0 .. p-1");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int per = antithetical ? 2 : 1;
+  const int64_t chunks = (m + MLIFT_RB - 1) / MLIFT_RB, entries = (int64_t)m * p;
+  // samples a launch: by the grid and by the lift vectors' bytes -- by B, m and p alone
+  const int64_t S = std::min(B, std::max<int64_t>(1, std::min(MLIFT_GRID_PER_LAUNCH / (per * chunks),
+                                                              MLIFT_LIFT_DOUBLES / entries)));
+  TRY(dev_alloc(ctx, W.lifts, (size_t)(S * entries)));
+  TRY(dev_alloc(ctx, W.perms, (size_t)(S * p)));
+  std::vector<hipEvent_t> ev(3, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  W.batch_ms = W.stats_ms = 0.0;
+  MultiLiftArgs a{};
+  a.G = W.G.ptr;
+  a.H = W.H.ptr;
+  a.ld = p;
+  a.g = W.g.ptr;
+  a.h = W.h.ptr;
+  a.yy = W.yy.ptr;
+  a.aug[0] = W.aug[0];
+  a.aug[1] = W.aug[1];
+  a.perms = W.perms.ptr;
+  a.p = p;
+  a.nb = (p + MLIFT_RB + 15) / 16;
+  a.per_sample = per;
+  a.count = a.m = m;
+  a.lifts = W.lifts.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.info = W.info.ptr;
+  for (int64_t s0 = 0; s0 < B; s0 += S) {
+    const int64_t ns = std::min(S, B - s0);
+    HIPCHK(hipMemcpyAsync(W.perms.ptr, perms + s0 * p, sizeof(int32_t) * (size_t)(ns * p), hipMemcpyHostToDevice,
+                          ctx->stream));
+    if (per == 2)     // the pair's two terms are added into a zeroed destination
+      HIPCHK(hipMemsetAsync(W.lifts.ptr, 0, sizeof(double) * (size_t)(ns * entries), ctx->stream));
+    a.n_samples = (int)ns;
+    HIPCHK(hipEventRecord(ev[0], ctx->stream));
+    HIPCHK(launch_multi_lift(a, ctx->stream));
+    HIPCHK(hipEventRecord(ev[1], ctx->stream));
+    if (accumulate) {
+      HIPCHK(launch_multi_lift_stats(W.lifts.ptr, entries, (int)ns, W.n, W.mean.ptr, W.M2.ptr, ctx->stream));
+      W.n += ns;
+    }
+    HIPCHK(hipEventRecord(ev[2], ctx->stream));
+    if (lifts_out)
+      HIPCHK(hipMemcpyAsync(lifts_out + s0 * entries, W.lifts.ptr, sizeof(double) * (size_t)(ns * entries),
+                            hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses both buffers
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    W.batch_ms += ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    if (accumulate) W.stats_ms += ms;
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_need_loaded(ctx));
+  MultiLiftWork& W = ctx->mlift;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t mp = (size_t)W.m * W.p;
+  if (n) *n = W.n;
+  if (mean) HIPCHK(hipMemcpy(mean, W.mean.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
+  if (m2) HIPCHK(hipMemcpy(m2, W.M2.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_reset(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_need_loaded(ctx));
+  MultiLiftWork& W = ctx->mlift;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t mp = (size_t)W.m * W.p;
+  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
+  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
+  HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
+  W.n = 0;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_need_loaded(ctx));
+  const MultiLiftWork& W = ctx->mlift;
+  if (G) std::copy(W.Gh.begin(), W.Gh.end(), G);
+  if (g) std::copy(W.gh.begin(), W.gh.end(), g);
+  if (H) std::copy(W.Hh.begin(), W.Hh.end(), H);
+  if (h) std::copy(W.hh.begin(), W.hh.end(), h);
+  if (yy) std::copy(W.yyh.begin(), W.yyh.end(), yy);
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_info(lsspa_ctx* ctx, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_need_loaded(ctx));
+  if (!info) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_info: info is NULL");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(info, ctx->mlift.info.ptr, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_multi_lift_timing(const lsspa_ctx* ctx, double* gram_ms, double* batch_ms, double* stats_ms) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (gram_ms) *gram_ms = ctx->mlift.gram_ms;
+  if (batch_ms) *batch_ms = ctx->mlift.batch_ms;
+  if (stats_ms) *stats_ms = ctx->mlift.stats_ms;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_multi_lift_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->mlift.release();
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

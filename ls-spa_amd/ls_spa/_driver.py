@@ -32,6 +32,7 @@ import numpy as np
 from . import _samplers as S
 from ._native import LSSPANativeError
 from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+                       SampledMultiResults,
                        MultiResponseResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
@@ -1564,6 +1565,116 @@ def ls_spa_interactions_sampled(X_train, X_test, y_train, y_test, reg=0., max_sa
     return SampledInteractionResults(interactions=_shap_matrix(phi, mean), attribution=phi, theta=theta,
                                      r_squared=r_squared, interaction_errors=pair_standard_errors(counts, m2),
                                      counts=counts, n_samples=int(n))
+
+
+MULTI_LIFT_MAX_P = 104     # include/lsspa.h, LSSPA_MULTI_LIFT_MAX_P
+
+
+def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2 ** 13, batch_size=2 ** 8,
+                         tolerance=None, seed=42, perms=None, *, method="random", antithetical=True, device=0,
+                         _engine=None):
+    """Sampled Shapley attribution of many responses on one design matrix (p <= 104): what ``ls_spa_multi`` gives
+    exactly for p <= 32, estimated from sampled orderings beyond that.
+
+    ``Y_train`` is [N][m] and ``Y_test`` [M][m] (a one-dimensional y counts as m = 1).  Every response sees the same
+    orderings, and of an ordering's work the two Cholesky factorisations and the triangular solve between them do not
+    depend on y: a workgroup carries eight responses through them at once, and only the O(p^2) lift scan is per response
+    (include/lsspa.h, lsspa_multi_lift_batch).  The rows of X are reduced once, by one Gram pass per side over [X | Y].
+    fp64 throughout; two calls agree bitwise.
+
+    Returns ``SampledMultiResults``: ``attribution`` [m][p] is the mean of the samples' lift vectors, row r an estimate
+    of what ``ls_spa(X_train, X_test, Y_train[:, r], Y_test[:, r], reg)`` estimates, and sums to ``r_squared[r]``;
+    ``attribution_errors`` [m][p] its standard errors sqrt(M2 / (n (n - 1))) (``inf`` while n < 2; indicative only for
+    the QMC sources and a caller's ``perms``, whose samples are not independent); ``theta`` [m][p] and ``r_squared`` [m]
+    the full models'; ``n_samples``.
+
+    max_samples, batch_size:  samples are drawn in batches of ``batch_size`` until ``max_samples``.
+    tolerance:  None (default): run to ``max_samples``.  Otherwise sampling stops after the first batch at which
+        n >= 2 and the largest standard error is <= tolerance.
+    method:  'random' (default), 'argsort', 'permutohedron', or 'exact' (all p! orderings, p up to 8 or 9): the ordering
+        sources of ``ls_spa``.
+    perms:  an iterable of orderings instead (leave ``method`` at its default).
+    antithetical:  a sample is the mean of an ordering and its reverse (default), as in ``ls_spa``.
+
+    Shapes that do not fit raise ``SizeIncompatible``; p > 104, M < p (the test Gram matrix must have a Cholesky factor)
+    or p + m > 32767 ValueError naming the limit, before any GPU work.  A column of ``Y_test`` that is identically zero
+    is a ValueError, a Gram matrix that is not numerically positive definite a RuntimeWarning (it is shared, so it
+    concerns every response); theta is then the solution of minimal norm.  Several ranks, checkpoints, ``groups=`` and
+    fp32 are not part of this function."""
+    X_train, X_test = np.asarray(X_train), np.asarray(X_test)
+    Y_train, Y_test = np.asarray(Y_train), np.asarray(Y_test)
+    if X_train.ndim != 2 or X_test.ndim != 2:
+        raise ValueError("X_train and X_test must be two-dimensional")
+    if Y_train.ndim == 1:
+        Y_train = Y_train[:, None]
+    if Y_test.ndim == 1:
+        Y_test = Y_test[:, None]
+    if Y_train.ndim != 2 or Y_test.ndim != 2:
+        raise ValueError("Y_train and Y_test must be [rows][m] (or one-dimensional for one response)")
+    if Y_train.shape[1] != Y_test.shape[1]:
+        raise SizeIncompatible("Y_train and Y_test should have the same number of columns (responses).")
+    validate_data(X_train, X_test, Y_train, Y_test)
+    p, m, M = X_train.shape[1], Y_train.shape[1], X_test.shape[0]
+    if p < 1 or m < 1:
+        raise ValueError(f"ls_spa_multi_sampled needs p >= 1 features and m >= 1 responses (p = {p}, m = {m})")
+    if p > MULTI_LIFT_MAX_P:
+        raise ValueError(f"ls_spa_multi_sampled takes at most p = {MULTI_LIFT_MAX_P} features (this problem has "
+                         f"p = {p}); use ls_spa per response")
+    if M < p:
+        raise ValueError(f"ls_spa_multi_sampled takes M >= p test rows (M = {M}, p = {p}): the test Gram matrix must "
+                         "have a Cholesky factor; use ls_spa per response")
+    if p + m > MULTI_MAX_COLS:
+        raise ValueError(f"ls_spa_multi_sampled takes p + m <= {MULTI_MAX_COLS} columns of [X | Y] (p = {p}, m = {m}); "
+                         "cut the responses into several calls")
+    if perms is not None:
+        if method != "random":
+            raise ValueError("pass either perms= or method=, not both")
+        method = None
+    elif method not in S.METHODS:
+        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
+    if int(batch_size) < 1 or int(max_samples) < 1:
+        raise ValueError("batch_size and max_samples must be positive")
+    _, source, batch_size, antithetical, max_samples, never_stop = prepare_sampling(
+        p, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
+        antithetical=bool(antithetical), method=method)
+    if never_stop:
+        tolerance = None
+    undo = [(lambda: _close_source(source), True)]
+    with _engine_call(_engine, device, undo=undo) as engine:
+        undo.append((engine.multi_lift_free, True))
+        engine.multi_lift_load(X_train, X_test, Y_train, Y_test, reg)
+        n, state = 0, None
+        while n < max_samples:
+            rows = source.take(min(batch_size, max_samples - n))
+            if len(rows) == 0:
+                break
+            engine.multi_lift_batch(rows, antithetical)
+            n += len(rows)
+            state = None
+            if tolerance is not None and n >= 2:
+                state = engine.multi_lift_get()      # the state is read once per batch
+                if _multi_standard_errors(state[0], state[2]).max() <= tolerance:
+                    break
+        if n == 0:
+            raise ValueError("no ordering to sample: perms is empty")
+        n, mean, m2 = state if state is not None else engine.multi_lift_get()
+        bits = engine.multi_lift_info()
+        theta, r_squared, singular = _multi_fit(*engine.multi_lift_gram())
+    bits |= int(singular)
+    # every sample's lifts of response r telescope to r_squared[r], so every row of the mean sums to it (the bound of
+    # LSSPA_INFO_SUM for well-conditioned data)
+    if not bits & 1 and not np.all(np.abs(mean.sum(axis=1) - r_squared) <= 1e-9 * np.maximum(1.0, np.abs(r_squared))):
+        bits |= 8
+    _info_verdict(bits, stacklevel=2)
+    return SampledMultiResults(attribution=mean, attribution_errors=_multi_standard_errors(n, m2), theta=theta,
+                               r_squared=r_squared, n_samples=int(n))
+
+
+def _multi_standard_errors(n, m2):
+    """Standard errors of the running means: sqrt(M2 / (n (n - 1))), inf while n < 2."""
+    if n < 2:
+        return np.full(np.shape(m2), np.inf)
+    return np.sqrt(np.maximum(m2, 0.0) / (float(n) * (n - 1.0)))
 
 
 # ------------------------------------------------------------------------------------------

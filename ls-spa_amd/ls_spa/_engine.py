@@ -553,6 +553,85 @@ class HipEngine:
         self._check(self._lib.lsspa_multi_free(self._h))
         self._multi_dims = None
 
+    # ---- sampled attribution of many responses on one design matrix (p <= 104) ----
+    MULTI_LIFT_MAX_P = 104     # include/lsspa.h, LSSPA_MULTI_LIFT_MAX_P
+
+    def multi_lift_load(self, X_train, X_test, Y_train, Y_test, reg: float):
+        """One Gram pass per side over [X | Y] (Y_train [N][m], Y_test [M][m]) for multi_lift_batch (include/lsspa.h,
+        lsspa_multi_lift_load); the loaded problem and the state of multi_load are not touched."""
+        dt = np.float32 if (X_train.dtype == np.float32 and X_test.dtype == np.float32) else np.float64
+        Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
+        Ya, Ye = np.ascontiguousarray(Y_train, dtype=dt), np.ascontiguousarray(Y_test, dtype=dt)
+        n, p = Xa.shape
+        m = Ya.shape[1]
+        self._check(self._lib.lsspa_multi_lift_load(
+            self._h, Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m, Xe.shape[0], p, m,
+            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._multi_lift_dims = (p, m)
+
+    def multi_lift_load_reduced(self, G, g, H, h, yy):
+        """The same from the Gram form: G, H [p][p], g, h [m][p], yy [m] (lsspa_multi_lift_set_reduced)."""
+        G, H = (np.ascontiguousarray(a, dtype=np.float64) for a in (G, H))
+        g, h = (np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64) for a in (g, h))
+        yy = np.ascontiguousarray(np.atleast_1d(yy), dtype=np.float64)
+        p, m = G.shape[0], g.shape[0]
+        if G.shape != (p, p) or H.shape != (p, p) or g.shape != (m, p) or h.shape != (m, p) or yy.shape != (m,):
+            raise ValueError("multi_lift_load_reduced takes G, H [p][p], g, h [m][p] and yy [m]")
+        self._check(self._lib.lsspa_multi_lift_set_reduced(self._h, p, m, N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
+                                                           N.dptr(yy)))
+        self._multi_lift_dims = (p, m)
+
+    def multi_lift_batch(self, perms, antithetical: bool, want_lifts: bool = False, accumulate: bool = True):
+        """The lift vectors of every response for the orderings perms [B][p] (with antithetical a sample is the mean of
+        an ordering and its reverse), folded into the running statistics if accumulate; lifts [B][m][p] if want_lifts
+        (include/lsspa.h, lsspa_multi_lift_batch).  The library checks the orderings."""
+        dims = getattr(self, "_multi_lift_dims", None)
+        p, m = dims or (1, 1)
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        if dims is None:                  # the library says what comes first
+            want_lifts = False
+        elif perms.ndim != 2 or perms.shape[1] != p:
+            raise ValueError(f"perms must be [B][p = {p}]")
+        out = np.empty((perms.shape[0], m, p)) if want_lifts else None
+        self._check(self._lib.lsspa_multi_lift_batch(self._h, N.iptr(perms) if perms.size else None, perms.shape[0],
+                                                     int(bool(antithetical)), N.dptr(out) if want_lifts else None,
+                                                     int(bool(accumulate))))
+        return out
+
+    def multi_lift_get(self):
+        """(n, mean [m][p], M2 [m][p]) of the samples folded in so far."""
+        p, m = getattr(self, "_multi_lift_dims", None) or (1, 1)
+        n, mean, m2 = C.c_int64(), np.empty((m, p)), np.empty((m, p))
+        self._check(self._lib.lsspa_multi_lift_get(self._h, C.byref(n), N.dptr(mean), N.dptr(m2)))
+        return n.value, mean, m2
+
+    def multi_lift_reset(self):
+        self._check(self._lib.lsspa_multi_lift_reset(self._h))
+
+    def multi_lift_gram(self):
+        """(G, g [m][p], H, h [m][p], yy [m]) of the loaded responses."""
+        p, m = getattr(self, "_multi_lift_dims", None) or (1, 1)
+        G, g, H, h, yy = np.empty((p, p)), np.empty((m, p)), np.empty((p, p)), np.empty((m, p)), np.empty(m)
+        self._check(self._lib.lsspa_multi_lift_get_gram(self._h, N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
+                                                        N.dptr(yy)))
+        return G, g, H, h, yy
+
+    def multi_lift_info(self) -> int:
+        info = C.c_int32()
+        self._check(self._lib.lsspa_multi_lift_info(self._h, C.byref(info)))
+        return info.value
+
+    def multi_lift_timing(self):
+        """Device seconds of the last multi_lift_load's Gram passes, of the last batch's lift launches and of its
+        statistics launches."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.lsspa_multi_lift_timing(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"gram": a.value / 1e3, "batch": b.value / 1e3, "stats": c.value / 1e3}
+
+    def multi_lift_free(self):
+        self._check(self._lib.lsspa_multi_lift_free(self._h))
+        self._multi_lift_dims = None
+
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()
         self._check(getter(self._h, C.byref(ms), C.byref(mx), C.byref(n)))

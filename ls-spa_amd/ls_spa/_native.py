@@ -152,6 +152,16 @@ SIGNATURES = {
     "lsspa_debug_multi_values": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64, _pd]),
     "lsspa_multi_groups_shapley": (C.c_int, [_vp, _pi32, _i32, _i64, _i64, _i64, _pd, _pi32]),
     "lsspa_debug_multi_group_values": (C.c_int, [_vp, _pi32, _i32, C.POINTER(C.c_uint64), _i64, _pd]),
+    "lsspa_multi_lift_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _dbl,
+                                        _i32, _i32]),
+    "lsspa_multi_lift_set_reduced": (C.c_int, [_vp, _i32, _i32, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_multi_lift_batch": (C.c_int, [_vp, _pi32, _i64, _i32, _pd, _i32]),
+    "lsspa_multi_lift_get": (C.c_int, [_vp, _pi64, _pd, _pd]),
+    "lsspa_multi_lift_reset": (C.c_int, [_vp]),
+    "lsspa_multi_lift_get_gram": (C.c_int, [_vp, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_multi_lift_info": (C.c_int, [_vp, _pi32]),
+    "lsspa_multi_lift_timing": (C.c_int, [_vp, _pd, _pd, _pd]),
+    "lsspa_multi_lift_free": (C.c_int, [_vp]),
 }
 
 

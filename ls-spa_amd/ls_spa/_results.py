@@ -159,6 +159,36 @@ class MultiGroupResults:
         return "\n".join(lines)
 
 
+@dataclass
+class SampledMultiResults:
+    """What ``ls_spa_multi_sampled`` returns for m responses on one design matrix.  ``attribution`` [m][p]: row r is the
+    mean of the ``n_samples`` lift vectors of response r, an estimate of its Shapley attribution; ``attribution_errors``
+    [m][p] the standard errors of those means, sqrt(M2 / (n (n - 1))), ``inf`` while n < 2.  They assume independent
+    samples: they are only indicative for the QMC sources ('argsort', 'permutohedron'), whose orderings are not
+    independent, and for a caller's ``perms``.  ``theta`` [m][p] the full-model coefficients of each response;
+    ``r_squared`` [m] their out-of-sample R^2 -- every sample's lifts telescope to it, so row r of ``attribution`` sums to
+    ``r_squared[r]``."""
+    attribution: np.ndarray
+    attribution_errors: np.ndarray
+    theta: np.ndarray
+    r_squared: np.ndarray
+    n_samples: int
+
+    def __repr__(self):
+        pad = " " * 8
+        att = np.asarray(self.attribution)
+        lines = [
+            "",
+            f"{pad}p = {att.shape[1]}, m = {att.shape[0]} responses, {self.n_samples} samples",
+            f"{pad}Out-of-sample R^2 with all features: {_head(self.r_squared)}",
+            "",
+            f"{pad}Shapley attribution of response 0: {_head(att[0])}",
+            f"{pad}Largest standard error: {float(np.max(self.attribution_errors)):.3g}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
 class SizeIncompatible(Exception):
     """Raised when the shapes of the four data arrays do not fit together."""
 
