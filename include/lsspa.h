@@ -356,6 +356,23 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels /* [p] 
  *                     over the batch in sample order, one Chan merge into the state, no atomics.  The batch is cut into
  *                     launches of whole samples (at most 2^16 workgroups and 256 MB of lift vectors a launch, a cut that
  *                     depends on B, m and p alone).  Returns when the batch is done.
+ *   lsspa_multi_lift_set_players : GROUPS of columns as the players, as lsspa_set_players names them: labels [p], -1 the
+ *                     baseline (the columns of every model), 0 .. g-1 the groups, each with a column at least (else
+ *                     LSSPA_ERR_ARG saying what is wrong).  labels = NULL, g = 0 clears the map.  Setting or clearing
+ *                     resets (n, mean, M2) and the info word; a new load, lsspa_multi_lift_set_reduced and
+ *                     lsspa_multi_lift_free drop the map.  The map is this path's alone: lsspa_set_players' map, the
+ *                     loaded problem and the state of lsspa_multi_* are not touched.  While a map is set,
+ *                     lsspa_multi_lift_batch takes perms [B][g], every row a permutation of 0 .. g-1, and lifts_out is
+ *                     [B][m][g]: lifts_out[s][r][k] = the summed lifts of group k's columns for response r when the
+ *                     group ordering is expanded to a column ordering with the baseline first and every group's columns
+ *                     contiguous and ascending; with antithetical != 0 the mean of that and of the expansion of the
+ *                     reversed group ordering (the baseline stays first).  The rows are expanded on the host; the kernel
+ *                     folds a response's p lifts to g in LDS -- one thread a group adds its columns in ascending order from
+ *                     0.0, no atomics in the fold -- and the pair's two workgroups each add half their group lift into the
+ *                     zeroed destination.  A group lift therefore has exactly the bits of that fold over the lifts_out
+ *                     of the call WITHOUT a map, antithetical = 0, on the same expanded rows (then 0.5 (a + b) for a
+ *                     pair), and the contract below holds with g for p.  The cut into launches depends on B, m, p and g
+ *                     alone.  lsspa_multi_lift_get returns [m][g].
  *   lsspa_multi_lift_get    : n, mean [m][p], m2 [m][p] (any pointer may be NULL); waits for work in flight.
  *   lsspa_multi_lift_reset  : n = 0, the info word cleared.
  *   lsspa_multi_lift_get_gram : the reduced form back, as lsspa_multi_get_gram.
@@ -385,6 +402,7 @@ int lsspa_multi_lift_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train,
 int lsspa_multi_lift_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const double* G /* [p][p] */,
                                  const double* g /* [m][p] */, const double* H /* [p][p] */,
                                  const double* h /* [m][p] */, const double* yy /* [m] */);
+int lsspa_multi_lift_set_players(lsspa_ctx* ctx, const int32_t* labels /* [p] or NULL */, int32_t g);
 int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms /* [B][p] */, int64_t B, int32_t antithetical,
                            double* lifts_out /* [B][m][p] or NULL */, int32_t accumulate);
 int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean /* [m][p] */, double* m2 /* [m][p] */);

@@ -23,6 +23,14 @@
 // slots' values enter only the corner and the other rows >= p.  The slot itself matters: the augmented rows may
 // straddle a 16-row block edge and then take another, equally accurate, route.
 //
+// GROUPED (lsspa_multi_lift_set_players): the players are groups of columns.  The orderings are then explicit rows -- the
+// host's expansions of the group orderings, baseline first, rows 2 s and 2 s + 1 the two of an antithetical sample -- and a
+// slot does not end with p lifts in HBM: they go to an LDS vector indexed by COLUMN, and one thread a group k < g adds its
+// columns cols[off[k] .. off[k+1]) in ascending order from 0.0 (k_players.hip's fold and its order: plain adds, one thread
+// a group) into out[sample][r][k].  Everything up to that epilogue is the column kernel's, line for line, so a group
+// lift has the bits of that fold over the column kernel's lifts for the same row.  The GROUPED = false instantiation is
+// the column kernel as it was.
+//
 // The second kernel folds a batch's lift vectors [B][m][p] into running (n, mean, M2) per entry: Welford over the batch
 // in sample order, one Chan merge into the state (k_pairs.hip's scheme), a thread an entry, no atomics.
 #include "kernels.h"
@@ -112,6 +120,7 @@ constexpr int MAXNB = (MLIFT_MAX_P + RB) / 16;     // 7
 
 }  // namespace
 
+template <bool GROUPED>
 __global__ __launch_bounds__(512) void multi_lift_kernel(MultiLiftArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int nb = a.nb, p = a.p;
@@ -124,6 +133,10 @@ __global__ __launch_bounds__(512) void multi_lift_kernel(MultiLiftArgs a) {
   double* const s_z = s_tol + 256;             // [RB][VEC]
   double* const s_y = s_z + RB * VEC;          // [RB][VEC]
   int32_t* const s_perm = reinterpret_cast<int32_t*>(s_y + RB * VEC);   // [128]
+  // GROUPED: a slot's lifts by column [VEC], then the player map's CSR off [g + 1] and cols [p - n_base], 128 words each
+  double* const s_lift = reinterpret_cast<double*>(s_perm + 128);
+  int32_t* const s_off = reinterpret_cast<int32_t*>(s_lift + VEC);
+  int32_t* const s_cols = s_off + 128;
   __shared__ int s_bad;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -134,10 +147,15 @@ __global__ __launch_bounds__(512) void multi_lift_kernel(MultiLiftArgs a) {
   const int r0 = blockIdx.y * RB;                       // the chunk's first response
   const int cnt = min(RB, a.count - r0);                // live slots (>= 1 by the grid)
   const int sample = ord / a.per_sample;
-  const int32_t* perm = a.perms + (int64_t)sample * p;
-  const bool backwards = a.per_sample == 2 && (ord & 1);   // the pair's second ordering is the first read backwards
+  // GROUPED: every ordering is a row of its own; else the pair's second ordering is the first read backwards
+  const int32_t* perm = a.perms + (int64_t)(GROUPED ? ord : sample) * p;
+  const bool backwards = !GROUPED && a.per_sample == 2 && (ord & 1);
 
   if (tid < 128) s_perm[tid] = (tid < p) ? perm[backwards ? p - 1 - tid : tid] : 0;
+  if constexpr (GROUPED) {
+    if (tid >= 128 && tid < 256) s_off[tid - 128] = (tid - 128 <= a.ng) ? a.off[tid - 128] : 0;
+    if (tid >= 256 && tid < 384) s_cols[tid - 256] = (tid - 256 < a.n_cols) ? a.cols[tid - 256] : 0;
+  }
   if (tid == 0) s_bad = 0;
   __syncthreads();
 
@@ -335,12 +353,30 @@ __global__ __launch_bounds__(512) void multi_lift_kernel(MultiLiftArgs a) {
       sacc += __shfl_xor(sacc, 2);
       if (j < p && q == 0) {
         const double lift = z[j] * sacc / a.yy[r0 + s];
-        double* dst = a.lifts + ((int64_t)sample * a.m + (r0 + s)) * p + s_perm[j];
-        if (a.per_sample == 2) atomicAdd(dst, 0.5 * lift);   // the pair's two terms commute: order-independent sum
-        else *dst = lift;
+        if constexpr (GROUPED) {
+          s_lift[s_perm[j]] = lift;
+        } else {
+          double* dst = a.lifts + ((int64_t)sample * a.m + (r0 + s)) * p + s_perm[j];
+          if (a.per_sample == 2) atomicAdd(dst, 0.5 * lift);   // the pair's two terms commute: order-independent sum
+          else *dst = lift;
+        }
       }
     }
     __syncthreads();           // the terms' storage is the next response's
+    if constexpr (GROUPED) {
+      // the fold, group k on thread 511 - k: the threads at the top end have no row or column of the scan (4 p <= 416),
+      // so the next slot's terms start beside it.  The next slot writes s_lift only behind its own barrier, which these
+      // threads reach after their reads.
+      for (int k = 511 - tid; k < a.ng; k += 512) {
+        double acc = 0.0;
+        const int c1 = s_off[k + 1];
+#pragma unroll 4
+        for (int c = s_off[k]; c < c1; ++c) acc += s_lift[s_cols[c]];
+        double* dst = a.lifts + ((int64_t)sample * a.m + (r0 + s)) * a.ng + k;
+        if (a.per_sample == 2) atomicAdd(dst, 0.5 * acc);    // 0.5 x is exact and two addends commute: 0.5 (a + b)
+        else *dst = acc;
+      }
+    }
   }
   if (tid == 0 && s_bad) atomicOr(a.info, 1);
 }
@@ -370,9 +406,10 @@ __global__ __launch_bounds__(256) void multi_lift_stats_kernel(const double* __r
   }
 }
 
-size_t multi_lift_lds_bytes(int nb) {
+size_t multi_lift_lds_bytes(int nb, bool grouped) {
   const size_t ntri = (size_t)nb * (nb + 1) / 2;
-  return (2 * ntri * 256 + 2 * 16 * SINV_LD + 256 + 256 + 2 * RB * VEC) * sizeof(double) + 128 * sizeof(int32_t);
+  return (2 * ntri * 256 + 2 * 16 * SINV_LD + 256 + 256 + 2 * RB * VEC) * sizeof(double) + 128 * sizeof(int32_t) +
+         (grouped ? VEC * sizeof(double) + 2 * 128 * sizeof(int32_t) : 0);
 }
 
 hipError_t launch_multi_lift(const MultiLiftArgs& a, hipStream_t st) {
@@ -381,12 +418,24 @@ hipError_t launch_multi_lift(const MultiLiftArgs& a, hipStream_t st) {
       a.m < a.count || (a.per_sample != 1 && a.per_sample != 2) || chunks > 65535 || a.ld < a.p || !a.G || !a.H || !a.g ||
       !a.h || !a.yy || !a.perms || !a.lifts || !a.info)
     return hipErrorInvalidValue;
-  const size_t bytes = multi_lift_lds_bytes(a.nb);
+  const bool grouped = a.ng != 0;
+  // (off and cols are the library's own tables: player_map_build has checked that every column index is in 0 .. p-1)
+  if (grouped && (a.ng < 1 || a.ng > a.p || a.n_cols < a.ng || a.n_cols > a.p || !a.off || !a.cols))
+    return hipErrorInvalidValue;
+  const size_t bytes = multi_lift_lds_bytes(a.nb, grouped);
   if (bytes > LDS_BYTES_PER_CU) return hipErrorInvalidValue;
-  static DynLdsGrant grant;   // per device
-  hipError_t e = grant.ensure(reinterpret_cast<const void*>(multi_lift_kernel), bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(multi_lift_kernel, dim3(a.n_samples * a.per_sample, (unsigned)chunks), dim3(512), bytes, st, a);
+  const dim3 grid(a.n_samples * a.per_sample, (unsigned)chunks);
+  if (grouped) {
+    static DynLdsGrant grant;   // per device
+    hipError_t e = grant.ensure(reinterpret_cast<const void*>(multi_lift_kernel<true>), bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(multi_lift_kernel<true>, grid, dim3(512), bytes, st, a);
+  } else {
+    static DynLdsGrant grant;   // per device
+    hipError_t e = grant.ensure(reinterpret_cast<const void*>(multi_lift_kernel<false>), bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(multi_lift_kernel<false>, grid, dim3(512), bytes, st, a);
+  }
   return hipGetLastError();
 }
 

@@ -455,6 +455,10 @@ hipError_t launch_multi_groups_debug(const MultiGroupArgs& a, const uint64_t* ma
 // LDS-resident kernel with MLIFT_RB augmented rows.  One workgroup per (ordering, chunk of MLIFT_RB responses): the grid
 // is (n_samples * per_sample) x ceil(count / MLIFT_RB).  With per_sample == 2 ordering 2 s + 1 is sample s's read
 // backwards and each adds half its lift vectors to sample s (lifts must be zero beforehand); with 1 they are stored.
+// ng != 0 (groups of columns as the players, the kernel's GROUPED instantiation): perms are explicit, [n_samples *
+// per_sample][p], rows s per_sample .. belong to sample s (never read backwards: a baseline stays in front), and a
+// response's p lifts are folded in the workgroup over the player map's CSR -- group k sums cols[off[k] .. off[k+1]) in
+// ascending order from 0.0, as fold_players_kernel does -- into lifts [n_samples][m][g].
 constexpr int MLIFT_MAX_P = 104, MLIFT_RB = 8;
 struct MultiLiftArgs {
   const double* G;         // [p][ld] training Gram, shared by the responses
@@ -465,14 +469,17 @@ struct MultiLiftArgs {
   const double* yy;        // [count] ||y_r||^2
   double aug[2];           // diagonal of the augmented rows (train, test): above the sum of any MLIFT_RB responses'
                            // ||L^-1 g_r||^2 (||L_t^-1 h_r||^2), so that their unused trailing corner stays positive definite
-  const int32_t* perms;    // [n_samples][p]
+  const int32_t* perms;    // [n_samples][p]; ng != 0: [n_samples * per_sample][p]
   int p, nb, n_samples, per_sample, count;   // nb = ceil((p + MLIFT_RB) / 16)
   int m;                   // responses of a sample's block of lifts (>= count)
-  double* lifts;           // [n_samples][m][p]
+  double* lifts;           // [n_samples][m][p]; ng != 0: [n_samples][m][ng]
+  int ng, n_cols;          // groups (0: the players are the columns) and the columns they own (p less the baseline's)
+  const int32_t* off;      // [ng + 1] device: the player map's CSR
+  const int32_t* cols;     // [n_cols]
   double piv_tol;          // relative pivot test of the pivots j < p: d <= piv_tol G_jj raises LSSPA_INFO_NOT_PD
   int32_t* info;           // one word: G and H are shared
 };
-size_t multi_lift_lds_bytes(int nb);
+size_t multi_lift_lds_bytes(int nb, bool grouped = false);
 hipError_t launch_multi_lift(const MultiLiftArgs& a, hipStream_t st);
 // (n, mean, M2) [entries] += the n_b lift vectors lifts [n_b][entries]: Welford over the batch in sample order, then one
 // Chan merge into the state of n_old samples.  No atomics: two runs agree bitwise.

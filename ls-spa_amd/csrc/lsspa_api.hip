@@ -112,10 +112,17 @@ struct MultiWork {
 // What the sampled attribution of many responses keeps (lsspa_multi_lift_load / lsspa_multi_lift_set_reduced ..
 // lsspa_multi_lift_free): the shared G and H, one g, h and ||y||^2 per response, the orderings and lift vectors of one
 // launch, the running (n, mean, M2) per (response, feature) and the last calls' timing.  Nothing of the loaded problem,
-// the sampling path's statistics, the enumerations, the bootstrap or lsspa_multi_* is in here.
+// the sampling path's statistics, the enumerations, the bootstrap or lsspa_multi_* is in here.  With a player map
+// (lsspa_multi_lift_set_players: ng != 0, its own map, not ctx->players) a sample is g group lifts a response: the lift
+// vectors and the first m g entries of (mean, M2) are [m][g], and perms holds the expanded rows of a launch.
 struct MultiLiftWork {
   bool loaded = false;
   int p = 0, m = 0;
+  int ng = 0;                              // groups of the player map (0: none)
+  PlayerMap map;
+  DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
+  std::vector<int32_t> rows;               // a launch's expanded rows on the host
+  int sd() const { return ng ? ng : p; }     // the dimension of a sample's lift vector
   double aug[2] = {1.0, 1.0};              // diagonal of the augmented rows (MultiLiftArgs::aug)
   DevBuf<double> G, H, g, h, yy;           // [p][p], [p][p], [m][p], [m][p], [m]
   DevBuf<double> lifts, mean, M2;          // [samples of a launch][m][p]; the running state [m][p]
@@ -125,9 +132,10 @@ struct MultiLiftWork {
   double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
   void release() {
     dev_free(G); dev_free(H); dev_free(g); dev_free(h); dev_free(yy); dev_free(lifts); dev_free(mean); dev_free(M2);
-    dev_free(perms); dev_free(info);
+    dev_free(perms); dev_free(info); dev_free(pl_off); dev_free(pl_cols);
     loaded = false;
     n = 0;
+    ng = 0;
   }
 };
 
@@ -4767,6 +4775,8 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_
 // The reduced form is lsspa_multi_load's (one Gram pass per side over Z = [X | Y]).  A batch of orderings runs as
 // launches of whole samples, a launch's grid (orderings of its samples) x (chunks of MLIFT_RB responses); its lift vectors
 // [samples][m][p] are folded into the running (n, mean, M2) [m][p] by a launch of their own and copied out if asked for.
+// With a player map the orderings are orderings of the g groups, expanded on the host as they are staged (two rows a
+// sample when antithetical), and the kernel folds each response's lifts to g group lifts itself: [samples][m][g].
 namespace {
 
 constexpr int64_t MLIFT_GRID_PER_LAUNCH = 1 << 16;            // workgroups a launch takes at most (one sample at least)
@@ -4829,6 +4839,7 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
                 const double* yy) {
   MultiLiftWork& W = ctx->mlift;
   W.loaded = false;
+  W.ng = 0;                // a player map belongs to the responses it was set on
   char msg[160];
   for (int r = 0; r < m; ++r)
     if (!(yy[r] > 0.0) || !std::isfinite(yy[r])) {
@@ -4867,6 +4878,18 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
   W.n = 0;
   W.batch_ms = W.stats_ms = 0.0;
   W.loaded = true;
+  return LSSPA_OK;
+}
+
+// n = 0, (mean, M2) and the info word cleared
+int mlift_reset(lsspa_ctx* ctx) {
+  MultiLiftWork& W = ctx->mlift;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t mp = (size_t)W.m * W.p;
+  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
+  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
+  HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
+  W.n = 0;
   return LSSPA_OK;
 }
 
@@ -4912,24 +4935,57 @@ int lsspa_multi_lift_set_reduced(lsspa_ctx* ctx, int32_t p, int32_t m, const dou
   return abi_caught(ctx);
 }
 
+int lsspa_multi_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(mlift_need_loaded(ctx));
+  MultiLiftWork& W = ctx->mlift;
+  if (!labels && g != 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
+  PlayerMap map;
+  if (labels) {
+    const char* why = player_map_build(labels, W.p, g, map);
+    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(mlift_reset(ctx));       // (waits for work in flight: a previous batch may still read the tables)
+  if (labels) {
+    TRY(dev_alloc(ctx, W.pl_off, (size_t)W.p + 1));
+    TRY(dev_alloc(ctx, W.pl_cols, (size_t)W.p));
+    HIPCHK(hipMemcpy(W.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
+    W.map = std::move(map);
+    W.ng = g;
+  } else {
+    W.ng = 0;
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
 int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int32_t antithetical, double* lifts_out,
                            int32_t accumulate) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
   MultiLiftWork& W = ctx->mlift;
-  const int p = W.p, m = W.m;
-  if (!perms || B < 1 || B > (int64_t)INT32_MAX / p)
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_batch: perms is NULL, B < 1 or B p >= 2^31");
-  if (!all_permutations(perms, (int)B, p, ctx->perm_mark))
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_batch: a row of perms is not a permutation of 0 .. p-1");
+  const int p = W.p, m = W.m, g = W.ng, d = W.sd();
+  if (!perms || B < 1 || B > (int64_t)INT32_MAX / (g ? 2 * p : p))     // (with a map: two expanded rows a sample)
+    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_multi_lift_batch: perms is NULL, B < 1 or 2 B p >= 2^31"
+                                      : "lsspa_multi_lift_batch: perms is NULL, B < 1 or B p >= 2^31");
+  if (!all_permutations(perms, (int)B, d, ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_multi_lift_batch: a row of perms is not a permutation of 0 .. g-1 (a player "
+                                        "map is set: the orderings are orderings of the groups)"
+                                      : "lsspa_multi_lift_batch: a row of perms is not a permutation of 0 .. p-1");
   HIPCHK(hipSetDevice(ctx->device));
   const int per = antithetical ? 2 : 1;
-  const int64_t chunks = (m + MLIFT_RB - 1) / MLIFT_RB, entries = (int64_t)m * p;
-  // samples a launch: by the grid and by the lift vectors' bytes -- by B, m and p alone
+  const int64_t chunks = (m + MLIFT_RB - 1) / MLIFT_RB, entries = (int64_t)m * d;
+  // samples a launch: by the grid and by the lift vectors' bytes -- by B, m, p and g alone
   const int64_t S = std::min(B, std::max<int64_t>(1, std::min(MLIFT_GRID_PER_LAUNCH / (per * chunks),
                                                               MLIFT_LIFT_DOUBLES / entries)));
+  const int64_t rows_per = g ? per : 1;      // rows of perms a sample takes on the device
   TRY(dev_alloc(ctx, W.lifts, (size_t)(S * entries)));
-  TRY(dev_alloc(ctx, W.perms, (size_t)(S * p)));
+  TRY(dev_alloc(ctx, W.perms, (size_t)(S * rows_per * p)));
+  if (g) W.rows.resize((size_t)(S * rows_per * p));
   std::vector<hipEvent_t> ev(3, nullptr);
   Events guard{ev};
   for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
@@ -4951,9 +5007,20 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
   a.lifts = W.lifts.ptr;
   a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
   a.info = W.info.ptr;
+  a.ng = g;
+  a.n_cols = g ? (int)W.map.cols.size() : 0;
+  a.off = g ? W.pl_off.ptr : nullptr;
+  a.cols = g ? W.pl_cols.ptr : nullptr;
   for (int64_t s0 = 0; s0 < B; s0 += S) {
     const int64_t ns = std::min(S, B - s0);
-    HIPCHK(hipMemcpyAsync(W.perms.ptr, perms + s0 * p, sizeof(int32_t) * (size_t)(ns * p), hipMemcpyHostToDevice,
+    const int32_t* src = perms + s0 * p;
+    if (g) {      // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
+      for (int64_t s = 0; s < ns; ++s)
+        for (int r = 0; r < per; ++r)
+          expand_group_row(W.map, perms + (s0 + s) * g, r, W.rows.data() + (size_t)((s * per + r) * p));
+      src = W.rows.data();
+    }
+    HIPCHK(hipMemcpyAsync(W.perms.ptr, src, sizeof(int32_t) * (size_t)(ns * rows_per * p), hipMemcpyHostToDevice,
                           ctx->stream));
     if (per == 2)     // the pair's two terms are added into a zeroed destination
       HIPCHK(hipMemsetAsync(W.lifts.ptr, 0, sizeof(double) * (size_t)(ns * entries), ctx->stream));
@@ -4987,7 +5054,7 @@ int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) t
   MultiLiftWork& W = ctx->mlift;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t mp = (size_t)W.m * W.p;
+  const size_t mp = (size_t)W.m * W.sd();
   if (n) *n = W.n;
   if (mean) HIPCHK(hipMemcpy(mean, W.mean.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
   if (m2) HIPCHK(hipMemcpy(m2, W.M2.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
@@ -4999,15 +5066,8 @@ int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) t
 int lsspa_multi_lift_reset(lsspa_ctx* ctx) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
-  MultiLiftWork& W = ctx->mlift;
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t mp = (size_t)W.m * W.p;
-  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
-  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
-  HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
-  W.n = 0;
-  return LSSPA_OK;
+  return mlift_reset(ctx);
 } catch (...) {
   return abi_caught(ctx);
 }

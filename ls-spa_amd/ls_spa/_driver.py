@@ -32,7 +32,7 @@ import numpy as np
 from . import _samplers as S
 from ._native import LSSPANativeError
 from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
-                       SampledMultiResults,
+                       SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
@@ -1571,8 +1571,8 @@ MULTI_LIFT_MAX_P = 104     # include/lsspa.h, LSSPA_MULTI_LIFT_MAX_P
 
 
 def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2 ** 13, batch_size=2 ** 8,
-                         tolerance=None, seed=42, perms=None, *, method="random", antithetical=True, device=0,
-                         _engine=None):
+                         tolerance=None, seed=42, perms=None, *, groups=None, method="random", antithetical=True,
+                         device=0, _engine=None):
     """Sampled Shapley attribution of many responses on one design matrix (p <= 104): what ``ls_spa_multi`` gives
     exactly for p <= 32, estimated from sampled orderings beyond that.
 
@@ -1595,12 +1595,22 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
         sources of ``ls_spa``.
     perms:  an iterable of orderings instead (leave ``method`` at its default).
     antithetical:  a sample is the mean of an ordering and its reverse (default), as in ``ls_spa``.
+    groups:  one integer label per column as ``ls_spa_groups`` takes them: k in 0 .. g-1 puts the column into group k,
+        -1 into a baseline that every model includes (any 1 <= g <= p; p <= 104 and M >= p as without groups).  The
+        players are then the g groups and the result is a ``SampledMultiGroupResults``: row r of ``attribution`` [m][g]
+        estimates what ``ls_spa_groups(X_train, X_test, Y_train[:, r], Y_test[:, r], groups, reg)`` estimates and sums
+        to ``r_squared[r] - baseline_r_squared[r]``, ``attribution_errors`` is [m][g], ``baseline_r_squared`` [m] each
+        response's R^2 of the baseline columns alone (0 without a baseline).  The ordering sources run in dimension g:
+        'exact' is all g! group orderings, ``perms`` an iterable of permutations of 0 .. g-1; with ``antithetical`` a
+        sample is a group ordering and its reverse, the baseline first in both.  The kernel folds a response's column
+        lifts to group lifts itself (include/lsspa.h, lsspa_multi_lift_set_players).  Labels are refused with
+        ValueError before any GPU work.
 
     Shapes that do not fit raise ``SizeIncompatible``; p > 104, M < p (the test Gram matrix must have a Cholesky factor)
     or p + m > 32767 ValueError naming the limit, before any GPU work.  A column of ``Y_test`` that is identically zero
     is a ValueError, a Gram matrix that is not numerically positive definite a RuntimeWarning (it is shared, so it
-    concerns every response); theta is then the solution of minimal norm.  Several ranks, checkpoints, ``groups=`` and
-    fp32 are not part of this function."""
+    concerns every response); theta is then the solution of minimal norm.  Several ranks, checkpoints and fp32 are not
+    part of this function."""
     X_train, X_test = np.asarray(X_train), np.asarray(X_test)
     Y_train, Y_test = np.asarray(Y_train), np.asarray(Y_test)
     if X_train.ndim != 2 or X_test.ndim != 2:
@@ -1626,6 +1636,9 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
     if p + m > MULTI_MAX_COLS:
         raise ValueError(f"ls_spa_multi_sampled takes p + m <= {MULTI_MAX_COLS} columns of [X | Y] (p = {p}, m = {m}); "
                          "cut the responses into several calls")
+    labels, d = None, p                # d: the dimension of a sample
+    if groups is not None:
+        labels, d = group_labels(groups, p, max_groups=None)
     if perms is not None:
         if method != "random":
             raise ValueError("pass either perms= or method=, not both")
@@ -1635,7 +1648,7 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
     if int(batch_size) < 1 or int(max_samples) < 1:
         raise ValueError("batch_size and max_samples must be positive")
     _, source, batch_size, antithetical, max_samples, never_stop = prepare_sampling(
-        p, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
+        d, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
         antithetical=bool(antithetical), method=method)
     if never_stop:
         tolerance = None
@@ -1643,6 +1656,8 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
     with _engine_call(_engine, device, undo=undo) as engine:
         undo.append((engine.multi_lift_free, True))
         engine.multi_lift_load(X_train, X_test, Y_train, Y_test, reg)
+        if labels is not None:
+            engine.multi_lift_set_players(labels)      # (multi_lift_free drops the map with everything else)
         n, state = 0, None
         while n < max_samples:
             rows = source.take(min(batch_size, max_samples - n))
@@ -1659,13 +1674,19 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
             raise ValueError("no ordering to sample: perms is empty")
         n, mean, m2 = state if state is not None else engine.multi_lift_get()
         bits = engine.multi_lift_info()
-        theta, r_squared, singular = _multi_fit(*engine.multi_lift_gram())
+        gram = engine.multi_lift_gram()
+        theta, r_squared, singular = _multi_fit(*gram)
     bits |= int(singular)
-    # every sample's lifts of response r telescope to r_squared[r], so every row of the mean sums to it (the bound of
-    # LSSPA_INFO_SUM for well-conditioned data)
-    if not bits & 1 and not np.all(np.abs(mean.sum(axis=1) - r_squared) <= 1e-9 * np.maximum(1.0, np.abs(r_squared))):
+    # every sample's lifts of response r telescope to r_squared[r] -- over groups from the baseline's R^2 to it --, so
+    # every row of the mean sums to that (the bound of LSSPA_INFO_SUM for well-conditioned data)
+    base = np.zeros(m) if labels is None else _multi_baseline_r_squared(*gram, labels)
+    if not bits & 1 and not np.all(np.abs(mean.sum(axis=1) - (r_squared - base))
+                                   <= 1e-9 * np.maximum(1.0, np.abs(r_squared))):
         bits |= 8
     _info_verdict(bits, stacklevel=2)
+    if labels is not None:
+        return SampledMultiGroupResults(attribution=mean, attribution_errors=_multi_standard_errors(n, m2), theta=theta,
+                                        r_squared=r_squared, baseline_r_squared=base, n_samples=int(n))
     return SampledMultiResults(attribution=mean, attribution_errors=_multi_standard_errors(n, m2), theta=theta,
                                r_squared=r_squared, n_samples=int(n))
 

@@ -567,7 +567,7 @@ class HipEngine:
         self._check(self._lib.lsspa_multi_lift_load(
             self._h, Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m, Xe.shape[0], p, m,
             float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
-        self._multi_lift_dims = (p, m)
+        self._multi_lift_dims, self._multi_lift_g = (p, m), 0
 
     def multi_lift_load_reduced(self, G, g, H, h, yy):
         """The same from the Gram form: G, H [p][p], g, h [m][p], yy [m] (lsspa_multi_lift_set_reduced)."""
@@ -579,19 +579,42 @@ class HipEngine:
             raise ValueError("multi_lift_load_reduced takes G, H [p][p], g, h [m][p] and yy [m]")
         self._check(self._lib.lsspa_multi_lift_set_reduced(self._h, p, m, N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
                                                            N.dptr(yy)))
-        self._multi_lift_dims = (p, m)
+        self._multi_lift_dims, self._multi_lift_g = (p, m), 0
+
+    def multi_lift_set_players(self, labels, g=None):
+        """Groups of columns as the players of multi_lift_batch: one label per column, -1 the baseline, 0 .. g-1 the
+        groups (g: the largest label + 1 unless given).  From now on multi_lift_batch takes [B][g] orderings of the
+        groups and multi_lift_get returns [m][g]; the statistics start over (include/lsspa.h,
+        lsspa_multi_lift_set_players).  The library checks the labels."""
+        labels, g_seen = self._labels(labels)
+        g = g_seen if g is None else int(g)
+        dims = getattr(self, "_multi_lift_dims", None)
+        if dims is not None and len(labels) != dims[0]:
+            raise ValueError(f"labels must have length p = {dims[0]}")
+        self._check(self._lib.lsspa_multi_lift_set_players(self._h, N.iptr(labels), g))
+        self._multi_lift_g = g
+
+    def multi_lift_clear_players(self):
+        self._check(self._lib.lsspa_multi_lift_set_players(self._h, None, 0))
+        self._multi_lift_g = 0
+
+    def _multi_lift_sd(self):
+        """(dimension of a sample: g with a player map, else p; m)"""
+        p, m = getattr(self, "_multi_lift_dims", None) or (1, 1)
+        return (getattr(self, "_multi_lift_g", 0) or p), m
 
     def multi_lift_batch(self, perms, antithetical: bool, want_lifts: bool = False, accumulate: bool = True):
         """The lift vectors of every response for the orderings perms [B][p] (with antithetical a sample is the mean of
         an ordering and its reverse), folded into the running statistics if accumulate; lifts [B][m][p] if want_lifts
-        (include/lsspa.h, lsspa_multi_lift_batch).  The library checks the orderings."""
+        (include/lsspa.h, lsspa_multi_lift_batch).  With a player map (multi_lift_set_players) perms is [B][g] and the
+        lifts [B][m][g].  The library checks the orderings."""
         dims = getattr(self, "_multi_lift_dims", None)
-        p, m = dims or (1, 1)
+        p, m = self._multi_lift_sd()
         perms = np.ascontiguousarray(perms, dtype=np.int32)
         if dims is None:                  # the library says what comes first
             want_lifts = False
         elif perms.ndim != 2 or perms.shape[1] != p:
-            raise ValueError(f"perms must be [B][p = {p}]")
+            raise ValueError(f"perms must be [B][{'g' if getattr(self, '_multi_lift_g', 0) else 'p'} = {p}]")
         out = np.empty((perms.shape[0], m, p)) if want_lifts else None
         self._check(self._lib.lsspa_multi_lift_batch(self._h, N.iptr(perms) if perms.size else None, perms.shape[0],
                                                      int(bool(antithetical)), N.dptr(out) if want_lifts else None,
@@ -599,8 +622,8 @@ class HipEngine:
         return out
 
     def multi_lift_get(self):
-        """(n, mean [m][p], M2 [m][p]) of the samples folded in so far."""
-        p, m = getattr(self, "_multi_lift_dims", None) or (1, 1)
+        """(n, mean [m][p], M2 [m][p]) of the samples folded in so far ([m][g] with a player map)."""
+        p, m = self._multi_lift_sd()
         n, mean, m2 = C.c_int64(), np.empty((m, p)), np.empty((m, p))
         self._check(self._lib.lsspa_multi_lift_get(self._h, C.byref(n), N.dptr(mean), N.dptr(m2)))
         return n.value, mean, m2
@@ -630,7 +653,7 @@ class HipEngine:
 
     def multi_lift_free(self):
         self._check(self._lib.lsspa_multi_lift_free(self._h))
-        self._multi_lift_dims = None
+        self._multi_lift_dims, self._multi_lift_g = None, 0
 
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()

@@ -155,6 +155,7 @@ SIGNATURES = {
     "lsspa_multi_lift_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _dbl,
                                         _i32, _i32]),
     "lsspa_multi_lift_set_reduced": (C.c_int, [_vp, _i32, _i32, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_multi_lift_set_players": (C.c_int, [_vp, _pi32, _i32]),
     "lsspa_multi_lift_batch": (C.c_int, [_vp, _pi32, _i64, _i32, _pd, _i32]),
     "lsspa_multi_lift_get": (C.c_int, [_vp, _pi64, _pd, _pd]),
     "lsspa_multi_lift_reset": (C.c_int, [_vp]),

@@ -189,6 +189,40 @@ class SampledMultiResults:
         return "\n".join(lines)
 
 
+@dataclass
+class SampledMultiGroupResults:
+    """What ``ls_spa_multi_sampled(groups=)`` returns for m responses on one design matrix whose columns form g groups.
+    ``attribution`` [m][g]: row r is the mean of the ``n_samples`` group lift vectors of response r, an estimate of its
+    Shapley attribution over the groups (what ``ls_spa_groups`` estimates for that column alone);
+    ``attribution_errors`` [m][g] the standard errors of those means, sqrt(M2 / (n (n - 1))), ``inf`` while n < 2 and
+    only indicative where the samples are not independent (the QMC sources, a caller's ``perms``).  ``theta`` [m][p] the
+    full-model coefficients of each response; ``r_squared`` [m] their out-of-sample R^2 and ``baseline_r_squared`` [m]
+    that of the baseline columns alone (0 without a baseline) -- every sample's group lifts telescope from the one to
+    the other, so row r of ``attribution`` sums to ``r_squared[r] - baseline_r_squared[r]``."""
+    attribution: np.ndarray
+    attribution_errors: np.ndarray
+    theta: np.ndarray
+    r_squared: np.ndarray
+    baseline_r_squared: np.ndarray
+    n_samples: int
+
+    def __repr__(self):
+        pad = " " * 8
+        att = np.asarray(self.attribution)
+        lines = [
+            "",
+            f"{pad}g = {att.shape[1]} groups, p = {np.asarray(self.theta).shape[1]}, m = {att.shape[0]} responses, "
+            f"{self.n_samples} samples",
+            f"{pad}Out-of-sample R^2 with all columns: {_head(self.r_squared)}",
+            f"{pad}Out-of-sample R^2 of the baseline: {_head(self.baseline_r_squared)}",
+            "",
+            f"{pad}Shapley attribution of response 0: {_head(att[0])}",
+            f"{pad}Largest standard error: {float(np.max(self.attribution_errors)):.3g}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
 class SizeIncompatible(Exception):
     """Raised when the shapes of the four data arrays do not fit together."""
 
