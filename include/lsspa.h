@@ -336,6 +336,56 @@ int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, d
 int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, const uint64_t* masks,
                                    int64_t n, double* u /* [n][m] */);
 
+/* PERMUTATION TEST of the exact attribution (p <= 32; over groups g <= 32, p <= 64): the null distribution of phi and R^2
+ * when y is exchangeable with respect to the rows of X.  Replicate r permutes y_train by pi_r and y_test by an
+ * independent pi'_r; G, H and ||y_test||^2 do not change, only g_r = X^T y[pi_r] / N and h_r = X_test^T y_test[pi'_r]
+ * do.  The rows of both sides stay on the device; for a block of replicates one fp64-MFMA pass per side gathers y
+ * through the block's index rows (csrc/k_perm.hip), a fixed-order sum over the row slices writes g_r, h_r into response
+ * slots, and the enumerations of lsspa_multi_shapley / lsspa_multi_groups_shapley re-attribute eight replicates a sweep.
+ * The state is its own: the loaded problem, the running statistics and the state of lsspa_subsets_*, lsspa_groups_*,
+ * lsspa_boot_*, lsspa_multi_* and lsspa_multi_lift_* are not touched by any call below.  fp64 throughout.
+ * pi for (seed, r, side s in {0 train, 1 test}, n) is a pure function of those four: Fisher-Yates on a[i] = i, for
+ * t = n - 1 down to 1 swap a[t] and a[j], j = (uint64(word) (t + 1)) >> 32, word = word t % 4 of Philox4x32-10 with key =
+ * the 64-bit seed and counter = (t / 4, 2 + s, r low, r high) (the bootstrap's counters are (., s, ., .)); y_pi[i] =
+ * y[a[i]].  Relative bias at most n / 2^32.
+ *   lsspa_perm_load     : X [N][ld], y [N] of both sides, dtype and location as lsspa_reduce's; one Gram pass per side over
+ *                     [X | y] gives G, H, the observed g, h and ||y_test||^2 (lsspa_multi_load with m = 1).  p > 64, N or
+ *                     M outside 1 .. 2^31 - 1 or a y_test that is identically zero (or NaN) is LSSPA_ERR_ARG.
+ *   lsspa_perm_run      : replicates first .. first + R - 1 into phi [R][d], d = p (labels NULL; p > 32 is then
+ *                     LSSPA_ERR_ARG naming the limit) or d = g (labels [p] as lsspa_groups_shapley takes them).  sides:
+ *                     bit 0 permutes the training side, bit 1 the test side; a side that is not permuted keeps its
+ *                     observed g or h.  gperm / hperm (may be NULL): g_r, h_r [R][p].  block: replicates a pass, 0 = as
+ *                     many as 256 MB hold of index rows (two sides, two buffers: 8 (N + M) bytes a replicate) and
+ *                     partial sums, at most 1024; a larger request is cut to that.  The next block's index rows are
+ *                     drawn by up to 16 threads of the library into pinned memory and uploaded while the GPU works on
+ *                     the current one.  info: one word -- G is shared, so LSSPA_INFO_NOT_PD concerns every replicate.
+ *                     A replicate's bits depend on (seed, its number) and the data alone: not on R, first, block or the
+ *                     labels (gperm, hperm), and two calls agree bitwise (row slices by the row count alone, sums in a
+ *                     fixed order, no floating-point atomics).
+ *   lsspa_perm_observed : the identity permutation -- the observed g, h -- through the same enumeration: phi [d].
+ *   lsspa_perm_get_gram : G, H [p][p], g, h [p], yy [1] of the load (any pointer may be NULL).
+ *   lsspa_perm_timing   : ms of the last run: drawing and uploading the index rows (host time of the library's threads,
+ *                     hidden behind the GPU from the second block on), the X^T y kernels and the enumeration (device).
+ *   lsspa_perm_free     : frees the rows and every buffer.
+ *   lsspa_debug_perm_indices : out [n] = a of (seed, r, side, n) above; host only, needs no context and no GPU.
+ *   lsspa_debug_perm_plan    : host only -- plan10 = {block, blocks, rows per slice train / test, slices train / test,
+ *                     16-column blocks of X, index row stride train / test, bytes a replicate}.  A slice is at least 256
+ *                     rows, a multiple of 16, at most 128 of them a side.
+ * LSSPA_ERR_STATE before a load; LSSPA_ERR_NOMEM when device or pinned memory runs out. */
+int lsspa_perm_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                    const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                    int32_t dtype, int32_t location);
+int lsspa_perm_run(lsspa_ctx* ctx, const int32_t* labels /* NULL or [p] */, int32_t g, int64_t R, uint64_t seed,
+                   int64_t first, int32_t sides, int64_t block, double* phi /* [R][d] */, double* gperm /* [R][p] or NULL */,
+                   double* hperm /* [R][p] or NULL */, int32_t* info);
+int lsspa_perm_observed(lsspa_ctx* ctx, const int32_t* labels /* NULL or [p] */, int32_t g, double* phi /* [d] */,
+                        int32_t* info);
+int lsspa_perm_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy);
+int lsspa_perm_timing(const lsspa_ctx* ctx, double* draw_ms, double* upload_ms, double* xty_ms, double* enum_ms);
+int lsspa_perm_free(lsspa_ctx* ctx);
+int lsspa_debug_perm_indices(uint64_t seed, uint64_t r, int32_t side, int64_t n, uint32_t* out /* [n] */);
+int lsspa_debug_perm_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan10);
+
 /* SAMPLED attribution of MANY RESPONSES on one design matrix (p <= 104): the lift vectors of m targets for the same
  * orderings.  Of an ordering's work the two factorisations G_pi = L L^T, H_pi = L_t L_t^T and V = L^-1 L_t are O(p^3)
  * and the same for every response; only z_r = L^-1 g_r[pi], y~_r = L_t^-1 h_r[pi] and the lift scan over V are O(p^2)

@@ -140,4 +140,25 @@ const char* boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, int p, int g
   return nullptr;
 }
 
+const char* perm_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, PermPlan& P) {
+  P = PermPlan{};
+  if (p < 1 || p > PERM_MAX_P) return "p must be 1 .. 64";
+  if (const char* why = plan_sizes(R, N, M, block)) return why;
+  P.cb = (p + 15) / 16;
+  P.ldx = 16 * P.cb;
+  const int64_t rows[2] = {N, M};
+  for (int s = 0; s < 2; ++s) {
+    int64_t rps = (rows[s] + PERM_MAX_SLICES - 1) / PERM_MAX_SLICES;
+    rps = std::max<int64_t>(PERM_MIN_SLICE_ROWS, (rps + 15) / 16 * 16);
+    P.rps[s] = rps;
+    P.slices[s] = (int)((rows[s] + rps - 1) / rps);
+    P.ldi[s] = (rows[s] + 3) / 4 * 4;
+  }
+  P.rep_bytes = 2 * 4 * (P.ldi[0] + P.ldi[1]) + (int64_t)(P.slices[0] + P.slices[1]) * P.cb * 16 * 8;
+  const int64_t most = std::max<int64_t>(1, std::min<int64_t>(PERM_MAX_BLOCK, PERM_BLOCK_BYTES / P.rep_bytes));
+  P.block = std::min<int64_t>(R, block > 0 ? std::min(block, most) : most);
+  P.n_blocks = (R + P.block - 1) / P.block;
+  return nullptr;
+}
+
 }  // namespace lsspa

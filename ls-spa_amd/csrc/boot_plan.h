@@ -55,4 +55,23 @@ const char* boot_inter_plan(int64_t R, int64_t N, int64_t M, int p, int64_t bloc
 const char* boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
                                    BootPlan& P);
 
+// The permutation test (lsspa_perm_run, k_perm.hip): X of a side lives on the device as [n][ldx], ldx = 16 cb, cb =
+// ceil(p / 16) <= 4; a block of replicates is one gathered X^T y pass per permuted side into per-slice partial sums
+// [slice][ceil(block / 16)][cb][256].  A slice is at least PERM_MIN_SLICE_ROWS rows, a multiple of 16, at most
+// PERM_MAX_SLICES of them: a function of the side's rows alone, so that a replicate's sums do not depend on its block.
+// ldi: the row stride of the index table [block][ldi], n rounded up to 4 (the kernel reads 16 bytes a lane).
+// rep_bytes: what one replicate of a block takes -- its index rows of both sides, twice (the next block's are drawn and
+// uploaded while this one runs; the same again in pinned host memory), and its partials; block = 0: as many replicates
+// as PERM_BLOCK_BYTES holds, at most PERM_MAX_BLOCK (a larger request is cut to that).
+struct PermPlan {
+  int cb, ldx;
+  int64_t rps[2], ldi[2];
+  int slices[2];
+  int64_t rep_bytes, block, n_blocks;
+};
+constexpr int64_t PERM_BLOCK_BYTES = 256ll << 20, PERM_MAX_BLOCK = 1024;
+constexpr int64_t PERM_MIN_SLICE_ROWS = 256, PERM_MAX_SLICES = 128;
+constexpr int PERM_MAX_P = 64;                  // GROUPS_MAX_P; without groups the enumeration takes p <= 32
+const char* perm_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, PermPlan& P);
+
 }  // namespace lsspa

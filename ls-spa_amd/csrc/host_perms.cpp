@@ -224,6 +224,69 @@ int64_t argsort_rows_host(const double* keys, int64_t B, int p, int32_t* out, ui
 }  // namespace lsspa
 
 // ---------------------------------------------------------------------------------------------------------------
+// The permutations of the permutation test (lsspa_perm_run, k_perm.hip).  pi for (seed, replicate r, side s in {0 train,
+// 1 test}, n) is a pure function of those four: Fisher-Yates on a[i] = i, for t = n - 1 down to 1 swap a[t] and a[j],
+//   j = (uint64(word) * (t + 1)) >> 32,
+// word = word t % 4 of Philox4x32-10 with key = (seed low, seed high) and counter = (t / 4, 2 + s, r low, r high); then
+// y_pi[i] = y[a[i]].  The 2 + s keeps these streams apart from the bootstrap's counters (., s, ., .) (k_boot.hip).  j takes
+// each of its t + 1 values with probability (ceil or floor of 2^32 / (t + 1)) / 2^32: a bias of at most n / 2^32 relative
+// to 1 / (t + 1), the same as k_boot.hip's header states for the bootstrap's draws (n < 2^31, exact integer arithmetic).
+// A device generator that follows this rule gives the same bits.
+namespace lsspa {
+
+static inline void philox4x32_10_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                      uint32_t out[4]) {
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t m0 = (uint64_t)0xD2511F53u * c0, m1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(m1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)m1;
+    const uint32_t n2 = (uint32_t)(m0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)m0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+void perm_indices(uint64_t seed, uint64_t r, int side, int64_t n, uint32_t* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = (uint32_t)i;
+  uint32_t w[4];
+  int64_t have = -1;             // the counter whose words w holds
+  for (int64_t t = n - 1; t >= 1; --t) {
+    if ((t >> 2) != have) {
+      have = t >> 2;
+      philox4x32_10_host((uint32_t)have, (uint32_t)(2 + side), (uint32_t)r, (uint32_t)(r >> 32), (uint32_t)seed,
+                         (uint32_t)(seed >> 32), w);
+    }
+    const uint64_t j = ((uint64_t)w[t & 3] * (uint64_t)(t + 1)) >> 32;      // j <= t
+    const uint32_t x = out[t];
+    out[t] = out[j];
+    out[j] = x;
+  }
+}
+
+void perm_draw_block(uint64_t seed, uint64_t r0, int reps, int side, int64_t n, int64_t ldi, uint32_t* out, int threads) {
+  auto range = [&](int lo, int hi) {
+    for (int k = lo; k < hi; ++k) {
+      uint32_t* row = out + (size_t)k * ldi;
+      perm_indices(seed, r0 + (uint64_t)k, side, n, row);
+      for (int64_t i = n; i < ldi; ++i) row[i] = 0;
+    }
+  };
+  int nt = threads < 1 ? 1 : (threads > 16 ? 16 : threads);
+  nt = std::min(nt, std::max(1, reps));
+  if (nt == 1) {
+    range(0, reps);
+    return;
+  }
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; ++t) th.emplace_back(range, (int)((int64_t)reps * t / nt), (int)((int64_t)reps * (t + 1) / nt));
+  range(0, reps / nt);               // the caller's thread takes the first share
+  for (auto& t : th) t.join();
+}
+
+}  // namespace lsspa
+
+// ---------------------------------------------------------------------------------------------------------------
 // The 'argsort' ordering source as a thread of this library: Sobol' points by the generator's own recurrence and their
 // row argsort, ahead of the loop that consumes them, with no interpreter in the way (the Python helper thread this
 // replaces shares the interpreter lock with the driver's thread: the public call of a small problem waited for

@@ -512,4 +512,26 @@ hipError_t launch_boot_finalize(const double* S_tr, const double* S_te, const do
 hipError_t launch_boot_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Z,
                             int ldz, int64_t row0, hipStream_t st);
 
+// Permutation test of the exact attribution (k_perm.hip, host_perms.cpp; PermPlan and perm_plan: boot_plan.h), p <=
+// GROUPS_MAX_P, fp64.  X of one side lives on the device as Xd [n][ldx], ldx = 16 cb, cb = ceil(p / 16), columns beyond p
+// zero, y as yd [n].  A block of replicates: index rows idx [reps][ldi] (uint32, entries < n), one gathered pass per
+// permuted side into per-slice partial sums, a fixed-order sum over the slices into the enumeration's response slots.
+// host_perms.cpp: out[i] = pi(i) of (seed, replicate r, side, n) -- Fisher-Yates on Philox4x32-10, its header has the rule
+void perm_indices(uint64_t seed, uint64_t r, int side, int64_t n, uint32_t* out);
+// out [reps][ldi] = the index rows of replicates r0 .. r0 + reps - 1 (entries n .. ldi - 1 zero) on up to `threads`
+// native threads (at most 16)
+void perm_draw_block(uint64_t seed, uint64_t r0, int reps, int side, int64_t n, int64_t ldi, uint32_t* out, int threads);
+// part[slice][set][b][256] = sum over the slice's rows of X[i][16 b + ..] y[idx[16 set + ..][i]], 16 features x 16
+// replicates in the matrix instruction's accumulator layout
+hipError_t launch_perm_xty(const PermPlan& P, int side, const double* X, const double* y, const uint32_t* idx, int64_t n,
+                           int reps, double* part, hipStream_t st);
+// out[r][j] (j < p, stride p) = scale * the sum over the slices, in order, of the partials
+hipError_t launch_perm_reduce(const PermPlan& P, int side, const double* part, int p, int reps, double scale, double* out,
+                              hipStream_t st);
+// Xd[row0 + i][:] = X[i][0 .. p-1], zero up to ldx, yd[row0 + i] = y[i]; X [rows][ld], y [rows]
+hipError_t launch_perm_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Xd, int ldx,
+                            double* yd, int64_t row0, hipStream_t st);
+// out[r][:] = src [p] for r < reps
+hipError_t launch_perm_fill(const double* src, int p, int reps, double* out, hipStream_t st);
+
 }  // namespace lsspa

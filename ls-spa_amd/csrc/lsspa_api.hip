@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "comm.h"
@@ -136,6 +137,44 @@ struct MultiLiftWork {
     loaded = false;
     n = 0;
     ng = 0;
+  }
+};
+
+// What the permutation test keeps (lsspa_perm_load .. lsspa_perm_free): X and y of both sides on the device, the shared
+// G and H and the observed g, h, the index rows of two blocks of replicates (device and pinned host: the next block is
+// drawn and uploaded while this one runs), the partials of one block, and a MultiWork of its own whose response slots
+// the reduce kernel writes and the enumerations of lsspa_multi_* read.  Nothing of the loaded problem, the sampling path,
+// the exact enumerations, the bootstrap, lsspa_multi_* or lsspa_multi_lift_* is in here.
+struct PermWork {
+  bool loaded = false;
+  int p = 0;
+  int64_t n[2] = {0, 0};                   // rows: train, test
+  DevBuf<double> X0, X1, y0, y1;           // [n][ldx] zero-padded columns; [n]
+  DevBuf<char> stage_x, stage_y;           // host rows on their way in
+  DevBuf<uint32_t> idx[2][2];              // [buffer][side]: [block][ldi]
+  uint32_t* pin[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // the same in pinned host memory
+  size_t pin_count[2][2] = {{0, 0}, {0, 0}};
+  DevBuf<double> part0, part1;             // [slices][ceil(block / 16)][cb][256]
+  DevBuf<double> obs_g, obs_h;             // [p] the observed g, h on the device
+  MultiWork mw;                            // G, H; g, h, inv_yy of one block of replicates
+  std::vector<double> Gh, Hh, gh, hh;      // the reduced form on the host (lsspa_perm_get_gram)
+  double yy = 0.0;
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};     // last run: draw (host), upload (host), X^T y kernels, enumeration
+  DevBuf<double>& X(int s) { return s ? X1 : X0; }
+  DevBuf<double>& y(int s) { return s ? y1 : y0; }
+  DevBuf<double>& part(int s) { return s ? part1 : part0; }
+  void release() {
+    dev_free(X0); dev_free(X1); dev_free(y0); dev_free(y1); dev_free(stage_x); dev_free(stage_y);
+    dev_free(part0); dev_free(part1); dev_free(obs_g); dev_free(obs_h);
+    for (int b = 0; b < 2; ++b)
+      for (int s = 0; s < 2; ++s) {
+        dev_free(idx[b][s]);
+        if (pin[b][s]) (void)hipHostFree(pin[b][s]);
+        pin[b][s] = nullptr;
+        pin_count[b][s] = 0;
+      }
+    mw.release();
+    loaded = false;
   }
 };
 
@@ -271,6 +310,7 @@ struct lsspa_ctx {
   BootWork boot;                 // bootstrap of the exact attribution (lsspa_boot_*)
   MultiWork multi;               // exact attribution of many responses at once (lsspa_multi_*)
   MultiLiftWork mlift;           // sampled attribution of many responses (lsspa_multi_lift_*)
+  PermWork perm;                 // permutation test of the exact attribution (lsspa_perm_*)
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
   // the streamed reduction's staging (two row chunks in flight), its copy stream and events: kept between calls
@@ -1285,6 +1325,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->boot.release();
   ctx->multi.release();
   ctx->mlift.release();
+  ctx->perm.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
   dev_free(ctx->pr_delta); dev_free(ctx->pr_lifts); dev_free(ctx->pr_pos); dev_free(ctx->pr_perms);
@@ -4325,8 +4366,7 @@ int multi_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
 }
 
 // The kernels' view of the loaded responses first .. first + count - 1: weights on the device, a cleared info word
-int multi_args(lsspa_ctx* ctx, int64_t first, int64_t count, MultiArgs& a) {
-  MultiWork& W = ctx->multi;
+int multi_args(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, MultiArgs& a) {
   const int p = W.p;
   constexpr int WR = EXACT_MAX_PLAYERS + 1;
   double w[EXACT_W_ROWS * WR];
@@ -4353,8 +4393,8 @@ int multi_args(lsspa_ctx* ctx, int64_t first, int64_t count, MultiArgs& a) {
 }
 
 // first, count, block of an enumeration call against the responses loaded
-int multi_range(lsspa_ctx* ctx, const char* name, int64_t first, int64_t count, int64_t block) {
-  const int m = ctx->multi.m;
+int multi_range(lsspa_ctx* ctx, const MultiWork& W, const char* name, int64_t first, int64_t count, int64_t block) {
+  const int m = W.m;
   if (first < 0 || count < 1 || first > m || count > m - first || block < 0) {
     char msg[200];
     snprintf(msg, sizeof msg, "%s: responses first = %lld, count = %lld must lie inside the %d loaded, "
@@ -4369,11 +4409,11 @@ int multi_range(lsspa_ctx* ctx, const char* name, int64_t first, int64_t count, 
 // chunk) passes a launch.  launch(r0, cnt, part, units, s0, s1): steps s0 .. s1 - 1 of every unit for the cnt responses
 // from r0 (among those of the call) into part; store(r, out): the n + 1 column sums of response r's table.  The steps a
 // launch takes depend on n_high and passes alone, so a response's bits do not depend on the block it runs in.  Leaves the
-// call's timing in ctx->multi and the info word in info (may be NULL).
+// call's timing in W and the info word in info (may be NULL).  W: the responses' owner (ctx->multi, or the permutation
+// test's own).
 template <typename Launch, typename Store>
-int multi_enumerate(lsspa_ctx* ctx, int n, uint64_t n_high, uint64_t passes, int64_t count, int64_t block,
+int multi_enumerate(lsspa_ctx* ctx, MultiWork& W, int n, uint64_t n_high, uint64_t passes, int64_t count, int64_t block,
                     Launch&& launch, Store&& store, int32_t* info) {
-  MultiWork& W = ctx->multi;
   const int64_t bmax = multi_block_max(n, n_high);
   const int64_t blk = std::min<int64_t>(block == 0 ? bmax : std::min(block, bmax), count);
   const uint64_t units = exact_units(n_high), per = n_high / units;
@@ -4433,9 +4473,8 @@ int multi_enumerate(lsspa_ctx* ctx, int n, uint64_t n_high, uint64_t passes, int
 
 // The grouped kernels' view of the loaded responses first .. first + count - 1: the layout L of the labels and its table
 // on the device, the weights of g players, a cleared info word
-int multi_group_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t first, int64_t count,
+int multi_group_args(lsspa_ctx* ctx, MultiWork& W, const int32_t* labels, int32_t g, int64_t first, int64_t count,
                      MultiGroupArgs& a, GroupLayout& L) {
-  MultiWork& W = ctx->multi;
   const int p = W.p;
   char msg[200];
   if (g > GROUPS_MAX_G) {
@@ -4567,6 +4606,61 @@ int multi_reduce_sides(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, co
   return LSSPA_OK;
 }
 
+// lsspa_multi_shapley on the responses of W (checked: loaded, p <= MULTI_MAX_P, phi, the range)
+int multi_shapley_on(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, int64_t block, double* phi,
+                     int32_t* info) {
+  const int p = W.p;
+  HIPCHK(hipSetDevice(ctx->device));
+  const int q = subsets_low_features(p);
+  const uint64_t n_high = 1ull << (p - q);
+  MultiArgs a;
+  TRY(multi_args(ctx, W, first, count, a));
+  a.per = n_high / exact_units(n_high);
+  auto launch = [&](int64_t r0, int64_t cnt, double* part, uint64_t units, uint64_t s0, uint64_t s1) {
+    MultiArgs l = a;
+    l.g = a.g + (size_t)r0 * p;
+    l.h = a.h + (size_t)r0 * p;
+    l.inv_yy = a.inv_yy + r0;
+    l.count = (int)cnt;
+    l.part = part;
+    return launch_multi_enum(l, units, s0, s1, ctx->stream);
+  };
+  auto store = [&](int64_t r, const double* out) {
+    for (int j = 0; j < p; ++j) phi[(size_t)r * p + j] = out[j] - out[p];
+  };
+  return multi_enumerate(ctx, W, p, n_high, MULTI_PASSES_PER_LAUNCH, count, block, launch, store, info);
+}
+
+// lsspa_multi_groups_shapley on the responses of W (checked: loaded, labels, phi, the range)
+int multi_groups_shapley_on(lsspa_ctx* ctx, MultiWork& W, const int32_t* labels, int32_t g, int64_t first, int64_t count,
+                            int64_t block, double* phi, int32_t* info) {
+  const int p = W.p;
+  HIPCHK(hipSetDevice(ctx->device));
+  MultiGroupArgs a;
+  GroupLayout L;
+  TRY(multi_group_args(ctx, W, labels, g, first, count, a, L));
+  const int ng = L.ng;
+  const uint64_t n_high = 1ull << L.gh;
+  a.per = n_high / exact_units(n_high);
+  // passes per launch: groups_enumerate's bound by the rows of a subset's matrix, a quarter of it as a pass carries
+  // MULTI_RB responses (MULTI_PASSES_PER_LAUNCH); by the layout alone, so a response's bits do not depend on the block
+  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
+  const uint64_t passes = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows) / 4);
+  auto launch = [&](int64_t r0, int64_t cnt, double* part, uint64_t units, uint64_t s0, uint64_t s1) {
+    MultiGroupArgs l = a;
+    l.g = a.g + (size_t)r0 * p;
+    l.h = a.h + (size_t)r0 * p;
+    l.inv_yy = a.inv_yy + r0;
+    l.count = (int)cnt;
+    l.part = part;
+    return launch_multi_groups_enum(l, units, s0, s1, ctx->stream);
+  };
+  auto store = [&](int64_t r, const double* out) {
+    for (int k = 0; k < ng; ++k) phi[(size_t)r * ng + L.gid[k]] = out[k] - out[ng];
+  };
+  return multi_enumerate(ctx, W, ng, n_high, passes, count, block, launch, store, info);
+}
+
 }  // namespace
 
 extern "C" {
@@ -4608,28 +4702,9 @@ int lsspa_multi_shapley(lsspa_ctx* ctx, int64_t first, int64_t count, int64_t bl
   TRY(multi_need_loaded(ctx));
   TRY(multi_need_ungrouped(ctx, "lsspa_multi_shapley"));
   MultiWork& W = ctx->multi;
-  const int p = W.p;
   if (!phi) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_shapley: phi is NULL");
-  TRY(multi_range(ctx, "lsspa_multi_shapley", first, count, block));
-  HIPCHK(hipSetDevice(ctx->device));
-  const int q = subsets_low_features(p);
-  const uint64_t n_high = 1ull << (p - q);
-  MultiArgs a;
-  TRY(multi_args(ctx, first, count, a));
-  a.per = n_high / exact_units(n_high);
-  auto launch = [&](int64_t r0, int64_t cnt, double* part, uint64_t units, uint64_t s0, uint64_t s1) {
-    MultiArgs l = a;
-    l.g = a.g + (size_t)r0 * p;
-    l.h = a.h + (size_t)r0 * p;
-    l.inv_yy = a.inv_yy + r0;
-    l.count = (int)cnt;
-    l.part = part;
-    return launch_multi_enum(l, units, s0, s1, ctx->stream);
-  };
-  auto store = [&](int64_t r, const double* out) {
-    for (int j = 0; j < p; ++j) phi[(size_t)r * p + j] = out[j] - out[p];
-  };
-  return multi_enumerate(ctx, p, n_high, MULTI_PASSES_PER_LAUNCH, count, block, launch, store, info);
+  TRY(multi_range(ctx, W, "lsspa_multi_shapley", first, count, block));
+  return multi_shapley_on(ctx, W, first, count, block, phi, info);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -4639,33 +4714,9 @@ int lsspa_multi_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g,
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(multi_need_loaded(ctx));
   MultiWork& W = ctx->multi;
-  const int p = W.p;
   if (!phi || !labels) return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_groups_shapley: labels / phi is NULL");
-  TRY(multi_range(ctx, "lsspa_multi_groups_shapley", first, count, block));
-  HIPCHK(hipSetDevice(ctx->device));
-  MultiGroupArgs a;
-  GroupLayout L;
-  TRY(multi_group_args(ctx, labels, g, first, count, a, L));
-  const int ng = L.ng;
-  const uint64_t n_high = 1ull << L.gh;
-  a.per = n_high / exact_units(n_high);
-  // passes per launch: groups_enumerate's bound by the rows of a subset's matrix, a quarter of it as a pass carries
-  // MULTI_RB responses (MULTI_PASSES_PER_LAUNCH); by the layout alone, so a response's bits do not depend on the block
-  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
-  const uint64_t passes = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows) / 4);
-  auto launch = [&](int64_t r0, int64_t cnt, double* part, uint64_t units, uint64_t s0, uint64_t s1) {
-    MultiGroupArgs l = a;
-    l.g = a.g + (size_t)r0 * p;
-    l.h = a.h + (size_t)r0 * p;
-    l.inv_yy = a.inv_yy + r0;
-    l.count = (int)cnt;
-    l.part = part;
-    return launch_multi_groups_enum(l, units, s0, s1, ctx->stream);
-  };
-  auto store = [&](int64_t r, const double* out) {
-    for (int k = 0; k < ng; ++k) phi[(size_t)r * ng + L.gid[k]] = out[k] - out[ng];
-  };
-  return multi_enumerate(ctx, ng, n_high, passes, count, block, launch, store, info);
+  TRY(multi_range(ctx, W, "lsspa_multi_groups_shapley", first, count, block));
+  return multi_groups_shapley_on(ctx, W, labels, g, first, count, block, phi, info);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -4719,7 +4770,7 @@ int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, d
   HIPCHK(hipSetDevice(ctx->device));
   const int m = W.m;
   MultiArgs a;
-  TRY(multi_args(ctx, 0, m, a));
+  TRY(multi_args(ctx, W, 0, m, a));
   TRY(dev_alloc(ctx, W.masks, (size_t)n));
   TRY(dev_alloc(ctx, W.vals, (size_t)n * m));
   HIPCHK(hipMemcpy(W.masks.ptr, masks, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
@@ -4744,7 +4795,7 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_
   const int m = W.m;
   MultiGroupArgs a;
   GroupLayout L;
-  TRY(multi_group_args(ctx, labels, g, 0, m, a, L));
+  TRY(multi_group_args(ctx, W, labels, g, 0, m, a, L));
   const uint64_t full = (1ull << L.ng) - 1ull;     // g <= 32
   for (int64_t i = 0; i < n; ++i)
     if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a group beyond g");
@@ -5113,6 +5164,359 @@ int lsspa_multi_lift_free(lsspa_ctx* ctx) try {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->mlift.release();
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+}  // extern "C"
+
+// ---- permutation test of the exact attribution (k_perm.hip, host_perms.cpp) -------------------------------------------
+// G, H and ||y_test||^2 do not depend on a permutation of y: one Gram pass per side over [X | y] at the load gives them
+// and the observed g, h.  A run then goes block by block: the index rows of a block's replicates are drawn by threads of
+// this library into pinned memory and uploaded on a stream of their own while the GPU works on the block before; one
+// gathered X^T y pass per permuted side and a fixed-order sum over its slices write g_r, h_r into the response slots of
+// the PermWork's own MultiWork, which the enumerations of lsspa_multi_shapley / lsspa_multi_groups_shapley then read.
+namespace {
+
+int perm_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->perm.loaded) return ctx->fail(LSSPA_ERR_STATE, "no permutation-test data loaded (lsspa_perm_load comes first)");
+  return LSSPA_OK;
+}
+
+// labels / g of a run against the loaded columns, before any GPU work
+int perm_players(lsspa_ctx* ctx, const char* name, const int32_t* labels, int32_t g) {
+  const int p = ctx->perm.p;
+  char msg[240];
+  if (!labels) {
+    if (p > MULTI_MAX_P) {
+      snprintf(msg, sizeof msg, "%s enumerates all 2^p feature subsets and takes at most p = %d features without labels "
+               "(%d loaded); with labels it attributes to groups of up to %d columns", name, MULTI_MAX_P, p, GROUPS_MAX_P);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+    return LSSPA_OK;
+  }
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G, (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  GroupLayout L;
+  if (const char* why = groups_layout(labels, p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+// response slots for `cap` replicates: g, h [cap][p] and inv_yy [cap] = 1 / ||y_test||^2 (a permutation leaves it)
+int perm_slots(lsspa_ctx* ctx, int64_t cap) {
+  PermWork& W = ctx->perm;
+  MultiWork& Mw = W.mw;
+  TRY(dev_alloc(ctx, Mw.g, (size_t)cap * W.p));
+  TRY(dev_alloc(ctx, Mw.h, (size_t)cap * W.p));
+  TRY(dev_alloc(ctx, Mw.inv_yy, (size_t)cap));
+  std::vector<double> inv((size_t)cap, 1.0 / W.yy);
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the slots
+  HIPCHK(hipMemcpy(Mw.inv_yy.ptr, inv.data(), sizeof(double) * (size_t)cap, hipMemcpyHostToDevice));
+  return LSSPA_OK;
+}
+
+int perm_enumerate(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t count, double* phi, int32_t* bits) {
+  MultiWork& Mw = ctx->perm.mw;
+  Mw.m = (int)count;
+  return labels ? multi_groups_shapley_on(ctx, Mw, labels, g, 0, count, 0, phi, bits)
+                : multi_shapley_on(ctx, Mw, 0, count, 0, phi, bits);
+}
+
+// the producer of one block's index rows: a thread of this library that draws into pinned memory and uploads on `up`
+struct PermProducer {
+  std::thread th;
+  hipError_t err = hipSuccess;
+  double draw_ms = 0.0, upload_ms = 0.0;
+  ~PermProducer() {
+    if (th.joinable()) th.join();
+  }
+  void wait() {
+    if (th.joinable()) th.join();
+  }
+};
+
+struct PermStream {
+  hipStream_t s = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~PermStream() {
+    if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_debug_perm_indices(uint64_t seed, uint64_t r, int32_t side, int64_t n, uint32_t* out) try {
+  if (!out || n < 1 || n >= (1ll << 31) || side < 0 || side > 1) return LSSPA_ERR_ARG;
+  perm_indices(seed, r, side, n, out);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_debug_perm_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan10) try {
+  if (!plan10) return LSSPA_ERR_ARG;
+  PermPlan P;
+  if (perm_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
+  const int64_t v[10] = {P.block, P.n_blocks, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.cb, P.ldi[0], P.ldi[1],
+                         P.rep_bytes};
+  std::copy(v, v + 10, plan10);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_perm_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                    const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                    int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  char msg[240];
+  if (p < 1 || p > GROUPS_MAX_P) {
+    snprintf(msg, sizeof msg, "lsspa_perm_load takes 1 <= p <= %d columns, of which the enumeration without labels takes "
+             "p <= %d (%d given)", GROUPS_MAX_P, MULTI_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  PermPlan P;
+  if (const char* why = perm_plan(1, N, M, p, 0, P)) {
+    snprintf(msg, sizeof msg, "lsspa_perm_load: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (!multi_sides_ok(X_train, ld_train, y_train, 1, N, X_test, ld_test, y_test, 1, M, p, 1, reg, dtype, location))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_perm_load: NULL array, N or M < 1, ld < p, reg not finite and >= 0, or bad "
+                                    "dtype / location");
+  HIPCHK(hipSetDevice(ctx->device));
+  PermWork& W = ctx->perm;
+  W.loaded = false;
+  W.mw.loaded = false;
+  std::vector<double> G, g, H, h, yy;
+  double gram_ms = 0.0;
+  TRY(multi_reduce_sides(ctx, X_train, ld_train, y_train, 1, N, X_test, ld_test, y_test, 1, M, p, 1, reg, dtype, location,
+                         G, g, H, h, yy, gram_ms));
+  if (!(yy[0] > 0.0) || !std::isfinite(yy[0])) return ctx->fail(LSSPA_ERR_ARG, "y_test is identically zero (or NaN)");
+  const void* X[2] = {X_train, X_test};
+  const void* y[2] = {y_train, y_test};
+  const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test};
+  const size_t esz = dtype == LSSPA_F32 ? 4 : 8;
+  for (int s = 0; s < 2; ++s) {
+    TRY(dev_alloc(ctx, W.X(s), (size_t)n[s] * P.ldx));
+    TRY(dev_alloc(ctx, W.y(s), (size_t)n[s]));
+    if (location == LSSPA_DEVICE) {
+      HIPCHK(launch_perm_pack(X[s], ld[s], y[s], n[s], p, dtype == LSSPA_F32, W.X(s).ptr, P.ldx, W.y(s).ptr, 0,
+                              ctx->stream));
+      continue;
+    }
+    // host rows: through a staging buffer of at most ~64 MB, chunk by chunk (plain copies, as lsspa_boot_load's)
+    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n[s], (64ll << 20) / (int64_t)(ld[s] * esz)));
+    TRY(dev_alloc(ctx, W.stage_x, (size_t)rows * ld[s] * esz));
+    TRY(dev_alloc(ctx, W.stage_y, (size_t)rows * esz));
+    for (int64_t r0 = 0; r0 < n[s]; r0 += rows) {
+      const int64_t nr = std::min(rows, n[s] - r0);
+      const size_t xbytes = ((size_t)(nr - 1) * ld[s] + p) * esz;     // the caller's last row ends with its column p - 1
+      HIPCHK(hipMemcpyAsync(W.stage_x.ptr, (const char*)X[s] + (size_t)r0 * ld[s] * esz, xbytes, hipMemcpyHostToDevice,
+                            ctx->stream));
+      HIPCHK(hipMemcpyAsync(W.stage_y.ptr, (const char*)y[s] + (size_t)r0 * esz, (size_t)nr * esz, hipMemcpyHostToDevice,
+                            ctx->stream));
+      HIPCHK(launch_perm_pack(W.stage_x.ptr, ld[s], W.stage_y.ptr, nr, p, dtype == LSSPA_F32, W.X(s).ptr, P.ldx,
+                              W.y(s).ptr, r0, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));     // the staging buffer is reused
+    }
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  dev_free(W.stage_x);
+  dev_free(W.stage_y);
+  const size_t pp = (size_t)p * p;
+  TRY(dev_alloc(ctx, W.mw.G, pp));
+  TRY(dev_alloc(ctx, W.mw.H, pp));
+  TRY(dev_alloc(ctx, W.obs_g, (size_t)p));
+  TRY(dev_alloc(ctx, W.obs_h, (size_t)p));
+  HIPCHK(hipMemcpy(W.mw.G.ptr, G.data(), sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.mw.H.ptr, H.data(), sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.obs_g.ptr, g.data(), sizeof(double) * p, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.obs_h.ptr, h.data(), sizeof(double) * p, hipMemcpyHostToDevice));
+  W.Gh = G;
+  W.Hh = H;
+  W.gh = g;
+  W.hh = h;
+  W.yy = yy[0];
+  W.p = W.mw.p = p;
+  W.mw.m = 0;
+  W.mw.gram_ms = gram_ms;
+  W.n[0] = N;
+  W.n[1] = M;
+  for (double& v : W.ms) v = 0.0;
+  W.mw.loaded = true;
+  W.loaded = true;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_perm_observed(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(perm_need_loaded(ctx));
+  if (!phi) return ctx->fail(LSSPA_ERR_ARG, "lsspa_perm_observed: phi is NULL");
+  TRY(perm_players(ctx, "lsspa_perm_observed", labels, g));
+  HIPCHK(hipSetDevice(ctx->device));
+  PermWork& W = ctx->perm;
+  TRY(perm_slots(ctx, 1));
+  HIPCHK(launch_perm_fill(W.obs_g.ptr, W.p, 1, W.mw.g.ptr, ctx->stream));
+  HIPCHK(launch_perm_fill(W.obs_h.ptr, W.p, 1, W.mw.h.ptr, ctx->stream));
+  int32_t bits = 0;
+  TRY(perm_enumerate(ctx, labels, g, 1, phi, &bits));
+  if (info) *info = bits;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_perm_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, uint64_t seed, int64_t first,
+                   int32_t sides, int64_t block, double* phi, double* gperm, double* hperm, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(perm_need_loaded(ctx));
+  if (!phi || first < 0 || sides < 1 || sides > 3)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_perm_run: phi is NULL, first < 0, or sides is not 1 (train), 2 (test) or 3 (both)");
+  TRY(perm_players(ctx, "lsspa_perm_run", labels, g));
+  PermWork& W = ctx->perm;
+  const int p = W.p, d = labels ? g : p;
+  PermPlan P;
+  if (const char* why = perm_plan(R, W.n[0], W.n[1], p, block, P)) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "lsspa_perm_run: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t blk = P.block, sets = (blk + 15) / 16;
+  TRY(perm_slots(ctx, blk));
+  for (int s = 0; s < 2; ++s) {
+    if (!((sides >> s) & 1)) continue;
+    TRY(dev_alloc(ctx, W.part(s), (size_t)P.slices[s] * sets * P.cb * 256));
+    for (int b = 0; b < 2; ++b) {
+      const size_t cnt = (size_t)blk * P.ldi[s];
+      TRY(dev_alloc(ctx, W.idx[b][s], cnt));
+      if (W.pin_count[b][s] < cnt) {
+        if (W.pin[b][s]) (void)hipHostFree(W.pin[b][s]);
+        W.pin[b][s] = nullptr;
+        W.pin_count[b][s] = 0;
+        if (hipHostMalloc((void**)&W.pin[b][s], cnt * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+          W.pin[b][s] = nullptr;
+          return ctx->fail(LSSPA_ERR_NOMEM, "pinned host memory for the index rows of a block of replicates");
+        }
+        W.pin_count[b][s] = cnt;
+      }
+    }
+  }
+  // the side that is not permuted keeps its observed g or h in every slot
+  if (!(sides & 1)) HIPCHK(launch_perm_fill(W.obs_g.ptr, p, (int)blk, W.mw.g.ptr, ctx->stream));
+  if (!(sides & 2)) HIPCHK(launch_perm_fill(W.obs_h.ptr, p, (int)blk, W.mw.h.ptr, ctx->stream));
+  PermStream up;
+  HIPCHK(hipStreamCreateWithFlags(&up.s, hipStreamNonBlocking));
+  for (hipEvent_t& e : up.ev) HIPCHK(hipEventCreate(&e));
+  for (double& v : W.ms) v = 0.0;
+  const int device = ctx->device;
+  PermProducer prod[2];
+  auto produce = [&](int64_t b) {
+    PermProducer& J = prod[b & 1];
+    const int64_t nb = std::min(blk, R - b * blk);
+    const uint64_t r0 = (uint64_t)first + (uint64_t)(b * blk);
+    J.err = hipSuccess;
+    J.draw_ms = J.upload_ms = 0.0;
+    J.th = std::thread([&W, &P, &J, &up, b, nb, r0, seed, sides, device] {
+      using clk = std::chrono::steady_clock;
+      J.err = hipSetDevice(device);
+      for (int s = 0; s < 2 && J.err == hipSuccess; ++s) {
+        if (!((sides >> s) & 1)) continue;
+        const auto t0 = clk::now();
+        perm_draw_block(seed, r0, (int)nb, s, W.n[s], P.ldi[s], W.pin[b & 1][s], 16);
+        const auto t1 = clk::now();
+        J.err = hipMemcpyAsync(W.idx[b & 1][s].ptr, W.pin[b & 1][s], sizeof(uint32_t) * (size_t)nb * P.ldi[s],
+                               hipMemcpyHostToDevice, up.s);
+        if (J.err == hipSuccess) J.err = hipStreamSynchronize(up.s);
+        const auto t2 = clk::now();
+        J.draw_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        J.upload_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
+      }
+    });
+  };
+  int32_t all_bits = 0;
+  produce(0);
+  for (int64_t b = 0; b < P.n_blocks; ++b) {
+    const int64_t nb = std::min(blk, R - b * blk);
+    PermProducer& J = prod[b & 1];
+    J.wait();
+    if (J.err != hipSuccess) return ctx->fail(LSSPA_ERR_HIP, "upload of a block's index rows", J.err);
+    W.ms[0] += J.draw_ms;
+    W.ms[1] += J.upload_ms;
+    // block b + 1 is drawn and uploaded while the GPU works on block b: its buffers were last read by block b - 1,
+    // whose enumeration this thread has waited for
+    if (b + 1 < P.n_blocks) produce(b + 1);
+    HIPCHK(hipEventRecord(up.ev[0], ctx->stream));
+    for (int s = 0; s < 2; ++s) {
+      if (!((sides >> s) & 1)) continue;
+      HIPCHK(launch_perm_xty(P, s, W.X(s).ptr, W.y(s).ptr, W.idx[b & 1][s].ptr, W.n[s], (int)nb, W.part(s).ptr,
+                             ctx->stream));
+      HIPCHK(launch_perm_reduce(P, s, W.part(s).ptr, p, (int)nb, s == 0 ? 1.0 / (double)W.n[0] : 1.0,
+                                s == 0 ? W.mw.g.ptr : W.mw.h.ptr, ctx->stream));
+    }
+    HIPCHK(hipEventRecord(up.ev[1], ctx->stream));
+    const size_t at = (size_t)(b * blk) * p;
+    if (gperm)
+      HIPCHK(hipMemcpyAsync(gperm + at, W.mw.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, ctx->stream));
+    if (hperm)
+      HIPCHK(hipMemcpyAsync(hperm + at, W.mw.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, ctx->stream));
+    int32_t bits = 0;
+    TRY(perm_enumerate(ctx, labels, g, nb, phi + (size_t)(b * blk) * d, &bits));
+    all_bits |= bits;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, up.ev[0], up.ev[1]));
+    W.ms[2] += ms;
+    W.ms[3] += W.mw.enum_ms;
+  }
+  if (info) *info = all_bits;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_perm_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(perm_need_loaded(ctx));
+  const PermWork& W = ctx->perm;
+  if (G) std::copy(W.Gh.begin(), W.Gh.end(), G);
+  if (g) std::copy(W.gh.begin(), W.gh.end(), g);
+  if (H) std::copy(W.Hh.begin(), W.Hh.end(), H);
+  if (h) std::copy(W.hh.begin(), W.hh.end(), h);
+  if (yy) *yy = W.yy;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_perm_timing(const lsspa_ctx* ctx, double* draw_ms, double* upload_ms, double* xty_ms, double* enum_ms) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (draw_ms) *draw_ms = ctx->perm.ms[0];
+  if (upload_ms) *upload_ms = ctx->perm.ms[1];
+  if (xty_ms) *xty_ms = ctx->perm.ms[2];
+  if (enum_ms) *enum_ms = ctx->perm.ms[3];
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_perm_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->perm.release();
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

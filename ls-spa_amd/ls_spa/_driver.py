@@ -33,7 +33,7 @@ from . import _samplers as S
 from ._native import LSSPANativeError
 from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
-                       MultiResponseResults,
+                       MultiResponseResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
@@ -1197,6 +1197,88 @@ def ls_spa_multi(X_train, X_test, Y_train, Y_test, reg=0., *, groups=None, devic
         return MultiResponseResults(attribution=phi, theta=theta, r_squared=r_squared)
     return MultiGroupResults(attribution=phi, theta=theta, r_squared=r_squared,
                              baseline_r_squared=_multi_baseline_r_squared(*gram, labels))
+
+
+def _permutation_options(n_perm, permute):
+    """(n_perm, sides): the number of replicates as an int and the sides to permute as lsspa_perm_run's bits (1 train,
+    2 test); ValueError names what is wrong.  Needs no engine."""
+    if isinstance(n_perm, bool) or int(n_perm) != n_perm or n_perm < 1:
+        raise ValueError(f"n_perm must be an integer >= 1 (got {n_perm!r})")
+    if isinstance(permute, str):
+        permute = (permute,)
+    sides = tuple(permute)
+    if not sides or any(s not in ("train", "test") for s in sides) or len(set(sides)) != len(sides):
+        raise ValueError(f"permute must name 'train', 'test' or both (got {permute!r})")
+    return int(n_perm), ("train" in sides) * 1 + ("test" in sides) * 2
+
+
+def ls_spa_permutation_test(X_train, X_test, y_train, y_test, reg=0., n_perm=1000, seed=42, *, groups=None,
+                            permute=("train", "test"), device=0, _engine=None):
+    """Permutation test of the exact attribution: p-values for the Shapley shares and for R^2 (p <= 32; with
+    ``groups=``, g <= 32 groups over p <= 64 columns).
+
+    The out-of-sample share of a feature that has nothing to do with y is not zero: it scatters around zero with a
+    spread that depends on N, M, p and the collinearity of X.  This call draws that null distribution.  The null is the
+    GLOBAL one -- y is exchangeable with respect to the rows of X: replicate r permutes ``y_train`` by pi_r and
+    ``y_test`` by an independent pi'_r, refits and re-attributes.  X^T X, X_test^T X_test and ||y_test||^2 do not change
+    under a permutation, so a replicate costs one gathered X^T y[pi] per side -- on the GPU, from rows that stay there
+    -- and a share of an enumeration that carries eight replicates a sweep (include/lsspa.h, lsspa_perm_run).  It is
+    NOT a per-feature conditional test (no column of X is permuted, nothing is held fixed): a small p-value says the
+    feature earns more than it would if y were unrelated to every column.  With a baseline that is not constant
+    (columns labelled -1 other than an intercept) the baseline is part of what y is permuted against; a constant column
+    is unaffected.  The permutations are a pure function of (seed, replicate, side): two calls agree bitwise, replicate
+    r is the same whatever ``n_perm`` is, and a seed gives the same permutations with and without ``groups=``.
+
+    Returns ``PermutationTestResults``: the observed ``attribution``, ``theta``, ``r_squared`` (computed as one more
+    response, the identity permutation, by the kernel that computes the null rows, so that ``>=`` compares like with
+    like; it agrees with ``ls_spa(method='subsets')`` to rounding), ``null_attribution`` [n_perm][d],
+    ``null_r_squared``, the one-sided ``p_values`` = (1 + #{null >= observed}) / (1 + n_valid), ``p_values_adjusted``
+    (single-step max-T over the d players: family-wise error control), ``r_squared_p_value``, ``n_perm`` and
+    ``n_failed``.  fp64 throughout; M < p works.
+
+    permute:  ('train', 'test') (default) or one of them; the side not named keeps its observed X^T y in every replicate.
+    groups:   one label per column as ``ls_spa(method='subsets', groups=)`` takes them (-1: a baseline that every model
+        includes, 0 .. g-1: the groups).  The players are then the groups; ``baseline_r_squared`` and
+        ``null_baseline_r_squared`` hold the R^2 of the baseline alone, and a null row sums to its R^2 minus that.
+    Shapes that do not fit raise ``SizeIncompatible``; p > 32 without groups, p > 64 or g > 32 with them, bad labels,
+    n_perm < 1, a bad ``permute`` or a ``y_test`` that is identically zero ValueError, all before any GPU work.  A Gram
+    matrix that is not numerically positive definite is a RuntimeWarning as for ``ls_spa_multi`` (it is shared by every
+    replicate; theta is then the solution of minimal norm); ``n_failed`` counts the replicates that are not finite."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    n, p = data[0].shape
+    m = data[1].shape[0]
+    labels = None
+    if groups is not None:
+        if p > GROUPS_MAX_P:
+            raise ValueError(f"ls_spa_permutation_test(groups=) takes at most p = {GROUPS_MAX_P} columns, the baseline's "
+                             f"included (this problem has p = {p})")
+        labels, _ = group_labels(groups, p)
+    elif p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_permutation_test re-runs the enumeration of all 2^p feature subsets and takes at most "
+                         f"p = {SUBSETS_MAX_P} features (this problem has p = {p}); group the columns (groups=) to "
+                         "attribute to at most 32 players")
+    n_perm, sides = _permutation_options(n_perm, permute)
+    if p < 1 or n < 1 or m < 1 or n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError(f"ls_spa_permutation_test needs p >= 1 features and 1 <= N, M < 2^31 rows (p = {p}, N = {n}, "
+                         f"M = {m})")
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+    undo = []
+    with _engine_call(_engine, device, undo=undo) as engine:
+        undo.append((engine.perm_free, True))
+        engine.perm_load(*data, reg)
+        phi, bits = engine.perm_observed(labels)
+        null, gperm, hperm, bits_null = engine.perm_run(n_perm, seed, labels, sides=sides)
+        G, g, H, h, yy = engine.perm_gram()
+    theta, r_squared, singular = _multi_fit(G, g[None, :], H, h[None, :], np.array([yy]))
+    yyv = np.full(n_perm, yy)
+    _, null_r2, _ = _multi_fit(G, gperm, H, hperm, yyv)
+    _info_verdict((bits | bits_null | int(singular)) & 1, stacklevel=2)
+    base = null_base = None
+    if labels is not None:
+        base = _multi_baseline_r_squared(G, g[None, :], H, h[None, :], np.array([yy]), labels)[0]
+        null_base = _multi_baseline_r_squared(G, gperm, H, hperm, yyv, labels)
+    return PermutationTestResults.from_null(phi, theta[0], r_squared[0], null, null_r2, base, null_base)
 
 
 BOOT_ONES_BYTES = 64 << 20     # ls_spa_bootstrap: host bytes of the unit weights of a side that is not resampled

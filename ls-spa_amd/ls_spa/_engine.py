@@ -92,6 +92,31 @@ def debug_boot_plan(R: int, n: int, m: int, p: int, block: int = 0, inter: bool 
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
+PERM_PLAN_FIELDS = ("block", "n_blocks", "rps_train", "rps_test", "slices_train", "slices_test", "cb", "ldi_train",
+                    "ldi_test", "rep_bytes")
+
+
+def debug_perm_plan(R: int, n: int, m: int, p: int, block: int = 0):
+    """Test hook, host only: how a permutation-test run of R replicates on n / m rows at p columns is cut
+    (include/lsspa.h, lsspa_debug_perm_plan), as a dict of PERM_PLAN_FIELDS."""
+    out = np.zeros(10, dtype=np.int64)
+    rc = N.load().lsspa_debug_perm_plan(int(R), int(n), int(m), int(p), int(block), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_perm_plan: status {rc}")
+    return dict(zip(PERM_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def debug_perm_indices(seed: int, r: int, side: int, n: int):
+    """Test hook, host only: the permutation a [n] (uint32) of (seed, replicate r, side, n): y_pi[i] = y[a[i]]
+    (include/lsspa.h, lsspa_debug_perm_indices)."""
+    out = np.empty(max(int(n), 0), dtype=np.uint32)
+    rc = N.load().lsspa_debug_perm_indices(int(seed) & (2 ** 64 - 1), int(r) & (2 ** 64 - 1), int(side), int(n),
+                                           out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_perm_indices: status {rc}")
+    return out
+
+
 def debug_boot_groups_plan(R: int, n: int, m: int, labels, block: int = 0, inter: bool = False):
     """Test hook, host only: debug_boot_plan for a bootstrap over the groups of columns that labels names (one label per
     column; include/lsspa.h, lsspa_debug_boot_groups_plan).  ValueError for labels or sizes the library refuses.
@@ -552,6 +577,67 @@ class HipEngine:
     def multi_free(self):
         self._check(self._lib.lsspa_multi_free(self._h))
         self._multi_dims = None
+
+    # ---- permutation test of the exact attribution (p <= 32; over groups g <= 32, p <= 64) ----
+    def perm_load(self, X_train, X_test, y_train, y_test, reg: float):
+        """Keep X and y of both sides on the device and reduce [X | y] once per side for perm_run / perm_observed
+        (include/lsspa.h, lsspa_perm_load); the loaded problem and every other call's state are not touched."""
+        dt = np.float32 if (X_train.dtype == np.float32 and X_test.dtype == np.float32) else np.float64
+        Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
+        ya, ye = np.ascontiguousarray(y_train, dtype=dt), np.ascontiguousarray(y_test, dtype=dt)
+        n, p = Xa.shape
+        self._check(self._lib.lsspa_perm_load(
+            self._h, Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p,
+            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._perm_dims = (p, n, Xe.shape[0])
+
+    def _perm_labels(self, labels):
+        p = (getattr(self, "_perm_dims", None) or (1,))[0]
+        if labels is None:
+            return None, 0, p
+        labels, g = self._labels(labels)
+        if len(labels) != p:
+            raise ValueError(f"labels must have length p = {p}")
+        return labels, g, max(g, 1)
+
+    def perm_run(self, R: int, seed: int, labels=None, first: int = 0, sides: int = 3, block: int = 0):
+        """(phi [R][d], gperm [R][p], hperm [R][p], info) of replicates first .. first + R - 1 (include/lsspa.h,
+        lsspa_perm_run): d = p, or the g groups of labels; sides: bit 0 permutes the training side, bit 1 the test side."""
+        labels, g, d = self._perm_labels(labels)
+        p = (getattr(self, "_perm_dims", None) or (1,))[0]
+        R = int(R)
+        phi, gp, hp = np.empty((max(R, 0), d)), np.empty((max(R, 0), p)), np.empty((max(R, 0), p))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_perm_run(self._h, N.iptr(labels), g, R, int(seed) & (2 ** 64 - 1), int(first),
+                                             int(sides), int(block), N.dptr(phi), N.dptr(gp), N.dptr(hp), C.byref(info)))
+        return phi, gp, hp, info.value
+
+    def perm_observed(self, labels=None):
+        """(phi [d], info): the identity permutation through perm_run's enumeration (lsspa_perm_observed)."""
+        labels, g, d = self._perm_labels(labels)
+        phi = np.empty(d)
+        info = C.c_int32()
+        self._check(self._lib.lsspa_perm_observed(self._h, N.iptr(labels), g, N.dptr(phi), C.byref(info)))
+        return phi, info.value
+
+    def perm_gram(self):
+        """(G, g [p], H, h [p], yy) of the load."""
+        p = self._perm_dims[0]
+        G, g, H, h, yy = np.empty((p, p)), np.empty(p), np.empty((p, p)), np.empty(p), np.empty(1)
+        self._check(self._lib.lsspa_perm_get_gram(self._h, N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h), N.dptr(yy)))
+        return G, g, H, h, float(yy[0])
+
+    def perm_timing(self):
+        """Seconds of the last perm_run: drawing and uploading the index rows (host threads of the library), the X^T y
+        kernels and the enumeration (device)."""
+        a, b, c, d = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.lsspa_perm_timing(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"draw": a.value / 1e3, "upload": b.value / 1e3, "xty": c.value / 1e3, "enumeration": d.value / 1e3}
+
+    def perm_free(self):
+        self.perm_timing_last = self.perm_timing()      # the data go, the last run's timing stays readable
+        self._check(self._lib.lsspa_perm_free(self._h))
+        self._perm_dims = None
 
     # ---- sampled attribution of many responses on one design matrix (p <= 104) ----
     MULTI_LIFT_MAX_P = 104     # include/lsspa.h, LSSPA_MULTI_LIFT_MAX_P

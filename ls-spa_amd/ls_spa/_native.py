@@ -163,6 +163,14 @@ SIGNATURES = {
     "lsspa_multi_lift_info": (C.c_int, [_vp, _pi32]),
     "lsspa_multi_lift_timing": (C.c_int, [_vp, _pd, _pd, _pd]),
     "lsspa_multi_lift_free": (C.c_int, [_vp]),
+    "lsspa_perm_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _dbl, _i32, _i32]),
+    "lsspa_perm_run": (C.c_int, [_vp, _pi32, _i32, _i64, C.c_uint64, _i64, _i32, _i64, _pd, _pd, _pd, _pi32]),
+    "lsspa_perm_observed": (C.c_int, [_vp, _pi32, _i32, _pd, _pi32]),
+    "lsspa_perm_get_gram": (C.c_int, [_vp, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_perm_timing": (C.c_int, [_vp, _pd, _pd, _pd, _pd]),
+    "lsspa_perm_free": (C.c_int, [_vp]),
+    "lsspa_debug_perm_indices": (C.c_int, [C.c_uint64, C.c_uint64, _i32, _i64, C.POINTER(C.c_uint32)]),
+    "lsspa_debug_perm_plan": (C.c_int, [_i64, _i64, _i64, _i32, _i64, _pi64]),
 }
 
 

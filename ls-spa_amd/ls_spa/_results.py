@@ -160,6 +160,65 @@ class MultiGroupResults:
 
 
 @dataclass
+class PermutationTestResults:
+    """What ``ls_spa_permutation_test`` returns; d = p, or the g groups of ``groups=``.  ``attribution`` [d], ``theta``
+    [p], ``r_squared`` (and ``baseline_r_squared`` with groups, else None): the observed values.  ``null_attribution``
+    [n_perm][d], ``null_r_squared`` [n_perm] (and ``null_baseline_r_squared`` [n_perm] with groups): the same under
+    permutations of y; a null row sums to its ``null_r_squared`` (minus its baseline's with groups).  With n_valid the
+    replicates that are finite (``n_failed`` = n_perm - n_valid):
+    ``p_values`` [d] = (1 + #{r : null_attribution[r][j] >= attribution[j]}) / (1 + n_valid), one-sided;
+    ``p_values_adjusted`` [d] = (1 + #{r : max_k null_attribution[r][k] >= attribution[j]}) / (1 + n_valid), single-step
+    max-T: family-wise error control over the d players;
+    ``r_squared_p_value`` the same from ``null_r_squared``."""
+    attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+    null_attribution: np.ndarray
+    null_r_squared: np.ndarray
+    p_values: np.ndarray
+    p_values_adjusted: np.ndarray
+    r_squared_p_value: float
+    n_perm: int
+    n_failed: int
+    baseline_r_squared: float | None = None
+    null_baseline_r_squared: np.ndarray | None = None
+
+    @classmethod
+    def from_null(cls, attribution, theta, r_squared, null_attribution, null_r_squared, baseline_r_squared=None,
+                  null_baseline_r_squared=None):
+        att, null = np.asarray(attribution, dtype=np.float64), np.asarray(null_attribution, dtype=np.float64)
+        null_r2 = np.asarray(null_r_squared, dtype=np.float64)
+        valid = np.isfinite(null).all(axis=1) & np.isfinite(null_r2)
+        if null_baseline_r_squared is not None:
+            valid &= np.isfinite(null_baseline_r_squared)
+        n_valid = int(valid.sum())
+        ok = null[valid]
+        top = ok.max(axis=1) if ok.size else np.empty(0)
+        return cls(
+            attribution=att, theta=theta, r_squared=float(r_squared), null_attribution=null, null_r_squared=null_r2,
+            p_values=(1 + (ok >= att[None, :]).sum(axis=0)) / (1 + n_valid),
+            p_values_adjusted=(1 + (top[:, None] >= att[None, :]).sum(axis=0)) / (1 + n_valid),
+            r_squared_p_value=float((1 + int((null_r2[valid] >= r_squared).sum())) / (1 + n_valid)),
+            n_perm=len(null), n_failed=len(null) - n_valid,
+            baseline_r_squared=None if baseline_r_squared is None else float(baseline_r_squared),
+            null_baseline_r_squared=null_baseline_r_squared)
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}d = {len(self.attribution)} players, n_perm = {self.n_perm} ({self.n_failed} failed)",
+            f"{pad}Out-of-sample R^2 with all features: {self.r_squared:.2f} (p = {self.r_squared_p_value:.3g})",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}p-values: {_head(self.p_values)}",
+            f"{pad}p-values, max-T adjusted: {_head(self.p_values_adjusted)}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class SampledMultiResults:
     """What ``ls_spa_multi_sampled`` returns for m responses on one design matrix.  ``attribution`` [m][p]: row r is the
     mean of the ``n_samples`` lift vectors of response r, an estimate of its Shapley attribution; ``attribution_errors``
