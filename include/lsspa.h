@@ -156,6 +156,33 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
 int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */,
                               double* inter /* [g*g] */, int32_t* info);
 
+/* Exact Owen values: the attribution of every COLUMN with the groups as coalition structure, the two-level Shapley
+ * value.  Labels, B, u and v as lsspa_groups_shapley's.  For a column i of group k, with B_k the group's columns,
+ * b = |B_k| and cols(R) the columns of the groups in R,
+ *   Ow_i = sum over R within groups \ {k}, T within B_k \ {i} of
+ *          |R|! (g - 1 - |R|)! / g!  |T|! (b - 1 - |T|)! / b!  (v(B + cols(R) + T + i) - v(B + cols(R) + T)):
+ * the mean of the column's lift over the orderings in which the baseline comes first and every group's columns are
+ * contiguous.  The Owen values of a group's columns sum to the group's phi, all of them to R^2(all columns) -
+ * R^2(B alone).  All-singleton labels give lsspa_subsets_shapley's phi, g = 1 the Shapley value of the group's columns
+ * with the baseline eliminated.
+ *   owen [p] : Ow_i per column, 0.0 on baseline columns; a group of one column gets its phi.
+ *   phi [g]  : the group game's Shapley values, bitwise lsspa_groups_shapley's.
+ * Per group of b >= 2 columns one enumeration of its refined game -- the other g - 1 groups whole and the group's
+ * columns as singletons, 2^(g - 1 + b) subsets -- by lsspa_groups_shapley's kernel with the weight of a subset looked up
+ * by two counts.  Hence one limit more: g - 1 + max_k b_k <= 32 players, refused with LSSPA_ERR_ARG naming the first
+ * offending group.  Everything else -- labels, refusals and their messages, fp64, bounded launches, bitwise
+ * reproducibility, nothing of the sampling path or of lsspa_subsets_shapley's state touched -- is lsspa_groups_shapley's,
+ * whose buffers this call shares.  info: the OR over all enumerations.  lsspa_groups_timing afterwards reports the sums
+ * over all launches of the call (the group game's included) and its longest launch.
+ *   lsspa_debug_owen_plan : host only (no context, no GPU) -- per target group k, plan[k][0 .. 7] = players of its
+ *                           refined game, gl, gh, ql of that game's layout, inner players (the group's columns) among the
+ *                           low and among the high players, high subsets enumerated (units x per = 2^gh), launches (0
+ *                           for a group of one column, which has no enumeration of its own).  Labels that
+ *                           lsspa_groups_owen would refuse: LSSPA_ERR_ARG. */
+int lsspa_groups_owen(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* owen /* [p] */, double* phi /* [g] */,
+                      int32_t* info);
+int lsspa_debug_owen_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* plan /* [g][8] */);
+
 /* Bootstrap of the exact attribution (p <= 32): how far would phi move had the rows been another draw from the same
  * population?  Replicate r resamples the rows of a side with replacement -- or takes the caller's weights -- and its
  * reduced problem is a WEIGHTED Gram of rows that stay on the device: with z = [x, y], S = sum_i w_i z_i z_i^T per side and

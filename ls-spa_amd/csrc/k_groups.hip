@@ -40,6 +40,18 @@
 //     the high groups in hi (thread j keeps group j's), the second to the pairs of high groups inside hi, which are
 //     dealt over the 256 threads (at most HH = 2 a thread) with their masks built once.
 // Every cell of the table is written by one thread, the sums are fixed butterflies and fixed loops: bitwise reproducible.
+//
+// Owen value (lsspa_groups_owen, the OWEN instantiation of the enumeration kernel): the two-level Shapley value of the
+// columns of one group, the target, with the groups as coalition structure.  The players of the launch are those of the
+// target's refined game -- the other groups whole (outer players), the target's b columns as singletons (inner players)
+// -- and everything above runs on them unchanged; only the weight of a subset K differs, by two counts instead of |K|:
+// with r outer and t inner players in K,
+//   a(K) = wo(r) wi(t - 1) u(K),  b(K) = wo(r) wi(t) u(K),   wo(r) = r! (g - 1 - r)! / g!,  wi(t) = t! (b - 1 - t)! / b!,
+//   Ow_i = sum_{K containing i} (a + b)(K) - sum_K b(K)      for an inner player i
+// (the outer players' columns of the table are written too and mean nothing).  t is a popcount of tid and one of hi
+// under the two masks of the inner players that the host leaves in GROUPS_TAB_OWEN_LO / _HI of the layout table, r the
+// rest of |K|; wo, wi(t - 1), wi(t) are rows 2 .. 4 of GroupArgs::w.  GroupArgs itself is as it was: a field more cost
+// an instantiation its registers once already (REPS below).
 #include "kernels.h"
 
 #include <algorithm>
@@ -80,6 +92,13 @@ struct GrpInterShared {
   double w2[3 * (GG + 1)];   // gamma, beta + gamma, alpha + 2 beta + gamma by |K|
   double dv[64];             // the step's (alpha + 2 beta + gamma) u per lane of wave 0
   double se, sd;             // the step's sums over wave 0 of (beta + gamma) u and of dv
+};
+
+// what the OWEN instantiation adds (the others declare none of it): the weights by the two counts
+struct GrpOwenShared {
+  double wo[GG + 1];         // wo(r), r = 0 .. g - 1 outer players
+  double wia[GG + 1];        // wi(t - 1), t = 0 .. b inner players (0 at t = 0)
+  double wib[GG + 1];        // wi(t) (0 at t = b)
 };
 
 __device__ inline double wave_sum(double x) {
@@ -283,11 +302,14 @@ __device__ inline int pair_col(int g, int i, int j) { return i * (2 * g - i - 1)
 
 // INTER: the interaction sums T0, T1, T2 beside phi's (lsspa_groups_interactions); a row of part is then
 // subsets_inter_cols(g) wide.  Everything of the phi-only instantiation is in both, unchanged.  REPS: the launch's second
-// grid dimension is the replicate (rep_offset above).
-template <bool INTER, bool REPS = false>
+// grid dimension is the replicate (rep_offset above).  OWEN (phi-only, one problem): the weights of the Owen value of a
+// target group's columns (the header); nothing else differs.
+template <bool INTER, bool REPS = false, bool OWEN = false>
 __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s0, uint64_t s1) {
+  static_assert(!OWEN || (!INTER && !REPS), "the Owen weights exist for phi of one problem only");
   __shared__ GrpShared sh;
   __shared__ GrpInterShared si;                // INTER only: never referenced, hence not allocated, otherwise
+  __shared__ GrpOwenShared so;                 // OWEN only, likewise
   const int tid = threadIdx.x;
   const int ng = a.ng, gl = a.gl, gh = a.gh;
   // INTER with REPS: the replicate's strides go into the arguments once, here, and the code below is the one-problem
@@ -333,6 +355,19 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
     }
     __syncthreads();                           // w2
   }
+  // OWEN only: the inner players among the high bits, and this lane's count of them among its low bits (tid)
+  uint32_t in_hi = 0;
+  int tl = 0;
+  if constexpr (OWEN) {
+    for (int e = tid; e <= GG; e += NT) {
+      so.wo[e] = a.w[2 * (GG + 1) + e];
+      so.wia[e] = a.w[3 * (GG + 1) + e];
+      so.wib[e] = a.w[4 * (GG + 1) + e];
+    }
+    in_hi = (uint32_t)a.tab[GROUPS_TAB_OWEN_HI];
+    tl = __popc(tid & a.tab[GROUPS_TAB_OWEN_LO]);
+    __syncthreads();                           // the three tables
+  }
   bool bad = false;
   const bool live = tid < (1 << gl);
   const int kt = __popc(tid);
@@ -341,9 +376,19 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
     const double v = group_values<RO>(sh, a, hi, tid, bad);
     if (live) {
       const int k = __popcll(hi) + kt;
-      const double c = (sh.wa[k] + sh.wb[k]) * v;
+      double wab, wb;
+      if constexpr (OWEN) {
+        const int t = tl + __popc((uint32_t)hi & in_hi);     // gh <= 31 (launch_groups_owen)
+        const double w = so.wo[k - t];
+        wab = w * (so.wia[t] + so.wib[t]);
+        wb = w * so.wib[t];
+      } else {
+        wab = sh.wa[k] + sh.wb[k];
+        wb = sh.wb[k];
+      }
+      const double c = wab * v;
       c_own += c;
-      b_own += sh.wb[k] * v;
+      b_own += wb * v;
 #pragma unroll
       for (int j = 0; j < GG; ++j)
         if (j < gh && ((hi >> j) & 1ull)) acc[j] += c;
@@ -562,6 +607,16 @@ hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, u
   } else {
     hipLaunchKernelGGL(groups_enum_kernel<false>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_groups_owen(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st) {
+  if (!args_ok(a) || !a.part || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  if (a.inv_yy_rep) return hipErrorInvalidValue;     // no replicates: one problem
+  // the kernel's mask of the inner players among the high ones is 32 bits wide (no layout of <= 64 columns has gh = 32)
+  if (a.gh > GHI) return hipErrorInvalidValue;
+  if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((groups_enum_kernel<false, false, true>), dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
   return hipGetLastError();
 }
 

@@ -368,6 +368,10 @@ constexpr int GROUPS_MAX_G = 32, GROUPS_MAX_P = 64, GROUPS_LOW_COLS = 6;
 constexpr int GROUPS_TAB_COLS = 0, GROUPS_TAB_COLGRP = GROUPS_MAX_P, GROUPS_TAB_COLIN = 2 * GROUPS_MAX_P,
               GROUPS_TAB_HSIZE = 3 * GROUPS_MAX_P, GROUPS_TAB_LGRP = GROUPS_TAB_HSIZE + GROUPS_MAX_G,
               GROUPS_TAB_LEN = GROUPS_TAB_LGRP + 8;
+// the two words behind the GROUPS_LOW_COLS of LGRP, 0 in every layout of groups_layout: the inner players of an Owen
+// enumeration (launch_groups_owen) as masks over the layout's low groups (bits of the lane) and high groups (bits of hi)
+constexpr int GROUPS_TAB_OWEN_LO = GROUPS_TAB_LGRP + GROUPS_LOW_COLS, GROUPS_TAB_OWEN_HI = GROUPS_TAB_OWEN_LO + 1;
+static_assert(GROUPS_TAB_OWEN_HI < GROUPS_TAB_LEN, "the Owen masks live inside the layout table");
 struct GroupLayout {
   int p, ng, nb, gl, gh, ql;
   int gid[GROUPS_MAX_G];
@@ -399,6 +403,13 @@ struct GroupArgs {
 // reps: with GroupArgs::inv_yy_rep only (phi-only or inter, units * reps <= 2^20)
 hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, bool inter,
                               hipStream_t st, int reps = 1);
+// The Owen value of one group's columns (k_groups.hip's header): launch_groups_enum's phi-only launch of one problem on
+// the layout of the target's refined game -- the other groups whole, the target's b columns as singletons -- with the
+// weights by two counts.  tab carries the inner players' masks in GROUPS_TAB_OWEN_LO / _HI; rows 2 .. 4 of w are
+// wo(r) = r! (g - 1 - r)! / g!, wi(t - 1) and wi(t) = t! (b - 1 - t)! / b! (0 outside 0 .. b - 1), each
+// [GROUPS_MAX_G + 1]; rows 0 and 1 are not read.  Refuses replicates (GroupArgs::inv_yy_rep).  Of a row of the table
+// the inner players' columns and b mean something: Ow_i = column i - column ng.
+hipError_t launch_groups_owen(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

@@ -3465,6 +3465,13 @@ int subsets_enumerate(lsspa_ctx* ctx, bool inter, double* out, int32_t* info) {
 // subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X: far below the bound of
 // 0.2 s, and long enough that the launches' own cost does not show.
 constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
+// steps of every unit that one launch of `units` workgroups takes on the layout L
+uint64_t groups_steps(const GroupLayout& L, uint64_t units) {
+  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
+  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
+  const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
+  return std::max<uint64_t>(1, per_launch / units);
+}
 
 int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, GroupLayout& L) {
   const int p = ctx->p;
@@ -3504,15 +3511,117 @@ int groups_enumerate(lsspa_ctx* ctx, bool inter, const int32_t* labels, int32_t 
   const uint64_t n_high = 1ull << L.gh;
   const uint64_t units = exact_units(n_high);
   a.per = n_high / units;
-  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
-  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
-  const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
-  const uint64_t steps = std::max<uint64_t>(1, per_launch / units);
+  const uint64_t steps = groups_steps(L, units);
   auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
     a.part = part;
     return launch_groups_enum(a, units, s0, s1, inter, ctx->stream);
   };
   return exact_enumerate(ctx, ctx->grp, inter ? subsets_inter_cols(ng) : ng + 1, n_high, steps, launch, out, info);
+}
+
+// ---- Owen value: the columns of a group, with the groups as coalition structure (k_groups.hip's header) ----
+// The refined game of target group k (b columns) has g - 1 + b players: the other groups whole (the outer players) and
+// the target's columns as singletons (the inner players), numbered in the caller's order with the target's columns in
+// the target's place -- group l < k stays l, the target's columns become k .. k + b - 1 in column order, group l > k
+// becomes l + b - 1.  groups_layout breaks ties between groups of one size by number, so the caller's numbering decides
+// which players of a size are low.
+constexpr int OWEN_MAX_PLAYERS = GROUPS_MAX_G;
+
+// size [g] of the groups; false where groups_layout would refuse the labels (which then names the reason)
+bool owen_sizes(const int32_t* labels, int p, int g, int* size) {
+  if (!labels || g < 1 || g > GROUPS_MAX_G || p < 1 || p > GROUPS_MAX_P) return false;
+  std::fill(size, size + g, 0);
+  for (int j = 0; j < p; ++j) {
+    if (labels[j] < -1 || labels[j] >= g) return false;
+    if (labels[j] >= 0) ++size[labels[j]];
+  }
+  return std::all_of(size, size + g, [](int s) { return s > 0; });
+}
+
+// the first group whose refined game has more than OWEN_MAX_PLAYERS players (-1: none)
+int owen_too_many(const int* size, int g) {
+  for (int k = 0; k < g; ++k)
+    if (g - 1 + size[k] > OWEN_MAX_PLAYERS) return k;
+  return -1;
+}
+
+void owen_limit_message(char* msg, size_t n, int k, int b, int g) {
+  snprintf(msg, n,
+           "the Owen value enumerates the refined game of every group, the other g - 1 groups and the group's own "
+           "columns, and takes at most %d players: group %d has %d columns beside %d other groups (%d players)",
+           OWEN_MAX_PLAYERS, k, b, g - 1, g - 1 + b);
+}
+
+// The layout L of target k's refined game with the inner players marked in its table (GROUPS_TAB_OWEN_LO / _HI);
+// ref [p]: the refined labels; n_lo, n_hi: the inner players among the low and the high groups.  (sizes as owen_sizes
+// gives them and within the player limit: the refined labels are then good)
+void owen_layout(const int32_t* labels, int p, int g, int k, int b, int32_t* ref, GroupLayout& L, int& n_lo, int& n_hi) {
+  for (int j = 0, n = 0; j < p; ++j) {
+    const int l = labels[j];
+    ref[j] = l < k ? l : l > k ? l + b - 1 : k + n++;
+  }
+  (void)groups_layout(ref, p, g - 1 + b, L);
+  uint32_t lo = 0, hi = 0;
+  for (int r = 0; r < L.ng; ++r)
+    if (L.gid[r] >= k && L.gid[r] < k + b) (r < L.gl ? lo : hi) |= 1u << (r < L.gl ? r : r - L.gl);
+  L.tab[GROUPS_TAB_OWEN_LO] = (int32_t)lo;
+  L.tab[GROUPS_TAB_OWEN_HI] = (int32_t)hi;      // gh <= 31: a layout of 32 high groups would have 7 x 32 columns
+  n_lo = __builtin_popcount(lo);
+  n_hi = __builtin_popcount(hi);
+}
+
+// rows 2 .. 4 of the weight table for launch_groups_owen: wo(r) of g groups, wi(t - 1) and wi(t) of b columns
+void owen_weight_rows(int g, int b, double* w3) {
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  std::fill(w3, w3 + 3 * WR, 0.0);
+  double binom = 1.0;                       // w(k) = 1 / (n C(n - 1, k)), as exact_weight_table forms it
+  for (int r = 0; r < g; ++r) {
+    w3[r] = 1.0 / ((double)g * binom);
+    binom = binom * (double)(g - 1 - r) / (double)(r + 1);
+  }
+  binom = 1.0;
+  for (int t = 0; t < b; ++t) {
+    const double wt = 1.0 / ((double)b * binom);
+    w3[WR + t + 1] = wt;                    // wi(t - 1) at t + 1
+    w3[2 * WR + t] = wt;                    // wi(t)
+    binom = binom * (double)(b - 1 - t) / (double)(t + 1);
+  }
+}
+
+// One OWEN enumeration: the Owen values of target k's columns into owen[col]; bits: its info word
+int owen_enumerate(lsspa_ctx* ctx, const int32_t* labels, int g, int k, int b, double* owen, int32_t* bits) {
+  const int p = ctx->p;
+  int32_t ref[GROUPS_MAX_P];
+  GroupLayout L, marked;
+  int n_lo, n_hi;
+  owen_layout(labels, p, g, k, b, ref, marked, n_lo, n_hi);
+  GroupArgs a;
+  TRY(groups_args(ctx, ref, g - 1 + b, a, L));
+  // what groups_args left on the device is the group game's of these labels: the marks and the Owen weights over it
+  // (the stream is idle but for the clearing of the info word)
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  double w3[3 * WR];
+  owen_weight_rows(g, b, w3);
+  HIPCHK(hipMemcpy(ctx->grp.w.ptr + 2 * WR, w3, sizeof w3, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->grp.tab.ptr + GROUPS_TAB_OWEN_LO, marked.tab + GROUPS_TAB_OWEN_LO, 2 * sizeof(int32_t),
+                   hipMemcpyHostToDevice));
+  const int ng = L.ng;
+  const uint64_t n_high = 1ull << L.gh;
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
+  const uint64_t steps = groups_steps(L, units);
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_groups_owen(a, units, s0, s1, ctx->stream);
+  };
+  double out[EXACT_MAX_PLAYERS + 1];
+  TRY(exact_enumerate(ctx, ctx->grp, ng + 1, n_high, steps, launch, out, bits));
+  int col_of[OWEN_MAX_PLAYERS];             // refined label - k of an inner player -> its column
+  for (int j = 0, n = 0; j < p; ++j)
+    if (labels[j] == k) col_of[n++] = j;
+  for (int r = 0; r < ng; ++r)
+    if (L.gid[r] >= k && L.gid[r] < k + b) owen[col_of[L.gid[r] - k]] = out[r] - out[ng];
+  return LSSPA_OK;
 }
 
 }  // namespace
@@ -3626,6 +3735,76 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
                             "a group subset's Gram matrix is not positive definite");
 } catch (...) {
   return abi_caught(ctx);
+}
+
+int lsspa_groups_owen(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* owen, double* phi, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!owen || !phi || !labels) return ctx->fail(LSSPA_ERR_ARG, "labels / owen / phi is NULL");
+  // the player limit before any enumeration; labels that groups_layout refuses go on to lsspa_groups_shapley's refusal
+  int size[GROUPS_MAX_G];
+  const bool sized = ctx->have_problem && owen_sizes(labels, ctx->p, g, size);
+  if (sized) {
+    const int k = owen_too_many(size, g);
+    if (k >= 0) {
+      char msg[320];
+      owen_limit_message(msg, sizeof msg, k, size[k], g);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  }
+  GroupLayout L;
+  double out[EXACT_MAX_PLAYERS + 1];
+  int32_t bits = 0;
+  TRY(groups_enumerate(ctx, false, labels, g, L, out, &bits));
+  if (!sized) return ctx->fail(LSSPA_ERR_STATE, "lsspa_groups_owen: the labels passed the group game's checks only");
+  for (int r = 0; r < L.ng; ++r) phi[L.gid[r]] = out[r] - out[L.ng];
+  ExactWork& W = ctx->grp;
+  double kernel_ms = W.kernel_ms, longest = W.max_launch_ms;
+  int64_t launches = W.launches;
+  const int p = ctx->p;
+  for (int j = 0; j < p; ++j)
+    if (labels[j] < 0) owen[j] = 0.0;
+  for (int k = 0; k < g; ++k) {
+    if (size[k] == 1) {
+      for (int j = 0; j < p; ++j)
+        if (labels[j] == k) owen[j] = phi[k];
+      continue;
+    }
+    int32_t b1 = 0;
+    TRY(owen_enumerate(ctx, labels, g, k, size[k], owen, &b1));
+    bits |= b1;
+    kernel_ms += W.kernel_ms;
+    longest = std::max(longest, W.max_launch_ms);
+    launches += W.launches;
+  }
+  W.kernel_ms = kernel_ms;
+  W.max_launch_ms = longest;
+  W.launches = launches;
+  if (info) *info = bits;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_owen_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* plan) try {
+  int size[GROUPS_MAX_G];
+  if (!plan || !owen_sizes(labels, p, g, size) || owen_too_many(size, g) >= 0) return LSSPA_ERR_ARG;
+  for (int k = 0; k < g; ++k) {
+    int32_t ref[GROUPS_MAX_P];
+    GroupLayout L;
+    int n_lo, n_hi;
+    owen_layout(labels, p, g, k, size[k], ref, L, n_lo, n_hi);
+    const uint64_t n_high = 1ull << L.gh;
+    const uint64_t units = exact_units(n_high), per = n_high / units;
+    const uint64_t steps = groups_steps(L, units);
+    int64_t* row = plan + 8 * k;
+    row[0] = L.ng; row[1] = L.gl; row[2] = L.gh; row[3] = L.ql;
+    row[4] = n_lo; row[5] = n_hi;
+    row[6] = (int64_t)(units * per);
+    row[7] = size[k] == 1 ? 0 : (int64_t)((per + steps - 1) / steps);    // a group of one column: no enumeration of its own
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@ from . import _samplers as S
 from ._native import LSSPANativeError
 from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
-                       MultiResponseResults, PermutationTestResults,
+                       MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
@@ -992,12 +992,14 @@ def ls_spa(X_train, X_test, y_train, y_test, reg=0., max_samples=2 ** 13, batch_
 SUBSETS_MAX_P = 32     # include/lsspa.h, lsspa_subsets_shapley
 GROUPS_MAX_G = 32      # include/lsspa.h, lsspa_groups_shapley
 GROUPS_MAX_P = 64
+OWEN_MAX_PLAYERS = 32  # include/lsspa.h, lsspa_groups_owen
 
 
-def group_labels(groups, p, max_groups=GROUPS_MAX_G):
+def group_labels(groups, p, max_groups=GROUPS_MAX_G, max_players=None):
     """(labels as int32, g) of ls_spa(groups=) and ls_spa_groups: a label per column, -1 the baseline, 0 .. g-1 the
     groups, none of them empty.  max_groups: the enumeration's limit (None for the sampled methods, whose only limit is
-    g <= p, which labels of length p cannot break).  ValueError names what is wrong."""
+    g <= p, which labels of length p cannot break).  max_players (ls_spa_owen): the limit on the players of a group's
+    refined game, the other g - 1 groups and the group's own columns.  ValueError names what is wrong."""
     labels = np.asarray(groups)
     if labels.ndim != 1 or len(labels) != p:
         raise ValueError(f"groups must have one label per column: length p = {p}, got shape {labels.shape}")
@@ -1016,6 +1018,14 @@ def group_labels(groups, p, max_groups=GROUPS_MAX_G):
     if len(missing):
         raise ValueError(f"groups has a gap in its numbering: no column carries label {int(missing[0])} "
                          f"(labels run to {g - 1})")
+    if max_players is not None:
+        size = np.bincount(labels[labels >= 0], minlength=g)
+        over = np.nonzero(g - 1 + size > max_players)[0]
+        if len(over):
+            k = int(over[0])
+            raise ValueError(f"the Owen value enumerates the refined game of every group, the other g - 1 groups and "
+                             f"the group's own columns, and takes at most {max_players} players: group {k} has "
+                             f"{int(size[k])} columns beside {g - 1} other groups ({g - 1 + int(size[k])} players)")
     return np.ascontiguousarray(labels, dtype=np.int32), g
 
 
@@ -1093,6 +1103,70 @@ def ls_spa_interactions(X_train, X_test, y_train, y_test, reg=0., *, groups=None
     return _ls_spa_subsets(*data, reg, perms=None, return_attribution_history=False,
                            device=device, row_sharded=row_sharded, checkpoint=None, comm=comm, engine=_engine,
                            groups=groups, interactions=True)
+
+
+def _baseline_r_squared(engine, labels, X_test, y_test):
+    """The out-of-sample R^2 of the baseline columns (label -1) alone from the engine's reduced problem, as
+    _singular_fit forms the full model's; 0.0 without a baseline."""
+    base = np.nonzero(np.asarray(labels) == -1)[0]
+    if len(base) == 0:
+        return 0.0
+    G, g, H, h = engine.gram()
+    sub = np.ix_(base, base)
+    try:
+        theta = np.linalg.solve(G[sub], g[base])
+    except np.linalg.LinAlgError:
+        theta = _min_norm_theta(G[sub], g[base])
+    if engine.tri:      # from the Gram side: also right when the test rows are sharded
+        return float((2.0 * (h[base] @ theta) - theta @ H[sub] @ theta) / engine.y_norm_sq)
+    pred = X_test[:, base].astype(np.float64) @ theta
+    return float((2.0 * (pred @ y_test) - pred @ pred) / engine.y_norm_sq)
+
+
+def ls_spa_owen(X_train, X_test, y_train, y_test, groups, reg=0., *, device=0, row_sharded=False, comm=None,
+                _engine=None):
+    """Exact Owen values of the out-of-sample R^2: the attribution of every column when the columns form groups (g <= 32
+    groups over p <= 64 columns, g - 1 + the largest group's size <= 32).
+
+    ``ls_spa(method='subsets', groups=)`` says what a variable -- a one-hot factor, a spline basis -- earns of the R^2;
+    this call says which of its columns earn it.  The Owen value is the two-level Shapley value under the coalition
+    structure ``groups``: the mean of a column's lift over exactly those orderings in which the baseline comes first and
+    every group's columns are contiguous.  (The ungrouped ``ls_spa(method='subsets')`` lets a factor's levels compete
+    with every other column one by one: another game, with other numbers.)  Per group of two or more columns the GPU
+    enumerates that group's refined game -- the other groups whole, its own columns as singletons -- in fp64, bitwise
+    reproducibly (include/lsspa.h, lsspa_groups_owen).
+
+    groups:  one integer label per column as ``ls_spa(method='subsets', groups=)`` takes them: k in 0 .. g-1 puts the
+        column into group k, -1 into a baseline that every model includes and that gets no attribution.
+
+    Returns ``OwenResults``: ``attribution`` [p], the Owen values (0.0 on baseline columns); ``group_attribution`` [g],
+    bitwise what ``ls_spa(method='subsets', groups=)`` returns; ``theta`` [p], ``r_squared`` and
+    ``baseline_r_squared``, the R^2 of the baseline alone (0 without one).  ``attribution[labels == k].sum()`` is
+    ``group_attribution[k]`` and ``attribution.sum()`` is ``r_squared - baseline_r_squared``, up to rounding.
+    All-singleton groups give the ungrouped exact attribution; one group gives the exact attribution of its columns
+    with the baseline eliminated.
+
+    p > 64, g > 32, a group whose refined game has more than 32 players and bad labels raise ValueError before any GPU
+    work.  ``reg``, ``device``, ``row_sharded``, ``comm`` and the RuntimeWarning for a Gram matrix that is not
+    numerically positive definite are those of ``ls_spa(method='subsets')``."""
+    X_train, X_test, y_train, y_test = _coerce_data(X_train, X_test, y_train, y_test)
+    p = X_train.shape[1]
+    if p > GROUPS_MAX_P:
+        raise ValueError(f"grouped attribution takes at most p = {GROUPS_MAX_P} columns, the baseline's included "
+                         f"(this problem has p = {p})")
+    labels, _ = group_labels(groups, p, max_players=OWEN_MAX_PLAYERS)
+    with _engine_call(_engine, device, comm) as engine:
+        # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like the values
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        theta, r_squared, info = _load_and_fit(engine, (X_train, X_test, y_train, y_test), reg, row_sharded, comm)
+        owen, phi, bits = engine.groups_owen(labels)
+        _info_verdict((bits | info) & 1, stacklevel=2)      # (an enumeration reports a broken pivot, nothing else)
+        if info & 1:
+            theta, r_squared = _singular_fit(engine, X_test, y_test)
+        base = _baseline_r_squared(engine, labels, X_test, y_test)
+    return OwenResults(attribution=owen, group_attribution=phi, theta=theta, r_squared=r_squared,
+                       baseline_r_squared=base)
 
 
 MULTI_MAX_COLS = 32767     # include/lsspa.h, lsspa_multi_load: p + m

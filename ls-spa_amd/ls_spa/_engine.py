@@ -132,6 +132,21 @@ def debug_boot_groups_plan(R: int, n: int, m: int, labels, block: int = 0, inter
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
+OWEN_PLAN_FIELDS = ("players", "gl", "gh", "ql", "inner_low", "inner_high", "high_subsets", "launches")
+
+
+def debug_owen_plan(labels):
+    """Test hook, host only: per target group, how groups_owen enumerates its refined game (include/lsspa.h,
+    lsspa_debug_owen_plan) -- a list of g dicts with OWEN_PLAN_FIELDS.  ValueError for labels the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros((max(g, 1), 8), dtype=np.int64)
+    rc = N.load().lsspa_debug_owen_plan(N.iptr(labels), len(labels), g, out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_owen_plan: status {rc}")
+    return [dict(zip(OWEN_PLAN_FIELDS, (int(v) for v in row))) for row in out[:g]]
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -793,9 +808,22 @@ class HipEngine:
                                                         C.byref(info)))
         return phi, inter, info.value
 
+    def groups_owen(self, labels):
+        """(owen, phi, info): the exact Owen value of every column with the groups that labels names as coalition
+        structure (include/lsspa.h, lsspa_groups_owen) -- owen of length p, 0.0 on baseline columns, a group's entries
+        summing to its phi -- and phi of length g, bitwise groups_shapley's.  groups_timing() then speaks of all of this
+        call's enumerations."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        owen, phi = np.empty(self.p), np.empty(max(g, 1))
+        info = C.c_int32()
+        self._check(self._lib.lsspa_groups_owen(self._h, N.iptr(labels), g, N.dptr(owen), N.dptr(phi), C.byref(info)))
+        return owen, phi, info.value
+
     def groups_timing(self):
-        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley or groups_interactions
-        call."""
+        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley, groups_interactions or
+        groups_owen call."""
         return self._exact_timing(self._lib.lsspa_groups_timing)
 
     def debug_group_values(self, labels, masks):

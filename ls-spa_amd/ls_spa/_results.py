@@ -160,6 +160,34 @@ class MultiGroupResults:
 
 
 @dataclass
+class OwenResults:
+    """What ``ls_spa_owen`` returns for p columns in g groups.  ``attribution`` [p]: the exact Owen value of every
+    column, 0.0 on baseline columns; ``group_attribution`` [g]: the groups' Shapley values, what
+    ``ls_spa(method='subsets', groups=)`` returns; ``theta`` [p] and ``r_squared`` the full model's;
+    ``baseline_r_squared`` the out-of-sample R^2 of the baseline columns alone (0 without a baseline).  The entries of
+    ``attribution`` of group k sum to ``group_attribution[k]``, all of them to ``r_squared - baseline_r_squared``."""
+    attribution: np.ndarray
+    group_attribution: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+    baseline_r_squared: float
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}p = {len(self.attribution)} columns in g = {len(self.group_attribution)} groups",
+            f"{pad}Out-of-sample R^2 with all columns: {self.r_squared:.2e}",
+            f"{pad}Out-of-sample R^2 of the baseline: {self.baseline_r_squared:.2e}",
+            "",
+            f"{pad}Shapley attribution of the groups: {_head(self.group_attribution)}",
+            f"{pad}Owen values of the columns: {_head(self.attribution)}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class PermutationTestResults:
     """What ``ls_spa_permutation_test`` returns; d = p, or the g groups of ``groups=``.  ``attribution`` [d], ``theta``
     [p], ``r_squared`` (and ``baseline_r_squared`` with groups, else None): the observed values.  ``null_attribution``
