@@ -123,6 +123,24 @@ int lsspa_debug_subset_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, 
  * 37 MB of device memory at p = 32. */
 int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi /* [p] */, double* inter /* [p*p] */, int32_t* info);
 
+/* Best subset of every size by the same v, over the same enumeration of all 2^p subsets (p <= 32): for k = 0 .. p
+ *   v[k] = max over the candidates K with |K| = k of v(K),   masks[k] = the K that attains it (bit j = feature j),
+ * an arg-max, not a sum: what lsspa_subsets_shapley folds away.  v[k] has the very bits lsspa_debug_subset_values
+ * returns for masks[k].
+ * Ties: the larger value wins, on equal values the numerically smaller mask -- a total order, so the result does not
+ * depend on how the work is cut into units and launches.
+ * Candidates: the subsets K with (K & include) == include (columns every model must contain; bits at or above p are
+ * LSSPA_ERR_ARG) whose own pivots all passed the relative test.  A subset with a failed pivot is not a candidate and
+ * raises LSSPA_INFO_NOT_PD in info (whether or not it contains include); a NaN value never wins.  found[k] = 0: no
+ * subset of size k was a candidate (k < popcount(include), or every one failed a pivot); v[k] is then NaN and masks[k]
+ * 0.  With include == 0, v[0] = 0.0 with the empty mask.
+ * Limits and errors are those of lsspa_subsets_shapley (p > 32, no problem loaded: LSSPA_ERR_ARG); NULL v, masks or
+ * found is LSSPA_ERR_ARG, info may be NULL.  fp64, bounded launches as that call cuts them, no atomics on the table:
+ * two calls agree bitwise.  It shares lsspa_subsets_shapley's buffers (a call of that before and after this one
+ * agrees bitwise) and leaves its timing where lsspa_subsets_timing reads it; nothing of the sampling path changes. */
+int lsspa_subsets_best(lsspa_ctx* ctx, uint32_t include, double* v /* [p+1] */, uint32_t* masks /* [p+1] */,
+                       uint8_t* found /* [p+1] */, int32_t* info);
+
 /* Exact Shapley attribution over GROUPS of columns: the players are the g <= 32 groups, the problem has p <= 64 columns.
  * labels[j] in {-1, 0 .. g-1} for every column j: group k is {j : labels[j] == k} (none may be empty), the columns
  * labelled -1 are the baseline B, part of every model and given no attribution.  With F(S) = B + the columns of the

@@ -39,6 +39,9 @@
 // Replicates (the bootstrap, k_boot.hip): launch_subsets_enum(.., reps) runs `reps` problems laid out one behind the other
 // as the second grid dimension of the kernel (the REPS instantiations, rep_offset below), phi-only or with the interaction
 // sums; a replicate's arithmetic is that of the one-problem kernel, operation for operation.
+//
+// Best subset of every size (lsspa_subsets_best, subsets_best_kernel below): the same enumeration keeps, instead of sums,
+// the largest v(K) and its mask per size |K| -- a kernel of its own beside the enumeration kernel, which it leaves alone.
 #include "kernels.h"
 
 namespace lsspa {
@@ -418,6 +421,117 @@ __global__ __launch_bounds__(64) void subsets_debug_kernel(SubsetArgs a, const u
   if (__any(bad) && lane == 0) atomicOr(a.info, 1);
 }
 
+// ---- best subset of every size (lsspa_subsets_best) ----
+// The same units, steps and launches as subsets_enum_kernel, the same subset_values; what is kept of v(K) is not a sum
+// but, per size k = |K|, the largest value and its mask (hi << q) | T.  Order: the larger value wins, on equal values
+// the numerically smaller mask; a subset whose own pivot failed, or that lacks a column of `include`, is no candidate
+// and NaN never wins (v > best from -inf).  The order is total, so the result does not depend on how the work is cut.
+//
+// Running bests: |K| = popc(hi) + popc(T) and hi = blockIdx.x per + s with per a power of two, so popc(hi) =
+// popc(blockIdx.x) + popc(s): inside a unit the size class of a lane's subset is popc(s), at most log2(per) + 1 <=
+// SBS = 14 classes (per <= 2^13).  A lane keeps (value, hi) per class in statically indexed registers; popc(s) is the
+// same for the whole wave, so the update is one compare-select behind a scalar branch.  Within a class a lane sees its
+// masks in ascending order: the strict compare keeps the smaller one.
+constexpr int SBS = 14;
+
+// (v, mask) <- the better of it and (bv, bmask) in the total order above; "no candidate" is v = -inf here (a candidate
+// won a strict compare against -inf, so its value is larger), which loses against every candidate
+__device__ inline void best_merge(double& v, uint32_t& mask, double bv, uint32_t bmask) {
+  const bool take = bv > v || (bv == v && bmask < mask);
+  v = take ? bv : v;
+  mask = take ? bmask : mask;
+}
+
+__device__ inline void wave_best(double& v, uint32_t& mask) {
+  // fixed butterfly; the order is total, so every lane ends with the same winner
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const uint32_t om = (uint32_t)__shfl_xor((int)mask, o, 64);
+    best_merge(v, mask, ov, om);
+  }
+}
+
+// a.part [units][p + 1] (values), bm [units][p + 1][2] (mask, found): unit u's best subset of every size so far; a launch
+// merges its own into them (found = 0: no candidate yet, the value and mask beside it mean nothing).  One workgroup owns a row, launches are ordered by the stream: plain loads and stores.
+__global__ __launch_bounds__(64) void subsets_best_kernel(SubsetArgs a, uint64_t s0, uint64_t s1, uint32_t include,
+                                                          uint32_t* __restrict__ bm) {
+  __shared__ SubShared sh;
+  const int lane = threadIdx.x;
+  const int p = a.p, q = a.q;
+  load_shared<false>(sh, a, lane);
+  double bv[SBS];
+  uint32_t bh[SBS];
+#pragma unroll
+  for (int j = 0; j < SBS; ++j) {
+    bv[j] = -__builtin_huge_val();
+    bh[j] = 0u;
+  }
+  const uint32_t inc_lo = include & ((1u << q) - 1u), inc_hi = include >> q;     // q >= 1
+  const bool lane_ok = lane < (1 << q) && ((uint32_t)lane & inc_lo) == inc_lo;
+  bool any_bad = false;
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    bool bad = false;                         // this subset's own pivots: the high ones the wave's, the low ones the lane's
+    const double v = subset_values<false>(sh, a, hi, lane, bad);
+    any_bad |= bad;
+    const uint32_t h32 = (uint32_t)hi;
+    const bool cand = lane_ok && !bad && (h32 & inc_hi) == inc_hi;
+    const int cls = __popcll(s);
+#pragma unroll
+    for (int j = 0; j < SBS; ++j)
+      if (cls == j && cand && v > bv[j]) {
+        bv[j] = v;
+        bh[j] = h32;
+      }
+    __syncthreads();
+  }
+  double* rv = a.part + (int64_t)blockIdx.x * (p + 1);
+  uint32_t* rm = bm + (int64_t)blockIdx.x * (p + 1) * 2;
+  // the sizes this unit can hold: popc(unit) + popc(s) + popc(T), s < per (a power of two), T < 2^q
+  const int k0 = __popc(blockIdx.x), k1 = min(p, k0 + __popcll(a.per - 1) + q);
+  const int base = k0 + __popc(lane);                       // |K| of this lane's class 0
+  for (int k = k0; k <= k1; ++k) {
+    double v = -__builtin_huge_val();
+    uint32_t mask = 0u;
+#pragma unroll
+    for (int j = 0; j < SBS; ++j)
+      if (base + j == k) {
+        v = bv[j];
+        mask = (bh[j] << q) | (uint32_t)lane;
+      }
+    wave_best(v, mask);
+    if (lane == 0 && v > -__builtin_huge_val()) {
+      if (rm[2 * k + 1] != 0u) best_merge(v, mask, rv[k], rm[2 * k]);
+      rv[k] = v;
+      rm[2 * k] = mask;
+      rm[2 * k + 1] = 1u;
+    }
+  }
+  if (__any(any_bad) && lane == 0) atomicOr(a.info, 1);
+}
+
+// out_v [p + 1], out_m [p + 1][2]: the best over the units, one workgroup per size, the units dealt over the lanes in a
+// fixed order (any order gives the same winner)
+__global__ __launch_bounds__(64) void subsets_best_reduce_kernel(const double* __restrict__ bv,
+                                                                 const uint32_t* __restrict__ bm, int64_t units, int p1,
+                                                                 double* __restrict__ out_v,
+                                                                 uint32_t* __restrict__ out_m) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  double v = -__builtin_huge_val();
+  uint32_t mask = 0u;
+  for (int64_t u = lane; u < units; u += 64) {
+    const int64_t e = u * p1 + k;
+    if (bm[2 * e + 1] != 0u) best_merge(v, mask, bv[e], bm[2 * e]);
+  }
+  wave_best(v, mask);
+  if (lane == 0) {
+    out_v[k] = v;
+    out_m[2 * k] = mask;
+    out_m[2 * k + 1] = v > -__builtin_huge_val() ? 1u : 0u;
+  }
+}
+
 // H = Ft Ft^T [p][p] (stride p) and h = Ft ytil (appended) of the rect-mode test factor: one workgroup per entry, its
 // 256 threads strided over the m columns, then a fixed tree (the same sums on every call; m may be up to 2^20 through
 // lsspa_set_reduced).  Entries (i, j) and (j, i) both form the product of rows min(i, j) and max(i, j) in the same
@@ -483,6 +597,25 @@ hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, do
   if (!part || !out || units < 1 || cols < 2 || cols > subsets_inter_cols(SP) || reps < 1 || reps > 65535)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(subsets_reduce_kernel, dim3(cols, (unsigned)reps), dim3(64), 0, st, part, units, cols, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_best(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, uint32_t include,
+                               uint32_t* bm, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !bm || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  const int nh = a.p - a.q;
+  if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  // the size classes of a unit are popc(s), s < per: per a power of two (it is: units per = 2^nh) of at most SBS - 1 bits
+  if (a.per > (1ull << (SBS - 1))) return hipErrorInvalidValue;
+  if (a.p < 32 && (include >> a.p) != 0u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_best_kernel, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1, include, bm);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_best_reduce(const double* bv, const uint32_t* bm, int64_t units, int p, double* out_v,
+                                      uint32_t* out_m, hipStream_t st) {
+  if (!bv || !bm || !out_v || !out_m || units < 1 || p < 1 || p > SP) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_best_reduce_kernel, dim3(p + 1), dim3(64), 0, st, bv, bm, units, p + 1, out_v, out_m);
   return hipGetLastError();
 }
 

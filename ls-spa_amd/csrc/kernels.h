@@ -348,6 +348,16 @@ hipError_t launch_subsets_enum(const SubsetArgs& a, uint64_t units, uint64_t s0,
 // part + r units cols and writes out + r cols
 hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, double* out, hipStream_t st,
                                  int reps = 1);
+// Best subset of every size (lsspa_subsets_best): the units, steps and launches of launch_subsets_enum (reps = 1), but
+// a.part [units][p + 1] holds each unit's largest v(K) per size |K| and bm [units][p + 1][2] its mask (bit j = feature
+// j) and a found flag; both zeroed before the first launch, every launch merges into them.  Larger value wins, on equal
+// values the smaller mask; only subsets K with (K & include) == include whose own pivots passed are candidates.  per
+// must be at most 2^13 (it is for units = min(2^(p - q), 8192)).
+hipError_t launch_subsets_best(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, uint32_t include,
+                               uint32_t* bm, hipStream_t st);
+// out_v[k], out_m[k][2] (mask, found): the best of size k = 0 .. p over the units' rows
+hipError_t launch_subsets_best_reduce(const double* bv, const uint32_t* bm, int64_t units, int p, double* out_v,
+                                      uint32_t* out_m, hipStream_t st);
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used

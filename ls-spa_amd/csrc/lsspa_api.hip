@@ -50,11 +50,12 @@ struct ExactWork {
   DevBuf<double> Hh, w, part, out, vals;   // rect-mode test Gram, Shapley weights, partial table, its sums, debug values
   DevBuf<uint64_t> masks;                  // the debug values' subsets
   DevBuf<int32_t> info, tab;               // info word; GroupLayout::tab (groups only)
+  DevBuf<uint32_t> best;                   // lsspa_subsets_best: (mask, found) of the units' rows, then of the result
   double kernel_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
     dev_free(Hh); dev_free(w); dev_free(part); dev_free(out); dev_free(vals);
-    dev_free(masks); dev_free(info); dev_free(tab);
+    dev_free(masks); dev_free(info); dev_free(tab); dev_free(best);
   }
 };
 
@@ -3344,9 +3345,11 @@ struct Events {
 // [units][cols], `steps` of the n_high / units a launch.  out[0 .. cols - 1]: the table's column sums
 // (launch_subsets_reduce).  With n players the first n + 1 columns are phi's: a player's phi is its column minus column
 // n; what follows them is the entry point's own.  info (may be NULL): the info word.  Leaves the call's timing in W.
-template <typename Launch>
-int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uint64_t steps, Launch&& launch,
-                    double* out, int32_t* info) {
+// exact_enumerate_with: the same launches, events and timing for a table that is not summed (lsspa_subsets_best):
+// finish(units) enqueues the reduction of the table and the copies of its result to the host instead.
+template <typename Launch, typename Finish>
+int exact_enumerate_with(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uint64_t steps, Launch&& launch,
+                         Finish&& finish, int32_t* info) {
   const uint64_t units = exact_units(n_high);
   const uint64_t per = n_high / units;                 // both powers of two
   TRY(dev_alloc(ctx, W.part, (size_t)units * cols));
@@ -3363,9 +3366,8 @@ int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uin
     HIPCHK(launch(W.part.ptr, s0, std::min(per, s0 + steps)));
     HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
   }
-  HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, cols, W.out.ptr, ctx->stream));
+  TRY(finish((int64_t)units));
   int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (info) *info = bits;
@@ -3379,6 +3381,17 @@ int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uin
     W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
   }
   return LSSPA_OK;
+}
+
+template <typename Launch>
+int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uint64_t steps, Launch&& launch,
+                    double* out, int32_t* info) {
+  auto finish = [&](int64_t units) {
+    HIPCHK(launch_subsets_reduce(W.part.ptr, units, cols, W.out.ptr, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
+    return (int)LSSPA_OK;
+  };
+  return exact_enumerate_with(ctx, W, cols, n_high, steps, launch, finish, info);
 }
 
 // inter [n][n] of the column sums `out` of an interactions table of n players (kernels.h): I_ij = T0 - T1_i - T1_j +
@@ -3457,6 +3470,42 @@ int subsets_enumerate(lsspa_ctx* ctx, bool inter, double* out, int32_t* info) {
     return launch_subsets_enum(a, units, s0, s1, inter, ctx->stream);
   };
   return exact_enumerate(ctx, ctx->sub, inter ? subsets_inter_cols(p) : p + 1, n_high, steps, launch, out, info);
+}
+
+// lsspa_subsets_best: the same units, launches and timing; the table holds each unit's best subset per size, values in
+// ctx->sub.part and (mask, found) in ctx->sub.best, whose last p + 1 pairs receive the result.
+int subsets_best(lsspa_ctx* ctx, uint32_t include, double* v, uint32_t* masks, uint8_t* found, int32_t* info) {
+  SubsetArgs a;
+  TRY(subsets_args(ctx, a));
+  const int p = ctx->p;
+  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
+  const uint64_t n_high = 1ull << (p - a.q);
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
+  const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
+  ExactWork& W = ctx->sub;
+  const size_t rows = (size_t)units * (p + 1);
+  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)p + 1)));
+  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, ctx->stream));
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_subsets_best(a, units, s0, s1, include, W.best.ptr, ctx->stream);
+  };
+  uint32_t mf[2 * (SUBSETS_MAX_P + 1)];
+  auto finish = [&](int64_t n_units) {
+    uint32_t* out_m = W.best.ptr + 2 * rows;
+    HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, n_units, p, W.out.ptr, out_m, ctx->stream));
+    HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
+    return (int)LSSPA_OK;
+  };
+  TRY(exact_enumerate_with(ctx, W, p + 1, n_high, steps, launch, finish, info));
+  for (int k = 0; k <= p; ++k) {
+    found[k] = mf[2 * k + 1] ? 1 : 0;
+    masks[k] = found[k] ? mf[2 * k] : 0u;
+    if (!found[k]) v[k] = std::nan("");
+  }
+  return LSSPA_OK;
 }
 
 // ---- ... over groups of columns (k_groups.hip) ----
@@ -3649,6 +3698,15 @@ int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi, double* inter, int32
   for (int j = 0; j < p; ++j) phi[j] = out[j] - out[p];
   exact_inter_matrix(out.data(), p, nullptr, inter);
   return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_subsets_best(lsspa_ctx* ctx, uint32_t include, double* v, uint32_t* masks, uint8_t* found,
+                       int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!v || !masks || !found) return ctx->fail(LSSPA_ERR_ARG, "v / masks / found is NULL");
+  return subsets_best(ctx, include, v, masks, found, info);
 } catch (...) {
   return abi_caught(ctx);
 }

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
@@ -1167,6 +1167,103 @@ def ls_spa_owen(X_train, X_test, y_train, y_test, groups, reg=0., *, device=0, r
         base = _baseline_r_squared(engine, labels, X_test, y_test)
     return OwenResults(attribution=owen, group_attribution=phi, theta=theta, r_squared=r_squared,
                        baseline_r_squared=base)
+
+
+def include_mask(include, p):
+    """The columns every model must contain as lsspa_subsets_best's mask (bit j = column j) and as a sorted index
+    array; ValueError names what is wrong with them.  Needs no engine."""
+    if include is None:
+        return 0, np.zeros(0, dtype=np.int64)
+    try:
+        raw = None if isinstance(include, (str, bytes)) else np.asarray(list(include))
+    except TypeError:
+        raw = None
+    if raw is None or raw.ndim != 1:
+        raise ValueError("include must be an iterable of column indices")
+    if raw.size == 0:
+        return 0, np.zeros(0, dtype=np.int64)
+    cols = raw.astype(np.int64)
+    if raw.dtype == bool or not np.array_equal(cols, raw):
+        raise ValueError("include must hold integer column indices")
+    if cols.min() < 0 or cols.max() >= p:
+        raise ValueError(f"include names a column outside 0 .. {p - 1}")
+    if len(np.unique(cols)) != len(cols):
+        raise ValueError("include names a column twice")
+    cols = np.sort(cols)
+    return sum(1 << int(j) for j in cols), cols
+
+
+def _subset_fit(G, g, cols):
+    """theta [p] of the model on the columns `cols` from the reduced problem: G_KK theta_K = g_K, exactly 0.0
+    elsewhere."""
+    theta = np.zeros(len(g))
+    if len(cols):
+        sub = np.ix_(cols, cols)
+        try:
+            theta[cols] = np.linalg.solve(G[sub], g[cols])
+        except np.linalg.LinAlgError:
+            theta[cols] = _min_norm_theta(G[sub], g[cols])
+    return theta
+
+
+def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=None, device=0, _engine=None):
+    """Exhaustive best-subset selection by out-of-sample R^2: the best model of every size over all 2^p feature subsets
+    (p <= 32).
+
+    ``ls_spa`` says who earns the R^2; this call says which model to keep.  v(S), the out-of-sample R^2 of the model
+    fitted on the features in S, is not monotone in S -- the best model is usually not the full one, and no
+    branch-and-bound rule applies -- so the GPU evaluates every subset, in the enumeration that
+    ``ls_spa(method='subsets')`` runs (fp64, bitwise reproducible; include/lsspa.h, lsspa_subsets_best), and keeps per
+    size the largest value and its subset.  On equal values the subset with the smaller mask (bit j = feature j) wins.
+
+    include:  an iterable of column indices that every model must contain (an intercept, controls); the sizes then
+        start at len(include).
+
+    Returns ``BestSubsetsResults``: ``sizes``, ``subsets`` [n][p] bool, ``r_squared`` [n], ``theta`` [n][p] (each
+    winner refitted on the host in fp64, exactly 0.0 outside its subset), ``best_size``, ``best_subset`` and
+    ``full_r_squared``, which is ``ls_spa(method='subsets').r_squared``.
+
+    p > 32, an ``include`` out of range or with duplicates, shapes that do not fit and a ``y_test`` that is identically
+    zero are refused before any GPU work.  A subset whose Gram matrix is not numerically positive definite is no
+    candidate and raises the RuntimeWarning of ``ls_spa(method='subsets')``; a size without any candidate is a NaN
+    row.  ``reg`` and ``device`` are that call's."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    p = data[0].shape[1]
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_best_subsets enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} "
+                         f"features (this problem has p = {p})")
+    if p < 1 or data[1].shape[0] < 1:
+        raise ValueError(f"ls_spa_best_subsets needs p >= 1 features and M >= 1 test rows (p = {p}, "
+                         f"M = {data[1].shape[0]})")
+    mask, inc = include_mask(include, p)
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+    with _engine_call(_engine, device) as engine:
+        # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like the values
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        _, full_r_squared, info = _load_and_fit(engine, data, reg, False, None)
+        v, masks, found, bits = engine.subsets_best(mask)
+        if info & 1:
+            _, full_r_squared = _singular_fit(engine, data[1], data[3])
+        G, g, _, _ = engine.gram()
+    _info_verdict((bits | info) & 1, stacklevel=2)      # (an enumeration reports a broken pivot, nothing else)
+    sizes = np.arange(len(inc), p + 1)
+    n = len(sizes)
+    subsets = np.zeros((n, p), dtype=bool)
+    r_squared = np.full(n, np.nan)
+    theta = np.full((n, p), np.nan)
+    for i, k in enumerate(sizes):
+        if found[k]:
+            subsets[i] = (int(masks[k]) >> np.arange(p)) & 1
+            r_squared[i] = v[k]
+            theta[i] = _subset_fit(G, g, np.nonzero(subsets[i])[0])
+    best_size, best_subset = -1, np.zeros(p, dtype=bool)
+    if not np.all(np.isnan(r_squared)):
+        i = int(np.nanargmax(r_squared))      # the first of equal maxima: the smallest size
+        best_size, best_subset = int(sizes[i]), subsets[i].copy()
+    return BestSubsetsResults(sizes=sizes, subsets=subsets, r_squared=r_squared, theta=theta, best_size=best_size,
+                              best_subset=best_subset, full_r_squared=float(full_r_squared))
 
 
 MULTI_MAX_COLS = 32767     # include/lsspa.h, lsspa_multi_load: p + m

@@ -394,6 +394,19 @@ class HipEngine:
         self._check(self._lib.lsspa_subsets_interactions(self._h, N.dptr(phi), N.dptr(inter), C.byref(info)))
         return phi, inter, info.value
 
+    def subsets_best(self, include=0):
+        """(v, masks, found, info): the best subset of every size k = 0 .. p by the out-of-sample R^2 v, over all 2^p
+        subsets that contain the columns of the mask `include` (include/lsspa.h, lsspa_subsets_best): v [p + 1] float64,
+        masks [p + 1] uint32 (bit j = feature j), found [p + 1] bool (False: no candidate of that size, v is NaN).
+        subsets_timing() then speaks of this call."""
+        n = self.p + 1
+        v, masks, found = np.empty(n), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)
+        info = C.c_int32()
+        self._check(self._lib.lsspa_subsets_best(
+            self._h, int(include), N.dptr(v), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            found.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)))
+        return v, masks, found.astype(bool), info.value
+
     # ---- bootstrap of the exact attribution (p <= 32; over groups of columns p <= 64) ------
     def boot_load(self, X_train, X_test, y_train, y_test, reg: float, grouped: bool = False):
         """Keep [X | y] of both sides on the device for boot_run (include/lsspa.h, lsspa_boot_load); the loaded problem is
@@ -768,8 +781,8 @@ class HipEngine:
         return out
 
     def subsets_timing(self):
-        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley or subsets_interactions
-        call."""
+        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley, subsets_interactions or
+        subsets_best call."""
         return self._exact_timing(self._lib.lsspa_subsets_timing)
 
     def debug_subset_values(self, masks):

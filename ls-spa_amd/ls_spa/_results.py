@@ -188,6 +188,41 @@ class OwenResults:
 
 
 @dataclass
+class BestSubsetsResults:
+    """What ``ls_spa_best_subsets`` returns for p features and n = p + 1 - len(include) sizes.  ``sizes`` [n]: the
+    model sizes len(include) .. p; ``subsets`` [n][p] bool: the best subset of each size (row i has ``sizes[i]`` True
+    entries, the columns of ``include`` among them); ``r_squared`` [n]: its out-of-sample R^2; ``theta`` [n][p]: its
+    coefficients, exactly 0.0 outside the subset.  A size without a candidate (every subset of that size had a Gram
+    matrix that is not numerically positive definite) is a row of NaN in ``r_squared`` and ``theta`` and of False in
+    ``subsets``.  ``best_size``: the size with the largest ``r_squared``, the smallest such size on ties, NaN sizes
+    skipped (-1 if every size is NaN); ``best_subset`` [p] bool: its subset; ``full_r_squared``: the R^2 of all p
+    features, what ``ls_spa(method='subsets').r_squared`` returns."""
+    sizes: np.ndarray
+    subsets: np.ndarray
+    r_squared: np.ndarray
+    theta: np.ndarray
+    best_size: int
+    best_subset: np.ndarray
+    full_r_squared: float
+
+    def __repr__(self):
+        pad = " " * 8
+        p = np.asarray(self.subsets).shape[1]
+        chosen = ", ".join(str(j) for j in np.nonzero(self.best_subset)[0][:12])
+        best = (f"{float(self.r_squared[self.best_size - int(self.sizes[0])]):.2e}"
+                if self.best_size >= 0 else "nan")
+        lines = [
+            "",
+            f"{pad}p = {p}, best subsets of sizes {int(self.sizes[0])} .. {int(self.sizes[-1])}",
+            f"{pad}Out-of-sample R^2 with all features: {self.full_r_squared:.2e}",
+            f"{pad}Best model: {self.best_size} features, out-of-sample R^2 {best}",
+            f"{pad}Its features: ({chosen}{', ...' if int(np.sum(self.best_subset)) > 12 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class PermutationTestResults:
     """What ``ls_spa_permutation_test`` returns; d = p, or the g groups of ``groups=``.  ``attribution`` [d], ``theta``
     [p], ``r_squared`` (and ``baseline_r_squared`` with groups, else None): the observed values.  ``null_attribution``
