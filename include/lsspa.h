@@ -174,6 +174,29 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
 int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */,
                               double* inter /* [g*g] */, int32_t* info);
 
+/* Best group subset of every size: lsspa_subsets_best with the groups of lsspa_groups_shapley as the players, over the
+ * same enumeration of all 2^g group subsets (g <= 32, p <= 64) and the same u.  For k = 0 .. g
+ *   u[k] = max over the candidates S with |S| = k groups of u(S),   masks[k] = the S that attains it (bit k = group k,
+ *   the caller's labels),
+ * so that size 0 is the baseline alone: u[0] = R^2(B), or 0.0 without a baseline.  u[k] has the very bits
+ * lsspa_debug_group_values returns for masks[k].
+ * Ties: the larger value wins, on equal values the numerically smaller mask in the caller's numbering -- a total order,
+ * so the result depends neither on how the work is cut into units and launches nor on which groups the layout makes
+ * low.  Candidates: the group subsets whose own pivots all passed the relative test; one with a failed pivot is no
+ * candidate and raises LSSPA_INFO_NOT_PD in info, and a NaN value never wins.  found[k] = 0: no subset of k groups was
+ * a candidate; u[k] is then NaN and masks[k] 0.
+ * Labels, limits, refusals and their messages are lsspa_groups_shapley's; NULL u, masks or found is LSSPA_ERR_ARG, info
+ * may be NULL.  fp64, bounded launches as that call cuts them, no atomics on the table: two calls agree bitwise.  It
+ * shares lsspa_groups_shapley's buffers (a call of that before and after this one agrees bitwise) and leaves its timing
+ * where lsspa_groups_timing reads it; nothing of the sampling path or of lsspa_subsets_shapley's state changes.
+ *   lsspa_debug_groups_best_plan : host only (no context, no GPU) -- plan[0 .. 7] = gl, gh, ql (low groups, high groups,
+ *                                  low columns of the labels' layout), nb (baseline columns), units, per (high subsets a
+ *                                  unit; units x per = 2^gh), launches and the size classes a unit holds
+ *                                  (log2(per) + 1).  Labels that lsspa_groups_best would refuse: LSSPA_ERR_ARG. */
+int lsspa_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* u /* [g+1] */,
+                      uint32_t* masks /* [g+1] */, uint8_t* found /* [g+1] */, int32_t* info);
+int lsspa_debug_groups_best_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* plan /* [8] */);
+
 /* Exact Owen values: the attribution of every COLUMN with the groups as coalition structure, the two-level Shapley
  * value.  Labels, B, u and v as lsspa_groups_shapley's.  For a column i of group k, with B_k the group's columns,
  * b = |B_k| and cols(R) the columns of the groups in R,

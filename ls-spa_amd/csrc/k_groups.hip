@@ -52,6 +52,26 @@
 // under the two masks of the inner players that the host leaves in GROUPS_TAB_OWEN_LO / _HI of the layout table, r the
 // rest of |K|; wo, wi(t - 1), wi(t) are rows 2 .. 4 of GroupArgs::w.  GroupArgs itself is as it was: a field more cost
 // an instantiation its registers once already (REPS below).
+//
+// Best group subset of every size (lsspa_groups_best, groups_best_kernel below): a kernel of its own beside the
+// enumeration kernel -- an arg-max cannot be had from its sums -- with the same workgroup, units, steps, load_shared and
+// group_values<false>; one problem, no replicates, no Owen weights.  What it keeps of u(Hs + T) is, per size k = |Hs| +
+// |T| (groups, not columns; size 0 is the baseline alone), the largest value and its subset.  Order: the larger value
+// wins, on equal values the numerically smaller mask in the CALLER's numbering (bit k = label k); a subset whose own
+// pivots failed -- the workgroup's high ones or the lane's low ones -- is no candidate and NaN never wins (v > best from
+// -inf).  The order is total, so the result does not depend on how the work is cut.
+//   Running bests: hi = blockIdx.x per + s with per a power of two, so inside a unit the size class of a step is
+// popc(s), at most GROUPS_BEST_CLASSES = 19 classes (per <= 2^18: gh <= 31 over 8192 units).  Lane T of wave 0 keeps
+// (value, hi) per class in LDS, [class][lane], its own slots only: popc(s) indexes them, no scratch and no unrolled
+// chain of 19 branches, and 14.6 KB on top of GrpShared leave the two workgroups a CU that the enumeration kernel's
+// registers allow.  groups_layout numbers the high groups in ascending label order, so for a fixed lane ascending hi is
+// ascending caller mask: the strict compare keeps the smaller mask of equal values.
+//   Merge: at the end of a launch, for every size the unit can hold, the lane translates (hi, T) to the caller's mask
+// through GroupLayout::gid (32 bytes by value in the kernel's arguments) -- across lanes the layout's order is not the
+// caller's: a low group has a small layout number whatever its label --, wave 0 reduces (value, mask) by a fixed
+// butterfly under the total order, and lane 0 merges the winner into the unit's row of the table, values [units][g + 1]
+// and (caller mask, found) [units][g + 1][2], with plain loads and stores (one workgroup owns a row, launches are ordered
+// by the stream).  launch_subsets_best_reduce then takes the best over the units.  No atomics on the table.
 #include "kernels.h"
 
 #include <algorithm>
@@ -502,6 +522,104 @@ __global__ __launch_bounds__(NT) void groups_enum_kernel(GroupArgs a, uint64_t s
   if (__any(bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<RO>(1), 1);
 }
 
+// ---- best group subset of every size (lsspa_groups_best; the header) ----
+constexpr int GBS = GROUPS_BEST_CLASSES;       // size classes of a unit: popc(s), s < per <= 2^(GBS - 1)
+
+struct GroupIds {
+  uint8_t id[GG];                              // GroupLayout::gid: the caller's label of the layout's group r
+};
+
+struct GrpBestShared {
+  double v[GBS * 64];      // [class][lane of wave 0]: the lane's largest u of the class so far (-inf: none)
+  uint32_t h[GBS * 64];    // and the hi that gave it
+  int gid[GG];
+};
+
+// k_subsets.hip's total order (best_merge, wave_best there): the larger value, on equal values the smaller mask; "no
+// candidate" is v = -inf, which loses against every candidate
+__device__ inline void best_merge(double& v, uint32_t& mask, double bv, uint32_t bmask) {
+  const bool take = bv > v || (bv == v && bmask < mask);
+  v = take ? bv : v;
+  mask = take ? bmask : mask;
+}
+
+__device__ inline void wave_best(double& v, uint32_t& mask) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const uint32_t om = (uint32_t)__shfl_xor((int)mask, o, 64);
+    best_merge(v, mask, ov, om);
+  }
+}
+
+// a.part [units][g + 1] (values), bm [units][g + 1][2] (caller mask, found): unit u's best subset of every size so far;
+// a launch merges its own into them (found = 0: no candidate yet).  One workgroup owns a row, launches are ordered by
+// the stream: plain loads and stores.
+__global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s0, uint64_t s1, GroupIds ids,
+                                                         uint32_t* __restrict__ bm) {
+  __shared__ GrpShared sh;
+  __shared__ GrpBestShared sb;
+  const int tid = threadIdx.x;
+  const int ng = a.ng, gl = a.gl, gh = a.gh;
+  const bool live = tid < (1 << gl);           // wave 0 only (gl <= 6)
+  if (tid < GG) sb.gid[tid] = ids.id[tid];
+  if (live) {
+    for (int j = 0; j < GBS; ++j) {            // the lane's own slots: nobody else reads or writes them
+      sb.v[j * 64 + tid] = -__builtin_huge_val();
+      sb.h[j * 64 + tid] = 0u;
+    }
+  }
+  load_shared<false>(sh, a, tid);              // (ends with a barrier: gid)
+  bool any_bad = false;
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    bool bad = false;                          // this subset's own pivots: the high ones the workgroup's, the low ones the lane's
+    const double v = group_values<false>(sh, a, hi, tid, bad);
+    any_bad |= bad;
+    // a lane sees the subsets of a class in ascending hi, which is ascending caller mask (groups_layout numbers the
+    // high groups in ascending label order): the strict compare keeps the smaller one, and NaN never wins
+    if (live && !bad) {
+      const int e = __popcll(s) * 64 + tid;    // popc(s) < GBS: launch_groups_best
+      if (v > sb.v[e]) {
+        sb.v[e] = v;
+        sb.h[e] = (uint32_t)hi;                // gh <= 31
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < 64) {
+    double* rv = a.part + (int64_t)blockIdx.x * (ng + 1);
+    uint32_t* rm = bm + (int64_t)blockIdx.x * (ng + 1) * 2;
+    // the sizes this unit can hold: popc(unit) + popc(s) + popc(T), s < per (a power of two), T < 2^gl
+    const int ncls = __popcll(a.per - 1) + 1;
+    const int k0 = __popc(blockIdx.x), k1 = min(ng, k0 + ncls - 1 + gl);
+    const int base = k0 + __popc(tid);         // |S| of this lane's class 0
+    uint32_t low = 0u;                         // the lane's low groups in the caller's numbering
+    for (int r = 0; r < gl; ++r)
+      if ((tid >> r) & 1) low |= 1u << sb.gid[r];
+    for (int k = k0; k <= k1; ++k) {
+      const int j = k - base;
+      double v = -__builtin_huge_val();
+      uint32_t mask = 0u;
+      if (live && j >= 0 && j < ncls) {
+        v = sb.v[j * 64 + tid];
+        const uint32_t h = sb.h[j * 64 + tid];
+        mask = low;
+        for (int r = 0; r < gh; ++r)
+          if ((h >> r) & 1u) mask |= 1u << sb.gid[gl + r];
+      }
+      wave_best(v, mask);                      // over caller masks: across lanes the layout's order is not the caller's
+      if (tid == 0 && v > -__builtin_huge_val()) {
+        if (rm[2 * k + 1] != 0u) best_merge(v, mask, rv[k], rm[2 * k]);
+        rv[k] = v;
+        rm[2 * k] = mask;
+        rm[2 * k + 1] = 1u;
+      }
+    }
+  }
+  if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info, 1);
+}
+
 // masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
 __global__ __launch_bounds__(NT) void groups_debug_kernel(GroupArgs a, const uint64_t* __restrict__ masks, int64_t n,
                                                           double* __restrict__ vals) {
@@ -617,6 +735,25 @@ hipError_t launch_groups_owen(const GroupArgs& a, uint64_t units, uint64_t s0, u
   if (a.gh > GHI) return hipErrorInvalidValue;
   if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
   hipLaunchKernelGGL((groups_enum_kernel<false, false, true>), dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1);
+  return hipGetLastError();
+}
+
+hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1, uint32_t* bm,
+                              hipStream_t st) {
+  if (!args_ok(a) || !a.part || !bm || !gid || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  if (a.inv_yy_rep) return hipErrorInvalidValue;     // no replicates: one problem
+  if (a.gh > GHI) return hipErrorInvalidValue;       // hi is kept in 32 bits (no layout of <= 64 columns has gh = 32)
+  if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  // the size classes of a unit are popc(s), s < per: per a power of two (it is: units per = 2^gh) of at most GBS - 1 bits
+  if (a.per > (1ull << (GBS - 1))) return hipErrorInvalidValue;
+  GroupIds ids{};
+  uint32_t seen = 0u;
+  for (int r = 0; r < a.ng; ++r) {                   // a permutation of 0 .. ng-1: the kernel shifts by them
+    if (gid[r] < 0 || gid[r] >= a.ng || ((seen >> gid[r]) & 1u)) return hipErrorInvalidValue;
+    seen |= 1u << gid[r];
+    ids.id[r] = (uint8_t)gid[r];
+  }
+  hipLaunchKernelGGL(groups_best_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1, ids, bm);
   return hipGetLastError();
 }
 

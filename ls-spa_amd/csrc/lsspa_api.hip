@@ -3568,6 +3568,45 @@ int groups_enumerate(lsspa_ctx* ctx, bool inter, const int32_t* labels, int32_t 
   return exact_enumerate(ctx, ctx->grp, inter ? subsets_inter_cols(ng) : ng + 1, n_high, steps, launch, out, info);
 }
 
+// lsspa_groups_best: the same units, launches and timing; the table holds each unit's best group subset per size, values
+// in ctx->grp.part and (caller mask, found) in ctx->grp.best, whose last g + 1 pairs receive the result.
+static_assert(((1ull << (GROUPS_MAX_G - 1)) / EXACT_UNITS) <= (1ull << (GROUPS_BEST_CLASSES - 1)),
+              "groups_best_kernel holds the size classes of the largest per: at most 31 high groups over EXACT_UNITS units");
+int groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* u, uint32_t* masks, uint8_t* found,
+                int32_t* info) {
+  GroupArgs a;
+  GroupLayout L;
+  TRY(groups_args(ctx, labels, g, a, L));
+  const int ng = L.ng;
+  const uint64_t n_high = 1ull << L.gh;
+  const uint64_t units = exact_units(n_high);
+  a.per = n_high / units;
+  const uint64_t steps = groups_steps(L, units);
+  ExactWork& W = ctx->grp;
+  const size_t rows = (size_t)units * (ng + 1);
+  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)ng + 1)));
+  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, ctx->stream));
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_groups_best(a, L.gid, units, s0, s1, W.best.ptr, ctx->stream);
+  };
+  uint32_t mf[2 * (GROUPS_MAX_G + 1)];
+  auto finish = [&](int64_t n_units) {
+    uint32_t* out_m = W.best.ptr + 2 * rows;
+    HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, n_units, ng, W.out.ptr, out_m, ctx->stream));
+    HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
+    return (int)LSSPA_OK;
+  };
+  TRY(exact_enumerate_with(ctx, W, ng + 1, n_high, steps, launch, finish, info));
+  for (int k = 0; k <= ng; ++k) {
+    found[k] = mf[2 * k + 1] ? 1 : 0;
+    masks[k] = found[k] ? mf[2 * k] : 0u;
+    if (!found[k]) u[k] = std::nan("");
+  }
+  return LSSPA_OK;
+}
+
 // ---- Owen value: the columns of a group, with the groups as coalition structure (k_groups.hip's header) ----
 // The refined game of target group k (b columns) has g - 1 + b players: the other groups whole (the outer players) and
 // the target's columns as singletons (the inner players), numbered in the caller's order with the target's columns in
@@ -3793,6 +3832,31 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
                             "a group subset's Gram matrix is not positive definite");
 } catch (...) {
   return abi_caught(ctx);
+}
+
+int lsspa_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* u, uint32_t* masks, uint8_t* found,
+                      int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!labels || !u || !masks || !found) return ctx->fail(LSSPA_ERR_ARG, "labels / u / masks / found is NULL");
+  return groups_best(ctx, labels, g, u, masks, found, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_groups_best_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* plan) try {
+  GroupLayout L;
+  if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || groups_layout(labels, p, g, L)) return LSSPA_ERR_ARG;
+  const uint64_t n_high = 1ull << L.gh;
+  const uint64_t units = exact_units(n_high), per = n_high / units;
+  const uint64_t steps = groups_steps(L, units);
+  plan[0] = L.gl; plan[1] = L.gh; plan[2] = L.ql; plan[3] = L.nb;
+  plan[4] = (int64_t)units;
+  plan[5] = (int64_t)per;
+  plan[6] = (int64_t)((per + steps - 1) / steps);
+  plan[7] = __builtin_popcountll(per - 1) + 1;       // size classes of a unit: popc(s), s < per
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
 }
 
 int lsspa_groups_owen(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* owen, double* phi, int32_t* info) try {

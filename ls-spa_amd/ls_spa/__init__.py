@@ -15,10 +15,11 @@ matrix, p <= 104, or with ``groups=`` over groups of those columns, returning ``
 g <= 32 groups of p <= 64 columns) and ``ls_spa_owen`` (exact Owen values: the attribution of every column with
 ``groups=`` as coalition structure, returning ``OwenResults``) and ``ls_spa_best_subsets`` (exhaustive best-subset
 selection: the best model of every size by out-of-sample R^2 over all 2^p subsets, p <= 32, returning
-``BestSubsetsResults``) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
+``BestSubsetsResults``, or with ``groups=`` over all 2^g sets of g <= 32 groups of p <= 64 columns, returning
+``BestGroupSubsetsResults``) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
-from ._results import (BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (BestGroupSubsetsResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
@@ -37,5 +38,5 @@ __all__ = [
     "ls_spa_interactions_bootstrap", "InteractionBootstrapResults", "ls_spa_multi", "MultiResponseResults",
     "MultiGroupResults", "ls_spa_multi_sampled", "SampledMultiResults", "SampledMultiGroupResults",
     "ls_spa_permutation_test", "PermutationTestResults", "ls_spa_owen", "OwenResults",
-    "ls_spa_best_subsets", "BestSubsetsResults",
+    "ls_spa_best_subsets", "BestSubsetsResults", "BestGroupSubsetsResults",
 ]

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (BestGroupSubsetsResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
@@ -1206,9 +1206,45 @@ def _subset_fit(G, g, cols):
     return theta
 
 
-def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=None, device=0, _engine=None):
+def _best_group_subsets(data, reg, labels, g, device, _engine):
+    """ls_spa_best_subsets(groups=): the best set of groups of every size 0 .. g on the engine (groups_best), each
+    winner refitted on the host on the baseline's and its groups' columns."""
+    p = data[0].shape[1]
+    with _engine_call(_engine, device) as engine:
+        # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like the values
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        _, full_r_squared, info = _load_and_fit(engine, data, reg, False, None)
+        u, masks, found, bits = engine.groups_best(labels)
+        if info & 1:
+            _, full_r_squared = _singular_fit(engine, data[1], data[3])
+        G, gv, _, _ = engine.gram()
+    _info_verdict((bits | info) & 1, stacklevel=3)      # (an enumeration reports a broken pivot, nothing else)
+    sizes = np.arange(g + 1)
+    group_subsets = np.zeros((g + 1, g), dtype=bool)
+    subsets = np.zeros((g + 1, p), dtype=bool)
+    r_squared = np.full(g + 1, np.nan)
+    theta = np.full((g + 1, p), np.nan)
+    for k in sizes:
+        if found[k]:
+            group_subsets[k] = (int(masks[k]) >> np.arange(g)) & 1
+            subsets[k] = (labels < 0) | group_subsets[k][np.maximum(labels, 0)]
+            r_squared[k] = u[k]
+            theta[k] = _subset_fit(G, gv, np.nonzero(subsets[k])[0])
+    best_size, best_groups, best_subset = -1, np.zeros(g, dtype=bool), np.zeros(p, dtype=bool)
+    if not np.all(np.isnan(r_squared)):
+        best_size = int(np.nanargmax(r_squared))      # the first of equal maxima: the smallest size
+        best_groups, best_subset = group_subsets[best_size].copy(), subsets[best_size].copy()
+    return BestGroupSubsetsResults(sizes=sizes, group_subsets=group_subsets, subsets=subsets,
+                                   n_columns=subsets.sum(axis=1), r_squared=r_squared, theta=theta,
+                                   best_size=best_size, best_group_subset=best_groups, best_subset=best_subset,
+                                   full_r_squared=float(full_r_squared), baseline_r_squared=float(r_squared[0]))
+
+
+def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=None, groups=None, device=0,
+                        _engine=None):
     """Exhaustive best-subset selection by out-of-sample R^2: the best model of every size over all 2^p feature subsets
-    (p <= 32).
+    (p <= 32) or, with ``groups=``, over all 2^g subsets of groups of columns (g <= 32 groups over p <= 64 columns).
 
     ``ls_spa`` says who earns the R^2; this call says which model to keep.  v(S), the out-of-sample R^2 of the model
     fitted on the features in S, is not monotone in S -- the best model is usually not the full one, and no
@@ -1218,6 +1254,18 @@ def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=Non
 
     include:  an iterable of column indices that every model must contain (an intercept, controls); the sizes then
         start at len(include).
+
+    groups:  a length-p sequence of integer labels, one per column, as for ``ls_spa(method='subsets', groups=)``: k in
+        0 .. g-1 puts the column into group k, -1 into the always-included baseline.  A one-hot factor or a spline
+        basis then goes in or out whole: the models are the 2^g sets of groups (each with the baseline's columns), a
+        model's size is its number of groups, 0 .. g, and the cost is set by g, not by p (include/lsspa.h,
+        lsspa_groups_best).  On equal values the set with the smaller mask (bit k = group k) wins.  The p <= 32 limit
+        does not apply; the limits and label errors are that call's, g <= 32 and p <= 64.  ``include=`` cannot be
+        combined with it: label those columns -1, the baseline is the include set.  Returns
+        ``BestGroupSubsetsResults``: ``sizes`` 0 .. g, ``group_subsets`` [n][g] bool, ``subsets`` [n][p] bool (the
+        baseline's and the winners' columns), ``n_columns`` [n], ``r_squared``, ``theta``, ``best_size``,
+        ``best_group_subset``, ``best_subset``, ``full_r_squared`` (``ls_spa(method='subsets', groups=).r_squared``)
+        and ``baseline_r_squared``, which is ``r_squared[0]``.
 
     Returns ``BestSubsetsResults``: ``sizes``, ``subsets`` [n][p] bool, ``r_squared`` [n], ``theta`` [n][p] (each
     winner refitted on the host in fp64, exactly 0.0 outside its subset), ``best_size``, ``best_subset`` and
@@ -1229,6 +1277,19 @@ def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=Non
     row.  ``reg`` and ``device`` are that call's."""
     data = _coerce_data(X_train, X_test, y_train, y_test)
     p = data[0].shape[1]
+    if groups is not None:
+        if include is not None:
+            raise ValueError("include= cannot be combined with groups=: label the columns every model must contain "
+                             "-1, the baseline is the include set")
+        if p > GROUPS_MAX_P:
+            raise ValueError(f"grouped attribution takes at most p = {GROUPS_MAX_P} columns, the baseline's included "
+                             f"(this problem has p = {p})")
+        labels, n_groups = group_labels(groups, p)
+        if data[1].shape[0] < 1:
+            raise ValueError(f"ls_spa_best_subsets needs M >= 1 test rows (M = {data[1].shape[0]})")
+        if not np.any(data[3]):
+            raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+        return _best_group_subsets(data, reg, labels, n_groups, device, _engine)
     if p > SUBSETS_MAX_P:
         raise ValueError(f"ls_spa_best_subsets enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} "
                          f"features (this problem has p = {p})")

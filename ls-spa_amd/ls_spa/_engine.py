@@ -147,6 +147,21 @@ def debug_owen_plan(labels):
     return [dict(zip(OWEN_PLAN_FIELDS, (int(v) for v in row))) for row in out[:g]]
 
 
+GROUPS_BEST_PLAN_FIELDS = ("gl", "gh", "ql", "nb", "units", "per", "launches", "classes")
+
+
+def debug_groups_best_plan(labels):
+    """Test hook, host only: how groups_best enumerates the group game of these labels (include/lsspa.h,
+    lsspa_debug_groups_best_plan) -- a dict with GROUPS_BEST_PLAN_FIELDS.  ValueError for labels the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(8, dtype=np.int64)
+    rc = N.load().lsspa_debug_groups_best_plan(N.iptr(labels), len(labels), g, out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_groups_best_plan: status {rc}")
+    return dict(zip(GROUPS_BEST_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -834,9 +849,25 @@ class HipEngine:
         self._check(self._lib.lsspa_groups_owen(self._h, N.iptr(labels), g, N.dptr(owen), N.dptr(phi), C.byref(info)))
         return owen, phi, info.value
 
+    def groups_best(self, labels):
+        """(u, masks, found, info): the best group subset of every size k = 0 .. g (the number of groups beside the
+        baseline) by the out-of-sample R^2 u, over all 2^g subsets of the groups that labels names (include/lsspa.h,
+        lsspa_groups_best): u [g + 1] float64, masks [g + 1] uint32 (bit k = group k), found [g + 1] bool (False: no
+        candidate of that size, u is NaN).  groups_timing() then speaks of this call."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        n = max(g, 0) + 1
+        u, masks, found = np.empty(n), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)
+        info = C.c_int32()
+        self._check(self._lib.lsspa_groups_best(
+            self._h, N.iptr(labels), g, N.dptr(u), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            found.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)))
+        return u, masks, found.astype(bool), info.value
+
     def groups_timing(self):
-        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley, groups_interactions or
-        groups_owen call."""
+        """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley, groups_interactions,
+        groups_owen or groups_best call."""
         return self._exact_timing(self._lib.lsspa_groups_timing)
 
     def debug_group_values(self, labels, masks):

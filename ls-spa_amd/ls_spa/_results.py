@@ -223,6 +223,50 @@ class BestSubsetsResults:
 
 
 @dataclass
+class BestGroupSubsetsResults:
+    """What ``ls_spa_best_subsets(groups=)`` returns for g groups over p columns: n = g + 1 sizes.  ``sizes`` [n]: 0 ..
+    g, the number of groups in the model beside the baseline; ``group_subsets`` [n][g] bool: the best set of groups of
+    each size (row i has ``sizes[i]`` True entries); ``subsets`` [n][p] bool: its columns, the baseline's (label -1)
+    and the winning groups'; ``n_columns`` [n]: how many those are; ``r_squared`` [n]: its out-of-sample R^2;
+    ``theta`` [n][p]: its coefficients, exactly 0.0 outside its columns.  A size without a candidate (every subset of
+    that size had a Gram matrix that is not numerically positive definite) is a row of NaN in ``r_squared`` and
+    ``theta``, of False in ``group_subsets`` and ``subsets`` and 0 in ``n_columns``.  ``best_size``: the size with the
+    largest ``r_squared``, the smallest such size on ties, NaN sizes skipped (-1 if every size is NaN);
+    ``best_group_subset`` [g] bool and ``best_subset`` [p] bool: its groups and its columns; ``full_r_squared``: the
+    R^2 of all p columns, what ``ls_spa(method='subsets', groups=).r_squared`` returns; ``baseline_r_squared``: the R^2
+    of the baseline alone, ``r_squared[0]`` (0.0 without a baseline)."""
+    sizes: np.ndarray
+    group_subsets: np.ndarray
+    subsets: np.ndarray
+    n_columns: np.ndarray
+    r_squared: np.ndarray
+    theta: np.ndarray
+    best_size: int
+    best_group_subset: np.ndarray
+    best_subset: np.ndarray
+    full_r_squared: float
+    baseline_r_squared: float
+
+    def __repr__(self):
+        pad = " " * 8
+        n, g = np.asarray(self.group_subsets).shape
+        p = np.asarray(self.subsets).shape[1]
+        chosen = ", ".join(str(k) for k in np.nonzero(self.best_group_subset)[0][:12])
+        best = f"{float(self.r_squared[self.best_size]):.2e}" if self.best_size >= 0 else "nan"
+        lines = [
+            "",
+            f"{pad}p = {p} columns in g = {g} groups, best group subsets of sizes 0 .. {n - 1}",
+            f"{pad}Out-of-sample R^2 with all columns: {self.full_r_squared:.2e}, with the baseline alone: "
+            f"{self.baseline_r_squared:.2e}",
+            f"{pad}Best model: {self.best_size} groups ({int(np.sum(self.best_subset))} columns), out-of-sample R^2 "
+            f"{best}",
+            f"{pad}Its groups: ({chosen}{', ...' if int(np.sum(self.best_group_subset)) > 12 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class PermutationTestResults:
     """What ``ls_spa_permutation_test`` returns; d = p, or the g groups of ``groups=``.  ``attribution`` [d], ``theta``
     [p], ``r_squared`` (and ``baseline_r_squared`` with groups, else None): the observed values.  ``null_attribution``
