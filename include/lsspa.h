@@ -337,6 +337,28 @@ int lsspa_debug_boot_inter_plan(int64_t R, int64_t N, int64_t M, int32_t p, int6
 int lsspa_debug_boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p,
                                        int32_t g, int64_t block, int64_t* plan15);
 
+/* Bootstrap of the best-subset selection (p <= 32): how stable is the chosen model?  The replicates of lsspa_boot_run --
+ * the same loaded rows, draws, weights, weighted Grams, finalise, r2, info, `first`, `block` and refusals (a seed
+ * resamples the same rows) -- each searched by lsspa_subsets_best's enumeration, all replicates of a launch in one grid.
+ *   lsspa_boot_best_run : after lsspa_boot_load (a load with p > 32 is LSSPA_ERR_ARG naming the limit).  include:
+ *                     lsspa_subsets_best's mask, refused like there.  Of replicate r, v [r][k] is the largest
+ *                     out-of-sample R^2 among its subsets of size k = 0 .. p, masks [r][k] that subset (bit j = feature
+ *                     j) and found [r][k] whether the size had a candidate (else v is NaN and the mask 0): the bits
+ *                     lsspa_subsets_best returns for the replicate's reduced problem, whatever R, block and first are --
+ *                     the larger value wins, then the smaller mask, a total order that no cut of the work can show in.
+ *                     A replicate whose pivot fails has LSSPA_INFO_NOT_PD in its own word only; the subsets whose own
+ *                     pivots failed are no candidates, every other subset of that replicate still is.
+ *   lsspa_boot_timing reports the run like the others.
+ *   lsspa_debug_boot_best_plan : host only -- the fifteen numbers of lsspa_debug_boot_plan for this run.  An entry of the
+ *                     enumeration's table takes 16 bytes (value, mask, found) against the 8 of lsspa_boot_run's, counted
+ *                     in the bytes per replicate: block * bytes <= 256 MB (or block = 1); units * replicates per launch
+ *                     * steps <= 2^20; high subsets per unit <= 2^13. */
+int lsspa_boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first,
+                        const double* w_train /* [R][N] or NULL */, const double* w_test /* [R][M] or NULL */,
+                        int64_t block, uint32_t include, double* v /* [R][p + 1] */, uint32_t* masks /* [R][p + 1] */,
+                        uint8_t* found /* [R][p + 1] */, double* r2 /* [R] */, int32_t* info /* [R] */);
+int lsspa_debug_boot_best_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15);
+
 /* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
  * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the
  * 2^p subsets are enumerated once for every 8 responses: a wave sweeps a high subset's pivots out of [G | g_r ...] with

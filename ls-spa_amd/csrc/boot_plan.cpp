@@ -30,9 +30,10 @@ void plan_gram(int64_t N, int64_t M, int c, BootPlan& P) {
 // per replicate: weights of both sides (8 bytes a row: fp64 weights; counts take half), the Gram partials of both
 // sides, the enumeration's partial table [units][players + 1], and the small per-replicate matrices (S, G, H, ...
 // < 8 c^2 doubles); then the replicates of a block and the blocks
-void plan_blocks(int64_t R, int64_t N, int64_t M, int c, int players, int64_t block, BootPlan& P) {
+// entry: the bytes of one entry of that table (8: a sum; 16: the best run's value, mask and found flag)
+void plan_blocks(int64_t R, int64_t N, int64_t M, int c, int players, int64_t block, BootPlan& P, int entry = 8) {
   P.rep_bytes = 8 * (N + M) + (int64_t)(P.slices[0] + P.slices[1]) * P.pairs * 256 * 8 +
-                (int64_t)P.units * (players + 1) * 8 + 8ll * c * c * 8;
+                (int64_t)P.units * (players + 1) * entry + 8ll * c * c * 8;
   int64_t most = std::max<int64_t>(1, std::min<int64_t>(BOOT_MAX_BLOCK, BOOT_BLOCK_BYTES / P.rep_bytes));
   P.block = std::min<int64_t>(R, block > 0 ? std::min(block, most) : most);
   P.n_blocks = (R + P.block - 1) / P.block;
@@ -79,6 +80,27 @@ const char* boot_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, Boo
   P.enum_reps = std::max<int64_t>(1, std::min<int64_t>(P.block, (int64_t)(BOOT_SUBSETS_PER_LAUNCH / P.units)));
   P.steps = std::max<uint64_t>(1, BOOT_SUBSETS_PER_LAUNCH / (P.units * (uint64_t)P.enum_reps));
   P.steps = std::min<uint64_t>(P.steps, P.per);
+  return nullptr;
+}
+
+const char* boot_best_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P) {
+  P = BootPlan{};
+  if (p < 1 || p > BOOT_MAX_P) return "p must be 1 .. 32";
+  if (const char* why = plan_sizes(R, N, M, block)) return why;
+  const int c = p + 1;
+  plan_gram(N, M, c, P);
+  const int q = p < BOOT_LOW ? p : BOOT_LOW;
+  const uint64_t n_high = 1ull << (p - q);
+  P.units = std::min<uint64_t>(n_high, BOOT_UNITS);
+  P.per = n_high / P.units;
+  if (P.per > BOOT_BEST_MAX_PER) return "more high subsets per unit than the best kernel's size classes hold";
+  plan_blocks(R, N, M, c, p, block, P, 16);
+  // The winner of a total order does not depend on the cut, so the cut is chosen for speed: a unit's steps first, as the
+  // one-problem call cuts them (a workgroup loads its replicate's H and merges into its row once per launch), then as
+  // many replicates as the launch has left
+  P.steps = std::min<uint64_t>(P.per, std::max<uint64_t>(1, BOOT_SUBSETS_PER_LAUNCH / P.units));
+  P.enum_reps = std::max<int64_t>(
+      1, std::min<int64_t>(P.block, (int64_t)(BOOT_SUBSETS_PER_LAUNCH / (P.units * P.steps))));
   return nullptr;
 }
 

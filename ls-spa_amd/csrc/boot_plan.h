@@ -26,6 +26,14 @@ constexpr uint64_t BOOT_UNITS = 8192, BOOT_SUBSETS_PER_LAUNCH = 1ull << 20;   //
 // BOOT_BLOCK_BYTES holds (at most BOOT_MAX_BLOCK); a larger request is cut to that.
 const char* boot_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P);
 constexpr int BOOT_MAX_P = 32, BOOT_LOW = 6;   // SUBSETS_MAX_P and the enumeration's low features (k_subsets.hip)
+// The bootstrap of the best-subset selection (lsspa_boot_best_run): boot_plan's cut with the enumeration's table holding,
+// per (unit, size), a value, a mask and a found flag -- 16 bytes an entry against the 8 of a sum, counted in rep_bytes
+// like boot_plan's: block rep_bytes <= BOOT_BLOCK_BYTES, or block = 1.  units enum_reps steps <= 2^20, and per <=
+// BOOT_BEST_MAX_PER, the size classes subsets_best_kernel holds (it is for p <= 32 over BOOT_UNITS units).  The winner
+// of a total order depends on no cut, which is therefore chosen for speed: steps as the one-problem call cuts a unit
+// (min(per, 2^20 / units)), then enum_reps = what such a launch has left, at most the block, at least 1.
+constexpr uint64_t BOOT_BEST_MAX_PER = 1ull << 13;
+const char* boot_best_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P);
 // The bootstrap over groups of columns (lsspa_boot_groups_run): g groups over p <= 64 columns, of which gh are high, nb
 // columns the baseline and ql the low groups' (GroupLayout, kernels.h).  c = p + 1 <= 65 columns of Z: cb up to 5; the
 // slices are boot_plan's for the same rows; units, per, steps cut the 2^gh high subsets as the one-problem grouped

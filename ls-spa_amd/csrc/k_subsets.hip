@@ -42,6 +42,8 @@
 //
 // Best subset of every size (lsspa_subsets_best, subsets_best_kernel below): the same enumeration keeps, instead of sums,
 // the largest v(K) and its mask per size |K| -- a kernel of its own beside the enumeration kernel, which it leaves alone.
+// Its REPS instantiation runs the replicates of a bootstrap of the selection (lsspa_boot_best_run) as the second grid
+// dimension, like the enumeration kernel's.
 #include "kernels.h"
 
 namespace lsspa {
@@ -454,11 +456,29 @@ __device__ inline void wave_best(double& v, uint32_t& mask) {
 
 // a.part [units][p + 1] (values), bm [units][p + 1][2] (mask, found): unit u's best subset of every size so far; a launch
 // merges its own into them (found = 0: no candidate yet, the value and mask beside it mean nothing).  One workgroup owns a row, launches are ordered by the stream: plain loads and stores.
+// REPS (the bootstrap of the selection, lsspa_boot_best_run): replicate blockIdx.y reads its own problem, 1 / ||y||^2 and
+// info word (rep_offset) and merges into its own rows of the tables [reps][units][p + 1] and [reps][units][p + 1][2].
+// The order is total, so a replicate's result depends neither on the cut of `per` into launches nor on the replicates
+// that share its launch.  The offsets are applied once, to the kernel's own copy of the arguments, and the helpers run
+// as for one problem: load_shared<true> and subset_values<true> form them again at every step, which in this kernel
+// (14 classes of running bests beside the sweep) costs 36 bytes of scratch a lane.  The addresses, and so the
+// arithmetic, are the same.  Without REPS the code is what it was.
+template <bool REPS = false>
 __global__ __launch_bounds__(64) void subsets_best_kernel(SubsetArgs a, uint64_t s0, uint64_t s1, uint32_t include,
                                                           uint32_t* __restrict__ bm) {
   __shared__ SubShared sh;
   const int lane = threadIdx.x;
   const int p = a.p, q = a.q;
+  if constexpr (REPS) {
+    a.G += rep_offset<REPS>(p * a.ldg);
+    a.H += rep_offset<REPS>(p * a.ldh);
+    a.g += rep_offset<REPS>(p);
+    a.h += rep_offset<REPS>(p);
+    a.inv_yy += rep_offset<REPS>(1);
+    a.info += rep_offset<REPS>(1);
+    a.part += rep_offset<REPS>((int64_t)gridDim.x * (p + 1));
+    bm += rep_offset<REPS>((int64_t)gridDim.x * (p + 1) * 2);
+  }
   load_shared<false>(sh, a, lane);
   double bv[SBS];
   uint32_t bh[SBS];
@@ -512,12 +532,17 @@ __global__ __launch_bounds__(64) void subsets_best_kernel(SubsetArgs a, uint64_t
 }
 
 // out_v [p + 1], out_m [p + 1][2]: the best over the units, one workgroup per size, the units dealt over the lanes in a
-// fixed order (any order gives the same winner)
+// fixed order (any order gives the same winner).  Replicate blockIdx.y: its rows of the tables, and a result `ostride`
+// doubles (out_v) or pairs (out_m) behind the first replicate's.
 __global__ __launch_bounds__(64) void subsets_best_reduce_kernel(const double* __restrict__ bv,
                                                                  const uint32_t* __restrict__ bm, int64_t units, int p1,
                                                                  double* __restrict__ out_v,
-                                                                 uint32_t* __restrict__ out_m) {
+                                                                 uint32_t* __restrict__ out_m, int64_t ostride) {
   const int k = blockIdx.x, lane = threadIdx.x;
+  bv += rep_offset<true>(units * p1);
+  bm += rep_offset<true>(units * p1 * 2);
+  out_v += rep_offset<true>(ostride);
+  out_m += rep_offset<true>(ostride * 2);
   double v = -__builtin_huge_val();
   uint32_t mask = 0u;
   for (int64_t u = lane; u < units; u += 64) {
@@ -601,21 +626,30 @@ hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, do
 }
 
 hipError_t launch_subsets_best(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, uint32_t include,
-                               uint32_t* bm, hipStream_t st) {
+                               uint32_t* bm, hipStream_t st, int reps) {
   if (!args_ok(a) || !a.part || !bm || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // replicates: the caller vouches for `reps` problems, rows of both tables and info words behind the first
+  if (reps < 1 || reps > 65535) return hipErrorInvalidValue;
   const int nh = a.p - a.q;
   if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
   // the size classes of a unit are popc(s), s < per: per a power of two (it is: units per = 2^nh) of at most SBS - 1 bits
   if (a.per > (1ull << (SBS - 1))) return hipErrorInvalidValue;
   if (a.p < 32 && (include >> a.p) != 0u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(subsets_best_kernel, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1, include, bm);
+  if (reps > 1)
+    hipLaunchKernelGGL(subsets_best_kernel<true>, dim3((unsigned)units, (unsigned)reps), dim3(64), 0, st, a, s0, s1,
+                       include, bm);
+  else
+    hipLaunchKernelGGL(subsets_best_kernel<false>, dim3((unsigned)units), dim3(64), 0, st, a, s0, s1, include, bm);
   return hipGetLastError();
 }
 
 hipError_t launch_subsets_best_reduce(const double* bv, const uint32_t* bm, int64_t units, int p, double* out_v,
-                                      uint32_t* out_m, hipStream_t st) {
-  if (!bv || !bm || !out_v || !out_m || units < 1 || p < 1 || p > SP) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(subsets_best_reduce_kernel, dim3(p + 1), dim3(64), 0, st, bv, bm, units, p + 1, out_v, out_m);
+                                      uint32_t* out_m, hipStream_t st, int reps, int64_t out_stride) {
+  if (!bv || !bm || !out_v || !out_m || units < 1 || p < 1 || p > SP || reps < 1 || reps > 65535 ||
+      (reps > 1 && out_stride < p + 1))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_best_reduce_kernel, dim3(p + 1, (unsigned)reps), dim3(64), 0, st, bv, bm, units, p + 1,
+                     out_v, out_m, out_stride);
   return hipGetLastError();
 }
 

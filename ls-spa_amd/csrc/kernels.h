@@ -353,11 +353,15 @@ hipError_t launch_subsets_reduce(const double* part, int64_t units, int cols, do
 // j) and a found flag; both zeroed before the first launch, every launch merges into them.  Larger value wins, on equal
 // values the smaller mask; only subsets K with (K & include) == include whose own pivots passed are candidates.  per
 // must be at most 2^13 (it is for units = min(2^(p - q), 8192)).
+// reps > 1 (1 <= reps <= 65535; lsspa_boot_best_run): the replicates behind the launch's problem as its second grid
+// dimension -- G, g, H, h, inv_yy and info as launch_subsets_enum's, the tables [reps][units][p + 1] and
+// [reps][units][p + 1][2].  A replicate's result does not depend on the launches' cut or on the replicates beside it.
 hipError_t launch_subsets_best(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, uint32_t include,
-                               uint32_t* bm, hipStream_t st);
-// out_v[k], out_m[k][2] (mask, found): the best of size k = 0 .. p over the units' rows
+                               uint32_t* bm, hipStream_t st, int reps = 1);
+// out_v[k], out_m[k][2] (mask, found): the best of size k = 0 .. p over the units' rows; replicate r of `reps` reads its
+// rows of the tables and writes out_v + r out_stride, out_m + 2 r out_stride (out_stride >= p + 1)
 hipError_t launch_subsets_best_reduce(const double* bv, const uint32_t* bm, int64_t units, int p, double* out_v,
-                                      uint32_t* out_m, hipStream_t st);
+                                      uint32_t* out_m, hipStream_t st, int reps = 1, int64_t out_stride = 0);
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used

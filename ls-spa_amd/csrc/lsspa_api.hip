@@ -76,6 +76,7 @@ struct BootWork {
   DevBuf<double> w, epart, eout;           // Shapley weights, the enumeration's partial table and its column sums
   DevBuf<int32_t> info;                    // [block]
   DevBuf<int32_t> tab;                     // GroupLayout::tab (lsspa_boot_groups_run)
+  DevBuf<uint32_t> ebest;                  // lsspa_boot_best_run: (mask, found) beside epart's values, one launch's replicates
   double ms[3] = {0.0, 0.0, 0.0};          // kernel ms of the last run: counts, Gram (to the reduced problems), enumeration
   DevBuf<double>& Z(int s) { return s ? Z1 : Z0; }
   DevBuf<uint32_t>& cnt(int s) { return s ? cnt1 : cnt0; }
@@ -86,7 +87,7 @@ struct BootWork {
     dev_free(Z0); dev_free(Z1); dev_free(stage_x); dev_free(stage_y); dev_free(cnt0); dev_free(cnt1);
     dev_free(wt0); dev_free(wt1); dev_free(part0); dev_free(part1); dev_free(S0); dev_free(S1); dev_free(wsum);
     dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(epart);
-    dev_free(eout); dev_free(info); dev_free(tab);
+    dev_free(eout); dev_free(info); dev_free(tab); dev_free(ebest);
     loaded = false;
   }
 };
@@ -4188,23 +4189,26 @@ int boot_upload_tables(lsspa_ctx* ctx, int players, const int32_t* tab) {
 
 // The block loop of the four run functions (phi or interactions, features or groups).  Per block of P.block replicates:
 // weights, the weighted Grams and their sums, finalise, then the enumeration in launches of P.enum_reps replicates and
-// P.steps steps into a partial table `cols` wide, its column sums, and the block's results on the host.  What differs
-// stays with the entry point:
+// P.steps steps into a partial table `cols` wide, its reduction to a row of `ocols` doubles a replicate, and the block's
+// results on the host.  What differs stays with the entry point:
 //   launch(e0, ne, s0, s1): steps s0 .. s1 - 1 of replicates e0 .. e0 + ne - 1 of the block into B.epart;
-//   emit(r, out, G, g, H, h, inv_yy): replicate r of the run from its `cols` column sums and its reduced problem (host).
+//   reduce(e0, ne): the table of those replicates into rows e0 .. e0 + ne - 1 of B.eout [block][ocols] (the sums: the
+//     table's column sums, boot_column_sums below; the best run: the best over the units);
+//   emit(r, out, G, g, H, h, inv_yy): replicate r of the run from its row of B.eout and its reduced problem (host).
 // The buffers are the caller's (boot_alloc_block with this P and cols, boot_upload_tables).  Leaves the run's timing in
 // B.ms.
-template <typename Launch, typename Emit>
+template <typename Launch, typename Reduce, typename Emit>
 int boot_run_blocks(lsspa_ctx* ctx, const BootPlan& P, int64_t R, uint64_t seed, int64_t first,
-                    const double* const w_host[2], int cols, Launch&& launch, Emit&& emit, int32_t* info) {
+                    const double* const w_host[2], int cols, int ocols, Launch&& launch, Reduce&& reduce, Emit&& emit,
+                    int32_t* info) {
   BootWork& B = ctx->boot;
   hipStream_t st = ctx->stream;
   const int p = B.p;
-  const size_t c = (size_t)cols;
+  const size_t c = (size_t)cols, oc = (size_t)ocols;
   std::vector<hipEvent_t> ev(4, nullptr);
   Events guard{ev};
   for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  std::vector<double> out((size_t)P.block * c), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
+  std::vector<double> out((size_t)P.block * oc), Gh((size_t)P.block * p * p), Hh((size_t)P.block * p * p),
       gh((size_t)P.block * p), hh((size_t)P.block * p), yh((size_t)P.block);
   B.ms[0] = B.ms[1] = B.ms[2] = 0.0;
   for (int64_t b0 = 0; b0 < R; b0 += P.block) {
@@ -4219,10 +4223,10 @@ int boot_run_blocks(lsspa_ctx* ctx, const BootPlan& P, int64_t R, uint64_t seed,
       const int ne = std::min<int>((int)P.enum_reps, nb - e0);
       HIPCHK(hipMemsetAsync(B.epart.ptr, 0, sizeof(double) * (size_t)ne * P.units * c, st));
       for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps) HIPCHK(launch(e0, ne, s0, std::min(P.per, s0 + P.steps)));
-      HIPCHK(launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, cols, B.eout.ptr + (size_t)e0 * c, st, ne));
+      HIPCHK(reduce(e0, ne));
     }
     HIPCHK(hipEventRecord(ev[3], st));
-    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out.data(), B.eout.ptr, sizeof(double) * (size_t)nb * oc, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(Gh.data(), B.G.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(Hh.data(), B.H.ptr, sizeof(double) * (size_t)nb * p * p, hipMemcpyDeviceToHost, st));
@@ -4231,7 +4235,7 @@ int boot_run_blocks(lsspa_ctx* ctx, const BootPlan& P, int64_t R, uint64_t seed,
     HIPCHK(hipMemcpyAsync(yh.data(), B.inv_yy.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int r = 0; r < nb; ++r)
-      emit(b0 + r, &out[(size_t)r * c], &Gh[(size_t)r * p * p], &gh[(size_t)r * p], &Hh[(size_t)r * p * p],
+      emit(b0 + r, &out[(size_t)r * oc], &Gh[(size_t)r * p * p], &gh[(size_t)r * p], &Hh[(size_t)r * p * p],
            &hh[(size_t)r * p], yh[r]);
     for (int k = 0; k < 3; ++k) {
       float ms = 0.f;
@@ -4240,6 +4244,14 @@ int boot_run_blocks(lsspa_ctx* ctx, const BootPlan& P, int64_t R, uint64_t seed,
     }
   }
   return LSSPA_OK;
+}
+
+// the reduce step of the runs that sum: the column sums of the table of replicates e0 .. e0 + ne - 1, `cols` wide
+auto boot_column_sums(lsspa_ctx* ctx, const BootPlan& P, int cols) {
+  return [ctx, &P, cols](int e0, int ne) {
+    BootWork& B = ctx->boot;
+    return launch_subsets_reduce(B.epart.ptr, (int64_t)P.units, cols, B.eout.ptr + (size_t)e0 * cols, ctx->stream, ne);
+  };
 }
 
 // lsspa_boot_run and, with inter, lsspa_boot_interactions_run: the enumeration of k_subsets.hip over the block's
@@ -4291,7 +4303,7 @@ int boot_subsets_run(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed,
     if (inter) exact_inter_matrix(out, p, nullptr, inter + (size_t)r * p * p);
     r2[r] = boot_r2(p, G, g, H, h, inv_yy);
   };
-  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, launch, emit, info);
+  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, cols, launch, boot_column_sums(ctx, P, cols), emit, info);
 }
 
 // lsspa_boot_groups_run and, with inter, lsspa_boot_groups_interactions_run: the enumeration of k_groups.hip
@@ -4354,7 +4366,79 @@ int boot_groups_run(lsspa_ctx* ctx, const char* name, const int32_t* labels, int
     r2[r] = boot_r2_cols(p, all, p, G, gv, H, h, inv_yy, r2_ws);
     r2_base[r] = boot_r2_cols(p, base, L.nb, G, gv, H, h, inv_yy, r2_ws);
   };
-  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, launch, emit, info);
+  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, cols, launch, boot_column_sums(ctx, P, cols), emit, info);
+}
+
+// lsspa_boot_best_run: subsets_best_kernel's replicates over the block's reduced problems.  The table: values in B.epart
+// [enum_reps][units][p + 1], (mask, found) in B.ebest [enum_reps][units][p + 1][2]; a replicate's row of B.eout is
+// 2 (p + 1) doubles wide, the best values and behind them the p + 1 (mask, found) pairs as launch_subsets_best_reduce
+// writes them (8 bytes a pair).
+int boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train, const double* w_test,
+                  int64_t block, uint32_t include, double* v, uint32_t* masks, uint8_t* found, double* r2,
+                  int32_t* info) {
+  BootWork& B = ctx->boot;
+  char msg[240];
+  if (B.p > SUBSETS_MAX_P) {
+    snprintf(msg, sizeof msg, "lsspa_boot_best_run enumerates feature subsets and takes at most p = %d features (%d "
+             "loaded by lsspa_boot_groups_load)", SUBSETS_MAX_P, B.p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  const int p = B.p, p1 = p + 1;
+  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
+  BootPlan P;
+  if (const char* why = boot_best_plan(R, B.n[0], B.n[1], p, block, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_best_run: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {!w_train, !w_test};
+  TRY(boot_alloc_block(ctx, P, counts, true, p1));
+  TRY(dev_alloc(ctx, B.eout, (size_t)P.block * 2 * p1));
+  const size_t rows = (size_t)P.units * p1;                // entries of one replicate's table
+  TRY(dev_alloc(ctx, B.ebest, 2 * rows * (size_t)P.enum_reps));
+  TRY(boot_upload_tables(ctx, p, nullptr));
+  auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
+    if (s0 == 0) {      // a new set of replicates: nothing found yet
+      hipError_t e = hipMemsetAsync(B.ebest.ptr, 0, sizeof(uint32_t) * 2 * rows * (size_t)ne, ctx->stream);
+      if (e != hipSuccess) return e;
+    }
+    SubsetArgs a{};
+    a.p = p;
+    a.q = subsets_low_features(p);
+    a.G = B.G.ptr + (size_t)e0 * p * p;
+    a.H = B.H.ptr + (size_t)e0 * p * p;
+    a.g = B.g.ptr + (size_t)e0 * p;
+    a.h = B.h.ptr + (size_t)e0 * p;
+    a.ldg = a.ldh = p;
+    a.w = B.w.ptr;
+    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+    a.inv_yy = B.inv_yy.ptr + e0;
+    a.info = B.info.ptr + e0;
+    a.per = P.per;
+    a.part = B.epart.ptr;
+    return launch_subsets_best(a, P.units, s0, s1, include, B.ebest.ptr, ctx->stream, ne);
+  };
+  auto reduce = [&](int e0, int ne) {
+    double* row = B.eout.ptr + (size_t)e0 * 2 * p1;
+    return launch_subsets_best_reduce(B.epart.ptr, B.ebest.ptr, (int64_t)P.units, p, row,
+                                      reinterpret_cast<uint32_t*>(row + p1), ctx->stream, ne, 2 * p1);
+  };
+  auto emit = [&](int64_t r, const double* out, const double* G, const double* g, const double* H, const double* h,
+                  double inv_yy) {
+    uint32_t mf[2 * (SUBSETS_MAX_P + 1)];
+    std::memcpy(mf, out + p1, sizeof(uint32_t) * 2 * p1);
+    for (int k = 0; k <= p; ++k) {
+      const bool f = mf[2 * k + 1] != 0u;
+      found[r * p1 + k] = f ? 1 : 0;
+      masks[r * p1 + k] = f ? mf[2 * k] : 0u;
+      v[r * p1 + k] = f ? out[k] : std::nan("");
+    }
+    r2[r] = boot_r2(p, G, g, H, h, inv_yy);
+  };
+  return boot_run_blocks(ctx, P, R, seed, first, w_host, p1, 2 * p1, launch, reduce, emit, info);
 }
 
 }  // namespace
@@ -4507,6 +4591,28 @@ int lsspa_boot_groups_interactions_run(lsspa_ctx* ctx, const int32_t* labels, in
                          phi, inter, r2, r2_base, info);
 } catch (...) {
   return abi_caught(ctx);
+}
+
+int lsspa_boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train,
+                        const double* w_test, int64_t block, uint32_t include, double* v, uint32_t* masks,
+                        uint8_t* found, double* r2, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  if (!v || !masks || !found || !r2 || !info || first < 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_best_run: v / masks / found / r2 / info NULL or first < 0");
+  return boot_best_run(ctx, R, seed, first, w_train, w_test, block, include, v, masks, found, r2, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_boot_best_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15) try {
+  if (!plan15) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_best_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
+  boot_plan15(P, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
 }
 
 int lsspa_boot_timing(const lsspa_ctx* ctx, double* counts_ms, double* gram_ms, double* enum_ms) try {

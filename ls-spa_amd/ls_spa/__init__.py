@@ -16,14 +16,16 @@ g <= 32 groups of p <= 64 columns) and ``ls_spa_owen`` (exact Owen values: the a
 ``groups=`` as coalition structure, returning ``OwenResults``) and ``ls_spa_best_subsets`` (exhaustive best-subset
 selection: the best model of every size by out-of-sample R^2 over all 2^p subsets, p <= 32, returning
 ``BestSubsetsResults``, or with ``groups=`` over all 2^g sets of g <= 32 groups of p <= 64 columns, returning
-``BestGroupSubsetsResults``) are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
+``BestGroupSubsetsResults``) and ``ls_spa_best_subsets_bootstrap`` (the bootstrap of that selection, p <= 32: how often
+each feature, each size and each winner is chosen again on resampled rows, returning ``BestSubsetsBootstrapResults``)
+are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
-from ._results import (BestGroupSubsetsResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
-from ._driver import (ls_spa, ls_spa_best_subsets, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
+from ._driver import (ls_spa, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
                       ls_spa_permutation_test,
                       reduce_data, square_shapley, run_estimator, release)
@@ -39,4 +41,5 @@ __all__ = [
     "MultiGroupResults", "ls_spa_multi_sampled", "SampledMultiResults", "SampledMultiGroupResults",
     "ls_spa_permutation_test", "PermutationTestResults", "ls_spa_owen", "OwenResults",
     "ls_spa_best_subsets", "BestSubsetsResults", "BestGroupSubsetsResults",
+    "ls_spa_best_subsets_bootstrap", "BestSubsetsBootstrapResults",
 ]

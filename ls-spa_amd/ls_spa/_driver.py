@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BestGroupSubsetsResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
@@ -1709,6 +1709,70 @@ def ls_spa_interactions_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_bo
         warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
                       "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
                       "`replicates` and left out of the intervals", RuntimeWarning, stacklevel=2)
+    return res
+
+
+def ls_spa_best_subsets_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, include=None,
+                                  weights=None, resample=("train", "test"), groups=None, device=0, _engine=None):
+    """Bootstrap of the best-subset selection (p <= 32): how stable is the chosen model?
+
+    ``ls_spa_best_subsets`` says "keep features 2, 5, 11" for the rows it was handed, and best-subset selection is
+    unstable: on another draw of the rows another set may win.  The point estimate is that call's (``sizes``,
+    ``subsets``, ``r_squared``, ``best_size``, ``best_subset``, ``full_r_squared``, by the same path).  Each of the
+    ``n_boot`` replicates is one of ``ls_spa_bootstrap``'s -- a given seed resamples the same rows -- and is searched over
+    all 2^p subsets on the GPU from rows that stay there, the replicates of a launch sharing one grid
+    (include/lsspa.h, lsspa_boot_best_run): per size the largest out-of-sample R^2 and its subset, the smaller mask on
+    equal values.  Two calls agree bitwise.
+
+    Returns ``BestSubsetsBootstrapResults``: the point estimate's fields, ``subset_replicates`` [n_boot][n][p] bool,
+    ``r_squared_replicates`` [n_boot][n], ``best_size_replicates`` [n_boot] (the rule of ``best_size``),
+    ``full_r_squared_replicates``, and over the valid replicates ``inclusion_frequency`` [n][p] (the share whose size-k
+    winner holds feature j), ``best_inclusion_frequency`` [p] (the same for each replicate's overall best model),
+    ``best_size_frequency`` [n], ``reselected`` [n] (the share whose size-k winner is the point estimate's) and
+    ``n_failed``: replicates whose Gram matrix was not numerically positive definite are NaN / False and left out, with a
+    RuntimeWarning; more than half of them is a RuntimeError.
+
+    include:  as ``ls_spa_best_subsets`` takes it; the n sizes then start at len(include).
+    weights, resample: as ``ls_spa_bootstrap`` takes them.
+    groups=:  not built yet (the bootstrap of ``ls_spa_best_subsets(groups=)``): a ValueError says so.
+    p > 32, a bad ``include``, ``n_boot``, ``weights`` or ``resample`` and a ``y_test`` that is identically zero are refused
+    before any GPU work."""
+    if groups is not None:
+        raise ValueError("ls_spa_best_subsets_bootstrap does not take groups= yet: the bootstrap of the selection over "
+                         "groups of columns is not built (ls_spa_best_subsets(groups=) gives the point estimate)")
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    n, p = data[0].shape
+    m = data[1].shape[0]
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_best_subsets_bootstrap re-runs the enumeration of all 2^p feature subsets and takes at "
+                         f"most p = {SUBSETS_MAX_P} features (this problem has p = {p})")
+    if p < 1 or m < 1:
+        raise ValueError(f"ls_spa_best_subsets_bootstrap needs p >= 1 features and M >= 1 test rows (p = {p}, M = {m})")
+    mask, inc = include_mask(include, p)
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+    w_train, w_test, sides = _bootstrap_options(n_boot, 0.95, weights, resample, n, m)
+    n_boot = int(n_boot)
+    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
+    undo = []
+    with _engine_call(_engine, device, undo=undo) as engine:
+        with warnings.catch_warnings(record=True) as caught:      # the point estimate's warnings are this call's
+            warnings.simplefilter("always")
+            point = ls_spa_best_subsets(*data, reg=reg, include=include, _engine=engine)
+        engine.boot_load(*data, reg)
+        undo.append((engine.boot_free, True))
+        run = functools.partial(engine.boot_best_run, include=mask)
+        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
+        v, masks, found, r2, binfo = (np.concatenate([q[k] for q in parts]) for k in range(5))
+    for w in caught:
+        warnings.warn(w.message, w.category, stacklevel=2)
+    failed = (binfo & 1).astype(bool) | ~np.isfinite(r2)
+    k0 = len(inc)
+    res = BestSubsetsBootstrapResults.from_replicates(point, v[:, k0:], masks[:, k0:], found[:, k0:], r2, failed)
+    if res.n_failed:
+        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
+                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
+                      "`r_squared_replicates` and left out of the frequencies", RuntimeWarning, stacklevel=2)
     return res
 
 

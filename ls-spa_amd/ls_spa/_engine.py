@@ -92,6 +92,16 @@ def debug_boot_plan(R: int, n: int, m: int, p: int, block: int = 0, inter: bool 
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def debug_boot_best_plan(R: int, n: int, m: int, p: int, block: int = 0):
+    """Test hook, host only: debug_boot_plan for a bootstrap of the best-subset selection (include/lsspa.h,
+    lsspa_debug_boot_best_plan): rep_bytes counts 16 bytes an entry of the enumeration's table."""
+    out = np.zeros(15, dtype=np.int64)
+    rc = N.load().lsspa_debug_boot_best_plan(int(R), int(n), int(m), int(p), int(block), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_boot_best_plan: status {rc}")
+    return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
+
+
 PERM_PLAN_FIELDS = ("block", "n_blocks", "rps_train", "rps_test", "slices_train", "slices_test", "cb", "ldi_train",
                     "ldi_test", "rep_bytes")
 
@@ -505,6 +515,23 @@ class HipEngine:
             self._h, N.iptr(labels), g, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa), N.dptr(we), int(block),
             N.dptr(phi), N.dptr(inter), N.dptr(r2), N.dptr(base), N.iptr(info)))
         return phi, inter, r2, base, info
+
+    def boot_best_run(self, R: int, seed: int, w_train=None, w_test=None, *, include=0, first: int = 0, block: int = 0):
+        """(v [R][p + 1], masks [R][p + 1] uint32, found [R][p + 1] bool, r2 [R], info [R]) of replicates first .. first +
+        R - 1: boot_run's replicates, each searched for its best subset of every size as subsets_best does it
+        (include/lsspa.h, lsspa_boot_best_run); r2 and info are boot_run's."""
+        dims = getattr(self, "_boot_dims", None)
+        n = (dims[0] if dims else 1) + 1
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        v, masks, found = np.empty((R, n)), np.empty((R, n), dtype=np.uint32), np.empty((R, n), dtype=np.uint8)
+        r2, info = np.empty(R), np.zeros(R, dtype=np.int32)
+        self._check(self._lib.lsspa_boot_best_run(
+            self._h, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa), N.dptr(we), int(block), int(include),
+            N.dptr(v), masks.ctypes.data_as(C.POINTER(C.c_uint32)), found.ctypes.data_as(C.POINTER(C.c_uint8)),
+            N.dptr(r2), N.iptr(info)))
+        return v, masks, found.astype(bool), r2, info
+
+    debug_boot_best_plan = staticmethod(debug_boot_best_plan)
 
     def boot_timing(self):
         """Kernel seconds of the last boot_run: counts (or the upload of weights), Gram, enumeration."""

@@ -563,3 +563,94 @@ class InteractionBootstrapResults:
             pad,
         ]
         return "\n".join(lines)
+
+
+def best_sizes(sizes, r_squared):
+    """Per row of r_squared [..., n], the size with the largest value: the first of equal maxima (the smallest size), NaN
+    skipped, -1 for a row that is all NaN -- the rule of ``BestSubsetsResults.best_size``."""
+    r2 = np.asarray(r_squared, dtype=np.float64)
+    empty = np.isnan(r2).all(axis=-1)
+    first = np.argmax(np.where(np.isnan(r2), -np.inf, r2), axis=-1)       # argmax takes the first of equal maxima
+    return np.where(empty, -1, np.asarray(sizes)[first]).astype(np.int64)
+
+
+@dataclass
+class BestSubsetsBootstrapResults:
+    """What ``ls_spa_best_subsets_bootstrap`` returns for p features, n = p + 1 - len(include) sizes and n_boot
+    replicates.  The point estimate on the original rows is exactly ``ls_spa_best_subsets``'s: ``sizes`` [n],
+    ``subsets`` [n][p] bool, ``r_squared`` [n], ``best_size``, ``best_subset`` [p] bool, ``full_r_squared``.  The
+    replicates: ``subset_replicates`` [n_boot][n][p] bool, the best subset of every size on the resampled rows;
+    ``r_squared_replicates`` [n_boot][n], its out-of-sample R^2 there (NaN for a size without a candidate);
+    ``best_size_replicates`` [n_boot], by the rule of ``best_size`` (the smallest of the sizes with the largest R^2, NaN
+    skipped, -1 where every size is NaN); ``full_r_squared_replicates`` [n_boot].  A replicate whose Gram matrix was
+    not numerically positive definite is NaN, False and -1 in these and counted in ``n_failed``.  Over the valid
+    replicates: ``inclusion_frequency`` [n][p], the share whose size-k winner holds feature j ("how often is feature 5
+    in the best model of three features?"); ``best_inclusion_frequency`` [p], the same for each replicate's overall best
+    model; ``best_size_frequency`` [n], the share whose best model has that size; ``reselected`` [n], the share whose
+    size-k winner is the point estimate's."""
+    sizes: np.ndarray
+    subsets: np.ndarray
+    r_squared: np.ndarray
+    best_size: int
+    best_subset: np.ndarray
+    full_r_squared: float
+    subset_replicates: np.ndarray
+    r_squared_replicates: np.ndarray
+    best_size_replicates: np.ndarray
+    full_r_squared_replicates: np.ndarray
+    inclusion_frequency: np.ndarray
+    best_inclusion_frequency: np.ndarray
+    best_size_frequency: np.ndarray
+    reselected: np.ndarray
+    n_failed: int
+
+    @classmethod
+    def from_replicates(cls, point, values, masks, found, full_r_squared_replicates, failed):
+        """The replicate and summary fields from the engine's rows.  point: the ``BestSubsetsResults`` of the original
+        rows; values, masks, found [n_boot][n]: every replicate's best value, mask (bit j = feature j) and found flag
+        at the sizes of ``point.sizes``; failed [n_boot]: which replicates to mask.  RuntimeError when more than half of
+        them failed."""
+        sizes = np.asarray(point.sizes)
+        p = np.asarray(point.subsets).shape[1]
+        failed = np.asarray(failed, dtype=bool)
+        ok_entry = np.asarray(found, dtype=bool) & ~failed[:, None]
+        bits = ((np.asarray(masks).astype(np.int64)[:, :, None] >> np.arange(p)) & 1).astype(bool)
+        sub = bits & ok_entry[:, :, None]
+        r2 = np.where(ok_entry, np.asarray(values, dtype=np.float64), np.nan)
+        full = np.where(failed, np.nan, np.asarray(full_r_squared_replicates, dtype=np.float64))
+        n_failed = int(failed.sum())
+        if 2 * n_failed > len(failed):
+            raise RuntimeError(f"{n_failed} of {len(failed)} bootstrap replicates had a Gram matrix that was not "
+                               "numerically positive definite: no interval can be read from the rest")
+        best = best_sizes(sizes, r2)
+        valid = ~failed
+        n_valid = max(int(valid.sum()), 1)
+        row = np.clip(best - int(sizes[0]), 0, len(sizes) - 1)
+        best_sub = sub[np.arange(len(sub)), row] & (best >= 0)[:, None]
+        same = ok_entry & (sub == np.asarray(point.subsets, dtype=bool)[None]).all(axis=2)
+        return cls(sizes=sizes, subsets=np.asarray(point.subsets), r_squared=np.asarray(point.r_squared),
+                   best_size=int(point.best_size), best_subset=np.asarray(point.best_subset),
+                   full_r_squared=float(point.full_r_squared), subset_replicates=sub, r_squared_replicates=r2,
+                   best_size_replicates=best, full_r_squared_replicates=full,
+                   inclusion_frequency=sub[valid].sum(axis=0) / n_valid,
+                   best_inclusion_frequency=best_sub[valid].sum(axis=0) / n_valid,
+                   best_size_frequency=(best[valid][:, None] == sizes[None, :]).sum(axis=0) / n_valid,
+                   reselected=same[valid].sum(axis=0) / n_valid, n_failed=n_failed)
+
+    def __repr__(self):
+        pad = " " * 8
+        p = np.asarray(self.subsets).shape[1]
+        chosen = np.nonzero(self.best_subset)[0]
+        freq = ", ".join(f"{j}: {self.best_inclusion_frequency[j]:.2f}" for j in chosen[:12])
+        lines = [
+            "",
+            f"{pad}p = {p}, {len(self.subset_replicates)} bootstrap replicates of the best subsets of sizes "
+            f"{int(self.sizes[0])} .. {int(self.sizes[-1])}" + (f" ({self.n_failed} failed)" if self.n_failed else ""),
+            f"{pad}Best model: {self.best_size} features, the best size in "
+            f"{float(self.best_size_frequency[self.best_size - int(self.sizes[0])]) if self.best_size >= 0 else 0.0:.2f}"
+            " of the replicates",
+            f"{pad}Its features and how often a replicate's best model holds them: ({freq}"
+            f"{', ...' if len(chosen) > 12 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)

@@ -7,7 +7,8 @@
 // Then the same for the grouped planner (boot_groups_plan) up to p = 64, and both planners' refusals.  The interaction
 // planners (boot_inter_plan, boot_groups_inter_plan) ride the same sweeps: the Gram side is the phi planner's, steps is
 // the one-problem call's cut whatever R and block are, units * enum_reps * steps <= 2^20 (grouped: and the work bound),
-// and block * rep_bytes + table_bytes <= BOOT_BLOCK_BYTES or block == 1.
+// and block * rep_bytes + table_bytes <= BOOT_BLOCK_BYTES or block == 1.  The best-subset planner (boot_best_plan) too:
+// boot_plan's Gram side and units, 16 bytes a table entry in rep_bytes, per within the kernel's size classes.
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
@@ -64,6 +65,17 @@ int main() {
             CHECK(I.table_bytes == I.enum_reps * (int64_t)I.units * boot_inter_cols(p) * 8);
             CHECK(I.block == 1 || I.block * I.rep_bytes + I.table_bytes <= BOOT_BLOCK_BYTES);
             CHECK(I.rep_bytes >= 8 * (N + M) + 8 * boot_inter_cols(p));
+            BootPlan B;      // the best-subset run: boot_plan's Gram side and units, a table entry of 16 bytes
+            CHECK(boot_best_plan(R, N, M, p, block, B) == nullptr);
+            CHECK(B.cb == P.cb && B.ldz == P.ldz && B.pairs == P.pairs && B.rpw == P.rpw);
+            for (int s = 0; s < 2; ++s) CHECK(B.rps[s] == P.rps[s] && B.slices[s] == P.slices[s]);
+            CHECK(B.units == P.units && B.per == P.per && B.per <= BOOT_BEST_MAX_PER);
+            CHECK(B.rep_bytes == P.rep_bytes + (int64_t)B.units * (p + 1) * 8);
+            CHECK(B.block >= 1 && B.block <= R && B.block <= P.block && (block == 0 || B.block <= block));
+            CHECK(B.n_blocks >= 1 && (B.n_blocks - 1) * B.block < R && B.n_blocks * B.block >= R);
+            CHECK(B.block == 1 || B.block * B.rep_bytes <= BOOT_BLOCK_BYTES);
+            CHECK(B.enum_reps >= 1 && B.enum_reps <= B.block && B.enum_reps <= 65535 && B.steps >= 1 && B.steps <= B.per);
+            CHECK(B.units * (uint64_t)B.enum_reps * B.steps <= BOOT_SUBSETS_PER_LAUNCH && B.table_bytes == 0);
             ++n_ok;
           }
   // The grouped planner (boot_groups_plan): every p up to 64 with layouts of gh high groups, nb baseline and ql low
@@ -131,6 +143,8 @@ int main() {
     CHECK(!boot_groups_inter_plan(1, 1, 1, 8, 2, 1, 0, 1, 0, P));
     CHECK(boot_inter_plan(0, 1, 1, 1, 0, P) && boot_inter_plan(1, 0, 1, 1, 0, P) && boot_inter_plan(1, 1, 1ll << 31, 1, 0, P));
     CHECK(boot_inter_plan(1, 1, 1, 33, 0, P) && boot_inter_plan(1, 1, 1, 0, 0, P) && boot_inter_plan(1, 1, 1, 1, -1, P));
+    CHECK(boot_best_plan(0, 1, 1, 1, 0, P) && boot_best_plan(1, 0, 1, 1, 0, P) && boot_best_plan(1, 1, 1ll << 31, 1, 0, P));
+    CHECK(boot_best_plan(1, 1, 1, 33, 0, P) && boot_best_plan(1, 1, 1, 0, 0, P) && boot_best_plan(1, 1, 1, 1, -1, P));
     // group layouts up to (g, p) = (32, 64): 26 high groups of one or two columns beside six low singletons
     for (int g = 7; g <= 32; ++g) {
       p = 64;
