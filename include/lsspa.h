@@ -359,6 +359,32 @@ int lsspa_boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first,
                         uint8_t* found /* [R][p + 1] */, double* r2 /* [R] */, int32_t* info /* [R] */);
 int lsspa_debug_boot_best_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64_t block, int64_t* plan15);
 
+/* Bootstrap of the best-subset selection over groups of columns (g <= 32 groups, p <= 64 columns, label -1 = the
+ * always-included baseline).  The replicates of lsspa_boot_groups_run -- the same loaded rows, draws, weights, weighted
+ * Grams, finalise, r2, r2_base, info, `first`, `block` and refusals (a seed resamples the same rows) -- each searched by
+ * lsspa_groups_best's enumeration of the 2^g group subsets, all replicates of a launch in one grid.
+ *   lsspa_boot_groups_best_run : after either load.  labels [p], g as lsspa_groups_best's, refused with its messages.
+ *                     Of replicate r, u [r][k] is the largest out-of-sample R^2 among its sets of k = 0 .. g groups
+ *                     (beside the baseline), masks [r][k] that set (bit j = label j) and found [r][k] whether the size
+ *                     had a candidate (else u is NaN and the mask 0): the bits lsspa_groups_best returns for the
+ *                     replicate's reduced problem, whatever R, block, first and the cut into launches are -- the larger
+ *                     value wins, then the smaller mask, a total order that no cut of the work can show in.  A replicate
+ *                     whose pivot fails has LSSPA_INFO_NOT_PD in its own word only; the sets whose own pivots failed
+ *                     are no candidates, every other set of that replicate still is.
+ *   lsspa_boot_timing reports the run like the others.
+ *   lsspa_debug_boot_groups_best_plan : host only -- the fifteen numbers of lsspa_debug_boot_groups_plan for this run.
+ *                     An entry of the enumeration's table takes 16 bytes (value, mask, found), counted in the bytes per
+ *                     replicate: block * bytes <= 256 MB (or block = 1).  steps is the one-problem call's; replicates
+ *                     per launch fill what it leaves of that call's work bound, units * replicates <= 2^20; high subsets
+ *                     per unit <= 2^18.  Bad labels or sizes: LSSPA_ERR_ARG. */
+int lsspa_boot_groups_best_run(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, int64_t R, uint64_t seed,
+                               int64_t first, const double* w_train /* [R][N] or NULL */,
+                               const double* w_test /* [R][M] or NULL */, int64_t block, double* u /* [R][g + 1] */,
+                               uint32_t* masks /* [R][g + 1] */, uint8_t* found /* [R][g + 1] */, double* r2 /* [R] */,
+                               double* r2_base /* [R] */, int32_t* info /* [R] */);
+int lsspa_debug_boot_groups_best_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p,
+                                      int32_t g, int64_t block, int64_t* plan15);
+
 /* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
  * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the
  * 2^p subsets are enumerated once for every 8 responses: a wave sweeps a high subset's pivots out of [G | g_r ...] with

@@ -131,6 +131,31 @@ const char* boot_groups_plan(int64_t R, int64_t N, int64_t M, int p, int g, int 
   return nullptr;
 }
 
+const char* boot_groups_best_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
+                                  BootPlan& P) {
+  BootPlan Q;      // arguments, Gram side, units and per: the phi planner's
+  if (const char* why = boot_groups_plan(R, N, M, p, g, gh, nb, ql, block, Q)) {
+    P = BootPlan{};
+    return why;
+  }
+  P = Q;
+  // units = min(2^gh, BOOT_UNITS) and gh < g <= 32 or gh = g = 32 (which no layout of <= 64 columns has, and which
+  // launch_groups_best refuses): the kernel's size classes hold every per a layout can give
+  static_assert(((1ull << (BOOT_GROUPS_MAX_G - 1)) / BOOT_UNITS) <= BOOT_GROUPS_BEST_MAX_PER,
+                "groups_best_kernel holds the size classes of the largest per: 31 high groups over BOOT_UNITS units");
+  if (P.per > BOOT_GROUPS_BEST_MAX_PER) return "more high subsets per unit than the best kernel's size classes hold";
+  plan_blocks(R, N, M, p + 1, g, block, P, 16);
+  // The winner of a total order does not depend on the cut, so the cut is chosen for speed: a unit's steps first, as the
+  // one-problem call cuts them (a workgroup loads its replicate's h and merges into its row once per launch), then as
+  // many replicates as the work bound and the 2^20 workgroups leave such a launch
+  const uint64_t rows = (uint64_t)(nb + ql + 1) + (uint64_t)(p - nb - ql + 1) / 2;
+  const uint64_t per_launch = std::max<uint64_t>(1, BOOT_GROUPS_WORK_PER_LAUNCH / (rows * rows));
+  P.steps = std::min<uint64_t>(P.per, std::max<uint64_t>(1, per_launch / P.units));
+  const uint64_t reps = std::min<uint64_t>(BOOT_SUBSETS_PER_LAUNCH / P.units, per_launch / (P.units * P.steps));
+  P.enum_reps = std::max<int64_t>(1, std::min<int64_t>(P.block, (int64_t)reps));
+  return nullptr;
+}
+
 const char* boot_inter_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, BootPlan& P) {
   P = BootPlan{};
   if (p < 1 || p > BOOT_MAX_P) return "p must be 1 .. 32";

@@ -44,6 +44,17 @@ const char* boot_groups_plan(int64_t R, int64_t N, int64_t M, int p, int g, int 
                              BootPlan& P);
 constexpr int BOOT_GROUPS_MAX_P = 64, BOOT_GROUPS_MAX_G = 32;   // GROUPS_MAX_P, GROUPS_MAX_G (k_groups.hip)
 constexpr uint64_t BOOT_GROUPS_WORK_PER_LAUNCH = 1ull << 26;    // that of lsspa_groups_shapley's host path
+// The bootstrap of the best-subset selection over groups (lsspa_boot_groups_best_run): boot_groups_plan's arguments,
+// Gram side, units and per, with the enumeration's table holding, per (unit, size), a value, a mask and a found flag --
+// 16 bytes an entry, units (g + 1) 16 bytes a replicate, counted in rep_bytes: block rep_bytes <= BOOT_BLOCK_BYTES, or
+// block = 1.  per <= BOOT_GROUPS_BEST_MAX_PER always (the size classes groups_best_kernel holds; asserted).  The winner
+// of a total order depends on no cut of a unit's steps into launches, and a workgroup computes each u(S) whole: the cut
+// is chosen for speed.  steps: the one-problem call's (min(per, max(1, work bound / rows^2 / units))); enum_reps: what
+// such a launch leaves -- units enum_reps steps rows^2 <= BOOT_GROUPS_WORK_PER_LAUNCH (unless one step of one replicate
+// is already more) and units enum_reps <= 2^20 workgroups --, at most the block, at least 1.
+constexpr uint64_t BOOT_GROUPS_BEST_MAX_PER = 1ull << 18;       // 2^(GROUPS_BEST_CLASSES - 1) (kernels.h)
+const char* boot_groups_best_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
+                                  BootPlan& P);
 
 // The bootstrap of the interaction values (lsspa_boot_interactions_run, lsspa_boot_groups_interactions_run): the plans
 // above with the enumeration's partial table inter_cols(d) = d (d + 3) / 2 + 2 wide, d = p or g players -- 37 MB a

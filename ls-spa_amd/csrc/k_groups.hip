@@ -55,7 +55,8 @@
 //
 // Best group subset of every size (lsspa_groups_best, groups_best_kernel below): a kernel of its own beside the
 // enumeration kernel -- an arg-max cannot be had from its sums -- with the same workgroup, units, steps, load_shared and
-// group_values<false>; one problem, no replicates, no Owen weights.  What it keeps of u(Hs + T) is, per size k = |Hs| +
+// group_values; no Owen weights, and replicates only in its REPS instantiation (the bootstrap of the selection,
+// lsspa_boot_groups_best_run: the launch's second grid dimension, like the enumeration kernel's).  What it keeps of u(Hs + T) is, per size k = |Hs| +
 // |T| (groups, not columns; size 0 is the baseline alone), the largest value and its subset.  Order: the larger value
 // wins, on equal values the numerically smaller mask in the CALLER's numbering (bit k = label k); a subset whose own
 // pivots failed -- the workgroup's high ones or the lane's low ones -- is no candidate and NaN never wins (v > best from
@@ -555,6 +556,14 @@ __device__ inline void wave_best(double& v, uint32_t& mask) {
 // a.part [units][g + 1] (values), bm [units][g + 1][2] (caller mask, found): unit u's best subset of every size so far;
 // a launch merges its own into them (found = 0: no candidate yet).  One workgroup owns a row, launches are ordered by
 // the stream: plain loads and stores.
+// REPS (the bootstrap of the selection over groups, lsspa_boot_groups_best_run): replicate blockIdx.y reads its own
+// problem, 1 / ||y||^2 and info word (rep_offset; load_shared<true>, group_values<true>) and merges into its own rows of
+// the tables [reps][units][g + 1] and [reps][units][g + 1][2]; layout, weights and ids are the launch's.  The order is
+// total, so a replicate's result depends neither on the cut of `per` into launches nor on the replicates beside it.
+// Offsets formed at every use, as the phi-only REPS enumeration forms them: this kernel keeps its running bests in LDS,
+// not in registers, and has the room (no scratch, the one-problem instantiation's registers).  Without REPS
+// the code is what it was.
+template <bool REPS = false>
 __global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s0, uint64_t s1, GroupIds ids,
                                                          uint32_t* __restrict__ bm) {
   __shared__ GrpShared sh;
@@ -569,12 +578,12 @@ __global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s
       sb.h[j * 64 + tid] = 0u;
     }
   }
-  load_shared<false>(sh, a, tid);              // (ends with a barrier: gid)
+  load_shared<REPS>(sh, a, tid);               // (ends with a barrier: gid)
   bool any_bad = false;
   for (uint64_t s = s0; s < s1; ++s) {
     const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
     bool bad = false;                          // this subset's own pivots: the high ones the workgroup's, the low ones the lane's
-    const double v = group_values<false>(sh, a, hi, tid, bad);
+    const double v = group_values<REPS>(sh, a, hi, tid, bad);
     any_bad |= bad;
     // a lane sees the subsets of a class in ascending hi, which is ascending caller mask (groups_layout numbers the
     // high groups in ascending label order): the strict compare keeps the smaller one, and NaN never wins
@@ -588,8 +597,8 @@ __global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s
     __syncthreads();
   }
   if (tid < 64) {
-    double* rv = a.part + (int64_t)blockIdx.x * (ng + 1);
-    uint32_t* rm = bm + (int64_t)blockIdx.x * (ng + 1) * 2;
+    double* rv = a.part + (rep_offset<REPS>(gridDim.x) + (int64_t)blockIdx.x) * (ng + 1);
+    uint32_t* rm = bm + (rep_offset<REPS>(gridDim.x) + (int64_t)blockIdx.x) * (ng + 1) * 2;
     // the sizes this unit can hold: popc(unit) + popc(s) + popc(T), s < per (a power of two), T < 2^gl
     const int ncls = __popcll(a.per - 1) + 1;
     const int k0 = __popc(blockIdx.x), k1 = min(ng, k0 + ncls - 1 + gl);
@@ -617,7 +626,7 @@ __global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s
       }
     }
   }
-  if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info, 1);
+  if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<REPS>(1), 1);
 }
 
 // masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
@@ -739,9 +748,11 @@ hipError_t launch_groups_owen(const GroupArgs& a, uint64_t units, uint64_t s0, u
 }
 
 hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1, uint32_t* bm,
-                              hipStream_t st) {
+                              hipStream_t st, int reps) {
   if (!args_ok(a) || !a.part || !bm || !gid || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
-  if (a.inv_yy_rep) return hipErrorInvalidValue;     // no replicates: one problem
+  // replicates: launch_groups_enum's terms (the caller vouches for `reps` problems, rows of both tables and info words)
+  if (reps < 1 || reps > 65535 || (a.inv_yy_rep ? units * (uint64_t)reps > (1ull << 20) : reps != 1))
+    return hipErrorInvalidValue;
   if (a.gh > GHI) return hipErrorInvalidValue;       // hi is kept in 32 bits (no layout of <= 64 columns has gh = 32)
   if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
   // the size classes of a unit are popc(s), s < per: per a power of two (it is: units per = 2^gh) of at most GBS - 1 bits
@@ -753,7 +764,11 @@ hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units
     seen |= 1u << gid[r];
     ids.id[r] = (uint8_t)gid[r];
   }
-  hipLaunchKernelGGL(groups_best_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1, ids, bm);
+  if (a.inv_yy_rep)
+    hipLaunchKernelGGL(groups_best_kernel<true>, dim3((unsigned)units, (unsigned)reps), dim3(NT), 0, st, a, s0, s1, ids,
+                       bm);
+  else
+    hipLaunchKernelGGL(groups_best_kernel<false>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1, ids, bm);
   return hipGetLastError();
 }
 

@@ -424,17 +424,20 @@ hipError_t launch_groups_enum(const GroupArgs& a, uint64_t units, uint64_t s0, u
 // [GROUPS_MAX_G + 1]; rows 0 and 1 are not read.  Refuses replicates (GroupArgs::inv_yy_rep).  Of a row of the table
 // the inner players' columns and b mean something: Ow_i = column i - column ng.
 hipError_t launch_groups_owen(const GroupArgs& a, uint64_t units, uint64_t s0, uint64_t s1, hipStream_t st);
-// Best group subset of every size (lsspa_groups_best): the units, steps and launches of launch_groups_enum (one problem,
-// no replicates), but a.part [units][g + 1] holds each unit's largest u(S) per size |S| (the number of groups) and bm
+// Best group subset of every size (lsspa_groups_best): the units, steps and launches of launch_groups_enum, but a.part [units][g + 1] holds each unit's largest u(S) per size |S| (the number of groups) and bm
 // [units][g + 1][2] its mask and a found flag, both zeroed before the first launch; every launch merges into them, and
 // launch_subsets_best_reduce (p = g) takes the best over the units.  Masks in the table are in the CALLER's numbering
 // (bit k = label k): gid is GroupLayout::gid, which the kernel receives by value.  Larger value wins, on equal values
 // the smaller caller mask; a subset with a failed pivot of its own is no candidate.  Inside a unit the size class of a
 // step is popc(s), s < per: the kernel holds GROUPS_BEST_CLASSES of them, and a per beyond 2^(GROUPS_BEST_CLASSES - 1)
 // is refused (hipErrorInvalidValue), as is gh = 32 (no layout of <= 64 columns has it).
+// reps: on launch_groups_enum's terms (with GroupArgs::inv_yy_rep only, 1 <= reps <= 65535, units * reps <= 2^20;
+// lsspa_boot_groups_best_run): the replicates behind the launch's problem as its second grid dimension, the tables
+// [reps][units][g + 1] and [reps][units][g + 1][2]; the layout, the weights and gid are the launch's.  A replicate's
+// result does not depend on the launches' cut or on the replicates beside it.
 constexpr int GROUPS_BEST_CLASSES = 19;   // per <= 2^18: gh <= 31 high groups over 8192 units (lsspa_api.hip asserts it)
 hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1,
-                              uint32_t* bm, hipStream_t st);
+                              uint32_t* bm, hipStream_t st, int reps = 1);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

@@ -4441,6 +4441,90 @@ int boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const
   return boot_run_blocks(ctx, P, R, seed, first, w_host, p1, 2 * p1, launch, reduce, emit, info);
 }
 
+// lsspa_boot_groups_best_run: groups_best_kernel's replicates over the block's reduced problems, boot_groups_run's in
+// everything before the enumeration.  The table and a replicate's row of B.eout as boot_best_run's, with the g groups as
+// the players: values in B.epart [enum_reps][units][g + 1], (caller mask, found) in B.ebest beside it.
+static_assert(BOOT_GROUPS_BEST_MAX_PER == (1ull << (GROUPS_BEST_CLASSES - 1)),
+              "boot_groups_best_plan's bound on per is groups_best_kernel's size classes");
+int boot_groups_best_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, uint64_t seed, int64_t first,
+                         const double* w_train, const double* w_test, int64_t block, double* u, uint32_t* masks,
+                         uint8_t* found, double* r2, double* r2_base, int32_t* info) {
+  BootWork& B = ctx->boot;
+  char msg[240];
+  if (g > GROUPS_MAX_G) {      // lsspa_groups_best's messages (groups_args)
+    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+             (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  GroupLayout L;
+  if (const char* why = groups_layout(labels, B.p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  if (const char* why = boot_groups_best_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_groups_best_run: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
+  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* const w_host[2] = {w_train, w_test};
+  bool counts[2] = {!w_train, !w_test};
+  const int p = B.p, ng = L.ng, g1 = ng + 1;
+  TRY(boot_alloc_block(ctx, P, counts, true, g1));
+  TRY(dev_alloc(ctx, B.eout, (size_t)P.block * 2 * g1));
+  const size_t rows = (size_t)P.units * g1;                // entries of one replicate's table
+  TRY(dev_alloc(ctx, B.ebest, 2 * rows * (size_t)P.enum_reps));
+  TRY(boot_upload_tables(ctx, ng, L.tab));
+  std::vector<double> r2_ws;
+  int all[GROUPS_MAX_P];       // the full model's columns; the baseline's are the layout's first nb
+  for (int j = 0; j < p; ++j) all[j] = j;
+  int base[GROUPS_MAX_P];
+  for (int j = 0; j < L.nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
+  auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
+    if (s0 == 0) {      // a new set of replicates: nothing found yet
+      hipError_t e = hipMemsetAsync(B.ebest.ptr, 0, sizeof(uint32_t) * 2 * rows * (size_t)ne, ctx->stream);
+      if (e != hipSuccess) return e;
+    }
+    GroupArgs a{};
+    a.p = p; a.ng = ng; a.nb = L.nb;
+    a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+    a.G = B.G.ptr + (size_t)e0 * p * p;
+    a.H = B.H.ptr + (size_t)e0 * p * p;
+    a.g = B.g.ptr + (size_t)e0 * p;
+    a.h = B.h.ptr + (size_t)e0 * p;
+    a.ldg = a.ldh = p;
+    a.w = B.w.ptr;
+    a.tab = B.tab.ptr;
+    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+    a.inv_yy_rep = B.inv_yy.ptr + e0;
+    a.info = B.info.ptr + e0;
+    a.per = P.per;
+    a.part = B.epart.ptr;
+    return launch_groups_best(a, L.gid, P.units, s0, s1, B.ebest.ptr, ctx->stream, ne);
+  };
+  auto reduce = [&](int e0, int ne) {
+    double* row = B.eout.ptr + (size_t)e0 * 2 * g1;
+    return launch_subsets_best_reduce(B.epart.ptr, B.ebest.ptr, (int64_t)P.units, ng, row,
+                                      reinterpret_cast<uint32_t*>(row + g1), ctx->stream, ne, 2 * g1);
+  };
+  auto emit = [&](int64_t r, const double* out, const double* G, const double* gv, const double* H, const double* h,
+                  double inv_yy) {
+    uint32_t mf[2 * (GROUPS_MAX_G + 1)];
+    std::memcpy(mf, out + g1, sizeof(uint32_t) * 2 * g1);
+    for (int k = 0; k <= ng; ++k) {
+      const bool f = mf[2 * k + 1] != 0u;
+      found[r * g1 + k] = f ? 1 : 0;
+      masks[r * g1 + k] = f ? mf[2 * k] : 0u;
+      u[r * g1 + k] = f ? out[k] : std::nan("");
+    }
+    r2[r] = boot_r2_cols(p, all, p, G, gv, H, h, inv_yy, r2_ws);
+    r2_base[r] = boot_r2_cols(p, base, L.nb, G, gv, H, h, inv_yy, r2_ws);
+  };
+  return boot_run_blocks(ctx, P, R, seed, first, w_host, g1, 2 * g1, launch, reduce, emit, info);
+}
+
 }  // namespace
 
 extern "C" {
@@ -4609,6 +4693,33 @@ int lsspa_debug_boot_best_plan(int64_t R, int64_t N, int64_t M, int32_t p, int64
   if (!plan15) return LSSPA_ERR_ARG;
   BootPlan P;
   if (boot_best_plan(R, N, M, p, block, P)) return LSSPA_ERR_ARG;
+  boot_plan15(P, plan15);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_boot_groups_best_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, uint64_t seed, int64_t first,
+                               const double* w_train, const double* w_test, int64_t block, double* u, uint32_t* masks,
+                               uint8_t* found, double* r2, double* r2_base, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(boot_need_loaded(ctx));
+  if (!labels || !u || !masks || !found || !r2 || !r2_base || !info || first < 0)
+    return ctx->fail(LSSPA_ERR_ARG,
+                     "lsspa_boot_groups_best_run: labels / u / masks / found / r2 / r2_base / info NULL or first < 0");
+  return boot_groups_best_run(ctx, labels, g, R, seed, first, w_train, w_test, block, u, masks, found, r2, r2_base,
+                              info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_boot_groups_best_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels, int32_t p, int32_t g,
+                                      int64_t block, int64_t* plan15) try {
+  if (!plan15 || !labels || p < 1 || p > GROUPS_MAX_P) return LSSPA_ERR_ARG;
+  GroupLayout L;
+  if (groups_layout(labels, p, g, L)) return LSSPA_ERR_ARG;
+  BootPlan P;
+  if (boot_groups_best_plan(R, N, M, p, L.ng, L.gh, L.nb, L.ql, block, P)) return LSSPA_ERR_ARG;
   boot_plan15(P, plan15);
   return LSSPA_OK;
 } catch (...) {

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
@@ -1734,7 +1734,8 @@ def ls_spa_best_subsets_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_bo
 
     include:  as ``ls_spa_best_subsets`` takes it; the n sizes then start at len(include).
     weights, resample: as ``ls_spa_bootstrap`` takes them.
-    groups=:  not built yet (the bootstrap of ``ls_spa_best_subsets(groups=)``): a ValueError says so.
+    groups=:  not taken here, a ValueError says so: the bootstrap of ``ls_spa_best_subsets(groups=)`` is a call of its
+        own, ``ls_spa_best_group_subsets_bootstrap``.
     p > 32, a bad ``include``, ``n_boot``, ``weights`` or ``resample`` and a ``y_test`` that is identically zero are refused
     before any GPU work."""
     if groups is not None:
@@ -1769,6 +1770,72 @@ def ls_spa_best_subsets_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_bo
     failed = (binfo & 1).astype(bool) | ~np.isfinite(r2)
     k0 = len(inc)
     res = BestSubsetsBootstrapResults.from_replicates(point, v[:, k0:], masks[:, k0:], found[:, k0:], r2, failed)
+    if res.n_failed:
+        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
+                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
+                      "`r_squared_replicates` and left out of the frequencies", RuntimeWarning, stacklevel=2)
+    return res
+
+
+def ls_spa_best_group_subsets_bootstrap(X_train, X_test, y_train, y_test, groups, reg=0., n_boot=1000, seed=42, *,
+                                        weights=None, resample=("train", "test"), device=0, _engine=None):
+    """Bootstrap of the best-subset selection over groups of columns (g <= 32 groups over p <= 64 columns): how stable
+    is the chosen set of groups?
+
+    ``ls_spa_best_subsets(groups=)`` says "keep the factor, drop the spline" for the rows it was handed; on another draw
+    of the rows another set of groups may win.  The point estimate is that call's (``sizes`` 0 .. g, ``group_subsets``,
+    ``subsets``, ``r_squared``, ``best_size``, ``best_group_subset``, ``best_subset``, ``full_r_squared``,
+    ``baseline_r_squared``, by the same path, its warnings this call's).  Each of the ``n_boot`` replicates is one of
+    ``ls_spa_bootstrap(groups=)``'s -- a given seed resamples the same rows -- and is searched over all 2^g sets of
+    groups on the GPU from rows that stay there, the replicates of a launch sharing one grid (include/lsspa.h,
+    lsspa_boot_groups_best_run): per number of groups the largest out-of-sample R^2 and its set, the smaller mask (bit
+    k = group k) on equal values.  Two calls agree bitwise.
+
+    groups:   one label per column as ``ls_spa_best_subsets(groups=)`` takes them: k in 0 .. g-1 puts the column into
+        group k, -1 into the baseline that every model contains.  There is no ``include=``: the baseline is the
+        include set.  The p <= 32 limit of ``ls_spa_best_subsets_bootstrap`` does not apply.
+    weights, resample: as ``ls_spa_bootstrap`` takes them.
+
+    Returns ``BestGroupSubsetsBootstrapResults``: the point estimate's fields, ``group_subset_replicates``
+    [n_boot][g + 1][g] bool, ``r_squared_replicates`` [n_boot][g + 1], ``best_size_replicates`` [n_boot] (the rule of
+    ``best_size``), ``full_r_squared_replicates``, ``baseline_r_squared_replicates`` (column 0 of
+    ``r_squared_replicates`` wherever the baseline alone is a candidate), and over the valid replicates
+    ``inclusion_frequency`` [g + 1][g] (the share whose size-k winner holds group j), ``best_inclusion_frequency`` [g]
+    (the same for each replicate's overall best model), ``best_size_frequency`` [g + 1], ``reselected`` [g + 1] (the
+    share whose size-k winner is the point estimate's) and ``n_failed``: replicates whose Gram matrix was not
+    numerically positive definite are NaN / False and left out, with a RuntimeWarning; more than half of them is a
+    RuntimeError.
+
+    Bad labels, p > 64, g > 32, a bad ``n_boot``, ``weights`` or ``resample``, shapes that do not fit and a ``y_test``
+    that is identically zero are refused before any GPU work."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    n, p = data[0].shape
+    m = data[1].shape[0]
+    if p > GROUPS_MAX_P:
+        raise ValueError(f"grouped attribution takes at most p = {GROUPS_MAX_P} columns, the baseline's included "
+                         f"(this problem has p = {p})")
+    labels, g = group_labels(groups, p)
+    if m < 1:
+        raise ValueError(f"ls_spa_best_group_subsets_bootstrap needs M >= 1 test rows (M = {m})")
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+    w_train, w_test, sides = _bootstrap_options(n_boot, 0.95, weights, resample, n, m)
+    n_boot = int(n_boot)
+    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
+    undo = []
+    with _engine_call(_engine, device, undo=undo) as engine:
+        with warnings.catch_warnings(record=True) as caught:      # the point estimate's warnings are this call's
+            warnings.simplefilter("always")
+            point = ls_spa_best_subsets(*data, reg=reg, groups=labels, _engine=engine)
+        engine.boot_load(*data, reg, grouped=True)
+        undo.append((engine.boot_free, True))
+        run = functools.partial(engine.boot_groups_best_run, labels)
+        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
+        u, masks, found, r2, base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(6))
+    for w in caught:
+        warnings.warn(w.message, w.category, stacklevel=2)
+    failed = (binfo & 1).astype(bool) | ~np.isfinite(r2) | ~np.isfinite(base)
+    res = BestGroupSubsetsBootstrapResults.from_replicates(point, u, masks, found, r2, base, failed)
     if res.n_failed:
         warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
                       "positive definite (a column constant or collinear on the resampled rows); they are NaN in "

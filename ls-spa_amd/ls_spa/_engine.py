@@ -142,6 +142,20 @@ def debug_boot_groups_plan(R: int, n: int, m: int, labels, block: int = 0, inter
     return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def debug_boot_groups_best_plan(R: int, n: int, m: int, labels, block: int = 0):
+    """Test hook, host only: debug_boot_groups_plan for a bootstrap of the best-subset selection over the groups of labels
+    (include/lsspa.h, lsspa_debug_boot_groups_best_plan): rep_bytes counts 16 bytes an entry of the enumeration's table,
+    and steps / enum_reps are chosen for speed within the launch bounds."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(15, dtype=np.int64)
+    rc = N.load().lsspa_debug_boot_groups_best_plan(int(R), int(n), int(m), N.iptr(labels), len(labels), g, int(block),
+                                                    out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_boot_groups_best_plan: status {rc}")
+    return dict(zip(BOOT_PLAN_FIELDS, (int(v) for v in out)))
+
+
 OWEN_PLAN_FIELDS = ("players", "gl", "gh", "ql", "inner_low", "inner_high", "high_subsets", "launches")
 
 
@@ -532,6 +546,28 @@ class HipEngine:
         return v, masks, found.astype(bool), r2, info
 
     debug_boot_best_plan = staticmethod(debug_boot_best_plan)
+
+    def boot_groups_best_run(self, labels, R: int, seed: int, w_train=None, w_test=None, *, first: int = 0,
+                             block: int = 0):
+        """(u [R][g + 1], masks [R][g + 1] uint32, found [R][g + 1] bool, r2 [R], r2_base [R], info [R]) of replicates
+        first .. first + R - 1: boot_groups_run's replicates, each searched for its best set of every number of groups
+        as groups_best does it (include/lsspa.h, lsspa_boot_groups_best_run; bit k of a mask = label k); r2, r2_base and
+        info are boot_groups_run's."""
+        labels, g = self._labels(labels)
+        dims = getattr(self, "_boot_dims", None)
+        if dims is not None and len(labels) != dims[0]:
+            raise ValueError(f"labels must have length p = {dims[0]}")
+        wa, we = self._boot_weights(w_train, R, 0), self._boot_weights(w_test, R, 1)
+        n = max(g, 0) + 1
+        u, masks, found = np.empty((R, n)), np.empty((R, n), dtype=np.uint32), np.empty((R, n), dtype=np.uint8)
+        r2, base, info = np.empty(R), np.empty(R), np.zeros(R, dtype=np.int32)
+        self._check(self._lib.lsspa_boot_groups_best_run(
+            self._h, N.iptr(labels), g, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa), N.dptr(we), int(block),
+            N.dptr(u), masks.ctypes.data_as(C.POINTER(C.c_uint32)), found.ctypes.data_as(C.POINTER(C.c_uint8)),
+            N.dptr(r2), N.dptr(base), N.iptr(info)))
+        return u, masks, found.astype(bool), r2, base, info
+
+    debug_boot_groups_best_plan = staticmethod(debug_boot_groups_best_plan)
 
     def boot_timing(self):
         """Kernel seconds of the last boot_run: counts (or the upload of weights), Gram, enumeration."""

@@ -654,3 +654,81 @@ class BestSubsetsBootstrapResults:
             pad,
         ]
         return "\n".join(lines)
+
+
+@dataclass
+class BestGroupSubsetsBootstrapResults:
+    """What ``ls_spa_best_group_subsets_bootstrap`` returns for g groups over p columns (sizes 0 .. g, n = g + 1) and
+    n_boot replicates.  The point estimate on the original rows is exactly ``ls_spa_best_subsets(groups=)``'s: ``sizes``
+    [n], ``group_subsets`` [n][g] bool, ``subsets`` [n][p] bool, ``r_squared`` [n], ``best_size``,
+    ``best_group_subset`` [g] bool, ``best_subset`` [p] bool, ``full_r_squared``, ``baseline_r_squared``.  The
+    replicates: ``group_subset_replicates`` [n_boot][n][g] bool, the best set of every number of groups on the resampled
+    rows; ``r_squared_replicates`` [n_boot][n], its out-of-sample R^2 there (NaN for a size without a candidate);
+    ``best_size_replicates`` [n_boot], by the rule of ``best_size`` (-1 where every size is NaN);
+    ``full_r_squared_replicates`` and ``baseline_r_squared_replicates`` [n_boot], the R^2 of each replicate's full model
+    and of its baseline columns alone.  A failed replicate (a Gram matrix that was not numerically positive definite) is
+    NaN, False and -1 in these and counted in ``n_failed``.  Over the valid replicates, with the groups as the players
+    of ``BestSubsetsBootstrapResults``: ``inclusion_frequency`` [n][g], the share whose size-k winner holds group j;
+    ``best_inclusion_frequency`` [g], the same for each replicate's overall best model; ``best_size_frequency`` [n];
+    ``reselected`` [n], the share whose size-k winner is the point estimate's."""
+    sizes: np.ndarray
+    group_subsets: np.ndarray
+    subsets: np.ndarray
+    r_squared: np.ndarray
+    best_size: int
+    best_group_subset: np.ndarray
+    best_subset: np.ndarray
+    full_r_squared: float
+    baseline_r_squared: float
+    group_subset_replicates: np.ndarray
+    r_squared_replicates: np.ndarray
+    best_size_replicates: np.ndarray
+    full_r_squared_replicates: np.ndarray
+    baseline_r_squared_replicates: np.ndarray
+    inclusion_frequency: np.ndarray
+    best_inclusion_frequency: np.ndarray
+    best_size_frequency: np.ndarray
+    reselected: np.ndarray
+    n_failed: int
+
+    @classmethod
+    def from_replicates(cls, point, values, masks, found, full_r_squared_replicates, baseline_r_squared_replicates,
+                        failed):
+        """The replicate and summary fields from the engine's rows.  point: the ``BestGroupSubsetsResults`` of the
+        original rows; values, masks, found [n_boot][g + 1]: every replicate's best value, mask (bit k = group k) and
+        found flag; failed [n_boot]: which replicates to mask.  The tallies are
+        ``BestSubsetsBootstrapResults.from_replicates``'s with the groups as the players; its RuntimeError when more
+        than half of the replicates failed."""
+        players = BestSubsetsResults(sizes=np.asarray(point.sizes), subsets=np.asarray(point.group_subsets),
+                                     r_squared=np.asarray(point.r_squared), theta=None, best_size=int(point.best_size),
+                                     best_subset=np.asarray(point.best_group_subset),
+                                     full_r_squared=float(point.full_r_squared))
+        t = BestSubsetsBootstrapResults.from_replicates(players, values, masks, found, full_r_squared_replicates, failed)
+        base = np.where(np.asarray(failed, dtype=bool), np.nan,
+                        np.asarray(baseline_r_squared_replicates, dtype=np.float64))
+        return cls(sizes=t.sizes, group_subsets=t.subsets, subsets=np.asarray(point.subsets), r_squared=t.r_squared,
+                   best_size=t.best_size, best_group_subset=t.best_subset, best_subset=np.asarray(point.best_subset),
+                   full_r_squared=t.full_r_squared, baseline_r_squared=float(point.baseline_r_squared),
+                   group_subset_replicates=t.subset_replicates, r_squared_replicates=t.r_squared_replicates,
+                   best_size_replicates=t.best_size_replicates, full_r_squared_replicates=t.full_r_squared_replicates,
+                   baseline_r_squared_replicates=base, inclusion_frequency=t.inclusion_frequency,
+                   best_inclusion_frequency=t.best_inclusion_frequency, best_size_frequency=t.best_size_frequency,
+                   reselected=t.reselected, n_failed=t.n_failed)
+
+    def __repr__(self):
+        pad = " " * 8
+        g = np.asarray(self.group_subsets).shape[1]
+        chosen = np.nonzero(self.best_group_subset)[0]
+        freq = ", ".join(f"{j}: {self.best_inclusion_frequency[j]:.2f}" for j in chosen[:12])
+        lines = [
+            "",
+            f"{pad}g = {g} groups over p = {np.asarray(self.subsets).shape[1]} columns, "
+            f"{len(self.group_subset_replicates)} bootstrap replicates of the best sets of 0 .. {g} groups"
+            + (f" ({self.n_failed} failed)" if self.n_failed else ""),
+            f"{pad}Best model: {self.best_size} groups, the best size in "
+            f"{float(self.best_size_frequency[self.best_size]) if self.best_size >= 0 else 0.0:.2f} of the replicates",
+            f"{pad}Its groups and how often a replicate's best model holds them: ({freq}"
+            f"{', ...' if len(chosen) > 12 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)

@@ -8,7 +8,9 @@
 // planners (boot_inter_plan, boot_groups_inter_plan) ride the same sweeps: the Gram side is the phi planner's, steps is
 // the one-problem call's cut whatever R and block are, units * enum_reps * steps <= 2^20 (grouped: and the work bound),
 // and block * rep_bytes + table_bytes <= BOOT_BLOCK_BYTES or block == 1.  The best-subset planner (boot_best_plan) too:
-// boot_plan's Gram side and units, 16 bytes a table entry in rep_bytes, per within the kernel's size classes.
+// boot_plan's Gram side and units, 16 bytes a table entry in rep_bytes, per within the kernel's size classes; and its
+// grouped sibling (boot_groups_best_plan) on the grouped sweep: boot_groups_plan's Gram side, units and per, 16 bytes an
+// entry, units * enum_reps <= 2^20 workgroups, and the work bound unless one step of one replicate is already more.
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
@@ -125,6 +127,19 @@ int main() {
                     I.units * (uint64_t)I.enum_reps * I.steps * mrows * mrows <= BOOT_GROUPS_WORK_PER_LAUNCH);
               CHECK(I.table_bytes == I.enum_reps * (int64_t)I.units * boot_inter_cols(L.g) * 8);
               CHECK(I.block == 1 || I.block * I.rep_bytes + I.table_bytes <= BOOT_BLOCK_BYTES);
+              BootPlan B;      // the best-subset run over groups: that Gram side, units and per, a table entry of 16 bytes
+              CHECK(boot_groups_best_plan(R, N, M, p, L.g, L.gh, L.nb, L.ql, block, B) == nullptr);
+              CHECK(B.cb == P.cb && B.ldz == P.ldz && B.pairs == P.pairs && B.rpw == P.rpw);
+              for (int s = 0; s < 2; ++s) CHECK(B.rps[s] == P.rps[s] && B.slices[s] == P.slices[s]);
+              CHECK(B.units == P.units && B.per == P.per && B.per <= BOOT_GROUPS_BEST_MAX_PER);
+              CHECK(B.rep_bytes == P.rep_bytes + (int64_t)B.units * (L.g + 1) * 8);
+              CHECK(B.block >= 1 && B.block <= R && B.block <= P.block && (block == 0 || B.block <= block));
+              CHECK(B.n_blocks >= 1 && (B.n_blocks - 1) * B.block < R && B.n_blocks * B.block >= R);
+              CHECK(B.block == 1 || B.block * B.rep_bytes <= BOOT_BLOCK_BYTES);
+              CHECK(B.enum_reps >= 1 && B.enum_reps <= B.block && B.enum_reps <= 65535 && B.steps >= 1 && B.steps <= B.per);
+              CHECK(B.units * (uint64_t)B.enum_reps <= BOOT_SUBSETS_PER_LAUNCH && B.table_bytes == 0);
+              CHECK((B.enum_reps == 1 && B.steps == 1) ||
+                    B.units * (uint64_t)B.enum_reps * B.steps * mrows * mrows <= BOOT_GROUPS_WORK_PER_LAUNCH);
               ++n_ok;
             }
           }
@@ -141,6 +156,9 @@ int main() {
     CHECK(boot_groups_inter_plan(1, 1, 1, 65, 1, 1, 0, 0, 0, P) && boot_groups_inter_plan(1, 1, 1, 40, 33, 27, 0, 6, 0, P));
     CHECK(boot_groups_inter_plan(0, 1, 1, 8, 2, 1, 0, 1, 0, P) && boot_groups_inter_plan(1, 1, 1, 8, 2, 1, 0, 1, -1, P));
     CHECK(!boot_groups_inter_plan(1, 1, 1, 8, 2, 1, 0, 1, 0, P));
+    CHECK(boot_groups_best_plan(1, 1, 1, 65, 1, 1, 0, 0, 0, P) && boot_groups_best_plan(1, 1, 1, 40, 33, 27, 0, 6, 0, P));
+    CHECK(boot_groups_best_plan(0, 1, 1, 8, 2, 1, 0, 1, 0, P) && boot_groups_best_plan(1, 1, 1, 8, 2, 1, 0, 1, -1, P));
+    CHECK(boot_groups_best_plan(1, 1, 1, 8, 2, 3, 0, 0, 0, P) && !boot_groups_best_plan(1, 1, 1, 8, 2, 1, 0, 1, 0, P));
     CHECK(boot_inter_plan(0, 1, 1, 1, 0, P) && boot_inter_plan(1, 0, 1, 1, 0, P) && boot_inter_plan(1, 1, 1ll << 31, 1, 0, P));
     CHECK(boot_inter_plan(1, 1, 1, 33, 0, P) && boot_inter_plan(1, 1, 1, 0, 0, P) && boot_inter_plan(1, 1, 1, 1, -1, P));
     CHECK(boot_best_plan(0, 1, 1, 1, 0, P) && boot_best_plan(1, 0, 1, 1, 0, P) && boot_best_plan(1, 1, 1ll << 31, 1, 0, P));
@@ -157,6 +175,13 @@ int main() {
         CHECK(boot_groups_plan(1, 1, 1, p, g, g - 6, 0, 6, 0, Q) == nullptr && Q.steps == I.steps && Q.units == I.units);
         CHECK(I.units * (uint64_t)I.enum_reps * I.steps <= BOOT_SUBSETS_PER_LAUNCH && I.enum_reps >= 1);
         CHECK(I.block == 1 || I.block * I.rep_bytes + I.table_bytes <= BOOT_BLOCK_BYTES);
+        BootPlan B;
+        CHECK(boot_groups_best_plan(R, N, M, p, g, g - 6, 0, 6, block, B) == nullptr && B.units == Q.units);
+        CHECK(B.per <= BOOT_GROUPS_BEST_MAX_PER && B.steps >= 1 && B.steps <= B.per && B.enum_reps >= 1);
+        CHECK(B.units * (uint64_t)B.enum_reps <= BOOT_SUBSETS_PER_LAUNCH);
+        CHECK((B.enum_reps == 1 && B.steps == 1) ||
+              B.units * (uint64_t)B.enum_reps * B.steps * 36 * 36 <= BOOT_GROUPS_WORK_PER_LAUNCH);   // rows: 7 + 59 / 2
+        CHECK(B.block == 1 || B.block * B.rep_bytes <= BOOT_BLOCK_BYTES);
         ++n_ok;
       }
     }
