@@ -270,9 +270,12 @@ __global__ __launch_bounds__(64) void multi_enum_kernel(MultiArgs a, uint64_t s0
     const bool mine = lane < nh && ((hi >> lane) & 1ull);
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
+      // The contraction is spelled out: left to the compiler, c_own += wc v became an fma in the one slot (7) where c
+      // was not kept in a register and a multiply and an add in the others, and a response's bits depended on its slot.
+#pragma clang fp contract(off)
       const double c = wc * v[r];
       c_own[r] += c;
-      b_own[r] += wbk * v[r];
+      b_own[r] = __builtin_fma(wbk, v[r], b_own[r]);
       if (nh > 0) {                            // the same for the whole wave
         const double tot = wave_sum(c);
         if (mine) h_own[r] += tot;

@@ -304,9 +304,12 @@ __global__ __launch_bounds__(NT) void multi_groups_enum_kernel(MultiGroupArgs a,
       const bool mine = lane < gh && ((hi >> lane) & 1ull);
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
+        // The contraction is spelled out, as in k_multi.hip: left to the compiler, c_own += wc v became an fma in the
+        // slot where c was not kept in a register and a multiply and an add in the other.
+#pragma clang fp contract(off)
         const double c = wc * v[r];
         c_own[r] += c;
-        b_own[r] += wbk * v[r];
+        b_own[r] = __builtin_fma(wbk, v[r], b_own[r]);
         if (gh > 0) {                          // the same for the whole wave
           const double tot = wave_sum(c);
           if (mine) h_own[r] += tot;

@@ -108,11 +108,11 @@ def test_p27_two_launches(engine):
 def block_game(sizes, seed):
     """A reduced problem whose G and H are block diagonal after a permutation of the features: the game is a sum of
     games on the blocks, so the index vanishes between blocks and inside a block is that of the block's own game (the
-    other features are dummies there).  Returns the problem and the expected raw index."""
+    other features are dummies there), as is phi.  Returns the problem, the expected raw index and the expected phi."""
     rng = np.random.default_rng(seed)
     p = sum(sizes)
     G, H, g, h = np.zeros((p, p)), np.zeros((p, p)), rng.standard_normal(p), rng.standard_normal(p)
-    want = np.zeros((p, p))
+    want, want_phi = np.zeros((p, p)), np.zeros(p)
     perm = rng.permutation(p)
     yy = 8.0 * p
     at = 0
@@ -124,19 +124,21 @@ def block_game(sizes, seed):
         H[np.ix_(idx, idx)] = B.T @ B
         sub = np.ix_(idx, idx)
         want[sub] = exact_interactions(G[sub], g[idx], H[sub], h[idx], yy)
-    return (G, g, H, h, yy), want
+        want_phi[idx] = exact_shapley(G[sub], g[idx], H[sub], h[idx], yy)
+    return (G, g, H, h, yy), want, want_phi
 
 
 @pytest.mark.parametrize("sizes", [(9, 9), (8, 7, 5), (9, 9, 9)], ids=["p18", "p20", "p27"])
 def test_block_games_beyond_the_oracle(engine, sizes):
     """Every pair checked at p = 18, 20 and 27 -- second slot, two subsets a unit, two launches -- at the price of three
     small oracles."""
-    (G, g, H, h, yy), want = block_game(sizes, seed=sum(sizes))
+    (G, g, H, h, yy), want, want_phi = block_game(sizes, seed=sum(sizes))
     engine.load_reduced(G, g, float(g @ np.linalg.solve(G, g)) + 1.0, yy, H=H, h=h)
     phi, raw, info = engine.subsets_interactions()
     assert info == 0
     np.testing.assert_allclose(raw, want, **ORACLE_TOL)
-    assert np.abs(want).max() > 1e-5
+    np.testing.assert_allclose(phi, want_phi, **ORACLE_TOL)
+    assert np.abs(want).max() > 1e-5 and np.abs(want_phi).max() > 1e-3
 
 
 @pytest.mark.parametrize("p", [9, 20, 27])
