@@ -92,22 +92,31 @@ struct BootWork {
   }
 };
 
+// The reduced form of m responses on one design: the shared G and H, one g and h per response and the test responses'
+// squared norms, on the host as they were stored (the *_get_gram entry points) and G, H, g, h on the device.  A member of
+// MultiWork and MultiLiftWork; the permutation test reaches it through its MultiWork.  reduced_store fills it.
+struct ReducedForm {
+  int p = 0, m = 0;
+  std::vector<double> Gh, Hh, gh, hh, yyh; // [p][p], [p][p], [m][p], [m][p], [m]
+  DevBuf<double> G, H, g, h;               // the first four on the device
+  void release() { dev_free(G); dev_free(H); dev_free(g); dev_free(h); }
+};
+
 // What the multi-response enumeration keeps (lsspa_multi_load / lsspa_multi_set_reduced .. lsspa_multi_free): the shared
 // G and H, one g, h and 1 / ||y||^2 per response, the buffers of one block of responses and the last call's timing.
 // Nothing of the loaded problem, the sampling path, the exact enumerations' or the bootstrap's state is in here.
 struct MultiWork {
   bool loaded = false;
-  int p = 0, m = 0;
-  DevBuf<double> G, H, g, h, inv_yy;       // [p][p], [p][p], [m][p], [m][p], [m]
+  ReducedForm rf;
+  DevBuf<double> inv_yy;                   // [m]
   DevBuf<double> w, part, out, vals;       // Shapley weights, partial table of a block, its column sums, debug values
   DevBuf<uint64_t> masks;
   DevBuf<int32_t> info, tab;               // tab: the layout of the last grouped call (GroupLayout::tab)
-  std::vector<double> Gh, Hh, gh, hh, yyh; // the same on the host (lsspa_multi_get_gram)
   double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
-    dev_free(G); dev_free(H); dev_free(g); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(part); dev_free(out);
-    dev_free(vals); dev_free(masks); dev_free(info); dev_free(tab);
+    rf.release(); dev_free(inv_yy); dev_free(w); dev_free(part); dev_free(out); dev_free(vals);
+    dev_free(masks); dev_free(info); dev_free(tab);
     loaded = false;
   }
 };
@@ -120,21 +129,20 @@ struct MultiWork {
 // vectors and the first m g entries of (mean, M2) are [m][g], and perms holds the expanded rows of a launch.
 struct MultiLiftWork {
   bool loaded = false;
-  int p = 0, m = 0;
+  ReducedForm rf;
   int ng = 0;                              // groups of the player map (0: none)
   PlayerMap map;
   DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
   std::vector<int32_t> rows;               // a launch's expanded rows on the host
-  int sd() const { return ng ? ng : p; }     // the dimension of a sample's lift vector
+  int sd() const { return ng ? ng : rf.p; }     // the dimension of a sample's lift vector
   double aug[2] = {1.0, 1.0};              // diagonal of the augmented rows (MultiLiftArgs::aug)
-  DevBuf<double> G, H, g, h, yy;           // [p][p], [p][p], [m][p], [m][p], [m]
+  DevBuf<double> yy;                       // [m]
   DevBuf<double> lifts, mean, M2;          // [samples of a launch][m][p]; the running state [m][p]
   DevBuf<int32_t> perms, info;             // [samples of a launch][p]; the info word
   int64_t n = 0;                           // samples folded into (mean, M2)
-  std::vector<double> Gh, Hh, gh, hh, yyh; // the reduced form on the host (lsspa_multi_lift_get_gram)
   double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
   void release() {
-    dev_free(G); dev_free(H); dev_free(g); dev_free(h); dev_free(yy); dev_free(lifts); dev_free(mean); dev_free(M2);
+    rf.release(); dev_free(yy); dev_free(lifts); dev_free(mean); dev_free(M2);
     dev_free(perms); dev_free(info); dev_free(pl_off); dev_free(pl_cols);
     loaded = false;
     n = 0;
@@ -158,9 +166,7 @@ struct PermWork {
   size_t pin_count[2][2] = {{0, 0}, {0, 0}};
   DevBuf<double> part0, part1;             // [slices][ceil(block / 16)][cb][256]
   DevBuf<double> obs_g, obs_h;             // [p] the observed g, h on the device
-  MultiWork mw;                            // G, H; g, h, inv_yy of one block of replicates
-  std::vector<double> Gh, Hh, gh, hh;      // the reduced form on the host (lsspa_perm_get_gram)
-  double yy = 0.0;
+  MultiWork mw;                            // the reduced form (m = 1); g, h, inv_yy of one block of replicates
   double ms[4] = {0.0, 0.0, 0.0, 0.0};     // last run: draw (host), upload (host), X^T y kernels, enumeration
   DevBuf<double>& X(int s) { return s ? X1 : X0; }
   DevBuf<double>& y(int s) { return s ? y1 : y0; }
@@ -3932,6 +3938,86 @@ int lsspa_debug_owen_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* 
 
 }  // extern "C"
 
+// ---- shared by the entry-point families below: rows onto the device, the reduced form of many responses -------------
+namespace {
+
+// The n rows of one side (X [n][ld], y [n]; dtype, location as lsspa_reduce's) to the caller's pack launch
+// pack(src_x, src_y, rows, first_row) -> hipError_t, whose sources are on the device.  Rows on the device go in one
+// launch.  Host rows go through the staging buffers, at most ~64 MB of X at a time, by plain copies on the context's
+// stream; the stream is waited for after every chunk (the buffers are reused), not after rows from the device.  The
+// staging buffers are the caller's to free.
+template <typename Pack>
+int load_rows(lsspa_ctx* ctx, DevBuf<char>& stage_x, DevBuf<char>& stage_y, const void* X, int64_t ld, const void* y,
+              int64_t n, int32_t p, int32_t dtype, int32_t location, Pack&& pack) {
+  if (location == LSSPA_DEVICE) {
+    HIPCHK(pack(X, y, n, (int64_t)0));
+    return LSSPA_OK;
+  }
+  const size_t esz = dtype == LSSPA_F32 ? 4 : 8;
+  const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n, (64ll << 20) / (int64_t)(ld * esz)));
+  TRY(dev_alloc(ctx, stage_x, (size_t)rows * ld * esz));
+  TRY(dev_alloc(ctx, stage_y, (size_t)rows * esz));
+  for (int64_t r0 = 0; r0 < n; r0 += rows) {
+    const int64_t nr = std::min(rows, n - r0);
+    const size_t xbytes = ((size_t)(nr - 1) * ld + p) * esz;     // the caller's last row ends with its column p - 1
+    HIPCHK(hipMemcpyAsync(stage_x.ptr, (const char*)X + (size_t)r0 * ld * esz, xbytes, hipMemcpyHostToDevice,
+                          ctx->stream));
+    HIPCHK(hipMemcpyAsync(stage_y.ptr, (const char*)y + (size_t)r0 * esz, (size_t)nr * esz, hipMemcpyHostToDevice,
+                          ctx->stream));
+    HIPCHK(pack(stage_x.ptr, stage_y.ptr, nr, r0));
+    HIPCHK(hipStreamSynchronize(ctx->stream));     // the staging buffers are reused
+  }
+  return LSSPA_OK;
+}
+
+// Every test response has a squared norm that is positive and finite; `text`: the caller's refusal, a format that may
+// take the response's index
+int reduced_check_yy(lsspa_ctx* ctx, int m, const double* yy, const char* text) {
+  for (int r = 0; r < m; ++r)
+    if (!(yy[r] > 0.0) || !std::isfinite(yy[r])) {
+      char msg[160];
+      snprintf(msg, sizeof msg, text, r);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  return LSSPA_OK;
+}
+
+// The reduced form (host arrays: G, H [p][p], g, h [m][p], yy [m], checked by reduced_check_yy) into F: the host
+// copies, then G, H, g, h onto the device, allocated in that order.  g_dev, h_dev: where g and h go on the device (the
+// permutation test keeps the observed pair beside F's, which are its replicates' slots).
+int reduced_store(lsspa_ctx* ctx, ReducedForm& F, int p, int m, const double* G, const double* g, const double* H,
+                  const double* h, const double* yy, DevBuf<double>& g_dev, DevBuf<double>& h_dev) {
+  const size_t pp = (size_t)p * p, mp = (size_t)m * p;
+  F.Gh.assign(G, G + pp);
+  F.Hh.assign(H, H + pp);
+  F.gh.assign(g, g + mp);
+  F.hh.assign(h, h + mp);
+  F.yyh.assign(yy, yy + m);
+  TRY(dev_alloc(ctx, F.G, pp));
+  TRY(dev_alloc(ctx, F.H, pp));
+  TRY(dev_alloc(ctx, g_dev, mp));
+  TRY(dev_alloc(ctx, h_dev, mp));
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the buffers
+  HIPCHK(hipMemcpy(F.G.ptr, G, sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(F.H.ptr, H, sizeof(double) * pp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g_dev.ptr, g, sizeof(double) * mp, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h_dev.ptr, h, sizeof(double) * mp, hipMemcpyHostToDevice));
+  F.p = p;
+  F.m = m;
+  return LSSPA_OK;
+}
+
+// the *_get_gram entry points: what was stored, each array only if asked for
+void reduced_get(const ReducedForm& F, double* G, double* g, double* H, double* h, double* yy) {
+  if (G) std::copy(F.Gh.begin(), F.Gh.end(), G);
+  if (g) std::copy(F.gh.begin(), F.gh.end(), g);
+  if (H) std::copy(F.Hh.begin(), F.Hh.end(), H);
+  if (h) std::copy(F.hh.begin(), F.hh.end(), h);
+  if (yy) std::copy(F.yyh.begin(), F.yyh.end(), yy);
+}
+
+}  // namespace
+
 // ---- bootstrap of the exact attribution (k_boot.hip, boot_plan.cpp) ------------------------------------------------
 // lsspa_boot_run cuts its R replicates into blocks (boot_plan: by memory).  A block: the weights of both sides on the
 // device (counts drawn there, or the caller's rows copied), one weighted Gram pass per side, the fixed-order sum of its
@@ -3982,7 +4068,7 @@ const char* boot_rows_plan(const BootWork& B, int64_t R, int64_t block, BootPlan
 }
 
 // ecols: the width of the enumeration's partial table (players + 1; the interaction runs: subsets_inter_cols(players))
-int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, bool counts[2], bool enumerate, int ecols = 0) {
+int boot_alloc_block(lsspa_ctx* ctx, const BootPlan& P, const bool counts[2], bool enumerate, int ecols = 0) {
   BootWork& B = ctx->boot;
   const size_t blk = (size_t)P.block, c = (size_t)B.p + 1, p = (size_t)B.p;
   const size_t ec = ecols ? (size_t)ecols : c;
@@ -4133,29 +4219,13 @@ int boot_load_rows(lsspa_ctx* ctx, const BootPlan& P, const char* name, const vo
   const void* X[2] = {X_train, X_test};
   const void* y[2] = {y_train, y_test};
   const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test};
-  const size_t esz = dtype == LSSPA_F32 ? 4 : 8;
   for (int s = 0; s < 2; ++s) {
     TRY(dev_alloc(ctx, B.Z(s), (size_t)n[s] * P.ldz));
-    if (location == LSSPA_DEVICE) {
-      HIPCHK(launch_boot_pack(X[s], ld[s], y[s], n[s], p, dtype == LSSPA_F32, B.Z(s).ptr, P.ldz, 0, ctx->stream));
-      continue;
-    }
-    // host rows: through a staging buffer of at most ~64 MB, chunk by chunk (plain copies, as lsspa_reduce's)
-    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n[s], (64ll << 20) / (int64_t)(ld[s] * esz)));
-    TRY(dev_alloc(ctx, B.stage_x, (size_t)rows * ld[s] * esz));
-    TRY(dev_alloc(ctx, B.stage_y, (size_t)rows * esz));
-    for (int64_t r0 = 0; r0 < n[s]; r0 += rows) {
-      const int64_t nr = std::min(rows, n[s] - r0);
-      // the last row of the caller's array ends with its column p - 1
-      const size_t xbytes = ((size_t)(nr - 1) * ld[s] + p) * esz;
-      HIPCHK(hipMemcpyAsync(B.stage_x.ptr, (const char*)X[s] + (size_t)r0 * ld[s] * esz, xbytes, hipMemcpyHostToDevice,
-                            ctx->stream));
-      HIPCHK(hipMemcpyAsync(B.stage_y.ptr, (const char*)y[s] + (size_t)r0 * esz, (size_t)nr * esz,
-                            hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(launch_boot_pack(B.stage_x.ptr, ld[s], B.stage_y.ptr, nr, p, dtype == LSSPA_F32, B.Z(s).ptr, P.ldz, r0,
-                              ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));     // the staging buffer is reused
-    }
+    TRY(load_rows(ctx, B.stage_x, B.stage_y, X[s], ld[s], y[s], n[s], p, dtype, location,
+                  [&](const void* sx, const void* sy, int64_t nr, int64_t r0) {
+                    return launch_boot_pack(sx, ld[s], sy, nr, p, dtype == LSSPA_F32, B.Z(s).ptr, P.ldz, r0,
+                                            ctx->stream);
+                  }));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   dev_free(B.stage_x);
@@ -4254,48 +4324,123 @@ auto boot_column_sums(lsspa_ctx* ctx, const BootPlan& P, int cols) {
   };
 }
 
-// lsspa_boot_run and, with inter, lsspa_boot_interactions_run: the enumeration of k_subsets.hip over the block's
-// replicates; `name` is the entry point's
-int boot_subsets_run(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, int64_t first, const double* w_train,
-                     const double* w_test, int64_t block, double* phi, double* inter, double* r2, int32_t* info) {
+// The weights of a run: the caller's [R][n] rows of a side, or NULL and counts drawn on the device
+struct BootWeights {
+  const double* w_host[2];
+  bool counts[2];
+};
+
+// What every run does between its plan and its first allocation: the planner's refusal `why` (NULL: none) under the
+// entry point's name, the caller's weights, the device
+int boot_begin(lsspa_ctx* ctx, const char* name, const char* why, int64_t R, const double* w_train, const double* w_test,
+               BootWeights& W) {
   BootWork& B = ctx->boot;
-  char msg[240];
-  if (B.p > SUBSETS_MAX_P) {
-    snprintf(msg, sizeof msg, "%s enumerates feature subsets and takes at most p = %d features (%d loaded by "
-             "lsspa_boot_groups_load: %s attributes to groups of them)", name, SUBSETS_MAX_P, B.p,
-             inter ? "lsspa_boot_groups_interactions_run" : "lsspa_boot_groups_run");
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  BootPlan P;
-  if (const char* why = inter ? boot_inter_plan(R, B.n[0], B.n[1], B.p, block, P)
-                              : boot_plan(R, B.n[0], B.n[1], B.p, block, P)) {
+  if (why) {
+    char msg[240];
     snprintf(msg, sizeof msg, "%s: %s", name, why);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
   if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
   if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
   HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {!w_train, !w_test};
-  const int p = B.p, cols = inter ? subsets_inter_cols(p) : p + 1;
-  TRY(boot_alloc_block(ctx, P, counts, true, cols));
+  W = BootWeights{{w_train, w_test}, {!w_train, !w_test}};
+  return LSSPA_OK;
+}
+
+// labels / g of a grouped run against the loaded columns; too_many: the entry point's refusal of g > GROUPS_MAX_G
+int boot_layout(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const char* too_many, GroupLayout& L) {
+  char msg[240];
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, too_many, GROUPS_MAX_G, (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (const char* why = groups_layout(labels, ctx->boot.p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+// k_subsets.hip's view of the block's replicates from e0 on (one launch's: the kernels' second grid dimension)
+SubsetArgs boot_subset_args(const BootWork& B, const BootPlan& P, int e0) {
+  const int p = B.p;
+  SubsetArgs a{};
+  a.p = p;
+  a.q = subsets_low_features(p);
+  a.G = B.G.ptr + (size_t)e0 * p * p;
+  a.H = B.H.ptr + (size_t)e0 * p * p;
+  a.g = B.g.ptr + (size_t)e0 * p;
+  a.h = B.h.ptr + (size_t)e0 * p;
+  a.ldg = a.ldh = p;
+  a.w = B.w.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.inv_yy = B.inv_yy.ptr + e0;
+  a.info = B.info.ptr + e0;
+  a.per = P.per;
+  a.part = B.epart.ptr;
+  return a;
+}
+
+// the same of k_groups.hip, over the layout L
+GroupArgs boot_group_args(const BootWork& B, const BootPlan& P, const GroupLayout& L, int e0) {
+  const int p = B.p;
+  GroupArgs a{};
+  a.p = p; a.ng = L.ng; a.nb = L.nb;
+  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+  a.G = B.G.ptr + (size_t)e0 * p * p;
+  a.H = B.H.ptr + (size_t)e0 * p * p;
+  a.g = B.g.ptr + (size_t)e0 * p;
+  a.h = B.h.ptr + (size_t)e0 * p;
+  a.ldg = a.ldh = p;
+  a.w = B.w.ptr;
+  a.tab = B.tab.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.inv_yy_rep = B.inv_yy.ptr + e0;
+  a.info = B.info.ptr + e0;
+  a.per = P.per;
+  a.part = B.epart.ptr;
+  return a;
+}
+
+// r2 and r2_base of a replicate of a grouped run, by boot_r2_cols: the model on all p columns, and on the baseline's,
+// the layout's first nb
+struct BootGroupR2 {
+  int p, nb;
+  int all[GROUPS_MAX_P], base[GROUPS_MAX_P];
+  std::vector<double> ws;
+  BootGroupR2(int p_, const GroupLayout& L) : p(p_), nb(L.nb) {
+    for (int j = 0; j < p; ++j) all[j] = j;
+    for (int j = 0; j < nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
+  }
+  void operator()(const double* G, const double* g, const double* H, const double* h, double inv_yy, double& r2,
+                  double& r2_base) {
+    r2 = boot_r2_cols(p, all, p, G, g, H, h, inv_yy, ws);
+    r2_base = boot_r2_cols(p, base, nb, G, g, H, h, inv_yy, ws);
+  }
+};
+
+// lsspa_boot_run and, with inter, lsspa_boot_interactions_run: the enumeration of k_subsets.hip over the block's
+// replicates; `name` is the entry point's
+int boot_subsets_run(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, int64_t first, const double* w_train,
+                     const double* w_test, int64_t block, double* phi, double* inter, double* r2, int32_t* info) {
+  BootWork& B = ctx->boot;
+  const int p = B.p;
+  if (p > SUBSETS_MAX_P) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s enumerates feature subsets and takes at most p = %d features (%d loaded by "
+             "lsspa_boot_groups_load: %s attributes to groups of them)", name, SUBSETS_MAX_P, p,
+             inter ? "lsspa_boot_groups_interactions_run" : "lsspa_boot_groups_run");
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;
+  BootWeights W;
+  TRY(boot_begin(ctx, name, inter ? boot_inter_plan(R, B.n[0], B.n[1], p, block, P)
+                                  : boot_plan(R, B.n[0], B.n[1], p, block, P), R, w_train, w_test, W));
+  const int cols = inter ? subsets_inter_cols(p) : p + 1;
+  TRY(boot_alloc_block(ctx, P, W.counts, true, cols));
   TRY(boot_upload_tables(ctx, p, nullptr));
   auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
-    SubsetArgs a{};
-    a.p = p;
-    a.q = subsets_low_features(p);
-    a.G = B.G.ptr + (size_t)e0 * p * p;
-    a.H = B.H.ptr + (size_t)e0 * p * p;
-    a.g = B.g.ptr + (size_t)e0 * p;
-    a.h = B.h.ptr + (size_t)e0 * p;
-    a.ldg = a.ldh = p;
-    a.w = B.w.ptr;
-    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-    a.inv_yy = B.inv_yy.ptr + e0;
-    a.info = B.info.ptr + e0;
-    a.per = P.per;
-    a.part = B.epart.ptr;
-    return launch_subsets_enum(a, P.units, s0, s1, inter != nullptr, ctx->stream, ne);
+    return launch_subsets_enum(boot_subset_args(B, P, e0), P.units, s0, s1, inter != nullptr, ctx->stream, ne);
   };
   auto emit = [&](int64_t r, const double* out, const double* G, const double* g, const double* H, const double* h,
                   double inv_yy) {
@@ -4303,7 +4448,8 @@ int boot_subsets_run(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed,
     if (inter) exact_inter_matrix(out, p, nullptr, inter + (size_t)r * p * p);
     r2[r] = boot_r2(p, G, g, H, h, inv_yy);
   };
-  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, cols, launch, boot_column_sums(ctx, P, cols), emit, info);
+  return boot_run_blocks(ctx, P, R, seed, first, W.w_host, cols, cols, launch, boot_column_sums(ctx, P, cols), emit,
+                         info);
 }
 
 // lsspa_boot_groups_run and, with inter, lsspa_boot_groups_interactions_run: the enumeration of k_groups.hip
@@ -4311,219 +4457,124 @@ int boot_groups_run(lsspa_ctx* ctx, const char* name, const int32_t* labels, int
                     int64_t first, const double* w_train, const double* w_test, int64_t block, double* phi,
                     double* inter, double* r2, double* r2_base, int32_t* info) {
   BootWork& B = ctx->boot;
-  char msg[200];
-  if (g > GROUPS_MAX_G) {
-    snprintf(msg, sizeof msg, "the bootstrap over groups of columns takes at most g = %d groups (%d given)", GROUPS_MAX_G,
-             (int)g);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
   GroupLayout L;
-  if (const char* why = groups_layout(labels, B.p, g, L)) {
-    snprintf(msg, sizeof msg, "group labels: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
+  TRY(boot_layout(ctx, labels, g, "the bootstrap over groups of columns takes at most g = %d groups (%d given)", L));
   BootPlan P;
-  if (const char* why = inter ? boot_groups_inter_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)
-                              : boot_groups_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)) {
-    snprintf(msg, sizeof msg, "%s: %s", name, why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
-  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {!w_train, !w_test};
-  const int p = B.p, ng = L.ng, cols = inter ? subsets_inter_cols(ng) : ng + 1;
-  TRY(boot_alloc_block(ctx, P, counts, true, cols));
+  BootWeights W;
+  TRY(boot_begin(ctx, name, inter ? boot_groups_inter_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)
+                                  : boot_groups_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P),
+                 R, w_train, w_test, W));
+  const int ng = L.ng, cols = inter ? subsets_inter_cols(ng) : ng + 1;
+  TRY(boot_alloc_block(ctx, P, W.counts, true, cols));
   TRY(boot_upload_tables(ctx, ng, L.tab));
-  std::vector<double> r2_ws;
-  int all[GROUPS_MAX_P];       // the full model's columns; the baseline's are the layout's first nb
-  for (int j = 0; j < p; ++j) all[j] = j;
-  int base[GROUPS_MAX_P];
-  for (int j = 0; j < L.nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
+  BootGroupR2 fit(B.p, L);
   auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
-    GroupArgs a{};
-    a.p = p; a.ng = ng; a.nb = L.nb;
-    a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
-    a.G = B.G.ptr + (size_t)e0 * p * p;
-    a.H = B.H.ptr + (size_t)e0 * p * p;
-    a.g = B.g.ptr + (size_t)e0 * p;
-    a.h = B.h.ptr + (size_t)e0 * p;
-    a.ldg = a.ldh = p;
-    a.w = B.w.ptr;
-    a.tab = B.tab.ptr;
-    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-    a.inv_yy_rep = B.inv_yy.ptr + e0;
-    a.info = B.info.ptr + e0;
-    a.per = P.per;
-    a.part = B.epart.ptr;
-    return launch_groups_enum(a, P.units, s0, s1, inter != nullptr, ctx->stream, ne);
+    return launch_groups_enum(boot_group_args(B, P, L, e0), P.units, s0, s1, inter != nullptr, ctx->stream, ne);
   };
   auto emit = [&](int64_t r, const double* out, const double* G, const double* gv, const double* H, const double* h,
                   double inv_yy) {
     for (int k = 0; k < ng; ++k) phi[r * ng + L.gid[k]] = out[k] - out[ng];
     if (inter) exact_inter_matrix(out, ng, L.gid, inter + (size_t)r * ng * ng);
-    r2[r] = boot_r2_cols(p, all, p, G, gv, H, h, inv_yy, r2_ws);
-    r2_base[r] = boot_r2_cols(p, base, L.nb, G, gv, H, h, inv_yy, r2_ws);
+    fit(G, gv, H, h, inv_yy, r2[r], r2_base[r]);
   };
-  return boot_run_blocks(ctx, P, R, seed, first, w_host, cols, cols, launch, boot_column_sums(ctx, P, cols), emit, info);
+  return boot_run_blocks(ctx, P, R, seed, first, W.w_host, cols, cols, launch, boot_column_sums(ctx, P, cols), emit,
+                         info);
 }
 
-// lsspa_boot_best_run: subsets_best_kernel's replicates over the block's reduced problems.  The table: values in B.epart
-// [enum_reps][units][p + 1], (mask, found) in B.ebest [enum_reps][units][p + 1][2]; a replicate's row of B.eout is
-// 2 (p + 1) doubles wide, the best values and behind them the p + 1 (mask, found) pairs as launch_subsets_best_reduce
-// writes them (8 bytes a pair).
-int boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train, const double* w_test,
-                  int64_t block, uint32_t include, double* v, uint32_t* masks, uint8_t* found, double* r2,
-                  int32_t* info) {
+// What the two best-subset runs do after their plan, over n players (features, or groups with their table `tab`).  The
+// table: values in B.epart [enum_reps][units][n + 1], (mask, found) in B.ebest [enum_reps][units][n + 1][2], cleared
+// before a set of replicates' first launch; a replicate's row of B.eout is 2 (n + 1) doubles wide, the best values and
+// behind them the n + 1 (mask, found) pairs as launch_subsets_best_reduce writes them (8 bytes a pair).
+//   launch(e0, ne, s0, s1): as boot_run_blocks', the kernel that also writes B.ebest;
+//   fit(r, G, g, H, h, inv_yy): the run's r2 entries of replicate r.
+template <typename Launch, typename Fit>
+int boot_best_blocks(lsspa_ctx* ctx, const BootPlan& P, const BootWeights& W, int64_t R, uint64_t seed, int64_t first,
+                     int n, const int32_t* tab, Launch&& launch, Fit&& fit, double* v, uint32_t* masks, uint8_t* found,
+                     int32_t* info) {
   BootWork& B = ctx->boot;
-  char msg[240];
-  if (B.p > SUBSETS_MAX_P) {
-    snprintf(msg, sizeof msg, "lsspa_boot_best_run enumerates feature subsets and takes at most p = %d features (%d "
-             "loaded by lsspa_boot_groups_load)", SUBSETS_MAX_P, B.p);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  const int p = B.p, p1 = p + 1;
-  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
-  BootPlan P;
-  if (const char* why = boot_best_plan(R, B.n[0], B.n[1], p, block, P)) {
-    snprintf(msg, sizeof msg, "lsspa_boot_best_run: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
-  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {!w_train, !w_test};
-  TRY(boot_alloc_block(ctx, P, counts, true, p1));
-  TRY(dev_alloc(ctx, B.eout, (size_t)P.block * 2 * p1));
-  const size_t rows = (size_t)P.units * p1;                // entries of one replicate's table
+  const int n1 = n + 1;
+  TRY(boot_alloc_block(ctx, P, W.counts, true, n1));
+  TRY(dev_alloc(ctx, B.eout, (size_t)P.block * 2 * n1));
+  const size_t rows = (size_t)P.units * n1;                // entries of one replicate's table
   TRY(dev_alloc(ctx, B.ebest, 2 * rows * (size_t)P.enum_reps));
-  TRY(boot_upload_tables(ctx, p, nullptr));
-  auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
+  TRY(boot_upload_tables(ctx, n, tab));
+  auto cleared = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
     if (s0 == 0) {      // a new set of replicates: nothing found yet
       hipError_t e = hipMemsetAsync(B.ebest.ptr, 0, sizeof(uint32_t) * 2 * rows * (size_t)ne, ctx->stream);
       if (e != hipSuccess) return e;
     }
-    SubsetArgs a{};
-    a.p = p;
-    a.q = subsets_low_features(p);
-    a.G = B.G.ptr + (size_t)e0 * p * p;
-    a.H = B.H.ptr + (size_t)e0 * p * p;
-    a.g = B.g.ptr + (size_t)e0 * p;
-    a.h = B.h.ptr + (size_t)e0 * p;
-    a.ldg = a.ldh = p;
-    a.w = B.w.ptr;
-    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-    a.inv_yy = B.inv_yy.ptr + e0;
-    a.info = B.info.ptr + e0;
-    a.per = P.per;
-    a.part = B.epart.ptr;
-    return launch_subsets_best(a, P.units, s0, s1, include, B.ebest.ptr, ctx->stream, ne);
+    return launch(e0, ne, s0, s1);
   };
   auto reduce = [&](int e0, int ne) {
-    double* row = B.eout.ptr + (size_t)e0 * 2 * p1;
-    return launch_subsets_best_reduce(B.epart.ptr, B.ebest.ptr, (int64_t)P.units, p, row,
-                                      reinterpret_cast<uint32_t*>(row + p1), ctx->stream, ne, 2 * p1);
+    double* row = B.eout.ptr + (size_t)e0 * 2 * n1;
+    return launch_subsets_best_reduce(B.epart.ptr, B.ebest.ptr, (int64_t)P.units, n, row,
+                                      reinterpret_cast<uint32_t*>(row + n1), ctx->stream, ne, 2 * n1);
   };
   auto emit = [&](int64_t r, const double* out, const double* G, const double* g, const double* H, const double* h,
                   double inv_yy) {
-    uint32_t mf[2 * (SUBSETS_MAX_P + 1)];
-    std::memcpy(mf, out + p1, sizeof(uint32_t) * 2 * p1);
-    for (int k = 0; k <= p; ++k) {
+    uint32_t mf[2 * (EXACT_MAX_PLAYERS + 1)];
+    std::memcpy(mf, out + n1, sizeof(uint32_t) * 2 * n1);
+    for (int k = 0; k <= n; ++k) {
       const bool f = mf[2 * k + 1] != 0u;
-      found[r * p1 + k] = f ? 1 : 0;
-      masks[r * p1 + k] = f ? mf[2 * k] : 0u;
-      v[r * p1 + k] = f ? out[k] : std::nan("");
+      found[r * n1 + k] = f ? 1 : 0;
+      masks[r * n1 + k] = f ? mf[2 * k] : 0u;
+      v[r * n1 + k] = f ? out[k] : std::nan("");
     }
+    fit(r, G, g, H, h, inv_yy);
+  };
+  return boot_run_blocks(ctx, P, R, seed, first, W.w_host, n1, 2 * n1, cleared, reduce, emit, info);
+}
+
+// lsspa_boot_best_run: subsets_best_kernel's replicates over the block's reduced problems
+int boot_best_run(lsspa_ctx* ctx, int64_t R, uint64_t seed, int64_t first, const double* w_train, const double* w_test,
+                  int64_t block, uint32_t include, double* v, uint32_t* masks, uint8_t* found, double* r2,
+                  int32_t* info) {
+  BootWork& B = ctx->boot;
+  const int p = B.p;
+  if (p > SUBSETS_MAX_P) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "lsspa_boot_best_run enumerates feature subsets and takes at most p = %d features (%d "
+             "loaded by lsspa_boot_groups_load)", SUBSETS_MAX_P, p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
+  BootPlan P;
+  BootWeights W;
+  TRY(boot_begin(ctx, "lsspa_boot_best_run", boot_best_plan(R, B.n[0], B.n[1], p, block, P), R, w_train, w_test, W));
+  auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
+    return launch_subsets_best(boot_subset_args(B, P, e0), P.units, s0, s1, include, B.ebest.ptr, ctx->stream, ne);
+  };
+  auto fit = [&](int64_t r, const double* G, const double* g, const double* H, const double* h, double inv_yy) {
     r2[r] = boot_r2(p, G, g, H, h, inv_yy);
   };
-  return boot_run_blocks(ctx, P, R, seed, first, w_host, p1, 2 * p1, launch, reduce, emit, info);
+  return boot_best_blocks(ctx, P, W, R, seed, first, p, nullptr, launch, fit, v, masks, found, info);
 }
 
 // lsspa_boot_groups_best_run: groups_best_kernel's replicates over the block's reduced problems, boot_groups_run's in
-// everything before the enumeration.  The table and a replicate's row of B.eout as boot_best_run's, with the g groups as
-// the players: values in B.epart [enum_reps][units][g + 1], (caller mask, found) in B.ebest beside it.
+// everything before the enumeration, with the g groups as the players and the caller's masks in B.ebest
 static_assert(BOOT_GROUPS_BEST_MAX_PER == (1ull << (GROUPS_BEST_CLASSES - 1)),
               "boot_groups_best_plan's bound on per is groups_best_kernel's size classes");
 int boot_groups_best_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, uint64_t seed, int64_t first,
                          const double* w_train, const double* w_test, int64_t block, double* u, uint32_t* masks,
                          uint8_t* found, double* r2, double* r2_base, int32_t* info) {
   BootWork& B = ctx->boot;
-  char msg[240];
-  if (g > GROUPS_MAX_G) {      // lsspa_groups_best's messages (groups_args)
-    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
-             (int)g);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  GroupLayout L;
-  if (const char* why = groups_layout(labels, B.p, g, L)) {
-    snprintf(msg, sizeof msg, "group labels: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
+  GroupLayout L;      // lsspa_groups_best's messages (groups_args)
+  TRY(boot_layout(ctx, labels, g, "exact attribution over groups takes at most g = %d groups (%d given)", L));
   BootPlan P;
-  if (const char* why = boot_groups_best_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P)) {
-    snprintf(msg, sizeof msg, "lsspa_boot_groups_best_run: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
-  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {!w_train, !w_test};
-  const int p = B.p, ng = L.ng, g1 = ng + 1;
-  TRY(boot_alloc_block(ctx, P, counts, true, g1));
-  TRY(dev_alloc(ctx, B.eout, (size_t)P.block * 2 * g1));
-  const size_t rows = (size_t)P.units * g1;                // entries of one replicate's table
-  TRY(dev_alloc(ctx, B.ebest, 2 * rows * (size_t)P.enum_reps));
-  TRY(boot_upload_tables(ctx, ng, L.tab));
-  std::vector<double> r2_ws;
-  int all[GROUPS_MAX_P];       // the full model's columns; the baseline's are the layout's first nb
-  for (int j = 0; j < p; ++j) all[j] = j;
-  int base[GROUPS_MAX_P];
-  for (int j = 0; j < L.nb; ++j) base[j] = L.tab[GROUPS_TAB_COLS + j];
+  BootWeights W;
+  TRY(boot_begin(ctx, "lsspa_boot_groups_best_run",
+                 boot_groups_best_plan(R, B.n[0], B.n[1], B.p, L.ng, L.gh, L.nb, L.ql, block, P), R, w_train, w_test,
+                 W));
+  BootGroupR2 both(B.p, L);
   auto launch = [&](int e0, int ne, uint64_t s0, uint64_t s1) {
-    if (s0 == 0) {      // a new set of replicates: nothing found yet
-      hipError_t e = hipMemsetAsync(B.ebest.ptr, 0, sizeof(uint32_t) * 2 * rows * (size_t)ne, ctx->stream);
-      if (e != hipSuccess) return e;
-    }
-    GroupArgs a{};
-    a.p = p; a.ng = ng; a.nb = L.nb;
-    a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
-    a.G = B.G.ptr + (size_t)e0 * p * p;
-    a.H = B.H.ptr + (size_t)e0 * p * p;
-    a.g = B.g.ptr + (size_t)e0 * p;
-    a.h = B.h.ptr + (size_t)e0 * p;
-    a.ldg = a.ldh = p;
-    a.w = B.w.ptr;
-    a.tab = B.tab.ptr;
-    a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-    a.inv_yy_rep = B.inv_yy.ptr + e0;
-    a.info = B.info.ptr + e0;
-    a.per = P.per;
-    a.part = B.epart.ptr;
-    return launch_groups_best(a, L.gid, P.units, s0, s1, B.ebest.ptr, ctx->stream, ne);
+    return launch_groups_best(boot_group_args(B, P, L, e0), L.gid, P.units, s0, s1, B.ebest.ptr, ctx->stream, ne);
   };
-  auto reduce = [&](int e0, int ne) {
-    double* row = B.eout.ptr + (size_t)e0 * 2 * g1;
-    return launch_subsets_best_reduce(B.epart.ptr, B.ebest.ptr, (int64_t)P.units, ng, row,
-                                      reinterpret_cast<uint32_t*>(row + g1), ctx->stream, ne, 2 * g1);
+  auto fit = [&](int64_t r, const double* G, const double* gv, const double* H, const double* h, double inv_yy) {
+    both(G, gv, H, h, inv_yy, r2[r], r2_base[r]);
   };
-  auto emit = [&](int64_t r, const double* out, const double* G, const double* gv, const double* H, const double* h,
-                  double inv_yy) {
-    uint32_t mf[2 * (GROUPS_MAX_G + 1)];
-    std::memcpy(mf, out + g1, sizeof(uint32_t) * 2 * g1);
-    for (int k = 0; k <= ng; ++k) {
-      const bool f = mf[2 * k + 1] != 0u;
-      found[r * g1 + k] = f ? 1 : 0;
-      masks[r * g1 + k] = f ? mf[2 * k] : 0u;
-      u[r * g1 + k] = f ? out[k] : std::nan("");
-    }
-    r2[r] = boot_r2_cols(p, all, p, G, gv, H, h, inv_yy, r2_ws);
-    r2_base[r] = boot_r2_cols(p, base, L.nb, G, gv, H, h, inv_yy, r2_ws);
-  };
-  return boot_run_blocks(ctx, P, R, seed, first, w_host, g1, 2 * g1, launch, reduce, emit, info);
+  return boot_best_blocks(ctx, P, W, R, seed, first, L.ng, L.tab, launch, fit, u, masks, found, info);
 }
+
 
 }  // namespace
 
@@ -4758,21 +4809,14 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
   TRY(boot_need_loaded(ctx));
   BootWork& B = ctx->boot;
   BootPlan P;
-  if (const char* why = boot_rows_plan(B, R, 0, P)) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "lsspa_boot_debug_grams: %s", why);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  if (w_train) TRY(boot_check_weights(ctx, w_train, R, B.n[0], "w_train"));
-  if (w_test) TRY(boot_check_weights(ctx, w_test, R, B.n[1], "w_test"));
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* const w_host[2] = {w_train, w_test};
-  bool counts[2] = {false, false};
-  TRY(boot_alloc_block(ctx, P, counts, false));
+  BootWeights W;
+  TRY(boot_begin(ctx, "lsspa_boot_debug_grams", boot_rows_plan(B, R, 0, P), R, w_train, w_test, W));
+  W.counts[0] = W.counts[1] = false;     // a side without weights gets ones, not counts
+  TRY(boot_alloc_block(ctx, P, W.counts, false));
   const size_t cc = (size_t)(B.p + 1) * (B.p + 1);
   for (int64_t b0 = 0; b0 < R; b0 += P.block) {
     const int nb = (int)std::min<int64_t>(P.block, R - b0);
-    TRY(boot_block_sums(ctx, P, w_host, true, 0, 0, b0, nb, nullptr));
+    TRY(boot_block_sums(ctx, P, W.w_host, true, 0, 0, b0, nb, nullptr));
     if (S_train)
       HIPCHK(hipMemcpyAsync(S_train + b0 * cc, B.S0.ptr, sizeof(double) * nb * cc, hipMemcpyDeviceToHost, ctx->stream));
     if (S_test)
@@ -4805,19 +4849,25 @@ constexpr size_t MULTI_TABLE_BYTES = 256ull << 20;     // the partial table of a
 constexpr int64_t MULTI_MAX_COLS = 32767;              // p + m
 constexpr int64_t MULTI_MAX_CHUNKS = 8191;             // chunks * MULTI_RB is launch_subsets_reduce's replicate count
 
-int multi_limits(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
-  char msg[200];
-  if (p < 1 || p > GROUPS_MAX_P) {       // (p > MULTI_MAX_P: for lsspa_multi_groups_shapley only, multi_need_ungrouped)
-    snprintf(msg, sizeof msg, "%s takes 1 <= p <= %d columns, of which the ungrouped enumeration takes p <= %d "
-             "(%lld given)", name, GROUPS_MAX_P, MULTI_MAX_P, (long long)p);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
+// m of a load against p (the loads of lsspa_multi_* and lsspa_multi_lift_*, after their own limit on p)
+int multi_cols_limit(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
   if (m < 1 || p + m > MULTI_MAX_COLS) {
+    char msg[200];
     snprintf(msg, sizeof msg, "%s takes m >= 1 responses with p + m <= %lld (p = %lld, m = %lld given)", name,
              (long long)MULTI_MAX_COLS, (long long)p, (long long)m);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
   return LSSPA_OK;
+}
+
+int multi_limits(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
+  if (p < 1 || p > GROUPS_MAX_P) {       // (p > MULTI_MAX_P: for lsspa_multi_groups_shapley only, multi_need_ungrouped)
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s takes 1 <= p <= %d columns, of which the ungrouped enumeration takes p <= %d "
+             "(%lld given)", name, GROUPS_MAX_P, MULTI_MAX_P, (long long)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return multi_cols_limit(ctx, name, p, m);
 }
 
 int multi_need_loaded(lsspa_ctx* ctx) {
@@ -4828,10 +4878,10 @@ int multi_need_loaded(lsspa_ctx* ctx) {
 
 // the enumeration over features takes p <= MULTI_MAX_P of the p <= GROUPS_MAX_P columns a load accepts
 int multi_need_ungrouped(lsspa_ctx* ctx, const char* name) {
-  if (ctx->multi.p > MULTI_MAX_P) {
+  if (ctx->multi.rf.p > MULTI_MAX_P) {
     char msg[240];
     snprintf(msg, sizeof msg, "%s enumerates all 2^p feature subsets and takes at most p = %d features (%d loaded); "
-             "lsspa_multi_groups_shapley attributes to groups of up to %d columns", name, MULTI_MAX_P, ctx->multi.p,
+             "lsspa_multi_groups_shapley attributes to groups of up to %d columns", name, MULTI_MAX_P, ctx->multi.rf.p,
              GROUPS_MAX_P);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
@@ -4852,40 +4902,19 @@ int multi_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
                 const double* yy) {
   MultiWork& W = ctx->multi;
   W.loaded = false;
-  char msg[160];
-  for (int r = 0; r < m; ++r)
-    if (!(yy[r] > 0.0) || !std::isfinite(yy[r])) {
-      snprintf(msg, sizeof msg, "column %d of Y_test is identically zero (or NaN)", r);
-      return ctx->fail(LSSPA_ERR_ARG, msg);
-    }
-  const size_t pp = (size_t)p * p, mp = (size_t)m * p;
-  W.Gh.assign(G, G + pp);
-  W.Hh.assign(H, H + pp);
-  W.gh.assign(g, g + mp);
-  W.hh.assign(h, h + mp);
-  W.yyh.assign(yy, yy + m);
+  TRY(reduced_check_yy(ctx, m, yy, "column %d of Y_test is identically zero (or NaN)"));
+  TRY(reduced_store(ctx, W.rf, p, m, G, g, H, h, yy, W.rf.g, W.rf.h));
   std::vector<double> inv((size_t)m);
   for (int r = 0; r < m; ++r) inv[r] = 1.0 / yy[r];
-  TRY(dev_alloc(ctx, W.G, pp));
-  TRY(dev_alloc(ctx, W.H, pp));
-  TRY(dev_alloc(ctx, W.g, mp));
-  TRY(dev_alloc(ctx, W.h, mp));
   TRY(dev_alloc(ctx, W.inv_yy, (size_t)m));
-  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the buffers
-  HIPCHK(hipMemcpy(W.G.ptr, G, sizeof(double) * pp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.H.ptr, H, sizeof(double) * pp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.g.ptr, g, sizeof(double) * mp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.h.ptr, h, sizeof(double) * mp, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(W.inv_yy.ptr, inv.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-  W.p = p;
-  W.m = m;
   W.loaded = true;
   return LSSPA_OK;
 }
 
 // The kernels' view of the loaded responses first .. first + count - 1: weights on the device, a cleared info word
 int multi_args(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, MultiArgs& a) {
-  const int p = W.p;
+  const int p = W.rf.p;
   constexpr int WR = EXACT_MAX_PLAYERS + 1;
   double w[EXACT_W_ROWS * WR];
   exact_weight_table(p, w);
@@ -4895,11 +4924,11 @@ int multi_args(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, Multi
   HIPCHK(hipMemcpy(W.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
   a = MultiArgs{};
-  a.G = W.G.ptr;
-  a.H = W.H.ptr;
+  a.G = W.rf.G.ptr;
+  a.H = W.rf.H.ptr;
   a.ldg = a.ldh = p;
-  a.g = W.g.ptr + (size_t)first * p;
-  a.h = W.h.ptr + (size_t)first * p;
+  a.g = W.rf.g.ptr + (size_t)first * p;
+  a.h = W.rf.h.ptr + (size_t)first * p;
   a.inv_yy = W.inv_yy.ptr + first;
   a.w = W.w.ptr;
   a.p = p;
@@ -4912,7 +4941,7 @@ int multi_args(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, Multi
 
 // first, count, block of an enumeration call against the responses loaded
 int multi_range(lsspa_ctx* ctx, const MultiWork& W, const char* name, int64_t first, int64_t count, int64_t block) {
-  const int m = W.m;
+  const int m = W.rf.m;
   if (first < 0 || count < 1 || first > m || count > m - first || block < 0) {
     char msg[200];
     snprintf(msg, sizeof msg, "%s: responses first = %lld, count = %lld must lie inside the %d loaded, "
@@ -4993,7 +5022,7 @@ int multi_enumerate(lsspa_ctx* ctx, MultiWork& W, int n, uint64_t n_high, uint64
 // on the device, the weights of g players, a cleared info word
 int multi_group_args(lsspa_ctx* ctx, MultiWork& W, const int32_t* labels, int32_t g, int64_t first, int64_t count,
                      MultiGroupArgs& a, GroupLayout& L) {
-  const int p = W.p;
+  const int p = W.rf.p;
   char msg[200];
   if (g > GROUPS_MAX_G) {
     snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
@@ -5015,11 +5044,11 @@ int multi_group_args(lsspa_ctx* ctx, MultiWork& W, const int32_t* labels, int32_
   HIPCHK(hipMemcpy(W.tab.ptr, L.tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
   a = MultiGroupArgs{};
-  a.G = W.G.ptr;
-  a.H = W.H.ptr;
+  a.G = W.rf.G.ptr;
+  a.H = W.rf.H.ptr;
   a.ldg = a.ldh = p;
-  a.g = W.g.ptr + (size_t)first * p;
-  a.h = W.h.ptr + (size_t)first * p;
+  a.g = W.rf.g.ptr + (size_t)first * p;
+  a.h = W.rf.h.ptr + (size_t)first * p;
   a.inv_yy = W.inv_yy.ptr + first;
   a.w = W.w.ptr;
   a.tab = W.tab.ptr;
@@ -5127,7 +5156,7 @@ int multi_reduce_sides(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, co
 // lsspa_multi_shapley on the responses of W (checked: loaded, p <= MULTI_MAX_P, phi, the range)
 int multi_shapley_on(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, int64_t block, double* phi,
                      int32_t* info) {
-  const int p = W.p;
+  const int p = W.rf.p;
   HIPCHK(hipSetDevice(ctx->device));
   const int q = subsets_low_features(p);
   const uint64_t n_high = 1ull << (p - q);
@@ -5152,7 +5181,7 @@ int multi_shapley_on(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count,
 // lsspa_multi_groups_shapley on the responses of W (checked: loaded, labels, phi, the range)
 int multi_groups_shapley_on(lsspa_ctx* ctx, MultiWork& W, const int32_t* labels, int32_t g, int64_t first, int64_t count,
                             int64_t block, double* phi, int32_t* info) {
-  const int p = W.p;
+  const int p = W.rf.p;
   HIPCHK(hipSetDevice(ctx->device));
   MultiGroupArgs a;
   GroupLayout L;
@@ -5242,12 +5271,7 @@ int lsspa_multi_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g,
 int lsspa_multi_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(multi_need_loaded(ctx));
-  const MultiWork& W = ctx->multi;
-  if (G) std::copy(W.Gh.begin(), W.Gh.end(), G);
-  if (g) std::copy(W.gh.begin(), W.gh.end(), g);
-  if (H) std::copy(W.Hh.begin(), W.Hh.end(), H);
-  if (h) std::copy(W.hh.begin(), W.hh.end(), h);
-  if (yy) std::copy(W.yyh.begin(), W.yyh.end(), yy);
+  reduced_get(ctx->multi.rf, G, g, H, h, yy);
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -5281,12 +5305,12 @@ int lsspa_debug_multi_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, d
   TRY(multi_need_ungrouped(ctx, "lsspa_debug_multi_values"));
   MultiWork& W = ctx->multi;
   if (n < 0 || (n > 0 && (!masks || !v))) return ctx->fail(LSSPA_ERR_ARG, "masks / v NULL or n < 0");
-  const uint64_t full = (1ull << W.p) - 1ull;     // p <= 32 here
+  const uint64_t full = (1ull << W.rf.p) - 1ull;     // p <= 32 here
   for (int64_t i = 0; i < n; ++i)
     if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a feature beyond p");
   if (n == 0) return LSSPA_OK;
   HIPCHK(hipSetDevice(ctx->device));
-  const int m = W.m;
+  const int m = W.rf.m;
   MultiArgs a;
   TRY(multi_args(ctx, W, 0, m, a));
   TRY(dev_alloc(ctx, W.masks, (size_t)n));
@@ -5310,7 +5334,7 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_
   MultiWork& W = ctx->multi;
   if (!labels || n < 0 || (n > 0 && (!masks || !u))) return ctx->fail(LSSPA_ERR_ARG, "labels / masks / u NULL or n < 0");
   HIPCHK(hipSetDevice(ctx->device));
-  const int m = W.m;
+  const int m = W.rf.m;
   MultiGroupArgs a;
   GroupLayout L;
   TRY(multi_group_args(ctx, W, labels, g, 0, m, a, L));
@@ -5352,18 +5376,13 @@ constexpr int64_t MLIFT_GRID_PER_LAUNCH = 1 << 16;            // workgroups a la
 constexpr int64_t MLIFT_LIFT_DOUBLES = (256ll << 20) / 8;     // lift vectors of a launch: 256 MB at most (one sample at least)
 
 int mlift_limits(lsspa_ctx* ctx, const char* name, int64_t p, int64_t m) {
-  char msg[200];
   if (p < 1 || p > MLIFT_MAX_P) {
+    char msg[200];
     snprintf(msg, sizeof msg, "%s takes 1 <= p <= %d features (%lld given): both work matrices and %d augmented rows "
              "stay in a compute unit's LDS", name, MLIFT_MAX_P, (long long)p, MLIFT_RB);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
-  if (m < 1 || p + m > MULTI_MAX_COLS) {
-    snprintf(msg, sizeof msg, "%s takes m >= 1 responses with p + m <= %lld (p = %lld, m = %lld given)", name,
-             (long long)MULTI_MAX_COLS, (long long)p, (long long)m);
-    return ctx->fail(LSSPA_ERR_ARG, msg);
-  }
-  return LSSPA_OK;
+  return multi_cols_limit(ctx, name, p, m);
 }
 
 int mlift_need_loaded(lsspa_ctx* ctx) {
@@ -5409,41 +5428,21 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
   MultiLiftWork& W = ctx->mlift;
   W.loaded = false;
   W.ng = 0;                // a player map belongs to the responses it was set on
-  char msg[160];
-  for (int r = 0; r < m; ++r)
-    if (!(yy[r] > 0.0) || !std::isfinite(yy[r])) {
-      snprintf(msg, sizeof msg, "column %d of Y_test is identically zero (or NaN)", r);
-      return ctx->fail(LSSPA_ERR_ARG, msg);
-    }
-  const size_t pp = (size_t)p * p, mp = (size_t)m * p;
-  W.Gh.assign(G, G + pp);
-  W.Hh.assign(H, H + pp);
-  W.gh.assign(g, g + mp);
-  W.hh.assign(h, h + mp);
-  W.yyh.assign(yy, yy + m);
+  TRY(reduced_check_yy(ctx, m, yy, "column %d of Y_test is identically zero (or NaN)"));
   // the augmented rows' trailing corner  aug I - Z Z^T  (Z: the z rows of a chunk) stays positive definite when aug
   // exceeds the sum of the chunk's ||z_r||^2: twice MLIFT_RB times the largest, plus one
   W.aug[0] = 1.0 + 2.0 * MLIFT_RB * mlift_rhs_bound(p, m, G, g);
   W.aug[1] = 1.0 + 2.0 * MLIFT_RB * mlift_rhs_bound(p, m, H, h);
-  TRY(dev_alloc(ctx, W.G, pp));
-  TRY(dev_alloc(ctx, W.H, pp));
-  TRY(dev_alloc(ctx, W.g, mp));
-  TRY(dev_alloc(ctx, W.h, mp));
+  TRY(reduced_store(ctx, W.rf, p, m, G, g, H, h, yy, W.rf.g, W.rf.h));
+  const size_t mp = (size_t)m * p;
   TRY(dev_alloc(ctx, W.yy, (size_t)m));
   TRY(dev_alloc(ctx, W.mean, mp));
   TRY(dev_alloc(ctx, W.M2, mp));
   TRY(dev_alloc(ctx, W.info, 8));
-  HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the buffers
-  HIPCHK(hipMemcpy(W.G.ptr, G, sizeof(double) * pp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.H.ptr, H, sizeof(double) * pp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.g.ptr, g, sizeof(double) * mp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.h.ptr, h, sizeof(double) * mp, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(W.yy.ptr, yy, sizeof(double) * m, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
   HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
   HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
-  W.p = p;
-  W.m = m;
   W.n = 0;
   W.batch_ms = W.stats_ms = 0.0;
   W.loaded = true;
@@ -5454,7 +5453,7 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
 int mlift_reset(lsspa_ctx* ctx) {
   MultiLiftWork& W = ctx->mlift;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t mp = (size_t)W.m * W.p;
+  const size_t mp = (size_t)W.rf.m * W.rf.p;
   HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
   HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
   HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
@@ -5512,14 +5511,14 @@ int lsspa_multi_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t 
     return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
   PlayerMap map;
   if (labels) {
-    const char* why = player_map_build(labels, W.p, g, map);
+    const char* why = player_map_build(labels, W.rf.p, g, map);
     if (why) return ctx->fail(LSSPA_ERR_ARG, why);
   }
   HIPCHK(hipSetDevice(ctx->device));
   TRY(mlift_reset(ctx));       // (waits for work in flight: a previous batch may still read the tables)
   if (labels) {
-    TRY(dev_alloc(ctx, W.pl_off, (size_t)W.p + 1));
-    TRY(dev_alloc(ctx, W.pl_cols, (size_t)W.p));
+    TRY(dev_alloc(ctx, W.pl_off, (size_t)W.rf.p + 1));
+    TRY(dev_alloc(ctx, W.pl_cols, (size_t)W.rf.p));
     HIPCHK(hipMemcpy(W.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(W.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
     W.map = std::move(map);
@@ -5537,7 +5536,7 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
   MultiLiftWork& W = ctx->mlift;
-  const int p = W.p, m = W.m, g = W.ng, d = W.sd();
+  const int p = W.rf.p, m = W.rf.m, g = W.ng, d = W.sd();
   if (!perms || B < 1 || B > (int64_t)INT32_MAX / (g ? 2 * p : p))     // (with a map: two expanded rows a sample)
     return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_multi_lift_batch: perms is NULL, B < 1 or 2 B p >= 2^31"
                                       : "lsspa_multi_lift_batch: perms is NULL, B < 1 or B p >= 2^31");
@@ -5560,11 +5559,11 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
   for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
   W.batch_ms = W.stats_ms = 0.0;
   MultiLiftArgs a{};
-  a.G = W.G.ptr;
-  a.H = W.H.ptr;
+  a.G = W.rf.G.ptr;
+  a.H = W.rf.H.ptr;
   a.ld = p;
-  a.g = W.g.ptr;
-  a.h = W.h.ptr;
+  a.g = W.rf.g.ptr;
+  a.h = W.rf.h.ptr;
   a.yy = W.yy.ptr;
   a.aug[0] = W.aug[0];
   a.aug[1] = W.aug[1];
@@ -5623,7 +5622,7 @@ int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) t
   MultiLiftWork& W = ctx->mlift;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t mp = (size_t)W.m * W.sd();
+  const size_t mp = (size_t)W.rf.m * W.sd();
   if (n) *n = W.n;
   if (mean) HIPCHK(hipMemcpy(mean, W.mean.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
   if (m2) HIPCHK(hipMemcpy(m2, W.M2.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
@@ -5644,12 +5643,7 @@ int lsspa_multi_lift_reset(lsspa_ctx* ctx) try {
 int lsspa_multi_lift_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
-  const MultiLiftWork& W = ctx->mlift;
-  if (G) std::copy(W.Gh.begin(), W.Gh.end(), G);
-  if (g) std::copy(W.gh.begin(), W.gh.end(), g);
-  if (H) std::copy(W.Hh.begin(), W.Hh.end(), H);
-  if (h) std::copy(W.hh.begin(), W.hh.end(), h);
-  if (yy) std::copy(W.yyh.begin(), W.yyh.end(), yy);
+  reduced_get(ctx->mlift.rf, G, g, H, h, yy);
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
@@ -5730,10 +5724,10 @@ int perm_players(lsspa_ctx* ctx, const char* name, const int32_t* labels, int32_
 int perm_slots(lsspa_ctx* ctx, int64_t cap) {
   PermWork& W = ctx->perm;
   MultiWork& Mw = W.mw;
-  TRY(dev_alloc(ctx, Mw.g, (size_t)cap * W.p));
-  TRY(dev_alloc(ctx, Mw.h, (size_t)cap * W.p));
+  TRY(dev_alloc(ctx, Mw.rf.g, (size_t)cap * W.p));
+  TRY(dev_alloc(ctx, Mw.rf.h, (size_t)cap * W.p));
   TRY(dev_alloc(ctx, Mw.inv_yy, (size_t)cap));
-  std::vector<double> inv((size_t)cap, 1.0 / W.yy);
+  std::vector<double> inv((size_t)cap, 1.0 / Mw.rf.yyh[0]);
   HIPCHK(hipStreamSynchronize(ctx->stream));     // a previous call may still read the slots
   HIPCHK(hipMemcpy(Mw.inv_yy.ptr, inv.data(), sizeof(double) * (size_t)cap, hipMemcpyHostToDevice));
   return LSSPA_OK;
@@ -5741,7 +5735,7 @@ int perm_slots(lsspa_ctx* ctx, int64_t cap) {
 
 int perm_enumerate(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t count, double* phi, int32_t* bits) {
   MultiWork& Mw = ctx->perm.mw;
-  Mw.m = (int)count;
+  Mw.rf.m = (int)count;
   return labels ? multi_groups_shapley_on(ctx, Mw, labels, g, 0, count, 0, phi, bits)
                 : multi_shapley_on(ctx, Mw, 0, count, 0, phi, bits);
 }
@@ -5819,54 +5813,26 @@ int lsspa_perm_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const
   double gram_ms = 0.0;
   TRY(multi_reduce_sides(ctx, X_train, ld_train, y_train, 1, N, X_test, ld_test, y_test, 1, M, p, 1, reg, dtype, location,
                          G, g, H, h, yy, gram_ms));
-  if (!(yy[0] > 0.0) || !std::isfinite(yy[0])) return ctx->fail(LSSPA_ERR_ARG, "y_test is identically zero (or NaN)");
+  TRY(reduced_check_yy(ctx, 1, yy.data(), "y_test is identically zero (or NaN)"));
   const void* X[2] = {X_train, X_test};
   const void* y[2] = {y_train, y_test};
   const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test};
-  const size_t esz = dtype == LSSPA_F32 ? 4 : 8;
   for (int s = 0; s < 2; ++s) {
     TRY(dev_alloc(ctx, W.X(s), (size_t)n[s] * P.ldx));
     TRY(dev_alloc(ctx, W.y(s), (size_t)n[s]));
-    if (location == LSSPA_DEVICE) {
-      HIPCHK(launch_perm_pack(X[s], ld[s], y[s], n[s], p, dtype == LSSPA_F32, W.X(s).ptr, P.ldx, W.y(s).ptr, 0,
-                              ctx->stream));
-      continue;
-    }
-    // host rows: through a staging buffer of at most ~64 MB, chunk by chunk (plain copies, as lsspa_boot_load's)
-    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(n[s], (64ll << 20) / (int64_t)(ld[s] * esz)));
-    TRY(dev_alloc(ctx, W.stage_x, (size_t)rows * ld[s] * esz));
-    TRY(dev_alloc(ctx, W.stage_y, (size_t)rows * esz));
-    for (int64_t r0 = 0; r0 < n[s]; r0 += rows) {
-      const int64_t nr = std::min(rows, n[s] - r0);
-      const size_t xbytes = ((size_t)(nr - 1) * ld[s] + p) * esz;     // the caller's last row ends with its column p - 1
-      HIPCHK(hipMemcpyAsync(W.stage_x.ptr, (const char*)X[s] + (size_t)r0 * ld[s] * esz, xbytes, hipMemcpyHostToDevice,
-                            ctx->stream));
-      HIPCHK(hipMemcpyAsync(W.stage_y.ptr, (const char*)y[s] + (size_t)r0 * esz, (size_t)nr * esz, hipMemcpyHostToDevice,
-                            ctx->stream));
-      HIPCHK(launch_perm_pack(W.stage_x.ptr, ld[s], W.stage_y.ptr, nr, p, dtype == LSSPA_F32, W.X(s).ptr, P.ldx,
-                              W.y(s).ptr, r0, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));     // the staging buffer is reused
-    }
+    TRY(load_rows(ctx, W.stage_x, W.stage_y, X[s], ld[s], y[s], n[s], p, dtype, location,
+                  [&](const void* sx, const void* sy, int64_t nr, int64_t r0) {
+                    return launch_perm_pack(sx, ld[s], sy, nr, p, dtype == LSSPA_F32, W.X(s).ptr, P.ldx, W.y(s).ptr, r0,
+                                            ctx->stream);
+                  }));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   dev_free(W.stage_x);
   dev_free(W.stage_y);
-  const size_t pp = (size_t)p * p;
-  TRY(dev_alloc(ctx, W.mw.G, pp));
-  TRY(dev_alloc(ctx, W.mw.H, pp));
-  TRY(dev_alloc(ctx, W.obs_g, (size_t)p));
-  TRY(dev_alloc(ctx, W.obs_h, (size_t)p));
-  HIPCHK(hipMemcpy(W.mw.G.ptr, G.data(), sizeof(double) * pp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.mw.H.ptr, H.data(), sizeof(double) * pp, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.obs_g.ptr, g.data(), sizeof(double) * p, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(W.obs_h.ptr, h.data(), sizeof(double) * p, hipMemcpyHostToDevice));
-  W.Gh = G;
-  W.Hh = H;
-  W.gh = g;
-  W.hh = h;
-  W.yy = yy[0];
-  W.p = W.mw.p = p;
-  W.mw.m = 0;
+  // the observed g, h beside the form's own, which are the response slots of a block of replicates (perm_slots)
+  TRY(reduced_store(ctx, W.mw.rf, p, 1, G.data(), g.data(), H.data(), h.data(), yy.data(), W.obs_g, W.obs_h));
+  W.p = p;
+  W.mw.rf.m = 0;
   W.mw.gram_ms = gram_ms;
   W.n[0] = N;
   W.n[1] = M;
@@ -5886,8 +5852,8 @@ int lsspa_perm_observed(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double
   HIPCHK(hipSetDevice(ctx->device));
   PermWork& W = ctx->perm;
   TRY(perm_slots(ctx, 1));
-  HIPCHK(launch_perm_fill(W.obs_g.ptr, W.p, 1, W.mw.g.ptr, ctx->stream));
-  HIPCHK(launch_perm_fill(W.obs_h.ptr, W.p, 1, W.mw.h.ptr, ctx->stream));
+  HIPCHK(launch_perm_fill(W.obs_g.ptr, W.p, 1, W.mw.rf.g.ptr, ctx->stream));
+  HIPCHK(launch_perm_fill(W.obs_h.ptr, W.p, 1, W.mw.rf.h.ptr, ctx->stream));
   int32_t bits = 0;
   TRY(perm_enumerate(ctx, labels, g, 1, phi, &bits));
   if (info) *info = bits;
@@ -5933,8 +5899,8 @@ int lsspa_perm_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, 
     }
   }
   // the side that is not permuted keeps its observed g or h in every slot
-  if (!(sides & 1)) HIPCHK(launch_perm_fill(W.obs_g.ptr, p, (int)blk, W.mw.g.ptr, ctx->stream));
-  if (!(sides & 2)) HIPCHK(launch_perm_fill(W.obs_h.ptr, p, (int)blk, W.mw.h.ptr, ctx->stream));
+  if (!(sides & 1)) HIPCHK(launch_perm_fill(W.obs_g.ptr, p, (int)blk, W.mw.rf.g.ptr, ctx->stream));
+  if (!(sides & 2)) HIPCHK(launch_perm_fill(W.obs_h.ptr, p, (int)blk, W.mw.rf.h.ptr, ctx->stream));
   PermStream up;
   HIPCHK(hipStreamCreateWithFlags(&up.s, hipStreamNonBlocking));
   for (hipEvent_t& e : up.ev) HIPCHK(hipEventCreate(&e));
@@ -5982,14 +5948,14 @@ int lsspa_perm_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, 
       HIPCHK(launch_perm_xty(P, s, W.X(s).ptr, W.y(s).ptr, W.idx[b & 1][s].ptr, W.n[s], (int)nb, W.part(s).ptr,
                              ctx->stream));
       HIPCHK(launch_perm_reduce(P, s, W.part(s).ptr, p, (int)nb, s == 0 ? 1.0 / (double)W.n[0] : 1.0,
-                                s == 0 ? W.mw.g.ptr : W.mw.h.ptr, ctx->stream));
+                                s == 0 ? W.mw.rf.g.ptr : W.mw.rf.h.ptr, ctx->stream));
     }
     HIPCHK(hipEventRecord(up.ev[1], ctx->stream));
     const size_t at = (size_t)(b * blk) * p;
     if (gperm)
-      HIPCHK(hipMemcpyAsync(gperm + at, W.mw.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipMemcpyAsync(gperm + at, W.mw.rf.g.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, ctx->stream));
     if (hperm)
-      HIPCHK(hipMemcpyAsync(hperm + at, W.mw.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipMemcpyAsync(hperm + at, W.mw.rf.h.ptr, sizeof(double) * (size_t)nb * p, hipMemcpyDeviceToHost, ctx->stream));
     int32_t bits = 0;
     TRY(perm_enumerate(ctx, labels, g, nb, phi + (size_t)(b * blk) * d, &bits));
     all_bits |= bits;
@@ -6008,12 +5974,7 @@ int lsspa_perm_run(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t R, 
 int lsspa_perm_get_gram(lsspa_ctx* ctx, double* G, double* g, double* H, double* h, double* yy) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(perm_need_loaded(ctx));
-  const PermWork& W = ctx->perm;
-  if (G) std::copy(W.Gh.begin(), W.Gh.end(), G);
-  if (g) std::copy(W.gh.begin(), W.gh.end(), g);
-  if (H) std::copy(W.Hh.begin(), W.Hh.end(), H);
-  if (h) std::copy(W.hh.begin(), W.hh.end(), h);
-  if (yy) *yy = W.yy;
+  reduced_get(ctx->perm.mw.rf, G, g, H, h, yy);
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);

@@ -1564,6 +1564,40 @@ def _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m):
     return parts
 
 
+def _bootstrap_arrays(engine, undo, data, reg, grouped, run, n_boot, seed, options, n_arrays):
+    """The shared middle of the bootstrap drivers, inside their engine call: the rows onto the device (boot_free goes into
+    `undo`), then `run` (an engine's boot_*_run, bound to what it takes before R) over the n_boot replicates; its n_arrays
+    results, each concatenated over the engine calls.  options: _bootstrap_options' (w_train, w_test, sides)."""
+    w_train, w_test, sides = options
+    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
+    engine.boot_load(*data, reg, grouped=grouped)
+    undo.append((engine.boot_free, True))
+    parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, len(data[0]), len(data[1]))
+    return [np.concatenate([q[k] for q in parts]) for k in range(n_arrays)]
+
+
+def _warn_failed_replicates(n_failed, n_boot, where):
+    """A bootstrap's RuntimeWarning about its failed replicates, attributed to the caller of the public function that
+    asks.  where: the array that holds their NaN and what they are left out of."""
+    if n_failed:
+        warnings.warn(f"{n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
+                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
+                      f"{where}", RuntimeWarning, stacklevel=3)
+
+
+class _PointWarnings(warnings.catch_warnings):
+    """The point estimate's warnings are this call's: recorded while the context (made with record=True) is open, and
+    handed to the caller of the public function that asks by emit(), once its engine call is over."""
+
+    def __enter__(self):
+        self._caught = super().__enter__()
+        warnings.simplefilter("always")
+
+    def emit(self):
+        for w in self._caught:
+            warnings.warn(w.message, w.category, stacklevel=3)
+
+
 def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, confidence=0.95, weights=None,
                      resample=("train", "test"), groups=None, device=0, _engine=None):
     """Bootstrap confidence intervals for the exact attribution (p <= 32; with ``groups=``, g <= 32 groups over p <= 64
@@ -1607,9 +1641,8 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
         raise ValueError(f"ls_spa_bootstrap re-runs the enumeration of all 2^p feature subsets and takes at most p = "
                          f"{SUBSETS_MAX_P} features (this problem has p = {p}); group the columns (ls_spa_groups) to "
                          "attribute to at most 32 players, or use a sampling method")
-    w_train, w_test, sides = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
+    options = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
     n_boot = int(n_boot)
-    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
     undo = []
     with _engine_call(_engine, device, undo=undo) as engine:
         if getattr(engine, "precision", "float64") != "float64":
@@ -1619,23 +1652,14 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
         _info_verdict((bits | info) & 1, stacklevel=3)
         if info & 1:
             theta, r_squared = _singular_fit(engine, data[1], data[3])
-        if labels is None:
-            engine.boot_load(*data, reg)
-            run = engine.boot_run
-        else:
-            engine.boot_load(*data, reg, grouped=True)
-            run = functools.partial(engine.boot_groups_run, labels)
-        undo.append((engine.boot_free, True))
-        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
-        rep, r2, *base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(len(parts[0])))
+        grouped = labels is not None
+        run = functools.partial(engine.boot_groups_run, labels) if grouped else engine.boot_run
+        rep, r2, *base, binfo = _bootstrap_arrays(engine, undo, data, reg, grouped, run, n_boot, seed, options, 3 + grouped)
     failed = (binfo & 1).astype(bool) | ~np.isfinite(rep).all(axis=1) | ~np.isfinite(r2)
     for b in base:
         failed |= ~np.isfinite(b)
     res = BootstrapResults.from_replicates(phi, theta, r_squared, rep, r2, failed, confidence, *base)
-    if res.n_failed:
-        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
-                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
-                      "`replicates` and left out of the intervals", RuntimeWarning, stacklevel=2)
+    _warn_failed_replicates(res.n_failed, n_boot, "`replicates` and left out of the intervals")
     return res
 
 
@@ -1678,9 +1702,8 @@ def ls_spa_interactions_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_bo
                          "at most 32 players")
     if d < 2:
         raise ValueError(f"an interaction needs two players (this problem has {d})")
-    w_train, w_test, sides = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
+    options = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
     n_boot = int(n_boot)
-    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
     undo = []
     with _engine_call(_engine, device, undo=undo) as engine:
         if getattr(engine, "precision", "float64") != "float64":
@@ -1690,25 +1713,17 @@ def ls_spa_interactions_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_bo
         _info_verdict((bits | info) & 1, stacklevel=3)
         if info & 1:
             theta, r_squared = _singular_fit(engine, data[1], data[3])
-        if labels is None:
-            engine.boot_load(*data, reg)
-            run = engine.boot_interactions_run
-        else:
-            engine.boot_load(*data, reg, grouped=True)
-            run = functools.partial(engine.boot_groups_interactions_run, labels)
-        undo.append((engine.boot_free, True))
-        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
-        att, index, r2, *base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(len(parts[0])))
+        grouped = labels is not None
+        run = functools.partial(engine.boot_groups_interactions_run, labels) if grouped else engine.boot_interactions_run
+        att, index, r2, *base, binfo = _bootstrap_arrays(engine, undo, data, reg, grouped, run, n_boot, seed, options,
+                                                         4 + grouped)
     failed = (binfo & 1).astype(bool) | ~np.isfinite(att).all(axis=1) | ~np.isfinite(index).all(axis=(1, 2)) | ~np.isfinite(r2)
     for b in base:
         failed |= ~np.isfinite(b)
     rep = np.stack([_shap_matrix(a, i) for a, i in zip(att, index)])
     res = InteractionBootstrapResults.from_replicates(_shap_matrix(phi, raw), phi, theta, r_squared, rep, att, r2, failed,
                                                       confidence, *base)
-    if res.n_failed:
-        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
-                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
-                      "`replicates` and left out of the intervals", RuntimeWarning, stacklevel=2)
+    _warn_failed_replicates(res.n_failed, n_boot, "`replicates` and left out of the intervals")
     return res
 
 
@@ -1752,28 +1767,19 @@ def ls_spa_best_subsets_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_bo
     mask, inc = include_mask(include, p)
     if not np.any(data[3]):
         raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
-    w_train, w_test, sides = _bootstrap_options(n_boot, 0.95, weights, resample, n, m)
+    options = _bootstrap_options(n_boot, 0.95, weights, resample, n, m)
     n_boot = int(n_boot)
-    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
-    undo = []
+    undo, point_warnings = [], _PointWarnings(record=True)
     with _engine_call(_engine, device, undo=undo) as engine:
-        with warnings.catch_warnings(record=True) as caught:      # the point estimate's warnings are this call's
-            warnings.simplefilter("always")
+        with point_warnings:
             point = ls_spa_best_subsets(*data, reg=reg, include=include, _engine=engine)
-        engine.boot_load(*data, reg)
-        undo.append((engine.boot_free, True))
         run = functools.partial(engine.boot_best_run, include=mask)
-        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
-        v, masks, found, r2, binfo = (np.concatenate([q[k] for q in parts]) for k in range(5))
-    for w in caught:
-        warnings.warn(w.message, w.category, stacklevel=2)
+        v, masks, found, r2, binfo = _bootstrap_arrays(engine, undo, data, reg, False, run, n_boot, seed, options, 5)
+    point_warnings.emit()
     failed = (binfo & 1).astype(bool) | ~np.isfinite(r2)
     k0 = len(inc)
     res = BestSubsetsBootstrapResults.from_replicates(point, v[:, k0:], masks[:, k0:], found[:, k0:], r2, failed)
-    if res.n_failed:
-        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
-                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
-                      "`r_squared_replicates` and left out of the frequencies", RuntimeWarning, stacklevel=2)
+    _warn_failed_replicates(res.n_failed, n_boot, "`r_squared_replicates` and left out of the frequencies")
     return res
 
 
@@ -1819,27 +1825,18 @@ def ls_spa_best_group_subsets_bootstrap(X_train, X_test, y_train, y_test, groups
         raise ValueError(f"ls_spa_best_group_subsets_bootstrap needs M >= 1 test rows (M = {m})")
     if not np.any(data[3]):
         raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
-    w_train, w_test, sides = _bootstrap_options(n_boot, 0.95, weights, resample, n, m)
+    options = _bootstrap_options(n_boot, 0.95, weights, resample, n, m)
     n_boot = int(n_boot)
-    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
-    undo = []
+    undo, point_warnings = [], _PointWarnings(record=True)
     with _engine_call(_engine, device, undo=undo) as engine:
-        with warnings.catch_warnings(record=True) as caught:      # the point estimate's warnings are this call's
-            warnings.simplefilter("always")
+        with point_warnings:
             point = ls_spa_best_subsets(*data, reg=reg, groups=labels, _engine=engine)
-        engine.boot_load(*data, reg, grouped=True)
-        undo.append((engine.boot_free, True))
         run = functools.partial(engine.boot_groups_best_run, labels)
-        parts = _bootstrap_parts(run, n_boot, seed, w_train, w_test, fixed, n, m)
-        u, masks, found, r2, base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(6))
-    for w in caught:
-        warnings.warn(w.message, w.category, stacklevel=2)
+        u, masks, found, r2, base, binfo = _bootstrap_arrays(engine, undo, data, reg, True, run, n_boot, seed, options, 6)
+    point_warnings.emit()
     failed = (binfo & 1).astype(bool) | ~np.isfinite(r2) | ~np.isfinite(base)
     res = BestGroupSubsetsBootstrapResults.from_replicates(point, u, masks, found, r2, base, failed)
-    if res.n_failed:
-        warnings.warn(f"{res.n_failed} of {n_boot} bootstrap replicates had a Gram matrix that was not numerically "
-                      "positive definite (a column constant or collinear on the resampled rows); they are NaN in "
-                      "`r_squared_replicates` and left out of the frequencies", RuntimeWarning, stacklevel=2)
+    _warn_failed_replicates(res.n_failed, n_boot, "`r_squared_replicates` and left out of the frequencies")
     return res
 
 
