@@ -141,6 +141,29 @@ int lsspa_subsets_interactions(lsspa_ctx* ctx, double* phi /* [p] */, double* in
 int lsspa_subsets_best(lsspa_ctx* ctx, uint32_t include, double* v /* [p+1] */, uint32_t* masks /* [p+1] */,
                        uint8_t* found /* [p+1] */, int32_t* info);
 
+/* The T best subsets of every size (1 <= T <= 16): lsspa_subsets_best's enumeration, v, candidates (include, own pivots
+ * passed, NaN never listed) and order, keeping per size k = 0 .. p not one winner but a list,
+ *   v[k][r], masks[k][r], r < count[k] = min(T, number of candidates of size k),
+ * best first: the larger value, on equal values the numerically smaller mask.  Masks are unique, so the order is strict
+ * and the list does not depend on how the work is cut into units and launches.  Entries past count[k] are NaN / 0.
+ * Rank 0 is bitwise lsspa_subsets_best's (value, mask, found) for the same include; every listed value has the very
+ * bits lsspa_debug_subset_values returns for its mask; the lists of a call with T are the first T ranks of a call with
+ * a larger T; two calls agree bitwise (no atomics on the table).
+ * Limits, refusals and messages are lsspa_subsets_best's (p > 32, no problem loaded, include bits at or above p:
+ * LSSPA_ERR_ARG); T outside 1 .. 16 is LSSPA_ERR_ARG naming the limit; NULL v, masks or count is LSSPA_ERR_ARG, info may
+ * be NULL (LSSPA_INFO_NOT_PD as there).  It shares lsspa_subsets_shapley's buffers (a call of that, or of
+ * lsspa_subsets_best, before and after this one agrees bitwise) and leaves its timing where lsspa_subsets_timing reads
+ * it; nothing of the sampling path, the grouped state or the bootstrap store changes.
+ * Device memory: the units' lists, units (p + 1) of them with units = min(2^(p - 6), 8192), 12 bytes an entry (value,
+ * mask) and 4 a list (count): 8192 x 33 x (12 x 16 + 4) bytes = 53 MB at p = 32 and T = 16.
+ *   lsspa_debug_subsets_top_plan : host only, no context, no GPU -- units, high subsets per unit, steps of a unit per
+ *                     launch, launches, sizes one unit can hold, bytes of the table, rounds of the final reduction (T),
+ *                     0; from the functions the call itself uses.  p outside 1 .. 32 or T outside 1 .. 16 is
+ *                     LSSPA_ERR_ARG. */
+int lsspa_subsets_top(lsspa_ctx* ctx, uint32_t include, int32_t T, double* v /* [p+1][T] */,
+                      uint32_t* masks /* [p+1][T] */, int32_t* count /* [p+1] */, int32_t* info);
+int lsspa_debug_subsets_top_plan(int32_t p, int32_t T, int64_t* plan /* [8] */);
+
 /* Exact Shapley attribution over GROUPS of columns: the players are the g <= 32 groups, the problem has p <= 64 columns.
  * labels[j] in {-1, 0 .. g-1} for every column j: group k is {j : labels[j] == k} (none may be empty), the columns
  * labelled -1 are the baseline B, part of every model and given no attribution.  With F(S) = B + the columns of the

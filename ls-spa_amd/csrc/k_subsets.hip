@@ -557,6 +557,183 @@ __global__ __launch_bounds__(64) void subsets_best_reduce_kernel(const double* _
   }
 }
 
+// ---- the T best subsets of every size (lsspa_subsets_top) ----
+// subsets_best_kernel's sibling: the same units, steps and launches, the same load_shared and subset_values, the same
+// candidates (the subset contains `include`, its own pivots passed, its value is above -inf, so never NaN); what is kept
+// per size k = |K| is not one winner but the T best, 1 <= T <= SUBSETS_TOP_MAX, in the same total order -- the larger
+// value first, on equal values the numerically smaller mask.  Masks are unique, so the order is strict and the T best of
+// any collection of subsets are one definite list: the result depends neither on the cut into units and launches nor
+// on the order of the inserts.
+//
+// Lists: |K| = popc(unit) + popc(s) + popc(T), so a unit meets at most STS = SBS + SQ = 20 sizes, popc(unit) + j with
+// j = popc(s) + popc(lane).  Per such j it keeps a sorted list of up to T (value, mask) and a count -- in LDS, not in
+// registers: a lane's size changes from step to step and a list belongs to the wave, not to a lane.  The lists are
+// dynamic LDS, 12 T + 4 bytes a size beside SubShared (T = 1: 320 B, seven workgroups a CU as before; T = 16: 3920 B,
+// six).  A launch loads them from the unit's rows of the table and stores them back at its end (one workgroup owns a
+// row, launches are ordered by the stream: plain loads and stores); the counts are cleared before the first launch, the
+// entries need not be.
+// Every step, fast path: a lane reads its list's count and last entry, compares, and one ballot says whether any lane
+// has something to insert.  Once the lists have filled almost no step does.  Slow path, the same for the whole wave:
+// the lowest lane of the ballot broadcasts (value, mask, j); lane t < T holds entry t of that list, rank = how many
+// entries come before the new one, entries from `rank` on move down by one shuffle and the one that falls off position
+// T - 1 is dropped; then the lanes still waiting compare again with the list as it now is.
+constexpr int STS = SBS + SQ;
+
+// does (v, m) come before (ov, om) in the total order?
+__device__ inline bool top_before(double v, uint32_t m, double ov, uint32_t om) { return v > ov || (v == ov && m < om); }
+
+// bytes of dynamic LDS: values [STS][T], masks [STS][T], counts [STS]
+constexpr size_t top_lds_bytes(int T) { return (size_t)STS * T * 12 + (size_t)STS * 4; }
+
+// a.part [units][p + 1][T] (values), tm [units][p + 1][T] (masks), tc [units][p + 1] (counts): unit u's T best of every
+// size so far, best first
+__global__ __launch_bounds__(64) void subsets_top_kernel(SubsetArgs a, uint64_t s0, uint64_t s1, uint32_t include, int T,
+                                                         uint32_t* __restrict__ tm, int32_t* __restrict__ tc) {
+  __shared__ SubShared sh;
+  extern __shared__ double top_lds[];
+  double* lv = top_lds;
+  uint32_t* lm = reinterpret_cast<uint32_t*>(lv + STS * T);
+  int* lc = reinterpret_cast<int*>(lm + STS * T);
+  const int lane = threadIdx.x;
+  const int p = a.p, q = a.q;
+  load_shared<false>(sh, a, lane);
+  // the sizes this unit can hold: k0 + j, j < ns (popc(s) + popc(T) with s < per, T < 2^q, and no more than p)
+  const int k0 = __popc(blockIdx.x);
+  const int ns = min(p - k0, __popcll(a.per - 1) + q) + 1;
+  double* gv = a.part + ((int64_t)blockIdx.x * (p + 1) + k0) * T;
+  uint32_t* gm = tm + ((int64_t)blockIdx.x * (p + 1) + k0) * T;
+  int32_t* gc = tc + (int64_t)blockIdx.x * (p + 1) + k0;
+  for (int e = lane; e < ns * T; e += 64) {
+    const int j = e / T;
+    if (e - j * T < gc[j]) {
+      lv[e] = gv[e];
+      lm[e] = gm[e];
+    }
+  }
+  if (lane < ns) lc[lane] = gc[lane];
+  // (subset_values passes a barrier before anything below reads the lists)
+  const uint32_t inc_lo = include & ((1u << q) - 1u), inc_hi = include >> q;     // q >= 1
+  const bool lane_ok = lane < (1 << q) && ((uint32_t)lane & inc_lo) == inc_lo;
+  const int jl = lane_ok ? __popc(lane) : 0;
+  bool any_bad = false;
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    bool bad = false;                         // this subset's own pivots, as in subsets_best_kernel
+    const double v = subset_values<false>(sh, a, hi, lane, bad);
+    any_bad |= bad;
+    const uint32_t h32 = (uint32_t)hi;
+    const uint32_t m = (h32 << q) | (uint32_t)lane;
+    const int j = __popcll(s) + jl;           // < ns for every lane that can be a candidate
+    // a candidate that belongs into its size's list as it is now: the list is not full, or its last entry comes later
+    auto wanted = [&]() {
+      const int c = lc[j];
+      return c < T || top_before(v, m, lv[j * T + T - 1], lm[j * T + T - 1]);
+    };
+    bool want = lane_ok && !bad && (h32 & inc_hi) == inc_hi && v > -__builtin_huge_val() && wanted();
+    for (uint64_t todo = __ballot(want); todo != 0ull; todo = __ballot(want)) {
+      const int src = __ffsll((unsigned long long)todo) - 1;
+      const double nv = __shfl(v, src, 64);
+      const uint32_t nm = (uint32_t)__shfl((int)m, src, 64);
+      const int nj = __shfl(j, src, 64);
+      double* rv = lv + nj * T;
+      uint32_t* rm = lm + nj * T;
+      const int c = lc[nj];
+      const bool have = lane < c;             // c <= T <= 16: lane t holds entry t
+      const double ev = have ? rv[lane] : 0.0;
+      const uint32_t em = have ? rm[lane] : 0u;
+      const int rank = __popcll(__ballot(have && top_before(ev, em, nv, nm)));
+      const double pv = __shfl_up(ev, 1, 64);
+      const uint32_t pm = (uint32_t)__shfl_up((int)em, 1, 64);
+      const int nc = min(c + 1, T);
+      if (lane >= rank && lane < nc) {        // a lane writes the entry it read: no other lane's
+        rv[lane] = lane == rank ? nv : pv;
+        rm[lane] = lane == rank ? nm : pm;
+      }
+      if (lane == 0) lc[nj] = nc;
+      __syncthreads();
+      if (lane == src) want = false;
+      want = want && wanted();
+    }
+    __syncthreads();
+  }
+  for (int e = lane; e < ns * T; e += 64) {
+    const int j = e / T;
+    if (e - j * T < lc[j]) {
+      gv[e] = lv[e];
+      gm[e] = lm[e];
+    }
+  }
+  if (lane < ns) gc[lane] = lc[lane];
+  if (__any(any_bad) && lane == 0) atomicOr(a.info, 1);
+}
+
+// out_v [p + 1][T], out_m [p + 1][T], out_c [p + 1]: per size the T best over all units' lists in the same order, NaN / 0
+// past the count.  One workgroup of TRT threads per size; a thread owns the units u = thread + TRT i.  A unit's list is
+// sorted, so the best entry it still has is its first one not yet taken: LDS keeps per unit how many were taken and how
+// many there are.  T rounds: every thread takes the best of its units' heads, fixed butterflies give the best of all
+// (the order is strict, so every thread sees the same winner whatever the order of the merges), which is written as
+// the next rank; the one thread that held it moves that unit on.  "No head" is -inf, which loses against every entry.
+constexpr int TRT = 256, TRU = 32;            // units <= TRT TRU = 8192
+__global__ __launch_bounds__(TRT) void subsets_top_reduce_kernel(const double* __restrict__ tv,
+                                                                 const uint32_t* __restrict__ tm,
+                                                                 const int32_t* __restrict__ tc, int units, int p1, int T,
+                                                                 double* __restrict__ out_v,
+                                                                 uint32_t* __restrict__ out_m,
+                                                                 int32_t* __restrict__ out_c) {
+  __shared__ double wv[TRT / 64];
+  __shared__ uint32_t wm[TRT / 64];
+  __shared__ uint8_t pos[TRT * TRU], cnt[TRT * TRU];      // of unit u: entries taken, entries there are (<= 16)
+  const int k = blockIdx.x, tid = threadIdx.x;
+  for (int u = tid; u < units; u += TRT) {                // a unit's two bytes are its thread's alone
+    pos[u] = 0;
+    cnt[u] = (uint8_t)tc[(int64_t)u * p1 + k];
+  }
+  int n = 0;
+  for (; n < T; ++n) {
+    double v = -__builtin_huge_val();
+    uint32_t mask = 0u;
+    int bu = -1;
+    for (int u = tid; u < units; u += TRT) {
+      const int t = pos[u];
+      if (t < cnt[u]) {
+        const int64_t e = ((int64_t)u * p1 + k) * T + t;
+        const double ev = tv[e];
+        const uint32_t em = tm[e];
+        if (bu < 0 || top_before(ev, em, v, mask)) {
+          v = ev;
+          mask = em;
+          bu = u;
+        }
+      }
+    }
+    const uint32_t own = mask;                            // (with bu >= 0) this thread's candidate
+    wave_best(v, mask);
+    if ((tid & 63) == 0) {
+      wv[tid >> 6] = v;
+      wm[tid >> 6] = mask;
+    }
+    __syncthreads();
+    v = wv[0];
+    mask = wm[0];
+#pragma unroll
+    for (int w = 1; w < TRT / 64; ++w) best_merge(v, mask, wv[w], wm[w]);
+    __syncthreads();
+    if (!(v > -__builtin_huge_val())) break;              // no head left: the same for every thread
+    if (tid == 0) {
+      out_v[k * T + n] = v;
+      out_m[k * T + n] = mask;
+    }
+    if (bu >= 0 && own == mask) ++pos[bu];                // masks of one size are unique: one thread
+  }
+  if (tid == 0) {
+    out_c[k] = n;
+    for (int r = n; r < T; ++r) {
+      out_v[k * T + r] = __builtin_nan("");
+      out_m[k * T + r] = 0u;
+    }
+  }
+}
+
 // H = Ft Ft^T [p][p] (stride p) and h = Ft ytil (appended) of the rect-mode test factor: one workgroup per entry, its
 // 256 threads strided over the m columns, then a fixed tree (the same sums on every call; m may be up to 2^20 through
 // lsspa_set_reduced).  Entries (i, j) and (j, i) both form the product of rows min(i, j) and max(i, j) in the same
@@ -650,6 +827,30 @@ hipError_t launch_subsets_best_reduce(const double* bv, const uint32_t* bm, int6
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(subsets_best_reduce_kernel, dim3(p + 1, (unsigned)reps), dim3(64), 0, st, bv, bm, units, p + 1,
                      out_v, out_m, out_stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_top(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, uint32_t include, int T,
+                              uint32_t* tm, int32_t* tc, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !tm || !tc || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  if (T < 1 || T > SUBSETS_TOP_MAX) return hipErrorInvalidValue;
+  const int nh = a.p - a.q;
+  if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  // the sizes of a unit are popc(s) + popc(lane), s < per: per a power of two of at most SBS - 1 bits, STS lists
+  if (a.per > (1ull << (SBS - 1))) return hipErrorInvalidValue;
+  if (a.p < 32 && (include >> a.p) != 0u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_top_kernel, dim3((unsigned)units), dim3(64), top_lds_bytes(T), st, a, s0, s1, include, T,
+                     tm, tc);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_top_reduce(const double* tv, const uint32_t* tm, const int32_t* tc, int64_t units, int p, int T,
+                                     double* out_v, uint32_t* out_m, int32_t* out_c, hipStream_t st) {
+  if (!tv || !tm || !tc || !out_v || !out_m || !out_c || units < 1 || units > TRT * TRU || p < 1 || p > SP || T < 1 ||
+      T > SUBSETS_TOP_MAX)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_top_reduce_kernel, dim3(p + 1), dim3(TRT), 0, st, tv, tm, tc, (int)units, p + 1, T, out_v,
+                     out_m, out_c);
   return hipGetLastError();
 }
 

@@ -362,6 +362,18 @@ hipError_t launch_subsets_best(const SubsetArgs& a, uint64_t units, uint64_t s0,
 // rows of the tables and writes out_v + r out_stride, out_m + 2 r out_stride (out_stride >= p + 1)
 hipError_t launch_subsets_best_reduce(const double* bv, const uint32_t* bm, int64_t units, int p, double* out_v,
                                       uint32_t* out_m, hipStream_t st, int reps = 1, int64_t out_stride = 0);
+// The T best subsets of every size (lsspa_subsets_top), 1 <= T <= SUBSETS_TOP_MAX: launch_subsets_best's units, steps,
+// launches, candidates and order (one problem, no replicates), but a unit keeps per size a list of its T best so far,
+// best first: a.part [units][p + 1][T] the values, tm [units][p + 1][T] the masks (bit j = feature j), tc [units][p + 1]
+// how many entries of a list are valid.  tc is zeroed before the first launch (the entries need not be); every launch
+// merges into the lists.  The order is strict (masks are unique), so the lists do not depend on the launches' cut.
+constexpr int SUBSETS_TOP_MAX = 16;
+hipError_t launch_subsets_top(const SubsetArgs& a, uint64_t units, uint64_t s0, uint64_t s1, uint32_t include, int T,
+                              uint32_t* tm, int32_t* tc, hipStream_t st);
+// out_v [p + 1][T], out_m [p + 1][T], out_c [p + 1]: per size k the T best over the units' lists in the same order and
+// their number, min(T, candidates of size k); NaN and 0 past it.  units <= 8192.
+hipError_t launch_subsets_top_reduce(const double* tv, const uint32_t* tm, const int32_t* tc, int64_t units, int p, int T,
+                                     double* out_v, uint32_t* out_m, int32_t* out_c, hipStream_t st);
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used

@@ -50,7 +50,8 @@ struct ExactWork {
   DevBuf<double> Hh, w, part, out, vals;   // rect-mode test Gram, Shapley weights, partial table, its sums, debug values
   DevBuf<uint64_t> masks;                  // the debug values' subsets
   DevBuf<int32_t> info, tab;               // info word; GroupLayout::tab (groups only)
-  DevBuf<uint32_t> best;                   // lsspa_subsets_best: (mask, found) of the units' rows, then of the result
+  DevBuf<uint32_t> best;                   // lsspa_subsets_best: (mask, found) of the units' rows, then of the result;
+                                           // lsspa_subsets_top: the lists' masks and counts, then the result's
   double kernel_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
@@ -3515,6 +3516,65 @@ int subsets_best(lsspa_ctx* ctx, uint32_t include, double* v, uint32_t* masks, u
   return LSSPA_OK;
 }
 
+// lsspa_subsets_top: the same units, launches and timing once more; the table holds each unit's T best subsets per size,
+// values in ctx->sub.part [units][p + 1][T] and in ctx->sub.best the masks [units][p + 1][T], the counts [units][p + 1]
+// and behind them the result's masks [p + 1][T] and counts [p + 1].  What the call and its plan hook both go by:
+struct TopPlan {
+  uint64_t units, per, steps, launches;
+  int sizes;                 // sizes one unit can hold: popc(s) + popc(T), s < per, T < 2^q, and no more than p + 1
+  size_t rows;               // units (p + 1): lists in the table
+  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
+};
+TopPlan subsets_top_plan(int p, int T) {
+  TopPlan P;
+  const int q = subsets_low_features(p);
+  const uint64_t n_high = 1ull << (p - q);
+  P.units = exact_units(n_high);
+  P.per = n_high / P.units;
+  P.steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / P.units);
+  P.launches = (P.per + P.steps - 1) / P.steps;
+  int per_bits = 0;
+  while ((1ull << per_bits) < P.per) ++per_bits;
+  P.sizes = std::min(p, per_bits + q) + 1;
+  P.rows = (size_t)P.units * (p + 1);
+  P.bytes = (int64_t)P.rows * (12 * T + 4);
+  return P;
+}
+
+int subsets_top(lsspa_ctx* ctx, uint32_t include, int T, double* v, uint32_t* masks, int32_t* count, int32_t* info) {
+  SubsetArgs a;
+  TRY(subsets_args(ctx, a));
+  const int p = ctx->p;
+  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
+  if (T < 1 || T > SUBSETS_TOP_MAX) {
+    char msg[120];
+    snprintf(msg, sizeof msg, "lsspa_subsets_top keeps 1 .. %d subsets of every size (T = %d)", SUBSETS_TOP_MAX, T);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  const TopPlan P = subsets_top_plan(p, T);
+  a.per = P.per;
+  ExactWork& W = ctx->sub;
+  const size_t n_out = (size_t)(p + 1) * T;
+  TRY(dev_alloc(ctx, W.best, P.rows * T + P.rows + n_out + (size_t)p + 1));
+  uint32_t* tm = W.best.ptr;
+  int32_t* tc = reinterpret_cast<int32_t*>(tm + P.rows * T);
+  uint32_t* out_m = tm + P.rows * T + P.rows;
+  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
+  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * P.rows, ctx->stream));      // the counts; no entry is read beyond one
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_subsets_top(a, P.units, s0, s1, include, T, tm, tc, ctx->stream);
+  };
+  auto finish = [&](int64_t n_units) {
+    HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, n_units, p, T, W.out.ptr, out_m, out_c, ctx->stream));
+    HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
+    return (int)LSSPA_OK;
+  };
+  return exact_enumerate_with(ctx, W, (p + 1) * T, (uint64_t)1 << (p - a.q), P.steps, launch, finish, info);
+}
+
 // ---- ... over groups of columns (k_groups.hip) ----
 // One enumeration launch takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high subset
 // counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
@@ -3755,6 +3815,25 @@ int lsspa_subsets_best(lsspa_ctx* ctx, uint32_t include, double* v, uint32_t* ma
   return subsets_best(ctx, include, v, masks, found, info);
 } catch (...) {
   return abi_caught(ctx);
+}
+
+int lsspa_subsets_top(lsspa_ctx* ctx, uint32_t include, int32_t T, double* v, uint32_t* masks, int32_t* count,
+                      int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!v || !masks || !count) return ctx->fail(LSSPA_ERR_ARG, "v / masks / count is NULL");
+  return subsets_top(ctx, include, T, v, masks, count, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_subsets_top_plan(int32_t p, int32_t T, int64_t* plan) try {
+  if (!plan || p < 1 || p > SUBSETS_MAX_P || T < 1 || T > SUBSETS_TOP_MAX) return LSSPA_ERR_ARG;
+  const TopPlan P = subsets_top_plan(p, T);
+  const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, (int64_t)P.launches, P.sizes, P.bytes, T, 0};
+  std::copy(out, out + 8, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
 }
 
 int lsspa_subsets_timing(const lsspa_ctx* ctx, double* kernel_ms, double* max_launch_ms, int64_t* launches) try {

@@ -34,7 +34,7 @@ from ._native import LSSPANativeError
 from ._results import (BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
-                       SampledInteractionResults, ShapleyResults, SizeIncompatible, validate_data)
+                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -1325,6 +1325,83 @@ def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=Non
         best_size, best_subset = int(sizes[i]), subsets[i].copy()
     return BestSubsetsResults(sizes=sizes, subsets=subsets, r_squared=r_squared, theta=theta, best_size=best_size,
                               best_subset=best_subset, full_r_squared=float(full_r_squared))
+
+
+SUBSETS_TOP_MAX = 16       # include/lsspa.h, lsspa_subsets_top: ranks per size
+
+
+def ls_spa_top_subsets(X_train, X_test, y_train, y_test, reg=0., n_best=10, *, include=None, device=0, _engine=None):
+    """The ``n_best`` best models of every size by out-of-sample R^2, over all 2^p feature subsets (p <= 32): how much
+    worse is the next model?
+
+    ``ls_spa_best_subsets`` names one winner per size; with collinear regressors the runner-up often differs from it
+    by one swapped feature and 1e-4 of R^2.  This call runs the same enumeration (fp64, bitwise reproducible;
+    include/lsspa.h, lsspa_subsets_top) and keeps per size the ``n_best`` (1 .. 16) best subsets, best first: the
+    larger R^2, on equal values the subset with the smaller mask (bit j = feature j).  Rank 0 of every size is
+    ``ls_spa_best_subsets``'s winner, bit for bit.
+
+    include:  an iterable of column indices that every model must contain, as for ``ls_spa_best_subsets``; the sizes
+        then start at len(include).
+
+    Returns ``TopSubsetsResults``: ``sizes`` [n], ``n_models`` [n] (the valid ranks of a size: min(n_best, the number
+    of subsets of that size)), ``subsets`` [n][n_best][p] bool, ``r_squared`` [n][n_best] (descending along a row),
+    ``theta`` [n][n_best][p] (each listed model refitted on the host in fp64, exactly 0.0 outside its subset), ``gap``
+    [n][n_best] (``r_squared[:, :1] - r_squared``: the price of each alternative), ``top_sizes``, ``top_subsets``,
+    ``top_r_squared`` (the n_best best models over all sizes) and ``best_size``, ``best_subset``, ``full_r_squared``,
+    which are ``ls_spa_best_subsets``'s.  Ranks past ``n_models`` are NaN (False in ``subsets``).
+
+    p > 32, an ``n_best`` that is not an integer in 1 .. 16, an ``include`` out of range or with duplicates, shapes that
+    do not fit and a ``y_test`` that is identically zero are refused before any GPU work.  A subset whose Gram matrix
+    is not numerically positive definite is no candidate and raises the RuntimeWarning of ``ls_spa(method='subsets')``.
+    ``reg`` and ``device`` are that call's.  Not built: ``groups=`` (top lists over groups of columns) and a bootstrap
+    of the top list."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    p = data[0].shape[1]
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"ls_spa_top_subsets enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} "
+                         f"features (this problem has p = {p})")
+    if p < 1 or data[1].shape[0] < 1:
+        raise ValueError(f"ls_spa_top_subsets needs p >= 1 features and M >= 1 test rows (p = {p}, "
+                         f"M = {data[1].shape[0]})")
+    if isinstance(n_best, (bool, np.bool_)) or not isinstance(n_best, (int, np.integer)) \
+            or not 1 <= n_best <= SUBSETS_TOP_MAX:
+        raise ValueError(f"n_best must be an integer in 1 .. {SUBSETS_TOP_MAX} (got {n_best!r})")
+    T = int(n_best)
+    mask, inc = include_mask(include, p)
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+    with _engine_call(_engine, device) as engine:
+        # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like the values
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        _, full_r_squared, info = _load_and_fit(engine, data, reg, False, None)
+        v, masks, count, bits = engine.subsets_top(mask, T)
+        if info & 1:
+            _, full_r_squared = _singular_fit(engine, data[1], data[3])
+        G, g, _, _ = engine.gram()
+    _info_verdict((bits | info) & 1, stacklevel=2)      # (an enumeration reports a broken pivot, nothing else)
+    sizes = np.arange(len(inc), p + 1)
+    n = len(sizes)
+    n_models = np.asarray(count)[sizes].astype(np.int64)
+    subsets = np.zeros((n, T, p), dtype=bool)
+    r_squared = np.full((n, T), np.nan)
+    theta = np.full((n, T, p), np.nan)
+    for i, k in enumerate(sizes):
+        for r in range(n_models[i]):
+            subsets[i, r] = (int(masks[k, r]) >> np.arange(p)) & 1
+            r_squared[i, r] = v[k, r]
+            theta[i, r] = _subset_fit(G, g, np.nonzero(subsets[i, r])[0])
+    # the best over all sizes lie inside the per-size lists: a merge under the same order, larger value then smaller mask
+    ii, rr = np.nonzero(np.arange(T)[None, :] < n_models[:, None])
+    order = np.lexsort((np.asarray(masks)[sizes[ii], rr], -r_squared[ii, rr]))[:T]
+    best_size, best_subset = -1, np.zeros(p, dtype=bool)
+    if n_models.any():
+        i = int(np.nanargmax(r_squared[:, 0]))      # the first of equal maxima: the smallest size
+        best_size, best_subset = int(sizes[i]), subsets[i, 0].copy()
+    return TopSubsetsResults(sizes=sizes, n_models=n_models, subsets=subsets, r_squared=r_squared, theta=theta,
+                             gap=r_squared[:, :1] - r_squared, top_sizes=sizes[ii[order]],
+                             top_subsets=subsets[ii[order], rr[order]], top_r_squared=r_squared[ii[order], rr[order]],
+                             best_size=best_size, best_subset=best_subset, full_r_squared=float(full_r_squared))
 
 
 MULTI_MAX_COLS = 32767     # include/lsspa.h, lsspa_multi_load: p + m

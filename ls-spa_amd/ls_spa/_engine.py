@@ -186,6 +186,20 @@ def debug_groups_best_plan(labels):
     return dict(zip(GROUPS_BEST_PLAN_FIELDS, (int(v) for v in out)))
 
 
+SUBSETS_TOP_PLAN_FIELDS = ("units", "per", "steps", "launches", "sizes", "table_bytes", "reduce_rounds")
+
+
+def debug_subsets_top_plan(p: int, n_best: int):
+    """Test hook, host only: how subsets_top enumerates p features for n_best models a size (include/lsspa.h,
+    lsspa_debug_subsets_top_plan) -- a dict with SUBSETS_TOP_PLAN_FIELDS.  ValueError for a p or n_best the library
+    refuses."""
+    out = np.zeros(8, dtype=np.int64)
+    rc = N.load().lsspa_debug_subsets_top_plan(int(p), int(n_best), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_subsets_top_plan: status {rc}")
+    return dict(zip(SUBSETS_TOP_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -445,6 +459,23 @@ class HipEngine:
             self._h, int(include), N.dptr(v), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
             found.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)))
         return v, masks, found.astype(bool), info.value
+
+    SUBSETS_TOP_MAX = 16
+
+    def subsets_top(self, include=0, n_best=10):
+        """(v, masks, count, info): the n_best <= 16 best subsets of every size k = 0 .. p among those that contain the
+        columns of the mask `include`, best first -- the larger v, on equal values the smaller mask (include/lsspa.h,
+        lsspa_subsets_top): v [p + 1][n_best] float64, masks [p + 1][n_best] uint32 (bit j = feature j), count [p + 1]
+        int32, the valid ranks of a size (NaN / 0 past them).  Rank 0 is subsets_best's.  subsets_timing() then speaks
+        of this call."""
+        n, T = self.p + 1, int(n_best)
+        v, masks = np.empty((n, max(T, 0))), np.empty((n, max(T, 0)), dtype=np.uint32)
+        count = np.empty(n, dtype=np.int32)
+        info = C.c_int32()
+        self._check(self._lib.lsspa_subsets_top(
+            self._h, int(include), T, N.dptr(v), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            count.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        return v, masks, count, info.value
 
     # ---- bootstrap of the exact attribution (p <= 32; over groups of columns p <= 64) ------
     def boot_load(self, X_train, X_test, y_train, y_test, reg: float, grouped: bool = False):
@@ -859,8 +890,8 @@ class HipEngine:
         return out
 
     def subsets_timing(self):
-        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley, subsets_interactions or
-        subsets_best call."""
+        """(kernel seconds, longest launch in seconds, launches) of the last subsets_shapley, subsets_interactions,
+        subsets_best or subsets_top call."""
         return self._exact_timing(self._lib.lsspa_subsets_timing)
 
     def debug_subset_values(self, masks):

@@ -114,6 +114,8 @@ SIGNATURES = {
     "lsspa_subsets_shapley": (C.c_int, [_vp, _pd, _pi32]),
     "lsspa_subsets_interactions": (C.c_int, [_vp, _pd, _pd, _pi32]),
     "lsspa_subsets_best": (C.c_int, [_vp, C.c_uint32, _pd, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), _pi32]),
+    "lsspa_subsets_top": (C.c_int, [_vp, C.c_uint32, _i32, _pd, C.POINTER(C.c_uint32), _pi32, _pi32]),
+    "lsspa_debug_subsets_top_plan": (C.c_int, [_i32, _i32, _pi64]),
     "lsspa_subsets_timing": (C.c_int, [_vp, _pd, _pd, _pi64]),
     "lsspa_debug_subset_values": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64, _pd]),
     "lsspa_groups_shapley": (C.c_int, [_vp, _pi32, _i32, _pd, _pi32]),

@@ -223,6 +223,52 @@ class BestSubsetsResults:
 
 
 @dataclass
+class TopSubsetsResults:
+    """What ``ls_spa_top_subsets`` returns for p features, n = p + 1 - len(include) sizes and T = n_best ranks.
+    ``sizes`` [n]: the model sizes len(include) .. p; ``n_models`` [n]: how many ranks of a size are valid, min(T, the
+    number of subsets of that size that contain ``include``) unless subsets were dropped for a Gram matrix that is not
+    numerically positive definite; ``subsets`` [n][T][p] bool: rank r of size i, best first -- the larger R^2, on equal
+    values the subset with the smaller mask (bit j = feature j); ``r_squared`` [n][T]: its out-of-sample R^2,
+    descending along a row; ``theta`` [n][T][p]: its coefficients, exactly 0.0 outside the subset; ``gap`` [n][T]:
+    ``r_squared[:, :1] - r_squared``, what choosing rank r instead of the winner of its size costs.  Ranks past
+    ``n_models`` are NaN in ``r_squared``, ``theta`` and ``gap`` and False in ``subsets``.  ``top_sizes`` [m],
+    ``top_subsets`` [m][p] bool, ``top_r_squared`` [m]: the m = min(T, all valid ranks) best models over all sizes,
+    in the same order.  ``best_size``, ``best_subset`` and ``full_r_squared`` are ``ls_spa_best_subsets``'s."""
+    sizes: np.ndarray
+    n_models: np.ndarray
+    subsets: np.ndarray
+    r_squared: np.ndarray
+    theta: np.ndarray
+    gap: np.ndarray
+    top_sizes: np.ndarray
+    top_subsets: np.ndarray
+    top_r_squared: np.ndarray
+    best_size: int
+    best_subset: np.ndarray
+    full_r_squared: float
+
+    def __repr__(self):
+        pad = " " * 8
+        n, T, p = np.asarray(self.subsets).shape
+        chosen = ", ".join(str(j) for j in np.nonzero(self.best_subset)[0][:12])
+        best = runner = "nan"
+        if self.best_size >= 0:
+            best = f"{float(self.top_r_squared[0]):.2e}"
+        if len(self.top_r_squared) > 1:
+            runner = f"{float(self.top_r_squared[0] - self.top_r_squared[1]):.2e}"
+        lines = [
+            "",
+            f"{pad}p = {p}, the {T} best subsets of sizes {int(self.sizes[0])} .. {int(self.sizes[-1])}",
+            f"{pad}Out-of-sample R^2 with all features: {self.full_r_squared:.2e}",
+            f"{pad}Best model: {self.best_size} features, out-of-sample R^2 {best}",
+            f"{pad}Its features: ({chosen}{', ...' if int(np.sum(self.best_subset)) > 12 else ''})",
+            f"{pad}The next model over all sizes is worse by {runner}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class BestGroupSubsetsResults:
     """What ``ls_spa_best_subsets(groups=)`` returns for g groups over p columns: n = g + 1 sizes.  ``sizes`` [n]: 0 ..
     g, the number of groups in the model beside the baseline; ``group_subsets`` [n][g] bool: the best set of groups of
