@@ -175,7 +175,7 @@ int lsspa_debug_subsets_top_plan(int32_t p, int32_t T, int64_t* plan /* [8] */);
  * lsspa_subsets_shapley's state touched.  g > 32, p > 64, a label outside -1 .. g-1, an empty group, g < 1 or no
  * problem loaded is LSSPA_ERR_ARG (lsspa_last_error names it).
  *   lsspa_groups_timing      : as lsspa_subsets_timing, for the last lsspa_groups_shapley or
- *                              lsspa_groups_interactions call
+ *                              lsspa_groups_interactions call (and lsspa_groups_owen, _best, _top)
  *   lsspa_debug_group_values : test hook -- u[i] = u(masks[i]) (bit k = group k; masks < 2^g) by the enumeration's own
  *                              device code; a failed pivot is LSSPA_ERR_STATE */
 int lsspa_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi /* [g] */, int32_t* info);
@@ -219,6 +219,31 @@ int lsspa_groups_interactions(lsspa_ctx* ctx, const int32_t* labels, int32_t g, 
 int lsspa_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* u /* [g+1] */,
                       uint32_t* masks /* [g+1] */, uint8_t* found /* [g+1] */, int32_t* info);
 int lsspa_debug_groups_best_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* plan /* [8] */);
+
+/* The T best group subsets of every size (1 <= T <= 16): lsspa_groups_best's enumeration, u, candidates (own pivots
+ * passed, NaN never listed) and order, keeping per size k = 0 .. g (the number of groups) not one winner but a list,
+ *   u[k][r], masks[k][r], r < count[k] = min(T, number of candidates of k groups),
+ * best first: the larger value, on equal values the numerically smaller mask in the caller's numbering (bit k = label
+ * k).  Masks are unique, so the order is strict and the list depends neither on how the work is cut into units and
+ * launches nor on which groups the layout makes low.  Entries past count[k] are NaN / 0.  Rank 0 is bitwise
+ * lsspa_groups_best's (value, mask, found); every listed value has the very bits lsspa_debug_group_values returns for
+ * its mask; the lists of a call with T are the first T ranks of a call with a larger T; two calls agree bitwise (no
+ * atomics on the table).
+ * Labels, limits, refusals and their messages are lsspa_groups_best's; T outside 1 .. 16 is LSSPA_ERR_ARG naming the
+ * limit; NULL labels, u, masks or count is LSSPA_ERR_ARG, info may be NULL (LSSPA_INFO_NOT_PD as there).  It shares
+ * lsspa_groups_shapley's buffers (a call of that, or of lsspa_groups_best, before and after this one agrees bitwise)
+ * and leaves its timing where lsspa_groups_timing reads it; nothing of the sampling path, of lsspa_subsets_shapley's
+ * state or of the bootstrap store changes.
+ * Device memory: the units' lists, units (g + 1) of them with units = min(2^gh, 8192), 12 bytes an entry (value, mask)
+ * and 4 a list (count): at most 8192 x 33 x (12 x 16 + 4) bytes = 53 MB.
+ *   lsspa_debug_groups_top_plan : host only (no context, no GPU) -- plan[0 .. 9] = gl, gh, ql, nb, units, per (as
+ *                                 lsspa_debug_groups_best_plan's), steps of a unit per launch, launches, the most sizes
+ *                                 one unit holds (at most 25) and the bytes of the table; from the function the call
+ *                                 itself uses.  Labels that lsspa_groups_best would refuse, or T outside 1 .. 16:
+ *                                 LSSPA_ERR_ARG. */
+int lsspa_groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int32_t T, double* u /* [g+1][T] */,
+                     uint32_t* masks /* [g+1][T] */, int32_t* count /* [g+1] */, int32_t* info);
+int lsspa_debug_groups_top_plan(const int32_t* labels, int32_t p, int32_t g, int32_t T, int64_t* plan /* [10] */);
 
 /* Exact Owen values: the attribution of every COLUMN with the groups as coalition structure, the two-level Shapley
  * value.  Labels, B, u and v as lsspa_groups_shapley's.  For a column i of group k, with B_k the group's columns,

@@ -629,6 +629,140 @@ __global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s
   if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<REPS>(1), 1);
 }
 
+// ---- the T best group subsets of every size (lsspa_groups_top) ----
+// groups_best_kernel's sibling, one problem only: the same workgroup, units, steps and launches, load_shared<false> and
+// group_values<false>, the same candidates (the subset's own pivots passed, its value is above -inf, so never NaN) and
+// the same total order -- the larger value first, on equal values the numerically smaller mask in the CALLER's
+// numbering.  What is kept per size k is not one winner but the T best, 1 <= T <= GROUPS_TOP_MAX.  Masks are unique, so
+// the order is strict and the T best of any collection of subsets are one definite list: the result depends neither on
+// the cut into units and launches nor on the order of the inserts.
+//   Lists: |S| = popc(unit) + popc(s) + popc(lane), so a unit meets at most GTS = (GBS - 1) + GQ + 1 = 25 sizes,
+// popc(unit) + j with j = popc(s) + popc(lane).  Per such j it keeps a sorted list of up to T (value, caller mask) and a
+// count in LDS, k_subsets.hip's subsets_top_kernel's lists at a fixed row stride of GROUPS_TOP_MAX: 4.9 KB beside
+// GrpShared, against the sibling's 14.6 KB.  The lists hold caller masks, for the threshold compare and the rank go by
+// the caller's order: a lane's low part is fixed and translated once, the high part of hi is the same for the whole
+// workgroup and translated once per step from the kernel's own arguments (GroupIds), on the scalar unit.  A launch loads
+// the unit's lists from its rows of the table and stores them back at its end (one workgroup owns a row, launches are
+// ordered by the stream: plain loads and stores); the counts are cleared before the first launch, the entries need
+// not be.
+//   Fast path and insert are subsets_top_kernel's: a live lane compares its value with its list's last entry, one ballot
+// says whether anything is to be inserted, and the insert is a wave-wide rank-and-shift with lane t < T holding entry t.
+// The one difference: four waves run the step, only wave 0 holds values.  The lists are wave 0's alone -- loaded before
+// load_shared's barrier, read and written between the last barrier of group_values and the barrier that ends the step,
+// stored after the last step's -- and the insert loop, which only wave 0 executes, contains no workgroup barrier.  What
+// orders its LDS writes against the reads of the next round is the wave itself: the 64 lanes are one instruction stream,
+// the LDS executes one wave's instructions in the order of their issue, and wave_lds_fence (a release/acquire fence of
+// wavefront scope, no instruction of its own) keeps the compiler from moving a read of the lists over a write of them
+// or from keeping an entry in a register across the round.
+constexpr int GTS = (GBS - 1) + GQ + 1;        // sizes a unit meets at most
+constexpr int GTM = GROUPS_TOP_MAX;            // row stride of the lists in LDS
+
+struct GrpTopShared {
+  double v[GTS * GTM];     // [size j][rank]: the unit's best values of size popc(unit) + j, best first
+  uint32_t m[GTS * GTM];   // their caller masks
+  int c[GTS];              // valid entries of a list
+  int gid[GG];
+};
+
+// does (v, m) come before (ov, om) in the total order? (k_subsets.hip, top_before)
+__device__ inline bool top_before(double v, uint32_t m, double ov, uint32_t om) { return v > ov || (v == ov && m < om); }
+
+// orders one wave's LDS accesses in program order (the header of this section)
+__device__ inline void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a.part [units][g + 1][T] (values), tm [units][g + 1][T] (caller masks), tc [units][g + 1] (counts): unit u's T best of
+// every size so far, best first
+__global__ __launch_bounds__(NT) void groups_top_kernel(GroupArgs a, uint64_t s0, uint64_t s1, GroupIds ids, int T,
+                                                        uint32_t* __restrict__ tm, int32_t* __restrict__ tc) {
+  __shared__ GrpShared sh;
+  __shared__ GrpTopShared st;
+  const int tid = threadIdx.x;
+  const int ng = a.ng, gl = a.gl;
+  const bool live = tid < (1 << gl);           // wave 0 only (gl <= 6)
+  // the sizes this unit can hold: k0 + j, j < ns (popc(s) + popc(lane) with s < per, lane < 2^gl, and no more than ng)
+  const int k0 = __popc(blockIdx.x);
+  const int ns = min(ng - k0, __popcll(a.per - 1) + gl) + 1;       // <= GTS: launch_groups_top
+  double* gv = a.part + ((int64_t)blockIdx.x * (ng + 1) + k0) * T;
+  uint32_t* gm = tm + ((int64_t)blockIdx.x * (ng + 1) + k0) * T;
+  int32_t* gc = tc + (int64_t)blockIdx.x * (ng + 1) + k0;
+  if (tid < 64) {
+    for (int e = tid; e < ns * T; e += 64) {
+      const int j = e / T, r = e - j * T;
+      if (r < gc[j]) {
+        st.v[j * GTM + r] = gv[e];
+        st.m[j * GTM + r] = gm[e];
+      }
+    }
+    if (tid < ns) st.c[tid] = gc[tid];
+  }
+  if (tid < GG) st.gid[tid] = ids.id[tid];
+  load_shared<false>(sh, a, tid);              // (ends with a barrier: the lists, gid)
+  uint32_t low = 0u;                           // the lane's low groups in the caller's numbering
+  for (int r = 0; r < gl; ++r)
+    if ((tid >> r) & 1) low |= 1u << st.gid[r];
+  const int jl = live ? __popc(tid) : 0;
+  bool any_bad = false;
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    bool bad = false;                          // this subset's own pivots, as in groups_best_kernel
+    const double v = group_values<false>(sh, a, hi, tid, bad);
+    any_bad |= bad;
+    if (tid < 64) {                            // wave 0: no workgroup barrier in here
+      // the high groups of hi in the caller's numbering: the same for every lane (gh <= 31)
+      uint32_t hm = 0u;
+      for (uint32_t b = (uint32_t)hi; b != 0u; b &= b - 1u) hm |= 1u << ids.id[gl + __ffs((int)b) - 1];
+      const uint32_t m = hm | low;
+      const int j = __popcll(s) + jl;          // < ns for every live lane
+      // a candidate that belongs into its size's list as it is now: the list is not full, or its last entry comes later
+      auto wanted = [&]() {
+        return st.c[j] < T || top_before(v, m, st.v[j * GTM + T - 1], st.m[j * GTM + T - 1]);
+      };
+      bool want = live && !bad && v > -__builtin_huge_val() && wanted();
+      for (uint64_t todo = __ballot(want); todo != 0ull; todo = __ballot(want)) {
+        const int src = __ffsll((unsigned long long)todo) - 1;
+        const double nv = __shfl(v, src, 64);
+        const uint32_t nm = (uint32_t)__shfl((int)m, src, 64);
+        const int nj = __shfl(j, src, 64);
+        double* rv = st.v + nj * GTM;
+        uint32_t* rm = st.m + nj * GTM;
+        const int c = st.c[nj];
+        const bool have = tid < c;             // c <= T <= 16: lane t holds entry t
+        const double ev = have ? rv[tid] : 0.0;
+        const uint32_t em = have ? rm[tid] : 0u;
+        const int rank = __popcll(__ballot(have && top_before(ev, em, nv, nm)));
+        const double pv = __shfl_up(ev, 1, 64);
+        const uint32_t pm = (uint32_t)__shfl_up((int)em, 1, 64);
+        const int nc = min(c + 1, T);
+        wave_lds_fence();                      // every lane has read its entry and the count
+        if (tid >= rank && tid < nc) {         // a lane writes the entry it read: no other lane's
+          rv[tid] = tid == rank ? nv : pv;
+          rm[tid] = tid == rank ? nm : pm;
+        }
+        if (tid == 0) st.c[nj] = nc;
+        wave_lds_fence();                      // the list as it now is, for every lane
+        if (tid == src) want = false;
+        want = want && wanted();
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < 64) {
+    for (int e = tid; e < ns * T; e += 64) {
+      const int j = e / T, r = e - j * T;
+      if (r < st.c[j]) {
+        gv[e] = st.v[j * GTM + r];
+        gm[e] = st.m[j * GTM + r];
+      }
+    }
+    if (tid < ns) gc[tid] = st.c[tid];
+  }
+  if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info, 1);
+}
+
 // masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
 __global__ __launch_bounds__(NT) void groups_debug_kernel(GroupArgs a, const uint64_t* __restrict__ masks, int64_t n,
                                                           double* __restrict__ vals) {
@@ -769,6 +903,26 @@ hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units
                        bm);
   else
     hipLaunchKernelGGL(groups_best_kernel<false>, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1, ids, bm);
+  return hipGetLastError();
+}
+
+hipError_t launch_groups_top(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1, int T,
+                             uint32_t* tm, int32_t* tc, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !tm || !tc || !gid || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  if (T < 1 || T > GROUPS_TOP_MAX) return hipErrorInvalidValue;
+  if (a.inv_yy_rep) return hipErrorInvalidValue;     // no replicates: one problem
+  if (a.gh > GHI) return hipErrorInvalidValue;       // hi is kept in 32 bits (no layout of <= 64 columns has gh = 32)
+  if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  // the sizes of a unit are popc(s) + popc(lane), s < per: per a power of two of at most GBS - 1 bits, GTS lists
+  if (a.per > (1ull << (GBS - 1))) return hipErrorInvalidValue;
+  GroupIds ids{};
+  uint32_t seen = 0u;
+  for (int r = 0; r < a.ng; ++r) {                   // a permutation of 0 .. ng-1: the kernel shifts by them
+    if (gid[r] < 0 || gid[r] >= a.ng || ((seen >> gid[r]) & 1u)) return hipErrorInvalidValue;
+    seen |= 1u << gid[r];
+    ids.id[r] = (uint8_t)gid[r];
+  }
+  hipLaunchKernelGGL(groups_top_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1, ids, T, tm, tc);
   return hipGetLastError();
 }
 

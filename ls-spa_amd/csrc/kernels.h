@@ -450,6 +450,15 @@ hipError_t launch_groups_owen(const GroupArgs& a, uint64_t units, uint64_t s0, u
 constexpr int GROUPS_BEST_CLASSES = 19;   // per <= 2^18: gh <= 31 high groups over 8192 units (lsspa_api.hip asserts it)
 hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1,
                               uint32_t* bm, hipStream_t st, int reps = 1);
+// The T best group subsets of every size (lsspa_groups_top), 1 <= T <= GROUPS_TOP_MAX: launch_groups_best's units,
+// steps, launches, candidates, order and refusals (one problem: GroupArgs::inv_yy_rep is refused), but a unit keeps per
+// size a list of its T best so far, best first: a.part [units][g + 1][T] the values, tm [units][g + 1][T] the masks in
+// the CALLER's numbering, tc [units][g + 1] how many entries of a list are valid.  tc is zeroed before the first launch
+// (the entries need not be); every launch merges into the lists.  The order is strict (masks are unique), so the lists
+// do not depend on the launches' cut.  launch_subsets_top_reduce (p = g) merges the units' lists.
+constexpr int GROUPS_TOP_MAX = SUBSETS_TOP_MAX;
+hipError_t launch_groups_top(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1, int T,
+                             uint32_t* tm, int32_t* tc, hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

@@ -51,7 +51,8 @@ struct ExactWork {
   DevBuf<uint64_t> masks;                  // the debug values' subsets
   DevBuf<int32_t> info, tab;               // info word; GroupLayout::tab (groups only)
   DevBuf<uint32_t> best;                   // lsspa_subsets_best: (mask, found) of the units' rows, then of the result;
-                                           // lsspa_subsets_top: the lists' masks and counts, then the result's
+                                           // lsspa_subsets_top, lsspa_groups_top: the lists' masks and counts, then
+                                           // the result's
   double kernel_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
@@ -3674,6 +3675,64 @@ int groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* u, uin
   return LSSPA_OK;
 }
 
+// lsspa_groups_top: the same units, launches and timing once more; the table holds each unit's T best group subsets per
+// size, values in ctx->grp.part [units][g + 1][T] and in ctx->grp.best the caller masks [units][g + 1][T], the counts
+// [units][g + 1] and behind them the result's masks [g + 1][T] and counts [g + 1] (subsets_top's layout of
+// ctx->sub.best).  What the call and its plan hook both go by:
+struct GroupTopPlan {
+  uint64_t units, per, steps, launches;
+  int sizes;                 // sizes one unit can hold: popc(s) + popc(T), s < per, T < 2^gl, and no more than g + 1
+  size_t rows;               // units (g + 1): lists in the table
+  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
+};
+GroupTopPlan groups_top_plan(const GroupLayout& L, int T) {
+  GroupTopPlan P;
+  const uint64_t n_high = 1ull << L.gh;
+  P.units = exact_units(n_high);
+  P.per = n_high / P.units;
+  P.steps = groups_steps(L, P.units);
+  P.launches = (P.per + P.steps - 1) / P.steps;
+  P.sizes = std::min(L.ng, __builtin_popcountll(P.per - 1) + L.gl) + 1;
+  P.rows = (size_t)P.units * (L.ng + 1);
+  P.bytes = (int64_t)P.rows * (12 * T + 4);
+  return P;
+}
+
+int groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int T, double* u, uint32_t* masks, int32_t* count,
+               int32_t* info) {
+  GroupArgs a;
+  GroupLayout L;
+  TRY(groups_args(ctx, labels, g, a, L));
+  if (T < 1 || T > GROUPS_TOP_MAX) {
+    char msg[120];
+    snprintf(msg, sizeof msg, "lsspa_groups_top keeps 1 .. %d subsets of every size (T = %d)", GROUPS_TOP_MAX, T);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  const int ng = L.ng;
+  const GroupTopPlan P = groups_top_plan(L, T);
+  a.per = P.per;
+  ExactWork& W = ctx->grp;
+  const size_t n_out = (size_t)(ng + 1) * T;
+  TRY(dev_alloc(ctx, W.best, P.rows * T + P.rows + n_out + (size_t)ng + 1));
+  uint32_t* tm = W.best.ptr;
+  int32_t* tc = reinterpret_cast<int32_t*>(tm + P.rows * T);
+  uint32_t* out_m = tm + P.rows * T + P.rows;
+  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
+  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * P.rows, ctx->stream));      // the counts; no entry is read beyond one
+  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
+    a.part = part;
+    return launch_groups_top(a, L.gid, P.units, s0, s1, T, tm, tc, ctx->stream);
+  };
+  auto finish = [&](int64_t n_units) {
+    HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, n_units, ng, T, W.out.ptr, out_m, out_c, ctx->stream));
+    HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
+    return (int)LSSPA_OK;
+  };
+  return exact_enumerate_with(ctx, W, (ng + 1) * T, (uint64_t)1 << L.gh, P.steps, launch, finish, info);
+}
+
 // ---- Owen value: the columns of a group, with the groups as coalition structure (k_groups.hip's header) ----
 // The refined game of target group k (b columns) has g - 1 + b players: the other groups whole (the outer players) and
 // the target's columns as singletons (the inner players), numbered in the caller's order with the target's columns in
@@ -3940,6 +3999,28 @@ int lsspa_debug_groups_best_plan(const int32_t* labels, int32_t p, int32_t g, in
   plan[5] = (int64_t)per;
   plan[6] = (int64_t)((per + steps - 1) / steps);
   plan[7] = __builtin_popcountll(per - 1) + 1;       // size classes of a unit: popc(s), s < per
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
+}
+
+int lsspa_groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int32_t T, double* u, uint32_t* masks,
+                     int32_t* count, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (!labels || !u || !masks || !count) return ctx->fail(LSSPA_ERR_ARG, "labels / u / masks / count is NULL");
+  return groups_top(ctx, labels, g, T, u, masks, count, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_groups_top_plan(const int32_t* labels, int32_t p, int32_t g, int32_t T, int64_t* plan) try {
+  GroupLayout L;
+  if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || T < 1 || T > GROUPS_TOP_MAX || groups_layout(labels, p, g, L))
+    return LSSPA_ERR_ARG;
+  const GroupTopPlan P = groups_top_plan(L, T);
+  const int64_t out[10] = {L.gl, L.gh, L.ql, L.nb, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps,
+                           (int64_t)P.launches, P.sizes, P.bytes};
+  std::copy(out, out + 10, plan);
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_ARG;

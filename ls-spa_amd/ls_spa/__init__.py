@@ -21,18 +21,19 @@ each feature, each size and each winner is chosen again on resampled rows, retur
 and ``ls_spa_best_group_subsets_bootstrap`` (the same over groups of columns, g <= 32 groups of p <= 64 columns: the
 bootstrap of ``ls_spa_best_subsets(groups=)``, returning ``BestGroupSubsetsBootstrapResults``) and
 ``ls_spa_top_subsets`` (the n_best <= 16 best models of every size, p <= 32: how much worse is the next model?,
-returning ``TopSubsetsResults``)
+returning ``TopSubsetsResults``) and ``ls_spa_top_group_subsets`` (the same over groups of columns, g <= 32 groups of
+p <= 64 columns: the n_best <= 16 best sets of groups of every size, returning ``TopGroupSubsetsResults``)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import (BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
-                       TopSubsetsResults, validate_data)
+                       TopGroupSubsetsResults, TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
 from ._driver import (ls_spa, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
-                      ls_spa_permutation_test, ls_spa_top_subsets,
+                      ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_subsets,
                       reduce_data, square_shapley, run_estimator, release)
 from ._native import LSSPANativeError
 from ._rccl import NativeComm
@@ -49,4 +50,5 @@ __all__ = [
     "ls_spa_best_subsets_bootstrap", "BestSubsetsBootstrapResults",
     "ls_spa_best_group_subsets_bootstrap", "BestGroupSubsetsBootstrapResults",
     "ls_spa_top_subsets", "TopSubsetsResults",
+    "ls_spa_top_group_subsets", "TopGroupSubsetsResults",
 ]

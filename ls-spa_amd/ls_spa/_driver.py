@@ -34,7 +34,7 @@ from ._native import LSSPANativeError
 from ._results import (BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
-                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopSubsetsResults, validate_data)
+                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsResults, TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -1353,8 +1353,8 @@ def ls_spa_top_subsets(X_train, X_test, y_train, y_test, reg=0., n_best=10, *, i
     p > 32, an ``n_best`` that is not an integer in 1 .. 16, an ``include`` out of range or with duplicates, shapes that
     do not fit and a ``y_test`` that is identically zero are refused before any GPU work.  A subset whose Gram matrix
     is not numerically positive definite is no candidate and raises the RuntimeWarning of ``ls_spa(method='subsets')``.
-    ``reg`` and ``device`` are that call's.  Not built: ``groups=`` (top lists over groups of columns) and a bootstrap
-    of the top list."""
+    ``reg`` and ``device`` are that call's.  Top lists over groups of columns (a one-hot factor, a spline basis; more
+    than 32 columns) are a call of their own, ``ls_spa_top_group_subsets``.  Not built: a bootstrap of the top list."""
     data = _coerce_data(X_train, X_test, y_train, y_test)
     p = data[0].shape[1]
     if p > SUBSETS_MAX_P:
@@ -1402,6 +1402,91 @@ def ls_spa_top_subsets(X_train, X_test, y_train, y_test, reg=0., n_best=10, *, i
                              gap=r_squared[:, :1] - r_squared, top_sizes=sizes[ii[order]],
                              top_subsets=subsets[ii[order], rr[order]], top_r_squared=r_squared[ii[order], rr[order]],
                              best_size=best_size, best_subset=best_subset, full_r_squared=float(full_r_squared))
+
+
+GROUPS_TOP_MAX = 16        # include/lsspa.h, lsspa_groups_top: ranks per size
+
+
+def ls_spa_top_group_subsets(X_train, X_test, y_train, y_test, groups, reg=0., n_best=10, *, device=0, _engine=None):
+    """The ``n_best`` best models of every size by out-of-sample R^2, over all 2^g subsets of groups of columns (g <= 32
+    groups over p <= 64 columns): how much worse is the next set of variables?
+
+    ``ls_spa_best_subsets(groups=)`` names one winner per number of groups; two variables that carry nearly the same
+    signal make the runner-up differ from it by one swapped variable and 1e-4 of R^2.  This call runs the same
+    enumeration (fp64, bitwise reproducible; include/lsspa.h, lsspa_groups_top) and keeps per size the ``n_best``
+    (1 .. 16) best sets of groups, best first: the larger R^2, on equal values the set with the smaller mask (bit k =
+    group k).  Rank 0 of every size is ``ls_spa_best_subsets(groups=)``'s winner, bit for bit.  The cost is set by g,
+    not by p, and the p <= 32 limit of ``ls_spa_top_subsets`` does not apply.
+
+    groups:  one label per column as ``ls_spa_best_subsets(groups=)`` takes them: k in 0 .. g-1 puts the column into
+        group k, -1 into the baseline that every model contains.  There is no ``include=``: the baseline is the
+        include set.
+
+    Returns ``TopGroupSubsetsResults``: ``sizes`` 0 .. g, ``n_models`` [n] (the valid ranks of a size: min(n_best,
+    C(g, size))), ``group_subsets`` [n][n_best][g] bool, ``subsets`` [n][n_best][p] bool (the baseline's and the listed
+    groups' columns), ``n_columns`` [n][n_best], ``r_squared`` [n][n_best] (descending along a row), ``theta``
+    [n][n_best][p] (each listed model refitted on the host in fp64, exactly 0.0 outside its columns), ``gap``
+    [n][n_best] (``r_squared[:, :1] - r_squared``: the price of each alternative), ``top_sizes``,
+    ``top_group_subsets``, ``top_subsets``, ``top_r_squared`` (the n_best best models over all sizes) and
+    ``best_size``, ``best_group_subset``, ``best_subset``, ``full_r_squared``, ``baseline_r_squared``, which are
+    ``ls_spa_best_subsets(groups=)``'s.  Ranks past ``n_models`` are NaN (False in the subsets, 0 in ``n_columns``).
+
+    Bad labels, p > 64, g > 32, an ``n_best`` that is not an integer in 1 .. 16, shapes that do not fit and a ``y_test``
+    that is identically zero are refused before any GPU work.  A group subset whose Gram matrix is not numerically
+    positive definite is no candidate and raises the RuntimeWarning of ``ls_spa(method='subsets')``.  ``reg`` and
+    ``device`` are that call's.  Not built: a bootstrap of the top list."""
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    p = data[0].shape[1]
+    if p > GROUPS_MAX_P:
+        raise ValueError(f"grouped attribution takes at most p = {GROUPS_MAX_P} columns, the baseline's included "
+                         f"(this problem has p = {p})")
+    labels, g = group_labels(groups, p)
+    if isinstance(n_best, (bool, np.bool_)) or not isinstance(n_best, (int, np.integer)) \
+            or not 1 <= n_best <= GROUPS_TOP_MAX:
+        raise ValueError(f"n_best must be an integer in 1 .. {GROUPS_TOP_MAX} (got {n_best!r})")
+    T = int(n_best)
+    if data[1].shape[0] < 1:
+        raise ValueError(f"ls_spa_top_group_subsets needs M >= 1 test rows (M = {data[1].shape[0]})")
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: the out-of-sample R^2 is not defined")
+    with _engine_call(_engine, device) as engine:
+        # precision stays set on a kept engine: theta and r_squared come from its fp64 factorisation, like the values
+        if getattr(engine, "precision", "float64") != "float64":
+            engine.set_precision("float64")
+        _, full_r_squared, info = _load_and_fit(engine, data, reg, False, None)
+        u, masks, count, bits = engine.groups_top(labels, T)
+        if info & 1:
+            _, full_r_squared = _singular_fit(engine, data[1], data[3])
+        G, gv, _, _ = engine.gram()
+    _info_verdict((bits | info) & 1, stacklevel=2)      # (an enumeration reports a broken pivot, nothing else)
+    sizes = np.arange(g + 1)
+    n = g + 1
+    n_models = np.asarray(count).astype(np.int64)
+    group_subsets = np.zeros((n, T, g), dtype=bool)
+    subsets = np.zeros((n, T, p), dtype=bool)
+    r_squared = np.full((n, T), np.nan)
+    theta = np.full((n, T, p), np.nan)
+    for k in sizes:
+        for r in range(n_models[k]):
+            group_subsets[k, r] = (int(masks[k, r]) >> np.arange(g)) & 1
+            subsets[k, r] = (labels < 0) | group_subsets[k, r][np.maximum(labels, 0)]
+            r_squared[k, r] = u[k, r]
+            theta[k, r] = _subset_fit(G, gv, np.nonzero(subsets[k, r])[0])
+    # the best over all sizes lie inside the per-size lists: a merge under the same order, larger value then smaller mask
+    ii, rr = np.nonzero(np.arange(T)[None, :] < n_models[:, None])
+    order = np.lexsort((np.asarray(masks)[ii, rr], -r_squared[ii, rr]))[:T]
+    best_size, best_groups, best_subset = -1, np.zeros(g, dtype=bool), np.zeros(p, dtype=bool)
+    if n_models.any():
+        best_size = int(np.nanargmax(r_squared[:, 0]))      # the first of equal maxima: the smallest size
+        best_groups, best_subset = group_subsets[best_size, 0].copy(), subsets[best_size, 0].copy()
+    return TopGroupSubsetsResults(sizes=sizes, n_models=n_models, group_subsets=group_subsets, subsets=subsets,
+                                  n_columns=subsets.sum(axis=2), r_squared=r_squared, theta=theta,
+                                  gap=r_squared[:, :1] - r_squared, top_sizes=sizes[ii[order]],
+                                  top_group_subsets=group_subsets[ii[order], rr[order]],
+                                  top_subsets=subsets[ii[order], rr[order]],
+                                  top_r_squared=r_squared[ii[order], rr[order]], best_size=best_size,
+                                  best_group_subset=best_groups, best_subset=best_subset,
+                                  full_r_squared=float(full_r_squared), baseline_r_squared=float(r_squared[0, 0]))
 
 
 MULTI_MAX_COLS = 32767     # include/lsspa.h, lsspa_multi_load: p + m

@@ -186,6 +186,22 @@ def debug_groups_best_plan(labels):
     return dict(zip(GROUPS_BEST_PLAN_FIELDS, (int(v) for v in out)))
 
 
+GROUPS_TOP_PLAN_FIELDS = ("gl", "gh", "ql", "nb", "units", "per", "steps", "launches", "sizes", "table_bytes")
+
+
+def debug_groups_top_plan(labels, n_best: int):
+    """Test hook, host only: how groups_top enumerates the group game of these labels for n_best models a size
+    (include/lsspa.h, lsspa_debug_groups_top_plan) -- a dict with GROUPS_TOP_PLAN_FIELDS.  ValueError for labels or an
+    n_best the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(10, dtype=np.int64)
+    rc = N.load().lsspa_debug_groups_top_plan(N.iptr(labels), len(labels), g, int(n_best), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_groups_top_plan: status {rc}")
+    return dict(zip(GROUPS_TOP_PLAN_FIELDS, (int(v) for v in out)))
+
+
 SUBSETS_TOP_PLAN_FIELDS = ("units", "per", "steps", "launches", "sizes", "table_bytes", "reduce_rounds")
 
 
@@ -959,9 +975,30 @@ class HipEngine:
             found.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)))
         return u, masks, found.astype(bool), info.value
 
+    GROUPS_TOP_MAX = 16
+
+    def groups_top(self, labels, n_best=10):
+        """(u, masks, count, info): the n_best <= 16 best group subsets of every size k = 0 .. g, best first -- the
+        larger u, on equal values the smaller mask (include/lsspa.h, lsspa_groups_top): u [g + 1][n_best] float64, masks
+        [g + 1][n_best] uint32 (bit k = group k), count [g + 1] int32, the valid ranks of a size (NaN / 0 past them).
+        Rank 0 is groups_best's.  groups_timing() then speaks of this call."""
+        labels, g = self._labels(labels)
+        if len(labels) != self.p:
+            raise ValueError(f"labels must have length p = {self.p}")
+        n, T = max(g, 0) + 1, int(n_best)
+        u, masks = np.empty((n, max(T, 0))), np.empty((n, max(T, 0)), dtype=np.uint32)
+        count = np.empty(n, dtype=np.int32)
+        info = C.c_int32()
+        self._check(self._lib.lsspa_groups_top(
+            self._h, N.iptr(labels), g, T, N.dptr(u), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            count.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        return u, masks, count, info.value
+
+    debug_groups_top_plan = staticmethod(debug_groups_top_plan)
+
     def groups_timing(self):
         """(kernel seconds, longest launch in seconds, launches) of the last groups_shapley, groups_interactions,
-        groups_owen or groups_best call."""
+        groups_owen, groups_best or groups_top call."""
         return self._exact_timing(self._lib.lsspa_groups_timing)
 
     def debug_group_values(self, labels, masks):

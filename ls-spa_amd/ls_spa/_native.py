@@ -124,6 +124,8 @@ SIGNATURES = {
     "lsspa_debug_group_values": (C.c_int, [_vp, _pi32, _i32, C.POINTER(C.c_uint64), _i64, _pd]),
     "lsspa_groups_best": (C.c_int, [_vp, _pi32, _i32, _pd, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), _pi32]),
     "lsspa_debug_groups_best_plan": (C.c_int, [_pi32, _i32, _i32, _pi64]),
+    "lsspa_groups_top": (C.c_int, [_vp, _pi32, _i32, _i32, _pd, C.POINTER(C.c_uint32), _pi32, _pi32]),
+    "lsspa_debug_groups_top_plan": (C.c_int, [_pi32, _i32, _i32, _i32, _pi64]),
     "lsspa_groups_owen": (C.c_int, [_vp, _pi32, _i32, _pd, _pd, _pi32]),
     "lsspa_debug_owen_plan": (C.c_int, [_pi32, _i32, _i32, _pi64]),
     "lsspa_set_players": (C.c_int, [_vp, _pi32, _i32]),

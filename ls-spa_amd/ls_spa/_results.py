@@ -313,6 +313,63 @@ class BestGroupSubsetsResults:
 
 
 @dataclass
+class TopGroupSubsetsResults:
+    """What ``ls_spa_top_group_subsets`` returns for g groups over p columns, n = g + 1 sizes and T = n_best ranks.
+    ``sizes`` [n]: 0 .. g, the number of groups in a model beside the baseline; ``n_models`` [n]: how many ranks of a
+    size are valid, min(T, C(g, size)) unless group subsets were dropped for a Gram matrix that is not numerically
+    positive definite; ``group_subsets`` [n][T][g] bool: rank r of size i, best first -- the larger R^2, on equal values
+    the set with the smaller mask (bit k = group k); ``subsets`` [n][T][p] bool: its columns, the baseline's (label -1)
+    and its groups'; ``n_columns`` [n][T]: how many those are; ``r_squared`` [n][T]: its out-of-sample R^2, descending
+    along a row; ``theta`` [n][T][p]: its coefficients, exactly 0.0 outside its columns; ``gap`` [n][T]:
+    ``r_squared[:, :1] - r_squared``, what choosing rank r instead of the winner of its size costs.  Ranks past
+    ``n_models`` are NaN in ``r_squared``, ``theta`` and ``gap``, False in ``group_subsets`` and ``subsets`` and 0 in
+    ``n_columns``.  ``top_sizes`` [m], ``top_group_subsets`` [m][g] bool, ``top_subsets`` [m][p] bool,
+    ``top_r_squared`` [m]: the m = min(T, all valid ranks) best models over all sizes, in the same order.
+    ``best_size``, ``best_group_subset``, ``best_subset``, ``full_r_squared`` and ``baseline_r_squared`` are
+    ``ls_spa_best_subsets(groups=)``'s."""
+    sizes: np.ndarray
+    n_models: np.ndarray
+    group_subsets: np.ndarray
+    subsets: np.ndarray
+    n_columns: np.ndarray
+    r_squared: np.ndarray
+    theta: np.ndarray
+    gap: np.ndarray
+    top_sizes: np.ndarray
+    top_group_subsets: np.ndarray
+    top_subsets: np.ndarray
+    top_r_squared: np.ndarray
+    best_size: int
+    best_group_subset: np.ndarray
+    best_subset: np.ndarray
+    full_r_squared: float
+    baseline_r_squared: float
+
+    def __repr__(self):
+        pad = " " * 8
+        n, T, g = np.asarray(self.group_subsets).shape
+        p = np.asarray(self.subsets).shape[2]
+        chosen = ", ".join(str(k) for k in np.nonzero(self.best_group_subset)[0][:12])
+        best = runner = "nan"
+        if self.best_size >= 0:
+            best = f"{float(self.top_r_squared[0]):.2e}"
+        if len(self.top_r_squared) > 1:
+            runner = f"{float(self.top_r_squared[0] - self.top_r_squared[1]):.2e}"
+        lines = [
+            "",
+            f"{pad}p = {p} columns in g = {g} groups, the {T} best group subsets of sizes 0 .. {n - 1}",
+            f"{pad}Out-of-sample R^2 with all columns: {self.full_r_squared:.2e}, with the baseline alone: "
+            f"{self.baseline_r_squared:.2e}",
+            f"{pad}Best model: {self.best_size} groups ({int(np.sum(self.best_subset))} columns), out-of-sample R^2 "
+            f"{best}",
+            f"{pad}Its groups: ({chosen}{', ...' if int(np.sum(self.best_group_subset)) > 12 else ''})",
+            f"{pad}The next model over all sizes is worse by {runner}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class PermutationTestResults:
     """What ``ls_spa_permutation_test`` returns; d = p, or the g groups of ``groups=``.  ``attribution`` [d], ``theta``
     [p], ``r_squared`` (and ``baseline_r_squared`` with groups, else None): the observed values.  ``null_attribution``
