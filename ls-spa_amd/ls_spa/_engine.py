@@ -501,11 +501,19 @@ class HipEngine:
         Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
         ya, ye = np.ascontiguousarray(y_train, dtype=dt), np.ascontiguousarray(y_test, dtype=dt)
         n, p = Xa.shape
+        self.boot_load_ptr(Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p, reg,
+                           f32=dt == np.float32, location=N.HOST, grouped=grouped)
+
+    def boot_load_ptr(self, X_train_ptr, ld_train, y_train_ptr, n, X_test_ptr, ld_test, y_test_ptr, m_rows, p, reg,
+                      f32=False, location=N.DEVICE, grouped: bool = False):
+        """Same, from pointers: rows [n][ld_train] and [m_rows][ld_test] of f32 or f64 on the host or the device (e.g.
+        torch tensors' data_ptr()), ld >= p."""
         load = self._lib.lsspa_boot_groups_load if grouped else self._lib.lsspa_boot_load
         self._check(load(
-            self._h, Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p,
-            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
-        self._boot_dims = (p, n, Xe.shape[0])
+            self._h, C.c_void_p(X_train_ptr), int(ld_train), C.c_void_p(y_train_ptr), int(n), C.c_void_p(X_test_ptr),
+            int(ld_test), C.c_void_p(y_test_ptr), int(m_rows), int(p), float(reg), N.F32 if f32 else N.F64,
+            int(location)))
+        self._boot_dims = (int(p), int(n), int(m_rows))
 
     def boot_free(self):
         self.boot_timing_last = self.boot_timing()      # the data go, the last run's timing stays readable
@@ -648,10 +656,18 @@ class HipEngine:
         Ya, Ye = np.ascontiguousarray(Y_train, dtype=dt), np.ascontiguousarray(Y_test, dtype=dt)
         n, p = Xa.shape
         m = Ya.shape[1]
+        self.multi_load_ptr(Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m,
+                            Xe.shape[0], p, m, reg, f32=dt == np.float32, location=N.HOST)
+
+    def multi_load_ptr(self, X_train_ptr, ld_train, Y_train_ptr, ldy_train, n, X_test_ptr, ld_test, Y_test_ptr,
+                       ldy_test, m_rows, p, m, reg, f32=False, location=N.DEVICE):
+        """Same, from pointers: X [n][ld_train] and Y [n][ldy_train] (the test side alike) of f32 or f64 on the host or
+        the device, ld >= p and ldy >= m."""
         self._check(self._lib.lsspa_multi_load(
-            self._h, Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m, Xe.shape[0], p, m,
-            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
-        self._multi_dims = (p, m)
+            self._h, C.c_void_p(X_train_ptr), int(ld_train), C.c_void_p(Y_train_ptr), int(ldy_train), int(n),
+            C.c_void_p(X_test_ptr), int(ld_test), C.c_void_p(Y_test_ptr), int(ldy_test), int(m_rows), int(p), int(m),
+            float(reg), N.F32 if f32 else N.F64, int(location)))
+        self._multi_dims = (int(p), int(m))
 
     def multi_load_reduced(self, G, g, H, h, yy):
         """The same from the Gram form: G, H [p][p], g, h [m][p], yy [m] (lsspa_multi_set_reduced)."""
@@ -739,10 +755,18 @@ class HipEngine:
         Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
         ya, ye = np.ascontiguousarray(y_train, dtype=dt), np.ascontiguousarray(y_test, dtype=dt)
         n, p = Xa.shape
+        self.perm_load_ptr(Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p, reg,
+                           f32=dt == np.float32, location=N.HOST)
+
+    def perm_load_ptr(self, X_train_ptr, ld_train, y_train_ptr, n, X_test_ptr, ld_test, y_test_ptr, m_rows, p, reg,
+                      f32=False, location=N.DEVICE):
+        """Same, from pointers: rows [n][ld_train] and [m_rows][ld_test] of f32 or f64 on the host or the device,
+        ld >= p."""
         self._check(self._lib.lsspa_perm_load(
-            self._h, Xa.ctypes.data, p, ya.ctypes.data, n, Xe.ctypes.data, p, ye.ctypes.data, Xe.shape[0], p,
-            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
-        self._perm_dims = (p, n, Xe.shape[0])
+            self._h, C.c_void_p(X_train_ptr), int(ld_train), C.c_void_p(y_train_ptr), int(n), C.c_void_p(X_test_ptr),
+            int(ld_test), C.c_void_p(y_test_ptr), int(m_rows), int(p), float(reg), N.F32 if f32 else N.F64,
+            int(location)))
+        self._perm_dims = (int(p), int(n), int(m_rows))
 
     def _perm_labels(self, labels):
         p = (getattr(self, "_perm_dims", None) or (1,))[0]
@@ -803,10 +827,18 @@ class HipEngine:
         Ya, Ye = np.ascontiguousarray(Y_train, dtype=dt), np.ascontiguousarray(Y_test, dtype=dt)
         n, p = Xa.shape
         m = Ya.shape[1]
+        self.multi_lift_load_ptr(Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m,
+                                 Xe.shape[0], p, m, reg, f32=dt == np.float32, location=N.HOST)
+
+    def multi_lift_load_ptr(self, X_train_ptr, ld_train, Y_train_ptr, ldy_train, n, X_test_ptr, ld_test, Y_test_ptr,
+                            ldy_test, m_rows, p, m, reg, f32=False, location=N.DEVICE):
+        """Same, from pointers: X [n][ld_train] and Y [n][ldy_train] (the test side alike) of f32 or f64 on the host or
+        the device, ld >= p and ldy >= m."""
         self._check(self._lib.lsspa_multi_lift_load(
-            self._h, Xa.ctypes.data, p, Ya.ctypes.data, m, n, Xe.ctypes.data, p, Ye.ctypes.data, m, Xe.shape[0], p, m,
-            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
-        self._multi_lift_dims, self._multi_lift_g = (p, m), 0
+            self._h, C.c_void_p(X_train_ptr), int(ld_train), C.c_void_p(Y_train_ptr), int(ldy_train), int(n),
+            C.c_void_p(X_test_ptr), int(ld_test), C.c_void_p(Y_test_ptr), int(ldy_test), int(m_rows), int(p), int(m),
+            float(reg), N.F32 if f32 else N.F64, int(location)))
+        self._multi_lift_dims, self._multi_lift_g = (int(p), int(m)), 0
 
     def multi_lift_load_reduced(self, G, g, H, h, yy):
         """The same from the Gram form: G, H [p][p], g, h [m][p], yy [m] (lsspa_multi_lift_set_reduced)."""
