@@ -433,6 +433,55 @@ int lsspa_boot_groups_best_run(lsspa_ctx* ctx, const int32_t* labels /* [p] */, 
 int lsspa_debug_boot_groups_best_plan(int64_t R, int64_t N, int64_t M, const int32_t* labels /* [p] */, int32_t p,
                                       int32_t g, int64_t block, int64_t* plan15);
 
+/* K-FOLD CROSS-VALIDATION (p <= 32, 2 <= K <= 32 folds, fp64, no groups): one data set, no split to choose.  Rows
+ * z_i = [x_i, y_i], i < N; fold f holds the rows with fold_ids[i] == f (n_f >= 1 of them), S_f = sum_{i in f} z_i z_i^T.
+ * Fold problem f is tested on fold f and trained on the other rows, in the bootstrap's normalisation with W_f = N - n_f:
+ *   G_f = (sum_{j != f} S_j)[:p,:p] / W_f + reg I,  g_f = (sum_{j != f} S_j)[:p,p] / W_f   (j ascending: sums, not a
+ *   total minus S_f),  H_f = S_f[:p,:p],  h_f = S_f[:p,p],
+ * and every fold divides by the same POOLED ||y||^2 = sum_j S_j[p][p] (j ascending): with one denominator the folds'
+ * values add up to the cross-validated R^2 exactly,
+ *   v_cv(K) = sum_f v_f(K) (f ascending, fp64) = 1 - sum_f ||y_f - X_f theta_K^(-f)||^2 / ||y||^2,
+ * v_f what lsspa_debug_subset_values gives for problem f.  The Shapley value is linear in the game:
+ * phi_cv = sum_f phi_f (f ascending), and its entries sum to v_cv(all columns).
+ *   lsspa_cv_load   : packs [X | y] once (arguments as lsspa_reduce's for one side; fold_ids a HOST array [N]), writes
+ *                     the folds' indicator weights on the device from the labels (no [K][N] array crosses the bus),
+ *                     runs the bootstrap's weighted Gram pass for S_f and finalises the K problems.  Refused before any
+ *                     GPU work with LSSPA_ERR_ARG naming the limit: p > 32, K outside 2 .. 32, a label outside
+ *                     0 .. K-1, an empty fold, sum y^2 = 0 (rows on the device: that one after the Gram pass).
+ *                     The loaded problem, the statistics, the enumerations' and the bootstrap's state are not touched,
+ *                     now or by any call below.
+ *   lsspa_cv_shapley: phi [p] = phi_cv, phi_fold [K][p] (row f has the bits lsspa_subsets_shapley gives for problem f:
+ *                     the same kernel, cut into launches as that call cuts it), r2_fold [K] = v_f(all columns), info
+ *                     [K]: LSSPA_INFO_NOT_PD in the word of the fold a pivot failed in.
+ *   lsspa_cv_best   : lsspa_subsets_best by v_cv: v [p+1], masks, found as there -- the larger v_cv wins, on equal
+ *                     values the smaller mask, so the result depends on no cut --, candidates: (K & include) == include
+ *                     and the subset's own pivots passed in EVERY fold (info [K] says which fold failed).  v[k] has the
+ *                     bits of lsspa_debug_cv_values for masks[k].  v_fold [p+1][K]: the winner's per-fold values (NaN
+ *                     where found[k] = 0).  steps = 0: the plan's steps of a unit per launch; > 0: that many (a test's
+ *                     way to cut a small p into several launches).  No floating-point atomics: two calls agree bitwise.
+ *   lsspa_cv_timing : kernel ms of the load's Gram side (weights, Gram, sums, finalise), of the last enumeration's
+ *                     launches, its longest launch and their number (any pointer may be NULL)
+ *   lsspa_cv_get_problem   : test hook -- fold problem f as the device computed it (G, H [p][p], g, h [p], the pooled
+ *                     1 / ||y||^2; any pointer may be NULL)
+ *   lsspa_debug_cv_values  : test hook -- v[i] = v_cv(masks[i]) and, unless NULL, v_fold[i][f] = v_f(masks[i]) by
+ *                     lsspa_cv_best's own device code.  A failed pivot is no error here: the value is what came out.
+ *   lsspa_debug_cv_plan    : host only, no context, no GPU -- lsspa_cv_best's units, high subsets per unit, steps of a
+ *                     unit per launch (each K fold evaluations: 2^20 / (units K), at least 1), launches, LDS bytes of
+ *                     a workgroup, its threads, 0, 0.  p outside 1 .. 32 or K outside 2 .. 32 is LSSPA_ERR_ARG.
+ * LSSPA_ERR_STATE before a load.  Top lists, groups, interactions and a bootstrap over the folds are not built. */
+int lsspa_cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+                  const int32_t* fold_ids /* [N], host */, int32_t K, double reg, int32_t dtype, int32_t location);
+int lsspa_cv_shapley(lsspa_ctx* ctx, double* phi /* [p] */, double* phi_fold /* [K][p] */, double* r2_fold /* [K] */,
+                     int32_t* info /* [K] */);
+int lsspa_cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v /* [p+1] */, uint32_t* masks /* [p+1] */,
+                  uint8_t* found /* [p+1] */, double* v_fold /* [p+1][K] */, int32_t* info /* [K] */);
+int lsspa_cv_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms, int64_t* launches);
+int lsspa_cv_free(lsspa_ctx* ctx);
+int lsspa_cv_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double* H, double* h, double* inv_yy);
+int lsspa_debug_cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v /* [n] */,
+                          double* v_fold /* [n][K] or NULL */);
+int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan /* [8] */);
+
 /* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
  * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the
  * 2^p subsets are enumerated once for every 8 responses: a wave sweeps a high subset's pivots out of [G | g_r ...] with

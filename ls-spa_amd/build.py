@@ -19,7 +19,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIBNAME = "liblsspa_hip.so"
 SOURCES = ["k_factor.hip", "k_small.hip", "k_small_multi.hip", "k_lift.hip", "k_gram.hip", "k_error.hip", "k_subsets.hip", "k_groups.hip",
-           "k_players.hip", "k_pairs.hip", "k_boot.hip", "k_multi.hip", "k_multi_groups.hip", "k_perm.hip", "boot_plan.cpp", "lsspa_comm.hip", "lsspa_api.hip", "host_perms.cpp"]
+           "k_players.hip", "k_pairs.hip", "k_boot.hip", "k_cv.hip", "k_multi.hip", "k_multi_groups.hip", "k_perm.hip", "boot_plan.cpp", "lsspa_comm.hip", "lsspa_api.hip", "host_perms.cpp"]
 HEADERS = ["tiles.h", "kernels.h", "players.h", "comm.h", "philox.h", "boot_plan.h", os.path.join("..", "..", "include", "lsspa.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # developer A/B builds: LSSPA_CXXFLAGS="-DSOMETHING" python ls-spa_amd/build.py --force --out ls-spa_amd/lib/ab/new.so

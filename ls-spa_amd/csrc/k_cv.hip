@@ -1,0 +1,94 @@
+// K-fold cross-validation (lsspa_cv_load .. lsspa_cv_free; DESIGN.md, "K-fold cross-validation"): the small kernels
+// between the bootstrap's weighted Gram pass (k_boot.hip) and the enumerations of k_subsets.hip.  fp64 throughout.
+//
+// The rows z_i = [x_i, y_i] are packed once (launch_boot_pack).  Fold f's Gram S_f = sum_{i in f} z_i z_i^T is the
+// bootstrap's weighted Gram with the indicator of the fold as the weights: cv_weights_kernel writes those from the
+// fold labels on the device, launch_boot_gram / launch_boot_reduce do the rest.  cv_finalize_kernel then forms the
+// fold problems in the replicate layout the enumerations read: fold f is tested on its own rows and trained on the
+// others',
+//   G_f = (sum_{j != f} S_j)[:p,:p] / (N - n_f) + reg I,   g_f likewise,   H_f = S_f[:p,:p],   h_f = S_f[:p,p],
+// the sums over j ascending (added, not subtracted from a total: no cancellation), and every fold divides by the same
+// pooled ||y||^2 = sum_j S_j[p][p], so that the folds' values add up to the cross-validated R^2.
+#include "kernels.h"
+
+namespace lsspa {
+namespace {
+
+__global__ __launch_bounds__(256) void cv_weights_kernel(const int32_t* __restrict__ fid, int64_t n,
+                                                         double* __restrict__ wt) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) wt[(int64_t)blockIdx.y * n + i] = fid[i] == (int32_t)blockIdx.y ? 1.0 : 0.0;
+}
+
+__global__ __launch_bounds__(256) void cv_finalize_kernel(const double* __restrict__ S, const int32_t* __restrict__ nf,
+                                                          int64_t n, int p, int folds, double reg,
+                                                          double* __restrict__ G, double* __restrict__ g,
+                                                          double* __restrict__ H, double* __restrict__ h,
+                                                          double* __restrict__ inv_yy) {
+  const int f = blockIdx.x, c = p + 1;
+  const int64_t cc = (int64_t)c * c;
+  const double W = (double)(n - nf[f]);
+  const double* T = S + f * cc;
+  for (int e = threadIdx.x; e < p * p; e += 256) {
+    const int i = e / p, j = e - i * p;
+    double s = 0.0;
+    for (int k = 0; k < folds; ++k)
+      if (k != f) s += S[k * cc + i * c + j];
+    G[(int64_t)f * p * p + e] = s / W + (i == j ? reg : 0.0);
+    H[(int64_t)f * p * p + e] = T[i * c + j];
+  }
+  if ((int)threadIdx.x < p) {
+    const int i = threadIdx.x;
+    double s = 0.0;
+    for (int k = 0; k < folds; ++k)
+      if (k != f) s += S[k * cc + i * c + p];
+    g[(int64_t)f * p + i] = s / W;
+    h[(int64_t)f * p + i] = T[i * c + p];
+  }
+  if (threadIdx.x == 0) {
+    double yy = 0.0;
+    for (int k = 0; k < folds; ++k) yy += S[k * cc + p * c + p];
+    inv_yy[f] = 1.0 / yy;
+  }
+}
+
+__global__ __launch_bounds__(64) void cv_foldsum_kernel(const double* __restrict__ out, int p, int folds,
+                                                        double* __restrict__ phi_fold, double* __restrict__ phi) {
+  const int j = threadIdx.x;
+  if (j >= p) return;
+  double s = 0.0;
+  for (int f = 0; f < folds; ++f) {
+    const double v = out[f * (p + 1) + j] - out[f * (p + 1) + p];
+    phi_fold[f * p + j] = v;
+    s = f == 0 ? v : s + v;
+  }
+  phi[j] = s;
+}
+
+}  // namespace
+
+hipError_t launch_cv_weights(const int32_t* fid, int64_t n, int folds, double* wt, hipStream_t st) {
+  if (!fid || !wt || n < 1 || n >= (1ll << 31) || folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cv_weights_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)folds), dim3(256), 0, st, fid, n,
+                     wt);
+  return hipGetLastError();
+}
+
+hipError_t launch_cv_finalize(const double* S, const int32_t* nf, int64_t n, int p, int folds, double reg, double* G,
+                              double* g, double* H, double* h, double* inv_yy, hipStream_t st) {
+  if (!S || !nf || !G || !g || !H || !h || !inv_yy || n < 2 || p < 1 || p > SUBSETS_MAX_P || folds < 2 ||
+      folds > CV_MAX_FOLDS)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cv_finalize_kernel, dim3((unsigned)folds), dim3(256), 0, st, S, nf, n, p, folds, reg, G, g, H, h,
+                     inv_yy);
+  return hipGetLastError();
+}
+
+hipError_t launch_cv_foldsum(const double* out, int p, int folds, double* phi_fold, double* phi, hipStream_t st) {
+  if (!out || !phi_fold || !phi || p < 1 || p > SUBSETS_MAX_P || folds < 2 || folds > CV_MAX_FOLDS)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cv_foldsum_kernel, dim3(1), dim3(64), 0, st, out, p, folds, phi_fold, phi);
+  return hipGetLastError();
+}
+
+}  // namespace lsspa

@@ -44,6 +44,9 @@
 // the largest v(K) and its mask per size |K| -- a kernel of its own beside the enumeration kernel, which it leaves alone.
 // Its REPS instantiation runs the replicates of a bootstrap of the selection (lsspa_boot_best_run) as the second grid
 // dimension, like the enumeration kernel's.
+//
+// K-fold cross-validation (lsspa_cv_best, subsets_cv_best_kernel below): that kernel's sibling, which evaluates every
+// high subset on the K fold problems of k_cv.hip in one step and keeps the best SUM of their values per size.
 #include "kernels.h"
 
 namespace lsspa {
@@ -734,6 +737,141 @@ __global__ __launch_bounds__(TRT) void subsets_top_reduce_kernel(const double* _
   }
 }
 
+// ---- best subset of every size by the K-fold cross-validated value (lsspa_cv_best) ----
+// subsets_best_kernel's sibling: the same units, steps and launches, running bests per class popc(s), best_merge /
+// wave_best, table layout and subsets_best_reduce_kernel.  What is compared is not one problem's v(K) but
+//   v_cv(K) = v_0(K) + v_1(K) + ... + v_{F-1}(K)   (fp64, in this order),
+// v_f the value subset_values gives for fold problem f: the F reduced problems lie one behind the other at the dense
+// replicate stride (SubsetArgs), and one step evaluates its high subset on all of them before the compare.  A subset is
+// a candidate only if it contains `include` and its own pivots passed in EVERY fold; a failed pivot raises the info word
+// of the fold it failed in.
+// The test side reaches the wave per fold-step: H_f, h_f and the diagonal of G_f are staged from memory (they stay in
+// the L2: F (p^2 + 2 p) doubles) into the one SubShared the workgroup has, then subset_values<false> runs on fold f's
+// arguments -- the same code on other addresses, so v_f has the bits the one-problem kernels give for problem f.  The
+// workgroup's LDS is SubShared's, as its siblings': seven one-wave workgroups a CU whatever F is ("K-fold
+// cross-validation", has the alternatives and why they lose).  The staging costs p^2 / 64 <= 16 loads a lane a
+// fold-step beside the up to 18 of the sweep matrix that subset_values does anyway.
+__device__ inline SubsetArgs fold_args(const SubsetArgs& a, int f) {
+  SubsetArgs b = a;
+  b.G += (int64_t)f * a.p * a.ldg;
+  b.H += (int64_t)f * a.p * a.ldh;
+  b.g += (int64_t)f * a.p;
+  b.h += (int64_t)f * a.p;
+  b.inv_yy += f;
+  return b;
+}
+
+// H, h and the pivot scale of one fold into sh; the caller's last barrier is behind every read of them
+__device__ inline void load_fold(SubShared& sh, const SubsetArgs& a, int lane) {
+  const int p = a.p;
+  for (int e = lane; e < p * p; e += 64) {
+    const int i = e / p, j = e - i * p;
+    sh.H[i * LDM + j] = a.H[(int64_t)i * a.ldh + j];
+  }
+  if (lane < p) {
+    sh.h[lane] = a.h[lane];
+    sh.gdiag[lane] = a.G[(int64_t)lane * a.ldg + lane];
+  }
+}
+
+// a.part [units][p + 1], bm [units][p + 1][2] as subsets_best_kernel's; a.info [F]
+__global__ __launch_bounds__(64, 2) void subsets_cv_best_kernel(SubsetArgs a, int F, uint64_t s0, uint64_t s1,
+                                                             uint32_t include, uint32_t* __restrict__ bm) {
+  __shared__ SubShared sh;
+  const int lane = threadIdx.x;
+  const int p = a.p, q = a.q;
+  for (int e = lane; e < (SQ + 1) * ZC; e += 64) sh.Z[e] = 0.0;   // rows / columns beyond q stay 0
+  double bv[SBS];
+  uint32_t bh[SBS];
+#pragma unroll
+  for (int j = 0; j < SBS; ++j) {
+    bv[j] = -__builtin_huge_val();
+    bh[j] = 0u;
+  }
+  const uint32_t inc_lo = include & ((1u << q) - 1u), inc_hi = include >> q;     // q >= 1
+  const bool lane_ok = lane < (1 << q) && ((uint32_t)lane & inc_lo) == inc_lo;
+  uint32_t bad_folds = 0u;                    // bit f: a pivot of fold f failed in a subset this lane saw
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    double v = 0.0;
+    bool bad_any = false;                     // this subset's own pivots, over the folds
+#pragma unroll 1
+    for (int f = 0; f < F; ++f) {
+      const SubsetArgs af = fold_args(a, f);
+      load_fold(sh, af, lane);
+      bool bad = false;
+      const double vf = subset_values<false>(sh, af, hi, lane, bad);
+      v = f == 0 ? vf : v + vf;
+      bad_any |= bad;
+      bad_folds |= bad ? (1u << f) : 0u;
+      __syncthreads();
+    }
+    const uint32_t h32 = (uint32_t)hi;
+    const bool cand = lane_ok && !bad_any && (h32 & inc_hi) == inc_hi;
+    const int cls = __popcll(s);
+#pragma unroll
+    for (int j = 0; j < SBS; ++j)
+      if (cls == j && cand && v > bv[j]) {
+        bv[j] = v;
+        bh[j] = h32;
+      }
+  }
+  double* rv = a.part + (int64_t)blockIdx.x * (p + 1);
+  uint32_t* rm = bm + (int64_t)blockIdx.x * (p + 1) * 2;
+  const int k0 = __popc(blockIdx.x), k1 = min(p, k0 + __popcll(a.per - 1) + q);
+  const int base = k0 + __popc(lane);                       // |K| of this lane's class 0
+  for (int k = k0; k <= k1; ++k) {
+    double v = -__builtin_huge_val();
+    uint32_t mask = 0u;
+#pragma unroll
+    for (int j = 0; j < SBS; ++j)
+      if (base + j == k) {
+        v = bv[j];
+        mask = (bh[j] << q) | (uint32_t)lane;
+      }
+    wave_best(v, mask);
+    if (lane == 0 && v > -__builtin_huge_val()) {
+      if (rm[2 * k + 1] != 0u) best_merge(v, mask, rv[k], rm[2 * k]);
+      rv[k] = v;
+      rm[2 * k] = mask;
+      rm[2 * k + 1] = 1u;
+    }
+  }
+  for (int f = 0; f < F; ++f)
+    if (__any((bad_folds >> f) & 1u) && lane == 0) atomicOr(a.info + f, 1);
+}
+
+// test hook and the winners' per-fold values: vals[i] = v_cv(masks[i]), vfold[i][f] = v_f(masks[i]) (vfold may be
+// null), by the very fold-step of subsets_cv_best_kernel
+__global__ __launch_bounds__(64, 2) void subsets_cv_debug_kernel(SubsetArgs a, int F, const uint64_t* __restrict__ masks,
+                                                              int64_t n, double* __restrict__ vals,
+                                                              double* __restrict__ vfold) {
+  __shared__ SubShared sh;
+  const int lane = threadIdx.x;
+  for (int e = lane; e < (SQ + 1) * ZC; e += 64) sh.Z[e] = 0.0;
+  uint32_t bad_folds = 0u;
+  const uint64_t low = (1ull << a.q) - 1ull;
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint64_t m = masks[i];
+    const bool mine = (uint64_t)lane == (m & low);
+    double v = 0.0;
+#pragma unroll 1
+    for (int f = 0; f < F; ++f) {
+      const SubsetArgs af = fold_args(a, f);
+      load_fold(sh, af, lane);
+      bool bad = false;
+      const double vf = subset_values<false>(sh, af, m >> a.q, lane, bad);
+      v = f == 0 ? vf : v + vf;
+      bad_folds |= (bad && mine) ? (1u << f) : 0u;
+      if (mine && vfold) vfold[i * F + f] = vf;
+      __syncthreads();
+    }
+    if (mine) vals[i] = v;
+  }
+  for (int f = 0; f < F; ++f)
+    if (__any((bad_folds >> f) & 1u) && lane == 0) atomicOr(a.info + f, 1);
+}
+
 // H = Ft Ft^T [p][p] (stride p) and h = Ft ytil (appended) of the rect-mode test factor: one workgroup per entry, its
 // 256 threads strided over the m columns, then a fixed tree (the same sums on every call; m may be up to 2^20 through
 // lsspa_set_reduced).  Entries (i, j) and (j, i) both form the product of rows min(i, j) and max(i, j) in the same
@@ -851,6 +989,29 @@ hipError_t launch_subsets_top_reduce(const double* tv, const uint32_t* tm, const
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(subsets_top_reduce_kernel, dim3(p + 1), dim3(TRT), 0, st, tv, tm, tc, (int)units, p + 1, T, out_v,
                      out_m, out_c);
+  return hipGetLastError();
+}
+
+size_t subsets_cv_lds_bytes() { return sizeof(SubShared); }
+
+hipError_t launch_subsets_cv_best(const SubsetArgs& a, int folds, uint64_t units, uint64_t s0, uint64_t s1,
+                                  uint32_t include, uint32_t* bm, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !bm || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // the caller vouches for `folds` problems and info words behind the first, as launch_subsets_best's for its replicates
+  if (folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  const int nh = a.p - a.q;
+  if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  if (a.per > (1ull << (SBS - 1))) return hipErrorInvalidValue;
+  if (a.p < 32 && (include >> a.p) != 0u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_cv_best_kernel, dim3((unsigned)units), dim3(64), 0, st, a, folds, s0, s1, include, bm);
+  return hipGetLastError();
+}
+
+hipError_t launch_subsets_cv_debug(const SubsetArgs& a, int folds, const uint64_t* masks, int64_t n, double* vals,
+                                   double* vfold, hipStream_t st) {
+  if (!args_ok(a) || !masks || !vals || n < 1 || folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  const int64_t grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(subsets_cv_debug_kernel, dim3((unsigned)grid), dim3(64), 0, st, a, folds, masks, n, vals, vfold);
   return hipGetLastError();
 }
 

@@ -374,6 +374,29 @@ hipError_t launch_subsets_top(const SubsetArgs& a, uint64_t units, uint64_t s0, 
 // their number, min(T, candidates of size k); NaN and 0 past it.  units <= 8192.
 hipError_t launch_subsets_top_reduce(const double* tv, const uint32_t* tm, const int32_t* tc, int64_t units, int p, int T,
                                      double* out_v, uint32_t* out_m, int32_t* out_c, hipStream_t st);
+// K-fold cross-validation (lsspa_cv_*; k_cv.hip has the kernels before the enumeration).  The `folds` reduced problems
+// lie behind a's at the dense replicate stride, as a launch's replicates do, with one info word each.
+// launch_subsets_cv_best: launch_subsets_best's units, steps, launches, tables, candidates and order, for
+//   v_cv(K) = v_0(K) + ... + v_{folds-1}(K), the fp64 sum in this order of the values launch_subsets_debug gives for
+// the fold problems; a candidate's own pivots passed in every fold, and a failed pivot raises a.info[fold].
+// launch_subsets_best_reduce takes the best over the units.  2 <= folds <= CV_MAX_FOLDS.
+constexpr int CV_MAX_FOLDS = 32;
+hipError_t launch_subsets_cv_best(const SubsetArgs& a, int folds, uint64_t units, uint64_t s0, uint64_t s1,
+                                  uint32_t include, uint32_t* bm, hipStream_t st);
+// vals[i] = v_cv(masks[i]) and, unless null, vfold[i][f] = v_f(masks[i]) by that kernel's own fold-step
+hipError_t launch_subsets_cv_debug(const SubsetArgs& a, int folds, const uint64_t* masks, int64_t n, double* vals,
+                                   double* vfold, hipStream_t st);
+size_t subsets_cv_lds_bytes();     // static LDS of a workgroup of launch_subsets_cv_best
+// wt[f][i] = 1.0 if fid[i] == f else 0.0, f < folds, i < n: the folds' indicator weights for launch_boot_gram
+hipError_t launch_cv_weights(const int32_t* fid, int64_t n, int folds, double* wt, hipStream_t st);
+// The fold problems from the per-fold Grams S [folds][c][c] (c = p + 1) and the folds' sizes nf [folds] of n rows:
+//   G[f] = (sum_{j != f} S[j])[:p,:p] / (n - nf[f]) + reg I (j ascending), g[f] likewise from column p,
+//   H[f] = S[f][:p,:p], h[f] = S[f][:p,p], inv_yy[f] = 1 / sum_j S[j][p][p] (j ascending, the same for every f)
+hipError_t launch_cv_finalize(const double* S, const int32_t* nf, int64_t n, int p, int folds, double reg, double* G,
+                              double* g, double* H, double* h, double* inv_yy, hipStream_t st);
+// phi_fold[f][j] = out[f][j] - out[f][p] of the enumeration's column sums out [folds][p + 1], phi[j] = their sum over f
+// in ascending order
+hipError_t launch_cv_foldsum(const double* out, int p, int folds, double* phi_fold, double* phi, hipStream_t st);
 // vals[i] = v(masks[i]) by the enumeration's own device code (test hook); masks < 2^p
 hipError_t launch_subsets_debug(const SubsetArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 // Hh = [H = Ft Ft^T (p x p, stride p) | h = Ft ytil] of a rect-mode test factor Ft [p][ldf], m columns used

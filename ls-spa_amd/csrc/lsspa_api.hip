@@ -94,6 +94,34 @@ struct BootWork {
   }
 };
 
+// What the K-fold cross-validation keeps (lsspa_cv_load .. lsspa_cv_free): the packed rows, the K fold problems in the
+// replicate layout the enumerations read (device; G, g, H, h and the pooled 1 / ||y||^2 also on the host as they were
+// computed), the enumerations' tables and the last calls' timing.  Nothing of the loaded problem, the sampling path, the
+// exact enumerations' or the bootstrap's state is in here.
+struct CvWork {
+  bool loaded = false;
+  int p = 0, K = 0;
+  int64_t n = 0;
+  DevBuf<double> Z;                        // [n][ldz] rows [X | y]
+  DevBuf<char> stage_x, stage_y;           // host rows on their way into Z
+  DevBuf<int32_t> fid, nf;                 // [n] fold labels, [K] fold sizes
+  DevBuf<double> wt, gpart, S;             // [K][n] indicator weights, Gram partials, S_f [K][c][c]
+  DevBuf<double> G, g, H, h, inv_yy;       // the fold problems [K]...
+  std::vector<double> Gh, gh, Hh, hh, yh;  // the same on the host
+  DevBuf<double> w, part, out, phi, vals;  // Shapley weights, partial table, its sums, phi_fold | phi, debug values
+  DevBuf<uint64_t> masks;
+  DevBuf<int32_t> info, dinfo;             // [K] info words of a call; the debug values' own
+  DevBuf<uint32_t> best;                   // lsspa_cv_best: (mask, found) of the units' rows, then of the result
+  double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
+  int64_t launches = 0;
+  void release() {
+    dev_free(Z); dev_free(stage_x); dev_free(stage_y); dev_free(fid); dev_free(nf); dev_free(wt); dev_free(gpart);
+    dev_free(S); dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(part);
+    dev_free(out); dev_free(phi); dev_free(vals); dev_free(masks); dev_free(info); dev_free(dinfo); dev_free(best);
+    loaded = false;
+  }
+};
+
 // The reduced form of m responses on one design: the shared G and H, one g and h per response and the test responses'
 // squared norms, on the host as they were stored (the *_get_gram entry points) and G, H, g, h on the device.  A member of
 // MultiWork and MultiLiftWork; the permutation test reaches it through its MultiWork.  reduced_store fills it.
@@ -318,6 +346,7 @@ struct lsspa_ctx {
   // exact attribution by subset enumeration (lsspa_subsets_shapley) and over groups of columns (lsspa_groups_shapley)
   ExactWork sub, grp;
   BootWork boot;                 // bootstrap of the exact attribution (lsspa_boot_*)
+  CvWork cv;                     // K-fold cross-validation (lsspa_cv_*)
   MultiWork multi;               // exact attribution of many responses at once (lsspa_multi_*)
   MultiLiftWork mlift;           // sampled attribution of many responses (lsspa_multi_lift_*)
   PermWork perm;                 // permutation test of the exact attribution (lsspa_perm_*)
@@ -1333,6 +1362,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->sub.release();
   ctx->grp.release();
   ctx->boot.release();
+  ctx->cv.release();
   ctx->multi.release();
   ctx->mlift.release();
   ctx->perm.release();
@@ -4987,6 +5017,393 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
+}
+
+}  // extern "C"
+
+// ---- K-fold cross-validation (k_cv.hip, the CV kernels of k_subsets.hip) ---------------------------------------------
+// lsspa_cv_load packs the rows once, forms the K per-fold Grams by the bootstrap's weighted Gram pass with indicator
+// weights written on the device, and finalises the K fold problems into the replicate layout.  lsspa_cv_shapley runs the
+// REPS enumeration over them, cut into launches as the one-problem call cuts a problem (the cut shows in the bits);
+// lsspa_cv_best runs subsets_cv_best_kernel.
+namespace {
+
+struct CvPlan {
+  uint64_t units, per, steps, launches;
+};
+// lsspa_cv_best's cut: a step of a unit evaluates K fold problems, so a launch takes 1 / K of the steps the one-problem
+// call gives it (at least one); forced > 0: that many steps a launch instead (test hook)
+CvPlan cv_best_plan(int p, int K, uint64_t forced) {
+  CvPlan P;
+  const uint64_t n_high = 1ull << (p - subsets_low_features(p));
+  P.units = exact_units(n_high);
+  P.per = n_high / P.units;
+  P.steps = forced ? forced : std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / (P.units * (uint64_t)K));
+  P.steps = std::min(P.steps, P.per);
+  P.launches = (P.per + P.steps - 1) / P.steps;
+  return P;
+}
+
+int cv_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->cv.loaded) return ctx->fail(LSSPA_ERR_STATE, "no cross-validation data loaded (lsspa_cv_load comes first)");
+  return LSSPA_OK;
+}
+
+// k_subsets.hip's view of the fold problems from e0 on; info: the [K] words the call reports into
+SubsetArgs cv_subset_args(const CvWork& W, int e0, int32_t* info) {
+  const int p = W.p;
+  SubsetArgs a{};
+  a.p = p;
+  a.q = subsets_low_features(p);
+  a.G = W.G.ptr + (size_t)e0 * p * p;
+  a.H = W.H.ptr + (size_t)e0 * p * p;
+  a.g = W.g.ptr + (size_t)e0 * p;
+  a.h = W.h.ptr + (size_t)e0 * p;
+  a.ldg = a.ldh = p;
+  a.w = W.w.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.inv_yy = W.inv_yy.ptr + e0;
+  a.info = info + e0;
+  return a;
+}
+
+// v [n] and, unless NULL, v_fold [n][K] of the host masks by subsets_cv_debug_kernel; the pivots' verdicts go to
+// W.dinfo, which nobody reads: a value is what came out
+int cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v, double* v_fold) {
+  CvWork& W = ctx->cv;
+  const int K = W.K;
+  TRY(dev_alloc(ctx, W.masks, (size_t)n));
+  TRY(dev_alloc(ctx, W.vals, (size_t)n * (K + 1)));
+  TRY(dev_alloc(ctx, W.dinfo, CV_MAX_FOLDS));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(W.masks.ptr, masks, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(W.dinfo.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, ctx->stream));
+  SubsetArgs a = cv_subset_args(W, 0, W.dinfo.ptr);
+  a.per = 1;
+  HIPCHK(launch_subsets_cv_debug(a, K, W.masks.ptr, n, W.vals.ptr, v_fold ? W.vals.ptr + n : nullptr, ctx->stream));
+  HIPCHK(hipMemcpyAsync(v, W.vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (v_fold)
+    HIPCHK(hipMemcpyAsync(v_fold, W.vals.ptr + n, sizeof(double) * n * K, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return LSSPA_OK;
+}
+
+// the launches' events into W's timing
+int cv_enum_timing(lsspa_ctx* ctx, const std::vector<hipEvent_t>& ev, size_t n_launch) {
+  CvWork& W = ctx->cv;
+  W.enum_ms = 0.0;
+  W.max_launch_ms = 0.0;
+  W.launches = (int64_t)n_launch;
+  for (size_t k = 0; k < n_launch; ++k) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
+    W.enum_ms += ms;
+    W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
+  }
+  return LSSPA_OK;
+}
+
+int cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p, const int32_t* fold_ids,
+            int32_t K, double reg, int32_t dtype, int32_t location) {
+  char msg[240];
+  if (p > SUBSETS_MAX_P) {
+    snprintf(msg, sizeof msg, "cross-validation enumerates feature subsets and takes at most p = %d features (%d given)",
+             SUBSETS_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (K < 2 || K > CV_MAX_FOLDS) {
+    snprintf(msg, sizeof msg, "cross-validation takes 2 .. %d folds (%d given)", CV_MAX_FOLDS, (int)K);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (!X || !y || !fold_ids || p < 1 || ld < p || !std::isfinite(reg) || (dtype != LSSPA_F64 && dtype != LSSPA_F32) ||
+      (location != LSSPA_HOST && location != LSSPA_DEVICE))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_load: NULL array, p < 1, ld < p, reg not finite, or bad dtype / location");
+  BootPlan P;
+  if (const char* why = boot_plan(K, N, N, p, 0, P)) {
+    snprintf(msg, sizeof msg, "lsspa_cv_load: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  int32_t nf[CV_MAX_FOLDS] = {0};
+  for (int64_t i = 0; i < N; ++i) {
+    if (fold_ids[i] < 0 || fold_ids[i] >= K) {
+      snprintf(msg, sizeof msg, "fold_ids[%lld] = %d: fold labels must be 0 .. %d (K - 1)", (long long)i,
+               (int)fold_ids[i], (int)K - 1);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+    ++nf[fold_ids[i]];
+  }
+  for (int f = 0; f < K; ++f)
+    if (nf[f] == 0) {
+      snprintf(msg, sizeof msg, "fold %d of %d is empty: every fold needs at least one row", f, (int)K);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  if (location == LSSPA_HOST) {          // (rows on the device: the pooled sum is looked at after the Gram pass)
+    bool any = false;
+    for (int64_t i = 0; i < N && !any; ++i)
+      any = dtype == LSSPA_F32 ? ((const float*)y)[i] != 0.f : ((const double*)y)[i] != 0.0;
+    if (!any) return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  CvWork& W = ctx->cv;
+  W.loaded = false;
+  hipStream_t st = ctx->stream;
+  const size_t c = (size_t)p + 1, pp = (size_t)p * p;
+  TRY(dev_alloc(ctx, W.Z, (size_t)N * P.ldz));
+  TRY(dev_alloc(ctx, W.fid, (size_t)N));
+  TRY(dev_alloc(ctx, W.nf, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.wt, (size_t)K * N));
+  TRY(dev_alloc(ctx, W.gpart, (size_t)P.slices[0] * K * P.pairs * 256));
+  TRY(dev_alloc(ctx, W.S, (size_t)K * c * c));
+  TRY(dev_alloc(ctx, W.G, (size_t)K * pp));
+  TRY(dev_alloc(ctx, W.H, (size_t)K * pp));
+  TRY(dev_alloc(ctx, W.g, (size_t)K * p));
+  TRY(dev_alloc(ctx, W.h, (size_t)K * p));
+  TRY(dev_alloc(ctx, W.inv_yy, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.info, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.w, EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)));
+  TRY(load_rows(ctx, W.stage_x, W.stage_y, X, ld, y, N, p, dtype, location,
+                [&](const void* sx, const void* sy, int64_t nr, int64_t r0) {
+                  return launch_boot_pack(sx, ld, sy, nr, p, dtype == LSSPA_F32, W.Z.ptr, P.ldz, r0, st);
+                }));
+  double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
+  exact_weight_table(p, w);
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(W.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.fid.ptr, fold_ids, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.nf.ptr, nf, sizeof nf, hipMemcpyHostToDevice));
+  std::vector<hipEvent_t> ev(2, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev[0], st));
+  HIPCHK(launch_cv_weights(W.fid.ptr, N, K, W.wt.ptr, st));
+  HIPCHK(launch_boot_gram(P, 0, W.Z.ptr, N, nullptr, W.wt.ptr, K, W.gpart.ptr, st));
+  HIPCHK(launch_boot_reduce(P, 0, W.gpart.ptr, p, K, W.S.ptr, st));
+  HIPCHK(launch_cv_finalize(W.S.ptr, W.nf.ptr, N, p, K, reg, W.G.ptr, W.g.ptr, W.H.ptr, W.h.ptr, W.inv_yy.ptr, st));
+  HIPCHK(hipEventRecord(ev[1], st));
+  W.Gh.resize(K * pp);
+  W.Hh.resize(K * pp);
+  W.gh.resize((size_t)K * p);
+  W.hh.resize((size_t)K * p);
+  W.yh.resize(K);
+  HIPCHK(hipMemcpyAsync(W.Gh.data(), W.G.ptr, sizeof(double) * K * pp, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(W.Hh.data(), W.H.ptr, sizeof(double) * K * pp, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(W.gh.data(), W.g.ptr, sizeof(double) * K * p, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(W.hh.data(), W.h.ptr, sizeof(double) * K * p, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(W.yh.data(), W.inv_yy.ptr, sizeof(double) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  W.gram_ms = ms;
+  W.enum_ms = W.max_launch_ms = 0.0;
+  W.launches = 0;
+  dev_free(W.stage_x);
+  dev_free(W.stage_y);
+  dev_free(W.wt);
+  dev_free(W.gpart);
+  if (!(W.yh[0] > 0.0) || !std::isfinite(W.yh[0]))
+    return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
+  W.p = p;
+  W.K = K;
+  W.n = N;
+  W.loaded = true;
+  return LSSPA_OK;
+}
+
+int cv_shapley(lsspa_ctx* ctx, double* phi, double* phi_fold, double* r2_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int p = W.p, K = W.K, cols = p + 1;
+  const uint64_t n_high = 1ull << (p - subsets_low_features(p));
+  const uint64_t units = exact_units(n_high), per = n_high / units;
+  // a fold's launches are the one-problem call's (the cut of `per` shows in the bits); as many folds share a launch as
+  // its bound on the subsets of a launch leaves
+  const uint64_t steps = std::min(per, std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units));
+  const int ereps = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, SUBSETS_PER_LAUNCH / (units * steps)));
+  TRY(dev_alloc(ctx, W.part, (size_t)ereps * units * cols));
+  TRY(dev_alloc(ctx, W.out, (size_t)K * cols));
+  TRY(dev_alloc(ctx, W.phi, (size_t)(K + 1) * p));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  const size_t n_launch = (size_t)((K + ereps - 1) / ereps) * (size_t)((per + steps - 1) / steps);
+  std::vector<hipEvent_t> ev(2 * n_launch, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  size_t l = 0;
+  for (int e0 = 0; e0 < K; e0 += ereps) {
+    const int ne = std::min(ereps, K - e0);
+    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)ne * units * cols, st));
+    SubsetArgs a = cv_subset_args(W, e0, W.info.ptr);
+    a.per = per;
+    a.part = W.part.ptr;
+    for (uint64_t s0 = 0; s0 < per; s0 += steps, ++l) {
+      HIPCHK(hipEventRecord(ev[2 * l], st));
+      HIPCHK(launch_subsets_enum(a, units, s0, std::min(per, s0 + steps), false, st, ne));
+      HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+    }
+    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, cols, W.out.ptr + (size_t)e0 * cols, st, ne));
+  }
+  HIPCHK(launch_cv_foldsum(W.out.ptr, p, K, W.phi.ptr, W.phi.ptr + (size_t)K * p, st));
+  HIPCHK(hipMemcpyAsync(phi_fold, W.phi.ptr, sizeof(double) * K * p, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(phi, W.phi.ptr + (size_t)K * p, sizeof(double) * p, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(cv_enum_timing(ctx, ev, n_launch));
+  // each fold's share of the R^2 of the full model: the value of the full mask, fold by fold
+  const uint64_t full = (1ull << p) - 1ull;      // p <= 32
+  double v = 0.0;
+  return cv_values(ctx, &full, 1, &v, r2_fold);
+}
+
+int cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, uint32_t* masks, uint8_t* found,
+            double* v_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  const int p = W.p, K = W.K;
+  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
+  if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_best: steps must be >= 0");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const CvPlan P = cv_best_plan(p, K, (uint64_t)steps);
+  const size_t rows = (size_t)P.units * (p + 1);
+  TRY(dev_alloc(ctx, W.part, rows));
+  TRY(dev_alloc(ctx, W.out, (size_t)K * (p + 1)));
+  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)p + 1)));
+  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * rows, st));
+  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, st));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  SubsetArgs a = cv_subset_args(W, 0, W.info.ptr);
+  a.per = P.per;
+  a.part = W.part.ptr;
+  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
+    HIPCHK(hipEventRecord(ev[2 * l], st));
+    HIPCHK(launch_subsets_cv_best(a, K, P.units, s0, std::min(P.per, s0 + P.steps), include, W.best.ptr, st));
+    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+  }
+  uint32_t mf[2 * (SUBSETS_MAX_P + 1)];
+  uint32_t* out_m = W.best.ptr + 2 * rows;
+  HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, (int64_t)P.units, p, W.out.ptr, out_m, st));
+  HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * (p + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (p + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
+  uint64_t win[SUBSETS_MAX_P + 1];
+  int at[SUBSETS_MAX_P + 1], nw = 0;
+  for (int k = 0; k <= p; ++k) {
+    found[k] = mf[2 * k + 1] ? 1 : 0;
+    masks[k] = found[k] ? mf[2 * k] : 0u;
+    if (!found[k]) v[k] = std::nan("");
+    for (int f = 0; f < K; ++f) v_fold[(size_t)k * K + f] = std::nan("");
+    if (found[k]) {
+      at[nw] = k;
+      win[nw++] = masks[k];
+    }
+  }
+  if (nw) {       // the winners' per-fold values, by the kernel's own fold-step
+    std::vector<double> wv((size_t)nw), wf((size_t)nw * K);
+    TRY(cv_values(ctx, win, nw, wv.data(), wf.data()));
+    for (int i = 0; i < nw; ++i) std::copy(&wf[(size_t)i * K], &wf[(size_t)i * K] + K, v_fold + (size_t)at[i] * K);
+  }
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+                  const int32_t* fold_ids, int32_t K, double reg, int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  return cv_load(ctx, X, ld, y, N, p, fold_ids, K, reg, dtype, location);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_shapley(lsspa_ctx* ctx, double* phi, double* phi_fold, double* r2_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!phi || !phi_fold || !r2_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_shapley: phi / phi_fold / r2_fold / info is NULL");
+  return cv_shapley(ctx, phi, phi_fold, r2_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, uint32_t* masks, uint8_t* found,
+                  double* v_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!v || !masks || !found || !v_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_best: v / masks / found / v_fold / info is NULL");
+  return cv_best(ctx, include, steps, v, masks, found, v_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms,
+                    int64_t* launches) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (gram_ms) *gram_ms = ctx->cv.gram_ms;
+  if (enum_ms) *enum_ms = ctx->cv.enum_ms;
+  if (max_launch_ms) *max_launch_ms = ctx->cv.max_launch_ms;
+  if (launches) *launches = ctx->cv.launches;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_cv_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->cv.release();
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double* H, double* h, double* inv_yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  const CvWork& W = ctx->cv;
+  if (f < 0 || f >= W.K) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_get_problem: f must be 0 .. K - 1");
+  const size_t p = (size_t)W.p, pp = p * p;
+  if (G) std::copy(&W.Gh[f * pp], &W.Gh[f * pp] + pp, G);
+  if (H) std::copy(&W.Hh[f * pp], &W.Hh[f * pp] + pp, H);
+  if (g) std::copy(&W.gh[f * p], &W.gh[f * p] + p, g);
+  if (h) std::copy(&W.hh[f * p], &W.hh[f * p] + p, h);
+  if (inv_yy) *inv_yy = W.yh[f];
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v, double* v_fold) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (n < 0 || (n > 0 && (!masks || !v))) return ctx->fail(LSSPA_ERR_ARG, "masks / v NULL or n < 0");
+  const uint64_t full = (1ull << ctx->cv.p) - 1ull;     // p <= 32 here
+  for (int64_t i = 0; i < n; ++i)
+    if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a feature beyond p");
+  if (n == 0) return LSSPA_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  return cv_values(ctx, masks, n, v, v_fold);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan) try {
+  if (!plan || p < 1 || p > SUBSETS_MAX_P || K < 2 || K > CV_MAX_FOLDS) return LSSPA_ERR_ARG;
+  const CvPlan P = cv_best_plan(p, K, 0);
+  const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, (int64_t)P.launches,
+                          (int64_t)subsets_cv_lds_bytes(), 64, 0, 0};
+  std::copy(out, out + 8, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
 }
 
 }  // extern "C"

@@ -22,16 +22,19 @@ and ``ls_spa_best_group_subsets_bootstrap`` (the same over groups of columns, g 
 bootstrap of ``ls_spa_best_subsets(groups=)``, returning ``BestGroupSubsetsBootstrapResults``) and
 ``ls_spa_top_subsets`` (the n_best <= 16 best models of every size, p <= 32: how much worse is the next model?,
 returning ``TopSubsetsResults``) and ``ls_spa_top_group_subsets`` (the same over groups of columns, g <= 32 groups of
-p <= 64 columns: the n_best <= 16 best sets of groups of every size, returning ``TopGroupSubsetsResults``)
+p <= 64 columns: the n_best <= 16 best sets of groups of every size, returning ``TopGroupSubsetsResults``) and
+``ls_spa_cv`` (the exact attribution of the K-fold cross-validated R^2 of one data set, p <= 32, returning
+``CVResults``) and ``ls_spa_best_subsets_cv`` (best-subset selection by that cross-validated R^2, returning
+``CVBestSubsetsResults``; ``cv_fold_ids`` is the fold assignment of both)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
-from ._results import (BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (CVBestSubsetsResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
                        TopGroupSubsetsResults, TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
-from ._driver import (ls_spa, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
+from ._driver import (ls_spa, ls_spa_cv, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
                       ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_subsets,
                       reduce_data, square_shapley, run_estimator, release)
@@ -51,4 +54,5 @@ __all__ = [
     "ls_spa_best_group_subsets_bootstrap", "BestGroupSubsetsBootstrapResults",
     "ls_spa_top_subsets", "TopSubsetsResults",
     "ls_spa_top_group_subsets", "TopGroupSubsetsResults",
+    "ls_spa_cv", "CVResults", "ls_spa_best_subsets_cv", "CVBestSubsetsResults", "cv_fold_ids",
 ]

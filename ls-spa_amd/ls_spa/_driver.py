@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (CVBestSubsetsResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsResults, TopSubsetsResults, validate_data)
@@ -1325,6 +1325,180 @@ def ls_spa_best_subsets(X_train, X_test, y_train, y_test, reg=0., *, include=Non
         best_size, best_subset = int(sizes[i]), subsets[i].copy()
     return BestSubsetsResults(sizes=sizes, subsets=subsets, r_squared=r_squared, theta=theta, best_size=best_size,
                               best_subset=best_subset, full_r_squared=float(full_r_squared))
+
+
+CV_MAX_FOLDS = 32          # include/lsspa.h, lsspa_cv_load
+
+
+def cv_fold_ids(n, folds=5, *, seed=42, shuffle=True):
+    """(fold_ids [n] int32, K): the fold of every row.  ``folds`` an int K: with ``shuffle`` row pi[i] goes to fold
+    i mod K, pi the host permutation of (seed, replicate 0, side 0, n) that ``ls_spa_permutation_test`` draws (a pure
+    function of (seed, n): include/lsspa.h, lsspa_debug_perm_indices); without, row i goes to fold i mod K.  ``folds`` an
+    integer array [n] of labels 0 .. K-1 is taken as given, K = its largest label + 1.  ValueError names what is wrong:
+    K outside 2 .. 32, a label outside 0 .. K-1, an empty fold.  Needs no GPU."""
+    n = int(n)
+    if np.ndim(folds) == 0:
+        if isinstance(folds, (bool, np.bool_)) or int(folds) != folds:
+            raise ValueError("folds must be an integer number of folds or an integer array of fold labels")
+        K = int(folds)
+        if K < 2 or K > CV_MAX_FOLDS:
+            raise ValueError(f"cross-validation takes 2 .. {CV_MAX_FOLDS} folds (folds = {K})")
+        if K > n:
+            raise ValueError(f"fold {n} of {K} would be empty: there are only N = {n} rows")
+        ids = np.empty(n, dtype=np.int32)
+        if shuffle:
+            from ._engine import debug_perm_indices
+            order = debug_perm_indices(int(seed), 0, 0, n).astype(np.int64)
+        else:
+            order = np.arange(n)
+        ids[order] = np.arange(n) % K
+        return ids, K
+    raw = np.asarray(folds)
+    if raw.shape != (n,):
+        raise ValueError(f"fold labels must have shape ({n},), got {raw.shape}")
+    if raw.dtype == bool or not np.issubdtype(raw.dtype, np.number) or not np.array_equal(raw.astype(np.int64), raw):
+        raise ValueError("fold labels must be integers")
+    lab = raw.astype(np.int64)
+    if lab.min() < 0:
+        raise ValueError(f"fold labels must be 0 .. K-1 (label {int(lab.min())} given)")
+    K = int(lab.max()) + 1
+    if K < 2 or K > CV_MAX_FOLDS:
+        raise ValueError(f"cross-validation takes 2 .. {CV_MAX_FOLDS} folds (the labels name {K})")
+    counts = np.bincount(lab, minlength=K)
+    if (counts == 0).any():
+        raise ValueError(f"fold {int(np.argmin(counts != 0))} of {K} is empty: every fold needs at least one row")
+    return lab.astype(np.int32), K
+
+
+def _cv_data(name, X, y, folds, seed, shuffle):
+    """The checks every cross-validation call makes before it touches an engine: (X, y, fold_ids, K)."""
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1:
+        raise ValueError(f"{name}: X must be two-dimensional and y one-dimensional")
+    if X.shape[0] != y.shape[0]:
+        raise SizeIncompatible(f"X has {X.shape[0]} rows, y has {y.shape[0]}")
+    n, p = X.shape
+    if p > SUBSETS_MAX_P:
+        raise ValueError(f"{name} enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} features "
+                         f"(this problem has p = {p})")
+    if p < 1 or n < 2:
+        raise ValueError(f"{name} needs p >= 1 features and N >= 2 rows (p = {p}, N = {n})")
+    ids, K = cv_fold_ids(n, folds, seed=seed, shuffle=shuffle)
+    if not np.any(y):
+        raise ValueError("y is identically zero: the cross-validated R^2 is not defined")
+    return X, y, ids, K
+
+
+def _cv_full_problem(X, y, reg):
+    """G = X^T X / N + reg I and g = X^T y / N of all rows, fp64 on the host: what the coefficients are refitted on."""
+    Xd, yd = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    n, p = Xd.shape
+    return Xd.T @ Xd / n + reg * np.eye(p), Xd.T @ yd / n
+
+
+def _cv_verdict(info, stacklevel):
+    """The RuntimeWarning of a cross-validation call whose fold problems met a broken pivot, naming the folds."""
+    bad = [int(f) for f in np.nonzero(np.asarray(info) & 1)[0]]
+    if bad:
+        warnings.warn(f"a Gram matrix of the training rows of fold(s) {', '.join(map(str, bad))} was not numerically "
+                      "positive definite; subsets of collinear features are no candidates there and their attribution "
+                      "is not meaningful", RuntimeWarning, stacklevel=stacklevel + 1)
+
+
+def _seq_sum(rows):
+    """The fp64 sum of the rows in ascending order, as the device forms it."""
+    total = np.array(rows[0], dtype=np.float64, copy=True)
+    for r in rows[1:]:
+        total = total + r
+    return total
+
+
+def ls_spa_cv(X, y, reg=0., folds=5, *, seed=42, shuffle=True, device=0, _engine=None):
+    """Exact Shapley attribution of the K-fold cross-validated out-of-sample R^2 (p <= 32): one data set, no split to
+    choose.
+
+    Fold f is predicted by the model fitted on the other folds' rows; with the pooled denominator ||y||^2 the folds'
+    values add up to the cross-validated R^2, 1 - sum_f ||y_f - X_f theta^(-f)||^2 / ||y||^2, and since the Shapley value
+    is linear in the game its attribution is the sum of the folds' attributions.  The rows go to the GPU once, the K
+    per-fold Grams come from one weighted pass, and the K fold problems are enumerated as ``ls_spa(method='subsets')``
+    enumerates one (fp64, bitwise reproducible; include/lsspa.h, lsspa_cv_shapley).
+
+    folds:  the number of folds K (2 .. 32) -- with ``shuffle`` the rows are dealt by a permutation that is a pure
+        function of (seed, N), without it row i goes to fold i mod K -- or an integer array [N] of labels 0 .. K-1.
+
+    Returns ``CVResults``: ``attribution`` [p], ``fold_attribution`` [K][p] (its rows sum to ``attribution``),
+    ``r_squared`` (the cross-validated R^2 of the full model, what ``attribution`` sums to), ``fold_r_squared`` [K]
+    (each fold's share, summing to ``r_squared``), ``theta`` [p] (fitted on all rows) and ``fold_ids`` [N].
+
+    Shapes that do not fit, p > 32, K outside 2 .. 32, a label outside 0 .. K-1, an empty fold and a y that is
+    identically zero are refused before any GPU work.  A fold whose training rows give a Gram matrix that is not
+    numerically positive definite raises a RuntimeWarning that names the fold."""
+    X, y, ids, K = _cv_data("ls_spa_cv", X, y, folds, seed, shuffle)
+    with _engine_call(_engine, device) as engine:
+        engine.cv_load(X, y, ids, K, reg)
+        try:
+            phi, phi_fold, r2_fold, info = engine.cv_shapley()
+        finally:
+            engine.cv_free()
+    _cv_verdict(info, stacklevel=2)
+    G, g = _cv_full_problem(X, y, reg)
+    return CVResults(attribution=phi, fold_attribution=phi_fold, r_squared=float(_seq_sum(list(r2_fold))),
+                     fold_r_squared=np.asarray(r2_fold), theta=_subset_fit(G, g, np.arange(X.shape[1])), fold_ids=ids)
+
+
+def ls_spa_best_subsets_cv(X, y, reg=0., folds=5, *, include=None, seed=42, shuffle=True, device=0, _engine=None):
+    """Exhaustive best-subset selection by the K-fold cross-validated R^2: the best model of every size over all 2^p
+    feature subsets (p <= 32), judged not by one split but by all K.
+
+    ``ls_spa_best_subsets`` keeps the model that wins on one train / test split, and
+    ``ls_spa_best_subsets_bootstrap`` shows how unstable that choice is.  Here a subset's value is
+    v_cv(S) = sum_f v_f(S), fold f predicted by the model on S fitted on the other folds' rows, every fold over the
+    pooled ||y||^2.  Selection is not linear in the game: the K values of a subset have to be added before the
+    comparison, so a kernel of its own evaluates every subset on all K fold problems and keeps per size the largest
+    sum and its subset (fp64, the folds added in ascending order, bitwise reproducible; include/lsspa.h,
+    lsspa_cv_best).  On equal values the subset with the smaller mask (bit j = feature j) wins.
+
+    folds, seed, shuffle:  as for ``ls_spa_cv``.   include:  as for ``ls_spa_best_subsets``.
+
+    Returns ``CVBestSubsetsResults``: ``sizes``, ``subsets`` [n][p] bool, ``r_squared`` [n] (the cross-validated value),
+    ``fold_r_squared`` [n][K] (the winner's per-fold values, summing to it), ``theta`` [n][p] (each winner refitted on
+    ALL rows on the host in fp64, exactly 0.0 outside its subset), ``best_size`` (the smallest size on ties, NaN rows
+    skipped), ``best_subset``, ``full_r_squared`` (the cross-validated R^2 of all p columns) and ``fold_ids``.
+
+    The refusals of ``ls_spa_cv`` and those of ``include`` come before any GPU work.  A subset with a pivot that failed
+    in any fold is no candidate and raises a RuntimeWarning that names the folds; a size without a candidate is a NaN
+    row."""
+    X, y, ids, K = _cv_data("ls_spa_best_subsets_cv", X, y, folds, seed, shuffle)
+    p = X.shape[1]
+    mask, inc = include_mask(include, p)
+    with _engine_call(_engine, device) as engine:
+        engine.cv_load(X, y, ids, K, reg)
+        try:
+            v, masks, found, v_fold, info = engine.cv_best(mask)
+            full, _ = engine.debug_cv_values(np.array([(1 << p) - 1], dtype=np.uint64), folds=False)
+        finally:
+            engine.cv_free()
+    _cv_verdict(info, stacklevel=2)
+    G, g = _cv_full_problem(X, y, reg)
+    sizes = np.arange(len(inc), p + 1)
+    n = len(sizes)
+    subsets = np.zeros((n, p), dtype=bool)
+    r_squared = np.full(n, np.nan)
+    fold_r_squared = np.full((n, K), np.nan)
+    theta = np.full((n, p), np.nan)
+    for i, k in enumerate(sizes):
+        if found[k]:
+            subsets[i] = (int(masks[k]) >> np.arange(p)) & 1
+            r_squared[i] = v[k]
+            fold_r_squared[i] = v_fold[k]
+            theta[i] = _subset_fit(G, g, np.nonzero(subsets[i])[0])
+    best_size, best_subset = -1, np.zeros(p, dtype=bool)
+    if not np.all(np.isnan(r_squared)):
+        i = int(np.nanargmax(r_squared))      # the first of equal maxima: the smallest size
+        best_size, best_subset = int(sizes[i]), subsets[i].copy()
+    return CVBestSubsetsResults(sizes=sizes, subsets=subsets, r_squared=r_squared, fold_r_squared=fold_r_squared,
+                                theta=theta, best_size=best_size, best_subset=best_subset,
+                                full_r_squared=float(full[0]), fold_ids=ids)
 
 
 SUBSETS_TOP_MAX = 16       # include/lsspa.h, lsspa_subsets_top: ranks per size

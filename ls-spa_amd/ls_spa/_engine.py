@@ -216,6 +216,19 @@ def debug_subsets_top_plan(p: int, n_best: int):
     return dict(zip(SUBSETS_TOP_PLAN_FIELDS, (int(v) for v in out)))
 
 
+CV_PLAN_FIELDS = ("units", "per", "steps", "launches", "lds_bytes", "workgroup")
+
+
+def debug_cv_plan(p: int, folds: int):
+    """Test hook, host only: how cv_best enumerates p features over `folds` fold problems (include/lsspa.h,
+    lsspa_debug_cv_plan) -- a dict with CV_PLAN_FIELDS.  ValueError for a p or a number of folds the library refuses."""
+    out = np.zeros(8, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_plan(int(p), int(folds), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_plan: status {rc}")
+    return dict(zip(CV_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -644,6 +657,85 @@ class HipEngine:
         self._check(self._lib.lsspa_boot_debug_grams(self._h, int(R), N.dptr(wa), N.dptr(we), N.dptr(Sa), N.dptr(Se),
                                                      N.dptr(ws)))
         return Sa, Se, ws
+
+    # ---- K-fold cross-validation (p <= 32, 2 <= K <= 32) ---------------------------------------
+    CV_MAX_FOLDS = 32
+
+    def cv_load(self, X, y, fold_ids, K: int, reg: float):
+        """Keep the rows [X | y] and the K fold problems of the labels fold_ids [N] (0 .. K-1) on the device
+        (include/lsspa.h, lsspa_cv_load); the loaded problem and the bootstrap's rows are not touched."""
+        dt = np.float32 if X.dtype == np.float32 else np.float64
+        Xa, ya = np.ascontiguousarray(X, dtype=dt), np.ascontiguousarray(y, dtype=dt)
+        n, p = Xa.shape
+        self.cv_load_ptr(Xa.ctypes.data, p, ya.ctypes.data, n, p, fold_ids, K, reg, f32=dt == np.float32,
+                         location=N.HOST)
+
+    def cv_load_ptr(self, X_ptr, ld, y_ptr, n, p, fold_ids, K, reg, f32=False, location=N.DEVICE):
+        """Same, from pointers: rows [n][ld] of f32 or f64 on the host or the device, ld >= p; fold_ids a host array."""
+        fid = np.ascontiguousarray(fold_ids, dtype=np.int32)
+        if fid.shape != (int(n),):
+            raise ValueError(f"fold_ids must have shape ({int(n)},), got {fid.shape}")
+        self._check(self._lib.lsspa_cv_load(
+            self._h, C.c_void_p(X_ptr), int(ld), C.c_void_p(y_ptr), int(n), int(p), N.iptr(fid), int(K), float(reg),
+            N.F32 if f32 else N.F64, int(location)))
+        self._cv_dims = (int(p), int(K), int(n))
+
+    def cv_free(self):
+        self._check(self._lib.lsspa_cv_free(self._h))
+        self._cv_dims = None
+
+    def _cv_pk(self):
+        dims = getattr(self, "_cv_dims", None)
+        return (dims[0], dims[1]) if dims else (1, 2)
+
+    def cv_shapley(self):
+        """(phi [p], phi_fold [K][p], r2_fold [K], info [K]): the attribution of the cross-validated R^2, the folds'
+        attributions it is the sum of, each fold's share of the R^2 of the full model and the folds' info words
+        (include/lsspa.h, lsspa_cv_shapley)."""
+        p, K = self._cv_pk()
+        phi, fold, r2, info = np.empty(p), np.empty((K, p)), np.empty(K), np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_shapley(self._h, N.dptr(phi), N.dptr(fold), N.dptr(r2), N.iptr(info)))
+        return phi, fold, r2, info
+
+    def cv_best(self, include=0, steps: int = 0):
+        """(v [p + 1], masks [p + 1] uint32, found [p + 1] bool, v_fold [p + 1][K], info [K]): the best subset of every
+        size by the cross-validated value (include/lsspa.h, lsspa_cv_best).  steps > 0: that many steps of a unit per
+        launch (test hook; the result does not depend on it)."""
+        p, K = self._cv_pk()
+        n = p + 1
+        v, masks, found = np.empty(n), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)
+        v_fold, info = np.empty((n, K)), np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_best(
+            self._h, int(include), int(steps), N.dptr(v), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            found.ctypes.data_as(C.POINTER(C.c_uint8)), N.dptr(v_fold), N.iptr(info)))
+        return v, masks, found.astype(bool), v_fold, info
+
+    def cv_timing(self):
+        """Kernel seconds of the load's Gram side and of the last enumeration, its longest launch and the launches."""
+        a, b, c, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._check(self._lib.lsspa_cv_timing(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return {"gram": a.value / 1e3, "enumeration": b.value / 1e3, "max_launch": c.value / 1e3, "launches": n.value}
+
+    def cv_get_problem(self, f: int):
+        """Test hook: (G, g, H, h, inv_yy) of fold problem f as the device computed it."""
+        p, _ = self._cv_pk()
+        G, g, H, h, yy = np.empty((p, p)), np.empty(p), np.empty((p, p)), np.empty(p), C.c_double()
+        self._check(self._lib.lsspa_cv_get_problem(self._h, int(f), N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
+                                                   C.byref(yy)))
+        return G, g, H, h, yy.value
+
+    def debug_cv_values(self, masks, folds: bool = True):
+        """Test hook: (v [n], v_fold [n][K] or None) of the subsets `masks` (bit j = feature j) by cv_best's own device
+        code (include/lsspa.h, lsspa_debug_cv_values)."""
+        _, K = self._cv_pk()
+        masks = np.ascontiguousarray(masks, dtype=np.uint64)
+        v = np.empty(len(masks))
+        v_fold = np.empty((len(masks), K)) if folds else None
+        self._check(self._lib.lsspa_debug_cv_values(self._h, masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks),
+                                                    N.dptr(v), N.dptr(v_fold)))
+        return v, v_fold
+
+    debug_cv_plan = staticmethod(debug_cv_plan)
 
     # ---- exact attribution of many responses at once (p <= 32; over groups g <= 32, p <= 64) ----
     MULTI_RB = 8      # responses a wave carries per pass (csrc/kernels.h)

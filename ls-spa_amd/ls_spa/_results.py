@@ -835,3 +835,66 @@ class BestGroupSubsetsBootstrapResults:
             pad,
         ]
         return "\n".join(lines)
+
+
+@dataclass
+class CVResults:
+    """What ``ls_spa_cv`` returns for p features, K folds and N rows.  ``attribution`` [p]: the exact Shapley attribution
+    of the K-fold cross-validated R^2; ``fold_attribution`` [K][p]: the folds' attributions, whose sum over the folds in
+    ascending order it is; ``r_squared``: the cross-validated R^2 of the full model,
+    1 - sum_f ||y_f - X_f theta^(-f)||^2 / ||y||^2, what ``attribution`` sums to; ``fold_r_squared`` [K]: each fold's
+    share of it (over the pooled ||y||^2, so the shares add up to ``r_squared``); ``theta`` [p]: the coefficients fitted
+    on all rows; ``fold_ids`` [N]: the fold of every row."""
+    attribution: np.ndarray
+    fold_attribution: np.ndarray
+    r_squared: float
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    fold_ids: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}p = {len(self.attribution)}, {len(self.fold_r_squared)}-fold cross-validation",
+            f"{pad}Cross-validated R^2: {self.r_squared:.2e}",
+            f"{pad}Attribution: ({_head(self.attribution)})",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
+class CVBestSubsetsResults:
+    """What ``ls_spa_best_subsets_cv`` returns for p features, K folds and n = p + 1 - len(include) sizes: the fields of
+    ``BestSubsetsResults`` with the K-fold cross-validated R^2 as the value.  ``r_squared`` [n]: the winner's
+    cross-validated value; ``fold_r_squared`` [n][K]: its per-fold values, whose sum in ascending fold order it is;
+    ``theta`` [n][p]: the winner refitted on ALL rows, exactly 0.0 outside its subset; ``full_r_squared``: the
+    cross-validated R^2 of all p columns; ``fold_ids`` [N]: the fold of every row.  A size without a candidate is a row
+    of NaN / False, as there; ``best_size`` is the smallest size on ties, NaN rows skipped (-1 if every size is NaN)."""
+    sizes: np.ndarray
+    subsets: np.ndarray
+    r_squared: np.ndarray
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    best_size: int
+    best_subset: np.ndarray
+    full_r_squared: float
+    fold_ids: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        p = np.asarray(self.subsets).shape[1]
+        chosen = ", ".join(str(j) for j in np.nonzero(self.best_subset)[0][:12])
+        best = (f"{float(self.r_squared[self.best_size - int(self.sizes[0])]):.2e}"
+                if self.best_size >= 0 else "nan")
+        lines = [
+            "",
+            f"{pad}p = {p}, {np.asarray(self.fold_r_squared).shape[1]}-fold cross-validation, best subsets of sizes "
+            f"{int(self.sizes[0])} .. {int(self.sizes[-1])}",
+            f"{pad}Cross-validated R^2 with all features: {self.full_r_squared:.2e}",
+            f"{pad}Best model: {self.best_size} features, cross-validated R^2 {best}",
+            f"{pad}Its features: ({chosen}{', ...' if int(np.sum(self.best_subset)) > 12 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)
