@@ -468,7 +468,8 @@ int lsspa_debug_boot_groups_best_plan(int64_t R, int64_t N, int64_t M, const int
  *   lsspa_debug_cv_plan    : host only, no context, no GPU -- lsspa_cv_best's units, high subsets per unit, steps of a
  *                     unit per launch (each K fold evaluations: 2^20 / (units K), at least 1), launches, LDS bytes of
  *                     a workgroup, its threads, 0, 0.  p outside 1 .. 32 or K outside 2 .. 32 is LSSPA_ERR_ARG.
- * LSSPA_ERR_STATE before a load.  Top lists, groups, interactions and a bootstrap over the folds are not built. */
+ * LSSPA_ERR_STATE before a load.  Groups of columns: the next block.  Top lists, interactions and a bootstrap over the
+ * folds are not built. */
 int lsspa_cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
                   const int32_t* fold_ids /* [N], host */, int32_t K, double reg, int32_t dtype, int32_t location);
 int lsspa_cv_shapley(lsspa_ctx* ctx, double* phi /* [p] */, double* phi_fold /* [K][p] */, double* r2_fold /* [K] */,
@@ -481,6 +482,47 @@ int lsspa_cv_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double
 int lsspa_debug_cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v /* [n] */,
                           double* v_fold /* [n][K] or NULL */);
 int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan /* [8] */);
+
+/* K-FOLD CROSS-VALIDATION OVER GROUPS OF COLUMNS (g <= 32 groups of p <= 64 columns, 2 <= K <= 32, fp64): the players
+ * are the groups of `labels` (-1: the baseline, in every model; 0 .. g-1: the group), as in lsspa_groups_shapley, and
+ * the game is u_cv(S) = sum_f u_f(S) (f ascending, fp64), u_f(S) = v_f(baseline + columns of the groups in S) what
+ * lsspa_debug_group_values gives for fold problem f.  u_cv({}) is the baseline's own cross-validated value.
+ *   lsspa_cv_groups_load   : lsspa_cv_load with the limit p <= 64 -- the same store, packing, weights, Gram pass and
+ *                     fold problems, the same refusals with the same wording, naming 64.  One cross-validation problem
+ *                     is loaded at a time: either load replaces the other.  After a load of p <= 32 columns by either
+ *                     call both families work; after one of p > 32 lsspa_cv_shapley, lsspa_cv_best and
+ *                     lsspa_debug_cv_values refuse with LSSPA_ERR_STATE.  lsspa_cv_get_problem, lsspa_cv_timing and
+ *                     lsspa_cv_free serve both.
+ *   lsspa_cv_groups_shapley: phi [g] = sum_f phi_fold[f] (f ascending), phi_fold [K][g] (row f has the bits
+ *                     lsspa_groups_shapley gives for problem f: the same kernel, each fold cut into launches as that
+ *                     call cuts one problem), r2_fold [K] = u_f(all groups), base_fold [K] = u_f({}), info [K].  phi sums
+ *                     to sum r2_fold - sum base_fold.  Labels, limits and refusals are lsspa_groups_shapley's.
+ *   lsspa_cv_groups_best   : lsspa_groups_best by u_cv: u [g+1], masks (the caller's numbering: bit k = label k), found
+ *                     -- size 0 is the baseline alone; the larger u_cv wins, on equal values the smaller mask, so the
+ *                     result depends on no cut --, candidates: the subset's own pivots passed in EVERY fold (info [K]
+ *                     says which fold failed).  u[k] has the bits of lsspa_debug_cv_group_values for masks[k]; u_fold
+ *                     [g+1][K]: the winner's per-fold values (NaN where found[k] = 0).  steps as in lsspa_cv_best.
+ *   lsspa_debug_cv_group_values: test hook -- u[i] = u_cv(masks[i]) and, unless NULL, u_fold[i][f] = u_f(masks[i]) by
+ *                     lsspa_cv_groups_best's own device code.  A failed pivot is no error here.
+ *   lsspa_debug_cv_groups_plan : host only -- lsspa_debug_groups_best_plan's gl, gh, ql, nb, units and per, then
+ *                     lsspa_cv_groups_best's steps of a unit per launch (each K fold evaluations: the one-problem
+ *                     launch bound / (units K), at least 1, at most per), its launches, the LDS bytes of a workgroup,
+ *                     its threads (256), the LDS bytes of lsspa_groups_best's workgroup and that launch bound.  Labels
+ *                     the library refuses, p > 64, g > 32 or K outside 2 .. 32: LSSPA_ERR_ARG.
+ * Top lists, interactions and a bootstrap over the folds are not built. */
+int lsspa_cv_groups_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+                         const int32_t* fold_ids /* [N], host */, int32_t K, double reg, int32_t dtype,
+                         int32_t location);
+int lsspa_cv_groups_shapley(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, double* phi /* [g] */,
+                            double* phi_fold /* [K][g] */, double* r2_fold /* [K] */, double* base_fold /* [K] */,
+                            int32_t* info /* [K] */);
+int lsspa_cv_groups_best(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, int64_t steps,
+                         double* u /* [g+1] */, uint32_t* masks /* [g+1] */, uint8_t* found /* [g+1] */,
+                         double* u_fold /* [g+1][K] */, int32_t* info /* [K] */);
+int lsspa_debug_cv_group_values(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, const uint64_t* masks,
+                                int64_t n, double* u /* [n] */, double* u_fold /* [n][K] or NULL */);
+int lsspa_debug_cv_groups_plan(const int32_t* labels /* [p] */, int32_t p, int32_t g, int32_t K,
+                               int64_t* plan /* [12] */);
 
 /* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
  * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the

@@ -1,5 +1,6 @@
 // K-fold cross-validation (lsspa_cv_load .. lsspa_cv_free; DESIGN.md, "K-fold cross-validation"): the small kernels
-// between the bootstrap's weighted Gram pass (k_boot.hip) and the enumerations of k_subsets.hip.  fp64 throughout.
+// between the bootstrap's weighted Gram pass (k_boot.hip) and the enumerations of k_subsets.hip and, over groups of
+// columns (lsspa_cv_groups_*, p <= 64), of k_groups.hip.  fp64 throughout.
 //
 // The rows z_i = [x_i, y_i] are packed once (launch_boot_pack).  Fold f's Gram S_f = sum_{i in f} z_i z_i^T is the
 // bootstrap's weighted Gram with the indicator of the fold as the weights: cv_weights_kernel writes those from the
@@ -65,6 +66,27 @@ __global__ __launch_bounds__(64) void cv_foldsum_kernel(const double* __restrict
   phi[j] = s;
 }
 
+// cv_foldsum_kernel over groups: the enumeration's columns are in the layout's numbering, gid[r] the caller's label of
+// the layout's group r (GroupLayout::gid, by value)
+struct CvGroupIds {
+  uint8_t id[GROUPS_MAX_G];
+};
+
+__global__ __launch_bounds__(64) void cv_groups_foldsum_kernel(const double* __restrict__ out, int ng, int folds,
+                                                               CvGroupIds ids, double* __restrict__ phi_fold,
+                                                               double* __restrict__ phi) {
+  const int r = threadIdx.x;
+  if (r >= ng) return;
+  const int k = ids.id[r];
+  double s = 0.0;
+  for (int f = 0; f < folds; ++f) {
+    const double v = out[f * (ng + 1) + r] - out[f * (ng + 1) + ng];
+    phi_fold[f * ng + k] = v;
+    s = f == 0 ? v : s + v;
+  }
+  phi[k] = s;
+}
+
 }  // namespace
 
 hipError_t launch_cv_weights(const int32_t* fid, int64_t n, int folds, double* wt, hipStream_t st) {
@@ -76,7 +98,8 @@ hipError_t launch_cv_weights(const int32_t* fid, int64_t n, int folds, double* w
 
 hipError_t launch_cv_finalize(const double* S, const int32_t* nf, int64_t n, int p, int folds, double reg, double* G,
                               double* g, double* H, double* h, double* inv_yy, hipStream_t st) {
-  if (!S || !nf || !G || !g || !H || !h || !inv_yy || n < 2 || p < 1 || p > SUBSETS_MAX_P || folds < 2 ||
+  // p up to GROUPS_MAX_P: the grouped load (lsspa_cv_groups_load); the kernel strides over p^2 and has 256 >= p threads
+  if (!S || !nf || !G || !g || !H || !h || !inv_yy || n < 2 || p < 1 || p > GROUPS_MAX_P || folds < 2 ||
       folds > CV_MAX_FOLDS)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(cv_finalize_kernel, dim3((unsigned)folds), dim3(256), 0, st, S, nf, n, p, folds, reg, G, g, H, h,
@@ -88,6 +111,21 @@ hipError_t launch_cv_foldsum(const double* out, int p, int folds, double* phi_fo
   if (!out || !phi_fold || !phi || p < 1 || p > SUBSETS_MAX_P || folds < 2 || folds > CV_MAX_FOLDS)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(cv_foldsum_kernel, dim3(1), dim3(64), 0, st, out, p, folds, phi_fold, phi);
+  return hipGetLastError();
+}
+
+hipError_t launch_cv_groups_foldsum(const double* out, int ng, int folds, const int* gid, double* phi_fold, double* phi,
+                                    hipStream_t st) {
+  if (!out || !gid || !phi_fold || !phi || ng < 1 || ng > GROUPS_MAX_G || folds < 2 || folds > CV_MAX_FOLDS)
+    return hipErrorInvalidValue;
+  CvGroupIds ids{};
+  uint32_t seen = 0u;
+  for (int r = 0; r < ng; ++r) {                     // a permutation of 0 .. ng-1: every entry of phi is written once
+    if (gid[r] < 0 || gid[r] >= ng || ((seen >> gid[r]) & 1u)) return hipErrorInvalidValue;
+    seen |= 1u << gid[r];
+    ids.id[r] = (uint8_t)gid[r];
+  }
+  hipLaunchKernelGGL(cv_groups_foldsum_kernel, dim3(1), dim3(64), 0, st, out, ng, folds, ids, phi_fold, phi);
   return hipGetLastError();
 }
 

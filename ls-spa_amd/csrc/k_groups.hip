@@ -73,6 +73,11 @@
 // butterfly under the total order, and lane 0 merges the winner into the unit's row of the table, values [units][g + 1]
 // and (caller mask, found) [units][g + 1][2], with plain loads and stores (one workgroup owns a row, launches are ordered
 // by the stream).  launch_subsets_best_reduce then takes the best over the units.  No atomics on the table.
+//
+// K-fold cross-validation over groups (lsspa_cv_groups_best, groups_cv_best_kernel below): that kernel's sibling, which
+// takes every high subset through the K fold problems of k_cv.hip in one step and keeps the best SUM of their values
+// per size.  The attribution (lsspa_cv_groups_shapley) needs no kernel of its own: the folds are replicates of the
+// enumeration kernel's REPS instantiation.
 #include "kernels.h"
 
 #include <algorithm>
@@ -629,6 +634,145 @@ __global__ __launch_bounds__(NT) void groups_best_kernel(GroupArgs a, uint64_t s
   if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info + rep_offset<REPS>(1), 1);
 }
 
+// ---- best group subset of every size by the K-fold cross-validated value (lsspa_cv_groups_best) ----
+// groups_best_kernel<false>'s sibling: the same workgroup, units, steps and launches, running bests per class popc(s) in
+// GrpBestShared, merge, table layout and launch_subsets_best_reduce.  What is compared is not one problem's u(S) but
+//   u_cv(S) = u_0(S) + u_1(S) + ... + u_{F-1}(S)   (fp64, in this order),
+// u_f the value group_values gives for fold problem f: the F reduced problems of k_cv.hip lie one behind the other at the
+// dense replicate stride (GroupArgs::inv_yy_rep has their F denominators), and one step takes its high subset through all
+// of them before the compare.  A subset is a candidate only if its own pivots passed in EVERY fold; a failed pivot raises
+// the info word of the fold it failed in.
+//   group_values reads G, g and H of its problem from memory; of the workgroup's LDS only sh.h and sh.gdiag belong to a
+// problem.  A fold-step stages fold f's 2 p words into them and runs group_values<false> on fold f's addresses -- the
+// same code on other addresses, so u_f has the bits the one-problem kernels give for problem f -- and LDS stays
+// GrpShared + GrpBestShared whatever F is: two workgroups a CU, as the sibling's ("K-fold cross-validation
+// over groups", has the alternatives).  The hazard: inside group_values wave 0 reads sh.gdiag in its 6 x 6 Cholesky
+// AFTER the function's last barrier, so fold f + 1 may be staged only behind a barrier that follows fold f's return --
+// the barrier that ends a step anyway (the next group_values writes sh.idx, which that Cholesky reads too) ends a
+// fold-step here.  The staged words are published by group_values' own first barrier, before anyone reads them.
+__device__ inline GroupArgs fold_args(const GroupArgs& a, int f) {
+  GroupArgs b = a;
+  b.G += (int64_t)f * a.p * a.ldg;
+  b.H += (int64_t)f * a.p * a.ldh;
+  b.g += (int64_t)f * a.p;
+  b.h += (int64_t)f * a.p;
+  b.inv_yy = a.inv_yy_rep[f];
+  return b;
+}
+
+// h and the pivot scale of one fold into sh; the caller's last barrier is behind every read of them
+__device__ inline void stage_fold(GrpShared& sh, const GroupArgs& a, int tid) {
+  if (tid < a.p) {
+    sh.h[tid] = a.h[tid];
+    sh.gdiag[tid] = a.G[(int64_t)tid * a.ldg + tid];
+  }
+}
+
+// a.part [units][g + 1], bm [units][g + 1][2] as groups_best_kernel's; a.info [F]
+__global__ __launch_bounds__(NT) void groups_cv_best_kernel(GroupArgs a, int F, uint64_t s0, uint64_t s1, GroupIds ids,
+                                                            uint32_t* __restrict__ bm) {
+  __shared__ GrpShared sh;
+  __shared__ GrpBestShared sb;
+  const int tid = threadIdx.x;
+  const int ng = a.ng, gl = a.gl, gh = a.gh;
+  const bool live = tid < (1 << gl);           // wave 0 only (gl <= 6)
+  if (tid < GG) sb.gid[tid] = ids.id[tid];
+  if (live) {
+    for (int j = 0; j < GBS; ++j) {            // the lane's own slots: nobody else reads or writes them
+      sb.v[j * 64 + tid] = -__builtin_huge_val();
+      sb.h[j * 64 + tid] = 0u;
+    }
+  }
+  load_shared<false>(sh, a, tid);              // (ends with a barrier: gid; h and gdiag are restaged per fold)
+  uint32_t bad_folds = 0u;                     // bit f: a pivot of fold f failed in a subset this thread saw
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    double v = 0.0;
+    bool bad_any = false;                      // this subset's own pivots, over the folds
+#pragma unroll 1
+    for (int f = 0; f < F; ++f) {
+      const GroupArgs af = fold_args(a, f);
+      stage_fold(sh, af, tid);
+      bool bad = false;
+      const double vf = group_values<false>(sh, af, hi, tid, bad);
+      v = f == 0 ? vf : v + vf;
+      bad_any |= bad;
+      bad_folds |= bad ? (1u << f) : 0u;
+      __syncthreads();
+    }
+    // the lane's own slots, written behind the step's last barrier: nobody else touches them (groups_best_kernel)
+    if (live && !bad_any) {
+      const int e = __popcll(s) * 64 + tid;    // popc(s) < GBS: launch_groups_cv_best
+      if (v > sb.v[e]) {
+        sb.v[e] = v;
+        sb.h[e] = (uint32_t)hi;                // gh <= 31
+      }
+    }
+  }
+  if (tid < 64) {
+    double* rv = a.part + (int64_t)blockIdx.x * (ng + 1);
+    uint32_t* rm = bm + (int64_t)blockIdx.x * (ng + 1) * 2;
+    const int ncls = __popcll(a.per - 1) + 1;
+    const int k0 = __popc(blockIdx.x), k1 = min(ng, k0 + ncls - 1 + gl);
+    const int base = k0 + __popc(tid);         // |S| of this lane's class 0
+    uint32_t low = 0u;                         // the lane's low groups in the caller's numbering
+    for (int r = 0; r < gl; ++r)
+      if ((tid >> r) & 1) low |= 1u << sb.gid[r];
+    for (int k = k0; k <= k1; ++k) {
+      const int j = k - base;
+      double v = -__builtin_huge_val();
+      uint32_t mask = 0u;
+      if (live && j >= 0 && j < ncls) {
+        v = sb.v[j * 64 + tid];
+        const uint32_t h = sb.h[j * 64 + tid];
+        mask = low;
+        for (int r = 0; r < gh; ++r)
+          if ((h >> r) & 1u) mask |= 1u << sb.gid[gl + r];
+      }
+      wave_best(v, mask);                      // over caller masks, as in groups_best_kernel
+      if (tid == 0 && v > -__builtin_huge_val()) {
+        if (rm[2 * k + 1] != 0u) best_merge(v, mask, rv[k], rm[2 * k]);
+        rv[k] = v;
+        rm[2 * k] = mask;
+        rm[2 * k + 1] = 1u;
+      }
+    }
+  }
+  for (int f = 0; f < F; ++f)
+    if (__any((bad_folds >> f) & 1u) && (tid & 63) == 0) atomicOr(a.info + f, 1);
+}
+
+// test hook and the winners' per-fold values: vals[i] = u_cv(masks[i]), vfold[i][f] = u_f(masks[i]) (vfold may be null),
+// masks in the layout's numbering, by the very fold-step of groups_cv_best_kernel
+__global__ __launch_bounds__(NT) void groups_cv_debug_kernel(GroupArgs a, int F, const uint64_t* __restrict__ masks,
+                                                             int64_t n, double* __restrict__ vals,
+                                                             double* __restrict__ vfold) {
+  __shared__ GrpShared sh;
+  const int tid = threadIdx.x;
+  load_shared<false>(sh, a, tid);
+  uint32_t bad_folds = 0u;
+  const uint64_t low = (1ull << a.gl) - 1ull;
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint64_t m = masks[i];
+    const bool mine = (uint64_t)tid == (m & low);
+    double v = 0.0;
+#pragma unroll 1
+    for (int f = 0; f < F; ++f) {
+      const GroupArgs af = fold_args(a, f);
+      stage_fold(sh, af, tid);
+      bool bad = false;
+      const double vf = group_values<false>(sh, af, m >> a.gl, tid, bad);
+      v = f == 0 ? vf : v + vf;
+      bad_folds |= bad ? (1u << f) : 0u;
+      if (mine && vfold) vfold[i * F + f] = vf;
+      __syncthreads();
+    }
+    if (mine) vals[i] = v;
+  }
+  for (int f = 0; f < F; ++f)
+    if (__any((bad_folds >> f) & 1u) && (tid & 63) == 0) atomicOr(a.info + f, 1);
+}
+
 // ---- the T best group subsets of every size (lsspa_groups_top) ----
 // groups_best_kernel's sibling, one problem only: the same workgroup, units, steps and launches, load_shared<false> and
 // group_values<false>, the same candidates (the subset's own pivots passed, its value is above -inf, so never NaN) and
@@ -923,6 +1067,40 @@ hipError_t launch_groups_top(const GroupArgs& a, const int* gid, uint64_t units,
     ids.id[r] = (uint8_t)gid[r];
   }
   hipLaunchKernelGGL(groups_top_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, s0, s1, ids, T, tm, tc);
+  return hipGetLastError();
+}
+
+// the two __shared__ objects both kernels declare, each at the 16-byte alignment the compiler gives them (its
+// resource report says 58352 for both)
+static constexpr size_t lds16(size_t n) { return (n + 15) / 16 * 16; }
+size_t groups_best_lds_bytes() { return lds16(sizeof(GrpShared)) + lds16(sizeof(GrpBestShared)); }
+size_t groups_cv_lds_bytes() { return lds16(sizeof(GrpShared)) + lds16(sizeof(GrpBestShared)); }
+
+hipError_t launch_groups_cv_best(const GroupArgs& a, int folds, const int* gid, uint64_t units, uint64_t s0, uint64_t s1,
+                                 uint32_t* bm, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !bm || !gid || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  // the caller vouches for `folds` problems, denominators (inv_yy_rep) and info words behind the first
+  if (!a.inv_yy_rep || folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  if (a.gh > GHI) return hipErrorInvalidValue;       // hi is kept in 32 bits (no layout of <= 64 columns has gh = 32)
+  if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  if (a.per > (1ull << (GBS - 1))) return hipErrorInvalidValue;
+  GroupIds ids{};
+  uint32_t seen = 0u;
+  for (int r = 0; r < a.ng; ++r) {                   // a permutation of 0 .. ng-1: the kernel shifts by them
+    if (gid[r] < 0 || gid[r] >= a.ng || ((seen >> gid[r]) & 1u)) return hipErrorInvalidValue;
+    seen |= 1u << gid[r];
+    ids.id[r] = (uint8_t)gid[r];
+  }
+  hipLaunchKernelGGL(groups_cv_best_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, folds, s0, s1, ids, bm);
+  return hipGetLastError();
+}
+
+hipError_t launch_groups_cv_debug(const GroupArgs& a, int folds, const uint64_t* masks, int64_t n, double* vals,
+                                  double* vfold, hipStream_t st) {
+  if (!args_ok(a) || !masks || !vals || n < 1) return hipErrorInvalidValue;
+  if (!a.inv_yy_rep || folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  const int64_t grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(groups_cv_debug_kernel, dim3((unsigned)grid), dim3(NT), 0, st, a, folds, masks, n, vals, vfold);
   return hipGetLastError();
 }
 

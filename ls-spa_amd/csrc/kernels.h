@@ -392,6 +392,7 @@ hipError_t launch_cv_weights(const int32_t* fid, int64_t n, int folds, double* w
 // The fold problems from the per-fold Grams S [folds][c][c] (c = p + 1) and the folds' sizes nf [folds] of n rows:
 //   G[f] = (sum_{j != f} S[j])[:p,:p] / (n - nf[f]) + reg I (j ascending), g[f] likewise from column p,
 //   H[f] = S[f][:p,:p], h[f] = S[f][:p,p], inv_yy[f] = 1 / sum_j S[j][p][p] (j ascending, the same for every f)
+// p <= GROUPS_MAX_P: the grouped calls (lsspa_cv_groups_*) read the same problems
 hipError_t launch_cv_finalize(const double* S, const int32_t* nf, int64_t n, int p, int folds, double reg, double* G,
                               double* g, double* H, double* h, double* inv_yy, hipStream_t st);
 // phi_fold[f][j] = out[f][j] - out[f][p] of the enumeration's column sums out [folds][p + 1], phi[j] = their sum over f
@@ -482,6 +483,25 @@ hipError_t launch_groups_best(const GroupArgs& a, const int* gid, uint64_t units
 constexpr int GROUPS_TOP_MAX = SUBSETS_TOP_MAX;
 hipError_t launch_groups_top(const GroupArgs& a, const int* gid, uint64_t units, uint64_t s0, uint64_t s1, int T,
                              uint32_t* tm, int32_t* tc, hipStream_t st);
+// K-fold cross-validation over groups (lsspa_cv_groups_*).  The `folds` fold problems of k_cv.hip lie behind a's at the
+// dense replicate stride with their denominators in GroupArgs::inv_yy_rep [folds] and one info word each (the caller
+// vouches for them); the attribution runs them as replicates of launch_groups_enum.
+// launch_groups_cv_best: launch_groups_best's units, steps, launches, tables, candidates, order and refusals (one table:
+// no second grid dimension), for u_cv(S) = u_0(S) + ... + u_{folds-1}(S), the fp64 sum in this order of the values
+// launch_groups_debug gives for the fold problems; a candidate's own pivots passed in every fold, and a failed pivot
+// raises a.info[fold].  launch_subsets_best_reduce (p = g) takes the best over the units.  2 <= folds <= CV_MAX_FOLDS.
+hipError_t launch_groups_cv_best(const GroupArgs& a, int folds, const int* gid, uint64_t units, uint64_t s0, uint64_t s1,
+                                 uint32_t* bm, hipStream_t st);
+// vals[i] = u_cv(masks[i]) and, unless null, vfold[i][f] = u_f(masks[i]) by that kernel's own fold-step; masks in the
+// layout's numbering
+hipError_t launch_groups_cv_debug(const GroupArgs& a, int folds, const uint64_t* masks, int64_t n, double* vals,
+                                  double* vfold, hipStream_t st);
+size_t groups_cv_lds_bytes();      // static LDS of a workgroup of launch_groups_cv_best
+size_t groups_best_lds_bytes();    // and of launch_groups_best's one-problem kernel
+// phi_fold[f][gid[r]] = out[f][r] - out[f][ng] of the grouped enumeration's column sums out [folds][ng + 1] (layout
+// numbering; gid: GroupLayout::gid), phi[k] = their sum over f in ascending order
+hipError_t launch_cv_groups_foldsum(const double* out, int ng, int folds, const int* gid, double* phi_fold, double* phi,
+                                    hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

@@ -109,6 +109,8 @@ struct CvWork {
   DevBuf<double> G, g, H, h, inv_yy;       // the fold problems [K]...
   std::vector<double> Gh, gh, Hh, hh, yh;  // the same on the host
   DevBuf<double> w, part, out, phi, vals;  // Shapley weights, partial table, its sums, phi_fold | phi, debug values
+  DevBuf<double> gw;                       // the grouped calls' Shapley weights (of g players; w is of p, p <= 32 only)
+  DevBuf<int32_t> tab;                     // and their layout table (GroupLayout::tab)
   DevBuf<uint64_t> masks;
   DevBuf<int32_t> info, dinfo;             // [K] info words of a call; the debug values' own
   DevBuf<uint32_t> best;                   // lsspa_cv_best: (mask, found) of the units' rows, then of the result
@@ -118,6 +120,7 @@ struct CvWork {
     dev_free(Z); dev_free(stage_x); dev_free(stage_y); dev_free(fid); dev_free(nf); dev_free(wt); dev_free(gpart);
     dev_free(S); dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(part);
     dev_free(out); dev_free(phi); dev_free(vals); dev_free(masks); dev_free(info); dev_free(dinfo); dev_free(best);
+    dev_free(gw); dev_free(tab);
     loaded = false;
   }
 };
@@ -3612,12 +3615,15 @@ int subsets_top(lsspa_ctx* ctx, uint32_t include, int T, double* v, uint32_t* ma
 // subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X: far below the bound of
 // 0.2 s, and long enough that the launches' own cost does not show.
 constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
-// steps of every unit that one launch of `units` workgroups takes on the layout L
-uint64_t groups_steps(const GroupLayout& L, uint64_t units) {
+// high subsets one launch takes at most over all its workgroups on the layout L
+uint64_t groups_per_launch(const GroupLayout& L) {
   // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
   const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
-  const uint64_t per_launch = std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
-  return std::max<uint64_t>(1, per_launch / units);
+  return std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
+}
+// steps of every unit that one launch of `units` workgroups takes on the layout L
+uint64_t groups_steps(const GroupLayout& L, uint64_t units) {
+  return std::max<uint64_t>(1, groups_per_launch(L) / units);
 }
 
 int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, GroupLayout& L) {
@@ -5103,12 +5109,13 @@ int cv_enum_timing(lsspa_ctx* ctx, const std::vector<hipEvent_t>& ev, size_t n_l
   return LSSPA_OK;
 }
 
-int cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p, const int32_t* fold_ids,
-            int32_t K, double reg, int32_t dtype, int32_t location) {
+// max_p: SUBSETS_MAX_P (lsspa_cv_load) or GROUPS_MAX_P (lsspa_cv_groups_load); `name` is the entry point's
+int cv_load(lsspa_ctx* ctx, const char* name, int max_p, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+            const int32_t* fold_ids, int32_t K, double reg, int32_t dtype, int32_t location) {
   char msg[240];
-  if (p > SUBSETS_MAX_P) {
+  if (p > max_p) {
     snprintf(msg, sizeof msg, "cross-validation enumerates feature subsets and takes at most p = %d features (%d given)",
-             SUBSETS_MAX_P, (int)p);
+             max_p, (int)p);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
   if (K < 2 || K > CV_MAX_FOLDS) {
@@ -5117,10 +5124,13 @@ int cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N,
   }
   if (!X || !y || !fold_ids || p < 1 || ld < p || !std::isfinite(reg) || (dtype != LSSPA_F64 && dtype != LSSPA_F32) ||
       (location != LSSPA_HOST && location != LSSPA_DEVICE))
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_load: NULL array, p < 1, ld < p, reg not finite, or bad dtype / location");
-  BootPlan P;
-  if (const char* why = boot_plan(K, N, N, p, 0, P)) {
-    snprintf(msg, sizeof msg, "lsspa_cv_load: %s", why);
+  {
+    snprintf(msg, sizeof msg, "%s: NULL array, p < 1, ld < p, reg not finite, or bad dtype / location", name);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootPlan P;      // the rows' layout and the Gram pass depend on N and p alone; beyond 32 columns: the columns as one group
+  if (const char* why = p <= SUBSETS_MAX_P ? boot_plan(K, N, N, p, 0, P) : boot_groups_plan(K, N, N, p, 1, 1, 0, 0, 0, P)) {
+    snprintf(msg, sizeof msg, "%s: %s", name, why);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
   int32_t nf[CV_MAX_FOLDS] = {0};
@@ -5165,8 +5175,8 @@ int cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N,
                 [&](const void* sx, const void* sy, int64_t nr, int64_t r0) {
                   return launch_boot_pack(sx, ld, sy, nr, p, dtype == LSSPA_F32, W.Z.ptr, P.ldz, r0, st);
                 }));
-  double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)];
-  exact_weight_table(p, w);
+  double w[EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1)] = {0.0};
+  if (p <= SUBSETS_MAX_P) exact_weight_table(p, w);    // the column calls' weights; they refuse a wider load
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipMemcpy(W.w.ptr, w, sizeof w, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(W.fid.ptr, fold_ids, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
@@ -5310,14 +5320,297 @@ int cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, uint32_t
   return LSSPA_OK;
 }
 
+// ---- ... over groups of columns (lsspa_cv_groups_*; the CV kernels of k_groups.hip) ----
+// The fold problems are the same store; the players are the g groups of the labels, the baseline (label -1) is in every
+// model.  lsspa_cv_groups_shapley runs the REPS enumeration of k_groups.hip over the folds, cut as lsspa_groups_shapley
+// cuts one problem; lsspa_cv_groups_best runs groups_cv_best_kernel.
+
+// the column calls after a grouped load of more columns than they enumerate
+int cv_need_columns(lsspa_ctx* ctx, const char* name) {
+  if (ctx->cv.p > SUBSETS_MAX_P) {
+    char msg[280];
+    snprintf(msg, sizeof msg, "%s enumerates feature subsets and takes at most p = %d features (%d loaded by "
+             "lsspa_cv_groups_load: lsspa_cv_groups_shapley and lsspa_cv_groups_best work on groups of them)", name,
+             SUBSETS_MAX_P, ctx->cv.p);
+    return ctx->fail(LSSPA_ERR_STATE, msg);
+  }
+  return LSSPA_OK;
+}
+
+// labels / g against the loaded columns: lsspa_groups_shapley's limits and messages (groups_args)
+int cv_layout(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupLayout& L) {
+  char msg[200];
+  if (g > GROUPS_MAX_G) {
+    snprintf(msg, sizeof msg, "exact attribution over groups takes at most g = %d groups (%d given)", GROUPS_MAX_G,
+             (int)g);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (const char* why = groups_layout(labels, ctx->cv.p, g, L)) {
+    snprintf(msg, sizeof msg, "group labels: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  return LSSPA_OK;
+}
+
+struct CvGroupsPlan {
+  uint64_t units, per, steps, launches;
+};
+// lsspa_cv_groups_best's cut: a step of a unit takes its high subset through K fold problems, so a launch takes 1 / K of
+// the steps lsspa_groups_best gives it (at least one); forced > 0: that many steps a launch instead (test hook)
+CvGroupsPlan cv_groups_best_plan(const GroupLayout& L, int K, uint64_t forced) {
+  CvGroupsPlan P;
+  const uint64_t n_high = 1ull << L.gh;
+  P.units = exact_units(n_high);
+  P.per = n_high / P.units;
+  P.steps = forced ? forced : std::max<uint64_t>(1, groups_per_launch(L) / (P.units * (uint64_t)K));
+  P.steps = std::min(P.steps, P.per);
+  P.launches = (P.per + P.steps - 1) / P.steps;
+  return P;
+}
+
+// the weights of L.ng players and the layout table, for the launches of one call
+int cv_groups_upload(lsspa_ctx* ctx, const GroupLayout& L) {
+  CvWork& W = ctx->cv;
+  constexpr int WR = EXACT_MAX_PLAYERS + 1;
+  double w[EXACT_W_ROWS * WR];
+  exact_weight_table(L.ng, w);
+  TRY(dev_alloc(ctx, W.gw, EXACT_W_ROWS * WR));
+  TRY(dev_alloc(ctx, W.tab, GROUPS_TAB_LEN));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // a previous call may still read them; the copies are from host frames
+  HIPCHK(hipMemcpy(W.gw.ptr, w, sizeof w, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(W.tab.ptr, L.tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
+  return LSSPA_OK;
+}
+
+// k_groups.hip's view of the fold problems from e0 on, over the layout L; info: the [K] words the call reports into
+GroupArgs cv_group_args(const CvWork& W, const GroupLayout& L, int e0, int32_t* info) {
+  const int p = W.p;
+  GroupArgs a{};
+  a.p = p; a.ng = L.ng; a.nb = L.nb;
+  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+  a.G = W.G.ptr + (size_t)e0 * p * p;
+  a.H = W.H.ptr + (size_t)e0 * p * p;
+  a.g = W.g.ptr + (size_t)e0 * p;
+  a.h = W.h.ptr + (size_t)e0 * p;
+  a.ldg = a.ldh = p;
+  a.w = W.gw.ptr;
+  a.tab = W.tab.ptr;
+  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.inv_yy_rep = W.inv_yy.ptr + e0;
+  a.info = info + e0;
+  return a;
+}
+
+// u [n] and, unless NULL, u_fold [n][K] of the host masks (bit k = group k, the caller's numbering) by
+// groups_cv_debug_kernel, after cv_groups_upload; the pivots' verdicts go to W.dinfo, which nobody reads
+int cv_group_values(lsspa_ctx* ctx, const GroupLayout& L, const uint64_t* masks, int64_t n, double* u, double* u_fold) {
+  CvWork& W = ctx->cv;
+  const int K = W.K;
+  std::vector<uint64_t> lay((size_t)n, 0);     // -> the layout's numbering (low groups first)
+  for (int64_t i = 0; i < n; ++i)
+    for (int r = 0; r < L.ng; ++r)
+      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  TRY(dev_alloc(ctx, W.masks, (size_t)n));
+  TRY(dev_alloc(ctx, W.vals, (size_t)n * (K + 1)));
+  TRY(dev_alloc(ctx, W.dinfo, CV_MAX_FOLDS));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(W.masks.ptr, lay.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(W.dinfo.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, ctx->stream));
+  GroupArgs a = cv_group_args(W, L, 0, W.dinfo.ptr);
+  a.per = 1;
+  HIPCHK(launch_groups_cv_debug(a, K, W.masks.ptr, n, W.vals.ptr, u_fold ? W.vals.ptr + n : nullptr, ctx->stream));
+  HIPCHK(hipMemcpyAsync(u, W.vals.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (u_fold)
+    HIPCHK(hipMemcpyAsync(u_fold, W.vals.ptr + n, sizeof(double) * n * K, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return LSSPA_OK;
+}
+
+int cv_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, double* phi_fold, double* r2_fold,
+                      double* base_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  GroupLayout L;
+  TRY(cv_layout(ctx, labels, g, L));
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(cv_groups_upload(ctx, L));
+  hipStream_t st = ctx->stream;
+  const int K = W.K, ng = L.ng, cols = ng + 1;
+  const uint64_t n_high = 1ull << L.gh;
+  const uint64_t units = exact_units(n_high), per = n_high / units;
+  // a fold's launches are lsspa_groups_shapley's (the cut of `per` shows in the bits); as many folds share a launch as
+  // its work bound and the 2^20 workgroups of a launch leave (boot_groups_plan's rule)
+  const uint64_t steps = std::min(per, groups_steps(L, units));
+  const uint64_t room = std::min<uint64_t>(1ull << 20, groups_per_launch(L)) / (units * steps);
+  const int ereps = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, room));
+  TRY(dev_alloc(ctx, W.part, (size_t)ereps * units * cols));
+  TRY(dev_alloc(ctx, W.out, (size_t)K * cols));
+  TRY(dev_alloc(ctx, W.phi, (size_t)(K + 1) * ng));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  const size_t n_launch = (size_t)((K + ereps - 1) / ereps) * (size_t)((per + steps - 1) / steps);
+  std::vector<hipEvent_t> ev(2 * n_launch, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  size_t l = 0;
+  for (int e0 = 0; e0 < K; e0 += ereps) {
+    const int ne = std::min(ereps, K - e0);
+    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)ne * units * cols, st));
+    GroupArgs a = cv_group_args(W, L, e0, W.info.ptr);
+    a.per = per;
+    a.part = W.part.ptr;
+    for (uint64_t s0 = 0; s0 < per; s0 += steps, ++l) {
+      HIPCHK(hipEventRecord(ev[2 * l], st));
+      HIPCHK(launch_groups_enum(a, units, s0, std::min(per, s0 + steps), false, st, ne));
+      HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+    }
+    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, cols, W.out.ptr + (size_t)e0 * cols, st, ne));
+  }
+  // a fold into label order as the bootstrap finishes a replicate, then the folds' sum in ascending order
+  HIPCHK(launch_cv_groups_foldsum(W.out.ptr, ng, K, L.gid, W.phi.ptr, W.phi.ptr + (size_t)K * ng, st));
+  HIPCHK(hipMemcpyAsync(phi_fold, W.phi.ptr, sizeof(double) * K * ng, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(phi, W.phi.ptr + (size_t)K * ng, sizeof(double) * ng, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(cv_enum_timing(ctx, ev, n_launch));
+  // each fold's value of all groups and of the baseline alone, fold by fold
+  const uint64_t both[2] = {ng < 64 ? (1ull << ng) - 1ull : ~0ull, 0ull};
+  double u[2];
+  std::vector<double> uf((size_t)2 * K);
+  TRY(cv_group_values(ctx, L, both, 2, u, uf.data()));
+  std::copy(uf.begin(), uf.begin() + K, r2_fold);
+  std::copy(uf.begin() + K, uf.end(), base_fold);
+  return LSSPA_OK;
+}
+
+static_assert(((1ull << (GROUPS_MAX_G - 1)) / EXACT_UNITS) <= (1ull << (GROUPS_BEST_CLASSES - 1)),
+              "groups_cv_best_kernel holds the size classes of the largest per, as groups_best_kernel does");
+int cv_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t steps, double* u, uint32_t* masks,
+                   uint8_t* found, double* u_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_groups_best: steps must be >= 0");
+  GroupLayout L;
+  TRY(cv_layout(ctx, labels, g, L));
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(cv_groups_upload(ctx, L));
+  hipStream_t st = ctx->stream;
+  const int K = W.K, ng = L.ng;
+  const CvGroupsPlan P = cv_groups_best_plan(L, K, (uint64_t)steps);
+  const size_t rows = (size_t)P.units * (ng + 1);
+  TRY(dev_alloc(ctx, W.part, rows));
+  TRY(dev_alloc(ctx, W.out, (size_t)ng + 1));
+  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)ng + 1)));
+  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * rows, st));
+  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, st));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  GroupArgs a = cv_group_args(W, L, 0, W.info.ptr);
+  a.per = P.per;
+  a.part = W.part.ptr;
+  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
+    HIPCHK(hipEventRecord(ev[2 * l], st));
+    HIPCHK(launch_groups_cv_best(a, K, L.gid, P.units, s0, std::min(P.per, s0 + P.steps), W.best.ptr, st));
+    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+  }
+  uint32_t mf[2 * (GROUPS_MAX_G + 1)];
+  uint32_t* out_m = W.best.ptr + 2 * rows;
+  HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, (int64_t)P.units, ng, W.out.ptr, out_m, st));
+  HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * (ng + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (ng + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
+  uint64_t win[GROUPS_MAX_G + 1];
+  int at[GROUPS_MAX_G + 1], nw = 0;
+  for (int k = 0; k <= ng; ++k) {
+    found[k] = mf[2 * k + 1] ? 1 : 0;
+    masks[k] = found[k] ? mf[2 * k] : 0u;
+    if (!found[k]) u[k] = std::nan("");
+    for (int f = 0; f < K; ++f) u_fold[(size_t)k * K + f] = std::nan("");
+    if (found[k]) {
+      at[nw] = k;
+      win[nw++] = masks[k];
+    }
+  }
+  if (nw) {       // the winners' per-fold values, by the kernel's own fold-step
+    std::vector<double> wv((size_t)nw), wf((size_t)nw * K);
+    TRY(cv_group_values(ctx, L, win, nw, wv.data(), wf.data()));
+    for (int i = 0; i < nw; ++i) std::copy(&wf[(size_t)i * K], &wf[(size_t)i * K] + K, u_fold + (size_t)at[i] * K);
+  }
+  return LSSPA_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+int lsspa_cv_groups_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+                         const int32_t* fold_ids, int32_t K, double reg, int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  return cv_load(ctx, "lsspa_cv_groups_load", GROUPS_MAX_P, X, ld, y, N, p, fold_ids, K, reg, dtype, location);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* phi, double* phi_fold,
+                            double* r2_fold, double* base_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!labels || !phi || !phi_fold || !r2_fold || !base_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_groups_shapley: labels / phi / phi_fold / r2_fold / base_fold / info is NULL");
+  return cv_groups_shapley(ctx, labels, g, phi, phi_fold, r2_fold, base_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t steps, double* u, uint32_t* masks,
+                         uint8_t* found, double* u_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!labels || !u || !masks || !found || !u_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_groups_best: labels / u / masks / found / u_fold / info is NULL");
+  return cv_groups_best(ctx, labels, g, steps, u, masks, found, u_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const uint64_t* masks, int64_t n,
+                                double* u, double* u_fold) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!labels || n < 0 || (n > 0 && (!masks || !u))) return ctx->fail(LSSPA_ERR_ARG, "labels / masks / u NULL or n < 0");
+  GroupLayout L;
+  TRY(cv_layout(ctx, labels, g, L));
+  const uint64_t full = L.ng < 64 ? (1ull << L.ng) - 1ull : ~0ull;
+  for (int64_t i = 0; i < n; ++i)
+    if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a group beyond g");
+  if (n == 0) return LSSPA_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(cv_groups_upload(ctx, L));
+  return cv_group_values(ctx, L, masks, n, u, u_fold);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_groups_plan(const int32_t* labels, int32_t p, int32_t g, int32_t K, int64_t* plan) try {
+  GroupLayout L;
+  if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || K < 2 || K > CV_MAX_FOLDS || groups_layout(labels, p, g, L))
+    return LSSPA_ERR_ARG;
+  const CvGroupsPlan P = cv_groups_best_plan(L, K, 0);
+  const int64_t out[12] = {L.gl, L.gh, L.ql, L.nb, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps,
+                           (int64_t)P.launches, (int64_t)groups_cv_lds_bytes(), 256, (int64_t)groups_best_lds_bytes(),
+                           (int64_t)groups_per_launch(L)};
+  std::copy(out, out + 12, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
+}
+
 int lsspa_cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
                   const int32_t* fold_ids, int32_t K, double reg, int32_t dtype, int32_t location) try {
   if (!ctx) return LSSPA_ERR_ARG;
-  return cv_load(ctx, X, ld, y, N, p, fold_ids, K, reg, dtype, location);
+  return cv_load(ctx, "lsspa_cv_load", SUBSETS_MAX_P, X, ld, y, N, p, fold_ids, K, reg, dtype, location);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -5325,6 +5618,7 @@ int lsspa_cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int6
 int lsspa_cv_shapley(lsspa_ctx* ctx, double* phi, double* phi_fold, double* r2_fold, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(cv_need_loaded(ctx));
+  TRY(cv_need_columns(ctx, "lsspa_cv_shapley"));
   if (!phi || !phi_fold || !r2_fold || !info)
     return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_shapley: phi / phi_fold / r2_fold / info is NULL");
   return cv_shapley(ctx, phi, phi_fold, r2_fold, info);
@@ -5336,6 +5630,7 @@ int lsspa_cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, ui
                   double* v_fold, int32_t* info) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(cv_need_loaded(ctx));
+  TRY(cv_need_columns(ctx, "lsspa_cv_best"));
   if (!v || !masks || !found || !v_fold || !info)
     return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_best: v / masks / found / v_fold / info is NULL");
   return cv_best(ctx, include, steps, v, masks, found, v_fold, info);
@@ -5384,6 +5679,7 @@ int lsspa_cv_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double
 int lsspa_debug_cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v, double* v_fold) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(cv_need_loaded(ctx));
+  TRY(cv_need_columns(ctx, "lsspa_debug_cv_values"));
   if (n < 0 || (n > 0 && (!masks || !v))) return ctx->fail(LSSPA_ERR_ARG, "masks / v NULL or n < 0");
   const uint64_t full = (1ull << ctx->cv.p) - 1ull;     // p <= 32 here
   for (int64_t i = 0; i < n; ++i)

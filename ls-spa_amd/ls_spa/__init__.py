@@ -25,11 +25,12 @@ returning ``TopSubsetsResults``) and ``ls_spa_top_group_subsets`` (the same over
 p <= 64 columns: the n_best <= 16 best sets of groups of every size, returning ``TopGroupSubsetsResults``) and
 ``ls_spa_cv`` (the exact attribution of the K-fold cross-validated R^2 of one data set, p <= 32, returning
 ``CVResults``) and ``ls_spa_best_subsets_cv`` (best-subset selection by that cross-validated R^2, returning
-``CVBestSubsetsResults``; ``cv_fold_ids`` is the fold assignment of both)
+``CVBestSubsetsResults``; ``cv_fold_ids`` is the fold assignment of both; with ``groups=`` both work on g <= 32 groups
+of p <= 64 columns and return ``CVGroupResults`` and ``CVBestGroupSubsetsResults``)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
-from ._results import (CVBestSubsetsResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
                        TopGroupSubsetsResults, TopSubsetsResults, validate_data)
@@ -55,4 +56,5 @@ __all__ = [
     "ls_spa_top_subsets", "TopSubsetsResults",
     "ls_spa_top_group_subsets", "TopGroupSubsetsResults",
     "ls_spa_cv", "CVResults", "ls_spa_best_subsets_cv", "CVBestSubsetsResults", "cv_fold_ids",
+    "CVGroupResults", "CVBestGroupSubsetsResults",
 ]

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (CVBestSubsetsResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsResults, TopSubsetsResults, validate_data)
@@ -1370,15 +1370,20 @@ def cv_fold_ids(n, folds=5, *, seed=42, shuffle=True):
     return lab.astype(np.int32), K
 
 
-def _cv_data(name, X, y, folds, seed, shuffle):
-    """The checks every cross-validation call makes before it touches an engine: (X, y, fold_ids, K)."""
+def _cv_data(name, X, y, folds, seed, shuffle, grouped=False):
+    """The checks every cross-validation call makes before it touches an engine: (X, y, fold_ids, K).  grouped: the
+    column limit is that of ``ls_spa(groups=)``."""
     X, y = np.asarray(X), np.asarray(y)
     if X.ndim != 2 or y.ndim != 1:
         raise ValueError(f"{name}: X must be two-dimensional and y one-dimensional")
     if X.shape[0] != y.shape[0]:
         raise SizeIncompatible(f"X has {X.shape[0]} rows, y has {y.shape[0]}")
     n, p = X.shape
-    if p > SUBSETS_MAX_P:
+    if grouped:
+        if p > GROUPS_MAX_P:
+            raise ValueError(f"grouped attribution takes at most p = {GROUPS_MAX_P} columns, the baseline's included "
+                             f"(this problem has p = {p})")
+    elif p > SUBSETS_MAX_P:
         raise ValueError(f"{name} enumerates all 2^p feature subsets and takes at most p = {SUBSETS_MAX_P} features "
                          f"(this problem has p = {p})")
     if p < 1 or n < 2:
@@ -1413,7 +1418,70 @@ def _seq_sum(rows):
     return total
 
 
-def ls_spa_cv(X, y, reg=0., folds=5, *, seed=42, shuffle=True, device=0, _engine=None):
+def _cv_group_verdict(info, stacklevel):
+    """_cv_verdict for the grouped calls: the folds by name, sets of groups instead of subsets of features."""
+    bad = [int(f) for f in np.nonzero(np.asarray(info) & 1)[0]]
+    if bad:
+        warnings.warn(f"a Gram matrix of the training rows of fold(s) {', '.join(map(str, bad))} was not numerically "
+                      "positive definite; sets of groups with collinear columns are no candidates there and their "
+                      "attribution is not meaningful", RuntimeWarning, stacklevel=stacklevel + 1)
+
+
+def _cv_groups(X, y, reg, ids, K, labels, g, device, _engine):
+    """ls_spa_cv(groups=): the attribution of the cross-validated R^2 to the g groups (cv_groups_shapley)."""
+    with _engine_call(_engine, device) as engine:
+        engine.cv_groups_load(X, y, ids, K, reg)
+        try:
+            phi, phi_fold, r2_fold, base_fold, info = engine.cv_groups_shapley(labels)
+        finally:
+            engine.cv_free()
+    _cv_group_verdict(info, stacklevel=3)
+    G, gv = _cv_full_problem(X, y, reg)
+    return CVGroupResults(attribution=phi, fold_attribution=phi_fold, r_squared=float(_seq_sum(list(r2_fold))),
+                          fold_r_squared=np.asarray(r2_fold), baseline_r_squared=float(_seq_sum(list(base_fold))),
+                          fold_baseline_r_squared=np.asarray(base_fold),
+                          theta=_subset_fit(G, gv, np.arange(X.shape[1])), fold_ids=ids)
+
+
+def _cv_best_group_subsets(X, y, reg, ids, K, labels, g, device, _engine):
+    """ls_spa_best_subsets_cv(groups=): the best set of groups of every size 0 .. g by the cross-validated value
+    (cv_groups_best), each winner refitted on all rows on the host on the baseline's and its groups' columns."""
+    p = X.shape[1]
+    with _engine_call(_engine, device) as engine:
+        engine.cv_groups_load(X, y, ids, K, reg)
+        try:
+            u, masks, found, u_fold, info = engine.cv_groups_best(labels)
+            full, _ = engine.debug_cv_group_values(labels, np.array([(1 << g) - 1], dtype=np.uint64), folds=False)
+        finally:
+            engine.cv_free()
+    _cv_group_verdict(info, stacklevel=3)
+    G, gv = _cv_full_problem(X, y, reg)
+    sizes = np.arange(g + 1)
+    group_subsets = np.zeros((g + 1, g), dtype=bool)
+    subsets = np.zeros((g + 1, p), dtype=bool)
+    r_squared = np.full(g + 1, np.nan)
+    fold_r_squared = np.full((g + 1, K), np.nan)
+    theta = np.full((g + 1, p), np.nan)
+    for k in sizes:
+        if found[k]:
+            group_subsets[k] = (int(masks[k]) >> np.arange(g)) & 1
+            subsets[k] = (labels < 0) | group_subsets[k][np.maximum(labels, 0)]
+            r_squared[k] = u[k]
+            fold_r_squared[k] = u_fold[k]
+            theta[k] = _subset_fit(G, gv, np.nonzero(subsets[k])[0])
+    best_size, best_groups, best_subset = -1, np.zeros(g, dtype=bool), np.zeros(p, dtype=bool)
+    if not np.all(np.isnan(r_squared)):
+        best_size = int(np.nanargmax(r_squared))      # the first of equal maxima: the smallest size
+        best_groups, best_subset = group_subsets[best_size].copy(), subsets[best_size].copy()
+    return CVBestGroupSubsetsResults(sizes=sizes, group_subsets=group_subsets, subsets=subsets,
+                                     n_columns=subsets.sum(axis=1), r_squared=r_squared,
+                                     fold_r_squared=fold_r_squared, theta=theta, best_size=best_size,
+                                     best_group_subset=best_groups, best_subset=best_subset,
+                                     full_r_squared=float(full[0]), baseline_r_squared=float(r_squared[0]),
+                                     fold_ids=ids)
+
+
+def ls_spa_cv(X, y, reg=0., folds=5, *, groups=None, seed=42, shuffle=True, device=0, _engine=None):
     """Exact Shapley attribution of the K-fold cross-validated out-of-sample R^2 (p <= 32): one data set, no split to
     choose.
 
@@ -1432,7 +1500,20 @@ def ls_spa_cv(X, y, reg=0., folds=5, *, seed=42, shuffle=True, device=0, _engine
 
     Shapes that do not fit, p > 32, K outside 2 .. 32, a label outside 0 .. K-1, an empty fold and a y that is
     identically zero are refused before any GPU work.  A fold whose training rows give a Gram matrix that is not
-    numerically positive definite raises a RuntimeWarning that names the fold."""
+    numerically positive definite raises a RuntimeWarning that names the fold.
+
+    groups:  a length-p sequence of integer labels, one per column, as for ``ls_spa(method='subsets', groups=)``: k in
+        0 .. g-1 puts the column into group k, -1 into the always-included baseline (an intercept, controls).  The
+        players are then the g groups -- a one-hot factor or a spline basis is attributed as one variable --, the cost
+        is set by g, not by p, and the limits are g <= 32 groups over p <= 64 columns (include/lsspa.h,
+        lsspa_cv_groups_shapley); the label errors are that call's.  Returns ``CVGroupResults``: ``attribution`` [g],
+        ``fold_attribution`` [K][g], ``r_squared``, ``fold_r_squared`` [K], ``baseline_r_squared`` (the cross-validated
+        R^2 of the baseline's columns alone; ``attribution`` sums to ``r_squared - baseline_r_squared``),
+        ``fold_baseline_r_squared`` [K], ``theta`` [p] and ``fold_ids``."""
+    if groups is not None:
+        X, y, ids, K = _cv_data("ls_spa_cv", X, y, folds, seed, shuffle, grouped=True)
+        labels, n_groups = group_labels(groups, X.shape[1])
+        return _cv_groups(X, y, reg, ids, K, labels, n_groups, device, _engine)
     X, y, ids, K = _cv_data("ls_spa_cv", X, y, folds, seed, shuffle)
     with _engine_call(_engine, device) as engine:
         engine.cv_load(X, y, ids, K, reg)
@@ -1446,7 +1527,8 @@ def ls_spa_cv(X, y, reg=0., folds=5, *, seed=42, shuffle=True, device=0, _engine
                      fold_r_squared=np.asarray(r2_fold), theta=_subset_fit(G, g, np.arange(X.shape[1])), fold_ids=ids)
 
 
-def ls_spa_best_subsets_cv(X, y, reg=0., folds=5, *, include=None, seed=42, shuffle=True, device=0, _engine=None):
+def ls_spa_best_subsets_cv(X, y, reg=0., folds=5, *, include=None, groups=None, seed=42, shuffle=True, device=0,
+                           _engine=None):
     """Exhaustive best-subset selection by the K-fold cross-validated R^2: the best model of every size over all 2^p
     feature subsets (p <= 32), judged not by one split but by all K.
 
@@ -1467,7 +1549,21 @@ def ls_spa_best_subsets_cv(X, y, reg=0., folds=5, *, include=None, seed=42, shuf
 
     The refusals of ``ls_spa_cv`` and those of ``include`` come before any GPU work.  A subset with a pivot that failed
     in any fold is no candidate and raises a RuntimeWarning that names the folds; a size without a candidate is a NaN
-    row."""
+    row.
+
+    groups:  labels as for ``ls_spa_cv(groups=)``.  The models are then the 2^g sets of groups, each with the baseline's
+        columns, a model's size is its number of groups, 0 .. g (size 0 is the baseline alone), and on equal values the
+        set with the smaller mask (bit k = group k) wins (include/lsspa.h, lsspa_cv_groups_best; g <= 32, p <= 64).
+        ``include=`` cannot be combined with it: label those columns -1.  Returns ``CVBestGroupSubsetsResults``: the
+        fields of ``BestGroupSubsetsResults`` with the cross-validated value, and ``fold_r_squared`` [g + 1][K] and
+        ``fold_ids``."""
+    if groups is not None:
+        if include is not None:
+            raise ValueError("include= cannot be combined with groups=: label the columns every model must contain "
+                             "-1, the baseline is the include set")
+        X, y, ids, K = _cv_data("ls_spa_best_subsets_cv", X, y, folds, seed, shuffle, grouped=True)
+        labels, n_groups = group_labels(groups, X.shape[1])
+        return _cv_best_group_subsets(X, y, reg, ids, K, labels, n_groups, device, _engine)
     X, y, ids, K = _cv_data("ls_spa_best_subsets_cv", X, y, folds, seed, shuffle)
     p = X.shape[1]
     mask, inc = include_mask(include, p)

@@ -229,6 +229,23 @@ def debug_cv_plan(p: int, folds: int):
     return dict(zip(CV_PLAN_FIELDS, (int(v) for v in out)))
 
 
+CV_GROUPS_PLAN_FIELDS = ("gl", "gh", "ql", "nb", "units", "per", "steps", "launches", "lds_bytes", "workgroup",
+                         "lds_bytes_one_problem", "launch_bound")
+
+
+def debug_cv_groups_plan(labels, folds: int):
+    """Test hook, host only: how cv_groups_best enumerates the group game of these labels over `folds` fold problems
+    (include/lsspa.h, lsspa_debug_cv_groups_plan) -- a dict with CV_GROUPS_PLAN_FIELDS.  ValueError for labels or a
+    number of folds the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(12, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_groups_plan(N.iptr(labels), len(labels), g, int(folds), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_groups_plan: status {rc}")
+    return dict(zip(CV_GROUPS_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -736,6 +753,67 @@ class HipEngine:
         return v, v_fold
 
     debug_cv_plan = staticmethod(debug_cv_plan)
+
+    # ---- ... over groups of columns (g <= 32 groups of p <= 64 columns) ----
+    def cv_groups_load(self, X, y, fold_ids, K: int, reg: float):
+        """cv_load with the limit p <= 64 (include/lsspa.h, lsspa_cv_groups_load): the same store, either load replaces
+        the other; after p <= 32 both families of calls work."""
+        dt = np.float32 if X.dtype == np.float32 else np.float64
+        Xa, ya = np.ascontiguousarray(X, dtype=dt), np.ascontiguousarray(y, dtype=dt)
+        n, p = Xa.shape
+        fid = np.ascontiguousarray(fold_ids, dtype=np.int32)
+        if fid.shape != (int(n),):
+            raise ValueError(f"fold_ids must have shape ({int(n)},), got {fid.shape}")
+        self._check(self._lib.lsspa_cv_groups_load(
+            self._h, C.c_void_p(Xa.ctypes.data), int(p), C.c_void_p(ya.ctypes.data), int(n), int(p), N.iptr(fid), int(K),
+            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._cv_dims = (int(p), int(K), int(n))
+
+    def _cv_labels(self, labels):
+        labels, g = self._labels(labels)
+        p, K = self._cv_pk()
+        if len(labels) != p:
+            raise ValueError(f"labels must have length p = {p}")
+        return labels, g, K
+
+    def cv_groups_shapley(self, labels):
+        """(phi [g], phi_fold [K][g], r2_fold [K], base_fold [K], info [K]): the attribution of the cross-validated R^2
+        to the groups of `labels`, the folds' attributions it is the sum of, each fold's value of all groups and of the
+        baseline alone, and the folds' info words (include/lsspa.h, lsspa_cv_groups_shapley)."""
+        labels, g, K = self._cv_labels(labels)
+        n = max(g, 1)
+        phi, fold, r2, base = np.empty(n), np.empty((K, n)), np.empty(K), np.empty(K)
+        info = np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_groups_shapley(self._h, N.iptr(labels), g, N.dptr(phi), N.dptr(fold), N.dptr(r2),
+                                                      N.dptr(base), N.iptr(info)))
+        return phi, fold, r2, base, info
+
+    def cv_groups_best(self, labels, steps: int = 0):
+        """(u [g + 1], masks [g + 1] uint32 (bit k = group k), found [g + 1] bool, u_fold [g + 1][K], info [K]): the best
+        set of groups of every size 0 .. g by the cross-validated value (include/lsspa.h, lsspa_cv_groups_best).
+        steps > 0: that many steps of a unit per launch (test hook; the result does not depend on it)."""
+        labels, g, K = self._cv_labels(labels)
+        n = max(g, 0) + 1
+        u, masks, found = np.empty(n), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)
+        u_fold, info = np.empty((n, K)), np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_groups_best(
+            self._h, N.iptr(labels), g, int(steps), N.dptr(u), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            found.ctypes.data_as(C.POINTER(C.c_uint8)), N.dptr(u_fold), N.iptr(info)))
+        return u, masks, found.astype(bool), u_fold, info
+
+    def debug_cv_group_values(self, labels, masks, folds: bool = True):
+        """Test hook: (u [n], u_fold [n][K] or None) of the sets of groups `masks` (bit k = group k) by cv_groups_best's
+        own device code (include/lsspa.h, lsspa_debug_cv_group_values)."""
+        labels, g, K = self._cv_labels(labels)
+        masks = np.ascontiguousarray(masks, dtype=np.uint64)
+        u = np.empty(len(masks))
+        u_fold = np.empty((len(masks), K)) if folds else None
+        self._check(self._lib.lsspa_debug_cv_group_values(
+            self._h, N.iptr(labels), g, masks.ctypes.data_as(C.POINTER(C.c_uint64)), len(masks), N.dptr(u),
+            N.dptr(u_fold)))
+        return u, u_fold
+
+    debug_cv_groups_plan = staticmethod(debug_cv_groups_plan)
 
     # ---- exact attribution of many responses at once (p <= 32; over groups g <= 32, p <= 64) ----
     MULTI_RB = 8      # responses a wave carries per pass (csrc/kernels.h)

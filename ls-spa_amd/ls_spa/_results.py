@@ -898,3 +898,76 @@ class CVBestSubsetsResults:
             pad,
         ]
         return "\n".join(lines)
+
+
+@dataclass
+class CVGroupResults:
+    """What ``ls_spa_cv(groups=)`` returns for g groups of p columns, K folds and N rows.  ``attribution`` [g]: the exact
+    Shapley attribution of the K-fold cross-validated R^2 to the groups; ``fold_attribution`` [K][g]: the folds'
+    attributions, whose sum over the folds in ascending order it is; ``r_squared``: the cross-validated R^2 of the full
+    model; ``fold_r_squared`` [K]: each fold's share of it; ``baseline_r_squared``: the cross-validated R^2 of the
+    baseline's columns alone (label -1; 0.0 without a baseline) and ``fold_baseline_r_squared`` [K] its shares --
+    ``attribution`` sums to ``r_squared - baseline_r_squared``; ``theta`` [p]: the coefficients fitted on all rows;
+    ``fold_ids`` [N]: the fold of every row."""
+    attribution: np.ndarray
+    fold_attribution: np.ndarray
+    r_squared: float
+    fold_r_squared: np.ndarray
+    baseline_r_squared: float
+    fold_baseline_r_squared: np.ndarray
+    theta: np.ndarray
+    fold_ids: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}g = {len(self.attribution)} groups of p = {len(self.theta)} columns, "
+            f"{len(self.fold_r_squared)}-fold cross-validation",
+            f"{pad}Cross-validated R^2: {self.r_squared:.2e} (baseline alone: {self.baseline_r_squared:.2e})",
+            f"{pad}Attribution: ({_head(self.attribution)})",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
+class CVBestGroupSubsetsResults:
+    """What ``ls_spa_best_subsets_cv(groups=)`` returns for g groups of p columns and K folds: the fields of
+    ``BestGroupSubsetsResults`` with the K-fold cross-validated R^2 as the value.  ``sizes``: 0 .. g (size 0 is the
+    baseline alone); ``group_subsets`` [g + 1][g] bool; ``subsets`` [g + 1][p] bool (the baseline's and the winners'
+    columns); ``n_columns`` [g + 1]; ``r_squared`` [g + 1]: the winner's cross-validated value; ``fold_r_squared``
+    [g + 1][K]: its per-fold values, whose sum in ascending fold order it is; ``theta`` [g + 1][p]: the winner refitted
+    on ALL rows, exactly 0.0 outside its columns; ``full_r_squared``: the cross-validated R^2 of all groups;
+    ``baseline_r_squared``: ``r_squared[0]``; ``fold_ids`` [N].  A size without a candidate is a row of NaN / False;
+    ``best_size`` is the smallest size on ties, NaN rows skipped (-1 if every size is NaN)."""
+    sizes: np.ndarray
+    group_subsets: np.ndarray
+    subsets: np.ndarray
+    n_columns: np.ndarray
+    r_squared: np.ndarray
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    best_size: int
+    best_group_subset: np.ndarray
+    best_subset: np.ndarray
+    full_r_squared: float
+    baseline_r_squared: float
+    fold_ids: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        g, p = np.asarray(self.group_subsets).shape[1], np.asarray(self.subsets).shape[1]
+        chosen = ", ".join(str(j) for j in np.nonzero(self.best_group_subset)[0][:12])
+        best = f"{float(self.r_squared[self.best_size]):.2e}" if self.best_size >= 0 else "nan"
+        lines = [
+            "",
+            f"{pad}g = {g} groups of p = {p} columns, {np.asarray(self.fold_r_squared).shape[1]}-fold cross-validation, "
+            f"best sets of groups of sizes 0 .. {g}",
+            f"{pad}Cross-validated R^2 with all groups: {self.full_r_squared:.2e} (baseline alone: "
+            f"{self.baseline_r_squared:.2e})",
+            f"{pad}Best model: {self.best_size} groups, cross-validated R^2 {best}",
+            f"{pad}Its groups: ({chosen}{', ...' if int(np.sum(self.best_group_subset)) > 12 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)
