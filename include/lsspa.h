@@ -459,6 +459,14 @@ int lsspa_debug_boot_groups_best_plan(int64_t R, int64_t N, int64_t M, const int
  *                     bits of lsspa_debug_cv_values for masks[k].  v_fold [p+1][K]: the winner's per-fold values (NaN
  *                     where found[k] = 0).  steps = 0: the plan's steps of a unit per launch; > 0: that many (a test's
  *                     way to cut a small p into several launches).  No floating-point atomics: two calls agree bitwise.
+ *   lsspa_cv_top    : lsspa_subsets_top by v_cv: per size k the T best subsets (1 <= T <= 16), best first, in
+ *                     lsspa_cv_best's order and over its candidates, whose sum is also above -inf (so never NaN).  v
+ *                     [p+1][T], masks [p+1][T], count [p+1] = min(T, candidates of size k); NaN / 0 past count[k].
+ *                     Masks are unique, so the lists depend on no cut; rank 0 is lsspa_cv_best's winner and the list
+ *                     for T is a prefix of the list for T' > T.  v[k][r] has the bits of lsspa_debug_cv_values for
+ *                     masks[k][r]; v_fold [p+1][T][K]: the listed models' per-fold values by that same device code
+ *                     (NaN past count[k]).  include, steps, info [K] as in lsspa_cv_best.  LSSPA_ERR_ARG: include
+ *                     beyond p, T outside 1 .. 16, steps < 0.  Two calls agree bitwise.
  *   lsspa_cv_timing : kernel ms of the load's Gram side (weights, Gram, sums, finalise), of the last enumeration's
  *                     launches, its longest launch and their number (any pointer may be NULL)
  *   lsspa_cv_get_problem   : test hook -- fold problem f as the device computed it (G, H [p][p], g, h [p], the pooled
@@ -468,20 +476,29 @@ int lsspa_debug_boot_groups_best_plan(int64_t R, int64_t N, int64_t M, const int
  *   lsspa_debug_cv_plan    : host only, no context, no GPU -- lsspa_cv_best's units, high subsets per unit, steps of a
  *                     unit per launch (each K fold evaluations: 2^20 / (units K), at least 1), launches, LDS bytes of
  *                     a workgroup, its threads, 0, 0.  p outside 1 .. 32 or K outside 2 .. 32 is LSSPA_ERR_ARG.
- * LSSPA_ERR_STATE before a load.  Groups of columns: the next block.  Top lists, interactions and a bootstrap over the
- * folds are not built. */
+ *   lsspa_debug_cv_top_plan: host only, no context, no GPU -- lsspa_cv_top's units, high subsets per unit, steps of a
+ *                     unit per launch and launches (lsspa_debug_cv_plan's), LDS bytes of a workgroup at this T (the
+ *                     static part and 20 lists of 12 T + 4 bytes), its threads, the sizes one unit can meet and the
+ *                     bytes of the table (units (p + 1) (12 T + 4), lsspa_debug_subsets_top_plan's).  p outside
+ *                     1 .. 32, K outside 2 .. 32 or T outside 1 .. 16 is LSSPA_ERR_ARG.
+ * LSSPA_ERR_STATE before a load.  Groups of columns: the next block.  Interactions and a bootstrap over the folds are
+ * not built. */
 int lsspa_cv_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
                   const int32_t* fold_ids /* [N], host */, int32_t K, double reg, int32_t dtype, int32_t location);
 int lsspa_cv_shapley(lsspa_ctx* ctx, double* phi /* [p] */, double* phi_fold /* [K][p] */, double* r2_fold /* [K] */,
                      int32_t* info /* [K] */);
 int lsspa_cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v /* [p+1] */, uint32_t* masks /* [p+1] */,
                   uint8_t* found /* [p+1] */, double* v_fold /* [p+1][K] */, int32_t* info /* [K] */);
+int lsspa_cv_top(lsspa_ctx* ctx, uint32_t include, int32_t T, int64_t steps, double* v /* [p+1][T] */,
+                 uint32_t* masks /* [p+1][T] */, int32_t* count /* [p+1] */, double* v_fold /* [p+1][T][K] */,
+                 int32_t* info /* [K] */);
 int lsspa_cv_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms, int64_t* launches);
 int lsspa_cv_free(lsspa_ctx* ctx);
 int lsspa_cv_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double* H, double* h, double* inv_yy);
 int lsspa_debug_cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v /* [n] */,
                           double* v_fold /* [n][K] or NULL */);
 int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan /* [8] */);
+int lsspa_debug_cv_top_plan(int32_t p, int32_t K, int32_t T, int64_t* plan /* [8] */);
 
 /* K-FOLD CROSS-VALIDATION OVER GROUPS OF COLUMNS (g <= 32 groups of p <= 64 columns, 2 <= K <= 32, fp64): the players
  * are the groups of `labels` (-1: the baseline, in every model; 0 .. g-1: the group), as in lsspa_groups_shapley, and

@@ -46,7 +46,8 @@
 // dimension, like the enumeration kernel's.
 //
 // K-fold cross-validation (lsspa_cv_best, subsets_cv_best_kernel below): that kernel's sibling, which evaluates every
-// high subset on the K fold problems of k_cv.hip in one step and keeps the best SUM of their values per size.
+// high subset on the K fold problems of k_cv.hip in one step and keeps the best SUM of their values per size;
+// lsspa_cv_top, subsets_cv_top_kernel: the same fold-step with subsets_top_kernel's lists, the T best sums per size.
 #include "kernels.h"
 
 namespace lsspa {
@@ -872,6 +873,111 @@ __global__ __launch_bounds__(64, 2) void subsets_cv_debug_kernel(SubsetArgs a, i
     if (__any((bad_folds >> f) & 1u) && lane == 0) atomicOr(a.info + f, 1);
 }
 
+// ---- the T best subsets of every size by the K-fold cross-validated value (lsspa_cv_top) ----
+// The product of the two kernels above it: subsets_cv_best_kernel's fold-step (the same units, steps and launches, fold_args /
+// load_fold / subset_values<false> per fold, v = v_0 + v_1 + ... in fold order, so every v_f and every sum has the bits
+// subsets_cv_debug_kernel gives for that mask; the same candidates -- valid lane, `include`, own pivots passed in EVERY
+// fold -- and the same info words) and subsets_top_kernel's lists (STS sizes a unit, T entries and a count each, in
+// dynamic LDS beside the one SubShared; loaded from the unit's rows of the table at the start of a launch and stored
+// back at its end; wanted(), the ballot and the rank-and-shift insert as there; top_before's strict order, so the
+// lists depend on no cut of the work).  The table is subsets_top_kernel's and subsets_top_reduce_kernel merges it.
+// A candidate's sum must also be above -inf, so it is never NaN.
+// The lists stay in LDS over the fold loop, which restages H, h and the pivot scale into SubShared F times a step and
+// touches nothing else of the workgroup's LDS; one list check a step stands against F sweeps.  Barriers: every
+// fold-step ends in one, so the lists' first reader (wanted(), after the folds) is behind the loads above the loop,
+// and every insert ends in one as in subsets_top_kernel; the step needs no barrier of its own behind the inserts,
+// because what follows (load_fold) writes SubShared only and the next reader of the lists is F barriers away.
+__global__ __launch_bounds__(64, 2) void subsets_cv_top_kernel(SubsetArgs a, int F, uint64_t s0, uint64_t s1,
+                                                            uint32_t include, int T, uint32_t* __restrict__ tm,
+                                                            int32_t* __restrict__ tc) {
+  __shared__ SubShared sh;
+  extern __shared__ double top_lds[];
+  double* lv = top_lds;
+  uint32_t* lm = reinterpret_cast<uint32_t*>(lv + STS * T);
+  int* lc = reinterpret_cast<int*>(lm + STS * T);
+  const int lane = threadIdx.x;
+  const int p = a.p, q = a.q;
+  for (int e = lane; e < (SQ + 1) * ZC; e += 64) sh.Z[e] = 0.0;   // rows / columns beyond q stay 0
+  // the sizes this unit can hold: k0 + j, j < ns (popc(s) + popc(T) with s < per, T < 2^q, and no more than p)
+  const int k0 = __popc(blockIdx.x);
+  const int ns = min(p - k0, __popcll(a.per - 1) + q) + 1;
+  double* gv = a.part + ((int64_t)blockIdx.x * (p + 1) + k0) * T;
+  uint32_t* gm = tm + ((int64_t)blockIdx.x * (p + 1) + k0) * T;
+  int32_t* gc = tc + (int64_t)blockIdx.x * (p + 1) + k0;
+  for (int e = lane; e < ns * T; e += 64) {
+    const int j = e / T;
+    if (e - j * T < gc[j]) {
+      lv[e] = gv[e];
+      lm[e] = gm[e];
+    }
+  }
+  if (lane < ns) lc[lane] = gc[lane];
+  const uint32_t inc_lo = include & ((1u << q) - 1u), inc_hi = include >> q;     // q >= 1
+  const bool lane_ok = lane < (1 << q) && ((uint32_t)lane & inc_lo) == inc_lo;
+  const int jl = lane_ok ? __popc(lane) : 0;
+  uint32_t bad_folds = 0u;                    // bit f: a pivot of fold f failed in a subset this lane saw
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    double v = 0.0;
+    bool bad_any = false;                     // this subset's own pivots, over the folds
+#pragma unroll 1
+    for (int f = 0; f < F; ++f) {
+      const SubsetArgs af = fold_args(a, f);
+      load_fold(sh, af, lane);
+      bool bad = false;
+      const double vf = subset_values<false>(sh, af, hi, lane, bad);
+      v = f == 0 ? vf : v + vf;
+      bad_any |= bad;
+      bad_folds |= bad ? (1u << f) : 0u;
+      __syncthreads();
+    }
+    const uint32_t h32 = (uint32_t)hi;
+    const uint32_t m = (h32 << q) | (uint32_t)lane;
+    const int j = __popcll(s) + jl;           // < ns for every lane that can be a candidate
+    // a candidate that belongs into its size's list as it is now: the list is not full, or its last entry comes later
+    auto wanted = [&]() {
+      const int c = lc[j];
+      return c < T || top_before(v, m, lv[j * T + T - 1], lm[j * T + T - 1]);
+    };
+    bool want = lane_ok && !bad_any && (h32 & inc_hi) == inc_hi && v > -__builtin_huge_val() && wanted();
+    for (uint64_t todo = __ballot(want); todo != 0ull; todo = __ballot(want)) {
+      const int src = __ffsll((unsigned long long)todo) - 1;
+      const double nv = __shfl(v, src, 64);
+      const uint32_t nm = (uint32_t)__shfl((int)m, src, 64);
+      const int nj = __shfl(j, src, 64);
+      double* rv = lv + nj * T;
+      uint32_t* rm = lm + nj * T;
+      const int c = lc[nj];
+      const bool have = lane < c;             // c <= T <= 16: lane t holds entry t
+      const double ev = have ? rv[lane] : 0.0;
+      const uint32_t em = have ? rm[lane] : 0u;
+      const int rank = __popcll(__ballot(have && top_before(ev, em, nv, nm)));
+      const double pv = __shfl_up(ev, 1, 64);
+      const uint32_t pm = (uint32_t)__shfl_up((int)em, 1, 64);
+      const int nc = min(c + 1, T);
+      if (lane >= rank && lane < nc) {        // a lane writes the entry it read: no other lane's
+        rv[lane] = lane == rank ? nv : pv;
+        rm[lane] = lane == rank ? nm : pm;
+      }
+      if (lane == 0) lc[nj] = nc;
+      __syncthreads();
+      if (lane == src) want = false;
+      want = want && wanted();
+    }
+  }
+  // (every write of the lists is behind a barrier: the loads' the fold-steps', an insert's its own)
+  for (int e = lane; e < ns * T; e += 64) {
+    const int j = e / T;
+    if (e - j * T < lc[j]) {
+      gv[e] = lv[e];
+      gm[e] = lm[e];
+    }
+  }
+  if (lane < ns) gc[lane] = lc[lane];
+  for (int f = 0; f < F; ++f)
+    if (__any((bad_folds >> f) & 1u) && lane == 0) atomicOr(a.info + f, 1);
+}
+
 // H = Ft Ft^T [p][p] (stride p) and h = Ft ytil (appended) of the rect-mode test factor: one workgroup per entry, its
 // 256 threads strided over the m columns, then a fixed tree (the same sums on every call; m may be up to 2^20 through
 // lsspa_set_reduced).  Entries (i, j) and (j, i) both form the product of rows min(i, j) and max(i, j) in the same
@@ -1004,6 +1110,24 @@ hipError_t launch_subsets_cv_best(const SubsetArgs& a, int folds, uint64_t units
   if (a.per > (1ull << (SBS - 1))) return hipErrorInvalidValue;
   if (a.p < 32 && (include >> a.p) != 0u) return hipErrorInvalidValue;
   hipLaunchKernelGGL(subsets_cv_best_kernel, dim3((unsigned)units), dim3(64), 0, st, a, folds, s0, s1, include, bm);
+  return hipGetLastError();
+}
+
+size_t subsets_cv_top_lds_bytes(int T) { return sizeof(SubShared) + top_lds_bytes(T); }
+
+hipError_t launch_subsets_cv_top(const SubsetArgs& a, int folds, uint64_t units, uint64_t s0, uint64_t s1,
+                                 uint32_t include, int T, uint32_t* tm, int32_t* tc, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !tm || !tc || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  if (T < 1 || T > SUBSETS_TOP_MAX) return hipErrorInvalidValue;
+  // the caller vouches for `folds` problems and info words behind the first, as launch_subsets_cv_best's does
+  if (folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  const int nh = a.p - a.q;
+  if (units * a.per != (1ull << nh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  // the sizes of a unit are popc(s) + popc(lane), s < per: per a power of two of at most SBS - 1 bits, STS lists
+  if (a.per > (1ull << (SBS - 1))) return hipErrorInvalidValue;
+  if (a.p < 32 && (include >> a.p) != 0u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(subsets_cv_top_kernel, dim3((unsigned)units), dim3(64), top_lds_bytes(T), st, a, folds, s0, s1,
+                     include, T, tm, tc);
   return hipGetLastError();
 }
 

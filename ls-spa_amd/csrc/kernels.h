@@ -387,6 +387,12 @@ hipError_t launch_subsets_cv_best(const SubsetArgs& a, int folds, uint64_t units
 hipError_t launch_subsets_cv_debug(const SubsetArgs& a, int folds, const uint64_t* masks, int64_t n, double* vals,
                                    double* vfold, hipStream_t st);
 size_t subsets_cv_lds_bytes();     // static LDS of a workgroup of launch_subsets_cv_best
+// launch_subsets_cv_top: launch_subsets_cv_best's units, steps, launches, fold-step, candidates (whose sum is also above
+// -inf) and info words with launch_subsets_top's lists, order and tables: a.part [units][p + 1][T], tm [units][p + 1][T],
+// tc [units][p + 1], tc zeroed before the first launch; launch_subsets_top_reduce merges the units' lists.
+hipError_t launch_subsets_cv_top(const SubsetArgs& a, int folds, uint64_t units, uint64_t s0, uint64_t s1,
+                                 uint32_t include, int T, uint32_t* tm, int32_t* tc, hipStream_t st);
+size_t subsets_cv_top_lds_bytes(int T);   // LDS of a workgroup of launch_subsets_cv_top: static and the lists at this T
 // wt[f][i] = 1.0 if fid[i] == f else 0.0, f < folds, i < n: the folds' indicator weights for launch_boot_gram
 hipError_t launch_cv_weights(const int32_t* fid, int64_t n, int folds, double* wt, hipStream_t st);
 // The fold problems from the per-fold Grams S [folds][c][c] (c = p + 1) and the folds' sizes nf [folds] of n rows:

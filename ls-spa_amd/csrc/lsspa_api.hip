@@ -113,7 +113,8 @@ struct CvWork {
   DevBuf<int32_t> tab;                     // and their layout table (GroupLayout::tab)
   DevBuf<uint64_t> masks;
   DevBuf<int32_t> info, dinfo;             // [K] info words of a call; the debug values' own
-  DevBuf<uint32_t> best;                   // lsspa_cv_best: (mask, found) of the units' rows, then of the result
+  DevBuf<uint32_t> best;                   // lsspa_cv_best: (mask, found) of the units' rows, then of the result;
+                                           // lsspa_cv_top: the lists' masks and counts, then the result's
   double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
@@ -5320,6 +5321,79 @@ int cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, uint32_t
   return LSSPA_OK;
 }
 
+// lsspa_cv_top: cv_best's cut into launches (cv_best_plan) and lifecycle with subsets_top's table, which depends on p
+// and T alone: values in W.part [units][p + 1][T], in W.best the masks [units][p + 1][T], the counts [units][p + 1] and
+// behind them the result's masks [p + 1][T] and counts [p + 1].  What the call and its plan hook both go by:
+struct CvTopPlan {
+  CvPlan cut;
+  TopPlan table;             // sizes, rows and bytes; its steps and launches are the one-problem call's, not this one's
+};
+CvTopPlan cv_top_plan(int p, int K, int T, uint64_t forced) { return {cv_best_plan(p, K, forced), subsets_top_plan(p, T)}; }
+
+int cv_top(lsspa_ctx* ctx, uint32_t include, int T, int64_t steps, double* v, uint32_t* masks, int32_t* count,
+           double* v_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  const int p = W.p, K = W.K;
+  if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
+  if (T < 1 || T > SUBSETS_TOP_MAX) {
+    char msg[120];
+    snprintf(msg, sizeof msg, "lsspa_cv_top keeps 1 .. %d subsets of every size (T = %d)", SUBSETS_TOP_MAX, T);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_top: steps must be >= 0");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const CvTopPlan CP = cv_top_plan(p, K, T, (uint64_t)steps);
+  const CvPlan& P = CP.cut;
+  const size_t rows = CP.table.rows, n_out = (size_t)(p + 1) * T;
+  TRY(dev_alloc(ctx, W.part, rows * T));
+  TRY(dev_alloc(ctx, W.out, std::max(n_out, (size_t)K * (p + 1))));
+  TRY(dev_alloc(ctx, W.best, rows * T + rows + n_out + (size_t)p + 1));
+  uint32_t* tm = W.best.ptr;
+  int32_t* tc = reinterpret_cast<int32_t*>(tm + rows * T);
+  uint32_t* out_m = tm + rows * T + rows;
+  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
+  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * rows, st));      // the counts; no entry is read beyond one
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  SubsetArgs a = cv_subset_args(W, 0, W.info.ptr);
+  a.per = P.per;
+  a.part = W.part.ptr;
+  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
+    HIPCHK(hipEventRecord(ev[2 * l], st));
+    HIPCHK(launch_subsets_cv_top(a, K, P.units, s0, std::min(P.per, s0 + P.steps), include, T, tm, tc, st));
+    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+  }
+  HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, (int64_t)P.units, p, T, W.out.ptr, out_m, out_c, st));
+  HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (p + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
+  std::vector<uint64_t> listed;
+  std::vector<size_t> at;
+  for (int k = 0; k <= p; ++k)
+    for (int r = 0; r < T; ++r) {
+      const size_t e = (size_t)k * T + r;
+      for (int f = 0; f < K; ++f) v_fold[e * K + f] = std::nan("");
+      if (r < count[k]) {
+        at.push_back(e);
+        listed.push_back(masks[e]);
+      }
+    }
+  if (!listed.empty()) {      // the listed models' per-fold values, by the kernel's own fold-step
+    const size_t nl = listed.size();
+    std::vector<double> lv(nl), lf(nl * K);
+    TRY(cv_values(ctx, listed.data(), (int64_t)nl, lv.data(), lf.data()));
+    for (size_t i = 0; i < nl; ++i) std::copy(&lf[i * K], &lf[i * K] + K, v_fold + at[i] * K);
+  }
+  return LSSPA_OK;
+}
+
 // ---- ... over groups of columns (lsspa_cv_groups_*; the CV kernels of k_groups.hip) ----
 // The fold problems are the same store; the players are the g groups of the labels, the baseline (label -1) is in every
 // model.  lsspa_cv_groups_shapley runs the REPS enumeration of k_groups.hip over the folds, cut as lsspa_groups_shapley
@@ -5638,6 +5712,18 @@ int lsspa_cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, ui
   return abi_caught(ctx);
 }
 
+int lsspa_cv_top(lsspa_ctx* ctx, uint32_t include, int32_t T, int64_t steps, double* v, uint32_t* masks, int32_t* count,
+                 double* v_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  TRY(cv_need_columns(ctx, "lsspa_cv_top"));
+  if (!v || !masks || !count || !v_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_top: v / masks / count / v_fold / info is NULL");
+  return cv_top(ctx, include, T, steps, v, masks, count, v_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
 int lsspa_cv_timing(const lsspa_ctx* ctx, double* gram_ms, double* enum_ms, double* max_launch_ms,
                     int64_t* launches) try {
   if (!ctx) return LSSPA_ERR_ARG;
@@ -5696,6 +5782,18 @@ int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan) try {
   const CvPlan P = cv_best_plan(p, K, 0);
   const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, (int64_t)P.launches,
                           (int64_t)subsets_cv_lds_bytes(), 64, 0, 0};
+  std::copy(out, out + 8, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_debug_cv_top_plan(int32_t p, int32_t K, int32_t T, int64_t* plan) try {
+  if (!plan || p < 1 || p > SUBSETS_MAX_P || K < 2 || K > CV_MAX_FOLDS || T < 1 || T > SUBSETS_TOP_MAX)
+    return LSSPA_ERR_ARG;
+  const CvTopPlan P = cv_top_plan(p, K, T, 0);
+  const int64_t out[8] = {(int64_t)P.cut.units, (int64_t)P.cut.per, (int64_t)P.cut.steps, (int64_t)P.cut.launches,
+                          (int64_t)subsets_cv_top_lds_bytes(T), 64, P.table.sizes, P.table.bytes};
   std::copy(out, out + 8, plan);
   return LSSPA_OK;
 } catch (...) {

@@ -26,18 +26,20 @@ p <= 64 columns: the n_best <= 16 best sets of groups of every size, returning `
 ``ls_spa_cv`` (the exact attribution of the K-fold cross-validated R^2 of one data set, p <= 32, returning
 ``CVResults``) and ``ls_spa_best_subsets_cv`` (best-subset selection by that cross-validated R^2, returning
 ``CVBestSubsetsResults``; ``cv_fold_ids`` is the fold assignment of both; with ``groups=`` both work on g <= 32 groups
-of p <= 64 columns and return ``CVGroupResults`` and ``CVBestGroupSubsetsResults``)
+of p <= 64 columns and return ``CVGroupResults`` and ``CVBestGroupSubsetsResults``) and ``ls_spa_top_subsets_cv`` (the
+n_best <= 16 best models of every size by that cross-validated R^2, p <= 32, with the one-standard-error fields the
+folds' paired values give, returning ``TopSubsetsCVResults``)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
-                       TopGroupSubsetsResults, TopSubsetsResults, validate_data)
+                       TopGroupSubsetsResults, TopSubsetsCVResults, TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
 from ._driver import (ls_spa, ls_spa_cv, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
-                      ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_subsets,
+                      ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_subsets, ls_spa_top_subsets_cv,
                       reduce_data, square_shapley, run_estimator, release)
 from ._native import LSSPANativeError
 from ._rccl import NativeComm
@@ -57,4 +59,5 @@ __all__ = [
     "ls_spa_top_group_subsets", "TopGroupSubsetsResults",
     "ls_spa_cv", "CVResults", "ls_spa_best_subsets_cv", "CVBestSubsetsResults", "cv_fold_ids",
     "CVGroupResults", "CVBestGroupSubsetsResults",
+    "ls_spa_top_subsets_cv", "TopSubsetsCVResults",
 ]

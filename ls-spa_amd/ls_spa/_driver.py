@@ -34,7 +34,8 @@ from ._native import LSSPANativeError
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
-                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsResults, TopSubsetsResults, validate_data)
+                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsResults, TopSubsetsCVResults,
+                       TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
 # problems up to this many features take the one-workgroup-per-ordering kernels (csrc/k_small.hip small_p_eligible:
@@ -1674,7 +1675,111 @@ def ls_spa_top_subsets(X_train, X_test, y_train, y_test, reg=0., n_best=10, *, i
                              best_size=best_size, best_subset=best_subset, full_r_squared=float(full_r_squared))
 
 
-GROUPS_TOP_MAX = 16        # include/lsspa.h, lsspa_groups_top: ranks per size
+def _one_se_fields(r_squared, fold_r_squared, n_models, best_row):
+    """(best_gap, best_gap_std_error, within_one_se) [n][T] of the listed models against the overall best one, rank 0 of
+    row ``best_row`` (-1: no model at all), in fp64 from the per-fold values alone: d_f = fold[b][f] - fold[i, r][f],
+    the standard error of their sum over K folds is sqrt(K) std(d, ddof=1)."""
+    n, T, K = fold_r_squared.shape
+    best_gap = np.full((n, T), np.nan)
+    std_error = np.full((n, T), np.nan)
+    within = np.zeros((n, T), dtype=bool)
+    if best_row < 0:
+        return best_gap, std_error, within
+    listed = np.arange(T)[None, :] < np.asarray(n_models)[:, None]
+    d = fold_r_squared[best_row, 0][None, None, :] - fold_r_squared
+    best_gap[listed] = (r_squared[best_row, 0] - r_squared)[listed]
+    std_error[listed] = (np.sqrt(K) * np.std(d, axis=2, ddof=1))[listed]
+    within[listed] = best_gap[listed] <= std_error[listed]
+    return best_gap, std_error, within
+
+
+def ls_spa_top_subsets_cv(X, y, reg=0., folds=5, n_best=10, *, include=None, seed=42, shuffle=True, device=0,
+                          _engine=None):
+    """The ``n_best`` best models of every size by the K-fold cross-validated R^2, over all 2^p feature subsets
+    (p <= 32): how much worse is the next model when all K folds judge -- and can the folds tell them apart at all?
+
+    ``ls_spa_top_subsets`` lists the near-best models of one train / test split, ``ls_spa_best_subsets_cv`` names one
+    winner per size by v_cv(S) = sum_f v_f(S).  This call is their product: the enumeration evaluates every subset on
+    all K fold problems, adds the K values in ascending order and keeps per size the ``n_best`` (1 .. 16) largest sums,
+    best first, on equal values the subset with the smaller mask (bit j = feature j) first (fp64, bitwise
+    reproducible; include/lsspa.h, lsspa_cv_top).  Rank 0 of every size is ``ls_spa_best_subsets_cv``'s winner, bit for
+    bit.  K calls of ``ls_spa_top_subsets`` could not be merged into this: a subset that is 17th in every fold can be
+    first in the sum.
+
+    folds, seed, shuffle:  as for ``ls_spa_cv``.   n_best, include:  as for ``ls_spa_top_subsets``.
+
+    Returns ``TopSubsetsCVResults``: the fields of ``TopSubsetsResults`` with the cross-validated value -- ``sizes`` [n],
+    ``n_models`` [n], ``subsets`` [n][n_best][p] bool, ``r_squared`` [n][n_best], ``theta`` [n][n_best][p] (each listed
+    model refitted on ALL rows on the host in fp64, exactly 0.0 outside its subset), ``gap`` [n][n_best]
+    (``r_squared[:, :1] - r_squared``), ``top_sizes``, ``top_subsets``, ``top_r_squared``, ``best_size``,
+    ``best_subset``, ``full_r_squared`` (the cross-validated R^2 of all p columns) -- plus ``fold_r_squared``
+    [n][n_best][K] (a listed model's per-fold values, summing to its ``r_squared``) and ``fold_ids`` [N].  Ranks past
+    ``n_models`` are NaN (False in ``subsets``).
+
+    What the folds add, computed on the host in fp64 from ``fold_r_squared`` alone.  With b the overall best model
+    (rank 0 of ``best_size``) and d_f = fold_r_squared[b][f] - fold_r_squared[i, r][f] -- paired differences, every
+    fold over the same pooled ||y||^2 --: ``best_gap`` [n][n_best] = r_squared[b] - r_squared[i, r],
+    ``best_gap_std_error`` [n][n_best] = sqrt(K) std(d, ddof=1), ``within_one_se`` [n][n_best] = best_gap <=
+    best_gap_std_error (False past ``n_models``), ``one_se_size``: the smallest size whose rank 0 is within one
+    standard error of the best (``best_size`` always qualifies) and ``one_se_subset``, that size's rank-0 subset.
+    K folds are few and their training sets overlap, so the d_f are neither many nor independent: this is the usual
+    one-standard-error heuristic for preferring the smaller model, not a test, and no p-value should be read from it.
+
+    The refusals of ``ls_spa_cv`` and those of ``n_best`` and ``include`` come before any GPU work.  A subset with a
+    pivot that failed in any fold is no candidate and raises a RuntimeWarning that names the folds.  There is no
+    ``groups=``: top lists of the cross-validated value over groups of columns are not built.  Neither is a bootstrap
+    of the list."""
+    X, y, ids, K = _cv_data("ls_spa_top_subsets_cv", X, y, folds, seed, shuffle)
+    p = X.shape[1]
+    if isinstance(n_best, (bool, np.bool_)) or not isinstance(n_best, (int, np.integer)) \
+            or not 1 <= n_best <= SUBSETS_TOP_MAX:
+        raise ValueError(f"n_best must be an integer in 1 .. {SUBSETS_TOP_MAX} (got {n_best!r})")
+    T = int(n_best)
+    mask, inc = include_mask(include, p)
+    with _engine_call(_engine, device) as engine:
+        engine.cv_load(X, y, ids, K, reg)
+        try:
+            v, masks, count, v_fold, info = engine.cv_top(mask, T)
+            full, _ = engine.debug_cv_values(np.array([(1 << p) - 1], dtype=np.uint64), folds=False)
+        finally:
+            engine.cv_free()
+    _cv_verdict(info, stacklevel=2)
+    G, g = _cv_full_problem(X, y, reg)
+    sizes = np.arange(len(inc), p + 1)
+    n = len(sizes)
+    n_models = np.asarray(count)[sizes].astype(np.int64)
+    subsets = np.zeros((n, T, p), dtype=bool)
+    r_squared = np.full((n, T), np.nan)
+    fold_r_squared = np.full((n, T, K), np.nan)
+    theta = np.full((n, T, p), np.nan)
+    for i, k in enumerate(sizes):
+        for r in range(n_models[i]):
+            subsets[i, r] = (int(masks[k, r]) >> np.arange(p)) & 1
+            r_squared[i, r] = v[k, r]
+            fold_r_squared[i, r] = v_fold[k, r]
+            theta[i, r] = _subset_fit(G, g, np.nonzero(subsets[i, r])[0])
+    # the best over all sizes lie inside the per-size lists: a merge under the same order, larger value then smaller mask
+    ii, rr = np.nonzero(np.arange(T)[None, :] < n_models[:, None])
+    order = np.lexsort((np.asarray(masks)[sizes[ii], rr], -r_squared[ii, rr]))[:T]
+    best_row, best_size, best_subset = -1, -1, np.zeros(p, dtype=bool)
+    if n_models.any():
+        best_row = int(np.nanargmax(r_squared[:, 0]))      # the first of equal maxima: the smallest size
+        best_size, best_subset = int(sizes[best_row]), subsets[best_row, 0].copy()
+    best_gap, std_error, within = _one_se_fields(r_squared, fold_r_squared, n_models, best_row)
+    one_se_size, one_se_subset = -1, np.zeros(p, dtype=bool)
+    if best_row >= 0:
+        i = int(np.argmax(within[:, 0]))                   # the first size that qualifies; best_size's own row does
+        one_se_size, one_se_subset = int(sizes[i]), subsets[i, 0].copy()
+    return TopSubsetsCVResults(sizes=sizes, n_models=n_models, subsets=subsets, r_squared=r_squared,
+                               fold_r_squared=fold_r_squared, theta=theta, gap=r_squared[:, :1] - r_squared,
+                               top_sizes=sizes[ii[order]], top_subsets=subsets[ii[order], rr[order]],
+                               top_r_squared=r_squared[ii[order], rr[order]], best_size=best_size,
+                               best_subset=best_subset, full_r_squared=float(full[0]), best_gap=best_gap,
+                               best_gap_std_error=std_error, within_one_se=within, one_se_size=one_se_size,
+                               one_se_subset=one_se_subset, fold_ids=ids)
+
+
+GROUPS_TOP_MAX = 16       # include/lsspa.h, lsspa_groups_top: ranks per size
 
 
 def ls_spa_top_group_subsets(X_train, X_test, y_train, y_test, groups, reg=0., n_best=10, *, device=0, _engine=None):

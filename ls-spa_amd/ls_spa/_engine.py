@@ -229,6 +229,20 @@ def debug_cv_plan(p: int, folds: int):
     return dict(zip(CV_PLAN_FIELDS, (int(v) for v in out)))
 
 
+CV_TOP_PLAN_FIELDS = ("units", "per", "steps", "launches", "lds_bytes", "workgroup", "sizes", "table_bytes")
+
+
+def debug_cv_top_plan(p: int, folds: int, n_best: int):
+    """Test hook, host only: how cv_top enumerates p features over `folds` fold problems for n_best models a size
+    (include/lsspa.h, lsspa_debug_cv_top_plan) -- a dict with CV_TOP_PLAN_FIELDS.  ValueError for a p, a number of folds
+    or an n_best the library refuses."""
+    out = np.zeros(8, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_top_plan(int(p), int(folds), int(n_best), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_top_plan: status {rc}")
+    return dict(zip(CV_TOP_PLAN_FIELDS, (int(v) for v in out)))
+
+
 CV_GROUPS_PLAN_FIELDS = ("gl", "gh", "ql", "nb", "units", "per", "steps", "launches", "lds_bytes", "workgroup",
                          "lds_bytes_one_problem", "launch_bound")
 
@@ -727,6 +741,21 @@ class HipEngine:
             found.ctypes.data_as(C.POINTER(C.c_uint8)), N.dptr(v_fold), N.iptr(info)))
         return v, masks, found.astype(bool), v_fold, info
 
+    def cv_top(self, include=0, n_best=10, steps: int = 0):
+        """(v [p + 1][n_best], masks [p + 1][n_best] uint32, count [p + 1] int32, v_fold [p + 1][n_best][K], info [K]):
+        the n_best <= 16 best subsets of every size by the cross-validated value, best first -- the larger value, on
+        equal values the smaller mask (include/lsspa.h, lsspa_cv_top); NaN / 0 past count.  Rank 0 is cv_best's.
+        steps as in cv_best.  cv_timing() then speaks of this call."""
+        p, K = self._cv_pk()
+        n, T = p + 1, int(n_best)
+        v, masks = np.empty((n, max(T, 0))), np.empty((n, max(T, 0)), dtype=np.uint32)
+        count = np.empty(n, dtype=np.int32)
+        v_fold, info = np.empty((n, max(T, 0), K)), np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_top(
+            self._h, int(include), T, int(steps), N.dptr(v), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            count.ctypes.data_as(C.POINTER(C.c_int32)), N.dptr(v_fold), N.iptr(info)))
+        return v, masks, count, v_fold, info
+
     def cv_timing(self):
         """Kernel seconds of the load's Gram side and of the last enumeration, its longest launch and the launches."""
         a, b, c, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
@@ -753,6 +782,7 @@ class HipEngine:
         return v, v_fold
 
     debug_cv_plan = staticmethod(debug_cv_plan)
+    debug_cv_top_plan = staticmethod(debug_cv_top_plan)
 
     # ---- ... over groups of columns (g <= 32 groups of p <= 64 columns) ----
     def cv_groups_load(self, X, y, fold_ids, K: int, reg: float):

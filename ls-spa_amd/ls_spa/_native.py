@@ -165,6 +165,8 @@ SIGNATURES = {
     "lsspa_cv_get_problem": (C.c_int, [_vp, _i32, _pd, _pd, _pd, _pd, _pd]),
     "lsspa_debug_cv_values": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64, _pd, _pd]),
     "lsspa_debug_cv_plan": (C.c_int, [_i32, _i32, _pi64]),
+    "lsspa_cv_top": (C.c_int, [_vp, C.c_uint32, _i32, _i64, _pd, C.POINTER(C.c_uint32), _pi32, _pd, _pi32]),
+    "lsspa_debug_cv_top_plan": (C.c_int, [_i32, _i32, _i32, _pi64]),
     "lsspa_cv_groups_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _pi32, _i32, _dbl, _i32, _i32]),
     "lsspa_cv_groups_shapley": (C.c_int, [_vp, _pi32, _i32, _pd, _pd, _pd, _pd, _pi32]),
     "lsspa_cv_groups_best": (C.c_int, [_vp, _pi32, _i32, _i64, _pd, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), _pd,

@@ -901,6 +901,68 @@ class CVBestSubsetsResults:
 
 
 @dataclass
+class TopSubsetsCVResults:
+    """What ``ls_spa_top_subsets_cv`` returns for p features, K folds, n = p + 1 - len(include) sizes and T = n_best
+    ranks: the fields of ``TopSubsetsResults`` with the K-fold cross-validated R^2 as the value.  ``r_squared`` [n][T]:
+    rank r of size i, best first -- the larger value, on equal values the subset with the smaller mask;
+    ``fold_r_squared`` [n][T][K]: its per-fold values, whose sum in ascending fold order it is; ``theta`` [n][T][p]: the
+    model refitted on ALL rows, exactly 0.0 outside its subset; ``gap`` [n][T]: ``r_squared[:, :1] - r_squared``;
+    ``top_sizes``, ``top_subsets``, ``top_r_squared``: the min(T, all valid ranks) best models over all sizes;
+    ``best_size``, ``best_subset``, ``full_r_squared``: ``ls_spa_best_subsets_cv``'s; ``fold_ids`` [N]: the fold of
+    every row.  Ranks past ``n_models`` are NaN (False in ``subsets`` and ``within_one_se``).
+
+    Against the overall best model b (rank 0 of ``best_size``), from ``fold_r_squared`` alone, with the paired per-fold
+    differences d_f = fold_r_squared[b][f] - fold_r_squared[i, r][f]: ``best_gap`` [n][T] = r_squared[b] -
+    r_squared[i, r]; ``best_gap_std_error`` [n][T] = sqrt(K) std(d, ddof=1); ``within_one_se`` [n][T] = best_gap <=
+    best_gap_std_error; ``one_se_size``: the smallest size whose rank 0 is within one standard error (``best_size``
+    always is; -1 if nothing is listed) and ``one_se_subset`` [p] bool, that size's rank 0.  K folds are few and their
+    training sets overlap: this is the usual one-standard-error heuristic, not a test."""
+    sizes: np.ndarray
+    n_models: np.ndarray
+    subsets: np.ndarray
+    r_squared: np.ndarray
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    gap: np.ndarray
+    top_sizes: np.ndarray
+    top_subsets: np.ndarray
+    top_r_squared: np.ndarray
+    best_size: int
+    best_subset: np.ndarray
+    full_r_squared: float
+    best_gap: np.ndarray
+    best_gap_std_error: np.ndarray
+    within_one_se: np.ndarray
+    one_se_size: int
+    one_se_subset: np.ndarray
+    fold_ids: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        n, T, p = np.asarray(self.subsets).shape
+        K = np.asarray(self.fold_r_squared).shape[2]
+        chosen = ", ".join(str(j) for j in np.nonzero(self.best_subset)[0][:12])
+        best = runner = "nan"
+        if self.best_size >= 0:
+            best = f"{float(self.top_r_squared[0]):.2e}"
+        if len(self.top_r_squared) > 1:
+            runner = f"{float(self.top_r_squared[0] - self.top_r_squared[1]):.2e}"
+        lines = [
+            "",
+            f"{pad}p = {p}, {K}-fold cross-validation, the {T} best subsets of sizes {int(self.sizes[0])} .. "
+            f"{int(self.sizes[-1])}",
+            f"{pad}Cross-validated R^2 with all features: {self.full_r_squared:.2e}",
+            f"{pad}Best model: {self.best_size} features, cross-validated R^2 {best}",
+            f"{pad}Its features: ({chosen}{', ...' if int(np.sum(self.best_subset)) > 12 else ''})",
+            f"{pad}The next model over all sizes is worse by {runner}",
+            f"{pad}Smallest size within one standard error of the best: {self.one_se_size}; listed models within it: "
+            f"{int(np.sum(self.within_one_se))}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class CVGroupResults:
     """What ``ls_spa_cv(groups=)`` returns for g groups of p columns, K folds and N rows.  ``attribution`` [g]: the exact
     Shapley attribution of the K-fold cross-validated R^2 to the groups; ``fold_attribution`` [K][g]: the folds'
