@@ -526,7 +526,24 @@ int lsspa_debug_cv_top_plan(int32_t p, int32_t K, int32_t T, int64_t* plan /* [8
  *                     launch bound / (units K), at least 1, at most per), its launches, the LDS bytes of a workgroup,
  *                     its threads (256), the LDS bytes of lsspa_groups_best's workgroup and that launch bound.  Labels
  *                     the library refuses, p > 64, g > 32 or K outside 2 .. 32: LSSPA_ERR_ARG.
- * Top lists, interactions and a bootstrap over the folds are not built. */
+ *   lsspa_cv_groups_top    : lsspa_groups_top by u_cv: per size k = 0 .. g the T best sets of groups (1 <= T <= 16), best
+ *                     first, in lsspa_cv_groups_best's order and over its candidates, whose sum is also above -inf (so
+ *                     never NaN).  u [g+1][T], masks [g+1][T] (the caller's numbering), count [g+1] = min(T, candidates
+ *                     of size k); NaN / 0 past count[k].  Masks are unique, so the lists depend on no cut; rank 0 is
+ *                     lsspa_cv_groups_best's winner and the list for T is a prefix of the list for T' > T.  u[k][r] has
+ *                     the bits of lsspa_debug_cv_group_values for masks[k][r]; u_fold [g+1][T][K]: the listed models'
+ *                     per-fold values by that same device code (NaN past count[k]).  The cut into units, steps and
+ *                     launches is lsspa_cv_groups_best's; steps, info [K] as there.  Refusals, in this order and before
+ *                     any launch (the loaded folds stay usable): nothing loaded (LSSPA_ERR_STATE), a NULL pointer, the
+ *                     labels (lsspa_groups_shapley's messages), T outside 1 .. 16, steps < 0 (LSSPA_ERR_ARG).  No
+ *                     floating-point atomics: two calls agree bitwise.
+ *   lsspa_debug_cv_groups_top_plan: host only, no context, no GPU -- lsspa_debug_cv_groups_plan's first eight entries
+ *                     (gl, gh, ql, nb, units, per, steps, launches), then the LDS bytes of a workgroup of
+ *                     lsspa_cv_groups_top's kernel (the same for every K and T), its threads (256), the sizes one unit
+ *                     can hold (min(g, popc(per - 1) + gl) + 1) and the bytes of the table (units (g + 1) (12 T + 4)).
+ *                     Labels the library refuses, p > 64, g > 32, K outside 2 .. 32 or T outside 1 .. 16:
+ *                     LSSPA_ERR_ARG.
+ * Interactions and a bootstrap over the folds are not built. */
 int lsspa_cv_groups_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
                          const int32_t* fold_ids /* [N], host */, int32_t K, double reg, int32_t dtype,
                          int32_t location);
@@ -540,6 +557,11 @@ int lsspa_debug_cv_group_values(lsspa_ctx* ctx, const int32_t* labels /* [p] */,
                                 int64_t n, double* u /* [n] */, double* u_fold /* [n][K] or NULL */);
 int lsspa_debug_cv_groups_plan(const int32_t* labels /* [p] */, int32_t p, int32_t g, int32_t K,
                                int64_t* plan /* [12] */);
+int lsspa_cv_groups_top(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g, int32_t T, int64_t steps,
+                        double* u /* [g+1][T] */, uint32_t* masks /* [g+1][T] */, int32_t* count /* [g+1] */,
+                        double* u_fold /* [g+1][T][K] */, int32_t* info /* [K] */);
+int lsspa_debug_cv_groups_top_plan(const int32_t* labels /* [p] */, int32_t p, int32_t g, int32_t K, int32_t T,
+                                   int64_t* plan /* [12] */);
 
 /* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
  * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the

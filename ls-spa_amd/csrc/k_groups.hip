@@ -77,7 +77,8 @@
 // K-fold cross-validation over groups (lsspa_cv_groups_best, groups_cv_best_kernel below): that kernel's sibling, which
 // takes every high subset through the K fold problems of k_cv.hip in one step and keeps the best SUM of their values
 // per size.  The attribution (lsspa_cv_groups_shapley) needs no kernel of its own: the folds are replicates of the
-// enumeration kernel's REPS instantiation.
+// enumeration kernel's REPS instantiation.  The T best sums per size (lsspa_cv_groups_top, groups_cv_top_kernel below):
+// that kernel's fold-step with groups_top_kernel's lists.
 #include "kernels.h"
 
 #include <algorithm>
@@ -907,6 +908,131 @@ __global__ __launch_bounds__(NT) void groups_top_kernel(GroupArgs a, uint64_t s0
   if (__any(any_bad) && (tid & 63) == 0) atomicOr(a.info, 1);
 }
 
+// ---- the T best group subsets of every size by the K-fold cross-validated value (lsspa_cv_groups_top) ----
+// groups_cv_best_kernel's fold-step with groups_top_kernel's lists; neither sibling changes.  The same workgroup, units,
+// per, steps and launches as groups_cv_best_kernel; load_shared<false> once; per step and per fold f = 0 .. F-1, in this
+// order: fold_args, stage_fold, group_values<false> on fold f's addresses, u = f == 0 ? u_f : u + u_f, the barrier that
+// ends the fold-step.  So every u_f has the bits groups_cv_debug_kernel gives and the sum is formed in fold order.  A
+// subset is a candidate if its own pivots passed in EVERY fold and its sum is above -inf (so never NaN); a failed pivot
+// raises the info word of the fold it failed in, as in groups_cv_best_kernel.  Lists, table, order (top_before over
+// CALLER masks: the lane's low part translated once, the high part once per step from GroupIds -- it is the same for all
+// folds of the step), fast path and wave-wide rank-and-shift insert are groups_top_kernel's, unchanged in logic.
+//   Hazards:
+//   - the lists (st.v, st.m, st.c) are wave 0's alone: loaded by wave 0 before load_shared's barrier, read and written by
+//     wave 0 in the insert, stored by wave 0 after the last step.  The insert loop contains no workgroup barrier and is
+//     executed by wave 0 only; wave_lds_fence orders its rounds (the header of groups_top_kernel);
+//   - the insert runs once per step, after the last fold's value is known, BEHIND the last fold-step's closing barrier
+//     and before the next step's first group_values -- where groups_cv_best_kernel updates its slots.  The next barrier
+//     all four waves reach is the first one inside that group_values (or, after the last step, none: the store of the
+//     lists is wave 0's own, in program order behind the insert).  Meanwhile the other three waves may already stage
+//     the next step's fold 0 into sh.h / sh.gdiag and write sh.idx: the insert reads and writes nothing of GrpShared --
+//     its operands are registers, the kernel's arguments and the lists -- and wave 0's own reads of sh.gdiag, sh.idx,
+//     sh.M and sh.Z in the last fold's 6 x 6 Cholesky are in front of the closing barrier.  The alternative, the insert
+//     in front of that barrier (groups_top_kernel's place), needs a test of f inside the fold loop and keeps three waves
+//     idle at the barrier for the length of the insert instead of letting them issue the next fold's loads;
+//   - stage_fold for fold f + 1 comes only behind the barrier that follows fold f's return (the 6 x 6 Cholesky hazard
+//     described above groups_cv_best_kernel): the structure of that kernel's fold loop is kept;
+//   - LDS is GrpShared + GrpTopShared, static, for every F and T: 4.9 KB beside GrpShared against the best-kernel's
+//     14.6 KB (groups_cv_top_lds_bytes), three workgroups a CU where groups_cv_best_kernel has two.
+// a.part [units][g + 1][T], tm [units][g + 1][T], tc [units][g + 1] as groups_top_kernel's; a.info [F]
+__global__ __launch_bounds__(NT) void groups_cv_top_kernel(GroupArgs a, int F, uint64_t s0, uint64_t s1, GroupIds ids,
+                                                           int T, uint32_t* __restrict__ tm, int32_t* __restrict__ tc) {
+  __shared__ GrpShared sh;
+  __shared__ GrpTopShared st;
+  const int tid = threadIdx.x;
+  const int ng = a.ng, gl = a.gl;
+  const bool live = tid < (1 << gl);           // wave 0 only (gl <= 6)
+  // the sizes this unit can hold: k0 + j, j < ns (popc(s) + popc(lane) with s < per, lane < 2^gl, and no more than ng)
+  const int k0 = __popc(blockIdx.x);
+  const int ns = min(ng - k0, __popcll(a.per - 1) + gl) + 1;       // <= GTS: launch_groups_cv_top
+  double* gv = a.part + ((int64_t)blockIdx.x * (ng + 1) + k0) * T;
+  uint32_t* gm = tm + ((int64_t)blockIdx.x * (ng + 1) + k0) * T;
+  int32_t* gc = tc + (int64_t)blockIdx.x * (ng + 1) + k0;
+  if (tid < 64) {
+    for (int e = tid; e < ns * T; e += 64) {
+      const int j = e / T, r = e - j * T;
+      if (r < gc[j]) {
+        st.v[j * GTM + r] = gv[e];
+        st.m[j * GTM + r] = gm[e];
+      }
+    }
+    if (tid < ns) st.c[tid] = gc[tid];
+  }
+  if (tid < GG) st.gid[tid] = ids.id[tid];
+  load_shared<false>(sh, a, tid);              // (ends with a barrier: the lists, gid; h and gdiag are restaged per fold)
+  uint32_t low = 0u;                           // the lane's low groups in the caller's numbering
+  for (int r = 0; r < gl; ++r)
+    if ((tid >> r) & 1) low |= 1u << st.gid[r];
+  const int jl = live ? __popc(tid) : 0;
+  uint32_t bad_folds = 0u;                     // bit f: a pivot of fold f failed in a subset this thread saw
+  for (uint64_t s = s0; s < s1; ++s) {
+    const uint64_t hi = (uint64_t)blockIdx.x * a.per + s;
+    double v = 0.0;
+    bool bad_any = false;                      // this subset's own pivots, over the folds
+#pragma unroll 1
+    for (int f = 0; f < F; ++f) {
+      const GroupArgs af = fold_args(a, f);
+      stage_fold(sh, af, tid);
+      bool bad = false;
+      const double vf = group_values<false>(sh, af, hi, tid, bad);
+      v = f == 0 ? vf : v + vf;
+      bad_any |= bad;
+      bad_folds |= bad ? (1u << f) : 0u;
+      __syncthreads();
+    }
+    // behind the step's last barrier, in front of the next group_values' first: the lists are wave 0's (the header)
+    if (tid < 64) {                            // wave 0: no workgroup barrier in here
+      // the high groups of hi in the caller's numbering: the same for every lane and every fold (gh <= 31)
+      uint32_t hm = 0u;
+      for (uint32_t b = (uint32_t)hi; b != 0u; b &= b - 1u) hm |= 1u << ids.id[gl + __ffs((int)b) - 1];
+      const uint32_t m = hm | low;
+      const int j = __popcll(s) + jl;          // < ns for every live lane
+      // a candidate that belongs into its size's list as it is now: the list is not full, or its last entry comes later
+      auto wanted = [&]() {
+        return st.c[j] < T || top_before(v, m, st.v[j * GTM + T - 1], st.m[j * GTM + T - 1]);
+      };
+      bool want = live && !bad_any && v > -__builtin_huge_val() && wanted();
+      for (uint64_t todo = __ballot(want); todo != 0ull; todo = __ballot(want)) {
+        const int src = __ffsll((unsigned long long)todo) - 1;
+        const double nv = __shfl(v, src, 64);
+        const uint32_t nm = (uint32_t)__shfl((int)m, src, 64);
+        const int nj = __shfl(j, src, 64);
+        double* rv = st.v + nj * GTM;
+        uint32_t* rm = st.m + nj * GTM;
+        const int c = st.c[nj];
+        const bool have = tid < c;             // c <= T <= 16: lane t holds entry t
+        const double ev = have ? rv[tid] : 0.0;
+        const uint32_t em = have ? rm[tid] : 0u;
+        const int rank = __popcll(__ballot(have && top_before(ev, em, nv, nm)));
+        const double pv = __shfl_up(ev, 1, 64);
+        const uint32_t pm = (uint32_t)__shfl_up((int)em, 1, 64);
+        const int nc = min(c + 1, T);
+        wave_lds_fence();                      // every lane has read its entry and the count
+        if (tid >= rank && tid < nc) {         // a lane writes the entry it read: no other lane's
+          rv[tid] = tid == rank ? nv : pv;
+          rm[tid] = tid == rank ? nm : pm;
+        }
+        if (tid == 0) st.c[nj] = nc;
+        wave_lds_fence();                      // the list as it now is, for every lane
+        if (tid == src) want = false;
+        want = want && wanted();
+      }
+    }
+  }
+  if (tid < 64) {                              // wave 0, behind its own last insert
+    for (int e = tid; e < ns * T; e += 64) {
+      const int j = e / T, r = e - j * T;
+      if (r < st.c[j]) {
+        gv[e] = st.v[j * GTM + r];
+        gm[e] = st.m[j * GTM + r];
+      }
+    }
+    if (tid < ns) gc[tid] = st.c[tid];
+  }
+  for (int f = 0; f < F; ++f)
+    if (__any((bad_folds >> f) & 1u) && (tid & 63) == 0) atomicOr(a.info + f, 1);
+}
+
 // masks in the layout's own numbering: bits 0 .. gl-1 the low groups, then the high ones
 __global__ __launch_bounds__(NT) void groups_debug_kernel(GroupArgs a, const uint64_t* __restrict__ masks, int64_t n,
                                                           double* __restrict__ vals) {
@@ -1092,6 +1218,32 @@ hipError_t launch_groups_cv_best(const GroupArgs& a, int folds, const int* gid, 
     ids.id[r] = (uint8_t)gid[r];
   }
   hipLaunchKernelGGL(groups_cv_best_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, folds, s0, s1, ids, bm);
+  return hipGetLastError();
+}
+
+// groups_cv_top_kernel's two: the compiler lays the lists first, padded to 16 bytes, and GrpShared (a multiple of 8)
+// behind them; its resource report says 48664, for this kernel and for groups_top_kernel
+size_t groups_cv_top_lds_bytes() { return lds16(sizeof(GrpTopShared)) + sizeof(GrpShared); }
+
+hipError_t launch_groups_cv_top(const GroupArgs& a, int folds, const int* gid, uint64_t units, uint64_t s0, uint64_t s1,
+                                int T, uint32_t* tm, int32_t* tc, hipStream_t st) {
+  if (!args_ok(a) || !a.part || !tm || !tc || !gid || units < 1 || s1 <= s0 || s1 > a.per) return hipErrorInvalidValue;
+  if (T < 1 || T > GROUPS_TOP_MAX) return hipErrorInvalidValue;
+  // the caller vouches for `folds` problems, denominators (inv_yy_rep) and info words behind the first
+  if (!a.inv_yy_rep || folds < 2 || folds > CV_MAX_FOLDS) return hipErrorInvalidValue;
+  if (a.gh > GHI) return hipErrorInvalidValue;       // hi is kept in 32 bits (no layout of <= 64 columns has gh = 32)
+  if (units * a.per != (1ull << a.gh) || units > (1ull << 31)) return hipErrorInvalidValue;
+  // the sizes of a unit are popc(s) + popc(lane), s < per: per a power of two of at most GBS - 1 bits, GTS lists
+  if (a.per > (1ull << (GBS - 1))) return hipErrorInvalidValue;
+  if (__builtin_popcountll(a.per - 1) + a.gl + 1 > GTS) return hipErrorInvalidValue;
+  GroupIds ids{};
+  uint32_t seen = 0u;
+  for (int r = 0; r < a.ng; ++r) {                   // a permutation of 0 .. ng-1: the kernel shifts by them
+    if (gid[r] < 0 || gid[r] >= a.ng || ((seen >> gid[r]) & 1u)) return hipErrorInvalidValue;
+    seen |= 1u << gid[r];
+    ids.id[r] = (uint8_t)gid[r];
+  }
+  hipLaunchKernelGGL(groups_cv_top_kernel, dim3((unsigned)units), dim3(NT), 0, st, a, folds, s0, s1, ids, T, tm, tc);
   return hipGetLastError();
 }
 

@@ -504,6 +504,14 @@ hipError_t launch_groups_cv_debug(const GroupArgs& a, int folds, const uint64_t*
                                   double* vfold, hipStream_t st);
 size_t groups_cv_lds_bytes();      // static LDS of a workgroup of launch_groups_cv_best
 size_t groups_best_lds_bytes();    // and of launch_groups_best's one-problem kernel
+// launch_groups_cv_top: launch_groups_cv_best's units, steps, launches, fold-step, candidates (whose sum is also above
+// -inf) and info words with launch_groups_top's lists, order and tables: a.part [units][g + 1][T], tm [units][g + 1][T]
+// (CALLER masks), tc [units][g + 1], tc zeroed before the first launch; every launch merges into the lists, which do not
+// depend on the cut.  launch_subsets_top_reduce (p = g) merges the units' lists.  The refusals of both siblings:
+// 1 <= T <= GROUPS_TOP_MAX, 2 <= folds <= CV_MAX_FOLDS, per of at most GROUPS_BEST_CLASSES - 1 bits.
+hipError_t launch_groups_cv_top(const GroupArgs& a, int folds, const int* gid, uint64_t units, uint64_t s0, uint64_t s1,
+                                int T, uint32_t* tm, int32_t* tc, hipStream_t st);
+size_t groups_cv_top_lds_bytes();  // static LDS of a workgroup of launch_groups_cv_top, whatever folds and T
 // phi_fold[f][gid[r]] = out[f][r] - out[f][ng] of the grouped enumeration's column sums out [folds][ng + 1] (layout
 // numbering; gid: GroupLayout::gid), phi[k] = their sum over f in ascending order
 hipError_t launch_cv_groups_foldsum(const double* out, int ng, int folds, const int* gid, double* phi_fold, double* phi,

@@ -114,7 +114,8 @@ struct CvWork {
   DevBuf<uint64_t> masks;
   DevBuf<int32_t> info, dinfo;             // [K] info words of a call; the debug values' own
   DevBuf<uint32_t> best;                   // lsspa_cv_best: (mask, found) of the units' rows, then of the result;
-                                           // lsspa_cv_top: the lists' masks and counts, then the result's
+                                           // lsspa_cv_top, lsspa_cv_groups_top: the lists' masks and counts, then the
+                                           // result's
   double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
@@ -5397,7 +5398,7 @@ int cv_top(lsspa_ctx* ctx, uint32_t include, int T, int64_t steps, double* v, ui
 // ---- ... over groups of columns (lsspa_cv_groups_*; the CV kernels of k_groups.hip) ----
 // The fold problems are the same store; the players are the g groups of the labels, the baseline (label -1) is in every
 // model.  lsspa_cv_groups_shapley runs the REPS enumeration of k_groups.hip over the folds, cut as lsspa_groups_shapley
-// cuts one problem; lsspa_cv_groups_best runs groups_cv_best_kernel.
+// cuts one problem; lsspa_cv_groups_best runs groups_cv_best_kernel, lsspa_cv_groups_top groups_cv_top_kernel.
 
 // the column calls after a grouped load of more columns than they enumerate
 int cv_need_columns(lsspa_ctx* ctx, const char* name) {
@@ -5615,6 +5616,91 @@ int cv_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t ste
   return LSSPA_OK;
 }
 
+// lsspa_cv_groups_top: cv_groups_best's cut into launches (cv_groups_best_plan) and lifecycle with groups_top's table,
+// which depends on the layout and T alone: values in W.part [units][g + 1][T], in W.best the caller masks
+// [units][g + 1][T], the counts [units][g + 1] and behind them the result's masks [g + 1][T] and counts [g + 1].  What
+// the call and its plan hook both go by:
+struct CvGroupsTopPlan {
+  CvGroupsPlan cut;
+  int sizes;                 // sizes one unit can hold (GroupTopPlan::sizes)
+  size_t rows;               // units (g + 1): lists in the table
+  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
+};
+CvGroupsTopPlan cv_groups_top_plan(const GroupLayout& L, int K, int T, uint64_t forced) {
+  CvGroupsTopPlan P;
+  P.cut = cv_groups_best_plan(L, K, forced);
+  P.sizes = std::min(L.ng, __builtin_popcountll(P.cut.per - 1) + L.gl) + 1;
+  P.rows = (size_t)P.cut.units * (L.ng + 1);
+  P.bytes = (int64_t)P.rows * (12 * T + 4);
+  return P;
+}
+
+int cv_groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int T, int64_t steps, double* u, uint32_t* masks,
+                  int32_t* count, double* u_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  GroupLayout L;
+  TRY(cv_layout(ctx, labels, g, L));
+  if (T < 1 || T > GROUPS_TOP_MAX) {
+    char msg[120];
+    snprintf(msg, sizeof msg, "lsspa_cv_groups_top keeps 1 .. %d subsets of every size (T = %d)", GROUPS_TOP_MAX, T);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_groups_top: steps must be >= 0");
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(cv_groups_upload(ctx, L));
+  hipStream_t st = ctx->stream;
+  const int K = W.K, ng = L.ng;
+  const CvGroupsTopPlan CP = cv_groups_top_plan(L, K, T, (uint64_t)steps);
+  const CvGroupsPlan& P = CP.cut;
+  const size_t rows = CP.rows, n_out = (size_t)(ng + 1) * T;
+  TRY(dev_alloc(ctx, W.part, rows * T));
+  TRY(dev_alloc(ctx, W.out, n_out));
+  TRY(dev_alloc(ctx, W.best, rows * T + rows + n_out + (size_t)ng + 1));
+  uint32_t* tm = W.best.ptr;
+  int32_t* tc = reinterpret_cast<int32_t*>(tm + rows * T);
+  uint32_t* out_m = tm + rows * T + rows;
+  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
+  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * rows, st));      // the counts; no entry is read beyond one
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  GroupArgs a = cv_group_args(W, L, 0, W.info.ptr);
+  a.per = P.per;
+  a.part = W.part.ptr;
+  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  size_t l = 0;
+  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
+    HIPCHK(hipEventRecord(ev[2 * l], st));
+    HIPCHK(launch_groups_cv_top(a, K, L.gid, P.units, s0, std::min(P.per, s0 + P.steps), T, tm, tc, st));
+    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+  }
+  HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, (int64_t)P.units, ng, T, W.out.ptr, out_m, out_c, st));
+  HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (ng + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
+  std::vector<uint64_t> listed;
+  std::vector<size_t> at;
+  for (int k = 0; k <= ng; ++k)
+    for (int r = 0; r < T; ++r) {
+      const size_t e = (size_t)k * T + r;
+      for (int f = 0; f < K; ++f) u_fold[e * K + f] = std::nan("");
+      if (r < count[k]) {
+        at.push_back(e);
+        listed.push_back(masks[e]);
+      }
+    }
+  if (!listed.empty()) {      // the listed models' per-fold values, by the kernel's own fold-step
+    const size_t nl = listed.size();
+    std::vector<double> lv(nl), lf(nl * K);
+    TRY(cv_group_values(ctx, L, listed.data(), (int64_t)nl, lv.data(), lf.data()));
+    for (size_t i = 0; i < nl; ++i) std::copy(&lf[i * K], &lf[i * K] + K, u_fold + at[i] * K);
+  }
+  return LSSPA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5647,6 +5733,32 @@ int lsspa_cv_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64
   return cv_groups_best(ctx, labels, g, steps, u, masks, found, u_fold, info);
 } catch (...) {
   return abi_caught(ctx);
+}
+
+int lsspa_cv_groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int32_t T, int64_t steps, double* u,
+                        uint32_t* masks, int32_t* count, double* u_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!labels || !u || !masks || !count || !u_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_groups_top: labels / u / masks / count / u_fold / info is NULL");
+  return cv_groups_top(ctx, labels, g, T, steps, u, masks, count, u_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_groups_top_plan(const int32_t* labels, int32_t p, int32_t g, int32_t K, int32_t T,
+                                   int64_t* plan) try {
+  GroupLayout L;
+  if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || K < 2 || K > CV_MAX_FOLDS || T < 1 || T > GROUPS_TOP_MAX ||
+      groups_layout(labels, p, g, L))
+    return LSSPA_ERR_ARG;
+  const CvGroupsTopPlan P = cv_groups_top_plan(L, K, T, 0);
+  const int64_t out[12] = {L.gl, L.gh, L.ql, L.nb, (int64_t)P.cut.units, (int64_t)P.cut.per, (int64_t)P.cut.steps,
+                           (int64_t)P.cut.launches, (int64_t)groups_cv_top_lds_bytes(), 256, P.sizes, P.bytes};
+  std::copy(out, out + 12, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
 }
 
 int lsspa_debug_cv_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const uint64_t* masks, int64_t n,

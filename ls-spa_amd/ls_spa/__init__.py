@@ -28,18 +28,21 @@ p <= 64 columns: the n_best <= 16 best sets of groups of every size, returning `
 ``CVBestSubsetsResults``; ``cv_fold_ids`` is the fold assignment of both; with ``groups=`` both work on g <= 32 groups
 of p <= 64 columns and return ``CVGroupResults`` and ``CVBestGroupSubsetsResults``) and ``ls_spa_top_subsets_cv`` (the
 n_best <= 16 best models of every size by that cross-validated R^2, p <= 32, with the one-standard-error fields the
-folds' paired values give, returning ``TopSubsetsCVResults``)
+folds' paired values give, returning ``TopSubsetsCVResults``) and ``ls_spa_top_group_subsets_cv`` (the same over g <= 32
+groups of p <= 64 columns, returning ``TopGroupSubsetsCVResults``)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
-                       TopGroupSubsetsResults, TopSubsetsCVResults, TopSubsetsResults, validate_data)
+                       TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults, TopSubsetsResults,
+                       validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
 from ._driver import (ls_spa, ls_spa_cv, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
-                      ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_subsets, ls_spa_top_subsets_cv,
+                      ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_group_subsets_cv, ls_spa_top_subsets,
+                      ls_spa_top_subsets_cv,
                       reduce_data, square_shapley, run_estimator, release)
 from ._native import LSSPANativeError
 from ._rccl import NativeComm
@@ -60,4 +63,5 @@ __all__ = [
     "ls_spa_cv", "CVResults", "ls_spa_best_subsets_cv", "CVBestSubsetsResults", "cv_fold_ids",
     "CVGroupResults", "CVBestGroupSubsetsResults",
     "ls_spa_top_subsets_cv", "TopSubsetsCVResults",
+    "ls_spa_top_group_subsets_cv", "TopGroupSubsetsCVResults",
 ]

@@ -34,7 +34,7 @@ from ._native import LSSPANativeError
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
-                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsResults, TopSubsetsCVResults,
+                       SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults,
                        TopSubsetsResults, validate_data)
 from ._stats import error_estimates, error_estimates_lowrank
 
@@ -1693,6 +1693,95 @@ def _one_se_fields(r_squared, fold_r_squared, n_models, best_row):
     return best_gap, std_error, within
 
 
+def ls_spa_top_group_subsets_cv(X, y, groups, reg=0., folds=5, n_best=10, *, seed=42, shuffle=True, device=0,
+                                _engine=None):
+    """The ``n_best`` best models of every size by the K-fold cross-validated R^2, over all 2^g sets of groups of columns
+    (g <= 32 groups over p <= 64 columns): ``ls_spa_top_subsets_cv`` for a design matrix with an intercept, a one-hot
+    factor or a spline basis among its columns -- there the column call cannot be used correctly: the intercept
+    competes as a feature, a factor's dummies are listed one by one, and p <= 32 is a hard wall.
+
+    ``ls_spa_top_group_subsets`` lists the near-best sets of groups of one train / test split,
+    ``ls_spa_best_subsets_cv(groups=)`` names one winner per size by u_cv(S) = sum_f u_f(S).  This call is their
+    product: the enumeration takes every set of groups through all K fold problems, adds the K values in ascending
+    order and keeps per size the ``n_best`` (1 .. 16) largest sums, best first, on equal values the set with the smaller
+    mask (bit k = group k) first (fp64, bitwise reproducible; include/lsspa.h, lsspa_cv_groups_top).  Rank 0 of every
+    size is ``ls_spa_best_subsets_cv(groups=)``'s winner, bit for bit.  K calls of ``ls_spa_top_group_subsets`` could
+    not be merged into this: a set that is 17th in every fold can be first in the sum.
+
+    groups:  one label per column as ``ls_spa_cv(groups=)`` takes them: k in 0 .. g-1 puts the column into group k, -1
+        into the baseline that every model contains.  There is no ``include=``: the baseline is the include set.
+    folds, seed, shuffle:  as for ``ls_spa_cv``.   n_best:  as for ``ls_spa_top_group_subsets``.
+
+    Returns ``TopGroupSubsetsCVResults``: the fields of ``TopGroupSubsetsResults`` with the cross-validated value --
+    ``sizes`` 0 .. g (size 0 is the baseline alone), ``n_models`` [n], ``group_subsets`` [n][n_best][g] bool, ``subsets``
+    [n][n_best][p] bool (the baseline's and the listed groups' columns), ``n_columns``, ``r_squared`` [n][n_best],
+    ``theta`` [n][n_best][p] (each listed model refitted on ALL rows on the host in fp64, exactly 0.0 outside its
+    columns), ``gap``, ``top_sizes``, ``top_group_subsets``, ``top_subsets``, ``top_r_squared``, ``best_size``,
+    ``best_group_subset``, ``best_subset``, ``full_r_squared``, ``baseline_r_squared`` -- plus ``fold_r_squared``
+    [n][n_best][K], ``fold_ids`` [N] and the one-standard-error fields of ``ls_spa_top_subsets_cv``, computed the same
+    way from ``fold_r_squared`` alone: ``best_gap``, ``best_gap_std_error``, ``within_one_se``, ``one_se_size``,
+    ``one_se_group_subset`` and ``one_se_subset``.  Ranks past ``n_models`` are NaN (False in the subsets, 0 in
+    ``n_columns``).
+
+    The refusals of ``ls_spa_cv(groups=)`` (shapes, p > 64, folds, a zero y, bad labels, g > 32) and that of ``n_best``
+    come before any GPU work.  A set of groups with a pivot that failed in any fold is no candidate and raises a
+    RuntimeWarning that names the folds.  Not built: a bootstrap of the list."""
+    X, y, ids, K = _cv_data("ls_spa_top_group_subsets_cv", X, y, folds, seed, shuffle, grouped=True)
+    p = X.shape[1]
+    labels, g = group_labels(groups, p)
+    if isinstance(n_best, (bool, np.bool_)) or not isinstance(n_best, (int, np.integer)) \
+            or not 1 <= n_best <= GROUPS_TOP_MAX:
+        raise ValueError(f"n_best must be an integer in 1 .. {GROUPS_TOP_MAX} (got {n_best!r})")
+    T = int(n_best)
+    with _engine_call(_engine, device) as engine:
+        engine.cv_groups_load(X, y, ids, K, reg)
+        try:
+            u, masks, count, u_fold, info = engine.cv_groups_top(labels, T)
+            full, _ = engine.debug_cv_group_values(labels, np.array([(1 << g) - 1], dtype=np.uint64), folds=False)
+        finally:
+            engine.cv_free()
+    _cv_group_verdict(info, stacklevel=2)
+    G, gv = _cv_full_problem(X, y, reg)
+    sizes = np.arange(g + 1)
+    n = g + 1
+    n_models = np.asarray(count).astype(np.int64)
+    group_subsets = np.zeros((n, T, g), dtype=bool)
+    subsets = np.zeros((n, T, p), dtype=bool)
+    r_squared = np.full((n, T), np.nan)
+    fold_r_squared = np.full((n, T, K), np.nan)
+    theta = np.full((n, T, p), np.nan)
+    for k in sizes:
+        for r in range(n_models[k]):
+            group_subsets[k, r] = (int(masks[k, r]) >> np.arange(g)) & 1
+            subsets[k, r] = (labels < 0) | group_subsets[k, r][np.maximum(labels, 0)]
+            r_squared[k, r] = u[k, r]
+            fold_r_squared[k, r] = u_fold[k, r]
+            theta[k, r] = _subset_fit(G, gv, np.nonzero(subsets[k, r])[0])
+    # the best over all sizes lie inside the per-size lists: a merge under the same order, larger value then smaller mask
+    ii, rr = np.nonzero(np.arange(T)[None, :] < n_models[:, None])
+    order = np.lexsort((np.asarray(masks)[ii, rr], -r_squared[ii, rr]))[:T]
+    best_size, best_groups, best_subset = -1, np.zeros(g, dtype=bool), np.zeros(p, dtype=bool)
+    if n_models.any():
+        best_size = int(np.nanargmax(r_squared[:, 0]))      # the first of equal maxima: the smallest size
+        best_groups, best_subset = group_subsets[best_size, 0].copy(), subsets[best_size, 0].copy()
+    best_gap, std_error, within = _one_se_fields(r_squared, fold_r_squared, n_models, best_size)
+    one_se_size, one_se_groups, one_se_subset = -1, np.zeros(g, dtype=bool), np.zeros(p, dtype=bool)
+    if best_size >= 0:
+        one_se_size = int(np.argmax(within[:, 0]))          # the first size that qualifies; best_size's own row does
+        one_se_groups, one_se_subset = group_subsets[one_se_size, 0].copy(), subsets[one_se_size, 0].copy()
+    return TopGroupSubsetsCVResults(sizes=sizes, n_models=n_models, group_subsets=group_subsets, subsets=subsets,
+                                    n_columns=subsets.sum(axis=2), r_squared=r_squared,
+                                    fold_r_squared=fold_r_squared, theta=theta, gap=r_squared[:, :1] - r_squared,
+                                    top_sizes=sizes[ii[order]], top_group_subsets=group_subsets[ii[order], rr[order]],
+                                    top_subsets=subsets[ii[order], rr[order]],
+                                    top_r_squared=r_squared[ii[order], rr[order]], best_size=best_size,
+                                    best_group_subset=best_groups, best_subset=best_subset,
+                                    full_r_squared=float(full[0]), baseline_r_squared=float(r_squared[0, 0]),
+                                    best_gap=best_gap, best_gap_std_error=std_error, within_one_se=within,
+                                    one_se_size=one_se_size, one_se_group_subset=one_se_groups,
+                                    one_se_subset=one_se_subset, fold_ids=ids)
+
+
 def ls_spa_top_subsets_cv(X, y, reg=0., folds=5, n_best=10, *, include=None, seed=42, shuffle=True, device=0,
                           _engine=None):
     """The ``n_best`` best models of every size by the K-fold cross-validated R^2, over all 2^p feature subsets
@@ -1727,8 +1816,8 @@ def ls_spa_top_subsets_cv(X, y, reg=0., folds=5, n_best=10, *, include=None, see
 
     The refusals of ``ls_spa_cv`` and those of ``n_best`` and ``include`` come before any GPU work.  A subset with a
     pivot that failed in any fold is no candidate and raises a RuntimeWarning that names the folds.  There is no
-    ``groups=``: top lists of the cross-validated value over groups of columns are not built.  Neither is a bootstrap
-    of the list."""
+    ``groups=``: top lists of the cross-validated value over groups of columns (a one-hot factor, a spline basis; more
+    than 32 columns) are a call of their own, ``ls_spa_top_group_subsets_cv``.  Not built: a bootstrap of the list."""
     X, y, ids, K = _cv_data("ls_spa_top_subsets_cv", X, y, folds, seed, shuffle)
     p = X.shape[1]
     if isinstance(n_best, (bool, np.bool_)) or not isinstance(n_best, (int, np.integer)) \

@@ -260,6 +260,24 @@ def debug_cv_groups_plan(labels, folds: int):
     return dict(zip(CV_GROUPS_PLAN_FIELDS, (int(v) for v in out)))
 
 
+CV_GROUPS_TOP_PLAN_FIELDS = ("gl", "gh", "ql", "nb", "units", "per", "steps", "launches", "lds_bytes", "workgroup",
+                             "sizes", "table_bytes")
+
+
+def debug_cv_groups_top_plan(labels, folds: int, n_best: int):
+    """Test hook, host only: how cv_groups_top enumerates the group game of these labels over `folds` fold problems for
+    n_best models a size (include/lsspa.h, lsspa_debug_cv_groups_top_plan) -- a dict with CV_GROUPS_TOP_PLAN_FIELDS.
+    ValueError for labels, a number of folds or an n_best the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(12, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_groups_top_plan(N.iptr(labels), len(labels), g, int(folds), int(n_best),
+                                                 out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_groups_top_plan: status {rc}")
+    return dict(zip(CV_GROUPS_TOP_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -843,7 +861,24 @@ class HipEngine:
             N.dptr(u_fold)))
         return u, u_fold
 
+    def cv_groups_top(self, labels, n_best=10, steps: int = 0):
+        """(u [g + 1][n_best], masks [g + 1][n_best] uint32 (bit k = group k), count [g + 1] int32,
+        u_fold [g + 1][n_best][K], info [K]): the n_best <= 16 best sets of groups of every size 0 .. g by the
+        cross-validated value, best first -- the larger value, on equal values the smaller mask (include/lsspa.h,
+        lsspa_cv_groups_top); NaN / 0 past count.  Rank 0 is cv_groups_best's.  steps as in cv_groups_best.
+        cv_timing() then speaks of this call."""
+        labels, g, K = self._cv_labels(labels)
+        n, T = max(g, 0) + 1, int(n_best)
+        u, masks = np.empty((n, max(T, 0))), np.empty((n, max(T, 0)), dtype=np.uint32)
+        count = np.empty(n, dtype=np.int32)
+        u_fold, info = np.empty((n, max(T, 0), K)), np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_groups_top(
+            self._h, N.iptr(labels), g, T, int(steps), N.dptr(u), masks.ctypes.data_as(C.POINTER(C.c_uint32)),
+            count.ctypes.data_as(C.POINTER(C.c_int32)), N.dptr(u_fold), N.iptr(info)))
+        return u, masks, count, u_fold, info
+
     debug_cv_groups_plan = staticmethod(debug_cv_groups_plan)
+    debug_cv_groups_top_plan = staticmethod(debug_cv_groups_top_plan)
 
     # ---- exact attribution of many responses at once (p <= 32; over groups g <= 32, p <= 64) ----
     MULTI_RB = 8      # responses a wave carries per pass (csrc/kernels.h)

@@ -173,6 +173,8 @@ SIGNATURES = {
                                        _pi32]),
     "lsspa_debug_cv_group_values": (C.c_int, [_vp, _pi32, _i32, C.POINTER(C.c_uint64), _i64, _pd, _pd]),
     "lsspa_debug_cv_groups_plan": (C.c_int, [_pi32, _i32, _i32, _i32, _pi64]),
+    "lsspa_cv_groups_top": (C.c_int, [_vp, _pi32, _i32, _i32, _i64, _pd, C.POINTER(C.c_uint32), _pi32, _pd, _pi32]),
+    "lsspa_debug_cv_groups_top_plan": (C.c_int, [_pi32, _i32, _i32, _i32, _i32, _pi64]),
     "lsspa_multi_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _dbl, _i32,
                                    _i32]),
     "lsspa_multi_set_reduced": (C.c_int, [_vp, _i32, _i32, _pd, _pd, _pd, _pd, _pd]),

@@ -1033,3 +1033,75 @@ class CVBestGroupSubsetsResults:
             pad,
         ]
         return "\n".join(lines)
+
+
+@dataclass
+class TopGroupSubsetsCVResults:
+    """What ``ls_spa_top_group_subsets_cv`` returns for g groups of p columns, K folds, n = g + 1 sizes and
+    T = n_best ranks: the fields of ``TopGroupSubsetsResults`` with the K-fold cross-validated R^2 as the value.
+    ``sizes`` [n]: 0 .. g (size 0 is the baseline alone); ``n_models`` [n]: the valid ranks of a size;
+    ``group_subsets`` [n][T][g] bool: rank r of size i, best first -- the larger value, on equal values the set with the
+    smaller mask (bit k = group k); ``subsets`` [n][T][p] bool: its columns, the baseline's and its groups';
+    ``n_columns`` [n][T]; ``r_squared`` [n][T]; ``fold_r_squared`` [n][T][K]: its per-fold values, whose sum in
+    ascending fold order it is; ``theta`` [n][T][p]: the model refitted on ALL rows, exactly 0.0 outside its columns;
+    ``gap`` [n][T]: ``r_squared[:, :1] - r_squared``; ``top_sizes``, ``top_group_subsets``, ``top_subsets``,
+    ``top_r_squared``: the min(T, all valid ranks) best models over all sizes; ``best_size``, ``best_group_subset``,
+    ``best_subset``, ``full_r_squared``, ``baseline_r_squared``: ``ls_spa_best_subsets_cv(groups=)``'s; ``fold_ids``
+    [N].  Ranks past ``n_models`` are NaN (False in the subsets and ``within_one_se``, 0 in ``n_columns``).
+
+    ``best_gap``, ``best_gap_std_error``, ``within_one_se`` [n][T], ``one_se_size`` and ``one_se_subset`` are those of
+    ``TopSubsetsCVResults``, against the overall best model (rank 0 of ``best_size``) from ``fold_r_squared`` alone;
+    ``one_se_group_subset`` [g] bool: the groups of that size's rank 0.  The usual one-standard-error heuristic, not a
+    test."""
+    sizes: np.ndarray
+    n_models: np.ndarray
+    group_subsets: np.ndarray
+    subsets: np.ndarray
+    n_columns: np.ndarray
+    r_squared: np.ndarray
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    gap: np.ndarray
+    top_sizes: np.ndarray
+    top_group_subsets: np.ndarray
+    top_subsets: np.ndarray
+    top_r_squared: np.ndarray
+    best_size: int
+    best_group_subset: np.ndarray
+    best_subset: np.ndarray
+    full_r_squared: float
+    baseline_r_squared: float
+    best_gap: np.ndarray
+    best_gap_std_error: np.ndarray
+    within_one_se: np.ndarray
+    one_se_size: int
+    one_se_group_subset: np.ndarray
+    one_se_subset: np.ndarray
+    fold_ids: np.ndarray
+
+    def __repr__(self):
+        pad = " " * 8
+        n, T, g = np.asarray(self.group_subsets).shape
+        p = np.asarray(self.subsets).shape[2]
+        K = np.asarray(self.fold_r_squared).shape[2]
+        chosen = ", ".join(str(k) for k in np.nonzero(self.best_group_subset)[0][:12])
+        best = runner = "nan"
+        if self.best_size >= 0:
+            best = f"{float(self.top_r_squared[0]):.2e}"
+        if len(self.top_r_squared) > 1:
+            runner = f"{float(self.top_r_squared[0] - self.top_r_squared[1]):.2e}"
+        lines = [
+            "",
+            f"{pad}g = {g} groups of p = {p} columns, {K}-fold cross-validation, the {T} best sets of groups of sizes "
+            f"0 .. {n - 1}",
+            f"{pad}Cross-validated R^2 with all groups: {self.full_r_squared:.2e} (baseline alone: "
+            f"{self.baseline_r_squared:.2e})",
+            f"{pad}Best model: {self.best_size} groups ({int(np.sum(self.best_subset))} columns), cross-validated R^2 "
+            f"{best}",
+            f"{pad}Its groups: ({chosen}{', ...' if int(np.sum(self.best_group_subset)) > 12 else ''})",
+            f"{pad}The next model over all sizes is worse by {runner}",
+            f"{pad}Smallest size within one standard error of the best: {self.one_se_size}; listed models within it: "
+            f"{int(np.sum(self.within_one_se))}",
+            pad,
+        ]
+        return "\n".join(lines)
