@@ -563,6 +563,52 @@ int lsspa_cv_groups_top(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t
 int lsspa_debug_cv_groups_top_plan(const int32_t* labels /* [p] */, int32_t p, int32_t g, int32_t K, int32_t T,
                                    int64_t* plan /* [12] */);
 
+/* The RIDGE PATH of the K-fold CV attribution: lsspa_cv_shapley / lsspa_cv_groups_shapley for L ridge values on one
+ * load.  reg enters a fold problem only as + reg on the diagonal of G_f, and the load keeps the per-fold Grams: the
+ * L K fold problems are written from them on the device and enumerated as replicates of shared grids, a block of ridge
+ * values at a time.  The load's own reg plays no part, and the loaded fold problems are not overwritten: the path has
+ * buffers of its own.
+ *   lsspa_cv_path_shapley : after lsspa_cv_load (or lsspa_cv_groups_load of p <= 32 columns).  regs [L] on the host,
+ *                     1 <= L <= 256, every value finite and >= 0.  Row l of phi [L][p], phi_fold [L][K][p], r2_fold
+ *                     [L][K] and info [L][K] is what lsspa_cv_shapley returns after a load of the same rows with
+ *                     reg = regs[l].
+ *   lsspa_cv_path_groups_shapley : the same after either load over the groups of labels / g (lsspa_cv_groups_shapley's
+ *                     limits and messages), with base_fold [L][K].
+ *   GUARANTEE: row l of every output has exactly the bits that lsspa_cv_shapley (lsspa_cv_groups_shapley) returns after
+ *                     a load of the same rows with reg = regs[l], whatever L, block and the position of l in regs:
+ *                     G_{l,f} is formed by the load's expressions in the load's order, a problem is cut into launches
+ *                     as those calls cut a fold, and a replicate's result does not depend on the replicates beside it.
+ *                     After the call lsspa_cv_shapley and every other call on the loaded folds still answer for the
+ *                     load's own reg, bit for bit.  No floating-point atomics: two calls agree bitwise.
+ *   block           : 0: as many ridge values a block as keep its problems within 64 MiB; > 0: that many (test hook:
+ *                     the result does not depend on it).  As many of a block's replicates share a launch as the bound
+ *                     of lsspa_subsets_shapley (2^20 subsets a launch) or lsspa_groups_shapley leaves.
+ *   Refusals, in this order and before any launch (the loaded folds stay usable): nothing loaded, and for the column
+ *                     call a load of more than 32 columns (LSSPA_ERR_STATE); a NULL pointer, L outside 1 .. 256,
+ *                     block < 0, a ridge value that is negative or not finite (the message names it), the labels
+ *                     (LSSPA_ERR_ARG).
+ *   lsspa_cv_timing afterwards reports the path's enumeration launches; nothing else of the context changes.
+ *   lsspa_debug_cv_path_plan, lsspa_debug_cv_path_groups_plan : host only, no context, no GPU.  plan [8] = units, per,
+ *                     steps of a launch (one problem's cut), ridge values a block, blocks, replicates of a launch of a
+ *                     full block, enumeration launches of the L values, and the bound replicates x units x steps stays
+ *                     within; the grouped plan [12] has gl, gh, ql, nb in front of them.  A p, K, L, block or labels
+ *                     that the calls refuse: LSSPA_ERR_ARG.
+ * Measured on one MI355X (tools/cv_path_time.py, on top of commit 421be8d; N = 10^4, K = 5, L = 32): the path's
+ * enumeration launches against 32 x lsspa_cv_shapley's take 0.28 x at p = 12, 0.88 x at p = 16, 0.965 x at p = 20,
+ * 0.95 x at (g, p) = (12, 64) and 0.995 x at (16, 48); the whole ls_spa_cv_path call against the loop of 32 ls_spa_cv
+ * calls 0.19 x, 0.30 x, 0.65 x, 0.62 x and 0.80 x (DESIGN.md has the tables).
+ * Not built: a path of the selection and top-list calls (L calls on re-finalised folds would serve them). */
+int lsspa_cv_path_shapley(lsspa_ctx* ctx, const double* regs /* [L] host */, int32_t L, int32_t block,
+                          double* phi /* [L][p] */, double* phi_fold /* [L][K][p] */, double* r2_fold /* [L][K] */,
+                          int32_t* info /* [L][K] */);
+int lsspa_cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels /* [p] */, int32_t g,
+                                 const double* regs /* [L] host */, int32_t L, int32_t block, double* phi /* [L][g] */,
+                                 double* phi_fold /* [L][K][g] */, double* r2_fold /* [L][K] */,
+                                 double* base_fold /* [L][K] */, int32_t* info /* [L][K] */);
+int lsspa_debug_cv_path_plan(int32_t p, int32_t K, int32_t L, int32_t block, int64_t* plan /* [8] */);
+int lsspa_debug_cv_path_groups_plan(const int32_t* labels /* [p] */, int32_t p, int32_t g, int32_t K, int32_t L,
+                                    int32_t block, int64_t* plan /* [12] */);
+
 /* Exact attribution of MANY RESPONSES at once (p <= 32): one design matrix, m targets.  Row r of phi is what
  * lsspa_subsets_shapley gives for response r alone (to rounding: ~1e-13), but the rows of X are reduced once and the
  * 2^p subsets are enumerated once for every 8 responses: a wave sweeps a high subset's pivots out of [G | g_r ...] with

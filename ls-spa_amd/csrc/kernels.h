@@ -516,6 +516,20 @@ size_t groups_cv_top_lds_bytes();  // static LDS of a workgroup of launch_groups
 // numbering; gid: GroupLayout::gid), phi[k] = their sum over f in ascending order
 hipError_t launch_cv_groups_foldsum(const double* out, int ng, int folds, const int* gid, double* phi_fold, double* phi,
                                     hipStream_t st);
+// The ridge path (lsspa_cv_path_shapley, lsspa_cv_path_groups_shapley): launch_cv_finalize for a block of nl ridge
+// values regs [nl] (device) on the same S and nf.  Problem (l, f) is replicate l folds + f of G, g, H, h and inv_yy
+// ([nl folds]...), and G of it has the bits launch_cv_finalize writes for fold f with reg = regs[l]; H, h and inv_yy of
+// fold f are repeated in every l (the replicate layout has one stride).  Grid (fold, ridge value), no atomics.
+constexpr int CV_PATH_MAX_REGS = 256;
+hipError_t launch_cv_path_finalize(const double* S, const int32_t* nf, const double* regs, int nl, int64_t n, int p,
+                                   int folds, double* G, double* g, double* H, double* h, double* inv_yy,
+                                   hipStream_t st);
+// launch_cv_foldsum / launch_cv_groups_foldsum for nl ridge values: out [nl][folds][cols], phi_fold [nl][folds][.],
+// phi [nl][.]; row l is what the one-value launch gives on out + l folds cols
+hipError_t launch_cv_path_foldsum(const double* out, int p, int folds, int nl, double* phi_fold, double* phi,
+                                  hipStream_t st);
+hipError_t launch_cv_path_groups_foldsum(const double* out, int ng, int folds, int nl, const int* gid, double* phi_fold,
+                                         double* phi, hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

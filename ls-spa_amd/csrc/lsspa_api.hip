@@ -118,11 +118,25 @@ struct CvWork {
                                            // result's
   double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
+  // The ridge path's own (lsspa_cv_path_shapley, lsspa_cv_path_groups_shapley): the problems of a block of ridge values
+  // [Lb K]..., written from S, and everything its launches write.  Of the above it reads S, nf, w (gw, tab: uploaded by
+  // every grouped call) and writes the timing.
+  struct Path {
+    DevBuf<double> regs, G, g, H, h, inv_yy; // [Lb] ridge values; the problems (l, f), l-major
+    DevBuf<double> part, out, phi, vals;     // partial table, its sums [Lb K][cols], phi_fold | phi, the full masks' values
+    DevBuf<uint64_t> masks;
+    DevBuf<int32_t> info, dinfo;             // [Lb K] info words of the enumeration; the values' own
+    void release() {
+      dev_free(regs); dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(part);
+      dev_free(out); dev_free(phi); dev_free(vals); dev_free(masks); dev_free(info); dev_free(dinfo);
+    }
+  } path;
   void release() {
     dev_free(Z); dev_free(stage_x); dev_free(stage_y); dev_free(fid); dev_free(nf); dev_free(wt); dev_free(gpart);
     dev_free(S); dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(w); dev_free(part);
     dev_free(out); dev_free(phi); dev_free(vals); dev_free(masks); dev_free(info); dev_free(dinfo); dev_free(best);
     dev_free(gw); dev_free(tab);
+    path.release();
     loaded = false;
   }
 };
@@ -5910,6 +5924,295 @@ int lsspa_debug_cv_top_plan(int32_t p, int32_t K, int32_t T, int64_t* plan) try 
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_NOMEM;
+}
+
+}  // extern "C"
+
+// ---- the ridge path of the K-fold CV attribution (lsspa_cv_path_*; the path kernels of k_cv.hip) ---------------------
+// reg enters a fold problem only as + reg on the diagonal of G_f, and the load keeps the per-fold Grams S: L ridge values
+// are L K fold problems written from S on the device (launch_cv_path_finalize) and enumerated as replicates of shared
+// grids, a block of ridge values at a time.  A problem is cut into launches exactly as cv_shapley / cv_groups_shapley
+// cut a fold (the cut of `per` shows in the bits) and a replicate's result does not depend on the replicates beside it,
+// so row l has the bits of a load with reg = regs[l].  Everything the path writes is CvWork::Path's.
+namespace {
+
+constexpr size_t CV_PATH_BLOCK_BYTES = 64ull << 20;   // the problems of a block of ridge values stay inside this
+
+struct CvPathPlan {
+  uint64_t units, per, steps;   // one problem's cut: that of cv_shapley / cv_groups_shapley
+  uint64_t bound, room;         // subsets a launch takes over its units, steps and replicates; replicates that leaves
+  int block, blocks, reps;      // ridge values a block; blocks of L values; replicates of a launch of a full block
+  uint64_t launches;            // enumeration launches of the L values
+};
+// n_high high subsets of a problem, `steps` of every unit a launch of one problem, at most `bound` subsets a launch;
+// forced > 0: that many ridge values a block (test hook; cut to L)
+CvPathPlan cv_path_plan(uint64_t n_high, uint64_t steps, uint64_t bound, int p, int K, int L, int forced) {
+  CvPathPlan P;
+  P.units = exact_units(n_high);
+  P.per = n_high / P.units;
+  P.steps = std::min(P.per, steps);
+  P.bound = bound;
+  P.room = std::max<uint64_t>(1, bound / (P.units * P.steps));
+  const size_t problem = sizeof(double) * (2 * (size_t)p * p + 2 * (size_t)p + 1) * (size_t)K;
+  P.block = forced > 0 ? forced : (int)std::max<size_t>(1, CV_PATH_BLOCK_BYTES / problem);
+  P.block = std::min(P.block, L);
+  P.blocks = (L + P.block - 1) / P.block;
+  P.reps = (int)std::min<uint64_t>((uint64_t)P.block * K, P.room);
+  P.launches = 0;
+  for (int l0 = 0; l0 < L; l0 += P.block) {
+    const uint64_t n = (uint64_t)std::min(P.block, L - l0) * K, reps = std::min(n, P.room);
+    P.launches += ((n + reps - 1) / reps) * ((P.per + P.steps - 1) / P.steps);
+  }
+  return P;
+}
+CvPathPlan cv_path_columns_plan(int p, int K, int L, int forced) {
+  const uint64_t n_high = 1ull << (p - subsets_low_features(p));
+  return cv_path_plan(n_high, std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / exact_units(n_high)), SUBSETS_PER_LAUNCH, p, K,
+                      L, forced);
+}
+CvPathPlan cv_path_groups_plan(const GroupLayout& G, int K, int L, int forced) {
+  const uint64_t n_high = 1ull << G.gh;
+  return cv_path_plan(n_high, groups_steps(G, exact_units(n_high)), std::min<uint64_t>(1ull << 20, groups_per_launch(G)),
+                      G.p, K, L, forced);
+}
+
+// regs [L], L and block of both entry points
+int cv_path_check(lsspa_ctx* ctx, const char* name, const double* regs, int32_t L, int32_t block) {
+  char msg[200];
+  if (L < 1 || L > CV_PATH_MAX_REGS) {
+    snprintf(msg, sizeof msg, "%s takes 1 .. %d ridge values (L = %d)", name, CV_PATH_MAX_REGS, (int)L);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (block < 0) {
+    snprintf(msg, sizeof msg, "%s: block must be >= 0", name);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  for (int l = 0; l < L; ++l)
+    if (!std::isfinite(regs[l]) || regs[l] < 0.0) {
+      snprintf(msg, sizeof msg, "%s: regs[%d] = %g: a ridge value must be finite and >= 0", name, l, regs[l]);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  return LSSPA_OK;
+}
+
+void cv_path_rep_inv_yy(SubsetArgs& a, const double* inv_yy) { a.inv_yy = inv_yy; }
+void cv_path_rep_inv_yy(GroupArgs& a, const double* inv_yy) { a.inv_yy_rep = inv_yy; }
+
+// a0 with the path's problems from replicate e0 on
+template <typename Args>
+Args cv_path_args(const CvWork& W, const Args& a0, int e0, int32_t* info) {
+  const CvWork::Path& Q = W.path;
+  const size_t p = (size_t)W.p;
+  Args a = a0;
+  a.G = Q.G.ptr + (size_t)e0 * p * p;
+  a.H = Q.H.ptr + (size_t)e0 * p * p;
+  a.g = Q.g.ptr + (size_t)e0 * p;
+  a.h = Q.h.ptr + (size_t)e0 * p;
+  cv_path_rep_inv_yy(a, Q.inv_yy.ptr + e0);
+  a.info = info;
+  return a;
+}
+
+// One block: the problems of the nl ridge values regs (host) into W.path, their enumeration -- launch(a, s0, s1, ne):
+// steps s0 .. s1 - 1 of every unit for the ne replicates behind a -- and the tables' sums into Q.out [nl K][cols].
+// a0: the call's arguments but for the problems' pointers; ev / l: the call's events and launches so far.
+template <typename Args, typename Launch>
+int cv_path_block(lsspa_ctx* ctx, const CvPathPlan& P, int cols, const double* regs, int nl, const Args& a0,
+                  Launch&& launch, std::vector<hipEvent_t>& ev, size_t& l) {
+  CvWork& W = ctx->cv;
+  CvWork::Path& Q = W.path;
+  hipStream_t st = ctx->stream;
+  const int p = W.p, K = W.K, n = nl * K;
+  const size_t pp = (size_t)p * p;
+  const int reps = (int)std::min<uint64_t>((uint64_t)n, P.room);
+  TRY(dev_alloc(ctx, Q.regs, (size_t)nl));
+  TRY(dev_alloc(ctx, Q.G, (size_t)n * pp));
+  TRY(dev_alloc(ctx, Q.H, (size_t)n * pp));
+  TRY(dev_alloc(ctx, Q.g, (size_t)n * p));
+  TRY(dev_alloc(ctx, Q.h, (size_t)n * p));
+  TRY(dev_alloc(ctx, Q.inv_yy, (size_t)n));
+  TRY(dev_alloc(ctx, Q.info, (size_t)n));
+  TRY(dev_alloc(ctx, Q.part, (size_t)reps * P.units * cols));
+  TRY(dev_alloc(ctx, Q.out, (size_t)n * cols));
+  HIPCHK(hipStreamSynchronize(st));            // the copy is from the caller's array; a block before this one is done
+  HIPCHK(hipMemcpy(Q.regs.ptr, regs, sizeof(double) * nl, hipMemcpyHostToDevice));
+  HIPCHK(launch_cv_path_finalize(W.S.ptr, W.nf.ptr, Q.regs.ptr, nl, W.n, p, K, Q.G.ptr, Q.g.ptr, Q.H.ptr, Q.h.ptr,
+                                 Q.inv_yy.ptr, st));
+  HIPCHK(hipMemsetAsync(Q.info.ptr, 0, sizeof(int32_t) * n, st));
+  for (int e0 = 0; e0 < n; e0 += reps) {
+    const int ne = std::min(reps, n - e0);
+    HIPCHK(hipMemsetAsync(Q.part.ptr, 0, sizeof(double) * (size_t)ne * P.units * cols, st));
+    Args a = cv_path_args(W, a0, e0, Q.info.ptr + e0);
+    a.per = P.per;
+    a.part = Q.part.ptr;
+    for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
+      HIPCHK(hipEventRecord(ev[2 * l], st));
+      HIPCHK(launch(a, s0, std::min(P.per, s0 + P.steps), ne));
+      HIPCHK(hipEventRecord(ev[2 * l + 1], st));
+    }
+    HIPCHK(launch_subsets_reduce(Q.part.ptr, (int64_t)P.units, cols, Q.out.ptr + (size_t)e0 * cols, st, ne));
+  }
+  return LSSPA_OK;
+}
+
+int cv_path_shapley(lsspa_ctx* ctx, const double* regs, int L, int block, double* phi, double* phi_fold,
+                    double* r2_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  CvWork::Path& Q = W.path;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int p = W.p, K = W.K, cols = p + 1;
+  const CvPathPlan P = cv_path_columns_plan(p, K, L, block);
+  std::vector<hipEvent_t> ev(2 * (size_t)P.launches, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  const SubsetArgs a0 = cv_subset_args(W, 0, W.info.ptr);    // p, q, the weights and the pivot test
+  const uint64_t full = (1ull << p) - 1ull;                   // p <= 32
+  TRY(dev_alloc(ctx, Q.masks, 1));
+  TRY(dev_alloc(ctx, Q.dinfo, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, Q.phi, (size_t)P.block * (K + 1) * p));
+  TRY(dev_alloc(ctx, Q.vals, (size_t)P.block * (K + 1)));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(Q.masks.ptr, &full, sizeof full, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(Q.dinfo.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  size_t l = 0;
+  for (int l0 = 0; l0 < L; l0 += P.block) {
+    const int nl = std::min(P.block, L - l0);
+    TRY(cv_path_block(ctx, P, cols, regs + l0, nl, a0,
+                      [&](const SubsetArgs& a, uint64_t s0, uint64_t s1, int ne) {
+                        return launch_subsets_enum(a, P.units, s0, s1, false, st, ne);
+                      },
+                      ev, l));
+    double* fold = Q.phi.ptr;
+    double* sum = Q.phi.ptr + (size_t)nl * K * p;
+    HIPCHK(launch_cv_path_foldsum(Q.out.ptr, p, K, nl, fold, sum, st));
+    // each fold's share of the R^2 of the full model, ridge value by ridge value: cv_values on the path's problems
+    for (int i = 0; i < nl; ++i) {
+      SubsetArgs a = cv_path_args(W, a0, i * K, Q.dinfo.ptr);
+      a.per = 1;
+      double* v = Q.vals.ptr + (size_t)i * (K + 1);
+      HIPCHK(launch_subsets_cv_debug(a, K, Q.masks.ptr, 1, v, v + 1, st));
+    }
+    HIPCHK(hipMemcpyAsync(phi_fold + (size_t)l0 * K * p, fold, sizeof(double) * nl * K * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(phi + (size_t)l0 * p, sum, sizeof(double) * nl * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info + (size_t)l0 * K, Q.info.ptr, sizeof(int32_t) * nl * K, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpy2DAsync(r2_fold + (size_t)l0 * K, sizeof(double) * K, Q.vals.ptr + 1, sizeof(double) * (K + 1),
+                            sizeof(double) * K, (size_t)nl, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return cv_enum_timing(ctx, ev, l);
+}
+
+int cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const double* regs, int L, int block,
+                           double* phi, double* phi_fold, double* r2_fold, double* base_fold, int32_t* info) {
+  CvWork& W = ctx->cv;
+  CvWork::Path& Q = W.path;
+  GroupLayout G;
+  TRY(cv_layout(ctx, labels, g, G));
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(cv_groups_upload(ctx, G));
+  hipStream_t st = ctx->stream;
+  const int K = W.K, ng = G.ng, cols = ng + 1;
+  const CvPathPlan P = cv_path_groups_plan(G, K, L, block);
+  std::vector<hipEvent_t> ev(2 * (size_t)P.launches, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  const GroupArgs a0 = cv_group_args(W, G, 0, W.info.ptr);   // the layout, the weights, the table and the pivot test
+  // all groups and the baseline alone (the same mask in the layout's numbering and the caller's)
+  const uint64_t both[2] = {ng < 64 ? (1ull << ng) - 1ull : ~0ull, 0ull};
+  const size_t vs = 2 * (size_t)(K + 1);                      // a ridge value's values: u [2], u_fold [2][K]
+  TRY(dev_alloc(ctx, Q.masks, 2));
+  TRY(dev_alloc(ctx, Q.dinfo, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, Q.phi, (size_t)P.block * (K + 1) * ng));
+  TRY(dev_alloc(ctx, Q.vals, (size_t)P.block * vs));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(Q.masks.ptr, both, sizeof both, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(Q.dinfo.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  size_t l = 0;
+  for (int l0 = 0; l0 < L; l0 += P.block) {
+    const int nl = std::min(P.block, L - l0);
+    TRY(cv_path_block(ctx, P, cols, regs + l0, nl, a0,
+                      [&](const GroupArgs& a, uint64_t s0, uint64_t s1, int ne) {
+                        return launch_groups_enum(a, P.units, s0, s1, false, st, ne);
+                      },
+                      ev, l));
+    double* fold = Q.phi.ptr;
+    double* sum = Q.phi.ptr + (size_t)nl * K * ng;
+    HIPCHK(launch_cv_path_groups_foldsum(Q.out.ptr, ng, K, nl, G.gid, fold, sum, st));
+    for (int i = 0; i < nl; ++i) {
+      GroupArgs a = cv_path_args(W, a0, i * K, Q.dinfo.ptr);
+      a.per = 1;
+      double* u = Q.vals.ptr + (size_t)i * vs;
+      HIPCHK(launch_groups_cv_debug(a, K, Q.masks.ptr, 2, u, u + 2, st));
+    }
+    HIPCHK(hipMemcpyAsync(phi_fold + (size_t)l0 * K * ng, fold, sizeof(double) * nl * K * ng, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(phi + (size_t)l0 * ng, sum, sizeof(double) * nl * ng, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info + (size_t)l0 * K, Q.info.ptr, sizeof(int32_t) * nl * K, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpy2DAsync(r2_fold + (size_t)l0 * K, sizeof(double) * K, Q.vals.ptr + 2, sizeof(double) * vs,
+                            sizeof(double) * K, (size_t)nl, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpy2DAsync(base_fold + (size_t)l0 * K, sizeof(double) * K, Q.vals.ptr + 2 + K, sizeof(double) * vs,
+                            sizeof(double) * K, (size_t)nl, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return cv_enum_timing(ctx, ev, l);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_cv_path_shapley(lsspa_ctx* ctx, const double* regs, int32_t L, int32_t block, double* phi, double* phi_fold,
+                          double* r2_fold, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  TRY(cv_need_columns(ctx, "lsspa_cv_path_shapley"));
+  if (!regs || !phi || !phi_fold || !r2_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_path_shapley: regs / phi / phi_fold / r2_fold / info is NULL");
+  TRY(cv_path_check(ctx, "lsspa_cv_path_shapley", regs, L, block));
+  return cv_path_shapley(ctx, regs, L, block, phi, phi_fold, r2_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const double* regs, int32_t L,
+                                 int32_t block, double* phi, double* phi_fold, double* r2_fold, double* base_fold,
+                                 int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cv_need_loaded(ctx));
+  if (!labels || !regs || !phi || !phi_fold || !r2_fold || !base_fold || !info)
+    return ctx->fail(LSSPA_ERR_ARG,
+                     "lsspa_cv_path_groups_shapley: labels / regs / phi / phi_fold / r2_fold / base_fold / info is NULL");
+  TRY(cv_path_check(ctx, "lsspa_cv_path_groups_shapley", regs, L, block));
+  return cv_path_groups_shapley(ctx, labels, g, regs, L, block, phi, phi_fold, r2_fold, base_fold, info);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_path_plan(int32_t p, int32_t K, int32_t L, int32_t block, int64_t* plan) try {
+  if (!plan || p < 1 || p > SUBSETS_MAX_P || K < 2 || K > CV_MAX_FOLDS || L < 1 || L > CV_PATH_MAX_REGS || block < 0)
+    return LSSPA_ERR_ARG;
+  const CvPathPlan P = cv_path_columns_plan(p, K, L, block);
+  const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, P.block, P.blocks, P.reps,
+                          (int64_t)P.launches, (int64_t)P.bound};
+  std::copy(out, out + 8, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
+}
+
+int lsspa_debug_cv_path_groups_plan(const int32_t* labels, int32_t p, int32_t g, int32_t K, int32_t L, int32_t block,
+                                    int64_t* plan) try {
+  GroupLayout G;
+  if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || K < 2 || K > CV_MAX_FOLDS || L < 1 || L > CV_PATH_MAX_REGS ||
+      block < 0 || groups_layout(labels, p, g, G))
+    return LSSPA_ERR_ARG;
+  const CvPathPlan P = cv_path_groups_plan(G, K, L, block);
+  const int64_t out[12] = {G.gl, G.gh, G.ql, G.nb, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, P.block, P.blocks,
+                           P.reps, (int64_t)P.launches, (int64_t)P.bound};
+  std::copy(out, out + 12, plan);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_ARG;
 }
 
 }  // extern "C"

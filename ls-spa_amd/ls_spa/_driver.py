@@ -31,7 +31,8 @@ import numpy as np
 
 from . import _samplers as S
 from ._native import LSSPANativeError
-from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupResults, CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupPathResults, CVGroupResults, CVPathResults,
+                       CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults,
@@ -1526,6 +1527,133 @@ def ls_spa_cv(X, y, reg=0., folds=5, *, groups=None, seed=42, shuffle=True, devi
     G, g = _cv_full_problem(X, y, reg)
     return CVResults(attribution=phi, fold_attribution=phi_fold, r_squared=float(_seq_sum(list(r2_fold))),
                      fold_r_squared=np.asarray(r2_fold), theta=_subset_fit(G, g, np.arange(X.shape[1])), fold_ids=ids)
+
+
+CV_PATH_MAX_REGS = 256     # include/lsspa.h, lsspa_cv_path_shapley
+
+
+def _cv_path_regs(regs):
+    """The ridge values of ``ls_spa_cv_path`` as a float64 array [L], or the ValueError that names what is wrong."""
+    try:
+        r = np.asarray(regs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("regs must be a one-dimensional sequence of numbers") from None
+    if r.ndim != 1:
+        raise ValueError(f"regs must be one-dimensional (got {r.ndim} dimensions)")
+    if not 1 <= r.shape[0] <= CV_PATH_MAX_REGS:
+        raise ValueError(f"ls_spa_cv_path takes 1 .. {CV_PATH_MAX_REGS} ridge values (got {r.shape[0]})")
+    bad = np.nonzero(~np.isfinite(r) | (r < 0))[0]
+    if len(bad):
+        raise ValueError(f"regs[{int(bad[0])}] = {float(r[bad[0]])!r}: a ridge value must be finite and >= 0")
+    return np.ascontiguousarray(r)
+
+
+def _cv_path_verdict(info, regs, what, stacklevel):
+    """_cv_verdict / _cv_group_verdict for a path: the RuntimeWarning names the ridge values and, for each, the folds.
+    what: the words of the one-value warning for what is no candidate."""
+    info = np.asarray(info)
+    rows = [l for l in range(info.shape[0]) if (info[l] & 1).any()]
+    if rows:
+        named = "; ".join(f"ridge value {regs[l]:g} (regs[{l}]): fold(s) "
+                          f"{', '.join(str(int(f)) for f in np.nonzero(info[l] & 1)[0])}" for l in rows)
+        warnings.warn(f"a Gram matrix of the training rows was not numerically positive definite at {named}; {what} "
+                      "are no candidates there and their attribution is not meaningful", RuntimeWarning,
+                      stacklevel=stacklevel + 1)
+
+
+def _cv_path_choice(regs, r_squared, fold_r_squared):
+    """(best_index, best_reg, best_gap [L], best_gap_std_error [L], within_one_se [L], one_se_index, one_se_reg) of a
+    path, in fp64 on the host from the per-fold values alone.  The best row: the largest r_squared, on equal values
+    the larger ridge value (then the earlier row), NaN rows skipped; -1 and NaN if there is none.  Against it
+    d_f = fold[best][f] - fold[l][f]: their sum, sqrt(K) std(d, ddof=1), and the largest ridge value whose sum is
+    within that (``ls_spa_top_subsets_cv``'s rule, with the stronger penalty in the place of the smaller model)."""
+    L, K = fold_r_squared.shape
+    best_gap, std_error, within = np.full(L, np.nan), np.full(L, np.nan), np.zeros(L, dtype=bool)
+    valid = np.nonzero(~np.isnan(r_squared))[0]
+    if not len(valid):
+        return -1, float("nan"), best_gap, std_error, within, -1, float("nan")
+    top = valid[r_squared[valid] == r_squared[valid].max()]
+    best = int(top[np.argmax(regs[top])])
+    d = fold_r_squared[best][None, :] - fold_r_squared
+    best_gap[valid] = d.sum(axis=1)[valid]
+    std_error[valid] = (np.sqrt(K) * np.std(d, axis=1, ddof=1))[valid]
+    within[valid] = best_gap[valid] <= std_error[valid]
+    ok = np.nonzero(within)[0]                   # never empty: the best row's gap and error are both 0
+    one_se = int(ok[np.argmax(regs[ok])])
+    return best, float(regs[best]), best_gap, std_error, within, one_se, float(regs[one_se])
+
+
+def ls_spa_cv_path(X, y, regs, folds=5, *, groups=None, seed=42, shuffle=True, device=0, _engine=None):
+    """``ls_spa_cv`` along a path of ridge values: the exact Shapley attribution of the K-fold cross-validated R^2 for
+    every ``regs[l]``, and which of them the folds prefer.
+
+    The cross-validated R^2 and the attribution both move with the ridge parameter -- with collinear columns credit
+    moves between correlated features as it grows -- and none of the other calls helps choose it.  The parameter enters
+    a fold problem only as + reg on the diagonal of its training Gram, so the path is ONE load and ONE weighted Gram
+    pass: the L K fold problems are written from the kept per-fold Grams on the device and enumerated as replicates
+    of shared grids (include/lsspa.h, lsspa_cv_path_shapley).  Row l of every per-value field is what
+    ``ls_spa_cv(X, y, reg=regs[l], ...)`` returns, bit for bit, whatever L and the position of l.
+
+    regs:  1 .. 256 finite ridge values >= 0, in any order (repeats allowed).
+    folds, groups, seed, shuffle:  as for ``ls_spa_cv``.
+
+    Returns ``CVPathResults``: ``regs`` [L] in the caller's order, ``attribution`` [L][p], ``fold_attribution``
+    [L][K][p], ``r_squared`` [L], ``fold_r_squared`` [L][K], ``theta`` [L][p] (each row refitted on all rows on the host
+    in fp64) and ``fold_ids`` [N]; with ``groups=`` ``CVGroupPathResults``: the attributions over the g groups, plus
+    ``baseline_r_squared`` [L] and ``fold_baseline_r_squared`` [L][K] (a row of ``attribution`` sums to ``r_squared -
+    baseline_r_squared``).
+
+    The choice of the parameter, computed on the host in fp64 from ``fold_r_squared`` alone: ``best_index`` /
+    ``best_reg``, the largest ``r_squared`` (on equal values the larger ridge value; NaN rows are skipped); with
+    d_f = fold_r_squared[best][f] - fold_r_squared[l][f] -- paired differences, every fold over the same pooled
+    ||y||^2 -- ``best_gap`` [L] = their sum, ``best_gap_std_error`` [L] = sqrt(K) std(d, ddof=1), ``within_one_se``
+    [L] = best_gap <= best_gap_std_error, and ``one_se_index`` / ``one_se_reg``, the largest ridge value within one
+    standard error of the best (the best itself always is).  K folds are few and their training sets overlap, so the
+    d_f are neither many nor independent: this is the usual one-standard-error heuristic for preferring the stronger
+    penalty, not a test, and no p-value should be read from it.
+
+    The refusals of ``ls_spa_cv`` (of ``ls_spa_cv(groups=)``) and a ``regs`` that is not one-dimensional, has no or
+    more than 256 entries or a negative or non-finite one -- the ValueError names the entry -- come before any GPU
+    work.  A fold problem whose training Gram is not numerically positive definite raises a RuntimeWarning that names
+    the ridge values and their folds; the other rows are not affected.  Not built: a path of the selection and
+    top-list calls, interactions, a bootstrap over the folds."""
+    grouped = groups is not None
+    X, y, ids, K = _cv_data("ls_spa_cv_path", X, y, folds, seed, shuffle, grouped=grouped)
+    p = X.shape[1]
+    if grouped:
+        labels, n_groups = group_labels(groups, p)
+    regs = _cv_path_regs(regs)
+    with _engine_call(_engine, device) as engine:
+        if grouped:
+            engine.cv_groups_load(X, y, ids, K, float(regs[0]))
+        else:
+            engine.cv_load(X, y, ids, K, float(regs[0]))
+        try:
+            if grouped:
+                phi, phi_fold, r2_fold, base_fold, info = engine.cv_path_groups_shapley(labels, regs)
+            else:
+                phi, phi_fold, r2_fold, info = engine.cv_path_shapley(regs)
+        finally:
+            engine.cv_free()
+    _cv_path_verdict(info, regs, "sets of groups with collinear columns" if grouped else
+                     "subsets of collinear features", stacklevel=2)
+    r2_fold = np.asarray(r2_fold)
+    r_squared = np.array([float(_seq_sum(list(row))) for row in r2_fold])
+    theta = np.empty((len(regs), p))
+    for l, r in enumerate(regs):
+        G, g = _cv_full_problem(X, y, float(r))
+        theta[l] = _subset_fit(G, g, np.arange(p))
+    best, best_reg, best_gap, std_error, within, one_se, one_se_reg = _cv_path_choice(regs, r_squared, r2_fold)
+    choice = dict(best_index=best, best_reg=best_reg, best_gap=best_gap, best_gap_std_error=std_error,
+                  within_one_se=within, one_se_index=one_se, one_se_reg=one_se_reg)
+    if grouped:
+        base_fold = np.asarray(base_fold)
+        return CVGroupPathResults(regs=regs, attribution=phi, fold_attribution=phi_fold, r_squared=r_squared,
+                                  fold_r_squared=r2_fold,
+                                  baseline_r_squared=np.array([float(_seq_sum(list(row))) for row in base_fold]),
+                                  fold_baseline_r_squared=base_fold, theta=theta, fold_ids=ids, **choice)
+    return CVPathResults(regs=regs, attribution=phi, fold_attribution=phi_fold, r_squared=r_squared,
+                         fold_r_squared=r2_fold, theta=theta, fold_ids=ids, **choice)
 
 
 def ls_spa_best_subsets_cv(X, y, reg=0., folds=5, *, include=None, groups=None, seed=42, shuffle=True, device=0,

@@ -278,6 +278,37 @@ def debug_cv_groups_top_plan(labels, folds: int, n_best: int):
     return dict(zip(CV_GROUPS_TOP_PLAN_FIELDS, (int(v) for v in out)))
 
 
+CV_PATH_PLAN_FIELDS = ("units", "per", "steps", "block", "blocks", "reps", "launches", "bound")
+
+
+def debug_cv_path_plan(p: int, folds: int, n_regs: int, block: int = 0):
+    """Test hook, host only: how cv_path_shapley runs n_regs ridge values of p features over `folds` fold problems
+    (include/lsspa.h, lsspa_debug_cv_path_plan) -- a dict with CV_PATH_PLAN_FIELDS.  ValueError for arguments the
+    library refuses."""
+    out = np.zeros(8, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_path_plan(int(p), int(folds), int(n_regs), int(block), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_path_plan: status {rc}")
+    return dict(zip(CV_PATH_PLAN_FIELDS, (int(v) for v in out)))
+
+
+CV_PATH_GROUPS_PLAN_FIELDS = ("gl", "gh", "ql", "nb") + CV_PATH_PLAN_FIELDS
+
+
+def debug_cv_path_groups_plan(labels, folds: int, n_regs: int, block: int = 0):
+    """Test hook, host only: how cv_path_groups_shapley runs n_regs ridge values of the group game of these labels over
+    `folds` fold problems (include/lsspa.h, lsspa_debug_cv_path_groups_plan) -- a dict with
+    CV_PATH_GROUPS_PLAN_FIELDS.  ValueError for arguments the library refuses."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    g = int(labels.max()) + 1 if len(labels) else 0
+    out = np.zeros(12, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_path_groups_plan(N.iptr(labels), len(labels), g, int(folds), int(n_regs), int(block),
+                                                  out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_path_groups_plan: status {rc}")
+    return dict(zip(CV_PATH_GROUPS_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def debug_gram_plan(n: int, p: int):
     """Test hook, host only: how a Gram launch of n rows at p features is cut (include/lsspa.h, lsspa_debug_gram_plan) --
     a dict of n_split, nt, xlive and, per unit class A / B / C, cnt, slices and rps (rows per slice)."""
@@ -879,6 +910,38 @@ class HipEngine:
 
     debug_cv_groups_plan = staticmethod(debug_cv_groups_plan)
     debug_cv_groups_top_plan = staticmethod(debug_cv_groups_top_plan)
+
+    # ---- ... the ridge path: L ridge values on one load ----
+    def cv_path_shapley(self, regs, block: int = 0):
+        """(phi [L][p], phi_fold [L][K][p], r2_fold [L][K], info [L][K]): row l is cv_shapley() after a load with
+        reg = regs[l], bit for bit (include/lsspa.h, lsspa_cv_path_shapley).  block > 0: that many ridge values a block
+        (test hook; the result does not depend on it).  cv_timing() then speaks of this call."""
+        p, K = self._cv_pk()
+        regs = np.ascontiguousarray(regs, dtype=np.float64)
+        L = len(regs)
+        phi, fold, r2 = np.empty((L, p)), np.empty((L, K, p)), np.empty((L, K))
+        info = np.zeros((L, K), dtype=np.int32)
+        self._check(self._lib.lsspa_cv_path_shapley(self._h, N.dptr(regs), L, int(block), N.dptr(phi), N.dptr(fold),
+                                                    N.dptr(r2), N.iptr(info)))
+        return phi, fold, r2, info
+
+    def cv_path_groups_shapley(self, labels, regs, block: int = 0):
+        """(phi [L][g], phi_fold [L][K][g], r2_fold [L][K], base_fold [L][K], info [L][K]): row l is
+        cv_groups_shapley(labels) after a load with reg = regs[l], bit for bit (include/lsspa.h,
+        lsspa_cv_path_groups_shapley).  block as in cv_path_shapley."""
+        labels, g, K = self._cv_labels(labels)
+        n = max(g, 1)
+        regs = np.ascontiguousarray(regs, dtype=np.float64)
+        L = len(regs)
+        phi, fold, r2, base = np.empty((L, n)), np.empty((L, K, n)), np.empty((L, K)), np.empty((L, K))
+        info = np.zeros((L, K), dtype=np.int32)
+        self._check(self._lib.lsspa_cv_path_groups_shapley(
+            self._h, N.iptr(labels), g, N.dptr(regs), L, int(block), N.dptr(phi), N.dptr(fold), N.dptr(r2),
+            N.dptr(base), N.iptr(info)))
+        return phi, fold, r2, base, info
+
+    debug_cv_path_plan = staticmethod(debug_cv_path_plan)
+    debug_cv_path_groups_plan = staticmethod(debug_cv_path_groups_plan)
 
     # ---- exact attribution of many responses at once (p <= 32; over groups g <= 32, p <= 64) ----
     MULTI_RB = 8      # responses a wave carries per pass (csrc/kernels.h)

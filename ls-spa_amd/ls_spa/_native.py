@@ -175,6 +175,10 @@ SIGNATURES = {
     "lsspa_debug_cv_groups_plan": (C.c_int, [_pi32, _i32, _i32, _i32, _pi64]),
     "lsspa_cv_groups_top": (C.c_int, [_vp, _pi32, _i32, _i32, _i64, _pd, C.POINTER(C.c_uint32), _pi32, _pd, _pi32]),
     "lsspa_debug_cv_groups_top_plan": (C.c_int, [_pi32, _i32, _i32, _i32, _i32, _pi64]),
+    "lsspa_cv_path_shapley": (C.c_int, [_vp, _pd, _i32, _i32, _pd, _pd, _pd, _pi32]),
+    "lsspa_cv_path_groups_shapley": (C.c_int, [_vp, _pi32, _i32, _pd, _i32, _i32, _pd, _pd, _pd, _pd, _pi32]),
+    "lsspa_debug_cv_path_plan": (C.c_int, [_i32, _i32, _i32, _i32, _pi64]),
+    "lsspa_debug_cv_path_groups_plan": (C.c_int, [_pi32, _i32, _i32, _i32, _i32, _i32, _pi64]),
     "lsspa_multi_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _dbl, _i32,
                                    _i32]),
     "lsspa_multi_set_reduced": (C.c_int, [_vp, _i32, _i32, _pd, _pd, _pd, _pd, _pd]),

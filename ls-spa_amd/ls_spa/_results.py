@@ -994,6 +994,95 @@ class CVGroupResults:
 
 
 @dataclass
+class CVPathResults:
+    """What ``ls_spa_cv_path`` returns for L ridge values, p features, K folds and N rows: row l of every field is
+    ``ls_spa_cv(X, y, reg=regs[l])``'s, bit for bit.  ``regs`` [L]: the ridge values in the caller's order;
+    ``attribution`` [L][p]; ``fold_attribution`` [L][K][p], whose sum over the folds in ascending order it is;
+    ``r_squared`` [L]: the cross-validated R^2 of the full model, what a row of ``attribution`` sums to;
+    ``fold_r_squared`` [L][K]: each fold's share of it; ``theta`` [L][p]: the coefficients fitted on all rows with that
+    ridge value; ``fold_ids`` [N]: the fold of every row.
+
+    ``best_index`` / ``best_reg``: the row of the largest ``r_squared``, on equal values the larger ridge value, NaN
+    rows skipped (-1 / NaN if every row is NaN).  Against that row b, from ``fold_r_squared`` alone, with the paired
+    per-fold differences d_f = fold_r_squared[b][f] - fold_r_squared[l][f]: ``best_gap`` [L] = their sum;
+    ``best_gap_std_error`` [L] = sqrt(K) std(d, ddof=1); ``within_one_se`` [L] = best_gap <= best_gap_std_error (False
+    in a NaN row); ``one_se_index`` / ``one_se_reg``: the largest ridge value within one standard error of the best
+    (``best_index``'s own row always is).  K folds are few and their training sets overlap: this is the usual
+    one-standard-error heuristic for preferring the stronger penalty, not a test."""
+    regs: np.ndarray
+    attribution: np.ndarray
+    fold_attribution: np.ndarray
+    r_squared: np.ndarray
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    fold_ids: np.ndarray
+    best_index: int
+    best_reg: float
+    best_gap: np.ndarray
+    best_gap_std_error: np.ndarray
+    within_one_se: np.ndarray
+    one_se_index: int
+    one_se_reg: float
+
+    def __repr__(self):
+        pad = " " * 8
+        L, p = np.asarray(self.attribution).shape
+        best = f"{float(self.r_squared[self.best_index]):.2e}" if self.best_index >= 0 else "nan"
+        lines = [
+            "",
+            f"{pad}p = {p}, {np.asarray(self.fold_r_squared).shape[1]}-fold cross-validation, {L} ridge values "
+            f"{float(np.min(self.regs)):.2e} .. {float(np.max(self.regs)):.2e}",
+            f"{pad}Best ridge value: {self.best_reg:.2e}, cross-validated R^2 {best}",
+            f"{pad}Largest ridge value within one standard error of it: {self.one_se_reg:.2e}",
+            f"{pad}Attribution at the best: ({_head(self.attribution[self.best_index]) if self.best_index >= 0 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
+class CVGroupPathResults:
+    """What ``ls_spa_cv_path(groups=)`` returns for L ridge values, g groups of p columns and K folds: the fields of
+    ``CVPathResults`` over the groups -- ``attribution`` [L][g], ``fold_attribution`` [L][K][g], row l
+    ``ls_spa_cv(X, y, reg=regs[l], groups=)``'s, bit for bit -- plus ``baseline_r_squared`` [L] (the cross-validated
+    R^2 of the baseline's columns alone; a row of ``attribution`` sums to ``r_squared - baseline_r_squared``) and
+    ``fold_baseline_r_squared`` [L][K].  The choice of the ridge value and the one-standard-error fields are those of
+    ``CVPathResults``, from ``r_squared`` and ``fold_r_squared`` of the full model."""
+    regs: np.ndarray
+    attribution: np.ndarray
+    fold_attribution: np.ndarray
+    r_squared: np.ndarray
+    fold_r_squared: np.ndarray
+    baseline_r_squared: np.ndarray
+    fold_baseline_r_squared: np.ndarray
+    theta: np.ndarray
+    fold_ids: np.ndarray
+    best_index: int
+    best_reg: float
+    best_gap: np.ndarray
+    best_gap_std_error: np.ndarray
+    within_one_se: np.ndarray
+    one_se_index: int
+    one_se_reg: float
+
+    def __repr__(self):
+        pad = " " * 8
+        L, g = np.asarray(self.attribution).shape
+        best = f"{float(self.r_squared[self.best_index]):.2e}" if self.best_index >= 0 else "nan"
+        lines = [
+            "",
+            f"{pad}g = {g} groups of p = {np.asarray(self.theta).shape[1]} columns, "
+            f"{np.asarray(self.fold_r_squared).shape[1]}-fold cross-validation, {L} ridge values "
+            f"{float(np.min(self.regs)):.2e} .. {float(np.max(self.regs)):.2e}",
+            f"{pad}Best ridge value: {self.best_reg:.2e}, cross-validated R^2 {best}",
+            f"{pad}Largest ridge value within one standard error of it: {self.one_se_reg:.2e}",
+            f"{pad}Attribution at the best: ({_head(self.attribution[self.best_index]) if self.best_index >= 0 else ''})",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class CVBestGroupSubsetsResults:
     """What ``ls_spa_best_subsets_cv(groups=)`` returns for g groups of p columns and K folds: the fields of
     ``BestGroupSubsetsResults`` with the K-fold cross-validated R^2 as the value.  ``sizes``: 0 .. g (size 0 is the
