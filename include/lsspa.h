@@ -104,8 +104,9 @@ int lsspa_set_reduced(lsspa_ctx* ctx, int32_t p, const double* G, const double* 
  * Nothing of the sampling path changes: running statistics, history, flags, lanes, per-batch workspace and the info
  * word of lsspa_get_info stay as they were.  The work is split into launches of bounded length; the result is
  * bitwise reproducible (partial sums are added in a fixed order).
- *   lsspa_subsets_timing      : device milliseconds of the last call's enumeration launches, its longest launch and
- *                               the number of launches (any pointer may be NULL)
+ *   lsspa_subsets_timing      : device milliseconds of the last call's enumeration launches (the sum of the launches'
+ *                               own intervals: the gaps between them do not count), its longest launch and the
+ *                               number of launches (any pointer may be NULL)
  *   lsspa_debug_subset_values : test hook -- v[i] = v(masks[i]) (bit j = feature j; masks < 2^p) by the enumeration's
  *                               own device code; a failed pivot is LSSPA_ERR_STATE */
 int lsspa_subsets_shapley(lsspa_ctx* ctx, double* phi, int32_t* info);

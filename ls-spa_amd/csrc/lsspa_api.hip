@@ -50,9 +50,7 @@ struct ExactWork {
   DevBuf<double> Hh, w, part, out, vals;   // rect-mode test Gram, Shapley weights, partial table, its sums, debug values
   DevBuf<uint64_t> masks;                  // the debug values' subsets
   DevBuf<int32_t> info, tab;               // info word; GroupLayout::tab (groups only)
-  DevBuf<uint32_t> best;                   // lsspa_subsets_best: (mask, found) of the units' rows, then of the result;
-                                           // lsspa_subsets_top, lsspa_groups_top: the lists' masks and counts, then
-                                           // the result's
+  DevBuf<uint32_t> best;                   // the selection calls' masks beside part's values (best_run, top_run)
   double kernel_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   void release() {
@@ -113,9 +111,7 @@ struct CvWork {
   DevBuf<int32_t> tab;                     // and their layout table (GroupLayout::tab)
   DevBuf<uint64_t> masks;
   DevBuf<int32_t> info, dinfo;             // [K] info words of a call; the debug values' own
-  DevBuf<uint32_t> best;                   // lsspa_cv_best: (mask, found) of the units' rows, then of the result;
-                                           // lsspa_cv_top, lsspa_cv_groups_top: the lists' masks and counts, then the
-                                           // result's
+  DevBuf<uint32_t> best;                   // the selection calls' masks beside part's values (best_run, top_run)
   double gram_ms = 0.0, enum_ms = 0.0, max_launch_ms = 0.0;
   int64_t launches = 0;
   // The ridge path's own (lsspa_cv_path_shapley, lsspa_cv_path_groups_shapley): the problems of a block of ridge values
@@ -3307,8 +3303,10 @@ int lsspa_debug_factor(lsspa_ctx* ctx, const int32_t* perm, double* L, double* L
 
 // ---- exact attribution by enumeration: the host path that k_subsets.hip and k_groups.hip share ---------------------
 // n players (features, or groups of columns) and 2^n subsets, of which the kernels enumerate the n_high high ones in
-// `units` workgroups of `per` each.  What differs between the two entry points stays with them: their limits, how many
-// steps one launch takes, which kernel runs and where a player's value goes in phi.
+// `units` workgroups of `per` each (EnumCut, which also holds how many steps one launch takes for either kind of
+// player).  What differs between the entry points stays with them: their limits, which kernel runs and where a player's
+// value goes in phi.  The selection calls and the K-fold CV calls go by the same pieces (best_run, top_run,
+// rep_enumerate): a new call supplies its checks and its launcher, nothing else.
 namespace {
 
 // row length of the weight table [2][EXACT_MAX_PLAYERS + 1], which each kernel indexes with its own constant
@@ -3317,11 +3315,85 @@ static_assert(SUBSETS_MAX_P == GROUPS_MAX_G, "the two enumerations share the lay
 constexpr uint64_t EXACT_UNITS = 8192;
 uint64_t exact_units(uint64_t n_high) { return std::min(n_high, EXACT_UNITS); }
 
+// high subsets one enumeration launch of k_subsets.hip takes at most (over all units): ~35 ms of GPU time at p = 32
+// 
+constexpr uint64_t SUBSETS_PER_LAUNCH = 1ull << 20;
+// One enumeration launch of k_groups.hip takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high
+// subset counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
+// subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X (DESIGN.md): far below the bound of
+// 0.2 s, and long enough that the launches' own cost does not show.
+constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
+// high subsets one launch takes at most over all its workgroups on the layout L
+uint64_t groups_per_launch(const GroupLayout& L) {
+  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
+  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
+  return std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
+}
+
+static_assert(((1ull << (GROUPS_MAX_G - 1)) / EXACT_UNITS) <= (1ull << (GROUPS_BEST_CLASSES - 1)),
+              "groups_best_kernel and groups_cv_best_kernel hold the size classes of the largest per: at most 31 high "
+              "groups over EXACT_UNITS units");
+// The cut of an enumeration: n_high high subsets in `units` workgroups of `per` each, `steps` of every unit a launch and
+// so `launches` launches.  K: problems a step of a unit evaluates (the folds of the CV selection kernels), which divides
+// the launch's bound; forced > 0: that many steps a launch instead (test hook).  steps is not cut to per: the launches
+// are the same either way, and the one-problem plan hooks report it so; launch_steps() is what a launch takes.
+struct EnumCut {
+  uint64_t units, per, steps, launches;
+  EnumCut(uint64_t n_high, uint64_t bound, int K, uint64_t forced) {
+    units = exact_units(n_high);
+    per = n_high / units;                                // both powers of two
+    steps = forced ? forced : std::max<uint64_t>(1, bound / (units * (uint64_t)K));
+    launches = (per + steps - 1) / steps;
+  }
+  explicit EnumCut(int p, int K = 1, uint64_t forced = 0)                   // the columns as players (k_subsets.hip)
+      : EnumCut(1ull << (p - subsets_low_features(p)), SUBSETS_PER_LAUNCH, K, forced) {}
+  explicit EnumCut(const GroupLayout& L, int K = 1, uint64_t forced = 0)    // the groups of a layout (k_groups.hip)
+      : EnumCut(1ull << L.gh, groups_per_launch(L), K, forced) {}
+  uint64_t launch_steps() const { return std::min(steps, per); }
+};
+
+// 1 / ||y||^2 of the replicate problems behind a, on the device: k_subsets.hip reads it there for every launch (one
+// problem: one replicate), k_groups.hip for a launch of replicates (one problem: GroupArgs::inv_yy, the value)
+inline void set_inv_yy(SubsetArgs& a, const double* on_device) { a.inv_yy = on_device; }
+inline void set_inv_yy(GroupArgs& a, const double* on_device) { a.inv_yy_rep = on_device; }
+// the relative pivot test of the exact paths (kernels.h, SubsetArgs::piv_tol)
+inline double exact_piv_tol(int p) { return 16.0 * (double)p * 2.220446049250313e-16; }
+// the layout's numbers as the kernels take them
+inline void set_layout(GroupArgs& a, const GroupLayout& L) {
+  a.p = L.p; a.ng = L.ng; a.nb = L.nb;
+  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+}
+// caller masks (bit k = group k) -> the layout's numbering (low groups first)
+std::vector<uint64_t> layout_masks(const GroupLayout& L, const uint64_t* masks, int64_t n) {
+  std::vector<uint64_t> lay((size_t)n, 0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int r = 0; r < L.ng; ++r)
+      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  return lay;
+}
+// The kernels' view of replicate e0 of a dense store of problems (a bootstrap block, the folds, a block of the ridge
+// path): G, H [.][p][p], g, h [.][p], inv_yy [.] and the info words [.] from there on, and the pivot test.  What else
+// Args holds (the players, the weights, per, part) is the caller's.
+template <typename Args>
+void rep_view(Args& a, int p, int e0, const double* G, const double* g, const double* H, const double* h,
+              const double* inv_yy, int32_t* info) {
+  const size_t pp = (size_t)p * p;
+  a.G = G + (size_t)e0 * pp;
+  a.H = H + (size_t)e0 * pp;
+  a.g = g + (size_t)e0 * p;
+  a.h = h + (size_t)e0 * p;
+  a.ldg = a.ldh = p;
+  a.piv_tol = exact_piv_tol(p);
+  set_inv_yy(a, inv_yy + e0);
+  a.info = info + e0;
+}
+
 // The kernels' view of the loaded problem, the part that SubsetArgs and GroupArgs (Args) have in common: G, g, the test
 // Gram (formed from the test factor in rect mode), the Shapley weights of n players by subset size, the tolerances and
 // a cleared info word.  no_problem: the entry point's error for that; tab: GROUPS_TAB_LEN words to upload into W.tab
 // beside the weights (nullptr: none).  The weight table carries three more rows, the interaction weights of n players
-// (kernels.h, SubsetArgs::w), which only the interactions kernel reads.
+// (kernels.h, SubsetArgs::w), which only the interactions kernel reads.  1 / ||y||^2 lies behind the table on the device
+// and is the caller's to set as its kernel takes it (subsets_args, groups_args).
 constexpr int EXACT_W_ROWS = 5;
 // w [EXACT_W_ROWS][EXACT_MAX_PLAYERS + 1]: the Shapley weights of n players by subset size (kernels.h, SubsetArgs::w)
 void exact_weight_table(int n, double* w) {
@@ -3350,9 +3422,6 @@ void exact_weight_table(int n, double* w) {
     w[4 * WR + k] = al + 2.0 * be + ga;
   }
 }
-// the subsets kernel reads 1 / ||y||^2 per replicate from the device, the groups kernel takes the value
-inline void set_inv_yy(SubsetArgs& a, const double* on_device, double) { a.inv_yy = on_device; }
-inline void set_inv_yy(GroupArgs& a, const double*, double value) { a.inv_yy = value; }
 template <typename Args>
 int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, const int32_t* tab, Args& a) {
   if (!ctx->have_problem) return ctx->fail(LSSPA_ERR_ARG, no_problem);
@@ -3385,8 +3454,7 @@ int exact_view(lsspa_ctx* ctx, ExactWork& W, const char* no_problem, int n, cons
   if (tab) HIPCHK(hipMemcpy(W.tab.ptr, tab, GROUPS_TAB_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(W.info.ptr, 0, 8 * sizeof(int32_t), ctx->stream));
   a.w = W.w.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  set_inv_yy(a, W.w.ptr + EXACT_W_ROWS * WR, w[EXACT_W_ROWS * WR]);
+  a.piv_tol = exact_piv_tol(p);
   a.info = W.info.ptr;
   return LSSPA_OK;
 }
@@ -3399,57 +3467,156 @@ struct Events {
   }
 };
 
-// The enumeration itself: launch(part, s0, s1) runs steps s0 .. s1 - 1 of every unit into the partial table part
-// [units][cols], `steps` of the n_high / units a launch.  out[0 .. cols - 1]: the table's column sums
-// (launch_subsets_reduce).  With n players the first n + 1 columns are phi's: a player's phi is its column minus column
-// n; what follows them is the entry point's own.  info (may be NULL): the info word.  Leaves the call's timing in W.
-// exact_enumerate_with: the same launches, events and timing for a table that is not summed (lsspa_subsets_best):
-// finish(units) enqueues the reduction of the table and the copies of its result to the host instead.
-template <typename Launch, typename Finish>
-int exact_enumerate_with(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uint64_t steps, Launch&& launch,
-                         Finish&& finish, int32_t* info) {
-  const uint64_t units = exact_units(n_high);
-  const uint64_t per = n_high / units;                 // both powers of two
-  TRY(dev_alloc(ctx, W.part, (size_t)units * cols));
-  TRY(dev_alloc(ctx, W.out, (size_t)cols));
-  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * units * cols, ctx->stream));
-  // every launch is bracketed by events: the call's kernel time and its longest launch (exact_timing)
-  const size_t n_launch = (size_t)((per + steps - 1) / steps);
-  std::vector<hipEvent_t> ev(n_launch + 1, nullptr);
+// The launches of a cut on a stream, each between an event pair of its own: after the caller's synchronise read() gives
+// the sum of the launches' own intervals, the longest of them and their number.  One timer serves all the launches of
+// a call (the sets of replicates, the blocks of the ridge path).
+struct LaunchTimer {
+  std::vector<hipEvent_t> ev;
   Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ev[0], ctx->stream));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < per; s0 += steps, ++l) {
-    HIPCHK(launch(W.part.ptr, s0, std::min(per, s0 + steps)));
-    HIPCHK(hipEventRecord(ev[l + 1], ctx->stream));
+  // launch(s0, s1): steps s0 .. s1 - 1 of every unit
+  template <typename Launch>
+  int run(lsspa_ctx* ctx, const EnumCut& c, Launch&& launch) {
+    size_t l = ev.size() / 2;
+    ev.resize(ev.size() + 2 * (size_t)c.launches, nullptr);
+    for (size_t k = 2 * l; k < ev.size(); ++k) HIPCHK(hipEventCreate(&ev[k]));
+    for (uint64_t s0 = 0; s0 < c.per; s0 += c.steps, ++l) {
+      HIPCHK(hipEventRecord(ev[2 * l], ctx->stream));
+      HIPCHK(launch(s0, std::min(c.per, s0 + c.steps)));
+      HIPCHK(hipEventRecord(ev[2 * l + 1], ctx->stream));
+    }
+    return LSSPA_OK;
   }
-  TRY(finish((int64_t)units));
-  int32_t bits = 0;
-  HIPCHK(hipMemcpyAsync(&bits, W.info.ptr, sizeof bits, hipMemcpyDeviceToHost, ctx->stream));
+  int read(lsspa_ctx* ctx, double& total_ms, double& max_launch_ms, int64_t& launches) const {
+    total_ms = max_launch_ms = 0.0;
+    launches = (int64_t)(ev.size() / 2);
+    for (size_t l = 0; l < ev.size() / 2; ++l) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[2 * l], ev[2 * l + 1]));
+      total_ms += ms;
+      max_launch_ms = std::max(max_launch_ms, (double)ms);
+    }
+    return LSSPA_OK;
+  }
+};
+// where a call's timing goes: lsspa_subsets_timing / lsspa_groups_timing, lsspa_cv_timing
+int keep_timing(lsspa_ctx* ctx, ExactWork& W, const LaunchTimer& t) {
+  return t.read(ctx, W.kernel_ms, W.max_launch_ms, W.launches);
+}
+int keep_timing(lsspa_ctx* ctx, CvWork& W, const LaunchTimer& t) {
+  return t.read(ctx, W.enum_ms, W.max_launch_ms, W.launches);
+}
+// The end of every enumeration call on W (ExactWork, CvWork) once its result's copies are enqueued: the first n_info
+// words of W.info into info (may be NULL), the synchronise, the launches' timing into W
+template <typename Work>
+int enum_finish(lsspa_ctx* ctx, Work& W, const LaunchTimer& t, int n_info, int32_t* info) {
+  int32_t bits[CV_MAX_FOLDS] = {0};
+  HIPCHK(hipMemcpyAsync(bits, W.info.ptr, sizeof(int32_t) * n_info, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (info) *info = bits;
-  W.kernel_ms = 0.0;
-  W.max_launch_ms = 0.0;
-  W.launches = (int64_t)n_launch;
-  for (size_t k = 0; k < n_launch; ++k) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-    W.kernel_ms += ms;
-    W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
+  if (info) std::copy(bits, bits + n_info, info);
+  return keep_timing(ctx, W, t);
+}
+
+// The enumeration that sums: launch(part, s0, s1) runs steps s0 .. s1 - 1 of every unit of the cut into the partial
+// table part [units][cols].  out[0 .. cols - 1]: the table's column sums (launch_subsets_reduce).  With n players the
+// first n + 1 columns are phi's: a player's phi is its column minus column n; what follows them is the entry point's
+// own.  info (may be NULL): the info word.  Leaves the call's timing in W.
+template <typename Launch>
+int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, const EnumCut& c, Launch&& launch, double* out,
+                    int32_t* info) {
+  TRY(dev_alloc(ctx, W.part, (size_t)c.units * cols));
+  TRY(dev_alloc(ctx, W.out, (size_t)cols));
+  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * c.units * cols, ctx->stream));
+  LaunchTimer t;
+  TRY(t.run(ctx, c, [&](uint64_t s0, uint64_t s1) { return launch(W.part.ptr, s0, s1); }));
+  HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)c.units, cols, W.out.ptr, ctx->stream));
+  HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
+  return enum_finish(ctx, W, t, 1, info);
+}
+
+// ---- selection: the best model of every size, or the T best (lsspa_subsets_best / _top, lsspa_groups_best / _top and
+// the four lsspa_cv_* selection calls) ----
+// One skeleton each for the eight calls, on the buffers of W (ExactWork, CvWork) over n players (features, or groups:
+// the masks are the caller's).  A call supplies its checks and its launcher, nothing else.
+//
+// best: every unit keeps its best model of every size 0 .. n, values in W.part [units][n + 1] and (mask, found) in
+// W.best [units][n + 1][2], both cleared before the first launch; behind them in W.best the n + 1 pairs of the result,
+// which launch_subsets_best_reduce takes over the units beside the values in W.out [n + 1].
+// found[k] = the pair's flag, masks[k] = its mask (0 if none), v[k] = NaN if none: the n + 1 pairs mf of a result
+void best_decode(const uint32_t* mf, int n, double* v, uint32_t* masks, uint8_t* found) {
+  for (int k = 0; k <= n; ++k) {
+    found[k] = mf[2 * k + 1] ? 1 : 0;
+    masks[k] = found[k] ? mf[2 * k] : 0u;
+    if (!found[k]) v[k] = std::nan("");
   }
+}
+// launch(s0, s1): steps s0 .. s1 - 1 of every unit into W.part and W.best; n_info: info words of the call
+template <typename Work, typename Launch>
+int best_run(lsspa_ctx* ctx, Work& W, const EnumCut& c, int n, int n_info, Launch&& launch, double* v, uint32_t* masks,
+             uint8_t* found, int32_t* info) {
+  hipStream_t st = ctx->stream;
+  const size_t rows = (size_t)c.units * (n + 1);
+  TRY(dev_alloc(ctx, W.part, rows));
+  TRY(dev_alloc(ctx, W.out, (size_t)n + 1));
+  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)n + 1)));
+  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * rows, st));
+  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, st));
+  LaunchTimer t;
+  TRY(t.run(ctx, c, launch));
+  uint32_t mf[2 * (EXACT_MAX_PLAYERS + 1)];
+  uint32_t* out_m = W.best.ptr + 2 * rows;
+  HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, (int64_t)c.units, n, W.out.ptr, out_m, st));
+  HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * (n + 1), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (n + 1), hipMemcpyDeviceToHost, st));
+  TRY(enum_finish(ctx, W, t, n_info, info));
+  best_decode(mf, n, v, masks, found);
   return LSSPA_OK;
 }
 
-template <typename Launch>
-int exact_enumerate(lsspa_ctx* ctx, ExactWork& W, int cols, uint64_t n_high, uint64_t steps, Launch&& launch,
-                    double* out, int32_t* info) {
-  auto finish = [&](int64_t units) {
-    HIPCHK(launch_subsets_reduce(W.part.ptr, units, cols, W.out.ptr, ctx->stream));
-    HIPCHK(hipMemcpyAsync(out, W.out.ptr, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
-    return (int)LSSPA_OK;
-  };
-  return exact_enumerate_with(ctx, W, cols, n_high, steps, launch, finish, info);
+// top: every unit keeps per size a list of its T best, values in W.part [units][n + 1][T] (not cleared: no entry is read
+// beyond a list's count) and in W.best the masks tm [units][n + 1][T], the counts tc [units][n + 1], cleared before the
+// first launch, and behind them the result's masks out_m [n + 1][T] and counts out_c [n + 1], which
+// launch_subsets_top_reduce merges from the units' lists beside the values in W.out [n + 1][T].
+struct TopTable {
+  int n, T;
+  int sizes;                 // sizes one unit can hold: popc(s) + popc(t), s < per, t < 2^low, and no more than n + 1
+  size_t rows;               // units (n + 1): lists in the table
+  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
+  // low: the low players, which a unit enumerates at every step (q features, gl groups)
+  TopTable(const EnumCut& c, int n_, int low, int T_)
+      : n(n_), T(T_), sizes(std::min(n_, __builtin_popcountll(c.per - 1) + low) + 1), rows((size_t)c.units * (n_ + 1)),
+        bytes((int64_t)rows * (12 * T_ + 4)) {}
+  size_t n_out() const { return (size_t)(n + 1) * T; }
+  size_t words() const { return rows * T + rows + n_out() + (size_t)n + 1; }      // of W.best
+};
+struct TopLists {
+  uint32_t* tm;
+  int32_t* tc;
+  uint32_t* out_m;
+  int32_t* out_c;
+};
+TopLists top_carve(const DevBuf<uint32_t>& best, const TopTable& t) {
+  uint32_t* tm = best.ptr;
+  uint32_t* out_m = tm + t.rows * t.T + t.rows;
+  return {tm, reinterpret_cast<int32_t*>(tm + t.rows * t.T), out_m, reinterpret_cast<int32_t*>(out_m + t.n_out())};
+}
+// launch(tm, tc, s0, s1): steps s0 .. s1 - 1 of every unit into W.part and the lists; n_info: info words of the call
+template <typename Work, typename Launch>
+int top_run(lsspa_ctx* ctx, Work& W, const EnumCut& c, const TopTable& tab, int n_info, Launch&& launch, double* v,
+            uint32_t* masks, int32_t* count, int32_t* info) {
+  hipStream_t st = ctx->stream;
+  const int n = tab.n, T = tab.T;
+  TRY(dev_alloc(ctx, W.part, tab.rows * T));
+  TRY(dev_alloc(ctx, W.out, tab.n_out()));
+  TRY(dev_alloc(ctx, W.best, tab.words()));
+  const TopLists b = top_carve(W.best, tab);
+  HIPCHK(hipMemsetAsync(b.tc, 0, sizeof(int32_t) * tab.rows, st));
+  LaunchTimer t;
+  TRY(t.run(ctx, c, [&](uint64_t s0, uint64_t s1) { return launch(b.tm, b.tc, s0, s1); }));
+  HIPCHK(launch_subsets_top_reduce(W.part.ptr, b.tm, b.tc, (int64_t)c.units, n, T, W.out.ptr, b.out_m, b.out_c, st));
+  HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * tab.n_out(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(masks, b.out_m, sizeof(uint32_t) * tab.n_out(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(count, b.out_c, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, st));
+  return enum_finish(ctx, W, t, n_info, info);
 }
 
 // inter [n][n] of the column sums `out` of an interactions table of n players (kernels.h): I_ij = T0 - T1_i - T1_j +
@@ -3471,6 +3638,8 @@ void exact_inter_matrix(const double* out, int n, const int* gid, double* inter)
   }
 }
 
+// lsspa_subsets_timing, lsspa_groups_timing: kernel_ms is the sum of the launches' own event intervals (LaunchTimer), so
+// the gaps between back-to-back launches do not count; max_launch_ms the longest of them, launches their number.
 int exact_timing(const ExactWork& W, double* kernel_ms, double* max_launch_ms, int64_t* launches) {
   if (kernel_ms) *kernel_ms = W.kernel_ms;
   if (max_launch_ms) *max_launch_ms = W.max_launch_ms;
@@ -3496,9 +3665,6 @@ int exact_debug_values(lsspa_ctx* ctx, ExactWork& W, const uint64_t* masks, int6
 }
 
 // ---- ... by subset enumeration (k_subsets.hip) ----
-// high subsets one enumeration launch takes at most (over all units): ~35 ms of GPU time at p = 32
-constexpr uint64_t SUBSETS_PER_LAUNCH = 1ull << 20;
-
 int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
   const int p = ctx->p;
   if (ctx->have_problem && p > SUBSETS_MAX_P) {   // (no problem loaded: exact_view says so)
@@ -3510,6 +3676,7 @@ int subsets_args(lsspa_ctx* ctx, SubsetArgs& a) {
   TRY(exact_view(ctx, ctx->sub, "no problem loaded (exact attribution by subsets)", p, nullptr, a));
   a.p = p;
   a.q = subsets_low_features(p);
+  set_inv_yy(a, ctx->sub.w.ptr + EXACT_W_ROWS * (EXACT_MAX_PLAYERS + 1));
   return LSSPA_OK;
 }
 
@@ -3519,78 +3686,32 @@ int subsets_enumerate(lsspa_ctx* ctx, bool inter, double* out, int32_t* info) {
   SubsetArgs a;
   TRY(subsets_args(ctx, a));
   const int p = ctx->p;
-  const uint64_t n_high = 1ull << (p - a.q);
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
+  const EnumCut c(p);
+  a.per = c.per;
   auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
     a.part = part;
-    return launch_subsets_enum(a, units, s0, s1, inter, ctx->stream);
+    return launch_subsets_enum(a, c.units, s0, s1, inter, ctx->stream);
   };
-  return exact_enumerate(ctx, ctx->sub, inter ? subsets_inter_cols(p) : p + 1, n_high, steps, launch, out, info);
+  return exact_enumerate(ctx, ctx->sub, inter ? subsets_inter_cols(p) : p + 1, c, launch, out, info);
 }
 
-// lsspa_subsets_best: the same units, launches and timing; the table holds each unit's best subset per size, values in
-// ctx->sub.part and (mask, found) in ctx->sub.best, whose last p + 1 pairs receive the result.
+// lsspa_subsets_best: the same cut and timing, best_run on ctx->sub
 int subsets_best(lsspa_ctx* ctx, uint32_t include, double* v, uint32_t* masks, uint8_t* found, int32_t* info) {
   SubsetArgs a;
   TRY(subsets_args(ctx, a));
   const int p = ctx->p;
   if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
-  const uint64_t n_high = 1ull << (p - a.q);
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  const uint64_t steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units);
+  const EnumCut c(p);
+  a.per = c.per;
   ExactWork& W = ctx->sub;
-  const size_t rows = (size_t)units * (p + 1);
-  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)p + 1)));
-  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, ctx->stream));
-  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
-    a.part = part;
-    return launch_subsets_best(a, units, s0, s1, include, W.best.ptr, ctx->stream);
+  auto launch = [&](uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_subsets_best(a, c.units, s0, s1, include, W.best.ptr, ctx->stream);
   };
-  uint32_t mf[2 * (SUBSETS_MAX_P + 1)];
-  auto finish = [&](int64_t n_units) {
-    uint32_t* out_m = W.best.ptr + 2 * rows;
-    HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, n_units, p, W.out.ptr, out_m, ctx->stream));
-    HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
-    return (int)LSSPA_OK;
-  };
-  TRY(exact_enumerate_with(ctx, W, p + 1, n_high, steps, launch, finish, info));
-  for (int k = 0; k <= p; ++k) {
-    found[k] = mf[2 * k + 1] ? 1 : 0;
-    masks[k] = found[k] ? mf[2 * k] : 0u;
-    if (!found[k]) v[k] = std::nan("");
-  }
-  return LSSPA_OK;
+  return best_run(ctx, W, c, p, 1, launch, v, masks, found, info);
 }
 
-// lsspa_subsets_top: the same units, launches and timing once more; the table holds each unit's T best subsets per size,
-// values in ctx->sub.part [units][p + 1][T] and in ctx->sub.best the masks [units][p + 1][T], the counts [units][p + 1]
-// and behind them the result's masks [p + 1][T] and counts [p + 1].  What the call and its plan hook both go by:
-struct TopPlan {
-  uint64_t units, per, steps, launches;
-  int sizes;                 // sizes one unit can hold: popc(s) + popc(T), s < per, T < 2^q, and no more than p + 1
-  size_t rows;               // units (p + 1): lists in the table
-  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
-};
-TopPlan subsets_top_plan(int p, int T) {
-  TopPlan P;
-  const int q = subsets_low_features(p);
-  const uint64_t n_high = 1ull << (p - q);
-  P.units = exact_units(n_high);
-  P.per = n_high / P.units;
-  P.steps = std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / P.units);
-  P.launches = (P.per + P.steps - 1) / P.steps;
-  int per_bits = 0;
-  while ((1ull << per_bits) < P.per) ++per_bits;
-  P.sizes = std::min(p, per_bits + q) + 1;
-  P.rows = (size_t)P.units * (p + 1);
-  P.bytes = (int64_t)P.rows * (12 * T + 4);
-  return P;
-}
-
+// lsspa_subsets_top: the same once more, top_run on ctx->sub
 int subsets_top(lsspa_ctx* ctx, uint32_t include, int T, double* v, uint32_t* masks, int32_t* count, int32_t* info) {
   SubsetArgs a;
   TRY(subsets_args(ctx, a));
@@ -3601,47 +3722,17 @@ int subsets_top(lsspa_ctx* ctx, uint32_t include, int T, double* v, uint32_t* ma
     snprintf(msg, sizeof msg, "lsspa_subsets_top keeps 1 .. %d subsets of every size (T = %d)", SUBSETS_TOP_MAX, T);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
-  const TopPlan P = subsets_top_plan(p, T);
-  a.per = P.per;
+  const EnumCut c(p);
+  a.per = c.per;
   ExactWork& W = ctx->sub;
-  const size_t n_out = (size_t)(p + 1) * T;
-  TRY(dev_alloc(ctx, W.best, P.rows * T + P.rows + n_out + (size_t)p + 1));
-  uint32_t* tm = W.best.ptr;
-  int32_t* tc = reinterpret_cast<int32_t*>(tm + P.rows * T);
-  uint32_t* out_m = tm + P.rows * T + P.rows;
-  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
-  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * P.rows, ctx->stream));      // the counts; no entry is read beyond one
-  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
-    a.part = part;
-    return launch_subsets_top(a, P.units, s0, s1, include, T, tm, tc, ctx->stream);
+  auto launch = [&](uint32_t* tm, int32_t* tc, uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_subsets_top(a, c.units, s0, s1, include, T, tm, tc, ctx->stream);
   };
-  auto finish = [&](int64_t n_units) {
-    HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, n_units, p, T, W.out.ptr, out_m, out_c, ctx->stream));
-    HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (p + 1), hipMemcpyDeviceToHost, ctx->stream));
-    return (int)LSSPA_OK;
-  };
-  return exact_enumerate_with(ctx, W, (p + 1) * T, (uint64_t)1 << (p - a.q), P.steps, launch, finish, info);
+  return top_run(ctx, W, c, TopTable(c, p, a.q, T), 1, launch, v, masks, count, info);
 }
 
 // ---- ... over groups of columns (k_groups.hip) ----
-// One enumeration launch takes at most GROUPS_WORK_PER_LAUNCH units of work over all workgroups, a high subset
-// counting as (rows of its matrix, on average)^2: the elimination of a subset costs that much per pivot row, and a
-// subset of 64 columns several times one of 32.  2^26 is about 5 ms of one MI355X (DESIGN.md): far below the bound of
-// 0.2 s, and long enough that the launches' own cost does not show.
-constexpr uint64_t GROUPS_WORK_PER_LAUNCH = 1ull << 26;
-// high subsets one launch takes at most over all its workgroups on the layout L
-uint64_t groups_per_launch(const GroupLayout& L) {
-  // rows of a subset's matrix: baseline and low columns always, the high columns half of the time
-  const uint64_t rows = (uint64_t)(L.nb + L.ql + 1) + (uint64_t)(L.p - L.nb - L.ql + 1) / 2;
-  return std::max<uint64_t>(1, GROUPS_WORK_PER_LAUNCH / (rows * rows));
-}
-// steps of every unit that one launch of `units` workgroups takes on the layout L
-uint64_t groups_steps(const GroupLayout& L, uint64_t units) {
-  return std::max<uint64_t>(1, groups_per_launch(L) / units);
-}
-
 int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, GroupLayout& L) {
   const int p = ctx->p;
   char msg[200];
@@ -3664,8 +3755,8 @@ int groups_args(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupArgs& a, 
   }
   TRY(exact_view(ctx, ctx->grp, "no problem loaded (exact attribution over groups)", L.ng, L.tab, a));
   a.tab = ctx->grp.tab.ptr;
-  a.p = p; a.ng = L.ng; a.nb = L.nb;
-  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
+  set_layout(a, L);
+  a.inv_yy = 1.0 / ctx->y_norm_sq;
   return LSSPA_OK;
 }
 
@@ -3677,79 +3768,32 @@ int groups_enumerate(lsspa_ctx* ctx, bool inter, const int32_t* labels, int32_t 
   GroupArgs a;
   TRY(groups_args(ctx, labels, g, a, L));
   const int ng = L.ng;
-  const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  const uint64_t steps = groups_steps(L, units);
+  const EnumCut c(L);
+  a.per = c.per;
   auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
     a.part = part;
-    return launch_groups_enum(a, units, s0, s1, inter, ctx->stream);
+    return launch_groups_enum(a, c.units, s0, s1, inter, ctx->stream);
   };
-  return exact_enumerate(ctx, ctx->grp, inter ? subsets_inter_cols(ng) : ng + 1, n_high, steps, launch, out, info);
+  return exact_enumerate(ctx, ctx->grp, inter ? subsets_inter_cols(ng) : ng + 1, c, launch, out, info);
 }
 
-// lsspa_groups_best: the same units, launches and timing; the table holds each unit's best group subset per size, values
-// in ctx->grp.part and (caller mask, found) in ctx->grp.best, whose last g + 1 pairs receive the result.
-static_assert(((1ull << (GROUPS_MAX_G - 1)) / EXACT_UNITS) <= (1ull << (GROUPS_BEST_CLASSES - 1)),
-              "groups_best_kernel holds the size classes of the largest per: at most 31 high groups over EXACT_UNITS units");
+// lsspa_groups_best: the same cut and timing, best_run on ctx->grp with the g groups as the players
 int groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* u, uint32_t* masks, uint8_t* found,
                 int32_t* info) {
   GroupArgs a;
   GroupLayout L;
   TRY(groups_args(ctx, labels, g, a, L));
-  const int ng = L.ng;
-  const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  const uint64_t steps = groups_steps(L, units);
+  const EnumCut c(L);
+  a.per = c.per;
   ExactWork& W = ctx->grp;
-  const size_t rows = (size_t)units * (ng + 1);
-  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)ng + 1)));
-  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, ctx->stream));
-  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
-    a.part = part;
-    return launch_groups_best(a, L.gid, units, s0, s1, W.best.ptr, ctx->stream);
+  auto launch = [&](uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_groups_best(a, L.gid, c.units, s0, s1, W.best.ptr, ctx->stream);
   };
-  uint32_t mf[2 * (GROUPS_MAX_G + 1)];
-  auto finish = [&](int64_t n_units) {
-    uint32_t* out_m = W.best.ptr + 2 * rows;
-    HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, n_units, ng, W.out.ptr, out_m, ctx->stream));
-    HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
-    return (int)LSSPA_OK;
-  };
-  TRY(exact_enumerate_with(ctx, W, ng + 1, n_high, steps, launch, finish, info));
-  for (int k = 0; k <= ng; ++k) {
-    found[k] = mf[2 * k + 1] ? 1 : 0;
-    masks[k] = found[k] ? mf[2 * k] : 0u;
-    if (!found[k]) u[k] = std::nan("");
-  }
-  return LSSPA_OK;
+  return best_run(ctx, W, c, L.ng, 1, launch, u, masks, found, info);
 }
 
-// lsspa_groups_top: the same units, launches and timing once more; the table holds each unit's T best group subsets per
-// size, values in ctx->grp.part [units][g + 1][T] and in ctx->grp.best the caller masks [units][g + 1][T], the counts
-// [units][g + 1] and behind them the result's masks [g + 1][T] and counts [g + 1] (subsets_top's layout of
-// ctx->sub.best).  What the call and its plan hook both go by:
-struct GroupTopPlan {
-  uint64_t units, per, steps, launches;
-  int sizes;                 // sizes one unit can hold: popc(s) + popc(T), s < per, T < 2^gl, and no more than g + 1
-  size_t rows;               // units (g + 1): lists in the table
-  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
-};
-GroupTopPlan groups_top_plan(const GroupLayout& L, int T) {
-  GroupTopPlan P;
-  const uint64_t n_high = 1ull << L.gh;
-  P.units = exact_units(n_high);
-  P.per = n_high / P.units;
-  P.steps = groups_steps(L, P.units);
-  P.launches = (P.per + P.steps - 1) / P.steps;
-  P.sizes = std::min(L.ng, __builtin_popcountll(P.per - 1) + L.gl) + 1;
-  P.rows = (size_t)P.units * (L.ng + 1);
-  P.bytes = (int64_t)P.rows * (12 * T + 4);
-  return P;
-}
-
+// lsspa_groups_top: the same once more, top_run on ctx->grp
 int groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int T, double* u, uint32_t* masks, int32_t* count,
                int32_t* info) {
   GroupArgs a;
@@ -3760,29 +3804,14 @@ int groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int T, double* 
     snprintf(msg, sizeof msg, "lsspa_groups_top keeps 1 .. %d subsets of every size (T = %d)", GROUPS_TOP_MAX, T);
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
-  const int ng = L.ng;
-  const GroupTopPlan P = groups_top_plan(L, T);
-  a.per = P.per;
+  const EnumCut c(L);
+  a.per = c.per;
   ExactWork& W = ctx->grp;
-  const size_t n_out = (size_t)(ng + 1) * T;
-  TRY(dev_alloc(ctx, W.best, P.rows * T + P.rows + n_out + (size_t)ng + 1));
-  uint32_t* tm = W.best.ptr;
-  int32_t* tc = reinterpret_cast<int32_t*>(tm + P.rows * T);
-  uint32_t* out_m = tm + P.rows * T + P.rows;
-  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
-  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * P.rows, ctx->stream));      // the counts; no entry is read beyond one
-  auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
-    a.part = part;
-    return launch_groups_top(a, L.gid, P.units, s0, s1, T, tm, tc, ctx->stream);
+  auto launch = [&](uint32_t* tm, int32_t* tc, uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_groups_top(a, L.gid, c.units, s0, s1, T, tm, tc, ctx->stream);
   };
-  auto finish = [&](int64_t n_units) {
-    HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, n_units, ng, T, W.out.ptr, out_m, out_c, ctx->stream));
-    HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (ng + 1), hipMemcpyDeviceToHost, ctx->stream));
-    return (int)LSSPA_OK;
-  };
-  return exact_enumerate_with(ctx, W, (ng + 1) * T, (uint64_t)1 << L.gh, P.steps, launch, finish, info);
+  return top_run(ctx, W, c, TopTable(c, L.ng, L.gl, T), 1, launch, u, masks, count, info);
 }
 
 // ---- Owen value: the columns of a group, with the groups as coalition structure (k_groups.hip's header) ----
@@ -3872,16 +3901,14 @@ int owen_enumerate(lsspa_ctx* ctx, const int32_t* labels, int g, int k, int b, d
   HIPCHK(hipMemcpy(ctx->grp.tab.ptr + GROUPS_TAB_OWEN_LO, marked.tab + GROUPS_TAB_OWEN_LO, 2 * sizeof(int32_t),
                    hipMemcpyHostToDevice));
   const int ng = L.ng;
-  const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = exact_units(n_high);
-  a.per = n_high / units;
-  const uint64_t steps = groups_steps(L, units);
+  const EnumCut c(L);
+  a.per = c.per;
   auto launch = [&](double* part, uint64_t s0, uint64_t s1) {
     a.part = part;
-    return launch_groups_owen(a, units, s0, s1, ctx->stream);
+    return launch_groups_owen(a, c.units, s0, s1, ctx->stream);
   };
   double out[EXACT_MAX_PLAYERS + 1];
-  TRY(exact_enumerate(ctx, ctx->grp, ng + 1, n_high, steps, launch, out, bits));
+  TRY(exact_enumerate(ctx, ctx->grp, ng + 1, c, launch, out, bits));
   int col_of[OWEN_MAX_PLAYERS];             // refined label - k of an inner player -> its column
   for (int j = 0, n = 0; j < p; ++j)
     if (labels[j] == k) col_of[n++] = j;
@@ -3939,8 +3966,10 @@ int lsspa_subsets_top(lsspa_ctx* ctx, uint32_t include, int32_t T, double* v, ui
 
 int lsspa_debug_subsets_top_plan(int32_t p, int32_t T, int64_t* plan) try {
   if (!plan || p < 1 || p > SUBSETS_MAX_P || T < 1 || T > SUBSETS_TOP_MAX) return LSSPA_ERR_ARG;
-  const TopPlan P = subsets_top_plan(p, T);
-  const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, (int64_t)P.launches, P.sizes, P.bytes, T, 0};
+  const EnumCut c(p);
+  const TopTable tab(c, p, subsets_low_features(p), T);
+  const int64_t out[8] = {(int64_t)c.units, (int64_t)c.per, (int64_t)c.steps, (int64_t)c.launches, tab.sizes, tab.bytes,
+                          T, 0};
   std::copy(out, out + 8, plan);
   return LSSPA_OK;
 } catch (...) {
@@ -4017,11 +4046,7 @@ int lsspa_debug_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_t g, c
   for (int64_t i = 0; i < n; ++i)
     if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a group beyond g");
   if (n == 0) return LSSPA_OK;
-  // bit k = group k  ->  the layout's numbering (low groups first)
-  std::vector<uint64_t> lay((size_t)n, 0);
-  for (int64_t i = 0; i < n; ++i)
-    for (int r = 0; r < L.ng; ++r)
-      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  const std::vector<uint64_t> lay = layout_masks(L, masks, n);
   auto launch = [&](const uint64_t* masks_d, double* vals_d) {
     return launch_groups_debug(a, masks_d, n, vals_d, ctx->stream);
   };
@@ -4043,14 +4068,12 @@ int lsspa_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* 
 int lsspa_debug_groups_best_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* plan) try {
   GroupLayout L;
   if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || groups_layout(labels, p, g, L)) return LSSPA_ERR_ARG;
-  const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = exact_units(n_high), per = n_high / units;
-  const uint64_t steps = groups_steps(L, units);
+  const EnumCut c(L);
   plan[0] = L.gl; plan[1] = L.gh; plan[2] = L.ql; plan[3] = L.nb;
-  plan[4] = (int64_t)units;
-  plan[5] = (int64_t)per;
-  plan[6] = (int64_t)((per + steps - 1) / steps);
-  plan[7] = __builtin_popcountll(per - 1) + 1;       // size classes of a unit: popc(s), s < per
+  plan[4] = (int64_t)c.units;
+  plan[5] = (int64_t)c.per;
+  plan[6] = (int64_t)c.launches;
+  plan[7] = __builtin_popcountll(c.per - 1) + 1;     // size classes of a unit: popc(s), s < per
   return LSSPA_OK;
 } catch (...) {
   return LSSPA_ERR_ARG;
@@ -4069,9 +4092,10 @@ int lsspa_debug_groups_top_plan(const int32_t* labels, int32_t p, int32_t g, int
   GroupLayout L;
   if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || T < 1 || T > GROUPS_TOP_MAX || groups_layout(labels, p, g, L))
     return LSSPA_ERR_ARG;
-  const GroupTopPlan P = groups_top_plan(L, T);
-  const int64_t out[10] = {L.gl, L.gh, L.ql, L.nb, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps,
-                           (int64_t)P.launches, P.sizes, P.bytes};
+  const EnumCut c(L);
+  const TopTable tab(c, L.ng, L.gl, T);
+  const int64_t out[10] = {L.gl, L.gh, L.ql, L.nb, (int64_t)c.units, (int64_t)c.per, (int64_t)c.steps,
+                           (int64_t)c.launches, tab.sizes, tab.bytes};
   std::copy(out, out + 10, plan);
   return LSSPA_OK;
 } catch (...) {
@@ -4134,14 +4158,12 @@ int lsspa_debug_owen_plan(const int32_t* labels, int32_t p, int32_t g, int64_t* 
     GroupLayout L;
     int n_lo, n_hi;
     owen_layout(labels, p, g, k, size[k], ref, L, n_lo, n_hi);
-    const uint64_t n_high = 1ull << L.gh;
-    const uint64_t units = exact_units(n_high), per = n_high / units;
-    const uint64_t steps = groups_steps(L, units);
+    const EnumCut c(L);
     int64_t* row = plan + 8 * k;
     row[0] = L.ng; row[1] = L.gl; row[2] = L.gh; row[3] = L.ql;
     row[4] = n_lo; row[5] = n_hi;
-    row[6] = (int64_t)(units * per);
-    row[7] = size[k] == 1 ? 0 : (int64_t)((per + steps - 1) / steps);    // a group of one column: no enumeration of its own
+    row[6] = (int64_t)(c.units * c.per);
+    row[7] = size[k] == 1 ? 0 : (int64_t)c.launches;    // a group of one column: no enumeration of its own
   }
   return LSSPA_OK;
 } catch (...) {
@@ -4575,42 +4597,25 @@ int boot_layout(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const char* to
 
 // k_subsets.hip's view of the block's replicates from e0 on (one launch's: the kernels' second grid dimension)
 SubsetArgs boot_subset_args(const BootWork& B, const BootPlan& P, int e0) {
-  const int p = B.p;
   SubsetArgs a{};
-  a.p = p;
-  a.q = subsets_low_features(p);
-  a.G = B.G.ptr + (size_t)e0 * p * p;
-  a.H = B.H.ptr + (size_t)e0 * p * p;
-  a.g = B.g.ptr + (size_t)e0 * p;
-  a.h = B.h.ptr + (size_t)e0 * p;
-  a.ldg = a.ldh = p;
+  a.p = B.p;
+  a.q = subsets_low_features(B.p);
   a.w = B.w.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  a.inv_yy = B.inv_yy.ptr + e0;
-  a.info = B.info.ptr + e0;
   a.per = P.per;
   a.part = B.epart.ptr;
+  rep_view(a, B.p, e0, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr, B.inv_yy.ptr, B.info.ptr);
   return a;
 }
 
 // the same of k_groups.hip, over the layout L
 GroupArgs boot_group_args(const BootWork& B, const BootPlan& P, const GroupLayout& L, int e0) {
-  const int p = B.p;
   GroupArgs a{};
-  a.p = p; a.ng = L.ng; a.nb = L.nb;
-  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
-  a.G = B.G.ptr + (size_t)e0 * p * p;
-  a.H = B.H.ptr + (size_t)e0 * p * p;
-  a.g = B.g.ptr + (size_t)e0 * p;
-  a.h = B.h.ptr + (size_t)e0 * p;
-  a.ldg = a.ldh = p;
+  set_layout(a, L);
   a.w = B.w.ptr;
   a.tab = B.tab.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  a.inv_yy_rep = B.inv_yy.ptr + e0;
-  a.info = B.info.ptr + e0;
   a.per = P.per;
   a.part = B.epart.ptr;
+  rep_view(a, B.p, e0, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr, B.inv_yy.ptr, B.info.ptr);
   return a;
 }
 
@@ -4694,9 +4699,10 @@ int boot_groups_run(lsspa_ctx* ctx, const char* name, const int32_t* labels, int
 }
 
 // What the two best-subset runs do after their plan, over n players (features, or groups with their table `tab`).  The
-// table: values in B.epart [enum_reps][units][n + 1], (mask, found) in B.ebest [enum_reps][units][n + 1][2], cleared
-// before a set of replicates' first launch; a replicate's row of B.eout is 2 (n + 1) doubles wide, the best values and
-// behind them the n + 1 (mask, found) pairs as launch_subsets_best_reduce writes them (8 bytes a pair).
+// table is best_run's, once per replicate of a launch: values in B.epart [enum_reps][units][n + 1], (mask, found) in
+// B.ebest [enum_reps][units][n + 1][2], cleared before a set of replicates' first launch; a replicate's row of B.eout is
+// 2 (n + 1) doubles wide, the best values and behind them the n + 1 (mask, found) pairs as launch_subsets_best_reduce
+// writes them (8 bytes a pair), which best_decode reads.
 //   launch(e0, ne, s0, s1): as boot_run_blocks', the kernel that also writes B.ebest;
 //   fit(r, G, g, H, h, inv_yy): the run's r2 entries of replicate r.
 template <typename Launch, typename Fit>
@@ -4726,12 +4732,8 @@ int boot_best_blocks(lsspa_ctx* ctx, const BootPlan& P, const BootWeights& W, in
                   double inv_yy) {
     uint32_t mf[2 * (EXACT_MAX_PLAYERS + 1)];
     std::memcpy(mf, out + n1, sizeof(uint32_t) * 2 * n1);
-    for (int k = 0; k <= n; ++k) {
-      const bool f = mf[2 * k + 1] != 0u;
-      found[r * n1 + k] = f ? 1 : 0;
-      masks[r * n1 + k] = f ? mf[2 * k] : 0u;
-      v[r * n1 + k] = f ? out[k] : std::nan("");
-    }
+    std::copy(out, out + n1, v + r * n1);
+    best_decode(mf, n, v + r * n1, masks + r * n1, found + r * n1);
     fit(r, G, g, H, h, inv_yy);
   };
   return boot_run_blocks(ctx, P, R, seed, first, W.w_host, n1, 2 * n1, cleared, reduce, emit, info);
@@ -5050,22 +5052,6 @@ int lsspa_boot_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, con
 // lsspa_cv_best runs subsets_cv_best_kernel.
 namespace {
 
-struct CvPlan {
-  uint64_t units, per, steps, launches;
-};
-// lsspa_cv_best's cut: a step of a unit evaluates K fold problems, so a launch takes 1 / K of the steps the one-problem
-// call gives it (at least one); forced > 0: that many steps a launch instead (test hook)
-CvPlan cv_best_plan(int p, int K, uint64_t forced) {
-  CvPlan P;
-  const uint64_t n_high = 1ull << (p - subsets_low_features(p));
-  P.units = exact_units(n_high);
-  P.per = n_high / P.units;
-  P.steps = forced ? forced : std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / (P.units * (uint64_t)K));
-  P.steps = std::min(P.steps, P.per);
-  P.launches = (P.per + P.steps - 1) / P.steps;
-  return P;
-}
-
 int cv_need_loaded(lsspa_ctx* ctx) {
   if (!ctx->cv.loaded) return ctx->fail(LSSPA_ERR_STATE, "no cross-validation data loaded (lsspa_cv_load comes first)");
   return LSSPA_OK;
@@ -5073,19 +5059,11 @@ int cv_need_loaded(lsspa_ctx* ctx) {
 
 // k_subsets.hip's view of the fold problems from e0 on; info: the [K] words the call reports into
 SubsetArgs cv_subset_args(const CvWork& W, int e0, int32_t* info) {
-  const int p = W.p;
   SubsetArgs a{};
-  a.p = p;
-  a.q = subsets_low_features(p);
-  a.G = W.G.ptr + (size_t)e0 * p * p;
-  a.H = W.H.ptr + (size_t)e0 * p * p;
-  a.g = W.g.ptr + (size_t)e0 * p;
-  a.h = W.h.ptr + (size_t)e0 * p;
-  a.ldg = a.ldh = p;
+  a.p = W.p;
+  a.q = subsets_low_features(W.p);
   a.w = W.w.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  a.inv_yy = W.inv_yy.ptr + e0;
-  a.info = info + e0;
+  rep_view(a, W.p, e0, W.G.ptr, W.g.ptr, W.H.ptr, W.h.ptr, W.inv_yy.ptr, info);
   return a;
 }
 
@@ -5110,18 +5088,45 @@ int cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, double* v, doubl
   return LSSPA_OK;
 }
 
-// the launches' events into W's timing
-int cv_enum_timing(lsspa_ctx* ctx, const std::vector<hipEvent_t>& ev, size_t n_launch) {
-  CvWork& W = ctx->cv;
-  W.enum_ms = 0.0;
-  W.max_launch_ms = 0.0;
-  W.launches = (int64_t)n_launch;
-  for (size_t k = 0; k < n_launch; ++k) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
-    W.enum_ms += ms;
-    W.max_launch_ms = std::max(W.max_launch_ms, (double)ms);
+// The enumeration of n replicate problems, `reps` of them a launch, on the cut of one problem: per set of replicates the
+// partial table part [reps][units][cols] cleared, the kernels' view of the set's first replicate (view(e0): everything
+// but per and part), the timed launches -- launch(a, s0, s1, ne): steps s0 .. s1 - 1 of every unit for the ne
+// replicates behind a -- and the tables' column sums into out + e0 cols.  lsspa_cv_shapley, lsspa_cv_groups_shapley and
+// a block of the ridge path; the bootstrap's block loop (boot_run_blocks) has the same inner loop without the events
+// -- it times a block's whole enumeration -- and keeps its own.
+template <typename View, typename Launch>
+int rep_enumerate(lsspa_ctx* ctx, LaunchTimer& t, const EnumCut& c, int n, int reps, int cols, double* part, double* out,
+                  View&& view, Launch&& launch) {
+  hipStream_t st = ctx->stream;
+  for (int e0 = 0; e0 < n; e0 += reps) {
+    const int ne = std::min(reps, n - e0);
+    HIPCHK(hipMemsetAsync(part, 0, sizeof(double) * (size_t)ne * c.units * cols, st));
+    auto a = view(e0);
+    a.per = c.per;
+    a.part = part;
+    TRY(t.run(ctx, c, [&](uint64_t s0, uint64_t s1) { return launch(a, s0, s1, ne); }));
+    HIPCHK(launch_subsets_reduce(part, (int64_t)c.units, cols, out + (size_t)e0 * cols, st, ne));
   }
+  return LSSPA_OK;
+}
+
+// The tail of the four CV selection calls: v_fold [n][K] is NaN but for the entries e with listed(e) -- the winners, the
+// lists' valid ranks -- whose masks go through values(masks, n, v, v_fold), the kernel's own fold-step (cv_values, or
+// cv_group_values on a layout)
+template <typename Values, typename Listed>
+int cv_fold_backfill(Values&& values, const uint32_t* masks, size_t n, Listed&& listed, int K, double* v_fold) {
+  std::fill(v_fold, v_fold + n * K, std::nan(""));
+  std::vector<uint64_t> m;
+  std::vector<size_t> at;
+  for (size_t e = 0; e < n; ++e)
+    if (listed(e)) {
+      at.push_back(e);
+      m.push_back(masks[e]);
+    }
+  if (m.empty()) return LSSPA_OK;
+  std::vector<double> v(m.size()), vf(m.size() * K);
+  TRY(values(m.data(), (int64_t)m.size(), v.data(), vf.data()));
+  for (size_t i = 0; i < m.size(); ++i) std::copy(&vf[i * K], &vf[i * K] + K, v_fold + at[i] * K);
   return LSSPA_OK;
 }
 
@@ -5240,46 +5245,33 @@ int cv_shapley(lsspa_ctx* ctx, double* phi, double* phi_fold, double* r2_fold, i
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int p = W.p, K = W.K, cols = p + 1;
-  const uint64_t n_high = 1ull << (p - subsets_low_features(p));
-  const uint64_t units = exact_units(n_high), per = n_high / units;
   // a fold's launches are the one-problem call's (the cut of `per` shows in the bits); as many folds share a launch as
   // its bound on the subsets of a launch leaves
-  const uint64_t steps = std::min(per, std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / units));
-  const int ereps = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, SUBSETS_PER_LAUNCH / (units * steps)));
-  TRY(dev_alloc(ctx, W.part, (size_t)ereps * units * cols));
+  const EnumCut c(p);
+  const uint64_t room = SUBSETS_PER_LAUNCH / (c.units * c.launch_steps());
+  const int ereps = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, room));
+  TRY(dev_alloc(ctx, W.part, (size_t)ereps * c.units * cols));
   TRY(dev_alloc(ctx, W.out, (size_t)K * cols));
   TRY(dev_alloc(ctx, W.phi, (size_t)(K + 1) * p));
   HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
-  const size_t n_launch = (size_t)((K + ereps - 1) / ereps) * (size_t)((per + steps - 1) / steps);
-  std::vector<hipEvent_t> ev(2 * n_launch, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  size_t l = 0;
-  for (int e0 = 0; e0 < K; e0 += ereps) {
-    const int ne = std::min(ereps, K - e0);
-    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)ne * units * cols, st));
-    SubsetArgs a = cv_subset_args(W, e0, W.info.ptr);
-    a.per = per;
-    a.part = W.part.ptr;
-    for (uint64_t s0 = 0; s0 < per; s0 += steps, ++l) {
-      HIPCHK(hipEventRecord(ev[2 * l], st));
-      HIPCHK(launch_subsets_enum(a, units, s0, std::min(per, s0 + steps), false, st, ne));
-      HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-    }
-    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, cols, W.out.ptr + (size_t)e0 * cols, st, ne));
-  }
+  LaunchTimer t;
+  TRY(rep_enumerate(ctx, t, c, K, ereps, cols, W.part.ptr, W.out.ptr,
+                    [&](int e0) { return cv_subset_args(W, e0, W.info.ptr); },
+                    [&](const SubsetArgs& a, uint64_t s0, uint64_t s1, int ne) {
+                      return launch_subsets_enum(a, c.units, s0, s1, false, st, ne);
+                    }));
   HIPCHK(launch_cv_foldsum(W.out.ptr, p, K, W.phi.ptr, W.phi.ptr + (size_t)K * p, st));
   HIPCHK(hipMemcpyAsync(phi_fold, W.phi.ptr, sizeof(double) * K * p, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(phi, W.phi.ptr + (size_t)K * p, sizeof(double) * p, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  TRY(cv_enum_timing(ctx, ev, n_launch));
+  TRY(enum_finish(ctx, W, t, K, info));
   // each fold's share of the R^2 of the full model: the value of the full mask, fold by fold
   const uint64_t full = (1ull << p) - 1ull;      // p <= 32
   double v = 0.0;
   return cv_values(ctx, &full, 1, &v, r2_fold);
 }
 
+// lsspa_cv_best: best_run on the fold problems.  A step of a unit evaluates K fold problems, so a launch takes 1 / K of
+// the steps the one-problem call gives it (EnumCut's K; steps > 0: the test hook)
 int cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, uint32_t* masks, uint8_t* found,
             double* v_fold, int32_t* info) {
   CvWork& W = ctx->cv;
@@ -5287,64 +5279,20 @@ int cv_best(lsspa_ctx* ctx, uint32_t include, int64_t steps, double* v, uint32_t
   if (p < 32 && (include >> p) != 0u) return ctx->fail(LSSPA_ERR_ARG, "include names a feature beyond p");
   if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_best: steps must be >= 0");
   HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const CvPlan P = cv_best_plan(p, K, (uint64_t)steps);
-  const size_t rows = (size_t)P.units * (p + 1);
-  TRY(dev_alloc(ctx, W.part, rows));
-  TRY(dev_alloc(ctx, W.out, (size_t)K * (p + 1)));
-  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)p + 1)));
-  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * rows, st));
-  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, st));
-  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, ctx->stream));
+  const EnumCut c(p, K, (uint64_t)steps);
   SubsetArgs a = cv_subset_args(W, 0, W.info.ptr);
-  a.per = P.per;
-  a.part = W.part.ptr;
-  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
-    HIPCHK(hipEventRecord(ev[2 * l], st));
-    HIPCHK(launch_subsets_cv_best(a, K, P.units, s0, std::min(P.per, s0 + P.steps), include, W.best.ptr, st));
-    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-  }
-  uint32_t mf[2 * (SUBSETS_MAX_P + 1)];
-  uint32_t* out_m = W.best.ptr + 2 * rows;
-  HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, (int64_t)P.units, p, W.out.ptr, out_m, st));
-  HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * (p + 1), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (p + 1), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
-  uint64_t win[SUBSETS_MAX_P + 1];
-  int at[SUBSETS_MAX_P + 1], nw = 0;
-  for (int k = 0; k <= p; ++k) {
-    found[k] = mf[2 * k + 1] ? 1 : 0;
-    masks[k] = found[k] ? mf[2 * k] : 0u;
-    if (!found[k]) v[k] = std::nan("");
-    for (int f = 0; f < K; ++f) v_fold[(size_t)k * K + f] = std::nan("");
-    if (found[k]) {
-      at[nw] = k;
-      win[nw++] = masks[k];
-    }
-  }
-  if (nw) {       // the winners' per-fold values, by the kernel's own fold-step
-    std::vector<double> wv((size_t)nw), wf((size_t)nw * K);
-    TRY(cv_values(ctx, win, nw, wv.data(), wf.data()));
-    for (int i = 0; i < nw; ++i) std::copy(&wf[(size_t)i * K], &wf[(size_t)i * K] + K, v_fold + (size_t)at[i] * K);
-  }
-  return LSSPA_OK;
+  a.per = c.per;
+  auto launch = [&](uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_subsets_cv_best(a, K, c.units, s0, s1, include, W.best.ptr, ctx->stream);
+  };
+  TRY(best_run(ctx, W, c, p, K, launch, v, masks, found, info));
+  auto values = [&](const uint64_t* m, int64_t n, double* mv, double* mf) { return cv_values(ctx, m, n, mv, mf); };
+  return cv_fold_backfill(values, masks, (size_t)p + 1, [&](size_t k) { return found[k] != 0; }, K, v_fold);
 }
 
-// lsspa_cv_top: cv_best's cut into launches (cv_best_plan) and lifecycle with subsets_top's table, which depends on p
-// and T alone: values in W.part [units][p + 1][T], in W.best the masks [units][p + 1][T], the counts [units][p + 1] and
-// behind them the result's masks [p + 1][T] and counts [p + 1].  What the call and its plan hook both go by:
-struct CvTopPlan {
-  CvPlan cut;
-  TopPlan table;             // sizes, rows and bytes; its steps and launches are the one-problem call's, not this one's
-};
-CvTopPlan cv_top_plan(int p, int K, int T, uint64_t forced) { return {cv_best_plan(p, K, forced), subsets_top_plan(p, T)}; }
-
+// lsspa_cv_top: top_run on the fold problems, cv_best's cut; the table depends on p and T alone
 int cv_top(lsspa_ctx* ctx, uint32_t include, int T, int64_t steps, double* v, uint32_t* masks, int32_t* count,
            double* v_fold, int32_t* info) {
   CvWork& W = ctx->cv;
@@ -5357,56 +5305,18 @@ int cv_top(lsspa_ctx* ctx, uint32_t include, int T, int64_t steps, double* v, ui
   }
   if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_top: steps must be >= 0");
   HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const CvTopPlan CP = cv_top_plan(p, K, T, (uint64_t)steps);
-  const CvPlan& P = CP.cut;
-  const size_t rows = CP.table.rows, n_out = (size_t)(p + 1) * T;
-  TRY(dev_alloc(ctx, W.part, rows * T));
-  TRY(dev_alloc(ctx, W.out, std::max(n_out, (size_t)K * (p + 1))));
-  TRY(dev_alloc(ctx, W.best, rows * T + rows + n_out + (size_t)p + 1));
-  uint32_t* tm = W.best.ptr;
-  int32_t* tc = reinterpret_cast<int32_t*>(tm + rows * T);
-  uint32_t* out_m = tm + rows * T + rows;
-  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
-  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * rows, st));      // the counts; no entry is read beyond one
-  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, ctx->stream));
+  const EnumCut c(p, K, (uint64_t)steps);
   SubsetArgs a = cv_subset_args(W, 0, W.info.ptr);
-  a.per = P.per;
-  a.part = W.part.ptr;
-  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
-    HIPCHK(hipEventRecord(ev[2 * l], st));
-    HIPCHK(launch_subsets_cv_top(a, K, P.units, s0, std::min(P.per, s0 + P.steps), include, T, tm, tc, st));
-    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-  }
-  HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, (int64_t)P.units, p, T, W.out.ptr, out_m, out_c, st));
-  HIPCHK(hipMemcpyAsync(v, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (p + 1), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
-  std::vector<uint64_t> listed;
-  std::vector<size_t> at;
-  for (int k = 0; k <= p; ++k)
-    for (int r = 0; r < T; ++r) {
-      const size_t e = (size_t)k * T + r;
-      for (int f = 0; f < K; ++f) v_fold[e * K + f] = std::nan("");
-      if (r < count[k]) {
-        at.push_back(e);
-        listed.push_back(masks[e]);
-      }
-    }
-  if (!listed.empty()) {      // the listed models' per-fold values, by the kernel's own fold-step
-    const size_t nl = listed.size();
-    std::vector<double> lv(nl), lf(nl * K);
-    TRY(cv_values(ctx, listed.data(), (int64_t)nl, lv.data(), lf.data()));
-    for (size_t i = 0; i < nl; ++i) std::copy(&lf[i * K], &lf[i * K] + K, v_fold + at[i] * K);
-  }
-  return LSSPA_OK;
+  a.per = c.per;
+  auto launch = [&](uint32_t* tm, int32_t* tc, uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_subsets_cv_top(a, K, c.units, s0, s1, include, T, tm, tc, ctx->stream);
+  };
+  TRY(top_run(ctx, W, c, TopTable(c, p, a.q, T), K, launch, v, masks, count, info));
+  auto values = [&](const uint64_t* m, int64_t n, double* mv, double* mf) { return cv_values(ctx, m, n, mv, mf); };
+  return cv_fold_backfill(values, masks, (size_t)(p + 1) * T, [&](size_t e) { return (int)(e % T) < count[e / T]; }, K,
+                          v_fold);
 }
 
 // ---- ... over groups of columns (lsspa_cv_groups_*; the CV kernels of k_groups.hip) ----
@@ -5441,22 +5351,6 @@ int cv_layout(lsspa_ctx* ctx, const int32_t* labels, int32_t g, GroupLayout& L) 
   return LSSPA_OK;
 }
 
-struct CvGroupsPlan {
-  uint64_t units, per, steps, launches;
-};
-// lsspa_cv_groups_best's cut: a step of a unit takes its high subset through K fold problems, so a launch takes 1 / K of
-// the steps lsspa_groups_best gives it (at least one); forced > 0: that many steps a launch instead (test hook)
-CvGroupsPlan cv_groups_best_plan(const GroupLayout& L, int K, uint64_t forced) {
-  CvGroupsPlan P;
-  const uint64_t n_high = 1ull << L.gh;
-  P.units = exact_units(n_high);
-  P.per = n_high / P.units;
-  P.steps = forced ? forced : std::max<uint64_t>(1, groups_per_launch(L) / (P.units * (uint64_t)K));
-  P.steps = std::min(P.steps, P.per);
-  P.launches = (P.per + P.steps - 1) / P.steps;
-  return P;
-}
-
 // the weights of L.ng players and the layout table, for the launches of one call
 int cv_groups_upload(lsspa_ctx* ctx, const GroupLayout& L) {
   CvWork& W = ctx->cv;
@@ -5473,20 +5367,11 @@ int cv_groups_upload(lsspa_ctx* ctx, const GroupLayout& L) {
 
 // k_groups.hip's view of the fold problems from e0 on, over the layout L; info: the [K] words the call reports into
 GroupArgs cv_group_args(const CvWork& W, const GroupLayout& L, int e0, int32_t* info) {
-  const int p = W.p;
   GroupArgs a{};
-  a.p = p; a.ng = L.ng; a.nb = L.nb;
-  a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
-  a.G = W.G.ptr + (size_t)e0 * p * p;
-  a.H = W.H.ptr + (size_t)e0 * p * p;
-  a.g = W.g.ptr + (size_t)e0 * p;
-  a.h = W.h.ptr + (size_t)e0 * p;
-  a.ldg = a.ldh = p;
+  set_layout(a, L);
   a.w = W.gw.ptr;
   a.tab = W.tab.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
-  a.inv_yy_rep = W.inv_yy.ptr + e0;
-  a.info = info + e0;
+  rep_view(a, W.p, e0, W.G.ptr, W.g.ptr, W.H.ptr, W.h.ptr, W.inv_yy.ptr, info);
   return a;
 }
 
@@ -5495,10 +5380,7 @@ GroupArgs cv_group_args(const CvWork& W, const GroupLayout& L, int e0, int32_t* 
 int cv_group_values(lsspa_ctx* ctx, const GroupLayout& L, const uint64_t* masks, int64_t n, double* u, double* u_fold) {
   CvWork& W = ctx->cv;
   const int K = W.K;
-  std::vector<uint64_t> lay((size_t)n, 0);     // -> the layout's numbering (low groups first)
-  for (int64_t i = 0; i < n; ++i)
-    for (int r = 0; r < L.ng; ++r)
-      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  const std::vector<uint64_t> lay = layout_masks(L, masks, n);
   TRY(dev_alloc(ctx, W.masks, (size_t)n));
   TRY(dev_alloc(ctx, W.vals, (size_t)n * (K + 1)));
   TRY(dev_alloc(ctx, W.dinfo, CV_MAX_FOLDS));
@@ -5524,42 +5406,26 @@ int cv_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* 
   TRY(cv_groups_upload(ctx, L));
   hipStream_t st = ctx->stream;
   const int K = W.K, ng = L.ng, cols = ng + 1;
-  const uint64_t n_high = 1ull << L.gh;
-  const uint64_t units = exact_units(n_high), per = n_high / units;
   // a fold's launches are lsspa_groups_shapley's (the cut of `per` shows in the bits); as many folds share a launch as
   // its work bound and the 2^20 workgroups of a launch leave (boot_groups_plan's rule)
-  const uint64_t steps = std::min(per, groups_steps(L, units));
-  const uint64_t room = std::min<uint64_t>(1ull << 20, groups_per_launch(L)) / (units * steps);
+  const EnumCut c(L);
+  const uint64_t room = std::min<uint64_t>(1ull << 20, groups_per_launch(L)) / (c.units * c.launch_steps());
   const int ereps = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, room));
-  TRY(dev_alloc(ctx, W.part, (size_t)ereps * units * cols));
+  TRY(dev_alloc(ctx, W.part, (size_t)ereps * c.units * cols));
   TRY(dev_alloc(ctx, W.out, (size_t)K * cols));
   TRY(dev_alloc(ctx, W.phi, (size_t)(K + 1) * ng));
   HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
-  const size_t n_launch = (size_t)((K + ereps - 1) / ereps) * (size_t)((per + steps - 1) / steps);
-  std::vector<hipEvent_t> ev(2 * n_launch, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  size_t l = 0;
-  for (int e0 = 0; e0 < K; e0 += ereps) {
-    const int ne = std::min(ereps, K - e0);
-    HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * (size_t)ne * units * cols, st));
-    GroupArgs a = cv_group_args(W, L, e0, W.info.ptr);
-    a.per = per;
-    a.part = W.part.ptr;
-    for (uint64_t s0 = 0; s0 < per; s0 += steps, ++l) {
-      HIPCHK(hipEventRecord(ev[2 * l], st));
-      HIPCHK(launch_groups_enum(a, units, s0, std::min(per, s0 + steps), false, st, ne));
-      HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-    }
-    HIPCHK(launch_subsets_reduce(W.part.ptr, (int64_t)units, cols, W.out.ptr + (size_t)e0 * cols, st, ne));
-  }
+  LaunchTimer t;
+  TRY(rep_enumerate(ctx, t, c, K, ereps, cols, W.part.ptr, W.out.ptr,
+                    [&](int e0) { return cv_group_args(W, L, e0, W.info.ptr); },
+                    [&](const GroupArgs& a, uint64_t s0, uint64_t s1, int ne) {
+                      return launch_groups_enum(a, c.units, s0, s1, false, st, ne);
+                    }));
   // a fold into label order as the bootstrap finishes a replicate, then the folds' sum in ascending order
   HIPCHK(launch_cv_groups_foldsum(W.out.ptr, ng, K, L.gid, W.phi.ptr, W.phi.ptr + (size_t)K * ng, st));
   HIPCHK(hipMemcpyAsync(phi_fold, W.phi.ptr, sizeof(double) * K * ng, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(phi, W.phi.ptr + (size_t)K * ng, sizeof(double) * ng, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  TRY(cv_enum_timing(ctx, ev, n_launch));
+  TRY(enum_finish(ctx, W, t, K, info));
   // each fold's value of all groups and of the baseline alone, fold by fold
   const uint64_t both[2] = {ng < 64 ? (1ull << ng) - 1ull : ~0ull, 0ull};
   double u[2];
@@ -5570,8 +5436,7 @@ int cv_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, double* 
   return LSSPA_OK;
 }
 
-static_assert(((1ull << (GROUPS_MAX_G - 1)) / EXACT_UNITS) <= (1ull << (GROUPS_BEST_CLASSES - 1)),
-              "groups_cv_best_kernel holds the size classes of the largest per, as groups_best_kernel does");
+// lsspa_cv_groups_best: best_run on the fold problems with the g groups as the players; cv_best's rule for the cut
 int cv_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t steps, double* u, uint32_t* masks,
                    uint8_t* found, double* u_fold, int32_t* info) {
   CvWork& W = ctx->cv;
@@ -5580,75 +5445,23 @@ int cv_groups_best(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int64_t ste
   TRY(cv_layout(ctx, labels, g, L));
   HIPCHK(hipSetDevice(ctx->device));
   TRY(cv_groups_upload(ctx, L));
-  hipStream_t st = ctx->stream;
-  const int K = W.K, ng = L.ng;
-  const CvGroupsPlan P = cv_groups_best_plan(L, K, (uint64_t)steps);
-  const size_t rows = (size_t)P.units * (ng + 1);
-  TRY(dev_alloc(ctx, W.part, rows));
-  TRY(dev_alloc(ctx, W.out, (size_t)ng + 1));
-  TRY(dev_alloc(ctx, W.best, 2 * (rows + (size_t)ng + 1)));
-  HIPCHK(hipMemsetAsync(W.part.ptr, 0, sizeof(double) * rows, st));
-  HIPCHK(hipMemsetAsync(W.best.ptr, 0, sizeof(uint32_t) * 2 * rows, st));
-  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, ctx->stream));
+  const int K = W.K;
+  const EnumCut c(L, K, (uint64_t)steps);
   GroupArgs a = cv_group_args(W, L, 0, W.info.ptr);
-  a.per = P.per;
-  a.part = W.part.ptr;
-  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
-    HIPCHK(hipEventRecord(ev[2 * l], st));
-    HIPCHK(launch_groups_cv_best(a, K, L.gid, P.units, s0, std::min(P.per, s0 + P.steps), W.best.ptr, st));
-    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-  }
-  uint32_t mf[2 * (GROUPS_MAX_G + 1)];
-  uint32_t* out_m = W.best.ptr + 2 * rows;
-  HIPCHK(launch_subsets_best_reduce(W.part.ptr, W.best.ptr, (int64_t)P.units, ng, W.out.ptr, out_m, st));
-  HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * (ng + 1), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(mf, out_m, sizeof(uint32_t) * 2 * (ng + 1), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
-  uint64_t win[GROUPS_MAX_G + 1];
-  int at[GROUPS_MAX_G + 1], nw = 0;
-  for (int k = 0; k <= ng; ++k) {
-    found[k] = mf[2 * k + 1] ? 1 : 0;
-    masks[k] = found[k] ? mf[2 * k] : 0u;
-    if (!found[k]) u[k] = std::nan("");
-    for (int f = 0; f < K; ++f) u_fold[(size_t)k * K + f] = std::nan("");
-    if (found[k]) {
-      at[nw] = k;
-      win[nw++] = masks[k];
-    }
-  }
-  if (nw) {       // the winners' per-fold values, by the kernel's own fold-step
-    std::vector<double> wv((size_t)nw), wf((size_t)nw * K);
-    TRY(cv_group_values(ctx, L, win, nw, wv.data(), wf.data()));
-    for (int i = 0; i < nw; ++i) std::copy(&wf[(size_t)i * K], &wf[(size_t)i * K] + K, u_fold + (size_t)at[i] * K);
-  }
-  return LSSPA_OK;
+  a.per = c.per;
+  auto launch = [&](uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_groups_cv_best(a, K, L.gid, c.units, s0, s1, W.best.ptr, ctx->stream);
+  };
+  TRY(best_run(ctx, W, c, L.ng, K, launch, u, masks, found, info));
+  auto values = [&](const uint64_t* m, int64_t n, double* mv, double* mf) {
+    return cv_group_values(ctx, L, m, n, mv, mf);
+  };
+  return cv_fold_backfill(values, masks, (size_t)L.ng + 1, [&](size_t k) { return found[k] != 0; }, K, u_fold);
 }
 
-// lsspa_cv_groups_top: cv_groups_best's cut into launches (cv_groups_best_plan) and lifecycle with groups_top's table,
-// which depends on the layout and T alone: values in W.part [units][g + 1][T], in W.best the caller masks
-// [units][g + 1][T], the counts [units][g + 1] and behind them the result's masks [g + 1][T] and counts [g + 1].  What
-// the call and its plan hook both go by:
-struct CvGroupsTopPlan {
-  CvGroupsPlan cut;
-  int sizes;                 // sizes one unit can hold (GroupTopPlan::sizes)
-  size_t rows;               // units (g + 1): lists in the table
-  int64_t bytes;             // of the table: 12 a list entry (value, mask) and 4 a list (count)
-};
-CvGroupsTopPlan cv_groups_top_plan(const GroupLayout& L, int K, int T, uint64_t forced) {
-  CvGroupsTopPlan P;
-  P.cut = cv_groups_best_plan(L, K, forced);
-  P.sizes = std::min(L.ng, __builtin_popcountll(P.cut.per - 1) + L.gl) + 1;
-  P.rows = (size_t)P.cut.units * (L.ng + 1);
-  P.bytes = (int64_t)P.rows * (12 * T + 4);
-  return P;
-}
-
+// lsspa_cv_groups_top: top_run on the fold problems, cv_groups_best's cut; the table depends on the layout and T alone
 int cv_groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int T, int64_t steps, double* u, uint32_t* masks,
                   int32_t* count, double* u_fold, int32_t* info) {
   CvWork& W = ctx->cv;
@@ -5662,57 +5475,21 @@ int cv_groups_top(lsspa_ctx* ctx, const int32_t* labels, int32_t g, int T, int64
   if (steps < 0) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_groups_top: steps must be >= 0");
   HIPCHK(hipSetDevice(ctx->device));
   TRY(cv_groups_upload(ctx, L));
-  hipStream_t st = ctx->stream;
-  const int K = W.K, ng = L.ng;
-  const CvGroupsTopPlan CP = cv_groups_top_plan(L, K, T, (uint64_t)steps);
-  const CvGroupsPlan& P = CP.cut;
-  const size_t rows = CP.rows, n_out = (size_t)(ng + 1) * T;
-  TRY(dev_alloc(ctx, W.part, rows * T));
-  TRY(dev_alloc(ctx, W.out, n_out));
-  TRY(dev_alloc(ctx, W.best, rows * T + rows + n_out + (size_t)ng + 1));
-  uint32_t* tm = W.best.ptr;
-  int32_t* tc = reinterpret_cast<int32_t*>(tm + rows * T);
-  uint32_t* out_m = tm + rows * T + rows;
-  int32_t* out_c = reinterpret_cast<int32_t*>(out_m + n_out);
-  HIPCHK(hipMemsetAsync(tc, 0, sizeof(int32_t) * rows, st));      // the counts; no entry is read beyond one
-  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
+  HIPCHK(hipMemsetAsync(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, ctx->stream));
+  const int K = W.K;
+  const EnumCut c(L, K, (uint64_t)steps);
   GroupArgs a = cv_group_args(W, L, 0, W.info.ptr);
-  a.per = P.per;
-  a.part = W.part.ptr;
-  std::vector<hipEvent_t> ev(2 * P.launches, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  size_t l = 0;
-  for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
-    HIPCHK(hipEventRecord(ev[2 * l], st));
-    HIPCHK(launch_groups_cv_top(a, K, L.gid, P.units, s0, std::min(P.per, s0 + P.steps), T, tm, tc, st));
-    HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-  }
-  HIPCHK(launch_subsets_top_reduce(W.part.ptr, tm, tc, (int64_t)P.units, ng, T, W.out.ptr, out_m, out_c, st));
-  HIPCHK(hipMemcpyAsync(u, W.out.ptr, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(masks, out_m, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(count, out_c, sizeof(int32_t) * (ng + 1), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(info, W.info.ptr, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  TRY(cv_enum_timing(ctx, ev, (size_t)P.launches));
-  std::vector<uint64_t> listed;
-  std::vector<size_t> at;
-  for (int k = 0; k <= ng; ++k)
-    for (int r = 0; r < T; ++r) {
-      const size_t e = (size_t)k * T + r;
-      for (int f = 0; f < K; ++f) u_fold[e * K + f] = std::nan("");
-      if (r < count[k]) {
-        at.push_back(e);
-        listed.push_back(masks[e]);
-      }
-    }
-  if (!listed.empty()) {      // the listed models' per-fold values, by the kernel's own fold-step
-    const size_t nl = listed.size();
-    std::vector<double> lv(nl), lf(nl * K);
-    TRY(cv_group_values(ctx, L, listed.data(), (int64_t)nl, lv.data(), lf.data()));
-    for (size_t i = 0; i < nl; ++i) std::copy(&lf[i * K], &lf[i * K] + K, u_fold + at[i] * K);
-  }
-  return LSSPA_OK;
+  a.per = c.per;
+  auto launch = [&](uint32_t* tm, int32_t* tc, uint64_t s0, uint64_t s1) {
+    a.part = W.part.ptr;
+    return launch_groups_cv_top(a, K, L.gid, c.units, s0, s1, T, tm, tc, ctx->stream);
+  };
+  TRY(top_run(ctx, W, c, TopTable(c, L.ng, L.gl, T), K, launch, u, masks, count, info));
+  auto values = [&](const uint64_t* m, int64_t n, double* mv, double* mf) {
+    return cv_group_values(ctx, L, m, n, mv, mf);
+  };
+  return cv_fold_backfill(values, masks, (size_t)(L.ng + 1) * T, [&](size_t e) { return (int)(e % T) < count[e / T]; },
+                          K, u_fold);
 }
 
 }  // namespace
@@ -5766,9 +5543,10 @@ int lsspa_debug_cv_groups_top_plan(const int32_t* labels, int32_t p, int32_t g, 
   if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || K < 2 || K > CV_MAX_FOLDS || T < 1 || T > GROUPS_TOP_MAX ||
       groups_layout(labels, p, g, L))
     return LSSPA_ERR_ARG;
-  const CvGroupsTopPlan P = cv_groups_top_plan(L, K, T, 0);
-  const int64_t out[12] = {L.gl, L.gh, L.ql, L.nb, (int64_t)P.cut.units, (int64_t)P.cut.per, (int64_t)P.cut.steps,
-                           (int64_t)P.cut.launches, (int64_t)groups_cv_top_lds_bytes(), 256, P.sizes, P.bytes};
+  const EnumCut c(L, K);
+  const TopTable tab(c, L.ng, L.gl, T);
+  const int64_t out[12] = {L.gl, L.gh, L.ql, L.nb, (int64_t)c.units, (int64_t)c.per, (int64_t)c.launch_steps(),
+                           (int64_t)c.launches, (int64_t)groups_cv_top_lds_bytes(), 256, tab.sizes, tab.bytes};
   std::copy(out, out + 12, plan);
   return LSSPA_OK;
 } catch (...) {
@@ -5797,9 +5575,9 @@ int lsspa_debug_cv_groups_plan(const int32_t* labels, int32_t p, int32_t g, int3
   GroupLayout L;
   if (!plan || g > GROUPS_MAX_G || p > GROUPS_MAX_P || K < 2 || K > CV_MAX_FOLDS || groups_layout(labels, p, g, L))
     return LSSPA_ERR_ARG;
-  const CvGroupsPlan P = cv_groups_best_plan(L, K, 0);
-  const int64_t out[12] = {L.gl, L.gh, L.ql, L.nb, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps,
-                           (int64_t)P.launches, (int64_t)groups_cv_lds_bytes(), 256, (int64_t)groups_best_lds_bytes(),
+  const EnumCut c(L, K);
+  const int64_t out[12] = {L.gl, L.gh, L.ql, L.nb, (int64_t)c.units, (int64_t)c.per, (int64_t)c.launch_steps(),
+                           (int64_t)c.launches, (int64_t)groups_cv_lds_bytes(), 256, (int64_t)groups_best_lds_bytes(),
                            (int64_t)groups_per_launch(L)};
   std::copy(out, out + 12, plan);
   return LSSPA_OK;
@@ -5905,8 +5683,8 @@ int lsspa_debug_cv_values(lsspa_ctx* ctx, const uint64_t* masks, int64_t n, doub
 
 int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan) try {
   if (!plan || p < 1 || p > SUBSETS_MAX_P || K < 2 || K > CV_MAX_FOLDS) return LSSPA_ERR_ARG;
-  const CvPlan P = cv_best_plan(p, K, 0);
-  const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, (int64_t)P.launches,
+  const EnumCut c(p, K);
+  const int64_t out[8] = {(int64_t)c.units, (int64_t)c.per, (int64_t)c.launch_steps(), (int64_t)c.launches,
                           (int64_t)subsets_cv_lds_bytes(), 64, 0, 0};
   std::copy(out, out + 8, plan);
   return LSSPA_OK;
@@ -5917,9 +5695,10 @@ int lsspa_debug_cv_plan(int32_t p, int32_t K, int64_t* plan) try {
 int lsspa_debug_cv_top_plan(int32_t p, int32_t K, int32_t T, int64_t* plan) try {
   if (!plan || p < 1 || p > SUBSETS_MAX_P || K < 2 || K > CV_MAX_FOLDS || T < 1 || T > SUBSETS_TOP_MAX)
     return LSSPA_ERR_ARG;
-  const CvTopPlan P = cv_top_plan(p, K, T, 0);
-  const int64_t out[8] = {(int64_t)P.cut.units, (int64_t)P.cut.per, (int64_t)P.cut.steps, (int64_t)P.cut.launches,
-                          (int64_t)subsets_cv_top_lds_bytes(T), 64, P.table.sizes, P.table.bytes};
+  const EnumCut c(p, K);
+  const TopTable tab(c, p, subsets_low_features(p), T);
+  const int64_t out[8] = {(int64_t)c.units, (int64_t)c.per, (int64_t)c.launch_steps(), (int64_t)c.launches,
+                          (int64_t)subsets_cv_top_lds_bytes(T), 64, tab.sizes, tab.bytes};
   std::copy(out, out + 8, plan);
   return LSSPA_OK;
 } catch (...) {
@@ -5939,41 +5718,30 @@ namespace {
 constexpr size_t CV_PATH_BLOCK_BYTES = 64ull << 20;   // the problems of a block of ridge values stay inside this
 
 struct CvPathPlan {
-  uint64_t units, per, steps;   // one problem's cut: that of cv_shapley / cv_groups_shapley
+  EnumCut cut;                  // one problem's: that of cv_shapley / cv_groups_shapley
   uint64_t bound, room;         // subsets a launch takes over its units, steps and replicates; replicates that leaves
   int block, blocks, reps;      // ridge values a block; blocks of L values; replicates of a launch of a full block
   uint64_t launches;            // enumeration launches of the L values
-};
-// n_high high subsets of a problem, `steps` of every unit a launch of one problem, at most `bound` subsets a launch;
-// forced > 0: that many ridge values a block (test hook; cut to L)
-CvPathPlan cv_path_plan(uint64_t n_high, uint64_t steps, uint64_t bound, int p, int K, int L, int forced) {
-  CvPathPlan P;
-  P.units = exact_units(n_high);
-  P.per = n_high / P.units;
-  P.steps = std::min(P.per, steps);
-  P.bound = bound;
-  P.room = std::max<uint64_t>(1, bound / (P.units * P.steps));
-  const size_t problem = sizeof(double) * (2 * (size_t)p * p + 2 * (size_t)p + 1) * (size_t)K;
-  P.block = forced > 0 ? forced : (int)std::max<size_t>(1, CV_PATH_BLOCK_BYTES / problem);
-  P.block = std::min(P.block, L);
-  P.blocks = (L + P.block - 1) / P.block;
-  P.reps = (int)std::min<uint64_t>((uint64_t)P.block * K, P.room);
-  P.launches = 0;
-  for (int l0 = 0; l0 < L; l0 += P.block) {
-    const uint64_t n = (uint64_t)std::min(P.block, L - l0) * K, reps = std::min(n, P.room);
-    P.launches += ((n + reps - 1) / reps) * ((P.per + P.steps - 1) / P.steps);
+  // at most `bound` subsets a launch; forced > 0: that many ridge values a block (test hook; cut to L)
+  CvPathPlan(const EnumCut& c, uint64_t bound_, int p, int K, int L, int forced) : cut(c), bound(bound_) {
+    room = std::max<uint64_t>(1, bound / (cut.units * cut.launch_steps()));
+    const size_t problem = sizeof(double) * (2 * (size_t)p * p + 2 * (size_t)p + 1) * (size_t)K;
+    block = forced > 0 ? forced : (int)std::max<size_t>(1, CV_PATH_BLOCK_BYTES / problem);
+    block = std::min(block, L);
+    blocks = (L + block - 1) / block;
+    reps = (int)std::min<uint64_t>((uint64_t)block * K, room);
+    launches = 0;
+    for (int l0 = 0; l0 < L; l0 += block) {
+      const uint64_t n = (uint64_t)std::min(block, L - l0) * K, r = std::min(n, room);
+      launches += ((n + r - 1) / r) * cut.launches;
+    }
   }
-  return P;
-}
+};
 CvPathPlan cv_path_columns_plan(int p, int K, int L, int forced) {
-  const uint64_t n_high = 1ull << (p - subsets_low_features(p));
-  return cv_path_plan(n_high, std::max<uint64_t>(1, SUBSETS_PER_LAUNCH / exact_units(n_high)), SUBSETS_PER_LAUNCH, p, K,
-                      L, forced);
+  return CvPathPlan(EnumCut(p), SUBSETS_PER_LAUNCH, p, K, L, forced);
 }
 CvPathPlan cv_path_groups_plan(const GroupLayout& G, int K, int L, int forced) {
-  const uint64_t n_high = 1ull << G.gh;
-  return cv_path_plan(n_high, groups_steps(G, exact_units(n_high)), std::min<uint64_t>(1ull << 20, groups_per_launch(G)),
-                      G.p, K, L, forced);
+  return CvPathPlan(EnumCut(G), std::min<uint64_t>(1ull << 20, groups_per_launch(G)), G.p, K, L, forced);
 }
 
 // regs [L], L and block of both entry points
@@ -5995,30 +5763,20 @@ int cv_path_check(lsspa_ctx* ctx, const char* name, const double* regs, int32_t 
   return LSSPA_OK;
 }
 
-void cv_path_rep_inv_yy(SubsetArgs& a, const double* inv_yy) { a.inv_yy = inv_yy; }
-void cv_path_rep_inv_yy(GroupArgs& a, const double* inv_yy) { a.inv_yy_rep = inv_yy; }
-
 // a0 with the path's problems from replicate e0 on
 template <typename Args>
-Args cv_path_args(const CvWork& W, const Args& a0, int e0, int32_t* info) {
-  const CvWork::Path& Q = W.path;
-  const size_t p = (size_t)W.p;
+Args cv_path_args(const CvWork::Path& Q, int p, const Args& a0, int e0) {
   Args a = a0;
-  a.G = Q.G.ptr + (size_t)e0 * p * p;
-  a.H = Q.H.ptr + (size_t)e0 * p * p;
-  a.g = Q.g.ptr + (size_t)e0 * p;
-  a.h = Q.h.ptr + (size_t)e0 * p;
-  cv_path_rep_inv_yy(a, Q.inv_yy.ptr + e0);
-  a.info = info;
+  rep_view(a, p, e0, Q.G.ptr, Q.g.ptr, Q.H.ptr, Q.h.ptr, Q.inv_yy.ptr, Q.info.ptr);
   return a;
 }
 
-// One block: the problems of the nl ridge values regs (host) into W.path, their enumeration -- launch(a, s0, s1, ne):
-// steps s0 .. s1 - 1 of every unit for the ne replicates behind a -- and the tables' sums into Q.out [nl K][cols].
-// a0: the call's arguments but for the problems' pointers; ev / l: the call's events and launches so far.
+// One block: the problems of the nl ridge values regs (host) into W.path, their enumeration (rep_enumerate with the
+// entry point's launch) and the tables' sums into Q.out [nl K][cols].  a0: the call's arguments but for the problems'
+// pointers; t: the call's timer.
 template <typename Args, typename Launch>
 int cv_path_block(lsspa_ctx* ctx, const CvPathPlan& P, int cols, const double* regs, int nl, const Args& a0,
-                  Launch&& launch, std::vector<hipEvent_t>& ev, size_t& l) {
+                  Launch&& launch, LaunchTimer& t) {
   CvWork& W = ctx->cv;
   CvWork::Path& Q = W.path;
   hipStream_t st = ctx->stream;
@@ -6032,27 +5790,15 @@ int cv_path_block(lsspa_ctx* ctx, const CvPathPlan& P, int cols, const double* r
   TRY(dev_alloc(ctx, Q.h, (size_t)n * p));
   TRY(dev_alloc(ctx, Q.inv_yy, (size_t)n));
   TRY(dev_alloc(ctx, Q.info, (size_t)n));
-  TRY(dev_alloc(ctx, Q.part, (size_t)reps * P.units * cols));
+  TRY(dev_alloc(ctx, Q.part, (size_t)reps * P.cut.units * cols));
   TRY(dev_alloc(ctx, Q.out, (size_t)n * cols));
   HIPCHK(hipStreamSynchronize(st));            // the copy is from the caller's array; a block before this one is done
   HIPCHK(hipMemcpy(Q.regs.ptr, regs, sizeof(double) * nl, hipMemcpyHostToDevice));
   HIPCHK(launch_cv_path_finalize(W.S.ptr, W.nf.ptr, Q.regs.ptr, nl, W.n, p, K, Q.G.ptr, Q.g.ptr, Q.H.ptr, Q.h.ptr,
                                  Q.inv_yy.ptr, st));
   HIPCHK(hipMemsetAsync(Q.info.ptr, 0, sizeof(int32_t) * n, st));
-  for (int e0 = 0; e0 < n; e0 += reps) {
-    const int ne = std::min(reps, n - e0);
-    HIPCHK(hipMemsetAsync(Q.part.ptr, 0, sizeof(double) * (size_t)ne * P.units * cols, st));
-    Args a = cv_path_args(W, a0, e0, Q.info.ptr + e0);
-    a.per = P.per;
-    a.part = Q.part.ptr;
-    for (uint64_t s0 = 0; s0 < P.per; s0 += P.steps, ++l) {
-      HIPCHK(hipEventRecord(ev[2 * l], st));
-      HIPCHK(launch(a, s0, std::min(P.per, s0 + P.steps), ne));
-      HIPCHK(hipEventRecord(ev[2 * l + 1], st));
-    }
-    HIPCHK(launch_subsets_reduce(Q.part.ptr, (int64_t)P.units, cols, Q.out.ptr + (size_t)e0 * cols, st, ne));
-  }
-  return LSSPA_OK;
+  return rep_enumerate(ctx, t, P.cut, n, reps, cols, Q.part.ptr, Q.out.ptr,
+                       [&](int e0) { return cv_path_args(Q, p, a0, e0); }, launch);
 }
 
 int cv_path_shapley(lsspa_ctx* ctx, const double* regs, int L, int block, double* phi, double* phi_fold,
@@ -6063,9 +5809,7 @@ int cv_path_shapley(lsspa_ctx* ctx, const double* regs, int L, int block, double
   hipStream_t st = ctx->stream;
   const int p = W.p, K = W.K, cols = p + 1;
   const CvPathPlan P = cv_path_columns_plan(p, K, L, block);
-  std::vector<hipEvent_t> ev(2 * (size_t)P.launches, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  LaunchTimer t;
   const SubsetArgs a0 = cv_subset_args(W, 0, W.info.ptr);    // p, q, the weights and the pivot test
   const uint64_t full = (1ull << p) - 1ull;                   // p <= 32
   TRY(dev_alloc(ctx, Q.masks, 1));
@@ -6075,20 +5819,20 @@ int cv_path_shapley(lsspa_ctx* ctx, const double* regs, int L, int block, double
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipMemcpy(Q.masks.ptr, &full, sizeof full, hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(Q.dinfo.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
-  size_t l = 0;
   for (int l0 = 0; l0 < L; l0 += P.block) {
     const int nl = std::min(P.block, L - l0);
     TRY(cv_path_block(ctx, P, cols, regs + l0, nl, a0,
                       [&](const SubsetArgs& a, uint64_t s0, uint64_t s1, int ne) {
-                        return launch_subsets_enum(a, P.units, s0, s1, false, st, ne);
+                        return launch_subsets_enum(a, P.cut.units, s0, s1, false, st, ne);
                       },
-                      ev, l));
+                      t));
     double* fold = Q.phi.ptr;
     double* sum = Q.phi.ptr + (size_t)nl * K * p;
     HIPCHK(launch_cv_path_foldsum(Q.out.ptr, p, K, nl, fold, sum, st));
     // each fold's share of the R^2 of the full model, ridge value by ridge value: cv_values on the path's problems
     for (int i = 0; i < nl; ++i) {
-      SubsetArgs a = cv_path_args(W, a0, i * K, Q.dinfo.ptr);
+      SubsetArgs a = cv_path_args(Q, p, a0, i * K);
+      a.info = Q.dinfo.ptr;
       a.per = 1;
       double* v = Q.vals.ptr + (size_t)i * (K + 1);
       HIPCHK(launch_subsets_cv_debug(a, K, Q.masks.ptr, 1, v, v + 1, st));
@@ -6100,7 +5844,7 @@ int cv_path_shapley(lsspa_ctx* ctx, const double* regs, int L, int block, double
                             sizeof(double) * K, (size_t)nl, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  return cv_enum_timing(ctx, ev, l);
+  return keep_timing(ctx, W, t);
 }
 
 int cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, const double* regs, int L, int block,
@@ -6114,9 +5858,7 @@ int cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, con
   hipStream_t st = ctx->stream;
   const int K = W.K, ng = G.ng, cols = ng + 1;
   const CvPathPlan P = cv_path_groups_plan(G, K, L, block);
-  std::vector<hipEvent_t> ev(2 * (size_t)P.launches, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  LaunchTimer t;
   const GroupArgs a0 = cv_group_args(W, G, 0, W.info.ptr);   // the layout, the weights, the table and the pivot test
   // all groups and the baseline alone (the same mask in the layout's numbering and the caller's)
   const uint64_t both[2] = {ng < 64 ? (1ull << ng) - 1ull : ~0ull, 0ull};
@@ -6128,19 +5870,19 @@ int cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, con
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipMemcpy(Q.masks.ptr, both, sizeof both, hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(Q.dinfo.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS, st));
-  size_t l = 0;
   for (int l0 = 0; l0 < L; l0 += P.block) {
     const int nl = std::min(P.block, L - l0);
     TRY(cv_path_block(ctx, P, cols, regs + l0, nl, a0,
                       [&](const GroupArgs& a, uint64_t s0, uint64_t s1, int ne) {
-                        return launch_groups_enum(a, P.units, s0, s1, false, st, ne);
+                        return launch_groups_enum(a, P.cut.units, s0, s1, false, st, ne);
                       },
-                      ev, l));
+                      t));
     double* fold = Q.phi.ptr;
     double* sum = Q.phi.ptr + (size_t)nl * K * ng;
     HIPCHK(launch_cv_path_groups_foldsum(Q.out.ptr, ng, K, nl, G.gid, fold, sum, st));
     for (int i = 0; i < nl; ++i) {
-      GroupArgs a = cv_path_args(W, a0, i * K, Q.dinfo.ptr);
+      GroupArgs a = cv_path_args(Q, W.p, a0, i * K);
+      a.info = Q.dinfo.ptr;
       a.per = 1;
       double* u = Q.vals.ptr + (size_t)i * vs;
       HIPCHK(launch_groups_cv_debug(a, K, Q.masks.ptr, 2, u, u + 2, st));
@@ -6154,7 +5896,7 @@ int cv_path_groups_shapley(lsspa_ctx* ctx, const int32_t* labels, int32_t g, con
                             sizeof(double) * K, (size_t)nl, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  return cv_enum_timing(ctx, ev, l);
+  return keep_timing(ctx, W, t);
 }
 
 }  // namespace
@@ -6192,8 +5934,8 @@ int lsspa_debug_cv_path_plan(int32_t p, int32_t K, int32_t L, int32_t block, int
   if (!plan || p < 1 || p > SUBSETS_MAX_P || K < 2 || K > CV_MAX_FOLDS || L < 1 || L > CV_PATH_MAX_REGS || block < 0)
     return LSSPA_ERR_ARG;
   const CvPathPlan P = cv_path_columns_plan(p, K, L, block);
-  const int64_t out[8] = {(int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, P.block, P.blocks, P.reps,
-                          (int64_t)P.launches, (int64_t)P.bound};
+  const int64_t out[8] = {(int64_t)P.cut.units, (int64_t)P.cut.per, (int64_t)P.cut.launch_steps(), P.block, P.blocks,
+                          P.reps, (int64_t)P.launches, (int64_t)P.bound};
   std::copy(out, out + 8, plan);
   return LSSPA_OK;
 } catch (...) {
@@ -6207,8 +5949,9 @@ int lsspa_debug_cv_path_groups_plan(const int32_t* labels, int32_t p, int32_t g,
       block < 0 || groups_layout(labels, p, g, G))
     return LSSPA_ERR_ARG;
   const CvPathPlan P = cv_path_groups_plan(G, K, L, block);
-  const int64_t out[12] = {G.gl, G.gh, G.ql, G.nb, (int64_t)P.units, (int64_t)P.per, (int64_t)P.steps, P.block, P.blocks,
-                           P.reps, (int64_t)P.launches, (int64_t)P.bound};
+  const int64_t out[12] = {G.gl, G.gh, G.ql, G.nb, (int64_t)P.cut.units, (int64_t)P.cut.per,
+                           (int64_t)P.cut.launch_steps(), P.block, P.blocks, P.reps, (int64_t)P.launches,
+                           (int64_t)P.bound};
   std::copy(out, out + 12, plan);
   return LSSPA_OK;
 } catch (...) {
@@ -6320,7 +6063,7 @@ int multi_args(lsspa_ctx* ctx, MultiWork& W, int64_t first, int64_t count, Multi
   a.p = p;
   a.q = subsets_low_features(p);
   a.count = (int)count;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.piv_tol = exact_piv_tol(p);
   a.info = W.info.ptr;
   return LSSPA_OK;
 }
@@ -6441,7 +6184,7 @@ int multi_group_args(lsspa_ctx* ctx, MultiWork& W, const int32_t* labels, int32_
   a.p = p; a.ng = L.ng; a.nb = L.nb;
   a.gl = L.gl; a.gh = L.gh; a.ql = L.ql;
   a.count = (int)count;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.piv_tol = exact_piv_tol(p);
   a.info = W.info.ptr;
   return LSSPA_OK;
 }
@@ -6728,11 +6471,7 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_
   for (int64_t i = 0; i < n; ++i)
     if (masks[i] & ~full) return ctx->fail(LSSPA_ERR_ARG, "a mask names a group beyond g");
   if (n == 0) return LSSPA_OK;
-  // bit k = group k  ->  the layout's numbering (low groups first)
-  std::vector<uint64_t> lay((size_t)n, 0);
-  for (int64_t i = 0; i < n; ++i)
-    for (int r = 0; r < L.ng; ++r)
-      if ((masks[i] >> L.gid[r]) & 1ull) lay[i] |= 1ull << r;
+  const std::vector<uint64_t> lay = layout_masks(L, masks, n);
   TRY(dev_alloc(ctx, W.masks, (size_t)n));
   TRY(dev_alloc(ctx, W.vals, (size_t)n * m));
   HIPCHK(hipMemcpy(W.masks.ptr, lay.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
@@ -6959,7 +6698,7 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
   a.per_sample = per;
   a.count = a.m = m;
   a.lifts = W.lifts.ptr;
-  a.piv_tol = 16.0 * (double)p * 2.220446049250313e-16;
+  a.piv_tol = exact_piv_tol(p);
   a.info = W.info.ptr;
   a.ng = g;
   a.n_cols = g ? (int)W.map.cols.size() : 0;
