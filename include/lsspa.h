@@ -803,6 +803,70 @@ int lsspa_multi_lift_info(lsspa_ctx* ctx, int32_t* info);
 int lsspa_multi_lift_timing(const lsspa_ctx* ctx, double* gram_ms, double* batch_ms, double* stats_ms);
 int lsspa_multi_lift_free(lsspa_ctx* ctx);
 
+/* SAMPLED attribution of the K-FOLD CROSS-VALIDATED R^2 (p <= 127): the game of lsspa_cv_load -- fold problem f trained
+ * on the other folds' rows and tested on fold f, every fold divided by the pooled ||y||^2 (the definition above
+ * lsspa_cv_load) -- estimated from sampled orderings.  A sample's lift vector is sum_f lift_f(pi) for ONE ordering pi
+ * shared by all folds.  One launch of csrc/k_small.hip's fold-problem instantiations runs a cut of the batch with the
+ * grid (orderings, K): blockIdx.y selects the fold problem, addressed at one stride; the ordering's p lifts are stored to
+ * raw[ordering][fold][p] by plain stores.  cv_lift_fold_kernel (csrc/k_cv.hip) takes raw to batch[sample][K + 1][d], rows
+ * 0 .. K-1 the folds and row K their sum in ascending fold order, and launch_multi_lift_stats folds that into the running
+ * (n, mean, M2).  fp64 throughout, no atomics anywhere.  The family has state of its own: the loaded problem, lsspa_cv_*,
+ * lsspa_multi_lift_* and every other store are not touched by any call below.
+ *   lsspa_cv_lift_load  : arguments as lsspa_cv_load's.  Limits: 1 <= p <= LSSPA_CV_LIFT_MAX_P, 2 <= K <= 32, fold labels
+ *                     0 .. K-1, no empty fold, every fold at least p rows (H_f must have a Cholesky factor; the message
+ *                     names the fold and its size), y not identically zero; each refusal is LSSPA_ERR_ARG naming the
+ *                     limit, before any GPU work.  The rows [X | y] are packed SORTED BY FOLD, stable in row order, so that
+ *                     fold f is a contiguous slice; the Gram reduction of lsspa_reduce (any width) runs once per slice
+ *                     for S_f, and the K problems are finalised by lsspa_cv_load's expressions in its order:
+ *                     G_f = (sum_{j != f} S_j) / (N - n_f) + reg I with j ascending (no "total minus S_f"), H_f = S_f,
+ *                     one pooled 1 / ||y||^2.  The two loads reduce the rows in different orders: their problems agree
+ *                     to round-off, not bitwise.  Clears the statistics, the info words and a player map.
+ *   lsspa_cv_lift_set_players : groups of columns as the players; meaning and reset rules are those of
+ *                     lsspa_multi_lift_set_players (labels [p], -1 the baseline, 0 .. g-1; NULL, 0 clears; setting or
+ *                     clearing resets the statistics and the info words; a load and lsspa_cv_lift_free drop the map).
+ *                     With a map d = g, else d = p.
+ *   lsspa_cv_lift_batch : perms [B][d], every row a permutation of 0 .. d-1 (else LSSPA_ERR_ARG).  Sample s is ordering
+ *                     s, with antithetical != 0 that ordering and its reverse (with a map: the reversed group ordering,
+ *                     the baseline first in both; rows are expanded on the host exactly as lsspa_multi_lift_batch's).
+ *                     fold_lifts_out [B][K][d] and lifts_out [B][d] may be NULL.  accumulate != 0 folds the batch into
+ *                     the running statistics.  The batch is cut into launches of whole samples: at most 2^16 workgroups
+ *                     (2^13 of the LDS-resident form, which runs one workgroup a compute unit) and 256 MB of raw lifts a
+ *                     launch, a function of B, K, p and d alone.  Returns when the batch is done.
+ *   lsspa_cv_lift_get   : n, mean [K + 1][d], m2 [K + 1][d] (any may be NULL): rows 0 .. K-1 the folds, row K the sum.
+ *   lsspa_cv_lift_reset : n = 0, the info words cleared.
+ *   lsspa_cv_lift_get_problem : G [p][p], g [p], H [p][p], h [p], inv_yy of fold problem f as the device computed it.
+ *   lsspa_cv_lift_info  : info [K], bit LSSPA_INFO_NOT_PD of word f: a pivot of G_f or H_f failed the relative test
+ *                     16 p eps in some ordering since the last reset.
+ *   lsspa_cv_lift_timing : device ms of the last load's Gram side (pack to finalise), of the last batch's lift launches
+ *                     and of its fold and statistics launches.
+ *   lsspa_cv_lift_free  : frees everything of the family.
+ *   lsspa_debug_cv_lift_plan : host only, no context, no GPU.  plan [8] = block rows nb = ceil((p + 1) / 16), the kernel
+ *                     form (0 register-resident, 1 LDS-resident), workgroups per sample, samples per launch, launches,
+ *                     LDS bytes of a workgroup, its threads, 0.  LSSPA_ERR_ARG outside the limits.
+ * LSSPA_ERR_STATE before a load (lsspa_cv_lift_free and lsspa_cv_lift_timing excepted); LSSPA_ERR_NOMEM when device
+ * memory runs out.
+ * Contract: two calls agree bitwise.  The bits of a sample's fold lifts and of its sum depend on the fold problems, the
+ * ordering, p and K only -- not on B, on the other orderings, on how a batch is cut into launches or calls, or on
+ * accumulate.  lifts_out[s] has exactly the bits of the ascending fold sum ((l_0 + l_1) + l_2) + .. of
+ * fold_lifts_out[s].  An antithetical sample has the bits of 0.5 * a + 0.5 * b of the two orderings run as plain
+ * samples.  A group lift has the bits of the ascending-column fold (from 0.0) of the column call on the expanded rows.
+ * Not built: fp32, several ranks, checkpoints, the device error estimator, the history, and a sampled CV of the
+ * interaction values. */
+#define LSSPA_CV_LIFT_MAX_P 127
+int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+                       const int32_t* fold_ids /* [N] host */, int32_t K, double reg, int32_t dtype, int32_t location);
+int lsspa_cv_lift_set_players(lsspa_ctx* ctx, const int32_t* labels /* [p] or NULL */, int32_t g);
+int lsspa_cv_lift_batch(lsspa_ctx* ctx, const int32_t* perms /* [B][d] */, int64_t B, int32_t antithetical,
+                        double* fold_lifts_out /* [B][K][d] or NULL */, double* lifts_out /* [B][d] or NULL */,
+                        int32_t accumulate);
+int lsspa_cv_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean /* [K + 1][d] */, double* m2 /* [K + 1][d] */);
+int lsspa_cv_lift_reset(lsspa_ctx* ctx);
+int lsspa_cv_lift_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double* H, double* h, double* inv_yy);
+int lsspa_cv_lift_info(lsspa_ctx* ctx, int32_t* info /* [K] */);
+int lsspa_cv_lift_timing(const lsspa_ctx* ctx, double* gram_ms, double* batch_ms, double* stats_ms);
+int lsspa_cv_lift_free(lsspa_ctx* ctx);
+int lsspa_debug_cv_lift_plan(int32_t p, int32_t d, int32_t K, int64_t B, int32_t antithetical, int64_t* plan /* [8] */);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

@@ -133,7 +133,12 @@ __device__ __forceinline__ void trailing_tiles(double* M, const int (&To)[NT], c
 
 }  // namespace
 
-__global__ __launch_bounds__(512) void small_p_kernel(SmallArgs a) {
+// FOLD: the fold-problem instantiation (launch_small_folds): blockIdx.y is the fold, whose problem lies behind the
+// launch's at one stride (SmallFolds); the fold index costs scalar registers and address arithmetic only.  The
+// ordering's p lifts are stored to lifts[ordering][fold][p] -- no atomicAdd of the pair's halves: K folds adding into one
+// destination would leave the order of the sum open -- and the pivot flag goes to the fold's own info word.
+template <bool FOLD>
+__device__ __forceinline__ void small_p_body(const SmallArgs& a, const SmallFolds& fo) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int nb = a.nb, p = a.p;
   const int ntri = nb * (nb + 1) / 2;
@@ -155,6 +160,9 @@ __global__ __launch_bounds__(512) void small_p_kernel(SmallArgs a) {
   const int ord = blockIdx.x;
   const int32_t* perm = a.perms + (int64_t)(a.fwd_only ? ord >> 1 : ord) * p;
   const bool backwards = a.fwd_only && (ord & 1);
+  // the fold's problem: offsets that are zero, and folded away, without FOLD (the arguments stay where they are: a copy
+  // of them indexed by the wave would live in scratch)
+  const int64_t fmat = FOLD ? (int64_t)blockIdx.y * fo.mat : 0, fvec = FOLD ? (int64_t)blockIdx.y * fo.vec : 0;
 
   SSTAMP(0);
   if (tid < 128) s_perm[tid] = (tid < p) ? perm[backwards ? p - 1 - tid : tid] : 0;
@@ -165,9 +173,9 @@ __global__ __launch_bounds__(512) void small_p_kernel(SmallArgs a) {
   // ---- permuted gather of both matrices (lower blocks), augmented row p, identity below ----------------------
   {
     double* const M = half ? M1 : M0;
-    const double* __restrict__ S = a.S[half];
-    const double* __restrict__ sv = a.s[half];
-    const double aug = a.aug[half];
+    const double* __restrict__ S = a.S[half] + fmat;
+    const double* __restrict__ sv = a.s[half] + fvec;
+    const double aug = FOLD ? fo.aug[2 * blockIdx.y + half] : a.aug[half];
     const int r = t2 >> 4, c = t2 & 15;
     const int swrc = sw(r, c);
     // every index this thread needs, then every element: all of a thread's (up to 36) scattered 8-byte loads are in
@@ -377,15 +385,22 @@ __global__ __launch_bounds__(512) void small_p_kernel(SmallArgs a) {
     sacc += __shfl_xor(sacc, 1);
     sacc += __shfl_xor(sacc, 2);
     if (j < p && q == 0) {
-      const double lift = s_z[j] * sacc / a.y_norm_sq;
-      double* dst = a.lifts + (int64_t)(ord / a.per_sample) * p + s_perm[j];
-      if (a.per_sample == 2) atomicAdd(dst, 0.5 * lift);   // the pair's two terms commute: order-independent sum
-      else *dst = lift;
+      if constexpr (FOLD) {
+        a.lifts[((int64_t)ord * gridDim.y + blockIdx.y) * p + s_perm[j]] = s_z[j] * sacc * fo.inv_yy[blockIdx.y];
+      } else {
+        const double lift = s_z[j] * sacc / a.y_norm_sq;
+        double* dst = a.lifts + (int64_t)(ord / a.per_sample) * p + s_perm[j];
+        if (a.per_sample == 2) atomicAdd(dst, 0.5 * lift);   // the pair's two terms commute: order-independent sum
+        else *dst = lift;
+      }
     }
   }
-  if (tid == 0 && s_bad) atomicOr(a.info, 1);
+  if (tid == 0 && s_bad) atomicOr(FOLD ? a.info + blockIdx.y : a.info, 1);
   SSTAMP(7);
 }
+
+__global__ __launch_bounds__(512) void small_p_kernel(SmallArgs a) { small_p_body<false>(a, SmallFolds{}); }
+__global__ __launch_bounds__(512) void small_p_fold_kernel(SmallArgs a, SmallFolds fo) { small_p_body<true>(a, fo); }
 
 // ---- the register-resident form (round 3) ---------------------------------------------------------------------
 // What bounds the kernel above is not work but the number of pivot chains a CU has in flight: LDS holds two matrices,
@@ -421,9 +436,8 @@ constexpr int small_reg_lds_doubles(int nb) { return small_reg_vregion(nb) + (nb
 // five (256), three below (168); LDS lets as many workgroups in
 constexpr int small_reg_waves(int nb) { return nb <= 3 ? 3 : (nb <= 4 ? 2 : 1); }
 
-template <int NB>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(small_reg_waves(NB), small_reg_waves(NB))))
-void small_reg_kernel(SmallArgs a) {
+template <int NB, bool FOLD>
+__device__ __forceinline__ void small_reg_body(const SmallArgs& a, const SmallFolds& fo) {
   constexpr int NTRI = NB * (NB + 1) / 2;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int VREG = small_reg_vregion(NB);
@@ -445,12 +459,15 @@ void small_reg_kernel(SmallArgs a) {
   const int ord = blockIdx.x;
   const int32_t* perm = a.perms + (int64_t)(a.fwd_only ? ord >> 1 : ord) * p;
   const bool backwards = a.fwd_only && (ord & 1);
+  // the fold's problem: offsets that are zero, and folded away, without FOLD (the arguments stay where they are: a copy
+  // of them indexed by the wave would live in scratch)
+  const int64_t fmat = FOLD ? (int64_t)blockIdx.y * fo.mat : 0, fvec = FOLD ? (int64_t)blockIdx.y * fo.vec : 0;
   RSTAMP(0);
   {
     const int src = (tid < p) ? perm[backwards ? p - 1 - tid : tid] : 0;
     s_perm[tid] = src;
-    s_z[tid] = a.s[0][src];          // the permuted right-hand sides g_pi, h_pi (row p of the two matrices) until the
-    s_y[tid] = a.s[1][src];          // factorisations have produced z and y~, which take their place
+    s_z[tid] = (a.s[0] + fvec)[src]; // the permuted right-hand sides g_pi, h_pi (row p of the two matrices) until the
+    s_y[tid] = (a.s[1] + fvec)[src]; // factorisations have produced z and y~, which take their place
   }
   if (tid == 0) {
     s_bad = 0;
@@ -465,8 +482,8 @@ void small_reg_kernel(SmallArgs a) {
   // per CU in flight that alone was 29 k cycles of the first version's 167 k -- the L1 passes a line per clock).  The
   // sixteen source rows of a block column are fetched whole instead (coalesced, seven lines a row) into the LDS region
   // that will hold L_t later, and the lanes pick from there. ---------------------------------------------------------
-  const double* __restrict__ S = a.S[wv];
-  const double aug = a.aug[wv];
+  const double* __restrict__ S = a.S[wv] + fmat;
+  const double aug = FOLD ? fo.aug[2 * blockIdx.y + wv] : a.aug[wv];
   const double* const svp = wv ? s_y : s_z;         // s[perm[j]]
   d4 U[NTRI];
   double* const tol = s_tol + wv * 128;
@@ -736,16 +753,22 @@ void small_reg_kernel(SmallArgs a) {
     for (int pass = 0; pass < 2; ++pass) {
       const int j = lane + 64 * pass;
       if (j < p) {
-        const double lift = s_z[j] * racc[pass] / a.y_norm_sq;
-        double* dst = a.lifts + (int64_t)(ord / a.per_sample) * p + s_perm[j];
-        if (a.per_sample == 2) atomicAdd(dst, 0.5 * lift);   // the pair's two terms commute: order-independent sum
-        else *dst = lift;
-        lsum += lift;
+        if constexpr (FOLD) {
+          a.lifts[((int64_t)ord * gridDim.y + blockIdx.y) * p + s_perm[j]] =
+              s_z[j] * racc[pass] * fo.inv_yy[blockIdx.y];
+        } else {
+          const double lift = s_z[j] * racc[pass] / a.y_norm_sq;
+          double* dst = a.lifts + (int64_t)(ord / a.per_sample) * p + s_perm[j];
+          if (a.per_sample == 2) atomicAdd(dst, 0.5 * lift);   // the pair's two terms commute: order-independent sum
+          else *dst = lift;
+          lsum += lift;
+        }
       }
     }
     // the ordering's lifts telescope to the full model's R^2 (sum_check_kernel in k_lift.hip makes this check per
     // sample by a launch of its own; here the wave holds all p lifts, and a dependent launch is 4 % of a p = 100 group)
-    if (a.sum_tol >= 0.0) {
+    // (the fold instantiation makes no such check: a fold's lifts sum to the fold's share, and the driver checks the sum)
+    if (!FOLD && a.sum_tol >= 0.0) {
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) lsum += __shfl_xor(lsum, o, 64);
       if (lane == 0) {
@@ -757,8 +780,20 @@ void small_reg_kernel(SmallArgs a) {
       }
     }
   }
-  if (tid == 0 && s_bad) atomicOr(a.info, 1);
+  if (tid == 0 && s_bad) atomicOr(FOLD ? a.info + blockIdx.y : a.info, 1);
   RSTAMP(7);
+}
+
+template <int NB>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(small_reg_waves(NB), small_reg_waves(NB))))
+void small_reg_kernel(SmallArgs a) {
+  small_reg_body<NB, false>(a, SmallFolds{});
+}
+
+template <int NB>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(small_reg_waves(NB), small_reg_waves(NB))))
+void small_reg_fold_kernel(SmallArgs a, SmallFolds fo) {
+  small_reg_body<NB, true>(a, fo);
 }
 
 size_t small_p_lds_bytes(int nb) {
@@ -778,6 +813,48 @@ static hipError_t launch_small_reg(const SmallArgs& a, hipStream_t st) {
   hipError_t e = grant.ensure(reinterpret_cast<const void*>(small_reg_kernel<NB>), bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(small_reg_kernel<NB>, dim3(a.n_ord), dim3(128), bytes, st, a);
+  return hipGetLastError();
+}
+
+template <int NB>
+static hipError_t launch_small_reg_fold(const SmallArgs& a, const SmallFolds& fo, hipStream_t st) {
+  const size_t bytes = (size_t)small_reg_lds_doubles(NB) * sizeof(double) + 128 * sizeof(int32_t);
+  static DynLdsGrant grant;   // per device, per instance
+  hipError_t e = grant.ensure(reinterpret_cast<const void*>(small_reg_fold_kernel<NB>), bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(small_reg_fold_kernel<NB>, dim3(a.n_ord, fo.folds), dim3(128), bytes, st, a, fo);
+  return hipGetLastError();
+}
+
+size_t small_folds_lds_bytes(int nb) {
+  return nb <= 7 ? (size_t)small_reg_lds_doubles(nb) * sizeof(double) + 128 * sizeof(int32_t) : small_p_lds_bytes(nb);
+}
+
+// The fold-problem launch (lsspa_cv_lift_batch): grid (orderings, folds), the kernel form launch_small_p picks for nb.
+hipError_t launch_small_folds(const SmallArgs& a, const SmallFolds& fo, hipStream_t st) {
+  if (!small_p_eligible(a.p) || a.nb != (a.p + 1 + 15) / 16 || a.n_ord < 1 || a.n_ord > SMALL_FOLDS_MAX_GRID ||
+      (a.per_sample != 1 && a.per_sample != 2) || (a.n_ord % a.per_sample) != 0 || !a.S[0] || !a.S[1] || !a.s[0] ||
+      !a.s[1] || !a.perms || !a.lifts || !a.info || (a.fwd_only && a.per_sample != 2) || fo.folds < 2 ||
+      fo.folds > CV_MAX_FOLDS || (int64_t)a.n_ord * fo.folds > SMALL_FOLDS_MAX_GRID || !fo.aug || !fo.inv_yy ||
+      a.ld_src < a.p + 1 || (a.ld_src & 1) || fo.mat < (int64_t)a.p * a.ld_src || (fo.mat & 1) ||
+      fo.vec < a.p || (reinterpret_cast<uintptr_t>(a.S[0]) & 15) || (reinterpret_cast<uintptr_t>(a.S[1]) & 15))
+    return hipErrorInvalidValue;      // (the register-resident gather reads pairs of columns: rows of even length, one
+                                      // column of room behind column p - 1, 16-byte aligned)
+  switch (a.nb) {
+    case 1: return launch_small_reg_fold<1>(a, fo, st);
+    case 2: return launch_small_reg_fold<2>(a, fo, st);
+    case 3: return launch_small_reg_fold<3>(a, fo, st);
+    case 4: return launch_small_reg_fold<4>(a, fo, st);
+    case 5: return launch_small_reg_fold<5>(a, fo, st);
+    case 6: return launch_small_reg_fold<6>(a, fo, st);
+    case 7: return launch_small_reg_fold<7>(a, fo, st);
+    default: break;
+  }
+  const size_t bytes = small_p_lds_bytes(a.nb);
+  static DynLdsGrant grant;
+  hipError_t e = grant.ensure(reinterpret_cast<const void*>(small_p_fold_kernel), bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(small_p_fold_kernel, dim3(a.n_ord, fo.folds), dim3(512), bytes, st, a, fo);
   return hipGetLastError();
 }
 

@@ -79,6 +79,24 @@ struct SmallArgs {
   double r2, sum_tol, sum_quiet;
 };
 bool small_p_checks_sum(const SmallArgs& a);
+// One ordering through `folds` different reduced problems in one launch (lsspa_cv_lift_batch): grid (n_ord, folds), the
+// kernel form launch_small_p picks for nb (register-resident for nb <= 7, LDS-resident for eight block rows).  Fold
+// f = blockIdx.y has its problem behind the launch's at one stride -- S[.] + f mat, s[.] + f vec, the augmented rows'
+// diagonals aug[2 f + .] (SmallArgs::aug is not read), 1 / ||y||^2 = inv_yy[f], its pivot flag in info[f].  Ordering o of
+// fold f stores its p lifts, multiplied by inv_yy[f], to lifts[(o folds + f) p + .] by plain stores (per_sample and
+// fwd_only only say how perms is read: with fwd_only ordering 2 s + 1 is row s read backwards); no atomics, no sum check;
+// y_norm_sq, r2 and sum_* are not read.  ld_src is even and >= p + 1, mat even, the matrices 16-byte aligned;
+// n_ord folds <= SMALL_FOLDS_MAX_GRID.  The fold arguments are a kernel parameter of their own: the one-problem
+// kernels' arguments, and with them their code, stay what they were.
+struct SmallFolds {
+  int64_t mat, vec;
+  const double* aug;       // [folds][2]
+  const double* inv_yy;    // [folds]
+  int folds;
+};
+constexpr int64_t SMALL_FOLDS_MAX_GRID = 1 << 16;
+hipError_t launch_small_folds(const SmallArgs& a, const SmallFolds& fo, hipStream_t st);
+size_t small_folds_lds_bytes(int nb);   // dynamic LDS of a workgroup of launch_small_folds
 // host_perms.cpp: every row of perms [B][p] a permutation of 0..p-1?  (sets by AVX2 for 8 <= p <= 128, stamps otherwise;
 // _plain: the stamp loop alone, the test's comparison)
 bool all_permutations(const int32_t* perms, int B, int p, std::vector<int32_t>& mark);
@@ -530,6 +548,24 @@ hipError_t launch_cv_path_foldsum(const double* out, int p, int folds, int nl, d
                                   hipStream_t st);
 hipError_t launch_cv_path_groups_foldsum(const double* out, int ng, int folds, int nl, const int* gid, double* phi_fold,
                                          double* phi, hipStream_t st);
+// Sampled attribution of the K-fold cross-validated R^2 (lsspa_cv_lift_*; k_cv.hip, launch_small_folds), p <= 127, fp64.
+// Every matrix of the family has rows of CV_LIFT_LD doubles: the packed rows Xs, launch_gram's per-fold Grams S
+// [folds][CV_LIFT_LD][CV_LIFT_LD], the fold problems G, H [folds][CV_LIFT_LD][CV_LIFT_LD] and g, h [folds][CV_LIFT_LD].
+constexpr int CV_LIFT_MAX_P = 127, CV_LIFT_LD = 128;
+// Xs[dest[i]][:] = X[i][0 .. p-1], zero up to CV_LIFT_LD, ys[dest[i]] = y[i], i < rows (dest: the rows' places when sorted
+// by fold, a permutation of the rows: every place is written once)
+hipError_t launch_cv_lift_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32,
+                               const int32_t* dest, double* Xs, double* ys, hipStream_t st);
+// launch_cv_finalize's expressions in its order on launch_gram's buffers S; aug[f] = {2 ||y_train||^2 / (n - nf[f]) + 1,
+// 2 ||y_f||^2 + 1}, the diagonals of the augmented rows
+hipError_t launch_cv_lift_finalize(const double* S, const int32_t* nf, int64_t n, int p, int folds, double reg, double* G,
+                                   double* g, double* H, double* h, double* inv_yy, double* aug, hipStream_t st);
+// batch[s][f][k], f < folds: sample s's entry of fold f and player k from raw [n_samples * per][folds][p] -- off == NULL
+// (d == p): the ordering's lift, or 0.5 * a + 0.5 * b of the pair's (per == 2); with the player map's CSR (off [d + 1],
+// cols) the sum of group k's columns in ascending column order from 0.0 per ordering, then the pair combined --, and
+// batch[s][folds][k] = ((e_0 + e_1) + e_2) + .. in ascending fold order.  One thread per (s, k), no atomics.
+hipError_t launch_cv_lift_fold(const double* raw, int p, int folds, int per, const int32_t* off, const int32_t* cols,
+                               int d, int64_t n_samples, double* batch, hipStream_t st);
 // vals[i] = u(masks[i]) by the enumeration's own device code (test hook); masks in the layout's numbering
 hipError_t launch_groups_debug(const GroupArgs& a, const uint64_t* masks, int64_t n, double* vals, hipStream_t st);
 

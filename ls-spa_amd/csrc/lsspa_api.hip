@@ -195,6 +195,34 @@ struct MultiLiftWork {
   }
 };
 
+// What the sampled K-fold CV attribution keeps (lsspa_cv_lift_load .. lsspa_cv_lift_free): the K fold problems at the
+// one stride the fold launch reads (rows of CV_LIFT_LD doubles; G, g, H, h and the pooled 1 / ||y||^2 also on the host,
+// dense), the augmented rows' diagonals, the orderings, raw lifts and samples of one launch, the running (n, mean, M2)
+// [K + 1][d] and the last calls' timing.  Nothing of the loaded problem, lsspa_cv_*, lsspa_multi_lift_* or any other
+// store is in here.  The player map is its own (lsspa_cv_lift_set_players).
+struct CvLiftWork {
+  bool loaded = false;
+  int p = 0, K = 0;
+  int ng = 0;                              // groups of the player map (0: none)
+  PlayerMap map;
+  DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
+  std::vector<int32_t> rows;               // a launch's expanded rows on the host
+  int sd() const { return ng ? ng : p; }   // the dimension of a sample
+  DevBuf<double> G, g, H, h, inv_yy, aug;  // [K][LD][LD], [K][LD], .., [K], [K][2]
+  std::vector<double> Gh, gh, Hh, hh, yh;  // [K][p][p], [K][p], .., [K] on the host
+  DevBuf<double> raw, batch, mean, M2;     // [orderings of a launch][K][p]; [samples of a launch][K + 1][d]; the state
+  DevBuf<int32_t> perms, info;             // a launch's rows; [K] info words
+  int64_t n = 0;                           // samples folded into (mean, M2)
+  double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
+  void release() {
+    dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(aug); dev_free(raw);
+    dev_free(batch); dev_free(mean); dev_free(M2); dev_free(perms); dev_free(info); dev_free(pl_off); dev_free(pl_cols);
+    loaded = false;
+    n = 0;
+    ng = 0;
+  }
+};
+
 // What the permutation test keeps (lsspa_perm_load .. lsspa_perm_free): X and y of both sides on the device, the shared
 // G and H and the observed g, h, the index rows of two blocks of replicates (device and pinned host: the next block is
 // drawn and uploaded while this one runs), the partials of one block, and a MultiWork of its own whose response slots
@@ -364,6 +392,7 @@ struct lsspa_ctx {
   CvWork cv;                     // K-fold cross-validation (lsspa_cv_*)
   MultiWork multi;               // exact attribution of many responses at once (lsspa_multi_*)
   MultiLiftWork mlift;           // sampled attribution of many responses (lsspa_multi_lift_*)
+  CvLiftWork cvlift;             // sampled attribution of the K-fold cross-validated R^2 (lsspa_cv_lift_*)
   PermWork perm;                 // permutation test of the exact attribution (lsspa_perm_*)
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
@@ -1380,6 +1409,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->cv.release();
   ctx->multi.release();
   ctx->mlift.release();
+  ctx->cvlift.release();
   ctx->perm.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
@@ -6804,6 +6834,404 @@ int lsspa_multi_lift_free(lsspa_ctx* ctx) try {
   return LSSPA_OK;
 } catch (...) {
   return abi_caught(ctx);
+}
+
+}  // extern "C"
+
+// ---- sampled attribution of the K-fold cross-validated R^2 (k_small.hip's fold launch, k_cv.hip) ----------------------
+// The load packs the rows sorted by fold, runs the Gram reduction once per fold slice and finalises the K problems at the
+// fold launch's stride.  A batch runs as launches of whole samples: the fold launch (grid (orderings, K)) writes
+// raw [orderings][K][p], cv_lift_fold_kernel folds that to batch [samples][K + 1][d], launch_multi_lift_stats folds the
+// samples into the running (n, mean, M2) [K + 1][d].
+namespace {
+
+constexpr int64_t CVLIFT_GRID_REG = 1 << 16;       // workgroups a launch of the register-resident form takes at most
+constexpr int64_t CVLIFT_GRID_LDS = 1 << 13;       // ... of the LDS-resident form: one workgroup a compute unit, 32 rounds
+constexpr int64_t CVLIFT_RAW_DOUBLES = (256ll << 20) / 8;     // raw lifts of a launch: 256 MB at most (one sample at least)
+
+struct CvLiftPlan {
+  int nb, form, threads;
+  int64_t per_sample_wg, S, launches;
+  size_t lds;
+};
+
+// the cut of a batch: a function of B, K, p and d alone (d does not enter: the raw lifts are p wide)
+bool cvlift_plan(int64_t p, int64_t d, int64_t K, int64_t B, int antithetical, CvLiftPlan& P) {
+  if (p < 1 || p > CV_LIFT_MAX_P || d < 1 || d > p || K < 2 || K > CV_MAX_FOLDS || B < 1) return false;
+  const int64_t per = antithetical ? 2 : 1;
+  P.nb = (int)((p + 1 + 15) / 16);
+  P.form = P.nb <= 7 ? 0 : 1;
+  P.threads = P.form ? 512 : 128;
+  P.per_sample_wg = per * K;
+  const int64_t cap = P.form ? CVLIFT_GRID_LDS : CVLIFT_GRID_REG;
+  P.S = std::min(B, std::max<int64_t>(1, std::min(cap / (per * K), CVLIFT_RAW_DOUBLES / (per * K * p))));
+  P.launches = (B + P.S - 1) / P.S;
+  P.lds = small_folds_lds_bytes(P.nb);
+  return true;
+}
+
+int cvlift_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->cvlift.loaded)
+    return ctx->fail(LSSPA_ERR_STATE, "no cross-validation data loaded for sampling (lsspa_cv_lift_load comes first)");
+  return LSSPA_OK;
+}
+
+// n = 0, (mean, M2) and the info words cleared
+int cvlift_reset(lsspa_ctx* ctx) {
+  CvLiftWork& W = ctx->cvlift;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t e = (size_t)(W.K + 1) * W.p;
+  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * e));
+  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * e));
+  HIPCHK(hipMemset(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS));
+  W.n = 0;
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
+                       const int32_t* fold_ids, int32_t K, double reg, int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  char msg[240];
+  if (p > CV_LIFT_MAX_P) {
+    snprintf(msg, sizeof msg, "lsspa_cv_lift_load takes at most p = %d features (%d given): both work matrices of an "
+             "ordering, p + 1 rows each, stay in one workgroup", CV_LIFT_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (K < 2 || K > CV_MAX_FOLDS) {
+    snprintf(msg, sizeof msg, "cross-validation takes 2 .. %d folds (%d given)", CV_MAX_FOLDS, (int)K);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (!X || !y || !fold_ids || p < 1 || N < 2 || N >= (1ll << 31) || ld < p || !std::isfinite(reg) || reg < 0.0 ||
+      (dtype != LSSPA_F64 && dtype != LSSPA_F32) || (location != LSSPA_HOST && location != LSSPA_DEVICE))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_load: NULL array, p < 1, N outside 2 .. 2^31 - 1, ld < p, reg not "
+                                    "finite and >= 0, or bad dtype / location");
+  int32_t nf[CV_MAX_FOLDS] = {0};
+  for (int64_t i = 0; i < N; ++i) {
+    if (fold_ids[i] < 0 || fold_ids[i] >= K) {
+      snprintf(msg, sizeof msg, "fold_ids[%lld] = %d: fold labels must be 0 .. %d (K - 1)", (long long)i,
+               (int)fold_ids[i], (int)K - 1);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+    ++nf[fold_ids[i]];
+  }
+  for (int f = 0; f < K; ++f)
+    if (nf[f] == 0) {
+      snprintf(msg, sizeof msg, "fold %d of %d is empty: every fold needs at least one row", f, (int)K);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  for (int f = 0; f < K; ++f)
+    if (nf[f] < p) {
+      snprintf(msg, sizeof msg, "fold %d of %d has %d rows, fewer than p = %d: the Gram matrix of a fold's own rows must "
+               "have a Cholesky factor", f, (int)K, (int)nf[f], (int)p);
+      return ctx->fail(LSSPA_ERR_ARG, msg);
+    }
+  if (location == LSSPA_HOST) {          // (rows on the device: the pooled sum is looked at after the Gram passes)
+    bool any = false;
+    for (int64_t i = 0; i < N && !any; ++i)
+      any = dtype == LSSPA_F32 ? ((const float*)y)[i] != 0.f : ((const double*)y)[i] != 0.0;
+    if (!any) return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  CvLiftWork& W = ctx->cvlift;
+  W.loaded = false;
+  W.ng = 0;                // a player map belongs to the data it was set on
+  hipStream_t st = ctx->stream;
+  // every row's place when the rows are sorted by fold, stable in row order
+  std::vector<int32_t> dest((size_t)N);
+  int64_t first[CV_MAX_FOLDS + 1] = {0};
+  for (int f = 0; f < K; ++f) first[f + 1] = first[f] + nf[f];
+  {
+    int64_t at[CV_MAX_FOLDS];
+    std::copy(first, first + K, at);
+    for (int64_t i = 0; i < N; ++i) dest[(size_t)i] = (int32_t)at[fold_ids[i]]++;
+  }
+  constexpr size_t LD = CV_LIFT_LD, LL = LD * LD;
+  DevBuf<double> Xs, ys, S;
+  DevBuf<int32_t> dst_d, nf_d;
+  DevBuf<char> stage_x, stage_y;
+  struct Scratch {
+    DevBuf<double>&a, &b, &c;
+    DevBuf<int32_t>&d, &e;
+    DevBuf<char>&f, &g;
+    ~Scratch() { dev_free(a); dev_free(b); dev_free(c); dev_free(d); dev_free(e); dev_free(f); dev_free(g); }
+  } scratch{Xs, ys, S, dst_d, nf_d, stage_x, stage_y};
+  TRY(dev_alloc(ctx, Xs, (size_t)N * LD));
+  TRY(dev_alloc(ctx, ys, (size_t)N));
+  TRY(dev_alloc(ctx, S, (size_t)K * LL));
+  TRY(dev_alloc(ctx, dst_d, (size_t)N));
+  TRY(dev_alloc(ctx, nf_d, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.G, (size_t)K * LL));
+  TRY(dev_alloc(ctx, W.H, (size_t)K * LL));
+  TRY(dev_alloc(ctx, W.g, (size_t)K * LD));
+  TRY(dev_alloc(ctx, W.h, (size_t)K * LD));
+  TRY(dev_alloc(ctx, W.inv_yy, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.aug, 2 * CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.info, CV_MAX_FOLDS));
+  TRY(dev_alloc(ctx, W.mean, (size_t)(K + 1) * p));
+  TRY(dev_alloc(ctx, W.M2, (size_t)(K + 1) * p));
+  HIPCHK(hipStreamSynchronize(st));      // a previous call may still read the buffers
+  HIPCHK(hipMemcpy(dst_d.ptr, dest.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(nf_d.ptr, nf, sizeof nf, hipMemcpyHostToDevice));
+  // the columns behind p of a problem's rows are read (the register-resident gather fetches pairs), never used: zero
+  HIPCHK(hipMemsetAsync(W.G.ptr, 0, sizeof(double) * K * LL, st));
+  HIPCHK(hipMemsetAsync(W.H.ptr, 0, sizeof(double) * K * LL, st));
+  HIPCHK(hipMemsetAsync(W.g.ptr, 0, sizeof(double) * K * LD, st));
+  HIPCHK(hipMemsetAsync(W.h.ptr, 0, sizeof(double) * K * LD, st));
+  std::vector<hipEvent_t> ev(2, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev[0], st));
+  TRY(load_rows(ctx, stage_x, stage_y, X, ld, y, N, p, dtype, location,
+                [&](const void* sx, const void* sy, int64_t nr, int64_t r0) {
+                  return launch_cv_lift_pack(sx, ld, sy, nr, p, dtype == LSSPA_F32, dst_d.ptr + r0, Xs.ptr, ys.ptr, st);
+                }));
+  for (int f = 0; f < K; ++f)            // S_f: the Gram reduction on the fold's slice (gram_side waits for it)
+    TRY(gram_side(ctx, Xs.ptr + (size_t)first[f] * LD, ys.ptr + first[f], nf[f], (int64_t)LD, p, 0, S.ptr + (size_t)f * LL));
+  HIPCHK(launch_cv_lift_finalize(S.ptr, nf_d.ptr, N, p, K, reg, W.G.ptr, W.g.ptr, W.H.ptr, W.h.ptr, W.inv_yy.ptr,
+                                 W.aug.ptr, st));
+  HIPCHK(hipEventRecord(ev[1], st));
+  const size_t pp = (size_t)p * p;
+  W.Gh.resize(K * pp);
+  W.Hh.resize(K * pp);
+  W.gh.resize((size_t)K * p);
+  W.hh.resize((size_t)K * p);
+  W.yh.resize((size_t)K);
+  for (int f = 0; f < K; ++f) {
+    HIPCHK(hipMemcpy2DAsync(W.Gh.data() + f * pp, sizeof(double) * p, W.G.ptr + f * LL, sizeof(double) * LD,
+                            sizeof(double) * p, (size_t)p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpy2DAsync(W.Hh.data() + f * pp, sizeof(double) * p, W.H.ptr + f * LL, sizeof(double) * LD,
+                            sizeof(double) * p, (size_t)p, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipMemcpy2DAsync(W.gh.data(), sizeof(double) * p, W.g.ptr, sizeof(double) * LD, sizeof(double) * p, (size_t)K,
+                          hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpy2DAsync(W.hh.data(), sizeof(double) * p, W.h.ptr, sizeof(double) * LD, sizeof(double) * p, (size_t)K,
+                          hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(W.yh.data(), W.inv_yy.ptr, sizeof(double) * K, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  W.gram_ms = ms;
+  W.batch_ms = W.stats_ms = 0.0;
+  if (!(W.yh[0] > 0.0) || !std::isfinite(W.yh[0]))
+    return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
+  W.p = p;
+  W.K = K;
+  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * (size_t)(K + 1) * p));
+  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * (size_t)(K + 1) * p));
+  HIPCHK(hipMemset(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS));
+  W.n = 0;
+  W.loaded = true;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cvlift_need_loaded(ctx));
+  CvLiftWork& W = ctx->cvlift;
+  if (!labels && g != 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
+  PlayerMap map;
+  if (labels) {
+    const char* why = player_map_build(labels, W.p, g, map);
+    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  TRY(cvlift_reset(ctx));       // (waits for work in flight: a previous batch may still read the tables)
+  if (labels) {
+    TRY(dev_alloc(ctx, W.pl_off, (size_t)W.p + 1));
+    TRY(dev_alloc(ctx, W.pl_cols, (size_t)W.p));
+    HIPCHK(hipMemcpy(W.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
+    W.map = std::move(map);
+    W.ng = g;
+  } else {
+    W.ng = 0;
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int32_t antithetical, double* fold_lifts_out,
+                        double* lifts_out, int32_t accumulate) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cvlift_need_loaded(ctx));
+  CvLiftWork& W = ctx->cvlift;
+  const int p = W.p, K = W.K, g = W.ng, d = W.sd();
+  if (!perms || B < 1 || B > (int64_t)INT32_MAX / (2 * p))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_batch: perms is NULL, B < 1 or 2 B p >= 2^31");
+  if (!all_permutations(perms, (int)B, d, ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_cv_lift_batch: a row of perms is not a permutation of 0 .. g-1 (a player "
+                                        "map is set: the orderings are orderings of the groups)"
+                                      : "lsspa_cv_lift_batch: a row of perms is not a permutation of 0 .. p-1");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int per = antithetical ? 2 : 1;
+  CvLiftPlan P;
+  if (!cvlift_plan(p, d, K, B, antithetical, P)) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_batch: no launch plan");
+  const int64_t S = P.S, entries = (int64_t)(K + 1) * d;
+  const int64_t rows_per = g ? per : 1;      // rows of perms a sample takes on the device
+  TRY(dev_alloc(ctx, W.raw, (size_t)(S * per * K * p)));
+  TRY(dev_alloc(ctx, W.batch, (size_t)(S * entries)));
+  TRY(dev_alloc(ctx, W.perms, (size_t)(S * rows_per * p)));
+  if (g) W.rows.resize((size_t)(S * rows_per * p));
+  std::vector<hipEvent_t> ev(3, nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  W.batch_ms = W.stats_ms = 0.0;
+  constexpr int64_t LD = CV_LIFT_LD;
+  SmallArgs a{};
+  a.S[0] = W.G.ptr;
+  a.S[1] = W.H.ptr;
+  a.s[0] = W.g.ptr;
+  a.s[1] = W.h.ptr;
+  a.ld_src = LD;
+  a.perms = W.perms.ptr;
+  a.fwd_only = (!g && per == 2) ? 1 : 0;     // with a map both rows of a pair are explicit (the baseline stays first)
+  a.p = p;
+  a.nb = P.nb;
+  a.per_sample = per;
+  a.lifts = W.raw.ptr;
+  a.y_norm_sq = 1.0;
+  a.piv_tol = exact_piv_tol(p);
+  a.info = W.info.ptr;
+  a.sum_tol = -1.0;
+  SmallFolds fo{};
+  fo.mat = LD * LD;
+  fo.vec = LD;
+  fo.aug = W.aug.ptr;
+  fo.inv_yy = W.inv_yy.ptr;
+  fo.folds = K;
+  for (int64_t s0 = 0; s0 < B; s0 += S) {
+    const int64_t ns = std::min(S, B - s0);
+    const int32_t* src = perms + s0 * p;
+    if (g) {      // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
+      for (int64_t s = 0; s < ns; ++s)
+        for (int r = 0; r < per; ++r)
+          expand_group_row(W.map, perms + (s0 + s) * g, r, W.rows.data() + (size_t)((s * per + r) * p));
+      src = W.rows.data();
+    }
+    HIPCHK(hipMemcpyAsync(W.perms.ptr, src, sizeof(int32_t) * (size_t)(ns * rows_per * p), hipMemcpyHostToDevice,
+                          ctx->stream));
+    a.n_ord = (int)(ns * per);
+    HIPCHK(hipEventRecord(ev[0], ctx->stream));
+    HIPCHK(launch_small_folds(a, fo, ctx->stream));
+    HIPCHK(hipEventRecord(ev[1], ctx->stream));
+    HIPCHK(launch_cv_lift_fold(W.raw.ptr, p, K, per, g ? W.pl_off.ptr : nullptr, g ? W.pl_cols.ptr : nullptr, d, ns,
+                               W.batch.ptr, ctx->stream));
+    if (accumulate) {
+      HIPCHK(launch_multi_lift_stats(W.batch.ptr, entries, (int)ns, W.n, W.mean.ptr, W.M2.ptr, ctx->stream));
+      W.n += ns;
+    }
+    HIPCHK(hipEventRecord(ev[2], ctx->stream));
+    if (fold_lifts_out)
+      HIPCHK(hipMemcpy2DAsync(fold_lifts_out + s0 * K * d, sizeof(double) * K * d, W.batch.ptr, sizeof(double) * entries,
+                              sizeof(double) * K * d, (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (lifts_out)
+      HIPCHK(hipMemcpy2DAsync(lifts_out + s0 * d, sizeof(double) * d, W.batch.ptr + (size_t)K * d,
+                              sizeof(double) * entries, sizeof(double) * d, (size_t)ns, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses the buffers
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    W.batch_ms += ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    W.stats_ms += ms;
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cvlift_need_loaded(ctx));
+  CvLiftWork& W = ctx->cvlift;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t e = (size_t)(W.K + 1) * W.sd();
+  if (n) *n = W.n;
+  if (mean) HIPCHK(hipMemcpy(mean, W.mean.ptr, sizeof(double) * e, hipMemcpyDeviceToHost));
+  if (m2) HIPCHK(hipMemcpy(m2, W.M2.ptr, sizeof(double) * e, hipMemcpyDeviceToHost));
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_reset(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cvlift_need_loaded(ctx));
+  HIPCHK(hipSetDevice(ctx->device));
+  return cvlift_reset(ctx);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_get_problem(lsspa_ctx* ctx, int32_t f, double* G, double* g, double* H, double* h, double* inv_yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cvlift_need_loaded(ctx));
+  const CvLiftWork& W = ctx->cvlift;
+  if (f < 0 || f >= W.K) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_get_problem: f must be 0 .. K - 1");
+  const size_t p = (size_t)W.p, pp = p * p;
+  if (G) std::copy(W.Gh.begin() + f * pp, W.Gh.begin() + (f + 1) * pp, G);
+  if (H) std::copy(W.Hh.begin() + f * pp, W.Hh.begin() + (f + 1) * pp, H);
+  if (g) std::copy(W.gh.begin() + f * p, W.gh.begin() + (f + 1) * p, g);
+  if (h) std::copy(W.hh.begin() + f * p, W.hh.begin() + (f + 1) * p, h);
+  if (inv_yy) *inv_yy = W.yh[(size_t)f];
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_info(lsspa_ctx* ctx, int32_t* info) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(cvlift_need_loaded(ctx));
+  if (!info) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_info: info is NULL");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(info, ctx->cvlift.info.ptr, sizeof(int32_t) * ctx->cvlift.K, hipMemcpyDeviceToHost));
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_cv_lift_timing(const lsspa_ctx* ctx, double* gram_ms, double* batch_ms, double* stats_ms) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (gram_ms) *gram_ms = ctx->cvlift.gram_ms;
+  if (batch_ms) *batch_ms = ctx->cvlift.batch_ms;
+  if (stats_ms) *stats_ms = ctx->cvlift.stats_ms;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_cv_lift_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->cvlift.release();
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_cv_lift_plan(int32_t p, int32_t d, int32_t K, int64_t B, int32_t antithetical, int64_t* plan) {
+  CvLiftPlan P;
+  if (!plan || !cvlift_plan(p, d, K, B, antithetical, P)) return LSSPA_ERR_ARG;
+  plan[0] = P.nb;
+  plan[1] = P.form;
+  plan[2] = P.per_sample_wg;
+  plan[3] = P.S;
+  plan[4] = P.launches;
+  plan[5] = (int64_t)P.lds;
+  plan[6] = P.threads;
+  plan[7] = 0;
+  return LSSPA_OK;
 }
 
 }  // extern "C"

@@ -31,18 +31,20 @@ n_best <= 16 best models of every size by that cross-validated R^2, p <= 32, wit
 folds' paired values give, returning ``TopSubsetsCVResults``) and ``ls_spa_top_group_subsets_cv`` (the same over g <= 32
 groups of p <= 64 columns, returning ``TopGroupSubsetsCVResults``) and ``ls_spa_cv_path`` (``ls_spa_cv`` for a path of
 ridge values on one load, row by row its bits, with the choice of the value the folds prefer, returning
-``CVPathResults``, with ``groups=`` ``CVGroupPathResults``)
+``CVPathResults``, with ``groups=`` ``CVGroupPathResults``) and ``ls_spa_cv_sampled`` (the sampled attribution of
+that cross-validated R^2 for p <= 127, or with ``groups=`` over groups of those columns, returning ``SampledCVResults``
+and ``SampledCVGroupResults``)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupPathResults, CVGroupResults, CVPathResults,
                        CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
-                       SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
+                       SampledCVGroupResults, SampledCVResults, SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
                        TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults, TopSubsetsResults,
                        validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
-from ._driver import (ls_spa, ls_spa_cv, ls_spa_cv_path, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
+from ._driver import (ls_spa, ls_spa_cv, ls_spa_cv_path, ls_spa_cv_sampled, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
                       ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_group_subsets_cv, ls_spa_top_subsets,
                       ls_spa_top_subsets_cv,
@@ -68,4 +70,5 @@ __all__ = [
     "ls_spa_top_subsets_cv", "TopSubsetsCVResults",
     "ls_spa_top_group_subsets_cv", "TopGroupSubsetsCVResults",
     "ls_spa_cv_path", "CVPathResults", "CVGroupPathResults",
+    "ls_spa_cv_sampled", "SampledCVResults", "SampledCVGroupResults",
 ]

@@ -33,7 +33,7 @@ from . import _samplers as S
 from ._native import LSSPANativeError
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupPathResults, CVGroupResults, CVPathResults,
                        CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
-                       SampledMultiGroupResults, SampledMultiResults,
+                       SampledCVGroupResults, SampledCVResults, SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults,
                        TopSubsetsResults, validate_data)
@@ -1527,6 +1527,124 @@ def ls_spa_cv(X, y, reg=0., folds=5, *, groups=None, seed=42, shuffle=True, devi
     G, g = _cv_full_problem(X, y, reg)
     return CVResults(attribution=phi, fold_attribution=phi_fold, r_squared=float(_seq_sum(list(r2_fold))),
                      fold_r_squared=np.asarray(r2_fold), theta=_subset_fit(G, g, np.arange(X.shape[1])), fold_ids=ids)
+
+
+CV_LIFT_MAX_P = 127        # include/lsspa.h, LSSPA_CV_LIFT_MAX_P
+
+
+def _cv_fold_values(problems, cols):
+    """[K]: fold f's value (2 h^T theta - theta^T H theta) / ||y||^2 of the model on the columns `cols`, theta fitted on
+    fold problem f = (G, g, H, h, inv_yy); 0 for no columns."""
+    out = np.zeros(len(problems))
+    for f, (G, g, H, h, inv_yy) in enumerate(problems):
+        th = _subset_fit(G, g, cols)
+        out[f] = (2.0 * (h @ th) - th @ H @ th) * inv_yy
+    return out
+
+
+def ls_spa_cv_sampled(X, y, reg=0., folds=5, max_samples=2 ** 13, batch_size=2 ** 8, tolerance=None, seed=42,
+                      perms=None, *, groups=None, method="random", antithetical=True, fold_seed=42, shuffle=True,
+                      device=0, _engine=None):
+    """Sampled Shapley attribution of the K-fold cross-validated out-of-sample R^2 (p <= 127): what ``ls_spa_cv`` gives
+    exactly for p <= 32, estimated from sampled orderings beyond that -- one data set, no split to choose.
+
+    The game is ``ls_spa_cv``'s: fold f is predicted by the model fitted on the other folds' rows, and every fold
+    divides by the pooled ||y||^2.  A sample's lift vector is the sum over the folds of the lift vectors of ONE ordering
+    shared by all folds; one launch runs a batch's orderings through the K fold problems at once (include/lsspa.h,
+    lsspa_cv_lift_batch).  fp64 throughout; two calls agree bitwise.
+
+    folds, fold_seed, shuffle:  what ``folds``, ``seed`` and ``shuffle`` are to ``ls_spa_cv`` (``cv_fold_ids``; an integer
+        array [N] of labels is taken as given).  K is 2 .. 32, and every fold needs at least p rows.
+    max_samples, batch_size, tolerance, seed, method, perms, antithetical:  as in ``ls_spa_multi_sampled``; ``seed`` seeds
+        the ordering source.  With ``tolerance`` sampling stops after the first batch with n >= 2 whose largest
+        standard error of the SUMMED attribution is <= tolerance.
+    groups:  one integer label per column as ``ls_spa_groups`` takes them (-1: the baseline, 0 .. g-1, any 1 <= g <= p).
+        The players are then the groups, the sources run in dimension g, ``perms`` are group orderings, and the result
+        is a ``SampledCVGroupResults``.
+
+    Returns ``SampledCVResults``: ``attribution`` [d] (sums to ``r_squared``, over groups to ``r_squared -
+    baseline_r_squared``), ``attribution_errors`` [d], ``fold_attribution`` [K][d] (its rows sum to ``attribution``),
+    ``fold_attribution_errors`` [K][d], ``r_squared``, ``fold_r_squared`` [K], ``theta`` [p] (fitted on all rows),
+    ``fold_ids`` and ``n_samples``.
+
+    Shapes that do not fit, p > 127, K outside 2 .. 32, a label out of range, an empty fold, a fold with fewer than p
+    rows, a y that is identically zero, bad group labels and ``perms`` together with ``method`` are refused before any
+    GPU work.  A fold problem that is not numerically positive definite raises a RuntimeWarning that names the folds.
+    Several ranks, checkpoints, fp32, the device error estimator and the history are not part of this function."""
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1:
+        raise ValueError("ls_spa_cv_sampled: X must be two-dimensional and y one-dimensional")
+    if X.shape[0] != y.shape[0]:
+        raise SizeIncompatible(f"X has {X.shape[0]} rows, y has {y.shape[0]}")
+    n_rows, p = X.shape
+    if p > CV_LIFT_MAX_P:
+        raise ValueError(f"ls_spa_cv_sampled takes at most p = {CV_LIFT_MAX_P} features (this problem has p = {p})")
+    if p < 1 or n_rows < 2:
+        raise ValueError(f"ls_spa_cv_sampled needs p >= 1 features and N >= 2 rows (p = {p}, N = {n_rows})")
+    ids, K = cv_fold_ids(n_rows, folds, seed=fold_seed, shuffle=shuffle)
+    sizes = np.bincount(ids, minlength=K)
+    if (sizes < p).any():
+        f = int(np.argmax(sizes < p))
+        raise ValueError(f"fold {f} of {K} has {int(sizes[f])} rows, fewer than p = {p}: the Gram matrix of a fold's own "
+                         "rows must have a Cholesky factor")
+    if not np.any(y):
+        raise ValueError("y is identically zero: the cross-validated R^2 is not defined")
+    labels, d = None, p                # d: the dimension of a sample
+    if groups is not None:
+        labels, d = group_labels(groups, p, max_groups=None)
+    if perms is not None:
+        if method != "random":
+            raise ValueError("pass either perms= or method=, not both")
+        method = None
+    elif method not in S.METHODS:
+        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
+    if int(batch_size) < 1 or int(max_samples) < 1:
+        raise ValueError("batch_size and max_samples must be positive")
+    _, source, batch_size, antithetical, max_samples, never_stop = prepare_sampling(
+        d, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
+        antithetical=bool(antithetical), method=method)
+    if never_stop:
+        tolerance = None
+    undo = [(lambda: _close_source(source), True)]
+    with _engine_call(_engine, device, undo=undo) as engine:
+        undo.append((engine.cv_lift_free, True))
+        engine.cv_lift_load(X, y, ids, K, reg)
+        if labels is not None:
+            engine.cv_lift_set_players(labels)      # (cv_lift_free drops the map with everything else)
+        n, state = 0, None
+        while n < max_samples:
+            rows = source.take(min(batch_size, max_samples - n))
+            if len(rows) == 0:
+                break
+            engine.cv_lift_batch(rows, antithetical)
+            n += len(rows)
+            state = None
+            if tolerance is not None and n >= 2:
+                state = engine.cv_lift_get()      # the state is read once per batch
+                if _multi_standard_errors(state[0], state[2][K]).max() <= tolerance:
+                    break
+        if n == 0:
+            raise ValueError("no ordering to sample: perms is empty")
+        n, mean, m2 = state if state is not None else engine.cv_lift_get()
+        info = engine.cv_lift_info()
+        problems = [engine.cv_lift_problem(f) for f in range(K)]
+    r2_fold = _cv_fold_values(problems, np.arange(p))
+    base_cols = np.zeros(0, dtype=np.int64) if labels is None else np.nonzero(np.asarray(labels) == -1)[0]
+    base_fold = _cv_fold_values(problems, base_cols)
+    r_squared, base = float(_seq_sum(list(r2_fold))), float(_seq_sum(list(base_fold)))
+    _cv_verdict(info, stacklevel=2)
+    # every sample's lifts of fold f telescope from the baseline's value to the full model's, so the mean of the sums
+    # does (the bound of LSSPA_INFO_SUM for well-conditioned data)
+    if not (np.asarray(info) & 1).any() and not abs(mean[K].sum() - (r_squared - base)) <= 1e-9 * max(1.0, abs(r_squared)):
+        _info_verdict(8, stacklevel=2)
+    errors = _multi_standard_errors(n, m2)
+    G, g = _cv_full_problem(X, y, reg)
+    common = dict(attribution=mean[K], attribution_errors=errors[K], fold_attribution=mean[:K],
+                  fold_attribution_errors=errors[:K], r_squared=r_squared, fold_r_squared=r2_fold,
+                  theta=_subset_fit(G, g, np.arange(p)), fold_ids=ids, n_samples=int(n))
+    if labels is not None:
+        return SampledCVGroupResults(baseline_r_squared=base, fold_baseline_r_squared=base_fold, **common)
+    return SampledCVResults(**common)
 
 
 CV_PATH_MAX_REGS = 256     # include/lsspa.h, lsspa_cv_path_shapley

@@ -229,6 +229,21 @@ def debug_cv_plan(p: int, folds: int):
     return dict(zip(CV_PLAN_FIELDS, (int(v) for v in out)))
 
 
+CV_LIFT_PLAN_FIELDS = ("nb", "form", "workgroups_per_sample", "samples_per_launch", "launches", "lds_bytes", "workgroup")
+
+
+def debug_cv_lift_plan(p: int, d: int, folds: int, B: int, antithetical: bool):
+    """Test hook, host only: how cv_lift_batch cuts a batch of B samples of dimension d over p columns and `folds` fold
+    problems into launches (include/lsspa.h, lsspa_debug_cv_lift_plan) -- a dict with CV_LIFT_PLAN_FIELDS; form 0 is the
+    register-resident kernel, 1 the LDS-resident one.  ValueError for arguments the library refuses."""
+    out = np.zeros(8, dtype=np.int64)
+    rc = N.load().lsspa_debug_cv_lift_plan(int(p), int(d), int(folds), int(B), int(bool(antithetical)),
+                                           out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_cv_lift_plan: status {rc}")
+    return dict(zip(CV_LIFT_PLAN_FIELDS, (int(v) for v in out)))
+
+
 CV_TOP_PLAN_FIELDS = ("units", "per", "steps", "launches", "lds_bytes", "workgroup", "sizes", "table_bytes")
 
 
@@ -1223,6 +1238,99 @@ class HipEngine:
     def multi_lift_free(self):
         self._check(self._lib.lsspa_multi_lift_free(self._h))
         self._multi_lift_dims, self._multi_lift_g = None, 0
+
+    # ---- sampled attribution of the K-fold cross-validated R^2 (p <= 127, 2 <= K <= 32) ----------
+    CV_LIFT_MAX_P = 127
+
+    def cv_lift_load(self, X, y, fold_ids, K: int, reg: float):
+        """The K fold problems of the labels fold_ids [N] (0 .. K-1) for cv_lift_batch (include/lsspa.h,
+        lsspa_cv_lift_load); the loaded problem and the state of cv_load and multi_lift_load are not touched."""
+        dt = np.float32 if X.dtype == np.float32 else np.float64
+        Xa, ya = np.ascontiguousarray(X, dtype=dt), np.ascontiguousarray(y, dtype=dt)
+        n, p = Xa.shape
+        fid = np.ascontiguousarray(fold_ids, dtype=np.int32)
+        if fid.shape != (int(n),):
+            raise ValueError(f"fold_ids must have shape ({int(n)},), got {fid.shape}")
+        self._check(self._lib.lsspa_cv_lift_load(
+            self._h, C.c_void_p(Xa.ctypes.data), int(p), C.c_void_p(ya.ctypes.data), int(n), int(p), N.iptr(fid), int(K),
+            float(reg), N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._cv_lift_dims, self._cv_lift_g = (int(p), int(K)), 0
+
+    def cv_lift_set_players(self, labels, g=None):
+        """Groups of columns as the players of cv_lift_batch, as multi_lift_set_players names them (include/lsspa.h,
+        lsspa_cv_lift_set_players): perms are then [B][g], the lifts and the statistics in dimension g.  The library
+        checks the labels."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        g = int(labels.max()) + 1 if g is None else int(g)
+        self._check(self._lib.lsspa_cv_lift_set_players(self._h, N.iptr(labels), g))
+        self._cv_lift_g = g
+
+    def cv_lift_clear_players(self):
+        self._check(self._lib.lsspa_cv_lift_set_players(self._h, None, 0))
+        self._cv_lift_g = 0
+
+    def _cv_lift_sd(self):
+        """(dimension of a sample: g with a player map, else p; K)"""
+        p, K = getattr(self, "_cv_lift_dims", None) or (1, 2)
+        return (getattr(self, "_cv_lift_g", 0) or p), K
+
+    def cv_lift_batch(self, perms, antithetical: bool, want_lifts: bool = False, accumulate: bool = True):
+        """One ordering through the K fold problems, for every row of perms [B][d] (with antithetical a sample is an
+        ordering and its reverse), folded into the running statistics if accumulate; with want_lifts
+        (fold_lifts [B][K][d], lifts [B][d]), the folds' lift vectors and their ascending sum (include/lsspa.h,
+        lsspa_cv_lift_batch).  The library checks the orderings."""
+        dims = getattr(self, "_cv_lift_dims", None)
+        d, K = self._cv_lift_sd()
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        if dims is None:                  # the library says what comes first
+            want_lifts = False
+        elif perms.ndim != 2 or perms.shape[1] != d:
+            raise ValueError(f"perms must be [B][{'g' if getattr(self, '_cv_lift_g', 0) else 'p'} = {d}]")
+        B = perms.shape[0] if perms.ndim == 2 else 0
+        fold = np.empty((B, K, d)) if want_lifts else None
+        tot = np.empty((B, d)) if want_lifts else None
+        self._check(self._lib.lsspa_cv_lift_batch(self._h, N.iptr(perms) if perms.size else None, B,
+                                                  int(bool(antithetical)), N.dptr(fold) if want_lifts else None,
+                                                  N.dptr(tot) if want_lifts else None, int(bool(accumulate))))
+        return (fold, tot) if want_lifts else None
+
+    def cv_lift_get(self):
+        """(n, mean [K + 1][d], M2 [K + 1][d]) of the samples folded in so far: rows 0 .. K-1 the folds, row K the sum."""
+        d, K = self._cv_lift_sd()
+        n, mean, m2 = C.c_int64(), np.empty((K + 1, d)), np.empty((K + 1, d))
+        self._check(self._lib.lsspa_cv_lift_get(self._h, C.byref(n), N.dptr(mean), N.dptr(m2)))
+        return n.value, mean, m2
+
+    def cv_lift_reset(self):
+        self._check(self._lib.lsspa_cv_lift_reset(self._h))
+
+    def cv_lift_problem(self, f: int):
+        """(G, g, H, h, inv_yy) of fold problem f as the device computed it."""
+        p, _ = getattr(self, "_cv_lift_dims", None) or (1, 2)
+        G, g, H, h, yy = np.empty((p, p)), np.empty(p), np.empty((p, p)), np.empty(p), C.c_double()
+        self._check(self._lib.lsspa_cv_lift_get_problem(self._h, int(f), N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
+                                                        C.byref(yy)))
+        return G, g, H, h, yy.value
+
+    def cv_lift_info(self):
+        """info [K]: bit 1 of word f: a pivot of fold problem f failed in some ordering since the last reset."""
+        _, K = self._cv_lift_sd()
+        info = np.zeros(K, dtype=np.int32)
+        self._check(self._lib.lsspa_cv_lift_info(self._h, N.iptr(info)))
+        return info
+
+    def cv_lift_timing(self):
+        """Device seconds of the last cv_lift_load's Gram side, of the last batch's lift launches and of its fold and
+        statistics launches."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.lsspa_cv_lift_timing(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"gram": a.value / 1e3, "batch": b.value / 1e3, "stats": c.value / 1e3}
+
+    def cv_lift_free(self):
+        self._check(self._lib.lsspa_cv_lift_free(self._h))
+        self._cv_lift_dims, self._cv_lift_g = None, 0
+
+    debug_cv_lift_plan = staticmethod(debug_cv_lift_plan)
 
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()

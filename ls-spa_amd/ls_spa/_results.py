@@ -459,6 +459,75 @@ class SampledMultiResults:
 
 
 @dataclass
+class SampledCVResults:
+    """What ``ls_spa_cv_sampled`` returns.  ``attribution`` [p]: the mean of the ``n_samples`` summed lift vectors
+    sum_f lift_f(pi), an estimate of the Shapley attribution of the K-fold cross-validated R^2 (what ``ls_spa_cv`` gives
+    exactly for p <= 32); ``attribution_errors`` [p] the standard errors of the SUMMED attribution, sqrt(M2 / (n (n - 1)))
+    of the sums (``inf`` while n < 2; only indicative for the QMC sources and a caller's ``perms``).
+    ``fold_attribution`` [K][p] and ``fold_attribution_errors`` [K][p]: the same per fold; the rows of
+    ``fold_attribution`` sum to ``attribution``.  ``r_squared``: the cross-validated R^2 of the full model, what
+    ``attribution`` sums to; ``fold_r_squared`` [K] each fold's share.  ``theta`` [p] is fitted on all rows;
+    ``fold_ids`` [N] the fold of every row."""
+    attribution: np.ndarray
+    attribution_errors: np.ndarray
+    fold_attribution: np.ndarray
+    fold_attribution_errors: np.ndarray
+    r_squared: float
+    fold_r_squared: np.ndarray
+    theta: np.ndarray
+    fold_ids: np.ndarray
+    n_samples: int
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}p = {len(self.attribution)}, K = {len(self.fold_r_squared)} folds, {self.n_samples} samples",
+            f"{pad}Cross-validated R^2 with all features: {self.r_squared:.6g}",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}Largest standard error: {float(np.max(self.attribution_errors)):.3g}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
+class SampledCVGroupResults:
+    """What ``ls_spa_cv_sampled(groups=)`` returns: ``SampledCVResults`` over the g groups -- ``attribution`` [g],
+    ``attribution_errors`` [g], ``fold_attribution`` [K][g], ``fold_attribution_errors`` [K][g] -- with
+    ``baseline_r_squared``, the cross-validated R^2 of the baseline's columns alone (0 without a baseline), and
+    ``fold_baseline_r_squared`` [K] its shares.  ``attribution`` sums to ``r_squared - baseline_r_squared``; ``theta``
+    keeps length p."""
+    attribution: np.ndarray
+    attribution_errors: np.ndarray
+    fold_attribution: np.ndarray
+    fold_attribution_errors: np.ndarray
+    r_squared: float
+    fold_r_squared: np.ndarray
+    baseline_r_squared: float
+    fold_baseline_r_squared: np.ndarray
+    theta: np.ndarray
+    fold_ids: np.ndarray
+    n_samples: int
+
+    def __repr__(self):
+        pad = " " * 8
+        lines = [
+            "",
+            f"{pad}g = {len(self.attribution)} groups, p = {len(self.theta)}, K = {len(self.fold_r_squared)} folds, "
+            f"{self.n_samples} samples",
+            f"{pad}Cross-validated R^2 with all columns: {self.r_squared:.6g}",
+            f"{pad}Cross-validated R^2 of the baseline: {self.baseline_r_squared:.6g}",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}Largest standard error: {float(np.max(self.attribution_errors)):.3g}",
+            pad,
+        ]
+        return "\n".join(lines)
+
+
+@dataclass
 class SampledMultiGroupResults:
     """What ``ls_spa_multi_sampled(groups=)`` returns for m responses on one design matrix whose columns form g groups.
     ``attribution`` [m][g]: row r is the mean of the ``n_samples`` group lift vectors of response r, an estimate of its
