@@ -867,6 +867,82 @@ int lsspa_cv_lift_timing(const lsspa_ctx* ctx, double* gram_ms, double* batch_ms
 int lsspa_cv_lift_free(lsspa_ctx* ctx);
 int lsspa_debug_cv_lift_plan(int32_t p, int32_t d, int32_t K, int64_t B, int32_t antithetical, int64_t* plan /* [8] */);
 
+/* BOOTSTRAP OF THE SAMPLED ATTRIBUTION (p <= 127): how far the attribution lsspa_small / ls_spa estimates from sampled
+ * orderings moves under another draw of the rows.  The replicates are lsspa_boot_run's -- the counts rule (Philox4x32-10
+ * keyed by (seed, replicate, side)), the weighted Gram pass over rows that stay on the device, its finalise -- with two
+ * differences: Z = [X | y] is packed at ldz = 16 cb, cb = ceil((p + 1) / 16) <= 8, and for cb = 6 .. 8 the Gram pass
+ * runs in a WIDE form in which the four waves of a workgroup share the rows and the replicate and divide the block pairs
+ * bi <= bj among themselves (csrc/k_boot.hip); and a replicate is not enumerated but run through ONE SET OF ORDERINGS
+ * that all replicates and the point problem share (common random numbers): the fold-problem instantiations of
+ * csrc/k_small.hip with the grid (orderings, replicates), blockIdx.y the replicate, plain stores to
+ * raw[ordering][replicate][p], and boot_lift_stats_kernel's Welford / Chan merge into one (n, mean, M2) per replicate.
+ * fp64 throughout, no floating-point atomics anywhere.  The family has state of its own: the loaded problem,
+ * lsspa_boot_*, lsspa_cv_lift_*, lsspa_multi_lift_* and every other store are not touched by any call below.
+ *   lsspa_boot_lift_load : both sides as lsspa_boot_load takes them.  Limits: 1 <= p <= LSSPA_BOOT_LIFT_MAX_P, N >= p,
+ *                     M >= p, y_test not identically zero; each refusal is LSSPA_ERR_ARG naming the limit, before any
+ *                     GPU work.  Drops a player map and the orderings.
+ *   lsspa_boot_lift_set_players : as lsspa_cv_lift_set_players (labels [p], -1 the baseline, 0 .. g-1, any 1 <= g <= p;
+ *                     NULL, 0 clears).  Setting or clearing drops the orderings.  With a map d = g, else d = p.
+ *   lsspa_boot_lift_set_orderings : perms [n_samples][d], every row a permutation of 0 .. d-1 (else LSSPA_ERR_ARG),
+ *                     validated on the host, expanded as lsspa_cv_lift_batch expands them (with antithetical != 0 a
+ *                     sample is the ordering and its reverse; with a map the reversed group ordering, the baseline first
+ *                     in both) and uploaded once.
+ *   lsspa_boot_lift_run : replicates first .. first + R - 1.  w_train [R][N] / w_test [R][M]: the caller's weights of a
+ *                     side (finite, >= 0, a positive sum per replicate) or NULL: the counts of (boot_seed, replicate,
+ *                     side), exactly lsspa_boot_debug_counts'.  block: replicates per block, 0: as many as
+ *                     BOOT_BLOCK_BYTES holds.  Out: mean [R][d], m2 [R][d] over the n_samples samples, r2 [R] of the
+ *                     full model and baseline_r2 [R] (may be NULL) of the baseline's columns alone, both on the host
+ *                     from the replicate's problem as the device wrote it (NaN where G has no Cholesky factor),
+ *                     info [R] (bit LSSPA_INFO_NOT_PD: a pivot of G or H failed the relative test 16 p eps in some
+ *                     ordering).  samples_out [R][n_samples][d] (test hook, may be NULL): every sample's entry.
+ *   lsspa_boot_lift_point : the original rows, weight 1 on every row, through the same Gram pass and the same kernels
+ *                     as a run of one problem: mean [d], m2 [d], r2, baseline_r2 (may be NULL), info [1],
+ *                     samples_out [n_samples][d] or NULL.
+ *   lsspa_boot_lift_get_problem : G [p][p], g [p], H [p][p], h [p], inv_yy of replicate r as the device writes it in a
+ *                     run: the counts of (boot_seed, r, side), or the caller's weights w_train [N] / w_test [M] of that
+ *                     one replicate; r < 0: the point problem (weight 1 where no weights are given).
+ *   lsspa_boot_lift_debug_grams : S_train / S_test [R][c][c], c = p + 1, and wsum [R] before finalise, as
+ *                     lsspa_boot_debug_grams (a side without weights gets ones); any output may be NULL.
+ *   lsspa_boot_lift_timing : device ms of the last pass: counts, Gram side (to the problems), lift launches, statistics
+ *                     launches; and the number of lift launches.
+ *   lsspa_boot_lift_free : frees everything of the family.
+ *   lsspa_debug_boot_lift_plan : host only, no context, no GPU.  plan [16] = cb, the Gram kernel form (0: one wave a
+ *                     replicate set, cb <= 5; 1: wide), rows per slice train / test, slices train / test, replicates per
+ *                     block, blocks, replicates per lift launch, orderings per lift launch, samples per lift launch,
+ *                     sample cuts, lift launches of the run, raw bytes of the largest launch, the lift kernel form
+ *                     (0 register-resident, 1 LDS-resident), bytes a replicate takes in a block.  A lift launch has at
+ *                     most 2^16 workgroups (2^13 of the LDS-resident form, p + 1 > 112) and 256 MB of raw lifts.
+ * LSSPA_ERR_STATE before a load or, for run and point, before the orderings are set.
+ * Contract: two calls agree bitwise.  Replicate r has the same bits whatever R, first, block and the number of
+ * replicates that share its launches: the row slices are a function of the side's rows alone, a workgroup computes one
+ * (ordering, replicate) whole, and the cut of the samples into launches -- which the Chan merges follow, in sample order
+ * -- is a function of n_samples and antithetical alone.  Its counts are lsspa_boot_debug_counts' for (boot_seed, r,
+ * side).  A sample's entry has the bits lsspa_cv_lift_batch documents: 0.5 * a + 0.5 * b of a pair, the ascending-column
+ * sum from 0.0 of a group.  No existing call changes.
+ * Not built: fp32 work matrices, several ranks, checkpoints, the device error estimator, the history, a tolerance. */
+#define LSSPA_BOOT_LIFT_MAX_P 127
+int lsspa_boot_lift_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                         const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                         int32_t dtype, int32_t location);
+int lsspa_boot_lift_set_players(lsspa_ctx* ctx, const int32_t* labels /* [p] or NULL */, int32_t g);
+int lsspa_boot_lift_set_orderings(lsspa_ctx* ctx, const int32_t* perms /* [n_samples][d] */, int64_t n_samples,
+                                  int32_t antithetical);
+int lsspa_boot_lift_run(lsspa_ctx* ctx, int64_t R, uint64_t boot_seed, int64_t first, const double* w_train,
+                        const double* w_test, int64_t block, double* mean /* [R][d] */, double* m2 /* [R][d] */,
+                        double* r2 /* [R] */, double* baseline_r2 /* [R] or NULL */, int32_t* info /* [R] */,
+                        double* samples_out /* [R][n_samples][d] or NULL */);
+int lsspa_boot_lift_point(lsspa_ctx* ctx, double* mean, double* m2, double* r2, double* baseline_r2, int32_t* info,
+                          double* samples_out);
+int lsspa_boot_lift_get_problem(lsspa_ctx* ctx, int64_t r, uint64_t boot_seed, const double* w_train, const double* w_test,
+                                double* G, double* g, double* H, double* h, double* inv_yy);
+int lsspa_boot_lift_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, const double* w_test, double* S_train,
+                                double* S_test, double* wsum);
+int lsspa_boot_lift_timing(const lsspa_ctx* ctx, double* counts_ms, double* gram_ms, double* lift_ms, double* stats_ms,
+                           int64_t* launches);
+int lsspa_boot_lift_free(lsspa_ctx* ctx);
+int lsspa_debug_boot_lift_plan(int64_t R, int64_t N, int64_t M, int32_t p, int32_t d, int64_t n_samples,
+                               int32_t antithetical, int64_t block, int64_t* plan /* [16] */);
+
 /* Element type of the per-ordering work (Cholesky factors, solves): LSSPA_F64 (default; matches the
  * reference to ~1e-15) or LSSPA_F32 (half the HBM traffic, fp32 MFMA; the Gram reduction, the lift
  * accumulation and the running statistics stay fp64).  The reference has no counterpart: it computes

@@ -187,6 +187,50 @@ const char* boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, int p, int g
   return nullptr;
 }
 
+const char* boot_lift_plan(int64_t R, int64_t N, int64_t M, int p, int d, int64_t n_samples, int antithetical,
+                           int64_t block, BootLiftPlan& P) {
+  P = BootLiftPlan{};
+  if (p < 1 || p > BOOT_LIFT_MAX_P) return "p must be 1 .. 127";
+  if (d < 1 || d > p) return "d must be 1 .. p";
+  if (n_samples < 1 || n_samples > (1ll << 30)) return "n_samples must be 1 .. 2^30";
+  if (const char* why = plan_sizes(R, N, M, block)) return why;
+  const int c = p + 1;
+  BootPlan Q{};
+  plan_gram(N, M, c, Q);
+  P.cb = Q.cb;
+  P.ldz = Q.ldz;
+  P.pairs = Q.pairs;
+  P.gram_form = Q.cb <= 5 ? 0 : 1;
+  P.rpw = Q.rpw;                     // (1 from cb = 4 on)
+  for (int s = 0; s < 2; ++s) {
+    P.rps[s] = Q.rps[s];
+    P.slices[s] = Q.slices[s];
+  }
+  // per replicate: weights of both sides, the Gram partials, S of both sides, the problem at the ordering kernels'
+  // stride (G, H, g, h, inv_yy, the augmented diagonals), its running mean and M2 and its info word
+  constexpr int64_t LD = BOOT_LIFT_LD;
+  P.rep_bytes = 8 * (N + M) + (int64_t)(P.slices[0] + P.slices[1]) * P.pairs * 256 * 8 + 2ll * c * c * 8 +
+                (2 * LD * LD + 2 * LD + 4) * 8 + 2ll * d * 8 + 8;
+  const int64_t most = std::max<int64_t>(1, std::min<int64_t>(BOOT_MAX_BLOCK, BOOT_BLOCK_BYTES / P.rep_bytes));
+  P.block = std::min<int64_t>(R, block > 0 ? std::min(block, most) : most);
+  P.n_blocks = (R + P.block - 1) / P.block;
+  const int64_t per = antithetical ? 2 : 1;
+  P.lift_form = P.cb <= 7 ? 0 : 1;
+  P.samples_per_launch = std::min<int64_t>(n_samples, BOOT_LIFT_ORD / per);
+  P.ord_per_launch = P.samples_per_launch * per;
+  P.sample_cuts = (n_samples + P.samples_per_launch - 1) / P.samples_per_launch;
+  const int64_t grid = P.lift_form ? BOOT_LIFT_GRID_LDS : BOOT_LIFT_GRID_REG;
+  P.reps_per_launch = std::max<int64_t>(
+      1, std::min<int64_t>(grid / P.ord_per_launch, BOOT_LIFT_RAW_BYTES / (P.ord_per_launch * p * 8)));
+  const int64_t full = R / P.block, rest = R - full * P.block;
+  // (full <= R, a block has at most BOOT_MAX_BLOCK launch rows: the sum fits; the product saturates)
+  const int64_t rep_launches = full * ((P.block + P.reps_per_launch - 1) / P.reps_per_launch) +
+                               (rest + P.reps_per_launch - 1) / P.reps_per_launch;
+  P.launches = rep_launches > INT64_MAX / P.sample_cuts ? INT64_MAX : rep_launches * P.sample_cuts;
+  P.raw_bytes = P.ord_per_launch * std::min(P.reps_per_launch, P.block) * p * 8;
+  return nullptr;
+}
+
 const char* perm_plan(int64_t R, int64_t N, int64_t M, int p, int64_t block, PermPlan& P) {
   P = PermPlan{};
   if (p < 1 || p > PERM_MAX_P) return "p must be 1 .. 64";

@@ -74,6 +74,37 @@ const char* boot_inter_plan(int64_t R, int64_t N, int64_t M, int p, int64_t bloc
 const char* boot_groups_inter_plan(int64_t R, int64_t N, int64_t M, int p, int g, int gh, int nb, int ql, int64_t block,
                                    BootPlan& P);
 
+// The bootstrap of the SAMPLED attribution (lsspa_boot_lift_run; k_boot.hip, launch_small_problems): p <= 127, c = p + 1
+// <= 128 columns of Z, cb up to 8.  The Gram side is boot_plan's for the same rows (cb, ldz, pairs, rps, slices: the
+// slices a function of the side's rows alone); gram_form 0 is boot_gram_kernel<CB, RPW> (cb <= 5, rpw as above), 1 the
+// wide form of cb = 6 .. 8, in which the four waves of a workgroup share the rows AND the replicate and divide the block
+// pairs among themselves (rpw = 1: one replicate a workgroup).  A replicate's problem is written at the ordering
+// kernels' stride: rows of BOOT_LIFT_LD doubles.  The orderings are one set for all replicates, n_samples samples of
+// per = 1 or 2 (antithetical) orderings; a lift launch is a grid (orderings, replicates):
+//   - samples_per_launch = min(n_samples, BOOT_LIFT_ORD / per): a function of n_samples and antithetical alone, never of
+//     R, first or block -- the running (n, mean, M2) of a replicate is merged once per cut, so the cut shows in the bits;
+//   - reps_per_launch fills what such a launch leaves: orderings x replicates <= BOOT_LIFT_GRID_REG workgroups of the
+//     register-resident kernel (lift_form 0, p + 1 <= 112), <= BOOT_LIFT_GRID_LDS of the LDS-resident one (lift_form 1,
+//     one workgroup a compute unit), and raw lifts [orderings][replicates][p] of at most BOOT_LIFT_RAW_BYTES; it does not
+//     show in the bits (a workgroup computes one (ordering, replicate) whole);
+//   - block rep_bytes <= BOOT_BLOCK_BYTES (or block = 1), block <= BOOT_MAX_BLOCK; the raw lifts stand beside the block.
+// launches: lift launches of the whole run; raw_bytes: those of the largest launch.
+struct BootLiftPlan {
+  int cb, ldz, pairs, gram_form, rpw;
+  int64_t rps[2];
+  int slices[2];
+  int64_t rep_bytes, block, n_blocks;
+  int lift_form;
+  int64_t samples_per_launch, ord_per_launch, reps_per_launch, sample_cuts, launches, raw_bytes;
+};
+constexpr int BOOT_LIFT_MAX_P = 127, BOOT_LIFT_LD = 128;      // CV_LIFT_MAX_P, CV_LIFT_LD (kernels.h)
+constexpr int64_t BOOT_LIFT_ORD = 256;
+constexpr int64_t BOOT_LIFT_GRID_REG = 1 << 16, BOOT_LIFT_GRID_LDS = 1 << 13;
+constexpr int64_t BOOT_LIFT_RAW_BYTES = 256ll << 20;
+// d: the dimension of a sample (p, or the groups of a player map, 1 <= d <= p); block as boot_plan's
+const char* boot_lift_plan(int64_t R, int64_t N, int64_t M, int p, int d, int64_t n_samples, int antithetical,
+                           int64_t block, BootLiftPlan& P);
+
 // The permutation test (lsspa_perm_run, k_perm.hip): X of a side lives on the device as [n][ldx], ldx = 16 cb, cb =
 // ceil(p / 16) <= 4; a block of replicates is one gathered X^T y pass per permuted side into per-slice partial sums
 // [slice][ceil(block / 16)][cb][256].  A slice is at least PERM_MIN_SLICE_ROWS rows, a multiple of 16, at most

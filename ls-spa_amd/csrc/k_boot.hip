@@ -177,6 +177,147 @@ __global__ __launch_bounds__(256) void boot_pack_kernel(const T* __restrict__ X,
   Z[(row0 + i) * ldz + j] = v;
 }
 
+// The wide form, cb = 6 .. 8 (the bootstrap of the sampled attribution, p + 1 = 81 .. 128 columns): a wave cannot hold
+// the cb (cb + 1) / 2 accumulators of even one replicate beside its operands (36 x 4 doubles at cb = 8), so the four
+// waves of a workgroup share the rows AND the replicate and divide the block pairs among themselves: pair e (row-major
+// over bi <= bj, boot_reduce_kernel's numbering) belongs to wave e & 3, which keeps it in accumulator e >> 2 -- at most
+// 9 accumulators of four doubles a wave.  Every wave loads the row's cb blocks once per four rows (the first wave from
+// memory, the others from the first-level cache) and forms the A operand w z in registers.  The accumulators go to the
+// same part[slice][r][pair][256] as they stand: boot_reduce_kernel sums and unfolds them unchanged.  No barrier, no
+// LDS, no atomics; rows beyond the slice get weight 0 and a clamped address.  W is the wave, a template parameter so
+// that every accumulator index is a constant (wide_wave picks the instantiation by the wave's number, a scalar).
+template <int CB, int W>
+__device__ __forceinline__ void boot_gram_wide_wave(const double* __restrict__ Z, int64_t n, int64_t beg, int64_t end,
+                                                    const uint32_t* __restrict__ cnt, const double* __restrict__ wt,
+                                                    int64_t wrow, double* __restrict__ out, int lane) {
+  constexpr int LDZ = 16 * CB, PAIRS = CB * (CB + 1) / 2, MINE = (PAIRS - W + 3) / 4;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  d4 acc[MINE];
+#pragma unroll
+  for (int e = 0; e < MINE; ++e) acc[e] = Tr<double>::zero();
+  for (int64_t base = beg; base < end; base += 4) {
+    const bool in = base + l4 < end;
+    const int64_t row = in ? base + l4 : beg;
+    double z[CB];
+#pragma unroll
+    for (int b = 0; b < CB; ++b) {
+      const double v = Z[row * LDZ + 16 * b + l15];
+      z[b] = in ? v : 0.0;
+    }
+    const double wv = cnt ? (double)cnt[wrow + row] : wt[wrow + row];
+    const double w = in ? wv : 0.0;
+    int e = 0;
+#pragma unroll
+    for (int bi = 0; bi < CB; ++bi) {
+      const double a = w * z[bi];
+#pragma unroll
+      for (int bj = bi; bj < CB; ++bj, ++e)
+        if ((e & 3) == W) acc[e >> 2] = Tr<double>::mfma(a, z[bj], acc[e >> 2]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < MINE; ++k)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) out[(int64_t)(4 * k + W) * 256 + v * 64 + lane] = acc[k][v];
+}
+
+template <int CB>
+__global__ __launch_bounds__(256) void boot_gram_wide_kernel(const double* __restrict__ Z, int64_t n, int64_t rps,
+                                                             const uint32_t* __restrict__ cnt,
+                                                             const double* __restrict__ wt, int reps,
+                                                             double* __restrict__ part) {
+  constexpr int PAIRS = CB * (CB + 1) / 2;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int r = blockIdx.y;                               // r < reps: the grid has reps rows
+  const int64_t beg = (int64_t)blockIdx.x * rps;
+  const int64_t end = beg + rps < n ? beg + rps : n;      // beg < n: the grid has ceil(n / rps) slices
+  const int64_t wrow = (int64_t)r * n;
+  double* out = part + (((int64_t)blockIdx.x * reps + r) * PAIRS) * 256;
+  switch (wave) {
+    case 0: boot_gram_wide_wave<CB, 0>(Z, n, beg, end, cnt, wt, wrow, out, lane); break;
+    case 1: boot_gram_wide_wave<CB, 1>(Z, n, beg, end, cnt, wt, wrow, out, lane); break;
+    case 2: boot_gram_wide_wave<CB, 2>(Z, n, beg, end, cnt, wt, wrow, out, lane); break;
+    default: boot_gram_wide_wave<CB, 3>(Z, n, beg, end, cnt, wt, wrow, out, lane); break;
+  }
+}
+
+// boot_finalize_kernel's expressions into the layout the ordering kernels of k_small.hip read (launch_small_problems):
+// rows of LD doubles, a replicate's matrices LD x LD apart; aug: the diagonals of the two augmented rows by
+// launch_cv_lift_finalize's rule (2 ||y_train||^2 / W + 1, 2 ||y_test||^2 + 1).  Entries beyond column p - 1 and row
+// p - 1 are not written: the caller has zeroed the buffers once.
+__global__ __launch_bounds__(256) void boot_lift_finalize_kernel(const double* __restrict__ S_tr,
+                                                                 const double* __restrict__ S_te,
+                                                                 const double* __restrict__ wsum_tr, int p, double reg,
+                                                                 double* __restrict__ G, double* __restrict__ g,
+                                                                 double* __restrict__ H, double* __restrict__ h,
+                                                                 double* __restrict__ inv_yy, double* __restrict__ aug) {
+  constexpr int LD = BOOT_LIFT_LD;
+  const int r = blockIdx.x, c = p + 1;
+  const double* A = S_tr + (int64_t)r * c * c;
+  const double* T = S_te + (int64_t)r * c * c;
+  const double W = wsum_tr[r];
+  for (int e = threadIdx.x; e < p * p; e += 256) {
+    const int i = e / p, j = e - i * p;
+    G[((int64_t)r * LD + i) * LD + j] = A[i * c + j] / W + (i == j ? reg : 0.0);
+    H[((int64_t)r * LD + i) * LD + j] = T[i * c + j];
+  }
+  if ((int)threadIdx.x < p) {
+    g[(int64_t)r * LD + threadIdx.x] = A[threadIdx.x * c + p] / W;
+    h[(int64_t)r * LD + threadIdx.x] = T[threadIdx.x * c + p];
+  }
+  if (threadIdx.x == 0) {
+    inv_yy[r] = 1.0 / T[p * c + p];
+    aug[2 * r] = 2.0 * (A[p * c + p] / W) + 1.0;
+    aug[2 * r + 1] = 2.0 * T[p * c + p] + 1.0;
+  }
+}
+
+// One thread per (replicate r of the launch, player k).  raw [ordering][reps][p] is a lift launch's output.  Sample s's
+// entry: the ordering's lift (no map), or the sum of group k's columns in ascending column order from 0.0 per ordering
+// (cv_lift_fold_kernel's rule and bits); a pair's is 0.5 a + 0.5 b of its two orderings' entries.  Welford over the
+// launch's samples in sample order, then one Chan merge into the replicate's running (mean, M2) of n_old samples
+// (multi_lift_stats_kernel's expressions).  samples (may be NULL): the entries themselves, [reps][n_s][d].
+__global__ __launch_bounds__(256) void boot_lift_stats_kernel(const double* __restrict__ raw, int p, int reps, int per,
+                                                              const int32_t* __restrict__ off,
+                                                              const int32_t* __restrict__ cols, int d, int n_s,
+                                                              double n_old, double* __restrict__ mean,
+                                                              double* __restrict__ M2, double* __restrict__ samples) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= (int64_t)reps * d) return;
+  const int r = (int)(o / d);
+  const int k = (int)(o - (int64_t)r * d);
+  const int c0 = off ? off[k] : 0, c1 = off ? off[k + 1] : 0;
+  double mb = 0.0, qb = 0.0;
+  for (int s = 0; s < n_s; ++s) {
+    double e[2] = {0.0, 0.0};
+    for (int q = 0; q < per; ++q) {
+      const double* row = raw + (((int64_t)s * per + q) * reps + r) * p;
+      if (off) {
+        double a = 0.0;
+        for (int c = c0; c < c1; ++c) a += row[cols[c]];
+        e[q] = a;
+      } else {
+        e[q] = row[k];
+      }
+    }
+    const double x = per == 2 ? 0.5 * e[0] + 0.5 * e[1] : e[0];
+    if (samples) samples[((int64_t)r * n_s + s) * d + k] = x;
+    const double dl = x - mb;
+    mb += dl / (double)(s + 1);
+    qb += dl * (x - mb);
+  }
+  if (n_old == 0.0) {
+    mean[o] = mb;
+    M2[o] = qb;
+  } else {
+    const double nbd = (double)n_s, n = n_old + nbd;
+    const double dl = mb - mean[o];
+    mean[o] += dl * (nbd / n);
+    M2[o] += qb + dl * dl * (n_old * nbd / n);
+  }
+}
+
 template <int CB, int RPW>
 void gram_launch(const BootPlan& P, int side, const double* Z, int64_t n, const uint32_t* cnt, const double* wt,
                  int reps, double* part, hipStream_t st) {
@@ -257,6 +398,83 @@ hipError_t launch_boot_pack(const void* X, int64_t ld, const void* y, int64_t ro
   else
     hipLaunchKernelGGL(boot_pack_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)X, ld,
                        (const double*)y, rows, p, Z, ldz, row0);
+  return hipGetLastError();
+}
+
+// ---- the bootstrap of the sampled attribution (lsspa_boot_lift_*): c = p + 1 up to 128 columns --------------------------
+// The launchers above keep their p <= GROUPS_MAX_P; these are their siblings for p <= BOOT_LIFT_MAX_P on the same kernels.
+hipError_t launch_boot_lift_gram(const BootLiftPlan& L, int side, const double* Z, int64_t n, const uint32_t* cnt,
+                                 const double* wt, int reps, double* part, hipStream_t st) {
+  if (L.cb < 1 || L.cb > 8 || L.gram_form != (L.cb >= 6) || side < 0 || side > 1) return hipErrorInvalidValue;
+  if (!L.gram_form) {                  // the existing instantiations, through their launcher
+    BootPlan P{};
+    P.cb = L.cb;
+    P.ldz = L.ldz;
+    P.pairs = L.pairs;
+    P.rpw = L.rpw;
+    P.rps[side] = L.rps[side];
+    P.slices[side] = L.slices[side];
+    return launch_boot_gram(P, side, Z, n, cnt, wt, reps, part, st);
+  }
+  if (!Z || !part || (cnt == nullptr) == (wt == nullptr) || n < 1 || n >= (1ll << 31) || reps < 1 || reps > 65535 ||
+      L.rps[side] < 4 || L.rps[side] % 4 || (int64_t)L.slices[side] != (n + L.rps[side] - 1) / L.rps[side] ||
+      L.ldz != 16 * L.cb || L.pairs != L.cb * (L.cb + 1) / 2)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)L.slices[side], (unsigned)reps);
+  if (L.cb == 6)
+    hipLaunchKernelGGL(boot_gram_wide_kernel<6>, grid, dim3(256), 0, st, Z, n, L.rps[side], cnt, wt, reps, part);
+  else if (L.cb == 7)
+    hipLaunchKernelGGL(boot_gram_wide_kernel<7>, grid, dim3(256), 0, st, Z, n, L.rps[side], cnt, wt, reps, part);
+  else
+    hipLaunchKernelGGL(boot_gram_wide_kernel<8>, grid, dim3(256), 0, st, Z, n, L.rps[side], cnt, wt, reps, part);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_lift_reduce(const BootLiftPlan& L, int side, const double* part, int p, int reps, double* S,
+                                   hipStream_t st) {
+  if (!part || !S || p < 1 || p > BOOT_LIFT_MAX_P || reps < 1 || side < 0 || side > 1 || L.cb != (p + 16) / 16 ||
+      L.slices[side] < 1)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(boot_reduce_kernel, dim3((unsigned)reps), dim3(256), 0, st, part, L.slices[side], reps, L.cb,
+                     p + 1, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_lift_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Z,
+                                 int ldz, int64_t row0, hipStream_t st) {
+  if (!X || !y || !Z || rows < 1 || p < 1 || p > BOOT_LIFT_MAX_P || ld < p || ldz < p + 1 || row0 < 0)
+    return hipErrorInvalidValue;
+  const int64_t blocks = (rows * ldz + 255) / 256;
+  if (blocks > (1ll << 31) - 1) return hipErrorInvalidValue;
+  if (is_f32)
+    hipLaunchKernelGGL(boot_pack_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)X, ld,
+                       (const float*)y, rows, p, Z, ldz, row0);
+  else
+    hipLaunchKernelGGL(boot_pack_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)X, ld,
+                       (const double*)y, rows, p, Z, ldz, row0);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_lift_finalize(const double* S_tr, const double* S_te, const double* wsum_tr, int p, double reg,
+                                     int reps, double* G, double* g, double* H, double* h, double* inv_yy, double* aug,
+                                     hipStream_t st) {
+  if (!S_tr || !S_te || !wsum_tr || !G || !g || !H || !h || !inv_yy || !aug || p < 1 || p > BOOT_LIFT_MAX_P || reps < 1)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(boot_lift_finalize_kernel, dim3((unsigned)reps), dim3(256), 0, st, S_tr, S_te, wsum_tr, p, reg, G,
+                     g, H, h, inv_yy, aug);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_lift_stats(const double* raw, int p, int reps, int per, const int32_t* off, const int32_t* cols,
+                                  int d, int n_s, int64_t n_old, double* mean, double* M2, double* samples,
+                                  hipStream_t st) {
+  // (off and cols are the library's own tables: player_map_build has checked that every column index is in 0 .. p-1)
+  if (!raw || !mean || !M2 || p < 1 || p > BOOT_LIFT_MAX_P || reps < 1 || (per != 1 && per != 2) || d < 1 || d > p ||
+      (off ? !cols : d != p) || n_s < 1 || n_old < 0)
+    return hipErrorInvalidValue;
+  const int64_t total = (int64_t)reps * d;
+  hipLaunchKernelGGL(boot_lift_stats_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, raw, p, reps, per,
+                     off, cols, d, n_s, (double)n_old, mean, M2, samples);
   return hipGetLastError();
 }
 

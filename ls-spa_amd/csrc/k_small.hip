@@ -830,6 +830,8 @@ size_t small_folds_lds_bytes(int nb) {
   return nb <= 7 ? (size_t)small_reg_lds_doubles(nb) * sizeof(double) + 128 * sizeof(int32_t) : small_p_lds_bytes(nb);
 }
 
+static hipError_t small_folds_dispatch(const SmallArgs& a, const SmallFolds& fo, hipStream_t st);
+
 // The fold-problem launch (lsspa_cv_lift_batch): grid (orderings, folds), the kernel form launch_small_p picks for nb.
 hipError_t launch_small_folds(const SmallArgs& a, const SmallFolds& fo, hipStream_t st) {
   if (!small_p_eligible(a.p) || a.nb != (a.p + 1 + 15) / 16 || a.n_ord < 1 || a.n_ord > SMALL_FOLDS_MAX_GRID ||
@@ -840,6 +842,22 @@ hipError_t launch_small_folds(const SmallArgs& a, const SmallFolds& fo, hipStrea
       fo.vec < a.p || (reinterpret_cast<uintptr_t>(a.S[0]) & 15) || (reinterpret_cast<uintptr_t>(a.S[1]) & 15))
     return hipErrorInvalidValue;      // (the register-resident gather reads pairs of columns: rows of even length, one
                                       // column of room behind column p - 1, 16-byte aligned)
+  return small_folds_dispatch(a, fo, st);
+}
+
+// Many problems on one set of orderings (lsspa_boot_lift_run): the same instantiations, one problem a grid row
+hipError_t launch_small_problems(const SmallArgs& a, const SmallFolds& fo, hipStream_t st) {
+  if (!small_p_eligible(a.p) || a.nb != (a.p + 1 + 15) / 16 || a.n_ord < 1 || a.n_ord > SMALL_FOLDS_MAX_GRID ||
+      (a.per_sample != 1 && a.per_sample != 2) || (a.n_ord % a.per_sample) != 0 || !a.S[0] || !a.S[1] || !a.s[0] ||
+      !a.s[1] || !a.perms || !a.lifts || !a.info || (a.fwd_only && a.per_sample != 2) || fo.folds < 1 ||
+      fo.folds > 65535 || (int64_t)a.n_ord * fo.folds > SMALL_FOLDS_MAX_GRID || !fo.aug || !fo.inv_yy ||
+      a.ld_src < a.p + 1 || (a.ld_src & 1) || fo.mat < (int64_t)a.p * a.ld_src || (fo.mat & 1) ||
+      fo.vec < a.p || (reinterpret_cast<uintptr_t>(a.S[0]) & 15) || (reinterpret_cast<uintptr_t>(a.S[1]) & 15))
+    return hipErrorInvalidValue;      // (launch_small_folds' demands on strides and alignment)
+  return small_folds_dispatch(a, fo, st);
+}
+
+hipError_t small_folds_dispatch(const SmallArgs& a, const SmallFolds& fo, hipStream_t st) {
   switch (a.nb) {
     case 1: return launch_small_reg_fold<1>(a, fo, st);
     case 2: return launch_small_reg_fold<2>(a, fo, st);

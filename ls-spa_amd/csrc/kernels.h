@@ -97,6 +97,10 @@ struct SmallFolds {
 constexpr int64_t SMALL_FOLDS_MAX_GRID = 1 << 16;
 hipError_t launch_small_folds(const SmallArgs& a, const SmallFolds& fo, hipStream_t st);
 size_t small_folds_lds_bytes(int nb);   // dynamic LDS of a workgroup of launch_small_folds
+// Many problems on one set of orderings (lsspa_boot_lift_run): launch_small_folds' kernels and arguments with
+// 1 <= fo.folds <= 65535 problems and n_ord fo.folds <= SMALL_FOLDS_MAX_GRID; problem blockIdx.y has its pivot flag in
+// info[blockIdx.y].  No kernel of its own: the instantiations are launch_small_folds', whose refusals stay as they are.
+hipError_t launch_small_problems(const SmallArgs& a, const SmallFolds& fo, hipStream_t st);
 // host_perms.cpp: every row of perms [B][p] a permutation of 0..p-1?  (sets by AVX2 for 8 <= p <= 128, stamps otherwise;
 // _plain: the stamp loop alone, the test's comparison)
 bool all_permutations(const int32_t* perms, int B, int p, std::vector<int32_t>& mark);
@@ -678,6 +682,34 @@ hipError_t launch_boot_finalize(const double* S_tr, const double* S_te, const do
 // Z[i][0 .. p-1] = X[i][:], Z[i][p] = y[i], zero up to ldz, for rows row0 .. row0 + rows - 1 of Z; X [rows][ld], y [rows]
 hipError_t launch_boot_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Z,
                             int ldz, int64_t row0, hipStream_t st);
+
+// The bootstrap of the sampled attribution (lsspa_boot_lift_*; BootLiftPlan: boot_plan.h), p <= BOOT_LIFT_MAX_P = 127,
+// fp64: the launchers above for c = p + 1 up to 128 columns (cb up to 8), the finalise into the ordering kernels' layout
+// and the per-replicate statistics.
+// launch_boot_gram's part[slice][r][pair][256]: gram_form 0 goes through launch_boot_gram (cb <= 5, the existing
+// instantiations); gram_form 1 (cb = 6 .. 8) is the wide form, grid (slices, reps): the four waves of a workgroup share
+// rows and replicate and take the block pairs e with (e & 3) == wave.  reps <= 65535.
+hipError_t launch_boot_lift_gram(const BootLiftPlan& L, int side, const double* Z, int64_t n, const uint32_t* cnt,
+                                 const double* wt, int reps, double* part, hipStream_t st);
+// launch_boot_reduce and launch_boot_pack for p <= BOOT_LIFT_MAX_P: the same kernels
+hipError_t launch_boot_lift_reduce(const BootLiftPlan& L, int side, const double* part, int p, int reps, double* S,
+                                   hipStream_t st);
+hipError_t launch_boot_lift_pack(const void* X, int64_t ld, const void* y, int64_t rows, int p, int is_f32, double* Z,
+                                 int ldz, int64_t row0, hipStream_t st);
+// launch_boot_finalize's expressions into G, H [reps][BOOT_LIFT_LD][BOOT_LIFT_LD], g, h [reps][BOOT_LIFT_LD],
+// inv_yy [reps] and aug [reps][2] = {2 S_tr[p][p] / W + 1, 2 S_te[p][p] + 1}, the augmented rows' diagonals
+// (launch_cv_lift_finalize's rule).  Only rows and columns < p are written: the caller zeroes the buffers once.
+hipError_t launch_boot_lift_finalize(const double* S_tr, const double* S_te, const double* wsum_tr, int p, double reg,
+                                     int reps, double* G, double* g, double* H, double* h, double* inv_yy, double* aug,
+                                     hipStream_t st);
+// (mean, M2) [reps][d] += the n_s samples of raw [n_s * per][reps][p] (launch_small_problems' output): a sample's entry
+// by launch_cv_lift_fold's rules (off == NULL, d == p: the lift, or 0.5 * a + 0.5 * b of the pair; with the player
+// map's CSR the ascending-column sum from 0.0 per ordering, then the pair combined), Welford in sample order, one Chan
+// merge into the state of n_old samples (launch_multi_lift_stats' expressions).  One thread per (replicate, player),
+// plain stores.  samples (may be NULL): the entries [reps][n_s][d].
+hipError_t launch_boot_lift_stats(const double* raw, int p, int reps, int per, const int32_t* off, const int32_t* cols,
+                                  int d, int n_s, int64_t n_old, double* mean, double* M2, double* samples,
+                                  hipStream_t st);
 
 // Permutation test of the exact attribution (k_perm.hip, host_perms.cpp; PermPlan and perm_plan: boot_plan.h), p <=
 // GROUPS_MAX_P, fp64.  X of one side lives on the device as Xd [n][ldx], ldx = 16 cb, cb = ceil(p / 16), columns beyond p

@@ -223,6 +223,49 @@ struct CvLiftWork {
   }
 };
 
+// What the bootstrap of the sampled attribution keeps (lsspa_boot_lift_load .. lsspa_boot_lift_free): the rows of both
+// sides, the player map and the one set of orderings every replicate shares, and the buffers of one block of replicates
+// -- weights, Gram partials and sums, the problems at the ordering kernels' stride (rows of BOOT_LIFT_LD doubles), one
+// launch's raw lifts, the running (mean, M2) [block][d].  Nothing of the loaded problem, lsspa_boot_*, lsspa_cv_lift_*,
+// lsspa_multi_lift_* or any other store is in here.
+struct BootLiftWork {
+  bool loaded = false;
+  int p = 0;
+  int64_t n[2] = {0, 0};                   // rows: train, test
+  double reg = 0.0;
+  int ng = 0;                              // groups of the player map (0: none)
+  PlayerMap map;
+  DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
+  int sd() const { return ng ? ng : p; }   // the dimension of a sample
+  int64_t n_samples = 0;                   // samples of the orderings set (0: none)
+  int per = 1;                             // orderings a sample (2: antithetical)
+  DevBuf<int32_t> perms;                   // the orderings' rows, expanded
+  DevBuf<double> Z0, Z1;                   // [n][ldz] rows [X | y] of the two sides, zero-padded columns
+  DevBuf<char> stage_x, stage_y;
+  DevBuf<uint32_t> cnt0, cnt1;             // [block][n] bootstrap counts
+  DevBuf<double> wt0, wt1;                 // [block][n] caller's weights
+  DevBuf<double> part0, part1, S0, S1, wsum;
+  DevBuf<double> G, g, H, h, inv_yy, aug;  // [block][LD][LD], [block][LD], .., [block], [block][2]
+  DevBuf<double> raw, mean, M2, samples;   // one launch's raw lifts; [block][d] twice; one launch's samples (test hook)
+  DevBuf<int32_t> info;                    // [block]
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};     // kernel ms of the last pass: counts, Gram (to the problems), lifts, statistics
+  int64_t launches = 0;                    // its lift launches
+  DevBuf<double>& Z(int s) { return s ? Z1 : Z0; }
+  DevBuf<uint32_t>& cnt(int s) { return s ? cnt1 : cnt0; }
+  DevBuf<double>& wt(int s) { return s ? wt1 : wt0; }
+  DevBuf<double>& part(int s) { return s ? part1 : part0; }
+  DevBuf<double>& S(int s) { return s ? S1 : S0; }
+  void release() {
+    dev_free(Z0); dev_free(Z1); dev_free(stage_x); dev_free(stage_y); dev_free(cnt0); dev_free(cnt1);
+    dev_free(wt0); dev_free(wt1); dev_free(part0); dev_free(part1); dev_free(S0); dev_free(S1); dev_free(wsum);
+    dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(aug); dev_free(raw);
+    dev_free(mean); dev_free(M2); dev_free(samples); dev_free(info); dev_free(perms); dev_free(pl_off); dev_free(pl_cols);
+    loaded = false;
+    ng = 0;
+    n_samples = 0;
+  }
+};
+
 // What the permutation test keeps (lsspa_perm_load .. lsspa_perm_free): X and y of both sides on the device, the shared
 // G and H and the observed g, h, the index rows of two blocks of replicates (device and pinned host: the next block is
 // drawn and uploaded while this one runs), the partials of one block, and a MultiWork of its own whose response slots
@@ -393,6 +436,7 @@ struct lsspa_ctx {
   MultiWork multi;               // exact attribution of many responses at once (lsspa_multi_*)
   MultiLiftWork mlift;           // sampled attribution of many responses (lsspa_multi_lift_*)
   CvLiftWork cvlift;             // sampled attribution of the K-fold cross-validated R^2 (lsspa_cv_lift_*)
+  BootLiftWork bootlift;         // bootstrap of the sampled attribution (lsspa_boot_lift_*)
   PermWork perm;                 // permutation test of the exact attribution (lsspa_perm_*)
   DevBuf<double> mean_snap, n_snap;   // running mean / n after every chunk of a group folded in one launch (small p)
   DevBuf<double> grp_P, grp_S, grp_D, grp_s, grp_norms;   // launch_error_group: products, sums and their snapshots
@@ -1410,6 +1454,7 @@ int lsspa_destroy(lsspa_ctx* ctx) try {
   ctx->multi.release();
   ctx->mlift.release();
   ctx->cvlift.release();
+  ctx->bootlift.release();
   ctx->perm.release();
   dev_free(ctx->pl_off); dev_free(ctx->pl_cols);
   dev_free(ctx->pr_count); dev_free(ctx->pr_mean); dev_free(ctx->pr_m2); dev_free(ctx->pr_phi);
@@ -7232,6 +7277,462 @@ int lsspa_debug_cv_lift_plan(int32_t p, int32_t d, int32_t K, int64_t B, int32_t
   plan[6] = P.threads;
   plan[7] = 0;
   return LSSPA_OK;
+}
+
+}  // extern "C"
+
+// ---- bootstrap of the sampled attribution (k_boot.hip's wide Gram pass, launch_small_problems) -------------------------
+// The rows of both sides stay on the device as Z = [X | y] (ldz = 16 cb, cb <= 8); the orderings are set once and shared
+// by every replicate and the point problem.  A run goes block by block (boot_lift_plan): weights, the weighted Grams and
+// their sums, finalise into the ordering kernels' layout, then lift launches with the grid (orderings, replicates) --
+// cut into samples_per_launch samples and reps_per_launch replicates -- each followed by boot_lift_stats_kernel's merge
+// into the replicates' running (mean, M2).
+namespace {
+
+int bootlift_need_loaded(lsspa_ctx* ctx) {
+  if (!ctx->bootlift.loaded)
+    return ctx->fail(LSSPA_ERR_STATE, "no bootstrap data loaded for sampling (lsspa_boot_lift_load comes first)");
+  return LSSPA_OK;
+}
+
+// what a pass over replicates leaves with the caller; any pointer may be NULL
+struct BootLiftOut {
+  double *mean = nullptr, *m2 = nullptr, *r2 = nullptr, *base = nullptr, *samples = nullptr;
+  int32_t* info = nullptr;
+  double *G = nullptr, *g = nullptr, *H = nullptr, *h = nullptr, *inv_yy = nullptr;      // of the pass's first replicate
+  double *S_train = nullptr, *S_test = nullptr, *wsum = nullptr;                          // before finalise
+  bool lifts = false;               // run the orderings (else the Gram side only)
+};
+
+// Replicates first .. first + R - 1: a side's weights are the caller's rows w_host[s] [R][n], or ones, or the counts of
+// (seed, replicate, side).
+int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, int64_t first, const double* const w_host[2],
+                  bool ones, int64_t block, const BootLiftOut& out) {
+  BootLiftWork& B = ctx->bootlift;
+  const int p = B.p, d = B.sd(), c = p + 1;
+  constexpr int64_t LD = BOOT_LIFT_LD, LL = LD * LD;
+  const int per = out.lifts ? B.per : 1;
+  const int64_t n_samples = out.lifts ? B.n_samples : 1;
+  BootLiftPlan P;
+  if (const char* why = boot_lift_plan(R, B.n[0], B.n[1], p, d, n_samples, per == 2, block, P)) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s: %s", name, why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (w_host[0]) TRY(boot_check_weights(ctx, w_host[0], R, B.n[0], "w_train"));
+  if (w_host[1]) TRY(boot_check_weights(ctx, w_host[1], R, B.n[1], "w_test"));
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t blk = (size_t)P.block, cc = (size_t)c * c;
+  for (int s = 0; s < 2; ++s) {
+    if (!w_host[s] && !ones)
+      TRY(dev_alloc(ctx, B.cnt(s), blk * (size_t)B.n[s]));
+    else
+      TRY(dev_alloc(ctx, B.wt(s), blk * (size_t)B.n[s]));
+    TRY(dev_alloc(ctx, B.part(s), (size_t)P.slices[s] * blk * P.pairs * 256));
+    TRY(dev_alloc(ctx, B.S(s), blk * cc));
+  }
+  TRY(dev_alloc(ctx, B.wsum, blk));
+  TRY(dev_alloc(ctx, B.G, blk * LL));
+  TRY(dev_alloc(ctx, B.H, blk * LL));
+  TRY(dev_alloc(ctx, B.g, blk * LD));
+  TRY(dev_alloc(ctx, B.h, blk * LD));
+  TRY(dev_alloc(ctx, B.inv_yy, blk));
+  TRY(dev_alloc(ctx, B.aug, 2 * blk));
+  TRY(dev_alloc(ctx, B.info, blk));
+  const int64_t E = std::min<int64_t>(P.reps_per_launch, P.block), S = P.samples_per_launch;
+  if (out.lifts) {
+    TRY(dev_alloc(ctx, B.raw, (size_t)(S * per * E * p)));
+    TRY(dev_alloc(ctx, B.mean, blk * d));
+    TRY(dev_alloc(ctx, B.M2, blk * d));
+    if (out.samples) TRY(dev_alloc(ctx, B.samples, (size_t)(E * S * d)));
+  }
+  HIPCHK(hipStreamSynchronize(st));        // a previous call may still read the buffers
+  // the columns behind p of a problem's rows are read (the register-resident gather fetches pairs), never used: zero
+  HIPCHK(hipMemsetAsync(B.G.ptr, 0, sizeof(double) * blk * LL, st));
+  HIPCHK(hipMemsetAsync(B.H.ptr, 0, sizeof(double) * blk * LL, st));
+  HIPCHK(hipMemsetAsync(B.g.ptr, 0, sizeof(double) * blk * LD, st));
+  HIPCHK(hipMemsetAsync(B.h.ptr, 0, sizeof(double) * blk * LD, st));
+  const int64_t cuts = P.sample_cuts, per_block = (P.block + E - 1) / E * cuts;
+  std::vector<hipEvent_t> ev((size_t)(3 + (out.lifts ? 2 * per_block : 0)), nullptr);
+  Events guard{ev};
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  const int g = B.ng;
+  const int64_t rows_per = g ? per : 1;      // rows of perms a sample takes on the device
+  SmallArgs a{};
+  a.s[0] = B.g.ptr;
+  a.s[1] = B.h.ptr;
+  a.ld_src = LD;
+  a.fwd_only = (!g && per == 2) ? 1 : 0;     // with a map both rows of a pair are explicit (the baseline stays first)
+  a.p = p;
+  a.nb = P.cb;
+  a.per_sample = per;
+  a.lifts = B.raw.ptr;
+  a.y_norm_sq = 1.0;
+  a.piv_tol = exact_piv_tol(p);
+  a.sum_tol = -1.0;
+  SmallFolds fo{};
+  fo.mat = LL;
+  fo.vec = LD;
+  std::vector<double> one, Gh, Hh, gh, hh, yh, ws;
+  std::vector<int> all((size_t)p), basec;
+  for (int j = 0; j < p; ++j) all[(size_t)j] = j;
+  if (g) basec.assign(B.map.base.begin(), B.map.base.end());
+  constexpr int CH = 32;                     // replicates whose problems come to the host at a time (their R^2)
+  if (out.r2 || out.base) {
+    Gh.resize((size_t)CH * LD * p);
+    Hh.resize((size_t)CH * LD * p);
+    gh.resize((size_t)CH * p);
+    hh.resize((size_t)CH * p);
+    yh.resize(CH);
+  }
+  B.ms[0] = B.ms[1] = B.ms[2] = B.ms[3] = 0.0;
+  B.launches = 0;
+  for (int64_t b0 = 0; b0 < R; b0 += P.block) {
+    const int nb = (int)std::min<int64_t>(P.block, R - b0);
+    HIPCHK(hipEventRecord(ev[0], st));
+    for (int s = 0; s < 2; ++s) {
+      if (w_host[s]) {
+        HIPCHK(hipMemcpyAsync(B.wt(s).ptr, w_host[s] + b0 * B.n[s], sizeof(double) * (size_t)nb * B.n[s],
+                              hipMemcpyHostToDevice, st));
+      } else if (ones) {
+        one.assign((size_t)nb * B.n[s], 1.0);
+        HIPCHK(hipMemcpyAsync(B.wt(s).ptr, one.data(), sizeof(double) * one.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));        // `one` is reused for the other side
+      } else {
+        HIPCHK(launch_boot_counts(seed, (uint64_t)first + (uint64_t)b0, s, B.n[s], nb, B.cnt(s).ptr, st));
+      }
+    }
+    HIPCHK(hipEventRecord(ev[1], st));
+    for (int s = 0; s < 2; ++s) {
+      const bool counts = !w_host[s] && !ones;
+      const uint32_t* cnt = counts ? B.cnt(s).ptr : nullptr;
+      const double* wt = counts ? nullptr : B.wt(s).ptr;
+      HIPCHK(launch_boot_lift_gram(P, s, B.Z(s).ptr, B.n[s], cnt, wt, nb, B.part(s).ptr, st));
+      if (s == 0) HIPCHK(launch_boot_wsum(cnt, wt, B.n[s], nb, B.wsum.ptr, st));
+      HIPCHK(launch_boot_lift_reduce(P, s, B.part(s).ptr, p, nb, B.S(s).ptr, st));
+    }
+    HIPCHK(launch_boot_lift_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
+                                     B.inv_yy.ptr, B.aug.ptr, st));
+    HIPCHK(hipEventRecord(ev[2], st));
+    HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
+    size_t ne = 3;
+    if (out.lifts) {
+      for (int64_t e0 = 0; e0 < nb; e0 += E) {
+        const int nr = (int)std::min<int64_t>(E, nb - e0);
+        a.S[0] = B.G.ptr + e0 * LL;
+        a.S[1] = B.H.ptr + e0 * LL;
+        a.s[0] = B.g.ptr + e0 * LD;
+        a.s[1] = B.h.ptr + e0 * LD;
+        a.info = B.info.ptr + e0;
+        fo.aug = B.aug.ptr + 2 * e0;
+        fo.inv_yy = B.inv_yy.ptr + e0;
+        fo.folds = nr;
+        for (int64_t s0 = 0; s0 < n_samples; s0 += S) {
+          const int ns = (int)std::min<int64_t>(S, n_samples - s0);
+          a.perms = B.perms.ptr + s0 * rows_per * p;
+          a.n_ord = ns * per;
+          HIPCHK(launch_small_problems(a, fo, st));
+          HIPCHK(hipEventRecord(ev[ne++], st));
+          HIPCHK(launch_boot_lift_stats(B.raw.ptr, p, nr, per, g ? B.pl_off.ptr : nullptr, g ? B.pl_cols.ptr : nullptr, d,
+                                        ns, s0, B.mean.ptr + e0 * d, B.M2.ptr + e0 * d,
+                                        out.samples ? B.samples.ptr : nullptr, st));
+          HIPCHK(hipEventRecord(ev[ne++], st));
+          if (out.samples)
+            HIPCHK(hipMemcpy2DAsync(out.samples + ((b0 + e0) * n_samples + s0) * d, sizeof(double) * n_samples * d,
+                                    B.samples.ptr, sizeof(double) * ns * d, sizeof(double) * ns * d, (size_t)nr,
+                                    hipMemcpyDeviceToHost, st));
+          ++B.launches;
+        }
+      }
+      if (out.mean)
+        HIPCHK(hipMemcpyAsync(out.mean + b0 * d, B.mean.ptr, sizeof(double) * (size_t)nb * d, hipMemcpyDeviceToHost, st));
+      if (out.m2)
+        HIPCHK(hipMemcpyAsync(out.m2 + b0 * d, B.M2.ptr, sizeof(double) * (size_t)nb * d, hipMemcpyDeviceToHost, st));
+    }
+    if (out.info) HIPCHK(hipMemcpyAsync(out.info + b0, B.info.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+    if (out.S_train)
+      HIPCHK(hipMemcpyAsync(out.S_train + b0 * cc, B.S0.ptr, sizeof(double) * nb * cc, hipMemcpyDeviceToHost, st));
+    if (out.S_test)
+      HIPCHK(hipMemcpyAsync(out.S_test + b0 * cc, B.S1.ptr, sizeof(double) * nb * cc, hipMemcpyDeviceToHost, st));
+    if (out.wsum) HIPCHK(hipMemcpyAsync(out.wsum + b0, B.wsum.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+    if (b0 == 0) {
+      const size_t w = sizeof(double) * p;
+      if (out.G) HIPCHK(hipMemcpy2DAsync(out.G, w, B.G.ptr, sizeof(double) * LD, w, (size_t)p, hipMemcpyDeviceToHost, st));
+      if (out.H) HIPCHK(hipMemcpy2DAsync(out.H, w, B.H.ptr, sizeof(double) * LD, w, (size_t)p, hipMemcpyDeviceToHost, st));
+      if (out.g) HIPCHK(hipMemcpyAsync(out.g, B.g.ptr, w, hipMemcpyDeviceToHost, st));
+      if (out.h) HIPCHK(hipMemcpyAsync(out.h, B.h.ptr, w, hipMemcpyDeviceToHost, st));
+      if (out.inv_yy) HIPCHK(hipMemcpyAsync(out.inv_yy, B.inv_yy.ptr, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 2; ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      B.ms[k] += ms;
+    }
+    for (size_t k = 2; k + 1 < ne; ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      B.ms[2 + (k & 1)] += ms;             // ev[2] -> ev[3]: a lift launch; ev[3] -> ev[4]: its statistics; ...
+    }
+    if (out.r2 || out.base)                // R^2 of the full model and of the baseline's columns, on the host
+      for (int c0 = 0; c0 < nb; c0 += CH) {
+        const int nc = std::min(CH, nb - c0);
+        const size_t w = sizeof(double) * p;
+        HIPCHK(hipMemcpy2D(Gh.data(), w, B.G.ptr + c0 * LL, sizeof(double) * LD, w, (size_t)nc * LD, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(Hh.data(), w, B.H.ptr + c0 * LL, sizeof(double) * LD, w, (size_t)nc * LD, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(gh.data(), w, B.g.ptr + c0 * LD, sizeof(double) * LD, w, (size_t)nc, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(hh.data(), w, B.h.ptr + c0 * LD, sizeof(double) * LD, w, (size_t)nc, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(yh.data(), B.inv_yy.ptr + c0, sizeof(double) * nc, hipMemcpyDeviceToHost));
+        for (int r = 0; r < nc; ++r) {
+          const double *Gr = &Gh[(size_t)r * LD * p], *Hr = &Hh[(size_t)r * LD * p];
+          const double *gr = &gh[(size_t)r * p], *hr = &hh[(size_t)r * p];
+          if (out.r2) out.r2[b0 + c0 + r] = boot_r2_cols(p, all.data(), p, Gr, gr, Hr, hr, yh[(size_t)r], ws);
+          if (out.base)
+            out.base[b0 + c0 + r] = boot_r2_cols(p, basec.data(), (int)basec.size(), Gr, gr, Hr, hr, yh[(size_t)r], ws);
+        }
+      }
+  }
+  return LSSPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsspa_boot_lift_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, const void* y_train, int64_t N,
+                         const void* X_test, int64_t ld_test, const void* y_test, int64_t M, int32_t p, double reg,
+                         int32_t dtype, int32_t location) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  char msg[240];
+  if (p > BOOT_LIFT_MAX_P) {
+    snprintf(msg, sizeof msg, "lsspa_boot_lift_load takes at most p = %d features (%d given): both work matrices of an "
+             "ordering, p + 1 rows each, stay in one workgroup", BOOT_LIFT_MAX_P, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  BootLiftPlan P;
+  if (const char* why = boot_lift_plan(1, N, M, p, p < 1 ? 1 : p, 1, 0, 0, P)) {
+    snprintf(msg, sizeof msg, "lsspa_boot_lift_load: %s", why);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (N < p || M < p) {
+    snprintf(msg, sizeof msg, "lsspa_boot_lift_load: N = %lld and M = %lld rows must both be at least p = %d (the Gram "
+             "matrices of both sides must have a Cholesky factor)", (long long)N, (long long)M, (int)p);
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  }
+  if (!X_train || !y_train || !X_test || !y_test || ld_train < p || ld_test < p || !std::isfinite(reg) || reg < 0.0 ||
+      (dtype != LSSPA_F64 && dtype != LSSPA_F32) || (location != LSSPA_HOST && location != LSSPA_DEVICE))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_load: NULL array, ld < p, reg not finite and >= 0, or bad dtype / "
+                                    "location");
+  if (location == LSSPA_HOST) {
+    bool any = false;
+    for (int64_t i = 0; i < M && !any; ++i)
+      any = dtype == LSSPA_F32 ? ((const float*)y_test)[i] != 0.f : ((const double*)y_test)[i] != 0.0;
+    if (!any) return ctx->fail(LSSPA_ERR_ARG, "y_test is identically zero (sum y^2 = 0): R^2 is not defined");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  BootLiftWork& B = ctx->bootlift;
+  B.loaded = false;
+  B.ng = 0;                // a player map and the orderings belong to the data they were set on
+  B.n_samples = 0;
+  const void* X[2] = {X_train, X_test};
+  const void* y[2] = {y_train, y_test};
+  const int64_t n[2] = {N, M}, ld[2] = {ld_train, ld_test};
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int s = 0; s < 2; ++s) {
+    TRY(dev_alloc(ctx, B.Z(s), (size_t)n[s] * P.ldz));
+    TRY(load_rows(ctx, B.stage_x, B.stage_y, X[s], ld[s], y[s], n[s], p, dtype, location,
+                  [&](const void* sx, const void* sy, int64_t nr, int64_t r0) {
+                    return launch_boot_lift_pack(sx, ld[s], sy, nr, p, dtype == LSSPA_F32, B.Z(s).ptr, P.ldz, r0,
+                                                 ctx->stream);
+                  }));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  dev_free(B.stage_x);
+  dev_free(B.stage_y);
+  B.p = p;
+  B.n[0] = N;
+  B.n[1] = M;
+  B.reg = reg;
+  B.ms[0] = B.ms[1] = B.ms[2] = B.ms[3] = 0.0;
+  B.loaded = true;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(bootlift_need_loaded(ctx));
+  BootLiftWork& B = ctx->bootlift;
+  if (!labels && g != 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
+  PlayerMap map;
+  if (labels) {
+    const char* why = player_map_build(labels, B.p, g, map);
+    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));      // a previous run may still read the tables
+  B.n_samples = 0;                                // the orderings were orderings of the other players
+  if (labels) {
+    TRY(dev_alloc(ctx, B.pl_off, (size_t)B.p + 1));
+    TRY(dev_alloc(ctx, B.pl_cols, (size_t)B.p));
+    HIPCHK(hipMemcpy(B.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
+    if (!map.cols.empty())
+      HIPCHK(hipMemcpy(B.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
+    B.map = std::move(map);
+    B.ng = g;
+  } else {
+    B.ng = 0;
+  }
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_set_orderings(lsspa_ctx* ctx, const int32_t* perms, int64_t n_samples, int32_t antithetical) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(bootlift_need_loaded(ctx));
+  BootLiftWork& B = ctx->bootlift;
+  const int p = B.p, g = B.ng, d = B.sd();
+  if (!perms || n_samples < 1 || n_samples > (int64_t)INT32_MAX / (2 * p))
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_set_orderings: perms is NULL, n_samples < 1 or 2 n_samples p >= 2^31");
+  if (!all_permutations(perms, (int)n_samples, d, ctx->perm_mark))
+    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_boot_lift_set_orderings: a row of perms is not a permutation of 0 .. g-1 (a "
+                                        "player map is set: the orderings are orderings of the groups)"
+                                      : "lsspa_boot_lift_set_orderings: a row of perms is not a permutation of 0 .. p-1");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int per = antithetical ? 2 : 1;
+  const int64_t rows_per = g ? per : 1;
+  HIPCHK(hipStreamSynchronize(ctx->stream));      // a previous run may still read the rows
+  B.n_samples = 0;
+  TRY(dev_alloc(ctx, B.perms, (size_t)(n_samples * rows_per * p)));
+  const int32_t* src = perms;
+  std::vector<int32_t> rows;
+  if (g) {      // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
+    rows.resize((size_t)(n_samples * rows_per * p));
+    for (int64_t s = 0; s < n_samples; ++s)
+      for (int r = 0; r < per; ++r) expand_group_row(B.map, perms + s * g, r, rows.data() + (size_t)((s * per + r) * p));
+    src = rows.data();
+  }
+  HIPCHK(hipMemcpy(B.perms.ptr, src, sizeof(int32_t) * (size_t)(n_samples * rows_per * p), hipMemcpyHostToDevice));
+  B.n_samples = n_samples;
+  B.per = per;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_run(lsspa_ctx* ctx, int64_t R, uint64_t boot_seed, int64_t first, const double* w_train,
+                        const double* w_test, int64_t block, double* mean, double* m2, double* r2, double* baseline_r2,
+                        int32_t* info, double* samples_out) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(bootlift_need_loaded(ctx));
+  if (ctx->bootlift.n_samples < 1)
+    return ctx->fail(LSSPA_ERR_STATE, "no orderings set (lsspa_boot_lift_set_orderings comes first)");
+  if (!mean || !m2 || !r2 || !info || first < 0)
+    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_run: mean / m2 / r2 / info NULL or first < 0");
+  BootLiftOut out;
+  out.mean = mean;
+  out.m2 = m2;
+  out.r2 = r2;
+  out.base = baseline_r2;
+  out.info = info;
+  out.samples = samples_out;
+  out.lifts = true;
+  const double* const w[2] = {w_train, w_test};
+  return bootlift_pass(ctx, "lsspa_boot_lift_run", R, boot_seed, first, w, false, block, out);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_point(lsspa_ctx* ctx, double* mean, double* m2, double* r2, double* baseline_r2, int32_t* info,
+                          double* samples_out) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(bootlift_need_loaded(ctx));
+  if (ctx->bootlift.n_samples < 1)
+    return ctx->fail(LSSPA_ERR_STATE, "no orderings set (lsspa_boot_lift_set_orderings comes first)");
+  if (!mean || !m2 || !r2 || !info) return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_point: mean / m2 / r2 / info NULL");
+  BootLiftOut out;
+  out.mean = mean;
+  out.m2 = m2;
+  out.r2 = r2;
+  out.base = baseline_r2;
+  out.info = info;
+  out.samples = samples_out;
+  out.lifts = true;
+  const double* const w[2] = {nullptr, nullptr};
+  return bootlift_pass(ctx, "lsspa_boot_lift_point", 1, 0, 0, w, true, 1, out);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_get_problem(lsspa_ctx* ctx, int64_t r, uint64_t boot_seed, const double* w_train, const double* w_test,
+                                double* G, double* g, double* H, double* h, double* inv_yy) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(bootlift_need_loaded(ctx));
+  BootLiftOut out;
+  out.G = G;
+  out.g = g;
+  out.H = H;
+  out.h = h;
+  out.inv_yy = inv_yy;
+  const double* const w[2] = {w_train, w_test};
+  // r < 0: the point problem, weight 1 on every row of a side without weights
+  return bootlift_pass(ctx, "lsspa_boot_lift_get_problem", 1, boot_seed, r < 0 ? 0 : r, w, r < 0, 1, out);
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_debug_grams(lsspa_ctx* ctx, int64_t R, const double* w_train, const double* w_test, double* S_train,
+                                double* S_test, double* wsum) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  TRY(bootlift_need_loaded(ctx));
+  BootLiftOut out;
+  out.S_train = S_train;
+  out.S_test = S_test;
+  out.wsum = wsum;
+  const double* const w[2] = {w_train, w_test};
+  return bootlift_pass(ctx, "lsspa_boot_lift_debug_grams", R, 0, 0, w, true, 0, out);   // no weights: ones, not counts
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_boot_lift_timing(const lsspa_ctx* ctx, double* counts_ms, double* gram_ms, double* lift_ms, double* stats_ms,
+                           int64_t* launches) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  if (counts_ms) *counts_ms = ctx->bootlift.ms[0];
+  if (gram_ms) *gram_ms = ctx->bootlift.ms[1];
+  if (lift_ms) *lift_ms = ctx->bootlift.ms[2];
+  if (stats_ms) *stats_ms = ctx->bootlift.ms[3];
+  if (launches) *launches = ctx->bootlift.launches;
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(const_cast<lsspa_ctx*>(ctx));
+}
+
+int lsspa_boot_lift_free(lsspa_ctx* ctx) try {
+  if (!ctx) return LSSPA_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->bootlift.release();
+  return LSSPA_OK;
+} catch (...) {
+  return abi_caught(ctx);
+}
+
+int lsspa_debug_boot_lift_plan(int64_t R, int64_t N, int64_t M, int32_t p, int32_t d, int64_t n_samples,
+                               int32_t antithetical, int64_t block, int64_t* plan16) try {
+  BootLiftPlan P;
+  if (!plan16 || boot_lift_plan(R, N, M, p, d, n_samples, antithetical, block, P)) return LSSPA_ERR_ARG;
+  const int64_t v[16] = {P.cb, P.gram_form, P.rps[0], P.rps[1], P.slices[0], P.slices[1], P.block, P.n_blocks,
+                         P.reps_per_launch, P.ord_per_launch, P.samples_per_launch, P.sample_cuts, P.launches,
+                         P.raw_bytes, P.lift_form, P.rep_bytes};
+  std::copy(v, v + 16, plan16);
+  return LSSPA_OK;
+} catch (...) {
+  return LSSPA_ERR_NOMEM;
 }
 
 }  // extern "C"

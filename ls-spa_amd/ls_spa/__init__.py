@@ -33,18 +33,20 @@ groups of p <= 64 columns, returning ``TopGroupSubsetsCVResults``) and ``ls_spa_
 ridge values on one load, row by row its bits, with the choice of the value the folds prefer, returning
 ``CVPathResults``, with ``groups=`` ``CVGroupPathResults``) and ``ls_spa_cv_sampled`` (the sampled attribution of
 that cross-validated R^2 for p <= 127, or with ``groups=`` over groups of those columns, returning ``SampledCVResults``
-and ``SampledCVGroupResults``)
+and ``SampledCVGroupResults``) and ``ls_spa_bootstrap_sampled`` (bootstrap confidence intervals for the sampled
+attribution for p <= 127, all replicates on one shared set of orderings, returning ``SampledBootstrapResults``, with
+``groups=`` ``SampledBootstrapGroupResults``)
 are this package's own.  Every ordering is evaluated by hand-written HIP kernels for gfx950
 behind a C ABI (include/lsspa.h); there is no CPU fallback.
 """
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupPathResults, CVGroupResults, CVPathResults,
                        CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
-                       SampledCVGroupResults, SampledCVResults, SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
+                       SampledBootstrapGroupResults, SampledBootstrapResults, SampledCVGroupResults, SampledCVResults, SampledInteractionResults, SampledMultiGroupResults, SampledMultiResults, ShapleyResults, SizeIncompatible,
                        TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults, TopSubsetsResults,
                        validate_data)
 from ._stats import error_estimates, error_estimates_lowrank, merge_sample_cov, merge_sample_mean
-from ._driver import (ls_spa, ls_spa_cv, ls_spa_cv_path, ls_spa_cv_sampled, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
+from ._driver import (ls_spa, ls_spa_cv, ls_spa_cv_path, ls_spa_cv_sampled, ls_spa_best_subsets_cv, cv_fold_ids, ls_spa_best_group_subsets_bootstrap, ls_spa_best_subsets, ls_spa_best_subsets_bootstrap, ls_spa_bootstrap, ls_spa_bootstrap_sampled, ls_spa_groups, ls_spa_interactions, ls_spa_interactions_bootstrap,
                       ls_spa_interactions_sampled, ls_spa_multi, ls_spa_multi_sampled, ls_spa_owen,
                       ls_spa_permutation_test, ls_spa_top_group_subsets, ls_spa_top_group_subsets_cv, ls_spa_top_subsets,
                       ls_spa_top_subsets_cv,
@@ -71,4 +73,5 @@ __all__ = [
     "ls_spa_top_group_subsets_cv", "TopGroupSubsetsCVResults",
     "ls_spa_cv_path", "CVPathResults", "CVGroupPathResults",
     "ls_spa_cv_sampled", "SampledCVResults", "SampledCVGroupResults",
+    "ls_spa_bootstrap_sampled", "SampledBootstrapResults", "SampledBootstrapGroupResults",
 ]

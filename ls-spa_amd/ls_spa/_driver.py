@@ -33,6 +33,7 @@ from . import _samplers as S
 from ._native import LSSPANativeError
 from ._results import (CVBestGroupSubsetsResults, CVBestSubsetsResults, CVGroupPathResults, CVGroupResults, CVPathResults,
                        CVResults, BestGroupSubsetsBootstrapResults, BestGroupSubsetsResults, BestSubsetsBootstrapResults, BestSubsetsResults, BootstrapResults, InteractionBootstrapResults, InteractionResults, MultiGroupResults,
+                       SampledBootstrapGroupResults, SampledBootstrapResults,
                        SampledCVGroupResults, SampledCVResults, SampledMultiGroupResults, SampledMultiResults,
                        MultiResponseResults, OwenResults, PermutationTestResults,
                        SampledInteractionResults, ShapleyResults, SizeIncompatible, TopGroupSubsetsCVResults, TopGroupSubsetsResults, TopSubsetsCVResults,
@@ -2533,6 +2534,121 @@ def ls_spa_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed
     res = BootstrapResults.from_replicates(phi, theta, r_squared, rep, r2, failed, confidence, *base)
     _warn_failed_replicates(res.n_failed, n_boot, "`replicates` and left out of the intervals")
     return res
+
+
+BOOT_LIFT_MAX_P = 127      # include/lsspa.h, LSSPA_BOOT_LIFT_MAX_P
+
+
+def ls_spa_bootstrap_sampled(X_train, X_test, y_train, y_test, reg=0., n_boot=200, n_samples=2 ** 10, seed=42, perms=None,
+                             *, groups=None, method="random", antithetical=True, boot_seed=42, confidence=0.95,
+                             weights=None, resample=("train", "test"), device=0, _engine=None):
+    """Bootstrap confidence intervals for the SAMPLED attribution (1 <= p <= 127; with ``groups=`` any 1 <= g <= p
+    groups of those columns): what ``ls_spa_bootstrap`` gives for the exact enumerations, beyond their limits.
+
+    ``ls_spa`` returns an attribution and a Monte-Carlo standard error that says how well the orderings were sampled;
+    this call says how far the attribution would move had the rows been another draw from the same population.  Each of
+    the ``n_boot`` replicates resamples the rows with replacement -- on the GPU, from rows that stay there, by
+    ``ls_spa_bootstrap``'s counts rule: a given ``boot_seed`` resamples exactly the rows that call's ``seed`` resamples
+    -- and is re-attributed over ONE set of ``n_samples`` orderings that is drawn ahead and shared by all replicates
+    and the point estimate (common random numbers): the Monte-Carlo error of the orderings moves all replicates
+    together instead of widening their spread.  One launch runs a cut of the orderings through many replicates'
+    problems at once (include/lsspa.h, lsspa_boot_lift_run).  fp64 throughout; two calls agree bitwise.
+
+    n_samples, seed, method, perms, antithetical:  the ordering source, as in ``ls_spa_multi_sampled`` (``seed`` seeds it;
+        a caller's ``perms`` are taken as they are, all of them).  The number of samples is fixed -- there is no
+        ``tolerance`` -- so that every replicate sees the same ones.
+    boot_seed, weights, resample, confidence:  ``ls_spa_bootstrap``'s ``seed``, ``weights``, ``resample`` and
+        ``confidence``.
+    groups:  one integer label per column as ``ls_spa_groups`` takes them (-1: the baseline, 0 .. g-1).  The players are
+        then the groups, the sources run in dimension g, ``perms`` are group orderings, and the result is a
+        ``SampledBootstrapGroupResults``.
+
+    Returns ``SampledBootstrapResults``: ``attribution`` and ``attribution_errors`` [d] (the original rows, weight 1 on
+    every row, through the same path as one more problem), ``replicates`` and ``replicate_errors`` [n_boot][d],
+    ``std_error``, ``lower``, ``upper``, ``prob_greater`` [d][d], ``r_squared``, ``r_squared_replicates``,
+    ``r_squared_interval``, ``theta``, ``n_samples`` and ``n_failed``: a replicate whose G or H fails the pivot test in any
+    ordering is NaN and left out, with a RuntimeWarning; more than half of them is a RuntimeError.
+
+    Shapes that do not fit, p > 127, fewer rows than columns on either side, ``n_boot`` < 2, ``n_samples`` < 2, ``perms``
+    together with ``method``, bad labels, ``weights``, ``resample`` or ``confidence`` and a ``y_test`` that is identically
+    zero are refused before any GPU work.  Several ranks, checkpoints, fp32, the device error estimator and the history
+    are not part of this function."""
+    sa, se = np.shape(X_train), np.shape(X_test)
+    if len(sa) == 2 and len(se) == 2 and sa[1] == se[1]:      # the limits by their names, ahead of the shape rules
+        if sa[1] > BOOT_LIFT_MAX_P:
+            raise ValueError(f"ls_spa_bootstrap_sampled takes at most p = {BOOT_LIFT_MAX_P} features (this problem has "
+                             f"p = {sa[1]})")
+        if 1 <= sa[1] and (sa[0] < sa[1] or se[0] < sa[1]) and np.shape(y_train) == sa[:1] and np.shape(y_test) == se[:1]:
+            raise ValueError(f"ls_spa_bootstrap_sampled needs at least p = {sa[1]} rows on both sides (N = {sa[0]}, M = "
+                             f"{se[0]}): a resampled Gram matrix must have a Cholesky factor")
+    data = _coerce_data(X_train, X_test, y_train, y_test)
+    n, p = data[0].shape
+    m = data[1].shape[0]
+    if p < 1:
+        raise ValueError("ls_spa_bootstrap_sampled needs p >= 1 features")
+    if int(n_samples) != n_samples or n_samples < 2:
+        raise ValueError(f"n_samples must be an integer >= 2 (got {n_samples!r})")
+    options = _bootstrap_options(n_boot, confidence, weights, resample, n, m)
+    n_boot, n_samples = int(n_boot), int(n_samples)
+    if not np.any(data[3]):
+        raise ValueError("y_test is identically zero: R^2 is not defined")
+    labels, d = None, p                # d: the dimension of a sample
+    if groups is not None:
+        labels, d = group_labels(groups, p, max_groups=None)
+    if perms is not None:
+        if method != "random":
+            raise ValueError("pass either perms= or method=, not both")
+        method = None
+    elif method not in S.METHODS:
+        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
+    _, source, _, antithetical, max_samples, _ = prepare_sampling(
+        d, max_samples=n_samples, batch_size=2 ** 8, seed=seed, perms=perms, antithetical=bool(antithetical),
+        method=method)
+    w_train, w_test, sides = options
+    fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
+    undo = [(lambda: _close_source(source), True)]
+    with _engine_call(_engine, device, undo=undo) as engine:
+        rows = []                      # the one set of orderings, drawn ahead
+        while sum(len(r) for r in rows) < max_samples:
+            got = source.take(min(2 ** 10, max_samples - sum(len(r) for r in rows)))
+            if len(got) == 0:
+                break
+            rows.append(np.array(got, dtype=np.int32))
+        if sum(len(r) for r in rows) < 2:
+            raise ValueError("fewer than two orderings to sample: perms needs at least two rows")
+        rows = np.concatenate(rows)
+        undo.append((engine.boot_lift_free, True))
+        engine.boot_lift_load(*data, reg)
+        if labels is not None:
+            engine.boot_lift_set_players(labels)      # (boot_lift_free drops the map with everything else)
+        engine.boot_lift_set_orderings(rows, antithetical)
+        phi, phi_m2, r_squared, base, info = engine.boot_lift_point()
+        G, g = engine.boot_lift_problem(-1)[:2]
+        parts = _bootstrap_parts(engine.boot_lift_run, n_boot, boot_seed, w_train, w_test, fixed, n, m)
+        rep, rep_m2, r2, r2_base, binfo = (np.concatenate([q[k] for q in parts]) for k in range(5))
+    ns = len(rows)
+    _info_verdict(info & 1, stacklevel=2)
+    failed = (binfo & 1).astype(bool) | ~np.isfinite(rep).all(axis=1) | ~np.isfinite(r2) | ~np.isfinite(r2_base)
+    # every sample's lifts telescope from the baseline's value to the full model's, so a replicate's mean does (the
+    # bound of LSSPA_INFO_SUM for well-conditioned data)
+    gap = np.abs(rep.sum(axis=1) - (r2 - r2_base)) > 1e-9 * np.maximum(1.0, np.abs(r2))
+    point_gap = abs(phi.sum() - (r_squared - base)) > 1e-9 * max(1.0, abs(r_squared))
+    if (gap & ~failed).any() or (point_gap and not info & 1):
+        _info_verdict(8, stacklevel=2)
+    core = BootstrapResults.from_replicates(phi, _subset_fit(G, g, np.arange(p)), r_squared, rep, r2, failed, confidence,
+                                            r2_base)
+    errors = _multi_standard_errors(ns, rep_m2)
+    errors[failed] = np.nan
+    common = dict(attribution=phi, attribution_errors=_multi_standard_errors(ns, phi_m2), theta=core.theta,
+                  r_squared=float(r_squared), replicates=core.replicates, replicate_errors=errors,
+                  r_squared_replicates=core.r_squared_replicates, std_error=core.std_error, lower=core.lower,
+                  upper=core.upper, r_squared_interval=core.r_squared_interval, prob_greater=core.prob_greater,
+                  n_samples=ns, n_failed=core.n_failed, confidence=core.confidence)
+    _warn_failed_replicates(core.n_failed, n_boot, "`replicates` and left out of the intervals")
+    if labels is not None:
+        return SampledBootstrapGroupResults(baseline_r_squared=float(base),
+                                            baseline_r_squared_replicates=core.baseline_r_squared_replicates, **common)
+    return SampledBootstrapResults(**common)
 
 
 def ls_spa_interactions_bootstrap(X_train, X_test, y_train, y_test, reg=0., n_boot=1000, seed=42, *, confidence=0.95,

@@ -229,6 +229,24 @@ def debug_cv_plan(p: int, folds: int):
     return dict(zip(CV_PLAN_FIELDS, (int(v) for v in out)))
 
 
+BOOT_LIFT_PLAN_FIELDS = ("cb", "gram_form", "rps_train", "rps_test", "slices_train", "slices_test", "block", "n_blocks",
+                         "reps_per_launch", "orderings_per_launch", "samples_per_launch", "sample_cuts", "launches",
+                         "raw_bytes", "lift_form", "rep_bytes")
+
+
+def debug_boot_lift_plan(R: int, n: int, m: int, p: int, d: int, n_samples: int, antithetical: bool, block: int = 0):
+    """Test hook, host only: how boot_lift_run cuts R replicates of n / m rows, p columns, samples of dimension d and
+    n_samples samples (include/lsspa.h, lsspa_debug_boot_lift_plan) -- a dict with BOOT_LIFT_PLAN_FIELDS; gram_form 1 is
+    the wide Gram kernel (cb = 6 .. 8), lift_form 1 the LDS-resident ordering kernel.  ValueError for arguments the
+    library refuses."""
+    out = np.zeros(16, dtype=np.int64)
+    rc = N.load().lsspa_debug_boot_lift_plan(int(R), int(n), int(m), int(p), int(d), int(n_samples),
+                                             int(bool(antithetical)), int(block), out.ctypes.data_as(N._pi64))
+    if rc != N.OK:
+        raise ValueError(f"lsspa_debug_boot_lift_plan: status {rc}")
+    return dict(zip(BOOT_LIFT_PLAN_FIELDS, (int(v) for v in out)))
+
+
 CV_LIFT_PLAN_FIELDS = ("nb", "form", "workgroups_per_sample", "samples_per_launch", "launches", "lds_bytes", "workgroup")
 
 
@@ -1331,6 +1349,122 @@ class HipEngine:
         self._cv_lift_dims, self._cv_lift_g = None, 0
 
     debug_cv_lift_plan = staticmethod(debug_cv_lift_plan)
+
+    # ---- bootstrap of the sampled attribution (p <= 127) -------------------------------------------
+    BOOT_LIFT_MAX_P = 127
+
+    def boot_lift_load(self, X_train, X_test, y_train, y_test, reg: float):
+        """Keep [X | y] of both sides on the device for boot_lift_run (include/lsspa.h, lsspa_boot_lift_load); the loaded
+        problem and the state of boot_load, cv_lift_load and multi_lift_load are not touched."""
+        dt = np.float32 if (X_train.dtype == np.float32 and X_test.dtype == np.float32) else np.float64
+        Xa, Xe = np.ascontiguousarray(X_train, dtype=dt), np.ascontiguousarray(X_test, dtype=dt)
+        ya, ye = np.ascontiguousarray(y_train, dtype=dt), np.ascontiguousarray(y_test, dtype=dt)
+        n, p = Xa.shape
+        self._check(self._lib.lsspa_boot_lift_load(
+            self._h, C.c_void_p(Xa.ctypes.data), int(p), C.c_void_p(ya.ctypes.data), int(n), C.c_void_p(Xe.ctypes.data),
+            int(p), C.c_void_p(ye.ctypes.data), int(Xe.shape[0]), int(p), float(reg),
+            N.F32 if dt == np.float32 else N.F64, N.HOST))
+        self._boot_lift_dims, self._boot_lift_g, self._boot_lift_n = (int(p), int(n), int(Xe.shape[0])), 0, 0
+
+    def boot_lift_set_players(self, labels, g=None):
+        """Groups of columns as the players, as cv_lift_set_players names them (include/lsspa.h,
+        lsspa_boot_lift_set_players); drops the orderings.  The library checks the labels."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        g = int(labels.max()) + 1 if g is None else int(g)
+        self._check(self._lib.lsspa_boot_lift_set_players(self._h, N.iptr(labels), g))
+        self._boot_lift_g, self._boot_lift_n = g, 0
+
+    def boot_lift_clear_players(self):
+        self._check(self._lib.lsspa_boot_lift_set_players(self._h, None, 0))
+        self._boot_lift_g, self._boot_lift_n = 0, 0
+
+    def _boot_lift_sd(self):
+        """(dimension of a sample: g with a player map, else p; samples of the orderings set)"""
+        p = (getattr(self, "_boot_lift_dims", None) or (1, 0, 0))[0]
+        return (getattr(self, "_boot_lift_g", 0) or p), getattr(self, "_boot_lift_n", 0)
+
+    def boot_lift_set_orderings(self, perms, antithetical: bool):
+        """The one set of orderings every replicate and the point problem run through: perms [n_samples][d] (with
+        antithetical a sample is an ordering and its reverse).  The library checks the orderings."""
+        d, _ = self._boot_lift_sd()
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        if getattr(self, "_boot_lift_dims", None) is not None and (perms.ndim != 2 or perms.shape[1] != d):
+            raise ValueError(f"perms must be [n_samples][{'g' if getattr(self, '_boot_lift_g', 0) else 'p'} = {d}]")
+        B = perms.shape[0] if perms.ndim == 2 else 0
+        self._check(self._lib.lsspa_boot_lift_set_orderings(self._h, N.iptr(perms) if perms.size else None, B,
+                                                            int(bool(antithetical))))
+        self._boot_lift_n = B
+
+    def _boot_lift_weights(self, w, shape, side):
+        if w is None:
+            return None
+        dims = getattr(self, "_boot_lift_dims", None)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        want = tuple(shape) + (dims[1 + side],) if dims is not None else w.shape
+        if w.shape != want:
+            raise ValueError(f"weights of the {('training', 'test')[side]} side must have shape {want}, got {w.shape}")
+        return w
+
+    def boot_lift_run(self, R: int, seed: int, w_train=None, w_test=None, block: int = 0, first: int = 0,
+                      want_samples: bool = False):
+        """(mean [R][d], m2 [R][d], r2 [R], r2_base [R], info [R]) of replicates first .. first + R - 1 over the orderings
+        set (include/lsspa.h, lsspa_boot_lift_run); with want_samples a sixth array [R][n_samples][d] of every sample's
+        entry.  A replicate's mean sums to r2 - r2_base."""
+        d, ns = self._boot_lift_sd()
+        wa, we = self._boot_lift_weights(w_train, (R,), 0), self._boot_lift_weights(w_test, (R,), 1)
+        mean, m2, r2, base = np.empty((R, d)), np.empty((R, d)), np.empty(R), np.empty(R)
+        info = np.zeros(R, dtype=np.int32)
+        samples = np.empty((R, ns, d)) if want_samples else None
+        self._check(self._lib.lsspa_boot_lift_run(self._h, int(R), int(seed) & (2 ** 64 - 1), int(first), N.dptr(wa),
+                                                  N.dptr(we), int(block), N.dptr(mean), N.dptr(m2), N.dptr(r2),
+                                                  N.dptr(base), N.iptr(info), N.dptr(samples)))
+        return (mean, m2, r2, base, info, samples) if want_samples else (mean, m2, r2, base, info)
+
+    def boot_lift_point(self, want_samples: bool = False):
+        """(mean [d], m2 [d], r2, r2_base, info) of the original rows, weight 1 on every row, through the same path as one
+        more problem (include/lsspa.h, lsspa_boot_lift_point); with want_samples a sixth array [n_samples][d]."""
+        d, ns = self._boot_lift_sd()
+        mean, m2, r2, base = np.empty(d), np.empty(d), C.c_double(), C.c_double()
+        info = np.zeros(1, dtype=np.int32)
+        samples = np.empty((ns, d)) if want_samples else None
+        self._check(self._lib.lsspa_boot_lift_point(self._h, N.dptr(mean), N.dptr(m2), C.byref(r2), C.byref(base),
+                                                    N.iptr(info), N.dptr(samples)))
+        out = (mean, m2, r2.value, base.value, int(info[0]))
+        return out + (samples,) if want_samples else out
+
+    def boot_lift_problem(self, r: int, seed: int = 0, w_train=None, w_test=None):
+        """(G, g, H, h, inv_yy) of replicate r as the device writes it in a run: the counts of (seed, r, side), or the
+        weights w_train [n] / w_test [m] of that replicate; r < 0: the point problem."""
+        p = (getattr(self, "_boot_lift_dims", None) or (1, 0, 0))[0]
+        wa, we = self._boot_lift_weights(w_train, (), 0), self._boot_lift_weights(w_test, (), 1)
+        G, g, H, h, yy = np.empty((p, p)), np.empty(p), np.empty((p, p)), np.empty(p), C.c_double()
+        self._check(self._lib.lsspa_boot_lift_get_problem(self._h, int(r), int(seed) & (2 ** 64 - 1), N.dptr(wa),
+                                                          N.dptr(we), N.dptr(G), N.dptr(g), N.dptr(H), N.dptr(h),
+                                                          C.byref(yy)))
+        return G, g, H, h, yy.value
+
+    def boot_lift_debug_grams(self, R: int, w_train=None, w_test=None):
+        """(S_train, S_test [R][p+1][p+1], wsum [R]): the weighted sums before finalise (None: weight 1 on that side)."""
+        c = self._boot_lift_dims[0] + 1
+        wa, we = self._boot_lift_weights(w_train, (R,), 0), self._boot_lift_weights(w_test, (R,), 1)
+        Sa, Se, ws = np.empty((R, c, c)), np.empty((R, c, c)), np.empty(R)
+        self._check(self._lib.lsspa_boot_lift_debug_grams(self._h, int(R), N.dptr(wa), N.dptr(we), N.dptr(Sa), N.dptr(Se),
+                                                          N.dptr(ws)))
+        return Sa, Se, ws
+
+    def boot_lift_timing(self):
+        """Device seconds of the last pass: counts, Gram side, lift launches, statistics launches; and `launches`, the
+        number of lift launches."""
+        a, b, c, d, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._check(self._lib.lsspa_boot_lift_timing(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(n)))
+        return {"counts": a.value / 1e3, "gram": b.value / 1e3, "lift": c.value / 1e3, "stats": d.value / 1e3,
+                "launches": n.value}
+
+    def boot_lift_free(self):
+        self._check(self._lib.lsspa_boot_lift_free(self._h))
+        self._boot_lift_dims, self._boot_lift_g, self._boot_lift_n = None, 0, 0
+
+    debug_boot_lift_plan = staticmethod(debug_boot_lift_plan)
 
     def _exact_timing(self, getter):
         ms, mx, n = C.c_double(), C.c_double(), C.c_int64()

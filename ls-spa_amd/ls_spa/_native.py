@@ -210,6 +210,16 @@ SIGNATURES = {
     "lsspa_cv_lift_timing": (C.c_int, [_vp, _pd, _pd, _pd]),
     "lsspa_cv_lift_free": (C.c_int, [_vp]),
     "lsspa_debug_cv_lift_plan": (C.c_int, [_i32, _i32, _i32, _i64, _i32, _pi64]),
+    "lsspa_boot_lift_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _dbl, _i32, _i32]),
+    "lsspa_boot_lift_set_players": (C.c_int, [_vp, _pi32, _i32]),
+    "lsspa_boot_lift_set_orderings": (C.c_int, [_vp, _pi32, _i64, _i32]),
+    "lsspa_boot_lift_run": (C.c_int, [_vp, _i64, C.c_uint64, _i64, _pd, _pd, _i64, _pd, _pd, _pd, _pd, _pi32, _pd]),
+    "lsspa_boot_lift_point": (C.c_int, [_vp, _pd, _pd, _pd, _pd, _pi32, _pd]),
+    "lsspa_boot_lift_get_problem": (C.c_int, [_vp, _i64, C.c_uint64, _pd, _pd, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_boot_lift_debug_grams": (C.c_int, [_vp, _i64, _pd, _pd, _pd, _pd, _pd]),
+    "lsspa_boot_lift_timing": (C.c_int, [_vp, _pd, _pd, _pd, _pd, _pi64]),
+    "lsspa_boot_lift_free": (C.c_int, [_vp]),
+    "lsspa_debug_boot_lift_plan": (C.c_int, [_i64, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _pi64]),
     "lsspa_perm_load": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _dbl, _i32, _i32]),
     "lsspa_perm_run": (C.c_int, [_vp, _pi32, _i32, _i64, C.c_uint64, _i64, _i32, _i64, _pd, _pd, _pd, _pi32]),
     "lsspa_perm_observed": (C.c_int, [_vp, _pi32, _i32, _pd, _pi32]),

@@ -662,6 +662,66 @@ class BootstrapResults:
 
 
 @dataclass
+class SampledBootstrapResults:
+    """What ``ls_spa_bootstrap_sampled`` returns.  ``attribution`` [d] and ``attribution_errors`` [d]: the point estimate
+    on the original rows -- the mean of the ``n_samples`` lift vectors -- and its Monte-Carlo standard error
+    sqrt(M2 / (n (n - 1))).  ``replicates`` [n_boot][d] and ``replicate_errors`` [n_boot][d]: each bootstrap replicate's
+    mean lift over the SAME samples and its Monte-Carlo standard error; since the orderings are shared, their error
+    moves all replicates together instead of widening their spread.  A replicate whose Gram matrix was not numerically
+    positive definite in some ordering is NaN in ``replicates``, ``replicate_errors`` and ``r_squared_replicates`` and
+    counted in ``n_failed``.  ``std_error``, ``lower``, ``upper``, ``prob_greater`` [d][d], ``r_squared_interval``:
+    computed from ``replicates`` exactly as ``BootstrapResults`` computes them.  ``theta`` [p] and ``r_squared`` are the
+    fit on the original rows."""
+    attribution: np.ndarray
+    attribution_errors: np.ndarray
+    theta: np.ndarray
+    r_squared: float
+    replicates: np.ndarray
+    replicate_errors: np.ndarray
+    r_squared_replicates: np.ndarray
+    std_error: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    r_squared_interval: tuple
+    prob_greater: np.ndarray
+    n_samples: int
+    n_failed: int
+    confidence: float = 0.95
+
+    def _lines(self, what):
+        pad = " " * 8
+        return [
+            "",
+            f"{pad}{what}, {len(self.replicates)} bootstrap replicates"
+            + (f" ({self.n_failed} failed)" if self.n_failed else "") + f", {self.n_samples} shared samples",
+            f"{pad}Out-of-sample R^2 with all features: {self.r_squared:.2f}"
+            f" [{self.r_squared_interval[0]:.2f}, {self.r_squared_interval[1]:.2f}]",
+            "",
+            f"{pad}Shapley attribution: {_head(self.attribution)}",
+            f"{pad}Largest Monte-Carlo standard error: {float(np.max(self.attribution_errors)):.3g}",
+            f"{pad}{100 * self.confidence:g} % interval, lower: {_head(self.lower)}",
+            f"{pad}{100 * self.confidence:g} % interval, upper: {_head(self.upper)}",
+            pad,
+        ]
+
+    def __repr__(self):
+        return "\n".join(self._lines(f"p = {np.asarray(self.attribution).size}"))
+
+
+@dataclass
+class SampledBootstrapGroupResults(SampledBootstrapResults):
+    """What ``ls_spa_bootstrap_sampled(groups=)`` returns: ``SampledBootstrapResults`` over the g groups, with
+    ``baseline_r_squared``, the R^2 of the baseline's columns alone on the original rows (0 without a baseline), and
+    ``baseline_r_squared_replicates`` [n_boot].  ``attribution`` sums to ``r_squared - baseline_r_squared`` and a
+    replicate to its R^2 minus its baseline's; ``theta`` keeps length p."""
+    baseline_r_squared: float = 0.0
+    baseline_r_squared_replicates: np.ndarray | None = None
+
+    def __repr__(self):
+        return "\n".join(self._lines(f"g = {np.asarray(self.attribution).size} groups, p = {len(self.theta)}"))
+
+
+@dataclass
 class InteractionBootstrapResults:
     """What ``ls_spa_interactions_bootstrap`` returns.  ``interactions`` [d][d], ``attribution``, ``theta`` and
     ``r_squared`` are the point estimate on the original rows, exactly those of ``ls_spa_interactions``; d is p, or g with

@@ -11,6 +11,8 @@
 // boot_plan's Gram side and units, 16 bytes a table entry in rep_bytes, per within the kernel's size classes; and its
 // grouped sibling (boot_groups_best_plan) on the grouped sweep: boot_groups_plan's Gram side, units and per, 16 bytes an
 // entry, units * enum_reps <= 2^20 workgroups, and the work bound unless one step of one replicate is already more.
+// The sampled bootstrap's planner (boot_lift_plan) up to p = 127: boot_plan's slices, the Gram and lift kernel forms at
+// their column-block edges, lift launches within their grid and raw-lift bounds, a sample cut that is not R's or the block's.
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
@@ -188,6 +190,54 @@ int main() {
     // the table does not cut a block to a handful of replicates at large p
     R = 1000; N = M = 10000; block = 0; p = 32;
     CHECK(boot_inter_plan(R, N, M, p, block, P) == nullptr && P.enum_reps == 1 && P.block >= 100);
+  }
+  // The sampled bootstrap's planner (boot_lift_plan): every p up to 127, samples at the launch cut's edges, both pair
+  // settings.  The Gram side is boot_plan's for the same rows; the sample cut is a function of n_samples and the pair
+  // setting alone; a lift launch stays within its grid and raw-lift bounds whatever R and block are.
+  {
+    const int64_t rows_l[] = {1, 257, 100000, (1ll << 31) - 1};
+    const int64_t samples[] = {1, 2, 127, 128, 129, 256, 257, 1024, 1ll << 30};
+    for (int64_t R : reps)
+      for (int64_t N : rows_l)
+        for (int64_t M : rows_l)
+          for (int p = 1; p <= BOOT_LIFT_MAX_P; ++p)
+            for (int64_t block : blocks)
+              for (int64_t ns : samples)
+                for (int anti = 0; anti < 2; ++anti) {
+                  const int d = p > 3 ? p / 3 : p;
+                  BootLiftPlan L, L1;
+                  CHECK(boot_lift_plan(R, N, M, p, anti ? d : p, ns, anti, block, L) == nullptr);
+                  CHECK(L.cb == (p + 16) / 16 && L.cb <= 8 && L.ldz == 16 * L.cb && L.pairs == L.cb * (L.cb + 1) / 2);
+                  CHECK(L.gram_form == (L.cb >= 6) && L.lift_form == (L.cb == 8));
+                  CHECK(L.rpw == (L.cb <= 2 ? 4 : L.cb == 3 ? 2 : 1));
+                  BootPlan Q;
+                  CHECK(boot_plan(R, N, M, 1, block, Q) == nullptr);
+                  for (int s = 0; s < 2; ++s) CHECK(L.rps[s] == Q.rps[s] && L.slices[s] == Q.slices[s]);
+                  CHECK(L.block >= 1 && L.block <= R && L.block <= BOOT_MAX_BLOCK && (block == 0 || L.block <= block));
+                  CHECK(L.n_blocks >= 1 && (L.n_blocks - 1) * L.block < R && L.n_blocks * L.block >= R);
+                  CHECK(L.block == 1 || L.block * L.rep_bytes <= BOOT_BLOCK_BYTES);
+                  const int64_t per = anti ? 2 : 1;
+                  CHECK(L.samples_per_launch >= 1 && L.samples_per_launch <= ns && L.ord_per_launch == per * L.samples_per_launch);
+                  CHECK(L.ord_per_launch <= BOOT_LIFT_ORD && L.sample_cuts * L.samples_per_launch >= ns &&
+                        (L.sample_cuts - 1) * L.samples_per_launch < ns);
+                  CHECK(L.reps_per_launch >= 1 &&
+                        L.ord_per_launch * L.reps_per_launch <= (L.lift_form ? BOOT_LIFT_GRID_LDS : BOOT_LIFT_GRID_REG));
+                  CHECK(L.ord_per_launch * L.reps_per_launch * p * 8 <= BOOT_LIFT_RAW_BYTES && L.raw_bytes <= BOOT_LIFT_RAW_BYTES);
+                  CHECK(L.launches == INT64_MAX || L.launches / L.sample_cuts >= L.n_blocks);   // (it saturates)
+                  // the cut is not R's, the block's or the rows'
+                  CHECK(boot_lift_plan(1, 1, 1, p, anti ? d : p, ns, anti, 0, L1) == nullptr);
+                  CHECK(L1.samples_per_launch == L.samples_per_launch && L1.reps_per_launch == L.reps_per_launch &&
+                        L1.sample_cuts == L.sample_cuts);
+                  ++n_ok;
+                }
+    BootLiftPlan L;
+    if (!(boot_lift_plan(1, 1, 1, 128, 1, 1, 0, 0, L) && boot_lift_plan(1, 1, 1, 0, 1, 1, 0, 0, L) &&
+          boot_lift_plan(1, 1, 1, 4, 5, 1, 0, 0, L) && boot_lift_plan(1, 1, 1, 4, 0, 1, 0, 0, L) &&
+          boot_lift_plan(1, 1, 1, 4, 4, 0, 0, 0, L) && boot_lift_plan(0, 1, 1, 4, 4, 1, 0, 0, L) &&
+          boot_lift_plan(1, 1, 1ll << 31, 4, 4, 1, 0, 0, L) && boot_lift_plan(1, 1, 1, 4, 4, 1, 0, -1, L))) {
+      std::fprintf(stderr, "FAILED: boot_lift_plan accepted a bad argument\n");
+      return 1;
+    }
   }
   BootPlan P;
   const bool refused = boot_plan(0, 1, 1, 1, 0, P) && boot_plan(1, 0, 1, 1, 0, P) && boot_plan(1, 1, 1ll << 31, 1, 0, P) &&
