@@ -8,6 +8,7 @@
 // entry is out of range and the set is full (p entries, p distinct values).  Anything else takes the stamp loop.
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <vector>
 
 #include "players.h"
@@ -114,6 +115,52 @@ void expand_group_row(const PlayerMap& m, const int32_t* gperm, int reversed, in
     const int k = gperm[reversed ? m.g - 1 - i : i];
     for (int c = m.off[k]; c < m.off[(size_t)k + 1]; ++c) *w++ = m.cols[c];
   }
+}
+
+// ---- the sampled families' orderings and fold labels (lsspa_multi_lift_*, lsspa_cv_lift_*, lsspa_boot_lift_*) --------
+// One check, one stager and one fold count for the entry points that take them; no HIP call (tools/lift_host_check.cpp
+// runs them under the host sanitisers).
+const char* lift_orderings_why(const char* entry, const char* count_name, const int32_t* perms, int64_t count, int p, int g,
+                               int d, int limit_rows, std::vector<int32_t>& mark, char* msg, size_t len) {
+  if (!perms || count < 1 || count > (int64_t)INT32_MAX / (limit_rows * p)) {
+    snprintf(msg, len, "%s: perms is NULL, %s < 1 or %s%s p >= 2^31", entry, count_name, limit_rows == 2 ? "2 " : "",
+             count_name);
+    return msg;
+  }
+  if (!all_permutations(perms, (int)count, d, mark)) {
+    snprintf(msg, len, g ? "%s: a row of perms is not a permutation of 0 .. g-1 (a player map is set: the orderings are "
+                           "orderings of the groups)"
+                         : "%s: a row of perms is not a permutation of 0 .. p-1", entry);
+    return msg;
+  }
+  return nullptr;
+}
+
+const int32_t* lift_stage_rows(const PlayerMap& m, int g, const int32_t* perms, int64_t s0, int64_t ns, int per, int p,
+                               std::vector<int32_t>& rows) {
+  if (!g) return perms + s0 * p;
+  // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
+  if (rows.size() < (size_t)(ns * per * p)) rows.resize((size_t)(ns * per * p));
+  for (int64_t s = 0; s < ns; ++s)
+    for (int r = 0; r < per; ++r) expand_group_row(m, perms + (s0 + s) * g, r, rows.data() + (size_t)((s * per + r) * p));
+  return rows.data();
+}
+
+const char* cv_count_folds(const int32_t* fold_ids, int64_t N, int K, int32_t* nf, char* msg, size_t len) {
+  for (int f = 0; f < K; ++f) nf[f] = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    if (fold_ids[i] < 0 || fold_ids[i] >= K) {
+      snprintf(msg, len, "fold_ids[%lld] = %d: fold labels must be 0 .. %d (K - 1)", (long long)i, (int)fold_ids[i], K - 1);
+      return msg;
+    }
+    ++nf[fold_ids[i]];
+  }
+  for (int f = 0; f < K; ++f)
+    if (nf[f] == 0) {
+      snprintf(msg, len, "fold %d of %d is empty: every fold needs at least one row", f, K);
+      return msg;
+    }
+  return nullptr;
 }
 
 // ---- sampled pairwise interactions (lsspa_pairs_batch) --------------------------------------------------------------

@@ -166,77 +166,97 @@ struct MultiWork {
   }
 };
 
-// What the sampled attribution of many responses keeps (lsspa_multi_lift_load / lsspa_multi_lift_set_reduced ..
-// lsspa_multi_lift_free): the shared G and H, one g, h and ||y||^2 per response, the orderings and lift vectors of one
-// launch, the running (n, mean, M2) per (response, feature) and the last calls' timing.  Nothing of the loaded problem,
-// the sampling path's statistics, the enumerations, the bootstrap or lsspa_multi_* is in here.  With a player map
-// (lsspa_multi_lift_set_players: ng != 0, its own map, not ctx->players) a sample is g group lifts a response: the lift
-// vectors and the first m g entries of (mean, M2) are [m][g], and perms holds the expanded rows of a launch.
-struct MultiLiftWork {
-  bool loaded = false;
-  ReducedForm rf;
+// What the three sampled families (lsspa_multi_lift_*, lsspa_cv_lift_*, lsspa_boot_lift_*) each keep one of ------------
+// A family's own player map (lift_players_set; not ctx->players): ng != 0 makes a sample g group lifts, and the
+// orderings given are orderings of the groups, expanded on the host as they are staged (lift_stage_rows).
+struct LiftPlayers {
   int ng = 0;                              // groups of the player map (0: none)
   PlayerMap map;
   DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
   std::vector<int32_t> rows;               // a launch's expanded rows on the host
-  int sd() const { return ng ? ng : rf.p; }     // the dimension of a sample's lift vector
-  double aug[2] = {1.0, 1.0};              // diagonal of the augmented rows (MultiLiftArgs::aug)
-  DevBuf<double> yy;                       // [m]
-  DevBuf<double> lifts, mean, M2;          // [samples of a launch][m][p]; the running state [m][p]
-  DevBuf<int32_t> perms, info;             // [samples of a launch][p]; the info word
-  int64_t n = 0;                           // samples folded into (mean, M2)
-  double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
+  int sd(int p) const { return ng ? ng : p; }                   // the dimension of a sample
+  int64_t rows_per(int per) const { return ng ? per : 1; }      // rows of perms a sample takes on the device
+  const int32_t* off() const { return ng ? pl_off.ptr : nullptr; }
+  const int32_t* cols() const { return ng ? pl_cols.ptr : nullptr; }
   void release() {
-    rf.release(); dev_free(yy); dev_free(lifts); dev_free(mean); dev_free(M2);
-    dev_free(perms); dev_free(info); dev_free(pl_off); dev_free(pl_cols);
-    loaded = false;
-    n = 0;
+    dev_free(pl_off); dev_free(pl_cols);
     ng = 0;
   }
 };
 
-// What the sampled K-fold CV attribution keeps (lsspa_cv_lift_load .. lsspa_cv_lift_free): the K fold problems at the
-// one stride the fold launch reads (rows of CV_LIFT_LD doubles; G, g, H, h and the pooled 1 / ||y||^2 also on the host,
-// dense), the augmented rows' diagonals, the orderings, raw lifts and samples of one launch, the running (n, mean, M2)
-// [K + 1][d] and the last calls' timing.  Nothing of the loaded problem, lsspa_cv_*, lsspa_multi_lift_* or any other
-// store is in here.  The player map is its own (lsspa_cv_lift_set_players).
+// The running (n, mean, M2) of a family's samples, `entries` doubles each (lift_stats_*).
+struct LiftStats {
+  int64_t n = 0;                           // samples folded into (mean, M2)
+  DevBuf<double> mean, M2;
+  void release() {
+    dev_free(mean); dev_free(M2);
+    n = 0;
+  }
+};
+
+// Problems kept at the ordering kernels' stride: G, H [count][LD][LD] and g, h [count][LD] in rows of LD = CV_LIFT_LD
+// doubles, the pooled 1 / ||y||^2 [count] and the augmented rows' diagonals [count][2] (lift_problems_*).
+struct LiftProblems {
+  static constexpr int64_t LD = CV_LIFT_LD, LL = LD * LD;
+  DevBuf<double> G, g, H, h, inv_yy, aug;
+  void release() { dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(aug); }
+};
+static_assert(BOOT_LIFT_LD == CV_LIFT_LD && BOOT_LIFT_MAX_P == CV_LIFT_MAX_P,
+              "the sampled bootstrap keeps its problems at the fold launch's stride");
+
+// What the sampled attribution of many responses keeps (lsspa_multi_lift_load / lsspa_multi_lift_set_reduced ..
+// lsspa_multi_lift_free): the reduced form, the orderings and lift vectors [samples][m][d] of one launch, the running
+// statistics [m][d] and the last calls' timing.  Nothing of the loaded problem, the sampling path's statistics, the
+// enumerations, the bootstrap or lsspa_multi_* is in here.
+struct MultiLiftWork {
+  bool loaded = false;
+  ReducedForm rf;
+  LiftPlayers pl;
+  LiftStats st;                            // [m][p] allocated, the first m d entries used
+  int sd() const { return pl.sd(rf.p); }
+  double aug[2] = {1.0, 1.0};              // diagonal of the augmented rows (MultiLiftArgs::aug)
+  DevBuf<double> yy;                       // [m]
+  DevBuf<double> lifts;                    // [samples of a launch][m][d]
+  DevBuf<int32_t> perms, info;             // [samples of a launch][p]; the info word
+  double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
+  void release() {
+    rf.release(); pl.release(); st.release(); dev_free(yy); dev_free(lifts); dev_free(perms); dev_free(info);
+    loaded = false;
+  }
+};
+
+// What the sampled K-fold CV attribution keeps (lsspa_cv_lift_load .. lsspa_cv_lift_free): the K fold problems (dense
+// on the host too), the orderings, raw lifts and samples of one launch, the running statistics [K + 1][d] and the last
+// calls' timing.  Nothing of the loaded problem, lsspa_cv_*, lsspa_multi_lift_* or any other store is in here.
 struct CvLiftWork {
   bool loaded = false;
   int p = 0, K = 0;
-  int ng = 0;                              // groups of the player map (0: none)
-  PlayerMap map;
-  DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
-  std::vector<int32_t> rows;               // a launch's expanded rows on the host
-  int sd() const { return ng ? ng : p; }   // the dimension of a sample
-  DevBuf<double> G, g, H, h, inv_yy, aug;  // [K][LD][LD], [K][LD], .., [K], [K][2]
+  LiftPlayers pl;
+  LiftStats st;                            // [K + 1][p] allocated, the first (K + 1) d entries used
+  LiftProblems pr;                         // [K] (inv_yy, aug: CV_MAX_FOLDS)
+  int sd() const { return pl.sd(p); }
   std::vector<double> Gh, gh, Hh, hh, yh;  // [K][p][p], [K][p], .., [K] on the host
-  DevBuf<double> raw, batch, mean, M2;     // [orderings of a launch][K][p]; [samples of a launch][K + 1][d]; the state
+  DevBuf<double> raw, batch;               // [orderings of a launch][K][p]; [samples of a launch][K + 1][d]
   DevBuf<int32_t> perms, info;             // a launch's rows; [K] info words
-  int64_t n = 0;                           // samples folded into (mean, M2)
   double gram_ms = 0.0, batch_ms = 0.0, stats_ms = 0.0;
   void release() {
-    dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(aug); dev_free(raw);
-    dev_free(batch); dev_free(mean); dev_free(M2); dev_free(perms); dev_free(info); dev_free(pl_off); dev_free(pl_cols);
+    pl.release(); st.release(); pr.release(); dev_free(raw); dev_free(batch); dev_free(perms); dev_free(info);
     loaded = false;
-    n = 0;
-    ng = 0;
   }
 };
 
 // What the bootstrap of the sampled attribution keeps (lsspa_boot_lift_load .. lsspa_boot_lift_free): the rows of both
-// sides, the player map and the one set of orderings every replicate shares, and the buffers of one block of replicates
-// -- weights, Gram partials and sums, the problems at the ordering kernels' stride (rows of BOOT_LIFT_LD doubles), one
-// launch's raw lifts, the running (mean, M2) [block][d].  Nothing of the loaded problem, lsspa_boot_*, lsspa_cv_lift_*,
-// lsspa_multi_lift_* or any other store is in here.
+// sides, the one set of orderings every replicate shares, and the buffers of one block of replicates -- weights, Gram
+// partials and sums, the block's problems, one launch's raw lifts, the replicates' running (mean, M2) [block][d].
+// Nothing of the loaded problem, lsspa_boot_*, lsspa_cv_lift_*, lsspa_multi_lift_* or any other store is in here.
 struct BootLiftWork {
   bool loaded = false;
   int p = 0;
   int64_t n[2] = {0, 0};                   // rows: train, test
   double reg = 0.0;
-  int ng = 0;                              // groups of the player map (0: none)
-  PlayerMap map;
-  DevBuf<int32_t> pl_off, pl_cols;         // the map's CSR on the device
-  int sd() const { return ng ? ng : p; }   // the dimension of a sample
+  LiftPlayers pl;
+  LiftProblems pr;                         // [block]
+  int sd() const { return pl.sd(p); }
   int64_t n_samples = 0;                   // samples of the orderings set (0: none)
   int per = 1;                             // orderings a sample (2: antithetical)
   DevBuf<int32_t> perms;                   // the orderings' rows, expanded
@@ -245,7 +265,6 @@ struct BootLiftWork {
   DevBuf<uint32_t> cnt0, cnt1;             // [block][n] bootstrap counts
   DevBuf<double> wt0, wt1;                 // [block][n] caller's weights
   DevBuf<double> part0, part1, S0, S1, wsum;
-  DevBuf<double> G, g, H, h, inv_yy, aug;  // [block][LD][LD], [block][LD], .., [block], [block][2]
   DevBuf<double> raw, mean, M2, samples;   // one launch's raw lifts; [block][d] twice; one launch's samples (test hook)
   DevBuf<int32_t> info;                    // [block]
   double ms[4] = {0.0, 0.0, 0.0, 0.0};     // kernel ms of the last pass: counts, Gram (to the problems), lifts, statistics
@@ -258,10 +277,9 @@ struct BootLiftWork {
   void release() {
     dev_free(Z0); dev_free(Z1); dev_free(stage_x); dev_free(stage_y); dev_free(cnt0); dev_free(cnt1);
     dev_free(wt0); dev_free(wt1); dev_free(part0); dev_free(part1); dev_free(S0); dev_free(S1); dev_free(wsum);
-    dev_free(G); dev_free(g); dev_free(H); dev_free(h); dev_free(inv_yy); dev_free(aug); dev_free(raw);
-    dev_free(mean); dev_free(M2); dev_free(samples); dev_free(info); dev_free(perms); dev_free(pl_off); dev_free(pl_cols);
+    pl.release(); pr.release(); dev_free(raw); dev_free(mean); dev_free(M2); dev_free(samples); dev_free(info);
+    dev_free(perms);
     loaded = false;
-    ng = 0;
     n_samples = 0;
   }
 };
@@ -503,6 +521,31 @@ int dev_alloc(lsspa_ctx* ctx, DevBuf<T>& b, size_t count) {
     int rc_ = (expr);                 \
     if (rc_ != LSSPA_OK) return rc_;  \
   } while (0)
+
+// A player map from labels (NULL: no map) into map / off / cols / ng, for lsspa_set_players and the sampled families'
+// own maps: the refusals (null_msg: the entry point's, for NULL labels with g != 0), then quiesce() -- the caller's wait
+// for work that may still read the tables, and whatever it resets with it -- then the allocations and the upload.
+template <typename Quiesce>
+int player_map_set(lsspa_ctx* ctx, const char* null_msg, const int32_t* labels, int p, int g, Quiesce&& quiesce,
+                   PlayerMap& map, DevBuf<int32_t>& off, DevBuf<int32_t>& cols, int& ng) {
+  if (!labels && g != 0) return ctx->fail(LSSPA_ERR_ARG, null_msg);
+  PlayerMap built;
+  if (labels)
+    if (const char* why = player_map_build(labels, p, g, built)) return ctx->fail(LSSPA_ERR_ARG, why);
+  TRY(quiesce());
+  if (!labels) {
+    ng = 0;
+    return LSSPA_OK;
+  }
+  TRY(dev_alloc(ctx, off, (size_t)p + 1));
+  TRY(dev_alloc(ctx, cols, (size_t)p));
+  HIPCHK(hipMemcpy(off.ptr, built.off.data(), sizeof(int32_t) * built.off.size(), hipMemcpyHostToDevice));
+  if (!built.cols.empty())     // (every column in the baseline cannot be: g >= 1 groups own one each; kept as a guard)
+    HIPCHK(hipMemcpy(cols.ptr, built.cols.data(), sizeof(int32_t) * built.cols.size(), hipMemcpyHostToDevice));
+  map = std::move(built);
+  ng = g;
+  return LSSPA_OK;
+}
 
 inline int round_up(int x, int q) { return ((x + q - 1) / q) * q; }
 
@@ -2140,23 +2183,8 @@ int lsspa_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) try {
   HIPCHK(hipSetDevice(ctx->device));
   for (const Lane& L : ctx->lanes)
     if (L.in_flight) return ctx->fail(LSSPA_ERR_STATE, "a launched batch is still to be collected");
-  if (!labels && g != 0) return ctx->fail(LSSPA_ERR_ARG, "labels is NULL (clear the map with labels = NULL, g = 0)");
-  PlayerMap map;
-  if (labels) {
-    const char* why = player_map_build(labels, ctx->p, g, map);
-    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
-  }
-  TRY(sync_all(ctx));
-  if (labels) {
-    TRY(dev_alloc(ctx, ctx->pl_off, (size_t)ctx->p + 1));
-    TRY(dev_alloc(ctx, ctx->pl_cols, (size_t)ctx->p));
-    HIPCHK(hipMemcpy(ctx->pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
-    ctx->players = std::move(map);
-    ctx->g_players = g;
-  } else {
-    ctx->g_players = 0;
-  }
+  TRY(player_map_set(ctx, "labels is NULL (clear the map with labels = NULL, g = 0)", labels, ctx->p, g,
+                     [&] { return sync_all(ctx); }, ctx->players, ctx->pl_off, ctx->pl_cols, ctx->g_players));
   ctx->pairs_on = false;   // the pair state has the dimension it was enabled at
   ctx->hist_cap = 0;
   ctx->hist_n = 0;
@@ -5205,6 +5233,14 @@ int cv_fold_backfill(Values&& values, const uint32_t* masks, size_t n, Listed&& 
   return LSSPA_OK;
 }
 
+// y [n] (host memory, dtype LSSPA_F64 / LSSPA_F32) has no entry that is not zero
+bool host_all_zero(const void* y, int64_t n, int32_t dtype) {
+  bool any = false;
+  for (int64_t i = 0; i < n && !any; ++i)
+    any = dtype == LSSPA_F32 ? ((const float*)y)[i] != 0.f : ((const double*)y)[i] != 0.0;
+  return !any;
+}
+
 // max_p: SUBSETS_MAX_P (lsspa_cv_load) or GROUPS_MAX_P (lsspa_cv_groups_load); `name` is the entry point's
 int cv_load(lsspa_ctx* ctx, const char* name, int max_p, const void* X, int64_t ld, const void* y, int64_t N, int32_t p,
             const int32_t* fold_ids, int32_t K, double reg, int32_t dtype, int32_t location) {
@@ -5230,25 +5266,10 @@ int cv_load(lsspa_ctx* ctx, const char* name, int max_p, const void* X, int64_t 
     return ctx->fail(LSSPA_ERR_ARG, msg);
   }
   int32_t nf[CV_MAX_FOLDS] = {0};
-  for (int64_t i = 0; i < N; ++i) {
-    if (fold_ids[i] < 0 || fold_ids[i] >= K) {
-      snprintf(msg, sizeof msg, "fold_ids[%lld] = %d: fold labels must be 0 .. %d (K - 1)", (long long)i,
-               (int)fold_ids[i], (int)K - 1);
-      return ctx->fail(LSSPA_ERR_ARG, msg);
-    }
-    ++nf[fold_ids[i]];
-  }
-  for (int f = 0; f < K; ++f)
-    if (nf[f] == 0) {
-      snprintf(msg, sizeof msg, "fold %d of %d is empty: every fold needs at least one row", f, (int)K);
-      return ctx->fail(LSSPA_ERR_ARG, msg);
-    }
-  if (location == LSSPA_HOST) {          // (rows on the device: the pooled sum is looked at after the Gram pass)
-    bool any = false;
-    for (int64_t i = 0; i < N && !any; ++i)
-      any = dtype == LSSPA_F32 ? ((const float*)y)[i] != 0.f : ((const double*)y)[i] != 0.0;
-    if (!any) return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
-  }
+  if (cv_count_folds(fold_ids, N, K, nf, msg, sizeof msg)) return ctx->fail(LSSPA_ERR_ARG, msg);
+  // (rows on the device: the pooled sum is looked at after the Gram pass)
+  if (location == LSSPA_HOST && host_all_zero(y, N, dtype))
+    return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
   HIPCHK(hipSetDevice(ctx->device));
   CvWork& W = ctx->cv;
   W.loaded = false;
@@ -6564,6 +6585,146 @@ int lsspa_debug_multi_group_values(lsspa_ctx* ctx, const int32_t* labels, int32_
 
 }  // extern "C"
 
+// ---- what the three sampled families share: player map, orderings, running statistics, launch timing, problem store ----
+namespace {
+
+// lsspa_*_lift_set_players on the family's map: the refusals, quiesce() (the family's wait for the stream, and what it
+// resets with it), the upload.  The map changes what a sample is, so the caller starts its statistics or orderings over.
+template <typename Quiesce>
+int lift_players_set(lsspa_ctx* ctx, LiftPlayers& P, const char* entry, int p, const int32_t* labels, int g,
+                     Quiesce&& quiesce) {
+  char msg[120];
+  snprintf(msg, sizeof msg, "%s: labels is NULL (clear the map with labels = NULL, g = 0)", entry);
+  return player_map_set(ctx, msg, labels, p, g, quiesce, P.map, P.pl_off, P.pl_cols, P.ng);
+}
+
+int lift_check_orderings(lsspa_ctx* ctx, const char* entry, const char* count_name, const int32_t* perms, int64_t count,
+                         int p, int g, int d, int limit_rows) {
+  char msg[240];
+  if (lift_orderings_why(entry, count_name, perms, count, p, g, d, limit_rows, ctx->perm_mark, msg, sizeof msg))
+    return ctx->fail(LSSPA_ERR_ARG, msg);
+  return LSSPA_OK;
+}
+
+int lift_stats_alloc(lsspa_ctx* ctx, LiftStats& S, size_t entries) {
+  TRY(dev_alloc(ctx, S.mean, entries));
+  return dev_alloc(ctx, S.M2, entries);
+}
+// n = 0, (mean, M2) cleared; the caller has waited for the stream
+int lift_stats_clear(lsspa_ctx* ctx, LiftStats& S, size_t entries) {
+  HIPCHK(hipMemset(S.mean.ptr, 0, sizeof(double) * entries));
+  HIPCHK(hipMemset(S.M2.ptr, 0, sizeof(double) * entries));
+  S.n = 0;
+  return LSSPA_OK;
+}
+// lsspa_*_lift_reset: the wait, the clear, and the family's info words
+int lift_stats_reset(lsspa_ctx* ctx, LiftStats& S, size_t entries, DevBuf<int32_t>& info, size_t n_info) {
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  TRY(lift_stats_clear(ctx, S, entries));
+  HIPCHK(hipMemset(info.ptr, 0, sizeof(int32_t) * n_info));
+  return LSSPA_OK;
+}
+// ns samples [ns][entries] into the running state
+int lift_stats_fold(lsspa_ctx* ctx, LiftStats& S, const double* samples, int64_t entries, int64_t ns) {
+  HIPCHK(launch_multi_lift_stats(samples, entries, (int)ns, S.n, S.mean.ptr, S.M2.ptr, ctx->stream));
+  S.n += ns;
+  return LSSPA_OK;
+}
+// lsspa_*_lift_get
+int lift_stats_get(lsspa_ctx* ctx, const LiftStats& S, size_t entries, int64_t* n, double* mean, double* m2) {
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (n) *n = S.n;
+  if (mean) HIPCHK(hipMemcpy(mean, S.mean.ptr, sizeof(double) * entries, hipMemcpyDeviceToHost));
+  if (m2) HIPCHK(hipMemcpy(m2, S.M2.ptr, sizeof(double) * entries, hipMemcpyDeviceToHost));
+  return LSSPA_OK;
+}
+
+// A batch launch's three events: the lift kernels between mark 0 and mark 1, what folds their output between 1 and 2.
+// finish() waits for the stream (the next launch reuses the buffers) and gives the two intervals.
+struct LiftLaunchTimer {
+  std::vector<hipEvent_t> ev = std::vector<hipEvent_t>(3, nullptr);
+  Events guard{ev};
+  int create(lsspa_ctx* ctx) {
+    for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+    return LSSPA_OK;
+  }
+  int mark(lsspa_ctx* ctx, int k) {
+    HIPCHK(hipEventRecord(ev[(size_t)k], ctx->stream));
+    return LSSPA_OK;
+  }
+  int finish(lsspa_ctx* ctx, double& lift_ms, double& fold_ms) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    lift_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    fold_ms = ms;
+    return LSSPA_OK;
+  }
+};
+
+// room for `count` problems; inv_yy takes `small` entries and aug twice as many
+int lift_problems_alloc(lsspa_ctx* ctx, LiftProblems& Q, size_t count, size_t small) {
+  TRY(dev_alloc(ctx, Q.G, count * LiftProblems::LL));
+  TRY(dev_alloc(ctx, Q.H, count * LiftProblems::LL));
+  TRY(dev_alloc(ctx, Q.g, count * LiftProblems::LD));
+  TRY(dev_alloc(ctx, Q.h, count * LiftProblems::LD));
+  TRY(dev_alloc(ctx, Q.inv_yy, small));
+  return dev_alloc(ctx, Q.aug, 2 * small);
+}
+// the columns behind p of a problem's rows are read (the register-resident gather fetches pairs), never used: zero
+int lift_problems_zero(lsspa_ctx* ctx, LiftProblems& Q, size_t count, hipStream_t st) {
+  HIPCHK(hipMemsetAsync(Q.G.ptr, 0, sizeof(double) * count * LiftProblems::LL, st));
+  HIPCHK(hipMemsetAsync(Q.H.ptr, 0, sizeof(double) * count * LiftProblems::LL, st));
+  HIPCHK(hipMemsetAsync(Q.g.ptr, 0, sizeof(double) * count * LiftProblems::LD, st));
+  HIPCHK(hipMemsetAsync(Q.h.ptr, 0, sizeof(double) * count * LiftProblems::LD, st));
+  return LSSPA_OK;
+}
+// problems first .. first + n - 1 dense to the host, enqueued on st: G, H [n][p][p], g, h [n][p], inv_yy [n]; any may be NULL
+int lift_problems_copy_out(lsspa_ctx* ctx, const LiftProblems& Q, int64_t first, int64_t n, int p, double* G, double* H,
+                           double* g, double* h, double* inv_yy, hipStream_t st) {
+  constexpr size_t LD = LiftProblems::LD, LL = LiftProblems::LL, row = sizeof(double) * LD;
+  const size_t w = sizeof(double) * p, pp = (size_t)p * p;
+  for (int64_t f = 0; f < n; ++f) {
+    if (G) HIPCHK(hipMemcpy2DAsync(G + f * pp, w, Q.G.ptr + (first + f) * LL, row, w, (size_t)p, hipMemcpyDeviceToHost, st));
+    if (H) HIPCHK(hipMemcpy2DAsync(H + f * pp, w, Q.H.ptr + (first + f) * LL, row, w, (size_t)p, hipMemcpyDeviceToHost, st));
+  }
+  if (g) HIPCHK(hipMemcpy2DAsync(g, w, Q.g.ptr + first * LD, row, w, (size_t)n, hipMemcpyDeviceToHost, st));
+  if (h) HIPCHK(hipMemcpy2DAsync(h, w, Q.h.ptr + first * LD, row, w, (size_t)n, hipMemcpyDeviceToHost, st));
+  if (inv_yy) HIPCHK(hipMemcpyAsync(inv_yy, Q.inv_yy.ptr + first, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  return LSSPA_OK;
+}
+// What launch_small_folds / launch_small_problems take of an ordering launch over stored problems, whoever calls: the
+// orderings' form (with a map both rows of a pair are explicit -- the baseline stays first) and the raw lifts ...
+SmallArgs lift_small_args(int p, int nb, int per, int g, double* raw) {
+  SmallArgs a{};
+  a.ld_src = LiftProblems::LD;
+  a.fwd_only = (!g && per == 2) ? 1 : 0;
+  a.p = p;
+  a.nb = nb;
+  a.per_sample = per;
+  a.lifts = raw;
+  a.y_norm_sq = 1.0;
+  a.piv_tol = exact_piv_tol(p);
+  a.sum_tol = -1.0;
+  return a;
+}
+// ... and problems first .. first + folds - 1 of the store
+void lift_problems_args(const LiftProblems& Q, int64_t first, int folds, SmallArgs& a, SmallFolds& fo) {
+  a.S[0] = Q.G.ptr + first * LiftProblems::LL;
+  a.S[1] = Q.H.ptr + first * LiftProblems::LL;
+  a.s[0] = Q.g.ptr + first * LiftProblems::LD;
+  a.s[1] = Q.h.ptr + first * LiftProblems::LD;
+  fo.mat = LiftProblems::LL;
+  fo.vec = LiftProblems::LD;
+  fo.aug = Q.aug.ptr + 2 * first;
+  fo.inv_yy = Q.inv_yy.ptr + first;
+  fo.folds = folds;
+}
+
+}  // namespace
+
 // ---- sampled attribution of many responses on one design matrix (k_small_multi.hip) ----------------------------------
 // The reduced form is lsspa_multi_load's (one Gram pass per side over Z = [X | Y]).  A batch of orderings runs as
 // launches of whole samples, a launch's grid (orderings of its samples) x (chunks of MLIFT_RB responses); its lift vectors
@@ -6627,7 +6788,7 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
                 const double* yy) {
   MultiLiftWork& W = ctx->mlift;
   W.loaded = false;
-  W.ng = 0;                // a player map belongs to the responses it was set on
+  W.pl.ng = 0;             // a player map belongs to the responses it was set on
   TRY(reduced_check_yy(ctx, m, yy, "column %d of Y_test is identically zero (or NaN)"));
   // the augmented rows' trailing corner  aug I - Z Z^T  (Z: the z rows of a chunk) stays positive definite when aug
   // exceeds the sum of the chunk's ||z_r||^2: twice MLIFT_RB times the largest, plus one
@@ -6636,14 +6797,11 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
   TRY(reduced_store(ctx, W.rf, p, m, G, g, H, h, yy, W.rf.g, W.rf.h));
   const size_t mp = (size_t)m * p;
   TRY(dev_alloc(ctx, W.yy, (size_t)m));
-  TRY(dev_alloc(ctx, W.mean, mp));
-  TRY(dev_alloc(ctx, W.M2, mp));
+  TRY(lift_stats_alloc(ctx, W.st, mp));
   TRY(dev_alloc(ctx, W.info, 8));
   HIPCHK(hipMemcpy(W.yy.ptr, yy, sizeof(double) * m, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
-  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
+  TRY(lift_stats_clear(ctx, W.st, mp));
   HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
-  W.n = 0;
   W.batch_ms = W.stats_ms = 0.0;
   W.loaded = true;
   return LSSPA_OK;
@@ -6652,13 +6810,7 @@ int mlift_store(lsspa_ctx* ctx, int p, int m, const double* G, const double* g, 
 // n = 0, (mean, M2) and the info word cleared
 int mlift_reset(lsspa_ctx* ctx) {
   MultiLiftWork& W = ctx->mlift;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t mp = (size_t)W.rf.m * W.rf.p;
-  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * mp));
-  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * mp));
-  HIPCHK(hipMemset(W.info.ptr, 0, 8 * sizeof(int32_t)));
-  W.n = 0;
-  return LSSPA_OK;
+  return lift_stats_reset(ctx, W.st, (size_t)W.rf.m * W.rf.p, W.info, 8);
 }
 
 }  // namespace
@@ -6707,26 +6859,10 @@ int lsspa_multi_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t 
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
   MultiLiftWork& W = ctx->mlift;
-  if (!labels && g != 0)
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_multi_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
-  PlayerMap map;
-  if (labels) {
-    const char* why = player_map_build(labels, W.rf.p, g, map);
-    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  TRY(mlift_reset(ctx));       // (waits for work in flight: a previous batch may still read the tables)
-  if (labels) {
-    TRY(dev_alloc(ctx, W.pl_off, (size_t)W.rf.p + 1));
-    TRY(dev_alloc(ctx, W.pl_cols, (size_t)W.rf.p));
-    HIPCHK(hipMemcpy(W.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(W.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
-    W.map = std::move(map);
-    W.ng = g;
-  } else {
-    W.ng = 0;
-  }
-  return LSSPA_OK;
+  return lift_players_set(ctx, W.pl, "lsspa_multi_lift_set_players", W.rf.p, labels, g, [&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    return mlift_reset(ctx);     // (waits for work in flight: a previous batch may still read the tables)
+  });
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -6736,27 +6872,20 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
   MultiLiftWork& W = ctx->mlift;
-  const int p = W.rf.p, m = W.rf.m, g = W.ng, d = W.sd();
-  if (!perms || B < 1 || B > (int64_t)INT32_MAX / (g ? 2 * p : p))     // (with a map: two expanded rows a sample)
-    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_multi_lift_batch: perms is NULL, B < 1 or 2 B p >= 2^31"
-                                      : "lsspa_multi_lift_batch: perms is NULL, B < 1 or B p >= 2^31");
-  if (!all_permutations(perms, (int)B, d, ctx->perm_mark))
-    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_multi_lift_batch: a row of perms is not a permutation of 0 .. g-1 (a player "
-                                        "map is set: the orderings are orderings of the groups)"
-                                      : "lsspa_multi_lift_batch: a row of perms is not a permutation of 0 .. p-1");
+  const int p = W.rf.p, m = W.rf.m, g = W.pl.ng, d = W.sd();
+  // (with a map: two expanded rows a sample)
+  TRY(lift_check_orderings(ctx, "lsspa_multi_lift_batch", "B", perms, B, p, g, d, g ? 2 : 1));
   HIPCHK(hipSetDevice(ctx->device));
   const int per = antithetical ? 2 : 1;
   const int64_t chunks = (m + MLIFT_RB - 1) / MLIFT_RB, entries = (int64_t)m * d;
   // samples a launch: by the grid and by the lift vectors' bytes -- by B, m, p and g alone
   const int64_t S = std::min(B, std::max<int64_t>(1, std::min(MLIFT_GRID_PER_LAUNCH / (per * chunks),
                                                               MLIFT_LIFT_DOUBLES / entries)));
-  const int64_t rows_per = g ? per : 1;      // rows of perms a sample takes on the device
+  const int64_t rows_per = W.pl.rows_per(per);
   TRY(dev_alloc(ctx, W.lifts, (size_t)(S * entries)));
   TRY(dev_alloc(ctx, W.perms, (size_t)(S * rows_per * p)));
-  if (g) W.rows.resize((size_t)(S * rows_per * p));
-  std::vector<hipEvent_t> ev(3, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  LiftLaunchTimer t;
+  TRY(t.create(ctx));
   W.batch_ms = W.stats_ms = 0.0;
   MultiLiftArgs a{};
   a.G = W.rf.G.ptr;
@@ -6776,40 +6905,29 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
   a.piv_tol = exact_piv_tol(p);
   a.info = W.info.ptr;
   a.ng = g;
-  a.n_cols = g ? (int)W.map.cols.size() : 0;
-  a.off = g ? W.pl_off.ptr : nullptr;
-  a.cols = g ? W.pl_cols.ptr : nullptr;
+  a.n_cols = g ? (int)W.pl.map.cols.size() : 0;
+  a.off = W.pl.off();
+  a.cols = W.pl.cols();
   for (int64_t s0 = 0; s0 < B; s0 += S) {
     const int64_t ns = std::min(S, B - s0);
-    const int32_t* src = perms + s0 * p;
-    if (g) {      // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
-      for (int64_t s = 0; s < ns; ++s)
-        for (int r = 0; r < per; ++r)
-          expand_group_row(W.map, perms + (s0 + s) * g, r, W.rows.data() + (size_t)((s * per + r) * p));
-      src = W.rows.data();
-    }
+    const int32_t* src = lift_stage_rows(W.pl.map, g, perms, s0, ns, per, p, W.pl.rows);
     HIPCHK(hipMemcpyAsync(W.perms.ptr, src, sizeof(int32_t) * (size_t)(ns * rows_per * p), hipMemcpyHostToDevice,
                           ctx->stream));
     if (per == 2)     // the pair's two terms are added into a zeroed destination
       HIPCHK(hipMemsetAsync(W.lifts.ptr, 0, sizeof(double) * (size_t)(ns * entries), ctx->stream));
     a.n_samples = (int)ns;
-    HIPCHK(hipEventRecord(ev[0], ctx->stream));
+    TRY(t.mark(ctx, 0));
     HIPCHK(launch_multi_lift(a, ctx->stream));
-    HIPCHK(hipEventRecord(ev[1], ctx->stream));
-    if (accumulate) {
-      HIPCHK(launch_multi_lift_stats(W.lifts.ptr, entries, (int)ns, W.n, W.mean.ptr, W.M2.ptr, ctx->stream));
-      W.n += ns;
-    }
-    HIPCHK(hipEventRecord(ev[2], ctx->stream));
+    TRY(t.mark(ctx, 1));
+    if (accumulate) TRY(lift_stats_fold(ctx, W.st, W.lifts.ptr, entries, ns));
+    TRY(t.mark(ctx, 2));
     if (lifts_out)
       HIPCHK(hipMemcpyAsync(lifts_out + s0 * entries, W.lifts.ptr, sizeof(double) * (size_t)(ns * entries),
                             hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses both buffers
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    W.batch_ms += ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    if (accumulate) W.stats_ms += ms;
+    double lift_ms, fold_ms;
+    TRY(t.finish(ctx, lift_ms, fold_ms));
+    W.batch_ms += lift_ms;
+    if (accumulate) W.stats_ms += fold_ms;
   }
   return LSSPA_OK;
 } catch (...) {
@@ -6819,14 +6937,8 @@ int lsspa_multi_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int3
 int lsspa_multi_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(mlift_need_loaded(ctx));
-  MultiLiftWork& W = ctx->mlift;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t mp = (size_t)W.rf.m * W.sd();
-  if (n) *n = W.n;
-  if (mean) HIPCHK(hipMemcpy(mean, W.mean.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
-  if (m2) HIPCHK(hipMemcpy(m2, W.M2.ptr, sizeof(double) * mp, hipMemcpyDeviceToHost));
-  return LSSPA_OK;
+  const MultiLiftWork& W = ctx->mlift;
+  return lift_stats_get(ctx, W.st, (size_t)W.rf.m * W.sd(), n, mean, m2);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -6924,13 +7036,7 @@ int cvlift_need_loaded(lsspa_ctx* ctx) {
 // n = 0, (mean, M2) and the info words cleared
 int cvlift_reset(lsspa_ctx* ctx) {
   CvLiftWork& W = ctx->cvlift;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t e = (size_t)(W.K + 1) * W.p;
-  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * e));
-  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * e));
-  HIPCHK(hipMemset(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS));
-  W.n = 0;
-  return LSSPA_OK;
+  return lift_stats_reset(ctx, W.st, (size_t)(W.K + 1) * W.p, W.info, CV_MAX_FOLDS);
 }
 
 }  // namespace
@@ -6955,35 +7061,20 @@ int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y,
     return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_load: NULL array, p < 1, N outside 2 .. 2^31 - 1, ld < p, reg not "
                                     "finite and >= 0, or bad dtype / location");
   int32_t nf[CV_MAX_FOLDS] = {0};
-  for (int64_t i = 0; i < N; ++i) {
-    if (fold_ids[i] < 0 || fold_ids[i] >= K) {
-      snprintf(msg, sizeof msg, "fold_ids[%lld] = %d: fold labels must be 0 .. %d (K - 1)", (long long)i,
-               (int)fold_ids[i], (int)K - 1);
-      return ctx->fail(LSSPA_ERR_ARG, msg);
-    }
-    ++nf[fold_ids[i]];
-  }
-  for (int f = 0; f < K; ++f)
-    if (nf[f] == 0) {
-      snprintf(msg, sizeof msg, "fold %d of %d is empty: every fold needs at least one row", f, (int)K);
-      return ctx->fail(LSSPA_ERR_ARG, msg);
-    }
+  if (cv_count_folds(fold_ids, N, K, nf, msg, sizeof msg)) return ctx->fail(LSSPA_ERR_ARG, msg);
   for (int f = 0; f < K; ++f)
     if (nf[f] < p) {
       snprintf(msg, sizeof msg, "fold %d of %d has %d rows, fewer than p = %d: the Gram matrix of a fold's own rows must "
                "have a Cholesky factor", f, (int)K, (int)nf[f], (int)p);
       return ctx->fail(LSSPA_ERR_ARG, msg);
     }
-  if (location == LSSPA_HOST) {          // (rows on the device: the pooled sum is looked at after the Gram passes)
-    bool any = false;
-    for (int64_t i = 0; i < N && !any; ++i)
-      any = dtype == LSSPA_F32 ? ((const float*)y)[i] != 0.f : ((const double*)y)[i] != 0.0;
-    if (!any) return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
-  }
+  // (rows on the device: the pooled sum is looked at after the Gram passes)
+  if (location == LSSPA_HOST && host_all_zero(y, N, dtype))
+    return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
   HIPCHK(hipSetDevice(ctx->device));
   CvLiftWork& W = ctx->cvlift;
   W.loaded = false;
-  W.ng = 0;                // a player map belongs to the data it was set on
+  W.pl.ng = 0;              // a player map belongs to the data it was set on
   hipStream_t st = ctx->stream;
   // every row's place when the rows are sorted by fold, stable in row order
   std::vector<int32_t> dest((size_t)N);
@@ -7009,23 +7100,13 @@ int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y,
   TRY(dev_alloc(ctx, S, (size_t)K * LL));
   TRY(dev_alloc(ctx, dst_d, (size_t)N));
   TRY(dev_alloc(ctx, nf_d, CV_MAX_FOLDS));
-  TRY(dev_alloc(ctx, W.G, (size_t)K * LL));
-  TRY(dev_alloc(ctx, W.H, (size_t)K * LL));
-  TRY(dev_alloc(ctx, W.g, (size_t)K * LD));
-  TRY(dev_alloc(ctx, W.h, (size_t)K * LD));
-  TRY(dev_alloc(ctx, W.inv_yy, CV_MAX_FOLDS));
-  TRY(dev_alloc(ctx, W.aug, 2 * CV_MAX_FOLDS));
+  TRY(lift_problems_alloc(ctx, W.pr, (size_t)K, CV_MAX_FOLDS));
   TRY(dev_alloc(ctx, W.info, CV_MAX_FOLDS));
-  TRY(dev_alloc(ctx, W.mean, (size_t)(K + 1) * p));
-  TRY(dev_alloc(ctx, W.M2, (size_t)(K + 1) * p));
+  TRY(lift_stats_alloc(ctx, W.st, (size_t)(K + 1) * p));
   HIPCHK(hipStreamSynchronize(st));      // a previous call may still read the buffers
   HIPCHK(hipMemcpy(dst_d.ptr, dest.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(nf_d.ptr, nf, sizeof nf, hipMemcpyHostToDevice));
-  // the columns behind p of a problem's rows are read (the register-resident gather fetches pairs), never used: zero
-  HIPCHK(hipMemsetAsync(W.G.ptr, 0, sizeof(double) * K * LL, st));
-  HIPCHK(hipMemsetAsync(W.H.ptr, 0, sizeof(double) * K * LL, st));
-  HIPCHK(hipMemsetAsync(W.g.ptr, 0, sizeof(double) * K * LD, st));
-  HIPCHK(hipMemsetAsync(W.h.ptr, 0, sizeof(double) * K * LD, st));
+  TRY(lift_problems_zero(ctx, W.pr, (size_t)K, st));
   std::vector<hipEvent_t> ev(2, nullptr);
   Events guard{ev};
   for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
@@ -7036,8 +7117,8 @@ int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y,
                 }));
   for (int f = 0; f < K; ++f)            // S_f: the Gram reduction on the fold's slice (gram_side waits for it)
     TRY(gram_side(ctx, Xs.ptr + (size_t)first[f] * LD, ys.ptr + first[f], nf[f], (int64_t)LD, p, 0, S.ptr + (size_t)f * LL));
-  HIPCHK(launch_cv_lift_finalize(S.ptr, nf_d.ptr, N, p, K, reg, W.G.ptr, W.g.ptr, W.H.ptr, W.h.ptr, W.inv_yy.ptr,
-                                 W.aug.ptr, st));
+  HIPCHK(launch_cv_lift_finalize(S.ptr, nf_d.ptr, N, p, K, reg, W.pr.G.ptr, W.pr.g.ptr, W.pr.H.ptr, W.pr.h.ptr,
+                                 W.pr.inv_yy.ptr, W.pr.aug.ptr, st));
   HIPCHK(hipEventRecord(ev[1], st));
   const size_t pp = (size_t)p * p;
   W.Gh.resize(K * pp);
@@ -7045,17 +7126,7 @@ int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y,
   W.gh.resize((size_t)K * p);
   W.hh.resize((size_t)K * p);
   W.yh.resize((size_t)K);
-  for (int f = 0; f < K; ++f) {
-    HIPCHK(hipMemcpy2DAsync(W.Gh.data() + f * pp, sizeof(double) * p, W.G.ptr + f * LL, sizeof(double) * LD,
-                            sizeof(double) * p, (size_t)p, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpy2DAsync(W.Hh.data() + f * pp, sizeof(double) * p, W.H.ptr + f * LL, sizeof(double) * LD,
-                            sizeof(double) * p, (size_t)p, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipMemcpy2DAsync(W.gh.data(), sizeof(double) * p, W.g.ptr, sizeof(double) * LD, sizeof(double) * p, (size_t)K,
-                          hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpy2DAsync(W.hh.data(), sizeof(double) * p, W.h.ptr, sizeof(double) * LD, sizeof(double) * p, (size_t)K,
-                          hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(W.yh.data(), W.inv_yy.ptr, sizeof(double) * K, hipMemcpyDeviceToHost, st));
+  TRY(lift_problems_copy_out(ctx, W.pr, 0, K, p, W.Gh.data(), W.Hh.data(), W.gh.data(), W.hh.data(), W.yh.data(), st));
   HIPCHK(hipStreamSynchronize(st));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -7065,10 +7136,8 @@ int lsspa_cv_lift_load(lsspa_ctx* ctx, const void* X, int64_t ld, const void* y,
     return ctx->fail(LSSPA_ERR_ARG, "y is identically zero (sum y^2 = 0): the cross-validated R^2 is not defined");
   W.p = p;
   W.K = K;
-  HIPCHK(hipMemset(W.mean.ptr, 0, sizeof(double) * (size_t)(K + 1) * p));
-  HIPCHK(hipMemset(W.M2.ptr, 0, sizeof(double) * (size_t)(K + 1) * p));
+  TRY(lift_stats_clear(ctx, W.st, (size_t)(K + 1) * p));
   HIPCHK(hipMemset(W.info.ptr, 0, sizeof(int32_t) * CV_MAX_FOLDS));
-  W.n = 0;
   W.loaded = true;
   return LSSPA_OK;
 } catch (...) {
@@ -7079,26 +7148,10 @@ int lsspa_cv_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g) 
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(cvlift_need_loaded(ctx));
   CvLiftWork& W = ctx->cvlift;
-  if (!labels && g != 0)
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
-  PlayerMap map;
-  if (labels) {
-    const char* why = player_map_build(labels, W.p, g, map);
-    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  TRY(cvlift_reset(ctx));       // (waits for work in flight: a previous batch may still read the tables)
-  if (labels) {
-    TRY(dev_alloc(ctx, W.pl_off, (size_t)W.p + 1));
-    TRY(dev_alloc(ctx, W.pl_cols, (size_t)W.p));
-    HIPCHK(hipMemcpy(W.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(W.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
-    W.map = std::move(map);
-    W.ng = g;
-  } else {
-    W.ng = 0;
-  }
-  return LSSPA_OK;
+  return lift_players_set(ctx, W.pl, "lsspa_cv_lift_set_players", W.p, labels, g, [&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    return cvlift_reset(ctx);    // (waits for work in flight: a previous batch may still read the tables)
+  });
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -7108,72 +7161,37 @@ int lsspa_cv_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int32_t
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(cvlift_need_loaded(ctx));
   CvLiftWork& W = ctx->cvlift;
-  const int p = W.p, K = W.K, g = W.ng, d = W.sd();
-  if (!perms || B < 1 || B > (int64_t)INT32_MAX / (2 * p))
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_batch: perms is NULL, B < 1 or 2 B p >= 2^31");
-  if (!all_permutations(perms, (int)B, d, ctx->perm_mark))
-    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_cv_lift_batch: a row of perms is not a permutation of 0 .. g-1 (a player "
-                                        "map is set: the orderings are orderings of the groups)"
-                                      : "lsspa_cv_lift_batch: a row of perms is not a permutation of 0 .. p-1");
+  const int p = W.p, K = W.K, g = W.pl.ng, d = W.sd();
+  TRY(lift_check_orderings(ctx, "lsspa_cv_lift_batch", "B", perms, B, p, g, d, 2));
   HIPCHK(hipSetDevice(ctx->device));
   const int per = antithetical ? 2 : 1;
   CvLiftPlan P;
   if (!cvlift_plan(p, d, K, B, antithetical, P)) return ctx->fail(LSSPA_ERR_ARG, "lsspa_cv_lift_batch: no launch plan");
   const int64_t S = P.S, entries = (int64_t)(K + 1) * d;
-  const int64_t rows_per = g ? per : 1;      // rows of perms a sample takes on the device
+  const int64_t rows_per = W.pl.rows_per(per);
   TRY(dev_alloc(ctx, W.raw, (size_t)(S * per * K * p)));
   TRY(dev_alloc(ctx, W.batch, (size_t)(S * entries)));
   TRY(dev_alloc(ctx, W.perms, (size_t)(S * rows_per * p)));
-  if (g) W.rows.resize((size_t)(S * rows_per * p));
-  std::vector<hipEvent_t> ev(3, nullptr);
-  Events guard{ev};
-  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  LiftLaunchTimer t;
+  TRY(t.create(ctx));
   W.batch_ms = W.stats_ms = 0.0;
-  constexpr int64_t LD = CV_LIFT_LD;
-  SmallArgs a{};
-  a.S[0] = W.G.ptr;
-  a.S[1] = W.H.ptr;
-  a.s[0] = W.g.ptr;
-  a.s[1] = W.h.ptr;
-  a.ld_src = LD;
-  a.perms = W.perms.ptr;
-  a.fwd_only = (!g && per == 2) ? 1 : 0;     // with a map both rows of a pair are explicit (the baseline stays first)
-  a.p = p;
-  a.nb = P.nb;
-  a.per_sample = per;
-  a.lifts = W.raw.ptr;
-  a.y_norm_sq = 1.0;
-  a.piv_tol = exact_piv_tol(p);
-  a.info = W.info.ptr;
-  a.sum_tol = -1.0;
+  SmallArgs a = lift_small_args(p, P.nb, per, g, W.raw.ptr);
   SmallFolds fo{};
-  fo.mat = LD * LD;
-  fo.vec = LD;
-  fo.aug = W.aug.ptr;
-  fo.inv_yy = W.inv_yy.ptr;
-  fo.folds = K;
+  lift_problems_args(W.pr, 0, K, a, fo);
+  a.perms = W.perms.ptr;
+  a.info = W.info.ptr;
   for (int64_t s0 = 0; s0 < B; s0 += S) {
     const int64_t ns = std::min(S, B - s0);
-    const int32_t* src = perms + s0 * p;
-    if (g) {      // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
-      for (int64_t s = 0; s < ns; ++s)
-        for (int r = 0; r < per; ++r)
-          expand_group_row(W.map, perms + (s0 + s) * g, r, W.rows.data() + (size_t)((s * per + r) * p));
-      src = W.rows.data();
-    }
+    const int32_t* src = lift_stage_rows(W.pl.map, g, perms, s0, ns, per, p, W.pl.rows);
     HIPCHK(hipMemcpyAsync(W.perms.ptr, src, sizeof(int32_t) * (size_t)(ns * rows_per * p), hipMemcpyHostToDevice,
                           ctx->stream));
     a.n_ord = (int)(ns * per);
-    HIPCHK(hipEventRecord(ev[0], ctx->stream));
+    TRY(t.mark(ctx, 0));
     HIPCHK(launch_small_folds(a, fo, ctx->stream));
-    HIPCHK(hipEventRecord(ev[1], ctx->stream));
-    HIPCHK(launch_cv_lift_fold(W.raw.ptr, p, K, per, g ? W.pl_off.ptr : nullptr, g ? W.pl_cols.ptr : nullptr, d, ns,
-                               W.batch.ptr, ctx->stream));
-    if (accumulate) {
-      HIPCHK(launch_multi_lift_stats(W.batch.ptr, entries, (int)ns, W.n, W.mean.ptr, W.M2.ptr, ctx->stream));
-      W.n += ns;
-    }
-    HIPCHK(hipEventRecord(ev[2], ctx->stream));
+    TRY(t.mark(ctx, 1));
+    HIPCHK(launch_cv_lift_fold(W.raw.ptr, p, K, per, W.pl.off(), W.pl.cols(), d, ns, W.batch.ptr, ctx->stream));
+    if (accumulate) TRY(lift_stats_fold(ctx, W.st, W.batch.ptr, entries, ns));
+    TRY(t.mark(ctx, 2));
     if (fold_lifts_out)
       HIPCHK(hipMemcpy2DAsync(fold_lifts_out + s0 * K * d, sizeof(double) * K * d, W.batch.ptr, sizeof(double) * entries,
                               sizeof(double) * K * d, (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
@@ -7181,12 +7199,10 @@ int lsspa_cv_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int32_t
       HIPCHK(hipMemcpy2DAsync(lifts_out + s0 * d, sizeof(double) * d, W.batch.ptr + (size_t)K * d,
                               sizeof(double) * entries, sizeof(double) * d, (size_t)ns, hipMemcpyDeviceToHost,
                               ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));     // the next launch reuses the buffers
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    W.batch_ms += ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    W.stats_ms += ms;
+    double lift_ms, fold_ms;
+    TRY(t.finish(ctx, lift_ms, fold_ms));
+    W.batch_ms += lift_ms;
+    W.stats_ms += fold_ms;
   }
   return LSSPA_OK;
 } catch (...) {
@@ -7196,14 +7212,8 @@ int lsspa_cv_lift_batch(lsspa_ctx* ctx, const int32_t* perms, int64_t B, int32_t
 int lsspa_cv_lift_get(lsspa_ctx* ctx, int64_t* n, double* mean, double* m2) try {
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(cvlift_need_loaded(ctx));
-  CvLiftWork& W = ctx->cvlift;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const size_t e = (size_t)(W.K + 1) * W.sd();
-  if (n) *n = W.n;
-  if (mean) HIPCHK(hipMemcpy(mean, W.mean.ptr, sizeof(double) * e, hipMemcpyDeviceToHost));
-  if (m2) HIPCHK(hipMemcpy(m2, W.M2.ptr, sizeof(double) * e, hipMemcpyDeviceToHost));
-  return LSSPA_OK;
+  const CvLiftWork& W = ctx->cvlift;
+  return lift_stats_get(ctx, W.st, (size_t)(W.K + 1) * W.sd(), n, mean, m2);
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -7310,7 +7320,7 @@ int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, in
                   bool ones, int64_t block, const BootLiftOut& out) {
   BootLiftWork& B = ctx->bootlift;
   const int p = B.p, d = B.sd(), c = p + 1;
-  constexpr int64_t LD = BOOT_LIFT_LD, LL = LD * LD;
+  constexpr int64_t LD = LiftProblems::LD, LL = LiftProblems::LL;
   const int per = out.lifts ? B.per : 1;
   const int64_t n_samples = out.lifts ? B.n_samples : 1;
   BootLiftPlan P;
@@ -7333,12 +7343,7 @@ int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, in
     TRY(dev_alloc(ctx, B.S(s), blk * cc));
   }
   TRY(dev_alloc(ctx, B.wsum, blk));
-  TRY(dev_alloc(ctx, B.G, blk * LL));
-  TRY(dev_alloc(ctx, B.H, blk * LL));
-  TRY(dev_alloc(ctx, B.g, blk * LD));
-  TRY(dev_alloc(ctx, B.h, blk * LD));
-  TRY(dev_alloc(ctx, B.inv_yy, blk));
-  TRY(dev_alloc(ctx, B.aug, 2 * blk));
+  TRY(lift_problems_alloc(ctx, B.pr, blk, blk));
   TRY(dev_alloc(ctx, B.info, blk));
   const int64_t E = std::min<int64_t>(P.reps_per_launch, P.block), S = P.samples_per_launch;
   if (out.lifts) {
@@ -7348,36 +7353,19 @@ int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, in
     if (out.samples) TRY(dev_alloc(ctx, B.samples, (size_t)(E * S * d)));
   }
   HIPCHK(hipStreamSynchronize(st));        // a previous call may still read the buffers
-  // the columns behind p of a problem's rows are read (the register-resident gather fetches pairs), never used: zero
-  HIPCHK(hipMemsetAsync(B.G.ptr, 0, sizeof(double) * blk * LL, st));
-  HIPCHK(hipMemsetAsync(B.H.ptr, 0, sizeof(double) * blk * LL, st));
-  HIPCHK(hipMemsetAsync(B.g.ptr, 0, sizeof(double) * blk * LD, st));
-  HIPCHK(hipMemsetAsync(B.h.ptr, 0, sizeof(double) * blk * LD, st));
+  TRY(lift_problems_zero(ctx, B.pr, blk, st));
   const int64_t cuts = P.sample_cuts, per_block = (P.block + E - 1) / E * cuts;
   std::vector<hipEvent_t> ev((size_t)(3 + (out.lifts ? 2 * per_block : 0)), nullptr);
   Events guard{ev};
   for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-  const int g = B.ng;
-  const int64_t rows_per = g ? per : 1;      // rows of perms a sample takes on the device
-  SmallArgs a{};
-  a.s[0] = B.g.ptr;
-  a.s[1] = B.h.ptr;
-  a.ld_src = LD;
-  a.fwd_only = (!g && per == 2) ? 1 : 0;     // with a map both rows of a pair are explicit (the baseline stays first)
-  a.p = p;
-  a.nb = P.cb;
-  a.per_sample = per;
-  a.lifts = B.raw.ptr;
-  a.y_norm_sq = 1.0;
-  a.piv_tol = exact_piv_tol(p);
-  a.sum_tol = -1.0;
+  const int g = B.pl.ng;
+  const int64_t rows_per = B.pl.rows_per(per);
+  SmallArgs a = lift_small_args(p, P.cb, per, g, B.raw.ptr);
   SmallFolds fo{};
-  fo.mat = LL;
-  fo.vec = LD;
   std::vector<double> one, Gh, Hh, gh, hh, yh, ws;
   std::vector<int> all((size_t)p), basec;
   for (int j = 0; j < p; ++j) all[(size_t)j] = j;
-  if (g) basec.assign(B.map.base.begin(), B.map.base.end());
+  if (g) basec.assign(B.pl.map.base.begin(), B.pl.map.base.end());
   constexpr int CH = 32;                     // replicates whose problems come to the host at a time (their R^2)
   if (out.r2 || out.base) {
     Gh.resize((size_t)CH * LD * p);
@@ -7412,31 +7400,24 @@ int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, in
       if (s == 0) HIPCHK(launch_boot_wsum(cnt, wt, B.n[s], nb, B.wsum.ptr, st));
       HIPCHK(launch_boot_lift_reduce(P, s, B.part(s).ptr, p, nb, B.S(s).ptr, st));
     }
-    HIPCHK(launch_boot_lift_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.G.ptr, B.g.ptr, B.H.ptr, B.h.ptr,
-                                     B.inv_yy.ptr, B.aug.ptr, st));
+    HIPCHK(launch_boot_lift_finalize(B.S0.ptr, B.S1.ptr, B.wsum.ptr, p, B.reg, nb, B.pr.G.ptr, B.pr.g.ptr, B.pr.H.ptr,
+                                     B.pr.h.ptr, B.pr.inv_yy.ptr, B.pr.aug.ptr, st));
     HIPCHK(hipEventRecord(ev[2], st));
     HIPCHK(hipMemsetAsync(B.info.ptr, 0, sizeof(int32_t) * nb, st));
     size_t ne = 3;
     if (out.lifts) {
       for (int64_t e0 = 0; e0 < nb; e0 += E) {
         const int nr = (int)std::min<int64_t>(E, nb - e0);
-        a.S[0] = B.G.ptr + e0 * LL;
-        a.S[1] = B.H.ptr + e0 * LL;
-        a.s[0] = B.g.ptr + e0 * LD;
-        a.s[1] = B.h.ptr + e0 * LD;
+        lift_problems_args(B.pr, e0, nr, a, fo);
         a.info = B.info.ptr + e0;
-        fo.aug = B.aug.ptr + 2 * e0;
-        fo.inv_yy = B.inv_yy.ptr + e0;
-        fo.folds = nr;
         for (int64_t s0 = 0; s0 < n_samples; s0 += S) {
           const int ns = (int)std::min<int64_t>(S, n_samples - s0);
           a.perms = B.perms.ptr + s0 * rows_per * p;
           a.n_ord = ns * per;
           HIPCHK(launch_small_problems(a, fo, st));
           HIPCHK(hipEventRecord(ev[ne++], st));
-          HIPCHK(launch_boot_lift_stats(B.raw.ptr, p, nr, per, g ? B.pl_off.ptr : nullptr, g ? B.pl_cols.ptr : nullptr, d,
-                                        ns, s0, B.mean.ptr + e0 * d, B.M2.ptr + e0 * d,
-                                        out.samples ? B.samples.ptr : nullptr, st));
+          HIPCHK(launch_boot_lift_stats(B.raw.ptr, p, nr, per, B.pl.off(), B.pl.cols(), d, ns, s0, B.mean.ptr + e0 * d,
+                                        B.M2.ptr + e0 * d, out.samples ? B.samples.ptr : nullptr, st));
           HIPCHK(hipEventRecord(ev[ne++], st));
           if (out.samples)
             HIPCHK(hipMemcpy2DAsync(out.samples + ((b0 + e0) * n_samples + s0) * d, sizeof(double) * n_samples * d,
@@ -7456,14 +7437,7 @@ int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, in
     if (out.S_test)
       HIPCHK(hipMemcpyAsync(out.S_test + b0 * cc, B.S1.ptr, sizeof(double) * nb * cc, hipMemcpyDeviceToHost, st));
     if (out.wsum) HIPCHK(hipMemcpyAsync(out.wsum + b0, B.wsum.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-    if (b0 == 0) {
-      const size_t w = sizeof(double) * p;
-      if (out.G) HIPCHK(hipMemcpy2DAsync(out.G, w, B.G.ptr, sizeof(double) * LD, w, (size_t)p, hipMemcpyDeviceToHost, st));
-      if (out.H) HIPCHK(hipMemcpy2DAsync(out.H, w, B.H.ptr, sizeof(double) * LD, w, (size_t)p, hipMemcpyDeviceToHost, st));
-      if (out.g) HIPCHK(hipMemcpyAsync(out.g, B.g.ptr, w, hipMemcpyDeviceToHost, st));
-      if (out.h) HIPCHK(hipMemcpyAsync(out.h, B.h.ptr, w, hipMemcpyDeviceToHost, st));
-      if (out.inv_yy) HIPCHK(hipMemcpyAsync(out.inv_yy, B.inv_yy.ptr, sizeof(double), hipMemcpyDeviceToHost, st));
-    }
+    if (b0 == 0) TRY(lift_problems_copy_out(ctx, B.pr, 0, 1, p, out.G, out.H, out.g, out.h, out.inv_yy, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int k = 0; k < 2; ++k) {
       float ms = 0.f;
@@ -7479,11 +7453,12 @@ int bootlift_pass(lsspa_ctx* ctx, const char* name, int64_t R, uint64_t seed, in
       for (int c0 = 0; c0 < nb; c0 += CH) {
         const int nc = std::min(CH, nb - c0);
         const size_t w = sizeof(double) * p;
-        HIPCHK(hipMemcpy2D(Gh.data(), w, B.G.ptr + c0 * LL, sizeof(double) * LD, w, (size_t)nc * LD, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy2D(Hh.data(), w, B.H.ptr + c0 * LL, sizeof(double) * LD, w, (size_t)nc * LD, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy2D(gh.data(), w, B.g.ptr + c0 * LD, sizeof(double) * LD, w, (size_t)nc, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy2D(hh.data(), w, B.h.ptr + c0 * LD, sizeof(double) * LD, w, (size_t)nc, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(yh.data(), B.inv_yy.ptr + c0, sizeof(double) * nc, hipMemcpyDeviceToHost));
+        // (a chunk's matrices in one copy each, the padding rows with them: not lift_problems_copy_out's dense form)
+        HIPCHK(hipMemcpy2D(Gh.data(), w, B.pr.G.ptr + c0 * LL, sizeof(double) * LD, w, (size_t)nc * LD, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(Hh.data(), w, B.pr.H.ptr + c0 * LL, sizeof(double) * LD, w, (size_t)nc * LD, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(gh.data(), w, B.pr.g.ptr + c0 * LD, sizeof(double) * LD, w, (size_t)nc, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(hh.data(), w, B.pr.h.ptr + c0 * LD, sizeof(double) * LD, w, (size_t)nc, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(yh.data(), B.pr.inv_yy.ptr + c0, sizeof(double) * nc, hipMemcpyDeviceToHost));
         for (int r = 0; r < nc; ++r) {
           const double *Gr = &Gh[(size_t)r * LD * p], *Hr = &Hh[(size_t)r * LD * p];
           const double *gr = &gh[(size_t)r * p], *hr = &hh[(size_t)r * p];
@@ -7524,16 +7499,12 @@ int lsspa_boot_lift_load(lsspa_ctx* ctx, const void* X_train, int64_t ld_train, 
       (dtype != LSSPA_F64 && dtype != LSSPA_F32) || (location != LSSPA_HOST && location != LSSPA_DEVICE))
     return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_load: NULL array, ld < p, reg not finite and >= 0, or bad dtype / "
                                     "location");
-  if (location == LSSPA_HOST) {
-    bool any = false;
-    for (int64_t i = 0; i < M && !any; ++i)
-      any = dtype == LSSPA_F32 ? ((const float*)y_test)[i] != 0.f : ((const double*)y_test)[i] != 0.0;
-    if (!any) return ctx->fail(LSSPA_ERR_ARG, "y_test is identically zero (sum y^2 = 0): R^2 is not defined");
-  }
+  if (location == LSSPA_HOST && host_all_zero(y_test, M, dtype))
+    return ctx->fail(LSSPA_ERR_ARG, "y_test is identically zero (sum y^2 = 0): R^2 is not defined");
   HIPCHK(hipSetDevice(ctx->device));
   BootLiftWork& B = ctx->bootlift;
   B.loaded = false;
-  B.ng = 0;                // a player map and the orderings belong to the data they were set on
+  B.pl.ng = 0;              // a player map and the orderings belong to the data they were set on
   B.n_samples = 0;
   const void* X[2] = {X_train, X_test};
   const void* y[2] = {y_train, y_test};
@@ -7565,28 +7536,12 @@ int lsspa_boot_lift_set_players(lsspa_ctx* ctx, const int32_t* labels, int32_t g
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(bootlift_need_loaded(ctx));
   BootLiftWork& B = ctx->bootlift;
-  if (!labels && g != 0)
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_set_players: labels is NULL (clear the map with labels = NULL, g = 0)");
-  PlayerMap map;
-  if (labels) {
-    const char* why = player_map_build(labels, B.p, g, map);
-    if (why) return ctx->fail(LSSPA_ERR_ARG, why);
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));      // a previous run may still read the tables
-  B.n_samples = 0;                                // the orderings were orderings of the other players
-  if (labels) {
-    TRY(dev_alloc(ctx, B.pl_off, (size_t)B.p + 1));
-    TRY(dev_alloc(ctx, B.pl_cols, (size_t)B.p));
-    HIPCHK(hipMemcpy(B.pl_off.ptr, map.off.data(), sizeof(int32_t) * map.off.size(), hipMemcpyHostToDevice));
-    if (!map.cols.empty())
-      HIPCHK(hipMemcpy(B.pl_cols.ptr, map.cols.data(), sizeof(int32_t) * map.cols.size(), hipMemcpyHostToDevice));
-    B.map = std::move(map);
-    B.ng = g;
-  } else {
-    B.ng = 0;
-  }
-  return LSSPA_OK;
+  return lift_players_set(ctx, B.pl, "lsspa_boot_lift_set_players", B.p, labels, g, [&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // a previous run may still read the tables
+    B.n_samples = 0;                                // the orderings were orderings of the other players
+    return (int)LSSPA_OK;
+  });
 } catch (...) {
   return abi_caught(ctx);
 }
@@ -7595,27 +7550,16 @@ int lsspa_boot_lift_set_orderings(lsspa_ctx* ctx, const int32_t* perms, int64_t 
   if (!ctx) return LSSPA_ERR_ARG;
   TRY(bootlift_need_loaded(ctx));
   BootLiftWork& B = ctx->bootlift;
-  const int p = B.p, g = B.ng, d = B.sd();
-  if (!perms || n_samples < 1 || n_samples > (int64_t)INT32_MAX / (2 * p))
-    return ctx->fail(LSSPA_ERR_ARG, "lsspa_boot_lift_set_orderings: perms is NULL, n_samples < 1 or 2 n_samples p >= 2^31");
-  if (!all_permutations(perms, (int)n_samples, d, ctx->perm_mark))
-    return ctx->fail(LSSPA_ERR_ARG, g ? "lsspa_boot_lift_set_orderings: a row of perms is not a permutation of 0 .. g-1 (a "
-                                        "player map is set: the orderings are orderings of the groups)"
-                                      : "lsspa_boot_lift_set_orderings: a row of perms is not a permutation of 0 .. p-1");
+  const int p = B.p, g = B.pl.ng, d = B.sd();
+  TRY(lift_check_orderings(ctx, "lsspa_boot_lift_set_orderings", "n_samples", perms, n_samples, p, g, d, 2));
   HIPCHK(hipSetDevice(ctx->device));
   const int per = antithetical ? 2 : 1;
-  const int64_t rows_per = g ? per : 1;
+  const int64_t rows_per = B.pl.rows_per(per);
   HIPCHK(hipStreamSynchronize(ctx->stream));      // a previous run may still read the rows
   B.n_samples = 0;
   TRY(dev_alloc(ctx, B.perms, (size_t)(n_samples * rows_per * p)));
-  const int32_t* src = perms;
-  std::vector<int32_t> rows;
-  if (g) {      // the group orderings' expansions, the pair's second row with the groups reversed (the baseline stays first)
-    rows.resize((size_t)(n_samples * rows_per * p));
-    for (int64_t s = 0; s < n_samples; ++s)
-      for (int r = 0; r < per; ++r) expand_group_row(B.map, perms + s * g, r, rows.data() + (size_t)((s * per + r) * p));
-    src = rows.data();
-  }
+  std::vector<int32_t> rows;     // (all the samples at once: not kept)
+  const int32_t* src = lift_stage_rows(B.pl.map, g, perms, 0, n_samples, per, p, rows);
   HIPCHK(hipMemcpy(B.perms.ptr, src, sizeof(int32_t) * (size_t)(n_samples * rows_per * p), hipMemcpyHostToDevice));
   B.n_samples = n_samples;
   B.per = per;

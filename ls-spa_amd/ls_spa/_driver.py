@@ -1543,6 +1543,49 @@ def _cv_fold_values(problems, cols):
     return out
 
 
+def _sampled_arguments(p, groups, perms, method, max_samples, batch_size, seed, antithetical):
+    """What the sampled families' public functions do with ``groups``, ``perms``, ``method`` and the sample counts, in
+    this order: the labels (None without groups) and d, the dimension of a sample; perms and method refused together;
+    the counts positive; the ordering source in dimension d.
+    Returns (labels, d, source, batch_size, antithetical, max_samples, never_stop)."""
+    labels, d = None, p
+    if groups is not None:
+        labels, d = group_labels(groups, p, max_groups=None)
+    if perms is not None:
+        if method != "random":
+            raise ValueError("pass either perms= or method=, not both")
+        method = None
+    elif method not in S.METHODS:
+        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
+    if int(batch_size) < 1 or int(max_samples) < 1:
+        raise ValueError("batch_size and max_samples must be positive")
+    _, source, batch_size, antithetical, max_samples, never_stop = prepare_sampling(
+        d, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
+        antithetical=bool(antithetical), method=method)
+    return labels, d, source, batch_size, antithetical, max_samples, never_stop
+
+
+def _sample_until(source, batch, get, worst_error, batch_size, max_samples, tolerance):
+    """Draw batches of orderings from source through batch(rows) until max_samples, the source's end or -- with a
+    tolerance, from two samples on -- worst_error(state) <= tolerance.  Returns the state get() gives (n first), read
+    once per batch; no ordering at all is a ValueError."""
+    n, state = 0, None
+    while n < max_samples:
+        rows = source.take(min(batch_size, max_samples - n))
+        if len(rows) == 0:
+            break
+        batch(rows)
+        n += len(rows)
+        state = None
+        if tolerance is not None and n >= 2:
+            state = get()
+            if worst_error(state) <= tolerance:
+                break
+    if n == 0:
+        raise ValueError("no ordering to sample: perms is empty")
+    return state if state is not None else get()
+
+
 def ls_spa_cv_sampled(X, y, reg=0., folds=5, max_samples=2 ** 13, batch_size=2 ** 8, tolerance=None, seed=42,
                       perms=None, *, groups=None, method="random", antithetical=True, fold_seed=42, shuffle=True,
                       device=0, _engine=None):
@@ -1590,20 +1633,8 @@ def ls_spa_cv_sampled(X, y, reg=0., folds=5, max_samples=2 ** 13, batch_size=2 *
                          "rows must have a Cholesky factor")
     if not np.any(y):
         raise ValueError("y is identically zero: the cross-validated R^2 is not defined")
-    labels, d = None, p                # d: the dimension of a sample
-    if groups is not None:
-        labels, d = group_labels(groups, p, max_groups=None)
-    if perms is not None:
-        if method != "random":
-            raise ValueError("pass either perms= or method=, not both")
-        method = None
-    elif method not in S.METHODS:
-        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
-    if int(batch_size) < 1 or int(max_samples) < 1:
-        raise ValueError("batch_size and max_samples must be positive")
-    _, source, batch_size, antithetical, max_samples, never_stop = prepare_sampling(
-        d, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
-        antithetical=bool(antithetical), method=method)
+    labels, d, source, batch_size, antithetical, max_samples, never_stop = _sampled_arguments(
+        p, groups, perms, method, max_samples, batch_size, seed, antithetical)
     if never_stop:
         tolerance = None
     undo = [(lambda: _close_source(source), True)]
@@ -1612,21 +1643,9 @@ def ls_spa_cv_sampled(X, y, reg=0., folds=5, max_samples=2 ** 13, batch_size=2 *
         engine.cv_lift_load(X, y, ids, K, reg)
         if labels is not None:
             engine.cv_lift_set_players(labels)      # (cv_lift_free drops the map with everything else)
-        n, state = 0, None
-        while n < max_samples:
-            rows = source.take(min(batch_size, max_samples - n))
-            if len(rows) == 0:
-                break
-            engine.cv_lift_batch(rows, antithetical)
-            n += len(rows)
-            state = None
-            if tolerance is not None and n >= 2:
-                state = engine.cv_lift_get()      # the state is read once per batch
-                if _multi_standard_errors(state[0], state[2][K]).max() <= tolerance:
-                    break
-        if n == 0:
-            raise ValueError("no ordering to sample: perms is empty")
-        n, mean, m2 = state if state is not None else engine.cv_lift_get()
+        n, mean, m2 = _sample_until(source, lambda rows: engine.cv_lift_batch(rows, antithetical), engine.cv_lift_get,
+                                    lambda state: _multi_standard_errors(state[0], state[2][K]).max(), batch_size,
+                                    max_samples, tolerance)
         info = engine.cv_lift_info()
         problems = [engine.cv_lift_problem(f) for f in range(K)]
     r2_fold = _cv_fold_values(problems, np.arange(p))
@@ -2592,18 +2611,9 @@ def ls_spa_bootstrap_sampled(X_train, X_test, y_train, y_test, reg=0., n_boot=20
     n_boot, n_samples = int(n_boot), int(n_samples)
     if not np.any(data[3]):
         raise ValueError("y_test is identically zero: R^2 is not defined")
-    labels, d = None, p                # d: the dimension of a sample
-    if groups is not None:
-        labels, d = group_labels(groups, p, max_groups=None)
-    if perms is not None:
-        if method != "random":
-            raise ValueError("pass either perms= or method=, not both")
-        method = None
-    elif method not in S.METHODS:
-        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
-    _, source, _, antithetical, max_samples, _ = prepare_sampling(
-        d, max_samples=n_samples, batch_size=2 ** 8, seed=seed, perms=perms, antithetical=bool(antithetical),
-        method=method)
+    # (n_samples >= 2 and the batch size are this function's own: the helper's refusal of either cannot fire)
+    labels, d, source, _, antithetical, max_samples, _ = _sampled_arguments(
+        p, groups, perms, method, n_samples, 2 ** 8, seed, antithetical)
     w_train, w_test, sides = options
     fixed = [k for k, (name, w) in enumerate(zip(("train", "test"), (w_train, w_test))) if name not in sides and w is None]
     undo = [(lambda: _close_source(source), True)]
@@ -3066,20 +3076,8 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
     if p + m > MULTI_MAX_COLS:
         raise ValueError(f"ls_spa_multi_sampled takes p + m <= {MULTI_MAX_COLS} columns of [X | Y] (p = {p}, m = {m}); "
                          "cut the responses into several calls")
-    labels, d = None, p                # d: the dimension of a sample
-    if groups is not None:
-        labels, d = group_labels(groups, p, max_groups=None)
-    if perms is not None:
-        if method != "random":
-            raise ValueError("pass either perms= or method=, not both")
-        method = None
-    elif method not in S.METHODS:
-        raise ValueError(f"method must be one of {tuple(S.METHODS)}")
-    if int(batch_size) < 1 or int(max_samples) < 1:
-        raise ValueError("batch_size and max_samples must be positive")
-    _, source, batch_size, antithetical, max_samples, never_stop = prepare_sampling(
-        d, max_samples=int(max_samples), batch_size=int(batch_size), seed=seed, perms=perms,
-        antithetical=bool(antithetical), method=method)
+    labels, d, source, batch_size, antithetical, max_samples, never_stop = _sampled_arguments(
+        p, groups, perms, method, max_samples, batch_size, seed, antithetical)
     if never_stop:
         tolerance = None
     undo = [(lambda: _close_source(source), True)]
@@ -3088,21 +3086,9 @@ def ls_spa_multi_sampled(X_train, X_test, Y_train, Y_test, reg=0., max_samples=2
         engine.multi_lift_load(X_train, X_test, Y_train, Y_test, reg)
         if labels is not None:
             engine.multi_lift_set_players(labels)      # (multi_lift_free drops the map with everything else)
-        n, state = 0, None
-        while n < max_samples:
-            rows = source.take(min(batch_size, max_samples - n))
-            if len(rows) == 0:
-                break
-            engine.multi_lift_batch(rows, antithetical)
-            n += len(rows)
-            state = None
-            if tolerance is not None and n >= 2:
-                state = engine.multi_lift_get()      # the state is read once per batch
-                if _multi_standard_errors(state[0], state[2]).max() <= tolerance:
-                    break
-        if n == 0:
-            raise ValueError("no ordering to sample: perms is empty")
-        n, mean, m2 = state if state is not None else engine.multi_lift_get()
+        n, mean, m2 = _sample_until(source, lambda rows: engine.multi_lift_batch(rows, antithetical),
+                                    engine.multi_lift_get, lambda state: _multi_standard_errors(state[0], state[2]).max(),
+                                    batch_size, max_samples, tolerance)
         bits = engine.multi_lift_info()
         gram = engine.multi_lift_gram()
         theta, r_squared, singular = _multi_fit(*gram)

@@ -1147,6 +1147,29 @@ class HipEngine:
         self._check(self._lib.lsspa_perm_free(self._h))
         self._perm_dims = None
 
+    # ---- what the sampled families (fam: multi_lift, cv_lift, boot_lift) share: player map, sample dimension, perms ----
+    def _lift_players(self, fam, labels, g):
+        """lsspa_<fam>_set_players: labels (g: the largest + 1 unless given), or None and 0 to clear; remembers g."""
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            g = int(labels.max()) + 1 if g is None else int(g)
+        self._check(getattr(self._lib, f"lsspa_{fam}_set_players")(self._h, N.iptr(labels), g))
+        setattr(self, f"_{fam}_g", g)
+
+    def _lift_sd(self, fam, unloaded):
+        """(dimension of a sample: g with a player map, else p; the second of the family's dimensions)"""
+        dims = getattr(self, f"_{fam}_dims", None) or unloaded
+        return (getattr(self, f"_{fam}_g", 0) or dims[0]), dims[1]
+
+    def _lift_perms(self, fam, perms, rows="B"):
+        """(perms as int32, loaded): loaded, perms must be [rows][d]; before, the library says what comes first."""
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        loaded = getattr(self, f"_{fam}_dims", None) is not None
+        d = self._lift_sd(fam, (1, 0))[0]
+        if loaded and (perms.ndim != 2 or perms.shape[1] != d):
+            raise ValueError(f"perms must be [{rows}][{'g' if getattr(self, f'_{fam}_g', 0) else 'p'} = {d}]")
+        return perms, loaded
+
     # ---- sampled attribution of many responses on one design matrix (p <= 104) ----
     MULTI_LIFT_MAX_P = 104     # include/lsspa.h, LSSPA_MULTI_LIFT_MAX_P
 
@@ -1193,30 +1216,22 @@ class HipEngine:
         dims = getattr(self, "_multi_lift_dims", None)
         if dims is not None and len(labels) != dims[0]:
             raise ValueError(f"labels must have length p = {dims[0]}")
-        self._check(self._lib.lsspa_multi_lift_set_players(self._h, N.iptr(labels), g))
-        self._multi_lift_g = g
+        self._lift_players("multi_lift", labels, g)
 
     def multi_lift_clear_players(self):
-        self._check(self._lib.lsspa_multi_lift_set_players(self._h, None, 0))
-        self._multi_lift_g = 0
+        self._lift_players("multi_lift", None, 0)
 
     def _multi_lift_sd(self):
         """(dimension of a sample: g with a player map, else p; m)"""
-        p, m = getattr(self, "_multi_lift_dims", None) or (1, 1)
-        return (getattr(self, "_multi_lift_g", 0) or p), m
+        return self._lift_sd("multi_lift", (1, 1))
 
     def multi_lift_batch(self, perms, antithetical: bool, want_lifts: bool = False, accumulate: bool = True):
         """The lift vectors of every response for the orderings perms [B][p] (with antithetical a sample is the mean of
         an ordering and its reverse), folded into the running statistics if accumulate; lifts [B][m][p] if want_lifts
         (include/lsspa.h, lsspa_multi_lift_batch).  With a player map (multi_lift_set_players) perms is [B][g] and the
         lifts [B][m][g].  The library checks the orderings."""
-        dims = getattr(self, "_multi_lift_dims", None)
-        p, m = self._multi_lift_sd()
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if dims is None:                  # the library says what comes first
-            want_lifts = False
-        elif perms.ndim != 2 or perms.shape[1] != p:
-            raise ValueError(f"perms must be [B][{'g' if getattr(self, '_multi_lift_g', 0) else 'p'} = {p}]")
+        (p, m), (perms, loaded) = self._multi_lift_sd(), self._lift_perms("multi_lift", perms)
+        want_lifts = want_lifts and loaded
         out = np.empty((perms.shape[0], m, p)) if want_lifts else None
         self._check(self._lib.lsspa_multi_lift_batch(self._h, N.iptr(perms) if perms.size else None, perms.shape[0],
                                                      int(bool(antithetical)), N.dptr(out) if want_lifts else None,
@@ -1278,32 +1293,22 @@ class HipEngine:
         """Groups of columns as the players of cv_lift_batch, as multi_lift_set_players names them (include/lsspa.h,
         lsspa_cv_lift_set_players): perms are then [B][g], the lifts and the statistics in dimension g.  The library
         checks the labels."""
-        labels = np.ascontiguousarray(labels, dtype=np.int32)
-        g = int(labels.max()) + 1 if g is None else int(g)
-        self._check(self._lib.lsspa_cv_lift_set_players(self._h, N.iptr(labels), g))
-        self._cv_lift_g = g
+        self._lift_players("cv_lift", np.asarray(labels), g)
 
     def cv_lift_clear_players(self):
-        self._check(self._lib.lsspa_cv_lift_set_players(self._h, None, 0))
-        self._cv_lift_g = 0
+        self._lift_players("cv_lift", None, 0)
 
     def _cv_lift_sd(self):
         """(dimension of a sample: g with a player map, else p; K)"""
-        p, K = getattr(self, "_cv_lift_dims", None) or (1, 2)
-        return (getattr(self, "_cv_lift_g", 0) or p), K
+        return self._lift_sd("cv_lift", (1, 2))
 
     def cv_lift_batch(self, perms, antithetical: bool, want_lifts: bool = False, accumulate: bool = True):
         """One ordering through the K fold problems, for every row of perms [B][d] (with antithetical a sample is an
         ordering and its reverse), folded into the running statistics if accumulate; with want_lifts
         (fold_lifts [B][K][d], lifts [B][d]), the folds' lift vectors and their ascending sum (include/lsspa.h,
         lsspa_cv_lift_batch).  The library checks the orderings."""
-        dims = getattr(self, "_cv_lift_dims", None)
-        d, K = self._cv_lift_sd()
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if dims is None:                  # the library says what comes first
-            want_lifts = False
-        elif perms.ndim != 2 or perms.shape[1] != d:
-            raise ValueError(f"perms must be [B][{'g' if getattr(self, '_cv_lift_g', 0) else 'p'} = {d}]")
+        (d, K), (perms, loaded) = self._cv_lift_sd(), self._lift_perms("cv_lift", perms)
+        want_lifts = want_lifts and loaded
         B = perms.shape[0] if perms.ndim == 2 else 0
         fold = np.empty((B, K, d)) if want_lifts else None
         tot = np.empty((B, d)) if want_lifts else None
@@ -1369,27 +1374,21 @@ class HipEngine:
     def boot_lift_set_players(self, labels, g=None):
         """Groups of columns as the players, as cv_lift_set_players names them (include/lsspa.h,
         lsspa_boot_lift_set_players); drops the orderings.  The library checks the labels."""
-        labels = np.ascontiguousarray(labels, dtype=np.int32)
-        g = int(labels.max()) + 1 if g is None else int(g)
-        self._check(self._lib.lsspa_boot_lift_set_players(self._h, N.iptr(labels), g))
-        self._boot_lift_g, self._boot_lift_n = g, 0
+        self._lift_players("boot_lift", np.asarray(labels), g)
+        self._boot_lift_n = 0
 
     def boot_lift_clear_players(self):
-        self._check(self._lib.lsspa_boot_lift_set_players(self._h, None, 0))
-        self._boot_lift_g, self._boot_lift_n = 0, 0
+        self._lift_players("boot_lift", None, 0)
+        self._boot_lift_n = 0
 
     def _boot_lift_sd(self):
         """(dimension of a sample: g with a player map, else p; samples of the orderings set)"""
-        p = (getattr(self, "_boot_lift_dims", None) or (1, 0, 0))[0]
-        return (getattr(self, "_boot_lift_g", 0) or p), getattr(self, "_boot_lift_n", 0)
+        return self._lift_sd("boot_lift", (1, 0))[0], getattr(self, "_boot_lift_n", 0)
 
     def boot_lift_set_orderings(self, perms, antithetical: bool):
         """The one set of orderings every replicate and the point problem run through: perms [n_samples][d] (with
         antithetical a sample is an ordering and its reverse).  The library checks the orderings."""
-        d, _ = self._boot_lift_sd()
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if getattr(self, "_boot_lift_dims", None) is not None and (perms.ndim != 2 or perms.shape[1] != d):
-            raise ValueError(f"perms must be [n_samples][{'g' if getattr(self, '_boot_lift_g', 0) else 'p'} = {d}]")
+        perms, _ = self._lift_perms("boot_lift", perms, "n_samples")
         B = perms.shape[0] if perms.ndim == 2 else 0
         self._check(self._lib.lsspa_boot_lift_set_orderings(self._h, N.iptr(perms) if perms.size else None, B,
                                                             int(bool(antithetical))))
